@@ -14,9 +14,16 @@ Multi-GPU: the exact path does not shard without a panel exchange every 128 colu
 --gpus N runs N independent replicas (one process per GPU, no data-path collective, weak scaling); ranks only
 meet at the barriers that bracket the timed region and for the MAX-over-ranks of the elapsed time.
 
-Prints ONE JSON line on rank 0 (see README / DESIGN.md for the field definitions).  Besides the headline (configs[2]) the
-line carries one sub-record per other GPU configuration of BASELINE.json, each measured by a CHILD process with a timeout
-(a fault there cannot take the headline down) and each with its own parity block against the committed golden fixture:
+Prints ONE JSON line on rank 0 (see README / DESIGN.md for the field definitions).  A plain run does only what the headline
+needs: set-up, the W warm-up steps, the K timed steps, --dump-outputs DIR if given (what the last timed step computed, as
+DIR/<name>.npy), and the line (metric, value, unit, higher_is_better, dtype, ms_per_step, config, lml).
+
+    python bench.py --gpus 1 --steps 20 --warmup 3 --full
+
+adds everything else: the parity gate before the timed region, the stage breakdown, per-kernel / roofline figures, the bare
+C-ABI and standalone-Cholesky timings, the golden check of the timed configuration, and one sub-record per other GPU
+configuration of BASELINE.json, each measured by a CHILD process with a timeout (a fault there cannot take the headline
+down) and each with its own parity block against the committed golden fixture:
     "c2"             configs[1]  RBF N=4096 D=8 (one GPU; roofline + cpu_baseline)
     "grid"           configs[3]  RBF N=32768 D=8 on the 2D block-cyclic grid: 2x4 LOGICAL ranks over the loopback transport
                                  when the launch has one GPU (the real block-cyclic code, all ranks time-sharing the device),
@@ -25,8 +32,9 @@ line carries one sub-record per other GPU configuration of BASELINE.json, each m
                                  its dominant MFMA GEMM + cpu_baseline from the sparse oracle)
     "c4_single"      configs[3]'s problem (RBF N=32768 D=8) on the dedicated SINGLE-GPU path (rank 0's GPU): the N = 1 anchor
                                  of the strong-scaling series, parity against the N=32768 golden
-Every `cpu_baseline` of the line is measured on rank 0 AFTER the GPU legs have ended, one after the other (nothing else of the
-run on the host): the headline configuration DIRECTLY at N=16384, configs[1] directly at N=4096, the sparse oracle at two sizes.
+Every `cpu_baseline` of a --full line is measured on rank 0 AFTER the GPU legs have ended, one after the other (nothing else of
+the run on the host): the headline configuration DIRECTLY at N=16384, configs[1] directly at N=4096, the sparse oracle at two
+sizes.
 """
 import argparse
 import json
@@ -141,6 +149,14 @@ def timed_region(comm, step_fn, steps, warmup, per_step=None):
     comm.barrier()
     dt = time.perf_counter() - t0
     return comm.max_over_ranks(dt)
+
+
+def dump_outputs(directory, arrays):
+    """--dump-outputs: what the timed path handed its caller in the last timed step, one DIR/<name>.npy per array (float64).
+    The inputs are seeded, so two builds run with the same arguments can be compared output for output."""
+    os.makedirs(directory, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(directory, name + ".npy"), np.array(a, dtype=np.float64, ndmin=1))
 
 
 def _cpu_threads():
@@ -397,7 +413,7 @@ C2_KEEP = ("ms_per_step", "step_ms", "value", "unit", "steps", "warmup", "config
 def c2_leg(comm, args):
     """BASELINE configs[1]: RBF iso, N=4096, D=8 on ONE GPU (rank 0's), through the drop-in classes."""
     steps = ["--steps", "20", "--warmup", "5"] if args.dry_run_sizes else ["--steps", "300", "--warmup", "20"]
-    rec = run_child(["--n", "4096", "--d", "8", "--kind", "rbf", "--iso"] + steps + ["--no-legs",
+    rec = run_child(["--n", "4096", "--d", "8", "--kind", "rbf", "--iso"] + steps + ["--full", "--no-legs",
                      "--device", str(comm.local_rank), "--no-cpu-baseline"], timeout=240.0)
     return {k: rec[k] for k in C2_KEEP if k in rec}
 
@@ -406,8 +422,8 @@ def c4_single_leg(comm, args):
     """BASELINE configs[3]'s problem (RBF iso, N=32768, D=8) on the DEDICATED single-GPU path: the N = 1 anchor of the
     strong-scaling series north_star asks for (N in {4k, 16k, 32k} at 1/2/4/8 GPUs), next to `grid` (the same problem on the
     block-cyclic code).  26 GB resident; parity against the N=32768 golden."""
-    rec = run_child(["--n", str(args.grid_n), "--d", "8", "--kind", "rbf", "--iso", "--steps", "4", "--warmup", "2", "--no-legs",
-                     "--device", str(comm.local_rank), "--no-cpu-baseline"], timeout=420.0)
+    rec = run_child(["--n", str(args.grid_n), "--d", "8", "--kind", "rbf", "--iso", "--steps", "4", "--warmup", "2", "--full",
+                     "--no-legs", "--device", str(comm.local_rank), "--no-cpu-baseline"], timeout=420.0)
     return {k: rec[k] for k in C2_KEEP if k in rec}
 
 
@@ -559,7 +575,14 @@ def main():
     ap.add_argument("--sparse", action="store_true", help="BASELINE configs[4]: SparseGPRegression (VarDTC) N=200000 "
                     "rows per GPU, M=2048, D=16; rows sharded across GPUs with one RCCL all-reduce per pass")
     ap.add_argument("--m", "--inducing", dest="m", type=int, default=2048, help="inducing points (--sparse)")
+    ap.add_argument("--full", action="store_true", help="everything besides the headline: parity gate, golden check, stage "
+                    "breakdown, roofline / per-kernel figures, C-ABI and standalone-Cholesky timings, the c2 / grid / c5 / "
+                    "c4_single legs and the CPU baselines")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="", help="write what the last timed step computed as "
+                    "DIR/<name>.npy (float64); the replica path only, not --grid / --sparse")
     args = ap.parse_args()
+    if args.dump_outputs and (args.grid or args.sparse):
+        ap.error("--dump-outputs covers the replica path only, not --grid / --sparse")
     if args.grid:
         return main_grid(args)
     if args.sparse:
@@ -569,6 +592,9 @@ def main():
     assert comm.world == max(1, args.gpus) or comm.world == 1, "launch with torch.distributed.run for --gpus > 1"
     if args.device >= 0 and comm.world == 1:
         comm.local_rank = args.device
+    if not args.full:
+        # a plain run: set-up, warm-up, the timed steps, --dump-outputs, the line; every other measurement or check is --full
+        args.no_legs = args.no_parity_gate = args.no_cpu_baseline = True
     if args.no_legs:
         args.no_grid_leg = True
     import gpy_amd
@@ -607,6 +633,25 @@ def main():
     out = None
     if comm.rank == 0:
         lml = last["r"]["lml"] if args.abi_only else last["lml"]
+        if args.dump_outputs:
+            if args.abi_only:
+                outputs = {"lml": last["r"]["lml"], "dtheta": last["r"]["dtheta"], "dnoise": last["r"]["dnoise"]}
+            else:
+                outputs = {"lml": last["lml"], "gradient": last["grad"], "woodbury_vector": m.posterior.woodbury_vector}
+            dump_outputs(args.dump_outputs, outputs)
+        out = {
+            "metric": "exact-GP log_lik+grad iters/sec", "value": its, "unit": "iters/s",
+            "n_gpus": n_gpus, "steps": args.steps, "warmup": args.warmup, "ms_per_step": 1e3 * dt / args.steps,
+            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f64", "data": "synthetic",
+            "config": {"workload": "BASELINE configs[2]: %s %s exact GP, one GPRegression.parameters_changed, N=%d D=%d Dy=1 per GPU" % (
+                           args.kind, "ARD" if ARD else "iso", N, D),
+                       "N": N, "D": D, "kernel": args.kind, "ARD": ARD, "parallelism": "replicas x%d" % n_gpus,
+                       "path": "C-ABI" if args.abi_only else "drop-in classes"},
+            "lml": lml,
+        }
+        if per_step:
+            out["step_ms"] = per_step
+    if comm.rank == 0 and args.full:
         # stage breakdown: one more evaluation with the stage events recorded (the timed steps run without them; below the
         # overlapped-inverse threshold they replay the factorisation from a hipGraph, which carries no timing events)
         step_abi(want_stage_ms=True)
@@ -655,14 +700,7 @@ def main():
         elif (N, D, args.kind) == (4096, 8, "rbf"):
             traffic, traffic_source = profiled_c2_traffic("k_potrf_persist" if pf.get("update_nt", (0, 0, 0))[2] == 0 else "k_update_nt<")
         traffic_source = ("profiles/%s" % traffic_source) if traffic_source else None
-        out = {
-            "metric": "exact-GP log_lik+grad iters/sec", "value": its, "unit": "iters/s",
-            "n_gpus": n_gpus, "steps": args.steps, "warmup": args.warmup, "ms_per_step": 1e3 * dt / args.steps,
-            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f64", "data": "synthetic",
-            "config": {"workload": "BASELINE configs[2]: %s %s exact GP, one GPRegression.parameters_changed, N=%d D=%d Dy=1 per GPU" % (
-                           args.kind, "ARD" if ARD else "iso", N, D),
-                       "N": N, "D": D, "kernel": args.kind, "ARD": ARD, "parallelism": "replicas x%d" % n_gpus,
-                       "path": "C-ABI" if args.abi_only else "drop-in classes"},
+        out.update({
             # "cholesky_gflops" (the metric's Cholesky GF/s, filled in below) is the factorisation timed ALONE on a resident
             # matrix; the pipeline's potrf stage also hosts the overlapped inverse kernels and is only reported as stage_ms
             # N^3 flops over the WALL CLOCK of a timed step; the device-side stage sum of one evaluation under its own name
@@ -687,10 +725,7 @@ def main():
                                  "frac": (pf["lauum"][1] / (pf["lauum"][0] * 1e-3) / 1e12 / PEAK_FP64_TFLOPS)
                                  if pf["lauum"][0] > 0 else 0.0},
             "families": families,
-            "lml": lml,
-        }
-        if per_step:
-            out["step_ms"] = per_step
+        })
         out["persist_aborts"] = {"timed_steps": aborts_timed, "profile_steps": ctx.get_option("persist_aborts") - aborts_timed}
         if N <= 128 * 36:
             # which schedule of a small factorisation the context's own timing settled on (boxes differ by 2x on the persistent
@@ -777,7 +812,7 @@ def main():
                     out["c5"]["cpu_baseline"] = timed_baseline(lambda: sparse_cpu_baseline(16, args.m, 200000))
         if args.dry_run_sizes:
             out["dry_run_sizes"] = True
-        print(compact_line(out), flush=True)
+        print(compact_line(out) if args.full else json.dumps(_slim(out, ()), separators=(",", ":")), flush=True)
     comm.close()
 
 

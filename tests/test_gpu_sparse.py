@@ -299,6 +299,7 @@ import numpy as np
 from gpy_amd import _lib as L, grid as G
 from oracle import gp_oracle as O, sparse_oracle as S
 rank, world = int(os.environ["RANK"]), int(os.environ["WORLD_SIZE"])
+dev = rank %% L.device_count()                   # one GPU: both ranks on device 0 over the hipIpc transport
 idb = G.unique_id() if rank == 0 else b"\0" * G.ID_BYTES
 idb = G.exchange_id_file(idb, rank, %(idfile)r, world=world)
 if %(mode)r == "sparse":
@@ -306,14 +307,14 @@ if %(mode)r == "sparse":
     X, Y = O.synthetic(N, D, seed=5); Z = S.synthetic_Z(X, M, 0)
     var, ls, noise = O.default_theta(D, True)
     lo, hi = G.shard_rows(N, rank, world)
-    c = L.SparseContext(rank); c.attach_comm(rank, world, idb); c.set_data(X[lo:hi], Y[lo:hi])
+    c = L.SparseContext(dev); c.attach_comm(rank, world, idb); c.set_data(X[lo:hi], Y[lo:hi])
     info, r = c.vardtc("rbf", True, L.theta_vec(var, ls, True, D), Z, noise)
     res = dict(info=info, lml=r["lml"], dtheta=r["dtheta"].tolist(), dZn=float(np.linalg.norm(r["dZ"])))
 else:
     N, D = 6000, 5
     X, Y = O.synthetic(N, D, seed=3)
     var, ls, noise = O.default_theta(D, True)
-    g = G.GridContext(rank, rank, world, 1, 2, 256, idb); g.set_data(X, Y)
+    g = G.GridContext(dev, rank, world, 1, 2, 256, idb); g.set_data(X, Y)
     info, r = g.exact_inference("matern52", True, L.theta_vec(var, ls, True, D), noise)
     res = dict(info=info, lml=r["lml"], dtheta=r["dtheta"].tolist(), an=float(np.linalg.norm(r["alpha"])))
 json.dump(res, open(%(out)r %% rank, "w"))
@@ -321,21 +322,21 @@ json.dump(res, open(%(out)r %% rank, "w"))
 
 
 @pytest.mark.parametrize("mode", ["grid", "sparse"])
-def test_two_process_rccl_over_xgmi(mode, tmp_path):
+def test_two_process_collectives_rccl_or_ipc(mode, tmp_path):
     """e1 / e2 with TWO processes on TWO GPUs over RCCL (panel broadcasts of the 1 x 2 block-cyclic grid; the all-reduces of
-    the row-sharded sparse path).  Skips on a single-GPU box; the loopback transports cover the same logic there."""
+    the row-sharded sparse path).  With one GPU, where RCCL refuses two ranks on one device, the same two processes share
+    device 0 over the hipIpc transport that stands in for RCCL there (MI355GP_TRANSPORT=ipc); the checks are the same."""
     import json
     import os
     import subprocess
     import sys
+    env = dict(os.environ, WORLD_SIZE="2", HSA_ENABLE_IPC_MODE_LEGACY="0")
     if L.device_count() < 2:
-        pytest.skip("needs two GPUs")
+        env.update(MI355GP_TRANSPORT="ipc", MI355GP_JOB_NONCE="x%d" % os.getpid(), MI355GP_IPC_TIMEOUT_S="240")
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     script = tmp_path / "w.py"
     script.write_text(_RCCL_WORKER % dict(root=root, idfile=str(tmp_path / "id.bin"), mode=mode, out=str(tmp_path / "r%d.json")))
-    procs = [subprocess.Popen([sys.executable, str(script)], env=dict(os.environ, RANK=str(r), WORLD_SIZE="2",
-                                                                     HSA_ENABLE_IPC_MODE_LEGACY="0"))
-             for r in range(2)]
+    procs = [subprocess.Popen([sys.executable, str(script)], env=dict(env, RANK=str(r))) for r in range(2)]
     for p in procs:
         assert p.wait(timeout=300) == 0
     res = [json.load(open(tmp_path / ("r%d.json" % r))) for r in range(2)]

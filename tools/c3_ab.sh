@@ -8,8 +8,8 @@ export TMPDIR=/tmp
 EXTRA=""; [ "${1:-}" = abi ] && EXTRA="--abi-only --no-parity-gate"
 for rep in 1 2 3; do
 for t in r3 r4 HEAD; do
-    d=.ab/$t; [ $t = HEAD ] && d=.
-    ( cd $d && timeout 200 python bench.py --steps 20 --warmup 5 --no-legs --no-cpu-baseline $EXTRA 2>/dev/null ) | python -c "
+    d=.ab/$t; F=""; [ $t = HEAD ] && d=. && F=--full      # older trees have no --full: their plain run is the full one
+    ( cd $d && timeout 200 python bench.py --steps 20 --warmup 5 $F --no-legs --no-cpu-baseline $EXTRA 2>/dev/null ) | python -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1])
 print('$t run $rep: ms_per_step %.3f  stage total %.3f  potrf %.2f trtri %.2f lauum %.2f grad %.2f  host_path %s' % (d['ms_per_step'], d['stage_ms']['total'], d['stage_ms']['potrf'], d['stage_ms']['trtri'], d['stage_ms']['lauum'], d['stage_ms']['grad'], {k: round(v, 3) for k, v in (d.get('host_path') or {}).items() if isinstance(v, float)}))"

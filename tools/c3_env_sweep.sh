@@ -5,7 +5,7 @@
 export MI355GP_LIB=${MI355GP_LIB:-$PWD/gpy_amd/libmi355gp_diag.so}
 export TMPDIR=/tmp
 run() {
-    ( env $1 timeout 200 python bench.py --steps 20 --warmup 5 --no-legs --no-cpu-baseline --abi-only --no-parity-gate 2>/dev/null ) | python -c "
+    ( env $1 timeout 200 python bench.py --steps 20 --warmup 5 --full --no-legs --no-cpu-baseline --abi-only --no-parity-gate 2>/dev/null ) | python -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1])
 s=d['stage_ms']

@@ -3,7 +3,7 @@
 start / end relative to the first, its queue and its grid -- where the exposed tails of a small evaluation (trtri after the
 persistent Cholesky, X^T X, the solves on the side stream) really sit.
 
-    rocprofv3 --output-format csv --kernel-trace -d OUT -o run -- python bench.py --n 4096 --d 8 --kind rbf --iso --steps 6 ...
+    rocprofv3 --output-format csv --kernel-trace -d OUT -o run -- python bench.py --n 4096 --d 8 --kind rbf --iso --steps 6 --full ...
     python tools/eval_timeline.py OUT/.../run_kernel_trace.csv [evaluation index from the end, default 2]
 """
 import csv

@@ -1,11 +1,11 @@
 #!/bin/bash
-# full GPU suite + the default bench exactly as the driver runs it (headline + c2 / grid / c5 legs)
+# full GPU suite + bench.py --full (headline + c2 / grid / c5 legs + CPU baselines)
 export TMPDIR=/tmp
 O=gpurun_out/${1:-r3a}
 mkdir -p $O
 ( time timeout 1200 python -m pytest tests -m gpu -q --maxfail=10 -x ) > $O/pytest.log 2>&1
 grep -E "passed|failed|error" $O/pytest.log | tail -3
-( time timeout 900 python bench.py > $O/bench.json 2>> $O/bench.err ) 2> $O/bench_time.log
+( time timeout 900 python bench.py --full > $O/bench.json 2>> $O/bench.err ) 2> $O/bench_time.log
 tail -4 $O/bench_time.log
 python - $O <<'PY'
 import json, sys

@@ -15,9 +15,9 @@ export MI355GP_IPC_TIMEOUT_S=${MI355GP_IPC_TIMEOUT_S:-120}
 PORT=$((29600 + RANDOM % 300))
 mkdir -p gpurun_out
 if [ "$MODE" = full ]; then
-    ARGS="--gpus $N --steps 3 --warmup 1"
+    ARGS="--gpus $N --steps 3 --warmup 1 --full"
 else
-    ARGS="--gpus $N --steps 2 --warmup 1 --size 4096 --dims 8 --kind rbf --iso --grid-n 8192 --dry-run-sizes"
+    ARGS="--gpus $N --steps 2 --warmup 1 --full --size 4096 --dims 8 --kind rbf --iso --grid-n 8192 --dry-run-sizes"
 fi
 echo "== default bench line with $N ranks on one GPU ($MODE legs)"
 python -m torch.distributed.run --nnodes=1 --nproc-per-node "$N" --master-addr 127.0.0.1 --master-port "$PORT" \

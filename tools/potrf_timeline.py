@@ -1,5 +1,5 @@
 """Per-outer-step timeline of the look-ahead Cholesky from a rocprofv3 kernel trace ("Where potrf's
-time goes"):   rocprofv3 --output-format csv --kernel-trace -d OUT -o run -- python bench.py --steps 2 --warmup 1
+time goes"):   rocprofv3 --output-format csv --kernel-trace -d OUT -o run -- python bench.py --steps 2 --warmup 1 --full
                   python tools/potrf_timeline.py OUT/run_kernel_trace.csv
 For every outer step: duration of part 1 / part 2 of the trailing update, span of the panel chain on the other stream
 (with the k_diag128 durations), how long the chain outlasts part 2, and the step time."""

@@ -11,10 +11,10 @@ run() {   # run <subdir> <rocprof args...> -- <cmd...>
     local sub=$1; shift
     timeout -k 5 150 rocprofv3 --output-format csv --kernel-trace "$@" > $OUT/$sub.log 2>&1 || echo "$sub: rc $?"
 }
-C3="python $PWD/bench.py --steps 5 --warmup 1 --no-cpu-baseline --no-legs --no-parity-gate --abi-only"
-C3ONE="python $PWD/bench.py --steps 1 --warmup 1 --no-cpu-baseline --no-legs --no-parity-gate --abi-only"
-C2="python $PWD/bench.py --n 4096 --d 8 --kind rbf --iso --steps 20 --warmup 3 --no-cpu-baseline --no-legs --no-parity-gate --abi-only"
-C2ONE="python $PWD/bench.py --n 4096 --d 8 --kind rbf --iso --steps 2 --warmup 3 --no-cpu-baseline --no-legs --no-parity-gate --abi-only"
+C3="python $PWD/bench.py --steps 5 --warmup 1 --full --no-cpu-baseline --no-legs --no-parity-gate --abi-only"
+C3ONE="python $PWD/bench.py --steps 1 --warmup 1 --full --no-cpu-baseline --no-legs --no-parity-gate --abi-only"
+C2="python $PWD/bench.py --n 4096 --d 8 --kind rbf --iso --steps 20 --warmup 3 --full --no-cpu-baseline --no-legs --no-parity-gate --abi-only"
+C2ONE="python $PWD/bench.py --n 4096 --d 8 --kind rbf --iso --steps 2 --warmup 3 --full --no-cpu-baseline --no-legs --no-parity-gate --abi-only"
 C5="python $PWD/bench.py --sparse --steps 3 --warmup 1 --no-cpu-baseline"
 C5ONE="python $PWD/bench.py --sparse --steps 1 --warmup 1 --no-cpu-baseline"
 # PROFILE_SET=mini: the three kernel-stats runs and the SQ counter pass of the headline only

@@ -5,7 +5,7 @@
 # 1  transport self-test over RCCL, 2 ranks (1x2): ncclCommInitRank, ncclCommSplit colour / key numbering, several ncclBroadcasts
 #    with different roots inside ONE ncclGroupStart / End, out-of-place broadcast on the root, all-reduces (mi355gp_dbg_comm_selftest)
 # 2  the same on the full grid shape of the node (2x2 / 2x4)
-# 3  the two GPU tests that need two devices (skipped on the 1-GPU boxes): tests/test_gpu_sparse.py::test_two_process_rccl_over_xgmi[grid|sparse]
+# 3  the two GPU tests that use RCCL with two devices (over the hipIpc stand-in with one): tests/test_gpu_sparse.py::test_two_process_collectives_rccl_or_ipc[grid|sparse]
 # 4  1x2 and 2x2 block-cyclic grids at N=4096 over RCCL with the collective-sequence check on, against the loopback bits
 # 5  the 2-way row-sharded VarDTC over RCCL against the unsharded run
 # 6  bench.py --gpus N (replicas + the grid / c5 legs over all ranks) and bench.py --grid PrxPc --gpus N
@@ -40,7 +40,7 @@ assert bad == 0 and (rrow, rcol) == ($r % $Pc, $r // $Pc)" &
 export -f selftest
 step 1_selftest_1x2 120 bash -c "selftest 1 2"
 step 2_selftest_$SHAPE 180 bash -c "selftest ${SHAPE%x*} ${SHAPE#*x}"
-step 3_two_gpu_tests 600 python -m pytest tests/test_gpu_sparse.py tests/test_gpu_grid.py -m gpu -q -k "two_process_rccl_over_xgmi or rccl_transport" -x
+step 3_two_gpu_tests 600 python -m pytest tests/test_gpu_sparse.py tests/test_gpu_grid.py -m gpu -q -k "two_process_collectives_rccl_or_ipc or rccl_transport" -x
 for shape in 1x2 2x2; do
     w=$(( ${shape%x*} * ${shape#*x} ))
     [ "$w" -le "$NG" ] || continue
@@ -50,7 +50,7 @@ done
 step 5_sparse_2way 300 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port $((PORT + 20)) \
     bench.py --sparse --gpus 2 --size 40000 --inducing 512 --steps 2 --warmup 1 --no-cpu-baseline
 step 6_bench_gpus_$W 1500 python -m torch.distributed.run --nnodes=1 --nproc-per-node $W --master-addr 127.0.0.1 --master-port $((PORT + 40)) \
-    bench.py --gpus $W --steps 10 --warmup 3
+    bench.py --gpus $W --steps 10 --warmup 3 --full
 step 6_bench_grid_$SHAPE 900 python -m torch.distributed.run --nnodes=1 --nproc-per-node $W --master-addr 127.0.0.1 --master-port $((PORT + 60)) \
     bench.py --grid $SHAPE --gpus $W --size 32768 --dims 8 --kind rbf --iso --steps 3 --warmup 1
 grep -h "^{" $O/6_bench_*.log | cut -c1-600

@@ -14,7 +14,7 @@ for T in 0 4 0 4; do
 done
 MI355GP_PERSIST_TUNE=0 timeout -k 5 60 python tools/persist_probe.py 4096 2>&1 | grep "^   step"
 for T in 0 4 0 4; do
-  MI355GP_PERSIST_TUNE=$T timeout -k 5 120 python bench.py --n 4096 --d 8 --kind rbf --iso --steps 300 --warmup 20 --no-legs --no-cpu-baseline \
+  MI355GP_PERSIST_TUNE=$T timeout -k 5 120 python bench.py --n 4096 --d 8 --kind rbf --iso --steps 300 --warmup 20 --full --no-legs --no-cpu-baseline \
     > "$OUT/c2_t$T.json" 2> "$OUT/c2_t$T.err"
   python - "$OUT/c2_t$T.json" $T <<'PY'
 import json, sys
