@@ -15,7 +15,12 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("MI355GP_LIB") or os.path.join(_HERE, "libmi355gp.so")
 CSRC = os.path.join(_HERE, "csrc")
 
-KIND_IDS = {"rbf": 0, "matern52": 1, "matern32": 2, "exponential": 3, "white": 4, "bias": 5}
+KIND_IDS = {"rbf": 0, "matern52": 1, "matern32": 2, "exponential": 3, "white": 4, "bias": 5, "ratquad": 6, "stdperiodic": 7}
+
+
+def ard_id(kind, ARD):
+    """`ard` of the C-ABI: a flag, or for StdPeriodic the bitmask ARD1 | ARD2 << 1"""
+    return int(ARD) & 3 if kind == "stdperiodic" else int(bool(ARD))
 
 
 class Part(ctypes.Structure):
@@ -36,7 +41,7 @@ def make_parts(specs):
         th = np.ascontiguousarray(theta, dtype=np.float64)
         keep.append(th)
         arr[i].kind = KIND_IDS[kind]
-        arr[i].ard = int(bool(ARD))
+        arr[i].ard = ard_id(kind, ARD)
         arr[i].theta = th.ctypes.data_as(ctypes.POINTER(ctypes.c_double))
         if dims is None:
             arr[i].n_active = 0
@@ -296,7 +301,7 @@ class Context(object):
         dtheta = np.zeros(theta.size)
         diag = np.empty(self.N) if want_diag else None
         ms = np.zeros(NUM_T) if want_stage_ms else None
-        rc = check(lib().mi355gp_exact_inference(self._h, KIND_IDS[kind], int(bool(ARD)), theta, noise, noise.size,
+        rc = check(lib().mi355gp_exact_inference(self._h, KIND_IDS[kind], ard_id(kind, ARD), theta, noise, noise.size,
                                                  jitter, extra_jitter, out, _opt(alpha), _opt(dtheta), _opt(diag),
                                                  _opt(ms)), "mi355gp_exact_inference")
         res = dict(lml=out[OUT_LML], logdet=out[OUT_LOGDET], datafit=out[OUT_DATAFIT], dnoise=out[OUT_DNOISE],
@@ -410,7 +415,7 @@ class Context(object):
         assert Xnew.shape[1] == self.D
         mu = np.empty((M, self.Dy))
         var = (np.empty((M, M)) if full_cov else np.empty(M)) if want_var else None
-        check(lib().mi355gp_predict(self._h, KIND_IDS[kind], int(bool(ARD)), f64(theta), Xnew, M,
+        check(lib().mi355gp_predict(self._h, KIND_IDS[kind], ard_id(kind, ARD), f64(theta), Xnew, M,
                                     mu.ctypes.data_as(_c_dp), _opt(var), int(bool(full_cov))), "mi355gp_predict")
         if var is not None and not full_cov:
             var = var[:, None]
@@ -546,7 +551,7 @@ def kern_K(kind, ARD, theta, X, X2=None, device=0):
         M, p2 = X2.shape[0], X2.ctypes.data_as(_c_dp)
         assert X2.shape[1] == D
     out = np.empty((N, M))
-    check(lib().mi355gp_kern_K(device, KIND_IDS[kind], int(bool(ARD)), f64(theta), X, N, p2, M, D, out),
+    check(lib().mi355gp_kern_K(device, KIND_IDS[kind], ard_id(kind, ARD), f64(theta), X, N, p2, M, D, out),
           "mi355gp_kern_K")
     return out
 
@@ -570,7 +575,7 @@ def update_gradients_full(kind, ARD, theta, dL_dK, X, X2=None, device=0):
     assert G.shape == (N, M), "dL_dK must be N x M"
     theta = f64(theta)
     out = np.zeros(theta.size)
-    check(lib().mi355gp_update_gradients_full(device, KIND_IDS[kind], int(bool(ARD)), theta, G, X, N, p2, M, D, out),
+    check(lib().mi355gp_update_gradients_full(device, KIND_IDS[kind], ard_id(kind, ARD), theta, G, X, N, p2, M, D, out),
           "mi355gp_update_gradients_full")
     return out
 
@@ -588,7 +593,7 @@ def gradients_X(kind, ARD, theta, dL_dK, X, X2=None, device=0):
     G = f64(dL_dK)
     assert G.shape == (N, M), "dL_dK must be N x M"
     out = np.zeros((N, D))
-    check(lib().mi355gp_gradients_X(device, KIND_IDS[kind], int(bool(ARD)), f64(theta), G, X, N, p2, M, D, out),
+    check(lib().mi355gp_gradients_X(device, KIND_IDS[kind], ard_id(kind, ARD), f64(theta), G, X, N, p2, M, D, out),
           "mi355gp_gradients_X")
     return out
 

@@ -74,7 +74,11 @@ struct mi355gp_ctx {
         std::vector<double> theta;      // [variance, lengthscale(s)]  (static kinds: [variance])
         std::vector<int> dims;          // active input dimensions (kern.py:49-53), indices into the D columns of X
         std::vector<double> inv_ls;     // length D: 1/l on active dimensions, 0 elsewhere (= the slicing of kern.py:112-117)
+                                        // (StdPeriodic: 1 on active dimensions -- its inputs stay unscaled)
         double* dXt = nullptr;          // D x npad scaled, dimension-major inputs of this part
+        int ard_in = 0;                 // the `ard` of the C-ABI part (StdPeriodic: the ARD1 | ARD2 bitmask)
+        std::vector<double> pw;         // StdPeriodic: [pi / T_q (D) | 1 / l_q (D)], uploaded to dPw (KernParams::pw)
+        double* dPw = nullptr;
         int term = 0;                   // parts with the same term id are multiplied (GPy/kern/src/prod.py), terms are summed
     };
     std::vector<Part> parts;
@@ -82,7 +86,8 @@ struct mi355gp_ctx {
     double* Mbuf = nullptr;             // npad x npad product of the OTHER factors of a term (allocated on first product kernel)
     // Everything an evaluation returns -- scalars, info, per-part gradient sums, alpha, diag(dL_dK) -- lives in ONE device
     // block and travels in ONE copy into ONE pinned host block (five small pageable copies cost ~80 us per evaluation:
-    // 2 % at N = 4096).  Layout (doubles): [scal 8 | grads MAXP*groups*GP_STRIDE | alpha N*Dy | diag N]
+    // 2 % at N = 4096).  Layout (doubles): [scal 8 | grads MAXP*groups*GP_STRIDE | second records of RatQuad / StdPeriodic
+    // parts MAXP*groups*GP_STRIDE | alpha N*Dy | diag N]
     // The factorisation region of an evaluation (potrf -> trtri -> alpha solve || lauum: ~110 launches on up to three streams at
     // N = 4096, every argument a fixed pointer or size of this context) replayed from ONE hipGraph for the sizes whose
     // factorisation is launch- / latency-bound (no CU-masked overlap stream below the overlapped-inverse threshold, so nothing
@@ -90,7 +95,7 @@ struct mi355gp_ctx {
     hipGraphExec_t fgraph = nullptr;
     int fgraph_calls = 0, fgraph_lookahead = -1, graph_enabled = 1;     // MI355GP_GRAPH=0 turns it off
     double *dPack = nullptr, *hPack = nullptr;
-    size_t packDoubles = 0, offGrad = 0, offAlpha = 0, offDiag = 0;
+    size_t packDoubles = 0, offGrad = 0, offExt = 0, offAlpha = 0, offDiag = 0;
     // schedule switches set through mi355gp_set_option (INT_MIN: the process default that factor_ws_alloc read)
     int opt[MI355GP_OPT_NUM];
     double* dGradOutAll = nullptr;      // = dPack + offGrad: [part][groups][GP_STRIDE]
@@ -116,8 +121,10 @@ static void apply_options(mi355gp_ctx* c) {
 }
 
 static void free_parts(mi355gp_ctx* c) {
-    for (auto& p : c->parts)
+    for (auto& p : c->parts) {
         if (p.dXt) (void)hipFree(p.dXt);
+        if (p.dPw) (void)hipFree(p.dPw);
+    }
     c->parts.clear();
 }
 
@@ -230,11 +237,12 @@ int mi355gp_set_data(mi355gp_ctx* c, const double* X, int64_t N, int D, const do
     const long nchunks = (N + trmv_chunk_rows(N) - 1) / trmv_chunk_rows(N);
     HIP_CHECK(hipMalloc(&c->dTrmvPart, sizeof(double) * nchunks * N * Dy));
     const int groups = (D + 31) / 32;
-    c->gradPartDoubles = (long)groups * 2048 * GP_STRIDE;
+    c->gradPartDoubles = 2L * groups * 2048 * GP_STRIDE;       // two records per block for RatQuad / StdPeriodic
     HIP_CHECK(hipMalloc(&c->dGradPart, sizeof(double) * c->gradPartDoubles));
     HIP_CHECK(hipMalloc(&c->dGradOut, sizeof(double) * groups * GP_STRIDE));
     c->offGrad = 8;
-    c->offAlpha = c->offGrad + (size_t)16 * groups * GP_STRIDE;
+    c->offExt = c->offGrad + (size_t)16 * groups * GP_STRIDE;
+    c->offAlpha = c->offExt + (size_t)16 * groups * GP_STRIDE;
     c->offDiag = c->offAlpha + (size_t)N * Dy;
     c->packDoubles = c->offDiag + (size_t)N;
     HIP_CHECK(hipMalloc(&c->dPack, sizeof(double) * c->packDoubles));
@@ -260,10 +268,89 @@ int mi355gp_set_targets(mi355gp_ctx* c, const double* R, int Dy) {
 }  // extern "C"
 
 // ---------------------------------------------------------------------------------------------------
-static int check_theta(int kind, int ard, const double* theta, int D, std::vector<double>* inv_ls) {
-    ARG_CHECK(kind >= 0 && kind <= 3, "unknown covariance kind");
+static bool is_ext_kind(int kind) { return kind == MI355GP_RATQUAD || kind == MI355GP_STDPERIODIC; }
+
+// RatQuad / StdPeriodic: validates theta for the active dimensions `dims` (of D input columns) and fills the input scaling
+// (inv_ls over the D columns), the StdPeriodic parameter block pw and the RatQuad power
+static int ext_setup(int kind, int ard, const double* theta, const std::vector<int>& dims, int D, std::vector<double>* inv_ls,
+                     std::vector<double>* pw, double* power, int* ntheta) {
+    const int na = (int)dims.size();
+    inv_ls->assign((size_t)D, 0.0);
+    pw->clear();
+    if (kind == MI355GP_RATQUAD) {                       // [variance, lengthscale (1 or n_active), power]
+        const int nl = ard ? na : 1;
+        for (int a = 0; a < na; ++a) {
+            const double l = theta[1 + (ard ? a : 0)];
+            ARG_CHECK(l > 0.0, "RatQuad: lengthscales must be positive");
+            (*inv_ls)[(size_t)dims[a]] = 1.0 / l;
+        }
+        *power = theta[1 + nl];
+        ARG_CHECK(*power > 0.0, "RatQuad: power must be positive");
+        *ntheta = 2 + nl;
+        return 0;
+    }
+    ARG_CHECK(ard >= 0 && ard <= 3, "StdPeriodic: ard is a bitmask (1 = one period, 2 = one lengthscale per dimension)");
+    const int nper = (ard & 1) ? na : 1, nl = (ard & 2) ? na : 1;
+    pw->assign(2 * (size_t)D, 0.0);
+    for (int a = 0; a < na; ++a) {
+        const double T = theta[1 + ((ard & 1) ? a : 0)], l = theta[1 + nper + ((ard & 2) ? a : 0)];
+        ARG_CHECK(T > 0.0, "StdPeriodic: periods must be positive");
+        ARG_CHECK(l > 0.0, "StdPeriodic: lengthscales must be positive");
+        const int q = dims[a];
+        (*inv_ls)[(size_t)q] = 1.0;                      // unscaled inputs: Delta from the raw coordinates
+        (*pw)[(size_t)q] = M_PI / T;
+        (*pw)[(size_t)(D + q)] = 1.0 / l;
+    }
+    *power = 0.0;
+    *ntheta = 1 + nper + nl;
+    return 0;
+}
+
+// post-scaling of the raw sums of a RatQuad / StdPeriodic part (records A, B: groups * GP_STRIDE each, see k_grad_ext);
+// writes the gradient in theta order at o and returns the number written
+static int finish_ext(int kind, int ard, const double* theta, const std::vector<int>& dims, const double* A, const double* B,
+                      double* o) {
+    auto at = [](const double* R, int q) { return R[(q / 32) * GP_STRIDE + 2 + (q % 32)]; };
+    const int na = (int)dims.size();
+    int k = 0;
+    o[k++] = A[0] / theta[0];                                          // sum g K / variance
+    if (kind == MI355GP_RATQUAD) {                                     // stationary.py:199,210-213,790-798
+        const int nl = ard ? na : 1;
+        if (!ard) o[k++] = -A[1] / theta[1];
+        else
+            for (int a = 0; a < na; ++a) o[k++] = -at(A, dims[a]) / theta[1 + a];
+        o[k++] = B[0];
+        (void)nl;
+        return k;
+    }
+    const int nper = (ard & 1) ? na : 1;                               // standard_periodic.py:501-526
+    double sT = 0.0, sL = 0.0;
+    for (int a = 0; a < na; ++a) {
+        const double T = theta[1 + ((ard & 1) ? a : 0)], l = theta[1 + nper + ((ard & 2) ? a : 0)];
+        const double gT = at(A, dims[a]) / (T * l * l), gL = at(B, dims[a]) / (l * l * l);
+        if (ard & 1) o[k + a] = gT;
+        else sT += gT;
+        if (ard & 2) o[k + nper + a] = gL;
+        else sL += gL;
+    }
+    if (!(ard & 1)) o[k] = sT;
+    k += nper;
+    if (!(ard & 2)) o[k] = sL;
+    k += (ard & 2) ? na : 1;
+    return k;
+}
+
+static int check_theta(int kind, int ard, const double* theta, int D, std::vector<double>* inv_ls,
+                       std::vector<double>* pw = nullptr, double* power = nullptr) {
+    ARG_CHECK((kind >= 0 && kind <= 3) || (is_ext_kind(kind) && pw && power), "unknown covariance kind");
     ARG_CHECK(theta != nullptr, "theta is NULL");
     ARG_CHECK(theta[0] > 0.0, "variance must be positive");
+    if (is_ext_kind(kind)) {
+        std::vector<int> dims((size_t)D);
+        for (int q = 0; q < D; ++q) dims[(size_t)q] = q;
+        int nt = 0;
+        return ext_setup(kind, ard, theta, dims, D, inv_ls, pw, power, &nt);
+    }
     const int nl = ard ? D : 1;
     inv_ls->resize(D);
     for (int q = 0; q < nl; ++q) {
@@ -365,6 +452,7 @@ static int run_pipeline(mi355gp_ctx* c, EngineShared* gate, bool with_kernel_gra
     const size_t nparts = with_kernel_grads ? c->parts.size() : 0;
     if (nparts > 0) {
         HIP_CHECK(hipMemsetAsync(c->dGradOutAll, 0, sizeof(double) * nparts * groups * GP_STRIDE, st));
+        HIP_CHECK(hipMemsetAsync(c->dPack + c->offExt, 0, sizeof(double) * nparts * groups * GP_STRIDE, st));
         const int nb = grad_num_blocks(n);
         for (size_t p = 0; p < nparts; ++p) {       // every part reduces the same dL_dK against its own dK/dtheta
             const mi355gp_ctx::Part& pt = c->parts[p];
@@ -385,6 +473,10 @@ static int run_pipeline(mi355gp_ctx* c, EngineShared* gate, bool with_kernel_gra
             for (int g = 0; g < (pt.kp.ard ? groups : 1); ++g)
                 launch_reduce_partials(st, c->dGradPart + (long)g * nb * GP_STRIDE, nb, GP_STRIDE,
                                        c->dGradOutAll + ((long)p * groups + g) * GP_STRIDE);
+            if (is_ext_kind(pt.kp.kind))                                   // their second record (k_grad_ext)
+                for (int g = 0; g < (pt.kp.ard ? groups : 1); ++g)
+                    launch_reduce_partials(st, c->dGradPart + ((long)groups + g) * nb * GP_STRIDE, nb, GP_STRIDE,
+                                           c->dPack + c->offExt + ((long)p * groups + g) * GP_STRIDE);
         }
     }
     HIP_CHECK(hipEventRecord(c->ev[6], st));
@@ -488,6 +580,11 @@ static int run_pipeline(mi355gp_ctx* c, EngineShared* gate, bool with_kernel_gra
         for (size_t p = 0; p < nparts; ++p) {
             const mi355gp_ctx::Part& pt = c->parts[p];
             const double* sp = sumsp + p * (size_t)groups * GP_STRIDE;
+            if (is_ext_kind(pt.kp.kind)) {
+                o += finish_ext(pt.kp.kind, pt.ard_in, pt.theta.data(), pt.dims, sp,
+                                c->hPack + c->offExt + p * (size_t)groups * GP_STRIDE, o);
+                continue;
+            }
             *o++ = sp[0] / pt.kp.variance;
             if (pt.kp.kind >= 4) continue;                                   // static kernels: variance only
             if (!pt.kp.ard) *o++ = -sp[1] / pt.theta[1];
@@ -531,6 +628,53 @@ static double expression_kdiag(const mi355gp_ctx* c) {
     return s;
 }
 
+// KernParams of a stateless RatQuad / StdPeriodic evaluation: power, and the StdPeriodic parameter block uploaded to *buf
+static int ext_params(KernParams* kp, const std::vector<double>& pw, double power, DevBuf* buf) {
+    if (!is_ext_kind(kp->kind)) return 0;
+    kp->power = power;
+    if (kp->kind == MI355GP_STDPERIODIC) {
+        kp->ard = 1;                                       // per-dimension reductions
+        HIP_CHECK(buf->alloc(pw.size()));
+        HIP_CHECK(hipMemcpy(*buf, pw.data(), sizeof(double) * pw.size(), hipMemcpyHostToDevice));
+        kp->pw = *buf;
+    }
+    return 0;
+}
+
+// StdPeriodic.gradients_X (standard_periodic.py:574-580): dX[i][q] = -pi / (2 T_q l_q^2) sum_j W_ij K_ij sin(2 Delta_ijq),
+// W = dL_dK (+ dL_dK^T against X itself), as a row reduction on the device (k_periodic_gradx)
+static int periodic_gradients_X(double variance, const std::vector<double>& pw, const double* dL_dK, const double* X, int64_t N,
+                                const double* X2, int64_t M, int D, bool sym, double* out) {
+    std::vector<double> W((size_t)N * M), ones((size_t)D, 1.0);
+    for (int64_t i = 0; i < N; ++i)
+        for (int64_t j = 0; j < M; ++j) W[(size_t)i * M + j] = sym ? dL_dK[i * M + j] + dL_dK[j * M + i] : dL_dK[i * M + j];
+    const long ld1 = round_up(N, 64), ld2 = round_up(M, 64);
+    DevBuf dX1, dX2, dXt1, dXt2, dOnes, dW, dPw, dOut;
+    HIP_CHECK(dX1.alloc(N * D));
+    HIP_CHECK(dX2.alloc(M * D));
+    HIP_CHECK(dXt1.alloc(D * ld1));
+    HIP_CHECK(dXt2.alloc(D * ld2));
+    HIP_CHECK(dOnes.alloc(D));
+    HIP_CHECK(dW.alloc(N * M));
+    HIP_CHECK(dPw.alloc(2 * D));
+    HIP_CHECK(dOut.alloc(N * D));
+    HIP_CHECK(hipMemcpy(dX1, X, sizeof(double) * N * D, hipMemcpyHostToDevice));
+    HIP_CHECK(hipMemcpy(dX2, X2, sizeof(double) * M * D, hipMemcpyHostToDevice));
+    HIP_CHECK(hipMemcpy(dOnes, ones.data(), sizeof(double) * D, hipMemcpyHostToDevice));
+    HIP_CHECK(hipMemcpy(dW, W.data(), sizeof(double) * N * M, hipMemcpyHostToDevice));
+    HIP_CHECK(hipMemcpy(dPw, pw.data(), sizeof(double) * 2 * D, hipMemcpyHostToDevice));
+    launch_scale_inputs(0, dX1, N, D, dOnes, 1, dXt1, ld1);
+    launch_scale_inputs(0, dX2, M, D, dOnes, 1, dXt2, ld2);
+    KernParams kp{MI355GP_STDPERIODIC, 1, D, variance};
+    kp.pw = dPw;
+    launch_periodic_gradx(0, kp, dXt1, ld1, N, dXt2, ld2, M, dW, M, 0, dOut);
+    HIP_CHECK(hipMemcpy(out, dOut, sizeof(double) * N * D, hipMemcpyDeviceToHost));
+    HIP_CHECK(hipGetLastError());
+    for (int64_t i = 0; i < N; ++i)
+        for (int q = 0; q < D; ++q) out[i * D + q] *= -0.5 * pw[(size_t)q] * pw[(size_t)(D + q)] * pw[(size_t)(D + q)];
+    return 0;
+}
+
 static int upload_noise(mi355gp_ctx* c, const double* noise, int64_t noise_len) {
     ARG_CHECK(noise != nullptr && (noise_len == 1 || noise_len == c->n),
               "noise must have 1 or N entries");
@@ -546,12 +690,16 @@ static int prepare_parts(mi355gp_ctx* c, int nparts, const mi355gp_part* parts) 
     if ((int)c->parts.size() != nparts) {
         free_parts(c);
         c->parts.resize((size_t)nparts);
-        for (auto& p : c->parts) HIP_CHECK(hipMalloc(&p.dXt, sizeof(double) * c->D * c->npad));
+        for (auto& p : c->parts) {
+            HIP_CHECK(hipMalloc(&p.dXt, sizeof(double) * c->D * c->npad));
+            HIP_CHECK(hipMalloc(&p.dPw, sizeof(double) * 2 * c->D));
+        }
     }
     for (int i = 0; i < nparts; ++i) {
         const mi355gp_part& in = parts[i];
         mi355gp_ctx::Part& p = c->parts[(size_t)i];
-        ARG_CHECK(in.kind >= 0 && in.kind <= 5 && in.theta, "unknown covariance kind / NULL theta in a kernel part");
+        ARG_CHECK(((in.kind >= 0 && in.kind <= 5) || is_ext_kind(in.kind)) && in.theta,
+                  "unknown covariance kind / NULL theta in a kernel part");
         ARG_CHECK(in.theta[0] > 0.0, "variance must be positive");
         p.dims.clear();
         if (in.active_dims && in.n_active > 0) {
@@ -563,6 +711,21 @@ static int prepare_parts(mi355gp_ctx* c, int nparts, const mi355gp_part* parts) 
             for (int q = 0; q < c->D; ++q) p.dims.push_back(q);
         }
         const int na = (int)p.dims.size();
+        p.term = in.term;
+        p.ard_in = in.ard;
+        if (is_ext_kind(in.kind)) {
+            double power = 0.0;
+            int nt = 0;
+            if (int rc = ext_setup(in.kind, in.ard, in.theta, p.dims, c->D, &p.inv_ls, &p.pw, &power, &nt)) return rc;
+            p.kp = KernParams{in.kind, (in.kind == MI355GP_STDPERIODIC || in.ard) ? 1 : 0, c->D, in.theta[0]};
+            p.kp.power = power;
+            if (in.kind == MI355GP_STDPERIODIC) {
+                HIP_CHECK(hipMemcpyAsync(p.dPw, p.pw.data(), sizeof(double) * 2 * c->D, hipMemcpyHostToDevice, c->st));
+                p.kp.pw = p.dPw;
+            }
+            p.theta.assign(in.theta, in.theta + nt);
+            continue;
+        }
         const bool stationary = in.kind <= 3;
         const int nl = stationary ? (in.ard ? na : 1) : 0;
         p.term = in.term;
@@ -664,7 +827,7 @@ int mi355gp_exact_studentt_sum(mi355gp_ctx* c, int nparts, const mi355gp_part* p
 int mi355gp_exact_inference(mi355gp_ctx* c, int kind, int ard, const double* theta, const double* noise,
                             int64_t noise_len, double jitter, double extra_jitter, double* out_scalars,
                             double* alpha_out, double* dtheta_out, double* diag_dLdK_out, double* stage_ms) {
-    ARG_CHECK(kind >= 0 && kind <= 3, "unknown covariance kind");
+    ARG_CHECK((kind >= 0 && kind <= 3) || is_ext_kind(kind), "unknown covariance kind");
     const mi355gp_part part{kind, ard, 0, nullptr, theta};
     return mi355gp_exact_inference_sum(c, 1, &part, noise, noise_len, jitter, extra_jitter, out_scalars, alpha_out,
                                        dtheta_out, diag_dLdK_out, stage_ms);
@@ -748,8 +911,9 @@ int mi355gp_kern_K(int device, int kind, int ard, const double* theta, const dou
                    const double* X2, int64_t M, int D, double* K_out) {
     ARG_CHECK(X && K_out && N > 0 && D > 0, "mi355gp_kern_K: bad arguments");
     HIP_CHECK(hipSetDevice(device));
-    std::vector<double> inv_ls;
-    if (int rc = check_theta(kind, ard, theta, D, &inv_ls)) return rc;
+    std::vector<double> inv_ls, pw;
+    double power = 0.0;
+    if (int rc = check_theta(kind, ard, theta, D, &inv_ls, &pw, &power)) return rc;
     const bool sym = (X2 == nullptr);
     if (sym) M = N;
     ARG_CHECK(M > 0, "mi355gp_kern_K: M must be positive");
@@ -771,6 +935,8 @@ int mi355gp_kern_K(int device, int kind, int ard, const double* theta, const dou
         pXt2 = dXt2;
     }
     KernParams kp{kind, ard ? 1 : 0, D, theta[0]};
+    DevBuf dPw;
+    if (int rc = ext_params(&kp, pw, power, &dPw)) return rc;
     launch_kbuild_cross(0, kp, dXt1, ld1, N, pXt2, sym ? ld1 : ld2, M, dK, M);
     HIP_CHECK(hipMemcpy(K_out, dK, sizeof(double) * N * M, hipMemcpyDeviceToHost));
     HIP_CHECK(hipGetLastError());
@@ -778,8 +944,9 @@ int mi355gp_kern_K(int device, int kind, int ard, const double* theta, const dou
 }
 
 int mi355gp_kern_Kdiag(int kind, const double* theta, int64_t N, double* out) {
-    ARG_CHECK(kind >= 0 && kind <= 3 && theta && out && N >= 0, "mi355gp_kern_Kdiag: bad arguments");
-    for (int64_t i = 0; i < N; ++i) out[i] = theta[0];   // stationary: K(x,x) = variance (stationary.py:170-173)
+    ARG_CHECK(((kind >= 0 && kind <= 3) || is_ext_kind(kind)) && theta && out && N >= 0, "mi355gp_kern_Kdiag: bad arguments");
+    // stationary: K(x,x) = variance (stationary.py:170-173); StdPeriodic likewise (standard_periodic.py:105-109)
+    for (int64_t i = 0; i < N; ++i) out[i] = theta[0];
     return 0;
 }
 
@@ -788,8 +955,9 @@ int mi355gp_update_gradients_full(int device, int kind, int ard, const double* t
                                   double* dtheta_out) {
     ARG_CHECK(dL_dK && X && dtheta_out && N > 0 && D > 0, "mi355gp_update_gradients_full: bad arguments");
     HIP_CHECK(hipSetDevice(device));
-    std::vector<double> inv_ls;
-    if (int rc = check_theta(kind, ard, theta, D, &inv_ls)) return rc;
+    std::vector<double> inv_ls, pw;
+    double power = 0.0;
+    if (int rc = check_theta(kind, ard, theta, D, &inv_ls, &pw, &power)) return rc;
     const bool sym = (X2 == nullptr);
     if (sym) M = N;
     const long ld1 = round_up(N, 64), ld2 = round_up(M, 64);
@@ -799,8 +967,8 @@ int mi355gp_update_gradients_full(int device, int kind, int ard, const double* t
     HIP_CHECK(dXt1.alloc(D * ld1));
     HIP_CHECK(dIl.alloc(D));
     HIP_CHECK(dG.alloc(N * M));
-    HIP_CHECK(dPart.alloc(groups * 2048 * GP_STRIDE));
-    HIP_CHECK(dOut.alloc(groups * GP_STRIDE));
+    HIP_CHECK(dPart.alloc(2 * groups * 2048 * GP_STRIDE));          // second records: RatQuad / StdPeriodic
+    HIP_CHECK(dOut.alloc(2 * groups * GP_STRIDE));
     HIP_CHECK(hipMemcpy(dX, X, sizeof(double) * N * D, hipMemcpyHostToDevice));
     HIP_CHECK(hipMemcpy(dIl, inv_ls.data(), sizeof(double) * D, hipMemcpyHostToDevice));
     HIP_CHECK(hipMemcpy(dG, dL_dK, sizeof(double) * N * M, hipMemcpyHostToDevice));
@@ -814,13 +982,24 @@ int mi355gp_update_gradients_full(int device, int kind, int ard, const double* t
         pXt2 = dXt2;
     }
     KernParams kp{kind, ard ? 1 : 0, D, theta[0]};
+    DevBuf dPw;
+    if (int rc = ext_params(&kp, pw, power, &dPw)) return rc;
     const int nb = grad_generic_num_blocks(N, M);
     launch_grad_generic(0, kp, dXt1, ld1, N, pXt2, sym ? ld1 : ld2, M, sym ? 1 : 0, dG, M, dPart, GP_STRIDE);
-    for (int g = 0; g < (kp.ard ? groups : 1); ++g)
-        launch_reduce_partials(0, dPart + (long)g * nb * GP_STRIDE, nb, GP_STRIDE, dOut + (long)g * GP_STRIDE);
-    std::vector<double> sums((size_t)groups * GP_STRIDE, 0.0);
-    HIP_CHECK(hipMemcpy(sums.data(), dOut, sizeof(double) * groups * GP_STRIDE, hipMemcpyDeviceToHost));
+    const int nrec = is_ext_kind(kind) ? 2 : 1;
+    for (int r = 0; r < nrec; ++r)
+        for (int g = 0; g < (kp.ard ? groups : 1); ++g)
+            launch_reduce_partials(0, dPart + ((long)r * groups + g) * nb * GP_STRIDE, nb, GP_STRIDE,
+                                   dOut + ((long)r * groups + g) * GP_STRIDE);
+    std::vector<double> sums((size_t)nrec * groups * GP_STRIDE, 0.0);
+    HIP_CHECK(hipMemcpy(sums.data(), dOut, sizeof(double) * sums.size(), hipMemcpyDeviceToHost));
     HIP_CHECK(hipGetLastError());
+    if (is_ext_kind(kind)) {
+        std::vector<int> dims((size_t)D);
+        for (int q = 0; q < D; ++q) dims[(size_t)q] = q;
+        finish_ext(kind, ard, theta, dims, sums.data(), sums.data() + (size_t)groups * GP_STRIDE, dtheta_out);
+        return 0;
+    }
     finish_dtheta(kp, theta, sums.data(), dtheta_out);
     return 0;
 }
@@ -832,11 +1011,13 @@ int mi355gp_gradients_X(int device, int kind, int ard, const double* theta, cons
                         int64_t N, const double* X2, int64_t M, int D, double* out) {
     ARG_CHECK(dL_dK && X && out && N > 0 && D > 0, "mi355gp_gradients_X: bad arguments");
     HIP_CHECK(hipSetDevice(device));
-    std::vector<double> inv_ls;
-    if (int rc = check_theta(kind, ard, theta, D, &inv_ls)) return rc;
+    std::vector<double> inv_ls, pw;
+    double power = 0.0;
+    if (int rc = check_theta(kind, ard, theta, D, &inv_ls, &pw, &power)) return rc;
     const bool sym = (X2 == nullptr);
     if (sym) { M = N; X2 = X; }
     ARG_CHECK(M > 0, "mi355gp_gradients_X: M must be positive");
+    if (kind == MI355GP_STDPERIODIC) return periodic_gradients_X(theta[0], pw, dL_dK, X, N, X2, M, D, sym, out);
     // transposed weights G' (M x N): rows = X2 points, columns = X points
     std::vector<double> Gt((size_t)M * N);
     for (int64_t i = 0; i < N; ++i)
@@ -850,7 +1031,7 @@ int mi355gp_gradients_X(int device, int kind, int ard, const double* theta, cons
     HIP_CHECK(dXtC.alloc(D * ldc));
     HIP_CHECK(dIl.alloc(D));
     HIP_CHECK(dG.alloc(M * N));
-    HIP_CHECK(dPart.alloc(2048 * GP_STRIDE));
+    HIP_CHECK(dPart.alloc(2 * 2048 * GP_STRIDE * ((D + 31) / 32)));   // every group, and the second records of RatQuad
     HIP_CHECK(dCol.alloc(64 * N * (D + 1)));
     HIP_CHECK(dHX.alloc(N * (D + 1)));
     HIP_CHECK(hipMemcpy(dXr, X2, sizeof(double) * M * D, hipMemcpyHostToDevice));
@@ -860,6 +1041,8 @@ int mi355gp_gradients_X(int device, int kind, int ard, const double* theta, cons
     launch_scale_inputs(0, dXr, M, D, dIl, ard ? 1 : 0, dXtR, ldr);
     launch_scale_inputs(0, dXc, N, D, dIl, ard ? 1 : 0, dXtC, ldc);
     KernParams kp{kind, ard ? 1 : 0, D, theta[0]};
+    DevBuf dPw;
+    if (int rc = ext_params(&kp, pw, power, &dPw)) return rc;
     launch_grad_generic(0, kp, dXtR, ldr, M, dXtC, ldc, N, 0, dG, N, dPart, GP_STRIDE, dG, N);   // H in place
     const int ns = launch_colreduce_multi(0, dG, N, M, N, dXtR, 1, ldr, D, 1, dCol);
     launch_sum_splits(0, dCol, N * (D + 1), ns, 0, dHX);
@@ -1073,7 +1256,7 @@ int mi355gp_predictive_gradients_sum(mi355gp_ctx* c, int nparts, const mi355gp_p
     HIP_CHECK(dT.alloc(np * mp));
     HIP_CHECK(dG.alloc(np * mp));
     HIP_CHECK(dH.alloc(np * mp));
-    HIP_CHECK(dPart.alloc(2048 * GP_STRIDE * ((D + 31) / 32)));
+    HIP_CHECK(dPart.alloc(2 * 2048 * GP_STRIDE * ((D + 31) / 32)));   // second records of RatQuad parts
     HIP_CHECK(dCol.alloc(64 * mp * (D + 1)));
     HIP_CHECK(dHX.alloc(mp * (D + 1)));
     HIP_CHECK(hipMemcpyAsync(dXn, Xnew, sizeof(double) * M * D, hipMemcpyHostToDevice, st));
@@ -1111,9 +1294,22 @@ int mi355gp_predictive_gradients_sum(mi355gp_ctx* c, int nparts, const mi355gp_p
         }
         for (size_t pi = 0; pi < c->parts.size(); ++pi) {
             const mi355gp_ctx::Part& pt = c->parts[pi];
-            if (pt.kp.kind >= 4) continue;                              // White / Bias: no dependence on X* (static.py)
+            if (pt.kp.kind == 4 || pt.kp.kind == 5) continue;          // White / Bias: no dependence on X* (static.py)
             scale_new(pt);
             HIP_CHECK(herr);
+            if (pt.kp.kind == MI355GP_STDPERIODIC) {                    // not a function of r: the row reduction instead of H
+                launch_periodic_gradx(st, pt.kp, dXt2, ld2, M, pt.dXt, np, n, W, mp, /*wt=*/1, dHX);
+                HIP_CHECK(hipMemcpyAsync(HX.data(), dHX, sizeof(double) * M * D, hipMemcpyDeviceToHost, st));
+                HIP_CHECK(hipStreamSynchronize(st));
+                for (int64_t m = 0; m < M; ++m)
+                    for (long q = 0; q < D; ++q) {
+                        const double il = pt.pw[(size_t)(D + q)];
+                        const double g = -0.5 * pt.pw[(size_t)q] * il * il * HX[(size_t)m * D + q];
+                        if (is_var) dvar_out[m * D + q] += -2.0 * g;
+                        else dmu_out[((size_t)m * D + q) * Dy + pass] += g;
+                    }
+                continue;
+            }
             launch_grad_generic(st, pt.kp, pt.dXt, np, n, dXt2, ld2, M, 0, W, mp, dPart, GP_STRIDE, dH, mp);
             const int ns = launch_colreduce_multi(st, dH, mp, n, M, pt.dXt, 1, np, (int)D, 1, dCol);
             launch_sum_splits(st, dCol, (long)hx, ns, 0, dHX);
@@ -1203,7 +1399,7 @@ int mi355gp_covariance_between_points(mi355gp_ctx* c, int nparts, const mi355gp_
 
 int mi355gp_predict(mi355gp_ctx* c, int kind, int ard, const double* theta, const double* Xnew, int64_t M,
                     double* mu_out, double* var_out, int full_cov) {
-    ARG_CHECK(kind >= 0 && kind <= 3, "unknown covariance kind");
+    ARG_CHECK((kind >= 0 && kind <= 3) || is_ext_kind(kind), "unknown covariance kind");
     const mi355gp_part part{kind, ard, 0, nullptr, theta};
     return mi355gp_predict_sum(c, 1, &part, Xnew, M, mu_out, var_out, full_cov);
 }

@@ -1613,6 +1613,7 @@ int mi355gp_grid_exact_inference(mi355gp_grid* g, int kind, int ard, const doubl
                                  double* alpha_out, double* dtheta_out, double* diag_dLdK_out, double* stage_ms) {
     ARGCHK(g && g->n > 0, "mi355gp_grid_exact_inference: set_data first");
     ARGCHK(out_scalars && theta && noise, "mi355gp_grid_exact_inference: NULL argument");
+    ARGCHK(kind >= 0 && kind <= 3, "unknown covariance kind");     // (the exact-only kinds 6 / 7 included)
     if (g->single) {
         double ms[MI355GP_NUM_T];
         const int rc = mi355gp_exact_inference(g->single, kind, ard, theta, noise, noise_len, jitter, extra_jitter, out_scalars,
@@ -1628,7 +1629,6 @@ int mi355gp_grid_exact_inference(mi355gp_grid* g, int kind, int ard, const doubl
         g->have_result = (rc == 0);
         return rc;
     }
-    ARGCHK(kind >= 0 && kind <= 3, "unknown covariance kind");
     ARGCHK(noise_len == 1 || noise_len == g->n, "noise must have 1 or N entries");
     ARGCHK(theta[0] > 0.0, "variance must be positive");
     HIP_CHECK(hipSetDevice(g->device));

@@ -216,6 +216,9 @@ struct KernParams {
     int ard;
     int D;
     double variance;
+    // kinds 6 / 7 only (the kernels of the other kinds never read them)
+    double power = 0.0;               // RatQuad: alpha
+    const double* pw = nullptr;       // StdPeriodic, device [2 D]: pi / T_q, then 1 / l_q (0 outside the active dimensions)
 };
 // Xt: scaled, transposed inputs [D][ldx] (x_q / l_q); builds lower tiles of Ky = K + diag(noise + jit) into A
 // (npad x npad); rows/cols >= n get the identity.
@@ -243,6 +246,9 @@ struct GradOut {
     int nblocks;
 };
 int grad_num_blocks(long n);
+// RatQuad (6) / StdPeriodic (7) write a SECOND partial record per block and group (RatQuad: [0] = dK/dpower sums;
+// StdPeriodic: [2 + q] = lengthscale sums, the first record's [2 + q] holding the period sums) at
+// partials + groups * nblocks * GP_STRIDE, groups = ceil(D / 32): partial buffers of these kinds are twice as long.
 // aa_scale (optional, device): factor on the alpha alpha^T term of dL_dK (Student-t process)
 void launch_grad_fused(hipStream_t st, KernParams kp, const double* Xt, long ldx, long n, const double* W,
                        long ldw, const double* alpha, int Dy, double* partials, int stride,
@@ -266,6 +272,11 @@ void launch_grad_generic(hipStream_t st, KernParams kp, const double* Xt1, long 
                          long ld2, long m, int symmetric, const double* G, long ldg, double* partials,
                          int stride, double* Hout = nullptr, long ldh = 0,
                          RankTerm rk = RankTerm{nullptr, nullptr, 0, 0.0, 1.0, nullptr});
+// StdPeriodic dK/dx (standard_periodic.py:574-580) as a row reduction over a group of 32 dimensions from q_off:
+//   out[i][q] = sum_j W(i, j) K(x1_i, x2_j) sin(2 Delta_ijq),  W(i, j) = W[i * ldw + j], or W[j * ldw + i] if wt
+// (out: n x D row-major; the caller applies -pi / (2 T_q l_q^2)).  Xt1 / Xt2: unscaled, dimension-major.
+void launch_periodic_gradx(hipStream_t st, KernParams kp, const double* Xt1, long ld1, long n, const double* Xt2, long ld2,
+                           long m, const double* W, long ldw, int wt, double* out);
 // part[split][cols][nv] = sum over a row range of M[i][j] * V(i, c); V(i, c) = V[i*sr + c*sc] plus an optional
 // all-ones column; returns the number of row splits (sum them with launch_sum_splits)
 int launch_colreduce_multi(hipStream_t st, const double* M, long ld, long rows, long cols, const double* V, long sr,

@@ -311,10 +311,24 @@ int launch_kbuild_cols(hipStream_t st, KernParams kp, const double* Xt1, long ld
     return nsplit;
 }
 
+// RatQuad / StdPeriodic (kinds 6 / 7): kernels of their own at the end of this file; the launchers below hand them over
+static void launch_kbuild_ext(hipStream_t st, bool sym, KernParams kp, const double* Xt1, long ld1, long n, const double* Xt2,
+                              long ld2, long m, double* out, long ldo, long nrows_out, const double* noise, long noise_len,
+                              double jit, int lower_only, int add_diag, int ntc, int nblocks, int accumulate, int diag_same,
+                              const double* mul);
+static void launch_grad_ext(hipStream_t st, bool fused, KernParams kp, const double* Xt1, long ld1, long n, const double* Xt2,
+                            long ld2, long m, const double* G, long ldg, const double* alpha, int Dy, long ntiles, int ntc,
+                            double* partials, double* Hout, long ldh, const double* aa_scale, const double* Mul, long ldm);
+
 void launch_kbuild_sym(hipStream_t st, KernParams kp, const double* Xt, long ldx, long n, long npad, double* A,
                        const double* noise, long noise_len, double jit, int lower_only, int add_diag, int accumulate,
                        const double* mul) {
     const int nt = (int)(npad / KT);
+    if (kp.kind >= 6) {
+        launch_kbuild_ext(st, true, kp, Xt, ldx, n, Xt, ldx, n, A, npad, npad, noise, noise_len, jit, lower_only, add_diag, nt,
+                          nt * nt, accumulate, 0, mul);
+        return;
+    }
     hipLaunchKernelGGL((k_kbuild<true>), dim3((unsigned)((long)nt * nt)), dim3(256), 0, st, kp, Xt, ldx, n, Xt, ldx, n,
                        A, npad, npad, noise, noise_len, jit, lower_only, add_diag, nt, accumulate, 0, mul);
 }
@@ -322,6 +336,11 @@ void launch_kbuild_sym(hipStream_t st, KernParams kp, const double* Xt, long ldx
 void launch_kbuild_cross(hipStream_t st, KernParams kp, const double* Xt1, long ld1, long n, const double* Xt2,
                          long ld2, long m, double* Kout, long ldk, int accumulate, int diag_same, const double* mul) {
     const int ntr = (int)((n + KT - 1) / KT), ntc = (int)((m + KT - 1) / KT);
+    if (kp.kind >= 6) {
+        launch_kbuild_ext(st, false, kp, Xt1, ld1, n, Xt2, ld2, m, Kout, ldk, n, nullptr, 0, 0.0, 0, 0, ntc, ntr * ntc,
+                          accumulate, diag_same, mul);
+        return;
+    }
     hipLaunchKernelGGL((k_kbuild<false>), dim3((unsigned)((long)ntr * ntc)), dim3(256), 0, st, kp, Xt1, ld1, n, Xt2,
                        ld2, m, Kout, ldk, n, nullptr, 0, 0.0, 0, 0, ntc, accumulate, diag_same, mul);
 }
@@ -501,6 +520,11 @@ void launch_grad_fused(hipStream_t st, KernParams kp, const double* Xt, long ldx
     const long nt = (n + KT - 1) / KT;
     const long ntiles = nt * (nt + 1) / 2;
     const int nb = pick_grad_blocks(ntiles);
+    if (kp.kind >= 6) {
+        launch_grad_ext(st, true, kp, Xt, ldx, n, Xt, ldx, n, W, ldw, alpha, Dy, ntiles, (int)nt, partials, nullptr, 0, aa_scale,
+                        Mul, ldm);
+        return;
+    }
     if (!kp.ard) {
         hipLaunchKernelGGL((k_grad<true, false>), dim3(nb), dim3(256), 0, st, kp, Xt, ldx, n, Xt, ldx, n, W, ldw,
                            alpha, Dy, 0, ntiles, (int)nt, partials, nullptr, 0, 0, aa_scale, Mul, ldm);
@@ -887,6 +911,12 @@ void launch_grad_generic(hipStream_t st, KernParams kp, const double* Xt1, long 
     const long ntr = (n + KT - 1) / KT, ntc = (m + KT - 1) / KT;
     const long ntiles = ntr * ntc;
     const int nb = pick_grad_blocks(ntiles);
+    if (kp.kind >= 6) {
+        if (rk.Y) return;                                  // the rank term belongs to the sparse path, which has no kind >= 6
+        launch_grad_ext(st, false, kp, Xt1, ld1, n, Xt2, ld2, m, G, ldg, nullptr, 0, ntiles, (int)ntc, partials, Hout, ldh,
+                        nullptr, nullptr, 0);
+        return;
+    }
     if (!kp.ard) {
         hipLaunchKernelGGL((k_grad<false, false>), dim3(nb), dim3(256), 0, st, kp, Xt1, ld1, n, Xt2, ld2, m, G, ldg,
                            nullptr, 0, 0, ntiles, (int)ntc, partials, Hout, ldh, symmetric, nullptr, nullptr, 0, rk);
@@ -1312,4 +1342,435 @@ void launch_rowscale_sqrt(hipStream_t st, const double* M, long ld, long rows, l
     if (rows <= 0) return;
     hipLaunchKernelGGL(k_rowscale_sqrt, dim3((unsigned)rows, (unsigned)((cols + 255) / 256)), dim3(256), 0, st, M, ld, rows,
                        cols, w, Out);
+}
+
+// ------------------------------------------------------------------------------------------------
+// RatQuad (kind 6, stationary.py:747-802) and StdPeriodic (kind 7, standard_periodic.py:15-580).
+// Kernels of their own (templates on the kind), so that the instantiations of the other kinds keep their code.
+//   RatQuad:     K = var exp(-a log1p(r^2 / 2)),  dK/dr / r = -a K / (1 + r^2 / 2),  dK/da = -K log1p(r^2 / 2)
+//                (inputs scaled by 1 / l as for the other stationary kinds)
+//   StdPeriodic: K = var exp(-1/2 sum_q (sin(Delta_q) / l_q)^2),  Delta_q = pi (x_iq - x_jq) / T_q
+//                (inputs staged UNSCALED: Delta is formed from the difference of the raw coordinates, so calendar-year
+//                inputs keep their precision; pi / T_q and 1 / l_q are applied per dimension in the pair loop)
+#define KIND_RATQUAD 6
+#define KIND_STDPER 7
+
+__device__ __forceinline__ void ratquad_all(double var, double a, double r2, double& k, double& dk_or, double& dk_a) {
+    const double h = 0.5 * r2;
+    const double lg = log1p(h);
+    k = var * exp(-a * lg);
+    dk_or = -a * k / (1.0 + h);
+    dk_a = -k * lg;
+}
+
+// s[a][b] += sum_q (sin(pi / T_q (xi[q][ty*4+a] - xj[q][tx*4+b])) / l_q)^2 over the staged dimensions q0 .. q0 + qc
+__device__ __forceinline__ void accum_per(const double* si, const double* sj, const double* __restrict__ pw, int D, int q0, int qc,
+                                          int ty, int tx, double (&s)[4][4]) {
+    for (int q = 0; q < qc; ++q) {
+        const double pt = pw[q0 + q], il = pw[D + q0 + q];
+        const d4 xi = *reinterpret_cast<const d4*>(si + q * KT + ty * 4);
+        const d4 xj = ld_xj(sj, q, tx);
+#pragma unroll
+        for (int a = 0; a < 4; ++a)
+#pragma unroll
+            for (int b = 0; b < 4; ++b) {
+                const double sn = sin((xi[a] - xj[b]) * pt) * il;
+                s[a][b] = fma(sn, sn, s[a][b]);
+            }
+    }
+}
+
+template <int KIND>
+__device__ __forceinline__ void accum_ext(const double* si, const double* sj, const KernParams& kp, int q0, int qc, int ty, int tx,
+                                          double (&s)[4][4]) {
+    if (KIND == KIND_RATQUAD) accum_r2(si, sj, qc, ty, tx, s);
+    else accum_per(si, sj, kp.pw, kp.D, q0, qc, ty, tx, s);
+}
+
+template <int KIND>
+__device__ __forceinline__ double ext_k(const KernParams& kp, double s) {
+    if (KIND == KIND_RATQUAD) return kp.variance * exp(-kp.power * log1p(0.5 * s));
+    return kp.variance * exp(-0.5 * s);
+}
+
+// Covariance assembly of k_kbuild (same tiling, same output conventions) for the two kinds.
+template <bool SYM, int KIND>
+__global__ __launch_bounds__(256) void k_kbuild_ext(KernParams kp, const double* __restrict__ Xt1, long ld1, long n,
+                                                    const double* __restrict__ Xt2, long ld2, long m,
+                                                    double* __restrict__ out, long ldo, long nrows_out,
+                                                    const double* __restrict__ noise, long noise_len, double jit,
+                                                    int lower_only, int add_diag, int ntc, int accumulate, const double* mul) {
+    __shared__ __attribute__((aligned(16))) double si[KDC * KT];
+    __shared__ __attribute__((aligned(16))) double sj[KDC * KTJ];
+    const int t = threadIdx.x, tx = t & 15, ty = t >> 4;
+    const long ti = blockIdx.x / ntc, tj = blockIdx.x % ntc;
+    if (SYM && lower_only && tj > ti) return;
+    const long i0 = ti * KT, j0 = tj * KT;
+    double s[4][4];
+#pragma unroll
+    for (int a = 0; a < 4; ++a)
+#pragma unroll
+        for (int b = 0; b < 4; ++b) s[a][b] = 0.0;
+    if ((i0 < n) && (j0 < m)) {
+        for (int q0 = 0; q0 < kp.D; q0 += KDC) {
+            const int qc = (kp.D - q0 < KDC) ? (kp.D - q0) : KDC;
+            __syncthreads();
+            stage_x(Xt1, ld1, i0, q0, qc, si, t);
+            stage_xj(Xt2, ld2, j0, q0, qc, sj, t);
+            __syncthreads();
+            accum_ext<KIND>(si, sj, kp, q0, qc, ty, tx, s);
+        }
+    }
+#pragma unroll
+    for (int a = 0; a < 4; ++a) {
+        const long i = i0 + ty * 4 + a;
+        double v[4];
+#pragma unroll
+        for (int b = 0; b < 4; ++b) {
+            const long j = j0 + tx * 4 + b;
+            if (i < n && j < m) v[b] = ext_k<KIND>(kp, s[a][b]);
+            else v[b] = (SYM && i == j && !accumulate) ? 1.0 : 0.0;
+        }
+        if (SYM) {
+            if (i < nrows_out) {
+                d4* p = reinterpret_cast<d4*>(out + i * ldo + j0 + tx * 4);
+                d4 o = (d4){v[0], v[1], v[2], v[3]};
+                if (mul) o *= *reinterpret_cast<const d4*>(mul + i * ldo + j0 + tx * 4);
+                if (add_diag && i < n) {
+                    const long d = i - (j0 + tx * 4);
+                    if (d >= 0 && d < 4) o[d] += noise[noise_len > 1 ? i : 0] + jit;
+                }
+                if (accumulate) o += *p;
+                *p = o;
+            }
+        } else if (i < n) {
+#pragma unroll
+            for (int b = 0; b < 4; ++b) {
+                const long j = j0 + tx * 4 + b;
+                if (j < m) {
+                    const double w = mul ? v[b] * mul[i * ldo + j] : v[b];
+                    out[i * ldo + j] = accumulate ? out[i * ldo + j] + w : w;
+                }
+            }
+        }
+    }
+}
+
+static void launch_kbuild_ext(hipStream_t st, bool sym, KernParams kp, const double* Xt1, long ld1, long n, const double* Xt2,
+                              long ld2, long m, double* out, long ldo, long nrows_out, const double* noise, long noise_len,
+                              double jit, int lower_only, int add_diag, int ntc, int nblocks, int accumulate, int diag_same,
+                              const double* mul) {
+    (void)diag_same;                                   // no White-like diagonal in either kind
+    const dim3 g((unsigned)nblocks), b(256);
+    if (kp.kind == KIND_RATQUAD) {
+        if (sym)
+            hipLaunchKernelGGL((k_kbuild_ext<true, KIND_RATQUAD>), g, b, 0, st, kp, Xt1, ld1, n, Xt2, ld2, m, out, ldo, nrows_out,
+                               noise, noise_len, jit, lower_only, add_diag, ntc, accumulate, mul);
+        else
+            hipLaunchKernelGGL((k_kbuild_ext<false, KIND_RATQUAD>), g, b, 0, st, kp, Xt1, ld1, n, Xt2, ld2, m, out, ldo,
+                               nrows_out, noise, noise_len, jit, lower_only, add_diag, ntc, accumulate, mul);
+    } else if (kp.kind == KIND_STDPER) {
+        if (sym)
+            hipLaunchKernelGGL((k_kbuild_ext<true, KIND_STDPER>), g, b, 0, st, kp, Xt1, ld1, n, Xt2, ld2, m, out, ldo, nrows_out,
+                               noise, noise_len, jit, lower_only, add_diag, ntc, accumulate, mul);
+        else
+            hipLaunchKernelGGL((k_kbuild_ext<false, KIND_STDPER>), g, b, 0, st, kp, Xt1, ld1, n, Xt2, ld2, m, out, ldo,
+                               nrows_out, noise, noise_len, jit, lower_only, add_diag, ntc, accumulate, mul);
+    }
+}
+
+// Gradient pass of k_grad for the two kinds, one launch per group of 32 dimensions (q_off).  Record A [GP_STRIDE] per block:
+//   [0] sum g K, RatQuad [1] sum g dK/dr r (isotropic) or [2 + q] sum g (dK/dr / r) (x~_iq - x~_jq)^2 (ARD),
+//   StdPeriodic [2 + q] sum g K sin(D_q) cos(D_q) D_q (period);
+// record B at partB: RatQuad [0] sum g dK/dpower, StdPeriodic [2 + q] sum g K sin^2(D_q) (lengthscale).
+// StdPeriodic always reduces per dimension; the host applies 1 / (T_q l_q^2), 1 / l_q^3 and sums the isotropic cases.
+template <bool FUSED, int KIND>
+__global__ __launch_bounds__(256) void k_grad_ext(KernParams kp, const double* __restrict__ Xt1, long ld1, long n,
+                                                  const double* __restrict__ Xt2, long ld2, long m,
+                                                  const double* __restrict__ G, long ldg,
+                                                  const double* __restrict__ alpha, int Dy, int q_off,
+                                                  long ntiles, int ntc, double* __restrict__ partA, double* __restrict__ partB,
+                                                  double* __restrict__ Hout, long ldh, const double* __restrict__ aa_scale,
+                                                  const double* __restrict__ Mul, long ldm) {
+    constexpr bool PER = (KIND == KIND_STDPER);
+    __shared__ __attribute__((aligned(16))) double si[KDC * KT];
+    __shared__ __attribute__((aligned(16))) double sj[KDC * KTJ];
+    __shared__ double red[256];
+    const int t = threadIdx.x, tx = t & 15, ty = t >> 4;
+    const bool perdim = PER || kp.ard;
+    double a_var = 0.0, a_iso = 0.0, a_pow = 0.0;
+    double a1[KDC], a2[PER ? KDC : 1];
+#pragma unroll
+    for (int q = 0; q < KDC; ++q) a1[q] = 0.0;
+#pragma unroll
+    for (int q = 0; q < (PER ? KDC : 1); ++q) a2[q] = 0.0;
+    const int qcnt = perdim ? ((kp.D - q_off < KDC) ? (kp.D - q_off) : KDC) : 0;
+    const double sc = (FUSED && aa_scale) ? aa_scale[0] : 1.0;
+
+    for (long tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+        long ti, tj;
+        if (FUSED) {
+            ti = (long)((sqrt(8.0 * (double)tile + 1.0) - 1.0) * 0.5);
+            while (ti * (ti + 1) / 2 > tile) --ti;
+            while ((ti + 1) * (ti + 2) / 2 <= tile) ++ti;
+            tj = tile - ti * (ti + 1) / 2;
+        } else {
+            ti = tile / ntc;
+            tj = tile - ti * ntc;
+        }
+        const long i0 = ti * KT, j0 = tj * KT;
+        double s[4][4];
+#pragma unroll
+        for (int a = 0; a < 4; ++a)
+#pragma unroll
+            for (int b = 0; b < 4; ++b) s[a][b] = 0.0;
+        int last_q0 = -1;
+        for (int q0 = 0; q0 < kp.D; q0 += KDC) {
+            const int qc = (kp.D - q0 < KDC) ? (kp.D - q0) : KDC;
+            __syncthreads();
+            stage_x(Xt1, ld1, i0, q0, qc, si, t);
+            stage_xj(Xt2, ld2, j0, q0, qc, sj, t);
+            __syncthreads();
+            accum_ext<KIND>(si, sj, kp, q0, qc, ty, tx, s);
+            last_q0 = q0;
+        }
+        double gw[4][4];   // RatQuad: g dK/dr / r;  StdPeriodic: g K
+#pragma unroll
+        for (int a = 0; a < 4; ++a) {
+            const long i = i0 + ty * 4 + a;
+#pragma unroll
+            for (int b = 0; b < 4; ++b) {
+                const long j = j0 + tx * 4 + b;
+                double g = 0.0;
+                if (i < n && j < m) {
+                    if (FUSED) {
+                        if (j <= i) {
+                            double aa = 0.0;
+                            for (int d = 0; d < Dy; ++d) aa = fma(alpha[i * Dy + d], alpha[j * Dy + d], aa);
+                            g = 0.5 * (sc * aa - (double)Dy * G[i * ldg + j]);
+                            if (j < i) g *= 2.0;
+                        }
+                    } else {
+                        g = G[i * ldg + j];
+                    }
+                    if (Mul) g *= Mul[i * ldm + j];
+                }
+                if (PER) {
+                    const double k = kp.variance * exp(-0.5 * s[a][b]);
+                    a_var = fma(g, k, a_var);
+                    gw[a][b] = g * k;
+                } else {
+                    double k, dk_or, dk_a;
+                    ratquad_all(kp.variance, kp.power, s[a][b], k, dk_or, dk_a);
+                    a_var = fma(g, k, a_var);
+                    a_pow = fma(g, dk_a, a_pow);
+                    if (!kp.ard) a_iso = fma(g, dk_or * s[a][b], a_iso);
+                    gw[a][b] = g * dk_or;
+                }
+            }
+        }
+        if (!PER && !FUSED && Hout) {   // H = dL_dK (dK/dr) / r for the gradients_X reductions, as in k_grad
+#pragma unroll
+            for (int a = 0; a < 4; ++a) {
+                const long i = i0 + ty * 4 + a;
+#pragma unroll
+                for (int b = 0; b < 4; ++b) {
+                    const long j = j0 + tx * 4 + b;
+                    if (i < n && j < m) Hout[i * ldh + j] = gw[a][b];
+                }
+            }
+        }
+        if (qcnt > 0) {
+            if (last_q0 != q_off) {
+                __syncthreads();
+                stage_x(Xt1, ld1, i0, q_off, qcnt, si, t);
+                stage_xj(Xt2, ld2, j0, q_off, qcnt, sj, t);
+                __syncthreads();
+            }
+#pragma unroll
+            for (int q = 0; q < KDC; ++q) {
+                if (q < qcnt) {
+                    const d4 xi = *reinterpret_cast<const d4*>(si + q * KT + ty * 4);
+                    const d4 xj = ld_xj(sj, q, tx);
+                    if (PER) {
+                        const double pt = kp.pw[q_off + q];
+                        double s1 = 0.0, s2 = 0.0;
+#pragma unroll
+                        for (int a = 0; a < 4; ++a)
+#pragma unroll
+                            for (int b = 0; b < 4; ++b) {
+                                const double dl = (xi[a] - xj[b]) * pt;
+                                double sn, cs;
+                                sincos(dl, &sn, &cs);
+                                s1 = fma(gw[a][b], sn * cs * dl, s1);
+                                s2 = fma(gw[a][b], sn * sn, s2);
+                            }
+                        a1[q] += s1;
+                        a2[PER ? q : 0] += s2;
+                    } else {
+                        double s1 = 0.0;
+#pragma unroll
+                        for (int a = 0; a < 4; ++a)
+#pragma unroll
+                            for (int b = 0; b < 4; ++b) {
+                                const double d = xi[a] - xj[b];
+                                s1 = fma(gw[a][b], d * d, s1);
+                            }
+                        a1[q] += s1;
+                    }
+                }
+            }
+        }
+    }
+    double* outA = partA + (long)blockIdx.x * GP_STRIDE;
+    double* outB = partB + (long)blockIdx.x * GP_STRIDE;
+    auto block_sum = [&](double v) -> double {
+        __syncthreads();
+        red[t] = v;
+        __syncthreads();
+        for (int s = 128; s > 0; s >>= 1) {
+            if (t < s) red[t] += red[t + s];
+            __syncthreads();
+        }
+        return red[0];
+    };
+    const double sv = block_sum(a_var);
+    if (t == 0) outA[0] = sv;
+    if (!PER) {
+        const double sp = block_sum(a_pow);
+        if (t == 0) outB[0] = sp;
+        if (!kp.ard) {
+            const double sl = block_sum(a_iso);
+            if (t == 0) outA[1] = sl;
+        }
+    }
+#pragma unroll
+    for (int q = 0; q < KDC; ++q) {
+        if (q < qcnt) {
+            const double s1 = block_sum(a1[q]);
+            if (t == 0) outA[2 + q] = s1;
+            if (PER) {
+                const double s2 = block_sum(a2[PER ? q : 0]);
+                if (t == 0) outB[2 + q] = s2;
+            }
+        }
+    }
+}
+
+static void launch_grad_ext(hipStream_t st, bool fused, KernParams kp, const double* Xt1, long ld1, long n, const double* Xt2,
+                            long ld2, long m, const double* G, long ldg, const double* alpha, int Dy, long ntiles, int ntc,
+                            double* partials, double* Hout, long ldh, const double* aa_scale, const double* Mul, long ldm) {
+    const int nb = pick_grad_blocks(ntiles);
+    const int groups = (kp.D + KDC - 1) / KDC;
+    const bool perdim = kp.kind == KIND_STDPER || kp.ard;
+    double* partB = partials + (long)groups * nb * GP_STRIDE;
+    for (int q_off = 0, gidx = 0; q_off < kp.D; q_off += KDC, ++gidx) {
+        if (!perdim && gidx > 0) break;
+        double* pa = partials + (long)gidx * nb * GP_STRIDE;
+        double* pb = partB + (long)gidx * nb * GP_STRIDE;
+        // Hout may alias G (in place): only the LAST group launch writes it
+        double* h = (!perdim || q_off + KDC >= kp.D) ? Hout : nullptr;
+        const dim3 g((unsigned)nb), b(256);
+        if (kp.kind == KIND_RATQUAD) {
+            if (fused)
+                hipLaunchKernelGGL((k_grad_ext<true, KIND_RATQUAD>), g, b, 0, st, kp, Xt1, ld1, n, Xt2, ld2, m, G, ldg, alpha, Dy,
+                                   q_off, ntiles, ntc, pa, pb, nullptr, 0, aa_scale, Mul, ldm);
+            else
+                hipLaunchKernelGGL((k_grad_ext<false, KIND_RATQUAD>), g, b, 0, st, kp, Xt1, ld1, n, Xt2, ld2, m, G, ldg, nullptr, 0,
+                                   q_off, ntiles, ntc, pa, pb, h, ldh, nullptr, nullptr, 0);
+        } else if (kp.kind == KIND_STDPER) {
+            if (fused)
+                hipLaunchKernelGGL((k_grad_ext<true, KIND_STDPER>), g, b, 0, st, kp, Xt1, ld1, n, Xt2, ld2, m, G, ldg, alpha, Dy,
+                                   q_off, ntiles, ntc, pa, pb, nullptr, 0, aa_scale, Mul, ldm);
+            else
+                hipLaunchKernelGGL((k_grad_ext<false, KIND_STDPER>), g, b, 0, st, kp, Xt1, ld1, n, Xt2, ld2, m, G, ldg, nullptr, 0,
+                                   q_off, ntiles, ntc, pa, pb, nullptr, 0, nullptr, nullptr, 0);
+        }
+    }
+}
+
+// StdPeriodic dK/dx as a row reduction (see internal.h).  Block = 64 rows x 4 column lanes; the block walks every 64-column
+// tile, the covariance of each pair is formed over all dimensions first (chunks of 32), then the dimensions of the group
+// q_off .. q_off + 31 are accumulated.  The four lanes of a row are combined in fixed order: bit reproducible.
+__global__ __launch_bounds__(256) void k_periodic_gradx(KernParams kp, const double* __restrict__ Xt1, long ld1, long n,
+                                                        const double* __restrict__ Xt2, long ld2, long m,
+                                                        const double* __restrict__ W, long ldw, int wt, int q_off,
+                                                        double* __restrict__ out) {
+    __shared__ double si[KDC * KT];
+    __shared__ double sj[KDC * KT];
+    __shared__ double red[4][KT];
+    const int t = threadIdx.x, r = t & 63, l = t >> 6;
+    const long i0 = (long)blockIdx.x * KT, i = i0 + r;
+    const int qcnt = (kp.D - q_off < KDC) ? (kp.D - q_off) : KDC;
+    const double* __restrict__ pt = kp.pw;
+    const double* __restrict__ il = kp.pw + kp.D;
+    double acc[KDC];
+#pragma unroll
+    for (int q = 0; q < KDC; ++q) acc[q] = 0.0;
+    for (long j0 = 0; j0 < m; j0 += KT) {
+        double s[16];
+#pragma unroll
+        for (int c = 0; c < 16; ++c) s[c] = 0.0;
+        int last_q0 = -1;
+        for (int q0 = 0; q0 < kp.D; q0 += KDC) {
+            const int qc = (kp.D - q0 < KDC) ? (kp.D - q0) : KDC;
+            __syncthreads();
+            stage_x(Xt1, ld1, i0, q0, qc, si, t);
+            stage_x(Xt2, ld2, j0, q0, qc, sj, t);
+            __syncthreads();
+            for (int q = 0; q < qc; ++q) {
+                const double xi = si[q * KT + r], p = pt[q0 + q], w = il[q0 + q];
+#pragma unroll
+                for (int c = 0; c < 16; ++c) {
+                    const double sn = sin((xi - sj[q * KT + 4 * c + l]) * p) * w;
+                    s[c] = fma(sn, sn, s[c]);
+                }
+            }
+            last_q0 = q0;
+        }
+        // weights W(i, j) K(i, j)
+#pragma unroll
+        for (int c = 0; c < 16; ++c) {
+            const long j = j0 + 4 * c + l;
+            double wk = 0.0;
+            if (i < n && j < m) wk = (wt ? W[j * ldw + i] : W[i * ldw + j]) * kp.variance * exp(-0.5 * s[c]);
+            s[c] = wk;
+        }
+        if (last_q0 != q_off) {
+            __syncthreads();
+            stage_x(Xt1, ld1, i0, q_off, qcnt, si, t);
+            stage_x(Xt2, ld2, j0, q_off, qcnt, sj, t);
+            __syncthreads();
+        }
+#pragma unroll
+        for (int q = 0; q < KDC; ++q) {
+            if (q < qcnt) {
+                const double xi = si[q * KT + r], p = pt[q_off + q];
+                double a = 0.0;
+#pragma unroll
+                for (int c = 0; c < 16; ++c) {
+                    double sn, cs;
+                    sincos((xi - sj[q * KT + 4 * c + l]) * p, &sn, &cs);
+                    a = fma(s[c], 2.0 * sn * cs, a);
+                }
+                acc[q] += a;
+            }
+        }
+    }
+#pragma unroll
+    for (int q = 0; q < KDC; ++q) {
+        if (q < qcnt) {
+            __syncthreads();
+            red[l][r] = acc[q];
+            __syncthreads();
+            if (l == 0 && i < n) out[i * kp.D + q_off + q] = (red[0][r] + red[1][r]) + (red[2][r] + red[3][r]);
+        }
+    }
+}
+
+void launch_periodic_gradx(hipStream_t st, KernParams kp, const double* Xt1, long ld1, long n, const double* Xt2, long ld2,
+                           long m, const double* W, long ldw, int wt, double* out) {
+    const unsigned nbr = (unsigned)((n + KT - 1) / KT);
+    for (int q_off = 0; q_off < kp.D; q_off += KDC)
+        hipLaunchKernelGGL(k_periodic_gradx, dim3(nbr), dim3(256), 0, st, kp, Xt1, ld1, n, Xt2, ld2, m, W, ldw, wt, q_off, out);
 }

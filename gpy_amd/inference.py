@@ -12,7 +12,7 @@ the same `numpy.linalg.LinAlgError` messages.
 import numpy as np
 
 from . import _lib
-from .kern import CombinationKernel, Stationary
+from .kern import DEVICE_KERNELS, CombinationKernel
 from .lazy import ArrayIdentity, DeviceResult, kernel_signature
 from .likelihoods import Gaussian
 from .posterior import PosteriorExact, StudentTPosterior
@@ -160,7 +160,7 @@ class ExactGaussianInference(object):
         R = _lib.f64(Y) if mean_function is None else _lib.f64(Y - mean_function.f(X))
         n = X.shape[0]
         is_sum = isinstance(kern, CombinationKernel)
-        fused = K is None and (isinstance(kern, Stationary) or is_sum)
+        fused = K is None and (isinstance(kern, DEVICE_KERNELS) or is_sum)
         Xdev = kern._slice_X(X) if fused else _lib.f64(X)
         if self._state is None:
             self._state = _DeviceState(self.device)
@@ -250,7 +250,7 @@ class ExactStudentTInference(object):
 
     def inference(self, kern, X, Y, nu, mean_function=None, K=None):
         from scipy.special import digamma
-        if K is not None or not isinstance(kern, (Stationary, CombinationKernel)):
+        if K is not None or not isinstance(kern, DEVICE_KERNELS + (CombinationKernel,)):
             raise NotImplementedError("the MI355X Student-t path evaluates gpy_amd kernels on the device")
         X = np.asarray(X)
         Y = np.asarray(Y, dtype=np.float64)

@@ -270,6 +270,173 @@ class OU(Exponential):
         super(OU, self).__init__(input_dim, variance, lengthscale, ARD, active_dims, name, **kw)
 
 
+class RatQuad(Stationary):
+    """Rational quadratic k(r) = variance (1 + r^2/2)^-power (reference `stationary.py:747-802`): the stationary
+    machinery plus a third parameter, `power`, linked after the lengthscale (`:757-760`) and reduced on the device in
+    the same gradient pass (`dK/dpower = -K log1p(r^2/2)`, `:790-798`)."""
+    kind = "ratquad"
+    _gpy_class = "GPy.kern.RatQuad"
+
+    def __init__(self, input_dim, variance=1., lengthscale=None, power=2., ARD=False, active_dims=None, name="RatQuad",
+                 **kw):
+        super(RatQuad, self).__init__(input_dim, variance, lengthscale, ARD, active_dims, name, **kw)
+        self.power = Param("power", power)
+        assert self.power.size == 1
+        self.link_parameter(self.power)
+
+    def _theta(self):
+        return np.concatenate([super(RatQuad, self)._theta(), [float(self.power.values[0])]])
+
+    def _install_gradients(self, g):
+        super(RatQuad, self)._install_gradients(g[:-1])
+        self.power.gradient = g[-1]
+
+    def update_gradients_diag(self, dL_dKdiag, X):
+        """(reference `stationary.py:800-802`)"""
+        super(RatQuad, self).update_gradients_diag(dL_dKdiag, X)
+        self.power.gradient = 0.
+
+    def reset_gradients(self):
+        super(RatQuad, self).reset_gradients()
+        self.power.gradient = 0.
+
+    def to_dict(self):
+        d = super(RatQuad, self).to_dict()
+        d["power"] = self.power.values.tolist()
+        return d
+
+
+class StdPeriodic(Parameterized):
+    """Standard periodic kernel k(x, y) = variance exp(-1/2 sum_q (sin(pi (x_q - y_q) / T_q) / l_q)^2) (reference
+    `GPy/kern/src/standard_periodic.py:15-133`).  Not stationary in GPy's class sense (no function of r), but it runs
+    on the same device paths: its own K-build and gradient kernels (C-ABI kind `MI355GP_STDPERIODIC`) and a row
+    reduction for `gradients_X`.  Parameters are linked as in the reference: variance, period, lengthscale; `ARD1` /
+    `ARD2` give one period / lengthscale per input dimension."""
+    kind = "stdperiodic"
+    _gpy_class = "GPy.kern.StdPeriodic"
+    _support_GPU = True
+
+    def __init__(self, input_dim, variance=1., period=None, lengthscale=None, ARD1=False, ARD2=False, active_dims=None,
+                 name="std_periodic", useGPU=True, device=0):
+        super(StdPeriodic, self).__init__(name)
+        self.input_dim = int(input_dim)
+        self.device = device
+        self.useGPU = True
+        if active_dims is None:
+            active_dims = np.arange(self.input_dim)
+        self.active_dims = np.atleast_1d(np.asarray(active_dims, dtype=np.int_))
+        assert self.active_dims.size == self.input_dim, "input_dim=%d does not match len(active_dims)=%d" % (
+            self.input_dim, self.active_dims.size)
+        self.ARD1, self.ARD2 = bool(ARD1), bool(ARD2)          # standard_periodic.py:56-88
+        if not self.ARD1:
+            if period is not None:
+                period = np.asarray(period, dtype=float)
+                assert period.size == 1, "Only one period needed for non-ARD kernel"
+            else:
+                period = np.ones(1)
+        else:
+            if period is not None:
+                period = np.asarray(period, dtype=float)
+                assert period.size == self.input_dim, "bad number of periods"
+            else:
+                period = np.ones(self.input_dim)
+        if not self.ARD2:
+            if lengthscale is not None:
+                lengthscale = np.asarray(lengthscale, dtype=float)
+                assert lengthscale.size == 1, "Only one lengthscale needed for non-ARD kernel"
+            else:
+                lengthscale = np.ones(1)
+        else:
+            if lengthscale is not None:
+                lengthscale = np.asarray(lengthscale, dtype=float)
+                assert lengthscale.size == self.input_dim, "bad number of lengthscales"
+            else:
+                lengthscale = np.ones(self.input_dim)
+        self.variance = Param("variance", variance)
+        assert self.variance.size == 1, "Variance size must be one"
+        self.period = Param("period", period)
+        self.lengthscale = Param("lengthscale", lengthscale)
+        self.link_parameters(self.variance, self.period, self.lengthscale)
+        self._K_cache = _KCache(limit=3)
+
+    @property
+    def ARD(self):
+        """the C-ABI's `ard` of this kind: bit 0 = ARD1, bit 1 = ARD2"""
+        return int(self.ARD1) | (int(self.ARD2) << 1)
+
+    def _theta(self):
+        return np.concatenate([[float(self.variance.values[0])], np.asarray(self.period.values, dtype=float).ravel(),
+                               np.asarray(self.lengthscale.values, dtype=float).ravel()])
+
+    # slicing, the cached K, Kdiag, the fused / device gradients and gradients_X are the stationary kernels' (they only go
+    # through kind / ARD / _theta)
+    __getstate__ = Stationary.__getstate__
+    _slice_X = Stationary._slice_X
+    K = Stationary.K
+    Kdiag = Stationary.Kdiag
+    update_gradients_full = Stationary.update_gradients_full
+    gradients_X = Stationary.gradients_X
+
+    def _install_gradients(self, g):
+        npr = self.period.size
+        self.variance.gradient = g[0]
+        self.period.gradient = g[1:1 + npr] if self.ARD1 else g[1]
+        self.lengthscale.gradient = g[1 + npr:] if self.ARD2 else g[1 + npr]
+
+    def update_gradients_diag(self, dL_dKdiag, X):
+        """(reference `standard_periodic.py:536-540`)"""
+        self.variance.gradient = np.sum(dL_dKdiag)
+        self.period.gradient = 0.
+        self.lengthscale.gradient = 0.
+
+    def reset_gradients(self):
+        self.variance.gradient = 0.
+        self.period.gradient = np.zeros(self.input_dim) if self.ARD1 else 0.
+        self.lengthscale.gradient = np.zeros(self.input_dim) if self.ARD2 else 0.
+
+    def gradients_X_diag(self, dL_dKdiag, X):
+        """(reference `standard_periodic.py:582-583`)"""
+        return np.zeros(np.asarray(X).shape)
+
+    def input_sensitivity(self, summarize=True):
+        """(reference `standard_periodic.py:585-586`)"""
+        return float(self.variance.values[0]) * np.ones(self.input_dim) / np.asarray(self.lengthscale.values) ** 2
+
+    def __add__(self, other):
+        return Add([self, other])
+
+    def __mul__(self, other):
+        return Prod([self, other])
+
+    def to_dict(self):
+        """(reference `standard_periodic.py:96-111`)"""
+        return {"class": self._gpy_class, "name": self.name, "input_dim": self.input_dim,
+                "active_dims": self.active_dims.tolist(), "variance": self.variance.values.tolist(),
+                "period": self.period.values.tolist(), "lengthscale": self.lengthscale.values.tolist(),
+                "ARD1": self.ARD1, "ARD2": self.ARD2, "useGPU": True}
+
+    @classmethod
+    def from_dict(cls, d):
+        d = dict(d)
+        d.pop("class", None)
+        d.pop("useGPU", None)
+        return cls(**d)
+
+    copy = Stationary.copy
+
+
+# kernels the exact-GP device path evaluates as one part (the fused inference call takes them alone or in Add / Prod)
+DEVICE_KERNELS = (Stationary, StdPeriodic)
+# kinds only the exact path has (the sparse and grid paths reject them)
+EXACT_ONLY_KINDS = ("ratquad", "stdperiodic")
+
+
+def exact_only_leaves(kern):
+    """names of the kernels in `kern` that only the exact-GP path evaluates"""
+    leaves = kern.leaves() if isinstance(kern, CombinationKernel) else [kern]
+    return [type(k).__name__ for k in leaves if getattr(k, "kind", None) in EXACT_ONLY_KINDS]
+
+
 class Static(Parameterized):
     """White / Bias (reference `GPy/kern/src/static.py:10-60`): one `variance` parameter, no input dependence."""
     kind = None
@@ -399,8 +566,8 @@ class Add(CombinationKernel):
         flat = []
         for p in parts:
             flat.extend(p.parts if isinstance(p, Add) else [p])          # add.py:24-33 flattens nested sums
-        assert all(isinstance(p, (Stationary, Static, Prod)) for p in flat), \
-            "Add supports stationary, White, Bias and Prod parts"
+        assert all(isinstance(p, (Stationary, StdPeriodic, Static, Prod)) for p in flat), \
+            "Add supports stationary, StdPeriodic, White, Bias and Prod parts"
         super(Add, self).__init__(flat, name)
 
     def part_specs(self):
@@ -455,7 +622,8 @@ class Prod(CombinationKernel):
         flat = []
         for k in kernels:
             flat.extend(k.parts if isinstance(k, Prod) else [k])
-        assert all(isinstance(k, (Stationary, Static)) for k in flat), "Prod supports stationary, White and Bias factors"
+        assert all(isinstance(k, (Stationary, StdPeriodic, Static)) for k in flat), \
+            "Prod supports stationary, StdPeriodic, White and Bias factors"
         super(Prod, self).__init__(flat, name)
 
     def part_specs(self):
@@ -515,4 +683,4 @@ class Prod(CombinationKernel):
 
 
 KERNEL_CLASSES = {"rbf": RBF, "expquad": ExpQuad, "matern52": Matern52, "matern32": Matern32, "exponential": Exponential,
-                  "white": White, "bias": Bias}
+                  "white": White, "bias": Bias, "ratquad": RatQuad, "stdperiodic": StdPeriodic}

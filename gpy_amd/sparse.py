@@ -198,7 +198,11 @@ class VarDTC(object):
 
     def inference(self, kern, X, Z, likelihood, Y, Y_metadata=None, mean_function=None, precision=None, Lm=None,
                   dL_dKmm=None, psi0=None, psi1=None, psi2=None, Z_tilde=None):
-        from .kern import Add, Prod, White
+        from .kern import Add, Prod, White, exact_only_leaves
+        new_kinds = exact_only_leaves(kern)
+        if new_kinds:
+            raise NotImplementedError("the MI355X sparse path does not evaluate %s kernels (the exact GPRegression path does)"
+                                      % ", ".join(sorted(set(new_kinds))))
         # stationary kernels, products (Prod, reference `prod.py:58-99`) of stationary / Bias factors, and sums (Add) of those
         # and of White / Bias parts
         def _prod_ok(k):

@@ -25,7 +25,17 @@ extern "C" {
 typedef struct mi355gp_ctx mi355gp_ctx;
 
 enum { MI355GP_RBF = 0, MI355GP_MATERN52 = 1, MI355GP_MATERN32 = 2, MI355GP_EXPONENTIAL = 3,
-       MI355GP_WHITE = 4, MI355GP_BIAS = 5 /* static kernels, only as parts of a sum (kern/src/static.py:63-98,151-173) */ };
+       MI355GP_WHITE = 4, MI355GP_BIAS = 5 /* static kernels, only as parts of a sum (kern/src/static.py:63-98,151-173) */,
+       MI355GP_RATQUAD = 6, MI355GP_STDPERIODIC = 7 };
+
+/* The exact-GP entry points (single kind and part lists; not the sparse or grid paths) also take
+ *   MI355GP_RATQUAD      k = var (1 + r^2/2)^-power (kern/src/stationary.py:747-802, GPy.kern.RatQuad);
+ *                        theta = [variance, lengthscale (1, or n_active if ard), power]  (link order :757-760)
+ *   MI355GP_STDPERIODIC  k = var exp(-1/2 sum_q (sin(pi (x_q - x'_q) / T_q) / l_q)^2) (kern/src/standard_periodic.py:15-133,
+ *                        GPy.kern.StdPeriodic); theta = [variance, period (1 or n_active), lengthscale (1 or n_active)]
+ *                        (:56-94); `ard` is a bitmask: bit 0 = ARD1 (one period per dimension), bit 1 = ARD2 (one
+ *                        lengthscale per dimension)
+ * Gradients come back in theta order.  Both have K(x, x) = variance.  Period, lengthscale and power must be positive. */
 
 /* One part of a sum-of-products kernel expression (GPy.kern.Add, kern/src/add.py:58-84; GPy.kern.Prod,
  * kern/src/prod.py:58-99).  theta = [variance, lengthscale (1, or n_active if ard)] (static kinds: [variance]);
@@ -95,13 +105,15 @@ int mi355gp_kern_K(int device, int kind, int ard, const double* theta, const dou
 int mi355gp_kern_Kdiag(int kind, const double* theta, int64_t N, double* out);
 /* dL/dtheta from a caller-supplied dL_dK (N x M, row-major, need not be symmetric).
  * Replaces Stationary.update_gradients_full (kern/src/stationary.py:193-243) incl. the native
- * lengthscale_grads loop (kern/src/stationary_cython.pyx:53-62).  dtheta_out: 1 + (ard ? D : 1). */
+ * lengthscale_grads loop (kern/src/stationary_cython.pyx:53-62).  dtheta_out: 1 + (ard ? D : 1); RatQuad / StdPeriodic:
+ * as long as their theta (RatQuad.update_gradients_full stationary.py:790-798, StdPeriodic standard_periodic.py:501-526). */
 int mi355gp_update_gradients_full(int device, int kind, int ard, const double* theta, const double* dL_dK,
                                   const double* X, int64_t N, const double* X2, int64_t M, int D,
                                   double* dtheta_out);
 
 /* dL/dX (N x D) from dL_dK (N x M): Stationary.gradients_X (kern/src/stationary.py:245-252,330-358, native loop
- * kern/src/stationary_utils.c:1-14).  X2 == NULL: the symmetric form (tmp + tmp^T against X itself).  Any D (the reductions run in groups of 32 dimensions). */
+ * kern/src/stationary_utils.c:1-14).  X2 == NULL: the symmetric form (tmp + tmp^T against X itself).  Any D (the reductions run in groups of 32 dimensions).
+ * StdPeriodic: StdPeriodic.gradients_X (kern/src/standard_periodic.py:574-580), a row reduction over X2. */
 int mi355gp_gradients_X(int device, int kind, int ard, const double* theta, const double* dL_dK, const double* X,
                         int64_t N, const double* X2, int64_t M, int D, double* out);
 
