@@ -9,24 +9,25 @@ HIP kernel in gpy_amd/csrc.  No PyTorch, no NumPy fallback: without an MI355X th
 from . import _lib
 from ._lib import MI355GPError, build, device_count
 from .inference import ExactGaussianInference, ExactStudentTInference
-from .kern import OU, RBF, Add, Prod, Bias, ExpQuad, Exponential, Matern32, Matern52, RatQuad, Stationary, StdPeriodic, White
-from .likelihoods import Gaussian, HeteroscedasticGaussian
-from .models import GP, GPHeteroscedasticRegression, GPRegression
+from .kern import (OU, RBF, Add, Prod, Bias, Coregionalize, ExpQuad, Exponential, Matern32, Matern52, RatQuad, Stationary,
+                   StdPeriodic, White)
+from .likelihoods import Gaussian, HeteroscedasticGaussian, MixedNoise
+from .models import GP, GPCoregionalizedRegression, GPHeteroscedasticRegression, GPRegression
 from .posterior import PosteriorExact, StudentTPosterior
 from .sparse import SparseGP, SparseGPRegression, VarDTC
 
-__all__ = ["RBF", "OU", "ExpQuad", "HeteroscedasticGaussian", "StudentTPosterior", "Matern52", "Matern32", "Exponential", "RatQuad", "StdPeriodic", "Stationary", "White", "Bias", "Add", "Prod", "Gaussian", "ExactGaussianInference", "ExactStudentTInference",
-           "PosteriorExact", "GP", "GPRegression", "GPHeteroscedasticRegression", "VarDTC", "SparseGP", "SparseGPRegression", "MI355GPError", "build", "device_count"]
+__all__ = ["RBF", "OU", "ExpQuad", "HeteroscedasticGaussian", "StudentTPosterior", "Matern52", "Matern32", "Exponential", "RatQuad", "StdPeriodic", "Coregionalize", "MixedNoise", "Stationary", "White", "Bias", "Add", "Prod", "Gaussian", "ExactGaussianInference", "ExactStudentTInference",
+           "PosteriorExact", "GP", "GPRegression", "GPHeteroscedasticRegression", "GPCoregionalizedRegression", "VarDTC", "SparseGP", "SparseGPRegression", "MI355GPError", "build", "device_count"]
 
 # GPy's import paths, so that `import gpy_amd as GPy` reads like the reference on this path:
 #   GPy.kern.RBF, GPy.likelihoods.Gaussian, GPy.models.GPRegression / SparseGPRegression / GPHeteroscedasticRegression,
 #   GPy.core.GP / SparseGP, GPy.inference.latent_function_inference.ExactGaussianInference / VarDTC
-from . import inference, kern, likelihoods, linalg, models, sparse  # noqa: E402
+from . import inference, kern, likelihoods, linalg, models, sparse, util  # noqa: E402
 import types as _types  # noqa: E402
 
 models.SparseGPRegression = SparseGPRegression
 core = _types.SimpleNamespace(GP=GP, SparseGP=SparseGP)
-util = _types.SimpleNamespace(linalg=linalg)
+likelihoods.mixed_noise = _types.SimpleNamespace(MixedNoise=MixedNoise)
 inference.latent_function_inference = _types.SimpleNamespace(
     ExactGaussianInference=ExactGaussianInference, ExactStudentTInference=ExactStudentTInference, VarDTC=VarDTC,
     PosteriorExact=PosteriorExact, StudentTPosterior=StudentTPosterior,

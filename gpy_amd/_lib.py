@@ -15,11 +15,14 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("MI355GP_LIB") or os.path.join(_HERE, "libmi355gp.so")
 CSRC = os.path.join(_HERE, "csrc")
 
-KIND_IDS = {"rbf": 0, "matern52": 1, "matern32": 2, "exponential": 3, "white": 4, "bias": 5, "ratquad": 6, "stdperiodic": 7}
+KIND_IDS = {"rbf": 0, "matern52": 1, "matern32": 2, "exponential": 3, "white": 4, "bias": 5, "ratquad": 6, "stdperiodic": 7,
+            "coregionalize": 8}
 
 
 def ard_id(kind, ARD):
-    """`ard` of the C-ABI: a flag, or for StdPeriodic the bitmask ARD1 | ARD2 << 1"""
+    """`ard` of the C-ABI: a flag, for StdPeriodic the bitmask ARD1 | ARD2 << 1, for Coregionalize the number of outputs"""
+    if kind == "coregionalize":
+        return int(ARD)
     return int(ARD) & 3 if kind == "stdperiodic" else int(bool(ARD))
 
 

@@ -36,6 +36,7 @@ void mi355gp_set_error(const char* fmt, ...) {
     } while (0)
 
 #define GP_STRIDE 34
+#define COREG_REC 256          // doubles of one Coregionalize part's S (P x P, P <= 16)
 #define LOG_2_PI 1.8378770664093454836
 
 // Scoped device allocation for the stateless entry points: every early return (HIP_CHECK) releases what was acquired.
@@ -99,6 +100,13 @@ struct mi355gp_ctx {
     // schedule switches set through mi355gp_set_option (INT_MIN: the process default that factor_ws_alloc read)
     int opt[MI355GP_OPT_NUM];
     double* dGradOutAll = nullptr;      // = dPack + offGrad: [part][groups][GP_STRIDE]
+    // Coregionalize (kind 8) parts: the P x P partial records of the bucketed gradient (allocated with the first such part),
+    // the S of every part in the result block at offCoreg ([part][256], behind diag; copied only when a kind-8 part is present),
+    // and a host copy of the training output-index column last validated (hIdxCol: its input column, -1 none)
+    double* dCoregPart = nullptr;
+    size_t offCoreg = 0;
+    std::vector<double> hIdx;
+    int hIdxCol = -1;
 };
 
 // (re)applies the context's option overrides to its factorisation workspace (after every factor_ws_alloc and set_option)
@@ -138,7 +146,7 @@ static void free_data(mi355gp_ctx* c) {
     drop_graph(c);                                            // every node holds pointers into the buffers freed below
     free_parts(c);
     double** ptrs[] = {&c->dX, &c->dR, &c->dXt, &c->dInvLs, &c->dNoise, &c->A, &c->B, &c->C, &c->Mbuf,
-                       &c->dTmp, &c->dTrmvPart, &c->dGradPart, &c->dGradOut, &c->dPack};
+                       &c->dTmp, &c->dTrmvPart, &c->dGradPart, &c->dGradOut, &c->dPack, &c->dCoregPart};
     for (auto p : ptrs) {
         if (*p) (void)hipFree(*p);
         *p = nullptr;
@@ -146,6 +154,8 @@ static void free_data(mi355gp_ctx* c) {
     if (c->hPack) (void)hipHostFree(c->hPack);
     c->hPack = nullptr;
     c->dAlpha = c->dScal = c->dDiag = c->dGradOutAll = nullptr;      // views into dPack
+    c->hIdx.clear();
+    c->hIdxCol = -1;
     factor_ws_free(&c->ws);
     c->have_factor = c->have_kernel = false;
 }
@@ -244,7 +254,8 @@ int mi355gp_set_data(mi355gp_ctx* c, const double* X, int64_t N, int D, const do
     c->offExt = c->offGrad + (size_t)16 * groups * GP_STRIDE;
     c->offAlpha = c->offExt + (size_t)16 * groups * GP_STRIDE;
     c->offDiag = c->offAlpha + (size_t)N * Dy;
-    c->packDoubles = c->offDiag + (size_t)N;
+    c->offCoreg = c->offDiag + (size_t)N;
+    c->packDoubles = c->offCoreg + (size_t)16 * COREG_REC;
     HIP_CHECK(hipMalloc(&c->dPack, sizeof(double) * c->packDoubles));
     HIP_CHECK(hipHostMalloc(&c->hPack, sizeof(double) * c->packDoubles, hipHostMallocDefault));
     c->dScal = c->dPack;
@@ -269,6 +280,26 @@ int mi355gp_set_targets(mi355gp_ctx* c, const double* R, int Dy) {
 
 // ---------------------------------------------------------------------------------------------------
 static bool is_ext_kind(int kind) { return kind == MI355GP_RATQUAD || kind == MI355GP_STDPERIODIC; }
+
+// Coregionalize (kind 8, coregionalize.py:82-157): `ard` = the number of outputs P, theta = B (P x P).  Output indices are
+// values of one input column; each must be an integer in [0, P) -- checked here, on the host, before any launch reads one.
+static int coreg_check_P(int P) {
+    if (P < 1 || P > 16) {
+        mi355gp_set_error("Coregionalize (kind 8): the number of outputs (ard) must be between 1 and 16, got %d", P);
+        return -1;
+    }
+    return 0;
+}
+static int coreg_check_index(const double* x, long n, long stride, int P, const char* what) {
+    for (long i = 0; i < n; ++i) {
+        const double v = x[i * stride];
+        if (!(v >= 0.0 && v < (double)P && v == std::floor(v))) {
+            mi355gp_set_error("Coregionalize (kind 8): %s output index %.17g (row %ld) is not an integer in [0, %d)", what, v, i, P);
+            return -1;
+        }
+    }
+    return 0;
+}
 
 // RatQuad / StdPeriodic: validates theta for the active dimensions `dims` (of D input columns) and fills the input scaling
 // (inv_ls over the D columns), the StdPeriodic parameter block pw and the RatQuad power
@@ -468,6 +499,13 @@ static int run_pipeline(mi355gp_ctx* c, EngineShared* gate, bool with_kernel_gra
                     Mul = c->Mbuf;
                 }
             }
+            if (pt.kp.kind == MI355GP_COREGIONALIZE) {                  // the bucketed gradient: S (P x P) per part
+                const int P = pt.kp.ard;
+                const int nbc = launch_grad_coreg(st, true, pt.kp, pt.dXt, np, n, pt.dXt, np, n, c->C, np, c->dAlpha, c->Dy,
+                                                  c->dCoregPart, studentt_nu > 0.0 ? c->dScal + 4 : nullptr, Mul, np);
+                launch_reduce_partials(st, c->dCoregPart, nbc, P * P, c->dPack + c->offCoreg + p * COREG_REC);
+                continue;
+            }
             launch_grad_fused(st, pt.kp, pt.dXt, np, n, c->C, np, c->dAlpha, c->Dy, c->dGradPart, GP_STRIDE,
                               studentt_nu > 0.0 ? c->dScal + 4 : nullptr, Mul, np);
             for (int g = 0; g < (pt.kp.ard ? groups : 1); ++g)
@@ -481,7 +519,9 @@ static int run_pipeline(mi355gp_ctx* c, EngineShared* gate, bool with_kernel_gra
     }
     HIP_CHECK(hipEventRecord(c->ev[6], st));
     // ONE device -> pinned host copy of the prefix of the result block that the caller asked for
-    const size_t ncopy = diag_out ? c->packDoubles : (alpha_out ? c->offDiag : c->offAlpha);
+    bool coreg = false;
+    for (size_t p = 0; p < nparts; ++p) coreg = coreg || c->parts[p].kp.kind == MI355GP_COREGIONALIZE;
+    const size_t ncopy = coreg ? c->packDoubles : (diag_out ? c->offCoreg : (alpha_out ? c->offDiag : c->offAlpha));
     HIP_CHECK(hipMemcpyAsync(c->hPack, c->dPack, sizeof(double) * ncopy, hipMemcpyDeviceToHost, st));
     HIP_CHECK(hipStreamSynchronize(st));
     HIP_CHECK(hipGetLastError());
@@ -580,6 +620,12 @@ static int run_pipeline(mi355gp_ctx* c, EngineShared* gate, bool with_kernel_gra
         for (size_t p = 0; p < nparts; ++p) {
             const mi355gp_ctx::Part& pt = c->parts[p];
             const double* sp = sumsp + p * (size_t)groups * GP_STRIDE;
+            if (pt.kp.kind == MI355GP_COREGIONALIZE) {                       // S in theta (= B) order
+                const int P = pt.kp.ard;
+                memcpy(o, c->hPack + c->offCoreg + p * (size_t)COREG_REC, sizeof(double) * P * P);
+                o += P * P;
+                continue;
+            }
             if (is_ext_kind(pt.kp.kind)) {
                 o += finish_ext(pt.kp.kind, pt.ard_in, pt.theta.data(), pt.dims, sp,
                                 c->hPack + c->offExt + p * (size_t)groups * GP_STRIDE, o);
@@ -626,6 +672,42 @@ static double expression_kdiag(const mi355gp_ctx* c) {
         s += v;
     }
     return s;
+}
+
+static bool has_coreg(const mi355gp_ctx* c) {
+    for (const auto& p : c->parts)
+        if (p.kp.kind == MI355GP_COREGIONALIZE) return true;
+    return false;
+}
+// new points (M x D, host) against every Coregionalize part: their output indices must be valid
+static int coreg_check_points(const mi355gp_ctx* c, const double* Xn, int64_t M, const char* what) {
+    for (const auto& p : c->parts)
+        if (p.kp.kind == MI355GP_COREGIONALIZE)
+            if (int rc = coreg_check_index(Xn + p.kp.col, M, c->D, p.kp.ard, what)) return rc;
+    return 0;
+}
+// Kdiag of the expression at each new point when it holds Coregionalize parts (Coregionalize.Kdiag = diag(B)[idx],
+// coregionalize.py:106-107): kd[m] = sum over terms of the product of the factors' B[idx_m][idx_m] or variance
+static std::vector<double> expression_kdiag_points(const mi355gp_ctx* c, const double* Xn, int64_t M) {
+    std::vector<double> kd((size_t)M, 0.0);
+    for (int64_t m = 0; m < M; ++m) {
+        double s = 0.0;
+        for (const auto& t : c->terms) {
+            double v = 1.0;
+            for (int f : t) {
+                const mi355gp_ctx::Part& p = c->parts[(size_t)f];
+                if (p.kp.kind == MI355GP_COREGIONALIZE) {
+                    const int a = (int)Xn[m * c->D + p.kp.col], P = p.kp.ard;
+                    v *= p.theta[(size_t)(a * P + a)];
+                } else {
+                    v *= p.kp.variance;
+                }
+            }
+            s += v;
+        }
+        kd[(size_t)m] = s;
+    }
+    return kd;
 }
 
 // KernParams of a stateless RatQuad / StdPeriodic evaluation: power, and the StdPeriodic parameter block uploaded to *buf
@@ -692,14 +774,40 @@ static int prepare_parts(mi355gp_ctx* c, int nparts, const mi355gp_part* parts) 
         c->parts.resize((size_t)nparts);
         for (auto& p : c->parts) {
             HIP_CHECK(hipMalloc(&p.dXt, sizeof(double) * c->D * c->npad));
-            HIP_CHECK(hipMalloc(&p.dPw, sizeof(double) * 2 * c->D));
+            HIP_CHECK(hipMalloc(&p.dPw, sizeof(double) * std::max(2 * c->D, COREG_REC)));   // (B of a Coregionalize part)
         }
     }
     for (int i = 0; i < nparts; ++i) {
         const mi355gp_part& in = parts[i];
         mi355gp_ctx::Part& p = c->parts[(size_t)i];
-        ARG_CHECK(((in.kind >= 0 && in.kind <= 5) || is_ext_kind(in.kind)) && in.theta,
+        ARG_CHECK(((in.kind >= 0 && in.kind <= 5) || is_ext_kind(in.kind) || in.kind == MI355GP_COREGIONALIZE) && in.theta,
                   "unknown covariance kind / NULL theta in a kernel part");
+        if (in.kind == MI355GP_COREGIONALIZE) {
+            ARG_CHECK(in.n_active == 1 && in.active_dims && in.active_dims[0] >= 0 && in.active_dims[0] < c->D,
+                      "Coregionalize (kind 8): n_active must be 1 (the input column of the output index)");
+            if (int rc = coreg_check_P(in.ard)) return rc;
+            const int P = in.ard, col = in.active_dims[0];
+            for (int k = 0; k < P * P; ++k) ARG_CHECK(std::isfinite(in.theta[k]), "Coregionalize (kind 8): B is not finite");
+            if (c->hIdxCol != col) {                     // the training indices of this column, validated once per upload
+                c->hIdx.resize((size_t)c->n);
+                HIP_CHECK(hipMemcpy2D(c->hIdx.data(), sizeof(double), c->dX + col, sizeof(double) * c->D, sizeof(double), c->n,
+                                      hipMemcpyDeviceToHost));
+                c->hIdxCol = col;
+            }
+            if (int rc = coreg_check_index(c->hIdx.data(), c->n, 1, P, "training")) return rc;
+            p.dims.assign(1, col);
+            p.term = in.term;
+            p.ard_in = P;
+            p.theta.assign(in.theta, in.theta + P * P);
+            p.inv_ls.assign((size_t)c->D, 0.0);
+            p.inv_ls[(size_t)col] = 1.0;                 // the index column stays unscaled
+            p.kp = KernParams{MI355GP_COREGIONALIZE, P, c->D, in.theta[0]};
+            p.kp.col = col;
+            HIP_CHECK(hipMemcpyAsync(p.dPw, p.theta.data(), sizeof(double) * P * P, hipMemcpyHostToDevice, c->st));
+            p.kp.pw = p.dPw;
+            if (!c->dCoregPart) HIP_CHECK(hipMalloc(&c->dCoregPart, sizeof(double) * grad_num_blocks(c->n) * COREG_REC));
+            continue;
+        }
         ARG_CHECK(in.theta[0] > 0.0, "variance must be positive");
         p.dims.clear();
         if (in.active_dims && in.n_active > 0) {
@@ -907,10 +1015,74 @@ int mi355gp_fetch(mi355gp_ctx* c, int which, double* out, int fortran_order) {
 }
 
 // ---- stateless kernel-function entry points --------------------------------------------------------
+// Coregionalize (kind 8) with D = 1: X / X2 are the output-index columns themselves (read as Xt with ld = N, row 0)
+static int coreg_stateless_check(int ard, const double* theta, const double* X, int64_t N, const double* X2, int64_t M, int D) {
+    if (int rc = coreg_check_P(ard)) return rc;
+    ARG_CHECK(theta != nullptr, "theta is NULL");
+    ARG_CHECK(D == 1, "Coregionalize (kind 8): D must be 1 (the output-index column)");
+    for (int k = 0; k < ard * ard; ++k) ARG_CHECK(std::isfinite(theta[k]), "Coregionalize (kind 8): B is not finite");
+    if (int rc = coreg_check_index(X, N, 1, ard, "X")) return rc;
+    if (X2)
+        if (int rc = coreg_check_index(X2, M, 1, ard, "X2")) return rc;
+    return 0;
+}
+
+static int coreg_kern_K(int device, int P, const double* theta, const double* X, int64_t N, const double* X2, int64_t M,
+                        double* K_out) {
+    const bool sym = (X2 == nullptr);
+    if (sym) M = N;
+    DevBuf dX, dX2, dB, dK;
+    HIP_CHECK(dX.alloc(N));
+    HIP_CHECK(dB.alloc(P * P));
+    HIP_CHECK(dK.alloc(N * M));
+    HIP_CHECK(hipMemcpy(dX, X, sizeof(double) * N, hipMemcpyHostToDevice));
+    HIP_CHECK(hipMemcpy(dB, theta, sizeof(double) * P * P, hipMemcpyHostToDevice));
+    if (!sym) {
+        HIP_CHECK(dX2.alloc(M));
+        HIP_CHECK(hipMemcpy(dX2, X2, sizeof(double) * M, hipMemcpyHostToDevice));
+    }
+    KernParams kp{MI355GP_COREGIONALIZE, P, 1, theta[0]};
+    kp.pw = dB;
+    launch_kbuild_cross(0, kp, dX, N, N, sym ? (double*)dX : (double*)dX2, M, M, dK, M, 0, /*diag_same=*/sym ? 1 : 0);
+    HIP_CHECK(hipMemcpy(K_out, dK, sizeof(double) * N * M, hipMemcpyDeviceToHost));
+    HIP_CHECK(hipGetLastError());
+    return 0;
+}
+
+// S[a][b] = sum over i with idx_i = a, j with idx2_j = b of dL_dK[i][j] (every element once, no symmetric completion);
+// GPy's dL_dK_small is its transpose (coregionalize.py:130-137)
+static int coreg_update_gradients(int device, int P, const double* theta, const double* dL_dK, const double* X, int64_t N,
+                                  const double* X2, int64_t M, double* out) {
+    const bool sym = (X2 == nullptr);
+    if (sym) M = N;
+    DevBuf dX, dX2, dG, dPart, dOut;
+    HIP_CHECK(dX.alloc(N));
+    HIP_CHECK(dG.alloc(N * M));
+    HIP_CHECK(dPart.alloc((size_t)2048 * COREG_REC));
+    HIP_CHECK(dOut.alloc(P * P));
+    HIP_CHECK(hipMemcpy(dX, X, sizeof(double) * N, hipMemcpyHostToDevice));
+    HIP_CHECK(hipMemcpy(dG, dL_dK, sizeof(double) * N * M, hipMemcpyHostToDevice));
+    if (!sym) {
+        HIP_CHECK(dX2.alloc(M));
+        HIP_CHECK(hipMemcpy(dX2, X2, sizeof(double) * M, hipMemcpyHostToDevice));
+    }
+    KernParams kp{MI355GP_COREGIONALIZE, P, 1, theta[0]};
+    const int nb = launch_grad_coreg(0, false, kp, dX, N, N, sym ? (double*)dX : (double*)dX2, M, M, dG, M, nullptr, 0, dPart);
+    launch_reduce_partials(0, dPart, nb, P * P, dOut);
+    HIP_CHECK(hipMemcpy(out, dOut, sizeof(double) * P * P, hipMemcpyDeviceToHost));
+    HIP_CHECK(hipGetLastError());
+    return 0;
+}
+
 int mi355gp_kern_K(int device, int kind, int ard, const double* theta, const double* X, int64_t N,
                    const double* X2, int64_t M, int D, double* K_out) {
     ARG_CHECK(X && K_out && N > 0 && D > 0, "mi355gp_kern_K: bad arguments");
     HIP_CHECK(hipSetDevice(device));
+    if (kind == MI355GP_COREGIONALIZE) {
+        ARG_CHECK(X2 == nullptr || M > 0, "mi355gp_kern_K: M must be positive");
+        if (int rc = coreg_stateless_check(ard, theta, X, N, X2, M, D)) return rc;
+        return coreg_kern_K(device, ard, theta, X, N, X2, M, K_out);
+    }
     std::vector<double> inv_ls, pw;
     double power = 0.0;
     if (int rc = check_theta(kind, ard, theta, D, &inv_ls, &pw, &power)) return rc;
@@ -955,6 +1127,11 @@ int mi355gp_update_gradients_full(int device, int kind, int ard, const double* t
                                   double* dtheta_out) {
     ARG_CHECK(dL_dK && X && dtheta_out && N > 0 && D > 0, "mi355gp_update_gradients_full: bad arguments");
     HIP_CHECK(hipSetDevice(device));
+    if (kind == MI355GP_COREGIONALIZE) {
+        ARG_CHECK(X2 == nullptr || M > 0, "mi355gp_update_gradients_full: M must be positive");
+        if (int rc = coreg_stateless_check(ard, theta, X, N, X2, M, D)) return rc;
+        return coreg_update_gradients(device, ard, theta, dL_dK, X, N, X2, M, dtheta_out);
+    }
     std::vector<double> inv_ls, pw;
     double power = 0.0;
     if (int rc = check_theta(kind, ard, theta, D, &inv_ls, &pw, &power)) return rc;
@@ -1161,6 +1338,7 @@ int mi355gp_predict_sum(mi355gp_ctx* c, int nparts, const mi355gp_part* parts, c
     HIP_CHECK(hipSetDevice(c->device));
     EngineShared gate(c->device);
     if (int rc = prepare_parts(c, nparts, parts)) return rc;
+    if (int rc = coreg_check_points(c, Xnew, M, "prediction")) return rc;
     hipStream_t st = c->st;
     const long n = c->n, np = c->npad, D = c->D, mp = round_up(M, NB), ld2 = round_up(M, 64);
     // (re)scale the training inputs for these parameters (normally identical to the inference call's)
@@ -1179,6 +1357,14 @@ int mi355gp_predict_sum(mi355gp_ctx* c, int nparts, const mi355gp_part* parts, c
     HIP_CHECK(hipMemsetAsync(dKx, 0, sizeof(double) * np * mp, st));
     if (full_cov && var_out) HIP_CHECK(hipMemsetAsync(dVar, 0, sizeof(double) * mp * mp, st));
     const double kdiag = expression_kdiag(c);                   // Kdiag(X*): sum over terms of the product of variances
+    DevBuf dKd;                                                 // ... or per point, with Coregionalize parts
+    const bool kd_points = has_coreg(c) && !full_cov && var_out;
+    std::vector<double> kd;
+    if (kd_points) {
+        kd = expression_kdiag_points(c, Xnew, M);
+        HIP_CHECK(dKd.alloc(M));
+        HIP_CHECK(hipMemcpyAsync(dKd, kd.data(), sizeof(double) * M, hipMemcpyHostToDevice, st));
+    }
     DevBuf dScr1, dScr2;
     if (has_product(c)) {
         HIP_CHECK(dScr1.alloc(np * mp));
@@ -1205,7 +1391,8 @@ int mi355gp_predict_sum(mi355gp_ctx* c, int nparts, const mi355gp_part* parts, c
     launch_col_reduce(st, dKx, mp, n, M, c->dAlpha, c->Dy, 0.0, 0, dMu);                  // mu = Kx^T alpha
     launch_trmm_lower(st, c->B, np, dKx, mp, dTmp, mp, (int)(np / NB), (int)(mp / NB));   // tmp = L^-1 Kx
     if (!full_cov) {
-        if (var_out) launch_col_reduce(st, dTmp, mp, n, M, nullptr, 1, kdiag, 1, dVar);
+        if (var_out && kd_points) launch_col_reduce_vec(st, dTmp, mp, n, M, dKd, dVar);
+        else if (var_out) launch_col_reduce(st, dTmp, mp, n, M, nullptr, 1, kdiag, 1, dVar);
     } else if (var_out) {
         launch_gemm_tn_sq(st, dTmp, mp, np, dVar, mp, (int)(mp / NB), -1.0, 1.0);         // - tmp^T tmp
     }
@@ -1243,6 +1430,7 @@ int mi355gp_predictive_gradients_sum(mi355gp_ctx* c, int nparts, const mi355gp_p
     EngineShared gate(c->device);
     if (int rc = prepare_parts(c, nparts, parts)) return rc;
     ARG_CHECK(!has_product(c), "mi355gp_predictive_gradients: product kernels are not supported on the device");
+    ARG_CHECK(!has_coreg(c), "mi355gp_predictive_gradients: Coregionalize (kind 8) parts are not supported on the device");
     hipStream_t st = c->st;
     const long n = c->n, np = c->npad, D = c->D, Dy = c->Dy, mp = round_up(M, NB), ld2 = round_up(M, 64);
     c->kp = c->parts[0].kp;
@@ -1338,6 +1526,8 @@ int mi355gp_covariance_between_points(mi355gp_ctx* c, int nparts, const mi355gp_
     HIP_CHECK(hipSetDevice(c->device));
     EngineShared gate(c->device);
     if (int rc = prepare_parts(c, nparts, parts)) return rc;
+    if (int rc = coreg_check_points(c, X1, M1, "X1")) return rc;
+    if (int rc = coreg_check_points(c, X2, M2, "X2")) return rc;
     hipStream_t st = c->st;
     const long n = c->n, np = c->npad, D = c->D;
     const long m1p = round_up(M1, NB), m2p = round_up(M2, NB), l1 = round_up(M1, 64), l2 = round_up(M2, 64);

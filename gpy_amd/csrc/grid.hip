@@ -1613,6 +1613,7 @@ int mi355gp_grid_exact_inference(mi355gp_grid* g, int kind, int ard, const doubl
                                  double* alpha_out, double* dtheta_out, double* diag_dLdK_out, double* stage_ms) {
     ARGCHK(g && g->n > 0, "mi355gp_grid_exact_inference: set_data first");
     ARGCHK(out_scalars && theta && noise, "mi355gp_grid_exact_inference: NULL argument");
+    ARGCHK(kind != 8, "Coregionalize (kind 8) runs on the exact-GP path only, not the grid path");
     ARGCHK(kind >= 0 && kind <= 3, "unknown covariance kind");     // (the exact-only kinds 6 / 7 included)
     if (g->single) {
         double ms[MI355GP_NUM_T];

@@ -219,6 +219,8 @@ struct KernParams {
     // kinds 6 / 7 only (the kernels of the other kinds never read them)
     double power = 0.0;               // RatQuad: alpha
     const double* pw = nullptr;       // StdPeriodic, device [2 D]: pi / T_q, then 1 / l_q (0 outside the active dimensions)
+                                      // Coregionalize, device [P x P]: B (row-major; P = ard)
+    int col = 0;                      // Coregionalize only: the input row of Xt that holds the (unscaled) output index
 };
 // Xt: scaled, transposed inputs [D][ldx] (x_q / l_q); builds lower tiles of Ky = K + diag(noise + jit) into A
 // (npad x npad); rows/cols >= n get the identity.
@@ -277,6 +279,16 @@ void launch_grad_generic(hipStream_t st, KernParams kp, const double* Xt1, long 
 // (out: n x D row-major; the caller applies -pi / (2 T_q l_q^2)).  Xt1 / Xt2: unscaled, dimension-major.
 void launch_periodic_gradx(hipStream_t st, KernParams kp, const double* Xt1, long ld1, long n, const double* Xt2, long ld2,
                            long m, const double* W, long ldw, int wt, double* out);
+// Coregionalize (kind 8) bucketed gradient (k_grad_coreg): per block ONE record of P x P doubles at partials + block * P * P,
+//   S[a][b] = sum over (i, j) with idx_i = a, idx_j = b of w_ij;  fused: w = dL_dK * Mul from C = Ky^-1 / alpha / Dy / aa_scale over
+//   the lower tiles with the symmetric completion (a lower off-diagonal element adds to S[a_i][a_j] and S[a_j][a_i]);
+//   !fused: w = G (n x m, any), every element once.  Returns the number of blocks (combine with launch_reduce_partials,
+//   stride P * P: fixed order, bit reproducible).  partials: at least 2048 * P * P doubles.
+int launch_grad_coreg(hipStream_t st, bool fused, KernParams kp, const double* Xt1, long ld1, long n, const double* Xt2, long ld2,
+                      long m, const double* G, long ldg, const double* alpha, int Dy, double* partials,
+                      const double* aa_scale = nullptr, const double* Mul = nullptr, long ldm = 0);
+// out[j] = kd[j] - sum_i M[i][j]^2  (the per-point Kdiag form of launch_col_reduce mode 1)
+void launch_col_reduce_vec(hipStream_t st, const double* M, long ld, long rows, long cols, const double* kd, double* out);
 // part[split][cols][nv] = sum over a row range of M[i][j] * V(i, c); V(i, c) = V[i*sr + c*sc] plus an optional
 // all-ones column; returns the number of row splits (sum them with launch_sum_splits)
 int launch_colreduce_multi(hipStream_t st, const double* M, long ld, long rows, long cols, const double* V, long sr,

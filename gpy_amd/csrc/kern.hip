@@ -319,11 +319,20 @@ static void launch_kbuild_ext(hipStream_t st, bool sym, KernParams kp, const dou
 static void launch_grad_ext(hipStream_t st, bool fused, KernParams kp, const double* Xt1, long ld1, long n, const double* Xt2,
                             long ld2, long m, const double* G, long ldg, const double* alpha, int Dy, long ntiles, int ntc,
                             double* partials, double* Hout, long ldh, const double* aa_scale, const double* Mul, long ldm);
+// Coregionalize (kind 8): at the end of this file as well
+static void launch_kbuild_coreg(hipStream_t st, bool sym, KernParams kp, const double* Xt1, long ld1, long n, const double* Xt2,
+                                long ld2, long m, double* out, long ldo, long nrows_out, const double* noise, long noise_len,
+                                double jit, int lower_only, int add_diag, int ntc, int nblocks, int accumulate, const double* mul);
 
 void launch_kbuild_sym(hipStream_t st, KernParams kp, const double* Xt, long ldx, long n, long npad, double* A,
                        const double* noise, long noise_len, double jit, int lower_only, int add_diag, int accumulate,
                        const double* mul) {
     const int nt = (int)(npad / KT);
+    if (kp.kind == 8) {
+        launch_kbuild_coreg(st, true, kp, Xt, ldx, n, Xt, ldx, n, A, npad, npad, noise, noise_len, jit, lower_only, add_diag, nt,
+                            nt * nt, accumulate, mul);
+        return;
+    }
     if (kp.kind >= 6) {
         launch_kbuild_ext(st, true, kp, Xt, ldx, n, Xt, ldx, n, A, npad, npad, noise, noise_len, jit, lower_only, add_diag, nt,
                           nt * nt, accumulate, 0, mul);
@@ -336,6 +345,11 @@ void launch_kbuild_sym(hipStream_t st, KernParams kp, const double* Xt, long ldx
 void launch_kbuild_cross(hipStream_t st, KernParams kp, const double* Xt1, long ld1, long n, const double* Xt2,
                          long ld2, long m, double* Kout, long ldk, int accumulate, int diag_same, const double* mul) {
     const int ntr = (int)((n + KT - 1) / KT), ntc = (int)((m + KT - 1) / KT);
+    if (kp.kind == 8) {                                // (no White-like diagonal: diag_same changes nothing)
+        launch_kbuild_coreg(st, false, kp, Xt1, ld1, n, Xt2, ld2, m, Kout, ldk, n, nullptr, 0, 0.0, 0, 0, ntc, ntr * ntc, accumulate,
+                            mul);
+        return;
+    }
     if (kp.kind >= 6) {
         launch_kbuild_ext(st, false, kp, Xt1, ld1, n, Xt2, ld2, m, Kout, ldk, n, nullptr, 0, 0.0, 0, 0, ntc, ntr * ntc,
                           accumulate, diag_same, mul);
@@ -1773,4 +1787,243 @@ void launch_periodic_gradx(hipStream_t st, KernParams kp, const double* Xt1, lon
     const unsigned nbr = (unsigned)((n + KT - 1) / KT);
     for (int q_off = 0; q_off < kp.D; q_off += KDC)
         hipLaunchKernelGGL(k_periodic_gradx, dim3(nbr), dim3(256), 0, st, kp, Xt1, ld1, n, Xt2, ld2, m, W, ldw, wt, q_off, out);
+}
+
+// ------------------------------------------------------------------------------------------------
+// Coregionalize (kind 8, coregionalize.py:82-157): k(x, x') = B[idx][idx'], idx = the value of input row kp.col of Xt (staged
+// unscaled), B = kp.pw (P x P row-major, P = kp.ard <= 16).  The host validates every index before a launch; an index that is
+// not an integer in [0, P) still never reads outside B here: it yields NaN (K-build) or poisons the block's record (gradient).
+#define KIND_COREG 8
+#define COREG_PMAX 16
+
+__device__ __forceinline__ int coreg_idx(double x, int P) {
+    const int a = (int)x;
+    return ((double)a == x && a >= 0 && a < P) ? a : -1;
+}
+
+// Covariance assembly of k_kbuild (same tiling and output conventions: lower tiles, noise + jitter on the diagonal, accumulate,
+// mul, identity padding).  B lives in LDS once per block, the tile's row / column indices as integers.
+template <bool SYM>
+__global__ __launch_bounds__(256) void k_kbuild_coreg(KernParams kp, const double* __restrict__ Xt1, long ld1, long n,
+                                                      const double* __restrict__ Xt2, long ld2, long m,
+                                                      double* __restrict__ out, long ldo, long nrows_out,
+                                                      const double* __restrict__ noise, long noise_len, double jit,
+                                                      int lower_only, int add_diag, int ntc, int accumulate, const double* mul) {
+    __shared__ double sB[COREG_PMAX * COREG_PMAX];
+    __shared__ int sa[KT], sb[KT];
+    const int t = threadIdx.x, tx = t & 15, ty = t >> 4;
+    const long ti = blockIdx.x / ntc, tj = blockIdx.x % ntc;
+    if (SYM && lower_only && tj > ti) return;
+    const long i0 = ti * KT, j0 = tj * KT;
+    const int P = kp.ard;
+    for (int k = t; k < P * P; k += 256) sB[k] = kp.pw[k];
+    if (t < KT) {
+        const long i = i0 + t;
+        sa[t] = (i < n) ? coreg_idx(Xt1[(long)kp.col * ld1 + i], P) : 0;
+    } else if (t < 2 * KT) {
+        const long j = j0 + (t - KT);
+        sb[t - KT] = (j < m) ? coreg_idx(Xt2[(long)kp.col * ld2 + j], P) : 0;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int a = 0; a < 4; ++a) {
+        const long i = i0 + ty * 4 + a;
+        const int ia = sa[ty * 4 + a];
+        double v[4];
+#pragma unroll
+        for (int b = 0; b < 4; ++b) {
+            const long j = j0 + tx * 4 + b;
+            const int jb = sb[tx * 4 + b];
+            if (i < n && j < m) v[b] = (ia >= 0 && jb >= 0) ? sB[ia * P + jb] : __builtin_nan("");
+            else v[b] = (SYM && i == j && !accumulate) ? 1.0 : 0.0;
+        }
+        if (SYM) {
+            if (i < nrows_out) {
+                d4* p = reinterpret_cast<d4*>(out + i * ldo + j0 + tx * 4);
+                d4 o = (d4){v[0], v[1], v[2], v[3]};
+                if (mul) o *= *reinterpret_cast<const d4*>(mul + i * ldo + j0 + tx * 4);
+                if (add_diag && i < n) {
+                    const long d = i - (j0 + tx * 4);
+                    if (d >= 0 && d < 4) o[d] += noise[noise_len > 1 ? i : 0] + jit;
+                }
+                if (accumulate) o += *p;
+                *p = o;
+            }
+        } else if (i < n) {
+#pragma unroll
+            for (int b = 0; b < 4; ++b) {
+                const long j = j0 + tx * 4 + b;
+                if (j < m) {
+                    const double w = mul ? v[b] * mul[i * ldo + j] : v[b];
+                    out[i * ldo + j] = accumulate ? out[i * ldo + j] + w : w;
+                }
+            }
+        }
+    }
+}
+
+static void launch_kbuild_coreg(hipStream_t st, bool sym, KernParams kp, const double* Xt1, long ld1, long n, const double* Xt2,
+                                long ld2, long m, double* out, long ldo, long nrows_out, const double* noise, long noise_len,
+                                double jit, int lower_only, int add_diag, int ntc, int nblocks, int accumulate, const double* mul) {
+    const dim3 g((unsigned)nblocks), b(256);
+    if (sym)
+        hipLaunchKernelGGL((k_kbuild_coreg<true>), g, b, 0, st, kp, Xt1, ld1, n, Xt2, ld2, m, out, ldo, nrows_out, noise, noise_len,
+                           jit, lower_only, add_diag, ntc, accumulate, mul);
+    else
+        hipLaunchKernelGGL((k_kbuild_coreg<false>), g, b, 0, st, kp, Xt1, ld1, n, Xt2, ld2, m, out, ldo, nrows_out, noise,
+                           noise_len, jit, lower_only, add_diag, ntc, accumulate, mul);
+}
+
+// The bucketed gradient (see internal.h).  Per tile: the row / column indices go to LDS and two waves OR them into the masks of
+// the outputs present among the tile's rows and columns; then, for every present pair (a, b) in a fixed order, each thread sums
+// its masked 4 x 4 register elements and a fixed-order wave / block tree reduces them into the block's LDS record.  Rows sorted
+// by output (build_XY) give one pair in nearly every tile: one reduction per tile.  FUSED runs over the lower tiles; the second
+// sum d (diagonal elements, diagonal tiles only) lets S[b][a] receive the strict lower part once more: the symmetric completion.
+template <bool FUSED>
+__global__ __launch_bounds__(256) void k_grad_coreg(KernParams kp, const double* __restrict__ Xt1, long ld1, long n,
+                                                    const double* __restrict__ Xt2, long ld2, long m,
+                                                    const double* __restrict__ G, long ldg, const double* __restrict__ alpha,
+                                                    int Dy, long ntiles, int ntc, double* __restrict__ partials,
+                                                    const double* __restrict__ aa_scale, const double* __restrict__ Mul,
+                                                    long ldm) {
+    __shared__ double sacc[COREG_PMAX * COREG_PMAX];
+    __shared__ int sa[KT], sb[KT];
+    __shared__ unsigned smask[2];
+    __shared__ double red[4][2];
+    const int t = threadIdx.x, tx = t & 15, ty = t >> 4, lane = t & 63, wv = t >> 6;
+    const int P = kp.ard;
+    for (int k = t; k < P * P; k += 256) sacc[k] = 0.0;
+    const double sc = (FUSED && aa_scale) ? aa_scale[0] : 1.0;
+    bool poisoned = false;                                 // (thread 0) an index outside [0, P) was met
+
+    for (long tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+        long ti, tj;
+        if (FUSED) {
+            ti = (long)((sqrt(8.0 * (double)tile + 1.0) - 1.0) * 0.5);
+            while (ti * (ti + 1) / 2 > tile) --ti;
+            while ((ti + 1) * (ti + 2) / 2 <= tile) ++ti;
+            tj = tile - ti * (ti + 1) / 2;
+        } else {
+            ti = tile / ntc;
+            tj = tile - ti * ntc;
+        }
+        const long i0 = ti * KT, j0 = tj * KT;
+        __syncthreads();                                   // the previous tile's reads of sa / sb / smask are done
+        if (wv < 2) {
+            const long r = (wv == 0 ? i0 : j0) + lane;
+            int v = -2;                                    // -2: padding (no element), -1: an invalid index
+            if (wv == 0 && r < n) v = coreg_idx(Xt1[(long)kp.col * ld1 + r], P);
+            if (wv == 1 && r < m) v = coreg_idx(Xt2[(long)kp.col * ld2 + r], P);
+            unsigned bit = (v >= 0) ? (1u << v) : (v == -1 ? (1u << COREG_PMAX) : 0u);
+            for (int off = 32; off > 0; off >>= 1) bit |= (unsigned)__shfl_xor((int)bit, off);
+            if (wv == 0) sa[lane] = v;
+            else sb[lane] = v;
+            if (lane == 0) smask[wv] = bit;
+        }
+        double w[4][4];
+#pragma unroll
+        for (int a = 0; a < 4; ++a) {
+            const long i = i0 + ty * 4 + a;
+#pragma unroll
+            for (int b = 0; b < 4; ++b) {
+                const long j = j0 + tx * 4 + b;
+                double g = 0.0;
+                if (i < n && j < m) {
+                    if (FUSED) {
+                        if (j <= i) {
+                            double aa = 0.0;
+                            for (int d = 0; d < Dy; ++d) aa = fma(alpha[i * Dy + d], alpha[j * Dy + d], aa);
+                            g = 0.5 * (sc * aa - (double)Dy * G[i * ldg + j]);
+                            if (Mul) g *= Mul[i * ldm + j];
+                        }
+                    } else {
+                        g = G[i * ldg + j];
+                    }
+                }
+                w[a][b] = g;
+            }
+        }
+        __syncthreads();
+        const unsigned rm = smask[0], cm = smask[1];
+        if (t == 0 && ((rm | cm) >> COREG_PMAX)) poisoned = true;
+        int ra[4], cb[4];
+#pragma unroll
+        for (int a = 0; a < 4; ++a) ra[a] = sa[ty * 4 + a];
+#pragma unroll
+        for (int b = 0; b < 4; ++b) cb[b] = sb[tx * 4 + b];
+        const bool diag_tile = FUSED && ti == tj;
+        for (unsigned rmm = rm & ((1u << COREG_PMAX) - 1); rmm; rmm &= rmm - 1) {
+            const int pa = __ffs(rmm) - 1;
+            for (unsigned cmm = cm & ((1u << COREG_PMAX) - 1); cmm; cmm &= cmm - 1) {
+                const int pb = __ffs(cmm) - 1;
+                double v = 0.0, dg = 0.0;
+#pragma unroll
+                for (int a = 0; a < 4; ++a)
+#pragma unroll
+                    for (int b = 0; b < 4; ++b)
+                        if (ra[a] == pa && cb[b] == pb) {
+                            v += w[a][b];
+                            if (diag_tile && ty * 4 + a == tx * 4 + b) dg += w[a][b];
+                        }
+                for (int off = 32; off > 0; off >>= 1) {
+                    v += __shfl_down(v, off);
+                    dg += __shfl_down(dg, off);
+                }
+                if (lane == 0) {
+                    red[wv][0] = v;
+                    red[wv][1] = dg;
+                }
+                __syncthreads();
+                if (t == 0) {
+                    const double sv = (red[0][0] + red[1][0]) + (red[2][0] + red[3][0]);
+                    const double sd = (red[0][1] + red[1][1]) + (red[2][1] + red[3][1]);
+                    sacc[pa * P + pb] += sv;
+                    if (FUSED) sacc[pb * P + pa] += sv - sd;
+                }
+                __syncthreads();
+            }
+        }
+    }
+    __syncthreads();
+    if (t == 0 && poisoned) sacc[0] = __builtin_nan("");
+    __syncthreads();
+    double* out = partials + (long)blockIdx.x * P * P;
+    for (int k = t; k < P * P; k += 256) out[k] = sacc[k];
+}
+
+int launch_grad_coreg(hipStream_t st, bool fused, KernParams kp, const double* Xt1, long ld1, long n, const double* Xt2, long ld2,
+                      long m, const double* G, long ldg, const double* alpha, int Dy, double* partials, const double* aa_scale,
+                      const double* Mul, long ldm) {
+    const long ntr = (n + KT - 1) / KT, ntc = (m + KT - 1) / KT;
+    const long ntiles = fused ? ntr * (ntr + 1) / 2 : ntr * ntc;
+    const int nb = pick_grad_blocks(ntiles);
+    if (fused)
+        hipLaunchKernelGGL((k_grad_coreg<true>), dim3(nb), dim3(256), 0, st, kp, Xt1, ld1, n, Xt1, ld1, n, G, ldg, alpha, Dy,
+                           ntiles, (int)ntr, partials, aa_scale, Mul, ldm);
+    else
+        hipLaunchKernelGGL((k_grad_coreg<false>), dim3(nb), dim3(256), 0, st, kp, Xt1, ld1, n, Xt2, ld2, m, G, ldg, nullptr, 0,
+                           ntiles, (int)ntc, partials, nullptr, nullptr, 0);
+    return nb;
+}
+
+// out[j] = kd[j] - sum_i M[i][j]^2: k_col_reduce's variance form with a per-point Kdiag (Coregionalize parts)
+__global__ __launch_bounds__(256) void k_col_reduce_vec(const double* __restrict__ M, long ld, long rows, long cols,
+                                                        const double* __restrict__ kd, double* __restrict__ out) {
+    __shared__ double red[4][64];
+    const int tx = threadIdx.x & 63, g = threadIdx.x >> 6;
+    const long j = (long)blockIdx.x * 64 + tx;
+    double s = 0.0;
+    if (j < cols) {
+        for (long i = g; i < rows; i += 4) {
+            const double x = M[i * ld + j];
+            s = fma(x, x, s);
+        }
+    }
+    red[g][tx] = s;
+    __syncthreads();
+    if (g == 0 && j < cols) out[j] = kd[j] - ((red[0][tx] + red[1][tx]) + (red[2][tx] + red[3][tx]));
+}
+
+void launch_col_reduce_vec(hipStream_t st, const double* M, long ld, long rows, long cols, const double* kd, double* out) {
+    hipLaunchKernelGGL(k_col_reduce_vec, dim3((unsigned)((cols + 63) / 64)), dim3(256), 0, st, M, ld, rows, cols, kd, out);
 }

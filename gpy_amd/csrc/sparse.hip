@@ -350,6 +350,7 @@ static int prepare_sparse_parts(mi355gp_sparse* s, int nparts, const mi355gp_par
     for (int i = 0; i < nparts; ++i) {
         const mi355gp_part& in = parts[i];
         SPart& p = s->parts[(size_t)i];
+        ARGCHK(in.kind != 8, "Coregionalize (kind 8) runs on the exact-GP path only, not the sparse path");
         ARGCHK(in.kind >= 0 && in.kind <= 5 && in.theta, "unknown covariance kind / NULL theta in a kernel part");
         p.term = in.term;
         ARGCHK(in.theta[0] > 0.0, "variance must be positive");

@@ -12,7 +12,7 @@ the same `numpy.linalg.LinAlgError` messages.
 import numpy as np
 
 from . import _lib
-from .kern import DEVICE_KERNELS, CombinationKernel
+from .kern import DEVICE_KERNELS, CombinationKernel, has_coregionalize
 from .lazy import ArrayIdentity, DeviceResult, kernel_signature
 from .likelihoods import Gaussian
 from .posterior import PosteriorExact, StudentTPosterior
@@ -176,7 +176,8 @@ class ExactGaussianInference(object):
         if fused:
             if is_sum:
                 specs = kern.part_specs()
-                diagA = kern.diag_variance() + noise + 1e-8
+                # jitchol's mean(diag(A)): with a Coregionalize part Kdiag depends on the point
+                diagA = (kern.Kdiag(X) if has_coregionalize(kern) else kern.diag_variance()) + noise + 1e-8
 
                 def attempt(extra):
                     return st.ctx.exact_inference_sum(specs, noise, jitter=1e-8, extra_jitter=extra, want_alpha=True,
@@ -272,7 +273,11 @@ class ExactStudentTInference(object):
                 break
             if tries >= self.maxtries:
                 raise LinAlgError("not positive definite, even with jitter.")
-            extra = (kern.diag_variance() if is_sum else float(specs[0][2][0])) * 1e-6 * 10 ** tries
+            if is_sum and has_coregionalize(kern):
+                kd = float(np.mean(kern.Kdiag(X)))
+            else:
+                kd = kern.diag_variance() if is_sum else float(specs[0][2][0])
+            extra = kd * 1e-6 * 10 ** tries
             tries += 1
         N, beta = Y.shape[0], r["beta"]
         dL_dnu = -N / (nu - 2.0) + digamma(0.5 * (nu + N)) - digamma(0.5 * nu)

@@ -425,10 +425,167 @@ class StdPeriodic(Parameterized):
     copy = Stationary.copy
 
 
+class Coregionalize(Parameterized):
+    """Coregionalization kernel k(x, x') = B[x, x'] over an input column of integer output indices, B = W W^T + diag(kappa)
+    (reference `GPy/kern/src/coregionalize.py:15-157`).  On the device it is C-ABI kind `MI355GP_COREGIONALIZE`: a factor
+    of the product terms that `util.multioutput.ICM` / `LCM` build, assembled in the K-build and reduced by the bucketed
+    gradient pass into S (P x P), which `_install_gradients` turns into dkappa = diag(S), dW = (S + S^T) W (`:110-128`).
+    W is linked untransformed (`positive=False`), kappa positive, in the reference's order."""
+    kind = "coregionalize"
+    _gpy_class = "GPy.kern.Coregionalize"
+    _support_GPU = True
+
+    def __init__(self, input_dim, output_dim, rank=1, W=None, kappa=None, active_dims=None, name="coregion", device=0):
+        super(Coregionalize, self).__init__(name)
+        assert int(input_dim) == 1, "Coregionalize acts on one input column (the output index): input_dim must be 1"
+        self.input_dim = 1
+        self.output_dim = int(output_dim)
+        self.rank = int(rank)
+        self.device = device
+        self.useGPU = True
+        self.active_dims = np.atleast_1d(np.asarray([0] if active_dims is None else active_dims, dtype=np.int_))
+        assert self.active_dims.size == 1, "Coregionalize takes one active dimension"
+        if self.rank > self.output_dim:
+            print("Warning: Unusual choice of rank, it should normally be less than the output_dim.")
+        if W is None:
+            W = 0.5 * np.random.randn(self.output_dim, self.rank) / np.sqrt(self.rank)
+        else:
+            W = np.asarray(W, dtype=float)
+            assert W.shape == (self.output_dim, self.rank)
+        if kappa is None:
+            kappa = 0.5 * np.ones(self.output_dim)
+        else:
+            kappa = np.asarray(kappa, dtype=float)
+            assert kappa.shape == (self.output_dim,)
+        self.W = Param("W", W, positive=False)
+        self.kappa = Param("kappa", kappa)
+        self.link_parameters(self.W, self.kappa)
+        self._K_cache = _KCache(limit=3)
+        self.parameters_changed()
+
+    @property
+    def ARD(self):
+        """the C-ABI's `ard` of this kind: the number of outputs P"""
+        return self.output_dim
+
+    def parameters_changed(self):
+        """(reference `coregionalize.py:80-81`)"""
+        self.B = np.dot(self.W.values, self.W.values.T) + np.diag(self.kappa.values)
+
+    def _theta(self):
+        """B, P x P row-major, symmetrised (W / kappa may have been edited in place since the last parameters_changed)"""
+        Wv = self.W.values
+        B = np.dot(Wv, Wv.T) + np.diag(self.kappa.values)
+        return (0.5 * (B + B.T)).ravel()
+
+    def _slice_X(self, X):
+        X = np.asarray(X)
+        return _lib.f64(X[:, self.active_dims])                   # [-1]: the last column (test_kernel.py:864)
+
+    def K(self, X, X2=None):
+        """B[idx, idx'] (reference `coregionalize.py:83-104`), built on the device"""
+        X = np.asarray(X)
+        X2 = None if X2 is None else np.asarray(X2)
+        theta = self._theta()
+
+        def compute():
+            return _lib.kern_K(self.kind, self.output_dim, theta, self._slice_X(X),
+                               None if X2 is None else self._slice_X(X2), device=self.device)
+        return self._K_cache.get(X, X2, theta, compute)
+
+    def Kdiag(self, X):
+        """diag(B)[idx] (reference `coregionalize.py:106-107`): O(N) host work"""
+        idx = self._index(self._slice_X(X))
+        return np.diag(self._theta().reshape(self.output_dim, self.output_dim))[idx]
+
+    def _index(self, Xs):
+        v = np.asarray(Xs).ravel()
+        idx = v.astype(np.int_)
+        if not np.all((idx == v) & (idx >= 0) & (idx < self.output_dim)):
+            bad = v[~((idx == v) & (idx >= 0) & (idx < self.output_dim))][0]
+            raise ValueError("Coregionalize: output index %r is not an integer in [0, %d)" % (bad, self.output_dim))
+        return idx
+
+    def update_gradients_full(self, dL_dK, X, X2=None):
+        """(reference `coregionalize.py:109-128`).  S comes from the device: the fused inference call's bucketed pass, or a
+        rectangular reduction of the given dL_dK."""
+        if isinstance(dL_dK, DeviceResult) and X2 is None and dL_dK.matches_kernel(self):
+            S = dL_dK.fused_dtheta
+        else:
+            S = _lib.update_gradients_full(self.kind, self.output_dim, self._theta(), np.asarray(dL_dK), self._slice_X(X),
+                                           None if X2 is None else self._slice_X(X2), device=self.device)
+        self._install_gradients(S)
+
+    def _install_gradients(self, g):
+        """S (P x P, S[a][b] = sum of dL_dK over rows of output a and columns of output b) -> dkappa = diag(S),
+        dW = (S + S^T) W (reference `coregionalize.py:123-128`; its dL_dK_small is S^T)"""
+        S = np.asarray(g, dtype=float).reshape(self.output_dim, self.output_dim)
+        self.kappa.gradient = np.diag(S).copy()
+        self.W.gradient = np.dot(S + S.T, self.W.values)
+
+    def update_gradients_diag(self, dL_dKdiag, X):
+        """(reference `coregionalize.py:145-151`)"""
+        idx = self._index(self._slice_X(X))
+        small = np.bincount(idx, weights=np.asarray(dL_dKdiag, dtype=float).ravel(), minlength=self.output_dim)
+        self.W.gradient = 2.0 * self.W.values * small[:, None]
+        self.kappa.gradient = small
+
+    def reset_gradients(self):
+        self.W.gradient = 0.
+        self.kappa.gradient = 0.
+
+    def gradients_X(self, dL_dK, X, X2=None):
+        """(reference `coregionalize.py:153-154`)"""
+        return np.zeros(np.asarray(X).shape)
+
+    def gradients_X_diag(self, dL_dKdiag, X):
+        """(reference `coregionalize.py:156-157`)"""
+        return np.zeros(np.asarray(X).shape)
+
+    def __add__(self, other):
+        return Add([self, other])
+
+    def __mul__(self, other):
+        return Prod([self, other])
+
+    def to_dict(self):
+        """(reference `coregionalize.py:159-174`)"""
+        return {"class": self._gpy_class, "name": self.name, "input_dim": self.input_dim,
+                "active_dims": self.active_dims.tolist(), "useGPU": True, "W": self.W.values.tolist(),
+                "kappa": self.kappa.values.tolist(), "output_dim": self.output_dim}
+
+    @classmethod
+    def from_dict(cls, d):
+        d = dict(d)
+        d.pop("class", None)
+        d.pop("useGPU", None)
+        d["W"], d["kappa"] = np.array(d["W"]), np.array(d["kappa"])
+        return cls(**d)
+
+    def copy(self):
+        return self.__class__.from_dict(self.to_dict())
+
+    __getstate__ = Stationary.__getstate__
+
+
 # kernels the exact-GP device path evaluates as one part (the fused inference call takes them alone or in Add / Prod)
 DEVICE_KERNELS = (Stationary, StdPeriodic)
 # kinds only the exact path has (the sparse and grid paths reject them)
-EXACT_ONLY_KINDS = ("ratquad", "stdperiodic")
+EXACT_ONLY_KINDS = ("ratquad", "stdperiodic", "coregionalize")
+
+
+def has_coregionalize(kern):
+    """True if the expression holds a Coregionalize part (its Kdiag then depends on the point)"""
+    leaves = kern.leaves() if isinstance(kern, CombinationKernel) else [kern]
+    return any(isinstance(k, Coregionalize) for k in leaves)
+
+
+def _spec_dims(f):
+    dims = np.asarray(f.active_dims)
+    if np.any(dims < 0):
+        raise ValueError("%s: negative active_dims are resolved against X by the kernel alone; give a kernel inside Add / Prod "
+                         "non-negative active_dims" % type(f).__name__)
+    return dims
 
 
 def exact_only_leaves(kern):
@@ -566,8 +723,8 @@ class Add(CombinationKernel):
         flat = []
         for p in parts:
             flat.extend(p.parts if isinstance(p, Add) else [p])          # add.py:24-33 flattens nested sums
-        assert all(isinstance(p, (Stationary, StdPeriodic, Static, Prod)) for p in flat), \
-            "Add supports stationary, StdPeriodic, White, Bias and Prod parts"
+        assert all(isinstance(p, (Stationary, StdPeriodic, Static, Coregionalize, Prod)) for p in flat), \
+            "Add supports stationary, StdPeriodic, White, Bias, Coregionalize and Prod parts"
         super(Add, self).__init__(flat, name)
 
     def part_specs(self):
@@ -577,9 +734,9 @@ class Add(CombinationKernel):
         for p in self.parts:
             if isinstance(p, Prod):
                 term += 1
-                specs.extend((f.kind, f.ARD, f._theta(), f.active_dims, term) for f in p.parts)
+                specs.extend((f.kind, f.ARD, f._theta(), _spec_dims(f), term) for f in p.parts)
             else:
-                specs.append((p.kind, p.ARD, p._theta(), p.active_dims, 0))
+                specs.append((p.kind, p.ARD, p._theta(), _spec_dims(p), 0))
         return specs
 
     def K(self, X, X2=None):
@@ -622,12 +779,12 @@ class Prod(CombinationKernel):
         flat = []
         for k in kernels:
             flat.extend(k.parts if isinstance(k, Prod) else [k])
-        assert all(isinstance(k, (Stationary, StdPeriodic, Static)) for k in flat), \
-            "Prod supports stationary, StdPeriodic, White and Bias factors"
+        assert all(isinstance(k, (Stationary, StdPeriodic, Static, Coregionalize)) for k in flat), \
+            "Prod supports stationary, StdPeriodic, White, Bias and Coregionalize factors"
         super(Prod, self).__init__(flat, name)
 
     def part_specs(self):
-        return [(f.kind, f.ARD, f._theta(), f.active_dims, 1) for f in self.parts]
+        return [(f.kind, f.ARD, f._theta(), _spec_dims(f), 1) for f in self.parts]
 
     def K(self, X, X2=None):                                                     # prod.py:58-65
         out = None
@@ -683,4 +840,4 @@ class Prod(CombinationKernel):
 
 
 KERNEL_CLASSES = {"rbf": RBF, "expquad": ExpQuad, "matern52": Matern52, "matern32": Matern32, "exponential": Exponential,
-                  "white": White, "bias": Bias, "ratquad": RatQuad, "stdperiodic": StdPeriodic}
+                  "white": White, "bias": Bias, "ratquad": RatQuad, "stdperiodic": StdPeriodic, "coregionalize": Coregionalize}

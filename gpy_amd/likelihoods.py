@@ -79,3 +79,83 @@ class HeteroscedasticGaussian(Gaussian):
     def to_dict(self):
         return {"class": "GPy.likelihoods.HeteroscedasticGaussian", "name": self.name,
                 "variance": self.variance.values.tolist()}
+
+
+class MixedNoise(Parameterized):
+    """One Gaussian likelihood per output (reference `GPy/likelihoods/mixed_noise.py:15-100`): the sub-likelihoods are linked,
+    so their variances are this likelihood's parameters in list order.  `gaussian_variance` hands the length-N noise vector
+    (the variance of each row's output, `Y_metadata['output_index']`) to the inference call and the noise gradients are the
+    per-output sums of diag(dL_dK), which the device returns as an N-vector.  Only Gaussian sub-likelihoods."""
+
+    def __init__(self, likelihoods_list, name="mixed_noise"):
+        super(MixedNoise, self).__init__(name)
+        if not all(isinstance(l, Gaussian) and not isinstance(l, HeteroscedasticGaussian) for l in likelihoods_list):
+            raise NotImplementedError("MixedNoise on the MI355X path takes Gaussian likelihoods only")
+        self.link_parameters(*likelihoods_list)
+        self.likelihoods_list = likelihoods_list
+        self.log_concave = False
+
+    def _index(self, Y_metadata):
+        return np.asarray(Y_metadata["output_index"]).flatten().astype(np.int_)
+
+    def _variances(self):
+        return np.array([float(l.variance.values[0]) for l in self.likelihoods_list])
+
+    def gaussian_variance(self, Y_metadata):
+        """(reference `mixed_noise.py:24-30`)"""
+        return self._variances()[self._index(Y_metadata)]
+
+    def betaY(self, Y, Y_metadata):
+        return Y / self.gaussian_variance(Y_metadata=Y_metadata)[:, None]
+
+    def update_gradients(self, gradients):
+        g = np.asarray(gradients, dtype=float).ravel()
+        for lik, gj in zip(self.likelihoods_list, g):
+            lik.update_gradients(gj)
+
+    def exact_inference_gradients(self, dL_dKdiag, Y_metadata):
+        """(reference `mixed_noise.py:39-42`): per-output sums of diag(dL_dK)"""
+        return np.bincount(self._index(Y_metadata), weights=np.asarray(dL_dKdiag, dtype=float).reshape(-1),
+                           minlength=len(self.likelihoods_list)).astype(float)
+
+    def predictive_values(self, mu, var, full_cov=False, Y_metadata=None):
+        """(reference `mixed_noise.py:44-51`; the caller's var is not modified)"""
+        s = self.gaussian_variance(Y_metadata)
+        if full_cov:
+            return mu, var + np.diag(s)
+        return mu, var + s.reshape(np.shape(var)[0], -1)
+
+    def predictive_variance(self, mu, sigma, Y_metadata):
+        """(reference `mixed_noise.py:53-55`)"""
+        return self.gaussian_variance(Y_metadata) + sigma ** 2
+
+    def predictive_quantiles(self, mu, var, quantiles, Y_metadata):
+        """(reference `mixed_noise.py:57-65`): each output's quantiles from its own likelihood"""
+        ind = self._index(Y_metadata)
+        mu, var = np.asarray(mu), np.asarray(var)
+        Q = np.zeros((mu.size, len(quantiles)))
+        for j in np.unique(ind):
+            q = self.likelihoods_list[j].predictive_quantiles(mu[ind == j, :], var[ind == j, :], quantiles)
+            Q[ind == j, :] = np.hstack(q)
+        return [q[:, None] for q in Q.T]
+
+    def log_predictive_density(self, y_test, mu_star, var_star, Y_metadata=None):
+        """independent Gaussian predictive densities with each row's own noise variance"""
+        v = np.asarray(var_star) + self.gaussian_variance(Y_metadata)[:, None]
+        return -0.5 * np.log(2 * np.pi) - 0.5 * np.log(v) - 0.5 * np.square(y_test - mu_star) / v
+
+    def samples(self, gp, Y_metadata):
+        """(reference `mixed_noise.py:67-84`)"""
+        gp = np.asarray(gp)
+        Ysim = np.zeros(gp.shape)
+        ind = self._index(Y_metadata)
+        for j in np.unique(ind):
+            flt = ind == j
+            Ysim[flt, :] = gp[flt, :] + np.sqrt(float(self.likelihoods_list[j].variance.values[0])) * np.random.normal(
+                size=gp[flt, :].shape)
+        return Ysim
+
+    def to_dict(self):
+        """(reference `mixed_noise.py:86-100`)"""
+        return {"name": self.name, "class": "GPy.likelihoods.MixedNoise",
+                "likelihoods_list": [l.to_dict() for l in self.likelihoods_list]}

@@ -242,8 +242,12 @@ class GP(PredictionCallers, Parameterized):
         self.set_XY(Y=Y)
 
     def optimize(self, max_iters=1000, messages=False, gtol=1e-6):
-        """L-BFGS-B on the negative log marginal likelihood in log-parameter space."""
+        """L-BFGS-B on the negative log marginal likelihood in log-parameter space; parameters declared `positive=False`
+        (Coregionalize's W) are optimised untransformed."""
         from scipy.optimize import minimize
+        pos = np.concatenate([np.full(p.size, bool(p.positive)) for p in self.flattened_parameters()])
+        if not pos.all():
+            return self._optimize_mixed(pos, max_iters, messages, gtol)
         x0 = np.log(self.param_array)
 
         def f(z):
@@ -255,6 +259,29 @@ class GP(PredictionCallers, Parameterized):
         res = minimize(f, x0, jac=True, method="L-BFGS-B", options={"maxiter": max_iters, "gtol": gtol,
                                                                      "disp": bool(messages)})
         self.param_array = np.exp(res.x)
+        return res
+
+    def _optimize_mixed(self, pos, max_iters, messages, gtol):
+        from scipy.optimize import minimize
+        x = self.param_array
+        x0 = x.copy()
+        x0[pos] = np.log(x[pos])
+
+        def params(z):
+            p = z.copy()
+            p[pos] = np.exp(z[pos])
+            return p
+
+        def f(z):
+            p = params(z)
+            try:
+                self.param_array = p
+            except np.linalg.LinAlgError:
+                return 1e300, np.zeros_like(z)
+            return self.objective_function(), self.objective_function_gradients() * np.where(pos, p, 1.0)
+        res = minimize(f, x0, jac=True, method="L-BFGS-B", options={"maxiter": max_iters, "gtol": gtol,
+                                                                     "disp": bool(messages)})
+        self.param_array = params(res.x)
         return res
 
 
@@ -287,3 +314,22 @@ class GPHeteroscedasticRegression(GP):
         super(GPHeteroscedasticRegression, self).__init__(X, Y, kernel, HeteroscedasticGaussian(Y_metadata),
                                                           name="gp_heteroscedastic_regression", Y_metadata=Y_metadata,
                                                           device=device)
+
+
+class GPCoregionalizedRegression(GP):
+    """Multi-output GP regression with coregionalization (reference `GPy/models/gp_coregionalized_regression.py:9-46`): the
+    per-output inputs are stacked with an output-index column (`util.multioutput.build_XY`), the kernel defaults to an ICM of
+    an RBF, the likelihood is MixedNoise (one Gaussian noise per output).  `predict(Xnew, Y_metadata={'output_index': ...})`
+    takes Xnew with the index column appended."""
+
+    def __init__(self, X_list, Y_list, kernel=None, likelihoods_list=None, name="GPCR", W_rank=1, kernel_name="coreg",
+                 device=0):
+        from .util import multioutput
+        X, Y, self.output_index = multioutput.build_XY(X_list, Y_list)
+        Ny = len(Y_list)
+        if kernel is None:
+            kernel = RBF(X.shape[1] - 1, device=device)
+            kernel = multioutput.ICM(input_dim=X.shape[1] - 1, num_outputs=Ny, kernel=kernel, W_rank=W_rank, name=kernel_name)
+        likelihood = multioutput.build_likelihood(Y_list, self.output_index, likelihoods_list)
+        super(GPCoregionalizedRegression, self).__init__(X, Y, kernel, likelihood, name=name,
+                                                         Y_metadata={"output_index": self.output_index}, device=device)

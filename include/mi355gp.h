@@ -26,7 +26,7 @@ typedef struct mi355gp_ctx mi355gp_ctx;
 
 enum { MI355GP_RBF = 0, MI355GP_MATERN52 = 1, MI355GP_MATERN32 = 2, MI355GP_EXPONENTIAL = 3,
        MI355GP_WHITE = 4, MI355GP_BIAS = 5 /* static kernels, only as parts of a sum (kern/src/static.py:63-98,151-173) */,
-       MI355GP_RATQUAD = 6, MI355GP_STDPERIODIC = 7 };
+       MI355GP_RATQUAD = 6, MI355GP_STDPERIODIC = 7, MI355GP_COREGIONALIZE = 8 };
 
 /* The exact-GP entry points (single kind and part lists; not the sparse or grid paths) also take
  *   MI355GP_RATQUAD      k = var (1 + r^2/2)^-power (kern/src/stationary.py:747-802, GPy.kern.RatQuad);
@@ -36,6 +36,20 @@ enum { MI355GP_RBF = 0, MI355GP_MATERN52 = 1, MI355GP_MATERN32 = 2, MI355GP_EXPO
  *                        (:56-94); `ard` is a bitmask: bit 0 = ARD1 (one period per dimension), bit 1 = ARD2 (one
  *                        lengthscale per dimension)
  * Gradients come back in theta order.  Both have K(x, x) = variance.  Period, lengthscale and power must be positive. */
+
+/* The exact-GP part-list entry points (mi355gp_exact_inference_sum, mi355gp_exact_studentt_sum, mi355gp_predict_sum,
+ * mi355gp_covariance_between_points) and the stateless mi355gp_kern_K / mi355gp_update_gradients_full also take
+ *   MI355GP_COREGIONALIZE  k(x, x') = B[idx][idx'] (kern/src/coregionalize.py:82-157, GPy.kern.Coregionalize), idx = the value
+ *                          of ONE input column holding the output index (n_active must be 1; the stateless entry points take
+ *                          that column itself, D = 1).  `ard` carries the number of outputs P, 1 <= P <= 16 (StdPeriodic
+ *                          reuses `ard` as well, as a bitmask).  theta = B, P x P row-major, symmetric (the host passes
+ *                          0.5 (B + B^T), B = W W^T + diag(kappa), :80-81).  Every index must be an integer in [0, P):
+ *                          anything else is an error return naming the value, never a clamp.
+ *                          Gradients come back as S, P x P row-major in theta order: S[a][b] = sum over rows i with idx_i = a
+ *                          and columns j with idx_j = b of dL_dK_ij (times the term's other factors).  The host turns S into
+ *                          dkappa = diag(S), dW = (S + S^T) W (:110-128).  Usually a factor of a product term (ICM / LCM);
+ *                          the single-kind entry points, mi355gp_kern_Kdiag, mi355gp_predictive_gradients_sum and the sparse
+ *                          and grid paths reject it. */
 
 /* One part of a sum-of-products kernel expression (GPy.kern.Add, kern/src/add.py:58-84; GPy.kern.Prod,
  * kern/src/prod.py:58-99).  theta = [variance, lengthscale (1, or n_active if ard)] (static kinds: [variance]);
