@@ -13,6 +13,7 @@
 #include "../../include/mi355gp.h"
 #include "../../include/mi355gp_debug.h"
 #include "internal.h"
+#include "parts.h"
 
 int run_peaks(int device, double* out4);
 
@@ -35,7 +36,6 @@ void mi355gp_set_error(const char* fmt, ...) {
         }                                 \
     } while (0)
 
-#define GP_STRIDE 34
 #define COREG_REC 256          // doubles of one Coregionalize part's S (P x P, P <= 16)
 #define LOG_2_PI 1.8378770664093454836
 
@@ -57,7 +57,7 @@ struct mi355gp_ctx {
     hipStream_t st = nullptr;
     long n = 0, npad = 0;
     int D = 0, Dy = 0;
-    double *dX = nullptr, *dR = nullptr, *dXt = nullptr, *dInvLs = nullptr, *dNoise = nullptr;
+    double *dX = nullptr, *dR = nullptr, *dInvLs = nullptr, *dNoise = nullptr;
     double *A = nullptr, *B = nullptr, *C = nullptr;
     FactorWs ws;
     double *dAlpha = nullptr, *dTmp = nullptr, *dTrmvPart = nullptr, *dGradPart = nullptr, *dGradOut = nullptr,
@@ -67,23 +67,13 @@ struct mi355gp_ctx {
     // state of the last inference call (for fetch / predict)
     bool have_factor = false, have_kernel = false;
     bool studentt = false;              // the last call was a Student-t process: dL_dK's alpha alpha^T term is scaled by dScal[4]
-    KernParams kp = {0, 0, 0, 1.0};
-    std::vector<double> theta;
-    // The covariance function of the last fused call as a SUM of parts (GPy/kern/src/add.py; one part = plain kernel).
-    struct Part {
-        KernParams kp = {0, 0, 0, 1.0};
-        std::vector<double> theta;      // [variance, lengthscale(s)]  (static kinds: [variance])
-        std::vector<int> dims;          // active input dimensions (kern.py:49-53), indices into the D columns of X
-        std::vector<double> inv_ls;     // length D: 1/l on active dimensions, 0 elsewhere (= the slicing of kern.py:112-117)
-                                        // (StdPeriodic: 1 on active dimensions -- its inputs stay unscaled)
+    // The covariance function of the last fused call as a sum of products of parts (GPy/kern/src/add.py, prod.py)
+    struct Part : PartSpec {
         double* dXt = nullptr;          // D x npad scaled, dimension-major inputs of this part
-        int ard_in = 0;                 // the `ard` of the C-ABI part (StdPeriodic: the ARD1 | ARD2 bitmask)
-        std::vector<double> pw;         // StdPeriodic: [pi / T_q (D) | 1 / l_q (D)], uploaded to dPw (KernParams::pw)
-        double* dPw = nullptr;
-        int term = 0;                   // parts with the same term id are multiplied (GPy/kern/src/prod.py), terms are summed
+        double* dPw = nullptr;          // pw on the device (KernParams::pw)
     };
     std::vector<Part> parts;
-    std::vector<std::vector<int>> terms;   // part indices per term, in order of first appearance
+    Terms terms;
     double* Mbuf = nullptr;             // npad x npad product of the OTHER factors of a term (allocated on first product kernel)
     // Everything an evaluation returns -- scalars, info, per-part gradient sums, alpha, diag(dL_dK) -- lives in ONE device
     // block and travels in ONE copy into ONE pinned host block (five small pageable copies cost ~80 us per evaluation:
@@ -145,7 +135,7 @@ static void drop_graph(mi355gp_ctx* c) {
 static void free_data(mi355gp_ctx* c) {
     drop_graph(c);                                            // every node holds pointers into the buffers freed below
     free_parts(c);
-    double** ptrs[] = {&c->dX, &c->dR, &c->dXt, &c->dInvLs, &c->dNoise, &c->A, &c->B, &c->C, &c->Mbuf,
+    double** ptrs[] = {&c->dX, &c->dR, &c->dInvLs, &c->dNoise, &c->A, &c->B, &c->C, &c->Mbuf,
                        &c->dTmp, &c->dTrmvPart, &c->dGradPart, &c->dGradOut, &c->dPack, &c->dCoregPart};
     for (auto p : ptrs) {
         if (*p) (void)hipFree(*p);
@@ -228,7 +218,6 @@ int mi355gp_set_data(mi355gp_ctx* c, const double* X, int64_t N, int D, const do
     const long np = c->npad;
     HIP_CHECK(hipMalloc(&c->dX, sizeof(double) * N * D));
     HIP_CHECK(hipMalloc(&c->dR, sizeof(double) * N * Dy));
-    HIP_CHECK(hipMalloc(&c->dXt, sizeof(double) * D * np));
     HIP_CHECK(hipMalloc(&c->dInvLs, sizeof(double) * D));
     HIP_CHECK(hipMalloc(&c->dNoise, sizeof(double) * N));
     HIP_CHECK(hipMalloc(&c->A, sizeof(double) * np * np));
@@ -278,135 +267,10 @@ int mi355gp_set_targets(mi355gp_ctx* c, const double* R, int Dy) {
 
 }  // extern "C"
 
-// ---------------------------------------------------------------------------------------------------
-static bool is_ext_kind(int kind) { return kind == MI355GP_RATQUAD || kind == MI355GP_STDPERIODIC; }
-
-// Coregionalize (kind 8, coregionalize.py:82-157): `ard` = the number of outputs P, theta = B (P x P).  Output indices are
-// values of one input column; each must be an integer in [0, P) -- checked here, on the host, before any launch reads one.
-static int coreg_check_P(int P) {
-    if (P < 1 || P > 16) {
-        mi355gp_set_error("Coregionalize (kind 8): the number of outputs (ard) must be between 1 and 16, got %d", P);
-        return -1;
-    }
-    return 0;
-}
-static int coreg_check_index(const double* x, long n, long stride, int P, const char* what) {
-    for (long i = 0; i < n; ++i) {
-        const double v = x[i * stride];
-        if (!(v >= 0.0 && v < (double)P && v == std::floor(v))) {
-            mi355gp_set_error("Coregionalize (kind 8): %s output index %.17g (row %ld) is not an integer in [0, %d)", what, v, i, P);
-            return -1;
-        }
-    }
-    return 0;
-}
-
-// RatQuad / StdPeriodic: validates theta for the active dimensions `dims` (of D input columns) and fills the input scaling
-// (inv_ls over the D columns), the StdPeriodic parameter block pw and the RatQuad power
-static int ext_setup(int kind, int ard, const double* theta, const std::vector<int>& dims, int D, std::vector<double>* inv_ls,
-                     std::vector<double>* pw, double* power, int* ntheta) {
-    const int na = (int)dims.size();
-    inv_ls->assign((size_t)D, 0.0);
-    pw->clear();
-    if (kind == MI355GP_RATQUAD) {                       // [variance, lengthscale (1 or n_active), power]
-        const int nl = ard ? na : 1;
-        for (int a = 0; a < na; ++a) {
-            const double l = theta[1 + (ard ? a : 0)];
-            ARG_CHECK(l > 0.0, "RatQuad: lengthscales must be positive");
-            (*inv_ls)[(size_t)dims[a]] = 1.0 / l;
-        }
-        *power = theta[1 + nl];
-        ARG_CHECK(*power > 0.0, "RatQuad: power must be positive");
-        *ntheta = 2 + nl;
-        return 0;
-    }
-    ARG_CHECK(ard >= 0 && ard <= 3, "StdPeriodic: ard is a bitmask (1 = one period, 2 = one lengthscale per dimension)");
-    const int nper = (ard & 1) ? na : 1, nl = (ard & 2) ? na : 1;
-    pw->assign(2 * (size_t)D, 0.0);
-    for (int a = 0; a < na; ++a) {
-        const double T = theta[1 + ((ard & 1) ? a : 0)], l = theta[1 + nper + ((ard & 2) ? a : 0)];
-        ARG_CHECK(T > 0.0, "StdPeriodic: periods must be positive");
-        ARG_CHECK(l > 0.0, "StdPeriodic: lengthscales must be positive");
-        const int q = dims[a];
-        (*inv_ls)[(size_t)q] = 1.0;                      // unscaled inputs: Delta from the raw coordinates
-        (*pw)[(size_t)q] = M_PI / T;
-        (*pw)[(size_t)(D + q)] = 1.0 / l;
-    }
-    *power = 0.0;
-    *ntheta = 1 + nper + nl;
-    return 0;
-}
-
-// post-scaling of the raw sums of a RatQuad / StdPeriodic part (records A, B: groups * GP_STRIDE each, see k_grad_ext);
-// writes the gradient in theta order at o and returns the number written
-static int finish_ext(int kind, int ard, const double* theta, const std::vector<int>& dims, const double* A, const double* B,
-                      double* o) {
-    auto at = [](const double* R, int q) { return R[(q / 32) * GP_STRIDE + 2 + (q % 32)]; };
-    const int na = (int)dims.size();
-    int k = 0;
-    o[k++] = A[0] / theta[0];                                          // sum g K / variance
-    if (kind == MI355GP_RATQUAD) {                                     // stationary.py:199,210-213,790-798
-        const int nl = ard ? na : 1;
-        if (!ard) o[k++] = -A[1] / theta[1];
-        else
-            for (int a = 0; a < na; ++a) o[k++] = -at(A, dims[a]) / theta[1 + a];
-        o[k++] = B[0];
-        (void)nl;
-        return k;
-    }
-    const int nper = (ard & 1) ? na : 1;                               // standard_periodic.py:501-526
-    double sT = 0.0, sL = 0.0;
-    for (int a = 0; a < na; ++a) {
-        const double T = theta[1 + ((ard & 1) ? a : 0)], l = theta[1 + nper + ((ard & 2) ? a : 0)];
-        const double gT = at(A, dims[a]) / (T * l * l), gL = at(B, dims[a]) / (l * l * l);
-        if (ard & 1) o[k + a] = gT;
-        else sT += gT;
-        if (ard & 2) o[k + nper + a] = gL;
-        else sL += gL;
-    }
-    if (!(ard & 1)) o[k] = sT;
-    k += nper;
-    if (!(ard & 2)) o[k] = sL;
-    k += (ard & 2) ? na : 1;
-    return k;
-}
-
-static int check_theta(int kind, int ard, const double* theta, int D, std::vector<double>* inv_ls,
-                       std::vector<double>* pw = nullptr, double* power = nullptr) {
-    ARG_CHECK((kind >= 0 && kind <= 3) || (is_ext_kind(kind) && pw && power), "unknown covariance kind");
-    ARG_CHECK(theta != nullptr, "theta is NULL");
-    ARG_CHECK(theta[0] > 0.0, "variance must be positive");
-    if (is_ext_kind(kind)) {
-        std::vector<int> dims((size_t)D);
-        for (int q = 0; q < D; ++q) dims[(size_t)q] = q;
-        int nt = 0;
-        return ext_setup(kind, ard, theta, dims, D, inv_ls, pw, power, &nt);
-    }
-    const int nl = ard ? D : 1;
-    inv_ls->resize(D);
-    for (int q = 0; q < nl; ++q) {
-        ARG_CHECK(theta[1 + q] > 0.0, "lengthscales must be positive");
-        (*inv_ls)[q] = 1.0 / theta[1 + q];
-    }
-    return 0;
-}
-
-// post-scaling of the raw reduction sums: dvar = S_var / variance; dl = -S / l
-// (GPy/kern/src/stationary.py:199,210-213 with x already divided by l inside the kernels)
-static void finish_dtheta(const KernParams& kp, const double* theta, const double* sums /*groups*GP_STRIDE*/,
-                          double* dtheta_out) {
-    dtheta_out[0] = sums[0] / kp.variance;
-    if (!kp.ard) {
-        dtheta_out[1] = -sums[1] / theta[1];
-    } else {
-        for (int q = 0; q < kp.D; ++q) dtheta_out[1 + q] = -sums[(q / 32) * GP_STRIDE + 2 + (q % 32)] / theta[1 + q];
-    }
-}
-
 // Shared tail: given Ky (lower) in c->A: factor, invert, alpha, scalars [, kernel gradients].
 // rebuild(): re-enqueues the construction of Ky in c->A (needed only after a DIRTY abort of the persistent factorisation).
-static int run_pipeline(mi355gp_ctx* c, EngineShared* gate, bool with_kernel_grads, const double* theta,
-                        double* out_scalars, double* alpha_out, double* dtheta_out, double* diag_out, double* stage_ms,
+static int run_pipeline(mi355gp_ctx* c, EngineShared* gate, bool with_kernel_grads, double* out_scalars, double* alpha_out,
+                        double* dtheta_out, double* diag_out, double* stage_ms,
                         const std::function<int()>& rebuild, double studentt_nu = 0.0, int attempt = 0) {
     hipStream_t st = c->st;
     const long n = c->n, np = c->npad;
@@ -489,17 +353,12 @@ static int run_pipeline(mi355gp_ctx* c, EngineShared* gate, bool with_kernel_gra
             const mi355gp_ctx::Part& pt = c->parts[p];
             // factor of a product: dL_dK is weighted by the covariances of the term's other factors (prod.py:86-99),
             // rebuilt into Mbuf (lower tiles) by one K-build pass per other factor
-            const double* Mul = nullptr;
-            for (const auto& t : c->terms) {
-                if (t.size() < 2 || std::find(t.begin(), t.end(), (int)p) == t.end()) continue;
-                for (int g : t) {
-                    if (g == (int)p) continue;
-                    launch_kbuild_sym(st, c->parts[(size_t)g].kp, c->parts[(size_t)g].dXt, np, n, np, c->Mbuf, nullptr, 0,
-                                      0.0, /*lower_only=*/1, /*add_diag=*/0, /*accumulate=*/0, Mul);
-                    Mul = c->Mbuf;
-                }
-            }
-            if (pt.kp.kind == MI355GP_COREGIONALIZE) {                  // the bucketed gradient: S (P x P) per part
+            const bool prod = emit_other_factors(c->terms, pt.tix, p, c->Mbuf, [&](int g, double* dst, const double* mul, int, bool) {
+                launch_kbuild_sym(st, c->parts[(size_t)g].kp, c->parts[(size_t)g].dXt, np, n, np, dst, nullptr, 0, 0.0,
+                                  /*lower_only=*/1, /*add_diag=*/0, /*accumulate=*/0, mul);
+            });
+            const double* Mul = prod ? c->Mbuf : nullptr;
+            if (pt.coreg()) {                                           // the bucketed gradient: S (P x P) per part
                 const int P = pt.kp.ard;
                 const int nbc = launch_grad_coreg(st, true, pt.kp, pt.dXt, np, n, pt.dXt, np, n, c->C, np, c->dAlpha, c->Dy,
                                                   c->dCoregPart, studentt_nu > 0.0 ? c->dScal + 4 : nullptr, Mul, np);
@@ -511,7 +370,7 @@ static int run_pipeline(mi355gp_ctx* c, EngineShared* gate, bool with_kernel_gra
             for (int g = 0; g < (pt.kp.ard ? groups : 1); ++g)
                 launch_reduce_partials(st, c->dGradPart + (long)g * nb * GP_STRIDE, nb, GP_STRIDE,
                                        c->dGradOutAll + ((long)p * groups + g) * GP_STRIDE);
-            if (is_ext_kind(pt.kp.kind))                                   // their second record (k_grad_ext)
+            if (pt.ext())                                                  // their second record (k_grad_ext)
                 for (int g = 0; g < (pt.kp.ard ? groups : 1); ++g)
                     launch_reduce_partials(st, c->dGradPart + ((long)groups + g) * nb * GP_STRIDE, nb, GP_STRIDE,
                                            c->dPack + c->offExt + ((long)p * groups + g) * GP_STRIDE);
@@ -520,7 +379,7 @@ static int run_pipeline(mi355gp_ctx* c, EngineShared* gate, bool with_kernel_gra
     HIP_CHECK(hipEventRecord(c->ev[6], st));
     // ONE device -> pinned host copy of the prefix of the result block that the caller asked for
     bool coreg = false;
-    for (size_t p = 0; p < nparts; ++p) coreg = coreg || c->parts[p].kp.kind == MI355GP_COREGIONALIZE;
+    for (size_t p = 0; p < nparts; ++p) coreg = coreg || c->parts[p].coreg();
     const size_t ncopy = coreg ? c->packDoubles : (diag_out ? c->offCoreg : (alpha_out ? c->offDiag : c->offAlpha));
     HIP_CHECK(hipMemcpyAsync(c->hPack, c->dPack, sizeof(double) * ncopy, hipMemcpyDeviceToHost, st));
     HIP_CHECK(hipStreamSynchronize(st));
@@ -552,7 +411,7 @@ static int run_pipeline(mi355gp_ctx* c, EngineShared* gate, bool with_kernel_gra
         if (attempt == 0 && (clean || rebuild)) {
             if (!clean)
                 if (int rc = rebuild()) return rc;
-            return run_pipeline(c, gate, with_kernel_grads, theta, out_scalars, alpha_out, dtheta_out, diag_out, stage_ms,
+            return run_pipeline(c, gate, with_kernel_grads, out_scalars, alpha_out, dtheta_out, diag_out, stage_ms,
                                 rebuild, studentt_nu, attempt + 1);
         }
         mi355gp_set_error("the persistent factorisation aborted and could not be redone (info %d); this context continues "
@@ -614,75 +473,25 @@ static int run_pipeline(mi355gp_ctx* c, EngineShared* gate, bool with_kernel_gra
         out_scalars[5] = (nu + N) / (nu + beta - 2.0);                       // factor of dL_dm = factor * alpha
         out_scalars[MI355GP_OUT_DNOISE] = 0.0;
     }
-    if (nparts > 0 && dtheta_out) {
-        // post-scaling of the raw sums (stationary.py:199,210-213): dvar = S/variance, dl = -S/l, per part, concatenated
+    if (nparts > 0 && dtheta_out) {                              // per part, concatenated in part order
         double* o = dtheta_out;
         for (size_t p = 0; p < nparts; ++p) {
-            const mi355gp_ctx::Part& pt = c->parts[p];
-            const double* sp = sumsp + p * (size_t)groups * GP_STRIDE;
-            if (pt.kp.kind == MI355GP_COREGIONALIZE) {                       // S in theta (= B) order
-                const int P = pt.kp.ard;
-                memcpy(o, c->hPack + c->offCoreg + p * (size_t)COREG_REC, sizeof(double) * P * P);
-                o += P * P;
-                continue;
-            }
-            if (is_ext_kind(pt.kp.kind)) {
-                o += finish_ext(pt.kp.kind, pt.ard_in, pt.theta.data(), pt.dims, sp,
-                                c->hPack + c->offExt + p * (size_t)groups * GP_STRIDE, o);
-                continue;
-            }
-            *o++ = sp[0] / pt.kp.variance;
-            if (pt.kp.kind >= 4) continue;                                   // static kernels: variance only
-            if (!pt.kp.ard) *o++ = -sp[1] / pt.theta[1];
-            else
-                for (size_t a = 0; a < pt.dims.size(); ++a) {
-                    const int q = pt.dims[a];
-                    *o++ = -sp[(q / 32) * GP_STRIDE + 2 + (q % 32)] / pt.theta[1 + a];
-                }
+            const double* rec = c->parts[p].coreg() ? c->hPack + c->offCoreg + p * COREG_REC : sumsp + p * (size_t)groups * GP_STRIDE;
+            o += part_dtheta(c->parts[p], rec, c->hPack + c->offExt + p * (size_t)groups * GP_STRIDE, o);
         }
     }
-    (void)theta;
     return 0;
-}
-
-// K = sum over terms of the element-wise product of the term's factors (add.py:58-72, prod.py:58-65).
-// emit(part, dst, mul, accumulate, first_into_out) launches one factor: dst (+)= k_part * mul.  The leading factors
-// of a multi-factor term are multiplied up in `scratch` (same shape as `out`), the last one lands in `out`.
-template <class Emit>
-static void build_expression(const mi355gp_ctx* c, double* out, double* scratch, bool out_holds_data, Emit emit) {
-    bool first = !out_holds_data;
-    for (const auto& t : c->terms) {
-        const size_t k = t.size();
-        for (size_t f = 0; f + 1 < k; ++f) emit(t[f], scratch, f > 0 ? scratch : nullptr, 0, false);
-        emit(t[k - 1], out, k > 1 ? scratch : nullptr, first ? 0 : 1, first);
-        first = false;
-    }
-}
-static bool has_product(const mi355gp_ctx* c) {
-    for (const auto& t : c->terms)
-        if (t.size() > 1) return true;
-    return false;
-}
-// Kdiag of the expression: sum over terms of the product of the factors' variances
-static double expression_kdiag(const mi355gp_ctx* c) {
-    double s = 0.0;
-    for (const auto& t : c->terms) {
-        double v = 1.0;
-        for (int f : t) v *= c->parts[(size_t)f].kp.variance;
-        s += v;
-    }
-    return s;
 }
 
 static bool has_coreg(const mi355gp_ctx* c) {
     for (const auto& p : c->parts)
-        if (p.kp.kind == MI355GP_COREGIONALIZE) return true;
+        if (p.coreg()) return true;
     return false;
 }
 // new points (M x D, host) against every Coregionalize part: their output indices must be valid
 static int coreg_check_points(const mi355gp_ctx* c, const double* Xn, int64_t M, const char* what) {
     for (const auto& p : c->parts)
-        if (p.kp.kind == MI355GP_COREGIONALIZE)
+        if (p.coreg())
             if (int rc = coreg_check_index(Xn + p.kp.col, M, c->D, p.kp.ard, what)) return rc;
     return 0;
 }
@@ -696,7 +505,7 @@ static std::vector<double> expression_kdiag_points(const mi355gp_ctx* c, const d
             double v = 1.0;
             for (int f : t) {
                 const mi355gp_ctx::Part& p = c->parts[(size_t)f];
-                if (p.kp.kind == MI355GP_COREGIONALIZE) {
+                if (p.coreg()) {
                     const int a = (int)Xn[m * c->D + p.kp.col], P = p.kp.ard;
                     v *= p.theta[(size_t)(a * P + a)];
                 } else {
@@ -708,53 +517,6 @@ static std::vector<double> expression_kdiag_points(const mi355gp_ctx* c, const d
         kd[(size_t)m] = s;
     }
     return kd;
-}
-
-// KernParams of a stateless RatQuad / StdPeriodic evaluation: power, and the StdPeriodic parameter block uploaded to *buf
-static int ext_params(KernParams* kp, const std::vector<double>& pw, double power, DevBuf* buf) {
-    if (!is_ext_kind(kp->kind)) return 0;
-    kp->power = power;
-    if (kp->kind == MI355GP_STDPERIODIC) {
-        kp->ard = 1;                                       // per-dimension reductions
-        HIP_CHECK(buf->alloc(pw.size()));
-        HIP_CHECK(hipMemcpy(*buf, pw.data(), sizeof(double) * pw.size(), hipMemcpyHostToDevice));
-        kp->pw = *buf;
-    }
-    return 0;
-}
-
-// StdPeriodic.gradients_X (standard_periodic.py:574-580): dX[i][q] = -pi / (2 T_q l_q^2) sum_j W_ij K_ij sin(2 Delta_ijq),
-// W = dL_dK (+ dL_dK^T against X itself), as a row reduction on the device (k_periodic_gradx)
-static int periodic_gradients_X(double variance, const std::vector<double>& pw, const double* dL_dK, const double* X, int64_t N,
-                                const double* X2, int64_t M, int D, bool sym, double* out) {
-    std::vector<double> W((size_t)N * M), ones((size_t)D, 1.0);
-    for (int64_t i = 0; i < N; ++i)
-        for (int64_t j = 0; j < M; ++j) W[(size_t)i * M + j] = sym ? dL_dK[i * M + j] + dL_dK[j * M + i] : dL_dK[i * M + j];
-    const long ld1 = round_up(N, 64), ld2 = round_up(M, 64);
-    DevBuf dX1, dX2, dXt1, dXt2, dOnes, dW, dPw, dOut;
-    HIP_CHECK(dX1.alloc(N * D));
-    HIP_CHECK(dX2.alloc(M * D));
-    HIP_CHECK(dXt1.alloc(D * ld1));
-    HIP_CHECK(dXt2.alloc(D * ld2));
-    HIP_CHECK(dOnes.alloc(D));
-    HIP_CHECK(dW.alloc(N * M));
-    HIP_CHECK(dPw.alloc(2 * D));
-    HIP_CHECK(dOut.alloc(N * D));
-    HIP_CHECK(hipMemcpy(dX1, X, sizeof(double) * N * D, hipMemcpyHostToDevice));
-    HIP_CHECK(hipMemcpy(dX2, X2, sizeof(double) * M * D, hipMemcpyHostToDevice));
-    HIP_CHECK(hipMemcpy(dOnes, ones.data(), sizeof(double) * D, hipMemcpyHostToDevice));
-    HIP_CHECK(hipMemcpy(dW, W.data(), sizeof(double) * N * M, hipMemcpyHostToDevice));
-    HIP_CHECK(hipMemcpy(dPw, pw.data(), sizeof(double) * 2 * D, hipMemcpyHostToDevice));
-    launch_scale_inputs(0, dX1, N, D, dOnes, 1, dXt1, ld1);
-    launch_scale_inputs(0, dX2, M, D, dOnes, 1, dXt2, ld2);
-    KernParams kp{MI355GP_STDPERIODIC, 1, D, variance};
-    kp.pw = dPw;
-    launch_periodic_gradx(0, kp, dXt1, ld1, N, dXt2, ld2, M, dW, M, 0, dOut);
-    HIP_CHECK(hipMemcpy(out, dOut, sizeof(double) * N * D, hipMemcpyDeviceToHost));
-    HIP_CHECK(hipGetLastError());
-    for (int64_t i = 0; i < N; ++i)
-        for (int q = 0; q < D; ++q) out[i * D + q] *= -0.5 * pw[(size_t)q] * pw[(size_t)(D + q)] * pw[(size_t)(D + q)];
-    return 0;
 }
 
 static int upload_noise(mi355gp_ctx* c, const double* noise, int64_t noise_len) {
@@ -778,91 +540,26 @@ static int prepare_parts(mi355gp_ctx* c, int nparts, const mi355gp_part* parts) 
         }
     }
     for (int i = 0; i < nparts; ++i) {
-        const mi355gp_part& in = parts[i];
         mi355gp_ctx::Part& p = c->parts[(size_t)i];
-        ARG_CHECK(((in.kind >= 0 && in.kind <= 5) || is_ext_kind(in.kind) || in.kind == MI355GP_COREGIONALIZE) && in.theta,
-                  "unknown covariance kind / NULL theta in a kernel part");
-        if (in.kind == MI355GP_COREGIONALIZE) {
-            ARG_CHECK(in.n_active == 1 && in.active_dims && in.active_dims[0] >= 0 && in.active_dims[0] < c->D,
-                      "Coregionalize (kind 8): n_active must be 1 (the input column of the output index)");
-            if (int rc = coreg_check_P(in.ard)) return rc;
-            const int P = in.ard, col = in.active_dims[0];
-            for (int k = 0; k < P * P; ++k) ARG_CHECK(std::isfinite(in.theta[k]), "Coregionalize (kind 8): B is not finite");
+        if (int rc = parse_part(parts[i], c->D, KS_STATIONARY | KS_STATIC | KS_EXT | KS_COREG, "exact-GP path", &p)) return rc;
+        if (p.coreg()) {
+            const int col = p.kp.col;
             if (c->hIdxCol != col) {                     // the training indices of this column, validated once per upload
                 c->hIdx.resize((size_t)c->n);
                 HIP_CHECK(hipMemcpy2D(c->hIdx.data(), sizeof(double), c->dX + col, sizeof(double) * c->D, sizeof(double), c->n,
                                       hipMemcpyDeviceToHost));
                 c->hIdxCol = col;
             }
-            if (int rc = coreg_check_index(c->hIdx.data(), c->n, 1, P, "training")) return rc;
-            p.dims.assign(1, col);
-            p.term = in.term;
-            p.ard_in = P;
-            p.theta.assign(in.theta, in.theta + P * P);
-            p.inv_ls.assign((size_t)c->D, 0.0);
-            p.inv_ls[(size_t)col] = 1.0;                 // the index column stays unscaled
-            p.kp = KernParams{MI355GP_COREGIONALIZE, P, c->D, in.theta[0]};
-            p.kp.col = col;
-            HIP_CHECK(hipMemcpyAsync(p.dPw, p.theta.data(), sizeof(double) * P * P, hipMemcpyHostToDevice, c->st));
-            p.kp.pw = p.dPw;
+            if (int rc = coreg_check_index(c->hIdx.data(), c->n, 1, p.kp.ard, "training")) return rc;
             if (!c->dCoregPart) HIP_CHECK(hipMalloc(&c->dCoregPart, sizeof(double) * grad_num_blocks(c->n) * COREG_REC));
-            continue;
         }
-        ARG_CHECK(in.theta[0] > 0.0, "variance must be positive");
-        p.dims.clear();
-        if (in.active_dims && in.n_active > 0) {
-            for (int a = 0; a < in.n_active; ++a) {
-                ARG_CHECK(in.active_dims[a] >= 0 && in.active_dims[a] < c->D, "active dimension out of range");
-                p.dims.push_back(in.active_dims[a]);
-            }
-        } else {
-            for (int q = 0; q < c->D; ++q) p.dims.push_back(q);
-        }
-        const int na = (int)p.dims.size();
-        p.term = in.term;
-        p.ard_in = in.ard;
-        if (is_ext_kind(in.kind)) {
-            double power = 0.0;
-            int nt = 0;
-            if (int rc = ext_setup(in.kind, in.ard, in.theta, p.dims, c->D, &p.inv_ls, &p.pw, &power, &nt)) return rc;
-            p.kp = KernParams{in.kind, (in.kind == MI355GP_STDPERIODIC || in.ard) ? 1 : 0, c->D, in.theta[0]};
-            p.kp.power = power;
-            if (in.kind == MI355GP_STDPERIODIC) {
-                HIP_CHECK(hipMemcpyAsync(p.dPw, p.pw.data(), sizeof(double) * 2 * c->D, hipMemcpyHostToDevice, c->st));
-                p.kp.pw = p.dPw;
-            }
-            p.theta.assign(in.theta, in.theta + nt);
-            continue;
-        }
-        const bool stationary = in.kind <= 3;
-        const int nl = stationary ? (in.ard ? na : 1) : 0;
-        p.term = in.term;
-        p.kp = KernParams{in.kind, (stationary && in.ard) ? 1 : 0, c->D, in.theta[0]};
-        p.theta.assign(in.theta, in.theta + 1 + nl);
-        p.inv_ls.assign((size_t)c->D, 0.0);
-        for (int a = 0; a < na && stationary; ++a) {
-            const double l = in.theta[1 + (in.ard ? a : 0)];
-            ARG_CHECK(l > 0.0, "lengthscales must be positive");
-            p.inv_ls[(size_t)p.dims[a]] = 1.0 / l;
+        if (!p.pw.empty()) {
+            HIP_CHECK(hipMemcpyAsync(p.dPw, p.pw.data(), sizeof(double) * p.pw.size(), hipMemcpyHostToDevice, c->st));
+            p.kp.pw = p.dPw;
         }
     }
-    c->terms.clear();
-    std::vector<int> ids;
-    bool any_product = false;
-    for (int i = 0; i < nparts; ++i) {
-        const int id = c->parts[(size_t)i].term;
-        size_t t = ids.size();
-        if (id != 0)                                   // term 0 = a plain summand of its own
-            for (t = 0; t < ids.size() && ids[t] != id; ++t) {}
-        if (t == ids.size()) {
-            ids.push_back(id);
-            c->terms.emplace_back();
-        } else {
-            any_product = true;
-        }
-        c->terms[t].push_back(i);
-    }
-    if (any_product && !c->Mbuf) HIP_CHECK(hipMalloc(&c->Mbuf, sizeof(double) * c->npad * c->npad));
+    c->terms = group_terms(c->parts);
+    if (has_product(c->terms) && !c->Mbuf) HIP_CHECK(hipMalloc(&c->Mbuf, sizeof(double) * c->npad * c->npad));
     return 0;
 }
 
@@ -885,21 +582,19 @@ int mi355gp_exact_inference_sum(mi355gp_ctx* c, int nparts, const mi355gp_part* 
     if (int rc = prepare_parts(c, nparts, parts)) return rc;
     if (int rc = upload_noise(c, noise, noise_len)) return rc;
     hipStream_t st = c->st;
-    c->kp = c->parts[0].kp;
-    c->theta = c->parts[0].theta;
     c->have_kernel = true;
     HIP_CHECK(hipEventRecord(c->ev[0], st));
     if (int rc = scale_parts(c)) return rc;
     // Ky = sum_t prod_f K_f + (noise + jitter) I   (add.py:58-72, prod.py:58-65)
     auto build = [&]() -> int {
-        build_expression(c, c->A, c->Mbuf, false, [&](int p, double* dst, const double* mul, int acc, bool first) {
+        emit_expression(c->terms, c->A, c->Mbuf, false, [&](int p, double* dst, const double* mul, int acc, bool first) {
             launch_kbuild_sym(st, c->parts[(size_t)p].kp, c->parts[(size_t)p].dXt, c->npad, c->n, c->npad, dst, c->dNoise,
                               noise_len, jitter + extra_jitter, /*lower_only=*/1, /*add_diag=*/first, acc, mul);
         });
         return 0;
     };
     build();
-    return run_pipeline(c, &gate, true, nullptr, out_scalars, alpha_out, dtheta_out, diag_dLdK_out, stage_ms, build);
+    return run_pipeline(c, &gate, true, out_scalars, alpha_out, dtheta_out, diag_dLdK_out, stage_ms, build);
 }
 
 // Student-t PROCESS inference (ExactStudentTInference.inference, exact_studentt_inference.py:20-52): the same pdinv +
@@ -916,26 +611,24 @@ int mi355gp_exact_studentt_sum(mi355gp_ctx* c, int nparts, const mi355gp_part* p
     const double zero = 0.0;
     if (int rc = upload_noise(c, &zero, 1)) return rc;
     hipStream_t st = c->st;
-    c->kp = c->parts[0].kp;
-    c->theta = c->parts[0].theta;
     c->have_kernel = true;
     HIP_CHECK(hipEventRecord(c->ev[0], st));
     if (int rc = scale_parts(c)) return rc;
     auto build = [&]() -> int {
-        build_expression(c, c->A, c->Mbuf, false, [&](int p, double* dst, const double* mul, int acc, bool first) {
+        emit_expression(c->terms, c->A, c->Mbuf, false, [&](int p, double* dst, const double* mul, int acc, bool first) {
             launch_kbuild_sym(st, c->parts[(size_t)p].kp, c->parts[(size_t)p].dXt, c->npad, c->n, c->npad, dst, c->dNoise, 1,
                               jitter + extra_jitter, 1, first, acc, mul);
         });
         return 0;
     };
     build();
-    return run_pipeline(c, &gate, true, nullptr, out_scalars, alpha_out, dtheta_out, nullptr, stage_ms, build, nu);
+    return run_pipeline(c, &gate, true, out_scalars, alpha_out, dtheta_out, nullptr, stage_ms, build, nu);
 }
 
 int mi355gp_exact_inference(mi355gp_ctx* c, int kind, int ard, const double* theta, const double* noise,
                             int64_t noise_len, double jitter, double extra_jitter, double* out_scalars,
                             double* alpha_out, double* dtheta_out, double* diag_dLdK_out, double* stage_ms) {
-    ARG_CHECK((kind >= 0 && kind <= 3) || is_ext_kind(kind), "unknown covariance kind");
+    if (int rc = check_kind(kind, KS_STATIONARY | KS_EXT, "mi355gp_exact_inference")) return rc;
     const mi355gp_part part{kind, ard, 0, nullptr, theta};
     return mi355gp_exact_inference_sum(c, 1, &part, noise, noise_len, jitter, extra_jitter, out_scalars, alpha_out,
                                        dtheta_out, diag_dLdK_out, stage_ms);
@@ -959,7 +652,7 @@ int mi355gp_inference_given_K(mi355gp_ctx* c, const double* K_host, const double
         return 0;
     };
     if (int rc = build()) return rc;
-    return run_pipeline(c, &gate, false, nullptr, out_scalars, alpha_out, nullptr, diag_dLdK_out, stage_ms, build);
+    return run_pipeline(c, &gate, false, out_scalars, alpha_out, nullptr, diag_dLdK_out, stage_ms, build);
 }
 
 int mi355gp_fetch(mi355gp_ctx* c, int which, double* out, int fortran_order) {
@@ -977,8 +670,8 @@ int mi355gp_fetch(mi355gp_ctx* c, int which, double* out, int fortran_order) {
             rc = -4;
         } else {
             double* scratch = nullptr;
-            if (has_product(c)) HIP_CHECK(hipMalloc(&scratch, sizeof(double) * n * n));
-            build_expression(c, tmp, scratch, false, [&](int p, double* dst, const double* mul, int acc, bool) {
+            if (has_product(c->terms)) HIP_CHECK(hipMalloc(&scratch, sizeof(double) * n * n));
+            emit_expression(c->terms, tmp, scratch, false, [&](int p, double* dst, const double* mul, int acc, bool) {
                 const mi355gp_ctx::Part& pt = c->parts[(size_t)p];                 // symmetric: no transpose needed
                 launch_kbuild_cross(st, pt.kp, pt.dXt, np, n, pt.dXt, np, n, dst, n, acc, /*diag_same=*/1, mul);
             });
@@ -1015,169 +708,117 @@ int mi355gp_fetch(mi355gp_ctx* c, int which, double* out, int fortran_order) {
 }
 
 // ---- stateless kernel-function entry points --------------------------------------------------------
-// Coregionalize (kind 8) with D = 1: X / X2 are the output-index columns themselves (read as Xt with ld = N, row 0)
-static int coreg_stateless_check(int ard, const double* theta, const double* X, int64_t N, const double* X2, int64_t M, int D) {
-    if (int rc = coreg_check_P(ard)) return rc;
-    ARG_CHECK(theta != nullptr, "theta is NULL");
-    ARG_CHECK(D == 1, "Coregionalize (kind 8): D must be 1 (the output-index column)");
-    for (int k = 0; k < ard * ard; ++k) ARG_CHECK(std::isfinite(theta[k]), "Coregionalize (kind 8): B is not finite");
-    if (int rc = coreg_check_index(X, N, 1, ard, "X")) return rc;
-    if (X2)
-        if (int rc = coreg_check_index(X2, M, 1, ard, "X2")) return rc;
-    return 0;
-}
-
-static int coreg_kern_K(int device, int P, const double* theta, const double* X, int64_t N, const double* X2, int64_t M,
-                        double* K_out) {
-    const bool sym = (X2 == nullptr);
-    if (sym) M = N;
-    DevBuf dX, dX2, dB, dK;
-    HIP_CHECK(dX.alloc(N));
-    HIP_CHECK(dB.alloc(P * P));
-    HIP_CHECK(dK.alloc(N * M));
-    HIP_CHECK(hipMemcpy(dX, X, sizeof(double) * N, hipMemcpyHostToDevice));
-    HIP_CHECK(hipMemcpy(dB, theta, sizeof(double) * P * P, hipMemcpyHostToDevice));
-    if (!sym) {
-        HIP_CHECK(dX2.alloc(M));
-        HIP_CHECK(hipMemcpy(dX2, X2, sizeof(double) * M, hipMemcpyHostToDevice));
+// The one part of a stateless call over all D columns of X, its inv_ls and pw on the device.  Coregionalize: D = 1, X / X2 are
+// the output-index columns themselves (their indices validated here).
+struct StatelessPart : PartSpec {
+    DevBuf dIl, dPw;
+    int load(int kind, int ard, const double* theta, int D, KindSet accepted, const char* where, const double* X, int64_t N,
+             const double* X2, int64_t M) {
+        const int col0 = 0;
+        const mi355gp_part in{kind, ard, kind == MI355GP_COREGIONALIZE ? 1 : 0, &col0, theta, 0};
+        if (int rc = parse_part(in, D, accepted, where, this)) return rc;
+        if (coreg()) {
+            ARG_CHECK(D == 1, "Coregionalize (kind 8): D must be 1 (the output-index column)");
+            if (int rc = coreg_check_index(X, N, 1, ard, "X")) return rc;
+            if (X2)
+                if (int rc = coreg_check_index(X2, M, 1, ard, "X2")) return rc;
+        }
+        HIP_CHECK(dIl.alloc(D));
+        HIP_CHECK(hipMemcpy(dIl, inv_ls.data(), sizeof(double) * D, hipMemcpyHostToDevice));
+        if (!pw.empty()) {
+            HIP_CHECK(dPw.alloc(pw.size()));
+            HIP_CHECK(hipMemcpy(dPw, pw.data(), sizeof(double) * pw.size(), hipMemcpyHostToDevice));
+            kp.pw = dPw;
+        }
+        return 0;
     }
-    KernParams kp{MI355GP_COREGIONALIZE, P, 1, theta[0]};
-    kp.pw = dB;
-    launch_kbuild_cross(0, kp, dX, N, N, sym ? (double*)dX : (double*)dX2, M, M, dK, M, 0, /*diag_same=*/sym ? 1 : 0);
-    HIP_CHECK(hipMemcpy(K_out, dK, sizeof(double) * N * M, hipMemcpyDeviceToHost));
-    HIP_CHECK(hipGetLastError());
-    return 0;
-}
+};
 
-// S[a][b] = sum over i with idx_i = a, j with idx2_j = b of dL_dK[i][j] (every element once, no symmetric completion);
-// GPy's dL_dK_small is its transpose (coregionalize.py:130-137)
-static int coreg_update_gradients(int device, int P, const double* theta, const double* dL_dK, const double* X, int64_t N,
-                                  const double* X2, int64_t M, double* out) {
-    const bool sym = (X2 == nullptr);
-    if (sym) M = N;
-    DevBuf dX, dX2, dG, dPart, dOut;
-    HIP_CHECK(dX.alloc(N));
-    HIP_CHECK(dG.alloc(N * M));
-    HIP_CHECK(dPart.alloc((size_t)2048 * COREG_REC));
-    HIP_CHECK(dOut.alloc(P * P));
-    HIP_CHECK(hipMemcpy(dX, X, sizeof(double) * N, hipMemcpyHostToDevice));
-    HIP_CHECK(hipMemcpy(dG, dL_dK, sizeof(double) * N * M, hipMemcpyHostToDevice));
-    if (!sym) {
-        HIP_CHECK(dX2.alloc(M));
-        HIP_CHECK(hipMemcpy(dX2, X2, sizeof(double) * M, hipMemcpyHostToDevice));
+// rows x D points (host) uploaded and scaled by inv_ls into dimension-major t (D x ld)
+struct ScaledInputs {
+    DevBuf raw, t;
+    long ld = 0;
+    int load(const double* X, int64_t rows, int D, const double* dIl) {
+        ld = round_up(rows, 64);
+        HIP_CHECK(raw.alloc(rows * D));
+        HIP_CHECK(t.alloc(D * ld));
+        HIP_CHECK(hipMemcpy(raw, X, sizeof(double) * rows * D, hipMemcpyHostToDevice));
+        launch_scale_inputs(0, raw, rows, D, dIl, 1, t, ld);
+        return 0;
     }
-    KernParams kp{MI355GP_COREGIONALIZE, P, 1, theta[0]};
-    const int nb = launch_grad_coreg(0, false, kp, dX, N, N, sym ? (double*)dX : (double*)dX2, M, M, dG, M, nullptr, 0, dPart);
-    launch_reduce_partials(0, dPart, nb, P * P, dOut);
-    HIP_CHECK(hipMemcpy(out, dOut, sizeof(double) * P * P, hipMemcpyDeviceToHost));
-    HIP_CHECK(hipGetLastError());
-    return 0;
-}
+};
 
 int mi355gp_kern_K(int device, int kind, int ard, const double* theta, const double* X, int64_t N,
                    const double* X2, int64_t M, int D, double* K_out) {
     ARG_CHECK(X && K_out && N > 0 && D > 0, "mi355gp_kern_K: bad arguments");
     HIP_CHECK(hipSetDevice(device));
-    if (kind == MI355GP_COREGIONALIZE) {
-        ARG_CHECK(X2 == nullptr || M > 0, "mi355gp_kern_K: M must be positive");
-        if (int rc = coreg_stateless_check(ard, theta, X, N, X2, M, D)) return rc;
-        return coreg_kern_K(device, ard, theta, X, N, X2, M, K_out);
-    }
-    std::vector<double> inv_ls, pw;
-    double power = 0.0;
-    if (int rc = check_theta(kind, ard, theta, D, &inv_ls, &pw, &power)) return rc;
     const bool sym = (X2 == nullptr);
     if (sym) M = N;
     ARG_CHECK(M > 0, "mi355gp_kern_K: M must be positive");
-    const long ld1 = round_up(N, 64), ld2 = round_up(M, 64);
-    DevBuf dX, dX2, dXt1, dXt2, dIl, dK;
-    HIP_CHECK(dX.alloc(N * D));
-    HIP_CHECK(dXt1.alloc(D * ld1));
-    HIP_CHECK(dIl.alloc(D));
+    StatelessPart pt;
+    if (int rc = pt.load(kind, ard, theta, D, KS_STATIONARY | KS_EXT | KS_COREG, "mi355gp_kern_K", X, N, X2, M)) return rc;
+    ScaledInputs x1, x2;
+    if (int rc = x1.load(X, N, D, pt.dIl)) return rc;
+    if (!sym)
+        if (int rc = x2.load(X2, M, D, pt.dIl)) return rc;
+    const ScaledInputs& y = sym ? x1 : x2;
+    DevBuf dK;
     HIP_CHECK(dK.alloc(N * M));
-    HIP_CHECK(hipMemcpy(dX, X, sizeof(double) * N * D, hipMemcpyHostToDevice));
-    HIP_CHECK(hipMemcpy(dIl, inv_ls.data(), sizeof(double) * D, hipMemcpyHostToDevice));
-    launch_scale_inputs(0, dX, N, D, dIl, ard ? 1 : 0, dXt1, ld1);
-    const double* pXt2 = dXt1;
-    if (!sym) {
-        HIP_CHECK(dX2.alloc(M * D));
-        HIP_CHECK(dXt2.alloc(D * ld2));
-        HIP_CHECK(hipMemcpy(dX2, X2, sizeof(double) * M * D, hipMemcpyHostToDevice));
-        launch_scale_inputs(0, dX2, M, D, dIl, ard ? 1 : 0, dXt2, ld2);
-        pXt2 = dXt2;
-    }
-    KernParams kp{kind, ard ? 1 : 0, D, theta[0]};
-    DevBuf dPw;
-    if (int rc = ext_params(&kp, pw, power, &dPw)) return rc;
-    launch_kbuild_cross(0, kp, dXt1, ld1, N, pXt2, sym ? ld1 : ld2, M, dK, M);
+    launch_kbuild_cross(0, pt.kp, x1.t, x1.ld, N, y.t, y.ld, M, dK, M);
     HIP_CHECK(hipMemcpy(K_out, dK, sizeof(double) * N * M, hipMemcpyDeviceToHost));
     HIP_CHECK(hipGetLastError());
     return 0;
 }
 
 int mi355gp_kern_Kdiag(int kind, const double* theta, int64_t N, double* out) {
-    ARG_CHECK(((kind >= 0 && kind <= 3) || is_ext_kind(kind)) && theta && out && N >= 0, "mi355gp_kern_Kdiag: bad arguments");
+    ARG_CHECK(kind_in(kind, KS_STATIONARY | KS_EXT) && theta && out && N >= 0, "mi355gp_kern_Kdiag: bad arguments");
     // stationary: K(x,x) = variance (stationary.py:170-173); StdPeriodic likewise (standard_periodic.py:105-109)
     for (int64_t i = 0; i < N; ++i) out[i] = theta[0];
     return 0;
 }
 
+// Coregionalize: S[a][b] = sum over i with idx_i = a, j with idx2_j = b of dL_dK[i][j] (every element once, no symmetric
+// completion); GPy's dL_dK_small is its transpose (coregionalize.py:130-137)
 int mi355gp_update_gradients_full(int device, int kind, int ard, const double* theta, const double* dL_dK,
                                   const double* X, int64_t N, const double* X2, int64_t M, int D,
                                   double* dtheta_out) {
     ARG_CHECK(dL_dK && X && dtheta_out && N > 0 && D > 0, "mi355gp_update_gradients_full: bad arguments");
     HIP_CHECK(hipSetDevice(device));
-    if (kind == MI355GP_COREGIONALIZE) {
-        ARG_CHECK(X2 == nullptr || M > 0, "mi355gp_update_gradients_full: M must be positive");
-        if (int rc = coreg_stateless_check(ard, theta, X, N, X2, M, D)) return rc;
-        return coreg_update_gradients(device, ard, theta, dL_dK, X, N, X2, M, dtheta_out);
-    }
-    std::vector<double> inv_ls, pw;
-    double power = 0.0;
-    if (int rc = check_theta(kind, ard, theta, D, &inv_ls, &pw, &power)) return rc;
     const bool sym = (X2 == nullptr);
     if (sym) M = N;
-    const long ld1 = round_up(N, 64), ld2 = round_up(M, 64);
-    const int groups = (D + 31) / 32;
-    DevBuf dX, dX2, dXt1, dXt2, dIl, dG, dPart, dOut;
-    HIP_CHECK(dX.alloc(N * D));
-    HIP_CHECK(dXt1.alloc(D * ld1));
-    HIP_CHECK(dIl.alloc(D));
+    ARG_CHECK(kind != MI355GP_COREGIONALIZE || M > 0, "mi355gp_update_gradients_full: M must be positive");
+    StatelessPart pt;
+    if (int rc = pt.load(kind, ard, theta, D, KS_STATIONARY | KS_EXT | KS_COREG, "mi355gp_update_gradients_full", X, N, X2, M))
+        return rc;
+    ScaledInputs x1, x2;
+    if (int rc = x1.load(X, N, D, pt.dIl)) return rc;
+    if (!sym)
+        if (int rc = x2.load(X2, M, D, pt.dIl)) return rc;
+    const ScaledInputs& y = sym ? x1 : x2;
+    const int groups = (D + 31) / 32, nrec = pt.ext() ? 2 : 1;
+    const size_t nsums = std::max((size_t)2 * groups * GP_STRIDE, (size_t)COREG_REC);
+    DevBuf dG, dPart, dOut;
     HIP_CHECK(dG.alloc(N * M));
-    HIP_CHECK(dPart.alloc(2 * groups * 2048 * GP_STRIDE));          // second records: RatQuad / StdPeriodic
-    HIP_CHECK(dOut.alloc(2 * groups * GP_STRIDE));
-    HIP_CHECK(hipMemcpy(dX, X, sizeof(double) * N * D, hipMemcpyHostToDevice));
-    HIP_CHECK(hipMemcpy(dIl, inv_ls.data(), sizeof(double) * D, hipMemcpyHostToDevice));
+    // (RatQuad / StdPeriodic: two records per block and group)
+    HIP_CHECK(dPart.alloc(std::max((size_t)2 * groups * 2048 * GP_STRIDE, (size_t)2048 * COREG_REC)));
+    HIP_CHECK(dOut.alloc(nsums));
     HIP_CHECK(hipMemcpy(dG, dL_dK, sizeof(double) * N * M, hipMemcpyHostToDevice));
-    launch_scale_inputs(0, dX, N, D, dIl, ard ? 1 : 0, dXt1, ld1);
-    const double* pXt2 = dXt1;
-    if (!sym) {
-        HIP_CHECK(dX2.alloc(M * D));
-        HIP_CHECK(dXt2.alloc(D * ld2));
-        HIP_CHECK(hipMemcpy(dX2, X2, sizeof(double) * M * D, hipMemcpyHostToDevice));
-        launch_scale_inputs(0, dX2, M, D, dIl, ard ? 1 : 0, dXt2, ld2);
-        pXt2 = dXt2;
+    if (pt.coreg()) {
+        const int nb = launch_grad_coreg(0, false, pt.kp, x1.t, x1.ld, N, y.t, y.ld, M, dG, M, nullptr, 0, dPart);
+        launch_reduce_partials(0, dPart, nb, ard * ard, dOut);
+    } else {
+        const int nb = grad_generic_num_blocks(N, M);
+        launch_grad_generic(0, pt.kp, x1.t, x1.ld, N, y.t, y.ld, M, sym ? 1 : 0, dG, M, dPart, GP_STRIDE);
+        for (int r = 0; r < nrec; ++r)
+            for (int g = 0; g < (pt.kp.ard ? groups : 1); ++g)
+                launch_reduce_partials(0, dPart + ((long)r * groups + g) * nb * GP_STRIDE, nb, GP_STRIDE,
+                                       dOut + ((long)r * groups + g) * GP_STRIDE);
     }
-    KernParams kp{kind, ard ? 1 : 0, D, theta[0]};
-    DevBuf dPw;
-    if (int rc = ext_params(&kp, pw, power, &dPw)) return rc;
-    const int nb = grad_generic_num_blocks(N, M);
-    launch_grad_generic(0, kp, dXt1, ld1, N, pXt2, sym ? ld1 : ld2, M, sym ? 1 : 0, dG, M, dPart, GP_STRIDE);
-    const int nrec = is_ext_kind(kind) ? 2 : 1;
-    for (int r = 0; r < nrec; ++r)
-        for (int g = 0; g < (kp.ard ? groups : 1); ++g)
-            launch_reduce_partials(0, dPart + ((long)r * groups + g) * nb * GP_STRIDE, nb, GP_STRIDE,
-                                   dOut + ((long)r * groups + g) * GP_STRIDE);
-    std::vector<double> sums((size_t)nrec * groups * GP_STRIDE, 0.0);
-    HIP_CHECK(hipMemcpy(sums.data(), dOut, sizeof(double) * sums.size(), hipMemcpyDeviceToHost));
+    std::vector<double> sums(nsums, 0.0);
+    HIP_CHECK(hipMemcpy(sums.data(), dOut, sizeof(double) * (pt.coreg() ? ard * ard : nrec * groups * GP_STRIDE),
+                        hipMemcpyDeviceToHost));
     HIP_CHECK(hipGetLastError());
-    if (is_ext_kind(kind)) {
-        std::vector<int> dims((size_t)D);
-        for (int q = 0; q < D; ++q) dims[(size_t)q] = q;
-        finish_ext(kind, ard, theta, dims, sums.data(), sums.data() + (size_t)groups * GP_STRIDE, dtheta_out);
-        return 0;
-    }
-    finish_dtheta(kp, theta, sums.data(), dtheta_out);
+    part_dtheta(pt, sums.data(), sums.data() + (size_t)groups * GP_STRIDE, dtheta_out);
     return 0;
 }
 
@@ -1188,48 +829,53 @@ int mi355gp_gradients_X(int device, int kind, int ard, const double* theta, cons
                         int64_t N, const double* X2, int64_t M, int D, double* out) {
     ARG_CHECK(dL_dK && X && out && N > 0 && D > 0, "mi355gp_gradients_X: bad arguments");
     HIP_CHECK(hipSetDevice(device));
-    std::vector<double> inv_ls, pw;
-    double power = 0.0;
-    if (int rc = check_theta(kind, ard, theta, D, &inv_ls, &pw, &power)) return rc;
+    StatelessPart pt;
+    if (int rc = pt.load(kind, ard, theta, D, KS_STATIONARY | KS_EXT, "mi355gp_gradients_X", nullptr, 0, nullptr, 0)) return rc;
     const bool sym = (X2 == nullptr);
     if (sym) { M = N; X2 = X; }
     ARG_CHECK(M > 0, "mi355gp_gradients_X: M must be positive");
-    if (kind == MI355GP_STDPERIODIC) return periodic_gradients_X(theta[0], pw, dL_dK, X, N, X2, M, D, sym, out);
+    ScaledInputs xc, xr;                                     // X and X2
+    if (int rc = xc.load(X, N, D, pt.dIl)) return rc;
+    if (int rc = xr.load(X2, M, D, pt.dIl)) return rc;
+    if (kind == MI355GP_STDPERIODIC) {
+        // StdPeriodic.gradients_X (standard_periodic.py:574-580): dX[i][q] = -pi / (2 T_q l_q^2) sum_j W_ij K_ij sin(2 Delta_ijq),
+        // W = dL_dK (+ dL_dK^T against X itself), as a row reduction on the device (k_periodic_gradx)
+        std::vector<double> W((size_t)N * M);
+        for (int64_t i = 0; i < N; ++i)
+            for (int64_t j = 0; j < M; ++j) W[(size_t)i * M + j] = sym ? dL_dK[i * M + j] + dL_dK[j * M + i] : dL_dK[i * M + j];
+        DevBuf dW, dOut;
+        HIP_CHECK(dW.alloc(N * M));
+        HIP_CHECK(dOut.alloc(N * D));
+        HIP_CHECK(hipMemcpy(dW, W.data(), sizeof(double) * N * M, hipMemcpyHostToDevice));
+        launch_periodic_gradx(0, pt.kp, xc.t, xc.ld, N, xr.t, xr.ld, M, dW, M, 0, dOut);
+        HIP_CHECK(hipMemcpy(out, dOut, sizeof(double) * N * D, hipMemcpyDeviceToHost));
+        HIP_CHECK(hipGetLastError());
+        const std::vector<double>& pw = pt.pw;
+        for (int64_t i = 0; i < N; ++i)
+            for (int q = 0; q < D; ++q) out[i * D + q] *= -0.5 * pw[(size_t)q] * pw[(size_t)(D + q)] * pw[(size_t)(D + q)];
+        return 0;
+    }
     // transposed weights G' (M x N): rows = X2 points, columns = X points
     std::vector<double> Gt((size_t)M * N);
     for (int64_t i = 0; i < N; ++i)
         for (int64_t j = 0; j < M; ++j)
             Gt[(size_t)j * N + i] = sym ? dL_dK[i * M + j] + dL_dK[j * M + i] : dL_dK[i * M + j];
-    const long ldr = round_up(M, 64), ldc = round_up(N, 64);
-    DevBuf dXr, dXc, dXtR, dXtC, dIl, dG, dPart, dCol, dHX;
-    HIP_CHECK(dXr.alloc(M * D));
-    HIP_CHECK(dXc.alloc(N * D));
-    HIP_CHECK(dXtR.alloc(D * ldr));
-    HIP_CHECK(dXtC.alloc(D * ldc));
-    HIP_CHECK(dIl.alloc(D));
+    DevBuf dG, dPart, dCol, dHX;
     HIP_CHECK(dG.alloc(M * N));
     HIP_CHECK(dPart.alloc(2 * 2048 * GP_STRIDE * ((D + 31) / 32)));   // every group, and the second records of RatQuad
     HIP_CHECK(dCol.alloc(64 * N * (D + 1)));
     HIP_CHECK(dHX.alloc(N * (D + 1)));
-    HIP_CHECK(hipMemcpy(dXr, X2, sizeof(double) * M * D, hipMemcpyHostToDevice));
-    HIP_CHECK(hipMemcpy(dXc, X, sizeof(double) * N * D, hipMemcpyHostToDevice));
-    HIP_CHECK(hipMemcpy(dIl, inv_ls.data(), sizeof(double) * D, hipMemcpyHostToDevice));
     HIP_CHECK(hipMemcpy(dG, Gt.data(), sizeof(double) * M * N, hipMemcpyHostToDevice));
-    launch_scale_inputs(0, dXr, M, D, dIl, ard ? 1 : 0, dXtR, ldr);
-    launch_scale_inputs(0, dXc, N, D, dIl, ard ? 1 : 0, dXtC, ldc);
-    KernParams kp{kind, ard ? 1 : 0, D, theta[0]};
-    DevBuf dPw;
-    if (int rc = ext_params(&kp, pw, power, &dPw)) return rc;
-    launch_grad_generic(0, kp, dXtR, ldr, M, dXtC, ldc, N, 0, dG, N, dPart, GP_STRIDE, dG, N);   // H in place
-    const int ns = launch_colreduce_multi(0, dG, N, M, N, dXtR, 1, ldr, D, 1, dCol);
+    launch_grad_generic(0, pt.kp, xr.t, xr.ld, M, xc.t, xc.ld, N, 0, dG, N, dPart, GP_STRIDE, dG, N);   // H in place
+    const int ns = launch_colreduce_multi(0, dG, N, M, N, xr.t, 1, xr.ld, D, 1, dCol);
     launch_sum_splits(0, dCol, N * (D + 1), ns, 0, dHX);
-    std::vector<double> HX((size_t)N * (D + 1)), Xs((size_t)D * ldc);
+    std::vector<double> HX((size_t)N * (D + 1)), Xs((size_t)D * xc.ld);
     HIP_CHECK(hipMemcpy(HX.data(), dHX, sizeof(double) * HX.size(), hipMemcpyDeviceToHost));
-    HIP_CHECK(hipMemcpy(Xs.data(), dXtC, sizeof(double) * Xs.size(), hipMemcpyDeviceToHost));
+    HIP_CHECK(hipMemcpy(Xs.data(), xc.t, sizeof(double) * Xs.size(), hipMemcpyDeviceToHost));
     HIP_CHECK(hipGetLastError());
     for (int64_t i = 0; i < N; ++i)
         for (int q = 0; q < D; ++q)
-            out[i * D + q] = (Xs[(size_t)q * ldc + i] * HX[i * (D + 1) + D] - HX[i * (D + 1) + q]) * inv_ls[ard ? q : 0];
+            out[i * D + q] = (Xs[(size_t)q * xc.ld + i] * HX[i * (D + 1) + D] - HX[i * (D + 1) + q]) * pt.inv_ls[(size_t)q];
     return 0;
 }
 
@@ -1342,8 +988,6 @@ int mi355gp_predict_sum(mi355gp_ctx* c, int nparts, const mi355gp_part* parts, c
     hipStream_t st = c->st;
     const long n = c->n, np = c->npad, D = c->D, mp = round_up(M, NB), ld2 = round_up(M, 64);
     // (re)scale the training inputs for these parameters (normally identical to the inference call's)
-    c->kp = c->parts[0].kp;
-    c->theta = c->parts[0].theta;
     c->have_kernel = true;
     if (int rc = scale_parts(c)) return rc;
     DevBuf dXn, dXt2, dKx, dTmp, dMu, dVar;
@@ -1356,7 +1000,7 @@ int mi355gp_predict_sum(mi355gp_ctx* c, int nparts, const mi355gp_part* parts, c
     HIP_CHECK(hipMemcpyAsync(dXn, Xnew, sizeof(double) * M * D, hipMemcpyHostToDevice, st));
     HIP_CHECK(hipMemsetAsync(dKx, 0, sizeof(double) * np * mp, st));
     if (full_cov && var_out) HIP_CHECK(hipMemsetAsync(dVar, 0, sizeof(double) * mp * mp, st));
-    const double kdiag = expression_kdiag(c);                   // Kdiag(X*): sum over terms of the product of variances
+    const double kdiag = expression_kdiag(c->parts, c->terms);                   // Kdiag(X*): sum over terms of the product of variances
     DevBuf dKd;                                                 // ... or per point, with Coregionalize parts
     const bool kd_points = has_coreg(c) && !full_cov && var_out;
     std::vector<double> kd;
@@ -1366,7 +1010,7 @@ int mi355gp_predict_sum(mi355gp_ctx* c, int nparts, const mi355gp_part* parts, c
         HIP_CHECK(hipMemcpyAsync(dKd, kd.data(), sizeof(double) * M, hipMemcpyHostToDevice, st));
     }
     DevBuf dScr1, dScr2;
-    if (has_product(c)) {
+    if (has_product(c->terms)) {
         HIP_CHECK(dScr1.alloc(np * mp));
         if (full_cov && var_out) HIP_CHECK(dScr2.alloc(mp * mp));
     }
@@ -1376,13 +1020,13 @@ int mi355gp_predict_sum(mi355gp_ctx* c, int nparts, const mi355gp_part* parts, c
         if (e != hipSuccess) herr = e;
         launch_scale_inputs(st, dXn, M, c->D, c->dInvLs, 1, dXt2, ld2);
     };
-    build_expression(c, dKx, dScr1, true, [&](int p, double* dst, const double* mul, int acc, bool) {
+    emit_expression(c->terms, dKx, dScr1, true, [&](int p, double* dst, const double* mul, int acc, bool) {
         const mi355gp_ctx::Part& pt = c->parts[(size_t)p];
         scale_new(pt);
         launch_kbuild_cross(st, pt.kp, pt.dXt, np, n, dXt2, ld2, M, dst, mp, acc, 0, mul);                 // K(X, X*) (n x M)
     });
     if (full_cov && var_out)
-        build_expression(c, dVar, dScr2, true, [&](int p, double* dst, const double* mul, int acc, bool) {
+        emit_expression(c->terms, dVar, dScr2, true, [&](int p, double* dst, const double* mul, int acc, bool) {
             const mi355gp_ctx::Part& pt = c->parts[(size_t)p];
             scale_new(pt);
             launch_kbuild_cross(st, pt.kp, dXt2, ld2, M, dXt2, ld2, M, dst, mp, acc, /*diag_same=*/1, mul);  // K(X*, X*)
@@ -1429,12 +1073,10 @@ int mi355gp_predictive_gradients_sum(mi355gp_ctx* c, int nparts, const mi355gp_p
     HIP_CHECK(hipSetDevice(c->device));
     EngineShared gate(c->device);
     if (int rc = prepare_parts(c, nparts, parts)) return rc;
-    ARG_CHECK(!has_product(c), "mi355gp_predictive_gradients: product kernels are not supported on the device");
+    ARG_CHECK(!has_product(c->terms), "mi355gp_predictive_gradients: product kernels are not supported on the device");
     ARG_CHECK(!has_coreg(c), "mi355gp_predictive_gradients: Coregionalize (kind 8) parts are not supported on the device");
     hipStream_t st = c->st;
     const long n = c->n, np = c->npad, D = c->D, Dy = c->Dy, mp = round_up(M, NB), ld2 = round_up(M, 64);
-    c->kp = c->parts[0].kp;
-    c->theta = c->parts[0].theta;
     c->have_kernel = true;
     if (int rc = scale_parts(c)) return rc;
     DevBuf dXn, dXt2, dU, dT, dG, dH, dPart, dCol, dHX;
@@ -1456,7 +1098,7 @@ int mi355gp_predictive_gradients_sum(mi355gp_ctx* c, int nparts, const mi355gp_p
     };
     if (dvar_out) {     // U = Ky^-1 K(X, X*)
         HIP_CHECK(hipMemsetAsync(dU, 0, sizeof(double) * np * mp, st));
-        build_expression(c, dU, nullptr, true, [&](int p, double* dst, const double* mul, int acc, bool) {
+        emit_expression(c->terms, dU, nullptr, true, [&](int p, double* dst, const double* mul, int acc, bool) {
             const mi355gp_ctx::Part& pt = c->parts[(size_t)p];
             scale_new(pt);
             launch_kbuild_cross(st, pt.kp, pt.dXt, np, n, dXt2, ld2, M, dst, mp, acc, 0, mul);
@@ -1482,7 +1124,7 @@ int mi355gp_predictive_gradients_sum(mi355gp_ctx* c, int nparts, const mi355gp_p
         }
         for (size_t pi = 0; pi < c->parts.size(); ++pi) {
             const mi355gp_ctx::Part& pt = c->parts[pi];
-            if (pt.kp.kind == 4 || pt.kp.kind == 5) continue;          // White / Bias: no dependence on X* (static.py)
+            if (pt.is_static()) continue;                                        // White / Bias: no dependence on X* (static.py)
             scale_new(pt);
             HIP_CHECK(herr);
             if (pt.kp.kind == MI355GP_STDPERIODIC) {                    // not a function of r: the row reduction instead of H
@@ -1549,7 +1191,7 @@ int mi355gp_covariance_between_points(mi355gp_ctx* c, int nparts, const mi355gp_
     HIP_CHECK(hipMemsetAsync(dK2, 0, sizeof(double) * np * m2p, st));
     HIP_CHECK(hipMemsetAsync(dC, 0, sizeof(double) * m1p * m2p, st));
     DevBuf dS1, dS2, dS3;
-    if (has_product(c)) {
+    if (has_product(c->terms)) {
         HIP_CHECK(dS1.alloc(np * m1p));
         HIP_CHECK(dS2.alloc(np * m2p));
         HIP_CHECK(dS3.alloc(m1p * m2p));
@@ -1561,17 +1203,17 @@ int mi355gp_covariance_between_points(mi355gp_ctx* c, int nparts, const mi355gp_
         launch_scale_inputs(st, dA, M1, c->D, c->dInvLs, 1, dXtA, l1);
         launch_scale_inputs(st, dB, M2, c->D, c->dInvLs, 1, dXtB, l2);
     };
-    build_expression(c, dK1, dS1, true, [&](int p, double* dst, const double* mul, int acc, bool) {
+    emit_expression(c->terms, dK1, dS1, true, [&](int p, double* dst, const double* mul, int acc, bool) {
         const mi355gp_ctx::Part& pt = c->parts[(size_t)p];
         scale_new(pt);
         launch_kbuild_cross(st, pt.kp, pt.dXt, np, n, dXtA, l1, M1, dst, m1p, acc, 0, mul);
     });
-    build_expression(c, dK2, dS2, true, [&](int p, double* dst, const double* mul, int acc, bool) {
+    emit_expression(c->terms, dK2, dS2, true, [&](int p, double* dst, const double* mul, int acc, bool) {
         const mi355gp_ctx::Part& pt = c->parts[(size_t)p];
         scale_new(pt);
         launch_kbuild_cross(st, pt.kp, pt.dXt, np, n, dXtB, l2, M2, dst, m2p, acc, 0, mul);
     });
-    build_expression(c, dC, dS3, true, [&](int p, double* dst, const double* mul, int acc, bool) {
+    emit_expression(c->terms, dC, dS3, true, [&](int p, double* dst, const double* mul, int acc, bool) {
         const mi355gp_ctx::Part& pt = c->parts[(size_t)p];
         scale_new(pt);
         launch_kbuild_cross(st, pt.kp, dXtA, l1, M1, dXtB, l2, M2, dst, m2p, acc, 0, mul);
@@ -1589,7 +1231,7 @@ int mi355gp_covariance_between_points(mi355gp_ctx* c, int nparts, const mi355gp_
 
 int mi355gp_predict(mi355gp_ctx* c, int kind, int ard, const double* theta, const double* Xnew, int64_t M,
                     double* mu_out, double* var_out, int full_cov) {
-    ARG_CHECK((kind >= 0 && kind <= 3) || is_ext_kind(kind), "unknown covariance kind");
+    if (int rc = check_kind(kind, KS_STATIONARY | KS_EXT, "mi355gp_predict")) return rc;
     const mi355gp_part part{kind, ard, 0, nullptr, theta};
     return mi355gp_predict_sum(c, 1, &part, Xnew, M, mu_out, var_out, full_cov);
 }

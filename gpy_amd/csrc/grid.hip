@@ -31,8 +31,8 @@
 #include "../../include/mi355gp_debug.h"
 #include "gemm_tile.h"
 #include "internal.h"
+#include "parts.h"
 
-#define GP_STRIDE 34
 #define LOG_2_PI 1.8378770664093454836
 #define ARGCHK(cond, msg)                 \
     do {                                  \
@@ -1252,9 +1252,9 @@ int mi355gp_grid_set_data(mi355gp_grid* g, const double* X, int64_t N, int D, co
 }  // extern "C"
 
 // one evaluation on all local ranks
-static int grid_run(mi355gp_grid* g, KernParams kp, const double* theta, const std::vector<double>& inv_ls,
-                    const double* noise, int64_t noise_len, double jit, double* out_scalars, double* alpha_out,
+static int grid_run(mi355gp_grid* g, const PartSpec& pt, const double* noise, int64_t noise_len, double jit, double* out_scalars, double* alpha_out,
                     double* dtheta_out, double* diag_out, double* stage_ms, int attempt = 0) {
+    const KernParams& kp = pt.kp;
     const long nb = g->nb, T = g->T, n = g->n;
     const int Pr = g->Pr, Pc = g->Pc, Dy = g->Dy, D = g->D, q = (int)(nb / NB);
     const size_t tile = (size_t)nb * nb;
@@ -1277,7 +1277,7 @@ static int grid_run(mi355gp_grid* g, KernParams kp, const double* theta, const s
     // ---- covariance tiles: K(X_rows, X_cols) + diagonal fix-up -------------------------------------------
     for (GridRank& r : g->ranks) {
         hipStream_t st = r.st;
-        HIP_CHECK(hipMemcpyAsync(r.invls, inv_ls.data(), sizeof(double) * D, hipMemcpyHostToDevice, st));
+        HIP_CHECK(hipMemcpyAsync(r.invls, pt.inv_ls.data(), sizeof(double) * D, hipMemcpyHostToDevice, st));
         HIP_CHECK(hipMemcpyAsync(r.noise, noise, sizeof(double) * noise_len, hipMemcpyHostToDevice, st));
         launch_scale_inputs(st, r.XsR, r.LR, D, r.invls, kp.ard, r.XtR, r.LR);
         launch_scale_inputs(st, r.XsC, r.LC, D, r.invls, kp.ard, r.XtC, r.LC);
@@ -1555,7 +1555,7 @@ static int grid_run(mi355gp_grid* g, KernParams kp, const double* theta, const s
             r.ws.persist = 0;
         }
         if (attempt == 0)
-            return grid_run(g, kp, theta, inv_ls, noise, noise_len, jit, out_scalars, alpha_out, dtheta_out, diag_out, stage_ms, 1);
+            return grid_run(g, pt, noise, noise_len, jit, out_scalars, alpha_out, dtheta_out, diag_out, stage_ms, 1);
         mi355gp_set_error("mi355gp_grid_exact_inference: a tile factorisation aborted twice");
         return -6;
     }
@@ -1597,12 +1597,7 @@ static int grid_run(mi355gp_grid* g, KernParams kp, const double* theta, const s
             for (int d = 0; d < Dy; ++d) a2 += alpha[i * Dy + d] * alpha[i * Dy + d];
             diag_out[i] = 0.5 * (a2 - Dy * dW[i]);
         }
-    if (dtheta_out) {
-        dtheta_out[0] = sums[0] / kp.variance;
-        if (!kp.ard) dtheta_out[1] = -sums[1] / theta[1];
-        else
-            for (int qd = 0; qd < D; ++qd) dtheta_out[1 + qd] = -sums[(qd / 32) * GP_STRIDE + 2 + (qd % 32)] / theta[1 + qd];
-    }
+    if (dtheta_out) part_dtheta(pt, sums.data(), nullptr, dtheta_out);
     return 0;
 }
 
@@ -1613,8 +1608,7 @@ int mi355gp_grid_exact_inference(mi355gp_grid* g, int kind, int ard, const doubl
                                  double* alpha_out, double* dtheta_out, double* diag_dLdK_out, double* stage_ms) {
     ARGCHK(g && g->n > 0, "mi355gp_grid_exact_inference: set_data first");
     ARGCHK(out_scalars && theta && noise, "mi355gp_grid_exact_inference: NULL argument");
-    ARGCHK(kind != 8, "Coregionalize (kind 8) runs on the exact-GP path only, not the grid path");
-    ARGCHK(kind >= 0 && kind <= 3, "unknown covariance kind");     // (the exact-only kinds 6 / 7 included)
+    if (int rc = check_kind(kind, KS_STATIONARY, "grid path")) return rc;     // (not the exact-only kinds 6 / 7 / 8)
     if (g->single) {
         double ms[MI355GP_NUM_T];
         const int rc = mi355gp_exact_inference(g->single, kind, ard, theta, noise, noise_len, jitter, extra_jitter, out_scalars,
@@ -1631,16 +1625,10 @@ int mi355gp_grid_exact_inference(mi355gp_grid* g, int kind, int ard, const doubl
         return rc;
     }
     ARGCHK(noise_len == 1 || noise_len == g->n, "noise must have 1 or N entries");
-    ARGCHK(theta[0] > 0.0, "variance must be positive");
+    PartSpec pt;
+    if (int rc = parse_part(mi355gp_part{kind, ard, 0, nullptr, theta, 0}, g->D, KS_STATIONARY, "grid path", &pt)) return rc;
     HIP_CHECK(hipSetDevice(g->device));
-    std::vector<double> inv_ls((size_t)g->D, 0.0);
-    const int nl = ard ? g->D : 1;
-    for (int qd = 0; qd < nl; ++qd) {
-        ARGCHK(theta[1 + qd] > 0.0, "lengthscales must be positive");
-        inv_ls[qd] = 1.0 / theta[1 + qd];
-    }
-    KernParams kp{kind, ard ? 1 : 0, g->D, theta[0]};
-    return grid_run(g, kp, theta, inv_ls, noise, noise_len, jitter + extra_jitter, out_scalars, alpha_out, dtheta_out,
+    return grid_run(g, pt, noise, noise_len, jitter + extra_jitter, out_scalars, alpha_out, dtheta_out,
                     diag_dLdK_out, stage_ms);
 }
 

@@ -10,6 +10,7 @@
 #include <cstdint>
 #include <cstdlib>
 
+#include "../../include/mi355gp.h"
 #include "internal.h"
 
 #define KT 64      // covariance tile edge
@@ -24,15 +25,15 @@ struct CovVal {
 // kinds 4 / 5 are the static kernels of GPy/kern/src/static.py: White (variance on coinciding points of the symmetric
 // case, :77-81) and Bias (constant, :165-167); `same` = the entry is a diagonal entry of a symmetric evaluation.
 __device__ __forceinline__ double cov_k(int kind, double var, double r2, bool same = false) {
-    if (kind == 4) return same ? var : 0.0;
-    if (kind == 5) return var;
-    if (kind == 0) return var * exp(-0.5 * r2);
+    if (kind == MI355GP_WHITE) return same ? var : 0.0;
+    if (kind == MI355GP_BIAS) return var;
+    if (kind == MI355GP_RBF) return var * exp(-0.5 * r2);
     const double r = sqrt(r2);
-    if (kind == 1) {
+    if (kind == MI355GP_MATERN52) {
         const double s5r = 2.2360679774997896964 * r;
         return var * (1.0 + s5r + (5.0 / 3.0) * r2) * exp(-s5r);
     }
-    if (kind == 2) {
+    if (kind == MI355GP_MATERN32) {
         const double s3r = 1.7320508075688772935 * r;
         return var * (1.0 + s3r) * exp(-s3r);
     }
@@ -41,20 +42,20 @@ __device__ __forceinline__ double cov_k(int kind, double var, double r2, bool sa
 
 __device__ __forceinline__ CovVal cov_all(int kind, double var, double r2, bool same = false) {
     CovVal c;
-    if (kind >= 4) {
-        c.k = (kind == 5 || same) ? var : 0.0;
+    if (kind >= MI355GP_WHITE) {
+        c.k = (kind == MI355GP_BIAS || same) ? var : 0.0;
         c.dk_r = 0.0;
         c.dk_or = 0.0;
         return c;
     }
-    if (kind == 0) {
+    if (kind == MI355GP_RBF) {
         c.k = var * exp(-0.5 * r2);
         c.dk_r = -r2 * c.k;
         c.dk_or = -c.k;
         return c;
     }
     const double r = sqrt(r2);
-    if (kind == 1) {
+    if (kind == MI355GP_MATERN52) {
         const double s5r = 2.2360679774997896964 * r;
         const double e = var * exp(-s5r);
         c.k = (1.0 + s5r + (5.0 / 3.0) * r2) * e;
@@ -62,7 +63,7 @@ __device__ __forceinline__ CovVal cov_all(int kind, double var, double r2, bool 
         c.dk_r = c.dk_or * r2;
         return c;
     }
-    if (kind == 2) {
+    if (kind == MI355GP_MATERN32) {
         const double s3r = 1.7320508075688772935 * r;
         const double e = var * exp(-s3r);
         c.k = (1.0 + s3r) * e;
@@ -298,7 +299,7 @@ __global__ __launch_bounds__(256) void k_kbuild_cols(KernParams kp, const double
 // returns the number of row splits (colpart: nsplit * mcols * Dy doubles), 0 if the fused form does not apply
 int launch_kbuild_cols(hipStream_t st, KernParams kp, const double* Xt1, long ld1, long n, const double* Xt2, long ld2, long m,
                        long mcols, double* Kout, long ldk, const double* V, int Dy, double* colpart) {
-    if (kp.D > KDC || kp.kind > 3 || Dy > KBC_DY || Dy < 1 || ldk % 4 != 0 || ((uintptr_t)Kout & 31) != 0) return 0;
+    if (kp.D > KDC || kp.kind > MI355GP_EXPONENTIAL || Dy > KBC_DY || Dy < 1 || ldk % 4 != 0 || ((uintptr_t)Kout & 31) != 0) return 0;
     const int ntr = (int)((n + KT - 1) / KT), ntc = (int)((mcols + KT - 1) / KT);
     int nsplit = 2048 / ntc;
     if (nsplit > 64) nsplit = 64;
@@ -328,12 +329,12 @@ void launch_kbuild_sym(hipStream_t st, KernParams kp, const double* Xt, long ldx
                        const double* noise, long noise_len, double jit, int lower_only, int add_diag, int accumulate,
                        const double* mul) {
     const int nt = (int)(npad / KT);
-    if (kp.kind == 8) {
+    if (kp.kind == MI355GP_COREGIONALIZE) {
         launch_kbuild_coreg(st, true, kp, Xt, ldx, n, Xt, ldx, n, A, npad, npad, noise, noise_len, jit, lower_only, add_diag, nt,
                             nt * nt, accumulate, mul);
         return;
     }
-    if (kp.kind >= 6) {
+    if (kp.kind >= MI355GP_RATQUAD) {
         launch_kbuild_ext(st, true, kp, Xt, ldx, n, Xt, ldx, n, A, npad, npad, noise, noise_len, jit, lower_only, add_diag, nt,
                           nt * nt, accumulate, 0, mul);
         return;
@@ -345,12 +346,12 @@ void launch_kbuild_sym(hipStream_t st, KernParams kp, const double* Xt, long ldx
 void launch_kbuild_cross(hipStream_t st, KernParams kp, const double* Xt1, long ld1, long n, const double* Xt2,
                          long ld2, long m, double* Kout, long ldk, int accumulate, int diag_same, const double* mul) {
     const int ntr = (int)((n + KT - 1) / KT), ntc = (int)((m + KT - 1) / KT);
-    if (kp.kind == 8) {                                // (no White-like diagonal: diag_same changes nothing)
+    if (kp.kind == MI355GP_COREGIONALIZE) {                                // (no White-like diagonal: diag_same changes nothing)
         launch_kbuild_coreg(st, false, kp, Xt1, ld1, n, Xt2, ld2, m, Kout, ldk, n, nullptr, 0, 0.0, 0, 0, ntc, ntr * ntc, accumulate,
                             mul);
         return;
     }
-    if (kp.kind >= 6) {
+    if (kp.kind >= MI355GP_RATQUAD) {
         launch_kbuild_ext(st, false, kp, Xt1, ld1, n, Xt2, ld2, m, Kout, ldk, n, nullptr, 0, 0.0, 0, 0, ntc, ntr * ntc,
                           accumulate, diag_same, mul);
         return;
@@ -534,7 +535,7 @@ void launch_grad_fused(hipStream_t st, KernParams kp, const double* Xt, long ldx
     const long nt = (n + KT - 1) / KT;
     const long ntiles = nt * (nt + 1) / 2;
     const int nb = pick_grad_blocks(ntiles);
-    if (kp.kind >= 6) {
+    if (kp.kind >= MI355GP_RATQUAD) {
         launch_grad_ext(st, true, kp, Xt, ldx, n, Xt, ldx, n, W, ldw, alpha, Dy, ntiles, (int)nt, partials, nullptr, 0, aa_scale,
                         Mul, ldm);
         return;
@@ -925,8 +926,8 @@ void launch_grad_generic(hipStream_t st, KernParams kp, const double* Xt1, long 
     const long ntr = (n + KT - 1) / KT, ntc = (m + KT - 1) / KT;
     const long ntiles = ntr * ntc;
     const int nb = pick_grad_blocks(ntiles);
-    if (kp.kind >= 6) {
-        if (rk.Y) return;                                  // the rank term belongs to the sparse path, which has no kind >= 6
+    if (kp.kind >= MI355GP_RATQUAD) {
+        if (rk.Y) return;                                  // the rank term belongs to the sparse path, which has neither kind
         launch_grad_ext(st, false, kp, Xt1, ld1, n, Xt2, ld2, m, G, ldg, nullptr, 0, ntiles, (int)ntc, partials, Hout, ldh,
                         nullptr, nullptr, 0);
         return;
@@ -1366,8 +1367,6 @@ void launch_rowscale_sqrt(hipStream_t st, const double* M, long ld, long rows, l
 //   StdPeriodic: K = var exp(-1/2 sum_q (sin(Delta_q) / l_q)^2),  Delta_q = pi (x_iq - x_jq) / T_q
 //                (inputs staged UNSCALED: Delta is formed from the difference of the raw coordinates, so calendar-year
 //                inputs keep their precision; pi / T_q and 1 / l_q are applied per dimension in the pair loop)
-#define KIND_RATQUAD 6
-#define KIND_STDPER 7
 
 __device__ __forceinline__ void ratquad_all(double var, double a, double r2, double& k, double& dk_or, double& dk_a) {
     const double h = 0.5 * r2;
@@ -1397,13 +1396,13 @@ __device__ __forceinline__ void accum_per(const double* si, const double* sj, co
 template <int KIND>
 __device__ __forceinline__ void accum_ext(const double* si, const double* sj, const KernParams& kp, int q0, int qc, int ty, int tx,
                                           double (&s)[4][4]) {
-    if (KIND == KIND_RATQUAD) accum_r2(si, sj, qc, ty, tx, s);
+    if (KIND == MI355GP_RATQUAD) accum_r2(si, sj, qc, ty, tx, s);
     else accum_per(si, sj, kp.pw, kp.D, q0, qc, ty, tx, s);
 }
 
 template <int KIND>
 __device__ __forceinline__ double ext_k(const KernParams& kp, double s) {
-    if (KIND == KIND_RATQUAD) return kp.variance * exp(-kp.power * log1p(0.5 * s));
+    if (KIND == MI355GP_RATQUAD) return kp.variance * exp(-kp.power * log1p(0.5 * s));
     return kp.variance * exp(-0.5 * s);
 }
 
@@ -1476,19 +1475,19 @@ static void launch_kbuild_ext(hipStream_t st, bool sym, KernParams kp, const dou
                               const double* mul) {
     (void)diag_same;                                   // no White-like diagonal in either kind
     const dim3 g((unsigned)nblocks), b(256);
-    if (kp.kind == KIND_RATQUAD) {
+    if (kp.kind == MI355GP_RATQUAD) {
         if (sym)
-            hipLaunchKernelGGL((k_kbuild_ext<true, KIND_RATQUAD>), g, b, 0, st, kp, Xt1, ld1, n, Xt2, ld2, m, out, ldo, nrows_out,
+            hipLaunchKernelGGL((k_kbuild_ext<true, MI355GP_RATQUAD>), g, b, 0, st, kp, Xt1, ld1, n, Xt2, ld2, m, out, ldo, nrows_out,
                                noise, noise_len, jit, lower_only, add_diag, ntc, accumulate, mul);
         else
-            hipLaunchKernelGGL((k_kbuild_ext<false, KIND_RATQUAD>), g, b, 0, st, kp, Xt1, ld1, n, Xt2, ld2, m, out, ldo,
+            hipLaunchKernelGGL((k_kbuild_ext<false, MI355GP_RATQUAD>), g, b, 0, st, kp, Xt1, ld1, n, Xt2, ld2, m, out, ldo,
                                nrows_out, noise, noise_len, jit, lower_only, add_diag, ntc, accumulate, mul);
-    } else if (kp.kind == KIND_STDPER) {
+    } else if (kp.kind == MI355GP_STDPERIODIC) {
         if (sym)
-            hipLaunchKernelGGL((k_kbuild_ext<true, KIND_STDPER>), g, b, 0, st, kp, Xt1, ld1, n, Xt2, ld2, m, out, ldo, nrows_out,
+            hipLaunchKernelGGL((k_kbuild_ext<true, MI355GP_STDPERIODIC>), g, b, 0, st, kp, Xt1, ld1, n, Xt2, ld2, m, out, ldo, nrows_out,
                                noise, noise_len, jit, lower_only, add_diag, ntc, accumulate, mul);
         else
-            hipLaunchKernelGGL((k_kbuild_ext<false, KIND_STDPER>), g, b, 0, st, kp, Xt1, ld1, n, Xt2, ld2, m, out, ldo,
+            hipLaunchKernelGGL((k_kbuild_ext<false, MI355GP_STDPERIODIC>), g, b, 0, st, kp, Xt1, ld1, n, Xt2, ld2, m, out, ldo,
                                nrows_out, noise, noise_len, jit, lower_only, add_diag, ntc, accumulate, mul);
     }
 }
@@ -1506,7 +1505,7 @@ __global__ __launch_bounds__(256) void k_grad_ext(KernParams kp, const double* _
                                                   long ntiles, int ntc, double* __restrict__ partA, double* __restrict__ partB,
                                                   double* __restrict__ Hout, long ldh, const double* __restrict__ aa_scale,
                                                   const double* __restrict__ Mul, long ldm) {
-    constexpr bool PER = (KIND == KIND_STDPER);
+    constexpr bool PER = (KIND == MI355GP_STDPERIODIC);
     __shared__ __attribute__((aligned(16))) double si[KDC * KT];
     __shared__ __attribute__((aligned(16))) double sj[KDC * KTJ];
     __shared__ double red[256];
@@ -1676,7 +1675,7 @@ static void launch_grad_ext(hipStream_t st, bool fused, KernParams kp, const dou
                             double* partials, double* Hout, long ldh, const double* aa_scale, const double* Mul, long ldm) {
     const int nb = pick_grad_blocks(ntiles);
     const int groups = (kp.D + KDC - 1) / KDC;
-    const bool perdim = kp.kind == KIND_STDPER || kp.ard;
+    const bool perdim = kp.kind == MI355GP_STDPERIODIC || kp.ard;
     double* partB = partials + (long)groups * nb * GP_STRIDE;
     for (int q_off = 0, gidx = 0; q_off < kp.D; q_off += KDC, ++gidx) {
         if (!perdim && gidx > 0) break;
@@ -1685,19 +1684,19 @@ static void launch_grad_ext(hipStream_t st, bool fused, KernParams kp, const dou
         // Hout may alias G (in place): only the LAST group launch writes it
         double* h = (!perdim || q_off + KDC >= kp.D) ? Hout : nullptr;
         const dim3 g((unsigned)nb), b(256);
-        if (kp.kind == KIND_RATQUAD) {
+        if (kp.kind == MI355GP_RATQUAD) {
             if (fused)
-                hipLaunchKernelGGL((k_grad_ext<true, KIND_RATQUAD>), g, b, 0, st, kp, Xt1, ld1, n, Xt2, ld2, m, G, ldg, alpha, Dy,
+                hipLaunchKernelGGL((k_grad_ext<true, MI355GP_RATQUAD>), g, b, 0, st, kp, Xt1, ld1, n, Xt2, ld2, m, G, ldg, alpha, Dy,
                                    q_off, ntiles, ntc, pa, pb, nullptr, 0, aa_scale, Mul, ldm);
             else
-                hipLaunchKernelGGL((k_grad_ext<false, KIND_RATQUAD>), g, b, 0, st, kp, Xt1, ld1, n, Xt2, ld2, m, G, ldg, nullptr, 0,
+                hipLaunchKernelGGL((k_grad_ext<false, MI355GP_RATQUAD>), g, b, 0, st, kp, Xt1, ld1, n, Xt2, ld2, m, G, ldg, nullptr, 0,
                                    q_off, ntiles, ntc, pa, pb, h, ldh, nullptr, nullptr, 0);
-        } else if (kp.kind == KIND_STDPER) {
+        } else if (kp.kind == MI355GP_STDPERIODIC) {
             if (fused)
-                hipLaunchKernelGGL((k_grad_ext<true, KIND_STDPER>), g, b, 0, st, kp, Xt1, ld1, n, Xt2, ld2, m, G, ldg, alpha, Dy,
+                hipLaunchKernelGGL((k_grad_ext<true, MI355GP_STDPERIODIC>), g, b, 0, st, kp, Xt1, ld1, n, Xt2, ld2, m, G, ldg, alpha, Dy,
                                    q_off, ntiles, ntc, pa, pb, nullptr, 0, aa_scale, Mul, ldm);
             else
-                hipLaunchKernelGGL((k_grad_ext<false, KIND_STDPER>), g, b, 0, st, kp, Xt1, ld1, n, Xt2, ld2, m, G, ldg, nullptr, 0,
+                hipLaunchKernelGGL((k_grad_ext<false, MI355GP_STDPERIODIC>), g, b, 0, st, kp, Xt1, ld1, n, Xt2, ld2, m, G, ldg, nullptr, 0,
                                    q_off, ntiles, ntc, pa, pb, nullptr, 0, nullptr, nullptr, 0);
         }
     }
@@ -1793,7 +1792,6 @@ void launch_periodic_gradx(hipStream_t st, KernParams kp, const double* Xt1, lon
 // Coregionalize (kind 8, coregionalize.py:82-157): k(x, x') = B[idx][idx'], idx = the value of input row kp.col of Xt (staged
 // unscaled), B = kp.pw (P x P row-major, P = kp.ard <= 16).  The host validates every index before a launch; an index that is
 // not an integer in [0, P) still never reads outside B here: it yields NaN (K-build) or poisons the block's record (gradient).
-#define KIND_COREG 8
 #define COREG_PMAX 16
 
 __device__ __forceinline__ int coreg_idx(double x, int P) {

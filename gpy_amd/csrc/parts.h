@@ -1,0 +1,269 @@
+// parts.h -- the host-side model of one kernel part (mi355gp_part) shared by the exact, sparse and grid paths: which kinds
+// an entry point takes, theta validation, active dimensions, input scaling, term grouping, Kdiag of a sum of products and
+// the post-scaling of the reduction records into gradients in theta order.  Host code only.
+#pragma once
+#include <cmath>
+#include <vector>
+
+#include "../../include/mi355gp.h"
+#include "internal.h"
+
+#define GP_STRIDE 34           // doubles of one reduction record: [0] variance sum, [1] lengthscale sum, [2 + q % 32] per dimension
+
+// the sums of dimension q in the records of one part (one GP_STRIDE record per group of 32 dimensions)
+static inline double rec_at(const double* rec, int q) { return rec[(q / 32) * GP_STRIDE + 2 + (q % 32)]; }
+
+typedef unsigned KindSet;      // bit k: kind k is accepted
+enum : KindSet {
+    KS_STATIONARY = 1u << MI355GP_RBF | 1u << MI355GP_MATERN52 | 1u << MI355GP_MATERN32 | 1u << MI355GP_EXPONENTIAL,
+    KS_STATIC = 1u << MI355GP_WHITE | 1u << MI355GP_BIAS,
+    KS_EXT = 1u << MI355GP_RATQUAD | 1u << MI355GP_STDPERIODIC,     // two reduction records per part (k_grad_ext)
+    KS_COREG = 1u << MI355GP_COREGIONALIZE,
+};
+static inline bool kind_in(int kind, KindSet s) { return kind >= 0 && kind < 32 && ((s >> kind) & 1u); }
+static inline const char* kind_name(int kind) {
+    static const char* const names[] = {"RBF", "Matern52", "Matern32", "Exponential", "White", "Bias", "RatQuad",
+                                        "StdPeriodic", "Coregionalize"};
+    return kind_in(kind, KS_STATIONARY | KS_STATIC | KS_EXT | KS_COREG) ? names[kind] : "unknown";
+}
+
+#define PART_FAIL(...)                    \
+    do {                                  \
+        mi355gp_set_error(__VA_ARGS__);   \
+        return -1;                        \
+    } while (0)
+
+static inline int check_kind(int kind, KindSet accepted, const char* where) {
+    if (!kind_in(kind, accepted)) PART_FAIL("%s: covariance kind %d (%s) is not supported here", where, kind, kind_name(kind));
+    return 0;
+}
+
+// Coregionalize (kind 8, coregionalize.py:82-157): `ard` = the number of outputs P, theta = B (P x P).  Output indices are
+// values of one input column; each must be an integer in [0, P) -- checked on the host, before any launch reads one.
+static inline int coreg_check_P(int P) {
+    if (P < 1 || P > 16)
+        PART_FAIL("Coregionalize (kind 8): the number of outputs (ard) must be between 1 and 16, got %d", P);
+    return 0;
+}
+static inline int coreg_check_index(const double* x, long n, long stride, int P, const char* what) {
+    for (long i = 0; i < n; ++i) {
+        const double v = x[i * stride];
+        if (!(v >= 0.0 && v < (double)P && v == std::floor(v)))
+            PART_FAIL("Coregionalize (kind 8): %s output index %.17g (row %ld) is not an integer in [0, %d)", what, v, i, P);
+    }
+    return 0;
+}
+
+// Everything the host derives from one mi355gp_part; no device pointers (kp.pw stays NULL: the owner points it at its own
+// device copy of pw).
+struct PartSpec {
+    KernParams kp = {0, 0, 0, 1.0};
+    int ard_in = 0;                 // the `ard` of the C-ABI part (StdPeriodic: the ARD1 | ARD2 bitmask; Coregionalize: P)
+    std::vector<int> dims;          // active input dimensions (kern.py:49-53), indices into the D columns of X
+    std::vector<double> theta;      // exactly the kind's parameters, in theta order
+    std::vector<double> inv_ls;     // length D: 1/l on active dimensions, 0 elsewhere (= the slicing of kern.py:112-117)
+                                    // (StdPeriodic: 1 on active dimensions, Coregionalize: 1 on the index column -- unscaled)
+    std::vector<double> pw;         // StdPeriodic: [pi / T_q (D) | 1 / l_q (D)]; Coregionalize: B (P x P); empty otherwise
+    int term = 0;                   // term id of the C-ABI part: parts with the same non-zero id are multiplied (prod.py)
+    int tix = 0;                    // index of its summand in the terms of group_terms
+    bool stationary() const { return kind_in(kp.kind, KS_STATIONARY); }
+    bool is_static() const { return kind_in(kp.kind, KS_STATIC); }
+    bool ext() const { return kind_in(kp.kind, KS_EXT); }
+    bool coreg() const { return kp.kind == MI355GP_COREGIONALIZE; }
+};
+
+// The one validator of a kernel part over D input columns (n_active = 0: all of them).  `accepted`: the kinds the entry point
+// takes; `where`: the entry point or path, named in every error.  Coregionalize output indices are checked where the data are.
+static inline int parse_part(const mi355gp_part& in, int D, KindSet accepted, const char* where, PartSpec* p) {
+    const int kind = in.kind, ard = in.ard;
+    if (int rc = check_kind(kind, accepted, where)) return rc;
+    if (!in.theta) PART_FAIL("%s: theta of a %s (kind %d) part is NULL", where, kind_name(kind), kind);
+    const double* th = in.theta;
+    p->dims.clear();
+    p->pw.clear();
+    p->inv_ls.assign((size_t)D, 0.0);
+    p->ard_in = ard;
+    p->term = in.term;
+    if (kind == MI355GP_COREGIONALIZE) {
+        if (!(in.n_active == 1 && in.active_dims && in.active_dims[0] >= 0 && in.active_dims[0] < D))
+            PART_FAIL("%s: Coregionalize (kind 8): n_active must be 1 (the input column of the output index), got %d", where,
+                      in.n_active);
+        if (int rc = coreg_check_P(ard)) return rc;
+        for (int k = 0; k < ard * ard; ++k)
+            if (!std::isfinite(th[k])) PART_FAIL("%s: Coregionalize (kind 8): B[%d] = %g is not finite", where, k, th[k]);
+        const int col = in.active_dims[0];
+        p->dims.assign(1, col);
+        p->theta.assign(th, th + ard * ard);
+        p->pw = p->theta;
+        p->inv_ls[(size_t)col] = 1.0;                 // the index column stays unscaled
+        p->kp = KernParams{kind, ard, D, th[0]};
+        p->kp.col = col;
+        return 0;
+    }
+    if (!(th[0] > 0.0)) PART_FAIL("%s: the variance of a %s (kind %d) part must be positive, got %g", where, kind_name(kind), kind, th[0]);
+    if (in.active_dims && in.n_active > 0) {
+        for (int a = 0; a < in.n_active; ++a) {
+            const int q = in.active_dims[a];
+            if (q < 0 || q >= D)
+                PART_FAIL("%s: active dimension %d of a %s (kind %d) part is out of range [0, %d)", where, q, kind_name(kind), kind, D);
+            p->dims.push_back(q);
+        }
+    } else {
+        for (int q = 0; q < D; ++q) p->dims.push_back(q);
+    }
+    const int na = (int)p->dims.size();
+    auto positive = [&](double v, const char* what) {
+        if (v > 0.0) return 0;
+        mi355gp_set_error("%s: %s %g of a %s (kind %d) part must be positive", where, what, v, kind_name(kind), kind);
+        return -1;
+    };
+    int nt = 1;                                        // static kinds: [variance]
+    p->kp = KernParams{kind, 0, D, th[0]};
+    if (kind == MI355GP_STDPERIODIC) {                 // [variance, period (1 or n_active), lengthscale (1 or n_active)]
+        if (ard < 0 || ard > 3)
+            PART_FAIL("%s: StdPeriodic (kind 7): ard %d is not a bitmask (1 = one period, 2 = one lengthscale per dimension)",
+                      where, ard);
+        const int nper = (ard & 1) ? na : 1, nl = (ard & 2) ? na : 1;
+        p->pw.assign(2 * (size_t)D, 0.0);
+        for (int a = 0; a < na; ++a) {
+            const double T = th[1 + ((ard & 1) ? a : 0)], l = th[1 + nper + ((ard & 2) ? a : 0)];
+            if (int rc = positive(T, "period")) return rc;
+            if (int rc = positive(l, "lengthscale")) return rc;
+            const int q = p->dims[a];
+            p->inv_ls[(size_t)q] = 1.0;                // unscaled inputs: Delta from the raw coordinates
+            p->pw[(size_t)q] = M_PI / T;
+            p->pw[(size_t)(D + q)] = 1.0 / l;
+        }
+        p->kp.ard = 1;                                 // per-dimension reductions
+        nt = 1 + nper + nl;
+    } else if (!p->is_static()) {                      // stationary and RatQuad: [variance, lengthscale (1 or n_active)(, power)]
+        const int nl = ard ? na : 1;
+        for (int a = 0; a < na; ++a) {
+            const double l = th[1 + (ard ? a : 0)];
+            if (int rc = positive(l, "lengthscale")) return rc;
+            p->inv_ls[(size_t)p->dims[a]] = 1.0 / l;
+        }
+        p->kp.ard = ard ? 1 : 0;
+        nt = 1 + nl;
+        if (kind == MI355GP_RATQUAD) {
+            p->kp.power = th[nt++];
+            if (int rc = positive(p->kp.power, "power")) return rc;
+        }
+    }
+    p->theta.assign(th, th + nt);
+    return 0;
+}
+
+// Gradient of one part in theta order from its reduction records (rec: the kind's first record, groups * GP_STRIDE;
+// rec2: the second record of RatQuad / StdPeriodic; Coregionalize: rec = S, P x P).  Returns the number written.
+// stationary.py:199,210-213 (x already divided by l inside the kernels), 790-798; standard_periodic.py:501-526
+static inline int part_dtheta(const PartSpec& p, const double* rec, const double* rec2, double* o) {
+    const double* th = p.theta.data();
+    const int na = (int)p.dims.size(), ard = p.ard_in;
+    if (p.coreg()) {                                   // S in theta (= B) order
+        for (int k = 0; k < ard * ard; ++k) o[k] = rec[k];
+        return ard * ard;
+    }
+    int k = 0;
+    o[k++] = rec[0] / p.kp.variance;                   // sum g K / variance
+    if (p.is_static()) return k;
+    if (p.kp.kind == MI355GP_STDPERIODIC) {
+        const int nper = (ard & 1) ? na : 1;
+        double sT = 0.0, sL = 0.0;
+        for (int a = 0; a < na; ++a) {
+            const double T = th[1 + ((ard & 1) ? a : 0)], l = th[1 + nper + ((ard & 2) ? a : 0)];
+            const double gT = rec_at(rec, p.dims[a]) / (T * l * l), gL = rec_at(rec2, p.dims[a]) / (l * l * l);
+            if (ard & 1) o[k + a] = gT;
+            else sT += gT;
+            if (ard & 2) o[k + nper + a] = gL;
+            else sL += gL;
+        }
+        if (!(ard & 1)) o[k] = sT;
+        k += nper;
+        if (!(ard & 2)) o[k] = sL;
+        return k + ((ard & 2) ? na : 1);
+    }
+    if (!p.kp.ard) o[k++] = -rec[1] / th[1];           // dl = -S / l
+    else
+        for (int a = 0; a < na; ++a) o[k++] = -rec_at(rec, p.dims[a]) / th[1 + a];
+    if (p.kp.kind == MI355GP_RATQUAD) o[k++] = rec2[0];
+    return k;
+}
+
+// ---- the expression: a sum over terms of the element-wise product of the term's parts (add.py:58-72, prod.py:58-65) -----
+typedef std::vector<std::vector<int>> Terms;
+
+// term id 0 = a summand of its own; parts sharing a non-zero id are the factors of one summand.  Returns the part indices per
+// summand in order of first appearance and sets every part's tix.
+template <class Part>
+static Terms group_terms(std::vector<Part>& parts) {
+    Terms terms;
+    std::vector<int> ids;
+    for (size_t i = 0; i < parts.size(); ++i) {
+        const int id = parts[i].term;
+        size_t t = ids.size();
+        if (id != 0)
+            for (t = 0; t < ids.size() && ids[t] != id; ++t) {}
+        if (t == ids.size()) {
+            ids.push_back(id);
+            terms.emplace_back();
+        }
+        terms[t].push_back((int)i);
+        parts[i].tix = (int)t;
+    }
+    return terms;
+}
+
+static inline bool has_product(const Terms& terms) {
+    for (const auto& t : terms)
+        if (t.size() > 1) return true;
+    return false;
+}
+
+// Kdiag of the expression: sum over terms of the product of the factors' variances (add.py:74-79, prod.py:67-71)
+template <class Part>
+static double expression_kdiag(const std::vector<Part>& parts, const Terms& terms) {
+    double s = 0.0;
+    for (const auto& t : terms) {
+        double v = 1.0;
+        for (int f : t) v *= parts[(size_t)f].kp.variance;
+        s += v;
+    }
+    return s;
+}
+
+// out (+)= the expression: emit(part, dst, mul, accumulate, first_into_out) launches one factor, dst (+)= K_part * mul.  The
+// leading factors of a multi-factor term are multiplied up in `scratch` (same shape as `out`), the last one lands in `out`.
+// skip(term): terms left out (e.g. White in a cross-covariance).  Returns false if nothing was emitted.
+template <class Skip, class Emit>
+static bool emit_expression(const Terms& terms, double* out, double* scratch, bool out_holds_data, Skip skip, Emit emit) {
+    bool first = !out_holds_data, any = false;
+    for (const auto& t : terms) {
+        if (skip(t)) continue;
+        const size_t k = t.size();
+        for (size_t f = 0; f + 1 < k; ++f) emit(t[f], scratch, f > 0 ? scratch : nullptr, 0, false);
+        emit(t[k - 1], out, k > 1 ? scratch : nullptr, first ? 0 : 1, first);
+        first = false;
+        any = true;
+    }
+    return any;
+}
+template <class Emit>
+static bool emit_expression(const Terms& terms, double* out, double* scratch, bool out_holds_data, Emit emit) {
+    return emit_expression(terms, out, scratch, out_holds_data, [](const std::vector<int>&) { return false; }, emit);
+}
+
+// dst = the product of the OTHER factors of part p's term (index tix), emit(part, dst, mul, accumulate, first) launching one
+// factor at a time; false: p stands alone
+template <class Emit>
+static bool emit_other_factors(const Terms& terms, int tix, size_t p, double* dst, Emit emit) {
+    const auto& t = terms[(size_t)tix];
+    if (t.size() < 2) return false;
+    bool first = true;
+    for (int f : t) {
+        if ((size_t)f == p) continue;
+        emit(f, dst, first ? nullptr : dst, 0, first);
+        first = false;
+    }
+    return true;
+}

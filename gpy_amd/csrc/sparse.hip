@@ -19,8 +19,8 @@
 #include "../../include/mi355gp.h"
 #include "../../include/mi355gp_debug.h"
 #include "internal.h"
+#include "parts.h"
 
-#define GP_STRIDE 34
 #define SPLITK_MAX 16
 #define CHUNK_MAX 262144                    // rows per chunk: 2 x (chunk x Mp) doubles of HBM (8.6 GB at M = 2048)
 #define ARGCHK(cond, msg)                 \
@@ -194,14 +194,8 @@ static int loop_allreduce(LoopGroup* G, int rank, double* buf, size_t count, hip
     return 0;
 }
 
-struct SPart {
-    KernParams kp = {0, 0, 0, 1.0};
-    std::vector<double> theta, inv_ls;
-    std::vector<int> dims;
+struct SPart : PartSpec {
     double *XtZ = nullptr, *XtC = nullptr, *HX = nullptr, *HZ = nullptr, *gradNM = nullptr, *gradMM = nullptr;
-    int term = 0;                 // parts with the same non-zero id are the factors of one product (GPy/kern/src/prod.py)
-    int tix = 0;                  // index into mi355gp_sparse::terms
-    bool stationary() const { return kp.kind <= 3; }
 };
 
 struct mi355gp_sparse {
@@ -236,7 +230,7 @@ struct mi355gp_sparse {
            *trmvPart = nullptr, *colPart = nullptr, *gradPart = nullptr, *gradChunk = nullptr, *scal = nullptr,
            *redbuf = nullptr;
     std::vector<SPart> parts;
-    std::vector<std::vector<int>> terms;   // part indices per summand, in order of first appearance (one part, or the factors of a Prod)
+    Terms terms;                  // part indices per summand, in order of first appearance (one part, or the factors of a Prod)
     FactorWs ws;
     bool ws_ok = false, have_result = false, winv_ok = false;
     hipEvent_t ev[6] = {};
@@ -347,65 +341,16 @@ static int prepare_sparse_parts(mi355gp_sparse* s, int nparts, const mi355gp_par
             HIP_CHECK(hipMalloc(&p.gradMM, sizeof(double) * groups * GP_STRIDE));
         }
     }
-    for (int i = 0; i < nparts; ++i) {
-        const mi355gp_part& in = parts[i];
-        SPart& p = s->parts[(size_t)i];
-        ARGCHK(in.kind != 8, "Coregionalize (kind 8) runs on the exact-GP path only, not the sparse path");
-        ARGCHK(in.kind >= 0 && in.kind <= 5 && in.theta, "unknown covariance kind / NULL theta in a kernel part");
-        p.term = in.term;
-        ARGCHK(in.theta[0] > 0.0, "variance must be positive");
-        p.dims.clear();
-        if (in.active_dims && in.n_active > 0) {
-            for (int a = 0; a < in.n_active; ++a) {
-                ARGCHK(in.active_dims[a] >= 0 && in.active_dims[a] < D, "active dimension out of range");
-                p.dims.push_back(in.active_dims[a]);
-            }
-        } else {
-            for (int q = 0; q < D; ++q) p.dims.push_back(q);
-        }
-        const int na = (int)p.dims.size();
-        const bool st = in.kind <= 3;
-        const int nl = st ? (in.ard ? na : 1) : 0;
-        p.kp = KernParams{in.kind, (st && in.ard) ? 1 : 0, (int)D, in.theta[0]};
-        p.theta.assign(in.theta, in.theta + 1 + nl);
-        p.inv_ls.assign((size_t)D, 0.0);
-        for (int a = 0; a < na && st; ++a) {
-            const double l = in.theta[1 + (in.ard ? a : 0)];
-            ARGCHK(l > 0.0, "lengthscales must be positive");
-            p.inv_ls[(size_t)p.dims[a]] = 1.0 / l;
-        }
-    }
-    // summands: term id 0 = a part of its own; parts sharing a non-zero id are multiplied (prod.py:58-72)
-    s->terms.clear();
-    std::vector<int> ids;
-    for (int i = 0; i < nparts; ++i) {
-        const int id = s->parts[(size_t)i].term;
-        size_t t = ids.size();
-        if (id != 0)
-            for (t = 0; t < ids.size() && ids[t] != id; ++t) {}
-        if (t == ids.size()) {
-            ids.push_back(id != 0 ? id : -1 - i);
-            s->terms.emplace_back();
-        }
-        s->terms[t].push_back(i);
-        s->parts[(size_t)i].tix = (int)t;
-    }
+    for (int i = 0; i < nparts; ++i)
+        if (int rc = parse_part(parts[i], (int)D, KS_STATIONARY | KS_STATIC, "sparse path", &s->parts[(size_t)i])) return rc;
+    s->terms = group_terms(s->parts);
     for (const auto& t : s->terms)
         if (t.size() > 1)
-            for (int f : t) ARGCHK(s->parts[(size_t)f].kp.kind != 4, "a White factor inside a product is not supported by the sparse path");
+            for (int f : t)
+                ARGCHK(s->parts[(size_t)f].kp.kind != MI355GP_WHITE, "a White factor inside a product is not supported by the sparse path");
     return 0;
 }
 
-// Kdiag of the expression (psi0_n): sum over summands of the product of the factors' variances (add.py:74-79, prod.py:67-71)
-static double sparse_kdiag(const mi355gp_sparse* s) {
-    double k = 0.0;
-    for (const auto& t : s->terms) {
-        double v = 1.0;
-        for (int f : t) v *= s->parts[(size_t)f].kp.variance;
-        k += v;
-    }
-    return k;
-}
 // product of the OTHER factors' variances of part p's summand (= dKdiag/dvariance_p; 1 for a plain summand)
 static double sparse_other_variances(const mi355gp_sparse* s, size_t p) {
     double v = 1.0;
@@ -413,32 +358,9 @@ static double sparse_other_variances(const mi355gp_sparse* s, size_t p) {
         if ((size_t)f != p) v *= s->parts[(size_t)f].kp.variance;
     return v;
 }
-// out (+)= sum over summands of the element-wise product of their factors: emit(part, dst, mul, accumulate) launches one
-// factor, dst (+)= K_part * mul.  The leading factors of a product are multiplied up in `scratch` (same shape as out).
-// skip_white: cross-covariances (White contributes nothing, static.py:77-81).  Returns false if nothing was emitted.
-template <class Emit>
-static bool sparse_expression(const mi355gp_sparse* s, double* out, double* scratch, bool skip_white, Emit emit) {
-    bool first = true;
-    for (const auto& t : s->terms) {
-        if (skip_white && t.size() == 1 && s->parts[(size_t)t[0]].kp.kind == 4) continue;
-        for (size_t f = 0; f + 1 < t.size(); ++f) emit(t[f], scratch, f > 0 ? scratch : nullptr, 0, false);
-        emit(t.back(), out, t.size() > 1 ? scratch : nullptr, first ? 0 : 1, first);
-        first = false;
-    }
-    return !first;
-}
-// dst = the product of the OTHER factors of part p's summand, evaluated by emit(part, dst, mul, accumulate); false: p stands alone
-template <class Emit>
-static bool sparse_other_factors(const mi355gp_sparse* s, size_t p, double* dst, Emit emit) {
-    const auto& t = s->terms[(size_t)s->parts[p].tix];
-    if (t.size() < 2) return false;
-    bool first = true;
-    for (int f : t) {
-        if ((size_t)f == p) continue;
-        emit(f, dst, first ? nullptr : dst, 0, first);
-        first = false;
-    }
-    return true;
+// cross-covariances leave out summands that are a White part alone (White contributes nothing off the diagonal, static.py:77-81)
+static bool skip_white(const mi355gp_sparse* s, const std::vector<int>& t) {
+    return t.size() == 1 && s->parts[(size_t)t[0]].kp.kind == MI355GP_WHITE;
 }
 
 // scaled, dimension-major copies of `rows` points (row-major src) for every part
@@ -453,7 +375,8 @@ static int scale_for_parts(mi355gp_sparse* s, const double* src, long rows, long
 // Kfu chunk = sum over summands of (the product of) K_p(X_chunk, Z)  (add.py:58-72, prod.py:58-65; White contributes nothing
 // off the diagonal, static.py:77-81).  Products are multiplied up in `scratch` (chunk x mp, e.g. the T buffer).
 static void build_cross_chunk(mi355gp_sparse* s, long rc, double* out, double* scratch) {
-    const bool any = sparse_expression(s, out, scratch, true, [&](int p, double* dst, const double* mul, int acc, bool) {
+    auto skip = [&](const std::vector<int>& t) { return skip_white(s, t); };
+    const bool any = emit_expression(s->terms, out, scratch, false, skip, [&](int p, double* dst, const double* mul, int acc, bool) {
         const SPart& pt = s->parts[(size_t)p];
         launch_kbuild_cross(s->st, pt.kp, pt.XtC, s->chunk, rc, pt.XtZ, s->mp, s->m, dst, s->mp, acc, 0, mul);
     });
@@ -462,7 +385,7 @@ static void build_cross_chunk(mi355gp_sparse* s, long rc, double* out, double* s
 // K(Z) (lower tiles; diag != NULL: + diag on the diagonal) of the expression into out (mp x mp), scratch mp x mp
 static void build_kmm(mi355gp_sparse* s, double* out, double* scratch, double jitter, int lower_only, hipStream_t st = nullptr) {
     if (!st) st = s->st;
-    sparse_expression(s, out, scratch, false, [&](int p, double* dst, const double* mul, int acc, bool first) {
+    emit_expression(s->terms, out, scratch, false, [&](int p, double* dst, const double* mul, int acc, bool first) {
         const SPart& pt = s->parts[(size_t)p];
         launch_kbuild_sym(st, pt.kp, pt.XtZ, s->mp, s->m, s->mp, dst, s->zero1, 1, jitter, lower_only,
                           /*add_diag=*/(first && dst == out) ? 1 : 0, acc, mul);
@@ -895,11 +818,11 @@ int mi355gp_vardtc_inference_sum(mi355gp_sparse* s, int nparts, const mi355gp_pa
         const size_t nstat = s->parts.size();
         for (size_t pi = 0; pi < nstat; ++pi) {
             SPart& p = s->parts[pi];
-            if (p.kp.kind == 4) continue;                    // White: K(X, Z) = 0, no contribution (static.py:89-93)
+            if (p.kp.kind == MI355GP_WHITE) continue;        // White: K(X, Z) = 0, no contribution (static.py:89-93)
             int nbk = 0, ns = 0;
             // a factor of a product sees dL_dKnm TIMES the other factors' covariance (prod.py:86-99): that weight matrix is
             // materialised in the Kfu buffer (free by now) -- other factors multiplied up, then dL_dKnm formed on top
-            const bool prod = sparse_other_factors(s, pi, s->Kfu, [&](int f, double* dst, const double* mul, int, bool) {
+            const bool prod = emit_other_factors(s->terms, p.tix, pi, s->Kfu, [&](int f, double* dst, const double* mul, int, bool) {
                 const SPart& pf = s->parts[(size_t)f];
                 launch_kbuild_cross(st, pf.kp, pf.XtC, chunk, rc, pf.XtZ, mp, m, dst, mp, 0, 0, mul);
             });
@@ -947,7 +870,7 @@ int mi355gp_vardtc_inference_sum(mi355gp_sparse* s, int nparts, const mi355gp_pa
     for (size_t pi = 0; pi < s->parts.size(); ++pi) {
         SPart& p = s->parts[pi];
         const int nbk = grad_generic_num_blocks(m, m);
-        const bool prod = sparse_other_factors(s, pi, s->T1, [&](int f, double* dst, const double* mul, int, bool) {
+        const bool prod = emit_other_factors(s->terms, p.tix, pi, s->T1, [&](int f, double* dst, const double* mul, int, bool) {
             const SPart& pf = s->parts[(size_t)f];
             launch_kbuild_cross(st, pf.kp, pf.XtZ, mp, m, pf.XtZ, mp, m, dst, mp, 0, /*diag_same=*/1, mul);
         });
@@ -1014,7 +937,7 @@ int mi355gp_vardtc_inference_sum(mi355gp_sparse* s, int nparts, const mi355gp_pa
     }
     const double trA = scal[0], sumAP = scal[1], logLB = scal[2], data_fit = scal[3];
     const double ng = (double)s->n_global, nd = ng * Dy;
-    const double kdiag = sparse_kdiag(s);                        // psi0_n = Kdiag of the expression
+    const double kdiag = expression_kdiag(s->parts, s->terms);                        // psi0_n = Kdiag of the expression
     // _compute_log_marginal_likelihood (var_dtc.py:264-276)
     double lik_1, lik_2;
     if (het) {
@@ -1063,20 +986,16 @@ int mi355gp_vardtc_inference_sum(mi355gp_sparse* s, int nparts, const mi355gp_pa
     }
     if (dtheta_out) {
         double* o = dtheta_out;
+        std::vector<double> ab(gsz);                              // the Knm and Kmm records of a part summed
         for (size_t i = 0; i < np_; ++i) {
-            const SPart& p = s->parts[i];
             const double* a = gnm.data() + i * gsz;
             const double* b = gmm.data() + i * gsz;
+            for (size_t k = 0; k < gsz; ++k) ab[k] = a[k] + b[k];
+            const int k = part_dtheta(s->parts[i], ab.data(), nullptr, o);
             // update_gradients_diag(dL_dKdiag = -0.5 Dy beta_n) (sparse_gp.py:110, stationary.py:175-184, static.py:95-96)
             // (a factor of a product: dKdiag / dvariance = the product of the other factors' variances, prod.py:67-71)
-            *o++ = -0.5 * Dy * glob[0] * sparse_other_variances(s, i) + (a[0] + b[0]) / p.kp.variance;
-            if (!p.stationary()) continue;
-            if (!p.kp.ard) *o++ = -(a[1] + b[1]) / p.theta[1];
-            else
-                for (size_t k = 0; k < p.dims.size(); ++k) {
-                    const int q = p.dims[k], off = (q / 32) * GP_STRIDE + 2 + (q % 32);
-                    *o++ = -(a[off] + b[off]) / p.theta[1 + k];
-                }
+            o[0] = -0.5 * Dy * glob[0] * sparse_other_variances(s, i) + o[0];
+            o += k;
         }
     }
     if (dZ_out) {
@@ -1107,7 +1026,8 @@ int mi355gp_vardtc_inference_sum(mi355gp_sparse* s, int nparts, const mi355gp_pa
 int mi355gp_vardtc_inference(mi355gp_sparse* s, int kind, int ard, const double* theta, const double* Z, int64_t M,
                              double noise_var, double extra_jitter, double* out_scalars, double* dtheta_out,
                              double* dZ_out, double* wv_out, double* stage_ms) {
-    ARGCHK(kind >= 0 && kind <= 3 && theta, "mi355gp_vardtc_inference: bad kernel parameters");
+    if (int rc = check_kind(kind, KS_STATIONARY, "mi355gp_vardtc_inference")) return rc;
+    ARGCHK(theta, "mi355gp_vardtc_inference: theta is NULL");
     const mi355gp_part part{kind, ard, 0, nullptr, theta, 0};
     return mi355gp_vardtc_inference_sum(s, 1, &part, Z, M, &noise_var, 1, extra_jitter, out_scalars, dtheta_out, dZ_out, wv_out,
                                         nullptr, nullptr, stage_ms);
@@ -1213,28 +1133,26 @@ int mi355gp_sparse_predict(mi355gp_sparse* s, int nparts, const mi355gp_part* pa
     (void)hipMemcpyAsync(dXn, Xnew, sizeof(double) * Mn * D, hipMemcpyHostToDevice, st);
     (void)hipMemsetAsync(Kx, 0, sizeof(double) * mp * mnp, st);
     if (full_cov && var_out) (void)hipMemsetAsync(dVar, 0, sizeof(double) * mnp * mnp, st);
-    const double kdiag = sparse_kdiag(s);
+    const double kdiag = expression_kdiag(s->parts, s->terms);
     // K(Z, X*) and (full_cov) K(X*, X*) of the expression: every factor is evaluated with ITS scaling of the new inputs;
     // products are multiplied up in Tmp / a second M* x M* scratch
     auto scale_new = [&](const SPart& p) {
         (void)hipMemcpyAsync(s->invls, p.inv_ls.data(), sizeof(double) * D, hipMemcpyHostToDevice, st);
         launch_scale_inputs(st, dXn, Mn, (int)D, s->invls, 1, dXt, ldn);
     };
-    sparse_expression(s, Kx, Tmp, true, [&](int pi, double* dst, const double* mul, int acc, bool) {
+    emit_expression(s->terms, Kx, Tmp, false, [&](const std::vector<int>& t) { return skip_white(s, t); }, [&](int pi, double* dst, const double* mul, int acc, bool) {
         const SPart& p = s->parts[(size_t)pi];
         scale_new(p);
         launch_kbuild_cross(st, p.kp, p.XtZ, mp, m, dXt, ldn, Mn, dst, mnp, acc, 0, mul);
     });
     if (full_cov && var_out) {
         double* scr = nullptr;
-        bool prod = false;
-        for (const auto& t : s->terms) prod = prod || t.size() > 1;
-        if (prod && hipMalloc(&scr, sizeof(double) * mnp * mnp) != hipSuccess) {
+        if (has_product(s->terms) && hipMalloc(&scr, sizeof(double) * mnp * mnp) != hipSuccess) {
             cleanup();
             mi355gp_set_error("mi355gp_sparse_predict: out of memory for the product scratch");
             return -3;
         }
-        sparse_expression(s, dVar, scr, false, [&](int pi, double* dst, const double* mul, int acc, bool) {
+        emit_expression(s->terms, dVar, scr, false, [&](int pi, double* dst, const double* mul, int acc, bool) {
             const SPart& p = s->parts[(size_t)pi];
             scale_new(p);
             launch_kbuild_cross(st, p.kp, dXt, ldn, Mn, dXt, ldn, Mn, dst, mnp, acc, /*diag_same=*/1, mul);
