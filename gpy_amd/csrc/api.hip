@@ -28,36 +28,14 @@ void mi355gp_set_error(const char* fmt, ...) {
     g_err = buf;
 }
 
-#define ARG_CHECK(cond, msg)              \
-    do {                                  \
-        if (!(cond)) {                    \
-            mi355gp_set_error("%s", msg); \
-            return -1;                    \
-        }                                 \
-    } while (0)
-
-#define COREG_REC 256          // doubles of one Coregionalize part's S (P x P, P <= 16)
 #define LOG_2_PI 1.8378770664093454836
-
-// Scoped device allocation for the stateless entry points: every early return (HIP_CHECK) releases what was acquired.
-struct DevBuf {
-    double* p = nullptr;
-    DevBuf() = default;
-    DevBuf(const DevBuf&) = delete;
-    DevBuf& operator=(const DevBuf&) = delete;
-    ~DevBuf() {
-        if (p) (void)hipFree(p);
-    }
-    hipError_t alloc(size_t doubles) { return hipMalloc(&p, sizeof(double) * (doubles ? doubles : 1)); }
-    operator double*() const { return p; }
-};
 
 struct mi355gp_ctx {
     int device = 0;
     hipStream_t st = nullptr;
     long n = 0, npad = 0;
     int D = 0, Dy = 0;
-    double *dX = nullptr, *dR = nullptr, *dInvLs = nullptr, *dNoise = nullptr;
+    double *dX = nullptr, *dR = nullptr, *dNoise = nullptr;
     double *A = nullptr, *B = nullptr, *C = nullptr;
     FactorWs ws;
     double *dAlpha = nullptr, *dTmp = nullptr, *dTrmvPart = nullptr, *dGradPart = nullptr, *dGradOut = nullptr,
@@ -68,9 +46,8 @@ struct mi355gp_ctx {
     bool have_factor = false, have_kernel = false;
     bool studentt = false;              // the last call was a Student-t process: dL_dK's alpha alpha^T term is scaled by dScal[4]
     // The covariance function of the last fused call as a sum of products of parts (GPy/kern/src/add.py, prod.py)
-    struct Part : PartSpec {
-        double* dXt = nullptr;          // D x npad scaled, dimension-major inputs of this part
-        double* dPw = nullptr;          // pw on the device (KernParams::pw)
+    struct Part : DevicePart {
+        DevBuf dXt;                     // D x npad scaled, dimension-major inputs of this part
     };
     std::vector<Part> parts;
     Terms terms;
@@ -118,14 +95,6 @@ static void apply_options(mi355gp_ctx* c) {
     if (c->opt[MI355GP_OPT_GRAPH] != INT_MIN) c->graph_enabled = c->opt[MI355GP_OPT_GRAPH] ? 1 : 0;
 }
 
-static void free_parts(mi355gp_ctx* c) {
-    for (auto& p : c->parts) {
-        if (p.dXt) (void)hipFree(p.dXt);
-        if (p.dPw) (void)hipFree(p.dPw);
-    }
-    c->parts.clear();
-}
-
 static void drop_graph(mi355gp_ctx* c) {
     if (c->fgraph) (void)hipGraphExecDestroy(c->fgraph);
     c->fgraph = nullptr;
@@ -134,8 +103,8 @@ static void drop_graph(mi355gp_ctx* c) {
 
 static void free_data(mi355gp_ctx* c) {
     drop_graph(c);                                            // every node holds pointers into the buffers freed below
-    free_parts(c);
-    double** ptrs[] = {&c->dX, &c->dR, &c->dInvLs, &c->dNoise, &c->A, &c->B, &c->C, &c->Mbuf,
+    c->parts.clear();
+    double** ptrs[] = {&c->dX, &c->dR, &c->dNoise, &c->A, &c->B, &c->C, &c->Mbuf,
                        &c->dTmp, &c->dTrmvPart, &c->dGradPart, &c->dGradOut, &c->dPack, &c->dCoregPart};
     for (auto p : ptrs) {
         if (*p) (void)hipFree(*p);
@@ -218,7 +187,6 @@ int mi355gp_set_data(mi355gp_ctx* c, const double* X, int64_t N, int D, const do
     const long np = c->npad;
     HIP_CHECK(hipMalloc(&c->dX, sizeof(double) * N * D));
     HIP_CHECK(hipMalloc(&c->dR, sizeof(double) * N * Dy));
-    HIP_CHECK(hipMalloc(&c->dInvLs, sizeof(double) * D));
     HIP_CHECK(hipMalloc(&c->dNoise, sizeof(double) * N));
     HIP_CHECK(hipMalloc(&c->A, sizeof(double) * np * np));
     HIP_CHECK(hipMalloc(&c->B, sizeof(double) * np * np));
@@ -532,12 +500,9 @@ extern "C" {
 static int prepare_parts(mi355gp_ctx* c, int nparts, const mi355gp_part* parts) {
     ARG_CHECK(nparts >= 1 && nparts <= 16 && parts, "between 1 and 16 kernel parts");
     if ((int)c->parts.size() != nparts) {
-        free_parts(c);
+        c->parts.clear();
         c->parts.resize((size_t)nparts);
-        for (auto& p : c->parts) {
-            HIP_CHECK(hipMalloc(&p.dXt, sizeof(double) * c->D * c->npad));
-            HIP_CHECK(hipMalloc(&p.dPw, sizeof(double) * std::max(2 * c->D, COREG_REC)));   // (B of a Coregionalize part)
-        }
+        for (auto& p : c->parts) HIP_CHECK(p.dXt.alloc((size_t)c->D * c->npad));
     }
     for (int i = 0; i < nparts; ++i) {
         mi355gp_ctx::Part& p = c->parts[(size_t)i];
@@ -553,10 +518,7 @@ static int prepare_parts(mi355gp_ctx* c, int nparts, const mi355gp_part* parts) 
             if (int rc = coreg_check_index(c->hIdx.data(), c->n, 1, p.kp.ard, "training")) return rc;
             if (!c->dCoregPart) HIP_CHECK(hipMalloc(&c->dCoregPart, sizeof(double) * grad_num_blocks(c->n) * COREG_REC));
         }
-        if (!p.pw.empty()) {
-            HIP_CHECK(hipMemcpyAsync(p.dPw, p.pw.data(), sizeof(double) * p.pw.size(), hipMemcpyHostToDevice, c->st));
-            p.kp.pw = p.dPw;
-        }
+        if (int rc = p.upload(c->st)) return rc;
     }
     c->terms = group_terms(c->parts);
     if (has_product(c->terms) && !c->Mbuf) HIP_CHECK(hipMalloc(&c->Mbuf, sizeof(double) * c->npad * c->npad));
@@ -564,13 +526,11 @@ static int prepare_parts(mi355gp_ctx* c, int nparts, const mi355gp_part* parts) 
 }
 
 // scaled inputs of every part (inactive dimensions scaled by 0: they drop out of r), on the context's stream
-static int scale_parts(mi355gp_ctx* c) {
-    for (auto& p : c->parts) {
-        HIP_CHECK(hipMemcpyAsync(c->dInvLs, p.inv_ls.data(), sizeof(double) * c->D, hipMemcpyHostToDevice, c->st));
-        launch_scale_inputs(c->st, c->dX, c->n, c->D, c->dInvLs, /*per-dimension vector*/ 1, p.dXt, c->npad);
-    }
-    return 0;
+static void scale_parts(mi355gp_ctx* c) {
+    for (auto& p : c->parts) launch_scale_inputs(c->st, c->dX, c->n, c->D, p.dIl, /*per-dimension vector*/ 1, p.dXt, c->npad);
 }
+// the training inputs as one side of a cross-covariance (emit_cross)
+static Resident<mi355gp_ctx::Part> training_points(const mi355gp_ctx* c) { return {&mi355gp_ctx::Part::dXt, c->npad, c->n}; }
 
 int mi355gp_exact_inference_sum(mi355gp_ctx* c, int nparts, const mi355gp_part* parts, const double* noise,
                                 int64_t noise_len, double jitter, double extra_jitter, double* out_scalars,
@@ -584,7 +544,7 @@ int mi355gp_exact_inference_sum(mi355gp_ctx* c, int nparts, const mi355gp_part* 
     hipStream_t st = c->st;
     c->have_kernel = true;
     HIP_CHECK(hipEventRecord(c->ev[0], st));
-    if (int rc = scale_parts(c)) return rc;
+    scale_parts(c);
     // Ky = sum_t prod_f K_f + (noise + jitter) I   (add.py:58-72, prod.py:58-65)
     auto build = [&]() -> int {
         emit_expression(c->terms, c->A, c->Mbuf, false, [&](int p, double* dst, const double* mul, int acc, bool first) {
@@ -613,7 +573,7 @@ int mi355gp_exact_studentt_sum(mi355gp_ctx* c, int nparts, const mi355gp_part* p
     hipStream_t st = c->st;
     c->have_kernel = true;
     HIP_CHECK(hipEventRecord(c->ev[0], st));
-    if (int rc = scale_parts(c)) return rc;
+    scale_parts(c);
     auto build = [&]() -> int {
         emit_expression(c->terms, c->A, c->Mbuf, false, [&](int p, double* dst, const double* mul, int acc, bool first) {
             launch_kbuild_sym(st, c->parts[(size_t)p].kp, c->parts[(size_t)p].dXt, c->npad, c->n, c->npad, dst, c->dNoise, 1,
@@ -661,28 +621,19 @@ int mi355gp_fetch(mi355gp_ctx* c, int which, double* out, int fortran_order) {
     EngineShared gate(c->device);
     const long n = c->n, np = c->npad;
     hipStream_t st = c->st;
-    double* tmp = nullptr;
-    HIP_CHECK(hipMalloc(&tmp, sizeof(double) * n * n));
-    int rc = 0;
+    DevBuf tmp, scratch;
+    HIP_CHECK(tmp.alloc(n * n));
     if (which == MI355GP_FETCH_K) {
         if (!c->have_kernel) {
             mi355gp_set_error("mi355gp_fetch(K): no device kernel evaluation in this context");
-            rc = -4;
-        } else {
-            double* scratch = nullptr;
-            if (has_product(c->terms)) HIP_CHECK(hipMalloc(&scratch, sizeof(double) * n * n));
-            emit_expression(c->terms, tmp, scratch, false, [&](int p, double* dst, const double* mul, int acc, bool) {
-                const mi355gp_ctx::Part& pt = c->parts[(size_t)p];                 // symmetric: no transpose needed
-                launch_kbuild_cross(st, pt.kp, pt.dXt, np, n, pt.dXt, np, n, dst, n, acc, /*diag_same=*/1, mul);
-            });
-            if (scratch) {
-                HIP_CHECK(hipStreamSynchronize(st));
-                (void)hipFree(scratch);
-            }
+            return -4;
         }
+        if (has_product(c->terms)) HIP_CHECK(scratch.alloc(n * n));
+        const auto x = training_points(c);                                                 // symmetric: no transpose needed
+        emit_cross(st, c->parts, c->terms, x, x, tmp, n, scratch, false, /*diag_same=*/1);
     } else if (!c->have_factor) {
         mi355gp_set_error("mi355gp_fetch: no successful factorisation in this context");
-        rc = -4;
+        return -4;
     } else if (which == MI355GP_FETCH_L) {
         launch_extract(st, c->A, np, n, 0, nullptr, 0, tmp, fortran_order);
     } else if (which == MI355GP_FETCH_LINV) {
@@ -693,25 +644,17 @@ int mi355gp_fetch(mi355gp_ctx* c, int which, double* out, int fortran_order) {
         launch_extract(st, c->C, np, n, 2, c->dAlpha, c->Dy, tmp, 0, c->studentt ? c->dScal + 4 : nullptr);
     } else {
         mi355gp_set_error("mi355gp_fetch: unknown matrix id %d", which);
-        rc = -1;
+        return -1;
     }
-    if (rc == 0) {
-        hipError_t e = hipMemcpyAsync(out, tmp, sizeof(double) * n * n, hipMemcpyDeviceToHost, st);
-        if (e == hipSuccess) e = hipStreamSynchronize(st);
-        if (e != hipSuccess) {
-            mi355gp_set_error("mi355gp_fetch: %s", hipGetErrorString(e));
-            rc = -(1000 + (int)e);
-        }
-    }
-    (void)hipFree(tmp);
-    return rc;
+    HIP_CHECK(hipMemcpyAsync(out, tmp, sizeof(double) * n * n, hipMemcpyDeviceToHost, st));
+    HIP_CHECK(hipStreamSynchronize(st));
+    return 0;
 }
 
 // ---- stateless kernel-function entry points --------------------------------------------------------
 // The one part of a stateless call over all D columns of X, its inv_ls and pw on the device.  Coregionalize: D = 1, X / X2 are
 // the output-index columns themselves (their indices validated here).
-struct StatelessPart : PartSpec {
-    DevBuf dIl, dPw;
+struct StatelessPart : DevicePart {
     int load(int kind, int ard, const double* theta, int D, KindSet accepted, const char* where, const double* X, int64_t N,
              const double* X2, int64_t M) {
         const int col0 = 0;
@@ -723,27 +666,12 @@ struct StatelessPart : PartSpec {
             if (X2)
                 if (int rc = coreg_check_index(X2, M, 1, ard, "X2")) return rc;
         }
-        HIP_CHECK(dIl.alloc(D));
-        HIP_CHECK(hipMemcpy(dIl, inv_ls.data(), sizeof(double) * D, hipMemcpyHostToDevice));
-        if (!pw.empty()) {
-            HIP_CHECK(dPw.alloc(pw.size()));
-            HIP_CHECK(hipMemcpy(dPw, pw.data(), sizeof(double) * pw.size(), hipMemcpyHostToDevice));
-            kp.pw = dPw;
-        }
-        return 0;
+        return upload(0);
     }
-};
-
-// rows x D points (host) uploaded and scaled by inv_ls into dimension-major t (D x ld)
-struct ScaledInputs {
-    DevBuf raw, t;
-    long ld = 0;
-    int load(const double* X, int64_t rows, int D, const double* dIl) {
-        ld = round_up(rows, 64);
-        HIP_CHECK(raw.alloc(rows * D));
-        HIP_CHECK(t.alloc(D * ld));
-        HIP_CHECK(hipMemcpy(raw, X, sizeof(double) * rows * D, hipMemcpyHostToDevice));
-        launch_scale_inputs(0, raw, rows, D, dIl, 1, t, ld);
+    // X (n x D, host) uploaded into xs and scaled for this part
+    int scaled(PointSet& xs, const double* X, int64_t n) const {
+        if (int rc = xs.load(0, X, n, (int)inv_ls.size())) return rc;
+        xs.points(0, *this);
         return 0;
     }
 };
@@ -757,11 +685,11 @@ int mi355gp_kern_K(int device, int kind, int ard, const double* theta, const dou
     ARG_CHECK(M > 0, "mi355gp_kern_K: M must be positive");
     StatelessPart pt;
     if (int rc = pt.load(kind, ard, theta, D, KS_STATIONARY | KS_EXT | KS_COREG, "mi355gp_kern_K", X, N, X2, M)) return rc;
-    ScaledInputs x1, x2;
-    if (int rc = x1.load(X, N, D, pt.dIl)) return rc;
+    PointSet x1, x2;
+    if (int rc = pt.scaled(x1, X, N)) return rc;
     if (!sym)
-        if (int rc = x2.load(X2, M, D, pt.dIl)) return rc;
-    const ScaledInputs& y = sym ? x1 : x2;
+        if (int rc = pt.scaled(x2, X2, M)) return rc;
+    const PointSet& y = sym ? x1 : x2;
     DevBuf dK;
     HIP_CHECK(dK.alloc(N * M));
     launch_kbuild_cross(0, pt.kp, x1.t, x1.ld, N, y.t, y.ld, M, dK, M);
@@ -790,11 +718,11 @@ int mi355gp_update_gradients_full(int device, int kind, int ard, const double* t
     StatelessPart pt;
     if (int rc = pt.load(kind, ard, theta, D, KS_STATIONARY | KS_EXT | KS_COREG, "mi355gp_update_gradients_full", X, N, X2, M))
         return rc;
-    ScaledInputs x1, x2;
-    if (int rc = x1.load(X, N, D, pt.dIl)) return rc;
+    PointSet x1, x2;
+    if (int rc = pt.scaled(x1, X, N)) return rc;
     if (!sym)
-        if (int rc = x2.load(X2, M, D, pt.dIl)) return rc;
-    const ScaledInputs& y = sym ? x1 : x2;
+        if (int rc = pt.scaled(x2, X2, M)) return rc;
+    const PointSet& y = sym ? x1 : x2;
     const int groups = (D + 31) / 32, nrec = pt.ext() ? 2 : 1;
     const size_t nsums = std::max((size_t)2 * groups * GP_STRIDE, (size_t)COREG_REC);
     DevBuf dG, dPart, dOut;
@@ -834,9 +762,9 @@ int mi355gp_gradients_X(int device, int kind, int ard, const double* theta, cons
     const bool sym = (X2 == nullptr);
     if (sym) { M = N; X2 = X; }
     ARG_CHECK(M > 0, "mi355gp_gradients_X: M must be positive");
-    ScaledInputs xc, xr;                                     // X and X2
-    if (int rc = xc.load(X, N, D, pt.dIl)) return rc;
-    if (int rc = xr.load(X2, M, D, pt.dIl)) return rc;
+    PointSet xc, xr;                                         // X and X2
+    if (int rc = pt.scaled(xc, X, N)) return rc;
+    if (int rc = pt.scaled(xr, X2, M)) return rc;
     if (kind == MI355GP_STDPERIODIC) {
         // StdPeriodic.gradients_X (standard_periodic.py:574-580): dX[i][q] = -pi / (2 T_q l_q^2) sum_j W_ij K_ij sin(2 Delta_ijq),
         // W = dL_dK (+ dL_dK^T against X itself), as a row reduction on the device (k_periodic_gradx)
@@ -850,9 +778,7 @@ int mi355gp_gradients_X(int device, int kind, int ard, const double* theta, cons
         launch_periodic_gradx(0, pt.kp, xc.t, xc.ld, N, xr.t, xr.ld, M, dW, M, 0, dOut);
         HIP_CHECK(hipMemcpy(out, dOut, sizeof(double) * N * D, hipMemcpyDeviceToHost));
         HIP_CHECK(hipGetLastError());
-        const std::vector<double>& pw = pt.pw;
-        for (int64_t i = 0; i < N; ++i)
-            for (int q = 0; q < D; ++q) out[i * D + q] *= -0.5 * pw[(size_t)q] * pw[(size_t)(D + q)] * pw[(size_t)(D + q)];
+        gradx_periodic(pt.pw, N, D, out, [&](long i, int q, double g) { out[i * D + q] = g; });      // in place
         return 0;
     }
     // transposed weights G' (M x N): rows = X2 points, columns = X points
@@ -869,13 +795,10 @@ int mi355gp_gradients_X(int device, int kind, int ard, const double* theta, cons
     launch_grad_generic(0, pt.kp, xr.t, xr.ld, M, xc.t, xc.ld, N, 0, dG, N, dPart, GP_STRIDE, dG, N);   // H in place
     const int ns = launch_colreduce_multi(0, dG, N, M, N, xr.t, 1, xr.ld, D, 1, dCol);
     launch_sum_splits(0, dCol, N * (D + 1), ns, 0, dHX);
-    std::vector<double> HX((size_t)N * (D + 1)), Xs((size_t)D * xc.ld);
+    std::vector<double> HX((size_t)N * (D + 1));
     HIP_CHECK(hipMemcpy(HX.data(), dHX, sizeof(double) * HX.size(), hipMemcpyDeviceToHost));
-    HIP_CHECK(hipMemcpy(Xs.data(), xc.t, sizeof(double) * Xs.size(), hipMemcpyDeviceToHost));
     HIP_CHECK(hipGetLastError());
-    for (int64_t i = 0; i < N; ++i)
-        for (int q = 0; q < D; ++q)
-            out[i * D + q] = (Xs[(size_t)q * xc.ld + i] * HX[i * (D + 1) + D] - HX[i * (D + 1) + q]) * pt.inv_ls[(size_t)q];
+    gradx_stationary(X, N, D, pt.inv_ls, HX.data(), [&](long i, int q, double g) { out[i * D + q] = g; });
     return 0;
 }
 
@@ -986,18 +909,17 @@ int mi355gp_predict_sum(mi355gp_ctx* c, int nparts, const mi355gp_part* parts, c
     if (int rc = prepare_parts(c, nparts, parts)) return rc;
     if (int rc = coreg_check_points(c, Xnew, M, "prediction")) return rc;
     hipStream_t st = c->st;
-    const long n = c->n, np = c->npad, D = c->D, mp = round_up(M, NB), ld2 = round_up(M, 64);
+    const long n = c->n, np = c->npad, mp = round_up(M, NB);
     // (re)scale the training inputs for these parameters (normally identical to the inference call's)
     c->have_kernel = true;
-    if (int rc = scale_parts(c)) return rc;
-    DevBuf dXn, dXt2, dKx, dTmp, dMu, dVar;
-    HIP_CHECK(dXn.alloc(M * D));
-    HIP_CHECK(dXt2.alloc(D * ld2));
+    scale_parts(c);
+    PointSet xs;
+    DevBuf dKx, dTmp, dMu, dVar;
+    if (int rc = xs.load(st, Xnew, M, c->D)) return rc;
     HIP_CHECK(dKx.alloc(np * mp));
     HIP_CHECK(dTmp.alloc(np * mp));
     HIP_CHECK(dMu.alloc(M * c->Dy));
     HIP_CHECK(dVar.alloc((full_cov ? mp * mp : M)));
-    HIP_CHECK(hipMemcpyAsync(dXn, Xnew, sizeof(double) * M * D, hipMemcpyHostToDevice, st));
     HIP_CHECK(hipMemsetAsync(dKx, 0, sizeof(double) * np * mp, st));
     if (full_cov && var_out) HIP_CHECK(hipMemsetAsync(dVar, 0, sizeof(double) * mp * mp, st));
     const double kdiag = expression_kdiag(c->parts, c->terms);                   // Kdiag(X*): sum over terms of the product of variances
@@ -1014,24 +936,8 @@ int mi355gp_predict_sum(mi355gp_ctx* c, int nparts, const mi355gp_part* parts, c
         HIP_CHECK(dScr1.alloc(np * mp));
         if (full_cov && var_out) HIP_CHECK(dScr2.alloc(mp * mp));
     }
-    hipError_t herr = hipSuccess;
-    auto scale_new = [&](const mi355gp_ctx::Part& pt) {
-        hipError_t e = hipMemcpyAsync(c->dInvLs, pt.inv_ls.data(), sizeof(double) * D, hipMemcpyHostToDevice, st);
-        if (e != hipSuccess) herr = e;
-        launch_scale_inputs(st, dXn, M, c->D, c->dInvLs, 1, dXt2, ld2);
-    };
-    emit_expression(c->terms, dKx, dScr1, true, [&](int p, double* dst, const double* mul, int acc, bool) {
-        const mi355gp_ctx::Part& pt = c->parts[(size_t)p];
-        scale_new(pt);
-        launch_kbuild_cross(st, pt.kp, pt.dXt, np, n, dXt2, ld2, M, dst, mp, acc, 0, mul);                 // K(X, X*) (n x M)
-    });
-    if (full_cov && var_out)
-        emit_expression(c->terms, dVar, dScr2, true, [&](int p, double* dst, const double* mul, int acc, bool) {
-            const mi355gp_ctx::Part& pt = c->parts[(size_t)p];
-            scale_new(pt);
-            launch_kbuild_cross(st, pt.kp, dXt2, ld2, M, dXt2, ld2, M, dst, mp, acc, /*diag_same=*/1, mul);  // K(X*, X*)
-        });
-    HIP_CHECK(herr);
+    emit_cross(st, c->parts, c->terms, training_points(c), xs, dKx, mp, dScr1, true, 0);                    // K(X, X*) (n x M)
+    if (full_cov && var_out) emit_cross(st, c->parts, c->terms, xs, xs, dVar, mp, dScr2, true, /*diag_same=*/1);  // K(X*, X*)
     launch_col_reduce(st, dKx, mp, n, M, c->dAlpha, c->Dy, 0.0, 0, dMu);                  // mu = Kx^T alpha
     launch_trmm_lower(st, c->B, np, dKx, mp, dTmp, mp, (int)(np / NB), (int)(mp / NB));   // tmp = L^-1 Kx
     if (!full_cov) {
@@ -1076,12 +982,12 @@ int mi355gp_predictive_gradients_sum(mi355gp_ctx* c, int nparts, const mi355gp_p
     ARG_CHECK(!has_product(c->terms), "mi355gp_predictive_gradients: product kernels are not supported on the device");
     ARG_CHECK(!has_coreg(c), "mi355gp_predictive_gradients: Coregionalize (kind 8) parts are not supported on the device");
     hipStream_t st = c->st;
-    const long n = c->n, np = c->npad, D = c->D, Dy = c->Dy, mp = round_up(M, NB), ld2 = round_up(M, 64);
+    const long n = c->n, np = c->npad, D = c->D, Dy = c->Dy, mp = round_up(M, NB);
     c->have_kernel = true;
-    if (int rc = scale_parts(c)) return rc;
-    DevBuf dXn, dXt2, dU, dT, dG, dH, dPart, dCol, dHX;
-    HIP_CHECK(dXn.alloc(M * D));
-    HIP_CHECK(dXt2.alloc(D * ld2));
+    scale_parts(c);
+    PointSet xs;
+    DevBuf dU, dT, dG, dH, dPart, dCol, dHX;
+    if (int rc = xs.load(st, Xnew, M, c->D)) return rc;
     HIP_CHECK(dU.alloc(np * mp));
     HIP_CHECK(dT.alloc(np * mp));
     HIP_CHECK(dG.alloc(np * mp));
@@ -1089,24 +995,12 @@ int mi355gp_predictive_gradients_sum(mi355gp_ctx* c, int nparts, const mi355gp_p
     HIP_CHECK(dPart.alloc(2 * 2048 * GP_STRIDE * ((D + 31) / 32)));   // second records of RatQuad parts
     HIP_CHECK(dCol.alloc(64 * mp * (D + 1)));
     HIP_CHECK(dHX.alloc(mp * (D + 1)));
-    HIP_CHECK(hipMemcpyAsync(dXn, Xnew, sizeof(double) * M * D, hipMemcpyHostToDevice, st));
-    hipError_t herr = hipSuccess;
-    auto scale_new = [&](const mi355gp_ctx::Part& pt) {
-        hipError_t e = hipMemcpyAsync(c->dInvLs, pt.inv_ls.data(), sizeof(double) * D, hipMemcpyHostToDevice, st);
-        if (e != hipSuccess) herr = e;
-        launch_scale_inputs(st, dXn, M, c->D, c->dInvLs, 1, dXt2, ld2);
-    };
     if (dvar_out) {     // U = Ky^-1 K(X, X*)
         HIP_CHECK(hipMemsetAsync(dU, 0, sizeof(double) * np * mp, st));
-        emit_expression(c->terms, dU, nullptr, true, [&](int p, double* dst, const double* mul, int acc, bool) {
-            const mi355gp_ctx::Part& pt = c->parts[(size_t)p];
-            scale_new(pt);
-            launch_kbuild_cross(st, pt.kp, pt.dXt, np, n, dXt2, ld2, M, dst, mp, acc, 0, mul);
-        });
+        emit_cross(st, c->parts, c->terms, training_points(c), xs, dU, mp, nullptr, true, 0);
         launch_trmm_lower(st, c->B, np, dU, mp, dT, mp, (int)(np / NB), (int)(mp / NB));
         launch_trmm_lower_T(st, c->B, np, dT, mp, dU, mp, (int)(np / NB), (int)(mp / NB));
     }
-    HIP_CHECK(herr);
     // one pass per weight matrix (Dy mean parts, one variance part) and stationary part
     const size_t hx = (size_t)M * (D + 1);
     std::vector<double> HX(hx);
@@ -1122,36 +1016,27 @@ int mi355gp_predictive_gradients_sum(mi355gp_ctx* c, int nparts, const mi355gp_p
                                c->dAlpha + pass, (int)Dy);
             W = dG;
         }
+        auto add = [&](long m, int q, double g) {
+            if (is_var) dvar_out[m * D + q] += -2.0 * g;
+            else dmu_out[((size_t)m * D + q) * Dy + pass] += g;
+        };
         for (size_t pi = 0; pi < c->parts.size(); ++pi) {
             const mi355gp_ctx::Part& pt = c->parts[pi];
             if (pt.is_static()) continue;                                        // White / Bias: no dependence on X* (static.py)
-            scale_new(pt);
-            HIP_CHECK(herr);
+            const double* xt = xs.points(st, pt);
             if (pt.kp.kind == MI355GP_STDPERIODIC) {                    // not a function of r: the row reduction instead of H
-                launch_periodic_gradx(st, pt.kp, dXt2, ld2, M, pt.dXt, np, n, W, mp, /*wt=*/1, dHX);
+                launch_periodic_gradx(st, pt.kp, xt, xs.ld, M, pt.dXt, np, n, W, mp, /*wt=*/1, dHX);
                 HIP_CHECK(hipMemcpyAsync(HX.data(), dHX, sizeof(double) * M * D, hipMemcpyDeviceToHost, st));
                 HIP_CHECK(hipStreamSynchronize(st));
-                for (int64_t m = 0; m < M; ++m)
-                    for (long q = 0; q < D; ++q) {
-                        const double il = pt.pw[(size_t)(D + q)];
-                        const double g = -0.5 * pt.pw[(size_t)q] * il * il * HX[(size_t)m * D + q];
-                        if (is_var) dvar_out[m * D + q] += -2.0 * g;
-                        else dmu_out[((size_t)m * D + q) * Dy + pass] += g;
-                    }
+                gradx_periodic(pt.pw, M, (int)D, HX.data(), add);
                 continue;
             }
-            launch_grad_generic(st, pt.kp, pt.dXt, np, n, dXt2, ld2, M, 0, W, mp, dPart, GP_STRIDE, dH, mp);
+            launch_grad_generic(st, pt.kp, pt.dXt, np, n, xt, xs.ld, M, 0, W, mp, dPart, GP_STRIDE, dH, mp);
             const int ns = launch_colreduce_multi(st, dH, mp, n, M, pt.dXt, 1, np, (int)D, 1, dCol);
             launch_sum_splits(st, dCol, (long)hx, ns, 0, dHX);
             HIP_CHECK(hipMemcpyAsync(HX.data(), dHX, sizeof(double) * hx, hipMemcpyDeviceToHost, st));
             HIP_CHECK(hipStreamSynchronize(st));
-            for (int64_t m = 0; m < M; ++m)
-                for (long q = 0; q < D; ++q) {
-                    const double il = pt.inv_ls[(size_t)q];                  // 0 for dimensions outside active_dims
-                    const double g = (Xnew[m * D + q] * il * HX[(size_t)m * (D + 1) + D] - HX[(size_t)m * (D + 1) + q]) * il;
-                    if (is_var) dvar_out[m * D + q] += -2.0 * g;
-                    else dmu_out[((size_t)m * D + q) * Dy + pass] += g;
-                }
+            gradx_stationary(Xnew, M, (int)D, pt.inv_ls, HX.data(), add);       // (il = 0 outside active_dims)
         }
     }
     HIP_CHECK(hipStreamSynchronize(st));
@@ -1171,22 +1056,18 @@ int mi355gp_covariance_between_points(mi355gp_ctx* c, int nparts, const mi355gp_
     if (int rc = coreg_check_points(c, X1, M1, "X1")) return rc;
     if (int rc = coreg_check_points(c, X2, M2, "X2")) return rc;
     hipStream_t st = c->st;
-    const long n = c->n, np = c->npad, D = c->D;
-    const long m1p = round_up(M1, NB), m2p = round_up(M2, NB), l1 = round_up(M1, 64), l2 = round_up(M2, 64);
+    const long np = c->npad, m1p = round_up(M1, NB), m2p = round_up(M2, NB);
     c->have_kernel = true;
-    if (int rc = scale_parts(c)) return rc;
-    DevBuf dA, dB, dXtA, dXtB, dK1, dK2, dT1, dT2, dC;
-    HIP_CHECK(dA.alloc(M1 * D));
-    HIP_CHECK(dB.alloc(M2 * D));
-    HIP_CHECK(dXtA.alloc(D * l1));
-    HIP_CHECK(dXtB.alloc(D * l2));
+    scale_parts(c);
+    PointSet x1, x2;
+    DevBuf dK1, dK2, dT1, dT2, dC;
+    if (int rc = x1.load(st, X1, M1, c->D)) return rc;
+    if (int rc = x2.load(st, X2, M2, c->D)) return rc;
     HIP_CHECK(dK1.alloc(np * m1p));
     HIP_CHECK(dK2.alloc(np * m2p));
     HIP_CHECK(dT1.alloc(np * m1p));
     HIP_CHECK(dT2.alloc(np * m2p));
     HIP_CHECK(dC.alloc(m1p * m2p));
-    HIP_CHECK(hipMemcpyAsync(dA, X1, sizeof(double) * M1 * D, hipMemcpyHostToDevice, st));
-    HIP_CHECK(hipMemcpyAsync(dB, X2, sizeof(double) * M2 * D, hipMemcpyHostToDevice, st));
     HIP_CHECK(hipMemsetAsync(dK1, 0, sizeof(double) * np * m1p, st));
     HIP_CHECK(hipMemsetAsync(dK2, 0, sizeof(double) * np * m2p, st));
     HIP_CHECK(hipMemsetAsync(dC, 0, sizeof(double) * m1p * m2p, st));
@@ -1196,29 +1077,9 @@ int mi355gp_covariance_between_points(mi355gp_ctx* c, int nparts, const mi355gp_
         HIP_CHECK(dS2.alloc(np * m2p));
         HIP_CHECK(dS3.alloc(m1p * m2p));
     }
-    hipError_t herr = hipSuccess;
-    auto scale_new = [&](const mi355gp_ctx::Part& pt) {
-        hipError_t e = hipMemcpyAsync(c->dInvLs, pt.inv_ls.data(), sizeof(double) * D, hipMemcpyHostToDevice, st);
-        if (e != hipSuccess) herr = e;
-        launch_scale_inputs(st, dA, M1, c->D, c->dInvLs, 1, dXtA, l1);
-        launch_scale_inputs(st, dB, M2, c->D, c->dInvLs, 1, dXtB, l2);
-    };
-    emit_expression(c->terms, dK1, dS1, true, [&](int p, double* dst, const double* mul, int acc, bool) {
-        const mi355gp_ctx::Part& pt = c->parts[(size_t)p];
-        scale_new(pt);
-        launch_kbuild_cross(st, pt.kp, pt.dXt, np, n, dXtA, l1, M1, dst, m1p, acc, 0, mul);
-    });
-    emit_expression(c->terms, dK2, dS2, true, [&](int p, double* dst, const double* mul, int acc, bool) {
-        const mi355gp_ctx::Part& pt = c->parts[(size_t)p];
-        scale_new(pt);
-        launch_kbuild_cross(st, pt.kp, pt.dXt, np, n, dXtB, l2, M2, dst, m2p, acc, 0, mul);
-    });
-    emit_expression(c->terms, dC, dS3, true, [&](int p, double* dst, const double* mul, int acc, bool) {
-        const mi355gp_ctx::Part& pt = c->parts[(size_t)p];
-        scale_new(pt);
-        launch_kbuild_cross(st, pt.kp, dXtA, l1, M1, dXtB, l2, M2, dst, m2p, acc, 0, mul);
-    });
-    HIP_CHECK(herr);
+    emit_cross(st, c->parts, c->terms, training_points(c), x1, dK1, m1p, dS1, true, 0);
+    emit_cross(st, c->parts, c->terms, training_points(c), x2, dK2, m2p, dS2, true, 0);
+    emit_cross(st, c->parts, c->terms, x1, x2, dC, m2p, dS3, true, 0);
     launch_trmm_lower(st, c->B, np, dK1, m1p, dT1, m1p, (int)(np / NB), (int)(m1p / NB));
     launch_trmm_lower(st, c->B, np, dK2, m2p, dT2, m2p, (int)(np / NB), (int)(m2p / NB));
     launch_gemm(st, 1, 1, m1p, m2p, np, dT1, m1p, dT2, m2p, dC, m2p, -1.0, 1.0);

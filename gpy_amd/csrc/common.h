@@ -55,6 +55,28 @@ void mi355gp_set_error(const char* fmt, ...);
             return -(1000 + (int)_e);                                                            \
         }                                                                                        \
     } while (0)
+#define ARG_CHECK(cond, msg)              \
+    do {                                  \
+        if (!(cond)) {                    \
+            mi355gp_set_error("%s", msg); \
+            return -1;                    \
+        }                                 \
+    } while (0)
+
+// Scoped device allocation: every early return (HIP_CHECK) releases what was acquired.  Movable, so that the owners of
+// per-part buffers can keep them in a std::vector.
+struct DevBuf {
+    double* p = nullptr;
+    DevBuf() = default;
+    DevBuf(DevBuf&& o) noexcept : p(o.p) { o.p = nullptr; }
+    DevBuf(const DevBuf&) = delete;
+    DevBuf& operator=(const DevBuf&) = delete;
+    ~DevBuf() {
+        if (p) (void)hipFree(p);
+    }
+    hipError_t alloc(size_t doubles) { return hipMalloc(&p, sizeof(double) * (doubles ? doubles : 1)); }
+    operator double*() const { return p; }
+};
 
 static inline int64_t round_up(int64_t n, int64_t m) { return (n + m - 1) / m * m; }
 

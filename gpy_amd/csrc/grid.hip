@@ -34,13 +34,6 @@
 #include "parts.h"
 
 #define LOG_2_PI 1.8378770664093454836
-#define ARGCHK(cond, msg)                 \
-    do {                                  \
-        if (!(cond)) {                    \
-            mi355gp_set_error("%s", msg); \
-            return -1;                    \
-        }                                 \
-    } while (0)
 
 // ---------------------------------------------------------------------------------------------------
 // RCCL: types, enums and prototypes come from the installed <rccl/rccl.h>; the library itself is dlopen'ed (so the
@@ -1032,7 +1025,7 @@ static int grid_check_sequences(mi355gp_grid* g) {
 extern "C" {
 
 int mi355gp_grid_unique_id(void* id128) {
-    ARGCHK(id128 != nullptr, "mi355gp_grid_unique_id: NULL");
+    ARG_CHECK(id128 != nullptr, "mi355gp_grid_unique_id: NULL");
     if (!g_rccl.load()) return -20;
     ncclUniqueId id;
     NCCL_CHECK(g_rccl.GetUniqueId(&id));
@@ -1042,9 +1035,9 @@ int mi355gp_grid_unique_id(void* id128) {
 
 int mi355gp_grid_create(int device, int rank, int world, int Pr, int Pc, int nb, const void* id128,
                         mi355gp_grid** out) {
-    ARGCHK(out && Pr >= 1 && Pc >= 1 && nb >= NB && nb % NB == 0, "mi355gp_grid_create: Pr, Pc >= 1, nb % 128 == 0");
-    ARGCHK(world == Pr * Pc, "mi355gp_grid_create: world must equal Pr*Pc");
-    ARGCHK(rank >= 0 && rank < world, "mi355gp_grid_create: bad rank");
+    ARG_CHECK(out && Pr >= 1 && Pc >= 1 && nb >= NB && nb % NB == 0, "mi355gp_grid_create: Pr, Pc >= 1, nb % 128 == 0");
+    ARG_CHECK(world == Pr * Pc, "mi355gp_grid_create: world must equal Pr*Pc");
+    ARG_CHECK(rank >= 0 && rank < world, "mi355gp_grid_create: bad rank");
     int ndev = 0;
     mi355gp_device_count(&ndev);
     if (device < 0 || device >= ndev) {
@@ -1142,7 +1135,7 @@ int mi355gp_grid_destroy(mi355gp_grid* g) {
 
 // Every rank passes the full (replicated) X and R: N*D*8 bytes is small next to the N^2/P matrix share.
 int mi355gp_grid_set_data(mi355gp_grid* g, const double* X, int64_t N, int D, const double* R, int Dy) {
-    ARGCHK(g && X && R && N > 0 && D > 0 && Dy > 0, "mi355gp_grid_set_data: bad arguments");
+    ARG_CHECK(g && X && R && N > 0 && D > 0 && Dy > 0, "mi355gp_grid_set_data: bad arguments");
     if (g->single) {
         g->n = N;
         return mi355gp_set_data(g->single, X, N, D, R, Dy);
@@ -1606,8 +1599,8 @@ extern "C" {
 int mi355gp_grid_exact_inference(mi355gp_grid* g, int kind, int ard, const double* theta, const double* noise,
                                  int64_t noise_len, double jitter, double extra_jitter, double* out_scalars,
                                  double* alpha_out, double* dtheta_out, double* diag_dLdK_out, double* stage_ms) {
-    ARGCHK(g && g->n > 0, "mi355gp_grid_exact_inference: set_data first");
-    ARGCHK(out_scalars && theta && noise, "mi355gp_grid_exact_inference: NULL argument");
+    ARG_CHECK(g && g->n > 0, "mi355gp_grid_exact_inference: set_data first");
+    ARG_CHECK(out_scalars && theta && noise, "mi355gp_grid_exact_inference: NULL argument");
     if (int rc = check_kind(kind, KS_STATIONARY, "grid path")) return rc;     // (not the exact-only kinds 6 / 7 / 8)
     if (g->single) {
         double ms[MI355GP_NUM_T];
@@ -1624,7 +1617,7 @@ int mi355gp_grid_exact_inference(mi355gp_grid* g, int kind, int ard, const doubl
         g->have_result = (rc == 0);
         return rc;
     }
-    ARGCHK(noise_len == 1 || noise_len == g->n, "noise must have 1 or N entries");
+    ARG_CHECK(noise_len == 1 || noise_len == g->n, "noise must have 1 or N entries");
     PartSpec pt;
     if (int rc = parse_part(mi355gp_part{kind, ard, 0, nullptr, theta, 0}, g->D, KS_STATIONARY, "grid path", &pt)) return rc;
     HIP_CHECK(hipSetDevice(g->device));
@@ -1633,8 +1626,8 @@ int mi355gp_grid_exact_inference(mi355gp_grid* g, int kind, int ard, const doubl
 }
 
 int mi355gp_grid_set_option(mi355gp_grid* g, int option, int value) {
-    ARGCHK(g && option >= 0 && option < MI355GP_GRID_OPT_NUM, "mi355gp_grid_set_option: unknown option");
-    ARGCHK(value >= -1, "mi355gp_grid_set_option: value must be >= 0 (or -1 for the default)");
+    ARG_CHECK(g && option >= 0 && option < MI355GP_GRID_OPT_NUM, "mi355gp_grid_set_option: unknown option");
+    ARG_CHECK(value >= -1, "mi355gp_grid_set_option: value must be >= 0 (or -1 for the default)");
     if (g->single) return 0;                              // the degenerate 1 x 1 grid runs the single-GPU pipeline
     if (value < 0) {
         grid_default_option(g, option);
@@ -1642,7 +1635,7 @@ int mi355gp_grid_set_option(mi355gp_grid* g, int option, int value) {
     }
     if (option == MI355GP_GRID_OPT_LOOKAHEAD) g->lookahead = value ? 1 : 0;
     else if (option == MI355GP_GRID_OPT_G) {
-        ARGCHK(value >= 1, "mi355gp_grid_set_option: G >= 1");
+        ARG_CHECK(value >= 1, "mi355gp_grid_set_option: G >= 1");
         g->G = value;
     } else if (option == MI355GP_GRID_OPT_CHECK_SEQ) g->check_seq = value ? 1 : 0;
     else g->GW = value;
@@ -1650,7 +1643,7 @@ int mi355gp_grid_set_option(mi355gp_grid* g, int option, int value) {
 }
 
 int mi355gp_grid_get_option(mi355gp_grid* g, int option, int* value) {
-    ARGCHK(g && value && option >= 0 && option < MI355GP_GRID_OPT_NUM, "mi355gp_grid_get_option: unknown option");
+    ARG_CHECK(g && value && option >= 0 && option < MI355GP_GRID_OPT_NUM, "mi355gp_grid_get_option: unknown option");
     *value = option == MI355GP_GRID_OPT_LOOKAHEAD ? g->lookahead : option == MI355GP_GRID_OPT_G ? g->G
              : option == MI355GP_GRID_OPT_CHECK_SEQ ? g->check_seq : g->GW;
     return 0;
@@ -1659,10 +1652,10 @@ int mi355gp_grid_get_option(mi355gp_grid* g, int option, int* value) {
 // Collective log of logical rank `rank` of this process (loopback: any rank of the grid; one rank per process: its own, rank is
 // ignored) for the LAST evaluation: out9 = [count world, row, column, then per communicator the hash as (high 32 bits, low 32 bits)].
 int mi355gp_grid_coll_log(mi355gp_grid* g, int rank, double* out9) {
-    ARGCHK(g && out9 && !g->single, "mi355gp_grid_coll_log: not available on the degenerate 1 x 1 grid");
+    ARG_CHECK(g && out9 && !g->single, "mi355gp_grid_coll_log: not available on the degenerate 1 x 1 grid");
     const GridRank* r = &g->ranks[0];
     if (g->loopback) {
-        ARGCHK(rank >= 0 && rank < (int)g->ranks.size(), "mi355gp_grid_coll_log: bad rank");
+        ARG_CHECK(rank >= 0 && rank < (int)g->ranks.size(), "mi355gp_grid_coll_log: bad rank");
         r = &g->ranks[(size_t)rank];
     }
     for (int c = 0; c < 3; ++c) {
@@ -1678,8 +1671,8 @@ int mi355gp_grid_coll_log(mi355gp_grid* g, int rank, double* out9) {
 // which: MI355GP_FETCH_L (lower tiles of L), MI355GP_FETCH_KINV is not available after the gradient pass consumed W;
 // 100 = X = L^-1 (lower).
 int mi355gp_grid_fetch(mi355gp_grid* g, int which, double* out) {
-    ARGCHK(g && out && g->n > 0 && g->have_result, "mi355gp_grid_fetch: run an inference call first");
-    ARGCHK(which == MI355GP_FETCH_L || which == 100, "mi355gp_grid_fetch: L (0) or L^-1 (100)");
+    ARG_CHECK(g && out && g->n > 0 && g->have_result, "mi355gp_grid_fetch: run an inference call first");
+    ARG_CHECK(which == MI355GP_FETCH_L || which == 100, "mi355gp_grid_fetch: L (0) or L^-1 (100)");
     if (g->single) return mi355gp_fetch(g->single, which, out, 0);
     HIP_CHECK(hipSetDevice(g->device));
     const long nb = g->nb, n = g->n;
@@ -1712,7 +1705,7 @@ int mi355gp_grid_fetch(mi355gp_grid* g, int which, double* out) {
 //   v = 2: the same with ONE panel store for both operands
 //   v = 3: k_grid_gemm_multi reading the row-major matrix (panel k = rows k*nb ..)
 int mi355gp_dbg_grid_multi(int device, int T, int nb, int reps, double* out_ms) {
-    ARGCHK(T >= 1 && nb >= NB && nb % NB == 0 && reps >= 1 && out_ms, "mi355gp_dbg_grid_multi: bad arguments");
+    ARG_CHECK(T >= 1 && nb >= NB && nb % NB == 0 && reps >= 1 && out_ms, "mi355gp_dbg_grid_multi: bad arguments");
     HIP_CHECK(hipSetDevice(device));
     const long N = (long)T * nb;
     const size_t tile = (size_t)nb * nb;

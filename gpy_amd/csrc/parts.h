@@ -2,6 +2,7 @@
 // an entry point takes, theta validation, active dimensions, input scaling, term grouping, Kdiag of a sum of products and
 // the post-scaling of the reduction records into gradients in theta order.  Host code only.
 #pragma once
+#include <algorithm>
 #include <cmath>
 #include <vector>
 
@@ -9,6 +10,7 @@
 #include "internal.h"
 
 #define GP_STRIDE 34           // doubles of one reduction record: [0] variance sum, [1] lengthscale sum, [2 + q % 32] per dimension
+#define COREG_REC 256          // doubles of one Coregionalize part's S (P x P, P <= 16)
 
 // the sums of dimension q in the records of one part (one GP_STRIDE record per group of 32 dimensions)
 static inline double rec_at(const double* rec, int q) { return rec[(q / 32) * GP_STRIDE + 2 + (q % 32)]; }
@@ -70,6 +72,23 @@ struct PartSpec {
     bool is_static() const { return kind_in(kp.kind, KS_STATIC); }
     bool ext() const { return kind_in(kp.kind, KS_EXT); }
     bool coreg() const { return kp.kind == MI355GP_COREGIONALIZE; }
+};
+
+// A part with its parameters on the device as well: inv_ls (D) and pw, uploaded together once per call by upload() (kp.pw ->
+// dPw).  Any point set is then scaled for the part with one launch_scale_inputs.  Owners: the exact context, the sparse
+// context and the stateless entry points.
+struct DevicePart : PartSpec {
+    DevBuf dIl, dPw;
+    int upload(hipStream_t st) {
+        if (!dIl) HIP_CHECK(dIl.alloc(inv_ls.size()));
+        HIP_CHECK(hipMemcpyAsync(dIl, inv_ls.data(), sizeof(double) * inv_ls.size(), hipMemcpyHostToDevice, st));
+        if (!pw.empty()) {
+            if (!dPw) HIP_CHECK(dPw.alloc(std::max(2 * inv_ls.size(), (size_t)COREG_REC)));   // (B of a Coregionalize part)
+            HIP_CHECK(hipMemcpyAsync(dPw, pw.data(), sizeof(double) * pw.size(), hipMemcpyHostToDevice, st));
+            kp.pw = dPw;
+        }
+        return 0;
+    }
 };
 
 // The one validator of a kernel part over D input columns (n_active = 0: all of them).  `accepted`: the kinds the entry point
@@ -266,4 +285,72 @@ static bool emit_other_factors(const Terms& terms, int tix, size_t p, double* ds
         first = false;
     }
     return true;
+}
+
+// ---- point sets and cross-covariances ---------------------------------------------------------------------------------
+// n host points (row-major n x D) uploaded once; points(part) scales them for that part into the ONE dimension-major buffer t
+// (D x ld), overwriting the previous part's scaling.
+struct PointSet {
+    DevBuf raw, t;
+    long n = 0, ld = 0;
+    int D = 0;
+    int load(hipStream_t st, const double* X, long rows, int dims) {
+        n = rows;
+        D = dims;
+        ld = round_up(rows, 64);
+        HIP_CHECK(raw.alloc(n * D));
+        HIP_CHECK(t.alloc(D * ld));
+        HIP_CHECK(hipMemcpyAsync(raw, X, sizeof(double) * n * D, hipMemcpyHostToDevice, st));
+        return 0;
+    }
+    template <class Part>
+    const double* points(hipStream_t st, const Part& p) const {
+        launch_scale_inputs(st, raw, n, D, p.dIl, /*per-dimension vector*/ 1, t, ld);
+        return t;
+    }
+};
+// the resident, already scaled copy that every part keeps of a point set (member xt: D x ld, n points)
+template <class Part>
+struct Resident {
+    DevBuf Part::*xt;
+    long ld, n;
+    const double* points(hipStream_t, const Part& p) const { return p.*xt; }
+};
+
+// out (+)= K_expr(A, B) (out: ld ldo), one launch_kbuild_cross per factor through emit_expression.  A side is a Resident or a
+// PointSet; a point set is scaled for every factor, once if both sides are the same set.  Returns false if nothing was emitted.
+template <class Parts, class SideA, class SideB, class Skip>
+static bool emit_cross(hipStream_t st, const Parts& parts, const Terms& terms, const SideA& a, const SideB& b, double* out,
+                       long ldo, double* scratch, bool out_holds_data, int diag_same, Skip skip) {
+    const bool same = (const void*)&a == (const void*)&b;
+    return emit_expression(terms, out, scratch, out_holds_data, skip, [&](int p, double* dst, const double* mul, int acc, bool) {
+        const auto& pt = parts[(size_t)p];
+        const double* xa = a.points(st, pt);
+        const double* xb = same ? xa : b.points(st, pt);
+        launch_kbuild_cross(st, pt.kp, xa, a.ld, a.n, xb, b.ld, b.n, dst, ldo, acc, diag_same, mul);
+    });
+}
+template <class Parts, class SideA, class SideB>
+static bool emit_cross(hipStream_t st, const Parts& parts, const Terms& terms, const SideA& a, const SideB& b, double* out,
+                       long ldo, double* scratch, bool out_holds_data, int diag_same) {
+    return emit_cross(st, parts, terms, a, b, out, ldo, scratch, out_holds_data, diag_same,
+                      [](const std::vector<int>&) { return false; });
+}
+
+// ---- dK/dX of one part from its device reductions (gradients_X, predictive_gradients) ----------------------------------
+// stationary (stationary.py:330-358): HX = H^T [x2~ | 1] (rows x (D + 1)), x the unscaled host points (rows x D):
+//   put(i, q, (x_iq il_q HX[i][D] - HX[i][q]) il_q)
+template <class Put>
+static void gradx_stationary(const double* x, long rows, int D, const std::vector<double>& il, const double* HX, Put put) {
+    for (long i = 0; i < rows; ++i)
+        for (int q = 0; q < D; ++q)
+            put(i, q, (x[i * D + q] * il[(size_t)q] * HX[i * (D + 1) + D] - HX[i * (D + 1) + q]) * il[(size_t)q]);
+}
+// StdPeriodic (standard_periodic.py:574-580): HX = the row reduction of launch_periodic_gradx (rows x D):
+//   put(i, q, -pi / (2 T_q l_q^2) HX[i][q])
+template <class Put>
+static void gradx_periodic(const std::vector<double>& pw, long rows, int D, const double* HX, Put put) {
+    for (long i = 0; i < rows; ++i)
+        for (int q = 0; q < D; ++q)
+            put(i, q, -0.5 * pw[(size_t)q] * pw[(size_t)(D + q)] * pw[(size_t)(D + q)] * HX[i * D + q]);
 }

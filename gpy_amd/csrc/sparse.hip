@@ -23,13 +23,6 @@
 
 #define SPLITK_MAX 16
 #define CHUNK_MAX 262144                    // rows per chunk: 2 x (chunk x Mp) doubles of HBM (8.6 GB at M = 2048)
-#define ARGCHK(cond, msg)                 \
-    do {                                  \
-        if (!(cond)) {                    \
-            mi355gp_set_error("%s", msg); \
-            return -1;                    \
-        }                                 \
-    } while (0)
 
 // ---- elementwise M x M helpers (mp x mp row-major, ld = mp) --------------------------------------------------
 // mirror the lower triangle onto the upper one; optionally sum `nsplit` partial matrices first
@@ -194,8 +187,8 @@ static int loop_allreduce(LoopGroup* G, int rank, double* buf, size_t count, hip
     return 0;
 }
 
-struct SPart : PartSpec {
-    double *XtZ = nullptr, *XtC = nullptr, *HX = nullptr, *HZ = nullptr, *gradNM = nullptr, *gradMM = nullptr;
+struct SPart : DevicePart {
+    DevBuf XtZ, XtC, HX, HZ, gradNM, gradMM;
 };
 
 struct mi355gp_sparse {
@@ -222,7 +215,7 @@ struct mi355gp_sparse {
            *T = nullptr;
     // M-dependent
     long m = 0, mp = 0;
-    double *dZ = nullptr, *invls = nullptr, *zero1 = nullptr;
+    double *dZ = nullptr, *zero1 = nullptr;
     double *Lm = nullptr, *Xm = nullptr, *Tm = nullptr, *psi2part = nullptr, *psi2 = nullptr, *Amat = nullptr,
            *LB = nullptr, *XB = nullptr, *Bi = nullptr, *P = nullptr, *E = nullptr, *T1 = nullptr, *Q2 = nullptr,
            *dLdKmm = nullptr, *Winv = nullptr;
@@ -246,20 +239,9 @@ static int sparse_allreduce(mi355gp_sparse* s, double* buf, size_t count) {
 }
 static bool sharded(const mi355gp_sparse* s) { return s->comm != nullptr || s->loop != nullptr; }
 
-static void free_parts(mi355gp_sparse* s) {
-    for (SPart& p : s->parts) {
-        double** ptrs[] = {&p.XtZ, &p.XtC, &p.HX, &p.HZ, &p.gradNM, &p.gradMM};
-        for (auto q : ptrs) {
-            if (*q) (void)hipFree(*q);
-            *q = nullptr;
-        }
-    }
-    s->parts.clear();
-}
-
 static void free_m(mi355gp_sparse* s) {
-    free_parts(s);
-    double** ptrs[] = {&s->dZ, &s->invls, &s->zero1, &s->Lm, &s->Xm, &s->Tm, &s->psi2part, &s->psi2, &s->Amat,
+    s->parts.clear();
+    double** ptrs[] = {&s->dZ, &s->zero1, &s->Lm, &s->Xm, &s->Tm, &s->psi2part, &s->psi2, &s->Amat,
                        &s->LB, &s->XB, &s->Bi, &s->P, &s->E, &s->T1, &s->Q2, &s->dLdKmm, &s->Winv, &s->psi1Y, &s->vecA,
                        &s->vecB, &s->cvec, &s->wvec, &s->vvec, &s->trmvPart, &s->colPart, &s->gradPart,
                        &s->gradChunk, &s->scal, &s->redbuf, &s->Kfu, &s->T};
@@ -298,7 +280,6 @@ static int alloc_m(mi355gp_sparse* s, long M) {
     const size_t mm = sizeof(double) * mp * mp;
     const int groups = (int)((D + 31) / 32);
     HIP_CHECK(hipMalloc(&s->dZ, sizeof(double) * M * D));
-    HIP_CHECK(hipMalloc(&s->invls, sizeof(double) * D));
     HIP_CHECK(hipMalloc(&s->zero1, sizeof(double) * 8));
     HIP_CHECK(hipMemset(s->zero1, 0, sizeof(double) * 8));
     double** mats[] = {&s->Lm, &s->Xm, &s->Tm, &s->psi2, &s->Amat, &s->LB, &s->XB, &s->Bi, &s->P, &s->E, &s->T1, &s->Q2,
@@ -323,31 +304,34 @@ static int alloc_m(mi355gp_sparse* s, long M) {
 
 // (re)builds the part list of a call; the device buffers of a part are kept while the number of parts is unchanged
 static int prepare_sparse_parts(mi355gp_sparse* s, int nparts, const mi355gp_part* parts) {
-    ARGCHK(nparts >= 1 && nparts <= 16 && parts, "between 1 and 16 kernel parts");
+    ARG_CHECK(nparts >= 1 && nparts <= 16 && parts, "between 1 and 16 kernel parts");
     const long mp = s->mp, D = s->D;
     const int groups = (int)((D + 31) / 32);
     if ((int)s->parts.size() != nparts) {
-        free_parts(s);
+        s->parts.clear();
         s->parts.resize((size_t)nparts);
         if (s->redbuf) (void)hipFree(s->redbuf);
         s->redbuf = nullptr;
         HIP_CHECK(hipMalloc(&s->redbuf, sizeof(double) * nparts * ((size_t)groups * GP_STRIDE + (size_t)mp * (D + 1))));
         for (SPart& p : s->parts) {
-            HIP_CHECK(hipMalloc(&p.XtZ, sizeof(double) * D * mp));
-            HIP_CHECK(hipMalloc(&p.XtC, sizeof(double) * D * s->chunk));
-            HIP_CHECK(hipMalloc(&p.HX, sizeof(double) * mp * (D + 1)));
-            HIP_CHECK(hipMalloc(&p.HZ, sizeof(double) * mp * (D + 1)));
-            HIP_CHECK(hipMalloc(&p.gradNM, sizeof(double) * groups * GP_STRIDE));
-            HIP_CHECK(hipMalloc(&p.gradMM, sizeof(double) * groups * GP_STRIDE));
+            HIP_CHECK(p.XtZ.alloc(D * mp));
+            HIP_CHECK(p.XtC.alloc(D * s->chunk));
+            HIP_CHECK(p.HX.alloc(mp * (D + 1)));
+            HIP_CHECK(p.HZ.alloc(mp * (D + 1)));
+            HIP_CHECK(p.gradNM.alloc(groups * GP_STRIDE));
+            HIP_CHECK(p.gradMM.alloc(groups * GP_STRIDE));
         }
     }
-    for (int i = 0; i < nparts; ++i)
-        if (int rc = parse_part(parts[i], (int)D, KS_STATIONARY | KS_STATIC, "sparse path", &s->parts[(size_t)i])) return rc;
+    for (int i = 0; i < nparts; ++i) {
+        SPart& p = s->parts[(size_t)i];
+        if (int rc = parse_part(parts[i], (int)D, KS_STATIONARY | KS_STATIC, "sparse path", &p)) return rc;
+        if (int rc = p.upload(s->st)) return rc;
+    }
     s->terms = group_terms(s->parts);
     for (const auto& t : s->terms)
         if (t.size() > 1)
             for (int f : t)
-                ARGCHK(s->parts[(size_t)f].kp.kind != MI355GP_WHITE, "a White factor inside a product is not supported by the sparse path");
+                ARG_CHECK(s->parts[(size_t)f].kp.kind != MI355GP_WHITE, "a White factor inside a product is not supported by the sparse path");
     return 0;
 }
 
@@ -364,22 +348,17 @@ static bool skip_white(const mi355gp_sparse* s, const std::vector<int>& t) {
 }
 
 // scaled, dimension-major copies of `rows` points (row-major src) for every part
-static int scale_for_parts(mi355gp_sparse* s, const double* src, long rows, long ldt, bool inducing) {
-    for (SPart& p : s->parts) {
-        HIP_CHECK(hipMemcpyAsync(s->invls, p.inv_ls.data(), sizeof(double) * s->D, hipMemcpyHostToDevice, s->st));
-        launch_scale_inputs(s->st, src, rows, s->D, s->invls, 1, inducing ? p.XtZ : p.XtC, ldt);
-    }
-    return 0;
+static void scale_for_parts(mi355gp_sparse* s, const double* src, long rows, long ldt, bool inducing) {
+    for (SPart& p : s->parts) launch_scale_inputs(s->st, src, rows, s->D, p.dIl, 1, inducing ? p.XtZ : p.XtC, ldt);
 }
+// the inducing inputs as one side of a cross-covariance (emit_cross)
+static Resident<SPart> inducing_points(const mi355gp_sparse* s) { return {&SPart::XtZ, s->mp, s->m}; }
 
 // Kfu chunk = sum over summands of (the product of) K_p(X_chunk, Z)  (add.py:58-72, prod.py:58-65; White contributes nothing
 // off the diagonal, static.py:77-81).  Products are multiplied up in `scratch` (chunk x mp, e.g. the T buffer).
 static void build_cross_chunk(mi355gp_sparse* s, long rc, double* out, double* scratch) {
-    auto skip = [&](const std::vector<int>& t) { return skip_white(s, t); };
-    const bool any = emit_expression(s->terms, out, scratch, false, skip, [&](int p, double* dst, const double* mul, int acc, bool) {
-        const SPart& pt = s->parts[(size_t)p];
-        launch_kbuild_cross(s->st, pt.kp, pt.XtC, s->chunk, rc, pt.XtZ, s->mp, s->m, dst, s->mp, acc, 0, mul);
-    });
+    const bool any = emit_cross(s->st, s->parts, s->terms, Resident<SPart>{&SPart::XtC, s->chunk, rc}, inducing_points(s), out, s->mp,
+                                scratch, false, 0, [&](const std::vector<int>& t) { return skip_white(s, t); });
     if (!any) (void)hipMemsetAsync(out, 0, sizeof(double) * rc * s->mp, s->st);       // only White parts: K(X, Z) = 0
 }
 // K(Z) (lower tiles; diag != NULL: + diag on the diagonal) of the expression into out (mp x mp), scratch mp x mp
@@ -442,7 +421,7 @@ int mi355gp_sparse_create(int device, mi355gp_sparse** out) {
 }
 
 int mi355gp_sparse_get_profile(mi355gp_sparse* s, double* out6) {
-    ARGCHK(s && out6, "mi355gp_sparse_get_profile: NULL argument");
+    ARG_CHECK(s && out6, "mi355gp_sparse_get_profile: NULL argument");
     HIP_CHECK(hipSetDevice(s->device));
     HIP_CHECK(hipStreamSynchronize(s->st));
     double ms[PF_NUM], fl[PF_NUM];
@@ -483,7 +462,7 @@ int mi355gp_sparse_destroy(mi355gp_sparse* s) {
 }
 
 int mi355gp_sparse_set_data(mi355gp_sparse* s, const double* X, int64_t N, int D, const double* Y, int Dy) {
-    ARGCHK(s && X && Y && N > 0 && D > 0 && Dy > 0, "mi355gp_sparse_set_data: bad arguments");
+    ARG_CHECK(s && X && Y && N > 0 && D > 0 && Dy > 0, "mi355gp_sparse_set_data: bad arguments");
     HIP_CHECK(hipSetDevice(s->device));
     EngineShared gate(s->device);
     HIP_CHECK(hipStreamSynchronize(s->st));
@@ -533,7 +512,7 @@ int mi355gp_sparse_set_data(mi355gp_sparse* s, const double* X, int64_t N, int D
 // Row-sharded mode: call once, before set_data, on every rank (id128 from mi355gp_grid_unique_id on rank 0).
 // Each rank then passes ITS rows to mi355gp_sparse_set_data; Z and theta are replicated; results are identical on all ranks.
 int mi355gp_sparse_attach_comm(mi355gp_sparse* s, int rank, int world, const void* id128) {
-    ARGCHK(s && id128 && world >= 1 && rank >= 0 && rank < world, "mi355gp_sparse_attach_comm: bad arguments");
+    ARG_CHECK(s && id128 && world >= 1 && rank >= 0 && rank < world, "mi355gp_sparse_attach_comm: bad arguments");
     HIP_CHECK(hipSetDevice(s->device));
     EngineShared gate(s->device);
     if (s->comm) rccl_comm_destroy(s->comm);
@@ -548,7 +527,7 @@ int mi355gp_sparse_attach_comm(mi355gp_sparse* s, int rank, int world, const voi
 // The same mode over the LOOPBACK transport: `world` contexts of this process (one host thread each, any devices... the
 // 1-GPU box: all on one) that name the same group_key meet at a process-local rendezvous for every exchange step.
 int mi355gp_sparse_attach_loopback(mi355gp_sparse* s, int rank, int world, int group_key) {
-    ARGCHK(s && world >= 1 && rank >= 0 && rank < world, "mi355gp_sparse_attach_loopback: bad arguments");
+    ARG_CHECK(s && world >= 1 && rank >= 0 && rank < world, "mi355gp_sparse_attach_loopback: bad arguments");
     std::lock_guard<std::mutex> lk(g_loop_mu);
     LoopGroup*& G = g_loop_groups[group_key];
     if (!G) {
@@ -556,7 +535,7 @@ int mi355gp_sparse_attach_loopback(mi355gp_sparse* s, int rank, int world, int g
         G->world = world;
         G->bufs.assign((size_t)world, nullptr);
     }
-    ARGCHK(G->world == world, "mi355gp_sparse_attach_loopback: the group exists with a different world size");
+    ARG_CHECK(G->world == world, "mi355gp_sparse_attach_loopback: the group exists with a different world size");
     if (s->comm) rccl_comm_destroy(s->comm);
     s->comm = nullptr;
     s->loop = G;
@@ -621,11 +600,11 @@ int mi355gp_vardtc_inference_sum(mi355gp_sparse* s, int nparts, const mi355gp_pa
                                  const double* noise, int64_t noise_len, double extra_jitter, double* out_scalars,
                                  double* dtheta_out, double* dZ_out, double* wv_out, double* dnoise_rows_out,
                                  double* dLdm_out, double* stage_ms) {
-    ARGCHK(s && s->n > 0, "mi355gp_vardtc_inference: set_data first");
-    ARGCHK(parts && Z && M > 0 && out_scalars && noise, "mi355gp_vardtc_inference: bad arguments");
-    ARGCHK(noise_len == 1 || noise_len == s->n, "noise must have 1 or N entries");
+    ARG_CHECK(s && s->n > 0, "mi355gp_vardtc_inference: set_data first");
+    ARG_CHECK(parts && Z && M > 0 && out_scalars && noise, "mi355gp_vardtc_inference: bad arguments");
+    ARG_CHECK(noise_len == 1 || noise_len == s->n, "noise must have 1 or N entries");
     const bool het = noise_len > 1;
-    ARGCHK(!het || dnoise_rows_out, "per-point noise: dnoise_rows_out (N x Dy) is required");
+    ARG_CHECK(!het || dnoise_rows_out, "per-point noise: dnoise_rows_out (N x Dy) is required");
     HIP_CHECK(hipSetDevice(s->device));
     EngineShared gate(s->device);
     const int D = s->D, Dy = s->Dy;
@@ -669,7 +648,7 @@ int mi355gp_vardtc_inference_sum(mi355gp_sparse* s, int nparts, const mi355gp_pa
         const long cnt = n * Dy;
         hipLaunchKernelGGL(k_scale_rows, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, st, s->dY, s->dBeta, cnt, Dy, s->dV);
     }
-    if (int rc = scale_for_parts(s, s->dZ, m, mp, true)) return rc;
+    scale_for_parts(s, s->dZ, m, mp, true);
     // Kmm + 1e-8 I (var_dtc.py:93-94) = sum of the parts' K(Z) (White on the diagonal), Lm = chol (jitchol, :95), Xm = Lm^-1.
     // They need only Z: when the factorisation is the single persistent launch (a latency-bound chain on an otherwise idle
     // GPU), the three go to a side stream and pass 1 is enqueued underneath; the launch is first in line, so its workgroups are
@@ -705,7 +684,7 @@ int mi355gp_vardtc_inference_sum(mi355gp_sparse* s, int nparts, const mi355gp_pa
     int nch = 0;
     for (long r0 = 0; r0 < n; r0 += chunk, ++nch) {
         const long rc = (n - r0 < chunk) ? (n - r0) : chunk;
-        if (int e = scale_for_parts(s, s->dX + r0 * D, rc, chunk, false)) return e;
+        scale_for_parts(s, s->dX + r0 * D, rc, chunk, false);
         // the cross-covariance kernel writes rows < rc, columns < m: zero only what it leaves out
         if (m < mp) {
             if (rc < chunk || nch == 0) HIP_CHECK(hipMemsetAsync(s->Kfu, 0, sizeof(double) * chunk * mp, st));
@@ -797,7 +776,7 @@ int mi355gp_vardtc_inference_sum(mi355gp_sparse* s, int nparts, const mi355gp_pa
         const long rc = (n - r0 < chunk) ? (n - r0) : chunk;
         const long rcp = round_up(rc, NB);
         if (!one_chunk) {                                    // a single chunk is still resident from pass 1
-            if (int e = scale_for_parts(s, s->dX + r0 * D, rc, chunk, false)) return e;
+            scale_for_parts(s, s->dX + r0 * D, rc, chunk, false);
             if (rc < chunk) HIP_CHECK(hipMemsetAsync(s->Kfu + rc * mp, 0, sizeof(double) * (chunk - rc) * mp, st));
             build_cross_chunk(s, rc, s->Kfu, s->T);
         }
@@ -1027,7 +1006,7 @@ int mi355gp_vardtc_inference(mi355gp_sparse* s, int kind, int ard, const double*
                              double noise_var, double extra_jitter, double* out_scalars, double* dtheta_out,
                              double* dZ_out, double* wv_out, double* stage_ms) {
     if (int rc = check_kind(kind, KS_STATIONARY, "mi355gp_vardtc_inference")) return rc;
-    ARGCHK(theta, "mi355gp_vardtc_inference: theta is NULL");
+    ARG_CHECK(theta, "mi355gp_vardtc_inference: theta is NULL");
     const mi355gp_part part{kind, ard, 0, nullptr, theta, 0};
     return mi355gp_vardtc_inference_sum(s, 1, &part, Z, M, &noise_var, 1, extra_jitter, out_scalars, dtheta_out, dZ_out, wv_out,
                                         nullptr, nullptr, stage_ms);
@@ -1049,7 +1028,7 @@ static int ensure_winv(mi355gp_sparse* s) {
 // M x M results of the last call: 0 = dL_dKmm, 1 = woodbury_inv = Lm^-T (I - B^-1) Lm^-1 (var_dtc.py:206-210),
 // 2 = Lm (lower, strict upper zero), 3 = Kmm (with the 1e-8 jitter), 4 = psi2 (heteroscedastic: sum_n beta_n k_n k_n^T)
 int mi355gp_sparse_fetch(mi355gp_sparse* s, int which, double* out) {
-    ARGCHK(s && out && s->have_result, "mi355gp_sparse_fetch: run mi355gp_vardtc_inference first");
+    ARG_CHECK(s && out && s->have_result, "mi355gp_sparse_fetch: run mi355gp_vardtc_inference first");
     HIP_CHECK(hipSetDevice(s->device));
     EngineShared gate(s->device);
     hipStream_t st = s->st;
@@ -1080,13 +1059,13 @@ int mi355gp_sparse_fetch(mi355gp_sparse* s, int which, double* out) {
 // what SparseGP._update_gradients hands to a FOREIGN kernel's update_gradients_full / gradients_X (sparse_gp.py:108-118).
 // The N x M matrix is never resident: the caller walks it in row blocks (nrows <= the context's chunk size).
 int mi355gp_sparse_fetch_dLdKnm(mi355gp_sparse* s, int64_t row0, int64_t nrows, double* out) {
-    ARGCHK(s && out && s->have_result, "mi355gp_sparse_fetch_dLdKnm: run mi355gp_vardtc_inference first");
-    ARGCHK(row0 >= 0 && nrows > 0 && row0 + nrows <= s->n && nrows <= s->chunk, "mi355gp_sparse_fetch_dLdKnm: bad row range");
+    ARG_CHECK(s && out && s->have_result, "mi355gp_sparse_fetch_dLdKnm: run mi355gp_vardtc_inference first");
+    ARG_CHECK(row0 >= 0 && nrows > 0 && row0 + nrows <= s->n && nrows <= s->chunk, "mi355gp_sparse_fetch_dLdKnm: bad row range");
     HIP_CHECK(hipSetDevice(s->device));
     EngineShared gate(s->device);
     hipStream_t st = s->st;
     const long m = s->m, mp = s->mp, rc = nrows, rcp = round_up(rc, NB);
-    if (int e = scale_for_parts(s, s->dX + row0 * s->D, rc, s->chunk, false)) return e;
+    scale_for_parts(s, s->dX + row0 * s->D, rc, s->chunk, false);
     HIP_CHECK(hipMemsetAsync(s->Kfu, 0, sizeof(double) * rcp * mp, st));
     build_cross_chunk(s, rc, s->Kfu, s->T);
     launch_gemm(st, 0, 1, rcp, mp, mp, s->Kfu, mp, s->Q2, mp, s->T, mp, 1.0, 0.0);
@@ -1104,63 +1083,35 @@ int mi355gp_sparse_fetch_dLdKnm(mi355gp_sparse* s, int64_t row0, int64_t nrows, 
 // K(X*, X*) - Kx^T Winv Kx.  The kernel (parts) must be the one of the last inference call.
 int mi355gp_sparse_predict(mi355gp_sparse* s, int nparts, const mi355gp_part* parts, const double* Xnew, int64_t Mn,
                            double* mu_out, double* var_out, int full_cov) {
-    ARGCHK(s && s->have_result, "mi355gp_sparse_predict: run mi355gp_vardtc_inference first");
-    ARGCHK(Xnew && Mn > 0 && mu_out, "mi355gp_sparse_predict: bad arguments");
+    ARG_CHECK(s && s->have_result, "mi355gp_sparse_predict: run mi355gp_vardtc_inference first");
+    ARG_CHECK(Xnew && Mn > 0 && mu_out, "mi355gp_sparse_predict: bad arguments");
     HIP_CHECK(hipSetDevice(s->device));
     EngineShared gate(s->device);
     if (int rc = prepare_sparse_parts(s, nparts, parts)) return rc;
     hipStream_t st = s->st;
-    const long m = s->m, mp = s->mp, D = s->D, Dy = s->Dy, mnp = round_up(Mn, NB), ldn = round_up(Mn, 64);
-    if (int rc = scale_for_parts(s, s->dZ, m, mp, true)) return rc;
+    const long m = s->m, mp = s->mp, Dy = s->Dy, mnp = round_up(Mn, NB);
+    scale_for_parts(s, s->dZ, m, mp, true);
     if (int rc = ensure_winv(s)) return rc;
-    double *dXn = nullptr, *dXt = nullptr, *Kx = nullptr, *Tmp = nullptr, *dMu = nullptr, *dVar = nullptr;
-    auto cleanup = [&]() {
-        double* ptrs[] = {dXn, dXt, Kx, Tmp, dMu, dVar};
-        for (double* p : ptrs)
-            if (p) (void)hipFree(p);
-    };
-    hipError_t e = hipMalloc(&dXn, sizeof(double) * Mn * D);
-    if (e == hipSuccess) e = hipMalloc(&dXt, sizeof(double) * D * ldn);
-    if (e == hipSuccess) e = hipMalloc(&Kx, sizeof(double) * mp * mnp);
-    if (e == hipSuccess) e = hipMalloc(&Tmp, sizeof(double) * mp * mnp);
-    if (e == hipSuccess) e = hipMalloc(&dMu, sizeof(double) * Mn * Dy);
-    if (e == hipSuccess) e = hipMalloc(&dVar, sizeof(double) * (full_cov ? mnp * mnp : Mn));
-    if (e != hipSuccess) {
-        cleanup();
-        mi355gp_set_error("mi355gp_sparse_predict: %s", hipGetErrorString(e));
-        return -(1000 + (int)e);
-    }
-    (void)hipMemcpyAsync(dXn, Xnew, sizeof(double) * Mn * D, hipMemcpyHostToDevice, st);
-    (void)hipMemsetAsync(Kx, 0, sizeof(double) * mp * mnp, st);
-    if (full_cov && var_out) (void)hipMemsetAsync(dVar, 0, sizeof(double) * mnp * mnp, st);
+    PointSet xs;
+    DevBuf Kx, Tmp, dMu, dVar, scr;
+    if (int rc = xs.load(st, Xnew, Mn, s->D)) return rc;
+    HIP_CHECK(Kx.alloc(mp * mnp));
+    HIP_CHECK(Tmp.alloc(mp * mnp));
+    HIP_CHECK(dMu.alloc(Mn * Dy));
+    HIP_CHECK(dVar.alloc(full_cov ? mnp * mnp : Mn));
+    HIP_CHECK(hipMemsetAsync(Kx, 0, sizeof(double) * mp * mnp, st));
+    if (full_cov && var_out) HIP_CHECK(hipMemsetAsync(dVar, 0, sizeof(double) * mnp * mnp, st));
     const double kdiag = expression_kdiag(s->parts, s->terms);
     // K(Z, X*) and (full_cov) K(X*, X*) of the expression: every factor is evaluated with ITS scaling of the new inputs;
     // products are multiplied up in Tmp / a second M* x M* scratch
-    auto scale_new = [&](const SPart& p) {
-        (void)hipMemcpyAsync(s->invls, p.inv_ls.data(), sizeof(double) * D, hipMemcpyHostToDevice, st);
-        launch_scale_inputs(st, dXn, Mn, (int)D, s->invls, 1, dXt, ldn);
-    };
-    emit_expression(s->terms, Kx, Tmp, false, [&](const std::vector<int>& t) { return skip_white(s, t); }, [&](int pi, double* dst, const double* mul, int acc, bool) {
-        const SPart& p = s->parts[(size_t)pi];
-        scale_new(p);
-        launch_kbuild_cross(st, p.kp, p.XtZ, mp, m, dXt, ldn, Mn, dst, mnp, acc, 0, mul);
-    });
+    emit_cross(st, s->parts, s->terms, inducing_points(s), xs, Kx, mnp, Tmp, false, 0,
+               [&](const std::vector<int>& t) { return skip_white(s, t); });
     if (full_cov && var_out) {
-        double* scr = nullptr;
-        if (has_product(s->terms) && hipMalloc(&scr, sizeof(double) * mnp * mnp) != hipSuccess) {
-            cleanup();
+        if (has_product(s->terms) && scr.alloc(mnp * mnp) != hipSuccess) {
             mi355gp_set_error("mi355gp_sparse_predict: out of memory for the product scratch");
             return -3;
         }
-        emit_expression(s->terms, dVar, scr, false, [&](int pi, double* dst, const double* mul, int acc, bool) {
-            const SPart& p = s->parts[(size_t)pi];
-            scale_new(p);
-            launch_kbuild_cross(st, p.kp, dXt, ldn, Mn, dXt, ldn, Mn, dst, mnp, acc, /*diag_same=*/1, mul);
-        });
-        if (scr) {
-            (void)hipStreamSynchronize(st);
-            (void)hipFree(scr);
-        }
+        emit_cross(st, s->parts, s->terms, xs, xs, dVar, mnp, scr, false, /*diag_same=*/1);
     }
     launch_col_reduce(st, Kx, mnp, m, Mn, s->vvec, (int)Dy, 0.0, 0, dMu);                              // mu = Kx^T v
     if (var_out) {
@@ -1170,19 +1121,16 @@ int mi355gp_sparse_predict(mi355gp_sparse* s, int nparts, const mi355gp_part* pa
         else
             launch_gemm(st, 1, 1, mnp, mnp, mp, Kx, mnp, Tmp, mnp, dVar, mnp, -1.0, 1.0);             // K** - Kx^T Winv Kx
     }
-    hipError_t e2 = hipMemcpyAsync(mu_out, dMu, sizeof(double) * Mn * Dy, hipMemcpyDeviceToHost, st);
-    if (var_out && e2 == hipSuccess) {
-        if (!full_cov) e2 = hipMemcpyAsync(var_out, dVar, sizeof(double) * Mn, hipMemcpyDeviceToHost, st);
-        else e2 = hipMemcpy2DAsync(var_out, sizeof(double) * Mn, dVar, sizeof(double) * mnp, sizeof(double) * Mn, Mn,
-                                   hipMemcpyDeviceToHost, st);
+    HIP_CHECK(hipMemcpyAsync(mu_out, dMu, sizeof(double) * Mn * Dy, hipMemcpyDeviceToHost, st));
+    if (var_out) {
+        if (!full_cov)
+            HIP_CHECK(hipMemcpyAsync(var_out, dVar, sizeof(double) * Mn, hipMemcpyDeviceToHost, st));
+        else
+            HIP_CHECK(hipMemcpy2DAsync(var_out, sizeof(double) * Mn, dVar, sizeof(double) * mnp, sizeof(double) * Mn, Mn,
+                                       hipMemcpyDeviceToHost, st));
     }
-    if (e2 == hipSuccess) e2 = hipStreamSynchronize(st);
-    if (e2 == hipSuccess) e2 = hipGetLastError();
-    cleanup();
-    if (e2 != hipSuccess) {
-        mi355gp_set_error("mi355gp_sparse_predict: %s", hipGetErrorString(e2));
-        return -(1000 + (int)e2);
-    }
+    HIP_CHECK(hipStreamSynchronize(st));
+    HIP_CHECK(hipGetLastError());
     if (var_out && !full_cov)
         for (int64_t i = 0; i < Mn; ++i) var_out[i] = var_out[i] < 1e-15 ? 1e-15 : var_out[i];      // posterior.py:248
     return 0;
