@@ -463,8 +463,15 @@ static int coreg_check_points(const mi355gp_ctx* c, const double* Xn, int64_t M,
             if (int rc = coreg_check_index(Xn + p.kp.col, M, c->D, p.kp.ard, what)) return rc;
     return 0;
 }
-// Kdiag of the expression at each new point when it holds Coregionalize parts (Coregionalize.Kdiag = diag(B)[idx],
-// coregionalize.py:106-107): kd[m] = sum over terms of the product of the factors' B[idx_m][idx_m] or variance
+// a part whose diagonal depends on the point (Coregionalize, Linear): Kdiag of the expression is then no constant
+static bool has_point_diag(const mi355gp_ctx* c) {
+    for (const auto& p : c->parts)
+        if (p.diag_by_point()) return true;
+    return false;
+}
+// Kdiag of the expression at each new point: kd[m] = sum over terms of the product of the factors' diagonals -- B[idx_m][idx_m]
+// of a Coregionalize factor (coregionalize.py:106-107), sum_q variance_q x_mq^2 over the active columns of a Linear factor
+// (linear.py:84-85), the variance of any other
 static std::vector<double> expression_kdiag_points(const mi355gp_ctx* c, const double* Xn, int64_t M) {
     std::vector<double> kd((size_t)M, 0.0);
     for (int64_t m = 0; m < M; ++m) {
@@ -476,6 +483,13 @@ static std::vector<double> expression_kdiag_points(const mi355gp_ctx* c, const d
                 if (p.coreg()) {
                     const int a = (int)Xn[m * c->D + p.kp.col], P = p.kp.ard;
                     v *= p.theta[(size_t)(a * P + a)];
+                } else if (p.linear()) {
+                    double d = 0.0;
+                    for (size_t a = 0; a < p.dims.size(); ++a) {
+                        const double x = Xn[m * c->D + p.dims[a]];
+                        d += p.theta[p.kp.ard ? a : 0] * x * x;
+                    }
+                    v *= d;
                 } else {
                     v *= p.kp.variance;
                 }
@@ -506,7 +520,7 @@ static int prepare_parts(mi355gp_ctx* c, int nparts, const mi355gp_part* parts) 
     }
     for (int i = 0; i < nparts; ++i) {
         mi355gp_ctx::Part& p = c->parts[(size_t)i];
-        if (int rc = parse_part(parts[i], c->D, KS_STATIONARY | KS_STATIC | KS_EXT | KS_COREG, "exact-GP path", &p)) return rc;
+        if (int rc = parse_part(parts[i], c->D, KS_STATIONARY | KS_STATIC | KS_EXT | KS_COREG | KS_LINEAR, "exact-GP path", &p)) return rc;
         if (p.coreg()) {
             const int col = p.kp.col;
             if (c->hIdxCol != col) {                     // the training indices of this column, validated once per upload
@@ -588,7 +602,7 @@ int mi355gp_exact_studentt_sum(mi355gp_ctx* c, int nparts, const mi355gp_part* p
 int mi355gp_exact_inference(mi355gp_ctx* c, int kind, int ard, const double* theta, const double* noise,
                             int64_t noise_len, double jitter, double extra_jitter, double* out_scalars,
                             double* alpha_out, double* dtheta_out, double* diag_dLdK_out, double* stage_ms) {
-    if (int rc = check_kind(kind, KS_STATIONARY | KS_EXT, "mi355gp_exact_inference")) return rc;
+    if (int rc = check_kind(kind, KS_STATIONARY | KS_EXT | KS_LINEAR, "mi355gp_exact_inference")) return rc;
     const mi355gp_part part{kind, ard, 0, nullptr, theta};
     return mi355gp_exact_inference_sum(c, 1, &part, noise, noise_len, jitter, extra_jitter, out_scalars, alpha_out,
                                        dtheta_out, diag_dLdK_out, stage_ms);
@@ -684,7 +698,7 @@ int mi355gp_kern_K(int device, int kind, int ard, const double* theta, const dou
     if (sym) M = N;
     ARG_CHECK(M > 0, "mi355gp_kern_K: M must be positive");
     StatelessPart pt;
-    if (int rc = pt.load(kind, ard, theta, D, KS_STATIONARY | KS_EXT | KS_COREG, "mi355gp_kern_K", X, N, X2, M)) return rc;
+    if (int rc = pt.load(kind, ard, theta, D, KS_STATIONARY | KS_EXT | KS_COREG | KS_LINEAR, "mi355gp_kern_K", X, N, X2, M)) return rc;
     PointSet x1, x2;
     if (int rc = pt.scaled(x1, X, N)) return rc;
     if (!sym)
@@ -699,6 +713,11 @@ int mi355gp_kern_K(int device, int kind, int ard, const double* theta, const dou
 }
 
 int mi355gp_kern_Kdiag(int kind, const double* theta, int64_t N, double* out) {
+    if (kind == MI355GP_LINEAR) {
+        mi355gp_set_error("mi355gp_kern_Kdiag: the diagonal of a Linear (kind 9) part depends on the points (sum_q variance_q "
+                          "x_q^2, linear.py:84-85) and this entry point takes no X");
+        return -1;
+    }
     ARG_CHECK(kind_in(kind, KS_STATIONARY | KS_EXT) && theta && out && N >= 0, "mi355gp_kern_Kdiag: bad arguments");
     // stationary: K(x,x) = variance (stationary.py:170-173); StdPeriodic likewise (standard_periodic.py:105-109)
     for (int64_t i = 0; i < N; ++i) out[i] = theta[0];
@@ -716,7 +735,7 @@ int mi355gp_update_gradients_full(int device, int kind, int ard, const double* t
     if (sym) M = N;
     ARG_CHECK(kind != MI355GP_COREGIONALIZE || M > 0, "mi355gp_update_gradients_full: M must be positive");
     StatelessPart pt;
-    if (int rc = pt.load(kind, ard, theta, D, KS_STATIONARY | KS_EXT | KS_COREG, "mi355gp_update_gradients_full", X, N, X2, M))
+    if (int rc = pt.load(kind, ard, theta, D, KS_STATIONARY | KS_EXT | KS_COREG | KS_LINEAR, "mi355gp_update_gradients_full", X, N, X2, M))
         return rc;
     PointSet x1, x2;
     if (int rc = pt.scaled(x1, X, N)) return rc;
@@ -758,7 +777,7 @@ int mi355gp_gradients_X(int device, int kind, int ard, const double* theta, cons
     ARG_CHECK(dL_dK && X && out && N > 0 && D > 0, "mi355gp_gradients_X: bad arguments");
     HIP_CHECK(hipSetDevice(device));
     StatelessPart pt;
-    if (int rc = pt.load(kind, ard, theta, D, KS_STATIONARY | KS_EXT, "mi355gp_gradients_X", nullptr, 0, nullptr, 0)) return rc;
+    if (int rc = pt.load(kind, ard, theta, D, KS_STATIONARY | KS_EXT | KS_LINEAR, "mi355gp_gradients_X", nullptr, 0, nullptr, 0)) return rc;
     const bool sym = (X2 == nullptr);
     if (sym) { M = N; X2 = X; }
     ARG_CHECK(M > 0, "mi355gp_gradients_X: M must be positive");
@@ -792,6 +811,16 @@ int mi355gp_gradients_X(int device, int kind, int ard, const double* theta, cons
     HIP_CHECK(dCol.alloc(64 * N * (D + 1)));
     HIP_CHECK(dHX.alloc(N * (D + 1)));
     HIP_CHECK(hipMemcpy(dG, Gt.data(), sizeof(double) * M * N, hipMemcpyHostToDevice));
+    if (pt.linear()) {
+        // Linear.gradients_X (linear.py:108-114): out[i][q] = variance_q sum_j W_ij x2_jq -- the weights are dL_dK itself
+        const int ns = launch_colreduce_multi(0, dG, N, M, N, xr.t, 1, xr.ld, D, 0, dCol);
+        launch_sum_splits(0, dCol, N * D, ns, 0, dHX);
+        std::vector<double> HX((size_t)N * D);
+        HIP_CHECK(hipMemcpy(HX.data(), dHX, sizeof(double) * HX.size(), hipMemcpyDeviceToHost));
+        HIP_CHECK(hipGetLastError());
+        gradx_linear(pt.inv_ls, N, D, HX.data(), [&](long i, int q, double g) { out[i * D + q] = g; });
+        return 0;
+    }
     launch_grad_generic(0, pt.kp, xr.t, xr.ld, M, xc.t, xc.ld, N, 0, dG, N, dPart, GP_STRIDE, dG, N);   // H in place
     const int ns = launch_colreduce_multi(0, dG, N, M, N, xr.t, 1, xr.ld, D, 1, dCol);
     launch_sum_splits(0, dCol, N * (D + 1), ns, 0, dHX);
@@ -923,8 +952,8 @@ int mi355gp_predict_sum(mi355gp_ctx* c, int nparts, const mi355gp_part* parts, c
     HIP_CHECK(hipMemsetAsync(dKx, 0, sizeof(double) * np * mp, st));
     if (full_cov && var_out) HIP_CHECK(hipMemsetAsync(dVar, 0, sizeof(double) * mp * mp, st));
     const double kdiag = expression_kdiag(c->parts, c->terms);                   // Kdiag(X*): sum over terms of the product of variances
-    DevBuf dKd;                                                 // ... or per point, with Coregionalize parts
-    const bool kd_points = has_coreg(c) && !full_cov && var_out;
+    DevBuf dKd;                                                 // ... or per point, with Coregionalize / Linear parts
+    const bool kd_points = has_point_diag(c) && !full_cov && var_out;
     std::vector<double> kd;
     if (kd_points) {
         kd = expression_kdiag_points(c, Xnew, M);
@@ -969,7 +998,7 @@ __global__ void k_fill_rows(double* __restrict__ G, long ld, long n, long m, con
 
 // GP.predictive_gradients (core/gp.py:418-474) for a sum of stationary (+ White / Bias) parts, everything N-sized on device:
 //   dmu[m][q][d]  = sum_n alpha[n][d] dK(x*_m, x_n)/dx*_mq                         (kern.gradients_X(alpha_d^T, X*, X), :448-451)
-//   dvar[m][q]    = dKdiag/dx* (= 0, stationary.py:360-361) - 2 sum_n (Ky^-1 K(X, X*))[n][m] dK(x*_m, x_n)/dx*_mq   (:454,462-465)
+//   dvar[m][q]    = dKdiag/dx* (= 0 for stationary kinds, stationary.py:360-361; 2 variance_q x*_mq for Linear) - 2 sum_n (Ky^-1 K(X, X*))[n][m] dK(x*_m, x_n)/dx*_mq   (:454,462-465)
 // with Ky^-1 K(X, X*) = X^T (X Kx), X = L^-1 resident from the inference call.  The reductions over n run as the column
 // reductions H^T [x~ | 1] of the sparse path's dL/dZ (H = weights * (dK/dr)/r, k_grad + k_colreduce_multi), per part.
 int mi355gp_predictive_gradients_sum(mi355gp_ctx* c, int nparts, const mi355gp_part* parts, const double* Xnew, int64_t M,
@@ -1023,6 +1052,19 @@ int mi355gp_predictive_gradients_sum(mi355gp_ctx* c, int nparts, const mi355gp_p
         for (size_t pi = 0; pi < c->parts.size(); ++pi) {
             const mi355gp_ctx::Part& pt = c->parts[pi];
             if (pt.is_static()) continue;                                        // White / Bias: no dependence on X* (static.py)
+            if (pt.linear()) {
+                // dK(x*_m, x_n)/dx*_mq = variance_q x_nq (linear.py:108-114): the column reduction W^T x~ of the weights themselves
+                const int ns = launch_colreduce_multi(st, W, mp, n, M, pt.dXt, 1, np, (int)D, 0, dCol);
+                launch_sum_splits(st, dCol, (long)M * D, ns, 0, dHX);
+                HIP_CHECK(hipMemcpyAsync(HX.data(), dHX, sizeof(double) * M * D, hipMemcpyDeviceToHost, st));
+                HIP_CHECK(hipStreamSynchronize(st));
+                gradx_linear(pt.inv_ls, M, (int)D, HX.data(), add);
+                if (is_var)                                                      // dKdiag/dx*_mq = 2 variance_q x*_mq
+                    for (long m = 0; m < M; ++m)
+                        for (size_t a = 0; a < pt.dims.size(); ++a)
+                            dvar_out[m * D + pt.dims[a]] += 2.0 * pt.theta[pt.kp.ard ? a : 0] * Xnew[m * D + pt.dims[a]];
+                continue;
+            }
             const double* xt = xs.points(st, pt);
             if (pt.kp.kind == MI355GP_STDPERIODIC) {                    // not a function of r: the row reduction instead of H
                 launch_periodic_gradx(st, pt.kp, xt, xs.ld, M, pt.dXt, np, n, W, mp, /*wt=*/1, dHX);
@@ -1092,7 +1134,7 @@ int mi355gp_covariance_between_points(mi355gp_ctx* c, int nparts, const mi355gp_
 
 int mi355gp_predict(mi355gp_ctx* c, int kind, int ard, const double* theta, const double* Xnew, int64_t M,
                     double* mu_out, double* var_out, int full_cov) {
-    if (int rc = check_kind(kind, KS_STATIONARY | KS_EXT, "mi355gp_predict")) return rc;
+    if (int rc = check_kind(kind, KS_STATIONARY | KS_EXT | KS_LINEAR, "mi355gp_predict")) return rc;
     const mi355gp_part part{kind, ard, 0, nullptr, theta};
     return mi355gp_predict_sum(c, 1, &part, Xnew, M, mu_out, var_out, full_cov);
 }

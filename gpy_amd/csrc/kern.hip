@@ -325,10 +325,23 @@ static void launch_kbuild_coreg(hipStream_t st, bool sym, KernParams kp, const d
                                 long ld2, long m, double* out, long ldo, long nrows_out, const double* noise, long noise_len,
                                 double jit, int lower_only, int add_diag, int ntc, int nblocks, int accumulate, const double* mul);
 
+// Linear (kind 9): at the end of this file as well
+static void launch_kbuild_lin(hipStream_t st, bool sym, KernParams kp, const double* Xt1, long ld1, long n, const double* Xt2,
+                              long ld2, long m, double* out, long ldo, long nrows_out, const double* noise, long noise_len,
+                              double jit, int lower_only, int add_diag, int ntc, int nblocks, int accumulate, const double* mul);
+static void launch_grad_lin(hipStream_t st, bool fused, KernParams kp, const double* Xt1, long ld1, long n, const double* Xt2,
+                            long ld2, long m, const double* G, long ldg, const double* alpha, int Dy, long ntiles, int ntc,
+                            double* partials, double* Hout, long ldh, const double* aa_scale, const double* Mul, long ldm);
+
 void launch_kbuild_sym(hipStream_t st, KernParams kp, const double* Xt, long ldx, long n, long npad, double* A,
                        const double* noise, long noise_len, double jit, int lower_only, int add_diag, int accumulate,
                        const double* mul) {
     const int nt = (int)(npad / KT);
+    if (kp.kind == MI355GP_LINEAR) {
+        launch_kbuild_lin(st, true, kp, Xt, ldx, n, Xt, ldx, n, A, npad, npad, noise, noise_len, jit, lower_only, add_diag, nt,
+                          nt * nt, accumulate, mul);
+        return;
+    }
     if (kp.kind == MI355GP_COREGIONALIZE) {
         launch_kbuild_coreg(st, true, kp, Xt, ldx, n, Xt, ldx, n, A, npad, npad, noise, noise_len, jit, lower_only, add_diag, nt,
                             nt * nt, accumulate, mul);
@@ -346,6 +359,11 @@ void launch_kbuild_sym(hipStream_t st, KernParams kp, const double* Xt, long ldx
 void launch_kbuild_cross(hipStream_t st, KernParams kp, const double* Xt1, long ld1, long n, const double* Xt2,
                          long ld2, long m, double* Kout, long ldk, int accumulate, int diag_same, const double* mul) {
     const int ntr = (int)((n + KT - 1) / KT), ntc = (int)((m + KT - 1) / KT);
+    if (kp.kind == MI355GP_LINEAR) {                                       // (the diagonal is whatever the dot product gives)
+        launch_kbuild_lin(st, false, kp, Xt1, ld1, n, Xt2, ld2, m, Kout, ldk, n, nullptr, 0, 0.0, 0, 0, ntc, ntr * ntc, accumulate,
+                          mul);
+        return;
+    }
     if (kp.kind == MI355GP_COREGIONALIZE) {                                // (no White-like diagonal: diag_same changes nothing)
         launch_kbuild_coreg(st, false, kp, Xt1, ld1, n, Xt2, ld2, m, Kout, ldk, n, nullptr, 0, 0.0, 0, 0, ntc, ntr * ntc, accumulate,
                             mul);
@@ -535,6 +553,11 @@ void launch_grad_fused(hipStream_t st, KernParams kp, const double* Xt, long ldx
     const long nt = (n + KT - 1) / KT;
     const long ntiles = nt * (nt + 1) / 2;
     const int nb = pick_grad_blocks(ntiles);
+    if (kp.kind == MI355GP_LINEAR) {
+        launch_grad_lin(st, true, kp, Xt, ldx, n, Xt, ldx, n, W, ldw, alpha, Dy, ntiles, (int)nt, partials, nullptr, 0, aa_scale,
+                        Mul, ldm);
+        return;
+    }
     if (kp.kind >= MI355GP_RATQUAD) {
         launch_grad_ext(st, true, kp, Xt, ldx, n, Xt, ldx, n, W, ldw, alpha, Dy, ntiles, (int)nt, partials, nullptr, 0, aa_scale,
                         Mul, ldm);
@@ -926,6 +949,12 @@ void launch_grad_generic(hipStream_t st, KernParams kp, const double* Xt1, long 
     const long ntr = (n + KT - 1) / KT, ntc = (m + KT - 1) / KT;
     const long ntiles = ntr * ntc;
     const int nb = pick_grad_blocks(ntiles);
+    if (kp.kind == MI355GP_LINEAR) {
+        if (rk.Y) return;                                  // (the sparse path's rank term: it does not have the kind)
+        launch_grad_lin(st, false, kp, Xt1, ld1, n, Xt2, ld2, m, G, ldg, nullptr, 0, ntiles, (int)ntc, partials, Hout, ldh,
+                        nullptr, nullptr, 0);
+        return;
+    }
     if (kp.kind >= MI355GP_RATQUAD) {
         if (rk.Y) return;                                  // the rank term belongs to the sparse path, which has neither kind
         launch_grad_ext(st, false, kp, Xt1, ld1, n, Xt2, ld2, m, G, ldg, nullptr, 0, ntiles, (int)ntc, partials, Hout, ldh,
@@ -2024,4 +2053,240 @@ __global__ __launch_bounds__(256) void k_col_reduce_vec(const double* __restrict
 
 void launch_col_reduce_vec(hipStream_t st, const double* M, long ld, long rows, long cols, const double* kd, double* out) {
     hipLaunchKernelGGL(k_col_reduce_vec, dim3((unsigned)((cols + 63) / 64)), dim3(256), 0, st, M, ld, rows, cols, kd, out);
+}
+
+// ------------------------------------------------------------------------------------------------
+// Linear (kind 9, linear.py:13-114): K = sum_q var_q x_iq x_jq.  Inputs arrive scaled by sqrt(var_q) on the active dimensions
+// (0 elsewhere), so K = sum_q x~_iq x~_jq with no further factor.  Kernels of their own again: every other instantiation keeps
+// its code.  The sum over q runs in the same order for (i, j) and (j, i) and fma(a, b, c) = fma(b, a, c): K(X, X) is bitwise
+// symmetric.  The diagonal is what the sum gives (it depends on the point; there is no variance to put there).
+
+// s[a][b] += sum_q xi[q][ty*4+a] * xj[q][tx*4+b]
+__device__ __forceinline__ void accum_dot(const double* si, const double* sj, int qc, int ty, int tx, double (&s)[4][4]) {
+    for (int q = 0; q < qc; ++q) {
+        const d4 xi = *reinterpret_cast<const d4*>(si + q * KT + ty * 4);
+        const d4 xj = ld_xj(sj, q, tx);
+#pragma unroll
+        for (int a = 0; a < 4; ++a)
+#pragma unroll
+            for (int b = 0; b < 4; ++b) s[a][b] = fma(xi[a], xj[b], s[a][b]);
+    }
+}
+
+// Covariance assembly of k_kbuild (same tiling, same output conventions).
+template <bool SYM>
+__global__ __launch_bounds__(256) void k_kbuild_lin(KernParams kp, const double* __restrict__ Xt1, long ld1, long n,
+                                                    const double* __restrict__ Xt2, long ld2, long m,
+                                                    double* __restrict__ out, long ldo, long nrows_out,
+                                                    const double* __restrict__ noise, long noise_len, double jit,
+                                                    int lower_only, int add_diag, int ntc, int accumulate, const double* mul) {
+    __shared__ __attribute__((aligned(16))) double si[KDC * KT];
+    __shared__ __attribute__((aligned(16))) double sj[KDC * KTJ];
+    const int t = threadIdx.x, tx = t & 15, ty = t >> 4;
+    const long ti = blockIdx.x / ntc, tj = blockIdx.x % ntc;
+    if (SYM && lower_only && tj > ti) return;
+    const long i0 = ti * KT, j0 = tj * KT;
+    double s[4][4];
+#pragma unroll
+    for (int a = 0; a < 4; ++a)
+#pragma unroll
+        for (int b = 0; b < 4; ++b) s[a][b] = 0.0;
+    if ((i0 < n) && (j0 < m)) {
+        for (int q0 = 0; q0 < kp.D; q0 += KDC) {
+            const int qc = (kp.D - q0 < KDC) ? (kp.D - q0) : KDC;
+            __syncthreads();
+            stage_x(Xt1, ld1, i0, q0, qc, si, t);
+            stage_xj(Xt2, ld2, j0, q0, qc, sj, t);
+            __syncthreads();
+            accum_dot(si, sj, qc, ty, tx, s);
+        }
+    }
+#pragma unroll
+    for (int a = 0; a < 4; ++a) {
+        const long i = i0 + ty * 4 + a;
+        double v[4];
+#pragma unroll
+        for (int b = 0; b < 4; ++b) {
+            const long j = j0 + tx * 4 + b;
+            if (i < n && j < m) v[b] = s[a][b];
+            else v[b] = (SYM && i == j && !accumulate) ? 1.0 : 0.0;
+        }
+        if (SYM) {
+            if (i < nrows_out) {
+                d4* p = reinterpret_cast<d4*>(out + i * ldo + j0 + tx * 4);
+                d4 o = (d4){v[0], v[1], v[2], v[3]};
+                if (mul) o *= *reinterpret_cast<const d4*>(mul + i * ldo + j0 + tx * 4);
+                if (add_diag && i < n) {
+                    const long d = i - (j0 + tx * 4);
+                    if (d >= 0 && d < 4) o[d] += noise[noise_len > 1 ? i : 0] + jit;
+                }
+                if (accumulate) o += *p;
+                *p = o;
+            }
+        } else if (i < n) {
+#pragma unroll
+            for (int b = 0; b < 4; ++b) {
+                const long j = j0 + tx * 4 + b;
+                if (j < m) {
+                    const double w = mul ? v[b] * mul[i * ldo + j] : v[b];
+                    out[i * ldo + j] = accumulate ? out[i * ldo + j] + w : w;
+                }
+            }
+        }
+    }
+}
+
+static void launch_kbuild_lin(hipStream_t st, bool sym, KernParams kp, const double* Xt1, long ld1, long n, const double* Xt2,
+                              long ld2, long m, double* out, long ldo, long nrows_out, const double* noise, long noise_len,
+                              double jit, int lower_only, int add_diag, int ntc, int nblocks, int accumulate, const double* mul) {
+    const dim3 g((unsigned)nblocks), b(256);
+    if (sym)
+        hipLaunchKernelGGL((k_kbuild_lin<true>), g, b, 0, st, kp, Xt1, ld1, n, Xt2, ld2, m, out, ldo, nrows_out, noise, noise_len,
+                           jit, lower_only, add_diag, ntc, accumulate, mul);
+    else
+        hipLaunchKernelGGL((k_kbuild_lin<false>), g, b, 0, st, kp, Xt1, ld1, n, Xt2, ld2, m, out, ldo, nrows_out, noise, noise_len,
+                           jit, lower_only, add_diag, ntc, accumulate, mul);
+}
+
+// Gradient pass of k_grad for the kind, one launch per group of 32 dimensions (q_off; one launch if !ard).  Record [GP_STRIDE]
+// per block: [0] sum g K, ARD [2 + q] sum g x~_iq x~_jq (the host divides by variance / variance_q, linear.py:87-98).
+// FUSED: g = 0.5 (sc alpha alpha^T - Dy W) over the lower triangle, off-diagonal weights doubled; else g = G (n x m).
+// g is multiplied by Mul (product terms) and, if Hout is given (generic form), written there: the weights of gradients_X.
+template <bool FUSED>
+__global__ __launch_bounds__(256) void k_grad_lin(KernParams kp, const double* __restrict__ Xt1, long ld1, long n,
+                                                  const double* __restrict__ Xt2, long ld2, long m,
+                                                  const double* __restrict__ G, long ldg,
+                                                  const double* __restrict__ alpha, int Dy, int q_off,
+                                                  long ntiles, int ntc, double* __restrict__ partials,
+                                                  double* __restrict__ Hout, long ldh, const double* __restrict__ aa_scale,
+                                                  const double* __restrict__ Mul, long ldm) {
+    __shared__ __attribute__((aligned(16))) double si[KDC * KT];
+    __shared__ __attribute__((aligned(16))) double sj[KDC * KTJ];
+    __shared__ double red[256];
+    const int t = threadIdx.x, tx = t & 15, ty = t >> 4;
+    double a_var = 0.0;
+    double a_q[KDC];
+#pragma unroll
+    for (int q = 0; q < KDC; ++q) a_q[q] = 0.0;
+    const int qcnt = kp.ard ? ((kp.D - q_off < KDC) ? (kp.D - q_off) : KDC) : 0;
+    const double sc = (FUSED && aa_scale) ? aa_scale[0] : 1.0;
+
+    for (long tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+        long ti, tj;
+        if (FUSED) {   // lower-triangular enumeration
+            ti = (long)((sqrt(8.0 * (double)tile + 1.0) - 1.0) * 0.5);
+            while (ti * (ti + 1) / 2 > tile) --ti;
+            while ((ti + 1) * (ti + 2) / 2 <= tile) ++ti;
+            tj = tile - ti * (ti + 1) / 2;
+        } else {
+            ti = tile / ntc;
+            tj = tile - ti * ntc;
+        }
+        const long i0 = ti * KT, j0 = tj * KT;
+        double s[4][4];
+#pragma unroll
+        for (int a = 0; a < 4; ++a)
+#pragma unroll
+            for (int b = 0; b < 4; ++b) s[a][b] = 0.0;
+        int last_q0 = -1;
+        for (int q0 = 0; q0 < kp.D; q0 += KDC) {
+            const int qc = (kp.D - q0 < KDC) ? (kp.D - q0) : KDC;
+            __syncthreads();
+            stage_x(Xt1, ld1, i0, q0, qc, si, t);
+            stage_xj(Xt2, ld2, j0, q0, qc, sj, t);
+            __syncthreads();
+            accum_dot(si, sj, qc, ty, tx, s);
+            last_q0 = q0;
+        }
+        double gw[4][4];   // g
+#pragma unroll
+        for (int a = 0; a < 4; ++a) {
+            const long i = i0 + ty * 4 + a;
+#pragma unroll
+            for (int b = 0; b < 4; ++b) {
+                const long j = j0 + tx * 4 + b;
+                double g = 0.0;
+                if (i < n && j < m) {
+                    if (FUSED) {
+                        if (j <= i) {
+                            double aa = 0.0;
+                            for (int d = 0; d < Dy; ++d) aa = fma(alpha[i * Dy + d], alpha[j * Dy + d], aa);
+                            g = 0.5 * (sc * aa - (double)Dy * G[i * ldg + j]);
+                            if (j < i) g *= 2.0;
+                        }
+                    } else {
+                        g = G[i * ldg + j];
+                    }
+                    if (Mul) g *= Mul[i * ldm + j];
+                    if (!FUSED && Hout) Hout[i * ldh + j] = g;
+                }
+                a_var = fma(g, s[a][b], a_var);
+                gw[a][b] = g;
+            }
+        }
+        if (qcnt > 0) {
+            if (last_q0 != q_off) {   // D > 32: bring the dims of this launch back into LDS
+                __syncthreads();
+                stage_x(Xt1, ld1, i0, q_off, qcnt, si, t);
+                stage_xj(Xt2, ld2, j0, q_off, qcnt, sj, t);
+                __syncthreads();
+            }
+#pragma unroll
+            for (int q = 0; q < KDC; ++q) {
+                if (q < qcnt) {
+                    const d4 xi = *reinterpret_cast<const d4*>(si + q * KT + ty * 4);
+                    const d4 xj = ld_xj(sj, q, tx);
+                    double s1 = 0.0;
+#pragma unroll
+                    for (int a = 0; a < 4; ++a) {
+                        double r = 0.0;
+#pragma unroll
+                        for (int b = 0; b < 4; ++b) r = fma(gw[a][b], xj[b], r);
+                        s1 = fma(xi[a], r, s1);
+                    }
+                    a_q[q] += s1;
+                }
+            }
+        }
+    }
+    // deterministic block reduction -> partials[blockIdx][...]
+    double* out = partials + (long)blockIdx.x * GP_STRIDE;
+    auto block_sum = [&](double v) -> double {
+        __syncthreads();
+        red[t] = v;
+        __syncthreads();
+        for (int s = 128; s > 0; s >>= 1) {
+            if (t < s) red[t] += red[t + s];
+            __syncthreads();
+        }
+        return red[0];
+    };
+    const double sv = block_sum(a_var);
+    if (t == 0) out[0] = sv;
+#pragma unroll
+    for (int q = 0; q < KDC; ++q) {
+        if (q < qcnt) {
+            const double sq = block_sum(a_q[q]);
+            if (t == 0) out[2 + q] = sq;
+        }
+    }
+}
+
+static void launch_grad_lin(hipStream_t st, bool fused, KernParams kp, const double* Xt1, long ld1, long n, const double* Xt2,
+                            long ld2, long m, const double* G, long ldg, const double* alpha, int Dy, long ntiles, int ntc,
+                            double* partials, double* Hout, long ldh, const double* aa_scale, const double* Mul, long ldm) {
+    const int nb = pick_grad_blocks(ntiles);
+    const dim3 g((unsigned)nb), b(256);
+    for (int q_off = 0, gidx = 0; q_off < kp.D; q_off += KDC, ++gidx) {
+        if (!kp.ard && gidx > 0) break;
+        double* pa = partials + (long)gidx * nb * GP_STRIDE;
+        // Hout may alias G (in place): only the LAST group launch writes it
+        double* h = (!kp.ard || q_off + KDC >= kp.D) ? Hout : nullptr;
+        if (fused)
+            hipLaunchKernelGGL((k_grad_lin<true>), g, b, 0, st, kp, Xt1, ld1, n, Xt2, ld2, m, G, ldg, alpha, Dy, q_off, ntiles, ntc, pa,
+                               nullptr, 0, aa_scale, Mul, ldm);
+        else
+            hipLaunchKernelGGL((k_grad_lin<false>), g, b, 0, st, kp, Xt1, ld1, n, Xt2, ld2, m, G, ldg, nullptr, 0, q_off, ntiles, ntc, pa,
+                               h, ldh, nullptr, Mul, ldm);
+    }
 }

@@ -21,12 +21,13 @@ enum : KindSet {
     KS_STATIC = 1u << MI355GP_WHITE | 1u << MI355GP_BIAS,
     KS_EXT = 1u << MI355GP_RATQUAD | 1u << MI355GP_STDPERIODIC,     // two reduction records per part (k_grad_ext)
     KS_COREG = 1u << MI355GP_COREGIONALIZE,
+    KS_LINEAR = 1u << MI355GP_LINEAR,                               // exact path only; Kdiag depends on the point
 };
 static inline bool kind_in(int kind, KindSet s) { return kind >= 0 && kind < 32 && ((s >> kind) & 1u); }
 static inline const char* kind_name(int kind) {
     static const char* const names[] = {"RBF", "Matern52", "Matern32", "Exponential", "White", "Bias", "RatQuad",
-                                        "StdPeriodic", "Coregionalize"};
-    return kind_in(kind, KS_STATIONARY | KS_STATIC | KS_EXT | KS_COREG) ? names[kind] : "unknown";
+                                        "StdPeriodic", "Coregionalize", "Linear"};
+    return kind_in(kind, KS_STATIONARY | KS_STATIC | KS_EXT | KS_COREG | KS_LINEAR) ? names[kind] : "unknown";
 }
 
 #define PART_FAIL(...)                    \
@@ -64,7 +65,8 @@ struct PartSpec {
     std::vector<int> dims;          // active input dimensions (kern.py:49-53), indices into the D columns of X
     std::vector<double> theta;      // exactly the kind's parameters, in theta order
     std::vector<double> inv_ls;     // length D: 1/l on active dimensions, 0 elsewhere (= the slicing of kern.py:112-117)
-                                    // (StdPeriodic: 1 on active dimensions, Coregionalize: 1 on the index column -- unscaled)
+                                    // (StdPeriodic: 1 on active dimensions, Coregionalize: 1 on the index column -- unscaled;
+                                    // Linear: sqrt(variance_q), so that K = sum_q x~_iq x~_jq)
     std::vector<double> pw;         // StdPeriodic: [pi / T_q (D) | 1 / l_q (D)]; Coregionalize: B (P x P); empty otherwise
     int term = 0;                   // term id of the C-ABI part: parts with the same non-zero id are multiplied (prod.py)
     int tix = 0;                    // index of its summand in the terms of group_terms
@@ -72,6 +74,8 @@ struct PartSpec {
     bool is_static() const { return kind_in(kp.kind, KS_STATIC); }
     bool ext() const { return kind_in(kp.kind, KS_EXT); }
     bool coreg() const { return kp.kind == MI355GP_COREGIONALIZE; }
+    bool linear() const { return kp.kind == MI355GP_LINEAR; }
+    bool diag_by_point() const { return coreg() || linear(); }   // Kdiag depends on the point: kp.variance is NOT the diagonal
 };
 
 // A part with its parameters on the device as well: inv_ls (D) and pw, uploaded together once per call by upload() (kp.pw ->
@@ -155,6 +159,14 @@ static inline int parse_part(const mi355gp_part& in, int D, KindSet accepted, co
         }
         p->kp.ard = 1;                                 // per-dimension reductions
         nt = 1 + nper + nl;
+    } else if (kind == MI355GP_LINEAR) {               // [variance (1 or n_active)] (linear.py:34-51)
+        nt = ard ? na : 1;
+        for (int a = 0; a < na; ++a) {
+            const double v = th[ard ? a : 0];
+            if (int rc = positive(v, "variance")) return rc;
+            p->inv_ls[(size_t)p->dims[a]] = std::sqrt(v);
+        }
+        p->kp.ard = ard ? 1 : 0;                       // per-dimension reductions
     } else if (!p->is_static()) {                      // stationary and RatQuad: [variance, lengthscale (1 or n_active)(, power)]
         const int nl = ard ? na : 1;
         for (int a = 0; a < na; ++a) {
@@ -184,6 +196,12 @@ static inline int part_dtheta(const PartSpec& p, const double* rec, const double
         return ard * ard;
     }
     int k = 0;
+    if (p.linear()) {                                  // linear.py:87-98: sum g K / variance, or per dimension sum g x~_iq x~_jq / variance_q
+        if (!p.kp.ard) o[k++] = rec[0] / th[0];
+        else
+            for (int a = 0; a < na; ++a) o[k++] = rec_at(rec, p.dims[a]) / th[a];
+        return k;
+    }
     o[k++] = rec[0] / p.kp.variance;                   // sum g K / variance
     if (p.is_static()) return k;
     if (p.kp.kind == MI355GP_STDPERIODIC) {
@@ -239,7 +257,8 @@ static inline bool has_product(const Terms& terms) {
     return false;
 }
 
-// Kdiag of the expression: sum over terms of the product of the factors' variances (add.py:74-79, prod.py:67-71)
+// Kdiag of the expression: sum over terms of the product of the factors' variances (add.py:74-79, prod.py:67-71).  Only for
+// expressions without a diag_by_point() part (the sparse path's kinds; the exact path asks expression_kdiag_points).
 template <class Part>
 static double expression_kdiag(const std::vector<Part>& parts, const Terms& terms) {
     double s = 0.0;
@@ -353,4 +372,11 @@ static void gradx_periodic(const std::vector<double>& pw, long rows, int D, cons
     for (long i = 0; i < rows; ++i)
         for (int q = 0; q < D; ++q)
             put(i, q, -0.5 * pw[(size_t)q] * pw[(size_t)(D + q)] * pw[(size_t)(D + q)] * HX[i * D + q]);
+}
+// Linear (linear.py:108-114): HX = H^T x2~ (rows x D, x2~ scaled by sqrt(variance_q) = il_q):
+//   put(i, q, il_q HX[i][q]) = variance_q sum_j H_ij x2_jq
+template <class Put>
+static void gradx_linear(const std::vector<double>& il, long rows, int D, const double* HX, Put put) {
+    for (long i = 0; i < rows; ++i)
+        for (int q = 0; q < D; ++q) put(i, q, il[(size_t)q] * HX[i * D + q]);
 }

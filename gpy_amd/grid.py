@@ -327,7 +327,10 @@ class GridContext(object):
     def exact_inference(self, kind, ARD, theta, noise, jitter=1e-8, extra_jitter=0.0, want_diag=False,
                         want_stage_ms=False):
         if kind not in KIND_IDS or KIND_IDS[kind] > 3:
-            raise NotImplementedError("the row-sharded grid path evaluates RBF / Matern / Exponential kernels, not %r" % kind)
+            from .kern import KERNEL_CLASSES                    # name the class as the sparse path does (e.g. Linear)
+            cls = KERNEL_CLASSES.get(kind)
+            raise NotImplementedError("the row-sharded grid path evaluates RBF / Matern / Exponential kernels, not %s"
+                                      % (cls.__name__ if cls is not None else repr(kind)))
         theta = f64(theta)
         noise = f64(np.atleast_1d(noise))
         out = np.zeros(NUM_OUT)

@@ -12,7 +12,7 @@ the same `numpy.linalg.LinAlgError` messages.
 import numpy as np
 
 from . import _lib
-from .kern import DEVICE_KERNELS, CombinationKernel, has_coregionalize
+from .kern import DEVICE_KERNELS, CombinationKernel, diag_depends_on_point
 from .lazy import ArrayIdentity, DeviceResult, kernel_signature
 from .likelihoods import Gaussian
 from .posterior import PosteriorExact, StudentTPosterior
@@ -176,8 +176,8 @@ class ExactGaussianInference(object):
         if fused:
             if is_sum:
                 specs = kern.part_specs()
-                # jitchol's mean(diag(A)): with a Coregionalize part Kdiag depends on the point
-                diagA = (kern.Kdiag(X) if has_coregionalize(kern) else kern.diag_variance()) + noise + 1e-8
+                # jitchol's mean(diag(A)): with a Coregionalize or Linear part Kdiag depends on the point
+                diagA = (kern.Kdiag(X) if diag_depends_on_point(kern) else kern.diag_variance()) + noise + 1e-8
 
                 def attempt(extra):
                     return st.ctx.exact_inference_sum(specs, noise, jitter=1e-8, extra_jitter=extra, want_alpha=True,
@@ -185,7 +185,8 @@ class ExactGaussianInference(object):
                                                       want_stage_ms=want_ms)
             else:
                 theta = kern._theta()
-                diagA = float(theta[0]) + noise + 1e-8
+                # (a lone Linear: theta[0] is a variance, not the diagonal)
+                diagA = (kern.Kdiag(X) if diag_depends_on_point(kern) else float(theta[0])) + noise + 1e-8
 
                 def attempt(extra):
                     return st.ctx.exact_inference(kern.kind, kern.ARD, theta, noise, jitter=1e-8, extra_jitter=extra,
@@ -273,7 +274,7 @@ class ExactStudentTInference(object):
                 break
             if tries >= self.maxtries:
                 raise LinAlgError("not positive definite, even with jitter.")
-            if is_sum and has_coregionalize(kern):
+            if diag_depends_on_point(kern):
                 kd = float(np.mean(kern.Kdiag(X)))
             else:
                 kd = kern.diag_variance() if is_sum else float(specs[0][2][0])

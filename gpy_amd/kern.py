@@ -568,16 +568,117 @@ class Coregionalize(Parameterized):
     __getstate__ = Stationary.__getstate__
 
 
+class Linear(Parameterized):
+    """Linear kernel k(x, y) = sum_q variances_q x_q y_q (reference `GPy/kern/src/linear.py:13-114`).  Not stationary: the
+    diagonal K(x, x) = sum_q variances_q x_q^2 depends on the point.  On the device it is C-ABI kind `MI355GP_LINEAR`: a
+    dot-product K-build and gradient pass of its own, alone, in `Add` and as a `Prod` factor; `Kdiag` and the diagonal
+    gradients are O(N D) host arithmetic.  One parameter, `variances` (one value, or one per input dimension with `ARD`)."""
+    kind = "linear"
+    _gpy_class = "GPy.kern.Linear"
+    _support_GPU = True
+
+    def __init__(self, input_dim, variances=None, ARD=False, active_dims=None, name="linear", useGPU=True, device=0):
+        super(Linear, self).__init__(name)
+        self.input_dim = int(input_dim)
+        self.ARD = bool(ARD)
+        self.device = device
+        self.useGPU = True
+        if active_dims is None:
+            active_dims = np.arange(self.input_dim)
+        self.active_dims = np.atleast_1d(np.asarray(active_dims, dtype=np.int_))
+        assert self.active_dims.size == self.input_dim, "input_dim=%d does not match len(active_dims)=%d" % (
+            self.input_dim, self.active_dims.size)
+        if not self.ARD:                                               # linear.py:37-48
+            if variances is not None:
+                variances = np.asarray(variances, dtype=float)
+                assert variances.size == 1, "Only one variance needed for non-ARD kernel"
+            else:
+                variances = np.ones(1)
+        else:
+            if variances is not None:
+                variances = np.asarray(variances, dtype=float)
+                assert variances.size == self.input_dim, "bad number of variances, need one ARD variance per input_dim"
+            else:
+                variances = np.ones(self.input_dim)
+        self.variances = Param("variances", variances)
+        self.link_parameter(self.variances)
+        self._K_cache = _KCache(limit=3)
+
+    def _theta(self):
+        return np.asarray(self.variances.values, dtype=np.float64).ravel().copy()
+
+    # slicing, the cached K, the fused / device gradients and gradients_X are the stationary kernels' (they only go through
+    # kind / ARD / _theta)
+    __getstate__ = Stationary.__getstate__
+    _slice_X = Stationary._slice_X
+    K = Stationary.K
+    update_gradients_full = Stationary.update_gradients_full
+    gradients_X = Stationary.gradients_X
+
+    def Kdiag(self, X):
+        """(reference `linear.py:84-85`)"""
+        return np.sum(self._theta() * np.square(self._slice_X(X)), -1)
+
+    def _install_gradients(self, g):
+        self.variances.gradient = np.asarray(g, dtype=float).copy() if self.ARD else g[0]
+
+    def update_gradients_diag(self, dL_dKdiag, X):
+        """(reference `linear.py:100-105`)"""
+        tmp = np.asarray(dL_dKdiag, dtype=float).ravel()[:, None] * self._slice_X(X) ** 2
+        self.variances.gradient = tmp.sum(0) if self.ARD else np.atleast_1d(tmp.sum())
+
+    def reset_gradients(self):
+        self.variances.gradient = np.zeros(self.input_dim) if self.ARD else 0.
+
+    def gradients_X_diag(self, dL_dKdiag, X):
+        """(reference `linear.py:140-141`): 2 variances_q x_q dL_dKdiag, zero outside the active dimensions"""
+        X = np.asarray(X, dtype=float)
+        out = np.zeros(X.shape)
+        out[:, self.active_dims] = 2. * self._theta() * np.asarray(dL_dKdiag, dtype=float).ravel()[:, None] * self._slice_X(X)
+        return out
+
+    def input_sensitivity(self, summarize=True):
+        """(reference `linear.py:151-152`)"""
+        return np.ones(self.input_dim) * self._theta()
+
+    def __add__(self, other):
+        return Add([self, other])
+
+    def __mul__(self, other):
+        return Prod([self, other])
+
+    def to_dict(self):
+        """(reference `linear.py:54-59`)"""
+        return {"class": self._gpy_class, "name": self.name, "input_dim": self.input_dim,
+                "active_dims": self.active_dims.tolist(), "variances": self.variances.values.tolist(), "ARD": self.ARD,
+                "useGPU": True}
+
+    @classmethod
+    def from_dict(cls, d):
+        d = dict(d)
+        d.pop("class", None)
+        d.pop("useGPU", None)
+        return cls(**d)
+
+    copy = Stationary.copy
+
+
 # kernels the exact-GP device path evaluates as one part (the fused inference call takes them alone or in Add / Prod)
-DEVICE_KERNELS = (Stationary, StdPeriodic)
+DEVICE_KERNELS = (Stationary, StdPeriodic, Linear)
 # kinds only the exact path has (the sparse and grid paths reject them)
-EXACT_ONLY_KINDS = ("ratquad", "stdperiodic", "coregionalize")
+EXACT_ONLY_KINDS = ("ratquad", "stdperiodic", "coregionalize", "linear")
 
 
 def has_coregionalize(kern):
     """True if the expression holds a Coregionalize part (its Kdiag then depends on the point)"""
     leaves = kern.leaves() if isinstance(kern, CombinationKernel) else [kern]
     return any(isinstance(k, Coregionalize) for k in leaves)
+
+
+def diag_depends_on_point(kern):
+    """True if Kdiag of the kernel or expression is not a constant: it holds a Coregionalize or a Linear leaf"""
+    leaves = kern.leaves() if isinstance(kern, CombinationKernel) else [kern]
+    return any(isinstance(k, (Coregionalize, Linear)) for k in leaves)
 
 
 def _spec_dims(f):
@@ -680,7 +781,8 @@ class CombinationKernel(Parameterized):
 
     def gradients_X_diag(self, dL_dKdiag, X):
         """Stationary and static leaves have a constant diagonal (reference `stationary.py:360-361`, `static.py:40-41`), and so
-        has every sum / product of them (`add.py:102-106`, `prod.py:123-128`)."""
+        has every sum / product of them (`add.py:102-106`, `prod.py:123-128`); `Add` / `Prod` compose their parts' so that a
+        Linear leaf (`linear.py:140-141`) enters."""
         return np.zeros(np.asarray(X).shape)
 
     def leaves(self):
@@ -710,7 +812,7 @@ class CombinationKernel(Parameterized):
         raise NotImplementedError
 
     def diag_variance(self):
-        """Kdiag of the expression (a constant for stationary / static leaves)"""
+        """Kdiag of the expression (a constant for stationary / static leaves; not meaningful when `diag_depends_on_point`)"""
         return float(self.Kdiag(np.zeros((1, self.input_dim)))[0])
 
 
@@ -723,8 +825,8 @@ class Add(CombinationKernel):
         flat = []
         for p in parts:
             flat.extend(p.parts if isinstance(p, Add) else [p])          # add.py:24-33 flattens nested sums
-        assert all(isinstance(p, (Stationary, StdPeriodic, Static, Coregionalize, Prod)) for p in flat), \
-            "Add supports stationary, StdPeriodic, White, Bias, Coregionalize and Prod parts"
+        assert all(isinstance(p, (Stationary, StdPeriodic, Linear, Static, Coregionalize, Prod)) for p in flat), \
+            "Add supports stationary, StdPeriodic, Linear, White, Bias, Coregionalize and Prod parts"
         super(Add, self).__init__(flat, name)
 
     def part_specs(self):
@@ -766,6 +868,9 @@ class Add(CombinationKernel):
         G = np.asarray(dL_dK)
         return sum(p.gradients_X(G, X, X2) for p in self.parts)
 
+    def gradients_X_diag(self, dL_dKdiag, X):                                    # add.py:102-105
+        return sum(p.gradients_X_diag(dL_dKdiag, X) for p in self.parts)
+
     def to_dict(self):
         return {"class": "GPy.kern.Add", "name": self.name, "parts": [p.to_dict() for p in self.parts]}
 
@@ -779,8 +884,8 @@ class Prod(CombinationKernel):
         flat = []
         for k in kernels:
             flat.extend(k.parts if isinstance(k, Prod) else [k])
-        assert all(isinstance(k, (Stationary, StdPeriodic, Static, Coregionalize)) for k in flat), \
-            "Prod supports stationary, StdPeriodic, White, Bias and Coregionalize factors"
+        assert all(isinstance(k, (Stationary, StdPeriodic, Linear, Static, Coregionalize)) for k in flat), \
+            "Prod supports stationary, StdPeriodic, Linear, White, Bias and Coregionalize factors"
         super(Prod, self).__init__(flat, name)
 
     def part_specs(self):
@@ -835,9 +940,22 @@ class Prod(CombinationKernel):
             out = out + p.gradients_X(W, X, X2)
         return out
 
+    def gradients_X_diag(self, dL_dKdiag, X):
+        """every factor sees dL_dKdiag times the other factors' diagonals (the product rule on `prod.py:67-71`)"""
+        ds = [p.Kdiag(X) for p in self.parts]
+        out = 0.
+        for i, p in enumerate(self.parts):
+            w = np.asarray(dL_dKdiag, dtype=float)
+            for j, d in enumerate(ds):
+                if j != i:
+                    w = w * d
+            out = out + p.gradients_X_diag(w, X)
+        return out
+
     def to_dict(self):
         return {"class": "GPy.kern.Prod", "name": self.name, "parts": [p.to_dict() for p in self.parts]}
 
 
 KERNEL_CLASSES = {"rbf": RBF, "expquad": ExpQuad, "matern52": Matern52, "matern32": Matern32, "exponential": Exponential,
-                  "white": White, "bias": Bias, "ratquad": RatQuad, "stdperiodic": StdPeriodic, "coregionalize": Coregionalize}
+                  "white": White, "bias": Bias, "ratquad": RatQuad, "stdperiodic": StdPeriodic, "coregionalize": Coregionalize,
+                  "linear": Linear}

@@ -26,7 +26,7 @@ typedef struct mi355gp_ctx mi355gp_ctx;
 
 enum { MI355GP_RBF = 0, MI355GP_MATERN52 = 1, MI355GP_MATERN32 = 2, MI355GP_EXPONENTIAL = 3,
        MI355GP_WHITE = 4, MI355GP_BIAS = 5 /* static kernels, only as parts of a sum (kern/src/static.py:63-98,151-173) */,
-       MI355GP_RATQUAD = 6, MI355GP_STDPERIODIC = 7, MI355GP_COREGIONALIZE = 8 };
+       MI355GP_RATQUAD = 6, MI355GP_STDPERIODIC = 7, MI355GP_COREGIONALIZE = 8, MI355GP_LINEAR = 9 };
 
 /* The exact-GP entry points (single kind and part lists; not the sparse or grid paths) also take
  *   MI355GP_RATQUAD      k = var (1 + r^2/2)^-power (kern/src/stationary.py:747-802, GPy.kern.RatQuad);
@@ -50,6 +50,16 @@ enum { MI355GP_RBF = 0, MI355GP_MATERN52 = 1, MI355GP_MATERN32 = 2, MI355GP_EXPO
  *                          dkappa = diag(S), dW = (S + S^T) W (:110-128).  Usually a factor of a product term (ICM / LCM);
  *                          the single-kind entry points, mi355gp_kern_Kdiag, mi355gp_predictive_gradients_sum and the sparse
  *                          and grid paths reject it. */
+
+/* The exact-GP entry points (single kind and part lists), mi355gp_predictive_gradients_sum and the stateless mi355gp_kern_K /
+ * mi355gp_update_gradients_full / mi355gp_gradients_X also take
+ *   MI355GP_LINEAR         k(x, x') = sum_q var_q x_q x'_q (kern/src/linear.py:13-85, GPy.kern.Linear), alone, as a summand or as
+ *                          a factor of a product term.  theta = the variances in GPy's order (:34-51): one value (ard = 0) or
+ *                          one per active dimension (ard = 1); every one must be positive.  Gradients come back in theta
+ *                          order (:87-98).  Not stationary: K(x, x) = sum_q var_q x_q^2 depends on the point (:84-85), so
+ *                          prediction variances take Kdiag per point and mi355gp_kern_Kdiag (no X argument) rejects the kind;
+ *                          dK/dx = var_q x'_q (:108-114) and dKdiag/dx = 2 var_q x_q enter mi355gp_predictive_gradients_sum.
+ *                          The sparse and grid paths reject it. */
 
 /* One part of a sum-of-products kernel expression (GPy.kern.Add, kern/src/add.py:58-84; GPy.kern.Prod,
  * kern/src/prod.py:58-99).  theta = [variance, lengthscale (1, or n_active if ard)] (static kinds: [variance]);
