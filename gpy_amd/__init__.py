@@ -9,14 +9,14 @@ HIP kernel in gpy_amd/csrc.  No PyTorch, no NumPy fallback: without an MI355X th
 from . import _lib
 from ._lib import MI355GPError, build, device_count
 from .inference import ExactGaussianInference, ExactStudentTInference
-from .kern import (OU, RBF, Add, Prod, Bias, Coregionalize, ExpQuad, Exponential, Linear, Matern32, Matern52, RatQuad, Stationary,
-                   StdPeriodic, White)
+from .kern import (OU, RBF, Add, Prod, Bias, Coregionalize, ExpQuad, Exponential, Linear, Matern32, Matern52, MLP, Poly, RatQuad,
+                   Stationary, StdPeriodic, White)
 from .likelihoods import Gaussian, HeteroscedasticGaussian, MixedNoise
 from .models import GP, GPCoregionalizedRegression, GPHeteroscedasticRegression, GPRegression
 from .posterior import PosteriorExact, StudentTPosterior
 from .sparse import SparseGP, SparseGPRegression, VarDTC
 
-__all__ = ["RBF", "OU", "ExpQuad", "HeteroscedasticGaussian", "StudentTPosterior", "Matern52", "Matern32", "Exponential", "RatQuad", "StdPeriodic", "Coregionalize", "Linear", "MixedNoise", "Stationary", "White", "Bias", "Add", "Prod", "Gaussian", "ExactGaussianInference", "ExactStudentTInference",
+__all__ = ["RBF", "OU", "ExpQuad", "HeteroscedasticGaussian", "StudentTPosterior", "Matern52", "Matern32", "Exponential", "RatQuad", "StdPeriodic", "Coregionalize", "Linear", "MLP", "Poly", "MixedNoise", "Stationary", "White", "Bias", "Add", "Prod", "Gaussian", "ExactGaussianInference", "ExactStudentTInference",
            "PosteriorExact", "GP", "GPRegression", "GPHeteroscedasticRegression", "GPCoregionalizedRegression", "VarDTC", "SparseGP", "SparseGPRegression", "MI355GPError", "build", "device_count"]
 
 # GPy's import paths, so that `import gpy_amd as GPy` reads like the reference on this path:

@@ -463,7 +463,7 @@ static int coreg_check_points(const mi355gp_ctx* c, const double* Xn, int64_t M,
             if (int rc = coreg_check_index(Xn + p.kp.col, M, c->D, p.kp.ard, what)) return rc;
     return 0;
 }
-// a part whose diagonal depends on the point (Coregionalize, Linear): Kdiag of the expression is then no constant
+// a part whose diagonal depends on the point (Coregionalize, Linear, MLP, Poly): Kdiag of the expression is then no constant
 static bool has_point_diag(const mi355gp_ctx* c) {
     for (const auto& p : c->parts)
         if (p.diag_by_point()) return true;
@@ -471,7 +471,8 @@ static bool has_point_diag(const mi355gp_ctx* c) {
 }
 // Kdiag of the expression at each new point: kd[m] = sum over terms of the product of the factors' diagonals -- B[idx_m][idx_m]
 // of a Coregionalize factor (coregionalize.py:106-107), sum_q variance_q x_mq^2 over the active columns of a Linear factor
-// (linear.py:84-85), the variance of any other
+// (linear.py:84-85), var (2/pi) asin(p / (p + 1)) of an MLP factor (mlp.py:61-64), var (scale |x|^2 + bias)^order of a Poly factor
+// (poly.py:33-34), the variance of any other
 static std::vector<double> expression_kdiag_points(const mi355gp_ctx* c, const double* Xn, int64_t M) {
     std::vector<double> kd((size_t)M, 0.0);
     for (int64_t m = 0; m < M; ++m) {
@@ -490,6 +491,10 @@ static std::vector<double> expression_kdiag_points(const mi355gp_ctx* c, const d
                         d += p.theta[p.kp.ard ? a : 0] * x * x;
                     }
                     v *= d;
+                } else if (p.mlp()) {
+                    v *= mlp_kdiag(p, Xn + m * c->D);
+                } else if (p.poly()) {
+                    v *= poly_kdiag(p, Xn + m * c->D);
                 } else {
                     v *= p.kp.variance;
                 }
@@ -520,7 +525,7 @@ static int prepare_parts(mi355gp_ctx* c, int nparts, const mi355gp_part* parts) 
     }
     for (int i = 0; i < nparts; ++i) {
         mi355gp_ctx::Part& p = c->parts[(size_t)i];
-        if (int rc = parse_part(parts[i], c->D, KS_STATIONARY | KS_STATIC | KS_EXT | KS_COREG | KS_LINEAR, "exact-GP path", &p)) return rc;
+        if (int rc = parse_part(parts[i], c->D, KS_STATIONARY | KS_STATIC | KS_EXT | KS_COREG | KS_LINEAR | KS_DOT, "exact-GP path", &p)) return rc;
         if (p.coreg()) {
             const int col = p.kp.col;
             if (c->hIdxCol != col) {                     // the training indices of this column, validated once per upload
@@ -602,7 +607,7 @@ int mi355gp_exact_studentt_sum(mi355gp_ctx* c, int nparts, const mi355gp_part* p
 int mi355gp_exact_inference(mi355gp_ctx* c, int kind, int ard, const double* theta, const double* noise,
                             int64_t noise_len, double jitter, double extra_jitter, double* out_scalars,
                             double* alpha_out, double* dtheta_out, double* diag_dLdK_out, double* stage_ms) {
-    if (int rc = check_kind(kind, KS_STATIONARY | KS_EXT | KS_LINEAR, "mi355gp_exact_inference")) return rc;
+    if (int rc = check_kind(kind, KS_STATIONARY | KS_EXT | KS_LINEAR | KS_DOT, "mi355gp_exact_inference")) return rc;
     const mi355gp_part part{kind, ard, 0, nullptr, theta};
     return mi355gp_exact_inference_sum(c, 1, &part, noise, noise_len, jitter, extra_jitter, out_scalars, alpha_out,
                                        dtheta_out, diag_dLdK_out, stage_ms);
@@ -698,7 +703,7 @@ int mi355gp_kern_K(int device, int kind, int ard, const double* theta, const dou
     if (sym) M = N;
     ARG_CHECK(M > 0, "mi355gp_kern_K: M must be positive");
     StatelessPart pt;
-    if (int rc = pt.load(kind, ard, theta, D, KS_STATIONARY | KS_EXT | KS_COREG | KS_LINEAR, "mi355gp_kern_K", X, N, X2, M)) return rc;
+    if (int rc = pt.load(kind, ard, theta, D, KS_STATIONARY | KS_EXT | KS_COREG | KS_LINEAR | KS_DOT, "mi355gp_kern_K", X, N, X2, M)) return rc;
     PointSet x1, x2;
     if (int rc = pt.scaled(x1, X, N)) return rc;
     if (!sym)
@@ -718,6 +723,12 @@ int mi355gp_kern_Kdiag(int kind, const double* theta, int64_t N, double* out) {
                           "x_q^2, linear.py:84-85) and this entry point takes no X");
         return -1;
     }
+    if (kind_in(kind, KS_DOT)) {
+        mi355gp_set_error("mi355gp_kern_Kdiag: the diagonal of a %s (kind %d) part depends on the points (%s) and this entry "
+                          "point takes no X", kind_name(kind), kind,
+                          kind == MI355GP_MLP ? "var (2/pi) asin(p / (p + 1)), mlp.py:61-64" : "var (scale |x|^2 + bias)^order, poly.py:33-34");
+        return -1;
+    }
     ARG_CHECK(kind_in(kind, KS_STATIONARY | KS_EXT) && theta && out && N >= 0, "mi355gp_kern_Kdiag: bad arguments");
     // stationary: K(x,x) = variance (stationary.py:170-173); StdPeriodic likewise (standard_periodic.py:105-109)
     for (int64_t i = 0; i < N; ++i) out[i] = theta[0];
@@ -735,7 +746,7 @@ int mi355gp_update_gradients_full(int device, int kind, int ard, const double* t
     if (sym) M = N;
     ARG_CHECK(kind != MI355GP_COREGIONALIZE || M > 0, "mi355gp_update_gradients_full: M must be positive");
     StatelessPart pt;
-    if (int rc = pt.load(kind, ard, theta, D, KS_STATIONARY | KS_EXT | KS_COREG | KS_LINEAR, "mi355gp_update_gradients_full", X, N, X2, M))
+    if (int rc = pt.load(kind, ard, theta, D, KS_STATIONARY | KS_EXT | KS_COREG | KS_LINEAR | KS_DOT, "mi355gp_update_gradients_full", X, N, X2, M))
         return rc;
     PointSet x1, x2;
     if (int rc = pt.scaled(x1, X, N)) return rc;
@@ -776,8 +787,12 @@ int mi355gp_gradients_X(int device, int kind, int ard, const double* theta, cons
                         int64_t N, const double* X2, int64_t M, int D, double* out) {
     ARG_CHECK(dL_dK && X && out && N > 0 && D > 0, "mi355gp_gradients_X: bad arguments");
     HIP_CHECK(hipSetDevice(device));
+    if (kind == MI355GP_POLY) {
+        mi355gp_set_error("mi355gp_gradients_X: Poly (kind 11) has no gradients_X (the reference raises NotImplementedError, poly.py:45-46)");
+        return -1;
+    }
     StatelessPart pt;
-    if (int rc = pt.load(kind, ard, theta, D, KS_STATIONARY | KS_EXT | KS_LINEAR, "mi355gp_gradients_X", nullptr, 0, nullptr, 0)) return rc;
+    if (int rc = pt.load(kind, ard, theta, D, KS_STATIONARY | KS_EXT | KS_LINEAR | 1u << MI355GP_MLP, "mi355gp_gradients_X", nullptr, 0, nullptr, 0)) return rc;
     const bool sym = (X2 == nullptr);
     if (sym) { M = N; X2 = X; }
     ARG_CHECK(M > 0, "mi355gp_gradients_X: M must be positive");
@@ -827,6 +842,10 @@ int mi355gp_gradients_X(int device, int kind, int ard, const double* theta, cons
     std::vector<double> HX((size_t)N * (D + 1));
     HIP_CHECK(hipMemcpy(HX.data(), dHX, sizeof(double) * HX.size(), hipMemcpyDeviceToHost));
     HIP_CHECK(hipGetLastError());
+    if (pt.mlp()) {                                          // H = c (mlp.py:105; X2 == NULL: from dL_dK + dL_dK^T, i.e. c + c^T, :124-127)
+        gradx_mlp(X, N, D, pt.inv_ls, pt.kp.bias, HX.data(), [&](long i, int q, double g) { out[i * D + q] = g; });
+        return 0;
+    }
     gradx_stationary(X, N, D, pt.inv_ls, HX.data(), [&](long i, int q, double g) { out[i * D + q] = g; });
     return 0;
 }
@@ -998,7 +1017,7 @@ __global__ void k_fill_rows(double* __restrict__ G, long ld, long n, long m, con
 
 // GP.predictive_gradients (core/gp.py:418-474) for a sum of stationary (+ White / Bias) parts, everything N-sized on device:
 //   dmu[m][q][d]  = sum_n alpha[n][d] dK(x*_m, x_n)/dx*_mq                         (kern.gradients_X(alpha_d^T, X*, X), :448-451)
-//   dvar[m][q]    = dKdiag/dx* (= 0 for stationary kinds, stationary.py:360-361; 2 variance_q x*_mq for Linear) - 2 sum_n (Ky^-1 K(X, X*))[n][m] dK(x*_m, x_n)/dx*_mq   (:454,462-465)
+//   dvar[m][q]    = dKdiag/dx* (= 0 for stationary kinds, stationary.py:360-361; 2 variance_q x*_mq for Linear; mlp.py:133-147 for MLP) - 2 sum_n (Ky^-1 K(X, X*))[n][m] dK(x*_m, x_n)/dx*_mq   (:454,462-465)
 // with Ky^-1 K(X, X*) = X^T (X Kx), X = L^-1 resident from the inference call.  The reductions over n run as the column
 // reductions H^T [x~ | 1] of the sparse path's dL/dZ (H = weights * (dK/dr)/r, k_grad + k_colreduce_multi), per part.
 int mi355gp_predictive_gradients_sum(mi355gp_ctx* c, int nparts, const mi355gp_part* parts, const double* Xnew, int64_t M,
@@ -1010,6 +1029,8 @@ int mi355gp_predictive_gradients_sum(mi355gp_ctx* c, int nparts, const mi355gp_p
     if (int rc = prepare_parts(c, nparts, parts)) return rc;
     ARG_CHECK(!has_product(c->terms), "mi355gp_predictive_gradients: product kernels are not supported on the device");
     ARG_CHECK(!has_coreg(c), "mi355gp_predictive_gradients: Coregionalize (kind 8) parts are not supported on the device");
+    for (const auto& p : c->parts)
+        ARG_CHECK(!p.poly(), "mi355gp_predictive_gradients: Poly (kind 11) has no gradients_X (poly.py:45-49)");
     hipStream_t st = c->st;
     const long n = c->n, np = c->npad, D = c->D, Dy = c->Dy, mp = round_up(M, NB);
     c->have_kernel = true;
@@ -1078,6 +1099,17 @@ int mi355gp_predictive_gradients_sum(mi355gp_ctx* c, int nparts, const mi355gp_p
             launch_sum_splits(st, dCol, (long)hx, ns, 0, dHX);
             HIP_CHECK(hipMemcpyAsync(HX.data(), dHX, sizeof(double) * hx, hipMemcpyDeviceToHost, st));
             HIP_CHECK(hipStreamSynchronize(st));
+            if (pt.mlp()) {
+                // H = c of the weights (k_grad_dot); dK(x*_m, x_n)/dx*_m from H^T [x~ | 1] (mlp.py:124-130, gradx_mlp)
+                gradx_mlp(Xnew, M, (int)D, pt.inv_ls, pt.kp.bias, HX.data(), add);
+                if (is_var)                                                      // dKdiag/dx*_mq = 2 cd_m w_q x*_mq (mlp.py:133-147)
+                    for (long m = 0; m < M; ++m) {
+                        const double cd = mlp_dkdiag_factor(pt, Xnew + m * D);
+                        for (size_t a = 0; a < pt.dims.size(); ++a)
+                            dvar_out[m * D + pt.dims[a]] += 2.0 * cd * pt.theta[1 + (pt.kp.ard ? a : 0)] * Xnew[m * D + pt.dims[a]];
+                    }
+                continue;
+            }
             gradx_stationary(Xnew, M, (int)D, pt.inv_ls, HX.data(), add);       // (il = 0 outside active_dims)
         }
     }
@@ -1134,7 +1166,7 @@ int mi355gp_covariance_between_points(mi355gp_ctx* c, int nparts, const mi355gp_
 
 int mi355gp_predict(mi355gp_ctx* c, int kind, int ard, const double* theta, const double* Xnew, int64_t M,
                     double* mu_out, double* var_out, int full_cov) {
-    if (int rc = check_kind(kind, KS_STATIONARY | KS_EXT | KS_LINEAR, "mi355gp_predict")) return rc;
+    if (int rc = check_kind(kind, KS_STATIONARY | KS_EXT | KS_LINEAR | KS_DOT, "mi355gp_predict")) return rc;
     const mi355gp_part part{kind, ard, 0, nullptr, theta};
     return mi355gp_predict_sum(c, 1, &part, Xnew, M, mu_out, var_out, full_cov);
 }

@@ -217,10 +217,11 @@ struct KernParams {
     int D;
     double variance;
     // kinds 6 / 7 only (the kernels of the other kinds never read them)
-    double power = 0.0;               // RatQuad: alpha
+    double power = 0.0;               // RatQuad: alpha; Poly: order
     const double* pw = nullptr;       // StdPeriodic, device [2 D]: pi / T_q, then 1 / l_q (0 outside the active dimensions)
                                       // Coregionalize, device [P x P]: B (row-major; P = ard)
     int col = 0;                      // Coregionalize only: the input row of Xt that holds the (unscaled) output index
+    double bias = 0.0;              // MLP: bias_variance; Poly: bias (Poly's order travels in `power`)
 };
 // Xt: scaled, transposed inputs [D][ldx] (x_q / l_q); builds lower tiles of Ky = K + diag(noise + jit) into A
 // (npad x npad); rows/cols >= n get the identity.

@@ -333,10 +333,24 @@ static void launch_grad_lin(hipStream_t st, bool fused, KernParams kp, const dou
                             long ld2, long m, const double* G, long ldg, const double* alpha, int Dy, long ntiles, int ntc,
                             double* partials, double* Hout, long ldh, const double* aa_scale, const double* Mul, long ldm);
 
+// MLP / Poly (kinds 10 / 11): at the end of this file as well
+static inline bool dot_kind(int kind) { return kind == MI355GP_MLP || kind == MI355GP_POLY; }
+static void launch_kbuild_dot(hipStream_t st, bool sym, KernParams kp, const double* Xt1, long ld1, long n, const double* Xt2,
+                              long ld2, long m, double* out, long ldo, long nrows_out, const double* noise, long noise_len,
+                              double jit, int lower_only, int add_diag, int ntc, int nblocks, int accumulate, const double* mul);
+static void launch_grad_dot(hipStream_t st, bool fused, KernParams kp, const double* Xt1, long ld1, long n, const double* Xt2,
+                            long ld2, long m, const double* G, long ldg, const double* alpha, int Dy, long ntiles, int ntc,
+                            double* partials, double* Hout, long ldh, const double* aa_scale, const double* Mul, long ldm);
+
 void launch_kbuild_sym(hipStream_t st, KernParams kp, const double* Xt, long ldx, long n, long npad, double* A,
                        const double* noise, long noise_len, double jit, int lower_only, int add_diag, int accumulate,
                        const double* mul) {
     const int nt = (int)(npad / KT);
+    if (dot_kind(kp.kind)) {
+        launch_kbuild_dot(st, true, kp, Xt, ldx, n, Xt, ldx, n, A, npad, npad, noise, noise_len, jit, lower_only, add_diag, nt,
+                          nt * nt, accumulate, mul);
+        return;
+    }
     if (kp.kind == MI355GP_LINEAR) {
         launch_kbuild_lin(st, true, kp, Xt, ldx, n, Xt, ldx, n, A, npad, npad, noise, noise_len, jit, lower_only, add_diag, nt,
                           nt * nt, accumulate, mul);
@@ -359,6 +373,11 @@ void launch_kbuild_sym(hipStream_t st, KernParams kp, const double* Xt, long ldx
 void launch_kbuild_cross(hipStream_t st, KernParams kp, const double* Xt1, long ld1, long n, const double* Xt2,
                          long ld2, long m, double* Kout, long ldk, int accumulate, int diag_same, const double* mul) {
     const int ntr = (int)((n + KT - 1) / KT), ntc = (int)((m + KT - 1) / KT);
+    if (dot_kind(kp.kind)) {                                               // (the diagonal is what the formula gives at i == j)
+        launch_kbuild_dot(st, false, kp, Xt1, ld1, n, Xt2, ld2, m, Kout, ldk, n, nullptr, 0, 0.0, 0, 0, ntc, ntr * ntc, accumulate,
+                          mul);
+        return;
+    }
     if (kp.kind == MI355GP_LINEAR) {                                       // (the diagonal is whatever the dot product gives)
         launch_kbuild_lin(st, false, kp, Xt1, ld1, n, Xt2, ld2, m, Kout, ldk, n, nullptr, 0, 0.0, 0, 0, ntc, ntr * ntc, accumulate,
                           mul);
@@ -553,6 +572,11 @@ void launch_grad_fused(hipStream_t st, KernParams kp, const double* Xt, long ldx
     const long nt = (n + KT - 1) / KT;
     const long ntiles = nt * (nt + 1) / 2;
     const int nb = pick_grad_blocks(ntiles);
+    if (dot_kind(kp.kind)) {
+        launch_grad_dot(st, true, kp, Xt, ldx, n, Xt, ldx, n, W, ldw, alpha, Dy, ntiles, (int)nt, partials, nullptr, 0, aa_scale,
+                        Mul, ldm);
+        return;
+    }
     if (kp.kind == MI355GP_LINEAR) {
         launch_grad_lin(st, true, kp, Xt, ldx, n, Xt, ldx, n, W, ldw, alpha, Dy, ntiles, (int)nt, partials, nullptr, 0, aa_scale,
                         Mul, ldm);
@@ -949,6 +973,12 @@ void launch_grad_generic(hipStream_t st, KernParams kp, const double* Xt1, long 
     const long ntr = (n + KT - 1) / KT, ntc = (m + KT - 1) / KT;
     const long ntiles = ntr * ntc;
     const int nb = pick_grad_blocks(ntiles);
+    if (dot_kind(kp.kind)) {
+        if (rk.Y) return;                                  // (the sparse path's rank term: it has neither kind)
+        launch_grad_dot(st, false, kp, Xt1, ld1, n, Xt2, ld2, m, G, ldg, nullptr, 0, ntiles, (int)ntc, partials, Hout, ldh,
+                        nullptr, nullptr, 0);
+        return;
+    }
     if (kp.kind == MI355GP_LINEAR) {
         if (rk.Y) return;                                  // (the sparse path's rank term: it does not have the kind)
         launch_grad_lin(st, false, kp, Xt1, ld1, n, Xt2, ld2, m, G, ldg, nullptr, 0, ntiles, (int)ntc, partials, Hout, ldh,
@@ -2288,5 +2318,332 @@ static void launch_grad_lin(hipStream_t st, bool fused, KernParams kp, const dou
         else
             hipLaunchKernelGGL((k_grad_lin<false>), g, b, 0, st, kp, Xt1, ld1, n, Xt2, ld2, m, G, ldg, nullptr, 0, q_off, ntiles, ntc, pa,
                                h, ldh, nullptr, Mul, ldm);
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
+// MLP (kind 10, mlp.py:48-147) and Poly (kind 11, poly.py:15-49): functions of the three numbers x.x', x.x and x'.x' of a pair.
+// Inputs arrive scaled by sqrt(weight_variance_q) (MLP) / sqrt(scale) (Poly) on the active dimensions, 0 elsewhere, so with
+// d_ij = sum_q x~_iq x~_jq, n_i = sum_q x~_iq^2 (both from the same staged slabs, kp.bias = b resp. c0):
+//   MLP   s = d + b, p_i = n_i + b:  K = var (2/pi) asin(s / sqrt((p_i + 1)(p_j + 1)))
+//   Poly  A = d + c0:                K = var A^order (kp.power; C pow for a negative A)
+// Kernels of their own again: every other instantiation keeps its code.  The sums over q run in the same order for (i, j) and
+// (j, i), fma(a, b, c) = fma(b, a, c) and (p_i + 1)(p_j + 1) commutes: K(X, X) is bitwise symmetric.  n_i is the same fma chain
+// as d_ii, so at i == j the element is the formula at s = p_i: var (2/pi) asin(p / sqrt((p + 1)^2)) = Kdiag.
+
+// ni[a] += sum_q xi[q][ty*4+a]^2, nj[b] += sum_q xj[q][tx*4+b]^2
+__device__ __forceinline__ void accum_norms(const double* si, const double* sj, int qc, int ty, int tx, double (&ni)[4],
+                                            double (&nj)[4]) {
+    for (int q = 0; q < qc; ++q) {
+        const d4 xi = *reinterpret_cast<const d4*>(si + q * KT + ty * 4);
+        const d4 xj = ld_xj(sj, q, tx);
+#pragma unroll
+        for (int a = 0; a < 4; ++a) {
+            ni[a] = fma(xi[a], xi[a], ni[a]);
+            nj[a] = fma(xj[a], xj[a], nj[a]);
+        }
+    }
+}
+
+#define TWO_OVER_PI 0.63661977236758134308
+// the asin argument is below 1 in exact arithmetic (Cauchy-Schwarz on (x~, sqrt b)); the clamp only absorbs a last-bit excess
+__device__ __forceinline__ double mlp_k(double var, double s, double qi, double qj) {
+    const double t = s / sqrt(qi * qj);
+    return var * TWO_OVER_PI * asin(fmin(fmax(t, -1.0), 1.0));
+}
+
+// Covariance assembly of k_kbuild (same tiling, same output conventions).
+template <bool SYM, int KIND>
+__global__ __launch_bounds__(256) void k_kbuild_dot(KernParams kp, const double* __restrict__ Xt1, long ld1, long n,
+                                                    const double* __restrict__ Xt2, long ld2, long m,
+                                                    double* __restrict__ out, long ldo, long nrows_out,
+                                                    const double* __restrict__ noise, long noise_len, double jit,
+                                                    int lower_only, int add_diag, int ntc, int accumulate, const double* mul) {
+    __shared__ __attribute__((aligned(16))) double si[KDC * KT];
+    __shared__ __attribute__((aligned(16))) double sj[KDC * KTJ];
+    const int t = threadIdx.x, tx = t & 15, ty = t >> 4;
+    const long ti = blockIdx.x / ntc, tj = blockIdx.x % ntc;
+    if (SYM && lower_only && tj > ti) return;
+    const long i0 = ti * KT, j0 = tj * KT;
+    double s[4][4], ni[4], nj[4];
+#pragma unroll
+    for (int a = 0; a < 4; ++a) {
+        ni[a] = nj[a] = 0.0;
+#pragma unroll
+        for (int b = 0; b < 4; ++b) s[a][b] = 0.0;
+    }
+    if ((i0 < n) && (j0 < m)) {
+        for (int q0 = 0; q0 < kp.D; q0 += KDC) {
+            const int qc = (kp.D - q0 < KDC) ? (kp.D - q0) : KDC;
+            __syncthreads();
+            stage_x(Xt1, ld1, i0, q0, qc, si, t);
+            stage_xj(Xt2, ld2, j0, q0, qc, sj, t);
+            __syncthreads();
+            accum_dot(si, sj, qc, ty, tx, s);
+            if (KIND == MI355GP_MLP) accum_norms(si, sj, qc, ty, tx, ni, nj);
+        }
+    }
+#pragma unroll
+    for (int a = 0; a < 4; ++a) {
+        const long i = i0 + ty * 4 + a;
+        double v[4];
+#pragma unroll
+        for (int b = 0; b < 4; ++b) {
+            const long j = j0 + tx * 4 + b;
+            if (i < n && j < m) {
+                const double sb = s[a][b] + kp.bias;
+                if (KIND == MI355GP_MLP) v[b] = mlp_k(kp.variance, sb, ni[a] + kp.bias + 1.0, nj[b] + kp.bias + 1.0);
+                else v[b] = kp.variance * pow(sb, kp.power);
+            } else {
+                v[b] = (SYM && i == j && !accumulate) ? 1.0 : 0.0;
+            }
+        }
+        if (SYM) {
+            if (i < nrows_out) {
+                d4* p = reinterpret_cast<d4*>(out + i * ldo + j0 + tx * 4);
+                d4 o = (d4){v[0], v[1], v[2], v[3]};
+                if (mul) o *= *reinterpret_cast<const d4*>(mul + i * ldo + j0 + tx * 4);
+                if (add_diag && i < n) {
+                    const long d = i - (j0 + tx * 4);
+                    if (d >= 0 && d < 4) o[d] += noise[noise_len > 1 ? i : 0] + jit;
+                }
+                if (accumulate) o += *p;
+                *p = o;
+            }
+        } else if (i < n) {
+#pragma unroll
+            for (int b = 0; b < 4; ++b) {
+                const long j = j0 + tx * 4 + b;
+                if (j < m) {
+                    const double w = mul ? v[b] * mul[i * ldo + j] : v[b];
+                    out[i * ldo + j] = accumulate ? out[i * ldo + j] + w : w;
+                }
+            }
+        }
+    }
+}
+
+static void launch_kbuild_dot(hipStream_t st, bool sym, KernParams kp, const double* Xt1, long ld1, long n, const double* Xt2,
+                              long ld2, long m, double* out, long ldo, long nrows_out, const double* noise, long noise_len,
+                              double jit, int lower_only, int add_diag, int ntc, int nblocks, int accumulate, const double* mul) {
+    const dim3 g((unsigned)nblocks), b(256);
+#define KBUILD_DOT(S, K)                                                                                                        \
+    hipLaunchKernelGGL((k_kbuild_dot<S, K>), g, b, 0, st, kp, Xt1, ld1, n, Xt2, ld2, m, out, ldo, nrows_out, noise, noise_len, jit, \
+                       lower_only, add_diag, ntc, accumulate, mul)
+    if (kp.kind == MI355GP_MLP) {
+        if (sym) KBUILD_DOT(true, MI355GP_MLP);
+        else KBUILD_DOT(false, MI355GP_MLP);
+    } else {
+        if (sym) KBUILD_DOT(true, MI355GP_POLY);
+        else KBUILD_DOT(false, MI355GP_POLY);
+    }
+#undef KBUILD_DOT
+}
+
+// Gradient pass of k_grad for the two kinds, one launch per group of 32 dimensions (q_off; one launch unless MLP with ard).
+// Record [GP_STRIDE] per block, g = the weight of the element (below):
+//   MLP   c = var (2/pi) g / sqrt((p_i + 1)(p_j + 1) - s^2)                                                  (mlp.py:105)
+//         [0] sum g K        [1] sum c (1 - s (1/(p_i+1) + 1/(p_j+1)) / 2)  = d/d bias_variance              (:122)
+//         ARD  [2 + q] sum c (x~_iq x~_jq - s (x~_iq^2/(p_i+1) + x~_jq^2/(p_j+1)) / 2)  = w_q d/dw_q           (:107-120)
+//         else [2]     sum c (d_ij - s (n_i/(p_i+1) + n_j/(p_j+1)) / 2)                 = w d/dw              (:121)
+//   Poly  h = g var order A^(order-1):  [0] sum g K   [1] sum h = d/d bias   [2] sum h d_ij = scale d/d scale (poly.py:36-42)
+// FUSED: g = 0.5 (sc alpha alpha^T - Dy W) over the lower triangle, off-diagonal weights doubled (every summand above is
+// symmetric in (i, j) when both sides are the same points); else g = G (n x m).  g is multiplied by Mul (product terms).
+// Generic form with Hout: c (MLP) is written there -- the weights of gradients_X (mlp.py:124-130, gradx_mlp in parts.h).
+// Every sum runs in a fixed order: two evaluations give identical bits.
+template <bool FUSED, int KIND>
+__global__ __launch_bounds__(256) void k_grad_dot(KernParams kp, const double* __restrict__ Xt1, long ld1, long n,
+                                                  const double* __restrict__ Xt2, long ld2, long m,
+                                                  const double* __restrict__ G, long ldg,
+                                                  const double* __restrict__ alpha, int Dy, int q_off,
+                                                  long ntiles, int ntc, double* __restrict__ partials,
+                                                  double* __restrict__ Hout, long ldh, const double* __restrict__ aa_scale,
+                                                  const double* __restrict__ Mul, long ldm) {
+    constexpr bool MLP = KIND == MI355GP_MLP;
+    __shared__ __attribute__((aligned(16))) double si[KDC * KT];
+    __shared__ __attribute__((aligned(16))) double sj[KDC * KTJ];
+    __shared__ double red[256];
+    const int t = threadIdx.x, tx = t & 15, ty = t >> 4;
+    double a_var = 0.0, a_b = 0.0, a_w = 0.0;
+    double a_q[KDC];
+#pragma unroll
+    for (int q = 0; q < KDC; ++q) a_q[q] = 0.0;
+    const int qcnt = (MLP && kp.ard) ? ((kp.D - q_off < KDC) ? (kp.D - q_off) : KDC) : 0;
+    const double sc = (FUSED && aa_scale) ? aa_scale[0] : 1.0;
+    const double coef = MLP ? kp.variance * TWO_OVER_PI : kp.variance * kp.power;
+
+    for (long tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+        long ti, tj;
+        if (FUSED) {   // lower-triangular enumeration
+            ti = (long)((sqrt(8.0 * (double)tile + 1.0) - 1.0) * 0.5);
+            while (ti * (ti + 1) / 2 > tile) --ti;
+            while ((ti + 1) * (ti + 2) / 2 <= tile) ++ti;
+            tj = tile - ti * (ti + 1) / 2;
+        } else {
+            ti = tile / ntc;
+            tj = tile - ti * ntc;
+        }
+        const long i0 = ti * KT, j0 = tj * KT;
+        double s[4][4], ni[4], nj[4];
+#pragma unroll
+        for (int a = 0; a < 4; ++a) {
+            ni[a] = nj[a] = 0.0;
+#pragma unroll
+            for (int b = 0; b < 4; ++b) s[a][b] = 0.0;
+        }
+        int last_q0 = -1;
+        for (int q0 = 0; q0 < kp.D; q0 += KDC) {
+            const int qc = (kp.D - q0 < KDC) ? (kp.D - q0) : KDC;
+            __syncthreads();
+            stage_x(Xt1, ld1, i0, q0, qc, si, t);
+            stage_xj(Xt2, ld2, j0, q0, qc, sj, t);
+            __syncthreads();
+            accum_dot(si, sj, qc, ty, tx, s);
+            if (MLP) accum_norms(si, sj, qc, ty, tx, ni, nj);
+            last_q0 = q0;
+        }
+        // MLP: qi = p_i + 1, hi = 1 / (2 (p_i + 1)); padded rows have x~ = 0, so every quantity below stays finite there
+        double qi[4], qj[4], hi[4], hj[4];
+        if (MLP) {
+#pragma unroll
+            for (int a = 0; a < 4; ++a) {
+                qi[a] = ni[a] + kp.bias + 1.0;
+                qj[a] = nj[a] + kp.bias + 1.0;
+                hi[a] = 0.5 / qi[a];
+                hj[a] = 0.5 / qj[a];
+            }
+        }
+        double cw[4][4];            // MLP: c
+        double rsum[4], csum[4];    // MLP with ard: row / column sums of c s over this thread's 4 x 4 elements
+#pragma unroll
+        for (int a = 0; a < 4; ++a) rsum[a] = csum[a] = 0.0;
+#pragma unroll
+        for (int a = 0; a < 4; ++a) {
+            const long i = i0 + ty * 4 + a;
+#pragma unroll
+            for (int b = 0; b < 4; ++b) {
+                const long j = j0 + tx * 4 + b;
+                double g = 0.0;
+                const bool in = i < n && j < m;
+                if (in) {
+                    if (FUSED) {
+                        if (j <= i) {
+                            double aa = 0.0;
+                            for (int d = 0; d < Dy; ++d) aa = fma(alpha[i * Dy + d], alpha[j * Dy + d], aa);
+                            g = 0.5 * (sc * aa - (double)Dy * G[i * ldg + j]);
+                            if (j < i) g *= 2.0;
+                        }
+                    } else {
+                        g = G[i * ldg + j];
+                    }
+                    if (Mul) g *= Mul[i * ldm + j];
+                }
+                const double sb = s[a][b] + kp.bias;
+                if (MLP) {
+                    const double prod = qi[a] * qj[b];
+                    const double c = coef * g / sqrt(fma(-sb, sb, prod));
+                    const double cs = c * sb;
+                    a_var = fma(g, mlp_k(kp.variance, sb, qi[a], qj[b]), a_var);
+                    a_b += fma(-cs, hi[a] + hj[b], c);
+                    if (qcnt > 0) {
+                        rsum[a] += cs;
+                        csum[b] += cs;
+                    } else {
+                        a_w += fma(-cs, ni[a] * hi[a] + nj[b] * hj[b], c * s[a][b]);
+                    }
+                    cw[a][b] = c;
+                    if (!FUSED && Hout && in) Hout[i * ldh + j] = c;
+                } else {
+                    const double pm1 = in ? pow(sb, kp.power - 1.0) : 0.0;
+                    const double h = coef * g * pm1;
+                    a_var = fma(g, kp.variance * pm1 * sb, a_var);
+                    a_b += h;
+                    a_w = fma(h, s[a][b], a_w);
+                }
+            }
+        }
+        if (MLP && qcnt > 0) {
+#pragma unroll
+            for (int a = 0; a < 4; ++a) {
+                rsum[a] *= hi[a];
+                csum[a] *= hj[a];
+            }
+            if (last_q0 != q_off) {   // D > 32: bring the dims of this launch back into LDS
+                __syncthreads();
+                stage_x(Xt1, ld1, i0, q_off, qcnt, si, t);
+                stage_xj(Xt2, ld2, j0, q_off, qcnt, sj, t);
+                __syncthreads();
+            }
+#pragma unroll
+            for (int q = 0; q < KDC; ++q) {
+                if (q < qcnt) {
+                    const d4 xi = *reinterpret_cast<const d4*>(si + q * KT + ty * 4);
+                    const d4 xj = ld_xj(sj, q, tx);
+                    double s1 = 0.0, s2 = 0.0;
+#pragma unroll
+                    for (int a = 0; a < 4; ++a) {
+                        double r = 0.0;
+#pragma unroll
+                        for (int b = 0; b < 4; ++b) r = fma(cw[a][b], xj[b], r);
+                        s1 = fma(xi[a], r, s1);
+                        s2 = fma(rsum[a], xi[a] * xi[a], s2);
+                        s2 = fma(csum[a], xj[a] * xj[a], s2);
+                    }
+                    a_q[q] += s1 - s2;
+                }
+            }
+        }
+    }
+    // deterministic block reduction -> partials[blockIdx][...]
+    double* out = partials + (long)blockIdx.x * GP_STRIDE;
+    auto block_sum = [&](double v) -> double {
+        __syncthreads();
+        red[t] = v;
+        __syncthreads();
+        for (int s = 128; s > 0; s >>= 1) {
+            if (t < s) red[t] += red[t + s];
+            __syncthreads();
+        }
+        return red[0];
+    };
+    const double sv = block_sum(a_var);
+    if (t == 0) out[0] = sv;
+    const double sb = block_sum(a_b);
+    if (t == 0) out[1] = sb;
+    if (qcnt == 0) {
+        const double sw = block_sum(a_w);
+        if (t == 0) out[2] = sw;
+    }
+#pragma unroll
+    for (int q = 0; q < KDC; ++q) {
+        if (q < qcnt) {
+            const double sq = block_sum(a_q[q]);
+            if (t == 0) out[2 + q] = sq;
+        }
+    }
+}
+
+static void launch_grad_dot(hipStream_t st, bool fused, KernParams kp, const double* Xt1, long ld1, long n, const double* Xt2,
+                            long ld2, long m, const double* G, long ldg, const double* alpha, int Dy, long ntiles, int ntc,
+                            double* partials, double* Hout, long ldh, const double* aa_scale, const double* Mul, long ldm) {
+    const int nb = pick_grad_blocks(ntiles);
+    const dim3 g((unsigned)nb), b(256);
+    const bool mlp = kp.kind == MI355GP_MLP, groups = mlp && kp.ard;
+    for (int q_off = 0, gidx = 0; q_off < kp.D; q_off += KDC, ++gidx) {
+        if (!groups && gidx > 0) break;
+        double* pa = partials + (long)gidx * nb * GP_STRIDE;
+        // Hout may alias G (in place): only the LAST group launch writes it
+        double* h = (!groups || q_off + KDC >= kp.D) ? Hout : nullptr;
+#define GRAD_DOT(F, K, AL, DY, HO, LH, AS)                                                                                       \
+    hipLaunchKernelGGL((k_grad_dot<F, K>), g, b, 0, st, kp, Xt1, ld1, n, Xt2, ld2, m, G, ldg, AL, DY, q_off, ntiles, ntc, pa, HO, LH, \
+                       AS, Mul, ldm)
+        if (mlp) {
+            if (fused) GRAD_DOT(true, MI355GP_MLP, alpha, Dy, nullptr, 0, aa_scale);
+            else GRAD_DOT(false, MI355GP_MLP, nullptr, 0, h, ldh, nullptr);
+        } else {
+            if (fused) GRAD_DOT(true, MI355GP_POLY, alpha, Dy, nullptr, 0, aa_scale);
+            else GRAD_DOT(false, MI355GP_POLY, nullptr, 0, nullptr, 0, nullptr);
+        }
+#undef GRAD_DOT
     }
 }

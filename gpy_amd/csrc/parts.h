@@ -22,12 +22,13 @@ enum : KindSet {
     KS_EXT = 1u << MI355GP_RATQUAD | 1u << MI355GP_STDPERIODIC,     // two reduction records per part (k_grad_ext)
     KS_COREG = 1u << MI355GP_COREGIONALIZE,
     KS_LINEAR = 1u << MI355GP_LINEAR,                               // exact path only; Kdiag depends on the point
+    KS_DOT = 1u << MI355GP_MLP | 1u << MI355GP_POLY,                // likewise: functions of x.x', x.x and x'.x' (k_kbuild_dot)
 };
 static inline bool kind_in(int kind, KindSet s) { return kind >= 0 && kind < 32 && ((s >> kind) & 1u); }
 static inline const char* kind_name(int kind) {
     static const char* const names[] = {"RBF", "Matern52", "Matern32", "Exponential", "White", "Bias", "RatQuad",
-                                        "StdPeriodic", "Coregionalize", "Linear"};
-    return kind_in(kind, KS_STATIONARY | KS_STATIC | KS_EXT | KS_COREG | KS_LINEAR) ? names[kind] : "unknown";
+                                        "StdPeriodic", "Coregionalize", "Linear", "MLP", "Poly"};
+    return kind_in(kind, KS_STATIONARY | KS_STATIC | KS_EXT | KS_COREG | KS_LINEAR | KS_DOT) ? names[kind] : "unknown";
 }
 
 #define PART_FAIL(...)                    \
@@ -66,7 +67,8 @@ struct PartSpec {
     std::vector<double> theta;      // exactly the kind's parameters, in theta order
     std::vector<double> inv_ls;     // length D: 1/l on active dimensions, 0 elsewhere (= the slicing of kern.py:112-117)
                                     // (StdPeriodic: 1 on active dimensions, Coregionalize: 1 on the index column -- unscaled;
-                                    // Linear: sqrt(variance_q), so that K = sum_q x~_iq x~_jq)
+                                    // Linear: sqrt(variance_q), so that K = sum_q x~_iq x~_jq; MLP: sqrt(weight_variance_q),
+                                    // Poly: sqrt(scale) -- the tile kernels see plain dot products)
     std::vector<double> pw;         // StdPeriodic: [pi / T_q (D) | 1 / l_q (D)]; Coregionalize: B (P x P); empty otherwise
     int term = 0;                   // term id of the C-ABI part: parts with the same non-zero id are multiplied (prod.py)
     int tix = 0;                    // index of its summand in the terms of group_terms
@@ -75,7 +77,10 @@ struct PartSpec {
     bool ext() const { return kind_in(kp.kind, KS_EXT); }
     bool coreg() const { return kp.kind == MI355GP_COREGIONALIZE; }
     bool linear() const { return kp.kind == MI355GP_LINEAR; }
-    bool diag_by_point() const { return coreg() || linear(); }   // Kdiag depends on the point: kp.variance is NOT the diagonal
+    bool mlp() const { return kp.kind == MI355GP_MLP; }
+    bool poly() const { return kp.kind == MI355GP_POLY; }
+    // Kdiag depends on the point: kp.variance is NOT the diagonal
+    bool diag_by_point() const { return coreg() || linear() || mlp() || poly(); }
 };
 
 // A part with its parameters on the device as well: inv_ls (D) and pw, uploaded together once per call by upload() (kp.pw ->
@@ -167,6 +172,26 @@ static inline int parse_part(const mi355gp_part& in, int D, KindSet accepted, co
             p->inv_ls[(size_t)p->dims[a]] = std::sqrt(v);
         }
         p->kp.ard = ard ? 1 : 0;                       // per-dimension reductions
+    } else if (kind == MI355GP_MLP) {                  // [variance, weight_variance (1 or n_active), bias_variance] (mlp.py:36-45)
+        const int nw = ard ? na : 1;
+        for (int a = 0; a < na; ++a) {
+            const double w = th[1 + (ard ? a : 0)];
+            if (int rc = positive(w, "weight_variance")) return rc;
+            p->inv_ls[(size_t)p->dims[a]] = std::sqrt(w);
+        }
+        p->kp.ard = ard ? 1 : 0;                       // per-dimension reductions
+        p->kp.bias = th[1 + nw];
+        if (int rc = positive(p->kp.bias, "bias_variance")) return rc;
+        nt = 2 + nw;
+    } else if (kind == MI355GP_POLY) {                 // [variance, scale, bias, order] (poly.py:15-23)
+        if (int rc = positive(th[1], "scale")) return rc;
+        if (int rc = positive(th[2], "bias")) return rc;
+        if (!(th[3] >= 1.0 && std::isfinite(th[3])))
+            PART_FAIL("%s: order %g of a Poly (kind %d) part must be at least 1 (poly.py:22)", where, th[3], kind);
+        for (int a = 0; a < na; ++a) p->inv_ls[(size_t)p->dims[a]] = std::sqrt(th[1]);
+        p->kp.bias = th[2];
+        p->kp.power = th[3];
+        nt = 4;
     } else if (!p->is_static()) {                      // stationary and RatQuad: [variance, lengthscale (1 or n_active)(, power)]
         const int nl = ard ? na : 1;
         for (int a = 0; a < na; ++a) {
@@ -201,6 +226,21 @@ static inline int part_dtheta(const PartSpec& p, const double* rec, const double
         else
             for (int a = 0; a < na; ++a) o[k++] = rec_at(rec, p.dims[a]) / th[a];
         return k;
+    }
+    if (p.mlp()) {                                     // mlp.py:98-123 from the record of k_grad_dot: [0] sum g K, [1] db,
+        o[k++] = rec[0] / th[0];                       // [2 + q] w_q dw_q (ARD) or [2] w dw
+        if (!p.kp.ard) o[k++] = rec[2] / th[1];
+        else
+            for (int a = 0; a < na; ++a) o[k++] = rec_at(rec, p.dims[a]) / th[1 + a];
+        o[k++] = rec[1];
+        return k;
+    }
+    if (p.poly()) {                                    // poly.py:36-42: [0] sum g K, [1] sum h, [2] scale sum h x.x'; order: no parameter
+        o[0] = rec[0] / th[0];
+        o[1] = rec[2] / th[1];
+        o[2] = rec[1];
+        o[3] = 0.0;
+        return 4;
     }
     o[k++] = rec[0] / p.kp.variance;                   // sum g K / variance
     if (p.is_static()) return k;
@@ -379,4 +419,43 @@ template <class Put>
 static void gradx_linear(const std::vector<double>& il, long rows, int D, const double* HX, Put put) {
     for (long i = 0; i < rows; ++i)
         for (int q = 0; q < D; ++q) put(i, q, il[(size_t)q] * HX[i * D + q]);
+}
+// MLP (mlp.py:124-130): HX = H^T [x2~ | 1] (rows x (D + 1)) with H = c, x the unscaled host points (rows x D), il_q =
+// sqrt(weight_variance_q), b = bias_variance.  The second weight sum_j c_ij s_ij / (p_i + 1) needs no pass of its own:
+// s_ij = x~_i . x2~_j + b is linear in x2~_j, so sum_j c_ij s_ij = x~_i . HX[i][0..D) + b HX[i][D].
+//   put(i, q, il_q HX[i][q] - il_q^2 x_iq (x~_i . HX_i + b HX[i][D]) / (p_i + 1))
+template <class Put>
+static void gradx_mlp(const double* x, long rows, int D, const std::vector<double>& il, double b, const double* HX, Put put) {
+    for (long i = 0; i < rows; ++i) {
+        const double* h = HX + i * (D + 1);
+        double p = b, cs = b * h[D];
+        for (int q = 0; q < D; ++q) {
+            const double xs = x[i * D + q] * il[(size_t)q];
+            p += xs * xs;
+            cs += xs * h[q];
+        }
+        const double r = cs / (p + 1.0);
+        for (int q = 0; q < D; ++q) put(i, q, il[(size_t)q] * (h[q] - il[(size_t)q] * x[i * D + q] * r));
+    }
+}
+// Kdiag of an MLP part at one point and its derivative factor (mlp.py:61-64,133-147): p = sum_q w_q x_q^2 + b over the active
+// columns; Kdiag = var (2/pi) asin(p / (p + 1)), dKdiag/dx_q = 2 cd w_q x_q with cd = var (2/pi) / (sqrt(1 - (p/(p+1))^2) (p+1)^2)
+static inline double mlp_point_p(const PartSpec& p, const double* x) {
+    double s = p.kp.bias;
+    for (size_t a = 0; a < p.dims.size(); ++a) s += p.theta[1 + (p.kp.ard ? a : 0)] * x[p.dims[a]] * x[p.dims[a]];
+    return s;
+}
+static inline double mlp_kdiag(const PartSpec& p, const double* x) {
+    const double s = mlp_point_p(p, x);
+    return p.kp.variance * M_2_PI * std::asin(s / (s + 1.0));
+}
+static inline double mlp_dkdiag_factor(const PartSpec& p, const double* x) {
+    const double s = mlp_point_p(p, x), t = s / (s + 1.0);
+    return p.kp.variance * M_2_PI / (std::sqrt(1.0 - t * t) * (s + 1.0) * (s + 1.0));
+}
+// Kdiag of a Poly part at one point (poly.py:33-34: the diagonal of K): var (scale |x|^2 + bias)^order
+static inline double poly_kdiag(const PartSpec& p, const double* x) {
+    double d = 0.0;
+    for (size_t a = 0; a < p.dims.size(); ++a) d += x[p.dims[a]] * x[p.dims[a]];
+    return p.kp.variance * std::pow(p.theta[1] * d + p.kp.bias, p.kp.power);
 }

@@ -70,7 +70,9 @@ class _DeviceState(object):
     def predictive_gradients(self, kern, Xnew, want_var=True):
         """(dmu (M x D x Dy), dvar (M x D)) -- reference `core/gp.py:418-474`; raises NotImplementedError for kernel
         expressions the device entry does not take (products), which the caller then evaluates on the host."""
-        from .kern import Prod
+        from .kern import Poly, Prod
+        if any(isinstance(k, Poly) for k in (kern.leaves() if isinstance(kern, CombinationKernel) else [kern])):
+            raise NotImplementedError("Poly has no gradients_X (reference `poly.py:47-48`)")       # before any device work
         if isinstance(kern, CombinationKernel):
             if isinstance(kern, Prod) or any(isinstance(p, Prod) for p in kern.parts):
                 raise NotImplementedError("product kernels")
@@ -176,7 +178,7 @@ class ExactGaussianInference(object):
         if fused:
             if is_sum:
                 specs = kern.part_specs()
-                # jitchol's mean(diag(A)): with a Coregionalize or Linear part Kdiag depends on the point
+                # jitchol's mean(diag(A)): with a Coregionalize, Linear, MLP or Poly part Kdiag depends on the point
                 diagA = (kern.Kdiag(X) if diag_depends_on_point(kern) else kern.diag_variance()) + noise + 1e-8
 
                 def attempt(extra):
@@ -185,7 +187,7 @@ class ExactGaussianInference(object):
                                                       want_stage_ms=want_ms)
             else:
                 theta = kern._theta()
-                # (a lone Linear: theta[0] is a variance, not the diagonal)
+                # (a lone Linear / MLP / Poly: theta[0] is a variance, not the diagonal)
                 diagA = (kern.Kdiag(X) if diag_depends_on_point(kern) else float(theta[0])) + noise + 1e-8
 
                 def attempt(extra):

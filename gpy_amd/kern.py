@@ -663,10 +663,211 @@ class Linear(Parameterized):
     copy = Stationary.copy
 
 
+class MLP(Parameterized):
+    """Multi-layer-perceptron (arc-sine, neural-network) kernel (reference `GPy/kern/src/mlp.py:11-147`):
+
+        k(x, y) = variance (2/pi) asin( (w.x.y + b) / sqrt((w.x.x + b + 1)(w.y.y + b + 1)) ),  w.x.y = sum_q w_q x_q y_q
+
+    with `weight_variance` w (one value, or one per input dimension with `ARD`) and `bias_variance` b.  Not stationary: the
+    diagonal depends on the point.  On the device it is C-ABI kind `MI355GP_MLP`: a K-build and a gradient pass of their own
+    (`k_kbuild_dot`, `k_grad_dot`), alone, in `Add` and as a `Prod` factor; `gradients_X` is reduced on the device, `Kdiag` and
+    the diagonal gradients are O(N D) host arithmetic.  Parameters in link order: `variance`, `weight_variance`,
+    `bias_variance`."""
+    kind = "mlp"
+    _gpy_class = "GPy.kern.MLP"
+    _support_GPU = True
+
+    def __init__(self, input_dim, variance=1., weight_variance=1., bias_variance=1., ARD=False, active_dims=None, name="mlp",
+                 useGPU=True, device=0):
+        super(MLP, self).__init__(name)
+        self.input_dim = int(input_dim)
+        self.ARD = bool(ARD)
+        self.device = device
+        self.useGPU = True
+        if active_dims is None:
+            active_dims = np.arange(self.input_dim)
+        self.active_dims = np.atleast_1d(np.asarray(active_dims, dtype=np.int_))
+        assert self.active_dims.size == self.input_dim, "input_dim=%d does not match len(active_dims)=%d" % (
+            self.input_dim, self.active_dims.size)
+        if self.ARD:                                                   # mlp.py:39-42
+            wv = np.empty((self.input_dim,))
+            wv[:] = weight_variance
+            weight_variance = wv
+        else:
+            weight_variance = np.asarray(weight_variance, dtype=float)
+            assert weight_variance.size == 1, "Only one weight variance needed for non-ARD kernel"
+        self.variance = Param("variance", variance)
+        self.weight_variance = Param("weight_variance", weight_variance)
+        self.bias_variance = Param("bias_variance", bias_variance)
+        assert self.variance.size == 1 and self.bias_variance.size == 1
+        self.link_parameters(self.variance, self.weight_variance, self.bias_variance)
+        self._K_cache = _KCache(limit=3)
+
+    def _theta(self):
+        return np.concatenate([[float(self.variance.values[0])],
+                               np.asarray(self.weight_variance.values, dtype=np.float64).ravel(),
+                               [float(self.bias_variance.values[0])]])
+
+    # slicing, the cached K, the fused / device gradients and gradients_X are the stationary kernels' (they only go through
+    # kind / ARD / _theta)
+    __getstate__ = Stationary.__getstate__
+    _slice_X = Stationary._slice_X
+    K = Stationary.K
+    update_gradients_full = Stationary.update_gradients_full
+    gradients_X = Stationary.gradients_X
+
+    def _vwb(self):
+        th = self._theta()
+        return th[0], th[1:-1], th[-1]
+
+    def _comp_prod(self, X):
+        """p_i = sum_q w_q x_iq^2 + b over the active columns (reference `mlp.py:90-95`)"""
+        _, w, b = self._vwb()
+        return np.sum(w * np.square(self._slice_X(X)), -1) + b
+
+    def Kdiag(self, X):
+        """(reference `mlp.py:61-64`)"""
+        p = self._comp_prod(X)
+        return float(self.variance.values[0]) * (2. / np.pi) * np.arcsin(p / (p + 1.))
+
+    def _install_gradients(self, g):
+        self.variance.gradient = g[0]
+        self.weight_variance.gradient = np.asarray(g[1:-1], dtype=float).copy() if self.ARD else g[1]
+        self.bias_variance.gradient = g[-1]
+
+    def _diag_common(self, dL_dKdiag, X):
+        """cd_i of the diagonal forms (reference `mlp.py:133-139`)"""
+        v, _, _ = self._vwb()
+        p = self._comp_prod(X)
+        g = np.asarray(dL_dKdiag, dtype=float).ravel()
+        return v * (2. / np.pi) / (np.sqrt(1. - np.square(p / (p + 1.))) * np.square(p + 1.)) * g, p, g
+
+    def update_gradients_diag(self, dL_dKdiag, X):
+        """(reference `mlp.py:72-76,133-147`)"""
+        v, w, b = self._vwb()
+        cd, p, g = self._diag_common(dL_dKdiag, X)
+        self.variance.gradient = np.sum(g * self.Kdiag(X)) / v
+        if self.ARD:
+            self.weight_variance.gradient = np.dot(cd, np.square(self._slice_X(X)))
+        else:
+            self.weight_variance.gradient = np.sum(cd * (p - b)) / w[0]
+        self.bias_variance.gradient = np.sum(cd)
+
+    def gradients_X_diag(self, dL_dKdiag, X):
+        """(reference `mlp.py:86-88,147`): 2 cd_i w_q x_iq, zero outside the active dimensions"""
+        _, w, _ = self._vwb()
+        cd, _, _ = self._diag_common(dL_dKdiag, X)
+        X = np.asarray(X, dtype=float)
+        out = np.zeros(X.shape)
+        out[:, self.active_dims] = 2. * cd[:, None] * w * self._slice_X(X)
+        return out
+
+    def reset_gradients(self):
+        self.variance.gradient = 0.
+        self.weight_variance.gradient = np.zeros(self.input_dim) if self.ARD else 0.
+        self.bias_variance.gradient = 0.
+
+    def __add__(self, other):
+        return Add([self, other])
+
+    def __mul__(self, other):
+        return Prod([self, other])
+
+    def to_dict(self):
+        return {"class": self._gpy_class, "name": self.name, "input_dim": self.input_dim,
+                "active_dims": self.active_dims.tolist(), "variance": self.variance.values.tolist(),
+                "weight_variance": self.weight_variance.values.tolist(),
+                "bias_variance": self.bias_variance.values.tolist(), "ARD": self.ARD, "useGPU": True}
+
+    @classmethod
+    def from_dict(cls, d):
+        d = dict(d)
+        d.pop("class", None)
+        d.pop("useGPU", None)
+        return cls(**d)
+
+    copy = Stationary.copy
+
+
+class Poly(Parameterized):
+    """Polynomial kernel k(x, y) = variance (scale x.y + bias)^order (reference `GPy/kern/src/poly.py:10-49`); `order` (a
+    float >= 1) is fixed, not a parameter.  C-ABI kind `MI355GP_POLY`, evaluated by the same device kernels as `MLP`, alone,
+    in `Add` and as a `Prod` factor.  As in the reference, `gradients_X`, `gradients_X_diag` and `update_gradients_diag` raise
+    `NotImplementedError` (`:45-49`), so a model whose kernel holds a Poly leaf has no `predictive_gradients`."""
+    kind = "poly"
+    _gpy_class = "GPy.kern.Poly"
+    _support_GPU = True
+
+    def __init__(self, input_dim, variance=1., scale=1., bias=1., order=3., active_dims=None, name="poly", useGPU=True,
+                 device=0):
+        super(Poly, self).__init__(name)
+        self.input_dim = int(input_dim)
+        self.ARD = False
+        self.device = device
+        self.useGPU = True
+        if active_dims is None:
+            active_dims = np.arange(self.input_dim)
+        self.active_dims = np.atleast_1d(np.asarray(active_dims, dtype=np.int_))
+        assert self.active_dims.size == self.input_dim, "input_dim=%d does not match len(active_dims)=%d" % (
+            self.input_dim, self.active_dims.size)
+        self.variance = Param("variance", variance)
+        self.scale = Param("scale", scale)
+        self.bias = Param("bias", bias)
+        assert self.variance.size == 1 and self.scale.size == 1 and self.bias.size == 1
+        self.link_parameters(self.variance, self.scale, self.bias)
+        assert order >= 1, "The order of the polynomial has to be at least 1."          # poly.py:22
+        self.order = float(order)
+        self._K_cache = _KCache(limit=3)
+
+    def _theta(self):
+        """[variance, scale, bias, order]: the order travels with the parameters and has no gradient"""
+        return np.array([float(self.variance.values[0]), float(self.scale.values[0]), float(self.bias.values[0]), self.order])
+
+    __getstate__ = Stationary.__getstate__
+    _slice_X = Stationary._slice_X
+    K = Stationary.K
+    update_gradients_full = Stationary.update_gradients_full
+
+    def Kdiag(self, X):
+        """(reference `poly.py:33-34`: the diagonal of K) variance (scale |x|^2 + bias)^order"""
+        v, a, c0, order = self._theta()
+        return v * (a * np.sum(np.square(self._slice_X(X)), -1) + c0) ** order
+
+    def _install_gradients(self, g):
+        self.variance.gradient, self.scale.gradient, self.bias.gradient = g[0], g[1], g[2]     # (g[3]: the order's slot, 0)
+
+    def update_gradients_diag(self, dL_dKdiag, X):
+        raise NotImplementedError("Poly has no update_gradients_diag (reference `poly.py:45-46`)")
+
+    def gradients_X(self, dL_dK, X, X2=None):
+        raise NotImplementedError("Poly has no gradients_X (reference `poly.py:47-48`), so an expression with a Poly leaf has "
+                                  "no predictive_gradients either")
+
+    def gradients_X_diag(self, dL_dKdiag, X):
+        raise NotImplementedError("Poly has no gradients_X_diag (reference `poly.py:49-50`)")
+
+    def reset_gradients(self):
+        self.variance.gradient = self.scale.gradient = self.bias.gradient = 0.
+
+    def __add__(self, other):
+        return Add([self, other])
+
+    def __mul__(self, other):
+        return Prod([self, other])
+
+    def to_dict(self):
+        return {"class": self._gpy_class, "name": self.name, "input_dim": self.input_dim,
+                "active_dims": self.active_dims.tolist(), "variance": self.variance.values.tolist(),
+                "scale": self.scale.values.tolist(), "bias": self.bias.values.tolist(), "order": self.order, "useGPU": True}
+
+    from_dict = classmethod(MLP.from_dict.__func__)
+    copy = Stationary.copy
+
+
 # kernels the exact-GP device path evaluates as one part (the fused inference call takes them alone or in Add / Prod)
-DEVICE_KERNELS = (Stationary, StdPeriodic, Linear)
+DEVICE_KERNELS = (Stationary, StdPeriodic, Linear, MLP, Poly)
 # kinds only the exact path has (the sparse and grid paths reject them)
-EXACT_ONLY_KINDS = ("ratquad", "stdperiodic", "coregionalize", "linear")
+EXACT_ONLY_KINDS = ("ratquad", "stdperiodic", "coregionalize", "linear", "mlp", "poly")
 
 
 def has_coregionalize(kern):
@@ -676,9 +877,9 @@ def has_coregionalize(kern):
 
 
 def diag_depends_on_point(kern):
-    """True if Kdiag of the kernel or expression is not a constant: it holds a Coregionalize or a Linear leaf"""
+    """True if Kdiag of the kernel or expression is not a constant: it holds a Coregionalize, Linear, MLP or Poly leaf"""
     leaves = kern.leaves() if isinstance(kern, CombinationKernel) else [kern]
-    return any(isinstance(k, (Coregionalize, Linear)) for k in leaves)
+    return any(isinstance(k, (Coregionalize, Linear, MLP, Poly)) for k in leaves)
 
 
 def _spec_dims(f):
@@ -782,7 +983,7 @@ class CombinationKernel(Parameterized):
     def gradients_X_diag(self, dL_dKdiag, X):
         """Stationary and static leaves have a constant diagonal (reference `stationary.py:360-361`, `static.py:40-41`), and so
         has every sum / product of them (`add.py:102-106`, `prod.py:123-128`); `Add` / `Prod` compose their parts' so that a
-        Linear leaf (`linear.py:140-141`) enters."""
+        Linear (`linear.py:140-141`) or MLP (`mlp.py:86-88`) leaf enters."""
         return np.zeros(np.asarray(X).shape)
 
     def leaves(self):
@@ -794,6 +995,12 @@ class CombinationKernel(Parameterized):
 
     def _slice_X(self, X):
         return _lib.f64(np.asarray(X))
+
+    def _refuse_poly_gradients_X(self):
+        """a Poly leaf has no gradients_X (reference `poly.py:47-48`): raise its error before any part does device work"""
+        for k in self.leaves():
+            if isinstance(k, Poly):
+                k.gradients_X(None, None)
 
     def __add__(self, other):
         return Add([self, other])
@@ -825,8 +1032,8 @@ class Add(CombinationKernel):
         flat = []
         for p in parts:
             flat.extend(p.parts if isinstance(p, Add) else [p])          # add.py:24-33 flattens nested sums
-        assert all(isinstance(p, (Stationary, StdPeriodic, Linear, Static, Coregionalize, Prod)) for p in flat), \
-            "Add supports stationary, StdPeriodic, Linear, White, Bias, Coregionalize and Prod parts"
+        assert all(isinstance(p, (Stationary, StdPeriodic, Linear, MLP, Poly, Static, Coregionalize, Prod)) for p in flat), \
+            "Add supports stationary, StdPeriodic, Linear, MLP, Poly, White, Bias, Coregionalize and Prod parts"
         super(Add, self).__init__(flat, name)
 
     def part_specs(self):
@@ -865,6 +1072,7 @@ class Add(CombinationKernel):
             p.update_gradients_diag(dL_dKdiag, X)
 
     def gradients_X(self, dL_dK, X, X2=None):
+        self._refuse_poly_gradients_X()
         G = np.asarray(dL_dK)
         return sum(p.gradients_X(G, X, X2) for p in self.parts)
 
@@ -884,8 +1092,8 @@ class Prod(CombinationKernel):
         flat = []
         for k in kernels:
             flat.extend(k.parts if isinstance(k, Prod) else [k])
-        assert all(isinstance(k, (Stationary, StdPeriodic, Linear, Static, Coregionalize)) for k in flat), \
-            "Prod supports stationary, StdPeriodic, Linear, White, Bias and Coregionalize factors"
+        assert all(isinstance(k, (Stationary, StdPeriodic, Linear, MLP, Poly, Static, Coregionalize)) for k in flat), \
+            "Prod supports stationary, StdPeriodic, Linear, MLP, Poly, White, Bias and Coregionalize factors"
         super(Prod, self).__init__(flat, name)
 
     def part_specs(self):
@@ -929,6 +1137,7 @@ class Prod(CombinationKernel):
             p.update_gradients_diag(w, X)
 
     def gradients_X(self, dL_dK, X, X2=None):                                    # prod.py:113-121
+        self._refuse_poly_gradients_X()
         G = np.asarray(dL_dK)
         Ks = [p.K(X, X2) for p in self.parts]
         out = 0.
@@ -958,4 +1167,4 @@ class Prod(CombinationKernel):
 
 KERNEL_CLASSES = {"rbf": RBF, "expquad": ExpQuad, "matern52": Matern52, "matern32": Matern32, "exponential": Exponential,
                   "white": White, "bias": Bias, "ratquad": RatQuad, "stdperiodic": StdPeriodic, "coregionalize": Coregionalize,
-                  "linear": Linear}
+                  "linear": Linear, "mlp": MLP, "poly": Poly}

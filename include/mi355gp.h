@@ -26,7 +26,8 @@ typedef struct mi355gp_ctx mi355gp_ctx;
 
 enum { MI355GP_RBF = 0, MI355GP_MATERN52 = 1, MI355GP_MATERN32 = 2, MI355GP_EXPONENTIAL = 3,
        MI355GP_WHITE = 4, MI355GP_BIAS = 5 /* static kernels, only as parts of a sum (kern/src/static.py:63-98,151-173) */,
-       MI355GP_RATQUAD = 6, MI355GP_STDPERIODIC = 7, MI355GP_COREGIONALIZE = 8, MI355GP_LINEAR = 9 };
+       MI355GP_RATQUAD = 6, MI355GP_STDPERIODIC = 7, MI355GP_COREGIONALIZE = 8, MI355GP_LINEAR = 9,
+       MI355GP_MLP = 10, MI355GP_POLY = 11 };
 
 /* The exact-GP entry points (single kind and part lists; not the sparse or grid paths) also take
  *   MI355GP_RATQUAD      k = var (1 + r^2/2)^-power (kern/src/stationary.py:747-802, GPy.kern.RatQuad);
@@ -60,6 +61,23 @@ enum { MI355GP_RBF = 0, MI355GP_MATERN52 = 1, MI355GP_MATERN32 = 2, MI355GP_EXPO
  *                          prediction variances take Kdiag per point and mi355gp_kern_Kdiag (no X argument) rejects the kind;
  *                          dK/dx = var_q x'_q (:108-114) and dKdiag/dx = 2 var_q x_q enter mi355gp_predictive_gradients_sum.
  *                          The sparse and grid paths reject it. */
+
+/* The same entry points take the two other dot-product kinds of GPy, functions of x.x', x.x and x'.x' alone:
+ *   MI355GP_MLP            the arc-sine / neural-network kernel (kern/src/mlp.py:48-64, GPy.kern.MLP):
+ *                            k(x, x') = var (2/pi) asin( s / sqrt((p + 1)(p' + 1)) ),  s = sum_q w_q x_q x'_q + b,
+ *                            p = sum_q w_q x_q^2 + b (p' likewise from x').
+ *                          theta = [variance, weight_variance (1, or n_active if ard), bias_variance] in GPy's link order
+ *                          (:36-45), every one positive; gradients come back in theta order (:98-123).  Not stationary:
+ *                          K(x, x) = var (2/pi) asin(p / (p + 1)) depends on the point (:61-64).  dK/dx (:124-130) serves
+ *                          mi355gp_gradients_X (X2 == NULL: the weights c + c^T of :124-127) and, with dKdiag/dx (:133-147),
+ *                          mi355gp_predictive_gradients_sum.
+ *   MI355GP_POLY           the polynomial kernel (kern/src/poly.py:15-49, GPy.kern.Poly): k(x, x') = var (a x.x' + c)^order.
+ *                          theta = [variance, scale, bias, order], the first three positive, order >= 1 and fixed (no
+ *                          parameter: its gradient slot is written as 0 so that theta and dtheta have the same length).
+ *                          A negative base follows C pow().  The reference has no gradients_X for it (:45-49):
+ *                          mi355gp_gradients_X and mi355gp_predictive_gradients_sum reject the kind.
+ * Both alone, as a summand or as a factor of a product term.  mi355gp_kern_Kdiag (no X argument) and the sparse and grid
+ * paths reject both. */
 
 /* One part of a sum-of-products kernel expression (GPy.kern.Add, kern/src/add.py:58-84; GPy.kern.Prod,
  * kern/src/prod.py:58-99).  theta = [variance, lengthscale (1, or n_active if ard)] (static kinds: [variance]);
