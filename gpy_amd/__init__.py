@@ -9,20 +9,22 @@ HIP kernel in gpy_amd/csrc.  No PyTorch, no NumPy fallback: without an MI355X th
 from . import _lib
 from ._lib import MI355GPError, build, device_count
 from .inference import ExactGaussianInference, ExactStudentTInference
+from .laplace import Laplace, LaplacePosterior
 from .kern import (OU, RBF, Add, Prod, Bias, Coregionalize, ExpQuad, Exponential, Linear, Matern32, Matern52, MLP, Poly, RatQuad,
                    Stationary, StdPeriodic, White)
-from .likelihoods import Gaussian, HeteroscedasticGaussian, MixedNoise
-from .models import GP, GPCoregionalizedRegression, GPHeteroscedasticRegression, GPRegression
+from .likelihoods import Bernoulli, Gaussian, HeteroscedasticGaussian, MixedNoise
+from .models import GP, GPClassification, GPCoregionalizedRegression, GPHeteroscedasticRegression, GPRegression
 from .posterior import PosteriorExact, StudentTPosterior
 from .sparse import SparseGP, SparseGPRegression, VarDTC
 
 __all__ = ["RBF", "OU", "ExpQuad", "HeteroscedasticGaussian", "StudentTPosterior", "Matern52", "Matern32", "Exponential", "RatQuad", "StdPeriodic", "Coregionalize", "Linear", "MLP", "Poly", "MixedNoise", "Stationary", "White", "Bias", "Add", "Prod", "Gaussian", "ExactGaussianInference", "ExactStudentTInference",
-           "PosteriorExact", "GP", "GPRegression", "GPHeteroscedasticRegression", "GPCoregionalizedRegression", "VarDTC", "SparseGP", "SparseGPRegression", "MI355GPError", "build", "device_count"]
+           "PosteriorExact", "GP", "GPRegression", "GPHeteroscedasticRegression", "GPCoregionalizedRegression", "Laplace", "LaplacePosterior", "Bernoulli", "GPClassification", "VarDTC", "SparseGP", "SparseGPRegression", "MI355GPError", "build", "device_count"]
 
 # GPy's import paths, so that `import gpy_amd as GPy` reads like the reference on this path:
 #   GPy.kern.RBF, GPy.likelihoods.Gaussian, GPy.models.GPRegression / SparseGPRegression / GPHeteroscedasticRegression,
-#   GPy.core.GP / SparseGP, GPy.inference.latent_function_inference.ExactGaussianInference / VarDTC
-from . import inference, kern, likelihoods, linalg, models, sparse, util  # noqa: E402
+#   GPy.models.GPClassification, GPy.likelihoods.Bernoulli, GPy.likelihoods.link_functions.Probit,
+#   GPy.core.GP / SparseGP, GPy.inference.latent_function_inference.ExactGaussianInference / VarDTC / Laplace
+from . import inference, kern, laplace, likelihoods, link_functions, linalg, models, sparse, util  # noqa: E402
 import types as _types  # noqa: E402
 
 models.SparseGPRegression = SparseGPRegression
@@ -30,6 +32,7 @@ core = _types.SimpleNamespace(GP=GP, SparseGP=SparseGP)
 likelihoods.mixed_noise = _types.SimpleNamespace(MixedNoise=MixedNoise)
 inference.latent_function_inference = _types.SimpleNamespace(
     ExactGaussianInference=ExactGaussianInference, ExactStudentTInference=ExactStudentTInference, VarDTC=VarDTC,
-    PosteriorExact=PosteriorExact, StudentTPosterior=StudentTPosterior,
+    PosteriorExact=PosteriorExact, StudentTPosterior=StudentTPosterior, Laplace=Laplace,
+    laplace=_types.SimpleNamespace(Laplace=Laplace),
     exact_gaussian_inference=_types.SimpleNamespace(ExactGaussianInference=ExactGaussianInference),
     var_dtc=_types.SimpleNamespace(VarDTC=VarDTC))

@@ -126,6 +126,11 @@ def lib():
     L.mi355gp_covariance_between_points.argtypes = [vp, ci, ctypes.POINTER(Part), _dp, i64, _dp, i64, _dp]
     L.mi355gp_predictive_gradients_sum.argtypes = [vp, ci, ctypes.POINTER(Part), _dp, i64, _c_dp, _c_dp]
     L.mi355gp_predict_sum.argtypes = [vp, ci, ctypes.POINTER(Part), _dp, i64, _c_dp, _c_dp, ci]
+    L.mi355gp_laplace_begin.argtypes = [vp, ci, ctypes.POINTER(Part)]
+    L.mi355gp_laplace_newton.argtypes = [vp, _dp, _dp, cd, _dp, _dp, _c_dp]
+    L.mi355gp_laplace_finish.argtypes = [vp, _dp, cd, _dp, _c_dp]
+    L.mi355gp_laplace_gradients.argtypes = [vp, _dp, _dp, _dp]
+    L.mi355gp_laplace_predict.argtypes = [vp, ci, ctypes.POINTER(Part), _dp, i64, _dp, _c_dp, _c_dp, ci]
     L.mi355gp_inference_given_K.argtypes = [vp, _dp, _dp, i64, cd, cd, _dp, _c_dp, _c_dp, _c_dp]
     L.mi355gp_fetch.argtypes = [vp, ci, _dp, ci]
     L.mi355gp_predict.argtypes = [vp, ci, ci, _dp, _dp, i64, _c_dp, _c_dp, ci]
@@ -187,7 +192,8 @@ def lib():
                  "vardtc_inference_sum", "sparse_predict", "sparse_fetch_dLdKnm", "sparse_attach_loopback",
                  "predictive_gradients_sum", "dbg_pipe_share", "pdinv_full", "dbg_graph_factor", "get_option",
                  "sparse_get_profile", "dbg_persist", "dbg_grid_multi", "dbg_update_nt", "dbg_update_rect",
-                 "dbg_ipc_selftest"):
+                 "dbg_ipc_selftest", "laplace_begin", "laplace_newton", "laplace_finish", "laplace_gradients",
+                 "laplace_predict"):
         getattr(L, "mi355gp_" + name).restype = ci
     _lib = L
     return L
@@ -208,7 +214,9 @@ EXPORTED = ("mi355gp_last_error", "mi355gp_version", "mi355gp_device_count", "mi
             "mi355gp_predictive_gradients_sum", "mi355gp_dbg_pipe_share", "mi355gp_pdinv_full", "mi355gp_dbg_graph_factor",
             "mi355gp_dbg_mfma", "mi355gp_dbg_gemm", "mi355gp_dbg_peaks", "mi355gp_dbg_mask_probe", "mi355gp_get_option",
             "mi355gp_sparse_get_profile", "mi355gp_dbg_persist", "mi355gp_dbg_grid_multi", "mi355gp_dbg_update_nt", "mi355gp_dbg_update_rect",
-            "mi355gp_dbg_ipc_selftest", "mi355gp_grid_coll_log", "mi355gp_dbg_lauum_plan", "mi355gp_dbg_persist_owners")
+            "mi355gp_dbg_ipc_selftest", "mi355gp_grid_coll_log", "mi355gp_dbg_lauum_plan", "mi355gp_dbg_persist_owners",
+            "mi355gp_laplace_begin", "mi355gp_laplace_newton", "mi355gp_laplace_finish", "mi355gp_laplace_gradients",
+            "mi355gp_laplace_predict")
 
 
 # mi355gp_set_option / mi355gp_get_option ids (include/mi355gp.h, MI355GP_OPT_*)
@@ -391,6 +399,54 @@ class Context(object):
         if ms is not None:
             res["stage_ms"] = dict(zip(STAGE_NAMES, ms[:len(STAGE_NAMES)]))
         return rc, res
+
+    # ---- Laplace session (include/mi355gp.h: begin, newton per mode-search iteration, finish, gradients, predict / fetch) ----
+    def laplace_begin(self, specs):
+        """K = kern.K(X) for the part list, resident for the session (reference `laplace.py:129`)."""
+        arr, keep, ntheta = make_parts(specs)
+        check(lib().mi355gp_laplace_begin(self._h, len(specs), arr), "mi355gp_laplace_begin")
+        self._lap_ntheta = ntheta
+
+    def laplace_newton(self, W, b, extra_jitter=0.0):
+        """One iteration of `rasm_mode` (reference `laplace.py:184-199`): (info, a = full-step Ki_f, K a, logdet B)."""
+        W, b = f64(np.ravel(W)), f64(np.ravel(b))
+        assert W.size == self.N and b.size == self.N
+        a, Ka = np.empty(self.N), np.empty(self.N)
+        ld = ctypes.c_double(0.0)
+        rc = check(lib().mi355gp_laplace_newton(self._h, W, b, float(extra_jitter), a, Ka, ctypes.byref(ld)),
+                   "mi355gp_laplace_newton")
+        return rc, a, Ka, ld.value
+
+    def laplace_finish(self, W, extra_jitter=0.0):
+        """The B statistics at the mode (reference `laplace.py:247,333-351`): (info, diag(Ki_W_i), logdet_I_KW)."""
+        W = f64(np.ravel(W))
+        assert W.size == self.N
+        d = np.empty(self.N)
+        ld = ctypes.c_double(0.0)
+        rc = check(lib().mi355gp_laplace_finish(self._h, W, float(extra_jitter), d, ctypes.byref(ld)), "mi355gp_laplace_finish")
+        return rc, d, ld.value
+
+    def laplace_gradients(self, Ki_f, dL_dfhat):
+        """dL/dtheta of every part (concatenated) from the device-resident dL_dK (reference `laplace.py:257-272`)."""
+        Ki_f, s = f64(np.ravel(Ki_f)), f64(np.ravel(dL_dfhat))
+        assert Ki_f.size == self.N and s.size == self.N
+        dtheta = np.zeros(self._lap_ntheta)
+        check(lib().mi355gp_laplace_gradients(self._h, Ki_f, s, dtheta), "mi355gp_laplace_gradients")
+        return dtheta
+
+    def laplace_predict(self, specs, Xnew, wv, full_cov=False, want_var=True):
+        """`Posterior._raw_predict` for the Laplace posterior (reference `laplace.py:146`, `posterior.py:198-262`)."""
+        arr, keep, _ = make_parts(specs)
+        Xnew, wv = f64(Xnew), f64(np.ravel(wv))
+        M = Xnew.shape[0]
+        assert Xnew.shape[1] == self.D and wv.size == self.N
+        mu = np.empty((M, 1))
+        var = (np.empty((M, M)) if full_cov else np.empty(M)) if want_var else None
+        check(lib().mi355gp_laplace_predict(self._h, len(specs), arr, Xnew, M, wv, mu.ctypes.data_as(_c_dp), _opt(var),
+                                            int(bool(full_cov))), "mi355gp_laplace_predict")
+        if var is not None and not full_cov:
+            var = var[:, None]
+        return mu, var
 
     def set_option(self, name, value):
         """Options of THIS context through the C-ABI (`mi355gp_set_option`; the MI355GP_* environment variables only give the

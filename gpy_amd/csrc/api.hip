@@ -30,51 +30,7 @@ void mi355gp_set_error(const char* fmt, ...) {
 
 #define LOG_2_PI 1.8378770664093454836
 
-struct mi355gp_ctx {
-    int device = 0;
-    hipStream_t st = nullptr;
-    long n = 0, npad = 0;
-    int D = 0, Dy = 0;
-    double *dX = nullptr, *dR = nullptr, *dNoise = nullptr;
-    double *A = nullptr, *B = nullptr, *C = nullptr;
-    FactorWs ws;
-    double *dAlpha = nullptr, *dTmp = nullptr, *dTrmvPart = nullptr, *dGradPart = nullptr, *dGradOut = nullptr,
-           *dScal = nullptr, *dDiag = nullptr;
-    long gradPartDoubles = 0;
-    hipEvent_t ev[8] = {};
-    // state of the last inference call (for fetch / predict)
-    bool have_factor = false, have_kernel = false;
-    bool studentt = false;              // the last call was a Student-t process: dL_dK's alpha alpha^T term is scaled by dScal[4]
-    // The covariance function of the last fused call as a sum of products of parts (GPy/kern/src/add.py, prod.py)
-    struct Part : DevicePart {
-        DevBuf dXt;                     // D x npad scaled, dimension-major inputs of this part
-    };
-    std::vector<Part> parts;
-    Terms terms;
-    double* Mbuf = nullptr;             // npad x npad product of the OTHER factors of a term (allocated on first product kernel)
-    // Everything an evaluation returns -- scalars, info, per-part gradient sums, alpha, diag(dL_dK) -- lives in ONE device
-    // block and travels in ONE copy into ONE pinned host block (five small pageable copies cost ~80 us per evaluation:
-    // 2 % at N = 4096).  Layout (doubles): [scal 8 | grads MAXP*groups*GP_STRIDE | second records of RatQuad / StdPeriodic
-    // parts MAXP*groups*GP_STRIDE | alpha N*Dy | diag N]
-    // The factorisation region of an evaluation (potrf -> trtri -> alpha solve || lauum: ~110 launches on up to three streams at
-    // N = 4096, every argument a fixed pointer or size of this context) replayed from ONE hipGraph for the sizes whose
-    // factorisation is launch- / latency-bound (no CU-masked overlap stream below the overlapped-inverse threshold, so nothing
-    // a graph node cannot carry): N = 4096 3.37 -> 3.21 ms, N = 2048 1.33 -> 1.26, N = 512 0.31 -> 0.28 (mi355gp_dbg_graph_factor).
-    hipGraphExec_t fgraph = nullptr;
-    int fgraph_calls = 0, fgraph_lookahead = -1, graph_enabled = 1;     // MI355GP_GRAPH=0 turns it off
-    double *dPack = nullptr, *hPack = nullptr;
-    size_t packDoubles = 0, offGrad = 0, offExt = 0, offAlpha = 0, offDiag = 0;
-    // schedule switches set through mi355gp_set_option (INT_MIN: the process default that factor_ws_alloc read)
-    int opt[MI355GP_OPT_NUM];
-    double* dGradOutAll = nullptr;      // = dPack + offGrad: [part][groups][GP_STRIDE]
-    // Coregionalize (kind 8) parts: the P x P partial records of the bucketed gradient (allocated with the first such part),
-    // the S of every part in the result block at offCoreg ([part][256], behind diag; copied only when a kind-8 part is present),
-    // and a host copy of the training output-index column last validated (hIdxCol: its input column, -1 none)
-    double* dCoregPart = nullptr;
-    size_t offCoreg = 0;
-    std::vector<double> hIdx;
-    int hIdxCol = -1;
-};
+#include "ctx.h"
 
 // (re)applies the context's option overrides to its factorisation workspace (after every factor_ws_alloc and set_option)
 static void apply_options(mi355gp_ctx* c) {
@@ -115,6 +71,9 @@ static void free_data(mi355gp_ctx* c) {
     c->dAlpha = c->dScal = c->dDiag = c->dGradOutAll = nullptr;      // views into dPack
     c->hIdx.clear();
     c->hIdxCol = -1;
+    laplace_session_free(c->lap);                             // the fourth N x N buffer and its vectors, if a session ever began
+    c->lap = nullptr;
+    c->lap_stage = 0;
     factor_ws_free(&c->ws);
     c->have_factor = c->have_kernel = false;
 }
@@ -242,6 +201,7 @@ static int run_pipeline(mi355gp_ctx* c, EngineShared* gate, bool with_kernel_gra
                         const std::function<int()>& rebuild, double studentt_nu = 0.0, int attempt = 0) {
     hipStream_t st = c->st;
     const long n = c->n, np = c->npad;
+    c->lap_stage = 0;                                        // A / B / C are this evaluation's from here on
     c->ws.prof.reset();
     c->ws.scratchX = c->B;                                   // free until trtri / lauum overwrite them
     c->ws.scratchT = c->C;
@@ -513,6 +473,17 @@ static int upload_noise(mi355gp_ctx* c, const double* noise, int64_t noise_len) 
     return 0;
 }
 
+// the helpers laplace.hip shares (ctx.h)
+static int prepare_parts(mi355gp_ctx* c, int nparts, const mi355gp_part* parts);
+static void scale_parts(mi355gp_ctx* c);
+static Resident<mi355gp_ctx::Part> training_points(const mi355gp_ctx* c);
+int ctx_prepare_parts(mi355gp_ctx* c, int nparts, const mi355gp_part* parts) { return prepare_parts(c, nparts, parts); }
+void ctx_scale_parts(mi355gp_ctx* c) { scale_parts(c); }
+Resident<mi355gp_ctx::Part> ctx_training_points(const mi355gp_ctx* c) { return training_points(c); }
+int ctx_coreg_check_points(const mi355gp_ctx* c, const double* Xn, int64_t M, const char* what) { return coreg_check_points(c, Xn, M, what); }
+bool ctx_has_point_diag(const mi355gp_ctx* c) { return has_point_diag(c); }
+std::vector<double> ctx_kdiag_points(const mi355gp_ctx* c, const double* Xn, int64_t M) { return expression_kdiag_points(c, Xn, M); }
+
 extern "C" {
 
 // validates the part list and (re)builds the per-part device inputs
@@ -642,7 +613,9 @@ int mi355gp_fetch(mi355gp_ctx* c, int which, double* out, int fortran_order) {
     hipStream_t st = c->st;
     DevBuf tmp, scratch;
     HIP_CHECK(tmp.alloc(n * n));
-    if (which == MI355GP_FETCH_K) {
+    if (c->lap_stage > 0) {                                   // the matrices of a Laplace session (laplace.hip)
+        if (int rc = laplace_fetch(c, which, tmp)) return rc;
+    } else if (which == MI355GP_FETCH_K) {
         if (!c->have_kernel) {
             mi355gp_set_error("mi355gp_fetch(K): no device kernel evaluation in this context");
             return -4;
@@ -950,7 +923,7 @@ int mi355gp_pdinv_full(int device, const double* A, int64_t N, double* Ainv, dou
 
 int mi355gp_predict_sum(mi355gp_ctx* c, int nparts, const mi355gp_part* parts, const double* Xnew, int64_t M,
                         double* mu_out, double* var_out, int full_cov) {
-    ARG_CHECK(c && c->n > 0 && c->have_factor, "mi355gp_predict: run an inference call first");
+    ARG_CHECK(c && c->n > 0 && c->have_factor && c->lap_stage == 0, "mi355gp_predict: run an inference call first");
     ARG_CHECK(Xnew && M > 0 && mu_out, "mi355gp_predict: bad arguments");
     HIP_CHECK(hipSetDevice(c->device));
     EngineShared gate(c->device);

@@ -330,6 +330,17 @@ void launch_rowdots(hipStream_t st, const double* K, const double* T, long ld, l
 // M[i][j] *= sqrt(w[i]) into Out (may alias M), rows x cols (ld shared)
 void launch_rowscale_sqrt(hipStream_t st, const double* M, long ld, long rows, long cols, const double* w, double* Out);
 
+// Laplace approximation (laplace.hip) over the resident K = kern.K(X) (npad x npad, ld = npad, symmetric, lower 64-tiles read)
+// A (lower 64-tiles) = I + diag(sw) K diag(sw) + jit I on the first n rows; identity in the padding   (laplace.py:333-334)
+void launch_laplace_B(hipStream_t st, const double* K, long npad, long n, const double* sw, double jit, double* A);
+// y0 = K v0 (and y1 = K v1 if v1 != NULL) from the lower tiles of K, fixed-order partials in `part` (symv_part_doubles(npad))
+size_t symv_part_doubles(long npad);
+void launch_symv_lower(hipStream_t st, const double* K, long npad, long n, const double* v0, const double* v1, double* y0,
+                       double* y1, double* part);
+// G (both triangles) = 0.5 (a a^T - diag(sw) Binv diag(sw)) + 0.5 (a u^T + u a^T), Binv read from its lower tiles (laplace.py:260-272)
+void launch_laplace_dLdK(hipStream_t st, const double* Binv, long npad, long n, const double* sw, const double* a,
+                         const double* u, double* G);
+
 // ---- grid.hip : RCCL (dlopen'ed) world communicator for row-sharded paths ---------------------------------------
 int rccl_comm_create(int rank, int world, const void* id128, void** comm);
 int rccl_allreduce_sum(void* comm, double* buf, size_t count, hipStream_t st);

@@ -159,3 +159,92 @@ class MixedNoise(Parameterized):
         """(reference `mixed_noise.py:86-100`)"""
         return {"name": self.name, "class": "GPy.likelihoods.MixedNoise",
                 "likelihoods_list": [l.to_dict() for l in self.likelihoods_list]}
+
+
+from . import link_functions  # noqa: E402  (GPy.likelihoods.link_functions)
+
+
+class Bernoulli(Parameterized):
+    """Bernoulli likelihood p(y | f) = lambda(f)^y (1 - lambda(f))^(1 - y), y in {0, 1} (reference
+    `GPy/likelihoods/bernoulli.py:9-273`), with the derivatives in f that the Laplace approximation needs, composed from
+    the derivatives in lambda and the link's by the chain rule (reference `likelihood.py:551-652`).  No parameters (`size == 0`);
+    with the probit link it is log-concave.  The probabilities are clipped where the reference clips them (1e-9), so values far
+    in the tails agree with it."""
+
+    def __init__(self, gp_link=None, name="Bernoulli"):
+        super(Bernoulli, self).__init__(name)
+        self.gp_link = link_functions.Probit() if gp_link is None else gp_link
+        self.log_concave = isinstance(self.gp_link, link_functions.Probit)
+        self.is_fixed = False
+
+    @staticmethod
+    def check_targets(Y):
+        """Y must hold zeros and ones only (the assertion of reference `bernoulli.py:53-55`)."""
+        Y = np.asarray(Y)
+        assert np.count_nonzero(Y == 1) + np.count_nonzero(Y == 0) == Y.size, \
+            "Bernoulli likelihood is meant to be used only with outputs in {0, 1}."
+        return Y
+
+    def update_gradients(self, grad):
+        pass
+
+    def exact_inference_gradients(self, dL_dKdiag, Y_metadata=None):
+        return np.zeros(self.size)
+
+    # ---- in terms of lambda = link(f) (reference `bernoulli.py:138-249`) -------------------------------------------------
+    def pdf_link(self, inv_link_f, y, Y_metadata=None):
+        return np.where(y == 1, inv_link_f, 1.0 - inv_link_f)
+
+    def logpdf_link(self, inv_link_f, y, Y_metadata=None):
+        return np.log(np.clip(self.pdf_link(inv_link_f, y), 1e-9, np.inf))
+
+    def dlogpdf_dlink(self, inv_link_f, y, Y_metadata=None):
+        lam = np.clip(inv_link_f, 1e-9, 1.0 - 1e-9)
+        return 1.0 / np.where(y == 1, lam, -(1.0 - lam))
+
+    def d2logpdf_dlink2(self, inv_link_f, y, Y_metadata=None):
+        return -1.0 / np.square(np.clip(self.pdf_link(inv_link_f, y), 1e-9, 1e9))
+
+    def d3logpdf_dlink3(self, inv_link_f, y, Y_metadata=None):
+        with np.errstate(divide="ignore"):
+            return np.where(y == 1, 2.0 / inv_link_f ** 3, -2.0 / (1.0 - inv_link_f) ** 3)
+
+    # ---- in terms of f: Faa di Bruno (reference `likelihood.py:551-652`, `util/misc.py` chain_1..3) ----------------------
+    def logpdf(self, f, y, Y_metadata=None):
+        return self.logpdf_link(self.gp_link.transf(f), y)
+
+    def dlogpdf_df(self, f, y, Y_metadata=None):
+        return self.dlogpdf_dlink(self.gp_link.transf(f), y) * self.gp_link.dtransf_df(f)
+
+    def d2logpdf_df2(self, f, y, Y_metadata=None):
+        lam, d1 = self.gp_link.transf(f), self.gp_link.dtransf_df(f)
+        return self.d2logpdf_dlink2(lam, y) * d1 ** 2 + self.dlogpdf_dlink(lam, y) * self.gp_link.d2transf_df2(f)
+
+    def d3logpdf_df3(self, f, y, Y_metadata=None):
+        lam, d1, d2 = self.gp_link.transf(f), self.gp_link.dtransf_df(f), self.gp_link.d2transf_df2(f)
+        return (self.d3logpdf_dlink3(lam, y) * d1 ** 3 + 3.0 * self.d2logpdf_dlink2(lam, y) * d1 * d2
+                + self.dlogpdf_dlink(lam, y) * self.gp_link.d3transf_df3(f))
+
+    # ---- prediction (reference `bernoulli.py:120-136,251-270`, `likelihood.py:734-755`) ---------------------------------
+    def predictive_mean(self, mu, variance, Y_metadata=None):
+        if not isinstance(self.gp_link, link_functions.Probit):
+            raise NotImplementedError("predictive_mean in closed form needs the probit link")
+        return link_functions.std_norm_cdf(mu / np.sqrt(1.0 + variance))
+
+    def predictive_variance(self, mu, variance, pred_mean=None, Y_metadata=None):
+        return np.nan                                      # as the reference returns it for the probit link
+
+    def predictive_values(self, mu, var, full_cov=False, Y_metadata=None):
+        pred_mean = self.predictive_mean(mu, var, Y_metadata=Y_metadata)
+        return pred_mean, self.predictive_variance(mu, var, pred_mean, Y_metadata=Y_metadata)
+
+    def predictive_quantiles(self, mu, var, quantiles, Y_metadata=None):
+        p = self.predictive_mean(mu, var)
+        return [np.asarray(p > (q / 100.0), dtype=np.int32) for q in quantiles]
+
+    def samples(self, gp, Y_metadata=None):
+        gp = np.asarray(gp)
+        return np.random.binomial(np.ones(gp.size, dtype=int), self.gp_link.transf(gp.ravel())).reshape(gp.shape)
+
+    def to_dict(self):
+        return {"class": "GPy.likelihoods.Bernoulli", "name": self.name, "gp_link_dict": self.gp_link.to_dict()}

@@ -45,6 +45,13 @@ class Standardize(object):
         return {"class": "GPy.util.normalizer.Standardize", "mean": self.mean.tolist(), "std": self.std.tolist()}
 
 
+def _gaussian_only(likelihood, what):
+    """The callers that lean on a Gaussian predictive density: a likelihood without `gaussian_variance` (Bernoulli) gets a
+    clear NotImplementedError instead of a wrong number."""
+    if not hasattr(likelihood, "gaussian_variance"):
+        raise NotImplementedError("%s is not implemented for the %s likelihood on this backend" % (what, type(likelihood).__name__))
+
+
 class PredictionCallers(object):
     """The prediction-side callers of the hot path in the reference's `GP` class (`core/gp.py:367-474,601-652,700-790`), shared
     by the exact and the sparse model driver: everything here is a thin wrapper around `_raw_predict` / the posterior, exactly as
@@ -84,8 +91,9 @@ class PredictionCallers(object):
 
     def predict_quantiles(self, X, quantiles=(2.5, 97.5), Y_metadata=None, kern=None, likelihood=None):
         """(reference `core/gp.py:395-416`)"""
-        m, v = self._raw_predict(X, full_cov=False) if kern is None else self._raw_predict(X, full_cov=False, kern=kern)
         likelihood = self.likelihood if likelihood is None else likelihood
+        _gaussian_only(likelihood, "predict_quantiles")
+        m, v = self._raw_predict(X, full_cov=False) if kern is None else self._raw_predict(X, full_cov=False, kern=kern)
         qs = likelihood.predictive_quantiles(m, v, quantiles, Y_metadata=Y_metadata)
         if self.normalizer is not None:
             qs = [self.normalizer.inverse_mean(q) for q in qs]
@@ -93,12 +101,14 @@ class PredictionCallers(object):
 
     def log_predictive_density(self, x_test, y_test, Y_metadata=None):
         """(reference `core/gp.py:700-714`)"""
+        _gaussian_only(self.likelihood, "log_predictive_density")
         mu_star, var_star = self._raw_predict(x_test)
         return self.likelihood.log_predictive_density(y_test, mu_star, var_star, Y_metadata=Y_metadata)
 
     def predictive_gradients(self, Xnew, kern=None):
         """d mean / d X* (N* x Q x D) and d var / d X* (N* x Q) of the latent prediction (reference `core/gp.py:418-474`),
         reduced on the device (`mi355gp_predictive_gradients_sum`)."""
+        _gaussian_only(self.likelihood, "predictive_gradients")
         mean_jac, var_jac = self.posterior.predictive_gradients(self.kern if kern is None else kern, np.asarray(Xnew),
                                                                 pred_var=self._predictive_variable)
         if self.normalizer is not None:              # (reference `core/gp.py:467-472`)
@@ -296,6 +306,33 @@ class GPRegression(GP):
                                            Y_metadata=Y_metadata, mean_function=mean_function, device=device,
                                            normalizer=bool(normalizer) if normalizer in (None, True, False)
                                            else normalizer)
+
+
+class GPClassification(GP):
+    """Gaussian-process classification (reference `GPy/models/gp_classification.py:10-39`): the reference's signature and its
+    defaults RBF and Bernoulli.  The reference's default inference is EP, which this backend does not have: rather than compute
+    something else silently, `inference_method=None` raises and names the alternative."""
+
+    def __init__(self, X, Y, kernel=None, Y_metadata=None, mean_function=None, inference_method=None, likelihood=None,
+                 normalizer=False, device=0):
+        from .likelihoods import Bernoulli
+        if inference_method is None:
+            raise NotImplementedError(
+                "GPy's GPClassification defaults to EP (expectation propagation), which gpy_amd does not implement; "
+                "pass inference_method=gpy_amd.Laplace() for the Laplace approximation")
+        if kernel is None:
+            kernel = RBF(np.asarray(X).shape[1], device=device)
+        if likelihood is None:
+            likelihood = Bernoulli()
+        if isinstance(likelihood, Bernoulli):
+            likelihood.check_targets(Y)
+        super(GPClassification, self).__init__(X, Y, kernel, likelihood, mean_function=mean_function,
+                                               inference_method=inference_method, name="gp_classification",
+                                               Y_metadata=Y_metadata, device=device, normalizer=normalizer)
+
+    def to_dict(self):
+        return {"class": "GPy.models.GPClassification", "name": self.name, "kernel": self.kern.to_dict(),
+                "likelihood": self.likelihood.to_dict(), "inference_method": self.inference_method.to_dict()}
 
 
 class GPHeteroscedasticRegression(GP):

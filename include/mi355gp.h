@@ -217,6 +217,39 @@ int mi355gp_predict_sum(mi355gp_ctx* ctx, int nparts, const mi355gp_part* parts,
 int mi355gp_predictive_gradients_sum(mi355gp_ctx* ctx, int nparts, const mi355gp_part* parts, const double* Xnew, int64_t M,
                                      double* dmu_out, double* dvar_out);
 
+/* ---- Laplace approximation for a non-Gaussian likelihood (one output column) ---------------------------------------------
+ * The N x N work of Laplace.inference (inference/latent_function_inference/laplace.py:122-353) as a session on an exact
+ * context; the likelihood's derivatives are O(N) host work and travel as vectors, nothing N x N crosses PCIe.  Call order:
+ * begin, newton (once per iteration of the mode search), finish, gradients, then predict / fetch as often as needed.  Any
+ * exact / Student-t / given-K evaluation on the context ends the session (and the other way round); both give their usual
+ * bits afterwards.  The first begin of a context allocates a fourth N x N buffer for K and the session's vectors. */
+/* K = kern.K(X) for the part list (laplace.py:129; add.py:58-72, prod.py:58-65): no noise, no jitter, the exact Kdiag on the
+ * diagonal; resident until the next begin / set_data. */
+int mi355gp_laplace_begin(mi355gp_ctx* ctx, int nparts, const mi355gp_part* parts);
+/* One iteration of rasm_mode (laplace.py:184-199) for W = -d2logpdf_df2(f) (N, finite, >= 0) and b = W f + dlogpdf_df(f):
+ * B = I + W^1/2 K W^1/2 + extra_jitter I, its Cholesky factor and inverse factor (_compute_B_statistics, :333-338, without
+ * the N^3 products), a_out = b - W^1/2 B^-1 W^1/2 K b (the full-step Ki_f, :195-198), Ka_out = K a_out -- f_trial =
+ * K (Ki_f + s dKi_f) is linear in the step s, so the line search (:202-208) is host work on these two vectors -- and
+ * *logdet_out (optional) = 2 sum log diag L_B.  Returns info > 0 when B is not positive definite (the caller runs jitchol's
+ * ladder through extra_jitter, util/linalg.py:56-75). */
+int mi355gp_laplace_newton(mi355gp_ctx* ctx, const double* W, const double* b, double extra_jitter, double* a_out,
+                           double* Ka_out, double* logdet_out);
+/* The B statistics at the mode (laplace.py:247, :333-351) for W at f_hat: diagKiWi_out (N) = diag(K - K K_Wi_i K) =
+ * Kdiag - colsumsq(L_B^-1 W^1/2 K) (:347-348), *logdet_out = logdet_I_KW (:351); B^-1 stays resident for gradients / fetch. */
+int mi355gp_laplace_finish(mi355gp_ctx* ctx, const double* W, double extra_jitter, double* diagKiWi_out, double* logdet_out);
+/* Kernel gradients at the mode (laplace.py:257-272 with kern.update_gradients_full applied to that dL_dK): Ki_f = Ki_fhat,
+ * dL_dfhat = -0.5 diag(Ki_W_i) dW_df (both N).  dL_dK = 0.5 (Ki_f Ki_f^T - K_Wi_i) + Ki_f dL_dfhat^T (I - K K_Wi_i) is formed
+ * on the device in its symmetrised form (every dK/dtheta is symmetric, so the gradients are the same) and reduced per part;
+ * dtheta_out as in mi355gp_exact_inference_sum.  Afterwards mi355gp_fetch gives MI355GP_FETCH_DLDK = that symmetrised
+ * dL_dK, MI355GP_FETCH_KINV = K_Wi_i = W^1/2 B^-1 W^1/2 (the posterior's woodbury_inv, :338) and MI355GP_FETCH_K = K;
+ * MI355GP_FETCH_L is an error (there is no Cholesky factor of Ky). */
+int mi355gp_laplace_gradients(mi355gp_ctx* ctx, const double* Ki_f, const double* dL_dfhat, double* dtheta_out);
+/* Posterior._raw_predict for Posterior(woodbury_vector = Ki_fhat, woodbury_inv = K_Wi_i, K) (posterior.py:198-262 as built at
+ * laplace.py:146): mu_out (M) = K(Xnew, X) wv; full_cov == 0: var_out (M) = Kdiag(Xnew) - colsumsq(L_B^-1 W^1/2 K(X, Xnew)),
+ * else M x M.  `parts` = the kernel of the session; needs mi355gp_laplace_finish. */
+int mi355gp_laplace_predict(mi355gp_ctx* ctx, int nparts, const mi355gp_part* parts, const double* Xnew, int64_t M,
+                            const double* wv, double* mu_out, double* var_out, int full_cov);
+
 /* Posterior covariance between two point sets (Posterior.covariance_between_points, posterior.py:109-130) */
 int mi355gp_covariance_between_points(mi355gp_ctx* ctx, int nparts, const mi355gp_part* parts, const double* X1,
                                       int64_t M1, const double* X2, int64_t M2, double* out);
