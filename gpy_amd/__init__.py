@@ -10,21 +10,22 @@ from . import _lib
 from ._lib import MI355GPError, build, device_count
 from .inference import ExactGaussianInference, ExactStudentTInference
 from .laplace import Laplace, LaplacePosterior
+from .ep import EP
 from .kern import (OU, RBF, Add, Prod, Bias, Coregionalize, ExpQuad, Exponential, Linear, Matern32, Matern52, MLP, Poly, RatQuad,
                    Stationary, StdPeriodic, White)
 from .likelihoods import Bernoulli, Gaussian, HeteroscedasticGaussian, MixedNoise
 from .models import GP, GPClassification, GPCoregionalizedRegression, GPHeteroscedasticRegression, GPRegression
-from .posterior import PosteriorExact, StudentTPosterior
+from .posterior import PosteriorEP, PosteriorExact, StudentTPosterior
 from .sparse import SparseGP, SparseGPRegression, VarDTC
 
 __all__ = ["RBF", "OU", "ExpQuad", "HeteroscedasticGaussian", "StudentTPosterior", "Matern52", "Matern32", "Exponential", "RatQuad", "StdPeriodic", "Coregionalize", "Linear", "MLP", "Poly", "MixedNoise", "Stationary", "White", "Bias", "Add", "Prod", "Gaussian", "ExactGaussianInference", "ExactStudentTInference",
-           "PosteriorExact", "GP", "GPRegression", "GPHeteroscedasticRegression", "GPCoregionalizedRegression", "Laplace", "LaplacePosterior", "Bernoulli", "GPClassification", "VarDTC", "SparseGP", "SparseGPRegression", "MI355GPError", "build", "device_count"]
+           "PosteriorExact", "GP", "GPRegression", "GPHeteroscedasticRegression", "GPCoregionalizedRegression", "Laplace", "LaplacePosterior", "EP", "PosteriorEP", "Bernoulli", "GPClassification", "VarDTC", "SparseGP", "SparseGPRegression", "MI355GPError", "build", "device_count"]
 
 # GPy's import paths, so that `import gpy_amd as GPy` reads like the reference on this path:
 #   GPy.kern.RBF, GPy.likelihoods.Gaussian, GPy.models.GPRegression / SparseGPRegression / GPHeteroscedasticRegression,
 #   GPy.models.GPClassification, GPy.likelihoods.Bernoulli, GPy.likelihoods.link_functions.Probit,
-#   GPy.core.GP / SparseGP, GPy.inference.latent_function_inference.ExactGaussianInference / VarDTC / Laplace
-from . import inference, kern, laplace, likelihoods, link_functions, linalg, models, sparse, util  # noqa: E402
+#   GPy.core.GP / SparseGP, GPy.inference.latent_function_inference.ExactGaussianInference / VarDTC / Laplace / EP
+from . import ep, inference, kern, laplace, likelihoods, link_functions, linalg, models, sparse, util  # noqa: E402
 import types as _types  # noqa: E402
 
 models.SparseGPRegression = SparseGPRegression
@@ -33,6 +34,7 @@ likelihoods.mixed_noise = _types.SimpleNamespace(MixedNoise=MixedNoise)
 inference.latent_function_inference = _types.SimpleNamespace(
     ExactGaussianInference=ExactGaussianInference, ExactStudentTInference=ExactStudentTInference, VarDTC=VarDTC,
     PosteriorExact=PosteriorExact, StudentTPosterior=StudentTPosterior, Laplace=Laplace,
-    laplace=_types.SimpleNamespace(Laplace=Laplace),
+    laplace=_types.SimpleNamespace(Laplace=Laplace), EP=EP, PosteriorEP=PosteriorEP,
+    expectation_propagation=_types.SimpleNamespace(EP=EP), posterior=_types.SimpleNamespace(PosteriorEP=PosteriorEP, PosteriorExact=PosteriorExact),
     exact_gaussian_inference=_types.SimpleNamespace(ExactGaussianInference=ExactGaussianInference),
     var_dtc=_types.SimpleNamespace(VarDTC=VarDTC))

@@ -57,6 +57,7 @@ def make_parts(specs):
         ntheta += th.size
     return arr, keep, ntheta
 FETCH_L, FETCH_KINV, FETCH_DLDK, FETCH_K = 0, 1, 2, 3
+EP_BERNOULLI_PROBIT = 0
 OUT_LML, OUT_LOGDET, OUT_DATAFIT, OUT_DNOISE, OUT_TRKINV, NUM_OUT = 0, 1, 2, 3, 4, 8
 STAGE_NAMES = ("kbuild", "potrf", "trtri", "lauum", "solve", "grad", "total")
 NUM_T = 8
@@ -131,6 +132,9 @@ def lib():
     L.mi355gp_laplace_finish.argtypes = [vp, _dp, cd, _dp, _c_dp]
     L.mi355gp_laplace_gradients.argtypes = [vp, _dp, _dp, _dp]
     L.mi355gp_laplace_predict.argtypes = [vp, ci, ctypes.POINTER(Part), _dp, i64, _dp, _c_dp, _c_dp, ci]
+    L.mi355gp_ep_recompute.argtypes = [vp, _dp, _dp, cd, cd, ci, _dp, _dp, _c_dp, _c_dp]
+    L.mi355gp_ep_sweep.argtypes = [vp, ci, ndpointer(dtype=np.int64, flags="C_CONTIGUOUS"), _dp, cd, cd, _dp, _dp, _dp, _dp, _dp, _dp,
+                                   _dp, _c_dp]
     L.mi355gp_inference_given_K.argtypes = [vp, _dp, _dp, i64, cd, cd, _dp, _c_dp, _c_dp, _c_dp]
     L.mi355gp_fetch.argtypes = [vp, ci, _dp, ci]
     L.mi355gp_predict.argtypes = [vp, ci, ci, _dp, _dp, i64, _c_dp, _c_dp, ci]
@@ -193,7 +197,7 @@ def lib():
                  "predictive_gradients_sum", "dbg_pipe_share", "pdinv_full", "dbg_graph_factor", "get_option",
                  "sparse_get_profile", "dbg_persist", "dbg_grid_multi", "dbg_update_nt", "dbg_update_rect",
                  "dbg_ipc_selftest", "laplace_begin", "laplace_newton", "laplace_finish", "laplace_gradients",
-                 "laplace_predict"):
+                 "laplace_predict", "ep_recompute", "ep_sweep"):
         getattr(L, "mi355gp_" + name).restype = ci
     _lib = L
     return L
@@ -216,7 +220,7 @@ EXPORTED = ("mi355gp_last_error", "mi355gp_version", "mi355gp_device_count", "mi
             "mi355gp_sparse_get_profile", "mi355gp_dbg_persist", "mi355gp_dbg_grid_multi", "mi355gp_dbg_update_nt", "mi355gp_dbg_update_rect",
             "mi355gp_dbg_ipc_selftest", "mi355gp_grid_coll_log", "mi355gp_dbg_lauum_plan", "mi355gp_dbg_persist_owners",
             "mi355gp_laplace_begin", "mi355gp_laplace_newton", "mi355gp_laplace_finish", "mi355gp_laplace_gradients",
-            "mi355gp_laplace_predict")
+            "mi355gp_laplace_predict", "mi355gp_ep_recompute", "mi355gp_ep_sweep")
 
 
 # mi355gp_set_option / mi355gp_get_option ids (include/mi355gp.h, MI355GP_OPT_*)
@@ -447,6 +451,34 @@ class Context(object):
         if var is not None and not full_cov:
             var = var[:, None]
         return mu, var
+
+    # ---- EP inside a Laplace session (include/mi355gp.h: recompute, sweep; the final pass is newton / finish / gradients) ----
+    def ep_recompute(self, tau, v, extra_jitter=0.0, add_diag=0.0, want_sigma=True, want_ms=False):
+        """`posteriorParams._recompute` (reference `expectation_propagation.py:129-143`): (info, mu, diag(Sigma), logdet B[, ms]);
+        with `want_sigma` the full Sigma stays on the device for `ep_sweep`."""
+        tau, v = f64(np.ravel(tau)), f64(np.ravel(v))
+        assert tau.size == self.N and v.size == self.N
+        mu, sd = np.empty(self.N), np.empty(self.N)
+        ld, ms = ctypes.c_double(0.0), ctypes.c_double(0.0)
+        rc = check(lib().mi355gp_ep_recompute(self._h, tau, v, float(extra_jitter), float(add_diag), int(bool(want_sigma)), mu, sd,
+                                              ctypes.byref(ld), ctypes.byref(ms)), "mi355gp_ep_recompute")
+        return (rc, mu, sd, ld.value) + ((ms.value,) if want_ms else ())
+
+    def ep_sweep(self, order, ysign, tau, v, eta=1.0, delta=1.0, lik=EP_BERNOULLI_PROBIT, want_ms=False):
+        """One sequential pass of `_local_updates` (reference `expectation_propagation.py:330-351`) on the device:
+        dict(tau, v (updated copies), cav_tau, cav_v, log_Z_hat, mu, Sigma_diag[, ms])."""
+        order = np.ascontiguousarray(np.ravel(order), dtype=np.int64)
+        ysign = f64(np.ravel(ysign))
+        tau, v = f64(np.ravel(tau)).copy(), f64(np.ravel(v)).copy()
+        assert order.size == self.N and ysign.size == self.N and tau.size == self.N and v.size == self.N
+        o = [np.empty(self.N) for _ in range(5)]
+        ms = ctypes.c_double(0.0)
+        check(lib().mi355gp_ep_sweep(self._h, int(lik), order, ysign, float(eta), float(delta), tau, v, o[0], o[1], o[2], o[3], o[4],
+                                     ctypes.byref(ms)), "mi355gp_ep_sweep")
+        r = dict(tau=tau, v=v, cav_tau=o[0], cav_v=o[1], log_Z_hat=o[2], mu=o[3], Sigma_diag=o[4])
+        if want_ms:
+            r["ms"] = ms.value
+        return r
 
     def set_option(self, name, value):
         """Options of THIS context through the C-ABI (`mi355gp_set_option`; the MI355GP_* environment variables only give the

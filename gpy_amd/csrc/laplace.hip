@@ -10,18 +10,7 @@
 #include <cstring>
 #include <vector>
 
-#include "ctx.h"
-
-struct LaplaceSession {
-    double* K = nullptr;            // npad x npad, symmetric, no noise, no jitter, exact Kdiag on the diagonal
-    FactorWs ws;
-    bool ws_ok = false;
-    double* vec = nullptr;          // NVEC device vectors of npad doubles + 8 scalars
-    double* part = nullptr;         // partials of launch_symv_lower
-    double* coregPart = nullptr;    // 2048 P x P records of the unfused Coregionalize reduction (first kind-8 part)
-    std::vector<double> host;       // staging of the small results
-};
-enum { LV_W = 0, LV_SW, LV_B, LV_A, LV_KA, LV_T0, LV_T1, LV_T2, LV_KD, LV_DIAG, LV_U, LV_S, LV_NUM };
+#include "lap_session.h"
 
 void laplace_session_free(LaplaceSession* s) {
     if (!s) return;
@@ -31,9 +20,6 @@ void laplace_session_free(LaplaceSession* s) {
     if (s->ws_ok) factor_ws_free(&s->ws);
     delete s;
 }
-
-static inline double* lvec(const mi355gp_ctx* c, int which) { return c->lap->vec + (size_t)which * c->npad; }
-static inline double* lscal(const mi355gp_ctx* c) { return c->lap->vec + (size_t)LV_NUM * c->npad; }
 
 // elementwise helpers on N-vectors (grid: ceil(n / 256) blocks of 256)
 __global__ void k_lap_sqrt(const double* __restrict__ w, long n, double* __restrict__ sw) {
@@ -74,7 +60,7 @@ __global__ void k_lap_extract_full(const double* __restrict__ A, long ld, long n
 #define VGRID(n) dim3((unsigned)(((n) + 255) / 256)), dim3(256)
 #define MGRID(n) dim3((unsigned)(((n) + 255) / 256), (unsigned)(n)), dim3(256)
 
-static int check_W(const double* W, long n, const char* where) {
+int lap_check_W(const double* W, long n, const char* where) {
     for (long i = 0; i < n; ++i) {
         if (std::isnan(W[i])) {
             mi355gp_set_error("%s: One or more element(s) of W is NaN (element %ld)", where, i);
@@ -87,7 +73,7 @@ static int check_W(const double* W, long n, const char* where) {
     }
     return 0;
 }
-static int check_vec(const double* v, long n, const char* where, const char* name) {
+int lap_check_vec(const double* v, long n, const char* where, const char* name) {
     for (long i = 0; i < n; ++i)
         if (!std::isfinite(v[i])) {
             mi355gp_set_error("%s: %s[%ld] = %g is not finite", where, name, i, v[i]);
@@ -97,8 +83,9 @@ static int check_vec(const double* v, long n, const char* where, const char* nam
 }
 
 // W (device, LV_W) -> sw, B into A, L_B in place, X = L_B^-1 into the context's B buffer; all enqueued, nothing read back
-static void enqueue_factor(mi355gp_ctx* c, double jit) {
+void lap_enqueue_factor(mi355gp_ctx* c, double jit) {
     LaplaceSession* L = c->lap;
+    L->ep_sigma = false;                                     // A is overwritten: a resident EP Sigma is gone
     hipStream_t st = c->st;
     const long n = c->n, np = c->npad;
     hipLaunchKernelGGL(k_lap_sqrt, VGRID(n), 0, st, lvec(c, LV_W), n, lvec(c, LV_SW));
@@ -109,12 +96,12 @@ static void enqueue_factor(mi355gp_ctx* c, double jit) {
     trtri_device(st, c->A, c->B, c->C, np, &L->ws);
 }
 // t = B^-1 r = X^T (X r)
-static void enqueue_Binv(mi355gp_ctx* c, const double* r, double* t) {
+void lap_enqueue_Binv(mi355gp_ctx* c, const double* r, double* t) {
     launch_tri_matvec(c->st, c->B, c->npad, c->n, r, 1, c->dTmp, t, c->dTrmvPart);
 }
 // after the stream has drained: info of the factorisation (from the scalar block).  Returns 1 = redo (persistent launch called
 // off), 0 = go on (*info_out: LAPACK info), < 0 error
-static int factor_outcome(mi355gp_ctx* c, int info, int attempt, int* info_out) {
+int lap_factor_outcome(mi355gp_ctx* c, int info, int attempt, int* info_out) {
     bool clean = false;
     if (potrf_persist_aborted(info, &c->lap->ws, &clean)) {
         if (attempt == 0) return 1;                          // B is rebuilt from the resident K either way
@@ -153,6 +140,7 @@ int mi355gp_laplace_begin(mi355gp_ctx* c, int nparts, const mi355gp_part* parts)
     c->have_kernel = true;
     c->have_factor = false;                                   // A / B / C belong to the session from here on
     c->lap_stage = 0;
+    L->ep_sigma = false;
     ctx_scale_parts(c);
     // K = sum_t prod_f K_f, both triangles (the prediction-style products read it whole; the mat-vecs read its lower tiles)
     emit_expression(c->terms, L->K, c->Mbuf, false, [&](int p, double* dst, const double* mul, int acc, bool) {
@@ -171,8 +159,8 @@ int mi355gp_laplace_newton(mi355gp_ctx* c, const double* W, const double* b, dou
     ARG_CHECK(c && c->n > 0 && c->lap && c->lap_stage >= 1, "mi355gp_laplace_newton: call mi355gp_laplace_begin first");
     ARG_CHECK(W && b && a_out && Ka_out, "mi355gp_laplace_newton: NULL argument");
     const long n = c->n, np = c->npad;
-    if (int rc = check_W(W, n, "mi355gp_laplace_newton")) return rc;
-    if (int rc = check_vec(b, n, "mi355gp_laplace_newton", "b")) return rc;
+    if (int rc = lap_check_W(W, n, "mi355gp_laplace_newton")) return rc;
+    if (int rc = lap_check_vec(b, n, "mi355gp_laplace_newton", "b")) return rc;
     HIP_CHECK(hipSetDevice(c->device));
     EngineShared gate(c->device);
     LaplaceSession* L = c->lap;
@@ -183,11 +171,11 @@ int mi355gp_laplace_newton(mi355gp_ctx* c, const double* W, const double* b, dou
     L->host.resize((size_t)2 * np + 8);
     int info = 0;
     for (int attempt = 0;; ++attempt) {
-        enqueue_factor(c, extra_jitter);
+        lap_enqueue_factor(c, extra_jitter);
         // a = b - W^1/2 B^-1 (W^1/2 K b), then K a   (laplace.py:193-198; f_trial = f + s K dKi_f is linear in the step, :202-208)
         launch_symv_lower(st, L->K, np, n, lvec(c, LV_B), nullptr, lvec(c, LV_T0), nullptr, L->part);
         hipLaunchKernelGGL(k_lap_mul, VGRID(n), 0, st, lvec(c, LV_SW), lvec(c, LV_T0), n, lvec(c, LV_T1));
-        enqueue_Binv(c, lvec(c, LV_T1), lvec(c, LV_T2));
+        lap_enqueue_Binv(c, lvec(c, LV_T1), lvec(c, LV_T2));
         hipLaunchKernelGGL(k_lap_sub_scaled, VGRID(n), 0, st, lvec(c, LV_B), lvec(c, LV_SW), lvec(c, LV_T2), n, lvec(c, LV_A));
         launch_symv_lower(st, L->K, np, n, lvec(c, LV_A), nullptr, lvec(c, LV_KA), nullptr, L->part);
         launch_scalars(st, lvec(c, LV_A), lvec(c, LV_A), nullptr, 0, n, 1, L->ws.logsum, L->ws.nblk, lscal(c), nullptr, L->ws.info);
@@ -196,7 +184,7 @@ int mi355gp_laplace_newton(mi355gp_ctx* c, const double* W, const double* b, dou
         HIP_CHECK(hipMemcpyAsync(L->host.data() + 2 * np, lscal(c), sizeof(double) * 8, hipMemcpyDeviceToHost, st));
         HIP_CHECK(hipStreamSynchronize(st));
         HIP_CHECK(hipGetLastError());
-        const int rc = factor_outcome(c, (int)L->host[(size_t)2 * np + 6], attempt, &info);
+        const int rc = lap_factor_outcome(c, (int)L->host[(size_t)2 * np + 6], attempt, &info);
         if (rc < 0) return rc;
         if (rc == 0) break;
     }
@@ -212,7 +200,7 @@ int mi355gp_laplace_finish(mi355gp_ctx* c, const double* W, double extra_jitter,
     ARG_CHECK(c && c->n > 0 && c->lap && c->lap_stage >= 1, "mi355gp_laplace_finish: call mi355gp_laplace_begin first");
     ARG_CHECK(W && diagKiWi_out && logdet_out, "mi355gp_laplace_finish: NULL argument");
     const long n = c->n, np = c->npad;
-    if (int rc = check_W(W, n, "mi355gp_laplace_finish")) return rc;
+    if (int rc = lap_check_W(W, n, "mi355gp_laplace_finish")) return rc;
     HIP_CHECK(hipSetDevice(c->device));
     EngineShared gate(c->device);
     LaplaceSession* L = c->lap;
@@ -223,7 +211,7 @@ int mi355gp_laplace_finish(mi355gp_ctx* c, const double* W, double extra_jitter,
     const int nt = (int)(np / NB);
     int info = 0;
     for (int attempt = 0;; ++attempt) {
-        enqueue_factor(c, extra_jitter);
+        lap_enqueue_factor(c, extra_jitter);
         // diag(Ki_W_i) = Kdiag - colsumsq(X (W^1/2 K))  (laplace.py:347-348): the scaled K goes through A (L_B is not needed
         // once X exists), the product through C; then C = B^-1 = X^T X
         launch_rowscale_sqrt(st, L->K, np, n, np, lvec(c, LV_W), c->A);
@@ -236,7 +224,7 @@ int mi355gp_laplace_finish(mi355gp_ctx* c, const double* W, double extra_jitter,
         HIP_CHECK(hipMemcpyAsync(L->host.data() + 2 * np, lscal(c), sizeof(double) * 8, hipMemcpyDeviceToHost, st));
         HIP_CHECK(hipStreamSynchronize(st));
         HIP_CHECK(hipGetLastError());
-        const int rc = factor_outcome(c, (int)L->host[(size_t)2 * np + 6], attempt, &info);
+        const int rc = lap_factor_outcome(c, (int)L->host[(size_t)2 * np + 6], attempt, &info);
         if (rc < 0) return rc;
         if (rc == 0) break;
     }
@@ -251,8 +239,8 @@ int mi355gp_laplace_gradients(mi355gp_ctx* c, const double* Ki_f, const double* 
     ARG_CHECK(c && c->n > 0 && c->lap && c->lap_stage >= 3, "mi355gp_laplace_gradients: call mi355gp_laplace_finish first");
     ARG_CHECK(Ki_f && dL_dfhat && dtheta_out, "mi355gp_laplace_gradients: NULL argument");
     const long n = c->n, np = c->npad;
-    if (int rc = check_vec(Ki_f, n, "mi355gp_laplace_gradients", "Ki_f")) return rc;
-    if (int rc = check_vec(dL_dfhat, n, "mi355gp_laplace_gradients", "dL_dfhat")) return rc;
+    if (int rc = lap_check_vec(Ki_f, n, "mi355gp_laplace_gradients", "Ki_f")) return rc;
+    if (int rc = lap_check_vec(dL_dfhat, n, "mi355gp_laplace_gradients", "dL_dfhat")) return rc;
     HIP_CHECK(hipSetDevice(c->device));
     EngineShared gate(c->device);
     LaplaceSession* L = c->lap;
@@ -262,7 +250,7 @@ int mi355gp_laplace_gradients(mi355gp_ctx* c, const double* Ki_f, const double* 
     // u = (I - K_Wi_i K) dL_dfhat, K_Wi_i = W^1/2 B^-1 W^1/2: the implicit part a dL_dfhat^T (I - K K_Wi_i) is a u^T (laplace.py:257-270)
     launch_symv_lower(st, L->K, np, n, lvec(c, LV_S), nullptr, lvec(c, LV_T0), nullptr, L->part);
     hipLaunchKernelGGL(k_lap_mul, VGRID(n), 0, st, lvec(c, LV_SW), lvec(c, LV_T0), n, lvec(c, LV_T1));
-    enqueue_Binv(c, lvec(c, LV_T1), lvec(c, LV_T2));
+    lap_enqueue_Binv(c, lvec(c, LV_T1), lvec(c, LV_T2));
     hipLaunchKernelGGL(k_lap_sub_scaled, VGRID(n), 0, st, lvec(c, LV_S), lvec(c, LV_SW), lvec(c, LV_T2), n, lvec(c, LV_U));
     // dL_dK, symmetrised, into A (what finish left there is spent); C keeps B^-1 for MI355GP_FETCH_KINV and prediction keeps X
     launch_laplace_dLdK(st, c->C, np, n, lvec(c, LV_SW), lvec(c, LV_A), lvec(c, LV_U), c->A);
@@ -314,7 +302,7 @@ int mi355gp_laplace_predict(mi355gp_ctx* c, int nparts, const mi355gp_part* part
     ARG_CHECK(c && c->n > 0 && c->lap && c->lap_stage >= 3, "mi355gp_laplace_predict: call mi355gp_laplace_finish first");
     ARG_CHECK(Xnew && M > 0 && wv && mu_out, "mi355gp_laplace_predict: bad arguments");
     const long n = c->n, np = c->npad, mp = round_up(M, NB);
-    if (int rc = check_vec(wv, n, "mi355gp_laplace_predict", "woodbury_vector")) return rc;
+    if (int rc = lap_check_vec(wv, n, "mi355gp_laplace_predict", "woodbury_vector")) return rc;
     HIP_CHECK(hipSetDevice(c->device));
     EngineShared gate(c->device);
     if (int rc = ctx_prepare_parts(c, nparts, parts)) return rc;

@@ -191,6 +191,43 @@ class Bernoulli(Parameterized):
     def exact_inference_gradients(self, dL_dKdiag, Y_metadata=None):
         return np.zeros(self.size)
 
+    # ---- EP (reference `bernoulli.py:59-92`) -----------------------------------------------------------------------------
+    def _ep_sign(self, Y_i):
+        Y_i = np.asarray(Y_i, dtype=np.float64)
+        if not np.all((Y_i == 1) | (Y_i == 0) | (Y_i == -1)):
+            raise ValueError("bad value for Bernoulli observation (0, 1)")
+        return np.where(Y_i == 1, 1.0, -1.0)
+
+    def log_moments_match_ep(self, Y_i, tau_i, v_i):
+        """(log Z_hat, mu_hat, sigma2_hat) of the tilted distribution of a cavity N(v / tau, 1 / tau), scalars or arrays.  With
+        z = sign v / sqrt(tau^2 + tau): log Z_hat = log Phi(z) and phi(z) / Phi(z) from their definitions, through the scaled
+        complementary error function where Phi underflows (z < 0), so both hold over the whole real line."""
+        from scipy import special
+        if not isinstance(self.gp_link, link_functions.Probit):
+            raise NotImplementedError("exact EP moment matching on this backend needs the probit link, not %s"
+                                      % type(self.gp_link).__name__)
+        sign = self._ep_sign(Y_i)
+        tau_i, v_i = np.asarray(tau_i, dtype=np.float64), np.asarray(v_i, dtype=np.float64)
+        q = tau_i ** 2 + tau_i
+        z = sign * v_i / np.sqrt(q)
+        zn = np.minimum(z, 0.0)
+        with np.errstate(over="ignore", under="ignore"):
+            ratio = np.where(z < 0.0, np.sqrt(2.0 / np.pi) / special.erfcx(-zn / np.sqrt(2.0)),
+                             np.exp(-0.5 * z * z) / np.sqrt(2.0 * np.pi) / special.ndtr(np.maximum(z, 0.0)))
+        log_Z_hat = special.log_ndtr(z)
+        mu_hat = v_i / tau_i + sign * ratio / np.sqrt(q)
+        sigma2_hat = 1.0 / tau_i - (ratio / q) * (z + ratio)
+        return log_Z_hat, mu_hat, sigma2_hat
+
+    def moments_match_ep(self, Y_i, tau_i, v_i, Y_metadata_i=None):
+        """(Z_hat, mu_hat, sigma2_hat) as the reference returns them (`bernoulli.py:92`)"""
+        log_Z_hat, mu_hat, sigma2_hat = self.log_moments_match_ep(Y_i, tau_i, v_i)
+        return np.exp(log_Z_hat), mu_hat, sigma2_hat
+
+    def ep_gradients(self, Y, cav_tau, cav_v, dL_dKdiag, Y_metadata=None, quad_mode="gh", boost_grad=1.):
+        """no parameters, no gradients (reference `likelihood.py:227-228` for `size == 0`)"""
+        return np.zeros(0)
+
     # ---- in terms of lambda = link(f) (reference `bernoulli.py:138-249`) -------------------------------------------------
     def pdf_link(self, inv_link_f, y, Y_metadata=None):
         return np.where(y == 1, inv_link_f, 1.0 - inv_link_f)

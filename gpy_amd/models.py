@@ -266,10 +266,17 @@ class GP(PredictionCallers, Parameterized):
             except np.linalg.LinAlgError:
                 return 1e300, np.zeros_like(z)
             return self.objective_function(), self.objective_function_gradients() * np.exp(z)
+        self._optimization_hook("on_optimization_start")              # (reference `core/gp.py:677-684`)
         res = minimize(f, x0, jac=True, method="L-BFGS-B", options={"maxiter": max_iters, "gtol": gtol,
                                                                      "disp": bool(messages)})
         self.param_array = np.exp(res.x)
+        self._optimization_hook("on_optimization_end")
         return res
+
+    def _optimization_hook(self, name):
+        hook = getattr(getattr(self, "inference_method", None), name, None)
+        if hook is not None:
+            hook()
 
     def _optimize_mixed(self, pos, max_iters, messages, gtol):
         from scipy.optimize import minimize
@@ -289,9 +296,11 @@ class GP(PredictionCallers, Parameterized):
             except np.linalg.LinAlgError:
                 return 1e300, np.zeros_like(z)
             return self.objective_function(), self.objective_function_gradients() * np.where(pos, p, 1.0)
+        self._optimization_hook("on_optimization_start")
         res = minimize(f, x0, jac=True, method="L-BFGS-B", options={"maxiter": max_iters, "gtol": gtol,
                                                                      "disp": bool(messages)})
         self.param_array = params(res.x)
+        self._optimization_hook("on_optimization_end")
         return res
 
 
@@ -310,16 +319,17 @@ class GPRegression(GP):
 
 class GPClassification(GP):
     """Gaussian-process classification (reference `GPy/models/gp_classification.py:10-39`): the reference's signature and its
-    defaults RBF and Bernoulli.  The reference's default inference is EP, which this backend does not have: rather than compute
-    something else silently, `inference_method=None` raises and names the alternative."""
+    defaults RBF and Bernoulli.  The reference's default inference is EP; this backend has both EP and the Laplace approximation
+    and, for now, asks for the choice to be explicit: `inference_method=None` raises and names the two."""
 
     def __init__(self, X, Y, kernel=None, Y_metadata=None, mean_function=None, inference_method=None, likelihood=None,
                  normalizer=False, device=0):
         from .likelihoods import Bernoulli
         if inference_method is None:
             raise NotImplementedError(
-                "GPy's GPClassification defaults to EP (expectation propagation), which gpy_amd does not implement; "
-                "pass inference_method=gpy_amd.Laplace() for the Laplace approximation")
+                "GPy's GPClassification defaults to EP (expectation propagation); this backend asks for the choice to be "
+                "explicit: pass inference_method=gpy_amd.EP() for expectation propagation or "
+                "inference_method=gpy_amd.Laplace() for the Laplace approximation")
         if kernel is None:
             kernel = RBF(np.asarray(X).shape[1], device=device)
         if likelihood is None:

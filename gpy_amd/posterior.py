@@ -97,3 +97,19 @@ class StudentTPosterior(PosteriorExact):
         beta = self._beta if self._beta is not None else float(np.sum(self.woodbury_vector * self.mean))
         N = self.woodbury_vector.shape[0]
         return mean_jac, (self.nu + beta - 2.0) / (self.nu + N - 2.0) * var_jac
+
+
+class PosteriorEP(PosteriorExact):
+    """Posterior(woodbury_vector = alpha, woodbury_inv = Wi = S^1/2 B^-1 S^1/2, K) of the EP approximation (reference
+    `expectation_propagation.py:395`, `posterior.py:305-336`): there is no Cholesky factor of a Ky, so `woodbury_chol` is None;
+    `_raw_predict` runs on the device through the session that produced it."""
+
+    def __init__(self, woodbury_vector, woodbury_inv, K, state=None):
+        super(PosteriorEP, self).__init__(woodbury_chol=None, woodbury_vector=woodbury_vector, K=K, woodbury_inv=woodbury_inv,
+                                          state=state)
+
+    def predictive_gradients(self, kern, Xnew, pred_var=None):
+        raise NotImplementedError("predictive_gradients is not implemented for a non-Gaussian likelihood on this backend")
+
+    def covariance_between_points(self, kern, X, X1, X2):
+        raise NotImplementedError("covariance_between_points is not implemented for a non-Gaussian likelihood on this backend")

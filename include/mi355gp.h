@@ -250,6 +250,32 @@ int mi355gp_laplace_gradients(mi355gp_ctx* ctx, const double* Ki_f, const double
 int mi355gp_laplace_predict(mi355gp_ctx* ctx, int nparts, const mi355gp_part* parts, const double* Xnew, int64_t M,
                             const double* wv, double* mu_out, double* var_out, int full_cov);
 
+/* ---- Expectation propagation inside a Laplace session (one output column, zero prior mean) -----------------------------------
+ * The two parts of EP.expectation_propagation (inference/latent_function_inference/expectation_propagation.py:279-310) that are
+ * EP and nothing else; they need mi355gp_laplace_begin (K resident).  After convergence the session's own calls give the rest
+ * with W = tau_tilde, b = v_tilde: mi355gp_laplace_newton returns alpha (:386-387), mu and log det B (:367), then
+ * mi355gp_laplace_finish, mi355gp_laplace_gradients(Ki_f = alpha, dL_dfhat = 0) (dL_dK = 0.5 (alpha alpha^T - Wi), :393) and
+ * mi355gp_laplace_predict (PosteriorEP._raw_predict, posterior.py:305-336). */
+enum { MI355GP_EP_BERNOULLI_PROBIT = 0 };
+/* posteriorParams._recompute (:129-143): B = I + S^1/2 K S^1/2 + extra_jitter I with S = diag(tau) (N, finite, >= 0), its factor
+ * (info > 0 when not positive definite, as mi355gp_laplace_newton), mu_out (N) = K alpha with alpha = v - S^1/2 B^-1 S^1/2 K v,
+ * sigdiag_out (N) = diag(Sigma) + add_diag, *logdet_out (optional) = 2 sum log diag L_B.  want_sigma != 0: the full symmetric
+ * Sigma = K - V^T V, V = L_B^-1 S^1/2 K (:136-137), is formed in one of the session's work buffers with add_diag on its diagonal
+ * (the 1e-7 of _init_approximations, :319, :326) and stays resident, with mu, for mi355gp_ep_sweep; any other session call
+ * overwrites it.  want_sigma == 0: only the diagonal, Kdiag - colsumsq(V).  tau = v = 0 gives Sigma = K + add_diag I, mu = 0
+ * (the cold start of :316-321).  *ms_out (optional): device time of the enqueued work between two events. */
+int mi355gp_ep_recompute(mi355gp_ctx* ctx, const double* tau, const double* v, double extra_jitter, double add_diag,
+                         int want_sigma, double* mu_out, double* sigdiag_out, double* logdet_out, double* ms_out);
+/* One pass of _local_updates (:330-351) with parallel_updates=False over the sites in `order` (N, a permutation of 0 .. N-1), on
+ * the device: cavity (:27-29), moment matching of likelihood `lik` (MI355GP_EP_BERNOULLI_PROBIT: bernoulli.py:73-79, carried
+ * as log Z_hat), site update with fractional power eta, damping delta and the clamp of tau at machine epsilon (:52-68), rank-one
+ * update of mu and Sigma (:101-105).  ysign (N): +1 / -1 per row.  tau, v (N): in / out.  cav_tau_out, cav_v_out, logZhat_out
+ * (N, by site), mu_out, sigdiag_out (N, after the sweep).  2 N launches on the context's stream, no host synchronisation inside;
+ * the same inputs give the same bits.  Needs mi355gp_ep_recompute with want_sigma as the last session call (or a sweep). */
+int mi355gp_ep_sweep(mi355gp_ctx* ctx, int lik, const int64_t* order, const double* ysign, double eta, double delta, double* tau,
+                     double* v, double* cav_tau_out, double* cav_v_out, double* logZhat_out, double* mu_out, double* sigdiag_out,
+                     double* ms_out);
+
 /* Posterior covariance between two point sets (Posterior.covariance_between_points, posterior.py:109-130) */
 int mi355gp_covariance_between_points(mi355gp_ctx* ctx, int nparts, const mi355gp_part* parts, const double* X1,
                                       int64_t M1, const double* X2, int64_t M2, double* out);
