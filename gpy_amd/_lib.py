@@ -274,6 +274,30 @@ def theta_vec(variance, lengthscale, ARD, D):
     return np.concatenate([[float(np.asarray(variance).ravel()[0])], ls])
 
 
+def _exact_result(out, ms, **arrays):
+    """the result dict of the exact-inference entries from their scalar block, stage times and output arrays"""
+    res = dict(lml=out[OUT_LML], logdet=out[OUT_LOGDET], datafit=out[OUT_DATAFIT], dnoise=out[OUT_DNOISE],
+               trKinv=out[OUT_TRKINV], **arrays)
+    if ms is not None:
+        res["stage_ms"] = dict(zip(STAGE_NAMES, ms[:len(STAGE_NAMES)]))
+    return res
+
+
+def _predict(entry, head, Xnew, D, Dy, full_cov, want_var, between=()):
+    """the shared part of the predict entries, which all end (..., Xnew, M, [between,] mu, var, full_cov):
+    (mu (M x Dy), var (M x 1) or cov (M x M) or None)"""
+    Xnew = f64(Xnew)
+    M = Xnew.shape[0]
+    assert Xnew.shape[1] == D
+    mu = np.empty((M, Dy))
+    var = (np.empty((M, M)) if full_cov else np.empty(M)) if want_var else None
+    check(getattr(lib(), entry)(*(tuple(head) + (Xnew, M) + tuple(between) + (mu.ctypes.data_as(_c_dp), _opt(var),
+                                                                              int(bool(full_cov))))), entry)
+    if var is not None and not full_cov:
+        var = var[:, None]
+    return mu, var
+
+
 class Context(object):
     """One device context = one uploaded data set (X, R = Y - mean) with its N x N buffers in HBM."""
 
@@ -306,56 +330,35 @@ class Context(object):
         R = f64(R)
         check(lib().mi355gp_set_targets(self._h, R, R.shape[1]), "mi355gp_set_targets")
 
-    def exact_inference(self, kind, ARD, theta, noise, jitter=1e-8, extra_jitter=0.0, want_alpha=True,
-                        want_diag=False, want_stage_ms=False):
-        """Returns (info, dict).  info > 0: not positive definite (the caller runs GPy's jitter ladder)."""
-        theta = f64(theta)
-        noise = f64(np.atleast_1d(noise))
-        out = np.zeros(NUM_OUT)
-        alpha = np.empty((self.N, self.Dy)) if want_alpha else None
-        dtheta = np.zeros(theta.size)
-        diag = np.empty(self.N) if want_diag else None
-        ms = np.zeros(NUM_T) if want_stage_ms else None
-        rc = check(lib().mi355gp_exact_inference(self._h, KIND_IDS[kind], ard_id(kind, ARD), theta, noise, noise.size,
-                                                 jitter, extra_jitter, out, _opt(alpha), _opt(dtheta), _opt(diag),
-                                                 _opt(ms)), "mi355gp_exact_inference")
-        res = dict(lml=out[OUT_LML], logdet=out[OUT_LOGDET], datafit=out[OUT_DATAFIT], dnoise=out[OUT_DNOISE],
-                   trKinv=out[OUT_TRKINV], alpha=alpha, dtheta=dtheta, diag_dL_dK=diag)
-        if ms is not None:
-            res["stage_ms"] = dict(zip(STAGE_NAMES, ms[:len(STAGE_NAMES)]))
-        return rc, res
-
-    def exact_inference_sum(self, specs, noise, jitter=1e-8, extra_jitter=0.0, want_alpha=True, want_diag=False,
-                            want_stage_ms=False):
-        """Sum kernel: specs = [(kind, ARD, theta, active_dims or None)]; dtheta is the concatenation over the parts."""
-        arr, keep, ntheta = make_parts(specs)
+    def _exact(self, entry, head, ntheta, noise, jitter, extra_jitter, want_alpha, want_diag, want_stage_ms):
+        """the shared part of `exact_inference` / `exact_inference_sum`: (info, dict)"""
         noise = f64(np.atleast_1d(noise))
         out = np.zeros(NUM_OUT)
         alpha = np.empty((self.N, self.Dy)) if want_alpha else None
         dtheta = np.zeros(ntheta)
         diag = np.empty(self.N) if want_diag else None
         ms = np.zeros(NUM_T) if want_stage_ms else None
-        rc = check(lib().mi355gp_exact_inference_sum(self._h, len(specs), arr, noise, noise.size, jitter, extra_jitter,
-                                                     out, _opt(alpha), _opt(dtheta), _opt(diag), _opt(ms)),
-                   "mi355gp_exact_inference_sum")
-        res = dict(lml=out[OUT_LML], logdet=out[OUT_LOGDET], datafit=out[OUT_DATAFIT], dnoise=out[OUT_DNOISE],
-                   trKinv=out[OUT_TRKINV], alpha=alpha, dtheta=dtheta, diag_dL_dK=diag)
-        if ms is not None:
-            res["stage_ms"] = dict(zip(STAGE_NAMES, ms[:len(STAGE_NAMES)]))
-        return rc, res
+        rc = check(getattr(lib(), entry)(self._h, *(tuple(head) + (noise, noise.size, jitter, extra_jitter, out, _opt(alpha),
+                                                                   _opt(dtheta), _opt(diag), _opt(ms)))), entry)
+        return rc, _exact_result(out, ms, alpha=alpha, dtheta=dtheta, diag_dL_dK=diag)
+
+    def exact_inference(self, kind, ARD, theta, noise, jitter=1e-8, extra_jitter=0.0, want_alpha=True,
+                        want_diag=False, want_stage_ms=False):
+        """Returns (info, dict).  info > 0: not positive definite (the caller runs GPy's jitter ladder)."""
+        theta = f64(theta)
+        return self._exact("mi355gp_exact_inference", (KIND_IDS[kind], ard_id(kind, ARD), theta), theta.size, noise, jitter,
+                           extra_jitter, want_alpha, want_diag, want_stage_ms)
+
+    def exact_inference_sum(self, specs, noise, jitter=1e-8, extra_jitter=0.0, want_alpha=True, want_diag=False,
+                            want_stage_ms=False):
+        """Sum kernel: specs = [(kind, ARD, theta, active_dims or None)]; dtheta is the concatenation over the parts."""
+        arr, keep, ntheta = make_parts(specs)
+        return self._exact("mi355gp_exact_inference_sum", (len(specs), arr), ntheta, noise, jitter, extra_jitter, want_alpha,
+                           want_diag, want_stage_ms)
 
     def predict_sum(self, specs, Xnew, full_cov=False, want_var=True):
         arr, keep, _ = make_parts(specs)
-        Xnew = f64(Xnew)
-        M = Xnew.shape[0]
-        assert Xnew.shape[1] == self.D
-        mu = np.empty((M, self.Dy))
-        var = (np.empty((M, M)) if full_cov else np.empty(M)) if want_var else None
-        check(lib().mi355gp_predict_sum(self._h, len(specs), arr, Xnew, M, mu.ctypes.data_as(_c_dp), _opt(var),
-                                        int(bool(full_cov))), "mi355gp_predict_sum")
-        if var is not None and not full_cov:
-            var = var[:, None]
-        return mu, var
+        return _predict("mi355gp_predict_sum", (self._h, len(specs), arr), Xnew, self.D, self.Dy, full_cov, want_var)
 
     def exact_studentt_sum(self, specs, nu, jitter=1e-8, extra_jitter=0.0):
         """Student-t process: (info, dict(lml, logdet, beta, scale, alpha, dtheta))"""
@@ -398,11 +401,7 @@ class Context(object):
         ms = np.zeros(NUM_T) if want_stage_ms else None
         rc = check(lib().mi355gp_inference_given_K(self._h, K, noise, noise.size, jitter, extra_jitter, out,
                                                    _opt(alpha), _opt(diag), _opt(ms)), "mi355gp_inference_given_K")
-        res = dict(lml=out[OUT_LML], logdet=out[OUT_LOGDET], datafit=out[OUT_DATAFIT], dnoise=out[OUT_DNOISE],
-                   trKinv=out[OUT_TRKINV], alpha=alpha, diag_dL_dK=diag)
-        if ms is not None:
-            res["stage_ms"] = dict(zip(STAGE_NAMES, ms[:len(STAGE_NAMES)]))
-        return rc, res
+        return rc, _exact_result(out, ms, alpha=alpha, diag_dL_dK=diag)
 
     # ---- Laplace session (include/mi355gp.h: begin, newton per mode-search iteration, finish, gradients, predict / fetch) ----
     def laplace_begin(self, specs):
@@ -441,16 +440,10 @@ class Context(object):
     def laplace_predict(self, specs, Xnew, wv, full_cov=False, want_var=True):
         """`Posterior._raw_predict` for the Laplace posterior (reference `laplace.py:146`, `posterior.py:198-262`)."""
         arr, keep, _ = make_parts(specs)
-        Xnew, wv = f64(Xnew), f64(np.ravel(wv))
-        M = Xnew.shape[0]
-        assert Xnew.shape[1] == self.D and wv.size == self.N
-        mu = np.empty((M, 1))
-        var = (np.empty((M, M)) if full_cov else np.empty(M)) if want_var else None
-        check(lib().mi355gp_laplace_predict(self._h, len(specs), arr, Xnew, M, wv, mu.ctypes.data_as(_c_dp), _opt(var),
-                                            int(bool(full_cov))), "mi355gp_laplace_predict")
-        if var is not None and not full_cov:
-            var = var[:, None]
-        return mu, var
+        wv = f64(np.ravel(wv))
+        assert wv.size == self.N
+        return _predict("mi355gp_laplace_predict", (self._h, len(specs), arr), Xnew, self.D, 1, full_cov, want_var,
+                        between=(wv,))
 
     # ---- EP inside a Laplace session (include/mi355gp.h: recompute, sweep; the final pass is newton / finish / gradients) ----
     def ep_recompute(self, tau, v, extra_jitter=0.0, add_diag=0.0, want_sigma=True, want_ms=False):
@@ -501,16 +494,8 @@ class Context(object):
 
     def predict(self, kind, ARD, theta, Xnew, full_cov=False, want_var=True):
         """(mu (M x Dy), var (M x 1) or cov (M x M)) of the latent function at Xnew, computed on the device."""
-        Xnew = f64(Xnew)
-        M = Xnew.shape[0]
-        assert Xnew.shape[1] == self.D
-        mu = np.empty((M, self.Dy))
-        var = (np.empty((M, M)) if full_cov else np.empty(M)) if want_var else None
-        check(lib().mi355gp_predict(self._h, KIND_IDS[kind], ard_id(kind, ARD), f64(theta), Xnew, M,
-                                    mu.ctypes.data_as(_c_dp), _opt(var), int(bool(full_cov))), "mi355gp_predict")
-        if var is not None and not full_cov:
-            var = var[:, None]
-        return mu, var
+        return _predict("mi355gp_predict", (self._h, KIND_IDS[kind], ard_id(kind, ARD), f64(theta)), Xnew, self.D, self.Dy,
+                        full_cov, want_var)
 
     def fetch(self, which, fortran_order=False):
         out = np.empty((self.N, self.N))
@@ -614,16 +599,7 @@ class SparseContext(object):
     def predict(self, specs, Xnew, full_cov=False, want_var=True):
         """(mu (M* x Dy), var (M* x 1) or cov) of the sparse posterior of the last call, on the device."""
         arr, keep, _ = make_parts(specs)
-        Xnew = f64(Xnew)
-        Mn = Xnew.shape[0]
-        assert Xnew.shape[1] == self.D
-        mu = np.empty((Mn, self.Dy))
-        var = (np.empty((Mn, Mn)) if full_cov else np.empty(Mn)) if want_var else None
-        check(lib().mi355gp_sparse_predict(self._h, len(specs), arr, Xnew, Mn, mu.ctypes.data_as(_c_dp), _opt(var),
-                                           int(bool(full_cov))), "mi355gp_sparse_predict")
-        if var is not None and not full_cov:
-            var = var[:, None]
-        return mu, var
+        return _predict("mi355gp_sparse_predict", (self._h, len(specs), arr), Xnew, self.D, self.Dy, full_cov, want_var)
 
     def fetch_dL_dKnm(self, row0, nrows):
         out = np.empty((nrows, self.M))

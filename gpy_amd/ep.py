@@ -10,11 +10,10 @@ gradients, prediction).  Nothing N x N leaves the device unless a caller materia
 import numpy as np
 
 from . import _lib
-from .inference import _DeviceState
-from .kern import DEVICE_KERNELS, CombinationKernel, diag_depends_on_point
-from .laplace import Laplace, _LaplaceState, _specs
+from .laplace import begin_session, entry_checks
 from .lazy import DeviceResult, kernel_signature
 from .likelihoods import Bernoulli
+from .linalg import jitter_ladder
 from .link_functions import Probit
 from .posterior import PosteriorEP
 
@@ -108,7 +107,9 @@ class EP(object):
         d["_state"] = None
         return d
 
-    _with_ladder = Laplace._with_ladder      # jitchol's ladder on the info codes of the device factorisation of B
+    def _with_ladder(self, attempt):
+        """jitchol's ladder on the info codes of the device factorisation of B"""
+        return jitter_ladder(attempt, self._kd, self.maxtries)[0]
 
     # ---- the public entry point (reference `expectation_propagation.py:246-277`) -----------------------------------------
     def inference(self, kern, X, likelihood, Y, mean_function=None, Y_metadata=None, precision=None, K=None):
@@ -118,34 +119,19 @@ class EP(object):
             raise NotImplementedError("EP on the MI355X path does not take precision=: the site precisions stay on the device path")
         if K is not None:
             raise NotImplementedError("EP on the MI355X path builds K on the device from the kernel: K= is not taken")
-        X = np.asarray(X)
-        Y = np.asarray(Y, dtype=np.float64)
-        if Y.ndim != 2 or Y.shape[1] > 1:
-            raise NotImplementedError("EP on the MI355X path takes one output column, Y has shape %r" % (Y.shape,))
+        Y = entry_checks("EP", "EP", kern, Y)
         if not isinstance(likelihood, Bernoulli):
             raise NotImplementedError("EP on the MI355X path matches moments for the Bernoulli likelihood only, not %s"
                                       % type(likelihood).__name__)
         if not isinstance(likelihood.gp_link, Probit):
             raise NotImplementedError("EP on the MI355X path matches moments for the probit link only, not %s"
                                       % type(likelihood.gp_link).__name__)
-        if not isinstance(kern, DEVICE_KERNELS + (CombinationKernel,)):
-            raise NotImplementedError("the MI355X EP path evaluates gpy_amd kernels on the device")
         if self.ep_mode not in ("nested", "alternated"):
             raise ValueError("ep_mode value not valid")
         if self.always_reset:
             self.reset()
-        n = X.shape[0]
-        specs = _specs(kern)
-        if self._state is None:
-            self._state = _LaplaceState(self.device)
-        st = self._state
-        st.ensure_data(kern._slice_X(X), _lib.f64(Y))
-        st.call_token += 1
-        ctx = st.ctx
-        ctx.laplace_begin(specs)
-        self._ctx = ctx
-        self._kd = float(np.mean(kern.Kdiag(X))) if diag_depends_on_point(kern) else (
-            kern.diag_variance() if isinstance(kern, CombinationKernel) else float(specs[0][2][0]))
+        st, self._kd = begin_session(self, kern, X, Y)
+        self._ctx, n = st.ctx, Y.shape[0]
 
         if self.ep_mode == "nested":
             self._ep_approximation = None
@@ -157,9 +143,8 @@ class EP(object):
     # ---- the sweeps (reference `expectation_propagation.py:279-361`) ----------------------------------------------------
     def _recompute(self, ga_approx, add_diag=0.0):
         """`posteriorParams._recompute` on the device; the full Sigma is formed only where the sequential sweep needs it"""
-        mu, sd, logdet = self._with_ladder(
-            lambda jit: (lambda r: (r[0], r[1:]))(self._ctx.ep_recompute(ga_approx.tau, ga_approx.v, jit, add_diag,
-                                                                         want_sigma=not self.parallel_updates)), self._kd)
+        mu, sd, logdet = self._with_ladder(lambda jit: self._ctx.ep_recompute(ga_approx.tau, ga_approx.v, jit, add_diag,
+                                                                              want_sigma=not self.parallel_updates))
         return posteriorParams(mu, sd, logdet)
 
     def expectation_propagation(self, Y, likelihood, Y_metadata=None):
@@ -221,15 +206,14 @@ class EP(object):
     # ---- the final pass (reference `expectation_propagation.py:363-395`) -------------------------------------------------
     def _ep_marginal(self, ga_approx, Z_tilde):
         """(log marginal, alpha): v^T Sigma v of the reference is v^T mu, mu = K alpha"""
-        alpha, mu, B_logdet = self._with_ladder(
-            lambda jit: (lambda r: (r[0], r[1:]))(self._ctx.laplace_newton(ga_approx.tau, ga_approx.v, jit)), self._kd)
+        alpha, mu, B_logdet = self._with_ladder(lambda jit: self._ctx.laplace_newton(ga_approx.tau, ga_approx.v, jit))
         log_marginal = 0.5 * (-len(ga_approx.tau) * log_2_pi - B_logdet + np.sum(ga_approx.v * mu)) + Z_tilde
         return float(log_marginal), alpha
 
     def _inference(self, kern, st, n, Y, ga_approx, cav_params, likelihood, Z_tilde, Y_metadata=None):
         ctx = self._ctx
         log_marginal, alpha = self._ep_marginal(ga_approx, Z_tilde)
-        self._with_ladder(lambda jit: (lambda r: (r[0], r[1:]))(ctx.laplace_finish(ga_approx.tau, jit)), self._kd)
+        self._with_ladder(lambda jit: ctx.laplace_finish(ga_approx.tau, jit))
         dtheta = ctx.laplace_gradients(alpha, np.zeros(n))       # dL_dK = 0.5 (alpha alpha^T - Wi), reduced per kernel part
         alpha = alpha[:, None]
         st.woodbury_vector = alpha

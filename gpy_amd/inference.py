@@ -7,17 +7,16 @@ returns `(Posterior, log_marginal_likelihood, {'dL_dK', 'dL_dthetaL', 'dL_dm'})`
 gpy_amd kernel the whole evaluation (K build, Cholesky, alpha, Ky^-1, all gradients) is one C-ABI call and the
 N x N results stay in HBM behind lazy proxies.  The jitter ladder of `jitchol` (reference
 `GPy/util/linalg.py:56-75`) runs here, on LAPACK-style `info` codes from the device factorisation, and raises
-the same `numpy.linalg.LinAlgError` messages.
+the same `numpy.linalg.LinAlgError` messages (`gpy_amd.linalg.jitter_ladder`).  A kernel, leaf or combination, describes itself
+to the device through `Kern.part_specs()` / `_slice_X()` / `jitter_diag()`.
 """
 import numpy as np
 
 from . import _lib
-from .kern import DEVICE_KERNELS, CombinationKernel, diag_depends_on_point
 from .lazy import ArrayIdentity, DeviceResult, kernel_signature
 from .likelihoods import Gaussian
+from .linalg import jitter_ladder
 from .posterior import PosteriorExact, StudentTPosterior
-
-LinAlgError = np.linalg.LinAlgError
 
 
 class _DeviceState(object):
@@ -61,24 +60,20 @@ class _DeviceState(object):
         return self.ctx.fetch(which, fortran_order=fortran_order)
 
     def covariance_between_points(self, kern, X1, X2):
-        if isinstance(kern, CombinationKernel):
-            return self.ctx.covariance_between_points(kern.part_specs(), _lib.f64(X1), _lib.f64(X2))
-        # a single kernel's active_dims were applied when X was uploaded: slice the new points the same way
-        return self.ctx.covariance_between_points([(kern.kind, kern.ARD, kern._theta(), None)], kern._slice_X(X1),
-                                                  kern._slice_X(X2))
+        # a lone kernel's active_dims were applied when X was uploaded: the new points are sliced the same way
+        return self.ctx.covariance_between_points(kern.part_specs(), kern._slice_X(X1), kern._slice_X(X2))
 
     def predictive_gradients(self, kern, Xnew, want_var=True):
         """(dmu (M x D x Dy), dvar (M x D)) -- reference `core/gp.py:418-474`; raises NotImplementedError for kernel
         expressions the device entry does not take (products), which the caller then evaluates on the host."""
-        from .kern import Poly, Prod
-        if any(isinstance(k, Poly) for k in (kern.leaves() if isinstance(kern, CombinationKernel) else [kern])):
+        from .kern import Poly
+        if any(isinstance(k, Poly) for k in kern.leaves()):
             raise NotImplementedError("Poly has no gradients_X (reference `poly.py:47-48`)")       # before any device work
-        if isinstance(kern, CombinationKernel):
-            if isinstance(kern, Prod) or any(isinstance(p, Prod) for p in kern.parts):
-                raise NotImplementedError("product kernels")
-            return self.ctx.predictive_gradients(kern.part_specs(), _lib.f64(Xnew), want_var=want_var)
+        specs = kern.part_specs()
+        if any(s[4] != 0 for s in specs):                        # a non-zero term id: a factor of a product
+            raise NotImplementedError("product kernels")
         Xs = kern._slice_X(Xnew)
-        dmu, dvar = self.ctx.predictive_gradients([(kern.kind, kern.ARD, kern._theta(), None)], Xs, want_var=want_var)
+        dmu, dvar = self.ctx.predictive_gradients(specs, Xs, want_var=want_var)
         if Xs.shape[1] == np.asarray(Xnew).shape[1]:
             return dmu, dvar
         full_mu = np.zeros((Xs.shape[0], np.asarray(Xnew).shape[1], dmu.shape[2]))   # active_dims of a single kernel
@@ -90,9 +85,7 @@ class _DeviceState(object):
         return full_mu, full_var
 
     def predict(self, kern, Xnew, full_cov=False):
-        if isinstance(kern, CombinationKernel):
-            return self.ctx.predict_sum(kern.part_specs(), _lib.f64(Xnew), full_cov=full_cov)
-        return self.ctx.predict(kern.kind, kern.ARD, kern._theta(), kern._slice_X(Xnew), full_cov=full_cov)
+        return self.ctx.predict_sum(kern.part_specs(), kern._slice_X(Xnew), full_cov=full_cov)
 
 
 class ExactGaussianInference(object):
@@ -135,21 +128,9 @@ class ExactGaussianInference(object):
         return -neg
 
     def _run_with_ladder(self, attempt, diagA):
-        """`attempt(extra_jitter)` -> (info, result).  Mirrors jitchol: plain try, then mean(diag)*1e-6 * 10^k."""
-        info, res = attempt(0.0)
-        if info == 0:
-            return res
-        if np.any(diagA <= 0.):
-            raise LinAlgError("not pd: non-positive diagonal elements")
-        jitter = float(np.mean(diagA)) * 1e-6
-        num_tries = 1
-        while num_tries <= self.maxtries and np.isfinite(jitter):
-            info, res = attempt(jitter)
-            if info == 0:
-                return res
-            jitter *= 10
-            num_tries += 1
-        raise LinAlgError("not positive definite, even with jitter.")
+        """`attempt(extra_jitter)` -> (info, result) under jitchol's ladder"""
+        (res,), _ = jitter_ladder(attempt, diagA, self.maxtries, check_diag=True)
+        return res
 
     def inference(self, kern, X, likelihood, Y, mean_function=None, Y_metadata=None, K=None, variance=None,
                   Z_tilde=None):
@@ -161,8 +142,8 @@ class ExactGaussianInference(object):
         # (reference :42-50) R = Y - m; without a mean function R IS Y (same object every iteration: O(1) data check)
         R = _lib.f64(Y) if mean_function is None else _lib.f64(Y - mean_function.f(X))
         n = X.shape[0]
-        is_sum = isinstance(kern, CombinationKernel)
-        fused = K is None and (isinstance(kern, DEVICE_KERNELS) or is_sum)
+        # a lone White / Bias / Coregionalize, a foreign kernel or a given K: K comes from the host (`inference_given_K`)
+        fused = K is None and getattr(kern, "fused_alone", False)
         Xdev = kern._slice_X(X) if fused else _lib.f64(X)
         if self._state is None:
             self._state = _DeviceState(self.device)
@@ -173,27 +154,15 @@ class ExactGaussianInference(object):
         # Gaussian.exact_inference_gradients == sum(diag(dL_dK)) == trace(dL_dK), which the device already reduces:
         # only likelihoods with per-row noise terms need the N-vector diag(dL_dK) shipped back.
         trace_only = isinstance(likelihood, Gaussian) and noise.size == 1
-        scalar_noise_lik = trace_only
+        want_diag = self.keep_diag or not trace_only
 
         if fused:
-            if is_sum:
-                specs = kern.part_specs()
-                # jitchol's mean(diag(A)): with a Coregionalize, Linear, MLP or Poly part Kdiag depends on the point
-                diagA = (kern.Kdiag(X) if diag_depends_on_point(kern) else kern.diag_variance()) + noise + 1e-8
+            specs = kern.part_specs()
+            diagA = kern.jitter_diag(X) + noise + 1e-8
 
-                def attempt(extra):
-                    return st.ctx.exact_inference_sum(specs, noise, jitter=1e-8, extra_jitter=extra, want_alpha=True,
-                                                      want_diag=self.keep_diag or not scalar_noise_lik,
-                                                      want_stage_ms=want_ms)
-            else:
-                theta = kern._theta()
-                # (a lone Linear / MLP / Poly: theta[0] is a variance, not the diagonal)
-                diagA = (kern.Kdiag(X) if diag_depends_on_point(kern) else float(theta[0])) + noise + 1e-8
-
-                def attempt(extra):
-                    return st.ctx.exact_inference(kern.kind, kern.ARD, theta, noise, jitter=1e-8, extra_jitter=extra,
-                                                  want_alpha=True, want_diag=self.keep_diag or not scalar_noise_lik,
-                                                  want_stage_ms=want_ms)
+            def attempt(extra):
+                return st.ctx.exact_inference_sum(specs, noise, jitter=1e-8, extra_jitter=extra, want_alpha=True,
+                                                  want_diag=want_diag, want_stage_ms=want_ms)
             res = self._run_with_ladder(attempt, diagA)
             sig = kernel_signature(kern)
             K_view = DeviceResult(st, _lib.FETCH_K, n, st.call_token)
@@ -205,8 +174,8 @@ class ExactGaussianInference(object):
             diagA = np.diag(K) + noise + 1e-8
 
             def attempt(extra):
-                return st.ctx.inference_given_K(K, noise, jitter=1e-8, extra_jitter=extra,
-                                                want_diag=self.keep_diag or not scalar_noise_lik, want_stage_ms=want_ms)
+                return st.ctx.inference_given_K(K, noise, jitter=1e-8, extra_jitter=extra, want_diag=want_diag,
+                                                want_stage_ms=want_ms)
             res = self._run_with_ladder(attempt, diagA)
             K_view = K
             dL_dK = DeviceResult(st, _lib.FETCH_DLDK, n, st.call_token)
@@ -254,34 +223,21 @@ class ExactStudentTInference(object):
 
     def inference(self, kern, X, Y, nu, mean_function=None, K=None):
         from scipy.special import digamma
-        if K is not None or not isinstance(kern, DEVICE_KERNELS + (CombinationKernel,)):
+        if K is not None or not getattr(kern, "fused_alone", False):
             raise NotImplementedError("the MI355X Student-t path evaluates gpy_amd kernels on the device")
         X = np.asarray(X)
         Y = np.asarray(Y, dtype=np.float64)
         m = 0 if mean_function is None else mean_function.f(X)
         R = _lib.f64(Y - m)
-        is_sum = isinstance(kern, CombinationKernel)
-        Xdev = kern._slice_X(X)
-        specs = kern.part_specs() if is_sum else [(kern.kind, kern.ARD, kern._theta(), None)]
+        specs = kern.part_specs()
         if self._state is None:
             self._state = _DeviceState(self.device)
         st = self._state
-        st.ensure_data(Xdev, R)
+        st.ensure_data(kern._slice_X(X), R)
         st.call_token += 1
         nu = float(np.asarray(nu).ravel()[0])
-        extra, tries = 0.0, 0
-        while True:                                   # jitchol's ladder (util/linalg.py:56-75)
-            info, r = st.ctx.exact_studentt_sum(specs, nu, jitter=1e-8, extra_jitter=extra)
-            if info == 0:
-                break
-            if tries >= self.maxtries:
-                raise LinAlgError("not positive definite, even with jitter.")
-            if diag_depends_on_point(kern):
-                kd = float(np.mean(kern.Kdiag(X)))
-            else:
-                kd = kern.diag_variance() if is_sum else float(specs[0][2][0])
-            extra = kd * 1e-6 * 10 ** tries
-            tries += 1
+        (r,), extra = jitter_ladder(lambda extra: st.ctx.exact_studentt_sum(specs, nu, jitter=1e-8, extra_jitter=extra),
+                                    lambda: kern.jitter_diag(X), self.maxtries)
         N, beta = Y.shape[0], r["beta"]
         dL_dnu = -N / (nu - 2.0) + digamma(0.5 * (nu + N)) - digamma(0.5 * nu)
         dL_dnu -= np.log(1 + beta / (nu - 2.0))

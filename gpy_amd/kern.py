@@ -1,12 +1,14 @@
-"""Stationary covariance functions backed by libmi355gp.so -- drop-in for the hot-path methods of
-`GPy.kern.RBF / Matern52 / Matern32 / Exponential`:
+"""Covariance functions backed by libmi355gp.so -- drop-in for the hot-path methods of the reference's kernels:
 
-    K(X, X2=None), Kdiag(X), update_gradients_full(dL_dK, X, X2=None), update_gradients_diag(dL_dKdiag, X)
+    K(X, X2=None), Kdiag(X), update_gradients_full(dL_dK, X, X2=None), update_gradients_diag(dL_dKdiag, X), gradients_X(...)
 
-Same constructor arguments, parameter names (`variance`, `lengthscale`, `inv_lengthscale`), link order and
-`.gradient` side effects as the reference (`GPy/kern/src/stationary.py:60-81,105-115,170-213`,
-`GPy/kern/src/rbf.py:22-33,373-375`); `active_dims` slicing follows `GPy/kern/src/kern.py:112-117`.
-All array math runs in hand-written HIP kernels (csrc/kern.hip); there is no NumPy fallback.
+`Kern` is the base of every kernel here, after `GPy/kern/src/kern.py:12-361`: the common constructor part, `active_dims`
+slicing (`kern.py:112-117`), `+` / `*`, serialisation, the cached device K-build and gradient passes, and the expression
+interface through which the inference classes describe any kernel, leaf or combination, to the C-ABI (`leaves`, `part_specs`,
+`_slice_X`, `jitter_diag`).  The leaves: the stationary kernels `RBF` / `ExpQuad` / `Matern52` / `Matern32` / `Exponential` /
+`OU` / `RatQuad` (`GPy/kern/src/stationary.py`, `rbf.py`), `StdPeriodic`, `Coregionalize`, `Linear`, `MLP`, `Poly` and the static
+`White` / `Bias`; the combinations: `Add` and `Prod`.  Same constructor arguments, parameter names, link order and `.gradient`
+side effects as the reference.  All array math runs in hand-written HIP kernels (csrc/kern.hip); there is no NumPy fallback.
 """
 import numpy as np
 
@@ -47,16 +49,20 @@ class _KCache(object):
         self.entries = []
 
 
-class Stationary(Parameterized):
+class Kern(Parameterized):
+    """Base of every kernel (reference `GPy/kern/src/kern.py:12-361`).  A subclass sets `kind` (the C-ABI's name for it) and
+    `_gpy_class`, links its parameters and gives `_theta()`, `Kdiag`, `_install_gradients(g)` and the diagonal gradients;
+    `ARD` is what the C-ABI takes as `ard` for the kind."""
     kind = None                # name understood by the C-ABI
     _gpy_class = None          # "class" string for to_dict (resolvable by GPy's loader)
     _support_GPU = True
+    is_leaf = True             # not an Add / Prod: what a Prod takes as a factor
+    fused_alone = True         # the fused inference entries take it on its own (a lone White / Bias / Coregionalize: they do not)
+    diag_is_constant = True    # Kdiag does not depend on the point
 
-    def __init__(self, input_dim, variance=1., lengthscale=None, ARD=False, active_dims=None, name=None,
-                 useGPU=True, device=0):
-        super(Stationary, self).__init__(name or self.kind)
+    def __init__(self, input_dim, active_dims, name, device=0):
+        super(Kern, self).__init__(name)
         self.input_dim = int(input_dim)
-        self.ARD = bool(ARD)
         self.device = device
         self.useGPU = True
         if active_dims is None:
@@ -64,6 +70,121 @@ class Stationary(Parameterized):
         self.active_dims = np.atleast_1d(np.asarray(active_dims, dtype=np.int_))
         assert self.active_dims.size == self.input_dim, "input_dim=%d does not match len(active_dims)=%d" % (
             self.input_dim, self.active_dims.size)
+        self._K_cache = _KCache(limit=3)
+
+    def __getstate__(self):
+        d = dict(self.__dict__)
+        d["_K_cache"] = _KCache(limit=3)
+        return d
+
+    # ---- the expression interface: how the inference classes describe a kernel, leaf or combination, to the C-ABI ---------
+    def leaves(self):
+        """the leaf kernels of the expression in link (= parameter, = gradient) order"""
+        return [self]
+
+    def part_specs(self):
+        """[(kind, ARD, theta, active_dims, term)] for the C-ABI (`mi355gp_part`).  A kernel on its own is one part without
+        active_dims: its column slicing is applied to X on upload (`_slice_X`)."""
+        return [(self.kind, self.ARD, self._theta(), None, 0)]
+
+    def _slice_X(self, X):
+        """The X the device is given for this kernel: the active columns (reference `kern.py:112-117`); a combination hands
+        over all of X, its parts carry their active_dims in `part_specs`."""
+        X = np.asarray(X)
+        if X.shape[1] == self.input_dim and np.array_equal(self.active_dims, np.arange(self.input_dim)):
+            return _lib.f64(X)
+        assert X.shape[1] > self.active_dims.max(), "At least %d dimensional X needed, X.shape=%r" % (
+            self.active_dims.max() + 1, X.shape)
+        return _lib.f64(X[:, self.active_dims])
+
+    def diag_variance(self):
+        """Kdiag where it is one number (`diag_is_constant`; theta starts with the variance)"""
+        return float(self._theta()[0])
+
+    def jitter_diag(self, X):
+        """diag K(X, X) as jitchol's mean(diag(A)) needs it (reference `util/linalg.py:65`): one number where it is constant,
+        `Kdiag(X)` where a Coregionalize, Linear, MLP or Poly leaf makes it depend on the point"""
+        return self.Kdiag(X) if diag_depends_on_point(self) else self.diag_variance()
+
+    def _install_fused(self, g):
+        """install the concatenated gradients of a fused inference call, leaf by leaf"""
+        i = 0
+        for p in self.leaves():
+            k = p._theta().size
+            p._install_gradients(g[i:i + k])
+            i += k
+
+    # ---- the hot-path interface -----------------------------------------------------------------------
+    def K(self, X, X2=None):
+        """Covariance matrix K(X, X2), built on the device (reference `stationary.py:105-115`, `@Cache_this(limit=3)` :105)."""
+        X = np.asarray(X)
+        X2 = None if X2 is None else np.asarray(X2)
+        theta = self._theta()
+
+        def compute():
+            Xs = self._slice_X(X)
+            X2s = None if X2 is None else self._slice_X(X2)
+            return _lib.kern_K(self.kind, self.ARD, theta, Xs, X2s, device=self.device)
+        return self._K_cache.get(X, X2, theta, compute)
+
+    def update_gradients_full(self, dL_dK, X, X2=None):
+        """Writes the parameters' `.gradient` (reference `stationary.py:193-213`).
+
+        When `dL_dK` is the device-resident result of a gpy_amd inference call for this kernel the gradients were already
+        reduced on the GPU in the same pass and are simply installed."""
+        if isinstance(dL_dK, DeviceResult) and X2 is None and dL_dK.matches_kernel(self):
+            g = dL_dK.fused_dtheta
+        else:
+            g = _lib.update_gradients_full(self.kind, self.ARD, self._theta(), np.asarray(dL_dK), self._slice_X(X),
+                                           None if X2 is None else self._slice_X(X2), device=self.device)
+        self._install_gradients(g)
+
+    def update_gradients_diag(self, dL_dKdiag, X):
+        raise NotImplementedError
+
+    def gradients_X(self, dL_dK, X, X2=None):
+        """dL/dX from dL_dK (reference `stationary.py:245-252,330-358`), reduced on the device."""
+        g = _lib.gradients_X(self.kind, self.ARD, self._theta(), np.asarray(dL_dK), self._slice_X(X),
+                             None if X2 is None else self._slice_X(X2), device=self.device)
+        if g.shape[1] == np.asarray(X).shape[1]:
+            return g
+        full = np.zeros(np.asarray(X).shape)          # active_dims slicing (kernel_slice_operations.py:113-136)
+        full[:, self.active_dims] = g
+        return full
+
+    def gradients_X_diag(self, dL_dKdiag, X):
+        """zero where the diagonal is constant (reference `stationary.py:360-361`, `static.py:40-41`,
+        `standard_periodic.py:582-583`, `coregionalize.py:156-157`)"""
+        return np.zeros(np.asarray(X).shape)
+
+    def __add__(self, other):
+        return Add([self, other])
+
+    def __mul__(self, other):
+        return Prod([self, other])
+
+    # ---- bookkeeping ----------------------------------------------------------------------------------
+    def to_dict(self):
+        """JSON-serialisable description with the reference's "class" string (`kern.py:63-76`); subclasses add their own keys"""
+        return {"class": self._gpy_class, "name": self.name, "input_dim": self.input_dim,
+                "active_dims": self.active_dims.tolist()}
+
+    @classmethod
+    def from_dict(cls, d):
+        d = dict(d)
+        d.pop("class", None)
+        d.pop("useGPU", None)
+        return cls(**d)
+
+    def copy(self):
+        return self.__class__.from_dict(self.to_dict())
+
+
+class Stationary(Kern):
+    def __init__(self, input_dim, variance=1., lengthscale=None, ARD=False, active_dims=None, name=None,
+                 useGPU=True, device=0):
+        super(Stationary, self).__init__(input_dim, active_dims, name or self.kind, device)
+        self.ARD = bool(ARD)
         if not self.ARD:
             if lengthscale is None:
                 lengthscale = np.ones(1)
@@ -82,53 +203,13 @@ class Stationary(Parameterized):
         self.lengthscale = Param("lengthscale", lengthscale)
         assert self.variance.size == 1
         self.link_parameters(self.variance, self.lengthscale)
-        self._K_cache = _KCache(limit=3)
-
-    def __getstate__(self):
-        d = dict(self.__dict__)
-        d["_K_cache"] = _KCache(limit=3)
-        return d
-
-    # ---- helpers ---------------------------------------------------------------------------------
-    def _slice_X(self, X):
-        X = np.asarray(X)
-        if X.shape[1] == self.input_dim and np.array_equal(self.active_dims, np.arange(self.input_dim)):
-            return _lib.f64(X)
-        assert X.shape[1] > self.active_dims.max(), "At least %d dimensional X needed, X.shape=%r" % (
-            self.active_dims.max() + 1, X.shape)
-        return _lib.f64(X[:, self.active_dims])
 
     def _theta(self):
         return _lib.theta_vec(self.variance.values, self.lengthscale.values, self.ARD, self.input_dim)
 
-    # ---- the hot-path interface -----------------------------------------------------------------------
-    def K(self, X, X2=None):
-        """Covariance matrix K(X, X2) (reference `stationary.py:105-115`, `@Cache_this(limit=3)` :105)."""
-        X = np.asarray(X)
-        X2 = None if X2 is None else np.asarray(X2)
-        theta = self._theta()
-
-        def compute():
-            Xs = self._slice_X(X)
-            X2s = None if X2 is None else self._slice_X(X2)
-            return _lib.kern_K(self.kind, self.ARD, theta, Xs, X2s, device=self.device)
-        return self._K_cache.get(X, X2, theta, compute)
-
     def Kdiag(self, X):
         """(reference `stationary.py:170-173`)"""
         return _lib.kern_Kdiag(self.kind, self._theta(), np.asarray(X).shape[0])
-
-    def update_gradients_full(self, dL_dK, X, X2=None):
-        """Writes `self.variance.gradient` and `self.lengthscale.gradient` (reference `stationary.py:193-213`).
-
-        When `dL_dK` is the device-resident result of `gpy_amd.ExactGaussianInference` for this kernel the
-        gradients were already reduced on the GPU in the same pass and are simply installed."""
-        if isinstance(dL_dK, DeviceResult) and X2 is None and dL_dK.matches_kernel(self):
-            g = dL_dK.fused_dtheta
-        else:
-            g = _lib.update_gradients_full(self.kind, self.ARD, self._theta(), np.asarray(dL_dK), self._slice_X(X),
-                                           None if X2 is None else self._slice_X(X2), device=self.device)
-        self._install_gradients(g)
 
     def _install_gradients(self, g):
         self.variance.gradient = g[0]
@@ -148,46 +229,16 @@ class Stationary(Parameterized):
         """variance / lengthscale^2 per input dimension (reference `stationary.py:363-364`)"""
         return float(self.variance.values[0]) * np.ones(self.input_dim) / np.asarray(self.lengthscale.values) ** 2
 
-    def gradients_X(self, dL_dK, X, X2=None):
-        """dL/dX from dL_dK (reference `stationary.py:245-252,330-358`), reduced on the device."""
-        g = _lib.gradients_X(self.kind, self.ARD, self._theta(), np.asarray(dL_dK), self._slice_X(X),
-                             None if X2 is None else self._slice_X(X2), device=self.device)
-        if g.shape[1] == np.asarray(X).shape[1]:
-            return g
-        full = np.zeros(np.asarray(X).shape)          # active_dims slicing (kernel_slice_operations.py:113-136)
-        full[:, self.active_dims] = g
-        return full
-
-    def gradients_X_diag(self, dL_dKdiag, X):
-        """(reference `stationary.py:360-361`)"""
-        return np.zeros(np.asarray(X).shape)
-
-    def __add__(self, other):
-        return Add([self, other])
-
-    def __mul__(self, other):
-        return Prod([self, other])
-
     def reset_gradients(self):
         self.variance.gradient = 0.
         self.lengthscale.gradient = np.zeros(self.input_dim) if self.ARD else 0.
 
-    # ---- bookkeeping ----------------------------------------------------------------------------------
     def to_dict(self):
-        """JSON-serialisable description with the reference's "class" string (`stationary.py:83-88`)."""
-        return {"class": self._gpy_class, "name": self.name, "input_dim": self.input_dim,
-                "active_dims": self.active_dims.tolist(), "variance": self.variance.values.tolist(),
-                "lengthscale": self.lengthscale.values.tolist(), "ARD": self.ARD, "useGPU": True}
-
-    @classmethod
-    def from_dict(cls, d):
-        d = dict(d)
-        d.pop("class", None)
-        d.pop("useGPU", None)
-        return cls(**d)
-
-    def copy(self):
-        return self.__class__.from_dict(self.to_dict())
+        """(reference `stationary.py:83-88`)"""
+        d = super(Stationary, self).to_dict()
+        d.update(variance=self.variance.values.tolist(), lengthscale=self.lengthscale.values.tolist(), ARD=self.ARD,
+                 useGPU=True)
+        return d
 
 
 class RBF(Stationary):
@@ -306,7 +357,7 @@ class RatQuad(Stationary):
         return d
 
 
-class StdPeriodic(Parameterized):
+class StdPeriodic(Kern):
     """Standard periodic kernel k(x, y) = variance exp(-1/2 sum_q (sin(pi (x_q - y_q) / T_q) / l_q)^2) (reference
     `GPy/kern/src/standard_periodic.py:15-133`).  Not stationary in GPy's class sense (no function of r), but it runs
     on the same device paths: its own K-build and gradient kernels (C-ABI kind `MI355GP_STDPERIODIC`) and a row
@@ -314,19 +365,10 @@ class StdPeriodic(Parameterized):
     `ARD2` give one period / lengthscale per input dimension."""
     kind = "stdperiodic"
     _gpy_class = "GPy.kern.StdPeriodic"
-    _support_GPU = True
 
     def __init__(self, input_dim, variance=1., period=None, lengthscale=None, ARD1=False, ARD2=False, active_dims=None,
                  name="std_periodic", useGPU=True, device=0):
-        super(StdPeriodic, self).__init__(name)
-        self.input_dim = int(input_dim)
-        self.device = device
-        self.useGPU = True
-        if active_dims is None:
-            active_dims = np.arange(self.input_dim)
-        self.active_dims = np.atleast_1d(np.asarray(active_dims, dtype=np.int_))
-        assert self.active_dims.size == self.input_dim, "input_dim=%d does not match len(active_dims)=%d" % (
-            self.input_dim, self.active_dims.size)
+        super(StdPeriodic, self).__init__(input_dim, active_dims, name, device)
         self.ARD1, self.ARD2 = bool(ARD1), bool(ARD2)          # standard_periodic.py:56-88
         if not self.ARD1:
             if period is not None:
@@ -357,7 +399,6 @@ class StdPeriodic(Parameterized):
         self.period = Param("period", period)
         self.lengthscale = Param("lengthscale", lengthscale)
         self.link_parameters(self.variance, self.period, self.lengthscale)
-        self._K_cache = _KCache(limit=3)
 
     @property
     def ARD(self):
@@ -368,14 +409,9 @@ class StdPeriodic(Parameterized):
         return np.concatenate([[float(self.variance.values[0])], np.asarray(self.period.values, dtype=float).ravel(),
                                np.asarray(self.lengthscale.values, dtype=float).ravel()])
 
-    # slicing, the cached K, Kdiag, the fused / device gradients and gradients_X are the stationary kernels' (they only go
-    # through kind / ARD / _theta)
-    __getstate__ = Stationary.__getstate__
-    _slice_X = Stationary._slice_X
-    K = Stationary.K
-    Kdiag = Stationary.Kdiag
-    update_gradients_full = Stationary.update_gradients_full
-    gradients_X = Stationary.gradients_X
+    def Kdiag(self, X):
+        """the variance (reference `standard_periodic.py:135-139`)"""
+        return _lib.kern_Kdiag(self.kind, self._theta(), np.asarray(X).shape[0])
 
     def _install_gradients(self, g):
         npr = self.period.size
@@ -394,38 +430,19 @@ class StdPeriodic(Parameterized):
         self.period.gradient = np.zeros(self.input_dim) if self.ARD1 else 0.
         self.lengthscale.gradient = np.zeros(self.input_dim) if self.ARD2 else 0.
 
-    def gradients_X_diag(self, dL_dKdiag, X):
-        """(reference `standard_periodic.py:582-583`)"""
-        return np.zeros(np.asarray(X).shape)
-
     def input_sensitivity(self, summarize=True):
         """(reference `standard_periodic.py:585-586`)"""
         return float(self.variance.values[0]) * np.ones(self.input_dim) / np.asarray(self.lengthscale.values) ** 2
 
-    def __add__(self, other):
-        return Add([self, other])
-
-    def __mul__(self, other):
-        return Prod([self, other])
-
     def to_dict(self):
         """(reference `standard_periodic.py:96-111`)"""
-        return {"class": self._gpy_class, "name": self.name, "input_dim": self.input_dim,
-                "active_dims": self.active_dims.tolist(), "variance": self.variance.values.tolist(),
-                "period": self.period.values.tolist(), "lengthscale": self.lengthscale.values.tolist(),
-                "ARD1": self.ARD1, "ARD2": self.ARD2, "useGPU": True}
-
-    @classmethod
-    def from_dict(cls, d):
-        d = dict(d)
-        d.pop("class", None)
-        d.pop("useGPU", None)
-        return cls(**d)
-
-    copy = Stationary.copy
+        d = super(StdPeriodic, self).to_dict()
+        d.update(variance=self.variance.values.tolist(), period=self.period.values.tolist(),
+                 lengthscale=self.lengthscale.values.tolist(), ARD1=self.ARD1, ARD2=self.ARD2, useGPU=True)
+        return d
 
 
-class Coregionalize(Parameterized):
+class Coregionalize(Kern):
     """Coregionalization kernel k(x, x') = B[x, x'] over an input column of integer output indices, B = W W^T + diag(kappa)
     (reference `GPy/kern/src/coregionalize.py:15-157`).  On the device it is C-ABI kind `MI355GP_COREGIONALIZE`: a factor
     of the product terms that `util.multioutput.ICM` / `LCM` build, assembled in the K-build and reduced by the bucketed
@@ -433,18 +450,15 @@ class Coregionalize(Parameterized):
     W is linked untransformed (`positive=False`), kappa positive, in the reference's order."""
     kind = "coregionalize"
     _gpy_class = "GPy.kern.Coregionalize"
-    _support_GPU = True
+    fused_alone = False
+    diag_is_constant = False
 
     def __init__(self, input_dim, output_dim, rank=1, W=None, kappa=None, active_dims=None, name="coregion", device=0):
-        super(Coregionalize, self).__init__(name)
         assert int(input_dim) == 1, "Coregionalize acts on one input column (the output index): input_dim must be 1"
-        self.input_dim = 1
+        assert active_dims is None or np.size(active_dims) == 1, "Coregionalize takes one active dimension"
+        super(Coregionalize, self).__init__(1, active_dims, name, device)
         self.output_dim = int(output_dim)
         self.rank = int(rank)
-        self.device = device
-        self.useGPU = True
-        self.active_dims = np.atleast_1d(np.asarray([0] if active_dims is None else active_dims, dtype=np.int_))
-        assert self.active_dims.size == 1, "Coregionalize takes one active dimension"
         if self.rank > self.output_dim:
             print("Warning: Unusual choice of rank, it should normally be less than the output_dim.")
         if W is None:
@@ -460,7 +474,6 @@ class Coregionalize(Parameterized):
         self.W = Param("W", W, positive=False)
         self.kappa = Param("kappa", kappa)
         self.link_parameters(self.W, self.kappa)
-        self._K_cache = _KCache(limit=3)
         self.parameters_changed()
 
     @property
@@ -482,17 +495,6 @@ class Coregionalize(Parameterized):
         X = np.asarray(X)
         return _lib.f64(X[:, self.active_dims])                   # [-1]: the last column (test_kernel.py:864)
 
-    def K(self, X, X2=None):
-        """B[idx, idx'] (reference `coregionalize.py:83-104`), built on the device"""
-        X = np.asarray(X)
-        X2 = None if X2 is None else np.asarray(X2)
-        theta = self._theta()
-
-        def compute():
-            return _lib.kern_K(self.kind, self.output_dim, theta, self._slice_X(X),
-                               None if X2 is None else self._slice_X(X2), device=self.device)
-        return self._K_cache.get(X, X2, theta, compute)
-
     def Kdiag(self, X):
         """diag(B)[idx] (reference `coregionalize.py:106-107`): O(N) host work"""
         idx = self._index(self._slice_X(X))
@@ -506,19 +508,10 @@ class Coregionalize(Parameterized):
             raise ValueError("Coregionalize: output index %r is not an integer in [0, %d)" % (bad, self.output_dim))
         return idx
 
-    def update_gradients_full(self, dL_dK, X, X2=None):
-        """(reference `coregionalize.py:109-128`).  S comes from the device: the fused inference call's bucketed pass, or a
-        rectangular reduction of the given dL_dK."""
-        if isinstance(dL_dK, DeviceResult) and X2 is None and dL_dK.matches_kernel(self):
-            S = dL_dK.fused_dtheta
-        else:
-            S = _lib.update_gradients_full(self.kind, self.output_dim, self._theta(), np.asarray(dL_dK), self._slice_X(X),
-                                           None if X2 is None else self._slice_X(X2), device=self.device)
-        self._install_gradients(S)
-
     def _install_gradients(self, g):
-        """S (P x P, S[a][b] = sum of dL_dK over rows of output a and columns of output b) -> dkappa = diag(S),
-        dW = (S + S^T) W (reference `coregionalize.py:123-128`; its dL_dK_small is S^T)"""
+        """(reference `coregionalize.py:109-128`) the device reduces dL_dK -- in the fused inference call's bucketed pass, or a
+        rectangular reduction of a given dL_dK -- to S (P x P, S[a][b] = sum of dL_dK over rows of output a and columns of
+        output b) -> dkappa = diag(S), dW = (S + S^T) W (`:123-128`; its dL_dK_small is S^T)"""
         S = np.asarray(g, dtype=float).reshape(self.output_dim, self.output_dim)
         self.kappa.gradient = np.diag(S).copy()
         self.W.gradient = np.dot(S + S.T, self.W.values)
@@ -538,56 +531,29 @@ class Coregionalize(Parameterized):
         """(reference `coregionalize.py:153-154`)"""
         return np.zeros(np.asarray(X).shape)
 
-    def gradients_X_diag(self, dL_dKdiag, X):
-        """(reference `coregionalize.py:156-157`)"""
-        return np.zeros(np.asarray(X).shape)
-
-    def __add__(self, other):
-        return Add([self, other])
-
-    def __mul__(self, other):
-        return Prod([self, other])
-
     def to_dict(self):
         """(reference `coregionalize.py:159-174`)"""
-        return {"class": self._gpy_class, "name": self.name, "input_dim": self.input_dim,
-                "active_dims": self.active_dims.tolist(), "useGPU": True, "W": self.W.values.tolist(),
-                "kappa": self.kappa.values.tolist(), "output_dim": self.output_dim}
+        d = super(Coregionalize, self).to_dict()
+        d.update(useGPU=True, W=self.W.values.tolist(), kappa=self.kappa.values.tolist(), output_dim=self.output_dim)
+        return d
 
     @classmethod
     def from_dict(cls, d):
-        d = dict(d)
-        d.pop("class", None)
-        d.pop("useGPU", None)
-        d["W"], d["kappa"] = np.array(d["W"]), np.array(d["kappa"])
-        return cls(**d)
-
-    def copy(self):
-        return self.__class__.from_dict(self.to_dict())
-
-    __getstate__ = Stationary.__getstate__
+        return super(Coregionalize, cls).from_dict(dict(d, W=np.array(d["W"]), kappa=np.array(d["kappa"])))
 
 
-class Linear(Parameterized):
+class Linear(Kern):
     """Linear kernel k(x, y) = sum_q variances_q x_q y_q (reference `GPy/kern/src/linear.py:13-114`).  Not stationary: the
     diagonal K(x, x) = sum_q variances_q x_q^2 depends on the point.  On the device it is C-ABI kind `MI355GP_LINEAR`: a
     dot-product K-build and gradient pass of its own, alone, in `Add` and as a `Prod` factor; `Kdiag` and the diagonal
     gradients are O(N D) host arithmetic.  One parameter, `variances` (one value, or one per input dimension with `ARD`)."""
     kind = "linear"
     _gpy_class = "GPy.kern.Linear"
-    _support_GPU = True
+    diag_is_constant = False
 
     def __init__(self, input_dim, variances=None, ARD=False, active_dims=None, name="linear", useGPU=True, device=0):
-        super(Linear, self).__init__(name)
-        self.input_dim = int(input_dim)
+        super(Linear, self).__init__(input_dim, active_dims, name, device)
         self.ARD = bool(ARD)
-        self.device = device
-        self.useGPU = True
-        if active_dims is None:
-            active_dims = np.arange(self.input_dim)
-        self.active_dims = np.atleast_1d(np.asarray(active_dims, dtype=np.int_))
-        assert self.active_dims.size == self.input_dim, "input_dim=%d does not match len(active_dims)=%d" % (
-            self.input_dim, self.active_dims.size)
         if not self.ARD:                                               # linear.py:37-48
             if variances is not None:
                 variances = np.asarray(variances, dtype=float)
@@ -602,18 +568,9 @@ class Linear(Parameterized):
                 variances = np.ones(self.input_dim)
         self.variances = Param("variances", variances)
         self.link_parameter(self.variances)
-        self._K_cache = _KCache(limit=3)
 
     def _theta(self):
         return np.asarray(self.variances.values, dtype=np.float64).ravel().copy()
-
-    # slicing, the cached K, the fused / device gradients and gradients_X are the stationary kernels' (they only go through
-    # kind / ARD / _theta)
-    __getstate__ = Stationary.__getstate__
-    _slice_X = Stationary._slice_X
-    K = Stationary.K
-    update_gradients_full = Stationary.update_gradients_full
-    gradients_X = Stationary.gradients_X
 
     def Kdiag(self, X):
         """(reference `linear.py:84-85`)"""
@@ -641,29 +598,14 @@ class Linear(Parameterized):
         """(reference `linear.py:151-152`)"""
         return np.ones(self.input_dim) * self._theta()
 
-    def __add__(self, other):
-        return Add([self, other])
-
-    def __mul__(self, other):
-        return Prod([self, other])
-
     def to_dict(self):
         """(reference `linear.py:54-59`)"""
-        return {"class": self._gpy_class, "name": self.name, "input_dim": self.input_dim,
-                "active_dims": self.active_dims.tolist(), "variances": self.variances.values.tolist(), "ARD": self.ARD,
-                "useGPU": True}
-
-    @classmethod
-    def from_dict(cls, d):
-        d = dict(d)
-        d.pop("class", None)
-        d.pop("useGPU", None)
-        return cls(**d)
-
-    copy = Stationary.copy
+        d = super(Linear, self).to_dict()
+        d.update(variances=self.variances.values.tolist(), ARD=self.ARD, useGPU=True)
+        return d
 
 
-class MLP(Parameterized):
+class MLP(Kern):
     """Multi-layer-perceptron (arc-sine, neural-network) kernel (reference `GPy/kern/src/mlp.py:11-147`):
 
         k(x, y) = variance (2/pi) asin( (w.x.y + b) / sqrt((w.x.x + b + 1)(w.y.y + b + 1)) ),  w.x.y = sum_q w_q x_q y_q
@@ -675,20 +617,12 @@ class MLP(Parameterized):
     `bias_variance`."""
     kind = "mlp"
     _gpy_class = "GPy.kern.MLP"
-    _support_GPU = True
+    diag_is_constant = False
 
     def __init__(self, input_dim, variance=1., weight_variance=1., bias_variance=1., ARD=False, active_dims=None, name="mlp",
                  useGPU=True, device=0):
-        super(MLP, self).__init__(name)
-        self.input_dim = int(input_dim)
+        super(MLP, self).__init__(input_dim, active_dims, name, device)
         self.ARD = bool(ARD)
-        self.device = device
-        self.useGPU = True
-        if active_dims is None:
-            active_dims = np.arange(self.input_dim)
-        self.active_dims = np.atleast_1d(np.asarray(active_dims, dtype=np.int_))
-        assert self.active_dims.size == self.input_dim, "input_dim=%d does not match len(active_dims)=%d" % (
-            self.input_dim, self.active_dims.size)
         if self.ARD:                                                   # mlp.py:39-42
             wv = np.empty((self.input_dim,))
             wv[:] = weight_variance
@@ -701,20 +635,11 @@ class MLP(Parameterized):
         self.bias_variance = Param("bias_variance", bias_variance)
         assert self.variance.size == 1 and self.bias_variance.size == 1
         self.link_parameters(self.variance, self.weight_variance, self.bias_variance)
-        self._K_cache = _KCache(limit=3)
 
     def _theta(self):
         return np.concatenate([[float(self.variance.values[0])],
                                np.asarray(self.weight_variance.values, dtype=np.float64).ravel(),
                                [float(self.bias_variance.values[0])]])
-
-    # slicing, the cached K, the fused / device gradients and gradients_X are the stationary kernels' (they only go through
-    # kind / ARD / _theta)
-    __getstate__ = Stationary.__getstate__
-    _slice_X = Stationary._slice_X
-    K = Stationary.K
-    update_gradients_full = Stationary.update_gradients_full
-    gradients_X = Stationary.gradients_X
 
     def _vwb(self):
         th = self._theta()
@@ -767,49 +692,26 @@ class MLP(Parameterized):
         self.weight_variance.gradient = np.zeros(self.input_dim) if self.ARD else 0.
         self.bias_variance.gradient = 0.
 
-    def __add__(self, other):
-        return Add([self, other])
-
-    def __mul__(self, other):
-        return Prod([self, other])
-
     def to_dict(self):
-        return {"class": self._gpy_class, "name": self.name, "input_dim": self.input_dim,
-                "active_dims": self.active_dims.tolist(), "variance": self.variance.values.tolist(),
-                "weight_variance": self.weight_variance.values.tolist(),
-                "bias_variance": self.bias_variance.values.tolist(), "ARD": self.ARD, "useGPU": True}
-
-    @classmethod
-    def from_dict(cls, d):
-        d = dict(d)
-        d.pop("class", None)
-        d.pop("useGPU", None)
-        return cls(**d)
-
-    copy = Stationary.copy
+        d = super(MLP, self).to_dict()
+        d.update(variance=self.variance.values.tolist(), weight_variance=self.weight_variance.values.tolist(),
+                 bias_variance=self.bias_variance.values.tolist(), ARD=self.ARD, useGPU=True)
+        return d
 
 
-class Poly(Parameterized):
+class Poly(Kern):
     """Polynomial kernel k(x, y) = variance (scale x.y + bias)^order (reference `GPy/kern/src/poly.py:10-49`); `order` (a
     float >= 1) is fixed, not a parameter.  C-ABI kind `MI355GP_POLY`, evaluated by the same device kernels as `MLP`, alone,
     in `Add` and as a `Prod` factor.  As in the reference, `gradients_X`, `gradients_X_diag` and `update_gradients_diag` raise
     `NotImplementedError` (`:45-49`), so a model whose kernel holds a Poly leaf has no `predictive_gradients`."""
     kind = "poly"
     _gpy_class = "GPy.kern.Poly"
-    _support_GPU = True
+    diag_is_constant = False
 
     def __init__(self, input_dim, variance=1., scale=1., bias=1., order=3., active_dims=None, name="poly", useGPU=True,
                  device=0):
-        super(Poly, self).__init__(name)
-        self.input_dim = int(input_dim)
+        super(Poly, self).__init__(input_dim, active_dims, name, device)
         self.ARD = False
-        self.device = device
-        self.useGPU = True
-        if active_dims is None:
-            active_dims = np.arange(self.input_dim)
-        self.active_dims = np.atleast_1d(np.asarray(active_dims, dtype=np.int_))
-        assert self.active_dims.size == self.input_dim, "input_dim=%d does not match len(active_dims)=%d" % (
-            self.input_dim, self.active_dims.size)
         self.variance = Param("variance", variance)
         self.scale = Param("scale", scale)
         self.bias = Param("bias", bias)
@@ -817,16 +719,10 @@ class Poly(Parameterized):
         self.link_parameters(self.variance, self.scale, self.bias)
         assert order >= 1, "The order of the polynomial has to be at least 1."          # poly.py:22
         self.order = float(order)
-        self._K_cache = _KCache(limit=3)
 
     def _theta(self):
         """[variance, scale, bias, order]: the order travels with the parameters and has no gradient"""
         return np.array([float(self.variance.values[0]), float(self.scale.values[0]), float(self.bias.values[0]), self.order])
-
-    __getstate__ = Stationary.__getstate__
-    _slice_X = Stationary._slice_X
-    K = Stationary.K
-    update_gradients_full = Stationary.update_gradients_full
 
     def Kdiag(self, X):
         """(reference `poly.py:33-34`: the diagonal of K) variance (scale |x|^2 + bias)^order"""
@@ -849,19 +745,11 @@ class Poly(Parameterized):
     def reset_gradients(self):
         self.variance.gradient = self.scale.gradient = self.bias.gradient = 0.
 
-    def __add__(self, other):
-        return Add([self, other])
-
-    def __mul__(self, other):
-        return Prod([self, other])
-
     def to_dict(self):
-        return {"class": self._gpy_class, "name": self.name, "input_dim": self.input_dim,
-                "active_dims": self.active_dims.tolist(), "variance": self.variance.values.tolist(),
-                "scale": self.scale.values.tolist(), "bias": self.bias.values.tolist(), "order": self.order, "useGPU": True}
-
-    from_dict = classmethod(MLP.from_dict.__func__)
-    copy = Stationary.copy
+        d = super(Poly, self).to_dict()
+        d.update(variance=self.variance.values.tolist(), scale=self.scale.values.tolist(), bias=self.bias.values.tolist(),
+                 order=self.order, useGPU=True)
+        return d
 
 
 # kernels the exact-GP device path evaluates as one part (the fused inference call takes them alone or in Add / Prod)
@@ -872,14 +760,12 @@ EXACT_ONLY_KINDS = ("ratquad", "stdperiodic", "coregionalize", "linear", "mlp", 
 
 def has_coregionalize(kern):
     """True if the expression holds a Coregionalize part (its Kdiag then depends on the point)"""
-    leaves = kern.leaves() if isinstance(kern, CombinationKernel) else [kern]
-    return any(isinstance(k, Coregionalize) for k in leaves)
+    return any(isinstance(k, Coregionalize) for k in kern.leaves())
 
 
 def diag_depends_on_point(kern):
     """True if Kdiag of the kernel or expression is not a constant: it holds a Coregionalize, Linear, MLP or Poly leaf"""
-    leaves = kern.leaves() if isinstance(kern, CombinationKernel) else [kern]
-    return any(isinstance(k, (Coregionalize, Linear, MLP, Poly)) for k in leaves)
+    return any(not k.diag_is_constant for k in kern.leaves())
 
 
 def _spec_dims(f):
@@ -891,23 +777,18 @@ def _spec_dims(f):
 
 
 def exact_only_leaves(kern):
-    """names of the kernels in `kern` that only the exact-GP path evaluates"""
-    leaves = kern.leaves() if isinstance(kern, CombinationKernel) else [kern]
-    return [type(k).__name__ for k in leaves if getattr(k, "kind", None) in EXACT_ONLY_KINDS]
+    """names of the kernels in `kern` (a foreign object has none) that only the exact-GP path evaluates"""
+    return [type(k).__name__ for k in (kern.leaves() if isinstance(kern, Kern) else []) if k.kind in EXACT_ONLY_KINDS]
 
 
-class Static(Parameterized):
-    """White / Bias (reference `GPy/kern/src/static.py:10-60`): one `variance` parameter, no input dependence."""
-    kind = None
-    _gpy_class = None
+class Static(Kern):
+    """White / Bias (reference `GPy/kern/src/static.py:10-60`): one `variance` parameter, no input dependence; K and its
+    gradients are host arithmetic."""
+    fused_alone = False
 
     def __init__(self, input_dim, variance=1., active_dims=None, name=None, device=0):
-        super(Static, self).__init__(name or self.kind)
-        self.input_dim = int(input_dim)
-        self.device = device
+        super(Static, self).__init__(input_dim, active_dims, name or self.kind, device)
         self.ARD = False
-        self.active_dims = np.arange(self.input_dim) if active_dims is None else np.atleast_1d(
-            np.asarray(active_dims, dtype=np.int_))
         self.variance = Param("variance", variance)
         self.link_parameter(self.variance)
 
@@ -926,19 +807,10 @@ class Static(Parameterized):
     def gradients_X(self, dL_dK, X, X2=None):
         return np.zeros(np.asarray(X).shape)
 
-    def gradients_X_diag(self, dL_dKdiag, X):
-        """(reference `static.py:40-41`)"""
-        return np.zeros(np.asarray(X).shape)
-
     def to_dict(self):
-        return {"class": self._gpy_class, "name": self.name, "input_dim": self.input_dim,
-                "active_dims": self.active_dims.tolist(), "variance": self.variance.values.tolist()}
-
-    def __add__(self, other):
-        return Add([self, other])
-
-    def __mul__(self, other):
-        return Prod([self, other])
+        d = super(Static, self).to_dict()
+        d["variance"] = self.variance.values.tolist()
+        return d
 
 
 class White(Static):
@@ -967,30 +839,22 @@ class Bias(Static):
         self.variance.gradient = np.sum(np.asarray(dL_dK))
 
 
-class CombinationKernel(Parameterized):
-    """Common part of `Add` and `Prod` (reference `GPy/kern/src/kern.py:327-390`): owns the parts, spans their input
+class CombinationKernel(Kern):
+    """Common part of `Add` and `Prod` (reference `GPy/kern/src/kern.py:363-451`): owns the parts, spans their input
     columns, and describes itself to the C-ABI as a list of parts with term ids (`mi355gp_part`)."""
+    is_leaf = False
 
     def __init__(self, parts, name):
-        super(CombinationKernel, self).__init__(name)
+        super(CombinationKernel, self).__init__(max(int(p.active_dims.max()) + 1 for p in parts), None, name,
+                                                parts[0].device)
         self.parts = parts
-        self.input_dim = max(int(p.active_dims.max()) + 1 for p in parts)
-        self.active_dims = np.arange(self.input_dim)
-        self.device = parts[0].device
         for p in parts:
             self.link_parameter(p)
 
-    def gradients_X_diag(self, dL_dKdiag, X):
-        """Stationary and static leaves have a constant diagonal (reference `stationary.py:360-361`, `static.py:40-41`), and so
-        has every sum / product of them (`add.py:102-106`, `prod.py:123-128`); `Add` / `Prod` compose their parts' so that a
-        Linear (`linear.py:140-141`) or MLP (`mlp.py:86-88`) leaf enters."""
-        return np.zeros(np.asarray(X).shape)
-
     def leaves(self):
-        """the stationary / static kernels of the expression in link (= parameter, = gradient) order"""
         out = []
         for p in self.parts:
-            out.extend(p.leaves() if isinstance(p, CombinationKernel) else [p])
+            out.extend(p.leaves())
         return out
 
     def _slice_X(self, X):
@@ -1002,21 +866,15 @@ class CombinationKernel(Parameterized):
             if isinstance(k, Poly):
                 k.gradients_X(None, None)
 
-    def __add__(self, other):
-        return Add([self, other])
+    def to_dict(self):
+        return {"class": self._gpy_class, "name": self.name, "parts": [p.to_dict() for p in self.parts]}
 
-    def __mul__(self, other):
-        return Prod([self, other])
+    @classmethod
+    def from_dict(cls, d):
+        raise NotImplementedError("%s.from_dict: build the parts with their own from_dict and combine them" % cls.__name__)
 
-    def _install_fused(self, g):
-        i = 0
-        for p in self.leaves():
-            k = p._theta().size
-            p._install_gradients(g[i:i + k])
-            i += k
-
-    def update_gradients_diag(self, dL_dKdiag, X):
-        raise NotImplementedError
+    def copy(self):
+        return self.__class__([p.copy() for p in self.parts], name=self.name)
 
     def diag_variance(self):
         """Kdiag of the expression (a constant for stationary / static leaves; not meaningful when `diag_depends_on_point`)"""
@@ -1027,12 +885,13 @@ class Add(CombinationKernel):
     """Sum of kernels (reference `GPy/kern/src/add.py:12-100`).  With `gpy_amd.ExactGaussianInference` the sum is
     assembled and differentiated on the device in the same fused call as a single kernel (C-ABI
     `mi355gp_exact_inference_sum`); parameter / gradient order = the parts' link order.  Parts may be `Prod`s."""
+    _gpy_class = "GPy.kern.Add"
 
     def __init__(self, parts, name="sum"):
         flat = []
         for p in parts:
             flat.extend(p.parts if isinstance(p, Add) else [p])          # add.py:24-33 flattens nested sums
-        assert all(isinstance(p, (Stationary, StdPeriodic, Linear, MLP, Poly, Static, Coregionalize, Prod)) for p in flat), \
+        assert all(getattr(p, "is_leaf", False) or isinstance(p, Prod) for p in flat), \
             "Add supports stationary, StdPeriodic, Linear, MLP, Poly, White, Bias, Coregionalize and Prod parts"
         super(Add, self).__init__(flat, name)
 
@@ -1079,20 +938,18 @@ class Add(CombinationKernel):
     def gradients_X_diag(self, dL_dKdiag, X):                                    # add.py:102-105
         return sum(p.gradients_X_diag(dL_dKdiag, X) for p in self.parts)
 
-    def to_dict(self):
-        return {"class": "GPy.kern.Add", "name": self.name, "parts": [p.to_dict() for p in self.parts]}
-
 
 class Prod(CombinationKernel):
     """Product of kernels (reference `GPy/kern/src/prod.py:24-99`; nested products are flattened, `:33-41`).  Fused on the
     device like `Add`: the factors share a term id of `mi355gp_part`, K is multiplied up factor by factor in the
     K-build kernel and each factor's gradient pass weights dL_dK by the other factors' covariances."""
+    _gpy_class = "GPy.kern.Prod"
 
     def __init__(self, kernels, name="mul"):
         flat = []
         for k in kernels:
             flat.extend(k.parts if isinstance(k, Prod) else [k])
-        assert all(isinstance(k, (Stationary, StdPeriodic, Linear, MLP, Poly, Static, Coregionalize)) for k in flat), \
+        assert all(getattr(k, "is_leaf", False) for k in flat), \
             "Prod supports stationary, StdPeriodic, Linear, MLP, Poly, White, Bias and Coregionalize factors"
         super(Prod, self).__init__(flat, name)
 
@@ -1160,9 +1017,6 @@ class Prod(CombinationKernel):
                     w = w * d
             out = out + p.gradients_X_diag(w, X)
         return out
-
-    def to_dict(self):
-        return {"class": "GPy.kern.Prod", "name": self.name, "parts": [p.to_dict() for p in self.parts]}
 
 
 KERNEL_CLASSES = {"rbf": RBF, "expquad": ExpQuad, "matern52": Matern52, "matern32": Matern32, "exponential": Exponential,

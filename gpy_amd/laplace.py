@@ -11,9 +11,9 @@ import warnings
 import numpy as np
 
 from . import _lib
-from .inference import LinAlgError, _DeviceState
-from .kern import DEVICE_KERNELS, CombinationKernel, diag_depends_on_point
+from .inference import _DeviceState
 from .lazy import DeviceResult, kernel_signature
+from .linalg import jitter_ladder
 from .posterior import PosteriorExact
 
 
@@ -21,9 +21,7 @@ class _LaplaceState(_DeviceState):
     """The device state of a Laplace posterior: prediction goes through `mi355gp_laplace_predict`."""
 
     def predict(self, kern, Xnew, full_cov=False):
-        specs = _specs(kern)
-        Xn = _lib.f64(Xnew) if isinstance(kern, CombinationKernel) else kern._slice_X(Xnew)
-        return self.ctx.laplace_predict(specs, Xn, self.woodbury_vector, full_cov=full_cov)
+        return self.ctx.laplace_predict(kern.part_specs(), kern._slice_X(Xnew), self.woodbury_vector, full_cov=full_cov)
 
     def predictive_gradients(self, kern, Xnew, want_var=True):
         raise NotImplementedError("predictive_gradients of a Laplace posterior")
@@ -32,8 +30,27 @@ class _LaplaceState(_DeviceState):
         raise NotImplementedError("covariance_between_points of a Laplace posterior")
 
 
-def _specs(kern):
-    return kern.part_specs() if isinstance(kern, CombinationKernel) else [(kern.kind, kern.ARD, kern._theta(), None)]
+def entry_checks(name, what, kern, Y):
+    """The entry checks `Laplace` and `EP` share (`name` in the kernel sentence, `what` in the other); returns Y as float64."""
+    Y = np.asarray(Y, dtype=np.float64)
+    if Y.ndim != 2 or Y.shape[1] > 1:
+        raise NotImplementedError("%s on the MI355X path takes one output column, Y has shape %r" % (what, Y.shape))
+    if not getattr(kern, "fused_alone", False):          # a lone White / Bias / Coregionalize, or a foreign kernel
+        raise NotImplementedError("the MI355X %s path evaluates gpy_amd kernels on the device" % name)
+    return Y
+
+
+def begin_session(inf, kern, X, Y):
+    """The start of a session of the exact context, for `Laplace` and `EP`: X and Y uploaded, K = kern.K(X) resident
+    (`mi355gp_laplace_begin`).  Returns (the device state, the mean of K's diagonal for the jitter ladder)."""
+    X = np.asarray(X)
+    if inf._state is None:
+        inf._state = _LaplaceState(inf.device)
+    st = inf._state
+    st.ensure_data(kern._slice_X(X), _lib.f64(Y))
+    st.call_token += 1
+    st.ctx.laplace_begin(kern.part_specs())
+    return st, float(np.mean(kern.jitter_diag(X)))
 
 
 class LaplacePosterior(PosteriorExact):
@@ -76,21 +93,6 @@ class Laplace(object):
         d["_state"] = None
         return d
 
-    def _with_ladder(self, attempt, kdiag_mean):
-        """jitchol's ladder (reference `util/linalg.py:56-75`) on the info codes of the device factorisation of B, whose
-        diagonal is 1 + W_i K_ii."""
-        info, res = attempt(0.0)
-        if info == 0:
-            return res
-        jitter, tries = float(kdiag_mean) * 1e-6, 1
-        while tries <= self.maxtries and np.isfinite(jitter):
-            info, res = attempt(jitter)
-            if info == 0:
-                return res
-            jitter *= 10
-            tries += 1
-        raise LinAlgError("not positive definite, even with jitter.")
-
     def _W(self, likelihood, f, Y, Y_metadata):
         W = -likelihood.d2logpdf_df2(f, Y, Y_metadata=Y_metadata)
         if np.any(np.isnan(W)):
@@ -101,23 +103,13 @@ class Laplace(object):
 
     def inference(self, kern, X, likelihood, Y, mean_function=None, Y_metadata=None):
         assert mean_function is None, "inference with a mean function not implemented"
-        X = np.asarray(X)
-        Y = np.asarray(Y, dtype=np.float64)
-        if Y.ndim != 2 or Y.shape[1] > 1:
-            raise NotImplementedError("Laplace inference on the MI355X path takes one output column, Y has shape %r" % (Y.shape,))
-        if not isinstance(kern, DEVICE_KERNELS + (CombinationKernel,)):
-            raise NotImplementedError("the MI355X Laplace path evaluates gpy_amd kernels on the device")
-        n = X.shape[0]
-        specs = _specs(kern)
-        if self._state is None:
-            self._state = _LaplaceState(self.device)
-        st = self._state
-        st.ensure_data(kern._slice_X(X), _lib.f64(Y))
-        st.call_token += 1
-        ctx = st.ctx
-        ctx.laplace_begin(specs)
-        kd = float(np.mean(kern.Kdiag(X))) if diag_depends_on_point(kern) else (
-            kern.diag_variance() if isinstance(kern, CombinationKernel) else float(specs[0][2][0]))
+        Y = entry_checks("Laplace", "Laplace inference", kern, Y)
+        st, kd = begin_session(self, kern, X, Y)
+        ctx, n = st.ctx, Y.shape[0]
+
+        def ladder(attempt):
+            """jitchol's ladder on the info codes of the device factorisation of B, whose diagonal is 1 + W_i K_ii"""
+            return jitter_ladder(attempt, kd, self.maxtries)[0]
 
         # ---- rasm_mode (reference `laplace.py:148-231`), cold start from Ki_f = 0 (:138) ----
         from scipy import optimize
@@ -133,7 +125,7 @@ class Laplace(object):
             if np.any(np.isnan(grad)):
                 raise ValueError("One or more element(s) of grad is NaN")
             b = W * f + grad
-            a, Ka, _ = self._with_ladder(lambda jit: (lambda r: (r[0], r[1:]))(ctx.laplace_newton(W, b, jit)), kd)
+            a, Ka, _ = ladder(lambda jit: ctx.laplace_newton(W, b, jit))
             dKi_f = a[:, None] - Ki_f
             Kd = Ka[:, None] - f             # K dKi_f, because f = K Ki_f
 
@@ -171,7 +163,7 @@ class Laplace(object):
 
         # ---- mode_computations (reference `laplace.py:233-306`) ----
         W = self._W(likelihood, f_hat, Y, Y_metadata)
-        diag_Ki_W_i, logdet_I_KW = self._with_ladder(lambda jit: (lambda r: (r[0], r[1:]))(ctx.laplace_finish(W, jit)), kd)
+        diag_Ki_W_i, logdet_I_KW = ladder(lambda jit: ctx.laplace_finish(W, jit))
         log_marginal = -0.5 * np.sum(Ki_fhat * f_hat) + np.sum(likelihood.logpdf(f_hat, Y, Y_metadata=Y_metadata)) \
             - 0.5 * logdet_I_KW
         dW_df = -likelihood.d3logpdf_df3(f_hat, Y, Y_metadata=Y_metadata)

@@ -20,25 +20,41 @@ from . import _lib
 LinAlgError = np.linalg.LinAlgError
 
 
-def _ladder(A, maxtries, attempt):
-    """`attempt(A_jittered)` -> (result, info); the reference's jitter ladder around it (`util/linalg.py:61-75`)."""
-    A = np.ascontiguousarray(A, dtype=np.float64)
-    res, info = attempt(A)
-    if info == 0:
-        return res
-    diagA = np.diag(A)
-    if np.any(diagA <= 0.):
+def jitter_ladder(attempt, diag, maxtries=5, check_diag=False):
+    """The reference's jitter ladder (`util/linalg.py:61-75`) on LAPACK-style info codes, for every factorisation of the package:
+    `attempt(extra_jitter)` -> (info, a, b, ...) is tried plainly, then with mean(diag) * 1e-6, times 10 per rung, `maxtries`
+    times.  `diag` is the diagonal of the matrix, one number where it is constant, or a function that gives either and is
+    only called once the plain attempt has failed; `check_diag` refuses a non-positive one like jitchol does.  Returns
+    ((a, b, ...), the jitter that succeeded)."""
+    r = attempt(0.0)
+    if r[0] == 0:
+        return r[1:], 0.0
+    if callable(diag):
+        diag = diag()
+    if check_diag and np.any(np.asarray(diag) <= 0.):
         raise LinAlgError("not pd: non-positive diagonal elements")
-    jitter = diagA.mean() * 1e-6
+    jitter = float(np.mean(diag)) * 1e-6
     num_tries = 1
     while num_tries <= maxtries and np.isfinite(jitter):
-        res, info = attempt(A + np.eye(A.shape[0]) * jitter)
-        if info == 0:
-            logging.getLogger(__name__).warning("Added jitter of {:.10e}".format(jitter))
-            return res
+        r = attempt(jitter)
+        if r[0] == 0:
+            return r[1:], jitter
         jitter *= 10
         num_tries += 1
     raise LinAlgError("not positive definite, even with jitter.")
+
+
+def _ladder(A, maxtries, factor):
+    """`factor(A_jittered)` -> (result, info) under the ladder, for a matrix on the host"""
+    A = np.ascontiguousarray(A, dtype=np.float64)
+
+    def attempt(jitter):
+        res, info = factor(A if jitter == 0.0 else A + np.eye(A.shape[0]) * jitter)
+        return info, res
+    (res,), jitter = jitter_ladder(attempt, np.diag(A), maxtries, check_diag=True)
+    if jitter > 0.0:
+        logging.getLogger(__name__).warning("Added jitter of {:.10e}".format(jitter))
+    return res
 
 
 def jitchol(A, maxtries=5, device=0):

@@ -13,13 +13,12 @@ foreign consumer can materialise in row blocks (`mi355gp_sparse_fetch_dLdKnm`).
 import numpy as np
 
 from . import _lib
-from .kern import RBF, Stationary
-from .lazy import ArrayIdentity, freeze
+from .kern import RBF, Add, Prod, White, exact_only_leaves
+from .lazy import ArrayIdentity, freeze, kernel_signature
 from .likelihoods import Gaussian
+from .linalg import LinAlgError, jitter_ladder
 from .models import PredictionCallers
 from .param import Param, Parameterized
-
-LinAlgError = np.linalg.LinAlgError
 
 
 class _LazyMM(object):
@@ -113,9 +112,8 @@ class SparsePosterior(object):
 
     def _raw_predict(self, kern, Xnew, pred_var, full_cov=False):
         dev = self._device
-        if dev is not None and dev["owner"]._token == dev["token"] and _kernel_sig(kern) == dev["sig"]:
-            Xn = kern._slice_X(np.asarray(Xnew)) if isinstance(kern, Stationary) else _lib.f64(Xnew)
-            return dev["ctx"].predict(_specs(kern), Xn, full_cov=full_cov)
+        if dev is not None and dev["owner"]._token == dev["token"] and kernel_signature(kern) == dev["sig"]:
+            return dev["ctx"].predict(kern.part_specs(), kern._slice_X(Xnew), full_cov=full_cov)
         Kx = kern.K(pred_var, Xnew)                                   # (M, N*): foreign kernel / stale device state
         mu = np.dot(Kx.T, self.woodbury_vector)
         Wi = np.asarray(self.woodbury_inv)
@@ -147,19 +145,6 @@ def _host_predictive_gradients(kern, Xnew, pred_var, woodbury_vector, woodbury_i
     var_jac = kern.gradients_X_diag(np.ones(Xnew.shape[0]), Xnew)
     a2 = -2.0 * np.dot(kern.K(Xnew, pred_var), np.asarray(woodbury_inv))
     return mean_jac, var_jac + kern.gradients_X(a2, Xnew, pred_var)
-
-
-def _specs(kern):
-    """[(kind, ARD, theta, active_dims, term)] of a stationary kernel (its own column slicing applied to X on upload) or
-    of an `Add` of stationary / White / Bias parts (active_dims index the model's X)"""
-    if isinstance(kern, Stationary):
-        return [(kern.kind, kern.ARD, kern._theta(), None, 0)]
-    return kern.part_specs()
-
-
-def _kernel_sig(kern):
-    from .lazy import kernel_signature
-    return kernel_signature(kern)
 
 
 class VarDTC(object):
@@ -198,7 +183,6 @@ class VarDTC(object):
 
     def inference(self, kern, X, Z, likelihood, Y, Y_metadata=None, mean_function=None, precision=None, Lm=None,
                   dL_dKmm=None, psi0=None, psi1=None, psi2=None, Z_tilde=None):
-        from .kern import Add, Prod, White, exact_only_leaves
         new_kinds = exact_only_leaves(kern)
         if new_kinds:
             raise NotImplementedError("the MI355X sparse path does not evaluate %s kernels (the exact GPRegression path does)"
@@ -207,7 +191,8 @@ class VarDTC(object):
         # and of White / Bias parts
         def _prod_ok(k):
             return isinstance(k, Prod) and not any(isinstance(f, (White, Add, Prod)) for f in k.parts)
-        ok = isinstance(kern, Stationary) or _prod_ok(kern) or (
+        lone = getattr(kern, "is_leaf", False) and kern.fused_alone          # (not a lone White / Bias)
+        ok = lone or _prod_ok(kern) or (
             isinstance(kern, Add) and all(_prod_ok(p) if isinstance(p, Prod) else not isinstance(p, Add) for p in kern.parts))
         if not ok:
             raise NotImplementedError("the MI355X sparse path covers gpy_amd's stationary kernels, products of stationary / "
@@ -223,23 +208,15 @@ class VarDTC(object):
         if het and mean_function is not None:                          # var_dtc.py:85-86
             raise ValueError("Mean function not implemented with uncertain inputs or heteroscedasticity")
         m = 0 if mean_function is None else mean_function.f(X)
-        single = isinstance(kern, Stationary)
-        Xs = kern._slice_X(X) if single else _lib.f64(X)
-        Zs = kern._slice_X(np.asarray(Z)) if single else _lib.f64(Z)
+        Xs, Zs = kern._slice_X(X), kern._slice_X(Z)
         R = _lib.f64(Y - m)
         self._ensure(Xs, R)
-        specs = _specs(kern)
-        kdiag = float(kern.variance.values[0]) if single else kern.diag_variance()
-        extra, tries, info = 0.0, 0, 1
-        while True:                                   # jitchol's ladder (util/linalg.py:56-75) for Kmm / B
-            info, r = self._ctx.vardtc_sum(specs, Zs, noise, extra_jitter=extra, want_dL_dm=mean_function is not None,
-                                           want_stage_ms=self.collect_stage_ms)
-            if info == 0:
-                break
-            if tries >= self.maxtries:
-                raise LinAlgError("not positive definite, even with jitter.")
-            extra = kdiag * 1e-6 * 10 ** tries
-            tries += 1
+        specs = kern.part_specs()
+        # jitchol's ladder (util/linalg.py:56-75) for Kmm / B
+        (r,), _ = jitter_ladder(lambda extra: self._ctx.vardtc_sum(specs, Zs, noise, extra_jitter=extra,
+                                                                   want_dL_dm=mean_function is not None,
+                                                                   want_stage_ms=self.collect_stage_ms),
+                                kern.diag_variance(), self.maxtries)
         self._token += 1
         self.last_stage_ms = r.get("stage_ms")
         M, N = Zs.shape[0], Xs.shape[0]
@@ -249,7 +226,7 @@ class VarDTC(object):
                                woodbury_vector=r["woodbury_vector"],
                                K=_LazyMM(self._ctx, C.FETCH_KMM, M, self._token, self),
                                K_chol=_LazyMM(self._ctx, C.FETCH_LM, M, self._token, self),
-                               device={"ctx": self._ctx, "token": self._token, "owner": self, "sig": _kernel_sig(kern)})
+                               device={"ctx": self._ctx, "token": self._token, "owner": self, "sig": kernel_signature(kern)})
         beta = 1.0 / np.fmax(noise, self.const_jitter)
         dL_dR = (r["dnoise"][:, None] if r["dnoise"].ndim == 1 else r["dnoise"]) if het else r["dnoise"]   # N x Dy (var_dtc.py:240-256)
         grad_dict = {"dL_dKmm": _LazyMM(self._ctx, C.FETCH_DLDKMM, M, self._token, self),
@@ -292,10 +269,7 @@ class SparseGP(PredictionCallers, Parameterized):
         if self.mean_function is not None:                                      # sparse_gp.py:84-85
             self.mean_function.update_gradients(self.grad_dict["dL_dm"], self.X)
         fused = self.grad_dict["fused"]
-        if isinstance(self.kern, Stationary):
-            self.kern._install_gradients(fused["dtheta"])
-        else:
-            self.kern._install_fused(fused["dtheta"])
+        self.kern._install_fused(fused["dtheta"])
         self.Z.gradient = fused["dZ"] if fused["dZ"].shape == self.Z.shape else self._scatter_dZ(fused["dZ"])
 
     def _scatter_dZ(self, dZ):
