@@ -489,14 +489,15 @@ __global__ __launch_bounds__(256) void k_grad(KernParams kp, const double* __res
                 gT[a][b] = g * c.dk_or;
             }
         }
-        if (!FUSED && Hout) {   // H = dL_dK * (dK/dr)/r for the gradients_X reductions (stationary.py:330-346)
+        if (!FUSED && Hout) {   // H = dL_dK * (dK/dr)/r for the gradients_X reductions (stationary.py:330-346); 0 at r = 0 as
+                                // `_inv_dist` has it (:225-232): a coincident pair gives exactly nothing, not x H - H x to rounding
 #pragma unroll
             for (int a = 0; a < 4; ++a) {
                 const long i = i0 + ty * 4 + a;
 #pragma unroll
                 for (int b = 0; b < 4; ++b) {
                     const long j = j0 + tx * 4 + b;
-                    if (i < n && j < m) Hout[i * ldh + j] = gT[a][b];
+                    if (i < n && j < m) Hout[i * ldh + j] = (r2[a][b] == 0.0) ? 0.0 : gT[a][b];
                 }
             }
         }
@@ -1641,14 +1642,14 @@ __global__ __launch_bounds__(256) void k_grad_ext(KernParams kp, const double* _
                 }
             }
         }
-        if (!PER && !FUSED && Hout) {   // H = dL_dK (dK/dr) / r for the gradients_X reductions, as in k_grad
+        if (!PER && !FUSED && Hout) {   // H = dL_dK (dK/dr) / r for the gradients_X reductions, as in k_grad (0 at r = 0)
 #pragma unroll
             for (int a = 0; a < 4; ++a) {
                 const long i = i0 + ty * 4 + a;
 #pragma unroll
                 for (int b = 0; b < 4; ++b) {
                     const long j = j0 + tx * 4 + b;
-                    if (i < n && j < m) Hout[i * ldh + j] = gw[a][b];
+                    if (i < n && j < m) Hout[i * ldh + j] = (s[a][b] == 0.0) ? 0.0 : gw[a][b];
                 }
             }
         }
