@@ -13,17 +13,18 @@ from .laplace import Laplace, LaplacePosterior
 from .ep import EP
 from .kern import (OU, RBF, Add, Prod, Bias, Coregionalize, ExpQuad, Exponential, Linear, Matern32, Matern52, MLP, Poly, RatQuad,
                    Stationary, StdPeriodic, White)
-from .likelihoods import Bernoulli, Gaussian, HeteroscedasticGaussian, MixedNoise
+from .likelihoods import Bernoulli, Gaussian, HeteroscedasticGaussian, MixedNoise, Poisson, StudentT
 from .models import GP, GPClassification, GPCoregionalizedRegression, GPHeteroscedasticRegression, GPRegression
 from .posterior import PosteriorEP, PosteriorExact, StudentTPosterior
 from .sparse import SparseGP, SparseGPRegression, VarDTC
 
 __all__ = ["RBF", "OU", "ExpQuad", "HeteroscedasticGaussian", "StudentTPosterior", "Matern52", "Matern32", "Exponential", "RatQuad", "StdPeriodic", "Coregionalize", "Linear", "MLP", "Poly", "MixedNoise", "Stationary", "White", "Bias", "Add", "Prod", "Gaussian", "ExactGaussianInference", "ExactStudentTInference",
-           "PosteriorExact", "GP", "GPRegression", "GPHeteroscedasticRegression", "GPCoregionalizedRegression", "Laplace", "LaplacePosterior", "EP", "PosteriorEP", "Bernoulli", "GPClassification", "VarDTC", "SparseGP", "SparseGPRegression", "MI355GPError", "build", "device_count"]
+           "PosteriorExact", "GP", "GPRegression", "GPHeteroscedasticRegression", "GPCoregionalizedRegression", "Laplace", "LaplacePosterior", "EP", "PosteriorEP", "Bernoulli", "StudentT", "Poisson", "GPClassification", "VarDTC", "SparseGP", "SparseGPRegression", "MI355GPError", "build", "device_count"]
 
 # GPy's import paths, so that `import gpy_amd as GPy` reads like the reference on this path:
 #   GPy.kern.RBF, GPy.likelihoods.Gaussian, GPy.models.GPRegression / SparseGPRegression / GPHeteroscedasticRegression,
-#   GPy.models.GPClassification, GPy.likelihoods.Bernoulli, GPy.likelihoods.link_functions.Probit,
+#   GPy.models.GPClassification, GPy.likelihoods.Bernoulli / StudentT / Poisson, GPy.likelihoods.link_functions.Probit /
+#   Identity / Log,
 #   GPy.core.GP / SparseGP, GPy.inference.latent_function_inference.ExactGaussianInference / VarDTC / Laplace / EP
 from . import ep, inference, kern, laplace, likelihoods, link_functions, linalg, models, sparse, util  # noqa: E402
 import types as _types  # noqa: E402

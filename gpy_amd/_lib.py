@@ -131,6 +131,7 @@ def lib():
     L.mi355gp_laplace_newton.argtypes = [vp, _dp, _dp, cd, _dp, _dp, _c_dp]
     L.mi355gp_laplace_finish.argtypes = [vp, _dp, cd, _dp, _c_dp]
     L.mi355gp_laplace_gradients.argtypes = [vp, _dp, _dp, _dp]
+    L.mi355gp_laplace_implicit.argtypes = [vp, _dp, _dp]
     L.mi355gp_laplace_predict.argtypes = [vp, ci, ctypes.POINTER(Part), _dp, i64, _dp, _c_dp, _c_dp, ci]
     L.mi355gp_ep_recompute.argtypes = [vp, _dp, _dp, cd, cd, ci, _dp, _dp, _c_dp, _c_dp]
     L.mi355gp_ep_sweep.argtypes = [vp, ci, ndpointer(dtype=np.int64, flags="C_CONTIGUOUS"), _dp, cd, cd, _dp, _dp, _dp, _dp, _dp, _dp,
@@ -197,7 +198,7 @@ def lib():
                  "predictive_gradients_sum", "dbg_pipe_share", "pdinv_full", "dbg_graph_factor", "get_option",
                  "sparse_get_profile", "dbg_persist", "dbg_grid_multi", "dbg_update_nt", "dbg_update_rect",
                  "dbg_ipc_selftest", "laplace_begin", "laplace_newton", "laplace_finish", "laplace_gradients",
-                 "laplace_predict", "ep_recompute", "ep_sweep"):
+                 "laplace_implicit", "laplace_predict", "ep_recompute", "ep_sweep"):
         getattr(L, "mi355gp_" + name).restype = ci
     _lib = L
     return L
@@ -220,7 +221,7 @@ EXPORTED = ("mi355gp_last_error", "mi355gp_version", "mi355gp_device_count", "mi
             "mi355gp_sparse_get_profile", "mi355gp_dbg_persist", "mi355gp_dbg_grid_multi", "mi355gp_dbg_update_nt", "mi355gp_dbg_update_rect",
             "mi355gp_dbg_ipc_selftest", "mi355gp_grid_coll_log", "mi355gp_dbg_lauum_plan", "mi355gp_dbg_persist_owners",
             "mi355gp_laplace_begin", "mi355gp_laplace_newton", "mi355gp_laplace_finish", "mi355gp_laplace_gradients",
-            "mi355gp_laplace_predict", "mi355gp_ep_recompute", "mi355gp_ep_sweep")
+            "mi355gp_laplace_implicit", "mi355gp_laplace_predict", "mi355gp_ep_recompute", "mi355gp_ep_sweep")
 
 
 # mi355gp_set_option / mi355gp_get_option ids (include/mi355gp.h, MI355GP_OPT_*)
@@ -436,6 +437,15 @@ class Context(object):
         dtheta = np.zeros(self._lap_ntheta)
         check(lib().mi355gp_laplace_gradients(self._h, Ki_f, s, dtheta), "mi355gp_laplace_gradients")
         return dtheta
+
+    def laplace_implicit(self, dL_dfhat):
+        """s = K (dL_dfhat - K_Wi_i K dL_dfhat): the implicit term of every likelihood-parameter gradient is s . g_i
+        (reference `laplace.py:293-295`, where it is dL_dfhat^T (I - K K_Wi_i) K g_i)."""
+        d = f64(np.ravel(dL_dfhat))
+        assert d.size == self.N
+        s = np.empty(self.N)
+        check(lib().mi355gp_laplace_implicit(self._h, d, s), "mi355gp_laplace_implicit")
+        return s
 
     def laplace_predict(self, specs, Xnew, wv, full_cov=False, want_var=True):
         """`Posterior._raw_predict` for the Laplace posterior (reference `laplace.py:146`, `posterior.py:198-262`)."""

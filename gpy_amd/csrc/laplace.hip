@@ -99,6 +99,16 @@ void lap_enqueue_factor(mi355gp_ctx* c, double jit) {
 void lap_enqueue_Binv(mi355gp_ctx* c, const double* r, double* t) {
     launch_tri_matvec(c->st, c->B, c->npad, c->n, r, 1, c->dTmp, t, c->dTrmvPart);
 }
+// LV_U = u = (I - K_Wi_i K) LV_S = s - W^1/2 B^-1 (W^1/2 K s) for the W of the last finish (LV_SW, X in the context's B buffer)
+static void lap_enqueue_u(mi355gp_ctx* c) {
+    LaplaceSession* L = c->lap;
+    hipStream_t st = c->st;
+    const long n = c->n, np = c->npad;
+    launch_symv_lower(st, L->K, np, n, lvec(c, LV_S), nullptr, lvec(c, LV_T0), nullptr, L->part);
+    hipLaunchKernelGGL(k_lap_mul, VGRID(n), 0, st, lvec(c, LV_SW), lvec(c, LV_T0), n, lvec(c, LV_T1));
+    lap_enqueue_Binv(c, lvec(c, LV_T1), lvec(c, LV_T2));
+    hipLaunchKernelGGL(k_lap_sub_scaled, VGRID(n), 0, st, lvec(c, LV_S), lvec(c, LV_SW), lvec(c, LV_T2), n, lvec(c, LV_U));
+}
 // after the stream has drained: info of the factorisation (from the scalar block).  Returns 1 = redo (persistent launch called
 // off), 0 = go on (*info_out: LAPACK info), < 0 error
 int lap_factor_outcome(mi355gp_ctx* c, int info, int attempt, int* info_out) {
@@ -248,10 +258,7 @@ int mi355gp_laplace_gradients(mi355gp_ctx* c, const double* Ki_f, const double* 
     HIP_CHECK(hipMemcpyAsync(lvec(c, LV_A), Ki_f, sizeof(double) * n, hipMemcpyHostToDevice, st));
     HIP_CHECK(hipMemcpyAsync(lvec(c, LV_S), dL_dfhat, sizeof(double) * n, hipMemcpyHostToDevice, st));
     // u = (I - K_Wi_i K) dL_dfhat, K_Wi_i = W^1/2 B^-1 W^1/2: the implicit part a dL_dfhat^T (I - K K_Wi_i) is a u^T (laplace.py:257-270)
-    launch_symv_lower(st, L->K, np, n, lvec(c, LV_S), nullptr, lvec(c, LV_T0), nullptr, L->part);
-    hipLaunchKernelGGL(k_lap_mul, VGRID(n), 0, st, lvec(c, LV_SW), lvec(c, LV_T0), n, lvec(c, LV_T1));
-    lap_enqueue_Binv(c, lvec(c, LV_T1), lvec(c, LV_T2));
-    hipLaunchKernelGGL(k_lap_sub_scaled, VGRID(n), 0, st, lvec(c, LV_S), lvec(c, LV_SW), lvec(c, LV_T2), n, lvec(c, LV_U));
+    lap_enqueue_u(c);
     // dL_dK, symmetrised, into A (what finish left there is spent); C keeps B^-1 for MI355GP_FETCH_KINV and prediction keeps X
     launch_laplace_dLdK(st, c->C, np, n, lvec(c, LV_SW), lvec(c, LV_A), lvec(c, LV_U), c->A);
     c->lap_stage = 4;
@@ -294,6 +301,26 @@ int mi355gp_laplace_gradients(mi355gp_ctx* c, const double* Ki_f, const double* 
                                                 : c->hPack + c->offGrad + p * (size_t)groups * GP_STRIDE;
         o += part_dtheta(c->parts[p], rec, c->hPack + c->offExt + p * (size_t)groups * GP_STRIDE, o);
     }
+    return 0;
+}
+
+int mi355gp_laplace_implicit(mi355gp_ctx* c, const double* dL_dfhat, double* s_out) {
+    ARG_CHECK(c && c->n > 0 && c->lap && c->lap_stage >= 3, "mi355gp_laplace_implicit: call mi355gp_laplace_finish first");
+    ARG_CHECK(dL_dfhat && s_out, "mi355gp_laplace_implicit: NULL argument");
+    const long n = c->n, np = c->npad;
+    if (int rc = lap_check_vec(dL_dfhat, n, "mi355gp_laplace_implicit", "dL_dfhat")) return rc;
+    HIP_CHECK(hipSetDevice(c->device));
+    EngineShared gate(c->device);
+    LaplaceSession* L = c->lap;
+    hipStream_t st = c->st;
+    HIP_CHECK(hipMemcpyAsync(lvec(c, LV_S), dL_dfhat, sizeof(double) * n, hipMemcpyHostToDevice, st));
+    // s = K u with the u of mi355gp_laplace_gradients: dL_dfhat^T (I - K K_Wi_i) K g = s^T g for every g, because K and K_Wi_i
+    // are symmetric (laplace.py:293-295).  Only vectors are written: K, X, B^-1 and a resident dL_dK stay as they are
+    lap_enqueue_u(c);
+    launch_symv_lower(st, L->K, np, n, lvec(c, LV_U), nullptr, lvec(c, LV_T0), nullptr, L->part);
+    HIP_CHECK(hipMemcpyAsync(s_out, lvec(c, LV_T0), sizeof(double) * n, hipMemcpyDeviceToHost, st));
+    HIP_CHECK(hipStreamSynchronize(st));
+    HIP_CHECK(hipGetLastError());
     return 0;
 }
 

@@ -171,9 +171,14 @@ class Laplace(object):
             raise ValueError("One or more element(s) of dW_df is NaN")
         dL_dfhat = -0.5 * (diag_Ki_W_i[:, None] * dW_df)
         dtheta = ctx.laplace_gradients(Ki_fhat, dL_dfhat)
-        if likelihood.size > 0 and not getattr(likelihood, "is_fixed", False):
-            raise NotImplementedError("likelihood parameters under the Laplace approximation (no such likelihood in gpy_amd)")
         dL_dthetaL = np.zeros(likelihood.size)
+        if likelihood.size > 0 and not getattr(likelihood, "is_fixed", False):
+            # (reference `laplace.py:276-299`) explicit: sum dlogpdf_dtheta_i + 0.5 diag(Ki_W_i) . d2logpdf_df2_dtheta_i; implicit:
+            # dL_dfhat^T (I - K K_Wi_i) K dlogpdf_df_dtheta_i = s . dlogpdf_df_dtheta_i with the one device vector s
+            dlik, dlik_grad, dlik_hess = likelihood._laplace_gradients(f_hat, Y, Y_metadata=Y_metadata)
+            s = ctx.laplace_implicit(dL_dfhat)
+            for i in range(likelihood.size):
+                dL_dthetaL[i] = (np.sum(dlik[i]) + 0.5 * np.sum(diag_Ki_W_i * dlik_hess[i][:, 0])) + np.dot(s, dlik_grad[i][:, 0])
 
         self.f_hat, self.W, self.diag_Ki_W_i = f_hat, W, diag_Ki_W_i
         self._previous_Ki_fhat = Ki_fhat.copy()

@@ -164,18 +164,116 @@ class MixedNoise(Parameterized):
 from . import link_functions  # noqa: E402  (GPy.likelihoods.link_functions)
 
 
-class Bernoulli(Parameterized):
+_SQUARE_LIMIT = np.sqrt(np.finfo(np.float64).max)
+_CUBE_LIMIT = np.nextafter(np.finfo(np.float64).max ** (1 / 3.0), -np.inf)
+
+
+class Likelihood(Parameterized):
+    """What the non-Gaussian likelihoods share (reference `GPy/likelihoods/likelihood.py:17-47,551-732`): a link function, the
+    derivatives in f composed from the subclass's derivatives in lambda = link(f) and the link's by the chain rule (Faa di Bruno;
+    `util/misc.py` chain_1..3, which clip the link's slope before squaring and cubing it), and `_laplace_gradients`, the
+    derivatives with respect to the likelihood's own parameters that the Laplace approximation asks for.  A subclass supplies
+    `logpdf_link` .. `d3logpdf_dlink3` and, if it has parameters, `dlogpdf_link_dtheta`, `dlogpdf_dlink_dtheta` and
+    `d2logpdf_dlink2_dtheta` (each `size` x N x 1, in link order)."""
+
+    def __init__(self, gp_link, name):
+        super(Likelihood, self).__init__(name)
+        assert isinstance(gp_link, link_functions.GPTransformation), "gp_link is not a valid GPTransformation."
+        self.gp_link = gp_link
+        self.log_concave = False
+        self.is_fixed = False
+
+    def update_gradients(self, grad):
+        pass
+
+    def exact_inference_gradients(self, dL_dKdiag, Y_metadata=None):
+        return np.zeros(self.size)
+
+    def conditional_mean(self, gp):
+        raise NotImplementedError
+
+    def conditional_variance(self, gp):
+        raise NotImplementedError
+
+    def _identity(self):
+        return isinstance(self.gp_link, link_functions.Identity)
+
+    # ---- in terms of f: Faa di Bruno (reference `likelihood.py:551-652`, `util/misc.py` chain_1..3) ----------------------
+    def logpdf(self, f, y, Y_metadata=None):
+        return self.logpdf_link(self.gp_link.transf(f), y)
+
+    def dlogpdf_df(self, f, y, Y_metadata=None):
+        if self._identity():
+            return self.dlogpdf_dlink(f, y)
+        return self.dlogpdf_dlink(self.gp_link.transf(f), y) * self.gp_link.dtransf_df(f)
+
+    def d2logpdf_df2(self, f, y, Y_metadata=None):
+        if self._identity():
+            return self.d2logpdf_dlink2(f, y)
+        lam, d1 = self.gp_link.transf(f), self.gp_link.dtransf_df(f)
+        return (self.d2logpdf_dlink2(lam, y) * np.clip(d1, -np.inf, _SQUARE_LIMIT) ** 2
+                + self.dlogpdf_dlink(lam, y) * self.gp_link.d2transf_df2(f))
+
+    def d3logpdf_df3(self, f, y, Y_metadata=None):
+        if self._identity():
+            return self.d3logpdf_dlink3(f, y)
+        lam, d1, d2 = self.gp_link.transf(f), self.gp_link.dtransf_df(f), self.gp_link.d2transf_df2(f)
+        return (self.d3logpdf_dlink3(lam, y) * np.clip(d1, -np.inf, _CUBE_LIMIT) ** 3 + 3.0 * self.d2logpdf_dlink2(lam, y) * d1 * d2
+                + self.dlogpdf_dlink(lam, y) * self.gp_link.d3transf_df3(f))
+
+    # ---- in terms of the likelihood's parameters (reference `likelihood.py:655-732`) -------------------------------------
+    def _no_parameters(self, f):
+        f = np.asarray(f)
+        return np.zeros((0,) + f.shape)
+
+    def dlogpdf_dtheta(self, f, y, Y_metadata=None):
+        if self.size == 0:
+            return self._no_parameters(f)
+        return np.asarray(self.dlogpdf_link_dtheta(self.gp_link.transf(f), y))
+
+    def dlogpdf_df_dtheta(self, f, y, Y_metadata=None):
+        if self.size == 0:
+            return self._no_parameters(f)
+        g = np.asarray(self.dlogpdf_dlink_dtheta(self.gp_link.transf(f), y))
+        return g if self._identity() else g * self.gp_link.dtransf_df(f)[None]
+
+    def d2logpdf_df2_dtheta(self, f, y, Y_metadata=None):
+        if self.size == 0:
+            return self._no_parameters(f)
+        lam = self.gp_link.transf(f)
+        h = np.asarray(self.d2logpdf_dlink2_dtheta(lam, y))
+        if self._identity():
+            return h
+        d1 = np.clip(self.gp_link.dtransf_df(f), -np.inf, _SQUARE_LIMIT)
+        return h * (d1 ** 2)[None] + np.asarray(self.dlogpdf_dlink_dtheta(lam, y)) * self.gp_link.d2transf_df2(f)[None]
+
+    def _laplace_gradients(self, f, y, Y_metadata=None):
+        """(dlogpdf_dtheta, dlogpdf_df_dtheta, d2logpdf_df2_dtheta), each `size` x N x 1 with the parameters in link order
+        (reference `likelihood.py:721-732`)"""
+        out = (self.dlogpdf_dtheta(f, y, Y_metadata=Y_metadata), self.dlogpdf_df_dtheta(f, y, Y_metadata=Y_metadata),
+               self.d2logpdf_df2_dtheta(f, y, Y_metadata=Y_metadata))
+        assert all(a.shape[0] == self.size for a in out)
+        return out
+
+    def predictive_values(self, mu, var, full_cov=False, Y_metadata=None):
+        """(reference `likelihood.py:734-755`)"""
+        pred_mean = self.predictive_mean(mu, var, Y_metadata=Y_metadata)
+        return pred_mean, self.predictive_variance(mu, var, pred_mean, Y_metadata=Y_metadata)
+
+    def to_dict(self):
+        return {"class": "GPy.likelihoods." + type(self).__name__, "name": self.name, "gp_link_dict": self.gp_link.to_dict()}
+
+
+class Bernoulli(Likelihood):
     """Bernoulli likelihood p(y | f) = lambda(f)^y (1 - lambda(f))^(1 - y), y in {0, 1} (reference
     `GPy/likelihoods/bernoulli.py:9-273`), with the derivatives in f that the Laplace approximation needs, composed from
-    the derivatives in lambda and the link's by the chain rule (reference `likelihood.py:551-652`).  No parameters (`size == 0`);
+    the derivatives in lambda and the link's by the chain rule in `Likelihood` (reference `likelihood.py:551-652`).  No parameters (`size == 0`);
     with the probit link it is log-concave.  The probabilities are clipped where the reference clips them (1e-9), so values far
     in the tails agree with it."""
 
     def __init__(self, gp_link=None, name="Bernoulli"):
-        super(Bernoulli, self).__init__(name)
-        self.gp_link = link_functions.Probit() if gp_link is None else gp_link
+        super(Bernoulli, self).__init__(link_functions.Probit() if gp_link is None else gp_link, name)
         self.log_concave = isinstance(self.gp_link, link_functions.Probit)
-        self.is_fixed = False
 
     @staticmethod
     def check_targets(Y):
@@ -184,12 +282,6 @@ class Bernoulli(Parameterized):
         assert np.count_nonzero(Y == 1) + np.count_nonzero(Y == 0) == Y.size, \
             "Bernoulli likelihood is meant to be used only with outputs in {0, 1}."
         return Y
-
-    def update_gradients(self, grad):
-        pass
-
-    def exact_inference_gradients(self, dL_dKdiag, Y_metadata=None):
-        return np.zeros(self.size)
 
     # ---- EP (reference `bernoulli.py:59-92`) -----------------------------------------------------------------------------
     def _ep_sign(self, Y_i):
@@ -246,22 +338,6 @@ class Bernoulli(Parameterized):
         with np.errstate(divide="ignore"):
             return np.where(y == 1, 2.0 / inv_link_f ** 3, -2.0 / (1.0 - inv_link_f) ** 3)
 
-    # ---- in terms of f: Faa di Bruno (reference `likelihood.py:551-652`, `util/misc.py` chain_1..3) ----------------------
-    def logpdf(self, f, y, Y_metadata=None):
-        return self.logpdf_link(self.gp_link.transf(f), y)
-
-    def dlogpdf_df(self, f, y, Y_metadata=None):
-        return self.dlogpdf_dlink(self.gp_link.transf(f), y) * self.gp_link.dtransf_df(f)
-
-    def d2logpdf_df2(self, f, y, Y_metadata=None):
-        lam, d1 = self.gp_link.transf(f), self.gp_link.dtransf_df(f)
-        return self.d2logpdf_dlink2(lam, y) * d1 ** 2 + self.dlogpdf_dlink(lam, y) * self.gp_link.d2transf_df2(f)
-
-    def d3logpdf_df3(self, f, y, Y_metadata=None):
-        lam, d1, d2 = self.gp_link.transf(f), self.gp_link.dtransf_df(f), self.gp_link.d2transf_df2(f)
-        return (self.d3logpdf_dlink3(lam, y) * d1 ** 3 + 3.0 * self.d2logpdf_dlink2(lam, y) * d1 * d2
-                + self.dlogpdf_dlink(lam, y) * self.gp_link.d3transf_df3(f))
-
     # ---- prediction (reference `bernoulli.py:120-136,251-270`, `likelihood.py:734-755`) ---------------------------------
     def predictive_mean(self, mu, variance, Y_metadata=None):
         if not isinstance(self.gp_link, link_functions.Probit):
@@ -271,10 +347,6 @@ class Bernoulli(Parameterized):
     def predictive_variance(self, mu, variance, pred_mean=None, Y_metadata=None):
         return np.nan                                      # as the reference returns it for the probit link
 
-    def predictive_values(self, mu, var, full_cov=False, Y_metadata=None):
-        pred_mean = self.predictive_mean(mu, var, Y_metadata=Y_metadata)
-        return pred_mean, self.predictive_variance(mu, var, pred_mean, Y_metadata=Y_metadata)
-
     def predictive_quantiles(self, mu, var, quantiles, Y_metadata=None):
         p = self.predictive_mean(mu, var)
         return [np.asarray(p > (q / 100.0), dtype=np.int32) for q in quantiles]
@@ -283,5 +355,191 @@ class Bernoulli(Parameterized):
         gp = np.asarray(gp)
         return np.random.binomial(np.ones(gp.size, dtype=int), self.gp_link.transf(gp.ravel())).reshape(gp.shape)
 
+
+class StudentT(Likelihood):
+    """Student-t likelihood with `deg_free` degrees of freedom and squared scale `t_scale2` around lambda(f) (reference
+    `GPy/likelihoods/student_t.py:16-319`; Bayesian Data Analysis' nomenclature):
+
+        log p(y | lambda) = lgamma((v + 1) / 2) - lgamma(v / 2) - log(sigma2 v pi) / 2 - (v + 1) / 2 log(1 + e^2 / (v sigma2)),  e = y - lambda
+
+    The parameters are `t_scale2` then `deg_free` in link order, both positive.  It is not log-concave: the Laplace
+    approximation clips W from below (reference `laplace.py:319-321`)."""
+
+    def __init__(self, gp_link=None, deg_free=5, sigma2=2, name="Student_T"):
+        super(StudentT, self).__init__(link_functions.Identity() if gp_link is None else gp_link, name)
+        self.sigma2 = Param("t_scale2", float(sigma2))          # a squared scale, not a noise variance
+        self.v = Param("deg_free", float(deg_free))
+        self.link_parameter(self.sigma2)
+        self.link_parameter(self.v)
+        self.log_concave = False
+
+    @property
+    def deg_free(self):
+        return self.v
+
+    def _sv(self):
+        return float(self.sigma2.values[0]), float(self.v.values[0])
+
+    def update_gradients(self, grads):
+        """in link order (reference `student_t.py:41-47`)"""
+        self.sigma2.gradient = grads[0]
+        self.v.gradient = grads[1]
+
+    # ---- in terms of lambda = link(f) (reference `student_t.py:76-171`) --------------------------------------------------
+    def logpdf_link(self, inv_link_f, y, Y_metadata=None):
+        from scipy.special import gammaln
+        s2, v = self._sv()
+        e = y - inv_link_f
+        return (gammaln((v + 1) * 0.5) - gammaln(v * 0.5) - 0.5 * np.log(s2 * v * np.pi)
+                - 0.5 * (v + 1) * np.log(1 + (1 / v) * ((e ** 2) / s2)))
+
+    def dlogpdf_dlink(self, inv_link_f, y, Y_metadata=None):
+        s2, v = self._sv()
+        e = y - inv_link_f
+        return ((v + 1) * e) / (v * s2 + e ** 2)
+
+    def d2logpdf_dlink2(self, inv_link_f, y, Y_metadata=None):
+        s2, v = self._sv()
+        e = y - inv_link_f
+        return ((v + 1) * (e ** 2 - v * s2)) / ((s2 * v + e ** 2) ** 2)
+
+    def d3logpdf_dlink3(self, inv_link_f, y, Y_metadata=None):
+        s2, v = self._sv()
+        e = y - inv_link_f
+        return -(2 * (v + 1) * (-e) * (e ** 2 - 3 * v * s2)) / ((e ** 2 + s2 * v) ** 3)
+
+    # ---- in terms of t_scale2 (reference `student_t.py:173-237`) and deg_free (`:239-268`) --------------------------------
+    def dlogpdf_link_dvar(self, inv_link_f, y, Y_metadata=None):
+        s2, v = self._sv()
+        e2 = np.square(y - inv_link_f)
+        return v * (e2 - s2) / (2 * s2 * (s2 * v + e2))
+
+    def dlogpdf_dlink_dvar(self, inv_link_f, y, Y_metadata=None):
+        s2, v = self._sv()
+        e = y - inv_link_f
+        return (v * (v + 1) * (-e)) / ((s2 * v + e ** 2) ** 2)
+
+    def d2logpdf_dlink2_dvar(self, inv_link_f, y, Y_metadata=None):
+        s2, v = self._sv()
+        e = y - inv_link_f
+        return (v * (v + 1) * (s2 * v - 3 * (e ** 2))) / ((s2 * v + (e ** 2)) ** 3)
+
+    def dlogpdf_link_dv(self, inv_link_f, y, Y_metadata=None):
+        from scipy.special import psi
+        s2, v = self._sv()
+        e2 = np.square(y - inv_link_f)
+        d = 0.5 * psi(0.5 * (v + 1)) - 0.5 * psi(0.5 * v) - 1.0 / (2 * v)
+        d = d + 0.5 * (v + 1) * e2 / (v * (e2 + s2 * v))
+        return d - 0.5 * np.log1p(e2 / (s2 * v))
+
+    def dlogpdf_dlink_dv(self, inv_link_f, y, Y_metadata=None):
+        s2, v = self._sv()
+        e = y - inv_link_f
+        e2 = np.square(e)
+        return e * (e2 - s2) / (e2 + s2 * v) ** 2
+
+    def d2logpdf_dlink2_dv(self, inv_link_f, y, Y_metadata=None):
+        s2, v = self._sv()
+        e2 = np.square(y - inv_link_f)
+        q = e2 + s2 * v
+        return (-s2 * (v + 1) + e2 - s2 * v) / q ** 2 - 2 * s2 * (v + 1) * (e2 - s2 * v) / q ** 3
+
+    def dlogpdf_link_dtheta(self, f, y, Y_metadata=None):
+        return np.array((self.dlogpdf_link_dvar(f, y), self.dlogpdf_link_dv(f, y)))
+
+    def dlogpdf_dlink_dtheta(self, f, y, Y_metadata=None):
+        return np.array((self.dlogpdf_dlink_dvar(f, y), self.dlogpdf_dlink_dv(f, y)))
+
+    def d2logpdf_dlink2_dtheta(self, f, y, Y_metadata=None):
+        return np.array((self.d2logpdf_dlink2_dvar(f, y), self.d2logpdf_dlink2_dv(f, y)))
+
+    # ---- prediction (reference `student_t.py:285-319`, `likelihood.py:440-497`) ------------------------------------------
+    def conditional_mean(self, gp):
+        return self.gp_link.transf(gp)
+
+    def conditional_variance(self, gp):
+        """v / (v - 2), as the reference states it (`student_t.py:302-303`: without the squared scale)"""
+        v = self._sv()[1]
+        return v / (v - 2.0)
+
+    def predictive_mean(self, mu, sigma, Y_metadata=None):
+        return self.gp_link.transf(mu)
+
+    def predictive_variance(self, mu, variance, predictive_mean=None, Y_metadata=None):
+        """E[V(y* | f*)] + V[E(y* | f*)] over f* ~ N(mu, variance) (reference `likelihood.py:440-497`, which integrates
+        numerically): with the identity link the first term is the constant `conditional_variance` and the second is
+        `variance`.  It does not exist for deg_free <= 2 (NaN, `student_t.py:289-293`)."""
+        mu = np.asarray(mu, dtype=np.float64)
+        if self._sv()[1] <= 2.0:
+            return np.full(mu.shape, np.nan)
+        if not self._identity():
+            raise NotImplementedError("predictive_variance in closed form needs the identity link")
+        return self.conditional_variance(mu) + np.asarray(variance, dtype=np.float64)
+
+    def samples(self, gp, Y_metadata=None):
+        from scipy import stats
+        gp = np.asarray(gp)
+        s2, v = self._sv()
+        return stats.t.rvs(v, loc=self.gp_link.transf(gp.ravel()), scale=np.sqrt(s2), size=gp.size).reshape(gp.shape)
+
     def to_dict(self):
-        return {"class": "GPy.likelihoods.Bernoulli", "name": self.name, "gp_link_dict": self.gp_link.to_dict()}
+        return dict(super(StudentT, self).to_dict(), deg_free=self.v.values.tolist(), t_scale2=self.sigma2.values.tolist())
+
+
+class Poisson(Likelihood):
+    """Poisson likelihood p(y | lambda) = lambda^y exp(-lambda) / y!, y in {0, 1, 2, ...} (reference
+    `GPy/likelihoods/poisson.py:11-152`); the default link is `Log`, with which it is log-concave
+    (d2 log p / df2 = -exp(f)).  No parameters."""
+
+    def __init__(self, gp_link=None, name="Poisson"):
+        super(Poisson, self).__init__(link_functions.Log() if gp_link is None else gp_link, name)
+        self.log_concave = isinstance(self.gp_link, link_functions.Log)
+
+    @staticmethod
+    def check_targets(Y):
+        """Y must hold non-negative whole numbers (the note of reference `poisson.py:18-19`)."""
+        Y = np.asarray(Y)
+        assert np.count_nonzero((Y >= 0) & (Y == np.floor(Y))) == Y.size, \
+            "Poisson likelihood is meant to be used only with outputs in {0, 1, 2, ...}."
+        return Y
+
+    # ---- in terms of lambda = link(f) (reference `poisson.py:52-127`) ----------------------------------------------------
+    def logpdf_link(self, link_f, y, Y_metadata=None):
+        from scipy.special import gammaln
+        return -link_f + y * np.log(link_f) - gammaln(y + 1)
+
+    def dlogpdf_dlink(self, link_f, y, Y_metadata=None):
+        return y / link_f - 1
+
+    def d2logpdf_dlink2(self, link_f, y, Y_metadata=None):
+        return -y / (link_f ** 2)
+
+    def d3logpdf_dlink3(self, link_f, y, Y_metadata=None):
+        return 2 * y / (link_f) ** 3
+
+    # ---- prediction (reference `poisson.py:129-152`, `likelihood.py:413-497`) --------------------------------------------
+    def conditional_mean(self, gp):
+        return self.gp_link.transf(gp)
+
+    def conditional_variance(self, gp):
+        return self.gp_link.transf(gp)
+
+    def _log_link_only(self, what):
+        if not isinstance(self.gp_link, link_functions.Log):
+            raise NotImplementedError("%s in closed form needs the log link" % what)
+
+    def predictive_mean(self, mu, variance, Y_metadata=None):
+        """E[exp(f*)] = exp(mu + v / 2) for f* ~ N(mu, v): the log-normal mean (the reference integrates numerically,
+        `likelihood.py:413-438`)"""
+        self._log_link_only("predictive_mean")
+        return np.exp(np.asarray(mu, dtype=np.float64) + 0.5 * np.asarray(variance, dtype=np.float64))
+
+    def predictive_variance(self, mu, variance, predictive_mean=None, Y_metadata=None):
+        """E[V(y* | f*)] + V[E(y* | f*)] = E + (exp(v) - 1) exp(2 mu + v) (`likelihood.py:440-497` in closed form)"""
+        self._log_link_only("predictive_variance")
+        mu, v = np.asarray(mu, dtype=np.float64), np.asarray(variance, dtype=np.float64)
+        return np.exp(mu + 0.5 * v) + np.expm1(v) * np.exp(2.0 * mu + v)
+
+    def samples(self, gp, Y_metadata=None):
+        gp = np.asarray(gp)
+        return np.random.poisson(self.gp_link.transf(gp.ravel())).reshape(gp.shape)

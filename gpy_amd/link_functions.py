@@ -51,3 +51,49 @@ class Probit(GPTransformation):
 
     def to_dict(self):
         return {"class": "GPy.likelihoods.link_functions.Probit"}
+
+
+_EXP_LIMIT = np.log(np.finfo(np.float64).max)
+
+
+def safe_exp(f):
+    """exp(f) with the argument clipped from above at log(DBL_MAX), so it never overflows (reference `GPy/util/misc.py:16-18`)."""
+    return np.exp(np.clip(f, -np.inf, _EXP_LIMIT))
+
+
+class Identity(GPTransformation):
+    """g(f) = f (reference `link_functions.py:77-107`)."""
+
+    def transf(self, f):
+        return f
+
+    def dtransf_df(self, f):
+        return np.ones_like(f)
+
+    def d2transf_df2(self, f):
+        return np.zeros_like(f)
+
+    def d3transf_df3(self, f):
+        return np.zeros_like(f)
+
+    def to_dict(self):
+        return {"class": "GPy.likelihoods.link_functions.Identity"}
+
+
+class Log(GPTransformation):
+    """g(f) = log(mu), i.e. mu = exp(f) and so is every derivative (reference `link_functions.py:205-222`)."""
+
+    def transf(self, f):
+        return safe_exp(f)
+
+    def dtransf_df(self, f):
+        return safe_exp(f)
+
+    def d2transf_df2(self, f):
+        return safe_exp(f)
+
+    def d3transf_df3(self, f):
+        return safe_exp(f)
+
+    def to_dict(self):
+        return {"class": "GPy.likelihoods.link_functions.Log"}

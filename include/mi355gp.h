@@ -244,6 +244,14 @@ int mi355gp_laplace_finish(mi355gp_ctx* ctx, const double* W, double extra_jitte
  * dL_dK, MI355GP_FETCH_KINV = K_Wi_i = W^1/2 B^-1 W^1/2 (the posterior's woodbury_inv, :338) and MI355GP_FETCH_K = K;
  * MI355GP_FETCH_L is an error (there is no Cholesky factor of Ky). */
 int mi355gp_laplace_gradients(mi355gp_ctx* ctx, const double* Ki_f, const double* dL_dfhat, double* dtheta_out);
+/* The implicit term of the likelihood-parameter gradients at the mode (laplace.py:276-299).  The reference forms, per
+ * likelihood parameter i, dfhat_dthetaL = (I - K K_Wi_i) K g_i with g_i = d(dlogpdf_df)/dthetaL_i (:293) and then
+ * dL_dfhat^T dfhat_dthetaL (:295).  K and K_Wi_i are symmetric, so that scalar is s^T g_i with the one vector
+ *   s_out (N) = K u,  u = dL_dfhat - K_Wi_i K dL_dfhat  (the u of mi355gp_laplace_gradients, formed by the same code),
+ * whatever the number of parameters: the products with g_i are O(N) host work.  Two N-vectors cross PCIe, nothing N x N.
+ * Needs mi355gp_laplace_finish; may be called before or after mi355gp_laplace_gradients and leaves every matrix of the
+ * session (K, B^-1, a resident dL_dK) as it is.  Fixed-order reductions: the same input gives the same bytes. */
+int mi355gp_laplace_implicit(mi355gp_ctx* ctx, const double* dL_dfhat, double* s_out);
 /* Posterior._raw_predict for Posterior(woodbury_vector = Ki_fhat, woodbury_inv = K_Wi_i, K) (posterior.py:198-262 as built at
  * laplace.py:146): mu_out (M) = K(Xnew, X) wv; full_cov == 0: var_out (M) = Kdiag(Xnew) - colsumsq(L_B^-1 W^1/2 K(X, Xnew)),
  * else M x M.  `parts` = the kernel of the session; needs mi355gp_laplace_finish. */
