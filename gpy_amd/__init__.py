@@ -17,9 +17,10 @@ from .likelihoods import Bernoulli, Gaussian, HeteroscedasticGaussian, MixedNois
 from .models import GP, GPClassification, GPCoregionalizedRegression, GPHeteroscedasticRegression, GPRegression
 from .posterior import PosteriorEP, PosteriorExact, StudentTPosterior
 from .sparse import SparseGP, SparseGPRegression, VarDTC
+from .variational import NormalPosterior
 
 __all__ = ["RBF", "OU", "ExpQuad", "HeteroscedasticGaussian", "StudentTPosterior", "Matern52", "Matern32", "Exponential", "RatQuad", "StdPeriodic", "Coregionalize", "Linear", "MLP", "Poly", "MixedNoise", "Stationary", "White", "Bias", "Add", "Prod", "Gaussian", "ExactGaussianInference", "ExactStudentTInference",
-           "PosteriorExact", "GP", "GPRegression", "GPHeteroscedasticRegression", "GPCoregionalizedRegression", "Laplace", "LaplacePosterior", "EP", "PosteriorEP", "Bernoulli", "StudentT", "Poisson", "GPClassification", "VarDTC", "SparseGP", "SparseGPRegression", "MI355GPError", "build", "device_count"]
+           "PosteriorExact", "GP", "GPRegression", "GPHeteroscedasticRegression", "GPCoregionalizedRegression", "Laplace", "LaplacePosterior", "EP", "PosteriorEP", "Bernoulli", "StudentT", "Poisson", "GPClassification", "VarDTC", "SparseGP", "SparseGPRegression", "NormalPosterior", "MI355GPError", "build", "device_count"]
 
 # GPy's import paths, so that `import gpy_amd as GPy` reads like the reference on this path:
 #   GPy.kern.RBF, GPy.likelihoods.Gaussian, GPy.models.GPRegression / SparseGPRegression / GPHeteroscedasticRegression,
@@ -30,7 +31,8 @@ from . import ep, inference, kern, laplace, likelihoods, link_functions, linalg,
 import types as _types  # noqa: E402
 
 models.SparseGPRegression = SparseGPRegression
-core = _types.SimpleNamespace(GP=GP, SparseGP=SparseGP)
+core = _types.SimpleNamespace(GP=GP, SparseGP=SparseGP, parameterization=_types.SimpleNamespace(
+    variational=_types.SimpleNamespace(NormalPosterior=NormalPosterior)))
 likelihoods.mixed_noise = _types.SimpleNamespace(MixedNoise=MixedNoise)
 inference.latent_function_inference = _types.SimpleNamespace(
     ExactGaussianInference=ExactGaussianInference, ExactStudentTInference=ExactStudentTInference, VarDTC=VarDTC,

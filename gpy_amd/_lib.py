@@ -170,10 +170,16 @@ def lib():
     L.mi355gp_sparse_fetch.argtypes = [vp, ci, _dp]
     L.mi355gp_vardtc_inference_sum.argtypes = [vp, ci, ctypes.POINTER(Part), _dp, i64, _dp, i64, cd, _dp, _c_dp, _c_dp, _c_dp,
                                                _c_dp, _c_dp, _c_dp]
+    L.mi355gp_sparse_set_input_variance.argtypes = [vp, _dp, i64, ci]
+    L.mi355gp_vardtc_inference_uncertain.argtypes = [vp, ci, ctypes.POINTER(Part), _dp, i64, _dp, i64, cd, _dp, _c_dp, _c_dp,
+                                                     _c_dp, _c_dp, _c_dp, _c_dp]
     L.mi355gp_sparse_predict.argtypes = [vp, ci, ctypes.POINTER(Part), _dp, i64, _c_dp, _c_dp, ci]
     L.mi355gp_sparse_fetch_dLdKnm.argtypes = [vp, i64, i64, _dp]
     L.mi355gp_sparse_attach_loopback.argtypes = [vp, ci, ci, ci]
     L.mi355gp_sparse_attach_comm.argtypes = [vp, ci, ci, ctypes.c_char_p]
+    L.mi355gp_rbf_psi.argtypes = [ci, cd, _dp, ci, _dp, i64, _dp, _dp, i64, ci, _c_dp, _c_dp, _c_dp]
+    L.mi355gp_rbf_psi_grad.argtypes = [ci, cd, _dp, ci, _dp, i64, _dp, _dp, i64, ci, _c_dp, _c_dp, _c_dp, _c_dp, _dp, _dp, _dp,
+                                       _dp, _dp]
     L.mi355gp_dbg_mfma.argtypes = [ci, _dp, _dp, _dp]
     L.mi355gp_dbg_gemm.argtypes = [ci, ci, ci, i64, i64, i64, _dp, _dp, _dp, cd, cd, ci, _c_dp]
     L.mi355gp_dbg_peaks.argtypes = [ci, _dp]
@@ -198,7 +204,8 @@ def lib():
                  "predictive_gradients_sum", "dbg_pipe_share", "pdinv_full", "dbg_graph_factor", "get_option",
                  "sparse_get_profile", "dbg_persist", "dbg_grid_multi", "dbg_update_nt", "dbg_update_rect",
                  "dbg_ipc_selftest", "laplace_begin", "laplace_newton", "laplace_finish", "laplace_gradients",
-                 "laplace_implicit", "laplace_predict", "ep_recompute", "ep_sweep"):
+                 "laplace_implicit", "laplace_predict", "ep_recompute", "ep_sweep", "rbf_psi", "rbf_psi_grad",
+                 "sparse_set_input_variance", "vardtc_inference_uncertain"):
         getattr(L, "mi355gp_" + name).restype = ci
     _lib = L
     return L
@@ -221,7 +228,9 @@ EXPORTED = ("mi355gp_last_error", "mi355gp_version", "mi355gp_device_count", "mi
             "mi355gp_sparse_get_profile", "mi355gp_dbg_persist", "mi355gp_dbg_grid_multi", "mi355gp_dbg_update_nt", "mi355gp_dbg_update_rect",
             "mi355gp_dbg_ipc_selftest", "mi355gp_grid_coll_log", "mi355gp_dbg_lauum_plan", "mi355gp_dbg_persist_owners",
             "mi355gp_laplace_begin", "mi355gp_laplace_newton", "mi355gp_laplace_finish", "mi355gp_laplace_gradients",
-            "mi355gp_laplace_implicit", "mi355gp_laplace_predict", "mi355gp_ep_recompute", "mi355gp_ep_sweep")
+            "mi355gp_laplace_implicit", "mi355gp_laplace_predict", "mi355gp_ep_recompute", "mi355gp_ep_sweep",
+            "mi355gp_rbf_psi", "mi355gp_rbf_psi_grad", "mi355gp_sparse_set_input_variance",
+            "mi355gp_vardtc_inference_uncertain")
 
 
 # mi355gp_set_option / mi355gp_get_option ids (include/mi355gp.h, MI355GP_OPT_*)
@@ -517,7 +526,8 @@ class Context(object):
 
 class SparseContext(object):
     """One device context of the sparse (VarDTC) path = one uploaded (X, Y); Z and theta change per call."""
-    FETCH_DLDKMM, FETCH_WOODBURY_INV, FETCH_LM, FETCH_KMM, FETCH_PSI2 = 0, 1, 2, 3, 4
+    FETCH_DLDKMM, FETCH_WOODBURY_INV, FETCH_LM, FETCH_KMM, FETCH_PSI2, FETCH_DLDPSI2_BETA = 0, 1, 2, 3, 4, 5
+    sharded = False
 
     def __init__(self, device=0):
         require_device(device)
@@ -539,6 +549,7 @@ class SparseContext(object):
     def attach_comm(self, rank, world, id_bytes):
         """Row-sharded multi-GPU mode: this rank will upload only its slice of (X, Y) (see gpy_amd.grid.shard_rows)."""
         check(lib().mi355gp_sparse_attach_comm(self._h, rank, world, id_bytes), "mi355gp_sparse_attach_comm")
+        self.sharded = True
 
     def set_data(self, X, Y):
         X, Y = f64(X), f64(Y)
@@ -579,6 +590,7 @@ class SparseContext(object):
     def attach_loopback(self, rank, world, group_key):
         """Row-sharded mode over the in-process loopback transport (one host thread per logical rank)."""
         check(lib().mi355gp_sparse_attach_loopback(self._h, rank, world, int(group_key)), "mi355gp_sparse_attach_loopback")
+        self.sharded = True
 
     def vardtc_sum(self, specs, Z, noise, extra_jitter=0.0, want_dL_dm=False, want_stage_ms=False):
         """Sum-of-parts kernel (specs as for `Context.exact_inference_sum`), scalar or per-point noise variances.
@@ -602,6 +614,37 @@ class SparseContext(object):
                                                       _opt(dm), _opt(ms)), "mi355gp_vardtc_inference_sum")
         res = dict(lml=out[0], dnoise=(rows[:, 0] if self.Dy == 1 else rows) if het else out[1], trA=out[2],
                    data_fit=out[3], dtheta=dtheta, dZ=dZ, woodbury_vector=wv, dL_dm=dm)
+        if ms is not None:
+            res["stage_ms"] = dict(pass1=ms[0], mxm=ms[1], pass2=ms[2], total=ms[3])
+        return rc, res
+
+    def set_input_variance(self, S):
+        """Input variances (N x D, positive and finite) for the data of `set_data`, whose X is then the mean of q(x_n)."""
+        S = f64(S)
+        assert S.ndim == 2, "S must be N x D"
+        check(lib().mi355gp_sparse_set_input_variance(self._h, S, S.shape[0], S.shape[1]), "mi355gp_sparse_set_input_variance")
+
+    def vardtc_uncertain(self, specs, Z, noise, extra_jitter=0.0, want_dmu_dS=True, want_stage_ms=False):
+        """One evaluation with uncertain inputs (one RBF part alone or with White parts, ONE noise variance).
+        (info, dict(lml, dnoise, dtheta (concatenated), dZ, woodbury_vector, dmu, dS[, stage_ms]))"""
+        arr, keep, ntheta = make_parts(specs)
+        Z = f64(Z)
+        self.M = Z.shape[0]
+        assert Z.shape[1] == self.D
+        noise = f64(np.atleast_1d(noise)).ravel()
+        out = np.zeros(NUM_OUT)
+        dtheta = np.zeros(ntheta)
+        dZ = np.zeros((self.M, self.D))
+        wv = np.zeros((self.M, self.Dy))
+        dmu = np.zeros((self.N, self.D)) if want_dmu_dS else None
+        dS = np.zeros((self.N, self.D)) if want_dmu_dS else None
+        ms = np.zeros(4) if want_stage_ms else None
+        rc = check(lib().mi355gp_vardtc_inference_uncertain(self._h, len(specs), arr, Z, self.M, noise, noise.size,
+                                                            float(extra_jitter), out, _opt(dtheta), _opt(dZ), _opt(wv),
+                                                            _opt(dmu), _opt(dS), _opt(ms)),
+                   "mi355gp_vardtc_inference_uncertain")
+        res = dict(lml=out[0], dnoise=out[1], trA=out[2], data_fit=out[3], dtheta=dtheta, dZ=dZ, woodbury_vector=wv,
+                   dmu=dmu, dS=dS)
         if ms is not None:
             res["stage_ms"] = dict(pass1=ms[0], mxm=ms[1], pass2=ms[2], total=ms[3])
         return rc, res
@@ -673,6 +716,47 @@ def gradients_X(kind, ARD, theta, dL_dK, X, X2=None, device=0):
     check(lib().mi355gp_gradients_X(device, KIND_IDS[kind], ard_id(kind, ARD), f64(theta), G, X, N, p2, M, D, out),
           "mi355gp_gradients_X")
     return out
+
+
+def _psi_args(variance, lengthscale, ARD, Z, mu, S, weights):
+    Z, mu, S = f64(Z), f64(mu), f64(S)
+    N, D = mu.shape
+    assert S.shape == mu.shape and Z.ndim == 2 and Z.shape[1] == D, "Z is M x D, mu and S are N x D"
+    ls = theta_vec(variance, lengthscale, ARD, D)[1:]
+    w = None if weights is None else f64(np.ravel(weights))
+    assert w is None or w.size == N
+    return (float(np.ravel(variance)[0]), f64(ls), int(bool(ARD)), Z, Z.shape[0], mu, S, N, D, _opt(w)), w
+
+
+def rbf_psi(variance, lengthscale, ARD, Z, mu, S, weights=None, want_psi1=True, want_psi2=True, device=0):
+    """(psi1 (N x M) or None, psi2 = sum_n w_n psi2n (M x M) or None) of an RBF kernel for inputs N(mu, diag S)
+    (reference `rbf_psi_comp.py:22-50`), on the device."""
+    require_device(device)
+    args, keep = _psi_args(variance, lengthscale, ARD, Z, mu, S, weights)
+    M, N = args[4], args[7]
+    p1 = np.empty((N, M)) if want_psi1 else None
+    p2 = np.empty((M, M)) if want_psi2 else None
+    check(lib().mi355gp_rbf_psi(device, *(args + (_opt(p1), _opt(p2)))), "mi355gp_rbf_psi")
+    return p1, p2
+
+
+def rbf_psi_grad(variance, lengthscale, ARD, Z, mu, S, dL_dpsi0=None, dL_dpsi1=None, dL_dpsi2=None, weights=None, device=0):
+    """(dvariance, dlengthscale, dZ, dmu, dS) from dL_dpsi0 (N), dL_dpsi1 (N x M), dL_dpsi2 (M x M)
+    (reference `rbf_psi_comp.py:70-133`), on the device."""
+    require_device(device)
+    args, keep = _psi_args(variance, lengthscale, ARD, Z, mu, S, weights)
+    M, N, D = args[4], args[7], args[8]
+    d0 = None if dL_dpsi0 is None else f64(np.ravel(dL_dpsi0))
+    d1 = None if dL_dpsi1 is None else f64(dL_dpsi1)
+    d2 = None if dL_dpsi2 is None else f64(dL_dpsi2)
+    assert d0 is None or d0.size == N
+    assert d1 is None or d1.shape == (N, M), "dL_dpsi1 must be N x M"
+    assert d2 is None or d2.shape == (M, M), "dL_dpsi2 must be M x M"
+    dvar, dl = np.zeros(1), np.zeros(D if ARD else 1)
+    dZ, dmu, dS = np.zeros((M, D)), np.zeros((N, D)), np.zeros((N, D))
+    check(lib().mi355gp_rbf_psi_grad(device, *(args + (_opt(d0), _opt(d1), _opt(d2), dvar, dl, dZ, dmu, dS))),
+          "mi355gp_rbf_psi_grad")
+    return dvar[0], dl, dZ, dmu, dS
 
 
 def potrf(A, device=0):

@@ -20,6 +20,7 @@
 #include "../../include/mi355gp_debug.h"
 #include "internal.h"
 #include "parts.h"
+#include "psi.h"
 
 #define SPLITK_MAX 16
 #define CHUNK_MAX 262144                    // rows per chunk: 2 x (chunk x Mp) doubles of HBM (8.6 GB at M = 2048)
@@ -210,6 +211,8 @@ struct mi355gp_sparse {
     LoopGroup* loop = nullptr;    // or the loopback rendezvous
     int world = 1, rank = 0;
     long n_global = 0;
+    double* dSvar = nullptr;      // N x D input variances (mi355gp_sparse_set_input_variance): X is then the mean of q(x_n)
+    bool uncertain_result = false; // the last result came from mi355gp_vardtc_inference_uncertain (no dL_dKnm then)
     double *dX = nullptr, *dY = nullptr, *dV = nullptr, *dBeta = nullptr, *dRowS = nullptr, *dRowT = nullptr, *dRowR = nullptr,
            *Kfu = nullptr,
            *T = nullptr;
@@ -443,7 +446,7 @@ int mi355gp_sparse_destroy(mi355gp_sparse* s) {
     (void)hipSetDevice(s->device);
     (void)hipStreamSynchronize(s->st);
     free_m(s);
-    double** ptrs[] = {&s->dX, &s->dY, &s->dV, &s->dBeta, &s->dRowS, &s->dRowT, &s->dRowR};
+    double** ptrs[] = {&s->dX, &s->dY, &s->dV, &s->dBeta, &s->dRowS, &s->dRowT, &s->dRowR, &s->dSvar};
     for (auto p : ptrs)
         if (*p) (void)hipFree(*p);
     if (s->comm) rccl_comm_destroy(s->comm);
@@ -467,7 +470,7 @@ int mi355gp_sparse_set_data(mi355gp_sparse* s, const double* X, int64_t N, int D
     EngineShared gate(s->device);
     HIP_CHECK(hipStreamSynchronize(s->st));
     free_m(s);
-    double** ptrs[] = {&s->dX, &s->dY, &s->dV, &s->dBeta, &s->dRowS, &s->dRowT, &s->dRowR};
+    double** ptrs[] = {&s->dX, &s->dY, &s->dV, &s->dBeta, &s->dRowS, &s->dRowT, &s->dRowR, &s->dSvar};
     for (auto p : ptrs) {
         if (*p) (void)hipFree(*p);
         *p = nullptr;
@@ -506,6 +509,25 @@ int mi355gp_sparse_set_data(mi355gp_sparse* s, const double* X, int64_t N, int D
         s->n_global = (long)(h[0] + 0.5);
         s->trYYT = h[1];
     }
+    return 0;
+}
+
+// Input variances S (N x D, the shape of set_data's X, which is then read as the mean of q(x_n) = N(mu_n, diag S_n)); every
+// entry must be positive and finite, checked here on the host before anything is launched.  set_data discards them.
+int mi355gp_sparse_set_input_variance(mi355gp_sparse* s, const double* S, int64_t N, int D) {
+    ARG_CHECK(s && s->n > 0, "mi355gp_sparse_set_input_variance: set_data first");
+    ARG_CHECK(S && N == s->n && D == s->D, "mi355gp_sparse_set_input_variance: S must be N x D, the shape of X");
+    ARG_CHECK(!sharded(s), "mi355gp_sparse_set_input_variance: uncertain inputs are not supported by a row-sharded context");
+    for (int64_t i = 0; i < N * D; ++i)
+        if (!(S[i] > 0.0) || !std::isfinite(S[i]))
+            PART_FAIL("mi355gp_sparse_set_input_variance: input variance S[%lld][%lld] = %g: every entry must be positive and finite",
+                      (long long)(i / D), (long long)(i % D), S[i]);
+    HIP_CHECK(hipSetDevice(s->device));
+    EngineShared gate(s->device);
+    HIP_CHECK(hipStreamSynchronize(s->st));
+    if (!s->dSvar) HIP_CHECK(hipMalloc(&s->dSvar, sizeof(double) * N * D));
+    HIP_CHECK(hipMemcpy(s->dSvar, S, sizeof(double) * N * D, hipMemcpyHostToDevice));
+    s->have_result = s->winv_ok = false;
     return 0;
 }
 
@@ -591,6 +613,83 @@ static int potrf_checked(hipStream_t st, double* A, double* X, double* T, double
                          const std::function<void()>& rebuild) {
     if (int rc = factor_launch(st, A, X, T, W, mp, ws)) return rc;
     return factor_check(st, A, X, T, W, mp, ws, info_host, rebuild);
+}
+
+// The M x M phase of an evaluation, shared by the certain- and the uncertain-input entry points: from psi2 (s->psi2), psi1^T V
+// (s->psi1Y) and Lm / Xm to A, LB, B^-1, the Woodbury vectors, dL_dKmm, Q2 = dL_dpsi2_beta and the four scalars; records ev[2].
+static int sparse_mm_block(mi355gp_sparse* s, bool het, double beta, int inject) {
+    hipStream_t st = s->st;
+    const long m = s->m, mp = s->mp;
+    const int Dy = s->Dy;
+    const bool het_multi = het && Dy > 1;
+    // ---- M x M algebra ----------------------------------------------------------------------------------------
+    // A = Lm^-1 psi2_beta Lm^-T (var_dtc.py:129-134), B = I + A (:137), LB = chol(B) (:138), XB = LB^-1
+    // (Xm = Lm^-1 is lower triangular: the four products below walk only its non-zero k range, half the flops of full GEMMs)
+    const int ntm = (int)(mp / NB);
+    launch_trmm64(st, 0, s->Xm, mp, s->psi2, mp, s->T1, mp, ntm, ntm, 1.0);
+    launch_trmm64(st, 2, s->Xm, mp, s->T1, mp, s->Amat, mp, ntm, ntm, het ? 1.0 : beta);
+    auto build_B = [&]() {
+        hipLaunchKernelGGL(k_mm_axpby, grid2d(mp, mp), dim3(256), 0, st, s->Amat, 1.0, (const double*)nullptr, 0.0, 1.0, mp,
+                           s->LB);
+    };
+    build_B();
+    if (inject == 11 || inject == 12) s->ws.persist_test = inject - 10, s->ws.persist_skip = 0;
+    // LB = chol(B), XB = LB^-1 and B^-1 = XB^T XB (lower tiles; :150) in one go
+    if (int rc = potrf_checked(st, s->LB, s->XB, s->Tm, s->Bi, mp, &s->ws, &s->h_info[1], build_B)) return rc;
+    // c = LB^-1 Lm^-1 psi1 V (:141-143), w = LB^-T c (:144), v = Lm^-T w = woodbury_vector (:145)
+    launch_trmv_lower(st, s->Xm, mp, mp, s->psi1Y, Dy, s->vecA);
+    launch_trmv_lower(st, s->XB, mp, mp, s->vecA, Dy, s->cvec);
+    launch_trmv_lower_T(st, s->XB, mp, mp, s->cvec, Dy, s->wvec, s->trmvPart);
+    launch_trmv_lower_T(st, s->Xm, mp, mp, s->wvec, Dy, s->vvec, s->trmvPart);
+    // B^-1 = XB^T XB (lower tiles: computed with the factorisation above), P = Dy B^-1 + w w^T = DBi_plus_BiPBi (:150-152)
+    hipLaunchKernelGGL(k_form_P, grid2d(mp, mp), dim3(256), 0, st, s->Bi, s->wvec, Dy, mp, m, s->P);
+    // dL_dKmm = Lm^-T (-0.5 P - 0.5 Dy B + Dy I) Lm^-1 (:153-158);  -0.5 Dy (I + A) + Dy I = -0.5 Dy A + 0.5 Dy I
+    hipLaunchKernelGGL(k_mm_axpby, grid2d(mp, mp), dim3(256), 0, st, s->P, -0.5, s->Amat, -0.5 * Dy, 0.5 * Dy, mp, s->E);
+    launch_trmm64(st, 1, s->Xm, mp, s->E, mp, s->T1, mp, ntm, ntm, 1.0);                 // Xm^T E
+    launch_trmm64(st, 3, s->Xm, mp, s->T1, mp, s->dLdKmm, mp, ntm, ntm, 1.0);            // (Xm^T E) Xm
+    // Q2 = dL_dpsi2_beta = 0.5 Lm^-T (Dy I - P) Lm^-1 (:220); the precision enters per row in pass 2 (:224-226,231)
+    hipLaunchKernelGGL(k_mm_axpby, grid2d(mp, mp), dim3(256), 0, st, s->P, -0.5, (const double*)nullptr, 0.0, 0.5 * Dy, mp,
+                       s->E);
+    launch_trmm64(st, 1, s->Xm, mp, s->E, mp, s->T1, mp, ntm, ntm, 1.0);
+    launch_trmm64(st, 3, s->Xm, mp, s->T1, mp, s->Q2, mp, ntm, ntm, 1.0);
+    if (het_multi) {
+        // several output columns with per-point noise: dL_dR (var_dtc.py:240-256) needs r_n = |LB^-1 Lm^-1 k_n|^2 on its own
+        // (for Dy = 1 it folds into t_n and s_n); r_n = k_n^T Gr k_n with Gr = Lm^-T B^-1 Lm^-1, built in the Winv buffer
+        hipLaunchKernelGGL(k_sym_from_lower, grid2d(mp, mp), dim3(256), 0, st, s->Bi, mp, 1, s->E);
+        launch_trmm64(st, 1, s->Xm, mp, s->E, mp, s->T1, mp, ntm, ntm, 1.0);
+        launch_trmm64(st, 3, s->Xm, mp, s->T1, mp, s->Winv, mp, ntm, ntm, 1.0);
+    }
+    hipLaunchKernelGGL(k_sparse_scalars_rows, dim3((unsigned)m), dim3(256), 0, st, s->Amat, s->P, s->LB, s->cvec, Dy, mp, m,
+                       s->colPart);
+    hipLaunchKernelGGL(k_sparse_scalars, dim3(1), dim3(256), 0, st, s->colPart, m, s->scal);
+    HIP_CHECK(hipEventRecord(s->ev[2], st));
+    return 0;
+}
+
+// update_gradients_full(dL_dKmm, Z) and gradients_X(dL_dKmm, Z) of every part into its gradMM records and HZ
+static void sparse_kmm_gradients(mi355gp_sparse* s) {
+    hipStream_t st = s->st;
+    const long m = s->m, mp = s->mp;
+    const int D = s->D, groups = (D + 31) / 32;
+    // the M x M part: update_gradients_full(dL_dKmm, Z) and gradients_X(dL_dKmm, Z) (sparse_gp.py:114-117), per part; a factor
+    // of a product sees dL_dKmm times the other factors' K(Z) (prod.py:86-99), materialised in T1
+    for (size_t pi = 0; pi < s->parts.size(); ++pi) {
+        SPart& p = s->parts[pi];
+        const int nbk = grad_generic_num_blocks(m, m);
+        const bool prod = emit_other_factors(s->terms, p.tix, pi, s->T1, [&](int f, double* dst, const double* mul, int, bool) {
+            const SPart& pf = s->parts[(size_t)f];
+            launch_kbuild_cross(st, pf.kp, pf.XtZ, mp, m, pf.XtZ, mp, m, dst, mp, 0, /*diag_same=*/1, mul);
+        });
+        if (prod) hipLaunchKernelGGL(k_mm_mul, grid2d(mp, mp), dim3(256), 0, st, s->T1, s->dLdKmm, mp);
+        launch_grad_generic(st, p.kp, p.XtZ, mp, m, p.XtZ, mp, m, 1, prod ? s->T1 : s->dLdKmm, mp, s->gradPart, GP_STRIDE,
+                            p.stationary() ? s->T1 : nullptr, mp);
+        for (int g = 0; g < (p.kp.ard ? groups : 1); ++g)
+            launch_reduce_partials(st, s->gradPart + (long)g * nbk * GP_STRIDE, nbk, GP_STRIDE, p.gradMM + (long)g * GP_STRIDE);
+        if (p.stationary()) {
+            const int ns = launch_colreduce_multi(st, s->T1, mp, m, mp, p.XtZ, 1, mp, D, 1, s->colPart);
+            launch_sum_splits(st, s->colPart, mp * (D + 1), ns, 0, p.HZ);
+        }
+    }
 }
 
 // One SparseGP.parameters_changed for a SUM of kernels, scalar or per-point noise and R = Y - mean (see mi355gp.h).
@@ -722,48 +821,8 @@ int mi355gp_vardtc_inference_sum(mi355gp_sparse* s, int nparts, const mi355gp_pa
         if (int rc = sparse_allreduce(s, s->psi1Y, (size_t)mp * Dy)) return rc;
     }
     HIP_CHECK(hipEventRecord(s->ev[1], st));
-    // ---- M x M algebra ----------------------------------------------------------------------------------------
-    // A = Lm^-1 psi2_beta Lm^-T (var_dtc.py:129-134), B = I + A (:137), LB = chol(B) (:138), XB = LB^-1
-    // (Xm = Lm^-1 is lower triangular: the four products below walk only its non-zero k range, half the flops of full GEMMs)
-    const int ntm = (int)(mp / NB);
-    launch_trmm64(st, 0, s->Xm, mp, s->psi2, mp, s->T1, mp, ntm, ntm, 1.0);
-    launch_trmm64(st, 2, s->Xm, mp, s->T1, mp, s->Amat, mp, ntm, ntm, het ? 1.0 : beta);
-    auto build_B = [&]() {
-        hipLaunchKernelGGL(k_mm_axpby, grid2d(mp, mp), dim3(256), 0, st, s->Amat, 1.0, (const double*)nullptr, 0.0, 1.0, mp,
-                           s->LB);
-    };
-    build_B();
-    if (inject == 11 || inject == 12) s->ws.persist_test = inject - 10, s->ws.persist_skip = 0;
-    // LB = chol(B), XB = LB^-1 and B^-1 = XB^T XB (lower tiles; :150) in one go
-    if (int rc = potrf_checked(st, s->LB, s->XB, s->Tm, s->Bi, mp, &s->ws, &s->h_info[1], build_B)) return rc;
-    // c = LB^-1 Lm^-1 psi1 V (:141-143), w = LB^-T c (:144), v = Lm^-T w = woodbury_vector (:145)
-    launch_trmv_lower(st, s->Xm, mp, mp, s->psi1Y, Dy, s->vecA);
-    launch_trmv_lower(st, s->XB, mp, mp, s->vecA, Dy, s->cvec);
-    launch_trmv_lower_T(st, s->XB, mp, mp, s->cvec, Dy, s->wvec, s->trmvPart);
-    launch_trmv_lower_T(st, s->Xm, mp, mp, s->wvec, Dy, s->vvec, s->trmvPart);
-    // B^-1 = XB^T XB (lower tiles: computed with the factorisation above), P = Dy B^-1 + w w^T = DBi_plus_BiPBi (:150-152)
-    hipLaunchKernelGGL(k_form_P, grid2d(mp, mp), dim3(256), 0, st, s->Bi, s->wvec, Dy, mp, m, s->P);
-    // dL_dKmm = Lm^-T (-0.5 P - 0.5 Dy B + Dy I) Lm^-1 (:153-158);  -0.5 Dy (I + A) + Dy I = -0.5 Dy A + 0.5 Dy I
-    hipLaunchKernelGGL(k_mm_axpby, grid2d(mp, mp), dim3(256), 0, st, s->P, -0.5, s->Amat, -0.5 * Dy, 0.5 * Dy, mp, s->E);
-    launch_trmm64(st, 1, s->Xm, mp, s->E, mp, s->T1, mp, ntm, ntm, 1.0);                 // Xm^T E
-    launch_trmm64(st, 3, s->Xm, mp, s->T1, mp, s->dLdKmm, mp, ntm, ntm, 1.0);            // (Xm^T E) Xm
-    // Q2 = dL_dpsi2_beta = 0.5 Lm^-T (Dy I - P) Lm^-1 (:220); the precision enters per row in pass 2 (:224-226,231)
-    hipLaunchKernelGGL(k_mm_axpby, grid2d(mp, mp), dim3(256), 0, st, s->P, -0.5, (const double*)nullptr, 0.0, 0.5 * Dy, mp,
-                       s->E);
-    launch_trmm64(st, 1, s->Xm, mp, s->E, mp, s->T1, mp, ntm, ntm, 1.0);
-    launch_trmm64(st, 3, s->Xm, mp, s->T1, mp, s->Q2, mp, ntm, ntm, 1.0);
     const bool het_multi = het && Dy > 1;
-    if (het_multi) {
-        // several output columns with per-point noise: dL_dR (var_dtc.py:240-256) needs r_n = |LB^-1 Lm^-1 k_n|^2 on its own
-        // (for Dy = 1 it folds into t_n and s_n); r_n = k_n^T Gr k_n with Gr = Lm^-T B^-1 Lm^-1, built in the Winv buffer
-        hipLaunchKernelGGL(k_sym_from_lower, grid2d(mp, mp), dim3(256), 0, st, s->Bi, mp, 1, s->E);
-        launch_trmm64(st, 1, s->Xm, mp, s->E, mp, s->T1, mp, ntm, ntm, 1.0);
-        launch_trmm64(st, 3, s->Xm, mp, s->T1, mp, s->Winv, mp, ntm, ntm, 1.0);
-    }
-    hipLaunchKernelGGL(k_sparse_scalars_rows, dim3((unsigned)m), dim3(256), 0, st, s->Amat, s->P, s->LB, s->cvec, Dy, mp, m,
-                       s->colPart);
-    hipLaunchKernelGGL(k_sparse_scalars, dim3(1), dim3(256), 0, st, s->colPart, m, s->scal);
-    HIP_CHECK(hipEventRecord(s->ev[2], st));
+    if (int rc = sparse_mm_block(s, het, beta, inject)) return rc;
     // ---- pass 2: dL_dKnm = beta_n (R v^T + 2 Kfu Q2) (:219,224-226,233), its theta reductions and H^T [X~ | 1] per part --
     for (SPart& p : s->parts) {
         HIP_CHECK(hipMemsetAsync(p.gradNM, 0, sizeof(double) * gsz, st));
@@ -844,25 +903,7 @@ int mi355gp_vardtc_inference_sum(mi355gp_sparse* s, int nparts, const mi355gp_pa
             rb += gsz + hsz;
         }
     }
-    // the M x M part: update_gradients_full(dL_dKmm, Z) and gradients_X(dL_dKmm, Z) (sparse_gp.py:114-117), per part; a factor
-    // of a product sees dL_dKmm times the other factors' K(Z) (prod.py:86-99), materialised in T1
-    for (size_t pi = 0; pi < s->parts.size(); ++pi) {
-        SPart& p = s->parts[pi];
-        const int nbk = grad_generic_num_blocks(m, m);
-        const bool prod = emit_other_factors(s->terms, p.tix, pi, s->T1, [&](int f, double* dst, const double* mul, int, bool) {
-            const SPart& pf = s->parts[(size_t)f];
-            launch_kbuild_cross(st, pf.kp, pf.XtZ, mp, m, pf.XtZ, mp, m, dst, mp, 0, /*diag_same=*/1, mul);
-        });
-        if (prod) hipLaunchKernelGGL(k_mm_mul, grid2d(mp, mp), dim3(256), 0, st, s->T1, s->dLdKmm, mp);
-        launch_grad_generic(st, p.kp, p.XtZ, mp, m, p.XtZ, mp, m, 1, prod ? s->T1 : s->dLdKmm, mp, s->gradPart, GP_STRIDE,
-                            p.stationary() ? s->T1 : nullptr, mp);
-        for (int g = 0; g < (p.kp.ard ? groups : 1); ++g)
-            launch_reduce_partials(st, s->gradPart + (long)g * nbk * GP_STRIDE, nbk, GP_STRIDE, p.gradMM + (long)g * GP_STRIDE);
-        if (p.stationary()) {
-            const int ns = launch_colreduce_multi(st, s->T1, mp, m, mp, p.XtZ, 1, mp, D, 1, s->colPart);
-            launch_sum_splits(st, s->colPart, mp * (D + 1), ns, 0, p.HZ);
-        }
-    }
+    sparse_kmm_gradients(s);
     HIP_CHECK(hipEventRecord(s->ev[3], st));
     // ---- small results to the host -------------------------------------------------------------------------------------
     const size_t np_ = s->parts.size();
@@ -999,6 +1040,7 @@ int mi355gp_vardtc_inference_sum(mi355gp_sparse* s, int nparts, const mi355gp_pa
         }
     }
     s->have_result = true;
+    s->uncertain_result = false;
     return 0;
 }
 
@@ -1010,6 +1052,237 @@ int mi355gp_vardtc_inference(mi355gp_sparse* s, int kind, int ard, const double*
     const mi355gp_part part{kind, ard, 0, nullptr, theta, 0};
     return mi355gp_vardtc_inference_sum(s, 1, &part, Z, M, &noise_var, 1, extra_jitter, out_scalars, dtheta_out, dZ_out, wv_out,
                                         nullptr, nullptr, stage_ms);
+}
+
+// out = scale * (A + A^T) / 2 over the leading m x m of mp x mp matrices, 0 in the padding (rbf_psi_comp.py:109)
+__global__ void k_sym_scaled(const double* __restrict__ A, long mp, long m, double scale, double* __restrict__ out) {
+    const long j = (long)blockIdx.x * blockDim.x + threadIdx.x, i = blockIdx.y;
+    if (j >= mp) return;
+    out[i * mp + j] = (i < m && j < m) ? 0.5 * scale * (A[i * mp + j] + A[j * mp + i]) : 0.0;
+}
+
+// One SparseGP.parameters_changed for UNCERTAIN inputs q(x_n) = N(X_n, diag S_n) (set_data + set_input_variance), a scalar
+// noise variance and one RBF part alone or with White parts (var_dtc.py:93-120,133-163,217-233,258-276 with psi statistics
+// in place of Kdiag / Knm / Knm^T Knm; rbf_psi_comp.py; static.py: White adds its variance to psi0 and to Kmm's diagonal).
+//   pass 1 over chunks of PSI_CHUNK rows: psi1 chunk -> psi1^T V, psi2 += the chunk's sum (fixed order)
+//   the M x M phase of the certain-input call (sparse_mm_block)
+//   pass 2: the psi1 / psi2 gradient kernels with dL_dpsi1 = beta R v^T formed on the fly, dL_dpsi2 = beta Q2,
+//           dL_dpsi0 = -Dy beta / 2; then the Kmm gradients as for certain inputs
+// out_scalars, dtheta_out (concatenated over the parts), dZ_out, wv_out, stage_ms as mi355gp_vardtc_inference_sum;
+// dmu_out / dS_out (optional, N x D): the gradients with respect to the means and variances of the inputs.
+int mi355gp_vardtc_inference_uncertain(mi355gp_sparse* s, int nparts, const mi355gp_part* parts, const double* Z, int64_t M,
+                                       const double* noise, int64_t noise_len, double extra_jitter, double* out_scalars,
+                                       double* dtheta_out, double* dZ_out, double* wv_out, double* dmu_out, double* dS_out,
+                                       double* stage_ms) {
+    const char* where = "mi355gp_vardtc_inference_uncertain";
+    ARG_CHECK(s && s->n > 0, "mi355gp_vardtc_inference_uncertain: set_data first");
+    ARG_CHECK(parts && Z && M > 0 && out_scalars && noise && nparts >= 1, "mi355gp_vardtc_inference_uncertain: bad arguments");
+    ARG_CHECK(!sharded(s), "mi355gp_vardtc_inference_uncertain: a row-sharded context is not supported with uncertain inputs");
+    ARG_CHECK(s->dSvar, "mi355gp_vardtc_inference_uncertain: no input variances; call mi355gp_sparse_set_input_variance after set_data");
+    if (noise_len != 1)
+        PART_FAIL("%s: per-point noise (%lld variances) is not supported with uncertain inputs (var_dtc.py:243); pass one noise variance",
+                  where, (long long)noise_len);
+    int irbf = -1;
+    for (int i = 0; i < nparts; ++i) {
+        if (parts[i].term != 0) PART_FAIL("%s: part %d is a factor of a product; products have no psi statistics here", where, i);
+        if (parts[i].kind == MI355GP_WHITE) continue;
+        if (parts[i].kind != MI355GP_RBF)
+            PART_FAIL("%s: part %d is a %s (kind %d) part; uncertain inputs take one RBF part and White parts only", where, i,
+                      kind_name(parts[i].kind), parts[i].kind);
+        if (irbf >= 0) PART_FAIL("%s: parts %d and %d are both RBF; uncertain inputs take ONE RBF part (and White parts)", where, irbf, i);
+        irbf = i;
+    }
+    if (irbf < 0) PART_FAIL("%s: no RBF part; uncertain inputs take one RBF part and White parts only", where);
+    ARG_CHECK(s->D <= PSI_QMAX, "mi355gp_vardtc_inference_uncertain: the psi-statistics kernels take at most 64 input dimensions");
+    ARG_CHECK(M <= PSI_MMAX, "mi355gp_vardtc_inference_uncertain: the psi-statistics kernels take at most 65535 inducing points");
+    HIP_CHECK(hipSetDevice(s->device));
+    EngineShared gate(s->device);
+    const int D = s->D, Dy = s->Dy;
+    if (M != s->m)
+        if (int rc = alloc_m(s, M)) return rc;
+    if (int rc = prepare_sparse_parts(s, nparts, parts)) return rc;
+    hipStream_t st = s->st;
+    const long n = s->n, m = s->m, mp = s->mp;
+    const int groups = (D + 31) / 32;
+    const size_t gsz = (size_t)groups * GP_STRIDE, hsz = (size_t)mp * (D + 1);
+    const double beta = 1.0 / fmax(noise[0], 1e-8);
+    s->beta_scalar = beta;
+    s->mfma_prof.on = false;
+    s->have_result = s->winv_ok = false;
+    // the psi kernels' operands: a_q = 1 / l_q^2 (0 on a dimension the RBF part does not see), Z zero padded to mpad x Qp
+    const SPart& rbf = s->parts[(size_t)irbf];
+    const double var = rbf.kp.variance;
+    const int Qp = psi_qp(D), RL = 1 + 2 * Qp;
+    const long mpad = round_up(m, PSI_KT), ld2 = round_up(m, PSI_T2), mt = (m + 15) / 16;
+    const long chunk = n < PSI_CHUNK ? n : PSI_CHUNK, nzb = (chunk + PSI_GROWS - 1) / PSI_GROWS;
+    std::vector<double> ha((size_t)Qp, 0.0), hzp((size_t)mpad * Qp, 0.0);
+    for (int q = 0; q < D; ++q) ha[(size_t)q] = rbf.inv_ls[(size_t)q] * rbf.inv_ls[(size_t)q];
+    for (long i = 0; i < m; ++i)
+        for (int q = 0; q < D; ++q) hzp[(size_t)i * Qp + q] = Z[i * D + q];
+    DevBuf dA, dZp, rd1, rd2, lg1, lg2, Ppart, P1s, P2s, Zpart, Zs1, Zs2, dMuO, dSO, rowrec, rec, zz;
+    HIP_CHECK(dA.alloc(Qp));
+    HIP_CHECK(dZp.alloc(hzp.size()));
+    HIP_CHECK(rd1.alloc(2 * chunk * Qp));
+    HIP_CHECK(rd2.alloc(2 * chunk * Qp));
+    HIP_CHECK(lg1.alloc(chunk));
+    HIP_CHECK(lg2.alloc(chunk));
+    HIP_CHECK(Ppart.alloc((size_t)mt * chunk * RL));
+    HIP_CHECK(P1s.alloc((size_t)chunk * RL));
+    HIP_CHECK(P2s.alloc((size_t)chunk * RL));
+    HIP_CHECK(Zpart.alloc((size_t)nzb * mpad * Qp));
+    HIP_CHECK(Zs1.alloc((size_t)mpad * Qp));
+    HIP_CHECK(Zs2.alloc((size_t)mpad * Qp));
+    HIP_CHECK(dMuO.alloc(n * D));
+    HIP_CHECK(dSO.alloc(n * D));
+    HIP_CHECK(rowrec.alloc((size_t)chunk * (1 + Qp)));
+    HIP_CHECK(rec.alloc(1 + Qp));
+    HIP_CHECK(zz.alloc((size_t)m * 2 * Qp));
+    HIP_CHECK(hipMemcpyAsync(dA, ha.data(), sizeof(double) * Qp, hipMemcpyHostToDevice, st));
+    HIP_CHECK(hipMemcpyAsync(dZp, hzp.data(), sizeof(double) * hzp.size(), hipMemcpyHostToDevice, st));
+    HIP_CHECK(hipMemsetAsync(Zpart, 0, sizeof(double) * nzb * mpad * Qp, st));   // the kernels write rows < round_up(m, 16) only
+    hipLaunchKernelGGL(k_fill_const, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, s->dBeta, n, beta);
+    HIP_CHECK(hipMemcpyAsync(s->dZ, Z, sizeof(double) * m * D, hipMemcpyHostToDevice, st));
+    HIP_CHECK(hipEventRecord(s->ev[0], st));
+    {   // V = beta * R
+        const long cnt = n * Dy;
+        hipLaunchKernelGGL(k_scale_rows, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, st, s->dY, s->dBeta, cnt, Dy, s->dV);
+    }
+    scale_for_parts(s, s->dZ, m, mp, true);
+    // Kmm + 1e-8 I (var_dtc.py:93-94), Lm = chol, Xm = Lm^-1 -- as for certain inputs, on the main stream
+    s->h_info[0] = s->h_info[1] = 0;
+    auto rebuild_kmm = [&]() { build_kmm(s, s->Lm, s->T1, 1e-8 + extra_jitter, /*lower_only=*/1, st); };
+    rebuild_kmm();
+    if (int rc = potrf_checked(st, s->Lm, s->Xm, s->Tm, nullptr, mp, &s->ws, &s->h_info[0], rebuild_kmm)) return rc;
+    // ---- pass 1: psi1 chunk (in the Kfu buffer, ld mp) -> psi1^T V; psi2 += sum over the chunk's rows ---------------------
+    HIP_CHECK(hipMemsetAsync(s->psi1Y, 0, sizeof(double) * mp * Dy, st));
+    HIP_CHECK(hipMemsetAsync(s->psi2, 0, sizeof(double) * mp * mp, st));
+    int nch = 0;
+    for (long r0 = 0; r0 < n; r0 += PSI_CHUNK, ++nch) {
+        const long rc = (n - r0 < PSI_CHUNK) ? (n - r0) : PSI_CHUNK;
+        launch_psi_rows(st, s->dX + r0 * D, s->dSvar + r0 * D, dA, rc, D, Qp, rd1, rd2, lg1, lg2);
+        HIP_CHECK(hipMemsetAsync(s->Kfu, 0, sizeof(double) * rc * mp, st));          // psi1 writes columns < m only
+        launch_psi1(st, rd1, lg1, dZp, rc, m, mpad, Qp, var, s->Kfu, mp);
+        const int nsc = launch_colreduce_multi(st, s->Kfu, mp, rc, mp, s->dV + r0 * Dy, Dy, 1, Dy, 0, s->colPart);
+        launch_sum_splits(st, s->colPart, mp * Dy, nsc, 1, s->psi1Y);                 // psi1^T V += psi1_chunk^T V_chunk
+        const int ns = launch_psi2(st, rd2, lg2, nullptr, dZp, dA, rc, m, Qp, var * var, ld2, s->psi2part);
+        launch_psi2_combine(st, s->psi2part, ld2, m, ns, nch > 0, s->psi2, mp);
+    }
+    HIP_CHECK(hipEventRecord(s->ev[1], st));
+    // ---- the M x M phase: A = Lm^-1 (beta psi2) Lm^-T and everything that follows, exactly as for certain inputs ----------
+    if (int rc = sparse_mm_block(s, false, beta, 0)) return rc;
+    // ---- pass 2: the chain rule through psi1 and psi2 ---------------------------------------------------------------------
+    // dL_dpsi2 = beta Q2 symmetrised (in E), LS = dL_dpsi2 * psi2 carries the z_m - z_o terms
+    hipLaunchKernelGGL(k_sym_scaled, grid2d(mp, mp), dim3(256), 0, st, s->Q2, mp, m, beta, s->E);
+    launch_psi2_zz(st, s->E, s->psi2, mp, dZp, m, Qp, zz);
+    std::vector<double> sums((size_t)(1 + Qp), 0.0), csum((size_t)(1 + Qp));
+    nch = 0;
+    for (long r0 = 0; r0 < n; r0 += PSI_CHUNK, ++nch) {
+        const long rc = (n - r0 < PSI_CHUNK) ? (n - r0) : PSI_CHUNK;
+        const int nb = (int)((rc + PSI_GROWS - 1) / PSI_GROWS);
+        launch_psi_rows(st, s->dX + r0 * D, s->dSvar + r0 * D, dA, rc, D, Qp, rd1, rd2, lg1, lg2);
+        launch_psi1_grad(st, rd1, lg1, dZp, nullptr, 0, PsiRank{s->dY + r0 * Dy, s->vvec, Dy, beta}, rc, m, mpad, Qp, var, Ppart,
+                         Zpart);
+        launch_sum_splits(st, Ppart, rc * RL, (int)mt, 0, P1s);
+        launch_sum_splits(st, Zpart, mpad * Qp, nb, nch > 0, Zs1);
+        launch_psi2_grad(st, rd2, lg2, nullptr, dZp, dA, s->E, mp, rc, m, mpad, Qp, var * var, Ppart, Zpart);
+        launch_sum_splits(st, Ppart, rc * RL, (int)mt, 0, P2s);
+        launch_sum_splits(st, Zpart, mpad * Qp, nb, nch > 0, Zs2);
+        launch_psi_rowfinish(st, P1s, P2s, s->dSvar + r0 * D, dA, rc, D, Qp, dMuO + r0 * D, dSO + r0 * D, rowrec);
+        launch_reduce_partials(st, rowrec, (int)rc, 1 + Qp, rec);
+        HIP_CHECK(hipMemcpyAsync(csum.data(), rec, sizeof(double) * (1 + Qp), hipMemcpyDeviceToHost, st));
+        HIP_CHECK(hipStreamSynchronize(st));
+        for (int k = 0; k <= Qp; ++k) sums[(size_t)k] += csum[(size_t)k];             // chunks in row order
+    }
+    sparse_kmm_gradients(s);
+    HIP_CHECK(hipEventRecord(s->ev[3], st));
+    // ---- small results to the host -----------------------------------------------------------------------------------------
+    const size_t np_ = s->parts.size();
+    std::vector<double> gmm(np_ * gsz), HZ(hsz), Zs((size_t)D * mp), zs1((size_t)mpad * Qp), zs2((size_t)mpad * Qp),
+        zzh((size_t)m * 2 * Qp);
+    double scal[8];
+    for (size_t i = 0; i < np_; ++i)
+        HIP_CHECK(hipMemcpyAsync(gmm.data() + i * gsz, s->parts[i].gradMM, sizeof(double) * gsz, hipMemcpyDeviceToHost, st));
+    HIP_CHECK(hipMemcpyAsync(HZ.data(), rbf.HZ, sizeof(double) * hsz, hipMemcpyDeviceToHost, st));
+    HIP_CHECK(hipMemcpyAsync(Zs.data(), rbf.XtZ, sizeof(double) * D * mp, hipMemcpyDeviceToHost, st));
+    HIP_CHECK(hipMemcpyAsync(zs1.data(), Zs1, sizeof(double) * zs1.size(), hipMemcpyDeviceToHost, st));
+    HIP_CHECK(hipMemcpyAsync(zs2.data(), Zs2, sizeof(double) * zs2.size(), hipMemcpyDeviceToHost, st));
+    HIP_CHECK(hipMemcpyAsync(zzh.data(), zz, sizeof(double) * zzh.size(), hipMemcpyDeviceToHost, st));
+    HIP_CHECK(hipMemcpyAsync(scal, s->scal, sizeof(double) * 4, hipMemcpyDeviceToHost, st));
+    if (wv_out) HIP_CHECK(hipMemcpyAsync(wv_out, s->vvec, sizeof(double) * m * Dy, hipMemcpyDeviceToHost, st));
+    if (dmu_out) HIP_CHECK(hipMemcpyAsync(dmu_out, dMuO, sizeof(double) * n * D, hipMemcpyDeviceToHost, st));
+    if (dS_out) HIP_CHECK(hipMemcpyAsync(dS_out, dSO, sizeof(double) * n * D, hipMemcpyDeviceToHost, st));
+    HIP_CHECK(hipStreamSynchronize(st));
+    HIP_CHECK(hipGetLastError());
+    if (stage_ms) {
+        float ms;
+        for (int i = 0; i < 3; ++i) {
+            HIP_CHECK(hipEventElapsedTime(&ms, s->ev[i], s->ev[i + 1]));
+            stage_ms[i] = ms;
+        }
+        HIP_CHECK(hipEventElapsedTime(&ms, s->ev[0], s->ev[3]));
+        stage_ms[3] = ms;
+    }
+    const int info_m = s->h_info[0], info_b = s->h_info[1];
+    if (info_m > 0) return info_m > m ? (int)m : info_m;                 // Kmm not positive definite: caller adds jitter
+    if (info_b > 0) return info_b > m ? (int)m : info_b;
+    const double trA = scal[0], sumAP = scal[1], logLB = scal[2], data_fit = scal[3];
+    const double ng = (double)n, nd = ng * Dy;
+    const double psi0 = expression_kdiag(s->parts, s->terms);           // psi0_n = variance_rbf + sum variance_white, every row
+    // _compute_log_marginal_likelihood and _compute_dL_dR (var_dtc.py:258-276) with psi0.sum() = N psi0
+    const double lik_1 = -0.5 * nd * (log(2.0 * M_PI) - log(beta)) - 0.5 * beta * s->trYYT;
+    const double lik_2 = -0.5 * Dy * (beta * ng * psi0 - trA);
+    const double lik_3 = -(double)Dy * logLB;
+    for (int i = 0; i < MI355GP_NUM_OUT; ++i) out_scalars[i] = 0.0;
+    out_scalars[0] = lik_1 + lik_2 + lik_3 + 0.5 * data_fit;
+    out_scalars[2] = trA;
+    out_scalars[3] = data_fit;
+    out_scalars[4] = logLB;
+    out_scalars[5] = beta;
+    {
+        double dL_dR = -0.5 * nd * beta + 0.5 * s->trYYT * beta * beta;
+        dL_dR += 0.5 * Dy * (ng * psi0 * beta * beta - trA * beta);
+        dL_dR += beta * (0.5 * sumAP - data_fit);
+        out_scalars[1] = dL_dR;
+    }
+    if (dtheta_out) {
+        double* o = dtheta_out;
+        std::vector<double> ab(gsz);
+        for (size_t i = 0; i < np_; ++i) {
+            const double* b = gmm.data() + i * gsz;
+            for (size_t k = 0; k < gsz; ++k) ab[k] = b[k];
+            if ((int)i == irbf) {
+                // the psi1 / psi2 sums in the layout of the reduction records (part_dtheta: dvariance = rec[0] / variance,
+                // dl = -rec / l); the z_m - z_o terms of psi2 add a_q sum LS dz^2 / 2 to dimension q
+                ab[0] += sums[0];
+                for (int q = 0; q < D; ++q) {
+                    double zq = 0.0;
+                    for (long j = 0; j < m; ++j) zq += zzh[(size_t)j * 2 * Qp + Qp + q];
+                    const double lq = sums[(size_t)(1 + q)] + 0.5 * ha[(size_t)q] * zq;
+                    ab[(size_t)(q / 32) * GP_STRIDE + 2 + (q % 32)] -= lq;
+                    ab[1] -= lq;
+                }
+            }
+            const int k = part_dtheta(s->parts[i], ab.data(), nullptr, o);
+            o[0] += -0.5 * Dy * beta * ng;                               // dL_dpsi0 = -Dy beta / 2 per row, dpsi0 / dvariance = 1
+            o += k;
+        }
+    }
+    if (dZ_out) {
+        // gradients_Z_expectations (psi1 and psi2 parts) + gradients_X(dL_dKmm, Z) (sparse_gp.py:100-107)
+        for (long j = 0; j < m; ++j)
+            for (int q = 0; q < D; ++q) {
+                const double il = rbf.inv_ls[(size_t)q];
+                double g = zs1[(size_t)j * Qp + q] + 2.0 * zs2[(size_t)j * Qp + q] - ha[(size_t)q] * zzh[(size_t)j * 2 * Qp + q];
+                if (il != 0.0) {
+                    const double z = Zs[(size_t)q * mp + j];
+                    g += 2.0 * (z * HZ[j * (D + 1) + D] - HZ[j * (D + 1) + q]) * il;
+                }
+                dZ_out[j * D + q] = g;
+            }
+    }
+    s->have_result = true;
+    s->uncertain_result = true;
+    return 0;
 }
 
 // woodbury_inv = Lm^-T (I - B^-1) Lm^-1 (var_dtc.py:206-210) into s->Winv, once per inference call
@@ -1026,7 +1299,8 @@ static int ensure_winv(mi355gp_sparse* s) {
 }
 
 // M x M results of the last call: 0 = dL_dKmm, 1 = woodbury_inv = Lm^-T (I - B^-1) Lm^-1 (var_dtc.py:206-210),
-// 2 = Lm (lower, strict upper zero), 3 = Kmm (with the 1e-8 jitter), 4 = psi2 (heteroscedastic: sum_n beta_n k_n k_n^T)
+// 2 = Lm (lower, strict upper zero), 3 = Kmm (with the 1e-8 jitter), 4 = psi2 (heteroscedastic: sum_n beta_n k_n k_n^T),
+// 5 = dL_dpsi2_beta = Lm^-T (Dy I - P) Lm^-1 / 2 (var_dtc.py:220; dL_dpsi2 = beta times it for a scalar noise)
 int mi355gp_sparse_fetch(mi355gp_sparse* s, int which, double* out) {
     ARG_CHECK(s && out && s->have_result, "mi355gp_sparse_fetch: run mi355gp_vardtc_inference first");
     HIP_CHECK(hipSetDevice(s->device));
@@ -1045,6 +1319,7 @@ int mi355gp_sparse_fetch(mi355gp_sparse* s, int which, double* out) {
         build_kmm(s, s->E, s->T1, 1e-8, /*lower_only=*/0);
         src = s->E;
     } else if (which == 4) src = s->psi2;
+    else if (which == 5) src = s->Q2;
     else {
         mi355gp_set_error("mi355gp_sparse_fetch: unknown matrix id %d", which);
         return -1;
@@ -1061,6 +1336,7 @@ int mi355gp_sparse_fetch(mi355gp_sparse* s, int which, double* out) {
 int mi355gp_sparse_fetch_dLdKnm(mi355gp_sparse* s, int64_t row0, int64_t nrows, double* out) {
     ARG_CHECK(s && out && s->have_result, "mi355gp_sparse_fetch_dLdKnm: run mi355gp_vardtc_inference first");
     ARG_CHECK(row0 >= 0 && nrows > 0 && row0 + nrows <= s->n && nrows <= s->chunk, "mi355gp_sparse_fetch_dLdKnm: bad row range");
+    ARG_CHECK(!s->uncertain_result, "mi355gp_sparse_fetch_dLdKnm: the last call had uncertain inputs (dL_dpsi1 / dL_dpsi2 take dL_dKnm's place)");
     HIP_CHECK(hipSetDevice(s->device));
     EngineShared gate(s->device);
     hipStream_t st = s->st;

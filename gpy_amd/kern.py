@@ -270,6 +270,56 @@ class RBF(Stationary):
         if self.use_invLengthscale:
             self.inv_l.gradient = self.lengthscale.gradient * (self.lengthscale.values ** 3 / -2.)
 
+    # ---- psi-statistics for Gaussian inputs qX = NormalPosterior (reference `rbf.py:344-367`, `psi_comp/rbf_psi_comp.py`) ----
+    def _psi_operands(self, Z, qX):
+        return self._slice_X(Z), self._slice_X(qX.mean), self._slice_X(qX.variance)
+
+    def psi0(self, Z, qX):
+        return np.full(qX.mean.shape[0], float(self.variance.values[0]))
+
+    def psi1(self, Z, qX):
+        Zs, mu, S = self._psi_operands(Z, qX)
+        return _lib.rbf_psi(self.variance.values, self.lengthscale.values, self.ARD, Zs, mu, S, want_psi2=False,
+                            device=self.device)[0]
+
+    def psi2(self, Z, qX):
+        Zs, mu, S = self._psi_operands(Z, qX)
+        return _lib.rbf_psi(self.variance.values, self.lengthscale.values, self.ARD, Zs, mu, S, want_psi1=False,
+                            device=self.device)[1]
+
+    def psi2n(self, Z, qX):
+        """N x M x M ON THE HOST for a foreign consumer that wants the summands; the inference path never forms it.
+        The cost is O(N) C-ABI calls: every row validates, uploads Z and allocates its buffers again (the device kernel has no
+        per-row output mode yet)."""
+        Zs, mu, S = self._psi_operands(Z, qX)
+        return np.stack([_lib.rbf_psi(self.variance.values, self.lengthscale.values, self.ARD, Zs, mu[n:n + 1], S[n:n + 1],
+                                      want_psi1=False, device=self.device)[1] for n in range(mu.shape[0])])
+
+    def _psi_grad(self, dL_dpsi0, dL_dpsi1, dL_dpsi2, Z, qX):
+        if dL_dpsi2 is not None and np.ndim(dL_dpsi2) != 2:
+            raise NotImplementedError("RBF psi gradients take dL_dpsi2 as M x M (the summed psi2), not per data point")
+        Zs, mu, S = self._psi_operands(Z, qX)
+        return _lib.rbf_psi_grad(self.variance.values, self.lengthscale.values, self.ARD, Zs, mu, S, dL_dpsi0, dL_dpsi1,
+                                 dL_dpsi2, device=self.device)
+
+    def _scatter(self, g, like):
+        if g.shape == np.shape(like):
+            return g
+        full = np.zeros(np.shape(like))
+        full[:, self.active_dims] = g
+        return full
+
+    def update_gradients_expectations(self, dL_dpsi0, dL_dpsi1, dL_dpsi2, Z, qX):
+        dvar, dl = self._psi_grad(dL_dpsi0, dL_dpsi1, dL_dpsi2, Z, qX)[:2]
+        self._install_gradients(np.concatenate([[dvar], dl]))
+
+    def gradients_Z_expectations(self, dL_dpsi0, dL_dpsi1, dL_dpsi2, Z, qX):
+        return self._scatter(self._psi_grad(dL_dpsi0, dL_dpsi1, dL_dpsi2, Z, qX)[2], Z)
+
+    def gradients_qX_expectations(self, dL_dpsi0, dL_dpsi1, dL_dpsi2, Z, qX):
+        g = self._psi_grad(dL_dpsi0, dL_dpsi1, dL_dpsi2, Z, qX)
+        return self._scatter(g[3], qX.mean), self._scatter(g[4], qX.mean)
+
     def to_dict(self):
         d = super(RBF, self).to_dict()
         d["inv_l"] = self.use_invLengthscale
@@ -825,6 +875,28 @@ class White(Static):
     def update_gradients_full(self, dL_dK, X, X2=None):
         self.variance.gradient = np.trace(np.asarray(dL_dK)) if X2 is None else 0.
 
+    # psi-statistics (reference `static.py:40-60,83-93`): psi0 = variance, psi1 = psi2 = 0
+    def psi0(self, Z, qX):
+        return np.full(qX.mean.shape[0], float(self.variance.values[0]))
+
+    def psi1(self, Z, qX):
+        return np.zeros((qX.mean.shape[0], np.asarray(Z).shape[0]))
+
+    def psi2(self, Z, qX):
+        return np.zeros((np.asarray(Z).shape[0],) * 2)
+
+    def psi2n(self, Z, qX):
+        return np.zeros((qX.mean.shape[0],) + (np.asarray(Z).shape[0],) * 2)
+
+    def update_gradients_expectations(self, dL_dpsi0, dL_dpsi1, dL_dpsi2, Z, qX):
+        self.variance.gradient = np.sum(dL_dpsi0)
+
+    def gradients_Z_expectations(self, dL_dpsi0, dL_dpsi1, dL_dpsi2, Z, qX):
+        return np.zeros(np.asarray(Z).shape)
+
+    def gradients_qX_expectations(self, dL_dpsi0, dL_dpsi1, dL_dpsi2, Z, qX):
+        return np.zeros(qX.mean.shape), np.zeros(qX.mean.shape)
+
 
 class Bias(Static):
     """(reference `static.py:151-173`): constant covariance."""
@@ -937,6 +1009,41 @@ class Add(CombinationKernel):
 
     def gradients_X_diag(self, dL_dKdiag, X):                                    # add.py:102-105
         return sum(p.gradients_X_diag(dL_dKdiag, X) for p in self.parts)
+
+    # ---- psi-statistics (reference `add.py:107-246`): one RBF part and White parts only.  White's psi1 is zero, so the cross
+    # terms of psi2 vanish and every part sees the same dL_dpsi0/1/2.
+    def _psi_parts(self):
+        for p in self.parts:
+            if not isinstance(p, (RBF, White)):
+                raise NotImplementedError("psi-statistics of a sum cover one RBF part and White parts; part %r is a %s"
+                                          % (p.name, type(p).__name__))
+        if sum(isinstance(p, RBF) for p in self.parts) > 1:
+            raise NotImplementedError("psi-statistics of a sum cover ONE RBF part (psi2 of two has cross terms); part %r is "
+                                      "a second RBF" % [p.name for p in self.parts if isinstance(p, RBF)][1])
+        return self.parts
+
+    def psi0(self, Z, qX):
+        return sum(p.psi0(Z, qX) for p in self._psi_parts())
+
+    def psi1(self, Z, qX):
+        return sum(p.psi1(Z, qX) for p in self._psi_parts())
+
+    def psi2(self, Z, qX):
+        return sum(p.psi2(Z, qX) for p in self._psi_parts())
+
+    def psi2n(self, Z, qX):
+        return sum(p.psi2n(Z, qX) for p in self._psi_parts())
+
+    def update_gradients_expectations(self, dL_dpsi0, dL_dpsi1, dL_dpsi2, Z, qX):
+        for p in self._psi_parts():
+            p.update_gradients_expectations(dL_dpsi0, dL_dpsi1, dL_dpsi2, Z, qX)
+
+    def gradients_Z_expectations(self, dL_dpsi0, dL_dpsi1, dL_dpsi2, Z, qX):
+        return sum(p.gradients_Z_expectations(dL_dpsi0, dL_dpsi1, dL_dpsi2, Z, qX) for p in self._psi_parts())
+
+    def gradients_qX_expectations(self, dL_dpsi0, dL_dpsi1, dL_dpsi2, Z, qX):
+        gs = [p.gradients_qX_expectations(dL_dpsi0, dL_dpsi1, dL_dpsi2, Z, qX) for p in self._psi_parts()]
+        return sum(g[0] for g in gs), sum(g[1] for g in gs)
 
 
 class Prod(CombinationKernel):

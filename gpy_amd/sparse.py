@@ -9,6 +9,11 @@ Gaussian noise variance and an optional mean function.  The N x M matrix `dL_dKn
 inducing-input gradients that `SparseGP._update_gradients` derives from it are reduced on the device in the second
 streaming pass and travel in `grad_dict['fused']`; `dL_dKmm` is a lazy device view and `dL_dKnm` a lazy object that a
 foreign consumer can materialise in row blocks (`mi355gp_sparse_fetch_dLdKnm`).
+
+Uncertain inputs: an X that is a `NormalPosterior` (or `SparseGPRegression(X, Y, X_variance=...)`) is evaluated through the
+RBF psi-statistics on the device (`mi355gp_vardtc_inference_uncertain`) for one RBF kernel alone or summed with White parts
+and one noise variance; `grad_dict` then has the reference's keys `dL_dpsi0 / dL_dpsi1 / dL_dpsi2` in place of
+`dL_dKdiag / dL_dKnm`, and `fused` also carries the gradients with respect to the inputs' means and variances.
 """
 import numpy as np
 
@@ -19,6 +24,7 @@ from .likelihoods import Gaussian
 from .linalg import LinAlgError, jitter_ladder
 from .models import PredictionCallers
 from .param import Param, Parameterized
+from .variational import NormalPosterior
 
 
 class _LazyMM(object):
@@ -94,6 +100,41 @@ class _LazyNM(object):
         return self.fetch().T
 
 
+class _LazyPsi1(object):
+    """dL_dpsi1 = beta R v^T (N x M, reference `var_dtc.py:219`) of an uncertain-input call.  The device forms it on the fly
+    inside the gradient kernels and never holds it; a foreign consumer gets the rank-Dy product from the host."""
+    __array_priority__ = 100.0
+    ndim = 2
+    dtype = np.dtype(np.float64)
+
+    def __init__(self, beta, R, wv):
+        self._beta, self._R, self._wv = beta, R, wv
+        self.shape = (R.shape[0], wv.shape[0])
+
+    def fetch(self):
+        return self._beta * np.dot(self._R, self._wv.T)
+
+    def __array__(self, dtype=None, copy=None):
+        a = self.fetch()
+        return a if dtype is None else a.astype(dtype, copy=False)
+
+    def __getitem__(self, idx):
+        return self.fetch()[idx]
+
+
+class _LazyScaledMM(_LazyMM):
+    """an M x M device result times a scalar (dL_dpsi2 = beta * dL_dpsi2_beta, `var_dtc.py:220-233`)"""
+
+    def __init__(self, scale, *a):
+        super(_LazyScaledMM, self).__init__(*a)
+        self._scale = scale
+
+    def fetch(self):
+        if self._host is None:
+            self._host = self._scale * super(_LazyScaledMM, self).fetch()
+        return self._host
+
+
 class SparsePosterior(object):
     """`Posterior(woodbury_inv, woodbury_vector, K=Kmm, K_chol=Lm)` of the reference (`var_dtc.py:213`,
     `posterior.py:21-77`); prediction follows `Posterior._raw_predict` (`posterior.py:198-262`) and runs on the device
@@ -153,7 +194,7 @@ class VarDTC(object):
     def __init__(self, device=0, maxtries=5):
         self.device, self.maxtries = device, maxtries
         self._ctx = None
-        self._X = self._Y = None
+        self._X = self._Y = self._S = None
         self._token = 0
         self.last_stage_ms = None
         self.collect_stage_ms = False
@@ -170,7 +211,7 @@ class VarDTC(object):
     def __getstate__(self):
         d = dict(self.__dict__)
         d["_ctx"] = None
-        d["_X"] = d["_Y"] = None
+        d["_X"] = d["_Y"] = d["_S"] = None
         return d
 
     def _ensure(self, X, Y):
@@ -179,10 +220,66 @@ class VarDTC(object):
         # frozen arrays (the model driver's X / Y) are recognised by identity, anything else by a full comparison
         if self._X is None or not (self._X.matches(X) and self._Y.matches(Y)):
             self._ctx.set_data(X, Y)
-            self._X, self._Y = ArrayIdentity(X), ArrayIdentity(Y)
+            self._X, self._Y, self._S = ArrayIdentity(X), ArrayIdentity(Y), None      # (set_data discards input variances)
+
+    def _inference_uncertain(self, kern, qX, Z, likelihood, Y, Y_metadata, mean_function, precision, Z_tilde):
+        """X is a `NormalPosterior`: the psi-statistics form of the same evaluation (reference `var_dtc.py:66-215` with
+        `uncertain_inputs`), for one RBF kernel alone or summed with White parts and ONE noise variance."""
+        if mean_function is not None:                                  # var_dtc.py:85-86
+            raise ValueError("Mean function not implemented with uncertain inputs or heteroscedasticity")
+        parts = kern.parts if isinstance(kern, Add) else [kern]
+        for p in parts:
+            if not isinstance(p, (RBF, White)) or type(p) not in (RBF, White):
+                raise NotImplementedError("uncertain inputs: the part %r (%s) has no psi-statistics on the MI355X sparse path; "
+                                          "one RBF kernel and White parts are covered" % (p.name, type(p).__name__))
+        rbfs = [p for p in parts if isinstance(p, RBF)]
+        if len(rbfs) != 1:
+            raise NotImplementedError("uncertain inputs: exactly one RBF part is covered, got %d (%s)"
+                                      % (len(rbfs), ", ".join(repr(p.name) for p in rbfs)))
+        Y = np.asarray(Y, dtype=np.float64)
+        if precision is None:
+            noise = np.atleast_1d(np.asarray(likelihood.gaussian_variance(Y_metadata), dtype=np.float64)).ravel()
+        else:
+            noise = 1.0 / np.atleast_1d(np.asarray(precision, dtype=np.float64)).ravel()
+        if noise.size > 1:                                             # var_dtc.py:243
+            raise NotImplementedError("heteroscedastic (per-point) noise is not implemented with uncertain inputs")
+        mu, S, Zs = kern._slice_X(qX.mean), kern._slice_X(qX.variance), kern._slice_X(Z)
+        R = _lib.f64(Y)
+        if self._ctx is not None and getattr(self._ctx, "sharded", False):
+            raise NotImplementedError("uncertain inputs are not supported by a row-sharded sparse context")
+        self._ensure(mu, R)
+        if self._S is None or not self._S.matches(S):
+            self._ctx.set_input_variance(S)
+            self._S = ArrayIdentity(S)
+        specs = kern.part_specs()
+        (r,), _ = jitter_ladder(lambda extra: self._ctx.vardtc_uncertain(specs, Zs, noise, extra_jitter=extra,
+                                                                         want_stage_ms=self.collect_stage_ms),
+                                kern.diag_variance(), self.maxtries)
+        self._token += 1
+        self.last_stage_ms = r.get("stage_ms")
+        M, N = Zs.shape[0], mu.shape[0]
+        lml = r["lml"] + (0.0 if Z_tilde is None else Z_tilde)
+        C = _lib.SparseContext
+        tok = (self._ctx, M, self._token, self)
+        post = SparsePosterior(woodbury_inv=_LazyMM(self._ctx, C.FETCH_WOODBURY_INV, *tok[1:]),
+                               woodbury_vector=r["woodbury_vector"],
+                               K=_LazyMM(self._ctx, C.FETCH_KMM, *tok[1:]), K_chol=_LazyMM(self._ctx, C.FETCH_LM, *tok[1:]),
+                               device={"ctx": self._ctx, "token": self._token, "owner": self, "sig": kernel_signature(kern)})
+        beta = float(1.0 / np.fmax(noise, self.const_jitter)[0])
+        grad_dict = {"dL_dKmm": _LazyMM(self._ctx, C.FETCH_DLDKMM, *tok[1:]),
+                     "dL_dpsi0": -0.5 * Y.shape[1] * beta * np.ones(N),             # var_dtc.py:218
+                     "dL_dpsi1": _LazyPsi1(beta, R, r["woodbury_vector"]),
+                     "dL_dpsi2": _LazyScaledMM(beta, self._ctx, C.FETCH_DLDPSI2_BETA, *tok[1:]),
+                     "dL_dthetaL": likelihood.exact_inference_gradients(r["dnoise"], Y_metadata),
+                     "fused": {"dtheta": r["dtheta"], "dZ": r["dZ"], "dmu": r["dmu"], "dS": r["dS"]}}
+        return post, lml, grad_dict
 
     def inference(self, kern, X, Z, likelihood, Y, Y_metadata=None, mean_function=None, precision=None, Lm=None,
                   dL_dKmm=None, psi0=None, psi1=None, psi2=None, Z_tilde=None):
+        if isinstance(X, NormalPosterior):
+            if any(a is not None for a in (Lm, dL_dKmm, psi0, psi1, psi2)):
+                raise NotImplementedError("precomputed statistics are not accepted by the MI355X sparse path")
+            return self._inference_uncertain(kern, X, Z, likelihood, Y, Y_metadata, mean_function, precision, Z_tilde)
         new_kinds = exact_only_leaves(kern)
         if new_kinds:
             raise NotImplementedError("the MI355X sparse path does not evaluate %s kernels (the exact GPRegression path does)"
@@ -244,10 +341,18 @@ class SparseGP(PredictionCallers, Parameterized):
     (`sparse_gp.py:59`: Z is linked at index 0)."""
 
     def __init__(self, X, Y, Z, kernel, likelihood, inference_method=None, name="sparse gp", device=0, mean_function=None,
-                 Y_metadata=None):
+                 Y_metadata=None, X_variance=None):
         super(SparseGP, self).__init__(name)
         self.mean_function, self.Y_metadata = mean_function, Y_metadata
-        self.X, self.Y = freeze(X), freeze(Y)        # private read-only copies (cf. `ObsAr`, reference `core/gp.py:44-60`)
+        self.Y = freeze(Y)                           # private read-only copies (cf. `ObsAr`, reference `core/gp.py:44-60`)
+        if isinstance(X, NormalPosterior):           # (reference `core/sparse_gp.py:45-51`)
+            self.X = X.copy()
+        elif X_variance is not None:                 # data, not a parameter: the flat parameter order is unchanged
+            self.X = NormalPosterior(X, X_variance)
+        else:
+            self.X = freeze(X)
+        if self.has_uncertain_inputs() and mean_function is not None:
+            raise ValueError("Mean function not implemented with uncertain inputs or heteroscedasticity")
         self.Y_normalized = self.Y
         self.num_data, self.input_dim = self.X.shape
         self.output_dim = self.Y.shape[1]
@@ -261,7 +366,13 @@ class SparseGP(PredictionCallers, Parameterized):
         self.posterior = None
         self.parameters_changed()
 
+    def has_uncertain_inputs(self):
+        """(reference `core/sparse_gp.py:68-69`)"""
+        return isinstance(self.X, NormalPosterior)
+
     def parameters_changed(self):
+        # certain and uncertain inputs alike: the kernel and inducing-input gradients of `_update_gradients` (reference
+        # `core/sparse_gp.py:88-118`, both branches) were reduced on the device and arrive in grad_dict['fused']
         self.posterior, self._log_marginal_likelihood, self.grad_dict = self.inference_method.inference(
             self.kern, self.X, self.Z.values, self.likelihood, self.Y_normalized, Y_metadata=self.Y_metadata,
             mean_function=self.mean_function)
@@ -293,6 +404,8 @@ class SparseGP(PredictionCallers, Parameterized):
 
     def _raw_predict(self, Xnew, full_cov=False, kern=None):
         """(reference `core/sparse_gp.py:121-160` -> `posterior.py:198-262`; same signature as `GP._raw_predict`)"""
+        if isinstance(Xnew, NormalPosterior):
+            raise NotImplementedError("prediction at uncertain new points is not implemented; pass their means")
         mu, var = self.posterior._raw_predict(self.kern if kern is None else kern, np.asarray(Xnew), self.Z.values,
                                               full_cov=full_cov)
         if self.mean_function is not None:
@@ -335,7 +448,8 @@ class SparseGP(PredictionCallers, Parameterized):
 class SparseGPRegression(SparseGP):
     """(reference `GPy/models/sparse_gp_regression.py:20-60`): Z defaults to a random subset of X."""
 
-    def __init__(self, X, Y, kernel=None, Z=None, num_inducing=10, noise_var=1., device=0, seed=None, mean_function=None):
+    def __init__(self, X, Y, kernel=None, Z=None, num_inducing=10, noise_var=1., device=0, seed=None, mean_function=None,
+                 X_variance=None):
         X = np.asarray(X, dtype=np.float64)
         if kernel is None:
             kernel = RBF(X.shape[1], device=device)
@@ -343,4 +457,5 @@ class SparseGPRegression(SparseGP):
             i = np.random.default_rng(seed).permutation(X.shape[0])[:min(num_inducing, X.shape[0])]
             Z = X[i].copy()
         super(SparseGPRegression, self).__init__(X, Y, Z, kernel, Gaussian(variance=noise_var),
-                                                 name="sparse_gp", device=device, mean_function=mean_function)
+                                                 name="sparse_gp", device=device, mean_function=mean_function,
+                                                 X_variance=X_variance)

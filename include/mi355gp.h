@@ -413,6 +413,20 @@ int mi355gp_vardtc_inference_sum(mi355gp_sparse* s, int nparts, const mi355gp_pa
                                  const double* noise, int64_t noise_len, double extra_jitter, double* out_scalars,
                                  double* dtheta_out, double* dZ_out, double* wv_out, double* dnoise_rows_out,
                                  double* dLdm_out, double* stage_ms);
+/* Uncertain inputs q(x_n) = N(X_n, diag S_n) (SparseGPRegression(X, Y, X_variance=S), var_dtc.py with psi statistics,
+ * kern/src/psi_comp/rbf_psi_comp.py).  S: N x D, the shape of set_data's X (then read as the means); every entry positive and
+ * finite, checked on the host before any launch.  set_data discards S. */
+int mi355gp_sparse_set_input_variance(mi355gp_sparse* s, const double* S, int64_t N, int D);
+/* One evaluation with uncertain inputs: one RBF part (iso or ARD, any active_dims) alone or summed with White parts; ONE
+ * noise variance (noise_len == 1).  Anything else -- a Bias part, a second RBF, a product, per-point noise, a row-sharded
+ * context, no input variances -- is refused with an error that names it.  out_scalars, dtheta_out, dZ_out, wv_out, stage_ms
+ * as mi355gp_vardtc_inference_sum; dmu_out / dS_out (optional, N x D): gradients with respect to the inputs' means and
+ * variances.  The context ends in the state of a certain-input call: mi355gp_sparse_predict and mi355gp_sparse_fetch work
+ * (mi355gp_sparse_fetch_dLdKnm does not: dL_dpsi1 / dL_dpsi2 take dL_dKnm's place).  Two calls give the same bits. */
+int mi355gp_vardtc_inference_uncertain(mi355gp_sparse* s, int nparts, const mi355gp_part* parts, const double* Z, int64_t M,
+                                       const double* noise, int64_t noise_len, double extra_jitter, double* out_scalars,
+                                       double* dtheta_out, double* dZ_out, double* wv_out, double* dmu_out, double* dS_out,
+                                       double* stage_ms);
 /* Sparse posterior prediction on the device (Posterior._raw_predict, inference/latent_function_inference/posterior.py:198-262,
  * for the (woodbury_inv, woodbury_vector) posterior of var_dtc.py:213): mu (Mn x Dy) = K(X*, Z) woodbury_vector;
  * full_cov == 0: var (Mn) = Kdiag - sum(Kx * (woodbury_inv Kx), 0), clipped at 1e-15 (posterior.py:248); else Mn x Mn.
@@ -430,12 +444,29 @@ int mi355gp_sparse_attach_comm(mi355gp_sparse* s, int rank, int world, const voi
 /* The same mode over the LOOPBACK transport: `world` contexts of ONE process (one host thread each) that name the same
  * group_key rendezvous for every exchange step and are summed in rank order -- world > 1 on a single GPU (tests). */
 int mi355gp_sparse_attach_loopback(mi355gp_sparse* s, int rank, int world, int group_key);
-/* M x M results of the last call: 0 dL_dKmm, 1 woodbury_inv (var_dtc.py:206-210), 2 Lm, 3 Kmm (+1e-8 I), 4 psi2 */
+/* M x M results of the last call: 0 dL_dKmm, 1 woodbury_inv (var_dtc.py:206-210), 2 Lm, 3 Kmm (+1e-8 I), 4 psi2,
+ * 5 dL_dpsi2_beta (var_dtc.py:220) */
 int mi355gp_sparse_fetch(mi355gp_sparse* s, int which, double* out);
 /* Launch timing of the two MFMA kernels of the last mi355gp_vardtc_inference_sum call (hipEvent pairs on the launching
  * stream, recorded on every call): out6 = [T = Kfu dL_dpsi2 GEMM: summed ms, algorithmic flops (2 rows M^2), launches,
  * split-K Gram psi2: summed ms, algorithmic flops (rows M^2, lower half), launches]. */
 int mi355gp_sparse_get_profile(mi355gp_sparse* s, double* out6);
+
+/* ---- psi-statistics of the RBF kernel for Gaussian inputs q(x_n) = N(mu_n, diag S_n) (kern/src/psi_comp/rbf_psi_comp.py) ----
+ * Stateless, like mi355gp_kern_K.  lengthscale: D entries if ard, else one.  Z: M x D, mu / S: N x D row-major; every S
+ * entry must be positive and finite (checked on the host before any launch); D <= 64.
+ * psi1_out (N x M) and psi2_out (M x M, = sum_n w_n psi2n; weights NULL: w_n = 1) may each be NULL.  The sum over n is
+ * combined in a fixed order: two calls give the same bits. */
+int mi355gp_rbf_psi(int device, double variance, const double* lengthscale, int ard, const double* Z, int64_t M,
+                    const double* mu, const double* S, int64_t N, int D, const double* weights, double* psi1_out,
+                    double* psi2_out);
+/* The five outputs of psiDerivativecomputations (rbf_psi_comp.py:70-133) from dL_dpsi0 (N), dL_dpsi1 (N x M) and dL_dpsi2
+ * (M x M, symmetrised inside), each of which may be NULL: dvar_out (1), dl_out (D if ard, else 1), dZ_out (M x D),
+ * dmu_out and dS_out (N x D).  psi2n is recomputed tile by tile; no N x M x M array exists. */
+int mi355gp_rbf_psi_grad(int device, double variance, const double* lengthscale, int ard, const double* Z, int64_t M,
+                         const double* mu, const double* S, int64_t N, int D, const double* weights, const double* dL_dpsi0,
+                         const double* dL_dpsi1, const double* dL_dpsi2, double* dvar_out, double* dl_out, double* dZ_out,
+                         double* dmu_out, double* dS_out);
 
 #ifdef __cplusplus
 }
