@@ -293,7 +293,7 @@ static int run_pipeline(mi355gp_ctx* c, EngineShared* gate, bool with_kernel_gra
                 launch_reduce_partials(st, c->dCoregPart, nbc, P * P, c->dPack + c->offCoreg + p * COREG_REC);
                 continue;
             }
-            launch_grad_fused(st, pt.kp, pt.dXt, np, n, c->C, np, c->dAlpha, c->Dy, c->dGradPart, GP_STRIDE,
+            launch_grad_fused(st, pt.kp, pt.dXt, np, n, c->C, np, c->dAlpha, c->Dy, c->dGradPart,
                               studentt_nu > 0.0 ? c->dScal + 4 : nullptr, Mul, np);
             for (int g = 0; g < (pt.kp.ard ? groups : 1); ++g)
                 launch_reduce_partials(st, c->dGradPart + (long)g * nb * GP_STRIDE, nb, GP_STRIDE,
@@ -739,7 +739,7 @@ int mi355gp_update_gradients_full(int device, int kind, int ard, const double* t
         launch_reduce_partials(0, dPart, nb, ard * ard, dOut);
     } else {
         const int nb = grad_generic_num_blocks(N, M);
-        launch_grad_generic(0, pt.kp, x1.t, x1.ld, N, y.t, y.ld, M, sym ? 1 : 0, dG, M, dPart, GP_STRIDE);
+        launch_grad_generic(0, pt.kp, x1.t, x1.ld, N, y.t, y.ld, M, sym ? 1 : 0, dG, M, dPart);
         for (int r = 0; r < nrec; ++r)
             for (int g = 0; g < (pt.kp.ard ? groups : 1); ++g)
                 launch_reduce_partials(0, dPart + ((long)r * groups + g) * nb * GP_STRIDE, nb, GP_STRIDE,
@@ -809,7 +809,7 @@ int mi355gp_gradients_X(int device, int kind, int ard, const double* theta, cons
         gradx_linear(pt.inv_ls, N, D, HX.data(), [&](long i, int q, double g) { out[i * D + q] = g; });
         return 0;
     }
-    launch_grad_generic(0, pt.kp, xr.t, xr.ld, M, xc.t, xc.ld, N, 0, dG, N, dPart, GP_STRIDE, dG, N);   // H in place
+    launch_grad_generic(0, pt.kp, xr.t, xr.ld, M, xc.t, xc.ld, N, 0, dG, N, dPart, dG, N);   // H in place
     const int ns = launch_colreduce_multi(0, dG, N, M, N, xr.t, 1, xr.ld, D, 1, dCol);
     launch_sum_splits(0, dCol, N * (D + 1), ns, 0, dHX);
     std::vector<double> HX((size_t)N * (D + 1));
@@ -1067,7 +1067,7 @@ int mi355gp_predictive_gradients_sum(mi355gp_ctx* c, int nparts, const mi355gp_p
                 gradx_periodic(pt.pw, M, (int)D, HX.data(), add);
                 continue;
             }
-            launch_grad_generic(st, pt.kp, pt.dXt, np, n, xt, xs.ld, M, 0, W, mp, dPart, GP_STRIDE, dH, mp);
+            launch_grad_generic(st, pt.kp, pt.dXt, np, n, xt, xs.ld, M, 0, W, mp, dPart, dH, mp);
             const int ns = launch_colreduce_multi(st, dH, mp, n, M, pt.dXt, 1, np, (int)D, 1, dCol);
             launch_sum_splits(st, dCol, (long)hx, ns, 0, dHX);
             HIP_CHECK(hipMemcpyAsync(HX.data(), dHX, sizeof(double) * hx, hipMemcpyDeviceToHost, st));

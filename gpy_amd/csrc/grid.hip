@@ -1510,7 +1510,7 @@ static int grid_run(mi355gp_grid* g, const PartSpec& pt, const double* noise, in
                            r.W, r.LC, r.nvr, r.nvc, r.gR, r.gC, r.alpha, Dy, n);
         const int nbk = grad_generic_num_blocks(r.nvr, r.nvc);
         nblocks[ri] = nbk;
-        launch_grad_generic(r.st, kp, r.XtR, r.LR, r.nvr, r.XtC, r.LC, r.nvc, 0, r.W, r.LC, r.gradPart, GP_STRIDE);
+        launch_grad_generic(r.st, kp, r.XtR, r.LR, r.nvr, r.XtC, r.LC, r.nvc, 0, r.W, r.LC, r.gradPart);
         for (int gi = 0; gi < (kp.ard ? groups : 1); ++gi)
             launch_reduce_partials(r.st, r.gradPart + (long)gi * nbk * GP_STRIDE, nbk, GP_STRIDE,
                                    r.gradOut + (long)gi * GP_STRIDE);

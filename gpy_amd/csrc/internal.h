@@ -211,6 +211,7 @@ int persist_early_h(long npad, const FactorWs* ws);
 void launch_wait_persist_rows(hipStream_t st, const FactorWs* ws, int r0, int r1, int cols, int give_up = 0);
 
 // ---- kern.hip : covariance assembly, reductions, solves, fetch helpers ----------------------------
+#define GP_STRIDE 34           // doubles of one reduction record: [0] variance sum, [1] lengthscale sum, [2 + q % 32] per dimension
 struct KernParams {
     int kind;
     int ard;
@@ -254,7 +255,7 @@ int grad_num_blocks(long n);
 // partials + groups * nblocks * GP_STRIDE, groups = ceil(D / 32): partial buffers of these kinds are twice as long.
 // aa_scale (optional, device): factor on the alpha alpha^T term of dL_dK (Student-t process)
 void launch_grad_fused(hipStream_t st, KernParams kp, const double* Xt, long ldx, long n, const double* W,
-                       long ldw, const double* alpha, int Dy, double* partials, int stride,
+                       long ldw, const double* alpha, int Dy, double* partials,
                        const double* aa_scale = nullptr, const double* Mul = nullptr, long ldm = 0);
 // optional on-the-fly form of the weight matrix read by launch_grad_generic:
 //   g = rowscale[i] * (gscale * G + beta * sum_d Y[i][d] V[j][d])        (rowscale == NULL: 1)
@@ -273,7 +274,7 @@ void launch_studentt_scale(hipStream_t st, const double* scal, double nu, long n
 // Hout (optional, may alias G): H = dL_dK * (dK/dr)/r, the weights of the gradients_X reductions
 void launch_grad_generic(hipStream_t st, KernParams kp, const double* Xt1, long ld1, long n, const double* Xt2,
                          long ld2, long m, int symmetric, const double* G, long ldg, double* partials,
-                         int stride, double* Hout = nullptr, long ldh = 0,
+                         double* Hout = nullptr, long ldh = 0,
                          RankTerm rk = RankTerm{nullptr, nullptr, 0, 0.0, 1.0, nullptr});
 // StdPeriodic dK/dx (standard_periodic.py:574-580) as a row reduction over a group of 32 dimensions from q_off:
 //   out[i][q] = sum_j W(i, j) K(x1_i, x2_j) sin(2 Delta_ijq),  W(i, j) = W[i * ldw + j], or W[j * ldw + i] if wt

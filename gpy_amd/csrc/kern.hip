@@ -143,6 +143,92 @@ __device__ __forceinline__ void accum_r2(const double* si, const double* sj, int
 // ------------------------------------------------------------------------------------------------
 // Covariance assembly.  SYM: Ky = K + diag(noise + jit) into the padded npad x npad buffer (identity in the
 // padding), optionally lower 64-tiles only.  !SYM: rectangular K(X1, X2) into a dense n x m buffer.
+// Every kind has a kernel of its own (k_kbuild below for the stationary and static kinds, the others in their sections
+// further down) that holds only what is the kind's: what it stages, what it accumulates over the staged slabs, how an
+// element follows from the sums.  The rest is one skeleton of inlined helpers: kbuild_tile, stage_chunk, kbuild_pad
+// and kbuild_store_row.  Inlining keeps every instantiation's code to what its kind needs.
+struct KbuildArgs {
+    KernParams kp;
+    const double* Xt1;                 // row side: dimension-major inputs [D][ld1], n points
+    long ld1, n;
+    const double* Xt2;                 // column side, m points
+    long ld2, m;
+    double* out;
+    long ldo, nrows_out;
+    const double* noise;
+    long noise_len;
+    double jit;
+    int lower_only, add_diag, ntc, accumulate;
+    int diag_same;                     // the stationary kernel only (White): a rectangular evaluation of coinciding points
+    const double* mul;                 // (may alias out): element-wise multiplier with out's layout -- product kernels
+                                       // (GPy/kern/src/prod.py:58-65)
+};
+
+// The origin of this block's tile; false: nothing to do (an upper tile of a lower_only build)
+template <bool SYM>
+__device__ __forceinline__ bool kbuild_tile(const KbuildArgs& A, long& i0, long& j0) {
+    const long ti = blockIdx.x / A.ntc, tj = blockIdx.x % A.ntc;
+    i0 = ti * KT;
+    j0 = tj * KT;
+    return !(SYM && A.lower_only && tj > ti);
+}
+
+__device__ __forceinline__ void zero_tile(double (&s)[4][4]) {
+#pragma unroll
+    for (int a = 0; a < 4; ++a)
+#pragma unroll
+        for (int b = 0; b < 4; ++b) s[a][b] = 0.0;
+}
+
+// Chunk q0 of the dimensions: both slabs of the tile at (i0, j0) go to LDS between two barriers.  Returns the number of
+// dimensions staged; the kind's accumulate step over them follows.
+__device__ __forceinline__ int stage_chunk(int D, int q0, const double* __restrict__ Xt1, long ld1, long i0,
+                                           const double* __restrict__ Xt2, long ld2, long j0, double* si, double* sj, int t) {
+    const int qc = (D - q0 < KDC) ? (D - q0) : KDC;
+    __syncthreads();
+    stage_x(Xt1, ld1, i0, q0, qc, si, t);
+    stage_xj(Xt2, ld2, j0, q0, qc, sj, t);
+    __syncthreads();
+    return qc;
+}
+
+// what an element outside n x m holds: the identity in the padding of a fresh symmetric build, nothing otherwise
+template <bool SYM>
+__device__ __forceinline__ double kbuild_pad(const KbuildArgs& A, long i, long j) {
+    return (SYM && i == j && !A.accumulate) ? 1.0 : 0.0;
+}
+
+// Row i of a thread's 4 x 4 elements, v[b] = element (i, j0 + tx * 4 + b), goes out: times mul, plus noise + jitter on the
+// diagonal, plus what is there (accumulate); one 32-byte store into the padded symmetric buffer, scalar stores otherwise.
+template <bool SYM>
+__device__ __forceinline__ void kbuild_store_row(const KbuildArgs& A, long i, long j0, int tx, const double (&v)[4]) {
+    if (SYM) {
+        if (i < A.nrows_out) {
+            d4* p = reinterpret_cast<d4*>(A.out + i * A.ldo + j0 + tx * 4);
+            d4 o = (d4){v[0], v[1], v[2], v[3]};
+            if (A.mul) o *= *reinterpret_cast<const d4*>(A.mul + i * A.ldo + j0 + tx * 4);
+            if (A.add_diag && i < A.n) {                      // noise + jitter enter once, outside any product
+                const long d = i - (j0 + tx * 4);
+                if (d >= 0 && d < 4) o[d] += A.noise[A.noise_len > 1 ? i : 0] + A.jit;
+            }
+            if (A.accumulate) o += *p;                       // sum kernels (GPy/kern/src/add.py:58-72): K += K_part
+            *p = o;
+        }
+    } else if (i < A.n) {
+#pragma unroll
+        for (int b = 0; b < 4; ++b) {
+            const long j = j0 + tx * 4 + b;
+            if (j < A.m) {
+                const double w = A.mul ? v[b] * A.mul[i * A.ldo + j] : v[b];
+                A.out[i * A.ldo + j] = A.accumulate ? A.out[i * A.ldo + j] + w : w;
+            }
+        }
+    }
+}
+
+// The stationary kinds and the static ones.  White puts its variance on coinciding points: the diagonal of a symmetric
+// build, and of a rectangular one that says so (diag_same).  The one kernel that takes KbuildArgs' fields as parameters of
+// its own: `__restrict__` on them is worth a wait less in the epilogue of the kernel that the benchmark times.
 template <bool SYM>
 __global__ __launch_bounds__(256) void k_kbuild(KernParams kp, const double* __restrict__ Xt1, long ld1, long n,
                                                 const double* __restrict__ Xt2, long ld2, long m,
@@ -150,29 +236,18 @@ __global__ __launch_bounds__(256) void k_kbuild(KernParams kp, const double* __r
                                                 const double* __restrict__ noise, long noise_len, double jit,
                                                 int lower_only, int add_diag, int ntc, int accumulate, int diag_same,
                                                 const double* mul) {
-    // mul (may alias out): element-wise multiplier with out's layout -- product kernels (GPy/kern/src/prod.py:58-65)
+    const KbuildArgs A{kp,    Xt1,        ld1,      n,   Xt2,        ld2,       m,  out, ldo, nrows_out, noise, noise_len,
+                       jit,   lower_only, add_diag, ntc, accumulate, diag_same, mul};
     __shared__ __attribute__((aligned(16))) double si[KDC * KT];
     __shared__ __attribute__((aligned(16))) double sj[KDC * KTJ];
     const int t = threadIdx.x, tx = t & 15, ty = t >> 4;
-    const long ti = blockIdx.x / ntc, tj = blockIdx.x % ntc;
-    if (SYM && lower_only && tj > ti) return;
-    const long i0 = ti * KT, j0 = tj * KT;
+    long i0, j0;
+    if (!kbuild_tile<SYM>(A, i0, j0)) return;
     double r2[4][4];
-#pragma unroll
-    for (int a = 0; a < 4; ++a)
-#pragma unroll
-        for (int b = 0; b < 4; ++b) r2[a][b] = 0.0;
-    const bool real_tile = (i0 < n) && (j0 < m);
-    if (real_tile) {
-        for (int q0 = 0; q0 < kp.D; q0 += KDC) {
-            const int qc = (kp.D - q0 < KDC) ? (kp.D - q0) : KDC;
-            __syncthreads();
-            stage_x(Xt1, ld1, i0, q0, qc, si, t);
-            stage_xj(Xt2, ld2, j0, q0, qc, sj, t);
-            __syncthreads();
-            accum_r2(si, sj, qc, ty, tx, r2);
-        }
-    }
+    zero_tile(r2);
+    if (i0 < A.n && j0 < A.m)
+        for (int q0 = 0; q0 < A.kp.D; q0 += KDC)
+            accum_r2(si, sj, stage_chunk(A.kp.D, q0, A.Xt1, A.ld1, i0, A.Xt2, A.ld2, j0, si, sj, t), ty, tx, r2);
 #pragma unroll
     for (int a = 0; a < 4; ++a) {
         const long i = i0 + ty * 4 + a;
@@ -180,31 +255,10 @@ __global__ __launch_bounds__(256) void k_kbuild(KernParams kp, const double* __r
 #pragma unroll
         for (int b = 0; b < 4; ++b) {
             const long j = j0 + tx * 4 + b;
-            if (i < n && j < m) v[b] = cov_k(kp.kind, kp.variance, r2[a][b], (SYM || diag_same) && i == j);
-            else v[b] = (SYM && i == j && !accumulate) ? 1.0 : 0.0;
+            if (i < A.n && j < A.m) v[b] = cov_k(A.kp.kind, A.kp.variance, r2[a][b], (SYM || A.diag_same) && i == j);
+            else v[b] = kbuild_pad<SYM>(A, i, j);
         }
-        if (SYM) {
-            if (i < nrows_out) {
-                d4* p = reinterpret_cast<d4*>(out + i * ldo + j0 + tx * 4);
-                d4 o = (d4){v[0], v[1], v[2], v[3]};
-                if (mul) o *= *reinterpret_cast<const d4*>(mul + i * ldo + j0 + tx * 4);
-                if (add_diag && i < n) {                        // noise + jitter enter once, outside any product
-                    const long d = i - (j0 + tx * 4);
-                    if (d >= 0 && d < 4) o[d] += noise[noise_len > 1 ? i : 0] + jit;
-                }
-                if (accumulate) o += *p;                       // sum kernels (GPy/kern/src/add.py:58-72): K += K_part
-                *p = o;
-            }
-        } else if (i < n) {
-#pragma unroll
-            for (int b = 0; b < 4; ++b) {
-                const long j = j0 + tx * 4 + b;
-                if (j < m) {
-                    const double w = mul ? v[b] * mul[i * ldo + j] : v[b];
-                    out[i * ldo + j] = accumulate ? out[i * ldo + j] + w : w;
-                }
-            }
-        }
+        kbuild_store_row<SYM>(A, i, j0, tx, v);
     }
 }
 
@@ -312,98 +366,99 @@ int launch_kbuild_cols(hipStream_t st, KernParams kp, const double* Xt1, long ld
     return nsplit;
 }
 
-// RatQuad / StdPeriodic (kinds 6 / 7): kernels of their own at the end of this file; the launchers below hand them over
-static void launch_kbuild_ext(hipStream_t st, bool sym, KernParams kp, const double* Xt1, long ld1, long n, const double* Xt2,
-                              long ld2, long m, double* out, long ldo, long nrows_out, const double* noise, long noise_len,
-                              double jit, int lower_only, int add_diag, int ntc, int nblocks, int accumulate, int diag_same,
-                              const double* mul);
-static void launch_grad_ext(hipStream_t st, bool fused, KernParams kp, const double* Xt1, long ld1, long n, const double* Xt2,
-                            long ld2, long m, const double* G, long ldg, const double* alpha, int Dy, long ntiles, int ntc,
-                            double* partials, double* Hout, long ldh, const double* aa_scale, const double* Mul, long ldm);
-// Coregionalize (kind 8): at the end of this file as well
-static void launch_kbuild_coreg(hipStream_t st, bool sym, KernParams kp, const double* Xt1, long ld1, long n, const double* Xt2,
-                                long ld2, long m, double* out, long ldo, long nrows_out, const double* noise, long noise_len,
-                                double jit, int lower_only, int add_diag, int ntc, int nblocks, int accumulate, const double* mul);
-
-// Linear (kind 9): at the end of this file as well
-static void launch_kbuild_lin(hipStream_t st, bool sym, KernParams kp, const double* Xt1, long ld1, long n, const double* Xt2,
-                              long ld2, long m, double* out, long ldo, long nrows_out, const double* noise, long noise_len,
-                              double jit, int lower_only, int add_diag, int ntc, int nblocks, int accumulate, const double* mul);
-static void launch_grad_lin(hipStream_t st, bool fused, KernParams kp, const double* Xt1, long ld1, long n, const double* Xt2,
-                            long ld2, long m, const double* G, long ldg, const double* alpha, int Dy, long ntiles, int ntc,
-                            double* partials, double* Hout, long ldh, const double* aa_scale, const double* Mul, long ldm);
-
-// MLP / Poly (kinds 10 / 11): at the end of this file as well
-static inline bool dot_kind(int kind) { return kind == MI355GP_MLP || kind == MI355GP_POLY; }
-static void launch_kbuild_dot(hipStream_t st, bool sym, KernParams kp, const double* Xt1, long ld1, long n, const double* Xt2,
-                              long ld2, long m, double* out, long ldo, long nrows_out, const double* noise, long noise_len,
-                              double jit, int lower_only, int add_diag, int ntc, int nblocks, int accumulate, const double* mul);
-static void launch_grad_dot(hipStream_t st, bool fused, KernParams kp, const double* Xt1, long ld1, long n, const double* Xt2,
-                            long ld2, long m, const double* G, long ldg, const double* alpha, int Dy, long ntiles, int ntc,
-                            double* partials, double* Hout, long ldh, const double* aa_scale, const double* Mul, long ldm);
-
-void launch_kbuild_sym(hipStream_t st, KernParams kp, const double* Xt, long ldx, long n, long npad, double* A,
-                       const double* noise, long noise_len, double jit, int lower_only, int add_diag, int accumulate,
-                       const double* mul) {
-    const int nt = (int)(npad / KT);
-    if (dot_kind(kp.kind)) {
-        launch_kbuild_dot(st, true, kp, Xt, ldx, n, Xt, ldx, n, A, npad, npad, noise, noise_len, jit, lower_only, add_diag, nt,
-                          nt * nt, accumulate, mul);
-        return;
-    }
-    if (kp.kind == MI355GP_LINEAR) {
-        launch_kbuild_lin(st, true, kp, Xt, ldx, n, Xt, ldx, n, A, npad, npad, noise, noise_len, jit, lower_only, add_diag, nt,
-                          nt * nt, accumulate, mul);
-        return;
-    }
-    if (kp.kind == MI355GP_COREGIONALIZE) {
-        launch_kbuild_coreg(st, true, kp, Xt, ldx, n, Xt, ldx, n, A, npad, npad, noise, noise_len, jit, lower_only, add_diag, nt,
-                            nt * nt, accumulate, mul);
-        return;
-    }
-    if (kp.kind >= MI355GP_RATQUAD) {
-        launch_kbuild_ext(st, true, kp, Xt, ldx, n, Xt, ldx, n, A, npad, npad, noise, noise_len, jit, lower_only, add_diag, nt,
-                          nt * nt, accumulate, 0, mul);
-        return;
-    }
-    hipLaunchKernelGGL((k_kbuild<true>), dim3((unsigned)((long)nt * nt)), dim3(256), 0, st, kp, Xt, ldx, n, Xt, ldx, n,
-                       A, npad, npad, noise, noise_len, jit, lower_only, add_diag, nt, accumulate, 0, mul);
-}
-
-void launch_kbuild_cross(hipStream_t st, KernParams kp, const double* Xt1, long ld1, long n, const double* Xt2,
-                         long ld2, long m, double* Kout, long ldk, int accumulate, int diag_same, const double* mul) {
-    const int ntr = (int)((n + KT - 1) / KT), ntc = (int)((m + KT - 1) / KT);
-    if (dot_kind(kp.kind)) {                                               // (the diagonal is what the formula gives at i == j)
-        launch_kbuild_dot(st, false, kp, Xt1, ld1, n, Xt2, ld2, m, Kout, ldk, n, nullptr, 0, 0.0, 0, 0, ntc, ntr * ntc, accumulate,
-                          mul);
-        return;
-    }
-    if (kp.kind == MI355GP_LINEAR) {                                       // (the diagonal is whatever the dot product gives)
-        launch_kbuild_lin(st, false, kp, Xt1, ld1, n, Xt2, ld2, m, Kout, ldk, n, nullptr, 0, 0.0, 0, 0, ntc, ntr * ntc, accumulate,
-                          mul);
-        return;
-    }
-    if (kp.kind == MI355GP_COREGIONALIZE) {                                // (no White-like diagonal: diag_same changes nothing)
-        launch_kbuild_coreg(st, false, kp, Xt1, ld1, n, Xt2, ld2, m, Kout, ldk, n, nullptr, 0, 0.0, 0, 0, ntc, ntr * ntc, accumulate,
-                            mul);
-        return;
-    }
-    if (kp.kind >= MI355GP_RATQUAD) {
-        launch_kbuild_ext(st, false, kp, Xt1, ld1, n, Xt2, ld2, m, Kout, ldk, n, nullptr, 0, 0.0, 0, 0, ntc, ntr * ntc,
-                          accumulate, diag_same, mul);
-        return;
-    }
-    hipLaunchKernelGGL((k_kbuild<false>), dim3((unsigned)((long)ntr * ntc)), dim3(256), 0, st, kp, Xt1, ld1, n, Xt2,
-                       ld2, m, Kout, ldk, n, nullptr, 0, 0.0, 0, 0, ntc, accumulate, diag_same, mul);
-}
-
 // ------------------------------------------------------------------------------------------------
 // Gradient reduction.  For every (i, j): g = weight * dL_dK[i][j];
 //   acc_var += g*K ; acc_iso += g*(dK/dr*r) ; acc_q += g*(dK/dr / r)*(x~_iq - x~_jq)^2   (x~ = x / l)
 // FUSED: dL_dK = 0.5*(alpha_i . alpha_j - Dy*W_ij) from the lower triangle of W (off-diagonal weight 2).
 // else : dL_dK read from G (n x m).
 // Per-block partials [2 + 32]: [0] var, [1] iso, [2+q] lengthscale dims q_off..q_off+31.
-#define GP_STRIDE 34
+// As for the assembly, every kind has a kernel of its own (k_grad below, the others in their sections) around shared inlined
+// pieces: grad_tile, stage_chunk / restage, grad_weight, store_h and block_sum.
+
+// Tile `tile` of a pass: FUSED walks the lower triangle row by row, else every tile of ntc tile columns
+template <bool FUSED>
+__device__ __forceinline__ void grad_tile(long tile, int ntc, long& ti, long& tj) {
+    if (FUSED) {   // lower-triangular enumeration
+        ti = (long)((sqrt(8.0 * (double)tile + 1.0) - 1.0) * 0.5);
+        while (ti * (ti + 1) / 2 > tile) --ti;
+        while ((ti + 1) * (ti + 2) / 2 <= tile) ++ti;
+        tj = tile - ti * (ti + 1) / 2;
+    } else {
+        ti = tile / ntc;
+        tj = tile - ti * ntc;
+    }
+}
+
+// D > 32: bring the qcnt dimensions from q_off, the ones this launch reduces, back into LDS unless they are what is there
+__device__ __forceinline__ void restage(int last_q0, int q_off, int qcnt, const double* __restrict__ Xt1, long ld1, long i0,
+                                        const double* __restrict__ Xt2, long ld2, long j0, double* si, double* sj, int t) {
+    if (last_q0 != q_off) {
+        __syncthreads();
+        stage_x(Xt1, ld1, i0, q_off, qcnt, si, t);
+        stage_xj(Xt2, ld2, j0, q_off, qcnt, sj, t);
+        __syncthreads();
+    }
+}
+
+// The weight dL_dK of element (i, j), 0 outside n x m.
+//   FUSED: 0.5 (sc * alpha_i . alpha_j - Dy * W_ij) from the lower triangle of W = Ky^-1 (G), j <= i only; sc = 1 for the Gaussian
+//          process, (nu+N)/(nu+beta-2) for the Student-t process (exact_studentt_inference.py:46).  With TWICE an element below
+//          the diagonal counts for its mirror image as well.
+//   else : G[i][j].
+//   Mul  : factor of a product kernel -- dL_dK times the other factors' covariances (prod.py:86-99).  !TWICE (Coregionalize, which
+//          completes symmetrically on its own) takes it on the elements j <= i of the fused form alone.
+template <bool FUSED, bool TWICE>
+__device__ __forceinline__ double grad_weight(long i, long j, long n, long m, const double* __restrict__ G, long ldg,
+                                              const double* __restrict__ alpha, int Dy, double sc,
+                                              const double* __restrict__ Mul, long ldm) {
+    double g = 0.0;
+    if (i < n && j < m) {
+        if (FUSED) {
+            if (j <= i) {
+                double aa = 0.0;
+                for (int d = 0; d < Dy; ++d) aa = fma(alpha[i * Dy + d], alpha[j * Dy + d], aa);
+                g = 0.5 * (sc * aa - (double)Dy * G[i * ldg + j]);
+                if (TWICE) {
+                    if (j < i) g *= 2.0;
+                } else if (Mul) {
+                    g *= Mul[i * ldm + j];
+                }
+            }
+        } else {
+            g = G[i * ldg + j];
+        }
+        if (TWICE && Mul) g *= Mul[i * ldm + j];
+    }
+    return g;
+}
+
+// A weight of the gradients_X reductions goes out: Hout[i][j] = h inside n x m.  MASKED: 0 where key == 0 -- for
+// H = dL_dK * (dK/dr)/r (stationary.py:330-346) and key = r^2 that is `_inv_dist` (:225-232): a coincident pair gives
+// exactly nothing, not x H - H x to rounding.
+template <bool MASKED>
+__device__ __forceinline__ void store_h(double* __restrict__ Hout, long ldh, long i, long j, long n, long m, double key, double h) {
+    if (i < n && j < m) Hout[i * ldh + j] = (MASKED && key == 0.0) ? 0.0 : h;
+}
+
+// 256 doubles of LDS: block_sum's scratch, free for a kernel's own fixed-order reductions between two calls
+__device__ __forceinline__ double* block_red() {
+    __shared__ double red[256];
+    return red;
+}
+
+// deterministic sum of v over the block's 256 threads
+__device__ __forceinline__ double block_sum(int t, double v) {
+    double* red = block_red();
+    __syncthreads();
+    red[t] = v;
+    __syncthreads();
+    for (int s = 128; s > 0; s >>= 1) {
+        if (t < s) red[t] += red[t + s];
+        __syncthreads();
+    }
+    return red[0];
+}
+
 template <bool FUSED, bool ARD>
 __global__ __launch_bounds__(256) void k_grad(KernParams kp, const double* __restrict__ Xt1, long ld1, long n,
                                               const double* __restrict__ Xt2, long ld2, long m,
@@ -416,44 +471,23 @@ __global__ __launch_bounds__(256) void k_grad(KernParams kp, const double* __res
                                               RankTerm rk = RankTerm{nullptr, nullptr, 0, 0.0, 1.0, nullptr}) {
     __shared__ __attribute__((aligned(16))) double si[KDC * KT];
     __shared__ __attribute__((aligned(16))) double sj[KDC * KTJ];
-    __shared__ double red[256];
     const int t = threadIdx.x, tx = t & 15, ty = t >> 4;
     double a_var = 0.0, a_iso = 0.0;
     double a_q[KDC];
 #pragma unroll
     for (int q = 0; q < KDC; ++q) a_q[q] = 0.0;
     const int qcnt = ARD ? ((kp.D - q_off < KDC) ? (kp.D - q_off) : KDC) : 0;
-    // dL_dK = 0.5 (sc * alpha alpha^T - Dy W): sc = 1 for the Gaussian process, (nu+N)/(nu+beta-2) for the Student-t
-    // process (exact_studentt_inference.py:46), read from device memory because beta is produced on the device
     const double sc = (FUSED && aa_scale) ? aa_scale[0] : 1.0;
 
     for (long tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
         long ti, tj;
-        if (FUSED) {   // lower-triangular enumeration
-            ti = (long)((sqrt(8.0 * (double)tile + 1.0) - 1.0) * 0.5);
-            while (ti * (ti + 1) / 2 > tile) --ti;
-            while ((ti + 1) * (ti + 2) / 2 <= tile) ++ti;
-            tj = tile - ti * (ti + 1) / 2;
-        } else {
-            ti = tile / ntc;
-            tj = tile - ti * ntc;
-        }
+        grad_tile<FUSED>(tile, ntc, ti, tj);
         const long i0 = ti * KT, j0 = tj * KT;
         double r2[4][4];
-#pragma unroll
-        for (int a = 0; a < 4; ++a)
-#pragma unroll
-            for (int b = 0; b < 4; ++b) r2[a][b] = 0.0;
+        zero_tile(r2);
         int last_q0 = -1;
-        for (int q0 = 0; q0 < kp.D; q0 += KDC) {
-            const int qc = (kp.D - q0 < KDC) ? (kp.D - q0) : KDC;
-            __syncthreads();
-            stage_x(Xt1, ld1, i0, q0, qc, si, t);
-            stage_xj(Xt2, ld2, j0, q0, qc, sj, t);
-            __syncthreads();
-            accum_r2(si, sj, qc, ty, tx, r2);
-            last_q0 = q0;
-        }
+        for (int q0 = 0; q0 < kp.D; last_q0 = q0, q0 += KDC)
+            accum_r2(si, sj, stage_chunk(kp.D, q0, Xt1, ld1, i0, Xt2, ld2, j0, si, sj, t), ty, tx, r2);
         // weights * dL_dK, then the covariance factors
         double gT[4][4];   // g * dK/dr / r
 #pragma unroll
@@ -462,7 +496,7 @@ __global__ __launch_bounds__(256) void k_grad(KernParams kp, const double* __res
 #pragma unroll
             for (int b = 0; b < 4; ++b) {
                 const long j = j0 + tx * 4 + b;
-                double g = 0.0;
+                double g = 0.0;   // grad_weight<FUSED, true> with the rank term, spelt out: see there
                 if (i < n && j < m) {
                     if (FUSED) {
                         if (j <= i) {
@@ -480,7 +514,6 @@ __global__ __launch_bounds__(256) void k_grad(KernParams kp, const double* __res
                             if (rk.rowscale) g *= rk.rowscale[i];   // per-point precision (var_dtc.py:224-226)
                         }
                     }
-                    // factor of a product kernel: dL_dK times the other factors' covariances (prod.py:86-99)
                     if (Mul) g *= Mul[i * ldm + j];
                 }
                 const CovVal c = cov_all(kp.kind, kp.variance, r2[a][b], (FUSED || diag_same) && i == j);
@@ -489,25 +522,14 @@ __global__ __launch_bounds__(256) void k_grad(KernParams kp, const double* __res
                 gT[a][b] = g * c.dk_or;
             }
         }
-        if (!FUSED && Hout) {   // H = dL_dK * (dK/dr)/r for the gradients_X reductions (stationary.py:330-346); 0 at r = 0 as
-                                // `_inv_dist` has it (:225-232): a coincident pair gives exactly nothing, not x H - H x to rounding
+        if (!FUSED && Hout) {
 #pragma unroll
-            for (int a = 0; a < 4; ++a) {
-                const long i = i0 + ty * 4 + a;
+            for (int a = 0; a < 4; ++a)
 #pragma unroll
-                for (int b = 0; b < 4; ++b) {
-                    const long j = j0 + tx * 4 + b;
-                    if (i < n && j < m) Hout[i * ldh + j] = (r2[a][b] == 0.0) ? 0.0 : gT[a][b];
-                }
-            }
+                for (int b = 0; b < 4; ++b) store_h<true>(Hout, ldh, i0 + ty * 4 + a, j0 + tx * 4 + b, n, m, r2[a][b], gT[a][b]);
         }
         if (ARD) {
-            if (last_q0 != q_off) {   // D > 32: bring the dims of this launch back into LDS
-                __syncthreads();
-                stage_x(Xt1, ld1, i0, q_off, qcnt, si, t);
-                stage_xj(Xt2, ld2, j0, q_off, qcnt, sj, t);
-                __syncthreads();
-            }
+            restage(last_q0, q_off, qcnt, Xt1, ld1, i0, Xt2, ld2, j0, si, sj, t);
 #pragma unroll
             for (int q = 0; q < KDC; ++q) {
                 if (q < qcnt) {
@@ -528,26 +550,16 @@ __global__ __launch_bounds__(256) void k_grad(KernParams kp, const double* __res
     }
     // deterministic block reduction -> partials[blockIdx][...]
     double* out = partials + (long)blockIdx.x * GP_STRIDE;
-    auto block_sum = [&](double v) -> double {
-        __syncthreads();
-        red[t] = v;
-        __syncthreads();
-        for (int s = 128; s > 0; s >>= 1) {
-            if (t < s) red[t] += red[t + s];
-            __syncthreads();
-        }
-        return red[0];
-    };
-    const double sv = block_sum(a_var);
+    const double sv = block_sum(t, a_var);
     if (t == 0) out[0] = sv;
     if (!ARD) {
-        const double sl = block_sum(a_iso);
+        const double sl = block_sum(t, a_iso);
         if (t == 0) out[1] = sl;
     } else {
 #pragma unroll
         for (int q = 0; q < KDC; ++q) {
             if (q < qcnt) {
-                const double sq = block_sum(a_q[q]);
+                const double sq = block_sum(t, a_q[q]);
                 if (t == 0) out[2 + q] = sq;
             }
         }
@@ -565,38 +577,17 @@ int grad_generic_num_blocks(long n, long m) {
     return pick_grad_blocks(((n + KT - 1) / KT) * ((m + KT - 1) / KT));
 }
 
-// one launch per group of 32 lengthscale dimensions (ARD); partials for group gidx at partials + gidx*nblocks*GP_STRIDE
-void launch_grad_fused(hipStream_t st, KernParams kp, const double* Xt, long ldx, long n, const double* W,
-                       long ldw, const double* alpha, int Dy, double* partials, int stride, const double* aa_scale,
-                       const double* Mul, long ldm) {
-    (void)stride;
-    const long nt = (n + KT - 1) / KT;
-    const long ntiles = nt * (nt + 1) / 2;
-    const int nb = pick_grad_blocks(ntiles);
-    if (dot_kind(kp.kind)) {
-        launch_grad_dot(st, true, kp, Xt, ldx, n, Xt, ldx, n, W, ldw, alpha, Dy, ntiles, (int)nt, partials, nullptr, 0, aa_scale,
-                        Mul, ldm);
+// One launch per group of 32 dimensions for a kind that reduces per dimension (ARD), one launch otherwise: launch(q_off, part,
+// h) with the records of group gidx at part = partials + gidx * nb * GP_STRIDE.  Hout may alias G (in place), which every
+// launch reads: only the LAST group's launch gets it as h.
+template <class Launch>
+static void for_each_group(int D, bool perdim, int nb, double* partials, double* Hout, Launch launch) {
+    if (!perdim) {
+        launch(0, partials, Hout);
         return;
     }
-    if (kp.kind == MI355GP_LINEAR) {
-        launch_grad_lin(st, true, kp, Xt, ldx, n, Xt, ldx, n, W, ldw, alpha, Dy, ntiles, (int)nt, partials, nullptr, 0, aa_scale,
-                        Mul, ldm);
-        return;
-    }
-    if (kp.kind >= MI355GP_RATQUAD) {
-        launch_grad_ext(st, true, kp, Xt, ldx, n, Xt, ldx, n, W, ldw, alpha, Dy, ntiles, (int)nt, partials, nullptr, 0, aa_scale,
-                        Mul, ldm);
-        return;
-    }
-    if (!kp.ard) {
-        hipLaunchKernelGGL((k_grad<true, false>), dim3(nb), dim3(256), 0, st, kp, Xt, ldx, n, Xt, ldx, n, W, ldw,
-                           alpha, Dy, 0, ntiles, (int)nt, partials, nullptr, 0, 0, aa_scale, Mul, ldm);
-    } else {
-        for (int q_off = 0, gidx = 0; q_off < kp.D; q_off += KDC, ++gidx)
-            hipLaunchKernelGGL((k_grad<true, true>), dim3(nb), dim3(256), 0, st, kp, Xt, ldx, n, Xt, ldx, n, W, ldw,
-                               alpha, Dy, q_off, ntiles, (int)nt, partials + (long)gidx * nb * GP_STRIDE, nullptr, 0, 0,
-                               aa_scale, Mul, ldm);
-    }
+    for (int q_off = 0, gidx = 0; q_off < D; q_off += KDC, ++gidx)
+        launch(q_off, partials + (long)gidx * nb * GP_STRIDE, (q_off + KDC >= D) ? Hout : nullptr);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -615,7 +606,7 @@ __global__ __launch_bounds__(256) void k_grad_cols(KernParams kp, const double* 
     constexpr int NVMAX = 17;
     __shared__ __attribute__((aligned(16))) double si[KDC * KT];
     __shared__ __attribute__((aligned(16))) double sj[KDC * KTJ];
-    __shared__ double red[256];
+    double* red = block_red();
     const int t = threadIdx.x, tx = t & 15, ty = t >> 4;
     const int tj = blockIdx.x % ntc, split = blockIdx.x / ntc;
     const long j0 = (long)tj * KT;
@@ -694,26 +685,16 @@ __global__ __launch_bounds__(256) void k_grad_cols(KernParams kp, const double* 
     }
     // theta partials of this block
     double* out = partials + (long)blockIdx.x * GP_STRIDE;
-    auto block_sum = [&](double v) -> double {
-        __syncthreads();
-        red[t] = v;
-        __syncthreads();
-        for (int s = 128; s > 0; s >>= 1) {
-            if (t < s) red[t] += red[t + s];
-            __syncthreads();
-        }
-        return red[0];
-    };
-    const double sv = block_sum(a_var);
+    const double sv = block_sum(t, a_var);
     if (t == 0) out[0] = sv;
     if (!ARD) {
-        const double sl = block_sum(a_iso);
+        const double sl = block_sum(t, a_iso);
         if (t == 0) out[1] = sl;
     } else {
 #pragma unroll
         for (int q = 0; q < NVMAX - 1; ++q) {
             if (q < D) {
-                const double sq = block_sum(a_q[q]);
+                const double sq = block_sum(t, a_q[q]);
                 if (t == 0) out[2 + q] = sq;
             }
         }
@@ -762,7 +743,7 @@ __global__ __launch_bounds__(256, 2) void k_grad_cols_mfma(KernParams kp, const 
     __shared__ __attribute__((aligned(16))) double sj[DM * KTJ];
     __shared__ __attribute__((aligned(16))) double sit[KT * 18];   // x~ slab row-major [i][c], stride 18: the B operand
     __shared__ __attribute__((aligned(16))) double sh[KT * GC_HS];
-    __shared__ double red[256];
+    double* red = block_red();
     const int t = threadIdx.x, tx = t & 15, ty = t >> 4, lane = t & 63, w = t >> 6;
     const int tj = blockIdx.x % ntc, split = blockIdx.x / ntc;
     const long j0 = (long)tj * KT;
@@ -875,26 +856,16 @@ __global__ __launch_bounds__(256, 2) void k_grad_cols_mfma(KernParams kp, const 
     }
     // theta partials of this block
     double* out = partials + (long)blockIdx.x * GP_STRIDE;
-    auto block_sum = [&](double v) -> double {
-        __syncthreads();
-        red[t] = v;
-        __syncthreads();
-        for (int s = 128; s > 0; s >>= 1) {
-            if (t < s) red[t] += red[t + s];
-            __syncthreads();
-        }
-        return red[0];
-    };
-    const double sv = block_sum(a_var);
+    const double sv = block_sum(t, a_var);
     if (t == 0) out[0] = sv;
     if (!ARD) {
-        const double sl = block_sum(a_iso);
+        const double sl = block_sum(t, a_iso);
         if (t == 0) out[1] = sl;
     } else {
 #pragma unroll
         for (int q = 0; q < DM; ++q) {
             if (q < D) {
-                const double sq = block_sum(a_q[q]);
+                const double sq = block_sum(t, a_q[q]);
                 if (t == 0) out[2 + q] = sq;
             }
         }
@@ -967,42 +938,6 @@ void launch_studentt_scale(hipStream_t st, const double* scal, double nu, long n
     hipLaunchKernelGGL(k_studentt_scale, dim3(1), dim3(64), 0, st, scal, nu, (double)n, out);
 }
 
-void launch_grad_generic(hipStream_t st, KernParams kp, const double* Xt1, long ld1, long n, const double* Xt2,
-                         long ld2, long m, int symmetric, const double* G, long ldg, double* partials,
-                         int stride, double* Hout, long ldh, RankTerm rk) {
-    (void)stride;
-    const long ntr = (n + KT - 1) / KT, ntc = (m + KT - 1) / KT;
-    const long ntiles = ntr * ntc;
-    const int nb = pick_grad_blocks(ntiles);
-    if (dot_kind(kp.kind)) {
-        if (rk.Y) return;                                  // (the sparse path's rank term: it has neither kind)
-        launch_grad_dot(st, false, kp, Xt1, ld1, n, Xt2, ld2, m, G, ldg, nullptr, 0, ntiles, (int)ntc, partials, Hout, ldh,
-                        nullptr, nullptr, 0);
-        return;
-    }
-    if (kp.kind == MI355GP_LINEAR) {
-        if (rk.Y) return;                                  // (the sparse path's rank term: it does not have the kind)
-        launch_grad_lin(st, false, kp, Xt1, ld1, n, Xt2, ld2, m, G, ldg, nullptr, 0, ntiles, (int)ntc, partials, Hout, ldh,
-                        nullptr, nullptr, 0);
-        return;
-    }
-    if (kp.kind >= MI355GP_RATQUAD) {
-        if (rk.Y) return;                                  // the rank term belongs to the sparse path, which has neither kind
-        launch_grad_ext(st, false, kp, Xt1, ld1, n, Xt2, ld2, m, G, ldg, nullptr, 0, ntiles, (int)ntc, partials, Hout, ldh,
-                        nullptr, nullptr, 0);
-        return;
-    }
-    if (!kp.ard) {
-        hipLaunchKernelGGL((k_grad<false, false>), dim3(nb), dim3(256), 0, st, kp, Xt1, ld1, n, Xt2, ld2, m, G, ldg,
-                           nullptr, 0, 0, ntiles, (int)ntc, partials, Hout, ldh, symmetric, nullptr, nullptr, 0, rk);
-    } else {
-        // Hout may alias G (in place): only the LAST group launch writes it, every launch reads G
-        for (int q_off = 0, gidx = 0; q_off < kp.D; q_off += KDC, ++gidx)
-            hipLaunchKernelGGL((k_grad<false, true>), dim3(nb), dim3(256), 0, st, kp, Xt1, ld1, n, Xt2, ld2, m, G, ldg,
-                               nullptr, 0, q_off, ntiles, (int)ntc, partials + (long)gidx * nb * GP_STRIDE,
-                               (q_off + KDC >= kp.D) ? Hout : nullptr, ldh, symmetric, nullptr, nullptr, 0, rk);
-    }
-}
 
 // out[j][c] = sum_i M[i][j] * V(i, c), c < nv <= 33.  V(i, c) = V[i*sr + c*sc] for c < nvt, 1 for c == nvt (the column
 // sums): sr = 1, sc = ld for a dimension-major input, sr = Dy, sc = 1 for a row-major (rows x Dy) one.  One thread per column, 4 row groups per block, optional row split over blockIdx.y with a
@@ -1421,7 +1356,7 @@ void launch_rowscale_sqrt(hipStream_t st, const double* M, long ld, long rows, l
 
 // ------------------------------------------------------------------------------------------------
 // RatQuad (kind 6, stationary.py:747-802) and StdPeriodic (kind 7, standard_periodic.py:15-580).
-// Kernels of their own (templates on the kind), so that the instantiations of the other kinds keep their code.
+// Their own kernels (templates on the kind) around the shared skeleton: the accumulate step and the element are what differs.
 //   RatQuad:     K = var exp(-a log1p(r^2 / 2)),  dK/dr / r = -a K / (1 + r^2 / 2),  dK/da = -K log1p(r^2 / 2)
 //                (inputs scaled by 1 / l as for the other stationary kinds)
 //   StdPeriodic: K = var exp(-1/2 sum_q (sin(Delta_q) / l_q)^2),  Delta_q = pi (x_iq - x_jq) / T_q
@@ -1466,34 +1401,19 @@ __device__ __forceinline__ double ext_k(const KernParams& kp, double s) {
     return kp.variance * exp(-0.5 * s);
 }
 
-// Covariance assembly of k_kbuild (same tiling, same output conventions) for the two kinds.
+// Covariance assembly for the two kinds: no White-like diagonal in either.
 template <bool SYM, int KIND>
-__global__ __launch_bounds__(256) void k_kbuild_ext(KernParams kp, const double* __restrict__ Xt1, long ld1, long n,
-                                                    const double* __restrict__ Xt2, long ld2, long m,
-                                                    double* __restrict__ out, long ldo, long nrows_out,
-                                                    const double* __restrict__ noise, long noise_len, double jit,
-                                                    int lower_only, int add_diag, int ntc, int accumulate, const double* mul) {
+__global__ __launch_bounds__(256) void k_kbuild_ext(KbuildArgs A) {
     __shared__ __attribute__((aligned(16))) double si[KDC * KT];
     __shared__ __attribute__((aligned(16))) double sj[KDC * KTJ];
     const int t = threadIdx.x, tx = t & 15, ty = t >> 4;
-    const long ti = blockIdx.x / ntc, tj = blockIdx.x % ntc;
-    if (SYM && lower_only && tj > ti) return;
-    const long i0 = ti * KT, j0 = tj * KT;
+    long i0, j0;
+    if (!kbuild_tile<SYM>(A, i0, j0)) return;
     double s[4][4];
-#pragma unroll
-    for (int a = 0; a < 4; ++a)
-#pragma unroll
-        for (int b = 0; b < 4; ++b) s[a][b] = 0.0;
-    if ((i0 < n) && (j0 < m)) {
-        for (int q0 = 0; q0 < kp.D; q0 += KDC) {
-            const int qc = (kp.D - q0 < KDC) ? (kp.D - q0) : KDC;
-            __syncthreads();
-            stage_x(Xt1, ld1, i0, q0, qc, si, t);
-            stage_xj(Xt2, ld2, j0, q0, qc, sj, t);
-            __syncthreads();
-            accum_ext<KIND>(si, sj, kp, q0, qc, ty, tx, s);
-        }
-    }
+    zero_tile(s);
+    if (i0 < A.n && j0 < A.m)
+        for (int q0 = 0; q0 < A.kp.D; q0 += KDC)
+            accum_ext<KIND>(si, sj, A.kp, q0, stage_chunk(A.kp.D, q0, A.Xt1, A.ld1, i0, A.Xt2, A.ld2, j0, si, sj, t), ty, tx, s);
 #pragma unroll
     for (int a = 0; a < 4; ++a) {
         const long i = i0 + ty * 4 + a;
@@ -1501,54 +1421,10 @@ __global__ __launch_bounds__(256) void k_kbuild_ext(KernParams kp, const double*
 #pragma unroll
         for (int b = 0; b < 4; ++b) {
             const long j = j0 + tx * 4 + b;
-            if (i < n && j < m) v[b] = ext_k<KIND>(kp, s[a][b]);
-            else v[b] = (SYM && i == j && !accumulate) ? 1.0 : 0.0;
+            if (i < A.n && j < A.m) v[b] = ext_k<KIND>(A.kp, s[a][b]);
+            else v[b] = kbuild_pad<SYM>(A, i, j);
         }
-        if (SYM) {
-            if (i < nrows_out) {
-                d4* p = reinterpret_cast<d4*>(out + i * ldo + j0 + tx * 4);
-                d4 o = (d4){v[0], v[1], v[2], v[3]};
-                if (mul) o *= *reinterpret_cast<const d4*>(mul + i * ldo + j0 + tx * 4);
-                if (add_diag && i < n) {
-                    const long d = i - (j0 + tx * 4);
-                    if (d >= 0 && d < 4) o[d] += noise[noise_len > 1 ? i : 0] + jit;
-                }
-                if (accumulate) o += *p;
-                *p = o;
-            }
-        } else if (i < n) {
-#pragma unroll
-            for (int b = 0; b < 4; ++b) {
-                const long j = j0 + tx * 4 + b;
-                if (j < m) {
-                    const double w = mul ? v[b] * mul[i * ldo + j] : v[b];
-                    out[i * ldo + j] = accumulate ? out[i * ldo + j] + w : w;
-                }
-            }
-        }
-    }
-}
-
-static void launch_kbuild_ext(hipStream_t st, bool sym, KernParams kp, const double* Xt1, long ld1, long n, const double* Xt2,
-                              long ld2, long m, double* out, long ldo, long nrows_out, const double* noise, long noise_len,
-                              double jit, int lower_only, int add_diag, int ntc, int nblocks, int accumulate, int diag_same,
-                              const double* mul) {
-    (void)diag_same;                                   // no White-like diagonal in either kind
-    const dim3 g((unsigned)nblocks), b(256);
-    if (kp.kind == MI355GP_RATQUAD) {
-        if (sym)
-            hipLaunchKernelGGL((k_kbuild_ext<true, MI355GP_RATQUAD>), g, b, 0, st, kp, Xt1, ld1, n, Xt2, ld2, m, out, ldo, nrows_out,
-                               noise, noise_len, jit, lower_only, add_diag, ntc, accumulate, mul);
-        else
-            hipLaunchKernelGGL((k_kbuild_ext<false, MI355GP_RATQUAD>), g, b, 0, st, kp, Xt1, ld1, n, Xt2, ld2, m, out, ldo,
-                               nrows_out, noise, noise_len, jit, lower_only, add_diag, ntc, accumulate, mul);
-    } else if (kp.kind == MI355GP_STDPERIODIC) {
-        if (sym)
-            hipLaunchKernelGGL((k_kbuild_ext<true, MI355GP_STDPERIODIC>), g, b, 0, st, kp, Xt1, ld1, n, Xt2, ld2, m, out, ldo, nrows_out,
-                               noise, noise_len, jit, lower_only, add_diag, ntc, accumulate, mul);
-        else
-            hipLaunchKernelGGL((k_kbuild_ext<false, MI355GP_STDPERIODIC>), g, b, 0, st, kp, Xt1, ld1, n, Xt2, ld2, m, out, ldo,
-                               nrows_out, noise, noise_len, jit, lower_only, add_diag, ntc, accumulate, mul);
+        kbuild_store_row<SYM>(A, i, j0, tx, v);
     }
 }
 
@@ -1568,7 +1444,6 @@ __global__ __launch_bounds__(256) void k_grad_ext(KernParams kp, const double* _
     constexpr bool PER = (KIND == MI355GP_STDPERIODIC);
     __shared__ __attribute__((aligned(16))) double si[KDC * KT];
     __shared__ __attribute__((aligned(16))) double sj[KDC * KTJ];
-    __shared__ double red[256];
     const int t = threadIdx.x, tx = t & 15, ty = t >> 4;
     const bool perdim = PER || kp.ard;
     double a_var = 0.0, a_iso = 0.0, a_pow = 0.0;
@@ -1582,31 +1457,13 @@ __global__ __launch_bounds__(256) void k_grad_ext(KernParams kp, const double* _
 
     for (long tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
         long ti, tj;
-        if (FUSED) {
-            ti = (long)((sqrt(8.0 * (double)tile + 1.0) - 1.0) * 0.5);
-            while (ti * (ti + 1) / 2 > tile) --ti;
-            while ((ti + 1) * (ti + 2) / 2 <= tile) ++ti;
-            tj = tile - ti * (ti + 1) / 2;
-        } else {
-            ti = tile / ntc;
-            tj = tile - ti * ntc;
-        }
+        grad_tile<FUSED>(tile, ntc, ti, tj);
         const long i0 = ti * KT, j0 = tj * KT;
         double s[4][4];
-#pragma unroll
-        for (int a = 0; a < 4; ++a)
-#pragma unroll
-            for (int b = 0; b < 4; ++b) s[a][b] = 0.0;
+        zero_tile(s);
         int last_q0 = -1;
-        for (int q0 = 0; q0 < kp.D; q0 += KDC) {
-            const int qc = (kp.D - q0 < KDC) ? (kp.D - q0) : KDC;
-            __syncthreads();
-            stage_x(Xt1, ld1, i0, q0, qc, si, t);
-            stage_xj(Xt2, ld2, j0, q0, qc, sj, t);
-            __syncthreads();
-            accum_ext<KIND>(si, sj, kp, q0, qc, ty, tx, s);
-            last_q0 = q0;
-        }
+        for (int q0 = 0; q0 < kp.D; last_q0 = q0, q0 += KDC)
+            accum_ext<KIND>(si, sj, kp, q0, stage_chunk(kp.D, q0, Xt1, ld1, i0, Xt2, ld2, j0, si, sj, t), ty, tx, s);
         double gw[4][4];   // RatQuad: g dK/dr / r;  StdPeriodic: g K
 #pragma unroll
         for (int a = 0; a < 4; ++a) {
@@ -1614,20 +1471,7 @@ __global__ __launch_bounds__(256) void k_grad_ext(KernParams kp, const double* _
 #pragma unroll
             for (int b = 0; b < 4; ++b) {
                 const long j = j0 + tx * 4 + b;
-                double g = 0.0;
-                if (i < n && j < m) {
-                    if (FUSED) {
-                        if (j <= i) {
-                            double aa = 0.0;
-                            for (int d = 0; d < Dy; ++d) aa = fma(alpha[i * Dy + d], alpha[j * Dy + d], aa);
-                            g = 0.5 * (sc * aa - (double)Dy * G[i * ldg + j]);
-                            if (j < i) g *= 2.0;
-                        }
-                    } else {
-                        g = G[i * ldg + j];
-                    }
-                    if (Mul) g *= Mul[i * ldm + j];
-                }
+                const double g = grad_weight<FUSED, true>(i, j, n, m, G, ldg, alpha, Dy, sc, Mul, ldm);
                 if (PER) {
                     const double k = kp.variance * exp(-0.5 * s[a][b]);
                     a_var = fma(g, k, a_var);
@@ -1642,24 +1486,15 @@ __global__ __launch_bounds__(256) void k_grad_ext(KernParams kp, const double* _
                 }
             }
         }
-        if (!PER && !FUSED && Hout) {   // H = dL_dK (dK/dr) / r for the gradients_X reductions, as in k_grad (0 at r = 0)
+        // RatQuad: H = dL_dK (dK/dr) / r as in k_grad (0 at r = 0); StdPeriodic has its own dK/dx pass (k_periodic_gradx)
+        if (!PER && !FUSED && Hout) {
 #pragma unroll
-            for (int a = 0; a < 4; ++a) {
-                const long i = i0 + ty * 4 + a;
+            for (int a = 0; a < 4; ++a)
 #pragma unroll
-                for (int b = 0; b < 4; ++b) {
-                    const long j = j0 + tx * 4 + b;
-                    if (i < n && j < m) Hout[i * ldh + j] = (s[a][b] == 0.0) ? 0.0 : gw[a][b];
-                }
-            }
+                for (int b = 0; b < 4; ++b) store_h<true>(Hout, ldh, i0 + ty * 4 + a, j0 + tx * 4 + b, n, m, s[a][b], gw[a][b]);
         }
         if (qcnt > 0) {
-            if (last_q0 != q_off) {
-                __syncthreads();
-                stage_x(Xt1, ld1, i0, q_off, qcnt, si, t);
-                stage_xj(Xt2, ld2, j0, q_off, qcnt, sj, t);
-                __syncthreads();
-            }
+            restage(last_q0, q_off, qcnt, Xt1, ld1, i0, Xt2, ld2, j0, si, sj, t);
 #pragma unroll
             for (int q = 0; q < KDC; ++q) {
                 if (q < qcnt) {
@@ -1697,69 +1532,50 @@ __global__ __launch_bounds__(256) void k_grad_ext(KernParams kp, const double* _
     }
     double* outA = partA + (long)blockIdx.x * GP_STRIDE;
     double* outB = partB + (long)blockIdx.x * GP_STRIDE;
-    auto block_sum = [&](double v) -> double {
-        __syncthreads();
-        red[t] = v;
-        __syncthreads();
-        for (int s = 128; s > 0; s >>= 1) {
-            if (t < s) red[t] += red[t + s];
-            __syncthreads();
-        }
-        return red[0];
-    };
-    const double sv = block_sum(a_var);
+    const double sv = block_sum(t, a_var);
     if (t == 0) outA[0] = sv;
     if (!PER) {
-        const double sp = block_sum(a_pow);
+        const double sp = block_sum(t, a_pow);
         if (t == 0) outB[0] = sp;
         if (!kp.ard) {
-            const double sl = block_sum(a_iso);
+            const double sl = block_sum(t, a_iso);
             if (t == 0) outA[1] = sl;
         }
     }
 #pragma unroll
     for (int q = 0; q < KDC; ++q) {
         if (q < qcnt) {
-            const double s1 = block_sum(a1[q]);
+            const double s1 = block_sum(t, a1[q]);
             if (t == 0) outA[2 + q] = s1;
             if (PER) {
-                const double s2 = block_sum(a2[PER ? q : 0]);
+                const double s2 = block_sum(t, a2[PER ? q : 0]);
                 if (t == 0) outB[2 + q] = s2;
             }
         }
     }
 }
 
+// (the signature every family's gradient launcher has: the arguments of the kernels but q_off, which for_each_group supplies)
 static void launch_grad_ext(hipStream_t st, bool fused, KernParams kp, const double* Xt1, long ld1, long n, const double* Xt2,
                             long ld2, long m, const double* G, long ldg, const double* alpha, int Dy, long ntiles, int ntc,
                             double* partials, double* Hout, long ldh, const double* aa_scale, const double* Mul, long ldm) {
     const int nb = pick_grad_blocks(ntiles);
-    const int groups = (kp.D + KDC - 1) / KDC;
-    const bool perdim = kp.kind == MI355GP_STDPERIODIC || kp.ard;
-    double* partB = partials + (long)groups * nb * GP_STRIDE;
-    for (int q_off = 0, gidx = 0; q_off < kp.D; q_off += KDC, ++gidx) {
-        if (!perdim && gidx > 0) break;
-        double* pa = partials + (long)gidx * nb * GP_STRIDE;
-        double* pb = partB + (long)gidx * nb * GP_STRIDE;
-        // Hout may alias G (in place): only the LAST group launch writes it
-        double* h = (!perdim || q_off + KDC >= kp.D) ? Hout : nullptr;
-        const dim3 g((unsigned)nb), b(256);
-        if (kp.kind == MI355GP_RATQUAD) {
-            if (fused)
-                hipLaunchKernelGGL((k_grad_ext<true, MI355GP_RATQUAD>), g, b, 0, st, kp, Xt1, ld1, n, Xt2, ld2, m, G, ldg, alpha, Dy,
-                                   q_off, ntiles, ntc, pa, pb, nullptr, 0, aa_scale, Mul, ldm);
-            else
-                hipLaunchKernelGGL((k_grad_ext<false, MI355GP_RATQUAD>), g, b, 0, st, kp, Xt1, ld1, n, Xt2, ld2, m, G, ldg, nullptr, 0,
-                                   q_off, ntiles, ntc, pa, pb, h, ldh, nullptr, nullptr, 0);
-        } else if (kp.kind == MI355GP_STDPERIODIC) {
-            if (fused)
-                hipLaunchKernelGGL((k_grad_ext<true, MI355GP_STDPERIODIC>), g, b, 0, st, kp, Xt1, ld1, n, Xt2, ld2, m, G, ldg, alpha, Dy,
-                                   q_off, ntiles, ntc, pa, pb, nullptr, 0, aa_scale, Mul, ldm);
-            else
-                hipLaunchKernelGGL((k_grad_ext<false, MI355GP_STDPERIODIC>), g, b, 0, st, kp, Xt1, ld1, n, Xt2, ld2, m, G, ldg, nullptr, 0,
-                                   q_off, ntiles, ntc, pa, pb, nullptr, 0, nullptr, nullptr, 0);
+    const dim3 g((unsigned)nb), b(256);
+    const bool per = kp.kind == MI355GP_STDPERIODIC;
+    const long offB = (long)((kp.D + KDC - 1) / KDC) * nb * GP_STRIDE;      // the second records follow every group's first
+    for_each_group(kp.D, per || kp.ard, nb, partials, Hout, [&](int q_off, double* pa, double* h) {
+#define GRAD_EXT(F, K)                                                                                                           \
+    hipLaunchKernelGGL((k_grad_ext<F, K>), g, b, 0, st, kp, Xt1, ld1, n, Xt2, ld2, m, G, ldg, alpha, Dy, q_off, ntiles, ntc, pa, \
+                       pa + offB, h, ldh, aa_scale, Mul, ldm)
+        if (per) {
+            if (fused) GRAD_EXT(true, MI355GP_STDPERIODIC);
+            else GRAD_EXT(false, MI355GP_STDPERIODIC);
+        } else {
+            if (fused) GRAD_EXT(true, MI355GP_RATQUAD);
+            else GRAD_EXT(false, MI355GP_RATQUAD);
         }
-    }
+#undef GRAD_EXT
+    });
 }
 
 // StdPeriodic dK/dx as a row reduction (see internal.h).  Block = 64 rows x 4 column lanes; the block walks every 64-column
@@ -1859,28 +1675,23 @@ __device__ __forceinline__ int coreg_idx(double x, int P) {
     return ((double)a == x && a >= 0 && a < P) ? a : -1;
 }
 
-// Covariance assembly of k_kbuild (same tiling and output conventions: lower tiles, noise + jitter on the diagonal, accumulate,
-// mul, identity padding).  B lives in LDS once per block, the tile's row / column indices as integers.
+// Covariance assembly: the skeleton's tile decode and row epilogue around a lookup -- nothing to accumulate.  B lives in LDS
+// once per block, the tile's row / column indices as integers.  The diagonal is what B gives.
 template <bool SYM>
-__global__ __launch_bounds__(256) void k_kbuild_coreg(KernParams kp, const double* __restrict__ Xt1, long ld1, long n,
-                                                      const double* __restrict__ Xt2, long ld2, long m,
-                                                      double* __restrict__ out, long ldo, long nrows_out,
-                                                      const double* __restrict__ noise, long noise_len, double jit,
-                                                      int lower_only, int add_diag, int ntc, int accumulate, const double* mul) {
+__global__ __launch_bounds__(256) void k_kbuild_coreg(KbuildArgs A) {
     __shared__ double sB[COREG_PMAX * COREG_PMAX];
     __shared__ int sa[KT], sb[KT];
     const int t = threadIdx.x, tx = t & 15, ty = t >> 4;
-    const long ti = blockIdx.x / ntc, tj = blockIdx.x % ntc;
-    if (SYM && lower_only && tj > ti) return;
-    const long i0 = ti * KT, j0 = tj * KT;
-    const int P = kp.ard;
-    for (int k = t; k < P * P; k += 256) sB[k] = kp.pw[k];
+    long i0, j0;
+    if (!kbuild_tile<SYM>(A, i0, j0)) return;
+    const int P = A.kp.ard;
+    for (int k = t; k < P * P; k += 256) sB[k] = A.kp.pw[k];
     if (t < KT) {
         const long i = i0 + t;
-        sa[t] = (i < n) ? coreg_idx(Xt1[(long)kp.col * ld1 + i], P) : 0;
+        sa[t] = (i < A.n) ? coreg_idx(A.Xt1[(long)A.kp.col * A.ld1 + i], P) : 0;
     } else if (t < 2 * KT) {
         const long j = j0 + (t - KT);
-        sb[t - KT] = (j < m) ? coreg_idx(Xt2[(long)kp.col * ld2 + j], P) : 0;
+        sb[t - KT] = (j < A.m) ? coreg_idx(A.Xt2[(long)A.kp.col * A.ld2 + j], P) : 0;
     }
     __syncthreads();
 #pragma unroll
@@ -1892,44 +1703,11 @@ __global__ __launch_bounds__(256) void k_kbuild_coreg(KernParams kp, const doubl
         for (int b = 0; b < 4; ++b) {
             const long j = j0 + tx * 4 + b;
             const int jb = sb[tx * 4 + b];
-            if (i < n && j < m) v[b] = (ia >= 0 && jb >= 0) ? sB[ia * P + jb] : __builtin_nan("");
-            else v[b] = (SYM && i == j && !accumulate) ? 1.0 : 0.0;
+            if (i < A.n && j < A.m) v[b] = (ia >= 0 && jb >= 0) ? sB[ia * P + jb] : __builtin_nan("");
+            else v[b] = kbuild_pad<SYM>(A, i, j);
         }
-        if (SYM) {
-            if (i < nrows_out) {
-                d4* p = reinterpret_cast<d4*>(out + i * ldo + j0 + tx * 4);
-                d4 o = (d4){v[0], v[1], v[2], v[3]};
-                if (mul) o *= *reinterpret_cast<const d4*>(mul + i * ldo + j0 + tx * 4);
-                if (add_diag && i < n) {
-                    const long d = i - (j0 + tx * 4);
-                    if (d >= 0 && d < 4) o[d] += noise[noise_len > 1 ? i : 0] + jit;
-                }
-                if (accumulate) o += *p;
-                *p = o;
-            }
-        } else if (i < n) {
-#pragma unroll
-            for (int b = 0; b < 4; ++b) {
-                const long j = j0 + tx * 4 + b;
-                if (j < m) {
-                    const double w = mul ? v[b] * mul[i * ldo + j] : v[b];
-                    out[i * ldo + j] = accumulate ? out[i * ldo + j] + w : w;
-                }
-            }
-        }
+        kbuild_store_row<SYM>(A, i, j0, tx, v);
     }
-}
-
-static void launch_kbuild_coreg(hipStream_t st, bool sym, KernParams kp, const double* Xt1, long ld1, long n, const double* Xt2,
-                                long ld2, long m, double* out, long ldo, long nrows_out, const double* noise, long noise_len,
-                                double jit, int lower_only, int add_diag, int ntc, int nblocks, int accumulate, const double* mul) {
-    const dim3 g((unsigned)nblocks), b(256);
-    if (sym)
-        hipLaunchKernelGGL((k_kbuild_coreg<true>), g, b, 0, st, kp, Xt1, ld1, n, Xt2, ld2, m, out, ldo, nrows_out, noise, noise_len,
-                           jit, lower_only, add_diag, ntc, accumulate, mul);
-    else
-        hipLaunchKernelGGL((k_kbuild_coreg<false>), g, b, 0, st, kp, Xt1, ld1, n, Xt2, ld2, m, out, ldo, nrows_out, noise,
-                           noise_len, jit, lower_only, add_diag, ntc, accumulate, mul);
 }
 
 // The bucketed gradient (see internal.h).  Per tile: the row / column indices go to LDS and two waves OR them into the masks of
@@ -1956,15 +1734,7 @@ __global__ __launch_bounds__(256) void k_grad_coreg(KernParams kp, const double*
 
     for (long tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
         long ti, tj;
-        if (FUSED) {
-            ti = (long)((sqrt(8.0 * (double)tile + 1.0) - 1.0) * 0.5);
-            while (ti * (ti + 1) / 2 > tile) --ti;
-            while ((ti + 1) * (ti + 2) / 2 <= tile) ++ti;
-            tj = tile - ti * (ti + 1) / 2;
-        } else {
-            ti = tile / ntc;
-            tj = tile - ti * ntc;
-        }
+        grad_tile<FUSED>(tile, ntc, ti, tj);
         const long i0 = ti * KT, j0 = tj * KT;
         __syncthreads();                                   // the previous tile's reads of sa / sb / smask are done
         if (wv < 2) {
@@ -1978,29 +1748,12 @@ __global__ __launch_bounds__(256) void k_grad_coreg(KernParams kp, const double*
             else sb[lane] = v;
             if (lane == 0) smask[wv] = bit;
         }
-        double w[4][4];
+        double w[4][4];   // no doubling below the diagonal: sd completes symmetrically
 #pragma unroll
-        for (int a = 0; a < 4; ++a) {
-            const long i = i0 + ty * 4 + a;
+        for (int a = 0; a < 4; ++a)
 #pragma unroll
-            for (int b = 0; b < 4; ++b) {
-                const long j = j0 + tx * 4 + b;
-                double g = 0.0;
-                if (i < n && j < m) {
-                    if (FUSED) {
-                        if (j <= i) {
-                            double aa = 0.0;
-                            for (int d = 0; d < Dy; ++d) aa = fma(alpha[i * Dy + d], alpha[j * Dy + d], aa);
-                            g = 0.5 * (sc * aa - (double)Dy * G[i * ldg + j]);
-                            if (Mul) g *= Mul[i * ldm + j];
-                        }
-                    } else {
-                        g = G[i * ldg + j];
-                    }
-                }
-                w[a][b] = g;
-            }
-        }
+            for (int b = 0; b < 4; ++b)
+                w[a][b] = grad_weight<FUSED, false>(i0 + ty * 4 + a, j0 + tx * 4 + b, n, m, G, ldg, alpha, Dy, sc, Mul, ldm);
         __syncthreads();
         const unsigned rm = smask[0], cm = smask[1];
         if (t == 0 && ((rm | cm) >> COREG_PMAX)) poisoned = true;
@@ -2088,9 +1841,10 @@ void launch_col_reduce_vec(hipStream_t st, const double* M, long ld, long rows, 
 
 // ------------------------------------------------------------------------------------------------
 // Linear (kind 9, linear.py:13-114): K = sum_q var_q x_iq x_jq.  Inputs arrive scaled by sqrt(var_q) on the active dimensions
-// (0 elsewhere), so K = sum_q x~_iq x~_jq with no further factor.  Kernels of their own again: every other instantiation keeps
-// its code.  The sum over q runs in the same order for (i, j) and (j, i) and fma(a, b, c) = fma(b, a, c): K(X, X) is bitwise
-// symmetric.  The diagonal is what the sum gives (it depends on the point; there is no variance to put there).
+// (0 elsewhere), so K = sum_q x~_iq x~_jq with no further factor.  Its own kernels around the shared skeleton: the dot product is
+// the accumulate step, the sum is the element.  The sum over q runs in the same order for (i, j) and (j, i) and
+// fma(a, b, c) = fma(b, a, c): K(X, X) is bitwise symmetric.  The diagonal is what the sum gives (it depends on the point; there
+// is no variance to put there).
 
 // s[a][b] += sum_q xi[q][ty*4+a] * xj[q][tx*4+b]
 __device__ __forceinline__ void accum_dot(const double* si, const double* sj, int qc, int ty, int tx, double (&s)[4][4]) {
@@ -2104,34 +1858,19 @@ __device__ __forceinline__ void accum_dot(const double* si, const double* sj, in
     }
 }
 
-// Covariance assembly of k_kbuild (same tiling, same output conventions).
+// Covariance assembly: the element is the sum itself.
 template <bool SYM>
-__global__ __launch_bounds__(256) void k_kbuild_lin(KernParams kp, const double* __restrict__ Xt1, long ld1, long n,
-                                                    const double* __restrict__ Xt2, long ld2, long m,
-                                                    double* __restrict__ out, long ldo, long nrows_out,
-                                                    const double* __restrict__ noise, long noise_len, double jit,
-                                                    int lower_only, int add_diag, int ntc, int accumulate, const double* mul) {
+__global__ __launch_bounds__(256) void k_kbuild_lin(KbuildArgs A) {
     __shared__ __attribute__((aligned(16))) double si[KDC * KT];
     __shared__ __attribute__((aligned(16))) double sj[KDC * KTJ];
     const int t = threadIdx.x, tx = t & 15, ty = t >> 4;
-    const long ti = blockIdx.x / ntc, tj = blockIdx.x % ntc;
-    if (SYM && lower_only && tj > ti) return;
-    const long i0 = ti * KT, j0 = tj * KT;
+    long i0, j0;
+    if (!kbuild_tile<SYM>(A, i0, j0)) return;
     double s[4][4];
-#pragma unroll
-    for (int a = 0; a < 4; ++a)
-#pragma unroll
-        for (int b = 0; b < 4; ++b) s[a][b] = 0.0;
-    if ((i0 < n) && (j0 < m)) {
-        for (int q0 = 0; q0 < kp.D; q0 += KDC) {
-            const int qc = (kp.D - q0 < KDC) ? (kp.D - q0) : KDC;
-            __syncthreads();
-            stage_x(Xt1, ld1, i0, q0, qc, si, t);
-            stage_xj(Xt2, ld2, j0, q0, qc, sj, t);
-            __syncthreads();
-            accum_dot(si, sj, qc, ty, tx, s);
-        }
-    }
+    zero_tile(s);
+    if (i0 < A.n && j0 < A.m)
+        for (int q0 = 0; q0 < A.kp.D; q0 += KDC)
+            accum_dot(si, sj, stage_chunk(A.kp.D, q0, A.Xt1, A.ld1, i0, A.Xt2, A.ld2, j0, si, sj, t), ty, tx, s);
 #pragma unroll
     for (int a = 0; a < 4; ++a) {
         const long i = i0 + ty * 4 + a;
@@ -2139,44 +1878,11 @@ __global__ __launch_bounds__(256) void k_kbuild_lin(KernParams kp, const double*
 #pragma unroll
         for (int b = 0; b < 4; ++b) {
             const long j = j0 + tx * 4 + b;
-            if (i < n && j < m) v[b] = s[a][b];
-            else v[b] = (SYM && i == j && !accumulate) ? 1.0 : 0.0;
+            if (i < A.n && j < A.m) v[b] = s[a][b];
+            else v[b] = kbuild_pad<SYM>(A, i, j);
         }
-        if (SYM) {
-            if (i < nrows_out) {
-                d4* p = reinterpret_cast<d4*>(out + i * ldo + j0 + tx * 4);
-                d4 o = (d4){v[0], v[1], v[2], v[3]};
-                if (mul) o *= *reinterpret_cast<const d4*>(mul + i * ldo + j0 + tx * 4);
-                if (add_diag && i < n) {
-                    const long d = i - (j0 + tx * 4);
-                    if (d >= 0 && d < 4) o[d] += noise[noise_len > 1 ? i : 0] + jit;
-                }
-                if (accumulate) o += *p;
-                *p = o;
-            }
-        } else if (i < n) {
-#pragma unroll
-            for (int b = 0; b < 4; ++b) {
-                const long j = j0 + tx * 4 + b;
-                if (j < m) {
-                    const double w = mul ? v[b] * mul[i * ldo + j] : v[b];
-                    out[i * ldo + j] = accumulate ? out[i * ldo + j] + w : w;
-                }
-            }
-        }
+        kbuild_store_row<SYM>(A, i, j0, tx, v);
     }
-}
-
-static void launch_kbuild_lin(hipStream_t st, bool sym, KernParams kp, const double* Xt1, long ld1, long n, const double* Xt2,
-                              long ld2, long m, double* out, long ldo, long nrows_out, const double* noise, long noise_len,
-                              double jit, int lower_only, int add_diag, int ntc, int nblocks, int accumulate, const double* mul) {
-    const dim3 g((unsigned)nblocks), b(256);
-    if (sym)
-        hipLaunchKernelGGL((k_kbuild_lin<true>), g, b, 0, st, kp, Xt1, ld1, n, Xt2, ld2, m, out, ldo, nrows_out, noise, noise_len,
-                           jit, lower_only, add_diag, ntc, accumulate, mul);
-    else
-        hipLaunchKernelGGL((k_kbuild_lin<false>), g, b, 0, st, kp, Xt1, ld1, n, Xt2, ld2, m, out, ldo, nrows_out, noise, noise_len,
-                           jit, lower_only, add_diag, ntc, accumulate, mul);
 }
 
 // Gradient pass of k_grad for the kind, one launch per group of 32 dimensions (q_off; one launch if !ard).  Record [GP_STRIDE]
@@ -2193,7 +1899,6 @@ __global__ __launch_bounds__(256) void k_grad_lin(KernParams kp, const double* _
                                                   const double* __restrict__ Mul, long ldm) {
     __shared__ __attribute__((aligned(16))) double si[KDC * KT];
     __shared__ __attribute__((aligned(16))) double sj[KDC * KTJ];
-    __shared__ double red[256];
     const int t = threadIdx.x, tx = t & 15, ty = t >> 4;
     double a_var = 0.0;
     double a_q[KDC];
@@ -2204,31 +1909,13 @@ __global__ __launch_bounds__(256) void k_grad_lin(KernParams kp, const double* _
 
     for (long tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
         long ti, tj;
-        if (FUSED) {   // lower-triangular enumeration
-            ti = (long)((sqrt(8.0 * (double)tile + 1.0) - 1.0) * 0.5);
-            while (ti * (ti + 1) / 2 > tile) --ti;
-            while ((ti + 1) * (ti + 2) / 2 <= tile) ++ti;
-            tj = tile - ti * (ti + 1) / 2;
-        } else {
-            ti = tile / ntc;
-            tj = tile - ti * ntc;
-        }
+        grad_tile<FUSED>(tile, ntc, ti, tj);
         const long i0 = ti * KT, j0 = tj * KT;
         double s[4][4];
-#pragma unroll
-        for (int a = 0; a < 4; ++a)
-#pragma unroll
-            for (int b = 0; b < 4; ++b) s[a][b] = 0.0;
+        zero_tile(s);
         int last_q0 = -1;
-        for (int q0 = 0; q0 < kp.D; q0 += KDC) {
-            const int qc = (kp.D - q0 < KDC) ? (kp.D - q0) : KDC;
-            __syncthreads();
-            stage_x(Xt1, ld1, i0, q0, qc, si, t);
-            stage_xj(Xt2, ld2, j0, q0, qc, sj, t);
-            __syncthreads();
-            accum_dot(si, sj, qc, ty, tx, s);
-            last_q0 = q0;
-        }
+        for (int q0 = 0; q0 < kp.D; last_q0 = q0, q0 += KDC)
+            accum_dot(si, sj, stage_chunk(kp.D, q0, Xt1, ld1, i0, Xt2, ld2, j0, si, sj, t), ty, tx, s);
         double gw[4][4];   // g
 #pragma unroll
         for (int a = 0; a < 4; ++a) {
@@ -2236,32 +1923,14 @@ __global__ __launch_bounds__(256) void k_grad_lin(KernParams kp, const double* _
 #pragma unroll
             for (int b = 0; b < 4; ++b) {
                 const long j = j0 + tx * 4 + b;
-                double g = 0.0;
-                if (i < n && j < m) {
-                    if (FUSED) {
-                        if (j <= i) {
-                            double aa = 0.0;
-                            for (int d = 0; d < Dy; ++d) aa = fma(alpha[i * Dy + d], alpha[j * Dy + d], aa);
-                            g = 0.5 * (sc * aa - (double)Dy * G[i * ldg + j]);
-                            if (j < i) g *= 2.0;
-                        }
-                    } else {
-                        g = G[i * ldg + j];
-                    }
-                    if (Mul) g *= Mul[i * ldm + j];
-                    if (!FUSED && Hout) Hout[i * ldh + j] = g;
-                }
+                const double g = grad_weight<FUSED, true>(i, j, n, m, G, ldg, alpha, Dy, sc, Mul, ldm);
+                if (!FUSED && Hout) store_h<false>(Hout, ldh, i, j, n, m, g, g);
                 a_var = fma(g, s[a][b], a_var);
                 gw[a][b] = g;
             }
         }
         if (qcnt > 0) {
-            if (last_q0 != q_off) {   // D > 32: bring the dims of this launch back into LDS
-                __syncthreads();
-                stage_x(Xt1, ld1, i0, q_off, qcnt, si, t);
-                stage_xj(Xt2, ld2, j0, q_off, qcnt, sj, t);
-                __syncthreads();
-            }
+            restage(last_q0, q_off, qcnt, Xt1, ld1, i0, Xt2, ld2, j0, si, sj, t);
 #pragma unroll
             for (int q = 0; q < KDC; ++q) {
                 if (q < qcnt) {
@@ -2282,22 +1951,12 @@ __global__ __launch_bounds__(256) void k_grad_lin(KernParams kp, const double* _
     }
     // deterministic block reduction -> partials[blockIdx][...]
     double* out = partials + (long)blockIdx.x * GP_STRIDE;
-    auto block_sum = [&](double v) -> double {
-        __syncthreads();
-        red[t] = v;
-        __syncthreads();
-        for (int s = 128; s > 0; s >>= 1) {
-            if (t < s) red[t] += red[t + s];
-            __syncthreads();
-        }
-        return red[0];
-    };
-    const double sv = block_sum(a_var);
+    const double sv = block_sum(t, a_var);
     if (t == 0) out[0] = sv;
 #pragma unroll
     for (int q = 0; q < KDC; ++q) {
         if (q < qcnt) {
-            const double sq = block_sum(a_q[q]);
+            const double sq = block_sum(t, a_q[q]);
             if (t == 0) out[2 + q] = sq;
         }
     }
@@ -2308,18 +1967,14 @@ static void launch_grad_lin(hipStream_t st, bool fused, KernParams kp, const dou
                             double* partials, double* Hout, long ldh, const double* aa_scale, const double* Mul, long ldm) {
     const int nb = pick_grad_blocks(ntiles);
     const dim3 g((unsigned)nb), b(256);
-    for (int q_off = 0, gidx = 0; q_off < kp.D; q_off += KDC, ++gidx) {
-        if (!kp.ard && gidx > 0) break;
-        double* pa = partials + (long)gidx * nb * GP_STRIDE;
-        // Hout may alias G (in place): only the LAST group launch writes it
-        double* h = (!kp.ard || q_off + KDC >= kp.D) ? Hout : nullptr;
+    for_each_group(kp.D, kp.ard != 0, nb, partials, Hout, [&](int q_off, double* pa, double* h) {
         if (fused)
             hipLaunchKernelGGL((k_grad_lin<true>), g, b, 0, st, kp, Xt1, ld1, n, Xt2, ld2, m, G, ldg, alpha, Dy, q_off, ntiles, ntc, pa,
-                               nullptr, 0, aa_scale, Mul, ldm);
+                               h, ldh, aa_scale, Mul, ldm);
         else
-            hipLaunchKernelGGL((k_grad_lin<false>), g, b, 0, st, kp, Xt1, ld1, n, Xt2, ld2, m, G, ldg, nullptr, 0, q_off, ntiles, ntc, pa,
-                               h, ldh, nullptr, Mul, ldm);
-    }
+            hipLaunchKernelGGL((k_grad_lin<false>), g, b, 0, st, kp, Xt1, ld1, n, Xt2, ld2, m, G, ldg, alpha, Dy, q_off, ntiles, ntc, pa,
+                               h, ldh, aa_scale, Mul, ldm);
+    });
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -2328,9 +1983,9 @@ static void launch_grad_lin(hipStream_t st, bool fused, KernParams kp, const dou
 // d_ij = sum_q x~_iq x~_jq, n_i = sum_q x~_iq^2 (both from the same staged slabs, kp.bias = b resp. c0):
 //   MLP   s = d + b, p_i = n_i + b:  K = var (2/pi) asin(s / sqrt((p_i + 1)(p_j + 1)))
 //   Poly  A = d + c0:                K = var A^order (kp.power; C pow for a negative A)
-// Kernels of their own again: every other instantiation keeps its code.  The sums over q run in the same order for (i, j) and
-// (j, i), fma(a, b, c) = fma(b, a, c) and (p_i + 1)(p_j + 1) commutes: K(X, X) is bitwise symmetric.  n_i is the same fma chain
-// as d_ii, so at i == j the element is the formula at s = p_i: var (2/pi) asin(p / sqrt((p + 1)^2)) = Kdiag.
+// Their own kernels around the shared skeleton: dot products (and MLP's norms) accumulate.  The sums over q run in the same
+// order for (i, j) and (j, i), fma(a, b, c) = fma(b, a, c) and (p_i + 1)(p_j + 1) commutes: K(X, X) is bitwise symmetric.  n_i is
+// the same fma chain as d_ii, so at i == j the element is the formula at s = p_i: var (2/pi) asin(p / sqrt((p + 1)^2)) = Kdiag.
 
 // ni[a] += sum_q xi[q][ty*4+a]^2, nj[b] += sum_q xj[q][tx*4+b]^2
 __device__ __forceinline__ void accum_norms(const double* si, const double* sj, int qc, int ty, int tx, double (&ni)[4],
@@ -2353,37 +2008,24 @@ __device__ __forceinline__ double mlp_k(double var, double s, double qi, double 
     return var * TWO_OVER_PI * asin(fmin(fmax(t, -1.0), 1.0));
 }
 
-// Covariance assembly of k_kbuild (same tiling, same output conventions).
+// Covariance assembly: the dot products, for MLP the squared norms of both sides as well.
 template <bool SYM, int KIND>
-__global__ __launch_bounds__(256) void k_kbuild_dot(KernParams kp, const double* __restrict__ Xt1, long ld1, long n,
-                                                    const double* __restrict__ Xt2, long ld2, long m,
-                                                    double* __restrict__ out, long ldo, long nrows_out,
-                                                    const double* __restrict__ noise, long noise_len, double jit,
-                                                    int lower_only, int add_diag, int ntc, int accumulate, const double* mul) {
+__global__ __launch_bounds__(256) void k_kbuild_dot(KbuildArgs A) {
     __shared__ __attribute__((aligned(16))) double si[KDC * KT];
     __shared__ __attribute__((aligned(16))) double sj[KDC * KTJ];
     const int t = threadIdx.x, tx = t & 15, ty = t >> 4;
-    const long ti = blockIdx.x / ntc, tj = blockIdx.x % ntc;
-    if (SYM && lower_only && tj > ti) return;
-    const long i0 = ti * KT, j0 = tj * KT;
+    long i0, j0;
+    if (!kbuild_tile<SYM>(A, i0, j0)) return;
     double s[4][4], ni[4], nj[4];
+    zero_tile(s);
 #pragma unroll
-    for (int a = 0; a < 4; ++a) {
-        ni[a] = nj[a] = 0.0;
-#pragma unroll
-        for (int b = 0; b < 4; ++b) s[a][b] = 0.0;
-    }
-    if ((i0 < n) && (j0 < m)) {
-        for (int q0 = 0; q0 < kp.D; q0 += KDC) {
-            const int qc = (kp.D - q0 < KDC) ? (kp.D - q0) : KDC;
-            __syncthreads();
-            stage_x(Xt1, ld1, i0, q0, qc, si, t);
-            stage_xj(Xt2, ld2, j0, q0, qc, sj, t);
-            __syncthreads();
+    for (int a = 0; a < 4; ++a) ni[a] = nj[a] = 0.0;
+    if (i0 < A.n && j0 < A.m)
+        for (int q0 = 0; q0 < A.kp.D; q0 += KDC) {
+            const int qc = stage_chunk(A.kp.D, q0, A.Xt1, A.ld1, i0, A.Xt2, A.ld2, j0, si, sj, t);
             accum_dot(si, sj, qc, ty, tx, s);
             if (KIND == MI355GP_MLP) accum_norms(si, sj, qc, ty, tx, ni, nj);
         }
-    }
 #pragma unroll
     for (int a = 0; a < 4; ++a) {
         const long i = i0 + ty * 4 + a;
@@ -2391,54 +2033,16 @@ __global__ __launch_bounds__(256) void k_kbuild_dot(KernParams kp, const double*
 #pragma unroll
         for (int b = 0; b < 4; ++b) {
             const long j = j0 + tx * 4 + b;
-            if (i < n && j < m) {
-                const double sb = s[a][b] + kp.bias;
-                if (KIND == MI355GP_MLP) v[b] = mlp_k(kp.variance, sb, ni[a] + kp.bias + 1.0, nj[b] + kp.bias + 1.0);
-                else v[b] = kp.variance * pow(sb, kp.power);
+            if (i < A.n && j < A.m) {
+                const double sb = s[a][b] + A.kp.bias;
+                if (KIND == MI355GP_MLP) v[b] = mlp_k(A.kp.variance, sb, ni[a] + A.kp.bias + 1.0, nj[b] + A.kp.bias + 1.0);
+                else v[b] = A.kp.variance * pow(sb, A.kp.power);
             } else {
-                v[b] = (SYM && i == j && !accumulate) ? 1.0 : 0.0;
+                v[b] = kbuild_pad<SYM>(A, i, j);
             }
         }
-        if (SYM) {
-            if (i < nrows_out) {
-                d4* p = reinterpret_cast<d4*>(out + i * ldo + j0 + tx * 4);
-                d4 o = (d4){v[0], v[1], v[2], v[3]};
-                if (mul) o *= *reinterpret_cast<const d4*>(mul + i * ldo + j0 + tx * 4);
-                if (add_diag && i < n) {
-                    const long d = i - (j0 + tx * 4);
-                    if (d >= 0 && d < 4) o[d] += noise[noise_len > 1 ? i : 0] + jit;
-                }
-                if (accumulate) o += *p;
-                *p = o;
-            }
-        } else if (i < n) {
-#pragma unroll
-            for (int b = 0; b < 4; ++b) {
-                const long j = j0 + tx * 4 + b;
-                if (j < m) {
-                    const double w = mul ? v[b] * mul[i * ldo + j] : v[b];
-                    out[i * ldo + j] = accumulate ? out[i * ldo + j] + w : w;
-                }
-            }
-        }
+        kbuild_store_row<SYM>(A, i, j0, tx, v);
     }
-}
-
-static void launch_kbuild_dot(hipStream_t st, bool sym, KernParams kp, const double* Xt1, long ld1, long n, const double* Xt2,
-                              long ld2, long m, double* out, long ldo, long nrows_out, const double* noise, long noise_len,
-                              double jit, int lower_only, int add_diag, int ntc, int nblocks, int accumulate, const double* mul) {
-    const dim3 g((unsigned)nblocks), b(256);
-#define KBUILD_DOT(S, K)                                                                                                        \
-    hipLaunchKernelGGL((k_kbuild_dot<S, K>), g, b, 0, st, kp, Xt1, ld1, n, Xt2, ld2, m, out, ldo, nrows_out, noise, noise_len, jit, \
-                       lower_only, add_diag, ntc, accumulate, mul)
-    if (kp.kind == MI355GP_MLP) {
-        if (sym) KBUILD_DOT(true, MI355GP_MLP);
-        else KBUILD_DOT(false, MI355GP_MLP);
-    } else {
-        if (sym) KBUILD_DOT(true, MI355GP_POLY);
-        else KBUILD_DOT(false, MI355GP_POLY);
-    }
-#undef KBUILD_DOT
 }
 
 // Gradient pass of k_grad for the two kinds, one launch per group of 32 dimensions (q_off; one launch unless MLP with ard).
@@ -2463,7 +2067,6 @@ __global__ __launch_bounds__(256) void k_grad_dot(KernParams kp, const double* _
     constexpr bool MLP = KIND == MI355GP_MLP;
     __shared__ __attribute__((aligned(16))) double si[KDC * KT];
     __shared__ __attribute__((aligned(16))) double sj[KDC * KTJ];
-    __shared__ double red[256];
     const int t = threadIdx.x, tx = t & 15, ty = t >> 4;
     double a_var = 0.0, a_b = 0.0, a_w = 0.0;
     double a_q[KDC];
@@ -2475,33 +2078,17 @@ __global__ __launch_bounds__(256) void k_grad_dot(KernParams kp, const double* _
 
     for (long tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
         long ti, tj;
-        if (FUSED) {   // lower-triangular enumeration
-            ti = (long)((sqrt(8.0 * (double)tile + 1.0) - 1.0) * 0.5);
-            while (ti * (ti + 1) / 2 > tile) --ti;
-            while ((ti + 1) * (ti + 2) / 2 <= tile) ++ti;
-            tj = tile - ti * (ti + 1) / 2;
-        } else {
-            ti = tile / ntc;
-            tj = tile - ti * ntc;
-        }
+        grad_tile<FUSED>(tile, ntc, ti, tj);
         const long i0 = ti * KT, j0 = tj * KT;
         double s[4][4], ni[4], nj[4];
+        zero_tile(s);
 #pragma unroll
-        for (int a = 0; a < 4; ++a) {
-            ni[a] = nj[a] = 0.0;
-#pragma unroll
-            for (int b = 0; b < 4; ++b) s[a][b] = 0.0;
-        }
+        for (int a = 0; a < 4; ++a) ni[a] = nj[a] = 0.0;
         int last_q0 = -1;
-        for (int q0 = 0; q0 < kp.D; q0 += KDC) {
-            const int qc = (kp.D - q0 < KDC) ? (kp.D - q0) : KDC;
-            __syncthreads();
-            stage_x(Xt1, ld1, i0, q0, qc, si, t);
-            stage_xj(Xt2, ld2, j0, q0, qc, sj, t);
-            __syncthreads();
+        for (int q0 = 0; q0 < kp.D; last_q0 = q0, q0 += KDC) {
+            const int qc = stage_chunk(kp.D, q0, Xt1, ld1, i0, Xt2, ld2, j0, si, sj, t);
             accum_dot(si, sj, qc, ty, tx, s);
             if (MLP) accum_norms(si, sj, qc, ty, tx, ni, nj);
-            last_q0 = q0;
         }
         // MLP: qi = p_i + 1, hi = 1 / (2 (p_i + 1)); padded rows have x~ = 0, so every quantity below stays finite there
         double qi[4], qj[4], hi[4], hj[4];
@@ -2524,21 +2111,7 @@ __global__ __launch_bounds__(256) void k_grad_dot(KernParams kp, const double* _
 #pragma unroll
             for (int b = 0; b < 4; ++b) {
                 const long j = j0 + tx * 4 + b;
-                double g = 0.0;
-                const bool in = i < n && j < m;
-                if (in) {
-                    if (FUSED) {
-                        if (j <= i) {
-                            double aa = 0.0;
-                            for (int d = 0; d < Dy; ++d) aa = fma(alpha[i * Dy + d], alpha[j * Dy + d], aa);
-                            g = 0.5 * (sc * aa - (double)Dy * G[i * ldg + j]);
-                            if (j < i) g *= 2.0;
-                        }
-                    } else {
-                        g = G[i * ldg + j];
-                    }
-                    if (Mul) g *= Mul[i * ldm + j];
-                }
+                const double g = grad_weight<FUSED, true>(i, j, n, m, G, ldg, alpha, Dy, sc, Mul, ldm);
                 const double sb = s[a][b] + kp.bias;
                 if (MLP) {
                     const double prod = qi[a] * qj[b];
@@ -2553,9 +2126,9 @@ __global__ __launch_bounds__(256) void k_grad_dot(KernParams kp, const double* _
                         a_w += fma(-cs, ni[a] * hi[a] + nj[b] * hj[b], c * s[a][b]);
                     }
                     cw[a][b] = c;
-                    if (!FUSED && Hout && in) Hout[i * ldh + j] = c;
+                    if (!FUSED && Hout) store_h<false>(Hout, ldh, i, j, n, m, c, c);
                 } else {
-                    const double pm1 = in ? pow(sb, kp.power - 1.0) : 0.0;
+                    const double pm1 = (i < n && j < m) ? pow(sb, kp.power - 1.0) : 0.0;
                     const double h = coef * g * pm1;
                     a_var = fma(g, kp.variance * pm1 * sb, a_var);
                     a_b += h;
@@ -2569,12 +2142,7 @@ __global__ __launch_bounds__(256) void k_grad_dot(KernParams kp, const double* _
                 rsum[a] *= hi[a];
                 csum[a] *= hj[a];
             }
-            if (last_q0 != q_off) {   // D > 32: bring the dims of this launch back into LDS
-                __syncthreads();
-                stage_x(Xt1, ld1, i0, q_off, qcnt, si, t);
-                stage_xj(Xt2, ld2, j0, q_off, qcnt, sj, t);
-                __syncthreads();
-            }
+            restage(last_q0, q_off, qcnt, Xt1, ld1, i0, Xt2, ld2, j0, si, sj, t);
 #pragma unroll
             for (int q = 0; q < KDC; ++q) {
                 if (q < qcnt) {
@@ -2597,28 +2165,18 @@ __global__ __launch_bounds__(256) void k_grad_dot(KernParams kp, const double* _
     }
     // deterministic block reduction -> partials[blockIdx][...]
     double* out = partials + (long)blockIdx.x * GP_STRIDE;
-    auto block_sum = [&](double v) -> double {
-        __syncthreads();
-        red[t] = v;
-        __syncthreads();
-        for (int s = 128; s > 0; s >>= 1) {
-            if (t < s) red[t] += red[t + s];
-            __syncthreads();
-        }
-        return red[0];
-    };
-    const double sv = block_sum(a_var);
+    const double sv = block_sum(t, a_var);
     if (t == 0) out[0] = sv;
-    const double sb = block_sum(a_b);
+    const double sb = block_sum(t, a_b);
     if (t == 0) out[1] = sb;
     if (qcnt == 0) {
-        const double sw = block_sum(a_w);
+        const double sw = block_sum(t, a_w);
         if (t == 0) out[2] = sw;
     }
 #pragma unroll
     for (int q = 0; q < KDC; ++q) {
         if (q < qcnt) {
-            const double sq = block_sum(a_q[q]);
+            const double sq = block_sum(t, a_q[q]);
             if (t == 0) out[2 + q] = sq;
         }
     }
@@ -2629,29 +2187,105 @@ static void launch_grad_dot(hipStream_t st, bool fused, KernParams kp, const dou
                             double* partials, double* Hout, long ldh, const double* aa_scale, const double* Mul, long ldm) {
     const int nb = pick_grad_blocks(ntiles);
     const dim3 g((unsigned)nb), b(256);
-    const bool mlp = kp.kind == MI355GP_MLP, groups = mlp && kp.ard;
-    for (int q_off = 0, gidx = 0; q_off < kp.D; q_off += KDC, ++gidx) {
-        if (!groups && gidx > 0) break;
-        double* pa = partials + (long)gidx * nb * GP_STRIDE;
-        // Hout may alias G (in place): only the LAST group launch writes it
-        double* h = (!groups || q_off + KDC >= kp.D) ? Hout : nullptr;
-#define GRAD_DOT(F, K, AL, DY, HO, LH, AS)                                                                                       \
-    hipLaunchKernelGGL((k_grad_dot<F, K>), g, b, 0, st, kp, Xt1, ld1, n, Xt2, ld2, m, G, ldg, AL, DY, q_off, ntiles, ntc, pa, HO, LH, \
-                       AS, Mul, ldm)
+    const bool mlp = kp.kind == MI355GP_MLP;
+    for_each_group(kp.D, mlp && kp.ard, nb, partials, Hout, [&](int q_off, double* pa, double* h) {
+#define GRAD_DOT(F, K)                                                                                                           \
+    hipLaunchKernelGGL((k_grad_dot<F, K>), g, b, 0, st, kp, Xt1, ld1, n, Xt2, ld2, m, G, ldg, alpha, Dy, q_off, ntiles, ntc, pa, \
+                       h, ldh, aa_scale, Mul, ldm)
         if (mlp) {
-            if (fused) GRAD_DOT(true, MI355GP_MLP, alpha, Dy, nullptr, 0, aa_scale);
-            else GRAD_DOT(false, MI355GP_MLP, nullptr, 0, h, ldh, nullptr);
+            if (fused) GRAD_DOT(true, MI355GP_MLP);
+            else GRAD_DOT(false, MI355GP_MLP);
         } else {
-            if (fused) GRAD_DOT(true, MI355GP_POLY, alpha, Dy, nullptr, 0, aa_scale);
-            else GRAD_DOT(false, MI355GP_POLY, nullptr, 0, nullptr, 0, nullptr);
+            if (fused) GRAD_DOT(true, MI355GP_POLY);
+            else GRAD_DOT(false, MI355GP_POLY);
         }
 #undef GRAD_DOT
+    });
+}
+
+// ------------------------------------------------------------------------------------------------
+// The launch functions of the assembly and gradient kernels: each prepares its geometry, one dispatch picks the kind's kernel.
+template <bool SYM>
+static void launch_kbuild(hipStream_t st, long nblocks, const KbuildArgs& A) {
+    const dim3 g((unsigned)nblocks), b(256);
+    switch (A.kp.kind) {
+    case MI355GP_RATQUAD: hipLaunchKernelGGL((k_kbuild_ext<SYM, MI355GP_RATQUAD>), g, b, 0, st, A); break;
+    case MI355GP_STDPERIODIC: hipLaunchKernelGGL((k_kbuild_ext<SYM, MI355GP_STDPERIODIC>), g, b, 0, st, A); break;
+    case MI355GP_COREGIONALIZE: hipLaunchKernelGGL((k_kbuild_coreg<SYM>), g, b, 0, st, A); break;
+    case MI355GP_LINEAR: hipLaunchKernelGGL((k_kbuild_lin<SYM>), g, b, 0, st, A); break;
+    case MI355GP_MLP: hipLaunchKernelGGL((k_kbuild_dot<SYM, MI355GP_MLP>), g, b, 0, st, A); break;
+    case MI355GP_POLY: hipLaunchKernelGGL((k_kbuild_dot<SYM, MI355GP_POLY>), g, b, 0, st, A); break;
+    default:
+        hipLaunchKernelGGL((k_kbuild<SYM>), g, b, 0, st, A.kp, A.Xt1, A.ld1, A.n, A.Xt2, A.ld2, A.m, A.out, A.ldo, A.nrows_out, A.noise,
+                           A.noise_len, A.jit, A.lower_only, A.add_diag, A.ntc, A.accumulate, A.diag_same, A.mul);
+        break;
     }
+}
+
+void launch_kbuild_sym(hipStream_t st, KernParams kp, const double* Xt, long ldx, long n, long npad, double* A,
+                       const double* noise, long noise_len, double jit, int lower_only, int add_diag, int accumulate,
+                       const double* mul) {
+    const int nt = (int)(npad / KT);
+    launch_kbuild<true>(st, (long)nt * nt, KbuildArgs{kp, Xt, ldx, n, Xt, ldx, n, A, npad, npad, noise, noise_len, jit, lower_only,
+                                                      add_diag, nt, accumulate, 0, mul});
+}
+
+void launch_kbuild_cross(hipStream_t st, KernParams kp, const double* Xt1, long ld1, long n, const double* Xt2,
+                         long ld2, long m, double* Kout, long ldk, int accumulate, int diag_same, const double* mul) {
+    const int ntr = (int)((n + KT - 1) / KT), ntc = (int)((m + KT - 1) / KT);
+    launch_kbuild<false>(st, (long)ntr * ntc, KbuildArgs{kp, Xt1, ld1, n, Xt2, ld2, m, Kout, ldk, n, nullptr, 0, 0.0, 0, 0, ntc,
+                                                         accumulate, diag_same, mul});
+}
+
+// fused: over the lower tiles of W (n x n); else over the ntiles = ntr * ntc tiles of G.  The sparse path's rank term (rk) is
+// the stationary kernel's alone: that path has no other kind.
+static void launch_grad(hipStream_t st, bool fused, KernParams kp, const double* Xt1, long ld1, long n, const double* Xt2, long ld2,
+                        long m, int diag_same, const double* G, long ldg, const double* alpha, int Dy, long ntiles, int ntc,
+                        double* partials, double* Hout, long ldh, const double* aa_scale, const double* Mul, long ldm,
+                        RankTerm rk) {
+    if (kp.kind == MI355GP_COREGIONALIZE) return;          // (launch_grad_coreg: records of its own shape)
+    if (kp.kind >= MI355GP_RATQUAD) {
+        if (rk.Y) return;
+        const bool dot = kp.kind == MI355GP_MLP || kp.kind == MI355GP_POLY;
+        auto family = dot ? launch_grad_dot : kp.kind == MI355GP_LINEAR ? launch_grad_lin : launch_grad_ext;
+        family(st, fused, kp, Xt1, ld1, n, Xt2, ld2, m, G, ldg, alpha, Dy, ntiles, ntc, partials, Hout, ldh, aa_scale, Mul, ldm);
+        return;
+    }
+    const dim3 g((unsigned)pick_grad_blocks(ntiles)), b(256);
+    for_each_group(kp.D, kp.ard != 0, (int)g.x, partials, Hout, [&](int q_off, double* pa, double* h) {
+#define GRAD(F, A)                                                                                                              \
+    hipLaunchKernelGGL((k_grad<F, A>), g, b, 0, st, kp, Xt1, ld1, n, Xt2, ld2, m, G, ldg, alpha, Dy, q_off, ntiles, ntc, pa, h, ldh, \
+                       diag_same, aa_scale, Mul, ldm, rk)
+        if (fused) {
+            if (kp.ard) GRAD(true, true);
+            else GRAD(true, false);
+        } else {
+            if (kp.ard) GRAD(false, true);
+            else GRAD(false, false);
+        }
+#undef GRAD
+    });
+}
+
+void launch_grad_fused(hipStream_t st, KernParams kp, const double* Xt, long ldx, long n, const double* W,
+                       long ldw, const double* alpha, int Dy, double* partials, const double* aa_scale,
+                       const double* Mul, long ldm) {
+    const long nt = (n + KT - 1) / KT;
+    launch_grad(st, true, kp, Xt, ldx, n, Xt, ldx, n, 0, W, ldw, alpha, Dy, nt * (nt + 1) / 2, (int)nt, partials, nullptr, 0,
+                aa_scale, Mul, ldm, RankTerm{nullptr, nullptr, 0, 0.0, 1.0, nullptr});
+}
+
+void launch_grad_generic(hipStream_t st, KernParams kp, const double* Xt1, long ld1, long n, const double* Xt2,
+                         long ld2, long m, int symmetric, const double* G, long ldg, double* partials,
+                         double* Hout, long ldh, RankTerm rk) {
+    const long ntr = (n + KT - 1) / KT, ntc = (m + KT - 1) / KT;
+    launch_grad(st, false, kp, Xt1, ld1, n, Xt2, ld2, m, symmetric, G, ldg, nullptr, 0, ntr * ntc, (int)ntc, partials, Hout, ldh,
+                nullptr, nullptr, 0, rk);
 }
 
 // ------------------------------------------------------------------------------------------------
 // Laplace approximation (GPy/inference/latent_function_inference/laplace.py): the three passes over the resident K = kern.K(X)
-// that one mode search and its gradients need.  Kernels of their own: the instantiations above keep their code.
+// that one mode search and its gradients need.  They share nothing with the assembly kernels above but the tile size.
 //
 // B = I + diag(sw) K diag(sw) (laplace.py:333-334), sw = sqrt(W), lower 64-tiles into A (npad x npad); identity in the
 // padding; `jit` (the jitchol ladder term) on the diagonal.  One read and one 32-byte store per four elements.

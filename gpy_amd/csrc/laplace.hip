@@ -285,7 +285,7 @@ int mi355gp_laplace_gradients(mi355gp_ctx* c, const double* Ki_f, const double* 
             launch_reduce_partials(st, L->coregPart, nbc, P * P, c->dPack + c->offCoreg + p * COREG_REC);
             continue;
         }
-        launch_grad_generic(st, pt.kp, pt.dXt, np, n, pt.dXt, np, n, /*symmetric=*/1, G, np, c->dGradPart, GP_STRIDE);
+        launch_grad_generic(st, pt.kp, pt.dXt, np, n, pt.dXt, np, n, /*symmetric=*/1, G, np, c->dGradPart);
         for (int r = 0; r < (pt.ext() ? 2 : 1); ++r)
             for (int g = 0; g < (pt.kp.ard ? groups : 1); ++g)
                 launch_reduce_partials(st, c->dGradPart + ((long)r * groups + g) * nb * GP_STRIDE, nb, GP_STRIDE,

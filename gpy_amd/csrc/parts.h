@@ -9,7 +9,6 @@
 #include "../../include/mi355gp.h"
 #include "internal.h"
 
-#define GP_STRIDE 34           // doubles of one reduction record: [0] variance sum, [1] lengthscale sum, [2 + q % 32] per dimension
 #define COREG_REC 256          // doubles of one Coregionalize part's S (P x P, P <= 16)
 
 // the sums of dimension q in the records of one part (one GP_STRIDE record per group of 32 dimensions)

@@ -681,7 +681,7 @@ static void sparse_kmm_gradients(mi355gp_sparse* s) {
             launch_kbuild_cross(st, pf.kp, pf.XtZ, mp, m, pf.XtZ, mp, m, dst, mp, 0, /*diag_same=*/1, mul);
         });
         if (prod) hipLaunchKernelGGL(k_mm_mul, grid2d(mp, mp), dim3(256), 0, st, s->T1, s->dLdKmm, mp);
-        launch_grad_generic(st, p.kp, p.XtZ, mp, m, p.XtZ, mp, m, 1, prod ? s->T1 : s->dLdKmm, mp, s->gradPart, GP_STRIDE,
+        launch_grad_generic(st, p.kp, p.XtZ, mp, m, p.XtZ, mp, m, 1, prod ? s->T1 : s->dLdKmm, mp, s->gradPart,
                             p.stationary() ? s->T1 : nullptr, mp);
         for (int g = 0; g < (p.kp.ard ? groups : 1); ++g)
             launch_reduce_partials(st, s->gradPart + (long)g * nbk * GP_STRIDE, nbk, GP_STRIDE, p.gradMM + (long)g * GP_STRIDE);
@@ -868,7 +868,7 @@ int mi355gp_vardtc_inference_sum(mi355gp_sparse* s, int nparts, const mi355gp_pa
                 hipLaunchKernelGGL(k_form_dLdKnm_times, dim3((unsigned)rcp, (unsigned)((mp + 255) / 256)), dim3(256), 0, st, s->T,
                                    s->Kfu, mp, rc, rcp, m, s->dY + r0 * Dy, s->vvec, Dy, s->dBeta + r0);
                 nbk = grad_generic_num_blocks(rc, m);
-                launch_grad_generic(st, p.kp, p.XtC, chunk, rc, p.XtZ, mp, m, 0, s->Kfu, mp, s->gradPart, GP_STRIDE,
+                launch_grad_generic(st, p.kp, p.XtC, chunk, rc, p.XtZ, mp, m, 0, s->Kfu, mp, s->gradPart,
                                     p.stationary() ? s->Kfu : nullptr, mp);         // H over the weights, in place
                 if (p.stationary()) ns = launch_colreduce_multi(st, s->Kfu, mp, rc, mp, p.XtC, 1, chunk, D, 1, s->colPart);
             } else {
@@ -877,7 +877,7 @@ int mi355gp_vardtc_inference_sum(mi355gp_sparse* s, int nparts, const mi355gp_pa
                 if (ns == 0) {
                     nbk = grad_generic_num_blocks(rc, m);
                     double* Hbuf = p.stationary() ? s->Kfu : nullptr;
-                    launch_grad_generic(st, p.kp, p.XtC, chunk, rc, p.XtZ, mp, m, 0, s->T, mp, s->gradPart, GP_STRIDE, Hbuf, mp, rk);
+                    launch_grad_generic(st, p.kp, p.XtC, chunk, rc, p.XtZ, mp, m, 0, s->T, mp, s->gradPart, Hbuf, mp, rk);
                     if (p.stationary()) ns = launch_colreduce_multi(st, s->Kfu, mp, rc, mp, p.XtC, 1, chunk, D, 1, s->colPart);
                 }
             }
