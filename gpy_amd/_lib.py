@@ -176,6 +176,9 @@ def lib():
     L.mi355gp_sparse_predict.argtypes = [vp, ci, ctypes.POINTER(Part), _dp, i64, _c_dp, _c_dp, ci]
     L.mi355gp_sparse_fetch_dLdKnm.argtypes = [vp, i64, i64, _dp]
     L.mi355gp_sparse_attach_loopback.argtypes = [vp, ci, ci, ci]
+    L.mi355gp_svgp_forward.argtypes = [vp, ci, ctypes.POINTER(Part), _dp, i64, _dp, _dp, ci, cd, _dp, _dp, _dp, _c_dp]
+    L.mi355gp_svgp_backward.argtypes = [vp, _dp, _dp, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp]
+    L.mi355gp_svgp_predict.argtypes = [vp, ci, ctypes.POINTER(Part), _c_dp, i64, ci, _c_dp, _c_dp, _c_dp, _c_dp]
     L.mi355gp_sparse_attach_comm.argtypes = [vp, ci, ci, ctypes.c_char_p]
     L.mi355gp_rbf_psi.argtypes = [ci, cd, _dp, ci, _dp, i64, _dp, _dp, i64, ci, _c_dp, _c_dp, _c_dp]
     L.mi355gp_rbf_psi_grad.argtypes = [ci, cd, _dp, ci, _dp, i64, _dp, _dp, i64, ci, _c_dp, _c_dp, _c_dp, _c_dp, _dp, _dp, _dp,
@@ -205,7 +208,8 @@ def lib():
                  "sparse_get_profile", "dbg_persist", "dbg_grid_multi", "dbg_update_nt", "dbg_update_rect",
                  "dbg_ipc_selftest", "laplace_begin", "laplace_newton", "laplace_finish", "laplace_gradients",
                  "laplace_implicit", "laplace_predict", "ep_recompute", "ep_sweep", "rbf_psi", "rbf_psi_grad",
-                 "sparse_set_input_variance", "vardtc_inference_uncertain"):
+                 "sparse_set_input_variance", "vardtc_inference_uncertain", "svgp_forward", "svgp_backward",
+                 "svgp_predict"):
         getattr(L, "mi355gp_" + name).restype = ci
     _lib = L
     return L
@@ -230,7 +234,7 @@ EXPORTED = ("mi355gp_last_error", "mi355gp_version", "mi355gp_device_count", "mi
             "mi355gp_laplace_begin", "mi355gp_laplace_newton", "mi355gp_laplace_finish", "mi355gp_laplace_gradients",
             "mi355gp_laplace_implicit", "mi355gp_laplace_predict", "mi355gp_ep_recompute", "mi355gp_ep_sweep",
             "mi355gp_rbf_psi", "mi355gp_rbf_psi_grad", "mi355gp_sparse_set_input_variance",
-            "mi355gp_vardtc_inference_uncertain")
+            "mi355gp_vardtc_inference_uncertain", "mi355gp_svgp_forward", "mi355gp_svgp_backward", "mi355gp_svgp_predict")
 
 
 # mi355gp_set_option / mi355gp_get_option ids (include/mi355gp.h, MI355GP_OPT_*)
@@ -658,6 +662,67 @@ class SparseContext(object):
         out = np.empty((nrows, self.M))
         check(lib().mi355gp_sparse_fetch_dLdKnm(self._h, int(row0), int(nrows), out), "mi355gp_sparse_fetch_dLdKnm")
         return out
+
+    # ---- SVGP: forward -> the likelihood's quadrature on the host -> backward (svgp.hip) ------------------------------------
+    def svgp_forward(self, specs, Z, q_mean, q_chol, extra_jitter=0.0, want_stage_ms=False):
+        """q_mean: M x L; q_chol: L x M x M lower-triangular factors.  (info, dict(mu (N x L), v (N x L), KL, logdet_Kmm,
+        logdet_S (L)[, stage_ms])); info > 0: Kmm is not positive definite, retry with `extra_jitter`."""
+        arr, keep, ntheta = make_parts(specs)
+        Z, q_mean, q_chol = f64(Z), f64(q_mean), f64(q_chol)
+        self.M = Z.shape[0]
+        assert Z.shape[1] == self.D
+        assert q_mean.ndim == 2 and q_mean.shape[0] == self.M, "q_mean must be M x L"
+        L = q_mean.shape[1]
+        assert q_chol.shape == (L, self.M, self.M), "q_chol must be L x M x M"
+        self.L, self._svgp_ntheta = L, ntheta
+        mu, v = np.zeros((self.N, L)), np.zeros((self.N, L))
+        sc = np.zeros(2 + L)
+        ms = np.zeros(3) if want_stage_ms else None
+        rc = check(lib().mi355gp_svgp_forward(self._h, len(specs), arr, Z, self.M, q_mean, q_chol, L, float(extra_jitter), mu, v,
+                                              sc, _opt(ms)), "mi355gp_svgp_forward")
+        res = dict(mu=mu, v=v, KL=sc[0], logdet_Kmm=sc[1], logdet_S=sc[2:2 + L].copy())
+        if ms is not None:
+            res["stage_ms"] = dict(mxm=ms[0], rows=ms[1], total=ms[2])
+        return rc, res
+
+    def svgp_backward(self, dF_dmu, dF_dv, want_stage_ms=False):
+        """dF_dmu, dF_dv: N x L, already times batch_scale.  dict(dtheta (concatenated), dZ, dL_dm (M x L), dL_dchol
+        (L x M x M, lower triangles)[, stage_ms]) after `svgp_forward` on the same data."""
+        L = getattr(self, "L", 0)
+        dF_dmu, dF_dv = f64(dF_dmu), f64(dF_dv)
+        if L:
+            assert dF_dmu.shape == (self.N, L) and dF_dv.shape == (self.N, L), "dF_dmu and dF_dv must be N x L"
+        dtheta = np.zeros(getattr(self, "_svgp_ntheta", 0))
+        dZ, dm, dchol = np.zeros((self.M, self.D)), np.zeros((self.M, L)), np.zeros((L, self.M, self.M))
+        ms = np.zeros(3) if want_stage_ms else None
+        check(lib().mi355gp_svgp_backward(self._h, dF_dmu, dF_dv, _opt(dtheta), _opt(dZ), _opt(dm), _opt(dchol), _opt(ms)),
+              "mi355gp_svgp_backward")
+        res = dict(dtheta=dtheta, dZ=dZ, dL_dm=dm, dL_dchol=dchol)
+        if ms is not None:
+            res["stage_ms"] = dict(rows=ms[0], mxm=ms[1], total=ms[2])
+        return res
+
+    def svgp_predict(self, specs, Xnew, full_cov=False, want_var=True):
+        """(mu (M* x L), var (M* x L) or cov (M* x M* x L) or None) of the SVGP posterior of the last `svgp_forward`."""
+        arr, keep, _ = make_parts(specs)
+        Xnew = f64(Xnew)
+        Mn, L = Xnew.shape[0], getattr(self, "L", 1)
+        assert Xnew.shape[1] == self.D
+        mu = np.empty((Mn, L))
+        var = (np.empty((Mn, Mn, L)) if full_cov else np.empty((Mn, L))) if want_var else None
+        check(lib().mi355gp_svgp_predict(self._h, len(specs), arr, Xnew.ctypes.data_as(_c_dp), Mn, int(bool(full_cov)),
+                                         mu.ctypes.data_as(_c_dp), _opt(var), None, None), "mi355gp_svgp_predict")
+        return mu, var
+
+    def svgp_woodbury(self, want_inv=True):
+        """(woodbury_vector = Kmm^-1 m (M x L), woodbury_inv (M x M x L, the reference's axis order) or None) of the last
+        `svgp_forward`"""
+        L = getattr(self, "L", 1)
+        wv = np.empty((self.M, L))
+        wi = np.empty((L, self.M, self.M)) if want_inv else None
+        check(lib().mi355gp_svgp_predict(self._h, 0, None, None, 0, 0, None, None, wv.ctypes.data_as(_c_dp), _opt(wi)),
+              "mi355gp_svgp_predict")
+        return wv, (None if wi is None else np.ascontiguousarray(np.transpose(wi, (1, 2, 0))))
 
 
 def kern_K(kind, ARD, theta, X, X2=None, device=0):

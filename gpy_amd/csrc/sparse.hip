@@ -21,6 +21,7 @@
 #include "internal.h"
 #include "parts.h"
 #include "psi.h"
+#include "sparse_ctx.h"
 
 #define SPLITK_MAX 16
 #define CHUNK_MAX 262144                    // rows per chunk: 2 x (chunk x Mp) doubles of HBM (8.6 GB at M = 2048)
@@ -188,61 +189,16 @@ static int loop_allreduce(LoopGroup* G, int rank, double* buf, size_t count, hip
     return 0;
 }
 
-struct SPart : DevicePart {
-    DevBuf XtZ, XtC, HX, HZ, gradNM, gradMM;
-};
-
-struct mi355gp_sparse {
-    // MI355GP_SPARSE_KMM_OVERLAP: Kmm's build + Cholesky + inverse (they need only Z) on a side stream UNDERNEATH pass 1 when the
-    // factorisation is the single persistent launch (~1.2 ms of latency-bound work that otherwise runs on an idle GPU)
-    int kmm_overlap = 1;
-    hipStream_t st_kmm = nullptr;
-    hipEvent_t ev_z = nullptr, ev_kmm = nullptr;
-    int fuse_cols = 1;            // MI355GP_SPARSE_FUSE_COLS: k_grad_cols (gradient pass + column reductions in one)
-    int device = 0;
-    hipStream_t st = nullptr;
-    long n = 0, chunk = 0;
-    int D = 0, Dy = 0, splitk = 8;
-    double trYYT = 0.0, trYYT_local = 0.0;
-    std::vector<double> rowYY;    // host: |R_n|^2 per row (heteroscedastic log likelihood)
-    // row-sharded multi-GPU mode (the reference's MPI design: var_dtc_parallel.py:121-130,387-394):
-    // this rank holds n of n_global rows; psi2 / psi1Y and the pass-2 sums are all-reduced, M x M algebra is replicated
-    void* comm = nullptr;         // RCCL communicator
-    LoopGroup* loop = nullptr;    // or the loopback rendezvous
-    int world = 1, rank = 0;
-    long n_global = 0;
-    double* dSvar = nullptr;      // N x D input variances (mi355gp_sparse_set_input_variance): X is then the mean of q(x_n)
-    bool uncertain_result = false; // the last result came from mi355gp_vardtc_inference_uncertain (no dL_dKnm then)
-    double *dX = nullptr, *dY = nullptr, *dV = nullptr, *dBeta = nullptr, *dRowS = nullptr, *dRowT = nullptr, *dRowR = nullptr,
-           *Kfu = nullptr,
-           *T = nullptr;
-    // M-dependent
-    long m = 0, mp = 0;
-    double *dZ = nullptr, *zero1 = nullptr;
-    double *Lm = nullptr, *Xm = nullptr, *Tm = nullptr, *psi2part = nullptr, *psi2 = nullptr, *Amat = nullptr,
-           *LB = nullptr, *XB = nullptr, *Bi = nullptr, *P = nullptr, *E = nullptr, *T1 = nullptr, *Q2 = nullptr,
-           *dLdKmm = nullptr, *Winv = nullptr;
-    double *psi1Y = nullptr, *vecA = nullptr, *vecB = nullptr, *cvec = nullptr, *wvec = nullptr, *vvec = nullptr,
-           *trmvPart = nullptr, *colPart = nullptr, *gradPart = nullptr, *gradChunk = nullptr, *scal = nullptr,
-           *redbuf = nullptr;
-    std::vector<SPart> parts;
-    Terms terms;                  // part indices per summand, in order of first appearance (one part, or the factors of a Prod)
-    FactorWs ws;
-    bool ws_ok = false, have_result = false, winv_ok = false;
-    hipEvent_t ev[6] = {};
-    int h_info[2] = {0, 0};       // LAPACK-style info of the two M x M factorisations (targets of async copies: not on the stack)
-    double beta_scalar = 0.0;     // homoscedastic precision of the last call (0: per-point)
-    KernelProf mfma_prof;         // launch timing of the two MFMA kernels of a call: family 0 = T = Kfu dL_dpsi2, 1 = split-K Gram
-};
 
 static int sparse_allreduce(mi355gp_sparse* s, double* buf, size_t count) {
     if (s->comm) return rccl_allreduce_sum(s->comm, buf, count, s->st);
     if (s->loop) return loop_allreduce(s->loop, s->rank, buf, count, s->st);
     return 0;
 }
-static bool sharded(const mi355gp_sparse* s) { return s->comm != nullptr || s->loop != nullptr; }
+bool sharded(const mi355gp_sparse* s) { return s->comm != nullptr || s->loop != nullptr; }
 
 static void free_m(mi355gp_sparse* s) {
+    svgp_release(s);
     s->parts.clear();
     double** ptrs[] = {&s->dZ, &s->zero1, &s->Lm, &s->Xm, &s->Tm, &s->psi2part, &s->psi2, &s->Amat,
                        &s->LB, &s->XB, &s->Bi, &s->P, &s->E, &s->T1, &s->Q2, &s->dLdKmm, &s->Winv, &s->psi1Y, &s->vecA,
@@ -255,10 +211,10 @@ static void free_m(mi355gp_sparse* s) {
     if (s->ws_ok) factor_ws_free(&s->ws);
     s->ws_ok = false;
     s->m = s->mp = 0;
-    s->have_result = s->winv_ok = false;
+    s->have_result = s->winv_ok = s->svgp_result = false;
 }
 
-static int alloc_m(mi355gp_sparse* s, long M) {
+int alloc_m(mi355gp_sparse* s, long M) {
     free_m(s);
     s->m = M;
     s->mp = round_up(M, NB);
@@ -306,7 +262,7 @@ static int alloc_m(mi355gp_sparse* s, long M) {
 }
 
 // (re)builds the part list of a call; the device buffers of a part are kept while the number of parts is unchanged
-static int prepare_sparse_parts(mi355gp_sparse* s, int nparts, const mi355gp_part* parts) {
+int prepare_sparse_parts(mi355gp_sparse* s, int nparts, const mi355gp_part* parts) {
     ARG_CHECK(nparts >= 1 && nparts <= 16 && parts, "between 1 and 16 kernel parts");
     const long mp = s->mp, D = s->D;
     const int groups = (int)((D + 31) / 32);
@@ -339,33 +295,33 @@ static int prepare_sparse_parts(mi355gp_sparse* s, int nparts, const mi355gp_par
 }
 
 // product of the OTHER factors' variances of part p's summand (= dKdiag/dvariance_p; 1 for a plain summand)
-static double sparse_other_variances(const mi355gp_sparse* s, size_t p) {
+double sparse_other_variances(const mi355gp_sparse* s, size_t p) {
     double v = 1.0;
     for (int f : s->terms[(size_t)s->parts[p].tix])
         if ((size_t)f != p) v *= s->parts[(size_t)f].kp.variance;
     return v;
 }
 // cross-covariances leave out summands that are a White part alone (White contributes nothing off the diagonal, static.py:77-81)
-static bool skip_white(const mi355gp_sparse* s, const std::vector<int>& t) {
+bool skip_white(const mi355gp_sparse* s, const std::vector<int>& t) {
     return t.size() == 1 && s->parts[(size_t)t[0]].kp.kind == MI355GP_WHITE;
 }
 
 // scaled, dimension-major copies of `rows` points (row-major src) for every part
-static void scale_for_parts(mi355gp_sparse* s, const double* src, long rows, long ldt, bool inducing) {
+void scale_for_parts(mi355gp_sparse* s, const double* src, long rows, long ldt, bool inducing) {
     for (SPart& p : s->parts) launch_scale_inputs(s->st, src, rows, s->D, p.dIl, 1, inducing ? p.XtZ : p.XtC, ldt);
 }
 // the inducing inputs as one side of a cross-covariance (emit_cross)
-static Resident<SPart> inducing_points(const mi355gp_sparse* s) { return {&SPart::XtZ, s->mp, s->m}; }
+Resident<SPart> inducing_points(const mi355gp_sparse* s) { return {&SPart::XtZ, s->mp, s->m}; }
 
 // Kfu chunk = sum over summands of (the product of) K_p(X_chunk, Z)  (add.py:58-72, prod.py:58-65; White contributes nothing
 // off the diagonal, static.py:77-81).  Products are multiplied up in `scratch` (chunk x mp, e.g. the T buffer).
-static void build_cross_chunk(mi355gp_sparse* s, long rc, double* out, double* scratch) {
+void build_cross_chunk(mi355gp_sparse* s, long rc, double* out, double* scratch) {
     const bool any = emit_cross(s->st, s->parts, s->terms, Resident<SPart>{&SPart::XtC, s->chunk, rc}, inducing_points(s), out, s->mp,
                                 scratch, false, 0, [&](const std::vector<int>& t) { return skip_white(s, t); });
     if (!any) (void)hipMemsetAsync(out, 0, sizeof(double) * rc * s->mp, s->st);       // only White parts: K(X, Z) = 0
 }
 // K(Z) (lower tiles; diag != NULL: + diag on the diagonal) of the expression into out (mp x mp), scratch mp x mp
-static void build_kmm(mi355gp_sparse* s, double* out, double* scratch, double jitter, int lower_only, hipStream_t st = nullptr) {
+void build_kmm(mi355gp_sparse* s, double* out, double* scratch, double jitter, int lower_only, hipStream_t st) {
     if (!st) st = s->st;
     emit_expression(s->terms, out, scratch, false, [&](int p, double* dst, const double* mul, int acc, bool first) {
         const SPart& pt = s->parts[(size_t)p];
@@ -527,7 +483,7 @@ int mi355gp_sparse_set_input_variance(mi355gp_sparse* s, const double* S, int64_
     HIP_CHECK(hipStreamSynchronize(s->st));
     if (!s->dSvar) HIP_CHECK(hipMalloc(&s->dSvar, sizeof(double) * N * D));
     HIP_CHECK(hipMemcpy(s->dSvar, S, sizeof(double) * N * D, hipMemcpyHostToDevice));
-    s->have_result = s->winv_ok = false;
+    s->have_result = s->winv_ok = s->svgp_result = false;
     return 0;
 }
 
@@ -609,8 +565,8 @@ static int factor_check(hipStream_t st, double* A, double* X, double* T, double*
     *info_host = info;
     return 0;
 }
-static int potrf_checked(hipStream_t st, double* A, double* X, double* T, double* W, long mp, FactorWs* ws, int* info_host,
-                         const std::function<void()>& rebuild) {
+int potrf_checked(hipStream_t st, double* A, double* X, double* T, double* W, long mp, FactorWs* ws, int* info_host,
+                  const std::function<void()>& rebuild) {
     if (int rc = factor_launch(st, A, X, T, W, mp, ws)) return rc;
     return factor_check(st, A, X, T, W, mp, ws, info_host, rebuild);
 }
@@ -667,7 +623,7 @@ static int sparse_mm_block(mi355gp_sparse* s, bool het, double beta, int inject)
 }
 
 // update_gradients_full(dL_dKmm, Z) and gradients_X(dL_dKmm, Z) of every part into its gradMM records and HZ
-static void sparse_kmm_gradients(mi355gp_sparse* s) {
+void sparse_kmm_gradients(mi355gp_sparse* s) {
     hipStream_t st = s->st;
     const long m = s->m, mp = s->mp;
     const int D = s->D, groups = (D + 31) / 32;
@@ -738,7 +694,7 @@ int mi355gp_vardtc_inference_sum(mi355gp_sparse* s, int nparts, const mi355gp_pa
     s->mfma_prof.on = true;
     s->mfma_prof.mask = 0x3u;
     s->mfma_prof.reset();
-    s->have_result = s->winv_ok = false;
+    s->have_result = s->winv_ok = s->svgp_result = false;
     if (het) HIP_CHECK(hipMemcpyAsync(s->dBeta, hbeta.data(), sizeof(double) * n, hipMemcpyHostToDevice, st));
     else hipLaunchKernelGGL(k_fill_const, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, s->dBeta, n, hbeta[0]);
     HIP_CHECK(hipMemcpyAsync(s->dZ, Z, sizeof(double) * m * D, hipMemcpyHostToDevice, st));
@@ -1108,7 +1064,7 @@ int mi355gp_vardtc_inference_uncertain(mi355gp_sparse* s, int nparts, const mi35
     const double beta = 1.0 / fmax(noise[0], 1e-8);
     s->beta_scalar = beta;
     s->mfma_prof.on = false;
-    s->have_result = s->winv_ok = false;
+    s->have_result = s->winv_ok = s->svgp_result = false;
     // the psi kernels' operands: a_q = 1 / l_q^2 (0 on a dimension the RBF part does not see), Z zero padded to mpad x Qp
     const SPart& rbf = s->parts[(size_t)irbf];
     const double var = rbf.kp.variance;
@@ -1302,6 +1258,7 @@ static int ensure_winv(mi355gp_sparse* s) {
 // 2 = Lm (lower, strict upper zero), 3 = Kmm (with the 1e-8 jitter), 4 = psi2 (heteroscedastic: sum_n beta_n k_n k_n^T),
 // 5 = dL_dpsi2_beta = Lm^-T (Dy I - P) Lm^-1 / 2 (var_dtc.py:220; dL_dpsi2 = beta times it for a scalar noise)
 int mi355gp_sparse_fetch(mi355gp_sparse* s, int which, double* out) {
+    ARG_CHECK(!s || !s->svgp_result, "mi355gp_sparse_fetch: the last call on this context was an SVGP call (this entry describes VarDTC's result; mi355gp_svgp_predict serves SVGP)");
     ARG_CHECK(s && out && s->have_result, "mi355gp_sparse_fetch: run mi355gp_vardtc_inference first");
     HIP_CHECK(hipSetDevice(s->device));
     EngineShared gate(s->device);
@@ -1334,6 +1291,7 @@ int mi355gp_sparse_fetch(mi355gp_sparse* s, int which, double* out) {
 // what SparseGP._update_gradients hands to a FOREIGN kernel's update_gradients_full / gradients_X (sparse_gp.py:108-118).
 // The N x M matrix is never resident: the caller walks it in row blocks (nrows <= the context's chunk size).
 int mi355gp_sparse_fetch_dLdKnm(mi355gp_sparse* s, int64_t row0, int64_t nrows, double* out) {
+    ARG_CHECK(!s || !s->svgp_result, "mi355gp_sparse_fetch_dLdKnm: the last call on this context was an SVGP call (this entry describes VarDTC's result; mi355gp_svgp_predict serves SVGP)");
     ARG_CHECK(s && out && s->have_result, "mi355gp_sparse_fetch_dLdKnm: run mi355gp_vardtc_inference first");
     ARG_CHECK(row0 >= 0 && nrows > 0 && row0 + nrows <= s->n && nrows <= s->chunk, "mi355gp_sparse_fetch_dLdKnm: bad row range");
     ARG_CHECK(!s->uncertain_result, "mi355gp_sparse_fetch_dLdKnm: the last call had uncertain inputs (dL_dpsi1 / dL_dpsi2 take dL_dKnm's place)");
@@ -1359,6 +1317,7 @@ int mi355gp_sparse_fetch_dLdKnm(mi355gp_sparse* s, int64_t row0, int64_t nrows, 
 // K(X*, X*) - Kx^T Winv Kx.  The kernel (parts) must be the one of the last inference call.
 int mi355gp_sparse_predict(mi355gp_sparse* s, int nparts, const mi355gp_part* parts, const double* Xnew, int64_t Mn,
                            double* mu_out, double* var_out, int full_cov) {
+    ARG_CHECK(!s || !s->svgp_result, "mi355gp_sparse_predict: the last call on this context was an SVGP call (this entry describes VarDTC's result; mi355gp_svgp_predict serves SVGP)");
     ARG_CHECK(s && s->have_result, "mi355gp_sparse_predict: run mi355gp_vardtc_inference first");
     ARG_CHECK(Xnew && Mn > 0 && mu_out, "mi355gp_sparse_predict: bad arguments");
     HIP_CHECK(hipSetDevice(s->device));

@@ -1,0 +1,80 @@
+// sparse_ctx.h -- the sparse context (mi355gp_sparse) and the helpers of sparse.hip that svgp.hip shares with it.
+#pragma once
+#include <functional>
+#include <vector>
+
+#include "../../include/mi355gp.h"
+#include "internal.h"
+#include "parts.h"
+
+struct LoopGroup;              // the loopback rendezvous of the row-sharded mode (sparse.hip)
+struct SvgpState;              // svgp.hip
+
+struct SPart : DevicePart {
+    DevBuf XtZ, XtC, HX, HZ, gradNM, gradMM;
+};
+
+struct mi355gp_sparse {
+    // MI355GP_SPARSE_KMM_OVERLAP: Kmm's build + Cholesky + inverse (they need only Z) on a side stream UNDERNEATH pass 1 when the
+    // factorisation is the single persistent launch (~1.2 ms of latency-bound work that otherwise runs on an idle GPU)
+    int kmm_overlap = 1;
+    hipStream_t st_kmm = nullptr;
+    hipEvent_t ev_z = nullptr, ev_kmm = nullptr;
+    int fuse_cols = 1;            // MI355GP_SPARSE_FUSE_COLS: k_grad_cols (gradient pass + column reductions in one)
+    int device = 0;
+    hipStream_t st = nullptr;
+    long n = 0, chunk = 0;
+    int D = 0, Dy = 0, splitk = 8;
+    double trYYT = 0.0, trYYT_local = 0.0;
+    std::vector<double> rowYY;    // host: |R_n|^2 per row (heteroscedastic log likelihood)
+    // row-sharded multi-GPU mode (the reference's MPI design: var_dtc_parallel.py:121-130,387-394):
+    // this rank holds n of n_global rows; psi2 / psi1Y and the pass-2 sums are all-reduced, M x M algebra is replicated
+    void* comm = nullptr;         // RCCL communicator
+    LoopGroup* loop = nullptr;    // or the loopback rendezvous
+    int world = 1, rank = 0;
+    long n_global = 0;
+    double* dSvar = nullptr;      // N x D input variances (mi355gp_sparse_set_input_variance): X is then the mean of q(x_n)
+    bool uncertain_result = false; // the last result came from mi355gp_vardtc_inference_uncertain (no dL_dKnm then)
+    double *dX = nullptr, *dY = nullptr, *dV = nullptr, *dBeta = nullptr, *dRowS = nullptr, *dRowT = nullptr, *dRowR = nullptr,
+           *Kfu = nullptr,
+           *T = nullptr;
+    // M-dependent
+    long m = 0, mp = 0;
+    double *dZ = nullptr, *zero1 = nullptr;
+    double *Lm = nullptr, *Xm = nullptr, *Tm = nullptr, *psi2part = nullptr, *psi2 = nullptr, *Amat = nullptr,
+           *LB = nullptr, *XB = nullptr, *Bi = nullptr, *P = nullptr, *E = nullptr, *T1 = nullptr, *Q2 = nullptr,
+           *dLdKmm = nullptr, *Winv = nullptr;
+    double *psi1Y = nullptr, *vecA = nullptr, *vecB = nullptr, *cvec = nullptr, *wvec = nullptr, *vvec = nullptr,
+           *trmvPart = nullptr, *colPart = nullptr, *gradPart = nullptr, *gradChunk = nullptr, *scal = nullptr,
+           *redbuf = nullptr;
+    std::vector<SPart> parts;
+    Terms terms;                  // part indices per summand, in order of first appearance (one part, or the factors of a Prod)
+    FactorWs ws;
+    bool ws_ok = false, have_result = false, winv_ok = false;
+    hipEvent_t ev[6] = {};
+    int h_info[2] = {0, 0};       // LAPACK-style info of the two M x M factorisations (targets of async copies: not on the stack)
+    double beta_scalar = 0.0;     // homoscedastic precision of the last call (0: per-point)
+    KernelProf mfma_prof;         // launch timing of the two MFMA kernels of a call: family 0 = T = Kfu dL_dpsi2, 1 = split-K Gram
+    // SVGP session (svgp.hip): its M x M state, and whether the context's latest result is an SVGP one (the VarDTC fetch /
+    // predict entry points describe VarDTC's result and refuse then, as fetch_dLdKnm does after an uncertain-input call)
+    SvgpState* svgp = nullptr;
+    bool svgp_result = false;
+};
+
+// ---- sparse.hip ----------------------------------------------------------------------------------------------------
+bool sharded(const mi355gp_sparse* s);
+int alloc_m(mi355gp_sparse* s, long M);
+int prepare_sparse_parts(mi355gp_sparse* s, int nparts, const mi355gp_part* parts);
+double sparse_other_variances(const mi355gp_sparse* s, size_t p);
+bool skip_white(const mi355gp_sparse* s, const std::vector<int>& t);
+void scale_for_parts(mi355gp_sparse* s, const double* src, long rows, long ldt, bool inducing);
+Resident<SPart> inducing_points(const mi355gp_sparse* s);
+void build_cross_chunk(mi355gp_sparse* s, long rc, double* out, double* scratch);
+void build_kmm(mi355gp_sparse* s, double* out, double* scratch, double jitter, int lower_only, hipStream_t st = nullptr);
+extern "C" {       // (defined among the entry points of sparse.hip)
+int potrf_checked(hipStream_t st, double* A, double* X, double* T, double* W, long mp, FactorWs* ws, int* info_host,
+                  const std::function<void()>& rebuild);
+void sparse_kmm_gradients(mi355gp_sparse* s);
+}
+// ---- svgp.hip ------------------------------------------------------------------------------------------------------
+void svgp_release(mi355gp_sparse* s);      // frees the SVGP state (M-dependent: called by free_m)

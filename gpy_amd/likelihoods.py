@@ -20,6 +20,20 @@ class Gaussian(Parameterized):
     def update_gradients(self, grad):
         self.variance.gradient = grad
 
+    def variational_expectations(self, Y, m, v, gh_points=None, Y_metadata=None):
+        """E_q[log p(y | f)] for q(f) = N(m, v), its derivatives in m and v and in the noise variance, in closed form
+        (reference `gaussian.py:336-345`): (F, dF_dmu, dF_dv, dF_dtheta), the last of shape (1, N, L)."""
+        if self.variance.size != 1:
+            raise NotImplementedError("variational_expectations takes one noise variance, not %d" % self.variance.size)
+        Y, m, v = np.asarray(Y), np.asarray(m), np.asarray(v)
+        lik_var = self.variance.values.ravel()[0].astype(np.result_type(m.dtype, np.float64))
+        q = np.square(Y) + np.square(m) + v - 2 * m * Y
+        F = -0.5 * np.log(2 * np.pi) - 0.5 * np.log(lik_var) - 0.5 * q / lik_var
+        dF_dmu = (Y - m) / lik_var
+        dF_dv = np.ones_like(v) * (-0.5 / lik_var)
+        dF_dtheta = -0.5 / lik_var + 0.5 * q / (lik_var ** 2)
+        return F, dF_dmu, dF_dv, dF_dtheta.reshape(1, Y.shape[0], Y.shape[1])
+
     def predictive_values(self, mu, var, full_cov=False, Y_metadata=None):
         if full_cov:
             var = var + np.eye(var.shape[0]) * float(self.variance.values[0])
@@ -255,6 +269,34 @@ class Likelihood(Parameterized):
         assert all(a.shape[0] == self.size for a in out)
         return out
 
+    @staticmethod
+    def _gh_points(T=20):
+        """the Gauss-Hermite rule of the reference (`likelihood.py:229-233`: 20 points)"""
+        return np.polynomial.hermite.hermgauss(T)
+
+    def variational_expectations(self, Y, m, v, gh_points=None, Y_metadata=None):
+        """E_q[log p(y | f)] for q(f) = N(m, v) and its derivatives in m and v by Gauss-Hermite quadrature (reference
+        `likelihood.py:358-411`): (F, dF_dmu, dF_dv, dF_dtheta); dF_dtheta is `size` x N x L, or None without parameters.
+        Y, m and v have the same shape."""
+        gh_x, gh_w = self._gh_points() if gh_points is None else gh_points
+        m, v, Y = np.asarray(m), np.asarray(v), np.asarray(Y)
+        shape = m.shape
+        m, v, Y = m.ravel(), v.ravel(), Y.ravel()
+        X = gh_x[None, :] * np.sqrt(2. * v[:, None]) + m[:, None]          # data along the first axis, nodes along the second
+        logp = self.logpdf(X, Y[:, None], Y_metadata=Y_metadata)
+        dlogp_dx = self.dlogpdf_df(X, Y[:, None], Y_metadata=Y_metadata)
+        d2logp_dx2 = self.d2logpdf_df2(X, Y[:, None], Y_metadata=Y_metadata)
+        F = np.dot(logp, gh_w) / np.sqrt(np.pi)
+        dF_dm = np.dot(dlogp_dx, gh_w) / np.sqrt(np.pi)
+        dF_dv = np.dot(d2logp_dx2, gh_w) / np.sqrt(np.pi) / 2.
+        if not (np.all(np.isfinite(dF_dv)) and np.all(np.isfinite(dF_dm))):
+            raise FloatingPointError("variational_expectations: the quadrature gave a non-finite derivative")
+        dF_dtheta = None
+        if self.size:
+            dF_dtheta = np.dot(self.dlogpdf_dtheta(X, Y[:, None], Y_metadata=Y_metadata), gh_w) / np.sqrt(np.pi)
+            dF_dtheta = dF_dtheta.reshape(self.size, shape[0], shape[1])
+        return F.reshape(*shape), dF_dm.reshape(*shape), dF_dv.reshape(*shape), dF_dtheta
+
     def predictive_values(self, mu, var, full_cov=False, Y_metadata=None):
         """(reference `likelihood.py:734-755`)"""
         pred_mean = self.predictive_mean(mu, var, Y_metadata=Y_metadata)
@@ -319,6 +361,25 @@ class Bernoulli(Likelihood):
     def ep_gradients(self, Y, cav_tau, cav_v, dL_dKdiag, Y_metadata=None, quad_mode="gh", boost_grad=1.):
         """no parameters, no gradients (reference `likelihood.py:227-228` for `size == 0`)"""
         return np.zeros(0)
+
+    def variational_expectations(self, Y, m, v, gh_points=None, Y_metadata=None):
+        """(reference `bernoulli.py:94-115`): the probit link's quadrature on y f, with Phi clipped to [1e-9, 1 - 1e-9]"""
+        if not isinstance(self.gp_link, link_functions.Probit):
+            raise NotImplementedError("variational_expectations of a Bernoulli likelihood needs the probit link, not %s"
+                                      % type(self.gp_link).__name__)
+        gh_x, gh_w = self._gh_points() if gh_points is None else gh_points
+        gh_w = gh_w / np.sqrt(np.pi)
+        m, v, Y = np.asarray(m), np.asarray(v), np.asarray(Y)
+        shape = m.shape
+        m, v, Y = m.ravel(), v.ravel(), Y.ravel()
+        Ysign = np.where(Y == 1, 1, -1)
+        X = gh_x[None, :] * np.sqrt(2. * v[:, None]) + (m * Ysign)[:, None]
+        p = np.clip(link_functions.std_norm_cdf(X), 1e-9, 1. - 1e-9)
+        NoverP = link_functions.std_norm_pdf(X) / p
+        F = np.log(p).dot(gh_w)
+        dF_dm = (NoverP * Ysign[:, None]).dot(gh_w)
+        dF_dv = -0.5 * (NoverP ** 2 + NoverP * X).dot(gh_w)
+        return F.reshape(*shape), dF_dm.reshape(*shape), dF_dv.reshape(*shape), None
 
     # ---- in terms of lambda = link(f) (reference `bernoulli.py:138-249`) -------------------------------------------------
     def pdf_link(self, inv_link_f, y, Y_metadata=None):

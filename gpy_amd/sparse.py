@@ -188,6 +188,24 @@ def _host_predictive_gradients(kern, Xnew, pred_var, woodbury_vector, woodbury_i
     return mean_jac, var_jac + kern.gradients_X(a2, Xnew, pred_var)
 
 
+def sparse_path_kernel_check(kern):
+    """What the sparse device context evaluates (VarDTC and SVGP alike); anything else is refused by name."""
+    new_kinds = exact_only_leaves(kern)
+    if new_kinds:
+        raise NotImplementedError("the MI355X sparse path does not evaluate %s kernels (the exact GPRegression path does)"
+                                  % ", ".join(sorted(set(new_kinds))))
+    # stationary kernels, products (Prod, reference `prod.py:58-99`) of stationary / Bias factors, and sums (Add) of those
+    # and of White / Bias parts
+    def _prod_ok(k):
+        return isinstance(k, Prod) and not any(isinstance(f, (White, Add, Prod)) for f in k.parts)
+    lone = getattr(kern, "is_leaf", False) and kern.fused_alone          # (not a lone White / Bias)
+    ok = lone or _prod_ok(kern) or (
+        isinstance(kern, Add) and all(_prod_ok(p) if isinstance(p, Prod) else not isinstance(p, Add) for p in kern.parts))
+    if not ok:
+        raise NotImplementedError("the MI355X sparse path covers gpy_amd's stationary kernels, products of stationary / "
+                                  "Bias factors and sums (Add) of those and of White / Bias parts")
+
+
 class VarDTC(object):
     const_jitter = 1e-8
 
@@ -280,20 +298,7 @@ class VarDTC(object):
             if any(a is not None for a in (Lm, dL_dKmm, psi0, psi1, psi2)):
                 raise NotImplementedError("precomputed statistics are not accepted by the MI355X sparse path")
             return self._inference_uncertain(kern, X, Z, likelihood, Y, Y_metadata, mean_function, precision, Z_tilde)
-        new_kinds = exact_only_leaves(kern)
-        if new_kinds:
-            raise NotImplementedError("the MI355X sparse path does not evaluate %s kernels (the exact GPRegression path does)"
-                                      % ", ".join(sorted(set(new_kinds))))
-        # stationary kernels, products (Prod, reference `prod.py:58-99`) of stationary / Bias factors, and sums (Add) of those
-        # and of White / Bias parts
-        def _prod_ok(k):
-            return isinstance(k, Prod) and not any(isinstance(f, (White, Add, Prod)) for f in k.parts)
-        lone = getattr(kern, "is_leaf", False) and kern.fused_alone          # (not a lone White / Bias)
-        ok = lone or _prod_ok(kern) or (
-            isinstance(kern, Add) and all(_prod_ok(p) if isinstance(p, Prod) else not isinstance(p, Add) for p in kern.parts))
-        if not ok:
-            raise NotImplementedError("the MI355X sparse path covers gpy_amd's stationary kernels, products of stationary / "
-                                      "Bias factors and sums (Add) of those and of White / Bias parts")
+        sparse_path_kernel_check(kern)
         if any(a is not None for a in (Lm, dL_dKmm, psi0, psi1, psi2)):
             raise NotImplementedError("precomputed statistics are not accepted by the MI355X sparse path")
         Y = np.asarray(Y, dtype=np.float64)

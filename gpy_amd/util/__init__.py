@@ -1,3 +1,5 @@
-"""GPy's `util` package on this path: `util.linalg` (the device factorisations) and `util.multioutput` (host bookkeeping)."""
+"""GPy's `util` package on this path: `util.linalg` (the device factorisations), `util.multioutput` and
+`util.choleskies` (host bookkeeping)."""
 from .. import linalg  # noqa: F401
 from . import multioutput  # noqa: F401
+from . import choleskies  # noqa: F401

@@ -452,6 +452,38 @@ int mi355gp_sparse_fetch(mi355gp_sparse* s, int which, double* out);
  * split-K Gram psi2: summed ms, algorithmic flops (rows M^2, lower half), launches]. */
 int mi355gp_sparse_get_profile(mi355gp_sparse* s, double* out6);
 
+/* ---- SVGP on the sparse context: minibatches and non-Gaussian likelihoods (Hensman et al. 2013, 2015) -------------------
+ * One SVGP.inference (inference/latent_function_inference/svgp.py:10-121) + SVGP.parameters_changed (core/svgp.py:54-71) for
+ * certain inputs and a zero mean function is a two-call session around the likelihood's quadrature
+ * (likelihood.variational_expectations, svgp.py:77), which stays with the caller: forward -> quadrature -> backward.
+ * q(u_d) = N(m_d, L_d L_d^T) for d < L latent functions, 1 <= L <= 16; M inducing points.  Accepted parts: those of
+ * mi355gp_vardtc_inference_sum.  A row-sharded context and a context holding input variances are refused.  All reductions run
+ * in a fixed order: two sessions on the same inputs give the same bytes.  After an SVGP call mi355gp_sparse_fetch,
+ * mi355gp_sparse_fetch_dLdKnm and mi355gp_sparse_predict (they describe VarDTC's result) are refused until the next VarDTC call.
+ *
+ * mi355gp_svgp_forward replaces svgp.py:12-56: Kmm = K(Z) with NO 1e-8 term (svgp.py:37, unlike var_dtc.py:93), Lm, Kmm^-1,
+ * S_d, S_d^-1, Kmm^-1 m, the KL term (:54-56), and over the context's row chunks A^T = K(X, Z) Kmm^-1, mu = A^T m,
+ * v[n,d] = sum_j (A^T L_d)[n,j]^2 + Kdiag - sum_j A^T[n,j] K(X, Z)[n,j] (:45-51).
+ *   q_mean: M x L row-major;  q_chol: L matrices M x M row-major whose lower triangles are the L_d (svgp.py:16)
+ *   mu_out, v_out: N x L;  scalars_out[2 + L]: [0] KL, [1] log det Kmm, [2 + d] log det S_d;  stage_ms[3] may be NULL
+ * Returns LAPACK-style info > 0 when Kmm is not positive definite: retry with extra_jitter as jitchol does (util/linalg.py:56-75). */
+int mi355gp_svgp_forward(mi355gp_sparse* s, int nparts, const mi355gp_part* parts, const double* Z, int64_t M, const double* q_mean,
+                         const double* q_chol, int L, double extra_jitter, double* mu_out, double* v_out, double* scalars_out,
+                         double* stage_ms);
+/* mi355gp_svgp_backward replaces svgp.py:84-117 and core/svgp.py:57-65 after a forward call on the same data.  dF_dmu, dF_dv:
+ * N x L, already multiplied by batch_scale (svgp.py:80); the weights dF_dv are signed.
+ *   dtheta_out: the parts' parameter gradients concatenated (dL_dKmm, dL_dKmn and dL_dKdiag terms summed, core/svgp.py:58-63)
+ *   dZ_out: M x D (core/svgp.py:65);  dm_out: M x L = dL_dm (svgp.py:112);  dchol_out: L x M x M, the lower triangle of
+ *   dL_dchol_d = 2 dL_dS_d L_d (svgp.py:114), zero above the diagonal;  stage_ms[3] may be NULL */
+int mi355gp_svgp_backward(mi355gp_sparse* s, const double* dF_dmu, const double* dF_dv, double* dtheta_out, double* dZ_out,
+                          double* dm_out, double* dchol_out, double* stage_ms);
+/* mi355gp_svgp_predict replaces Posterior._raw_predict (posterior.py:220-248) for Posterior(mean = m, cov = S) of svgp.py:121 after
+ * a forward call: woodbury_vector = Kmm^-1 m and woodbury_inv_d = Kmm^-1 - Kmm^-1 S_d Kmm^-1 (posterior.py:190-209) stay resident.
+ *   mu_out: Mn x L;  var_out (may be NULL): Mn x L clipped at 1e-15, or Mn x Mn x L with full_cov (posterior.py:233-248)
+ *   wv_out (M x L) / winv_out (L x M x M) may be NULL: the Woodbury quantities themselves; Mn == 0 fetches only them. */
+int mi355gp_svgp_predict(mi355gp_sparse* s, int nparts, const mi355gp_part* parts, const double* Xnew, int64_t Mn, int full_cov,
+                         double* mu_out, double* var_out, double* wv_out, double* winv_out);
+
 /* ---- psi-statistics of the RBF kernel for Gaussian inputs q(x_n) = N(mu_n, diag S_n) (kern/src/psi_comp/rbf_psi_comp.py) ----
  * Stateless, like mi355gp_kern_K.  lengthscale: D entries if ard, else one.  Z: M x D, mu / S: N x D row-major; every S
  * entry must be positive and finite (checked on the host before any launch); D <= 64.
