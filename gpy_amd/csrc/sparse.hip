@@ -144,7 +144,13 @@ __global__ void k_fill_const(double* __restrict__ out, long cnt, double v) {
     if (l < cnt) out[l] = v;
 }
 
-static dim3 grid2d(long cols, long rows) { return dim3((unsigned)((cols + 255) / 256), (unsigned)rows); }
+dim3 grid2d(long cols, long rows) { return dim3((unsigned)((cols + 255) / 256), (unsigned)rows); }
+void launch_mm_sym(hipStream_t st, const double* low, long mp, double* out) {
+    hipLaunchKernelGGL(k_sym_from_lower, grid2d(mp, mp), dim3(256), 0, st, low, mp, 1, out);
+}
+void launch_mm_axpby(hipStream_t st, const double* A, double ca, const double* B, double cb, double ci, long mp, double* out) {
+    hipLaunchKernelGGL(k_mm_axpby, grid2d(mp, mp), dim3(256), 0, st, A, ca, B, cb, ci, mp, out);
+}
 
 // ---- communicators of the row-sharded mode ------------------------------------------------------------------------
 // RCCL (one rank per process / GPU) or LOOPBACK: `world` contexts of ONE process on one device, driven by one host thread
@@ -584,10 +590,7 @@ static int sparse_mm_block(mi355gp_sparse* s, bool het, double beta, int inject)
     const int ntm = (int)(mp / NB);
     launch_trmm64(st, 0, s->Xm, mp, s->psi2, mp, s->T1, mp, ntm, ntm, 1.0);
     launch_trmm64(st, 2, s->Xm, mp, s->T1, mp, s->Amat, mp, ntm, ntm, het ? 1.0 : beta);
-    auto build_B = [&]() {
-        hipLaunchKernelGGL(k_mm_axpby, grid2d(mp, mp), dim3(256), 0, st, s->Amat, 1.0, (const double*)nullptr, 0.0, 1.0, mp,
-                           s->LB);
-    };
+    auto build_B = [&]() { launch_mm_axpby(st, s->Amat, 1.0, nullptr, 0.0, 1.0, mp, s->LB); };
     build_B();
     if (inject == 11 || inject == 12) s->ws.persist_test = inject - 10, s->ws.persist_skip = 0;
     // LB = chol(B), XB = LB^-1 and B^-1 = XB^T XB (lower tiles; :150) in one go
@@ -600,18 +603,17 @@ static int sparse_mm_block(mi355gp_sparse* s, bool het, double beta, int inject)
     // B^-1 = XB^T XB (lower tiles: computed with the factorisation above), P = Dy B^-1 + w w^T = DBi_plus_BiPBi (:150-152)
     hipLaunchKernelGGL(k_form_P, grid2d(mp, mp), dim3(256), 0, st, s->Bi, s->wvec, Dy, mp, m, s->P);
     // dL_dKmm = Lm^-T (-0.5 P - 0.5 Dy B + Dy I) Lm^-1 (:153-158);  -0.5 Dy (I + A) + Dy I = -0.5 Dy A + 0.5 Dy I
-    hipLaunchKernelGGL(k_mm_axpby, grid2d(mp, mp), dim3(256), 0, st, s->P, -0.5, s->Amat, -0.5 * Dy, 0.5 * Dy, mp, s->E);
+    launch_mm_axpby(st, s->P, -0.5, s->Amat, -0.5 * Dy, 0.5 * Dy, mp, s->E);
     launch_trmm64(st, 1, s->Xm, mp, s->E, mp, s->T1, mp, ntm, ntm, 1.0);                 // Xm^T E
     launch_trmm64(st, 3, s->Xm, mp, s->T1, mp, s->dLdKmm, mp, ntm, ntm, 1.0);            // (Xm^T E) Xm
     // Q2 = dL_dpsi2_beta = 0.5 Lm^-T (Dy I - P) Lm^-1 (:220); the precision enters per row in pass 2 (:224-226,231)
-    hipLaunchKernelGGL(k_mm_axpby, grid2d(mp, mp), dim3(256), 0, st, s->P, -0.5, (const double*)nullptr, 0.0, 0.5 * Dy, mp,
-                       s->E);
+    launch_mm_axpby(st, s->P, -0.5, nullptr, 0.0, 0.5 * Dy, mp, s->E);
     launch_trmm64(st, 1, s->Xm, mp, s->E, mp, s->T1, mp, ntm, ntm, 1.0);
     launch_trmm64(st, 3, s->Xm, mp, s->T1, mp, s->Q2, mp, ntm, ntm, 1.0);
     if (het_multi) {
         // several output columns with per-point noise: dL_dR (var_dtc.py:240-256) needs r_n = |LB^-1 Lm^-1 k_n|^2 on its own
         // (for Dy = 1 it folds into t_n and s_n); r_n = k_n^T Gr k_n with Gr = Lm^-T B^-1 Lm^-1, built in the Winv buffer
-        hipLaunchKernelGGL(k_sym_from_lower, grid2d(mp, mp), dim3(256), 0, st, s->Bi, mp, 1, s->E);
+        launch_mm_sym(st, s->Bi, mp, s->E);
         launch_trmm64(st, 1, s->Xm, mp, s->E, mp, s->T1, mp, ntm, ntm, 1.0);
         launch_trmm64(st, 3, s->Xm, mp, s->T1, mp, s->Winv, mp, ntm, ntm, 1.0);
     }
@@ -648,73 +650,279 @@ void sparse_kmm_gradients(mi355gp_sparse* s) {
     }
 }
 
-// One SparseGP.parameters_changed for a SUM of kernels, scalar or per-point noise and R = Y - mean (see mi355gp.h).
-// out_scalars: [0] log marginal likelihood, [1] dL/d(noise variance) (homoscedastic; 0 otherwise), [2] trace(A),
-//              [3] data_fit, [4] sum(log diag LB), [5] beta (homoscedastic)
-int mi355gp_vardtc_inference_sum(mi355gp_sparse* s, int nparts, const mi355gp_part* parts, const double* Z, int64_t M,
-                                 const double* noise, int64_t noise_len, double extra_jitter, double* out_scalars,
-                                 double* dtheta_out, double* dZ_out, double* wv_out, double* dnoise_rows_out,
-                                 double* dLdm_out, double* stage_ms) {
-    ARG_CHECK(s && s->n > 0, "mi355gp_vardtc_inference: set_data first");
-    ARG_CHECK(parts && Z && M > 0 && out_scalars && noise, "mi355gp_vardtc_inference: bad arguments");
-    ARG_CHECK(noise_len == 1 || noise_len == s->n, "noise must have 1 or N entries");
-    const bool het = noise_len > 1;
-    ARG_CHECK(!het || dnoise_rows_out, "per-point noise: dnoise_rows_out (N x Dy) is required");
+// ---- the phases an inference family is built from ---------------------------------------------------------
+// Opens a call (the caller holds the EngineShared gate): the buffers for M inducing points and the part list; the previous
+// result is forgotten
+int sparse_open(mi355gp_sparse* s, int nparts, const mi355gp_part* parts, int64_t M) {
     HIP_CHECK(hipSetDevice(s->device));
-    EngineShared gate(s->device);
-    const int D = s->D, Dy = s->Dy;
     if (M != s->m)
         if (int rc = alloc_m(s, M)) return rc;
-    if (int rc = prepare_sparse_parts(s, nparts, parts)) return rc;
+    s->have_result = s->winv_ok = s->svgp_result = false;
+    s->h_info[0] = s->h_info[1] = 0;
+    return prepare_sparse_parts(s, nparts, parts);
+}
+
+// Starts the stream work of a call: the precision vector (nbeta = 1: beta[0] for every row, filled on the device; nbeta = n:
+// per point; 0: the family has none), Z, ev[0], V = beta R (var_dtc.py:88) and Z scaled for every part
+int sparse_start(mi355gp_sparse* s, const double* Z, const double* beta, long nbeta) {
+    hipStream_t st = s->st;
+    const long n = s->n, cnt = n * s->Dy;
+    if (nbeta > 1) HIP_CHECK(hipMemcpyAsync(s->dBeta, beta, sizeof(double) * n, hipMemcpyHostToDevice, st));
+    else if (nbeta == 1) hipLaunchKernelGGL(k_fill_const, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, s->dBeta, n, beta[0]);
+    HIP_CHECK(hipMemcpyAsync(s->dZ, Z, sizeof(double) * s->m * s->D, hipMemcpyHostToDevice, st));
+    HIP_CHECK(hipEventRecord(s->ev[0], st));
+    if (nbeta) hipLaunchKernelGGL(k_scale_rows, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, st, s->dY, s->dBeta, cnt, s->Dy, s->dV);
+    scale_for_parts(s, s->dZ, s->m, s->mp, true);
+    return 0;
+}
+
+// Ends the stream work of a call: waits for it; stage_ms (optional): [i] = ev[i] .. ev[i + 1] for i < nstage, [nstage] = the
+// total.  Returns the LAPACK-style info of the call's two M x M factorisations: 0, or 1 .. M when one is not positive
+// definite (the caller adds jitter), or a negative error.
+int sparse_finish(mi355gp_sparse* s, int nstage, double* stage_ms) {
+    HIP_CHECK(hipStreamSynchronize(s->st));
+    HIP_CHECK(hipGetLastError());
+    if (stage_ms) {
+        float ms;
+        for (int i = 0; i < nstage; ++i) {
+            HIP_CHECK(hipEventElapsedTime(&ms, s->ev[i], s->ev[i + 1]));
+            stage_ms[i] = ms;
+        }
+        HIP_CHECK(hipEventElapsedTime(&ms, s->ev[0], s->ev[nstage]));
+        stage_ms[nstage] = ms;
+    }
+    for (int info : s->h_info)
+        if (info > 0) return info > s->m ? (int)s->m : info;
+    return 0;
+}
+
+// Kfu of rows [r0, r0 + rc) of X into s->Kfu (products are multiplied up in s->T).  The cross-covariance kernels write rows
+// < rc, columns < m only: rows [z0, z1) of the buffer are zeroed first (z0 >= z1: nothing is).  V != NULL: where one pass can do
+// both (one plain stationary part), the column partials of Kfu^T V go to s->colPart as well and their number of splits is
+// returned; otherwise 0, or a negative error.
+int sparse_cross_rows(mi355gp_sparse* s, long r0, long rc, long z0, long z1, const double* V) {
+    const long mp = s->mp, chunk = s->chunk;
+    scale_for_parts(s, s->dX + r0 * s->D, rc, chunk, false);
+    if (z0 < z1) HIP_CHECK(hipMemsetAsync(s->Kfu + z0 * mp, 0, sizeof(double) * (z1 - z0) * mp, s->st));
+    if (V && s->parts.size() == 1 && s->parts[0].stationary() && s->fuse_cols) {
+        const SPart& pt = s->parts[0];
+        const int ns = launch_kbuild_cols(s->st, pt.kp, pt.XtC, chunk, rc, pt.XtZ, mp, s->m, mp, s->Kfu, mp, V, s->Dy, s->colPart);
+        if (ns > 0) return ns;
+    }
+    build_cross_chunk(s, rc, s->Kfu, s->T);
+    return 0;
+}
+
+// zeroes what sparse_rows_gradients accumulates over the chunks of a call
+int sparse_rows_gradients_reset(mi355gp_sparse* s) {
+    for (SPart& p : s->parts) {
+        HIP_CHECK(hipMemsetAsync(p.gradNM, 0, sizeof(double) * rec_doubles(s), s->st));
+        HIP_CHECK(hipMemsetAsync(p.HX, 0, sizeof(double) * hsum_doubles(s), s->st));
+    }
+    return 0;
+}
+
+// The row-gradient step of one chunk of rc rows (scaled into the parts' XtC): from W, the chunk's rows of dL_dKnm without the
+// rank term rk, every part's theta record (added to gradNM) and H^T [X~ | 1] (added to HX), H = dL_dKnm * (dK/dr) / r.
+// dL_dKnm is formed inside the gradient pass (no separate read-modify-write of the chunk).  D <= 16: the same pass also
+// accumulates H^T [X~ | 1] (H stays on chip); otherwise H is written to `scratch` (rc x mp) and reduced by a second pass -- W
+// itself must survive for the parts that follow.  A factor of a product sees dL_dKnm TIMES the other factors' covariance
+// (prod.py:86-99): those are multiplied up in `scratch`, and form_times(), the call site's own launch, forms dL_dKnm on top.
+void sparse_rows_gradients(mi355gp_sparse* s, long rc, const double* W, double* scratch, const RankTerm& rk,
+                           const std::function<void()>& form_times) {
+    hipStream_t st = s->st;
+    const long m = s->m, mp = s->mp, chunk = s->chunk;
+    const int D = s->D, groups = (D + 31) / 32;
+    const long gsz = (long)rec_doubles(s);
+    for (size_t pi = 0; pi < s->parts.size(); ++pi) {
+        SPart& p = s->parts[pi];
+        if (p.kp.kind == MI355GP_WHITE) continue;        // White: K(X, Z) = 0, no contribution (static.py:89-93)
+        int nbk = 0, ns = 0;
+        const bool prod = emit_other_factors(s->terms, p.tix, pi, scratch, [&](int f, double* dst, const double* mul, int, bool) {
+            const SPart& pf = s->parts[(size_t)f];
+            launch_kbuild_cross(st, pf.kp, pf.XtC, chunk, rc, pf.XtZ, mp, m, dst, mp, 0, 0, mul);
+        });
+        if (prod) {
+            form_times();
+            nbk = grad_generic_num_blocks(rc, m);
+            launch_grad_generic(st, p.kp, p.XtC, chunk, rc, p.XtZ, mp, m, 0, scratch, mp, s->gradPart,
+                                p.stationary() ? scratch : nullptr, mp);            // H over the weights, in place
+            if (p.stationary()) ns = launch_colreduce_multi(st, scratch, mp, rc, mp, p.XtC, 1, chunk, D, 1, s->colPart);
+        } else {
+            if (p.stationary() && s->fuse_cols)
+                ns = launch_grad_cols(st, p.kp, p.XtC, chunk, rc, p.XtZ, mp, m, mp, W, mp, rk, s->gradPart, s->colPart, &nbk);
+            if (ns == 0) {
+                nbk = grad_generic_num_blocks(rc, m);
+                launch_grad_generic(st, p.kp, p.XtC, chunk, rc, p.XtZ, mp, m, 0, W, mp, s->gradPart,
+                                    p.stationary() ? scratch : nullptr, mp, rk);
+                if (p.stationary()) ns = launch_colreduce_multi(st, scratch, mp, rc, mp, p.XtC, 1, chunk, D, 1, s->colPart);
+            }
+        }
+        for (int g = 0; g < (p.kp.ard ? groups : 1); ++g)
+            launch_reduce_partials(st, s->gradPart + (long)g * nbk * GP_STRIDE, nbk, GP_STRIDE, s->gradChunk + (long)g * GP_STRIDE);
+        // (every entry of the record: one block of 256 threads ends at dimension 239)
+        hipLaunchKernelGGL(k_vec_axpy, dim3((unsigned)((gsz + 255) / 256)), dim3(256), 0, st, p.gradNM, s->gradChunk, gsz, 1.0);
+        if (p.stationary()) launch_sum_splits(st, s->colPart, mp * (D + 1), ns, 1, p.HX);
+    }
+}
+
+// The kernel-side gradients of a call, first half: the parts' reduction records and H^T [X~ | 1] sums on their way to the
+// host (valid after the call's stream synchronisation); with_nm = false: the Kmm side only (gradMM, HZ)
+int sparse_fetch_gradients(mi355gp_sparse* s, bool with_nm, KernGrads* h) {
+    const size_t np_ = s->parts.size(), gsz = rec_doubles(s), hsz = hsum_doubles(s), zsz = (size_t)s->D * s->mp;
+    h->with_nm = with_nm;
+    h->gnm.assign(np_ * gsz, 0.0);
+    h->gmm.assign(np_ * gsz, 0.0);
+    h->HX.assign(np_ * hsz, 0.0);
+    h->HZ.assign(np_ * hsz, 0.0);
+    h->Zs.assign(np_ * zsz, 0.0);
+    for (size_t i = 0; i < np_; ++i) {
+        SPart& p = s->parts[i];
+        if (with_nm) HIP_CHECK(hipMemcpyAsync(h->gnm.data() + i * gsz, p.gradNM, sizeof(double) * gsz, hipMemcpyDeviceToHost, s->st));
+        HIP_CHECK(hipMemcpyAsync(h->gmm.data() + i * gsz, p.gradMM, sizeof(double) * gsz, hipMemcpyDeviceToHost, s->st));
+        if (!p.stationary()) continue;
+        if (with_nm) HIP_CHECK(hipMemcpyAsync(h->HX.data() + i * hsz, p.HX, sizeof(double) * hsz, hipMemcpyDeviceToHost, s->st));
+        HIP_CHECK(hipMemcpyAsync(h->HZ.data() + i * hsz, p.HZ, sizeof(double) * hsz, hipMemcpyDeviceToHost, s->st));
+        HIP_CHECK(hipMemcpyAsync(h->Zs.data() + i * zsz, p.XtZ, sizeof(double) * zsz, hipMemcpyDeviceToHost, s->st));
+    }
+    return 0;
+}
+
+// ... second half, on the host.  dtheta_out (optional): the parts' parameter gradients, concatenated: per part the Knm and the
+// Kmm record summed, part_dtheta, then update_gradients_diag: kdiag_coef = sum_n dL_dKdiag_n to the variance (stationary.py:
+// 175-184, static.py:95-96; a factor of a product: times the other factors' variances, prod.py:67-71).  dZ_out (optional,
+// M x D) = gradients_X(dL_dKnm^T, Z, X) + gradients_X(dL_dKmm, Z), summed over the parts (add.py:84-88):
+//   sum_n H[n,m] (z~_mq - x~_nq) / l_q  +  2 sum_j Hmm[j,m] (z~_mq - z~_jq) / l_q
+void sparse_assemble_gradients(const mi355gp_sparse* s, const KernGrads& h, double kdiag_coef, double* dtheta_out, double* dZ_out) {
+    const size_t np_ = s->parts.size(), gsz = rec_doubles(s), hsz = hsum_doubles(s);
+    const long m = s->m, mp = s->mp;
+    const int D = s->D;
+    if (dtheta_out) {
+        double* o = dtheta_out;
+        std::vector<double> ab(gsz);
+        for (size_t i = 0; i < np_; ++i) {
+            const double* a = h.gnm.data() + i * gsz;
+            const double* b = h.gmm.data() + i * gsz;
+            for (size_t k = 0; k < gsz; ++k) ab[k] = h.with_nm ? a[k] + b[k] : b[k];
+            const int k = part_dtheta(s->parts[i], ab.data(), nullptr, o);
+            o[0] = kdiag_coef * sparse_other_variances(s, i) + o[0];
+            o += k;
+        }
+    }
+    if (dZ_out) {
+        for (long j = 0; j < m * D; ++j) dZ_out[j] = 0.0;
+        for (size_t i = 0; i < np_; ++i) {
+            const SPart& p = s->parts[i];
+            if (!p.stationary()) continue;
+            const double* hx = h.HX.data() + i * hsz;
+            const double* hz = h.HZ.data() + i * hsz;
+            const double* zs = h.Zs.data() + i * (size_t)D * mp;
+            for (long j = 0; j < m; ++j)
+                for (int q = 0; q < D; ++q) {
+                    const double il = p.inv_ls[(size_t)q];
+                    if (il == 0.0) continue;
+                    const double z = zs[(size_t)q * mp + j];
+                    const double a = h.with_nm ? z * hx[j * (D + 1) + D] - hx[j * (D + 1) + q] : 0.0;
+                    const double b = z * hz[j * (D + 1) + D] - hz[j * (D + 1) + q];
+                    dZ_out[j * D + q] += (a + 2.0 * b) * il;
+                }
+        }
+    }
+}
+
+// Prediction at Mn new points, first half: Kx = K(Z, X*) (mp x mnp, zero in the padding), with want_cov Kss = K(X*, X*), and
+// the mean Kx^T wv (wv: mp x ncol) into q->Mu.  Every factor is evaluated with ITS scaling of the new inputs; products are
+// multiplied up in Tmp / a second M* x M* scratch.
+int sparse_newpoints(mi355gp_sparse* s, const double* Xnew, int64_t Mn, bool want_cov, const double* wv, int ncol,
+                     const char* where, NewPoints* q) {
+    hipStream_t st = s->st;
+    const long m = s->m, mp = s->mp, mnp = round_up(Mn, NB);
+    q->Mn = Mn;
+    q->mnp = mnp;
+    q->kdiag = expression_kdiag(s->parts, s->terms);
+    if (int rc = q->xs.load(st, Xnew, Mn, s->D)) return rc;
+    HIP_CHECK(q->Kx.alloc(mp * mnp));
+    HIP_CHECK(q->Tmp.alloc(mp * mnp));
+    HIP_CHECK(q->Mu.alloc(Mn * ncol));
+    HIP_CHECK(hipMemsetAsync(q->Kx, 0, sizeof(double) * mp * mnp, st));
+    emit_cross(st, s->parts, s->terms, inducing_points(s), q->xs, q->Kx, mnp, q->Tmp, false, 0,
+               [&](const std::vector<int>& t) { return skip_white(s, t); });
+    if (want_cov) {
+        HIP_CHECK(q->Kss.alloc(mnp * mnp));
+        HIP_CHECK(hipMemsetAsync(q->Kss, 0, sizeof(double) * mnp * mnp, st));
+        if (has_product(s->terms) && q->scr.alloc(mnp * mnp) != hipSuccess) {
+            mi355gp_set_error("%s: out of memory for the product scratch", where);
+            return -3;
+        }
+        emit_cross(st, s->parts, s->terms, q->xs, q->xs, q->Kss, mnp, q->scr, false, /*diag_same=*/1);
+    }
+    launch_col_reduce(st, q->Kx, mnp, m, Mn, wv, ncol, 0.0, 0, q->Mu);
+    return 0;
+}
+// ... second half, once per Woodbury inverse: Kdiag - sum(Kx * (Winv Kx), 0) (Mn doubles), or with full_cov
+// K(X*, X*) - Kx^T Winv Kx (ld mnp).  The result is in q->var: q->Var, or Kss itself when it need not be kept for another inverse.
+int sparse_newpoints_var(mi355gp_sparse* s, NewPoints* q, const double* Winv, bool full_cov, bool keep_kss) {
+    hipStream_t st = s->st;
+    const long m = s->m, mp = s->mp, mnp = q->mnp, Mn = q->Mn;
+    q->var = q->Kss;
+    if (!full_cov || keep_kss) {
+        if (!q->Var) HIP_CHECK(q->Var.alloc(full_cov ? mnp * mnp : Mn));
+        q->var = q->Var;
+    }
+    launch_gemm(st, 0, 1, mp, mnp, mp, Winv, mp, q->Kx, mnp, q->Tmp, mnp, 1.0, 0.0);                   // Winv Kx
+    if (!full_cov) {
+        hipLaunchKernelGGL(k_col_dot, dim3((unsigned)((Mn + 63) / 64)), dim3(256), 0, st, (const double*)q->Kx, (const double*)q->Tmp,
+                           mnp, m, Mn, q->kdiag, q->var);
+        return 0;
+    }
+    if (keep_kss) HIP_CHECK(hipMemcpyAsync(q->var, q->Kss, sizeof(double) * mnp * mnp, hipMemcpyDeviceToDevice, st));
+    launch_gemm(st, 1, 1, mnp, mnp, mp, q->Kx, mnp, q->Tmp, mnp, q->var, mnp, -1.0, 1.0);               // K** - Kx^T Winv Kx
+    return 0;
+}
+
+// ---- VarDTC -------------------------------------------------------------------------------------------------------------
+// _compute_log_marginal_likelihood (var_dtc.py:264-276) and, for one noise variance (beta > 0), _compute_dL_dR (:258-261) into
+// out_scalars: [0] log marginal likelihood, [1] dL/d(noise variance) (0 for per-point noise), [2] trace(A), [3] data_fit,
+// [4] sum(log diag LB), [5] beta.  scal: the four sums of sparse_mm_block; kdiag: psi0_n, the same for every row; sums: {sum
+// beta_n, sum log beta_n, sum beta_n |R_n|^2} over ALL shards (read for per-point noise, beta == 0, only)
+static void vardtc_scalars(const mi355gp_sparse* s, const double* scal, double kdiag, double beta, const double* sums,
+                           double* out_scalars) {
+    const int Dy = s->Dy;
+    const double trA = scal[0], sumAP = scal[1], logLB = scal[2], data_fit = scal[3];
+    const double ng = (double)s->n_global, nd = ng * Dy;
+    double lik_1, lik_2;
+    if (beta == 0.0) {
+        lik_1 = -0.5 * nd * log(2.0 * M_PI) + 0.5 * Dy * sums[1] - 0.5 * sums[2];
+        lik_2 = -0.5 * Dy * (sums[0] * kdiag - trA);
+    } else {
+        lik_1 = -0.5 * nd * (log(2.0 * M_PI) - log(beta)) - 0.5 * beta * s->trYYT;
+        lik_2 = -0.5 * Dy * (beta * ng * kdiag - trA);
+    }
+    const double lik_3 = -(double)Dy * logLB;
+    for (int i = 0; i < MI355GP_NUM_OUT; ++i) out_scalars[i] = 0.0;
+    out_scalars[0] = lik_1 + lik_2 + lik_3 + 0.5 * data_fit;
+    out_scalars[2] = trA;
+    out_scalars[3] = data_fit;
+    out_scalars[4] = logLB;
+    out_scalars[5] = beta;
+    if (beta != 0.0) {
+        double dL_dR = -0.5 * nd * beta + 0.5 * s->trYYT * beta * beta;
+        dL_dR += 0.5 * Dy * (ng * kdiag * beta * beta - trA * beta);
+        dL_dR += beta * (0.5 * sumAP - data_fit);
+        out_scalars[1] = dL_dR;
+    }
+}
+
+// Kmm + (1e-8 + extra_jitter) I (var_dtc.py:93-94) = sum of the parts' K(Z) (White on the diagonal), Lm = chol (jitchol, :95),
+// Xm = Lm^-1, and pass 1 over the row chunks: psi2 = sum_n beta_n k_n k_n^T (heteroscedastic) or Kuf Kfu (then A carries
+// beta), psi1V = Kuf V; records ev[1].
+// Kmm's three steps need only Z: when the factorisation is the single persistent launch (a latency-bound chain on an otherwise
+// idle GPU), they go to a side stream and pass 1 is enqueued underneath; the launch is first in line, so its workgroups are
+// resident before pass 1 fills the remaining CUs.  info is read (and a called-off launch redone) after pass 1 is queued.
+static int vardtc_pass1(mi355gp_sparse* s, bool het, double extra_jitter) {
     hipStream_t st = s->st;
     const long n = s->n, m = s->m, mp = s->mp, chunk = s->chunk;
-    const int groups = (D + 31) / 32;
-    const size_t gsz = (size_t)groups * GP_STRIDE, hsz = (size_t)mp * (D + 1);
-    // per-point precision beta_n = 1 / max(noise_n, 1e-8) (var_dtc.py:78-80), V = beta * R (:88)
-    // (scalar noise: the three sums are closed forms -- unused by the homoscedastic formulas -- and the precision vector is filled on
-    //  the device: the N-element host loop with its logarithms and the 1.6 MB upload cost ~1 ms per evaluation at N = 200000)
-    std::vector<double> hbeta(het ? (size_t)n : (size_t)1);
-    double sum_beta = 0.0, sum_logbeta = 0.0, sum_bYY = 0.0;
-    if (het) {
-        for (long i = 0; i < n; ++i) {
-            const double b = 1.0 / fmax(noise[i], 1e-8);
-            hbeta[(size_t)i] = b;
-            sum_beta += b;
-            sum_logbeta += log(b);
-            sum_bYY += b * s->rowYY[(size_t)i];
-        }
-    } else {
-        hbeta[0] = 1.0 / fmax(noise[0], 1e-8);
-        sum_beta = hbeta[0] * (double)n;
-        sum_logbeta = log(hbeta[0]) * (double)n;
-        sum_bYY = hbeta[0] * s->trYYT_local;
-    }
-    const double beta = het ? 0.0 : hbeta[0];
-    s->beta_scalar = beta;
-    s->mfma_prof.on = true;
-    s->mfma_prof.mask = 0x3u;
-    s->mfma_prof.reset();
-    s->have_result = s->winv_ok = s->svgp_result = false;
-    if (het) HIP_CHECK(hipMemcpyAsync(s->dBeta, hbeta.data(), sizeof(double) * n, hipMemcpyHostToDevice, st));
-    else hipLaunchKernelGGL(k_fill_const, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, s->dBeta, n, hbeta[0]);
-    HIP_CHECK(hipMemcpyAsync(s->dZ, Z, sizeof(double) * m * D, hipMemcpyHostToDevice, st));
-    HIP_CHECK(hipEventRecord(s->ev[0], st));
-    {   // V = beta * R
-        const long cnt = n * Dy;
-        hipLaunchKernelGGL(k_scale_rows, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, st, s->dY, s->dBeta, cnt, Dy, s->dV);
-    }
-    scale_for_parts(s, s->dZ, m, mp, true);
-    // Kmm + 1e-8 I (var_dtc.py:93-94) = sum of the parts' K(Z) (White on the diagonal), Lm = chol (jitchol, :95), Xm = Lm^-1.
-    // They need only Z: when the factorisation is the single persistent launch (a latency-bound chain on an otherwise idle
-    // GPU), the three go to a side stream and pass 1 is enqueued underneath; the launch is first in line, so its workgroups are
-    // resident before pass 1 fills the remaining CUs.  info is read (and a called-off launch redone) after pass 1 is queued.
-    s->h_info[0] = s->h_info[1] = 0;
-    int inject = 0;                                            // fault injection for the tests: 1 / 2 hit Kmm's launch, 11 / 12 B's
-    {
-        const char* et = DIAG_ENV("SPARSE_PERSIST_TEST");
-        if (et && *et) inject = atoi(et);
-    }
-    if (inject == 1 || inject == 2) s->ws.persist_test = inject, s->ws.persist_skip = 0;
+    const int Dy = s->Dy;
     const bool overlap_kmm = s->kmm_overlap && s->st_kmm && potrf_persist_eligible(mp, &s->ws);
     hipStream_t sk = overlap_kmm ? s->st_kmm : st;
     auto rebuild_kmm = [&]() { build_kmm(s, s->Lm, s->T1, 1e-8 + extra_jitter, /*lower_only=*/1, sk); };
@@ -734,26 +942,22 @@ int mi355gp_vardtc_inference_sum(mi355gp_sparse* s, int nparts, const mi355gp_pa
         HIP_CHECK(hipStreamWaitEvent(st, s->ev_z, 0));
         launch_wait_persist_resident(st, &s->ws);
     }
-    // ---- pass 1: psi2 = sum_n beta_n k_n k_n^T (heteroscedastic) or Kuf Kfu (then A carries beta), psi1V = Kuf V -------
     HIP_CHECK(hipMemsetAsync(s->psi1Y, 0, sizeof(double) * mp * Dy, st));
     int nch = 0;
     for (long r0 = 0; r0 < n; r0 += chunk, ++nch) {
         const long rc = (n - r0 < chunk) ? (n - r0) : chunk;
-        scale_for_parts(s, s->dX + r0 * D, rc, chunk, false);
-        // the cross-covariance kernel writes rows < rc, columns < m: zero only what it leaves out
+        // zero only what the cross-covariance kernel leaves out: the padding columns (m < mp) of a buffer not yet zeroed or
+        // holding the rows of a longer chunk, else the rows past a short chunk
+        long z0 = 0, z1 = 0;
         if (m < mp) {
-            if (rc < chunk || nch == 0) HIP_CHECK(hipMemsetAsync(s->Kfu, 0, sizeof(double) * chunk * mp, st));
+            if (rc < chunk || nch == 0) z1 = chunk;
         } else if (rc < chunk) {
-            HIP_CHECK(hipMemsetAsync(s->Kfu + rc * mp, 0, sizeof(double) * (chunk - rc) * mp, st));
+            z0 = rc, z1 = chunk;
         }
         // one plain stationary part: K(X_chunk, Z) and the column sums of psi1^T V in ONE pass over the chunk; otherwise the
         // expression is accumulated part by part and reduced by a second pass
-        int ns_fused = 0;
-        if (s->parts.size() == 1 && s->parts[0].stationary() && s->fuse_cols) {
-            const SPart& pt = s->parts[0];
-            ns_fused = launch_kbuild_cols(st, pt.kp, pt.XtC, chunk, rc, pt.XtZ, mp, m, mp, s->Kfu, mp, s->dV + r0 * Dy, Dy, s->colPart);
-        }
-        if (ns_fused == 0) build_cross_chunk(s, rc, s->Kfu, s->T);
+        const int ns_fused = sparse_cross_rows(s, r0, rc, z0, z1, s->dV + r0 * Dy);
+        if (ns_fused < 0) return ns_fused;
         const double* G = s->Kfu;
         if (het) {                                            // rows scaled by sqrt(beta_n) (var_dtc.py:126-129) into T
             HIP_CHECK(hipMemsetAsync(s->T + rc * mp, 0, sizeof(double) * (round_up(rc, 16L * s->splitk) - rc) * mp, st));
@@ -777,24 +981,22 @@ int mi355gp_vardtc_inference_sum(mi355gp_sparse* s, int nparts, const mi355gp_pa
         if (int rc = sparse_allreduce(s, s->psi1Y, (size_t)mp * Dy)) return rc;
     }
     HIP_CHECK(hipEventRecord(s->ev[1], st));
-    const bool het_multi = het && Dy > 1;
-    if (int rc = sparse_mm_block(s, het, beta, inject)) return rc;
-    // ---- pass 2: dL_dKnm = beta_n (R v^T + 2 Kfu Q2) (:219,224-226,233), its theta reductions and H^T [X~ | 1] per part --
-    for (SPart& p : s->parts) {
-        HIP_CHECK(hipMemsetAsync(p.gradNM, 0, sizeof(double) * gsz, st));
-        HIP_CHECK(hipMemsetAsync(p.HX, 0, sizeof(double) * hsz, st));
-    }
-    const bool want_rows = het || dLdm_out != nullptr;
-    nch = 0;
-    const int one_chunk = (n <= chunk);
-    for (long r0 = 0; r0 < n; r0 += chunk, ++nch) {
+    return 0;
+}
+
+// pass 2 over the same chunks: dL_dKnm = beta_n (R v^T + 2 Kfu Q2) (var_dtc.py:219,224-226,233), its theta reductions and
+// H^T [X~ | 1] per part; want_rows: the per-row sums of dL_dm and of the per-point noise gradient as well
+static int vardtc_pass2(mi355gp_sparse* s, bool het, bool want_rows) {
+    hipStream_t st = s->st;
+    const long n = s->n, m = s->m, mp = s->mp, chunk = s->chunk;
+    const int Dy = s->Dy;
+    const bool het_multi = het && Dy > 1, one_chunk = (n <= chunk);
+    if (int rc = sparse_rows_gradients_reset(s)) return rc;
+    for (long r0 = 0; r0 < n; r0 += chunk) {
         const long rc = (n - r0 < chunk) ? (n - r0) : chunk;
         const long rcp = round_up(rc, NB);
-        if (!one_chunk) {                                    // a single chunk is still resident from pass 1
-            scale_for_parts(s, s->dX + r0 * D, rc, chunk, false);
-            if (rc < chunk) HIP_CHECK(hipMemsetAsync(s->Kfu + rc * mp, 0, sizeof(double) * (chunk - rc) * mp, st));
-            build_cross_chunk(s, rc, s->Kfu, s->T);
-        }
+        if (!one_chunk)                                      // a single chunk is still resident from pass 1
+            if (int rc2 = sparse_cross_rows(s, r0, rc, rc, chunk, nullptr)) return rc2;
         if (het_multi) {                                     // r_n = sum_j (Kfu Gr)_nj Kfu_nj, before T is needed for anything else
             launch_gemm(st, 0, 1, rcp, mp, mp, s->Kfu, mp, s->Winv, mp, s->T, mp, 1.0, 0.0);
             launch_rowdots(st, s->Kfu, s->T, mp, rc, m, s->vvec, Dy, s->dRowS + r0 * Dy, s->dRowR + r0);
@@ -804,47 +1006,16 @@ int mi355gp_vardtc_inference_sum(mi355gp_sparse* s, int nparts, const mi355gp_pa
         s->mfma_prof.end(st);
         // per-row reductions for dL_dm = V - Kfu v (:148) and the per-point noise gradient (t_n = sum_j T_nj Kfu_nj)
         if (want_rows) launch_rowdots(st, s->Kfu, s->T, mp, rc, m, s->vvec, Dy, s->dRowS + r0 * Dy, het ? s->dRowT + r0 : nullptr);
-        // dL_dKnm is formed inside the gradient pass (no separate read-modify-write of the chunk).  D <= 16: the same pass
-        // also accumulates H^T [X~ | 1] (H = dL_dKnm * (dK/dr)/r stays on chip); otherwise H is written to the Kfu buffer
-        // (not needed any more for this chunk: the gradient kernels recompute the covariance from the inputs) and reduced
-        // by a second pass -- T itself must survive for the parts that follow.
+        // the weights are T, the scratch the Kfu buffer: not needed any more for this chunk (the gradient kernels recompute
+        // the covariance from the inputs)
         const RankTerm rk{s->dY + r0 * Dy, s->vvec, Dy, 1.0, 2.0, s->dBeta + r0};
-        const size_t nstat = s->parts.size();
-        for (size_t pi = 0; pi < nstat; ++pi) {
-            SPart& p = s->parts[pi];
-            if (p.kp.kind == MI355GP_WHITE) continue;        // White: K(X, Z) = 0, no contribution (static.py:89-93)
-            int nbk = 0, ns = 0;
-            // a factor of a product sees dL_dKnm TIMES the other factors' covariance (prod.py:86-99): that weight matrix is
-            // materialised in the Kfu buffer (free by now) -- other factors multiplied up, then dL_dKnm formed on top
-            const bool prod = emit_other_factors(s->terms, p.tix, pi, s->Kfu, [&](int f, double* dst, const double* mul, int, bool) {
-                const SPart& pf = s->parts[(size_t)f];
-                launch_kbuild_cross(st, pf.kp, pf.XtC, chunk, rc, pf.XtZ, mp, m, dst, mp, 0, 0, mul);
-            });
-            if (prod) {
-                hipLaunchKernelGGL(k_form_dLdKnm_times, dim3((unsigned)rcp, (unsigned)((mp + 255) / 256)), dim3(256), 0, st, s->T,
-                                   s->Kfu, mp, rc, rcp, m, s->dY + r0 * Dy, s->vvec, Dy, s->dBeta + r0);
-                nbk = grad_generic_num_blocks(rc, m);
-                launch_grad_generic(st, p.kp, p.XtC, chunk, rc, p.XtZ, mp, m, 0, s->Kfu, mp, s->gradPart,
-                                    p.stationary() ? s->Kfu : nullptr, mp);         // H over the weights, in place
-                if (p.stationary()) ns = launch_colreduce_multi(st, s->Kfu, mp, rc, mp, p.XtC, 1, chunk, D, 1, s->colPart);
-            } else {
-                if (p.stationary() && s->fuse_cols)
-                    ns = launch_grad_cols(st, p.kp, p.XtC, chunk, rc, p.XtZ, mp, m, mp, s->T, mp, rk, s->gradPart, s->colPart, &nbk);
-                if (ns == 0) {
-                    nbk = grad_generic_num_blocks(rc, m);
-                    double* Hbuf = p.stationary() ? s->Kfu : nullptr;
-                    launch_grad_generic(st, p.kp, p.XtC, chunk, rc, p.XtZ, mp, m, 0, s->T, mp, s->gradPart, Hbuf, mp, rk);
-                    if (p.stationary()) ns = launch_colreduce_multi(st, s->Kfu, mp, rc, mp, p.XtC, 1, chunk, D, 1, s->colPart);
-                }
-            }
-            for (int g = 0; g < (p.kp.ard ? groups : 1); ++g)
-                launch_reduce_partials(st, s->gradPart + (long)g * nbk * GP_STRIDE, nbk, GP_STRIDE,
-                                       s->gradChunk + (long)g * GP_STRIDE);
-            hipLaunchKernelGGL(k_vec_axpy, dim3(1), dim3(256), 0, st, p.gradNM, s->gradChunk, (long)gsz, 1.0);
-            if (p.stationary()) launch_sum_splits(st, s->colPart, mp * (D + 1), ns, 1, p.HX);
-        }
+        sparse_rows_gradients(s, rc, s->T, s->Kfu, rk, [&]() {
+            hipLaunchKernelGGL(k_form_dLdKnm_times, dim3((unsigned)rcp, (unsigned)((mp + 255) / 256)), dim3(256), 0, st, s->T, s->Kfu,
+                               mp, rc, rcp, m, s->dY + r0 * Dy, s->vvec, Dy, s->dBeta + r0);
+        });
     }
     if (sharded(s)) {                                           // the one exchange step of pass 2 (one buffer, one all-reduce)
+        const size_t gsz = rec_doubles(s), hsz = hsum_doubles(s);
         double* rb = s->redbuf;
         for (SPart& p : s->parts) {
             HIP_CHECK(hipMemcpyAsync(rb, p.gradNM, sizeof(double) * gsz, hipMemcpyDeviceToDevice, st));
@@ -859,22 +1030,87 @@ int mi355gp_vardtc_inference_sum(mi355gp_sparse* s, int nparts, const mi355gp_pa
             rb += gsz + hsz;
         }
     }
+    return 0;
+}
+
+// dL_dR per point and output column for per-point noise (var_dtc.py:240-256 AS WRITTEN there), with s_nd = k_n^T v_d,
+// t_n = sum_j T_nj Kfu_nj, q_n = |Lm^-1 k_n|^2, r_n = |LB^-1 Lm^-1 k_n|^2 and the identity Dy q_n = 2 t_n + Dy r_n + sum_d s_nd^2:
+//   dL_dR_nd = -b/2 + (b R_nd)^2/2 + Dy b^2 psi0/2 - b^2 t_n - (Dy - 1) b^2 r_n/2 - b^2 sum_d' s_nd'^2/2
+//              - b^2 s_nd R_nd + b^2 s_nd^2/2                       (Dy = 1: the r_n and s^2 terms cancel; rowR is then empty)
+static void vardtc_dnoise_rows(long n, int Dy, double kdiag, const double* hbeta, const double* Rh, const std::vector<double>& rowS,
+                               const std::vector<double>& rowT, const std::vector<double>& rowR, double* out) {
+    for (long i = 0; i < n; ++i) {
+        const double b = hbeta[i], b2 = b * b;
+        double ss = 0.0;
+        for (int d = 0; d < Dy; ++d) ss += rowS[(size_t)i * Dy + d] * rowS[(size_t)i * Dy + d];
+        const double common = -0.5 * b + 0.5 * Dy * b2 * kdiag - b2 * rowT[(size_t)i] - 0.5 * b2 * ss -
+                              (rowR.empty() ? 0.0 : 0.5 * (Dy - 1) * b2 * rowR[(size_t)i]);
+        for (int d = 0; d < Dy; ++d) {
+            const double R = Rh[(size_t)i * Dy + d], sv = rowS[(size_t)i * Dy + d];
+            out[i * Dy + d] = common + 0.5 * b2 * R * R - b2 * sv * R + 0.5 * b2 * sv * sv;
+        }
+    }
+}
+
+// One SparseGP.parameters_changed for a SUM of kernels, scalar or per-point noise and R = Y - mean (see mi355gp.h), as
+// VarDTC.inference reads: pass 1 (the psi statistics of certain inputs), the M x M algebra, pass 2 (dL_dKnm and what the
+// kernels make of it), the Kmm gradients, the scalars.  out_scalars: see vardtc_scalars.
+int mi355gp_vardtc_inference_sum(mi355gp_sparse* s, int nparts, const mi355gp_part* parts, const double* Z, int64_t M,
+                                 const double* noise, int64_t noise_len, double extra_jitter, double* out_scalars,
+                                 double* dtheta_out, double* dZ_out, double* wv_out, double* dnoise_rows_out,
+                                 double* dLdm_out, double* stage_ms) {
+    ARG_CHECK(s && s->n > 0, "mi355gp_vardtc_inference: set_data first");
+    ARG_CHECK(parts && Z && M > 0 && out_scalars && noise, "mi355gp_vardtc_inference: bad arguments");
+    ARG_CHECK(noise_len == 1 || noise_len == s->n, "noise must have 1 or N entries");
+    const bool het = noise_len > 1;
+    ARG_CHECK(!het || dnoise_rows_out, "per-point noise: dnoise_rows_out (N x Dy) is required");
+    EngineShared gate(s->device);
+    if (int rc = sparse_open(s, nparts, parts, M)) return rc;
+    hipStream_t st = s->st;
+    const long n = s->n, m = s->m;
+    const int Dy = s->Dy;
+    // per-point precision beta_n = 1 / max(noise_n, 1e-8) (var_dtc.py:78-80)
+    // (scalar noise: the three sums are closed forms -- unused by the homoscedastic formulas -- and the precision vector is filled on
+    //  the device: the N-element host loop with its logarithms and the 1.6 MB upload cost ~1 ms per evaluation at N = 200000)
+    std::vector<double> hbeta(het ? (size_t)n : (size_t)1);
+    double glob[3] = {0.0, 0.0, 0.0};                            // sum beta_n, sum log beta_n, sum beta_n |R_n|^2
+    if (het) {
+        for (long i = 0; i < n; ++i) {
+            const double b = 1.0 / fmax(noise[i], 1e-8);
+            hbeta[(size_t)i] = b;
+            glob[0] += b;
+            glob[1] += log(b);
+            glob[2] += b * s->rowYY[(size_t)i];
+        }
+    } else {
+        hbeta[0] = 1.0 / fmax(noise[0], 1e-8);
+        glob[0] = hbeta[0] * (double)n;
+        glob[1] = log(hbeta[0]) * (double)n;
+        glob[2] = hbeta[0] * s->trYYT_local;
+    }
+    const double beta = het ? 0.0 : hbeta[0];
+    s->beta_scalar = beta;
+    s->mfma_prof.on = true;
+    s->mfma_prof.mask = 0x3u;
+    s->mfma_prof.reset();
+    if (int rc = sparse_start(s, Z, hbeta.data(), (long)hbeta.size())) return rc;
+    int inject = 0;                                            // fault injection for the tests: 1 / 2 hit Kmm's launch, 11 / 12 B's
+    {
+        const char* et = DIAG_ENV("SPARSE_PERSIST_TEST");
+        if (et && *et) inject = atoi(et);
+    }
+    if (inject == 1 || inject == 2) s->ws.persist_test = inject, s->ws.persist_skip = 0;
+    const bool want_rows = het || dLdm_out != nullptr;
+    if (int rc = vardtc_pass1(s, het, extra_jitter)) return rc;
+    if (int rc = sparse_mm_block(s, het, beta, inject)) return rc;
+    if (int rc = vardtc_pass2(s, het, want_rows)) return rc;
     sparse_kmm_gradients(s);
     HIP_CHECK(hipEventRecord(s->ev[3], st));
     // ---- small results to the host -------------------------------------------------------------------------------------
-    const size_t np_ = s->parts.size();
-    std::vector<double> gnm(np_ * gsz), gmm(np_ * gsz), HX(np_ * hsz), HZ(np_ * hsz), Zs(np_ * (size_t)D * mp);
-    std::vector<double> rowS, rowT, rowR;
+    KernGrads kg;
+    std::vector<double> rowS, rowT, rowR, Rh;
     double scal[8];
-    for (size_t i = 0; i < np_; ++i) {
-        SPart& p = s->parts[i];
-        HIP_CHECK(hipMemcpyAsync(gnm.data() + i * gsz, p.gradNM, sizeof(double) * gsz, hipMemcpyDeviceToHost, st));
-        HIP_CHECK(hipMemcpyAsync(gmm.data() + i * gsz, p.gradMM, sizeof(double) * gsz, hipMemcpyDeviceToHost, st));
-        if (!p.stationary()) continue;
-        HIP_CHECK(hipMemcpyAsync(HX.data() + i * hsz, p.HX, sizeof(double) * hsz, hipMemcpyDeviceToHost, st));
-        HIP_CHECK(hipMemcpyAsync(HZ.data() + i * hsz, p.HZ, sizeof(double) * hsz, hipMemcpyDeviceToHost, st));
-        HIP_CHECK(hipMemcpyAsync(Zs.data() + i * (size_t)D * mp, p.XtZ, sizeof(double) * D * mp, hipMemcpyDeviceToHost, st));
-    }
+    if (int rc = sparse_fetch_gradients(s, true, &kg)) return rc;
     HIP_CHECK(hipMemcpyAsync(scal, s->scal, sizeof(double) * 4, hipMemcpyDeviceToHost, st));
     if (wv_out) HIP_CHECK(hipMemcpyAsync(wv_out, s->vvec, sizeof(double) * m * Dy, hipMemcpyDeviceToHost, st));
     if (want_rows) {
@@ -883,118 +1119,31 @@ int mi355gp_vardtc_inference_sum(mi355gp_sparse* s, int nparts, const mi355gp_pa
         if (het) {
             rowT.resize((size_t)n);
             HIP_CHECK(hipMemcpyAsync(rowT.data(), s->dRowT, sizeof(double) * n, hipMemcpyDeviceToHost, st));
-            if (het_multi) {
+            if (Dy > 1) {
                 rowR.resize((size_t)n);
                 HIP_CHECK(hipMemcpyAsync(rowR.data(), s->dRowR, sizeof(double) * n, hipMemcpyDeviceToHost, st));
             }
         }
     }
-    HIP_CHECK(hipStreamSynchronize(st));
-    HIP_CHECK(hipGetLastError());
-    if (stage_ms) {
-        float ms;
-        for (int i = 0; i < 3; ++i) {
-            HIP_CHECK(hipEventElapsedTime(&ms, s->ev[i], s->ev[i + 1]));
-            stage_ms[i] = ms;
-        }
-        HIP_CHECK(hipEventElapsedTime(&ms, s->ev[0], s->ev[3]));
-        stage_ms[3] = ms;
-    }
-    const int info_m = s->h_info[0], info_b = s->h_info[1];
-    if (info_m > 0) return info_m > m ? (int)m : info_m;                 // Kmm not positive definite: caller adds jitter
-    if (info_b > 0) return info_b > m ? (int)m : info_b;
-    // sums over ALL shards of the per-point quantities
-    double glob[3] = {sum_beta, sum_logbeta, sum_bYY};
-    if (sharded(s)) {
+    if (int rc = sparse_finish(s, 3, stage_ms)) return rc;      // (info > 0: Kmm or B not positive definite, the caller adds jitter)
+    if (sharded(s)) {                                           // sums over ALL shards of the per-point quantities
         HIP_CHECK(hipMemcpy(s->scal + 4, glob, sizeof(glob), hipMemcpyHostToDevice));
         if (int rc = sparse_allreduce(s, s->scal + 4, 3)) return rc;
         HIP_CHECK(hipStreamSynchronize(st));
         HIP_CHECK(hipMemcpy(glob, s->scal + 4, sizeof(glob), hipMemcpyDeviceToHost));
     }
-    const double trA = scal[0], sumAP = scal[1], logLB = scal[2], data_fit = scal[3];
-    const double ng = (double)s->n_global, nd = ng * Dy;
     const double kdiag = expression_kdiag(s->parts, s->terms);                        // psi0_n = Kdiag of the expression
-    // _compute_log_marginal_likelihood (var_dtc.py:264-276)
-    double lik_1, lik_2;
-    if (het) {
-        lik_1 = -0.5 * nd * log(2.0 * M_PI) + 0.5 * Dy * glob[1] - 0.5 * glob[2];
-        lik_2 = -0.5 * Dy * (glob[0] * kdiag - trA);
-    } else {
-        lik_1 = -0.5 * nd * (log(2.0 * M_PI) - log(beta)) - 0.5 * beta * s->trYYT;
-        lik_2 = -0.5 * Dy * (beta * ng * kdiag - trA);
-    }
-    const double lik_3 = -(double)Dy * logLB;
-    for (int i = 0; i < MI355GP_NUM_OUT; ++i) out_scalars[i] = 0.0;
-    out_scalars[0] = lik_1 + lik_2 + lik_3 + 0.5 * data_fit;
-    out_scalars[2] = trA;
-    out_scalars[3] = data_fit;
-    out_scalars[4] = logLB;
-    out_scalars[5] = beta;
-    if (!het) {                                                  // _compute_dL_dR (var_dtc.py:258-261)
-        double dL_dR = -0.5 * nd * beta + 0.5 * s->trYYT * beta * beta;
-        dL_dR += 0.5 * Dy * (ng * kdiag * beta * beta - trA * beta);
-        dL_dR += beta * (0.5 * sumAP - data_fit);
-        out_scalars[1] = dL_dR;
-    } else {
-        // per point and output column (var_dtc.py:240-256 AS WRITTEN there), with s_nd = k_n^T v_d, t_n = sum_j T_nj Kfu_nj,
-        // q_n = |Lm^-1 k_n|^2, r_n = |LB^-1 Lm^-1 k_n|^2 and the identity Dy q_n = 2 t_n + Dy r_n + sum_d s_nd^2:
-        //   dL_dR_nd = -b/2 + (b R_nd)^2/2 + Dy b^2 psi0/2 - b^2 t_n - (Dy - 1) b^2 r_n/2 - b^2 sum_d' s_nd'^2/2
-        //              - b^2 s_nd R_nd + b^2 s_nd^2/2                       (Dy = 1: the r_n and s^2 terms cancel)
-        std::vector<double> Rh((size_t)n * Dy);
+    vardtc_scalars(s, scal, kdiag, beta, glob, out_scalars);
+    if (want_rows) {
+        Rh.resize((size_t)n * Dy);
         HIP_CHECK(hipMemcpy(Rh.data(), s->dY, sizeof(double) * n * Dy, hipMemcpyDeviceToHost));
-        for (long i = 0; i < n; ++i) {
-            const double b = hbeta[(size_t)i], b2 = b * b;
-            double ss = 0.0;
-            for (int d = 0; d < Dy; ++d) ss += rowS[(size_t)i * Dy + d] * rowS[(size_t)i * Dy + d];
-            const double common = -0.5 * b + 0.5 * Dy * b2 * kdiag - b2 * rowT[(size_t)i] - 0.5 * b2 * ss -
-                                  (het_multi ? 0.5 * (Dy - 1) * b2 * rowR[(size_t)i] : 0.0);
-            for (int d = 0; d < Dy; ++d) {
-                const double R = Rh[(size_t)i * Dy + d], sv = rowS[(size_t)i * Dy + d];
-                dnoise_rows_out[i * Dy + d] = common + 0.5 * b2 * R * R - b2 * sv * R + 0.5 * b2 * sv * sv;
-            }
-        }
     }
-    if (dLdm_out) {                                              // dL_dm = V - Kfu v (var_dtc.py:148)
-        std::vector<double> Rh((size_t)n * Dy);
-        HIP_CHECK(hipMemcpy(Rh.data(), s->dY, sizeof(double) * n * Dy, hipMemcpyDeviceToHost));
+    if (het) vardtc_dnoise_rows(n, Dy, kdiag, hbeta.data(), Rh.data(), rowS, rowT, rowR, dnoise_rows_out);
+    if (dLdm_out)                                                // dL_dm = V - Kfu v (var_dtc.py:148)
         for (long i = 0; i < n; ++i)
             for (int d = 0; d < Dy; ++d) dLdm_out[i * Dy + d] = hbeta[het ? (size_t)i : (size_t)0] * Rh[(size_t)i * Dy + d] - rowS[(size_t)i * Dy + d];
-    }
-    if (dtheta_out) {
-        double* o = dtheta_out;
-        std::vector<double> ab(gsz);                              // the Knm and Kmm records of a part summed
-        for (size_t i = 0; i < np_; ++i) {
-            const double* a = gnm.data() + i * gsz;
-            const double* b = gmm.data() + i * gsz;
-            for (size_t k = 0; k < gsz; ++k) ab[k] = a[k] + b[k];
-            const int k = part_dtheta(s->parts[i], ab.data(), nullptr, o);
-            // update_gradients_diag(dL_dKdiag = -0.5 Dy beta_n) (sparse_gp.py:110, stationary.py:175-184, static.py:95-96)
-            // (a factor of a product: dKdiag / dvariance = the product of the other factors' variances, prod.py:67-71)
-            o[0] = -0.5 * Dy * glob[0] * sparse_other_variances(s, i) + o[0];
-            o += k;
-        }
-    }
-    if (dZ_out) {
-        // gradients_X(dL_dKnm^T, Z, X) + gradients_X(dL_dKmm, Z) (sparse_gp.py:116-118), summed over the parts (add.py:84-88):
-        //   sum_n H[n,m] (z~_mq - x~_nq) / l_q  +  2 sum_j Hmm[j,m] (z~_mq - z~_jq) / l_q
-        for (long j = 0; j < m * D; ++j) dZ_out[j] = 0.0;
-        for (size_t i = 0; i < np_; ++i) {
-            const SPart& p = s->parts[i];
-            if (!p.stationary()) continue;
-            const double* hx = HX.data() + i * hsz;
-            const double* hz = HZ.data() + i * hsz;
-            const double* zs = Zs.data() + i * (size_t)D * mp;
-            for (long j = 0; j < m; ++j)
-                for (int q = 0; q < D; ++q) {
-                    const double il = p.inv_ls[(size_t)q];
-                    if (il == 0.0) continue;
-                    const double z = zs[(size_t)q * mp + j];
-                    const double a = z * hx[j * (D + 1) + D] - hx[j * (D + 1) + q];
-                    const double b = z * hz[j * (D + 1) + D] - hz[j * (D + 1) + q];
-                    dZ_out[j * D + q] += (a + 2.0 * b) * il;
-                }
-        }
-    }
+    // update_gradients_diag(dL_dKdiag = -0.5 Dy beta_n) (sparse_gp.py:110)
+    sparse_assemble_gradients(s, kg, -0.5 * Dy * glob[0], dtheta_out, dZ_out);
     s->have_result = true;
     s->uncertain_result = false;
     return 0;
@@ -1010,6 +1159,7 @@ int mi355gp_vardtc_inference(mi355gp_sparse* s, int kind, int ard, const double*
                                         nullptr, nullptr, stage_ms);
 }
 
+// ---- VarDTC with uncertain inputs -----------------------------------------------------------------------------------------
 // out = scale * (A + A^T) / 2 over the leading m x m of mp x mp matrices, 0 in the padding (rbf_psi_comp.py:109)
 __global__ void k_sym_scaled(const double* __restrict__ A, long mp, long m, double scale, double* __restrict__ out) {
     const long j = (long)blockIdx.x * blockDim.x + threadIdx.x, i = blockIdx.y;
@@ -1017,27 +1167,116 @@ __global__ void k_sym_scaled(const double* __restrict__ A, long mp, long m, doub
     out[i * mp + j] = (i < m && j < m) ? 0.5 * scale * (A[i * mp + j] + A[j * mp + i]) : 0.0;
 }
 
-// One SparseGP.parameters_changed for UNCERTAIN inputs q(x_n) = N(X_n, diag S_n) (set_data + set_input_variance), a scalar
-// noise variance and one RBF part alone or with White parts (var_dtc.py:93-120,133-163,217-233,258-276 with psi statistics
-// in place of Kdiag / Knm / Knm^T Knm; rbf_psi_comp.py; static.py: White adds its variance to psi0 and to Kmm's diagonal).
-//   pass 1 over chunks of PSI_CHUNK rows: psi1 chunk -> psi1^T V, psi2 += the chunk's sum (fixed order)
-//   the M x M phase of the certain-input call (sparse_mm_block)
-//   pass 2: the psi1 / psi2 gradient kernels with dL_dpsi1 = beta R v^T formed on the fly, dL_dpsi2 = beta Q2,
-//           dL_dpsi0 = -Dy beta / 2; then the Kmm gradients as for certain inputs
-// out_scalars, dtheta_out (concatenated over the parts), dZ_out, wv_out, stage_ms as mi355gp_vardtc_inference_sum;
-// dmu_out / dS_out (optional, N x D): the gradients with respect to the means and variances of the inputs.
-int mi355gp_vardtc_inference_uncertain(mi355gp_sparse* s, int nparts, const mi355gp_part* parts, const double* Z, int64_t M,
-                                       const double* noise, int64_t noise_len, double extra_jitter, double* out_scalars,
-                                       double* dtheta_out, double* dZ_out, double* wv_out, double* dmu_out, double* dS_out,
-                                       double* stage_ms) {
+// The psi kernels' operands and partial sums for one call: a_q = 1 / l_q^2 (0 on a dimension the RBF part does not see), Z zero
+// padded to mpad x Qp, the per-chunk row records and the sums the two passes leave behind
+struct PsiWork {
+    int Qp = 0, RL = 0;
+    long mpad = 0, ld2 = 0, mt = 0, chunk = 0;
+    double var = 0.0;                       // the RBF part's variance
+    std::vector<double> ha, hzp, sums;      // a_q; padded Z; [0] the variance record, [1 + q] the lengthscale sums of psi1 and psi2
+    DevBuf dA, dZp, rd1, rd2, lg1, lg2, Ppart, P1s, P2s, Zpart, Zs1, Zs2, dMuO, dSO, rowrec, rec, zz;
+};
+
+static int psi_work_setup(mi355gp_sparse* s, const SPart& rbf, const double* Z, PsiWork* w) {
+    const long n = s->n, m = s->m;
+    const int D = s->D, Qp = psi_qp(D);
+    w->Qp = Qp;
+    w->RL = 1 + 2 * Qp;
+    w->var = rbf.kp.variance;
+    w->mpad = round_up(m, PSI_KT);
+    w->ld2 = round_up(m, PSI_T2);
+    w->mt = (m + 15) / 16;
+    w->chunk = n < PSI_CHUNK ? n : PSI_CHUNK;
+    const long chunk = w->chunk, mpad = w->mpad, nzb = (chunk + PSI_GROWS - 1) / PSI_GROWS;
+    std::vector<double>& hzp = w->hzp;
+    hzp.assign((size_t)mpad * Qp, 0.0);
+    w->ha.assign((size_t)Qp, 0.0);
+    w->sums.assign((size_t)(1 + Qp), 0.0);
+    for (int q = 0; q < D; ++q) w->ha[(size_t)q] = rbf.inv_ls[(size_t)q] * rbf.inv_ls[(size_t)q];
+    for (long i = 0; i < m; ++i)
+        for (int q = 0; q < D; ++q) hzp[(size_t)i * Qp + q] = Z[i * D + q];
+    HIP_CHECK(w->dA.alloc(Qp));
+    HIP_CHECK(w->dZp.alloc(hzp.size()));
+    HIP_CHECK(w->rd1.alloc(2 * chunk * Qp));
+    HIP_CHECK(w->rd2.alloc(2 * chunk * Qp));
+    HIP_CHECK(w->lg1.alloc(chunk));
+    HIP_CHECK(w->lg2.alloc(chunk));
+    HIP_CHECK(w->Ppart.alloc((size_t)w->mt * chunk * w->RL));
+    HIP_CHECK(w->P1s.alloc((size_t)chunk * w->RL));
+    HIP_CHECK(w->P2s.alloc((size_t)chunk * w->RL));
+    HIP_CHECK(w->Zpart.alloc((size_t)nzb * mpad * Qp));
+    HIP_CHECK(w->Zs1.alloc((size_t)mpad * Qp));
+    HIP_CHECK(w->Zs2.alloc((size_t)mpad * Qp));
+    HIP_CHECK(w->dMuO.alloc(n * D));
+    HIP_CHECK(w->dSO.alloc(n * D));
+    HIP_CHECK(w->rowrec.alloc((size_t)chunk * (1 + Qp)));
+    HIP_CHECK(w->rec.alloc(1 + Qp));
+    HIP_CHECK(w->zz.alloc((size_t)m * 2 * Qp));
+    HIP_CHECK(hipMemcpyAsync(w->dA, w->ha.data(), sizeof(double) * Qp, hipMemcpyHostToDevice, s->st));
+    HIP_CHECK(hipMemcpyAsync(w->dZp, hzp.data(), sizeof(double) * hzp.size(), hipMemcpyHostToDevice, s->st));
+    HIP_CHECK(hipMemsetAsync(w->Zpart, 0, sizeof(double) * nzb * mpad * Qp, s->st));   // the kernels write rows < round_up(m, 16) only
+    return 0;
+}
+
+// Kmm, Lm, Xm as for certain inputs, on the main stream; pass 1 over chunks of PSI_CHUNK rows: psi1 chunk (in the Kfu buffer,
+// ld mp) -> psi1^T V, psi2 += the chunk's sum (fixed order); records ev[1]
+static int uncertain_pass1(mi355gp_sparse* s, PsiWork& w, double extra_jitter) {
+    hipStream_t st = s->st;
+    const long n = s->n, m = s->m, mp = s->mp;
+    const int D = s->D, Dy = s->Dy;
+    auto rebuild_kmm = [&]() { build_kmm(s, s->Lm, s->T1, 1e-8 + extra_jitter, /*lower_only=*/1, st); };
+    rebuild_kmm();
+    if (int rc = potrf_checked(st, s->Lm, s->Xm, s->Tm, nullptr, mp, &s->ws, &s->h_info[0], rebuild_kmm)) return rc;
+    HIP_CHECK(hipMemsetAsync(s->psi1Y, 0, sizeof(double) * mp * Dy, st));
+    HIP_CHECK(hipMemsetAsync(s->psi2, 0, sizeof(double) * mp * mp, st));
+    int nch = 0;
+    for (long r0 = 0; r0 < n; r0 += PSI_CHUNK, ++nch) {
+        const long rc = (n - r0 < PSI_CHUNK) ? (n - r0) : PSI_CHUNK;
+        launch_psi_rows(st, s->dX + r0 * D, s->dSvar + r0 * D, w.dA, rc, D, w.Qp, w.rd1, w.rd2, w.lg1, w.lg2);
+        HIP_CHECK(hipMemsetAsync(s->Kfu, 0, sizeof(double) * rc * mp, st));          // psi1 writes columns < m only
+        launch_psi1(st, w.rd1, w.lg1, w.dZp, rc, m, w.mpad, w.Qp, w.var, s->Kfu, mp);
+        const int nsc = launch_colreduce_multi(st, s->Kfu, mp, rc, mp, s->dV + r0 * Dy, Dy, 1, Dy, 0, s->colPart);
+        launch_sum_splits(st, s->colPart, mp * Dy, nsc, 1, s->psi1Y);                 // psi1^T V += psi1_chunk^T V_chunk
+        const int ns = launch_psi2(st, w.rd2, w.lg2, nullptr, w.dZp, w.dA, rc, m, w.Qp, w.var * w.var, w.ld2, s->psi2part);
+        launch_psi2_combine(st, s->psi2part, w.ld2, m, ns, nch > 0, s->psi2, mp);
+    }
+    HIP_CHECK(hipEventRecord(s->ev[1], st));
+    return 0;
+}
+
+// pass 2, the chain rule through psi1 and psi2: the psi1 / psi2 gradient kernels with dL_dpsi1 = beta R v^T formed on the fly
+// and dL_dpsi2 = beta Q2 symmetrised (in E; LS = dL_dpsi2 * psi2 carries the z_m - z_o terms); leaves dmu / dS per row, the Z
+// sums (Zs1, Zs2, zz) and, on the host, w.sums
+static int uncertain_pass2(mi355gp_sparse* s, PsiWork& w, double beta) {
+    hipStream_t st = s->st;
+    const long n = s->n, m = s->m, mp = s->mp;
+    const int D = s->D, Dy = s->Dy, Qp = w.Qp;
+    hipLaunchKernelGGL(k_sym_scaled, grid2d(mp, mp), dim3(256), 0, st, s->Q2, mp, m, beta, s->E);
+    launch_psi2_zz(st, s->E, s->psi2, mp, w.dZp, m, Qp, w.zz);
+    std::vector<double> csum((size_t)(1 + Qp));
+    int nch = 0;
+    for (long r0 = 0; r0 < n; r0 += PSI_CHUNK, ++nch) {
+        const long rc = (n - r0 < PSI_CHUNK) ? (n - r0) : PSI_CHUNK;
+        const int nb = (int)((rc + PSI_GROWS - 1) / PSI_GROWS);
+        launch_psi_rows(st, s->dX + r0 * D, s->dSvar + r0 * D, w.dA, rc, D, Qp, w.rd1, w.rd2, w.lg1, w.lg2);
+        launch_psi1_grad(st, w.rd1, w.lg1, w.dZp, nullptr, 0, PsiRank{s->dY + r0 * Dy, s->vvec, Dy, beta}, rc, m, w.mpad, Qp, w.var,
+                         w.Ppart, w.Zpart);
+        launch_sum_splits(st, w.Ppart, rc * w.RL, (int)w.mt, 0, w.P1s);
+        launch_sum_splits(st, w.Zpart, w.mpad * Qp, nb, nch > 0, w.Zs1);
+        launch_psi2_grad(st, w.rd2, w.lg2, nullptr, w.dZp, w.dA, s->E, mp, rc, m, w.mpad, Qp, w.var * w.var, w.Ppart, w.Zpart);
+        launch_sum_splits(st, w.Ppart, rc * w.RL, (int)w.mt, 0, w.P2s);
+        launch_sum_splits(st, w.Zpart, w.mpad * Qp, nb, nch > 0, w.Zs2);
+        launch_psi_rowfinish(st, w.P1s, w.P2s, s->dSvar + r0 * D, w.dA, rc, D, Qp, w.dMuO + r0 * D, w.dSO + r0 * D, w.rowrec);
+        launch_reduce_partials(st, w.rowrec, (int)rc, 1 + Qp, w.rec);
+        HIP_CHECK(hipMemcpyAsync(csum.data(), w.rec, sizeof(double) * (1 + Qp), hipMemcpyDeviceToHost, st));
+        HIP_CHECK(hipStreamSynchronize(st));
+        for (int k = 0; k <= Qp; ++k) w.sums[(size_t)k] += csum[(size_t)k];           // chunks in row order
+    }
+    return 0;
+}
+
+static int uncertain_check_parts(const mi355gp_sparse* s, int nparts, const mi355gp_part* parts, int64_t M, int* irbf_out) {
     const char* where = "mi355gp_vardtc_inference_uncertain";
-    ARG_CHECK(s && s->n > 0, "mi355gp_vardtc_inference_uncertain: set_data first");
-    ARG_CHECK(parts && Z && M > 0 && out_scalars && noise && nparts >= 1, "mi355gp_vardtc_inference_uncertain: bad arguments");
-    ARG_CHECK(!sharded(s), "mi355gp_vardtc_inference_uncertain: a row-sharded context is not supported with uncertain inputs");
-    ARG_CHECK(s->dSvar, "mi355gp_vardtc_inference_uncertain: no input variances; call mi355gp_sparse_set_input_variance after set_data");
-    if (noise_len != 1)
-        PART_FAIL("%s: per-point noise (%lld variances) is not supported with uncertain inputs (var_dtc.py:243); pass one noise variance",
-                  where, (long long)noise_len);
     int irbf = -1;
     for (int i = 0; i < nparts; ++i) {
         if (parts[i].term != 0) PART_FAIL("%s: part %d is a factor of a product; products have no psi statistics here", where, i);
@@ -1051,203 +1290,92 @@ int mi355gp_vardtc_inference_uncertain(mi355gp_sparse* s, int nparts, const mi35
     if (irbf < 0) PART_FAIL("%s: no RBF part; uncertain inputs take one RBF part and White parts only", where);
     ARG_CHECK(s->D <= PSI_QMAX, "mi355gp_vardtc_inference_uncertain: the psi-statistics kernels take at most 64 input dimensions");
     ARG_CHECK(M <= PSI_MMAX, "mi355gp_vardtc_inference_uncertain: the psi-statistics kernels take at most 65535 inducing points");
-    HIP_CHECK(hipSetDevice(s->device));
+    *irbf_out = irbf;
+    return 0;
+}
+
+// One SparseGP.parameters_changed for UNCERTAIN inputs q(x_n) = N(X_n, diag S_n) (set_data + set_input_variance), a scalar
+// noise variance and one RBF part alone or with White parts (var_dtc.py:93-120,133-163,217-233,258-276 with psi statistics
+// in place of Kdiag / Knm / Knm^T Knm; rbf_psi_comp.py; static.py: White adds its variance to psi0 and to Kmm's diagonal):
+// the phases of the certain-input call with the psi kernels in the two passes and dL_dpsi0 = -Dy beta / 2.
+// out_scalars, dtheta_out (concatenated over the parts), dZ_out, wv_out, stage_ms as mi355gp_vardtc_inference_sum;
+// dmu_out / dS_out (optional, N x D): the gradients with respect to the means and variances of the inputs.
+int mi355gp_vardtc_inference_uncertain(mi355gp_sparse* s, int nparts, const mi355gp_part* parts, const double* Z, int64_t M,
+                                       const double* noise, int64_t noise_len, double extra_jitter, double* out_scalars,
+                                       double* dtheta_out, double* dZ_out, double* wv_out, double* dmu_out, double* dS_out,
+                                       double* stage_ms) {
+    ARG_CHECK(s && s->n > 0, "mi355gp_vardtc_inference_uncertain: set_data first");
+    ARG_CHECK(parts && Z && M > 0 && out_scalars && noise && nparts >= 1, "mi355gp_vardtc_inference_uncertain: bad arguments");
+    ARG_CHECK(!sharded(s), "mi355gp_vardtc_inference_uncertain: a row-sharded context is not supported with uncertain inputs");
+    ARG_CHECK(s->dSvar, "mi355gp_vardtc_inference_uncertain: no input variances; call mi355gp_sparse_set_input_variance after set_data");
+    if (noise_len != 1)
+        PART_FAIL("mi355gp_vardtc_inference_uncertain: per-point noise (%lld variances) is not supported with uncertain inputs "
+                  "(var_dtc.py:243); pass one noise variance", (long long)noise_len);
+    int irbf = -1;
+    if (int rc = uncertain_check_parts(s, nparts, parts, M, &irbf)) return rc;
     EngineShared gate(s->device);
-    const int D = s->D, Dy = s->Dy;
-    if (M != s->m)
-        if (int rc = alloc_m(s, M)) return rc;
-    if (int rc = prepare_sparse_parts(s, nparts, parts)) return rc;
+    if (int rc = sparse_open(s, nparts, parts, M)) return rc;
     hipStream_t st = s->st;
-    const long n = s->n, m = s->m, mp = s->mp;
-    const int groups = (D + 31) / 32;
-    const size_t gsz = (size_t)groups * GP_STRIDE, hsz = (size_t)mp * (D + 1);
+    const long n = s->n, m = s->m;
+    const int D = s->D, Dy = s->Dy;
     const double beta = 1.0 / fmax(noise[0], 1e-8);
     s->beta_scalar = beta;
     s->mfma_prof.on = false;
-    s->have_result = s->winv_ok = s->svgp_result = false;
-    // the psi kernels' operands: a_q = 1 / l_q^2 (0 on a dimension the RBF part does not see), Z zero padded to mpad x Qp
     const SPart& rbf = s->parts[(size_t)irbf];
-    const double var = rbf.kp.variance;
-    const int Qp = psi_qp(D), RL = 1 + 2 * Qp;
-    const long mpad = round_up(m, PSI_KT), ld2 = round_up(m, PSI_T2), mt = (m + 15) / 16;
-    const long chunk = n < PSI_CHUNK ? n : PSI_CHUNK, nzb = (chunk + PSI_GROWS - 1) / PSI_GROWS;
-    std::vector<double> ha((size_t)Qp, 0.0), hzp((size_t)mpad * Qp, 0.0);
-    for (int q = 0; q < D; ++q) ha[(size_t)q] = rbf.inv_ls[(size_t)q] * rbf.inv_ls[(size_t)q];
-    for (long i = 0; i < m; ++i)
-        for (int q = 0; q < D; ++q) hzp[(size_t)i * Qp + q] = Z[i * D + q];
-    DevBuf dA, dZp, rd1, rd2, lg1, lg2, Ppart, P1s, P2s, Zpart, Zs1, Zs2, dMuO, dSO, rowrec, rec, zz;
-    HIP_CHECK(dA.alloc(Qp));
-    HIP_CHECK(dZp.alloc(hzp.size()));
-    HIP_CHECK(rd1.alloc(2 * chunk * Qp));
-    HIP_CHECK(rd2.alloc(2 * chunk * Qp));
-    HIP_CHECK(lg1.alloc(chunk));
-    HIP_CHECK(lg2.alloc(chunk));
-    HIP_CHECK(Ppart.alloc((size_t)mt * chunk * RL));
-    HIP_CHECK(P1s.alloc((size_t)chunk * RL));
-    HIP_CHECK(P2s.alloc((size_t)chunk * RL));
-    HIP_CHECK(Zpart.alloc((size_t)nzb * mpad * Qp));
-    HIP_CHECK(Zs1.alloc((size_t)mpad * Qp));
-    HIP_CHECK(Zs2.alloc((size_t)mpad * Qp));
-    HIP_CHECK(dMuO.alloc(n * D));
-    HIP_CHECK(dSO.alloc(n * D));
-    HIP_CHECK(rowrec.alloc((size_t)chunk * (1 + Qp)));
-    HIP_CHECK(rec.alloc(1 + Qp));
-    HIP_CHECK(zz.alloc((size_t)m * 2 * Qp));
-    HIP_CHECK(hipMemcpyAsync(dA, ha.data(), sizeof(double) * Qp, hipMemcpyHostToDevice, st));
-    HIP_CHECK(hipMemcpyAsync(dZp, hzp.data(), sizeof(double) * hzp.size(), hipMemcpyHostToDevice, st));
-    HIP_CHECK(hipMemsetAsync(Zpart, 0, sizeof(double) * nzb * mpad * Qp, st));   // the kernels write rows < round_up(m, 16) only
-    hipLaunchKernelGGL(k_fill_const, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, s->dBeta, n, beta);
-    HIP_CHECK(hipMemcpyAsync(s->dZ, Z, sizeof(double) * m * D, hipMemcpyHostToDevice, st));
-    HIP_CHECK(hipEventRecord(s->ev[0], st));
-    {   // V = beta * R
-        const long cnt = n * Dy;
-        hipLaunchKernelGGL(k_scale_rows, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, st, s->dY, s->dBeta, cnt, Dy, s->dV);
-    }
-    scale_for_parts(s, s->dZ, m, mp, true);
-    // Kmm + 1e-8 I (var_dtc.py:93-94), Lm = chol, Xm = Lm^-1 -- as for certain inputs, on the main stream
-    s->h_info[0] = s->h_info[1] = 0;
-    auto rebuild_kmm = [&]() { build_kmm(s, s->Lm, s->T1, 1e-8 + extra_jitter, /*lower_only=*/1, st); };
-    rebuild_kmm();
-    if (int rc = potrf_checked(st, s->Lm, s->Xm, s->Tm, nullptr, mp, &s->ws, &s->h_info[0], rebuild_kmm)) return rc;
-    // ---- pass 1: psi1 chunk (in the Kfu buffer, ld mp) -> psi1^T V; psi2 += sum over the chunk's rows ---------------------
-    HIP_CHECK(hipMemsetAsync(s->psi1Y, 0, sizeof(double) * mp * Dy, st));
-    HIP_CHECK(hipMemsetAsync(s->psi2, 0, sizeof(double) * mp * mp, st));
-    int nch = 0;
-    for (long r0 = 0; r0 < n; r0 += PSI_CHUNK, ++nch) {
-        const long rc = (n - r0 < PSI_CHUNK) ? (n - r0) : PSI_CHUNK;
-        launch_psi_rows(st, s->dX + r0 * D, s->dSvar + r0 * D, dA, rc, D, Qp, rd1, rd2, lg1, lg2);
-        HIP_CHECK(hipMemsetAsync(s->Kfu, 0, sizeof(double) * rc * mp, st));          // psi1 writes columns < m only
-        launch_psi1(st, rd1, lg1, dZp, rc, m, mpad, Qp, var, s->Kfu, mp);
-        const int nsc = launch_colreduce_multi(st, s->Kfu, mp, rc, mp, s->dV + r0 * Dy, Dy, 1, Dy, 0, s->colPart);
-        launch_sum_splits(st, s->colPart, mp * Dy, nsc, 1, s->psi1Y);                 // psi1^T V += psi1_chunk^T V_chunk
-        const int ns = launch_psi2(st, rd2, lg2, nullptr, dZp, dA, rc, m, Qp, var * var, ld2, s->psi2part);
-        launch_psi2_combine(st, s->psi2part, ld2, m, ns, nch > 0, s->psi2, mp);
-    }
-    HIP_CHECK(hipEventRecord(s->ev[1], st));
-    // ---- the M x M phase: A = Lm^-1 (beta psi2) Lm^-T and everything that follows, exactly as for certain inputs ----------
+    PsiWork w;
+    if (int rc = psi_work_setup(s, rbf, Z, &w)) return rc;
+    if (int rc = sparse_start(s, Z, &beta, 1)) return rc;
+    if (int rc = uncertain_pass1(s, w, extra_jitter)) return rc;
     if (int rc = sparse_mm_block(s, false, beta, 0)) return rc;
-    // ---- pass 2: the chain rule through psi1 and psi2 ---------------------------------------------------------------------
-    // dL_dpsi2 = beta Q2 symmetrised (in E), LS = dL_dpsi2 * psi2 carries the z_m - z_o terms
-    hipLaunchKernelGGL(k_sym_scaled, grid2d(mp, mp), dim3(256), 0, st, s->Q2, mp, m, beta, s->E);
-    launch_psi2_zz(st, s->E, s->psi2, mp, dZp, m, Qp, zz);
-    std::vector<double> sums((size_t)(1 + Qp), 0.0), csum((size_t)(1 + Qp));
-    nch = 0;
-    for (long r0 = 0; r0 < n; r0 += PSI_CHUNK, ++nch) {
-        const long rc = (n - r0 < PSI_CHUNK) ? (n - r0) : PSI_CHUNK;
-        const int nb = (int)((rc + PSI_GROWS - 1) / PSI_GROWS);
-        launch_psi_rows(st, s->dX + r0 * D, s->dSvar + r0 * D, dA, rc, D, Qp, rd1, rd2, lg1, lg2);
-        launch_psi1_grad(st, rd1, lg1, dZp, nullptr, 0, PsiRank{s->dY + r0 * Dy, s->vvec, Dy, beta}, rc, m, mpad, Qp, var, Ppart,
-                         Zpart);
-        launch_sum_splits(st, Ppart, rc * RL, (int)mt, 0, P1s);
-        launch_sum_splits(st, Zpart, mpad * Qp, nb, nch > 0, Zs1);
-        launch_psi2_grad(st, rd2, lg2, nullptr, dZp, dA, s->E, mp, rc, m, mpad, Qp, var * var, Ppart, Zpart);
-        launch_sum_splits(st, Ppart, rc * RL, (int)mt, 0, P2s);
-        launch_sum_splits(st, Zpart, mpad * Qp, nb, nch > 0, Zs2);
-        launch_psi_rowfinish(st, P1s, P2s, s->dSvar + r0 * D, dA, rc, D, Qp, dMuO + r0 * D, dSO + r0 * D, rowrec);
-        launch_reduce_partials(st, rowrec, (int)rc, 1 + Qp, rec);
-        HIP_CHECK(hipMemcpyAsync(csum.data(), rec, sizeof(double) * (1 + Qp), hipMemcpyDeviceToHost, st));
-        HIP_CHECK(hipStreamSynchronize(st));
-        for (int k = 0; k <= Qp; ++k) sums[(size_t)k] += csum[(size_t)k];             // chunks in row order
-    }
+    if (int rc = uncertain_pass2(s, w, beta)) return rc;
     sparse_kmm_gradients(s);
     HIP_CHECK(hipEventRecord(s->ev[3], st));
     // ---- small results to the host -----------------------------------------------------------------------------------------
-    const size_t np_ = s->parts.size();
-    std::vector<double> gmm(np_ * gsz), HZ(hsz), Zs((size_t)D * mp), zs1((size_t)mpad * Qp), zs2((size_t)mpad * Qp),
-        zzh((size_t)m * 2 * Qp);
+    const int Qp = w.Qp;
+    KernGrads kg;
+    std::vector<double> zs1((size_t)w.mpad * Qp), zs2((size_t)w.mpad * Qp), zzh((size_t)m * 2 * Qp);
     double scal[8];
-    for (size_t i = 0; i < np_; ++i)
-        HIP_CHECK(hipMemcpyAsync(gmm.data() + i * gsz, s->parts[i].gradMM, sizeof(double) * gsz, hipMemcpyDeviceToHost, st));
-    HIP_CHECK(hipMemcpyAsync(HZ.data(), rbf.HZ, sizeof(double) * hsz, hipMemcpyDeviceToHost, st));
-    HIP_CHECK(hipMemcpyAsync(Zs.data(), rbf.XtZ, sizeof(double) * D * mp, hipMemcpyDeviceToHost, st));
-    HIP_CHECK(hipMemcpyAsync(zs1.data(), Zs1, sizeof(double) * zs1.size(), hipMemcpyDeviceToHost, st));
-    HIP_CHECK(hipMemcpyAsync(zs2.data(), Zs2, sizeof(double) * zs2.size(), hipMemcpyDeviceToHost, st));
-    HIP_CHECK(hipMemcpyAsync(zzh.data(), zz, sizeof(double) * zzh.size(), hipMemcpyDeviceToHost, st));
+    if (int rc = sparse_fetch_gradients(s, false, &kg)) return rc;
+    HIP_CHECK(hipMemcpyAsync(zs1.data(), w.Zs1, sizeof(double) * zs1.size(), hipMemcpyDeviceToHost, st));
+    HIP_CHECK(hipMemcpyAsync(zs2.data(), w.Zs2, sizeof(double) * zs2.size(), hipMemcpyDeviceToHost, st));
+    HIP_CHECK(hipMemcpyAsync(zzh.data(), w.zz, sizeof(double) * zzh.size(), hipMemcpyDeviceToHost, st));
     HIP_CHECK(hipMemcpyAsync(scal, s->scal, sizeof(double) * 4, hipMemcpyDeviceToHost, st));
     if (wv_out) HIP_CHECK(hipMemcpyAsync(wv_out, s->vvec, sizeof(double) * m * Dy, hipMemcpyDeviceToHost, st));
-    if (dmu_out) HIP_CHECK(hipMemcpyAsync(dmu_out, dMuO, sizeof(double) * n * D, hipMemcpyDeviceToHost, st));
-    if (dS_out) HIP_CHECK(hipMemcpyAsync(dS_out, dSO, sizeof(double) * n * D, hipMemcpyDeviceToHost, st));
-    HIP_CHECK(hipStreamSynchronize(st));
-    HIP_CHECK(hipGetLastError());
-    if (stage_ms) {
-        float ms;
-        for (int i = 0; i < 3; ++i) {
-            HIP_CHECK(hipEventElapsedTime(&ms, s->ev[i], s->ev[i + 1]));
-            stage_ms[i] = ms;
-        }
-        HIP_CHECK(hipEventElapsedTime(&ms, s->ev[0], s->ev[3]));
-        stage_ms[3] = ms;
+    if (dmu_out) HIP_CHECK(hipMemcpyAsync(dmu_out, w.dMuO, sizeof(double) * n * D, hipMemcpyDeviceToHost, st));
+    if (dS_out) HIP_CHECK(hipMemcpyAsync(dS_out, w.dSO, sizeof(double) * n * D, hipMemcpyDeviceToHost, st));
+    if (int rc = sparse_finish(s, 3, stage_ms)) return rc;
+    // psi0_n = variance_rbf + sum variance_white, every row: psi0.sum() = N psi0
+    vardtc_scalars(s, scal, expression_kdiag(s->parts, s->terms), beta, nullptr, out_scalars);
+    // on top of the Kmm record of the RBF part: the psi1 / psi2 sums in the layout of the reduction records (part_dtheta:
+    // dvariance = rec[0] / variance, dl = -rec / l); the z_m - z_o terms of psi2 add a_q sum LS dz^2 / 2 to dimension q
+    double* ab = kg.gmm.data() + (size_t)irbf * rec_doubles(s);
+    ab[0] += w.sums[0];
+    for (int q = 0; q < D; ++q) {
+        double zq = 0.0;
+        for (long j = 0; j < m; ++j) zq += zzh[(size_t)j * 2 * Qp + Qp + q];
+        const double lq = w.sums[(size_t)(1 + q)] + 0.5 * w.ha[(size_t)q] * zq;
+        ab[(size_t)(q / 32) * GP_STRIDE + 2 + (q % 32)] -= lq;
+        ab[1] -= lq;
     }
-    const int info_m = s->h_info[0], info_b = s->h_info[1];
-    if (info_m > 0) return info_m > m ? (int)m : info_m;                 // Kmm not positive definite: caller adds jitter
-    if (info_b > 0) return info_b > m ? (int)m : info_b;
-    const double trA = scal[0], sumAP = scal[1], logLB = scal[2], data_fit = scal[3];
-    const double ng = (double)n, nd = ng * Dy;
-    const double psi0 = expression_kdiag(s->parts, s->terms);           // psi0_n = variance_rbf + sum variance_white, every row
-    // _compute_log_marginal_likelihood and _compute_dL_dR (var_dtc.py:258-276) with psi0.sum() = N psi0
-    const double lik_1 = -0.5 * nd * (log(2.0 * M_PI) - log(beta)) - 0.5 * beta * s->trYYT;
-    const double lik_2 = -0.5 * Dy * (beta * ng * psi0 - trA);
-    const double lik_3 = -(double)Dy * logLB;
-    for (int i = 0; i < MI355GP_NUM_OUT; ++i) out_scalars[i] = 0.0;
-    out_scalars[0] = lik_1 + lik_2 + lik_3 + 0.5 * data_fit;
-    out_scalars[2] = trA;
-    out_scalars[3] = data_fit;
-    out_scalars[4] = logLB;
-    out_scalars[5] = beta;
-    {
-        double dL_dR = -0.5 * nd * beta + 0.5 * s->trYYT * beta * beta;
-        dL_dR += 0.5 * Dy * (ng * psi0 * beta * beta - trA * beta);
-        dL_dR += beta * (0.5 * sumAP - data_fit);
-        out_scalars[1] = dL_dR;
-    }
-    if (dtheta_out) {
-        double* o = dtheta_out;
-        std::vector<double> ab(gsz);
-        for (size_t i = 0; i < np_; ++i) {
-            const double* b = gmm.data() + i * gsz;
-            for (size_t k = 0; k < gsz; ++k) ab[k] = b[k];
-            if ((int)i == irbf) {
-                // the psi1 / psi2 sums in the layout of the reduction records (part_dtheta: dvariance = rec[0] / variance,
-                // dl = -rec / l); the z_m - z_o terms of psi2 add a_q sum LS dz^2 / 2 to dimension q
-                ab[0] += sums[0];
-                for (int q = 0; q < D; ++q) {
-                    double zq = 0.0;
-                    for (long j = 0; j < m; ++j) zq += zzh[(size_t)j * 2 * Qp + Qp + q];
-                    const double lq = sums[(size_t)(1 + q)] + 0.5 * ha[(size_t)q] * zq;
-                    ab[(size_t)(q / 32) * GP_STRIDE + 2 + (q % 32)] -= lq;
-                    ab[1] -= lq;
-                }
-            }
-            const int k = part_dtheta(s->parts[i], ab.data(), nullptr, o);
-            o[0] += -0.5 * Dy * beta * ng;                               // dL_dpsi0 = -Dy beta / 2 per row, dpsi0 / dvariance = 1
-            o += k;
-        }
-    }
-    if (dZ_out) {
-        // gradients_Z_expectations (psi1 and psi2 parts) + gradients_X(dL_dKmm, Z) (sparse_gp.py:100-107)
+    // dL_dpsi0 = -Dy beta / 2 per row, dpsi0 / dvariance = 1
+    sparse_assemble_gradients(s, kg, -0.5 * Dy * beta * (double)n, dtheta_out, dZ_out);
+    if (dZ_out)         // + gradients_Z_expectations (the psi1 and psi2 parts; sparse_gp.py:100-107)
         for (long j = 0; j < m; ++j)
-            for (int q = 0; q < D; ++q) {
-                const double il = rbf.inv_ls[(size_t)q];
-                double g = zs1[(size_t)j * Qp + q] + 2.0 * zs2[(size_t)j * Qp + q] - ha[(size_t)q] * zzh[(size_t)j * 2 * Qp + q];
-                if (il != 0.0) {
-                    const double z = Zs[(size_t)q * mp + j];
-                    g += 2.0 * (z * HZ[j * (D + 1) + D] - HZ[j * (D + 1) + q]) * il;
-                }
-                dZ_out[j * D + q] = g;
-            }
-    }
+            for (int q = 0; q < D; ++q)
+                dZ_out[j * D + q] += zs1[(size_t)j * Qp + q] + 2.0 * zs2[(size_t)j * Qp + q] - w.ha[(size_t)q] * zzh[(size_t)j * 2 * Qp + q];
     s->have_result = true;
     s->uncertain_result = true;
     return 0;
 }
 
+// ---- results of the last VarDTC call ------------------------------------------------------------------------------------
 // woodbury_inv = Lm^-T (I - B^-1) Lm^-1 (var_dtc.py:206-210) into s->Winv, once per inference call
 static int ensure_winv(mi355gp_sparse* s) {
     if (s->winv_ok) return 0;
     hipStream_t st = s->st;
     const long mp = s->mp;
-    hipLaunchKernelGGL(k_sym_from_lower, grid2d(mp, mp), dim3(256), 0, st, s->Bi, mp, 1, s->E);
-    hipLaunchKernelGGL(k_mm_axpby, grid2d(mp, mp), dim3(256), 0, st, s->E, -1.0, (const double*)nullptr, 0.0, 1.0, mp, s->E);
+    launch_mm_sym(st, s->Bi, mp, s->E);
+    launch_mm_axpby(st, s->E, -1.0, nullptr, 0.0, 1.0, mp, s->E);
     launch_gemm(st, 1, 1, mp, mp, mp, s->Xm, mp, s->E, mp, s->T1, mp, 1.0, 0.0);
     launch_gemm(st, 0, 1, mp, mp, mp, s->T1, mp, s->Xm, mp, s->Winv, mp, 1.0, 0.0);
     s->winv_ok = true;
@@ -1299,9 +1427,7 @@ int mi355gp_sparse_fetch_dLdKnm(mi355gp_sparse* s, int64_t row0, int64_t nrows, 
     EngineShared gate(s->device);
     hipStream_t st = s->st;
     const long m = s->m, mp = s->mp, rc = nrows, rcp = round_up(rc, NB);
-    scale_for_parts(s, s->dX + row0 * s->D, rc, s->chunk, false);
-    HIP_CHECK(hipMemsetAsync(s->Kfu, 0, sizeof(double) * rcp * mp, st));
-    build_cross_chunk(s, rc, s->Kfu, s->T);
+    if (int rc2 = sparse_cross_rows(s, row0, rc, 0, rcp, nullptr)) return rc2;
     launch_gemm(st, 0, 1, rcp, mp, mp, s->Kfu, mp, s->Q2, mp, s->T, mp, 1.0, 0.0);
     hipLaunchKernelGGL(k_form_dLdKnm, dim3((unsigned)rcp, (unsigned)((mp + 255) / 256)), dim3(256), 0, st, s->T, mp, rc, rcp, m,
                        s->dY + row0 * s->Dy, s->vvec, s->Dy, s->dBeta + row0);
@@ -1324,44 +1450,18 @@ int mi355gp_sparse_predict(mi355gp_sparse* s, int nparts, const mi355gp_part* pa
     EngineShared gate(s->device);
     if (int rc = prepare_sparse_parts(s, nparts, parts)) return rc;
     hipStream_t st = s->st;
-    const long m = s->m, mp = s->mp, Dy = s->Dy, mnp = round_up(Mn, NB);
-    scale_for_parts(s, s->dZ, m, mp, true);
+    scale_for_parts(s, s->dZ, s->m, s->mp, true);
     if (int rc = ensure_winv(s)) return rc;
-    PointSet xs;
-    DevBuf Kx, Tmp, dMu, dVar, scr;
-    if (int rc = xs.load(st, Xnew, Mn, s->D)) return rc;
-    HIP_CHECK(Kx.alloc(mp * mnp));
-    HIP_CHECK(Tmp.alloc(mp * mnp));
-    HIP_CHECK(dMu.alloc(Mn * Dy));
-    HIP_CHECK(dVar.alloc(full_cov ? mnp * mnp : Mn));
-    HIP_CHECK(hipMemsetAsync(Kx, 0, sizeof(double) * mp * mnp, st));
-    if (full_cov && var_out) HIP_CHECK(hipMemsetAsync(dVar, 0, sizeof(double) * mnp * mnp, st));
-    const double kdiag = expression_kdiag(s->parts, s->terms);
-    // K(Z, X*) and (full_cov) K(X*, X*) of the expression: every factor is evaluated with ITS scaling of the new inputs;
-    // products are multiplied up in Tmp / a second M* x M* scratch
-    emit_cross(st, s->parts, s->terms, inducing_points(s), xs, Kx, mnp, Tmp, false, 0,
-               [&](const std::vector<int>& t) { return skip_white(s, t); });
-    if (full_cov && var_out) {
-        if (has_product(s->terms) && scr.alloc(mnp * mnp) != hipSuccess) {
-            mi355gp_set_error("mi355gp_sparse_predict: out of memory for the product scratch");
-            return -3;
-        }
-        emit_cross(st, s->parts, s->terms, xs, xs, dVar, mnp, scr, false, /*diag_same=*/1);
-    }
-    launch_col_reduce(st, Kx, mnp, m, Mn, s->vvec, (int)Dy, 0.0, 0, dMu);                              // mu = Kx^T v
-    if (var_out) {
-        launch_gemm(st, 0, 1, mp, mnp, mp, s->Winv, mp, Kx, mnp, Tmp, mnp, 1.0, 0.0);                 // Winv Kx
-        if (!full_cov)
-            hipLaunchKernelGGL(k_col_dot, dim3((unsigned)((Mn + 63) / 64)), dim3(256), 0, st, Kx, Tmp, mnp, m, (long)Mn, kdiag, dVar);
-        else
-            launch_gemm(st, 1, 1, mnp, mnp, mp, Kx, mnp, Tmp, mnp, dVar, mnp, -1.0, 1.0);             // K** - Kx^T Winv Kx
-    }
-    HIP_CHECK(hipMemcpyAsync(mu_out, dMu, sizeof(double) * Mn * Dy, hipMemcpyDeviceToHost, st));
+    NewPoints q;
+    if (int rc = sparse_newpoints(s, Xnew, Mn, full_cov && var_out, s->vvec, s->Dy, "mi355gp_sparse_predict", &q)) return rc;
+    if (var_out)
+        if (int rc = sparse_newpoints_var(s, &q, s->Winv, full_cov != 0, /*keep_kss=*/false)) return rc;
+    HIP_CHECK(hipMemcpyAsync(mu_out, q.Mu, sizeof(double) * Mn * s->Dy, hipMemcpyDeviceToHost, st));
     if (var_out) {
         if (!full_cov)
-            HIP_CHECK(hipMemcpyAsync(var_out, dVar, sizeof(double) * Mn, hipMemcpyDeviceToHost, st));
+            HIP_CHECK(hipMemcpyAsync(var_out, q.var, sizeof(double) * Mn, hipMemcpyDeviceToHost, st));
         else
-            HIP_CHECK(hipMemcpy2DAsync(var_out, sizeof(double) * Mn, dVar, sizeof(double) * mnp, sizeof(double) * Mn, Mn,
+            HIP_CHECK(hipMemcpy2DAsync(var_out, sizeof(double) * Mn, q.var, sizeof(double) * q.mnp, sizeof(double) * Mn, Mn,
                                        hipMemcpyDeviceToHost, st));
     }
     HIP_CHECK(hipStreamSynchronize(st));

@@ -62,6 +62,20 @@ struct mi355gp_sparse {
 };
 
 // ---- sparse.hip ----------------------------------------------------------------------------------------------------
+// doubles of one part's theta record (one GP_STRIDE record per 32 dimensions) and of its H^T [X~ | 1] sums
+inline size_t rec_doubles(const mi355gp_sparse* s) { return (size_t)((s->D + 31) / 32) * GP_STRIDE; }
+inline size_t hsum_doubles(const mi355gp_sparse* s) { return (size_t)s->mp * (s->D + 1); }
+struct KernGrads {             // the parts' records and sums on the host (sparse_fetch_gradients)
+    bool with_nm = true;
+    std::vector<double> gnm, gmm, HX, HZ, Zs;
+};
+struct NewPoints {             // K(Z, X*) and what a prediction derives from it (sparse_newpoints)
+    PointSet xs;
+    DevBuf Kx, Tmp, Kss, scr, Mu, Var;
+    long Mn = 0, mnp = 0;
+    double kdiag = 0.0;
+    double* var = nullptr;     // where sparse_newpoints_var left its result
+};
 bool sharded(const mi355gp_sparse* s);
 int alloc_m(mi355gp_sparse* s, long M);
 int prepare_sparse_parts(mi355gp_sparse* s, int nparts, const mi355gp_part* parts);
@@ -71,10 +85,26 @@ void scale_for_parts(mi355gp_sparse* s, const double* src, long rows, long ldt, 
 Resident<SPart> inducing_points(const mi355gp_sparse* s);
 void build_cross_chunk(mi355gp_sparse* s, long rc, double* out, double* scratch);
 void build_kmm(mi355gp_sparse* s, double* out, double* scratch, double jitter, int lower_only, hipStream_t st = nullptr);
+dim3 grid2d(long cols, long rows);                                                   // 256 columns a block, one row each
+void launch_mm_sym(hipStream_t st, const double* low, long mp, double* out);         // out = the lower triangle mirrored
+void launch_mm_axpby(hipStream_t st, const double* A, double ca, const double* B, double cb, double ci, long mp, double* out);
 extern "C" {       // (defined among the entry points of sparse.hip)
 int potrf_checked(hipStream_t st, double* A, double* X, double* T, double* W, long mp, FactorWs* ws, int* info_host,
                   const std::function<void()>& rebuild);
 void sparse_kmm_gradients(mi355gp_sparse* s);
+// the phases an inference family is built from, in the order of a call (each is described where it is defined)
+int sparse_open(mi355gp_sparse* s, int nparts, const mi355gp_part* parts, int64_t M);
+int sparse_start(mi355gp_sparse* s, const double* Z, const double* beta, long nbeta);
+int sparse_cross_rows(mi355gp_sparse* s, long r0, long rc, long z0, long z1, const double* V);
+int sparse_rows_gradients_reset(mi355gp_sparse* s);
+void sparse_rows_gradients(mi355gp_sparse* s, long rc, const double* W, double* scratch, const RankTerm& rk,
+                           const std::function<void()>& form_times);
+int sparse_fetch_gradients(mi355gp_sparse* s, bool with_nm, KernGrads* h);
+int sparse_finish(mi355gp_sparse* s, int nstage, double* stage_ms);
+void sparse_assemble_gradients(const mi355gp_sparse* s, const KernGrads& h, double kdiag_coef, double* dtheta_out, double* dZ_out);
+int sparse_newpoints(mi355gp_sparse* s, const double* Xnew, int64_t Mn, bool want_cov, const double* wv, int ncol,
+                     const char* where, NewPoints* q);
+int sparse_newpoints_var(mi355gp_sparse* s, NewPoints* q, const double* Winv, bool full_cov, bool keep_kss);
 }
 // ---- svgp.hip ------------------------------------------------------------------------------------------------------
 void svgp_release(mi355gp_sparse* s);      // frees the SVGP state (M-dependent: called by free_m)

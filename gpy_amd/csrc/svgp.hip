@@ -34,25 +34,7 @@ void svgp_release(mi355gp_sparse* s) {
     s->svgp_result = false;
 }
 
-// ---- kernels ---------------------------------------------------------------------------------------------------------
-static dim3 sv_grid2d(long cols, long rows) { return dim3((unsigned)((cols + 255) / 256), (unsigned)rows); }
-
-// out = mirror of the lower triangle (the inverse that X^T X leaves in its lower tiles)
-__global__ void k_svgp_sym(const double* __restrict__ low, long mp, double* __restrict__ out) {
-    const long j = (long)blockIdx.x * blockDim.x + threadIdx.x, i = blockIdx.y;
-    if (j >= mp) return;
-    out[i * mp + j] = (i >= j) ? low[i * mp + j] : low[j * mp + i];
-}
-// out = ca * A + cb * B + ci * I   (B may be NULL)
-__global__ void k_svgp_axpby(const double* __restrict__ A, double ca, const double* __restrict__ B, double cb, double ci, long mp,
-                             double* __restrict__ out) {
-    const long j = (long)blockIdx.x * blockDim.x + threadIdx.x, i = blockIdx.y;
-    if (j >= mp) return;
-    double v = (i == j) ? ci : 0.0;
-    v = fma(ca, A[i * mp + j], v);
-    if (B) v = fma(cb, B[i * mp + j], v);
-    out[i * mp + j] = v;
-}
+// ---- kernels (the elementwise M x M ones are sparse.hip's: launch_mm_sym, launch_mm_axpby) ---------------------------
 // out = sum_d A_d in the order d = 0 .. L-1
 __global__ void k_svgp_sum_lat(const double* __restrict__ A, int L, long mp, double* __restrict__ out) {
     const long j = (long)blockIdx.x * blockDim.x + threadIdx.x, i = blockIdx.y;
@@ -196,23 +178,6 @@ __global__ void k_svgp_dLdKmm(const double* __restrict__ sumA, const double* __r
     }
     out[i * mp + j] = v;
 }
-__global__ void k_svgp_axpy(double* __restrict__ dst, const double* __restrict__ src, long cnt) {
-    const long l = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (l < cnt) dst[l] += src[l];
-}
-// out[j] = c0 - sum_i A[i][j] * B[i][j]   (64 columns per block, 4 row groups, fixed-order combine)
-__global__ __launch_bounds__(256) void k_svgp_col_dot(const double* __restrict__ A, const double* __restrict__ B, long ld, long rows,
-                                                      long cols, double c0, double* __restrict__ out) {
-    __shared__ double red[4][64];
-    const int tx = threadIdx.x & 63, g = threadIdx.x >> 6;
-    const long j = (long)blockIdx.x * 64 + tx;
-    double acc = 0.0;
-    if (j < cols)
-        for (long i = g; i < rows; i += 4) acc = fma(A[i * ld + j], B[i * ld + j], acc);
-    red[g][tx] = acc;
-    __syncthreads();
-    if (g == 0 && j < cols) out[j] = c0 - ((red[0][tx] + red[1][tx]) + (red[2][tx] + red[3][tx]));
-}
 
 // ---- state -----------------------------------------------------------------------------------------------------------
 static int svgp_state(mi355gp_sparse* s, int L) {
@@ -253,9 +218,7 @@ static int svgp_chunk_A(mi355gp_sparse* s, long r0, long rc) {
     SvgpState* sv = s->svgp;
     hipStream_t st = s->st;
     const long mp = s->mp, rcp = round_up(rc, NB);
-    scale_for_parts(s, s->dX + r0 * s->D, rc, s->chunk, false);
-    HIP_CHECK(hipMemsetAsync(s->Kfu, 0, sizeof(double) * rcp * mp, st));     // the cross-covariance kernel writes rows < rc, columns < m
-    build_cross_chunk(s, rc, s->Kfu, s->T);
+    if (int rc2 = sparse_cross_rows(s, r0, rc, 0, rcp, nullptr)) return rc2;
     launch_gemm(st, 0, 1, rcp, mp, mp, s->Kfu, mp, sv->Kmmi, mp, s->T, mp, 1.0, 0.0);
     return 0;
 }
@@ -282,19 +245,13 @@ int mi355gp_svgp_forward(mi355gp_sparse* s, int nparts, const mi355gp_part* part
     if (int rc = svgp_common_checks(s, "mi355gp_svgp_forward")) return rc;
     if (L < 1 || L > SVGP_LMAX) PART_FAIL("mi355gp_svgp_forward: %d latent functions; between 1 and %d are supported", L, SVGP_LMAX);
     ARG_CHECK(parts && Z && M > 0 && q_mean && q_chol && mu_out && v_out && scalars_out, "mi355gp_svgp_forward: bad arguments");
-    HIP_CHECK(hipSetDevice(s->device));
     EngineShared gate(s->device);
-    if (M != s->m)
-        if (int rc = alloc_m(s, M)) return rc;
-    s->have_result = s->winv_ok = s->svgp_result = false;
-    if (s->svgp) s->svgp->fwd_ok = s->svgp->winv_ok = false;
-    if (int rc = prepare_sparse_parts(s, nparts, parts)) return rc;
+    if (int rc = sparse_open(s, nparts, parts, M)) return rc;
     if (int rc = svgp_state(s, L)) return rc;
     SvgpState* sv = s->svgp;
     sv->fwd_ok = sv->winv_ok = false;
     hipStream_t st = s->st;
     const long n = s->n, m = s->m, mp = s->mp, chunk = s->chunk;
-    const int D = s->D;
     const size_t mm = (size_t)mp * mp;
     s->mfma_prof.on = false;
     // q(u): m zero padded, L_d with the identity in the padding block; log det S_d = 2 sum log |L_d,ii| (svgp.py:23)
@@ -310,18 +267,15 @@ int mi355gp_svgp_forward(mi355gp_sparse* s, int nparts, const mi355gp_part* part
         }
         for (long i = m; i < mp; ++i) dst[i * mp + i] = 1.0;
     }
-    HIP_CHECK(hipMemcpyAsync(s->dZ, Z, sizeof(double) * m * D, hipMemcpyHostToDevice, st));
     HIP_CHECK(hipMemcpyAsync(sv->qm, hqm.data(), sizeof(double) * mp * L, hipMemcpyHostToDevice, st));
     HIP_CHECK(hipMemcpyAsync(sv->Ld, hld.data(), sizeof(double) * mm * L, hipMemcpyHostToDevice, st));
-    HIP_CHECK(hipEventRecord(s->ev[0], st));
-    scale_for_parts(s, s->dZ, m, mp, true);
+    if (int rc = sparse_start(s, Z, nullptr, 0)) return rc;
     // ---- M x M phase -------------------------------------------------------------------------------------------------------
     // Kmm = K(Z) (+ the ladder's jitter only, svgp.py:37,40), Lm = chol, Xm = Lm^-1, Kmm^-1 = Xm^T Xm (svgp.py:40-42)
-    s->h_info[0] = s->h_info[1] = 0;
     auto rebuild_kmm = [&]() { build_kmm(s, s->Lm, s->T1, extra_jitter, /*lower_only=*/1, st); };
     rebuild_kmm();
     if (int rc = potrf_checked(st, s->Lm, s->Xm, s->Tm, s->Bi, mp, &s->ws, &s->h_info[0], rebuild_kmm)) return rc;
-    hipLaunchKernelGGL(k_svgp_sym, sv_grid2d(mp, mp), dim3(256), 0, st, s->Bi, mp, sv->Kmmi);
+    launch_mm_sym(st, s->Bi, mp, sv->Kmmi);
     // S_d = L_d L_d^T (svgp.py:19-20) and S_d^-1 (svgp.py:22) through its own factorisation
     for (int d = 0; d < L; ++d) {
         double* Ld = sv->Ld + (size_t)d * mm;
@@ -331,7 +285,7 @@ int mi355gp_svgp_forward(mi355gp_sparse* s, int nparts, const mi355gp_part* part
         rebuild_s();
         sv->h_info[d] = 0;
         if (int rc = potrf_checked(st, s->LB, s->XB, s->Tm, s->P, mp, &s->ws, &sv->h_info[d], rebuild_s)) return rc;
-        hipLaunchKernelGGL(k_svgp_sym, sv_grid2d(mp, mp), dim3(256), 0, st, s->P, mp, sv->Si + (size_t)d * mm);
+        launch_mm_sym(st, s->P, mp, sv->Si + (size_t)d * mm);
     }
     // Kmm^-1 m (svgp.py:54) and the sums of the KL term (svgp.py:55)
     hipLaunchKernelGGL(k_svgp_matvec, dim3((unsigned)((mp + 3) / 4)), dim3(256), 0, st, sv->Kmmi, mp, sv->qm, L, sv->Kmmim);
@@ -356,19 +310,7 @@ int mi355gp_svgp_forward(mi355gp_sparse* s, int nparts, const mi355gp_part* part
     HIP_CHECK(hipMemcpyAsync(mu_out, sv->dMu, sizeof(double) * n * L, hipMemcpyDeviceToHost, st));
     HIP_CHECK(hipMemcpyAsync(v_out, sv->dVv, sizeof(double) * n * L, hipMemcpyDeviceToHost, st));
     HIP_CHECK(hipMemcpyAsync(red.data(), sv->red, sizeof(double) * (2 * L + 1), hipMemcpyDeviceToHost, st));
-    HIP_CHECK(hipStreamSynchronize(st));
-    HIP_CHECK(hipGetLastError());
-    if (stage_ms) {
-        float ms;
-        for (int i = 0; i < 2; ++i) {
-            HIP_CHECK(hipEventElapsedTime(&ms, s->ev[i], s->ev[i + 1]));
-            stage_ms[i] = ms;
-        }
-        HIP_CHECK(hipEventElapsedTime(&ms, s->ev[0], s->ev[2]));
-        stage_ms[2] = ms;
-    }
-    const int info_m = s->h_info[0];
-    if (info_m > 0) return info_m > m ? (int)m : info_m;                 // Kmm not positive definite: caller adds jitter
+    if (int rc = sparse_finish(s, 2, stage_ms)) return rc;      // (info > 0: Kmm not positive definite, the caller adds jitter)
     for (int d = 0; d < L; ++d)
         if (sv->h_info[d] > 0 || !std::isfinite(logdetS[(size_t)d])) {
             mi355gp_set_error("mi355gp_svgp_forward: Cholesky representation unstable: S_%d = L_%d L_%d^T is not positive definite "
@@ -404,22 +346,17 @@ int mi355gp_svgp_backward(mi355gp_sparse* s, const double* dF_dmu, const double*
     SvgpState* sv = s->svgp;
     hipStream_t st = s->st;
     const long n = s->n, m = s->m, mp = s->mp, chunk = s->chunk;
-    const int D = s->D, L = sv->L, groups = (D + 31) / 32;
+    const int L = sv->L;
     const size_t mm = (size_t)mp * mp;
-    const size_t gsz = (size_t)groups * GP_STRIDE, hsz = (size_t)mp * (D + 1);
     HIP_CHECK(hipMemcpyAsync(sv->dFmu, dF_dmu, sizeof(double) * n * L, hipMemcpyHostToDevice, st));
     HIP_CHECK(hipMemcpyAsync(sv->dFv, dF_dv, sizeof(double) * n * L, hipMemcpyHostToDevice, st));
     HIP_CHECK(hipEventRecord(s->ev[0], st));
     // tmp_d = 2 (S_d Kmmi - I) (svgp.py:92-93; zero in the padding block)
     for (int d = 0; d < L; ++d) {
         launch_gemm(st, 0, 1, mp, mp, mp, sv->Sd + (size_t)d * mm, mp, sv->Kmmi, mp, s->E, mp, 1.0, 0.0);
-        hipLaunchKernelGGL(k_svgp_axpby, sv_grid2d(mp, mp), dim3(256), 0, st, s->E, 2.0, (const double*)nullptr, 0.0, -2.0, mp,
-                           sv->Tq + (size_t)d * mm);
+        launch_mm_axpby(st, s->E, 2.0, nullptr, 0.0, -2.0, mp, sv->Tq + (size_t)d * mm);
     }
-    for (SPart& p : s->parts) {
-        HIP_CHECK(hipMemsetAsync(p.gradNM, 0, sizeof(double) * gsz, st));
-        HIP_CHECK(hipMemsetAsync(p.HX, 0, sizeof(double) * hsz, st));
-    }
+    if (int rc = sparse_rows_gradients_reset(s)) return rc;
     HIP_CHECK(hipMemsetAsync(sv->Admu, 0, sizeof(double) * mp * L, st));
     // ---- row phase -----------------------------------------------------------------------------------------------------------
     const bool one_chunk = (n <= chunk);                      // A^T of a single chunk is still resident in s->T
@@ -441,91 +378,44 @@ int mi355gp_svgp_backward(mi355gp_sparse* s, const double* dF_dmu, const double*
             launch_gemm(st, 1, 1, mp, mp, rcp, At, mp, sv->U, mp, sv->AdvA + (size_t)d * mm, mp, 1.0, nch > 0 ? 1.0 : 0.0);
             launch_gemm(st, 0, 1, rcp, mp, mp, sv->U, mp, sv->Tq + (size_t)d * mm, mp, G, mp, 1.0, d > 0 ? 1.0 : 0.0);
         }
-        // dL_dKmn = (Kmmi m) dF_dmu^T + ... (svgp.py:95): the rank-L term is formed inside the gradient pass; the theta sums and
-        // H^T [X~ | 1] of every part as in the second pass of VarDTC
+        // dL_dKmn = (Kmmi m) dF_dmu^T + G (svgp.py:95): the rank-L term is formed inside the gradient pass
         const RankTerm rk{sv->dFmu + r0 * L, sv->Kmmim, L, 1.0, 1.0, nullptr};
-        for (size_t pi = 0; pi < s->parts.size(); ++pi) {
-            SPart& p = s->parts[pi];
-            if (p.kp.kind == MI355GP_WHITE) continue;        // White: K(X, Z) = 0, no contribution (static.py:89-93)
-            int nbk = 0, ns = 0;
-            const bool prod = emit_other_factors(s->terms, p.tix, pi, sv->U, [&](int f, double* dst, const double* mul, int, bool) {
-                const SPart& pf = s->parts[(size_t)f];
-                launch_kbuild_cross(st, pf.kp, pf.XtC, chunk, rc, pf.XtZ, mp, m, dst, mp, 0, 0, mul);
-            });
-            if (prod) {
-                hipLaunchKernelGGL(k_svgp_weights_times, dim3((unsigned)rcp, (unsigned)((mp + 255) / 256)), dim3(256), 0, st, G, sv->U,
-                                   mp, rc, rcp, m, sv->dFmu + r0 * L, sv->Kmmim, L);
-                nbk = grad_generic_num_blocks(rc, m);
-                launch_grad_generic(st, p.kp, p.XtC, chunk, rc, p.XtZ, mp, m, 0, sv->U, mp, s->gradPart,
-                                    p.stationary() ? sv->U : nullptr, mp);          // H over the weights, in place
-                if (p.stationary()) ns = launch_colreduce_multi(st, sv->U, mp, rc, mp, p.XtC, 1, chunk, D, 1, s->colPart);
-            } else {
-                if (p.stationary() && s->fuse_cols)
-                    ns = launch_grad_cols(st, p.kp, p.XtC, chunk, rc, p.XtZ, mp, m, mp, G, mp, rk, s->gradPart, s->colPart, &nbk);
-                if (ns == 0) {
-                    nbk = grad_generic_num_blocks(rc, m);
-                    double* Hbuf = p.stationary() ? sv->U : nullptr;
-                    launch_grad_generic(st, p.kp, p.XtC, chunk, rc, p.XtZ, mp, m, 0, G, mp, s->gradPart, Hbuf, mp, rk);
-                    if (p.stationary()) ns = launch_colreduce_multi(st, sv->U, mp, rc, mp, p.XtC, 1, chunk, D, 1, s->colPart);
-                }
-            }
-            for (int g = 0; g < (p.kp.ard ? groups : 1); ++g)
-                launch_reduce_partials(st, s->gradPart + (long)g * nbk * GP_STRIDE, nbk, GP_STRIDE, s->gradChunk + (long)g * GP_STRIDE);
-            hipLaunchKernelGGL(k_svgp_axpy, dim3((unsigned)((gsz + 255) / 256)), dim3(256), 0, st, (double*)p.gradNM,
-                               (const double*)s->gradChunk, (long)gsz);
-            if (p.stationary()) launch_sum_splits(st, s->colPart, mp * (D + 1), ns, 1, p.HX);
-        }
+        sparse_rows_gradients(s, rc, G, sv->U, rk, [&]() {
+            hipLaunchKernelGGL(k_svgp_weights_times, dim3((unsigned)rcp, (unsigned)((mp + 255) / 256)), dim3(256), 0, st, G, sv->U, mp,
+                               rc, rcp, m, sv->dFmu + r0 * L, sv->Kmmim, L);
+        });
     }
     HIP_CHECK(hipEventRecord(s->ev[1], st));
     // ---- M x M phase ---------------------------------------------------------------------------------------------------------
     // sumA = sum_d AdvA_d (in Amat), tmp = (sum_d AdvA_d S_d) Kmmi (svgp.py:89, in T1), KSK = Kmmi (sum_d S_d) Kmmi (svgp.py:60, in Q2)
-    hipLaunchKernelGGL(k_svgp_sum_lat, sv_grid2d(mp, mp), dim3(256), 0, st, sv->AdvA, L, mp, s->Amat);
+    hipLaunchKernelGGL(k_svgp_sum_lat, grid2d(mp, mp), dim3(256), 0, st, sv->AdvA, L, mp, s->Amat);
     for (int d = 0; d < L; ++d)
         launch_gemm(st, 0, 1, mp, mp, mp, sv->AdvA + (size_t)d * mm, mp, sv->Sd + (size_t)d * mm, mp, s->E, mp, 1.0, d > 0 ? 1.0 : 0.0);
     launch_gemm(st, 0, 1, mp, mp, mp, s->E, mp, sv->Kmmi, mp, s->T1, mp, 1.0, 0.0);
-    hipLaunchKernelGGL(k_svgp_sum_lat, sv_grid2d(mp, mp), dim3(256), 0, st, sv->Sd, L, mp, s->E);
+    hipLaunchKernelGGL(k_svgp_sum_lat, grid2d(mp, mp), dim3(256), 0, st, sv->Sd, L, mp, s->E);
     launch_gemm(st, 0, 1, mp, mp, mp, sv->Kmmi, mp, s->E, mp, s->P, mp, 1.0, 0.0);
     launch_gemm(st, 0, 1, mp, mp, mp, s->P, mp, sv->Kmmi, mp, s->Q2, mp, 1.0, 0.0);
-    hipLaunchKernelGGL(k_svgp_dLdKmm, sv_grid2d(mp, mp), dim3(256), 0, st, s->Amat, s->T1, sv->Kmmi, s->Q2, sv->Admu, sv->Kmmim, L, mp, m,
+    hipLaunchKernelGGL(k_svgp_dLdKmm, grid2d(mp, mp), dim3(256), 0, st, s->Amat, s->T1, sv->Kmmi, s->Q2, sv->Admu, sv->Kmmim, L, mp, m,
                        s->dLdKmm);
     // dL_dchol_d = 2 dL_dS_d L_d, dL_dS_d = AdvA_d - (Kmmi - S_d^-1) / 2 (svgp.py:59,100,112,114), into Tq (tmp_d is spent)
     for (int d = 0; d < L; ++d) {
-        hipLaunchKernelGGL(k_svgp_axpby, sv_grid2d(mp, mp), dim3(256), 0, st, sv->Kmmi, -0.5, sv->Si + (size_t)d * mm, 0.5, 0.0, mp, s->E);
-        hipLaunchKernelGGL(k_svgp_axpby, sv_grid2d(mp, mp), dim3(256), 0, st, sv->AdvA + (size_t)d * mm, 1.0, s->E, 1.0, 0.0, mp, s->P);
+        launch_mm_axpby(st, sv->Kmmi, -0.5, sv->Si + (size_t)d * mm, 0.5, 0.0, mp, s->E);
+        launch_mm_axpby(st, sv->AdvA + (size_t)d * mm, 1.0, s->E, 1.0, 0.0, mp, s->P);
         launch_gemm(st, 0, 1, mp, mp, mp, s->P, mp, sv->Ld + (size_t)d * mm, mp, sv->Tq + (size_t)d * mm, mp, 2.0, 0.0);
     }
     sparse_kmm_gradients(s);
     HIP_CHECK(hipEventRecord(s->ev[2], st));
     // ---- small results to the host ------------------------------------------------------------------------------------------
-    const size_t np_ = s->parts.size();
-    std::vector<double> gnm(np_ * gsz), gmm(np_ * gsz), HX(np_ * hsz), HZ(np_ * hsz), Zs(np_ * (size_t)D * mp);
+    KernGrads kg;
     std::vector<double> admu((size_t)mp * L), kmmim((size_t)mp * L);
-    for (size_t i = 0; i < np_; ++i) {
-        SPart& p = s->parts[i];
-        HIP_CHECK(hipMemcpyAsync(gnm.data() + i * gsz, p.gradNM, sizeof(double) * gsz, hipMemcpyDeviceToHost, st));
-        HIP_CHECK(hipMemcpyAsync(gmm.data() + i * gsz, p.gradMM, sizeof(double) * gsz, hipMemcpyDeviceToHost, st));
-        if (!p.stationary()) continue;
-        HIP_CHECK(hipMemcpyAsync(HX.data() + i * hsz, p.HX, sizeof(double) * hsz, hipMemcpyDeviceToHost, st));
-        HIP_CHECK(hipMemcpyAsync(HZ.data() + i * hsz, p.HZ, sizeof(double) * hsz, hipMemcpyDeviceToHost, st));
-        HIP_CHECK(hipMemcpyAsync(Zs.data() + i * (size_t)D * mp, p.XtZ, sizeof(double) * D * mp, hipMemcpyDeviceToHost, st));
-    }
+    if (int rc = sparse_fetch_gradients(s, true, &kg)) return rc;
     HIP_CHECK(hipMemcpyAsync(admu.data(), sv->Admu, sizeof(double) * mp * L, hipMemcpyDeviceToHost, st));
     HIP_CHECK(hipMemcpyAsync(kmmim.data(), sv->Kmmim, sizeof(double) * mp * L, hipMemcpyDeviceToHost, st));
     if (dchol_out)
         for (int d = 0; d < L; ++d)
             HIP_CHECK(hipMemcpy2DAsync(dchol_out + (size_t)d * m * m, sizeof(double) * m, sv->Tq + (size_t)d * mm, sizeof(double) * mp,
                                        sizeof(double) * m, m, hipMemcpyDeviceToHost, st));
-    HIP_CHECK(hipStreamSynchronize(st));
-    HIP_CHECK(hipGetLastError());
-    if (stage_ms) {
-        float ms;
-        for (int i = 0; i < 2; ++i) {
-            HIP_CHECK(hipEventElapsedTime(&ms, s->ev[i], s->ev[i + 1]));
-            stage_ms[i] = ms;
-        }
-        HIP_CHECK(hipEventElapsedTime(&ms, s->ev[0], s->ev[2]));
-        stage_ms[2] = ms;
-    }
+    if (int rc = sparse_finish(s, 2, stage_ms)) return rc;
     if (dchol_out)                                              // the lower triangle is the gradient (choleskies.triang_to_flat)
         for (int d = 0; d < L; ++d)
             for (long i = 0; i < m; ++i)
@@ -535,40 +425,7 @@ int mi355gp_svgp_backward(mi355gp_sparse* s, const double* dF_dmu, const double*
     // dL_dKdiag = dF_dv.sum(1) (svgp.py:117): update_gradients_diag gives its sum to every part's variance
     double sum_dv = 0.0;
     for (long i = 0; i < n * L; ++i) sum_dv += dF_dv[i];
-    if (dtheta_out) {
-        double* o = dtheta_out;
-        std::vector<double> ab(gsz);                              // the Kmn and Kmm records of a part summed
-        for (size_t i = 0; i < np_; ++i) {
-            const double* a = gnm.data() + i * gsz;
-            const double* b = gmm.data() + i * gsz;
-            for (size_t k = 0; k < gsz; ++k) ab[k] = a[k] + b[k];
-            const int k = part_dtheta(s->parts[i], ab.data(), nullptr, o);
-            // (a factor of a product: dKdiag / dvariance = the product of the other factors' variances, prod.py:67-71)
-            o[0] = sum_dv * sparse_other_variances(s, i) + o[0];
-            o += k;
-        }
-    }
-    if (dZ_out) {
-        // gradients_X(dL_dKmn, Z, X) + gradients_X(dL_dKmm, Z) (core/svgp.py:65), summed over the parts (add.py:84-88):
-        //   sum_n H[n,m] (z~_mq - x~_nq) / l_q  +  2 sum_j Hmm[j,m] (z~_mq - z~_jq) / l_q
-        for (long j = 0; j < m * D; ++j) dZ_out[j] = 0.0;
-        for (size_t i = 0; i < np_; ++i) {
-            const SPart& p = s->parts[i];
-            if (!p.stationary()) continue;
-            const double* hx = HX.data() + i * hsz;
-            const double* hz = HZ.data() + i * hsz;
-            const double* zs = Zs.data() + i * (size_t)D * mp;
-            for (long j = 0; j < m; ++j)
-                for (int q = 0; q < D; ++q) {
-                    const double il = p.inv_ls[(size_t)q];
-                    if (il == 0.0) continue;
-                    const double z = zs[(size_t)q * mp + j];
-                    const double a = z * hx[j * (D + 1) + D] - hx[j * (D + 1) + q];
-                    const double b = z * hz[j * (D + 1) + D] - hz[j * (D + 1) + q];
-                    dZ_out[j * D + q] += (a + 2.0 * b) * il;
-                }
-        }
-    }
+    sparse_assemble_gradients(s, kg, sum_dv, dtheta_out, dZ_out);             // (core/svgp.py:58-65)
     return 0;
 }
 
@@ -583,7 +440,7 @@ static int svgp_ensure_winv(mi355gp_sparse* s) {
     for (int d = 0; d < sv->L; ++d) {
         launch_gemm(st, 0, 1, mp, mp, mp, sv->Kmmi, mp, sv->Sd + (size_t)d * mm, mp, s->E, mp, 1.0, 0.0);
         launch_gemm(st, 0, 1, mp, mp, mp, s->E, mp, sv->Kmmi, mp, s->P, mp, 1.0, 0.0);
-        hipLaunchKernelGGL(k_svgp_axpby, sv_grid2d(mp, mp), dim3(256), 0, st, sv->Kmmi, 1.0, s->P, -1.0, 0.0, mp, sv->Wd + (size_t)d * mm);
+        launch_mm_axpby(st, sv->Kmmi, 1.0, s->P, -1.0, 0.0, mp, sv->Wd + (size_t)d * mm);
     }
     sv->winv_ok = true;
     return 0;
@@ -621,44 +478,20 @@ int mi355gp_svgp_predict(mi355gp_sparse* s, int nparts, const mi355gp_part* part
     }
     if (Mn == 0) return 0;
     if (int rc = prepare_sparse_parts(s, nparts, parts)) return rc;
-    const long mnp = round_up(Mn, NB);
     scale_for_parts(s, s->dZ, m, mp, true);
-    PointSet xs;
-    DevBuf Kx, Tmp, dMu, dVar, Kss, scr;
-    if (int rc = xs.load(st, Xnew, Mn, s->D)) return rc;
-    HIP_CHECK(Kx.alloc(mp * mnp));
-    HIP_CHECK(Tmp.alloc(mp * mnp));
-    HIP_CHECK(dMu.alloc(Mn * L));
-    HIP_CHECK(dVar.alloc(full_cov ? mnp * mnp : Mn));
-    HIP_CHECK(hipMemsetAsync(Kx, 0, sizeof(double) * mp * mnp, st));
-    const double kdiag = expression_kdiag(s->parts, s->terms);
-    emit_cross(st, s->parts, s->terms, inducing_points(s), xs, Kx, mnp, Tmp, false, 0,
-               [&](const std::vector<int>& t) { return skip_white(s, t); });
-    if (full_cov && var_out) {
-        HIP_CHECK(Kss.alloc(mnp * mnp));
-        HIP_CHECK(hipMemsetAsync(Kss, 0, sizeof(double) * mnp * mnp, st));
-        if (has_product(s->terms) && scr.alloc(mnp * mnp) != hipSuccess) {
-            mi355gp_set_error("mi355gp_svgp_predict: out of memory for the product scratch");
-            return -3;
-        }
-        emit_cross(st, s->parts, s->terms, xs, xs, Kss, mnp, scr, false, /*diag_same=*/1);
-    }
-    launch_col_reduce(st, Kx, mnp, m, Mn, sv->Kmmim, (int)L, 0.0, 0, dMu);                              // mu = Kx^T Kmmi m
-    HIP_CHECK(hipMemcpyAsync(mu_out, dMu, sizeof(double) * Mn * L, hipMemcpyDeviceToHost, st));
+    NewPoints q;
+    if (int rc = sparse_newpoints(s, Xnew, Mn, full_cov && var_out, sv->Kmmim, (int)L, "mi355gp_svgp_predict", &q)) return rc;   // mu = Kx^T Kmmi m
+    HIP_CHECK(hipMemcpyAsync(mu_out, q.Mu, sizeof(double) * Mn * L, hipMemcpyDeviceToHost, st));
     if (var_out) {
         std::vector<double> hv(full_cov ? (size_t)Mn * Mn : (size_t)Mn);
-        for (long d = 0; d < L; ++d) {
-            launch_gemm(st, 0, 1, mp, mnp, mp, sv->Wd + (size_t)d * mm, mp, Kx, mnp, Tmp, mnp, 1.0, 0.0);       // Winv_d Kx
+        for (long d = 0; d < L; ++d) {                            // one latent after the other, the host interleaving each
+            if (int rc = sparse_newpoints_var(s, &q, sv->Wd + (size_t)d * mm, full_cov != 0, /*keep_kss=*/true)) return rc;
             if (!full_cov) {
-                hipLaunchKernelGGL(k_svgp_col_dot, dim3((unsigned)((Mn + 63) / 64)), dim3(256), 0, st, (const double*)Kx,
-                                   (const double*)Tmp, mnp, m, (long)Mn, kdiag, (double*)dVar);
-                HIP_CHECK(hipMemcpyAsync(hv.data(), dVar, sizeof(double) * Mn, hipMemcpyDeviceToHost, st));
+                HIP_CHECK(hipMemcpyAsync(hv.data(), q.var, sizeof(double) * Mn, hipMemcpyDeviceToHost, st));
                 HIP_CHECK(hipStreamSynchronize(st));
                 for (int64_t i = 0; i < Mn; ++i) var_out[i * L + d] = hv[(size_t)i] < 1e-15 ? 1e-15 : hv[(size_t)i];   // posterior.py:248
             } else {
-                HIP_CHECK(hipMemcpyAsync(dVar, Kss, sizeof(double) * mnp * mnp, hipMemcpyDeviceToDevice, st));
-                launch_gemm(st, 1, 1, mnp, mnp, mp, Kx, mnp, Tmp, mnp, dVar, mnp, -1.0, 1.0);                      // K** - Kx^T Winv_d Kx
-                HIP_CHECK(hipMemcpy2DAsync(hv.data(), sizeof(double) * Mn, dVar, sizeof(double) * mnp, sizeof(double) * Mn, Mn,
+                HIP_CHECK(hipMemcpy2DAsync(hv.data(), sizeof(double) * Mn, q.var, sizeof(double) * q.mnp, sizeof(double) * Mn, Mn,
                                            hipMemcpyDeviceToHost, st));
                 HIP_CHECK(hipStreamSynchronize(st));
                 for (int64_t i = 0; i < Mn * Mn; ++i) var_out[i * L + d] = hv[(size_t)i];

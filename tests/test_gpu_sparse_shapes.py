@@ -23,6 +23,9 @@ is there for the next one.  Families (N, M, D, Dy):
     dispatch  N = 193, M = 65, (D, Dy) = (16,4) (16,5) (17,1) (32,4) (32,5) (33,1) (1,1), rbf_ard and matern32_ard
     stale     no set_data between: product + per-point noise, Dy = 3, M = 129 -> rbf_ard, scalar noise, M = 129 -> M = 128 -> new
               Z and theta
+    wide      N = 70, M = 20, Dy = 1, rbf_ard at D = 240 | 241: eight theta records of 34 doubles; D = 241 is the first to use
+              entry 256 (the lengthscale sum of q = 240), which one 256-thread block does not reach (the shipped code before
+              the row-gradient step became shared failed it: dtheta 8.6e-07 against a bound of 2.0e-12)
     chunks    blocked reference: 262145/128/2/1 rbf_ard (fused, m == mp, ragged second chunk), 266240/3/2/2 rbf_ard + bias
               with per-point noise and dL_dm (two full chunks with m < mp: no memset; unfused; dL_dKnm rows 133000 ... 133299
               straddle the chunk boundary), 262145/65/3/1 product + white
@@ -42,7 +45,7 @@ the prediction columns are those at 129 points; err/bound = the worst ratio of a
 
 The interior dL_dKnm block and the one-point prediction stay within 3e-13; dL_dKmm differs from its transpose by at most 3e-14
 of its largest entry.  Every case passed as the code stood: the sweep found no fault in the device path, and no product code
-changed with it.  The whole file: 62 cases, about 30 s of wall time, most of it the long-double references (the two
+changed with it.  The whole file: 64 cases, about 30 s of wall time, most of it the long-double references (the two
 262145-row cases take 4 ... 6 s each, the blocked reference and the fp64 oracle on a quarter of a million rows).
 """
 import numpy as np
@@ -115,6 +118,20 @@ def test_sparse_shape_edges(name, sctx):
 @pytest.mark.parametrize("name", SL.BLOCKED)
 def test_sparse_several_chunks(name, sctx):
     _check(sctx, name)
+
+
+# Entry 256 of a part's theta record (eight records of 34 doubles, one per 32 dimensions) is the lengthscale sum of dimension
+# q = 240: D = 241 is the smallest D that uses it, D = 240 the largest that does not.  Rows accumulate into the record one
+# chunk at a time with a launch that must cover all of it, not its first 256 entries.  N = 70, M = 20, Dy = 1, scalar noise;
+# not in sparse_ld.CASES (the CPU sweep and the bit dumps of tools/sparse_bits.py walk that list): known by name to
+# sparse_ld.make_case for the length of the test.
+WIDE = [SL._case("dispatch", "rbf_ard", 70, 20, D, 1) for D in (240, 241)]
+
+
+@pytest.mark.parametrize("case", WIDE, ids=lambda c: c["name"])
+def test_sparse_theta_record_past_256_entries(case, sctx, monkeypatch):
+    monkeypatch.setitem(SL.BY_NAME, case["name"], case)
+    _check(sctx, case["name"])
 
 
 def test_sparse_is_deterministic_across_fresh_contexts():
