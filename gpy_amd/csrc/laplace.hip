@@ -45,13 +45,15 @@ __global__ void k_lap_mm_mul(double* __restrict__ M, const double* __restrict__ 
     const long j = (long)blockIdx.x * blockDim.x + threadIdx.x, i = blockIdx.y;
     if (j < n) M[i * ld + j] *= G[i * ld + j];
 }
-// out[i][j] = sw_i A_(max, min) sw_j: K_Wi_i = W^1/2 B^-1 W^1/2 (laplace.py:338) from the lower tiles of B^-1
+// out[i][j] = sw_max A_(max, min) sw_min: K_Wi_i = W^1/2 B^-1 W^1/2 (laplace.py:338) from the lower tiles of B^-1.  The two
+// products are taken in the order of the lower triangle on both sides of the diagonal (the order k_laplace_dLdK uses), so that
+// (i, j) and (j, i) are the same number: (sw_i A) sw_j and (sw_j A) sw_i differ in the last bit
 __global__ void k_lap_extract_kwi(const double* __restrict__ A, long ld, long n, const double* __restrict__ sw,
                                   double* __restrict__ out) {
     const long j = (long)blockIdx.x * blockDim.x + threadIdx.x, i = blockIdx.y;
     if (j >= n) return;
     const long hi = i > j ? i : j, lo = i > j ? j : i;
-    out[i * n + j] = sw[i] * A[hi * ld + lo] * sw[j];
+    out[i * n + j] = sw[hi] * A[hi * ld + lo] * sw[lo];
 }
 __global__ void k_lap_extract_full(const double* __restrict__ A, long ld, long n, double* __restrict__ out) {
     const long j = (long)blockIdx.x * blockDim.x + threadIdx.x, i = blockIdx.y;
