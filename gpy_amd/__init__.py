@@ -16,26 +16,27 @@ from .kern import (OU, RBF, Add, Prod, Bias, Coregionalize, ExpQuad, Exponential
 from .likelihoods import Bernoulli, Gaussian, HeteroscedasticGaussian, MixedNoise, Poisson, StudentT
 from .models import GP, GPClassification, GPCoregionalizedRegression, GPHeteroscedasticRegression, GPRegression
 from .posterior import PosteriorEP, PosteriorExact, StudentTPosterior
-from .sparse import SparseGP, SparseGPRegression, VarDTC
+from .sparse import BayesianGPLVM, SparseGP, SparseGPRegression, VarDTC
 from .svgp import SVGPModel as SVGP
 from .svgp import SVGPPosterior
-from .variational import NormalPosterior
+from .variational import NormalPosterior, NormalPrior
 
 __all__ = ["RBF", "OU", "ExpQuad", "HeteroscedasticGaussian", "StudentTPosterior", "Matern52", "Matern32", "Exponential", "RatQuad", "StdPeriodic", "Coregionalize", "Linear", "MLP", "Poly", "MixedNoise", "Stationary", "White", "Bias", "Add", "Prod", "Gaussian", "ExactGaussianInference", "ExactStudentTInference",
-           "PosteriorExact", "GP", "GPRegression", "GPHeteroscedasticRegression", "GPCoregionalizedRegression", "Laplace", "LaplacePosterior", "EP", "PosteriorEP", "Bernoulli", "StudentT", "Poisson", "GPClassification", "VarDTC", "SparseGP", "SparseGPRegression", "SVGP", "SVGPPosterior", "NormalPosterior", "MI355GPError", "build", "device_count"]
+           "PosteriorExact", "GP", "GPRegression", "GPHeteroscedasticRegression", "GPCoregionalizedRegression", "Laplace", "LaplacePosterior", "EP", "PosteriorEP", "Bernoulli", "StudentT", "Poisson", "GPClassification", "VarDTC", "SparseGP", "SparseGPRegression", "SVGP", "SVGPPosterior", "NormalPosterior", "NormalPrior", "BayesianGPLVM", "MI355GPError", "build", "device_count"]
 
 # GPy's import paths, so that `import gpy_amd as GPy` reads like the reference on this path:
 #   GPy.kern.RBF, GPy.likelihoods.Gaussian, GPy.models.GPRegression / SparseGPRegression / GPHeteroscedasticRegression,
 #   GPy.models.GPClassification, GPy.likelihoods.Bernoulli / StudentT / Poisson, GPy.likelihoods.link_functions.Probit /
 #   Identity / Log,
 #   GPy.core.GP / SparseGP / SVGP, GPy.inference.latent_function_inference.ExactGaussianInference / VarDTC / Laplace / EP / SVGP,
-#   GPy.util.choleskies
+#   GPy.util.choleskies, GPy.models.BayesianGPLVM, GPy.util.initialization.initialize_latent
 from . import ep, inference, kern, laplace, likelihoods, link_functions, linalg, models, sparse, svgp, util  # noqa: E402
 import types as _types  # noqa: E402
 
 models.SparseGPRegression = SparseGPRegression
+models.BayesianGPLVM = BayesianGPLVM
 core = _types.SimpleNamespace(GP=GP, SparseGP=SparseGP, SVGP=SVGP, svgp=_types.SimpleNamespace(SVGP=SVGP), parameterization=_types.SimpleNamespace(
-    variational=_types.SimpleNamespace(NormalPosterior=NormalPosterior)))
+    variational=_types.SimpleNamespace(NormalPosterior=NormalPosterior, NormalPrior=NormalPrior)))
 likelihoods.mixed_noise = _types.SimpleNamespace(MixedNoise=MixedNoise)
 inference.latent_function_inference = _types.SimpleNamespace(
     ExactGaussianInference=ExactGaussianInference, ExactStudentTInference=ExactStudentTInference, VarDTC=VarDTC,

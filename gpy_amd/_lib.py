@@ -174,6 +174,9 @@ def lib():
     L.mi355gp_vardtc_inference_uncertain.argtypes = [vp, ci, ctypes.POINTER(Part), _dp, i64, _dp, i64, cd, _dp, _c_dp, _c_dp,
                                                      _c_dp, _c_dp, _c_dp, _c_dp]
     L.mi355gp_sparse_predict.argtypes = [vp, ci, ctypes.POINTER(Part), _dp, i64, _c_dp, _c_dp, ci]
+    L.mi355gp_sparse_set_inputs.argtypes = [vp, _dp, _c_dp, i64, ci]
+    L.mi355gp_sparse_predict_uncertain.argtypes = [vp, ci, ctypes.POINTER(Part), _dp, _dp, i64, _dp, _c_dp]
+    L.mi355gp_sparse_get_predict_ms.argtypes = [vp, _c_dp]
     L.mi355gp_sparse_fetch_dLdKnm.argtypes = [vp, i64, i64, _dp]
     L.mi355gp_sparse_attach_loopback.argtypes = [vp, ci, ci, ci]
     L.mi355gp_svgp_forward.argtypes = [vp, ci, ctypes.POINTER(Part), _dp, i64, _dp, _dp, ci, cd, _dp, _dp, _dp, _c_dp]
@@ -209,7 +212,8 @@ def lib():
                  "dbg_ipc_selftest", "laplace_begin", "laplace_newton", "laplace_finish", "laplace_gradients",
                  "laplace_implicit", "laplace_predict", "ep_recompute", "ep_sweep", "rbf_psi", "rbf_psi_grad",
                  "sparse_set_input_variance", "vardtc_inference_uncertain", "svgp_forward", "svgp_backward",
-                 "svgp_predict"):
+                 "svgp_predict", "sparse_set_inputs", "sparse_predict_uncertain",
+                 "sparse_get_predict_ms"):
         getattr(L, "mi355gp_" + name).restype = ci
     _lib = L
     return L
@@ -234,7 +238,8 @@ EXPORTED = ("mi355gp_last_error", "mi355gp_version", "mi355gp_device_count", "mi
             "mi355gp_laplace_begin", "mi355gp_laplace_newton", "mi355gp_laplace_finish", "mi355gp_laplace_gradients",
             "mi355gp_laplace_implicit", "mi355gp_laplace_predict", "mi355gp_ep_recompute", "mi355gp_ep_sweep",
             "mi355gp_rbf_psi", "mi355gp_rbf_psi_grad", "mi355gp_sparse_set_input_variance",
-            "mi355gp_vardtc_inference_uncertain", "mi355gp_svgp_forward", "mi355gp_svgp_backward", "mi355gp_svgp_predict")
+            "mi355gp_vardtc_inference_uncertain", "mi355gp_svgp_forward", "mi355gp_svgp_backward", "mi355gp_svgp_predict",
+            "mi355gp_sparse_set_inputs", "mi355gp_sparse_predict_uncertain", "mi355gp_sparse_get_predict_ms")
 
 
 # mi355gp_set_option / mi355gp_get_option ids (include/mi355gp.h, MI355GP_OPT_*)
@@ -627,6 +632,31 @@ class SparseContext(object):
         S = f64(S)
         assert S.ndim == 2, "S must be N x D"
         check(lib().mi355gp_sparse_set_input_variance(self._h, S, S.shape[0], S.shape[1]), "mi355gp_sparse_set_input_variance")
+
+    def set_inputs(self, X, S=None):
+        """Replaces the inputs of `set_data` (and, with S, their variances); Y stays resident on the device."""
+        X = f64(X)
+        S = None if S is None else f64(S)
+        assert X.ndim == 2 and (S is None or S.shape == X.shape), "X and S must be N x D"
+        check(lib().mi355gp_sparse_set_inputs(self._h, X, _opt(S), X.shape[0], X.shape[1]), "mi355gp_sparse_set_inputs")
+
+    def predict_uncertain(self, specs, mu_new, S_new, want_var=True):
+        """(mean (M* x Dy), var (M* x Dy) or None) of the sparse posterior of the last call at points N(mu_new, diag S_new)."""
+        arr, keep, _ = make_parts(specs)
+        mu_new, S_new = f64(mu_new), f64(S_new)
+        assert mu_new.ndim == 2 and mu_new.shape[1] == self.D and S_new.shape == mu_new.shape, "mu_new and S_new must be M* x D"
+        Mn = mu_new.shape[0]
+        mean = np.empty((Mn, self.Dy))
+        var = np.empty((Mn, self.Dy)) if want_var else None
+        check(lib().mi355gp_sparse_predict_uncertain(self._h, len(specs), arr, mu_new, S_new, Mn, mean, _opt(var)),
+              "mi355gp_sparse_predict_uncertain")
+        return mean, var
+
+    def predict_ms(self):
+        """HIP-event time (ms) of the stream work of the last `predict_uncertain` call"""
+        out = np.zeros(1)
+        check(lib().mi355gp_sparse_get_predict_ms(self._h, out.ctypes.data_as(_c_dp)), "mi355gp_sparse_get_predict_ms")
+        return float(out[0])
 
     def vardtc_uncertain(self, specs, Z, noise, extra_jitter=0.0, want_dmu_dS=True, want_stage_ms=False):
         """One evaluation with uncertain inputs (one RBF part alone or with White parts, ONE noise variance).

@@ -10,6 +10,9 @@
 #define PSI_SPLIT_MAX 16       // most row splits of the psi2 sum
 #define PSI_GROWS 256          // rows one workgroup of a gradient kernel walks (16 at a time)
 #define PSI_CHUNK 2048         // rows per chunk (bounds every partial buffer); psi2 is compute-bound, not HBM-bound
+#define PSI_CG 4               // output columns one register group of the psi2n contraction carries
+#define PSI_CONTRACT_RB(QP) ((QP) > 32 ? 16 : ((QP) > 16 ? 32 : 64))     // rows a workgroup of the contraction stages (16 KB)
+#define PSI_CONTRACT_SPLIT_MAX 64    // most splits of the contraction's lower-tile list
 #define PSI_MMAX 65535         // most inducing points: the M x M helper kernels put M in gridDim.y
 
 // dL_dpsi1[n][m] = beta sum_d R[n][d] v[m][d] formed on the fly (the fit's rank-Dy product, var_dtc.py:219)
@@ -44,3 +47,12 @@ void launch_psi_rowfinish(hipStream_t st, const double* P1s, const double* P2s, 
                           int D, int Qp, double* dmu, double* dS, double* rowrec);
 // zz (m x 2 Qp): the z_m - z_o sums of dL * psi2 (both ld ldm, dL symmetric)
 void launch_psi2_zz(hipStream_t st, const double* dL, const double* psi2, long ldm, const double* Zp, long m, int Qp, double* zz);
+// Prediction at uncertain points: part[split][n][c] (splits x rows x (Dy + 1)) = the split's share of
+// sum_mo psi2n[m][o] lam[m][c] lam[o][c] (c < Dy; lam: m x Dy) and of sum_mo psi2n[m][o] W[m][o] (c == Dy; W ld ldw); returns the
+// number of splits written, psi_contract_nsplit(rows, m, Qp) (sum them with launch_sum_splits: a fixed order)
+int psi_contract_nsplit(long rows, long m, int Qp);
+int launch_psi2n_contract(hipStream_t st, const double* rd2, const double* lg2, const double* Zp, const double* ap,
+                          const double* lam, int Dy, const double* W, long ldw, long rows, long m, int Qp, double var2,
+                          double* part);
+// var (rows x Dy) = max(psi0 + C[n][d] - C[n][Dy] - mean[n][d]^2, 1e-15); C: rows x (Dy + 1)
+void launch_psi_predvar(hipStream_t st, const double* C, const double* mean, double psi0, long rows, int Dy, double* var);

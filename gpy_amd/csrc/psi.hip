@@ -16,6 +16,8 @@
 // and per inducing point m and dimension q   Zs = sum c L d (over n, resp. n and o).  psi2n is recomputed tile by tile, an
 // N x M x M array never exists.  k_psi_rowfinish turns the P into dmu, dS and the per-row variance / lengthscale sums; the
 // z_m - z_o terms of psi2 need only the M x M matrix dL_dpsi2 * psi2 (k_psi2_zz).
+//
+// Prediction at uncertain points (posterior.py:249-269) contracts psi2n per row against given M x M weights: k_psi2n_contract.
 #include <cmath>
 #include <vector>
 
@@ -164,6 +166,114 @@ __global__ void k_psi2_combine(const double* __restrict__ part, long ld, long m,
     double s = accumulate ? out[i * ldo + j] : 0.0;
     for (int k = 0; k < nsplit; ++k) s += part[(long)k * ld * ld + a * ld + b];
     out[i * ldo + j] = s;
+}
+
+// ---- prediction at uncertain points: psi2n contracted per row against given matrices ---------------------------------------
+// part[split][n][c] = sum over the split's lower (m, o) tiles of psi2n[m][o] * wgt_c[m][o], c < Dy + 1, with
+//   wgt_c = lam[m][c] lam[o][c] for c < Dy (woodbury_vector, M x Dy) and wgt_Dy = W[m][o] (woodbury_inv, ld ldw):
+// the two sums of Posterior._raw_predict at uncertain points (posterior.py:262-266); an off-diagonal tile stands for its
+// mirror as well (factor 2 on lam lam^T, W[m][o] + W[o][m]).  A workgroup owns RB rows (staged in LDS once) and walks its
+// tiles tl = split, split + nsplit, ... in that order.  Per tile and 16 rows: thread (m, o) evaluates psi2n once into LDS
+// (Ps, 16 x 256); then thread (row, slice) sums 16 of the 256 values against PSI_CG output columns at a time -- weights
+// formed in LDS from the tile's 2 x 16 rows of lam -- the 16 slices are added by lane shuffles (fixed tree) and the slice-0
+// lane adds the sum to ITS element of part: one thread, program order, no atomics.  Neither an N* x M x M array nor Dy
+// M x M matrices exist.  Static LDS: 16 (rows) + 32 (Ps) + 8 (weights) + 1.5 KB at every QP.
+template <int QP>
+__global__ __launch_bounds__(256) void k_psi2n_contract(const double2* __restrict__ rd2, const double* __restrict__ lg2,
+                                                        const double* __restrict__ Zp, const double* __restrict__ ap,
+                                                        const double* __restrict__ lam, int Dy, const double* __restrict__ W,
+                                                        long ldw, long rows, long m, long ntl, int nsplit, double var2,
+                                                        double* __restrict__ part) {
+    constexpr int RB = PSI_CONTRACT_RB(QP);
+    __shared__ double2 rs[RB * QP];
+    __shared__ double lgs[RB];
+    __shared__ double Ps[16 * 256];
+    __shared__ double wt[PSI_CG * 256];
+    __shared__ double lamT[2 * 16 * PSI_CG];
+    const int t = threadIdx.x, NC = Dy + 1;
+    const long rb0 = (long)blockIdx.y * RB;
+    const int nr = (rows - rb0 < RB) ? (int)(rows - rb0) : RB;           // rows of this workgroup (>= 1)
+    for (int idx = t; idx < RB * QP; idx += 256) {
+        const int r = idx / QP;
+        rs[idx] = (r < nr) ? rd2[(rb0 + r) * QP + (idx % QP)] : make_double2(0.0, 0.0);
+    }
+    if (t < RB) lgs[t] = (t < nr) ? lg2[rb0 + t] : 0.0;
+    const int br = t >> 4, ks = t & 15;                                  // the contraction's (row, slice)
+    bool first = true;
+    for (long tl = blockIdx.x; tl < ntl; tl += nsplit) {
+        int ti, tj;
+        psi_tile(tl, &ti, &tj);
+        const long mi = (long)ti * PSI_T2 + (t >> 4), oj = (long)tj * PSI_T2 + (t & 15);
+        const bool ok = mi < m && oj < m;
+        double zb[QP];
+        double zd = 0.0;
+#pragma unroll
+        for (int q = 0; q < QP; ++q) {
+            const double zm = Zp[mi * QP + q], zo = Zp[oj * QP + q], dz = zm - zo;
+            zb[q] = 0.5 * (zm + zo);
+            zd = fma(ap[q] * dz, dz, zd);
+        }
+        zd *= 0.25;
+        const double f = (ti == tj) ? 1.0 : 2.0;
+        const double wmo = ok ? ((ti == tj) ? W[mi * ldw + oj] : W[mi * ldw + oj] + W[oj * ldw + mi]) : 0.0;
+        for (int sb = 0; sb < nr; sb += 16) {
+            __syncthreads();                                             // Ps is free (and rs / lgs are stored)
+#pragma unroll 4
+            for (int r = 0; r < 16; ++r) {
+                double e = zd;
+#pragma unroll
+                for (int q = 0; q < QP; ++q) {
+                    const double2 v = rs[(sb + r) * QP + q];
+                    const double d = v.x - zb[q];
+                    e = fma(v.y * d, d, e);
+                }
+                Ps[r * 256 + t] = ok ? var2 * exp(lgs[sb + r] - e) : 0.0;
+            }
+            for (int g0 = 0; g0 < NC; g0 += PSI_CG) {
+                if (t < 2 * 16 * PSI_CG) {                               // the tile's rows of lam: [0] m side, [1] o side
+                    const int side = t / (16 * PSI_CG), r = (t / PSI_CG) & 15, c = t % PSI_CG;
+                    const long row = (side ? (long)tj : (long)ti) * PSI_T2 + r;
+                    lamT[t] = (row < m && g0 + c < Dy) ? lam[row * Dy + g0 + c] : 0.0;
+                }
+                __syncthreads();                                         // (also: Ps complete, the last contraction done)
+#pragma unroll
+                for (int c = 0; c < PSI_CG; ++c) {
+                    const double ll = f * lamT[(t >> 4) * PSI_CG + c] * lamT[(16 + (t & 15)) * PSI_CG + c];
+                    wt[c * 256 + t] = (g0 + c < Dy) ? (ok ? ll : 0.0) : (g0 + c == Dy ? wmo : 0.0);
+                }
+                __syncthreads();
+                double acc[PSI_CG];
+#pragma unroll
+                for (int c = 0; c < PSI_CG; ++c) acc[c] = 0.0;
+                for (int j = 0; j < 16; ++j) {
+                    const double p = Ps[br * 256 + j * 16 + ks];
+#pragma unroll
+                    for (int c = 0; c < PSI_CG; ++c) acc[c] = fma(p, wt[c * 256 + j * 16 + ks], acc[c]);
+                }
+#pragma unroll
+                for (int s = 1; s < 16; s <<= 1)
+#pragma unroll
+                    for (int c = 0; c < PSI_CG; ++c) acc[c] += __shfl_xor(acc[c], s);
+                if (ks == 0 && sb + br < nr) {
+                    double* o = part + ((long)blockIdx.x * rows + rb0 + sb + br) * NC + g0;
+#pragma unroll
+                    for (int c = 0; c < PSI_CG; ++c)
+                        if (g0 + c < NC) o[c] = first ? acc[c] : o[c] + acc[c];
+                }
+            }
+        }
+        first = false;
+    }
+}
+
+// var[n][d] = max(psi0 + C[n][d] - C[n][Dy] - mean[n][d]^2, 1e-15)   (posterior.py:262-268; C: rows x (Dy + 1))
+__global__ void k_psi_predvar(const double* __restrict__ C, const double* __restrict__ mean, double psi0, long rows, int Dy,
+                              double* __restrict__ var) {
+    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= rows * Dy) return;
+    const long n = i / Dy;
+    const double mu = mean[i], v = psi0 + C[n * (Dy + 1) + (i - n * Dy)] - C[n * (Dy + 1) + Dy] - mu * mu;
+    var[i] = v < 1e-15 ? 1e-15 : v;
 }
 
 // ---- gradient kernels --------------------------------------------------------------------------------------------
@@ -527,6 +637,41 @@ void launch_psi_rowfinish(hipStream_t st, const double* P1s, const double* P2s, 
 }
 void launch_psi2_zz(hipStream_t st, const double* dL, const double* psi2, long ldm, const double* Zp, long m, int Qp, double* zz) {
     hipLaunchKernelGGL(k_psi2_zz, dim3((unsigned)m), dim3(256), 0, st, dL, psi2, ldm, Zp, m, Qp, zz);
+}
+
+int psi_contract_nsplit(long rows, long m, int Qp) {
+    const long nt = (m + PSI_T2 - 1) / PSI_T2, ntl = nt * (nt + 1) / 2, rb = PSI_CONTRACT_RB(Qp), nrb = (rows + rb - 1) / rb;
+    long s = (1024 + nrb - 1) / nrb;                           // about four workgroups per CU
+    if (s > ntl) s = ntl;
+    if (s > PSI_CONTRACT_SPLIT_MAX) s = PSI_CONTRACT_SPLIT_MAX;
+    return s < 1 ? 1 : (int)s;
+}
+template <int QP>
+static void launch_psi2n_contract_t(hipStream_t st, const double2* rd2, const double* lg2, const double* Zp, const double* ap,
+                                    const double* lam, int Dy, const double* W, long ldw, long rows, long m, int ns, double var2,
+                                    double* part) {
+    const long nt = (m + PSI_T2 - 1) / PSI_T2, ntl = nt * (nt + 1) / 2, nrb = (rows + PSI_CONTRACT_RB(QP) - 1) / PSI_CONTRACT_RB(QP);
+    hipLaunchKernelGGL((k_psi2n_contract<QP>), dim3((unsigned)ns, (unsigned)nrb), dim3(256), 0, st, rd2, lg2, Zp, ap, lam, Dy, W,
+                       ldw, rows, m, ntl, ns, var2, part);
+}
+int launch_psi2n_contract(hipStream_t st, const double* rd2, const double* lg2, const double* Zp, const double* ap,
+                          const double* lam, int Dy, const double* W, long ldw, long rows, long m, int Qp, double var2,
+                          double* part) {
+    const int ns = psi_contract_nsplit(rows, m, Qp);
+    const double2* rd = (const double2*)rd2;
+    switch (Qp) {
+        case 1: launch_psi2n_contract_t<1>(st, rd, lg2, Zp, ap, lam, Dy, W, ldw, rows, m, ns, var2, part); break;
+        case 2: launch_psi2n_contract_t<2>(st, rd, lg2, Zp, ap, lam, Dy, W, ldw, rows, m, ns, var2, part); break;
+        case 4: launch_psi2n_contract_t<4>(st, rd, lg2, Zp, ap, lam, Dy, W, ldw, rows, m, ns, var2, part); break;
+        case 8: launch_psi2n_contract_t<8>(st, rd, lg2, Zp, ap, lam, Dy, W, ldw, rows, m, ns, var2, part); break;
+        case 16: launch_psi2n_contract_t<16>(st, rd, lg2, Zp, ap, lam, Dy, W, ldw, rows, m, ns, var2, part); break;
+        case 32: launch_psi2n_contract_t<32>(st, rd, lg2, Zp, ap, lam, Dy, W, ldw, rows, m, ns, var2, part); break;
+        default: launch_psi2n_contract_t<64>(st, rd, lg2, Zp, ap, lam, Dy, W, ldw, rows, m, ns, var2, part); break;
+    }
+    return ns;
+}
+void launch_psi_predvar(hipStream_t st, const double* C, const double* mean, double psi0, long rows, int Dy, double* var) {
+    hipLaunchKernelGGL(k_psi_predvar, dim3((unsigned)((rows * Dy + 255) / 256)), dim3(256), 0, st, C, mean, psi0, rows, Dy, var);
 }
 
 // ---- the stateless entry points ----------------------------------------------------------------------------------

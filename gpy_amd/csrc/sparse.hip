@@ -493,6 +493,30 @@ int mi355gp_sparse_set_input_variance(mi355gp_sparse* s, const double* S, int64_
     return 0;
 }
 
+// Replaces the inputs of set_data -- X (N x D), and with S != NULL the input variances -- and nothing else: Y and everything
+// sized by Y stay resident (a Bayesian GPLVM step changes every mean and variance of q(X) and not Y, the wide matrix).  S is
+// validated as mi355gp_sparse_set_input_variance validates it; the last result is forgotten as after set_data.
+int mi355gp_sparse_set_inputs(mi355gp_sparse* s, const double* X, const double* S, int64_t N, int D) {
+    ARG_CHECK(s && s->n > 0, "mi355gp_sparse_set_inputs: set_data first");
+    ARG_CHECK(X && N == s->n && D == s->D, "mi355gp_sparse_set_inputs: X (and S) must be N x D, the shape of set_data's X");
+    ARG_CHECK(!sharded(s), "mi355gp_sparse_set_inputs: replacing the inputs of a row-sharded context is not supported");
+    for (int64_t i = 0; i < N * D; ++i) {
+        if (!std::isfinite(X[i]))
+            PART_FAIL("mi355gp_sparse_set_inputs: input X[%lld][%lld] = %g is not finite", (long long)(i / D), (long long)(i % D), X[i]);
+        if (S && (!(S[i] > 0.0) || !std::isfinite(S[i])))
+            PART_FAIL("mi355gp_sparse_set_inputs: input variance S[%lld][%lld] = %g: every entry must be positive and finite",
+                      (long long)(i / D), (long long)(i % D), S[i]);
+    }
+    HIP_CHECK(hipSetDevice(s->device));
+    EngineShared gate(s->device);
+    HIP_CHECK(hipStreamSynchronize(s->st));
+    if (S && !s->dSvar) HIP_CHECK(hipMalloc(&s->dSvar, sizeof(double) * N * D));
+    HIP_CHECK(hipMemcpy(s->dX, X, sizeof(double) * N * D, hipMemcpyHostToDevice));
+    if (S) HIP_CHECK(hipMemcpy(s->dSvar, S, sizeof(double) * N * D, hipMemcpyHostToDevice));
+    s->have_result = s->winv_ok = s->svgp_result = false;
+    return 0;
+}
+
 // Row-sharded mode: call once, before set_data, on every rank (id128 from mi355gp_grid_unique_id on rank 0).
 // Each rank then passes ITS rows to mi355gp_sparse_set_data; Z and theta are replicated; results are identical on all ranks.
 int mi355gp_sparse_attach_comm(mi355gp_sparse* s, int rank, int world, const void* id128) {
@@ -1275,8 +1299,8 @@ static int uncertain_pass2(mi355gp_sparse* s, PsiWork& w, double beta) {
     return 0;
 }
 
-static int uncertain_check_parts(const mi355gp_sparse* s, int nparts, const mi355gp_part* parts, int64_t M, int* irbf_out) {
-    const char* where = "mi355gp_vardtc_inference_uncertain";
+static int uncertain_check_parts(const mi355gp_sparse* s, int nparts, const mi355gp_part* parts, int64_t M, int* irbf_out,
+                                 const char* where = "mi355gp_vardtc_inference_uncertain") {
     int irbf = -1;
     for (int i = 0; i < nparts; ++i) {
         if (parts[i].term != 0) PART_FAIL("%s: part %d is a factor of a product; products have no psi statistics here", where, i);
@@ -1288,8 +1312,8 @@ static int uncertain_check_parts(const mi355gp_sparse* s, int nparts, const mi35
         irbf = i;
     }
     if (irbf < 0) PART_FAIL("%s: no RBF part; uncertain inputs take one RBF part and White parts only", where);
-    ARG_CHECK(s->D <= PSI_QMAX, "mi355gp_vardtc_inference_uncertain: the psi-statistics kernels take at most 64 input dimensions");
-    ARG_CHECK(M <= PSI_MMAX, "mi355gp_vardtc_inference_uncertain: the psi-statistics kernels take at most 65535 inducing points");
+    if (s->D > PSI_QMAX) PART_FAIL("%s: the psi-statistics kernels take at most 64 input dimensions", where);
+    if (M > PSI_MMAX) PART_FAIL("%s: the psi-statistics kernels take at most 65535 inducing points", where);
     *irbf_out = irbf;
     return 0;
 }
@@ -1468,6 +1492,95 @@ int mi355gp_sparse_predict(mi355gp_sparse* s, int nparts, const mi355gp_part* pa
     HIP_CHECK(hipGetLastError());
     if (var_out && !full_cov)
         for (int64_t i = 0; i < Mn; ++i) var_out[i] = var_out[i] < 1e-15 ? 1e-15 : var_out[i];      // posterior.py:248
+    return 0;
+}
+
+// Prediction at UNCERTAIN new points q(x*) = N(mu_new, diag S_new) (Posterior._raw_predict with a VariationalPosterior,
+// posterior.py:249-269, full_cov = False) for the kernel of the last VarDTC call, one RBF part alone or with White parts
+// (White adds to psi0* only: its psi1 / psi2 are zero, static.py):
+//   mean = psi1* lam,  var[n][d] = psi0* + sum_mo psi2n*[m][o] (lam[m][d] lam[o][d] - W[m][o]) - mean[n][d]^2, clipped at 1e-15
+// with lam = woodbury_vector and W = woodbury_inv, both resident.  Rows go in chunks of PSI_CHUNK: psi1 and the thin product
+// for the mean, k_psi2n_contract (psi.hip) for the two sums; every sum has a fixed order.
+int mi355gp_sparse_predict_uncertain(mi355gp_sparse* s, int nparts, const mi355gp_part* parts, const double* mu_new,
+                                     const double* S_new, int64_t Mn, double* mean_out, double* var_out) {
+    const char* where = "mi355gp_sparse_predict_uncertain";
+    ARG_CHECK(!s || !s->svgp_result, "mi355gp_sparse_predict_uncertain: the last call on this context was an SVGP call (this entry describes VarDTC's result)");
+    ARG_CHECK(s && s->have_result, "mi355gp_sparse_predict_uncertain: no result yet; run a VarDTC inference call first");
+    ARG_CHECK(!sharded(s), "mi355gp_sparse_predict_uncertain: a row-sharded context is not supported at uncertain points");
+    ARG_CHECK(parts && nparts >= 1 && mu_new && S_new && Mn > 0 && mean_out, "mi355gp_sparse_predict_uncertain: bad arguments");
+    int irbf = -1;
+    if (int rc = uncertain_check_parts(s, nparts, parts, s->m, &irbf, where)) return rc;
+    const int D = s->D, Dy = s->Dy, NC = Dy + 1;
+    for (int64_t i = 0; i < Mn * D; ++i)
+        if (!(S_new[i] > 0.0) || !std::isfinite(S_new[i]) || !std::isfinite(mu_new[i]))
+            PART_FAIL("%s: input variance S[%lld][%lld] = %g (mean %g): every entry must be positive and finite", where,
+                      (long long)(i / D), (long long)(i % D), S_new[i], mu_new[i]);
+    HIP_CHECK(hipSetDevice(s->device));
+    EngineShared gate(s->device);
+    if (int rc = prepare_sparse_parts(s, nparts, parts)) return rc;
+    hipStream_t st = s->st;
+    scale_for_parts(s, s->dZ, s->m, s->mp, true);
+    if (int rc = ensure_winv(s)) return rc;
+    const long m = s->m, mp = s->mp, mpad = round_up(m, PSI_KT), chunk = Mn < PSI_CHUNK ? Mn : PSI_CHUNK;
+    const int Qp = psi_qp(D);
+    const SPart& rbf = s->parts[(size_t)irbf];
+    const double var = rbf.kp.variance, psi0 = expression_kdiag(s->parts, s->terms);
+    std::vector<double> ha((size_t)Qp, 0.0), hz((size_t)m * D), hzp((size_t)mpad * Qp, 0.0);
+    HIP_CHECK(hipMemcpyAsync(hz.data(), s->dZ, sizeof(double) * m * D, hipMemcpyDeviceToHost, st));
+    HIP_CHECK(hipStreamSynchronize(st));
+    for (int q = 0; q < D; ++q) ha[(size_t)q] = rbf.inv_ls[(size_t)q] * rbf.inv_ls[(size_t)q];
+    for (long i = 0; i < m; ++i)
+        for (int q = 0; q < D; ++q) hzp[(size_t)i * Qp + q] = hz[(size_t)i * D + q];
+    DevBuf dA, dZp, dMu, dS, rd1, rd2, lg1, lg2, psi1, part, C, mean, vout;
+    HIP_CHECK(dA.alloc(Qp));
+    HIP_CHECK(dZp.alloc(hzp.size()));
+    HIP_CHECK(dMu.alloc(chunk * D));
+    HIP_CHECK(dS.alloc(chunk * D));
+    HIP_CHECK(rd1.alloc(2 * chunk * Qp));
+    HIP_CHECK(rd2.alloc(2 * chunk * Qp));
+    HIP_CHECK(lg1.alloc(chunk));
+    HIP_CHECK(lg2.alloc(chunk));
+    HIP_CHECK(psi1.alloc(chunk * m));
+    HIP_CHECK(mean.alloc(chunk * Dy));
+    if (var_out) {
+        const long last = Mn - (Mn - 1) / PSI_CHUNK * PSI_CHUNK;       // rows of the last chunk: its split count may be larger
+        const size_t full = (size_t)psi_contract_nsplit(chunk, m, Qp) * chunk, tail = (size_t)psi_contract_nsplit(last, m, Qp) * last;
+        HIP_CHECK(part.alloc((full > tail ? full : tail) * NC));
+        HIP_CHECK(C.alloc(chunk * NC));
+        HIP_CHECK(vout.alloc(chunk * Dy));
+    }
+    HIP_CHECK(hipMemcpyAsync(dA, ha.data(), sizeof(double) * Qp, hipMemcpyHostToDevice, st));
+    HIP_CHECK(hipMemcpyAsync(dZp, hzp.data(), sizeof(double) * hzp.size(), hipMemcpyHostToDevice, st));
+    HIP_CHECK(hipEventRecord(s->ev[4], st));
+    for (long r0 = 0; r0 < Mn; r0 += PSI_CHUNK) {
+        const long rc = (Mn - r0 < PSI_CHUNK) ? (Mn - r0) : PSI_CHUNK;
+        HIP_CHECK(hipMemcpyAsync(dMu, mu_new + r0 * D, sizeof(double) * rc * D, hipMemcpyHostToDevice, st));
+        HIP_CHECK(hipMemcpyAsync(dS, S_new + r0 * D, sizeof(double) * rc * D, hipMemcpyHostToDevice, st));
+        launch_psi_rows(st, dMu, dS, dA, rc, D, Qp, rd1, rd2, lg1, lg2);
+        launch_psi1(st, rd1, lg1, dZp, rc, m, mpad, Qp, var, psi1, m);
+        launch_rowdots(st, psi1, psi1, m, rc, m, s->vvec, Dy, mean, nullptr);
+        HIP_CHECK(hipMemcpyAsync(mean_out + r0 * Dy, mean, sizeof(double) * rc * Dy, hipMemcpyDeviceToHost, st));
+        if (var_out) {
+            const int ns = launch_psi2n_contract(st, rd2, lg2, dZp, dA, s->vvec, Dy, s->Winv, mp, rc, m, Qp, var * var, part);
+            launch_sum_splits(st, part, rc * NC, ns, 0, C);
+            launch_psi_predvar(st, C, mean, psi0, rc, Dy, vout);
+            HIP_CHECK(hipMemcpyAsync(var_out + r0 * Dy, vout, sizeof(double) * rc * Dy, hipMemcpyDeviceToHost, st));
+        }
+        HIP_CHECK(hipStreamSynchronize(st));                   // the chunk's buffers are reused
+    }
+    HIP_CHECK(hipEventRecord(s->ev[5], st));
+    HIP_CHECK(hipStreamSynchronize(st));
+    HIP_CHECK(hipGetLastError());
+    float ms = 0.0f;
+    HIP_CHECK(hipEventElapsedTime(&ms, s->ev[4], s->ev[5]));   // the chunks' uploads, kernels and copies back
+    s->predict_ms = ms;
+    return 0;
+}
+
+// HIP-event time of the stream work of the last mi355gp_sparse_predict_uncertain call, in milliseconds
+int mi355gp_sparse_get_predict_ms(mi355gp_sparse* s, double* ms_out) {
+    ARG_CHECK(s && ms_out, "mi355gp_sparse_get_predict_ms: bad arguments");
+    *ms_out = s->predict_ms;
     return 0;
 }
 

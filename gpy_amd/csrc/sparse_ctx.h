@@ -53,6 +53,7 @@ struct mi355gp_sparse {
     bool ws_ok = false, have_result = false, winv_ok = false;
     hipEvent_t ev[6] = {};
     int h_info[2] = {0, 0};       // LAPACK-style info of the two M x M factorisations (targets of async copies: not on the stack)
+    double predict_ms = 0.0;      // stream time of the last mi355gp_sparse_predict_uncertain call (HIP events ev[4] .. ev[5])
     double beta_scalar = 0.0;     // homoscedastic precision of the last call (0: per-point)
     KernelProf mfma_prof;         // launch timing of the two MFMA kernels of a call: family 0 = T = Kfu dL_dpsi2, 1 = split-K Gram
     // SVGP session (svgp.hip): its M x M state, and whether the context's latest result is an SVGP one (the VarDTC fetch /

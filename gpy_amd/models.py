@@ -380,3 +380,10 @@ class GPCoregionalizedRegression(GP):
         likelihood = multioutput.build_likelihood(Y_list, self.output_index, likelihoods_list)
         super(GPCoregionalizedRegression, self).__init__(X, Y, kernel, likelihood, name=name,
                                                          Y_metadata={"output_index": self.output_index}, device=device)
+
+
+def __getattr__(name):
+    """the latent variable models of the reference that this backend does not have are refused by name"""
+    if name in ("SSGPLVM", "MRD", "GPLVM", "SparseGPLVM"):
+        raise NotImplementedError("GPy.models.%s is not implemented on the MI355X path; BayesianGPLVM is" % name)
+    raise AttributeError("module %r has no attribute %r" % (__name__, name))

@@ -14,6 +14,10 @@ Uncertain inputs: an X that is a `NormalPosterior` (or `SparseGPRegression(X, Y,
 RBF psi-statistics on the device (`mi355gp_vardtc_inference_uncertain`) for one RBF kernel alone or summed with White parts
 and one noise variance; `grad_dict` then has the reference's keys `dL_dpsi0 / dL_dpsi1 / dL_dpsi2` in place of
 `dL_dKdiag / dL_dKnm`, and `fused` also carries the gradients with respect to the inputs' means and variances.
+
+`BayesianGPLVM` (reference `models/bayesian_gplvm.py`) is the `SparseGP` whose inputs are parameters: it consumes those
+gradients, subtracts the KL term of the standard normal prior, uploads a step's new means and variances without Y
+(`mi355gp_sparse_set_inputs`) and predicts at uncertain new points on the device (`mi355gp_sparse_predict_uncertain`).
 """
 import numpy as np
 
@@ -24,7 +28,7 @@ from .likelihoods import Gaussian
 from .linalg import LinAlgError, jitter_ladder
 from .models import PredictionCallers
 from .param import Param, Parameterized
-from .variational import NormalPosterior
+from .variational import NormalPosterior, NormalPrior
 
 
 class _LazyMM(object):
@@ -153,7 +157,10 @@ class SparsePosterior(object):
 
     def _raw_predict(self, kern, Xnew, pred_var, full_cov=False):
         dev = self._device
-        if dev is not None and dev["owner"]._token == dev["token"] and kernel_signature(kern) == dev["sig"]:
+        live = dev is not None and dev["owner"]._token == dev["token"] and kernel_signature(kern) == dev["sig"]
+        if isinstance(Xnew, NormalPosterior):
+            return self._raw_predict_uncertain(kern, Xnew, pred_var, full_cov, dev if live else None)
+        if live:
             return dev["ctx"].predict(kern.part_specs(), kern._slice_X(Xnew), full_cov=full_cov)
         Kx = kern.K(pred_var, Xnew)                                   # (M, N*): foreign kernel / stale device state
         mu = np.dot(Kx.T, self.woodbury_vector)
@@ -163,6 +170,26 @@ class SparsePosterior(object):
         else:
             var = (kern.Kdiag(Xnew) - np.sum(np.dot(Wi.T, Kx) * Kx, 0))[:, None]
             var = np.clip(var, 1e-15, np.inf)                        # posterior.py:248
+        return mu, var
+
+    def _raw_predict_uncertain(self, kern, Xnew, pred_var, full_cov, dev):
+        """at points q(x*) = N(mean, diag variance) (reference `posterior.py:249-269`): on the device
+        (C-ABI `mi355gp_sparse_predict_uncertain`) while the posterior is the context's latest result, otherwise from
+        `kern.psi0 / psi1 / psi2n` on the host, in row blocks that keep the N* x M x M array bounded"""
+        if full_cov:
+            raise NotImplementedError("Full covariance at uncertain new points is not implemented (the reference has none either)")
+        if dev is not None:
+            return dev["ctx"].predict_uncertain(kern.part_specs(), kern._slice_X(Xnew.mean), kern._slice_X(Xnew.variance))
+        la, Wi = np.asarray(self.woodbury_vector), np.asarray(self.woodbury_inv)
+        M, n = la.shape[0], Xnew.shape[0]
+        step = max(1, (1 << 22) // (M * M))                          # at most 32 MB of psi2n at a time
+        mu, var = np.empty((n, la.shape[1])), np.empty((n, la.shape[1]))
+        for r0 in range(0, n, step):
+            q = Xnew[r0:r0 + step]
+            psi0, psi1, psi2n = kern.psi0(pred_var, q), kern.psi1(pred_var, q), kern.psi2n(pred_var, q)
+            mb = np.dot(psi1, la)
+            vb = np.einsum("nmo,md,od->nd", psi2n, la, la) - mb * mb + psi0[:, None] - np.einsum("nmo,mo->n", psi2n, Wi)[:, None]
+            mu[r0:r0 + step], var[r0:r0 + step] = mb, np.clip(vb, 1e-15, np.inf)
         return mu, var
 
     def predictive_gradients(self, kern, Xnew, pred_var=None):
@@ -265,10 +292,15 @@ class VarDTC(object):
         R = _lib.f64(Y)
         if self._ctx is not None and getattr(self._ctx, "sharded", False):
             raise NotImplementedError("uncertain inputs are not supported by a row-sharded sparse context")
-        self._ensure(mu, R)
-        if self._S is None or not self._S.matches(S):
-            self._ctx.set_input_variance(S)
-            self._S = ArrayIdentity(S)
+        if (self._ctx is not None and self._X is not None and self._Y.matches(R) and self._X.value().shape == mu.shape
+                and not self._X.matches(mu)):
+            self._ctx.set_inputs(mu, S)                                # the same Y, new inputs: Y is not uploaded again
+            self._X, self._S = ArrayIdentity(mu), ArrayIdentity(S)
+        else:
+            self._ensure(mu, R)
+            if self._S is None or not self._S.matches(S):
+                self._ctx.set_input_variance(S)
+                self._S = ArrayIdentity(S)
         specs = kern.part_specs()
         (r,), _ = jitter_ladder(lambda extra: self._ctx.vardtc_uncertain(specs, Zs, noise, extra_jitter=extra,
                                                                          want_stage_ms=self.collect_stage_ms),
@@ -464,3 +496,82 @@ class SparseGPRegression(SparseGP):
         super(SparseGPRegression, self).__init__(X, Y, Z, kernel, Gaussian(variance=noise_var),
                                                  name="sparse_gp", device=device, mean_function=mean_function,
                                                  X_variance=X_variance)
+
+
+class BayesianGPLVM(SparseGP):
+    """Bayesian GP latent variable model (reference `GPy/models/bayesian_gplvm.py:12-100`): a `SparseGP` whose inputs are the
+    parameters of q(X) = prod_n N(mean_n, diag variance_n), with the standard normal prior's KL term subtracted from the
+    bound.  The flat parameter order is [X.mean, X.variance, Z, kernel, noise] (X is linked at index 0).  The bound, its
+    gradients in every parameter -- the means and variances of q(X) included -- and prediction at certain or uncertain
+    latent points run on the device through the uncertain-input path of `VarDTC`: the kernel is one `RBF` alone or summed
+    with `White` parts (the reference's default, `RBF(input_dim, ARD=True)`, is covered)."""
+
+    def __init__(self, Y, input_dim, X=None, X_variance=None, init="PCA", num_inducing=10, Z=None, kernel=None,
+                 inference_method=None, likelihood=None, name="bayesian gplvm", device=0, mpi_comm=None, normalizer=None,
+                 missing_data=False, stochastic=False, batchsize=1, Y_metadata=None):
+        for arg, value, default in (("mpi_comm", mpi_comm, None), ("normalizer", normalizer, None),
+                                    ("missing_data", missing_data, False), ("stochastic", stochastic, False),
+                                    ("batchsize", batchsize, 1)):
+            if value is not default and value != default:
+                raise NotImplementedError("BayesianGPLVM: %s = %r is not implemented on the MI355X path (the minibatch / MPI "
+                                          "variant, missing data and normalizers are out of scope)" % (arg, value))
+        Y = np.asarray(Y, dtype=np.float64)
+        if X is None:
+            from .util.initialization import initialize_latent
+            X, fracs = initialize_latent(init, input_dim, Y)
+        else:
+            X = np.asarray(X, dtype=np.float64)
+            fracs = np.ones(input_dim)
+        if X.shape != (Y.shape[0], input_dim):
+            raise ValueError("BayesianGPLVM: X must be %d x %d (one latent point per row of Y), got %r"
+                             % (Y.shape[0], input_dim, X.shape))
+        self.init = init
+        if X_variance is None:
+            X_variance = np.random.uniform(0, 0.1, X.shape)
+        if Z is None:
+            Z = np.random.permutation(X.copy())[:num_inducing]
+        Z = np.asarray(Z, dtype=np.float64)
+        if Z.ndim != 2 or Z.shape[1] != X.shape[1]:
+            raise ValueError("BayesianGPLVM: Z must have %d columns, got shape %r" % (X.shape[1], Z.shape))
+        if kernel is None:
+            kernel = RBF(input_dim, lengthscale=1.0 / fracs, ARD=True, device=device)
+        if likelihood is None:
+            likelihood = Gaussian()
+        self.variational_prior = NormalPrior()
+        super(BayesianGPLVM, self).__init__(NormalPosterior(X, X_variance), Y, Z, kernel, likelihood,
+                                            inference_method=inference_method, name=name, device=device, Y_metadata=Y_metadata)
+        self.link_parameter(self.X, index=0)
+
+    def set_X_gradients(self, X, X_grad):
+        """(dL/dmean, dL/dvariance) onto the two parameters of a `NormalPosterior` (reference `bayesian_gplvm.py:76-78`)"""
+        X.mean.gradient, X.variance.gradient = X_grad
+
+    def get_X_gradients(self, X):
+        """the (mean, variance) gradients of a `NormalPosterior` (reference `bayesian_gplvm.py:80-82`)"""
+        return X.mean.gradient, X.variance.gradient
+
+    def _scatter_X(self, g):
+        if g.shape == self.X.shape:
+            return g
+        full = np.zeros(self.X.shape)
+        full[:, self.kern.active_dims] = g
+        return full
+
+    def parameters_changed(self):
+        super(BayesianGPLVM, self).parameters_changed()
+        self._log_marginal_likelihood = self._log_marginal_likelihood - self.variational_prior.KL_divergence(self.X)
+        # gradients_qX_expectations of the reference (bayesian_gplvm.py:91-96): the device reduced them inside the fit
+        fused = self.grad_dict["fused"]
+        self.set_X_gradients(self.X, (self._scatter_X(fused["dmu"]), self._scatter_X(fused["dS"])))
+        self.variational_prior.update_gradients_KL(self.X)
+        self._Xgrad = self.X.gradient.copy()
+
+    def _raw_predict(self, Xnew, full_cov=False, kern=None):
+        """as `SparseGP._raw_predict`; a `NormalPosterior` Xnew is predicted at as a distribution (reference
+        `posterior.py:249-269`)"""
+        if not isinstance(Xnew, NormalPosterior):
+            return super(BayesianGPLVM, self)._raw_predict(Xnew, full_cov=full_cov, kern=kern)
+        return self.posterior._raw_predict(self.kern if kern is None else kern, Xnew, self.Z.values, full_cov=full_cov)
+
+    def infer_newX(self, Y_new, optimize=True):
+        raise NotImplementedError("BayesianGPLVM.infer_newX is not implemented on the MI355X path")

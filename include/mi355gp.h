@@ -417,6 +417,11 @@ int mi355gp_vardtc_inference_sum(mi355gp_sparse* s, int nparts, const mi355gp_pa
  * kern/src/psi_comp/rbf_psi_comp.py).  S: N x D, the shape of set_data's X (then read as the means); every entry positive and
  * finite, checked on the host before any launch.  set_data discards S. */
 int mi355gp_sparse_set_input_variance(mi355gp_sparse* s, const double* S, int64_t N, int D);
+/* Replaces the inputs of set_data and nothing else: X (N x D, the means when the inputs are uncertain) and, with S != NULL, the
+ * input variances.  Y and everything sized by Y stay resident: this is the upload of one Bayesian GPLVM step, where every mean
+ * and variance of q(X) changes and Y (N x Dy, the wide matrix) does not.  N, D must be set_data's; S is validated as
+ * mi355gp_sparse_set_input_variance validates it; a row-sharded context is refused; the last result is forgotten. */
+int mi355gp_sparse_set_inputs(mi355gp_sparse* s, const double* X, const double* S, int64_t N, int D);
 /* One evaluation with uncertain inputs: one RBF part (iso or ARD, any active_dims) alone or summed with White parts; ONE
  * noise variance (noise_len == 1).  Anything else -- a Bias part, a second RBF, a product, per-point noise, a row-sharded
  * context, no input variances -- is refused with an error that names it.  out_scalars, dtheta_out, dZ_out, wv_out, stage_ms
@@ -433,6 +438,16 @@ int mi355gp_vardtc_inference_uncertain(mi355gp_sparse* s, int nparts, const mi35
  * `parts` = the kernel of the last inference call. */
 int mi355gp_sparse_predict(mi355gp_sparse* s, int nparts, const mi355gp_part* parts, const double* Xnew, int64_t Mn,
                            double* mu_out, double* var_out, int full_cov);
+/* Prediction at UNCERTAIN new points q(x*) = N(mu_new, diag S_new) (Posterior._raw_predict with a VariationalPosterior,
+ * posterior.py:249-269, full_cov = False): mean_out (Mn x Dy) = psi1* woodbury_vector; var_out (optional, Mn x Dy)
+ * = psi0* + sum_mo psi2n*[m][o] (lam[m][d] lam[o][d] - woodbury_inv[m][o]) - mean^2, clipped at 1e-15.  `parts` = the kernel
+ * of the last VarDTC call (certain or uncertain inputs), one RBF part alone or with White parts; anything else, a context
+ * without a result, an SVGP result, a row-sharded context and a non-positive S entry are refused by name.  Neither an
+ * Mn x M x M array nor Dy M x M matrices are formed; two calls give the same bits. */
+int mi355gp_sparse_predict_uncertain(mi355gp_sparse* s, int nparts, const mi355gp_part* parts, const double* mu_new,
+                                     const double* S_new, int64_t Mn, double* mean_out, double* var_out);
+/* Time of the last mi355gp_sparse_predict_uncertain call's stream work (HIP events on the launching stream), milliseconds. */
+int mi355gp_sparse_get_predict_ms(mi355gp_sparse* s, double* ms_out);
 /* Rows [row0, row0 + nrows) of dL_dKnm (nrows x M, row-major) of the last call -- the matrix SparseGP._update_gradients
  * hands to a foreign kernel's update_gradients_full / gradients_X (core/sparse_gp.py:108-118).  It is never resident as a
  * whole (3.3 GB at config 5): the caller walks it in row blocks. */
