@@ -64,19 +64,30 @@ void mi355gp_set_error(const char* fmt, ...);
     } while (0)
 
 // Scoped device allocation: every early return (HIP_CHECK) releases what was acquired.  Movable, so that the owners of
-// per-part buffers can keep them in a std::vector.
-struct DevBuf {
-    double* p = nullptr;
-    DevBuf() = default;
-    DevBuf(DevBuf&& o) noexcept : p(o.p) { o.p = nullptr; }
-    DevBuf(const DevBuf&) = delete;
-    DevBuf& operator=(const DevBuf&) = delete;
-    ~DevBuf() {
+// per-part buffers can keep them in a std::vector; move-assignable, so that an owner can be replaced by a fresh one (the
+// buffer held before is released).  DevBuf is the array of doubles; the grid mode also keeps index and pointer tables.
+template <typename T>
+struct DevArr {
+    T* p = nullptr;
+    DevArr() = default;
+    DevArr(DevArr&& o) noexcept : p(o.p) { o.p = nullptr; }
+    DevArr(const DevArr&) = delete;
+    DevArr& operator=(const DevArr&) = delete;
+    DevArr& operator=(DevArr&& o) noexcept {
+        if (this != &o) {
+            if (p) (void)hipFree(p);
+            p = o.p;
+            o.p = nullptr;
+        }
+        return *this;
+    }
+    ~DevArr() {
         if (p) (void)hipFree(p);
     }
-    hipError_t alloc(size_t doubles) { return hipMalloc(&p, sizeof(double) * (doubles ? doubles : 1)); }
-    operator double*() const { return p; }
+    hipError_t alloc(size_t count) { return hipMalloc(&p, sizeof(T) * (count ? count : 1)); }
+    operator T*() const { return p; }
 };
+typedef DevArr<double> DevBuf;
 
 static inline int64_t round_up(int64_t n, int64_t m) { return (n + m - 1) / m * m; }
 

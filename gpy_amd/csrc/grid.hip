@@ -17,127 +17,19 @@
 //
 // Two transports behind one driver: RCCL (one rank per process, one GPU each; librccl.so is dlopen'ed so the
 // single-GPU library has no RCCL dependency) and LOOPBACK (all Pr*Pc logical ranks inside one process on one
-// device, broadcasts are device copies) used to test the algorithm on a 1-GPU box.
-#include <dlfcn.h>
-
+// device, broadcasts are device copies) used to test the algorithm on a 1-GPU box.  Both live in grid_comm.hip; this file
+// holds the tile kernels, the context's lifecycle and the evaluation, built from named phases (grid_run at the end of them).
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
-#include <functional>
-#include <string>
 #include <vector>
 
-#include "../../include/mi355gp.h"
 #include "../../include/mi355gp_debug.h"
 #include "gemm_tile.h"
-#include "internal.h"
+#include "grid_ctx.h"
 #include "parts.h"
 
 #define LOG_2_PI 1.8378770664093454836
-
-// ---------------------------------------------------------------------------------------------------
-// RCCL: types, enums and prototypes come from the installed <rccl/rccl.h>; the library itself is dlopen'ed (so the
-// single-GPU library has no link-time RCCL dependency) and every entry point is bound through decltype(&ncclXxx): a
-// signature change in RCCL is a compile error here, not silent ABI drift.
-#include <rccl/rccl.h>
-static_assert(sizeof(ncclUniqueId) == 128, "mi355gp_grid_unique_id hands out 128-byte ids");
-// the second provider of the same entry points (ipc_comm.hip): ranks = processes sharing ONE GPU, MI355GP_TRANSPORT=ipc
-ncclResult_t ipcGetUniqueId(ncclUniqueId* id);
-ncclResult_t ipcCommInitRank(ncclComm_t* out, int nranks, ncclUniqueId id, int rank);
-ncclResult_t ipcCommSplit(ncclComm_t parent, int color, int key, ncclComm_t* out, ncclConfig_t* cfg);
-ncclResult_t ipcCommDestroy(ncclComm_t comm);
-ncclResult_t ipcBroadcast(const void* send, void* recv, size_t count, ncclDataType_t type, int root, ncclComm_t comm, hipStream_t st);
-ncclResult_t ipcAllReduce(const void* send, void* recv, size_t count, ncclDataType_t type, ncclRedOp_t op, ncclComm_t comm, hipStream_t st);
-ncclResult_t ipcGroupStart();
-ncclResult_t ipcGroupEnd();
-const char* ipcGetErrorString(ncclResult_t r);
-
-struct Rccl {
-    void* h = nullptr;
-    bool ipc = false;
-    decltype(&ncclGetUniqueId) GetUniqueId = nullptr;
-    decltype(&ncclCommInitRank) CommInitRank = nullptr;
-    decltype(&ncclCommSplit) CommSplit = nullptr;
-    decltype(&ncclCommDestroy) CommDestroy = nullptr;
-    decltype(&ncclBroadcast) Broadcast = nullptr;
-    decltype(&ncclAllReduce) AllReduce = nullptr;
-    decltype(&ncclGroupStart) GroupStart = nullptr;
-    decltype(&ncclGroupEnd) GroupEnd = nullptr;
-    decltype(&ncclGetErrorString) GetErrorString = nullptr;
-    bool load() {
-        if (h) return true;
-        {
-            const char* t = PRODUCT_ENV("TRANSPORT");
-            if (t && strcmp(t, "ipc") == 0) {                // multi-process transport over hipIpc + shared memory (ipc_comm.hip)
-                GetUniqueId = ipcGetUniqueId;
-                CommInitRank = ipcCommInitRank;
-                CommSplit = ipcCommSplit;
-                CommDestroy = ipcCommDestroy;
-                Broadcast = ipcBroadcast;
-                AllReduce = ipcAllReduce;
-                GroupStart = ipcGroupStart;
-                GroupEnd = ipcGroupEnd;
-                GetErrorString = ipcGetErrorString;
-                ipc = true;
-                h = (void*)this;
-                return true;
-            }
-        }
-        const char* names[] = {"librccl.so.1", "librccl.so", "/opt/rocm/lib/librccl.so.1"};
-        for (const char* n : names) {
-            h = dlopen(n, RTLD_NOW | RTLD_GLOBAL);
-            if (h) break;
-        }
-        if (!h) {
-            mi355gp_set_error("cannot dlopen librccl.so: %s", dlerror());
-            return false;
-        }
-#define SYM(field, name)                                                   \
-    *(void**)(&field) = dlsym(h, name);                                    \
-    if (!field) {                                                          \
-        mi355gp_set_error("librccl.so lacks %s", name);                    \
-        return false;                                                      \
-    }
-        SYM(GetUniqueId, "ncclGetUniqueId");
-        SYM(CommInitRank, "ncclCommInitRank");
-        SYM(CommSplit, "ncclCommSplit");
-        SYM(CommDestroy, "ncclCommDestroy");
-        SYM(Broadcast, "ncclBroadcast");
-        SYM(AllReduce, "ncclAllReduce");
-        SYM(GroupStart, "ncclGroupStart");
-        SYM(GroupEnd, "ncclGroupEnd");
-        SYM(GetErrorString, "ncclGetErrorString");
-#undef SYM
-        return true;
-    }
-};
-static Rccl g_rccl;
-#define NCCL_CHECK(expr)                                                                                  \
-    do {                                                                                                  \
-        ncclResult_t _r = (expr);                                                                         \
-        if (_r != ncclSuccess) {                                                                          \
-            mi355gp_set_error("%s failed: %s (%s:%d)", #expr, g_rccl.GetErrorString(_r), __FILE__, __LINE__); \
-            return -(2000 + (int)_r);                                                                       \
-        }                                                                                                 \
-    } while (0)
-
-// plain world communicator for the row-sharded sparse path (sparse.hip): one all-reduce per streaming pass
-int rccl_comm_create(int rank, int world, const void* id128, void** comm) {
-    if (!g_rccl.load()) return -20;
-    ncclUniqueId id;
-    memcpy(&id, id128, sizeof(id));
-    ncclComm_t c = nullptr;
-    NCCL_CHECK(g_rccl.CommInitRank(&c, world, id, rank));
-    *comm = c;
-    return 0;
-}
-int rccl_allreduce_sum(void* comm, double* buf, size_t count, hipStream_t st) {
-    NCCL_CHECK(g_rccl.AllReduce(buf, buf, count, ncclFloat64, ncclSum, (ncclComm_t)comm, st));
-    return 0;
-}
-void rccl_comm_destroy(void* comm) {
-    if (comm && g_rccl.h) g_rccl.CommDestroy((ncclComm_t)comm);
-}
 
 // ---------------------------------------------------------------------------------------------------
 // device kernels specific to the distributed layout
@@ -404,9 +296,16 @@ __global__ void k_grid_scatter(const double* __restrict__ loc, long cnt, const l
     if (g < n) gvec[g * stride + d] = loc[l];
 }
 
-__global__ void k_grid_axpy(double* __restrict__ dst, const double* __restrict__ src, long cnt) {
-    const long l = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (l < cnt) dst[l] += src[l];
+// nt tiles of nb x nb, contiguous at src, into the row block dst (row stride ldd): tile t at columns t * nb ..  (one launch
+// instead of one 2-D copy per tile: 7,000 of them per evaluation at N = 32768 on a 2 x 4 grid)
+__global__ __launch_bounds__(256) void k_tiles_to_rowblock(double* __restrict__ dst, long ldd, const double* __restrict__ src, int nb) {
+    const double* s = src + (long)blockIdx.y * nb * nb;
+    double* d = dst + (long)blockIdx.y * nb;
+    const int half = nb >> 1;
+    for (long e = (long)blockIdx.x * blockDim.x + threadIdx.x; e < (long)nb * half; e += (long)gridDim.x * blockDim.x) {
+        const long i = e / half, j = 2 * (e - i * half);
+        *reinterpret_cast<d2*>(d + i * ldd + j) = *reinterpret_cast<const d2*>(s + i * nb + j);
+    }
 }
 
 // after a tile factorisation: scal[0] += sum(logsum[0..q)) ; info_g = first failure in global numbering
@@ -425,91 +324,6 @@ __global__ void k_grid_tile_stats(const double* __restrict__ logsum, int q, cons
 }
 
 // ---------------------------------------------------------------------------------------------------
-struct GridRank {
-    int rank = 0, pr = 0, pc = 0;
-    int TLr = 0, TLc = 0;            // local tile rows / cols actually owned
-    long LR = 0, LC = 0;             // allocated local rows / cols (uniform over ranks)
-    long nvr = 0, nvc = 0;           // local rows / cols whose global index is < n (a prefix of the local order)
-    double *A = nullptr, *X = nullptr, *W = nullptr;
-    // Panel stores (alloc_panel_stores):
-    //   RPs: L_ik for the local row tiles with I > k          CPs: L_jk for the local column tiles with J > k
-    //   XRs: X_kj for the local column tiles with J <= k      XRrs: X_ki for the local row tiles with I <= k
-    // The L panels of a step are read only by the updates of its own group (near, part 1 on sc; bulk on st), and the
-    // critical path of group g+2 starts after sc has waited for bulk(g): they live in a RING of 2 G full-height slots (panel
-    // k in slot k % 2G), 2 G (N/Pr + N/Pc) nb doubles instead of ~N^2/2 (1/Pr + 1/Pc).  The X panels are also read by the
-    // deferred W = X^T X on the low-priority stream, which may trail by any number of steps (all of them with GW = 0): every
-    // step keeps its own, packed back to back.
-    // hRP[k] .. are the panels' VIRTUAL bases (local tile l of panel k at base + l * nb * nb; only the tiles the panel holds
-    // are ever addressed), dRP .. the same tables in device memory for k_grid_gemm_multi.
-    double *RPs = nullptr, *CPs = nullptr, *XRs = nullptr, *XRrs = nullptr;
-    long ring_slots = 0;             // L-panel ring slots the stores were sized for (2 G at allocation time)
-    std::vector<double*> hRP, hCP, hXR, hXRr;
-    const double **dRP = nullptr, **dCP = nullptr, **dXR = nullptr, **dXRr = nullptr;
-    double* cpart = nullptr;         // column-reduction partials [row chunk][LC]
-    double *Dt = nullptr, *Dv = nullptr, *Ds = nullptr;
-    double* bstage = nullptr;        // one-rank-per-process transports: packed tiles of a strided panel broadcast (grid_bcast_tile_runs)
-    double *XtR = nullptr, *XtC = nullptr, *XsR = nullptr, *XsC = nullptr;   // scaled dimension-major / raw row-major
-    long *gR = nullptr, *gC = nullptr;                                       // global index of every local row / col
-    int *dl_r = nullptr, *dl_c = nullptr, *dg = nullptr;
-    int ndiag = 0;
-    double *vloc = nullptr, *gvec = nullptr, *gvec2 = nullptr, *alpha = nullptr, *ybuf = nullptr, *Rg = nullptr;
-    double *scal = nullptr, *gradPart = nullptr, *gradOut = nullptr, *invls = nullptr, *noise = nullptr;
-    int* info_g = nullptr;
-    // Log of the collectives this rank took part in during the current evaluation, per communicator (0 world, 1 process row,
-    // 2 process column): count and an FNV-1a hash over (operation, root, doubles).  RCCL matches collectives by ORDER: two members
-    // of a communicator that enqueue different sequences dead-lock or, worse, exchange the wrong panels.  check_seq compares
-    // the logs of all members after every evaluation (mi355gp_grid_coll_log reads them).
-    uint64_t coll_hash[3] = {0, 0, 0};
-    long coll_count[3] = {0, 0, 0};
-    double* seqbuf = nullptr;        // 3 * max(world, Pr, Pc) doubles: the exchange buffer of the sequence check
-    int seqbuf_members = 0;          // members it was sized for
-    FactorWs ws;
-    hipStream_t st = nullptr;        // bulk updates and everything outside the factorisation loop
-    hipStream_t sc = nullptr;        // the critical path of a step: diagonal tile, panel solves, all panel broadcasts
-    hipStream_t sw = nullptr;        // W = X^T X updates
-};
-
-// loopback transport: destinations of one broadcast / the broadcasts of one group (kernel arguments of k_bcast_copy / k_bcast_batch)
-#define BCAST_MAX_DST 8
-#define BCAST_BATCH 24
-struct BcastDst { double* p[BCAST_MAX_DST]; };
-struct BcastItem { const double* src; double* dst[BCAST_MAX_DST]; int nd; };
-struct BcastBatch { BcastItem it[BCAST_BATCH]; };
-
-struct mi355gp_grid {
-    int device = 0, world = 1, Pr = 1, Pc = 1, my_rank = 0;
-    long nb = 512;
-    bool loopback = true;
-    std::vector<GridRank> ranks;     // logical ranks hosted by this process (loopback: all, RCCL: one)
-    ncclComm_t comm_world = nullptr, comm_row = nullptr, comm_col = nullptr;
-    hipStream_t st = nullptr;        // loopback: shared by all logical ranks
-    hipStream_t sc = nullptr;        // second stream (high priority): panel factorisation + broadcasts, one step ahead
-    hipStream_t sw = nullptr;        // third stream (low priority): the W = X^T X updates, which nothing waits for until the end
-    hipEvent_t ev_w = nullptr;
-    std::vector<hipEvent_t> ev_cr, ev_p1;   // [k]: panels of step k are in place / the part-1 updates of step k are done
-    int lookahead = 1;               // MI355GP_GRID_LOOKAHEAD=0: everything in order on one stream
-    int check_seq = 0;               // MI355GP_GRID_CHECK_SEQ=1: compare the collective logs of all ranks after every evaluation
-    int G = 1;                       // MI355GP_GRID_G: steps per group of the two-level blocked factorisation (K = G * nb updates)
-    int GW = 4;                      // MI355GP_GRID_GW: steps per W = X^T X update; 0 = one deep-K pass after the last step
-    // diagnostics build, MI355GP_GRID_DBG_CRIT (WRONG RESULTS; tools/grid_crit_probe.py): 1 = every update (near / part1 / bulk /
-    // W) skipped: the critical path crit(k) of every step alone; 2 = ... and its broadcasts skipped; 3 = ... and only phase (a),
-    // the factorisation + inverse of the diagonal tile, left
-    int dbg_crit = 0;
-    long n = 0, npad = 0, T = 0;
-    int D = 0, Dy = 0;
-    hipEvent_t ev[6] = {};
-    bool have_result = false;
-    // Pr = Pc = 1 over the loopback transport degenerates to the dedicated single-GPU pipeline ("with Pr = Pc = 1
-    // degenerate to the single-GPU path"): deep-K trtri / lauum tiles instead of three K = nb read-modify-write updates per
-    // step (N=32768: 527 vs 623 ms).  MI355GP_GRID_FORCE_GENERIC=1 keeps the generic one-pass code (tests).
-    mi355gp_ctx* single = nullptr;
-    // loopback transport: the broadcasts of an open group, launched together at its end
-    bool batching = false;
-    size_t batch_count = 0;
-    hipStream_t batch_stream = nullptr;
-    std::vector<BcastItem> batch;
-};
-
 // process defaults of the schedule options: environment, else built-in
 static void grid_default_option(mi355gp_grid* g, int o) {
     if (o == MI355GP_GRID_OPT_LOOKAHEAD) {
@@ -527,266 +341,26 @@ static void grid_default_option(mi355gp_grid* g, int o) {
     }
 }
 
-static void coll_log(GridRank& r, int comm, int op, int root, size_t count) {
-    uint64_t h = r.coll_hash[comm];
-    const uint64_t words[3] = {(uint64_t)op, (uint64_t)(unsigned)root, (uint64_t)count};
-    for (uint64_t w : words)
-        for (int b = 0; b < 8; ++b) {
-            h ^= (w >> (8 * b)) & 0xffu;
-            h *= 1099511628211ull;
-        }
-    r.coll_hash[comm] = h;
-    r.coll_count[comm] += 1;
-}
-
 static int cnt_le(long k, int p, int P) { return (k >= p) ? (int)((k - p) / P + 1) : 0; }   // tiles t <= k with t % P == p
 static int cnt_lt(long k, int p, int P) { return (k > 0) ? cnt_le(k - 1, p, P) : 0; }
 
-static void free_rank(GridRank& r) {
-    void* ptrs[] = {r.A, r.X, r.W, r.RPs, r.CPs, r.XRs, r.XRrs, (void*)r.dRP, (void*)r.dCP, (void*)r.dXR, (void*)r.dXRr, r.cpart, r.Dt, r.Dv, r.Ds, r.bstage, r.XtR, r.XtC, r.XsR, r.XsC, r.gR, r.gC,
-                    r.dl_r, r.dl_c, r.dg, r.vloc, r.gvec, r.gvec2, r.alpha, r.ybuf, r.Rg, r.scal, r.gradPart,
-                    r.gradOut, r.invls, r.noise, r.info_g, r.seqbuf};
-    for (void* p : ptrs)
-        if (p) (void)hipFree(p);
+// the identity of a rank: what a fresh GridRank keeps of the one it replaces
+static GridRank make_rank(int rank, int Pc, hipStream_t st, hipStream_t sc, hipStream_t sw) {
+    GridRank r;
+    r.rank = rank;
+    r.pr = rank / Pc;
+    r.pc = rank % Pc;
+    r.st = st;
+    r.sc = sc;
+    r.sw = sw;
+    return r;
+}
+// releases everything the rank holds on the device
+static void free_rank(GridRank& r, int Pc) {
     factor_ws_free(&r.ws);
-    r = GridRank();
+    r = make_rank(r.rank, Pc, r.st, r.sc, r.sw);
 }
 
-// ---- transports ------------------------------------------------------------------------------------------
-// Broadcast inside one process row (group = GROUP_ROW, index = pr) or column (GROUP_COL, index = pc).
-// `buf(rank, is_root)` returns the send pointer for the root and the receive pointer for everyone (the root's
-// receive pointer may differ from its send pointer: out-of-place on the root, like ncclBroadcast).
-enum { GROUP_ROW = 0, GROUP_COL = 1 };
-// loopback transport: a broadcast is a device copy from the root's buffer into every other member's
-__global__ __launch_bounds__(256) void k_bcast_copy(const double* __restrict__ src, BcastDst dst, int nd, long count) {
-    const long n2 = count >> 1;                               // tiles and panels are 16-byte aligned and even-sized
-    const d2* s2 = reinterpret_cast<const d2*>(src);
-    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n2; i += (long)gridDim.x * blockDim.x) {
-        const d2 v = s2[i];
-        for (int q = 0; q < nd; ++q) reinterpret_cast<d2*>(dst.p[q])[i] = v;
-    }
-    if ((count & 1) && blockIdx.x == 0 && threadIdx.x == 0)
-        for (int q = 0; q < nd; ++q) dst.p[q][count - 1] = src[count - 1];
-}
-// a GROUP of loopback broadcasts (grid_group_start .. grid_group_end: the per-tile broadcasts of crit(k), up to k + 1 of them
-// with different roots) as ONE launch per 24 of them instead of one per broadcast: blockIdx.y picks the broadcast
-__global__ __launch_bounds__(256) void k_bcast_batch(BcastBatch b, long count) {
-    const BcastItem& it = b.it[blockIdx.y];
-    const long n2 = count >> 1;
-    const d2* s2 = reinterpret_cast<const d2*>(it.src);
-    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n2; i += (long)gridDim.x * blockDim.x) {
-        const d2 v = s2[i];
-        for (int q = 0; q < it.nd; ++q) reinterpret_cast<d2*>(it.dst[q])[i] = v;
-    }
-    if ((count & 1) && blockIdx.x == 0 && threadIdx.x == 0)
-        for (int q = 0; q < it.nd; ++q) it.dst[q][count - 1] = it.src[count - 1];
-}
-// nt tiles of nb x nb, contiguous at src, into the row block dst (row stride ldd): tile t at columns t * nb ..  (one launch
-// instead of one 2-D copy per tile: 7,000 of them per evaluation at N = 32768 on a 2 x 4 grid)
-__global__ __launch_bounds__(256) void k_tiles_to_rowblock(double* __restrict__ dst, long ldd, const double* __restrict__ src, int nb) {
-    const double* s = src + (long)blockIdx.y * nb * nb;
-    double* d = dst + (long)blockIdx.y * nb;
-    const int half = nb >> 1;
-    for (long e = (long)blockIdx.x * blockDim.x + threadIdx.x; e < (long)nb * half; e += (long)gridDim.x * blockDim.x) {
-        const long i = e / half, j = 2 * (e - i * half);
-        *reinterpret_cast<d2*>(d + i * ldd + j) = *reinterpret_cast<const d2*>(s + i * nb + j);
-    }
-}
-static void launch_bcast_copy(hipStream_t st, const double* src, const BcastDst& dst, int nd, size_t count) {
-    long blocks = (long)((count / 2 + 255) / 256);
-    if (blocks > 2048) blocks = 2048;
-    if (blocks < 1) blocks = 1;
-    hipLaunchKernelGGL(k_bcast_copy, dim3((unsigned)blocks), dim3(256), 0, st, src, dst, nd, (long)count);
-}
-typedef std::function<double*(GridRank&, bool)> BufFn;
-
-// loopback transport: launch the broadcasts collected since grid_group_start
-static int grid_flush_bcasts(mi355gp_grid* g) {
-    const size_t n = g->batch.size();
-    for (size_t i0 = 0; i0 < n; i0 += BCAST_BATCH) {
-        BcastBatch b;
-        const int m = (int)((n - i0 < BCAST_BATCH) ? n - i0 : BCAST_BATCH);
-        for (int q = 0; q < m; ++q) b.it[q] = g->batch[i0 + (size_t)q];
-        long blocks = (long)((g->batch_count / 2 + 255) / 256);
-        if (blocks > 256) blocks = 256;
-        if (blocks < 1) blocks = 1;
-        hipLaunchKernelGGL(k_bcast_batch, dim3((unsigned)blocks, (unsigned)m), dim3(256), 0, g->batch_stream, b, (long)g->batch_count);
-    }
-    g->batch.clear();
-    g->batch_count = 0;
-    HIP_CHECK(hipGetLastError());
-    return 0;
-}
-static int grid_bcast(mi355gp_grid* g, int group, int index, int root_coord, size_t count, const BufFn& buf) {
-    if (count == 0) return 0;
-    hipStream_t lst = g->lookahead ? g->sc : g->st;            // every panel broadcast travels on the communication stream
-    if (g->loopback) {
-        GridRank* root = nullptr;
-        for (GridRank& r : g->ranks) {
-            const bool in = (group == GROUP_ROW) ? (r.pr == index) : (r.pc == index);
-            const int coord = (group == GROUP_ROW) ? r.pc : r.pr;
-            if (in && coord == root_coord) root = &r;
-        }
-        const double* src = buf(*root, true);
-        if (g->batching && (g->batch_count != count || g->batch_stream != lst)) {
-            if (int rc = grid_flush_bcasts(g)) return rc;      // (a group of equal-sized tiles in practice: one flush at its end)
-        }
-        BcastItem item;                                       // every member's copy in ONE launch (one blit per member cost the
-        item.src = src;                                       // loopback run ~13,000 copy launches per evaluation at N = 32768)
-        item.nd = 0;
-        auto emit = [&]() {
-            if (item.nd == 0) return;
-            if (g->batching) {
-                g->batch_count = count;
-                g->batch_stream = lst;
-                g->batch.push_back(item);
-            } else {
-                BcastDst dsts;
-                for (int q = 0; q < item.nd; ++q) dsts.p[q] = item.dst[q];
-                launch_bcast_copy(lst, src, dsts, item.nd, count);
-            }
-            item.nd = 0;
-        };
-        for (GridRank& r : g->ranks) {
-            const bool in = (group == GROUP_ROW) ? (r.pr == index) : (r.pc == index);
-            if (!in) continue;
-            coll_log(r, group == GROUP_ROW ? 1 : 2, 1, root_coord, count);
-            double* dst = buf(r, false);
-            if (dst == src) continue;
-            if (item.nd == BCAST_MAX_DST) emit();
-            item.dst[item.nd++] = dst;
-        }
-        emit();
-        return 0;
-    }
-    GridRank& r = g->ranks[0];
-    const bool in = (group == GROUP_ROW) ? (r.pr == index) : (r.pc == index);
-    if (!in) return 0;
-    const int coord = (group == GROUP_ROW) ? r.pc : r.pr;
-    const bool is_root = coord == root_coord;
-    const double* send = is_root ? buf(r, true) : buf(r, false);
-    coll_log(r, group == GROUP_ROW ? 1 : 2, 1, root_coord, count);
-    NCCL_CHECK(g_rccl.Broadcast(send, buf(r, false), count, ncclFloat64, root_coord,
-                                group == GROUP_ROW ? g->comm_row : g->comm_col, lst));
-    return 0;
-}
-static int grid_group_start(mi355gp_grid* g) {
-    if (!g->loopback) NCCL_CHECK(g_rccl.GroupStart());
-    else g->batching = true;
-    return 0;
-}
-static int grid_group_end(mi355gp_grid* g) {
-    if (!g->loopback) {
-        NCCL_CHECK(g_rccl.GroupEnd());
-        return 0;
-    }
-    g->batching = false;
-    return grid_flush_bcasts(g);
-}
-// ---- panel tiles that change hands between process rows / columns: ONE broadcast per (communicator, root) ----------------------
-// Phases (e) and (i) of crit(k) move single tiles whose source and destination are both determined by the tile's GLOBAL index:
-// tile j of a column panel lives on process row j % Pr (local tile j / Pr of the row panel there) and is wanted by process
-// column j % Pc (local tile j / Pc of its column panel).  For one communicator and one root the tiles form an arithmetic
-// progression in j with step lcm(Pr, Pc): a run of `n` tiles at local index s0 + m * ss on the root and d0 + m * ds on every
-// member.  Rounds 2-5 sent every tile as its own broadcast inside a group (up to T - k - 1 of them per step: ~4,000 RCCL calls
-// per evaluation at N = 32768); now a run travels as ONE broadcast of n tiles: packed into the staging buffer by one small kernel
-// where the root's tiles are not contiguous (ss != 1), received in place where the members' are (ds == 1) and unpacked by one
-// kernel where they are not.  On a Pr x Pc grid with Pr | Pc (2 x 4) a column panel needs no unpack and an X panel no pack.
-// The loopback transport moves the same tiles with its batched copy kernel and LOGS the merged broadcast, so that the collective
-// sequences of the two transports stay comparable (tests/test_gpu_multiproc.py).
-struct TileRun { int group, index, root, n; long s0, ss, d0, ds; };
-__global__ __launch_bounds__(256) void k_tiles_restride(double* __restrict__ dst, long dstride, const double* __restrict__ src,
-                                                        long sstride, long tile) {
-    const d2* s2 = reinterpret_cast<const d2*>(src + (long)blockIdx.y * sstride);
-    d2* q2 = reinterpret_cast<d2*>(dst + (long)blockIdx.y * dstride);
-    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < (tile >> 1); i += (long)gridDim.x * blockDim.x) q2[i] = s2[i];
-}
-typedef std::function<double*(GridRank&)> BaseFn;
-static int grid_bcast_tile_runs(mi355gp_grid* g, const std::vector<TileRun>& runs, size_t tile, const BaseFn& srcbase,
-                                const BaseFn& dstbase) {
-    hipStream_t lst = g->lookahead ? g->sc : g->st;
-    if (g->loopback) {
-        if (int rc = grid_group_start(g)) return rc;
-        for (const TileRun& tr : runs) {
-            if (tr.n <= 0) continue;
-            for (GridRank& r : g->ranks) {
-                const bool in = (tr.group == GROUP_ROW) ? (r.pr == tr.index) : (r.pc == tr.index);
-                if (in) coll_log(r, tr.group == GROUP_ROW ? 1 : 2, 1, tr.root, (size_t)tr.n * tile);
-            }
-            for (int m = 0; m < tr.n; ++m) {
-                if (g->batch_count != tile || g->batch_stream != lst)
-                    if (int rc = grid_flush_bcasts(g)) return rc;
-                BcastItem item;
-                item.nd = 0;
-                item.src = nullptr;
-                for (GridRank& r : g->ranks) {
-                    const bool in = (tr.group == GROUP_ROW) ? (r.pr == tr.index) : (r.pc == tr.index);
-                    const int coord = (tr.group == GROUP_ROW) ? r.pc : r.pr;
-                    if (in && coord == tr.root) item.src = srcbase(r) + (tr.s0 + m * tr.ss) * (long)tile;
-                }
-                auto emit = [&]() {
-                    if (item.nd == 0) return;
-                    g->batch_count = tile;
-                    g->batch_stream = lst;
-                    g->batch.push_back(item);
-                    item.nd = 0;
-                };
-                for (GridRank& r : g->ranks) {
-                    const bool in = (tr.group == GROUP_ROW) ? (r.pr == tr.index) : (r.pc == tr.index);
-                    if (!in) continue;
-                    if (item.nd == BCAST_MAX_DST) emit();
-                    item.dst[item.nd++] = dstbase(r) + (tr.d0 + m * tr.ds) * (long)tile;
-                }
-                emit();
-            }
-        }
-        return grid_group_end(g);
-    }
-    GridRank& r = g->ranks[0];
-    struct Mine { const TileRun* tr; bool is_root; const double* send; double* recv; double* stage; };
-    std::vector<Mine> mine;
-    long used = 0;
-    for (const TileRun& tr : runs) {
-        if (tr.n <= 0) continue;
-        const bool in = (tr.group == GROUP_ROW) ? (r.pr == tr.index) : (r.pc == tr.index);
-        if (!in) continue;
-        Mine m;
-        m.tr = &tr;
-        m.is_root = ((tr.group == GROUP_ROW) ? r.pc : r.pr) == tr.root;
-        const bool need_stage = (m.is_root && tr.ss != 1 && tr.n > 1) || (tr.ds != 1 && tr.n > 1);
-        m.stage = need_stage ? r.bstage + used * (long)tile : nullptr;
-        if (need_stage) used += tr.n;
-        double* dst0 = dstbase(r) + tr.d0 * (long)tile;
-        m.recv = (tr.ds != 1 && tr.n > 1) ? m.stage : dst0;
-        m.send = m.recv;
-        if (m.is_root) {
-            const double* src0 = srcbase(r) + tr.s0 * (long)tile;
-            if (tr.ss != 1 && tr.n > 1) {                    // pack the root's tiles
-                hipLaunchKernelGGL(k_tiles_restride, dim3(64, (unsigned)tr.n), dim3(256), 0, lst, m.stage, (long)tile, src0,
-                                   tr.ss * (long)tile, (long)tile);
-                m.send = m.stage;
-            } else {
-                m.send = src0;
-            }
-        }
-        mine.push_back(m);
-    }
-    if (mine.empty()) return 0;
-    HIP_CHECK(hipGetLastError());
-    if (mine.size() > 1) NCCL_CHECK(g_rccl.GroupStart());
-    for (const Mine& m : mine) {
-        coll_log(r, m.tr->group == GROUP_ROW ? 1 : 2, 1, m.tr->root, (size_t)m.tr->n * tile);
-        NCCL_CHECK(g_rccl.Broadcast(m.send, m.recv, (size_t)m.tr->n * tile, ncclFloat64, m.tr->root,
-                                    m.tr->group == GROUP_ROW ? g->comm_row : g->comm_col, lst));
-    }
-    if (mine.size() > 1) NCCL_CHECK(g_rccl.GroupEnd());
-    for (const Mine& m : mine)
-        if (m.tr->ds != 1 && m.tr->n > 1)                    // unpack into the members' panel
-            hipLaunchKernelGGL(k_tiles_restride, dim3(64, (unsigned)m.tr->n), dim3(256), 0, lst,
-                               dstbase(r) + m.tr->d0 * (long)tile, m.tr->ds * (long)tile, (const double*)m.stage, (long)tile, (long)tile);
-    HIP_CHECK(hipGetLastError());
-    return 0;
-}
 // the tiles t in (lo, hi] ... [lo, hi) with t % Pa == a and t % Pb == b, as first / step / count (step = lcm(Pa, Pb))
 static void tile_progression(long lo, long hi, int a, int Pa, int b, int Pb, long* first, long* step, int* count) {
     long L = Pa;
@@ -798,140 +372,14 @@ static void tile_progression(long lo, long hi, int a, int Pa, int b, int Pb, lon
         if (t % Pa == a && t % Pb == b) { *first = t; break; }
     if (*first >= 0) *count = (int)((hi - 1 - *first) / L + 1);
 }
-// ---- self-test of the bound transport (RCCL, or the hipIpc stand-in under MI355GP_TRANSPORT=ipc) --------------------------------
-// Exactly the communicator set-up and the call patterns of the per-rank grid code, without the numerics: world communicator,
-// row / column communicators by CommSplit (colour = own grid row / column, key = the other coordinate), then
-//   (1) a world broadcast, (2) inside ONE group: `rounds` tile broadcasts on the row communicator with rotating roots (the
-//   pattern of crit(k) step (i)), (3) the same on the column communicator (steps (d) / (f)), (4) a world all-reduce in place,
-//   (5) a row-communicator all-reduce -- all on one non-default stream, every payload checked element by element.
-// out4 = [mismatching doubles, checksum, rank inside the row communicator, rank inside the column communicator].
-// This is the first thing to run on a node with more than one GPU (tools/rccl_first_light.sh): it separates "RCCL does not do
-// what grid.hip assumes" (split numbering, several roots in one group, out-of-place broadcast on the root) from everything else.
-extern "C" int mi355gp_dbg_comm_selftest(int device, const void* id128, int rank, int world, int Pr, int Pc, int64_t count,
-                                         int rounds, double* out4) {
-    if (!id128 || !out4 || world != Pr * Pc || count <= 0 || rounds < 1 || rank < 0 || rank >= world) {
-        mi355gp_set_error("mi355gp_dbg_comm_selftest: invalid argument");
-        return -1;
-    }
-    if (!g_rccl.load()) return -2;
-    HIP_CHECK(hipSetDevice(device));
-    ncclUniqueId id;
-    memcpy(&id, id128, sizeof(id));
-    ncclComm_t cw = nullptr, crow = nullptr, ccol = nullptr;
-    NCCL_CHECK(g_rccl.CommInitRank(&cw, world, id, rank));
-    const int pr = rank / Pc, pc = rank % Pc;
-    NCCL_CHECK(g_rccl.CommSplit(cw, pr, pc, &crow, nullptr));
-    NCCL_CHECK(g_rccl.CommSplit(cw, pc, pr, &ccol, nullptr));
-    hipStream_t st;
-    HIP_CHECK(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
-    const size_t n = (size_t)count, total = n * (size_t)(rounds + 1);
-    double *dsend = nullptr, *drecv = nullptr;
-    HIP_CHECK(hipMalloc(&dsend, sizeof(double) * total));
-    HIP_CHECK(hipMalloc(&drecv, sizeof(double) * total));
-    std::vector<double> hs(total), hr(total);
-    double bad = 0.0, sum = 0.0;
-    auto val = [](double tag, size_t i) { return tag + 1e-3 * (double)(i % 1000); };
-    auto fill = [&](int slot, double tag) {
-        for (size_t i = 0; i < n; ++i) hs[(size_t)slot * n + i] = val(tag, i);
-    };
-    auto upload = [&]() -> int {
-        HIP_CHECK(hipMemcpyAsync(dsend, hs.data(), sizeof(double) * total, hipMemcpyHostToDevice, st));
-        HIP_CHECK(hipMemsetAsync(drecv, 0, sizeof(double) * total, st));
-        return 0;
-    };
-    auto download = [&]() -> int {
-        HIP_CHECK(hipMemcpyAsync(hr.data(), drecv, sizeof(double) * total, hipMemcpyDeviceToHost, st));
-        HIP_CHECK(hipStreamSynchronize(st));
-        return 0;
-    };
-    auto expect = [&](int slot, double tag) {
-        for (size_t i = 0; i < n; ++i) {
-            const double got = hr[(size_t)slot * n + i];
-            if (got != val(tag, i)) bad += 1.0;
-            sum += got;
-        }
-    };
-    // (1) world broadcast from the last rank, out of place everywhere (the root included, as grid_bcast does it)
-    fill(0, 100.0 + rank);
-    if (int rc = upload()) return rc;
-    NCCL_CHECK(g_rccl.Broadcast(dsend, drecv, n, ncclFloat64, world - 1, cw, st));
-    if (int rc = download()) return rc;
-    expect(0, 100.0 + (world - 1));
-    // (2) / (3): one GROUP of `rounds` broadcasts with rotating roots on the row, then on the column communicator
-    for (int which = 0; which < 2; ++which) {
-        const int size = which == 0 ? Pc : Pr, me = which == 0 ? pc : pr, line = which == 0 ? pr : pc;
-        const ncclComm_t comm = which == 0 ? crow : ccol;
-        for (int q = 0; q < rounds; ++q) fill(q, 1000.0 * (which + 1) + 10.0 * line + me + 0.25 * q);
-        if (int rc = upload()) return rc;
-        NCCL_CHECK(g_rccl.GroupStart());
-        for (int q = 0; q < rounds; ++q)
-            NCCL_CHECK(g_rccl.Broadcast(dsend + (size_t)q * n, drecv + (size_t)q * n, n, ncclFloat64, q % size, comm, st));
-        NCCL_CHECK(g_rccl.GroupEnd());
-        if (int rc = download()) return rc;
-        for (int q = 0; q < rounds; ++q) expect(q, 1000.0 * (which + 1) + 10.0 * line + (q % size) + 0.25 * q);
-    }
-    // (4) world all-reduce in place: sum over ranks of (rank + pattern)
-    fill(0, (double)rank);
-    if (int rc = upload()) return rc;
-    NCCL_CHECK(g_rccl.AllReduce(dsend, dsend, n, ncclFloat64, ncclSum, cw, st));
-    HIP_CHECK(hipMemcpyAsync(hr.data(), dsend, sizeof(double) * n, hipMemcpyDeviceToHost, st));
-    HIP_CHECK(hipStreamSynchronize(st));
-    for (size_t i = 0; i < n; ++i) {
-        double want = 0.0;
-        for (int r = 0; r < world; ++r) want += val((double)r, i);          // rank order = the order the loopback transport sums in
-        if (fabs(hr[i] - want) > 1e-9 * fabs(want) + 1e-12) bad += 1.0;
-        sum += hr[i];
-    }
-    // (5) row all-reduce out of place
-    fill(0, 10.0 * rank);
-    if (int rc = upload()) return rc;
-    NCCL_CHECK(g_rccl.AllReduce(dsend, drecv, n, ncclFloat64, ncclSum, crow, st));
-    if (int rc = download()) return rc;
-    for (size_t i = 0; i < n; ++i) {
-        double want = 0.0;
-        for (int c = 0; c < Pc; ++c) want += val(10.0 * (pr * Pc + c), i);
-        if (fabs(hr[i] - want) > 1e-9 * fabs(want) + 1e-12) bad += 1.0;
-        sum += hr[i];
-    }
-    out4[0] = bad;
-    out4[1] = sum;
-    out4[2] = (double)pc;                                          // key of the row split = grid column: must be the rank inside crow
-    out4[3] = (double)pr;
-    (void)hipFree(dsend);
-    (void)hipFree(drecv);
-    (void)hipStreamDestroy(st);
-    NCCL_CHECK(g_rccl.CommDestroy(crow));
-    NCCL_CHECK(g_rccl.CommDestroy(ccol));
-    NCCL_CHECK(g_rccl.CommDestroy(cw));
-    return 0;
-}
-
-// sum `count` doubles at `pick(rank)` over all ranks, result everywhere
-static int grid_allreduce(mi355gp_grid* g, size_t count, const std::function<double*(GridRank&)>& pick) {
-    for (GridRank& r : g->ranks) coll_log(r, 0, 2, 0, count);
-    if (g->loopback) {
-        double* acc = pick(g->ranks[0]);
-        const unsigned nblk = (unsigned)((count + 255) / 256);
-        for (size_t i = 1; i < g->ranks.size(); ++i)
-            hipLaunchKernelGGL(k_grid_axpy, dim3(nblk), dim3(256), 0, g->st, acc, pick(g->ranks[i]), (long)count);
-        for (size_t i = 1; i < g->ranks.size(); ++i)
-            HIP_CHECK(hipMemcpyAsync(pick(g->ranks[i]), acc, count * sizeof(double), hipMemcpyDeviceToDevice, g->st));
-        return 0;
-    }
-    GridRank& r = g->ranks[0];
-    NCCL_CHECK(g_rccl.AllReduce(pick(r), pick(r), count, ncclFloat64, ncclSum, g->comm_world, r.st));
-    return 0;
-}
-
 // (Re)allocates the four panel stores of a rank and their pointer tables for the current group size G (see GridRank).
 static int alloc_panel_stores(mi355gp_grid* g, GridRank& r) {
     const long nb = g->nb, T = g->T;
     const size_t tile = (size_t)nb * nb;
-    void* old[] = {r.RPs, r.CPs, r.XRs, r.XRrs, (void*)r.dRP, (void*)r.dCP, (void*)r.dXR, (void*)r.dXRr};
-    for (void* p : old)
-        if (p) (void)hipFree(p);
-    r.RPs = r.CPs = r.XRs = r.XRrs = nullptr;
-    r.dRP = r.dCP = r.dXR = r.dXRr = nullptr;
+    DevBuf* store[4] = {&r.RPs, &r.CPs, &r.XRs, &r.XRrs};
+    DevArr<const double*>* table[4] = {&r.dRP, &r.dCP, &r.dXR, &r.dXRr};
+    for (DevBuf* s : store) *s = DevBuf();                   // the stores sized for another G go first
+    for (DevArr<const double*>* t : table) *t = DevArr<const double*>();
     const long G = g->G < 1 ? 1 : g->G;
     long slots = 2 * G;
     if (slots > T) slots = T;
@@ -943,9 +391,8 @@ static int alloc_panel_stores(mi355gp_grid* g, GridRank& r) {
     }
     const size_t bytes[4] = {sizeof(double) * tile * (size_t)(slots * r.TLr + 1), sizeof(double) * tile * (size_t)(slots * r.TLc + 1),
                              sizeof(double) * tile * (size_t)(oXR[T] + 1), sizeof(double) * tile * (size_t)(oXRr[T] + 1)};
-    double** dst[4] = {&r.RPs, &r.CPs, &r.XRs, &r.XRrs};
     for (int i = 0; i < 4; ++i)
-        if (hipMalloc(dst[i], bytes[i]) != hipSuccess) {
+        if (store[i]->alloc(bytes[i] / sizeof(double)) != hipSuccess) {
             (void)hipGetLastError();
             mi355gp_set_error("grid mode: out of device memory for the panel stores of rank %d (N=%ld on %dx%d, nb=%ld: L-panel ring "
                               "%.2f + %.2f GB for G=%ld, X panels %.2f + %.2f GB, next to 3 x %.2f GB of local matrices); use more "
@@ -961,77 +408,42 @@ static int alloc_panel_stores(mi355gp_grid* g, GridRank& r) {
         r.hXR[k] = r.XRs + oXR[k] * (long)tile;
         r.hXRr[k] = r.XRrs + oXRr[k] * (long)tile;
     }
-    const size_t tb = sizeof(double*) * (size_t)T;
-    HIP_CHECK(hipMalloc((void**)&r.dRP, tb));
-    HIP_CHECK(hipMalloc((void**)&r.dCP, tb));
-    HIP_CHECK(hipMalloc((void**)&r.dXR, tb));
-    HIP_CHECK(hipMalloc((void**)&r.dXRr, tb));
-    HIP_CHECK(hipMemcpy((void*)r.dRP, r.hRP.data(), tb, hipMemcpyHostToDevice));
-    HIP_CHECK(hipMemcpy((void*)r.dCP, r.hCP.data(), tb, hipMemcpyHostToDevice));
-    HIP_CHECK(hipMemcpy((void*)r.dXR, r.hXR.data(), tb, hipMemcpyHostToDevice));
-    HIP_CHECK(hipMemcpy((void*)r.dXRr, r.hXRr.data(), tb, hipMemcpyHostToDevice));
+    const std::vector<double*>* host[4] = {&r.hRP, &r.hCP, &r.hXR, &r.hXRr};
+    for (DevArr<const double*>* t : table) HIP_CHECK(t->alloc((size_t)T));
+    for (int i = 0; i < 4; ++i)
+        HIP_CHECK(hipMemcpy((void*)table[i]->p, host[i]->data(), sizeof(double*) * (size_t)T, hipMemcpyHostToDevice));
     return 0;
 }
 
-// Debug mode (MI355GP_GRID_CHECK_SEQ=1 / MI355GP_GRID_OPT_CHECK_SEQ): after an evaluation, every member of a communicator must
-// have logged the SAME sequence of collectives on it.  Loopback: the logical ranks are compared on the host.  One rank per
-// process: every member contributes (hash high, hash low, count) at its own position of a vector that is sum-all-reduced inside
-// the communicator (the three numbers are integers below 2^32: exact in fp64), then compares all positions with its own.
-static int grid_check_sequences(mi355gp_grid* g) {
+// Streams, events, ranks and communicators of a new context.  On a failing return the context is partly built:
+// mi355gp_grid_create hands it to mi355gp_grid_destroy, which releases whatever is there.
+static int grid_init(mi355gp_grid* g, const void* id128) {
+    const int world = g->world, Pc = g->Pc;
+    {
+        const char* envf = DIAG_ENV("GRID_FORCE_GENERIC");
+        if (g->loopback && world == 1 && !(envf && atoi(envf))) return mi355gp_create(g->device, &g->single);
+    }
+    HIP_CHECK(hipStreamCreateWithFlags(&g->st, hipStreamNonBlocking));
+    {
+        int least = 0, greatest = 0;
+        HIP_CHECK(hipDeviceGetStreamPriorityRange(&least, &greatest));
+        HIP_CHECK(hipStreamCreateWithPriority(&g->sc, hipStreamNonBlocking, greatest));
+        HIP_CHECK(hipStreamCreateWithPriority(&g->sw, hipStreamNonBlocking, least));
+        HIP_CHECK(hipEventCreateWithFlags(&g->ev_w, hipEventDisableTiming));
+        for (int o = 0; o < MI355GP_GRID_OPT_NUM; ++o) grid_default_option(g, o);
+        g->dbg_crit = diag_env_int(DIAG_ENV("GRID_DBG_CRIT"), 0);
+    }
+    for (auto& e : g->ev) HIP_CHECK(hipEventCreate(&e));
     if (g->loopback) {
-        for (const GridRank& a : g->ranks)
-            for (const GridRank& b : g->ranks) {
-                const bool same[3] = {true, a.pr == b.pr, a.pc == b.pc};
-                for (int c = 0; c < 3; ++c)
-                    if (same[c] && (a.coll_hash[c] != b.coll_hash[c] || a.coll_count[c] != b.coll_count[c])) {
-                        mi355gp_set_error("grid mode: ranks %d and %d logged different collective sequences on communicator %d "
-                                          "(%ld vs %ld collectives)", a.rank, b.rank, c, a.coll_count[c], b.coll_count[c]);
-                        return -7;
-                    }
-            }
+        for (int r = 0; r < world; ++r) g->ranks.push_back(make_rank(r, Pc, g->st, g->sc, g->sw));
         return 0;
     }
-    GridRank& r = g->ranks[0];
-    const ncclComm_t comms[3] = {g->comm_world, g->comm_row, g->comm_col};
-    const int sizes[3] = {g->world, g->Pc, g->Pr}, me[3] = {r.rank, r.pc, r.pr};
-    if (r.seqbuf_members < g->world) {                      // world >= Pr, Pc: one buffer serves the three communicators
-        if (r.seqbuf) (void)hipFree(r.seqbuf);
-        r.seqbuf = nullptr;
-        HIP_CHECK(hipMalloc(&r.seqbuf, sizeof(double) * 3 * (size_t)g->world));
-        r.seqbuf_members = g->world;
-    }
-    const uint64_t hash[3] = {r.coll_hash[0], r.coll_hash[1], r.coll_hash[2]};       // before the check's own collectives
-    const long cnt[3] = {r.coll_count[0], r.coll_count[1], r.coll_count[2]};
-    for (int c = 0; c < 3; ++c) {
-        std::vector<double> v((size_t)3 * sizes[c], 0.0);
-        v[(size_t)3 * me[c]] = (double)(hash[c] >> 32);
-        v[(size_t)3 * me[c] + 1] = (double)(hash[c] & 0xffffffffull);
-        v[(size_t)3 * me[c] + 2] = (double)cnt[c];
-        HIP_CHECK(hipMemcpyAsync(r.seqbuf, v.data(), sizeof(double) * v.size(), hipMemcpyHostToDevice, r.st));
-        NCCL_CHECK(g_rccl.AllReduce(r.seqbuf, r.seqbuf, v.size(), ncclFloat64, ncclSum, comms[c], r.st));
-        HIP_CHECK(hipMemcpyAsync(v.data(), r.seqbuf, sizeof(double) * v.size(), hipMemcpyDeviceToHost, r.st));
-        HIP_CHECK(hipStreamSynchronize(r.st));
-        for (int m = 0; m < sizes[c]; ++m)
-            for (int q = 0; q < 3; ++q)
-                if (v[(size_t)3 * m + q] != v[(size_t)3 * me[c] + q]) {
-                    mi355gp_set_error("grid mode: rank %d and member %d of communicator %d logged different collective sequences "
-                                      "(%.0f vs %ld collectives)", r.rank, m, c, v[(size_t)3 * m + 2], cnt[c]);
-                    return -7;
-                }
-    }
-    return 0;
+    if (int rc = grid_comm_load()) return rc;
+    g->ranks.push_back(make_rank(g->my_rank, Pc, g->st, g->sc, g->sw));
+    return grid_comm_connect(g, g->ranks[0], id128);
 }
 
 extern "C" {
-
-int mi355gp_grid_unique_id(void* id128) {
-    ARG_CHECK(id128 != nullptr, "mi355gp_grid_unique_id: NULL");
-    if (!g_rccl.load()) return -20;
-    ncclUniqueId id;
-    NCCL_CHECK(g_rccl.GetUniqueId(&id));
-    memcpy(id128, &id, sizeof(id));
-    return 0;
-}
 
 int mi355gp_grid_create(int device, int rank, int world, int Pr, int Pc, int nb, const void* id128,
                         mi355gp_grid** out) {
@@ -1053,50 +465,9 @@ int mi355gp_grid_create(int device, int rank, int world, int Pr, int Pc, int nb,
     g->nb = nb;
     g->my_rank = rank;
     g->loopback = (id128 == nullptr);
-    {
-        const char* envf = DIAG_ENV("GRID_FORCE_GENERIC");
-        if (g->loopback && world == 1 && !(envf && atoi(envf))) {
-            if (int rc = mi355gp_create(device, &g->single)) return rc;
-            *out = g;
-            return 0;
-        }
-    }
-    HIP_CHECK(hipStreamCreateWithFlags(&g->st, hipStreamNonBlocking));
-    {
-        int least = 0, greatest = 0;
-        HIP_CHECK(hipDeviceGetStreamPriorityRange(&least, &greatest));
-        HIP_CHECK(hipStreamCreateWithPriority(&g->sc, hipStreamNonBlocking, greatest));
-        HIP_CHECK(hipStreamCreateWithPriority(&g->sw, hipStreamNonBlocking, least));
-        HIP_CHECK(hipEventCreateWithFlags(&g->ev_w, hipEventDisableTiming));
-        for (int o = 0; o < MI355GP_GRID_OPT_NUM; ++o) grid_default_option(g, o);
-        g->dbg_crit = diag_env_int(DIAG_ENV("GRID_DBG_CRIT"), 0);
-    }
-    for (auto& e : g->ev) HIP_CHECK(hipEventCreate(&e));
-    if (g->loopback) {
-        g->ranks.resize((size_t)world);
-        for (int r = 0; r < world; ++r) {
-            g->ranks[r].rank = r;
-            g->ranks[r].pr = r / Pc;
-            g->ranks[r].pc = r % Pc;
-            g->ranks[r].st = g->st;
-            g->ranks[r].sc = g->sc;
-            g->ranks[r].sw = g->sw;
-        }
-    } else {
-        if (!g_rccl.load()) return -20;
-        g->ranks.resize(1);
-        GridRank& r = g->ranks[0];
-        r.rank = rank;
-        r.pr = rank / Pc;
-        r.pc = rank % Pc;
-        r.st = g->st;
-        r.sc = g->sc;
-        r.sw = g->sw;
-        ncclUniqueId id;
-        memcpy(&id, id128, sizeof(id));
-        NCCL_CHECK(g_rccl.CommInitRank(&g->comm_world, world, id, rank));
-        NCCL_CHECK(g_rccl.CommSplit(g->comm_world, r.pr, r.pc, &g->comm_row, nullptr));   // rank inside = pc
-        NCCL_CHECK(g_rccl.CommSplit(g->comm_world, r.pc, r.pr, &g->comm_col, nullptr));   // rank inside = pr
+    if (int rc = grid_init(g, id128)) {
+        mi355gp_grid_destroy(g);
+        return rc;
     }
     *out = g;
     return 0;
@@ -1109,12 +480,11 @@ int mi355gp_grid_destroy(mi355gp_grid* g) {
         delete g;
         return 0;
     }
+    // (also the exit of a mi355gp_grid_create that failed half way: every handle below may still be null, the lists empty)
     (void)hipSetDevice(g->device);
-    (void)hipStreamSynchronize(g->st);
-    for (GridRank& r : g->ranks) free_rank(r);
-    if (g->comm_row) g_rccl.CommDestroy(g->comm_row);
-    if (g->comm_col) g_rccl.CommDestroy(g->comm_col);
-    if (g->comm_world) g_rccl.CommDestroy(g->comm_world);
+    if (g->st) (void)hipStreamSynchronize(g->st);
+    for (GridRank& r : g->ranks) free_rank(r, g->Pc);
+    grid_comm_disconnect(g);
     for (auto& e : g->ev)
         if (e) (void)hipEventDestroy(e);
     for (auto& e : g->ev_cr) (void)hipEventDestroy(e);
@@ -1161,24 +531,22 @@ int mi355gp_grid_set_data(mi355gp_grid* g, const double* X, int64_t N, int D, co
     const long T = g->T, TLrM = (T + g->Pr - 1) / g->Pr, TLcM = (T + g->Pc - 1) / g->Pc;
     const int groups = (D + 31) / 32;
     for (GridRank& r : g->ranks) {
-        const int rank = r.rank, pr = r.pr, pc = r.pc;
-        hipStream_t st = r.st, sc = r.sc, sw = r.sw;
-        free_rank(r);
-        r.rank = rank; r.pr = pr; r.pc = pc; r.st = st; r.sc = sc; r.sw = sw;
+        free_rank(r, g->Pc);                     // a fresh rank that keeps its identity
+        const int pr = r.pr, pc = r.pc;
         r.TLr = cnt_le(T - 1, pr, g->Pr);
         r.TLc = cnt_le(T - 1, pc, g->Pc);
         r.LR = TLrM * nb;
         r.LC = TLcM * nb;
-        const size_t mat = sizeof(double) * r.LR * r.LC;
-        HIP_CHECK(hipMalloc(&r.A, mat));
-        HIP_CHECK(hipMalloc(&r.X, mat));
-        HIP_CHECK(hipMalloc(&r.W, mat));
+        const size_t mat = (size_t)r.LR * r.LC;
+        HIP_CHECK(r.A.alloc(mat));
+        HIP_CHECK(r.X.alloc(mat));
+        HIP_CHECK(r.W.alloc(mat));
         if (int rc = alloc_panel_stores(g, r)) return rc;
-        HIP_CHECK(hipMalloc(&r.cpart, sizeof(double) * (size_t)(r.LR / CR_ROWS + 1) * r.LC));
-        HIP_CHECK(hipMalloc(&r.Dt, sizeof(double) * nb * nb));
-        HIP_CHECK(hipMalloc(&r.Dv, sizeof(double) * nb * nb));
-        HIP_CHECK(hipMalloc(&r.Ds, sizeof(double) * nb * nb));
-        if (!g->loopback) HIP_CHECK(hipMalloc(&r.bstage, sizeof(double) * nb * nb * (size_t)(TLrM > TLcM ? TLrM : TLcM)));
+        HIP_CHECK(r.cpart.alloc((size_t)(r.LR / CR_ROWS + 1) * r.LC));
+        HIP_CHECK(r.Dt.alloc((size_t)nb * nb));
+        HIP_CHECK(r.Dv.alloc((size_t)nb * nb));
+        HIP_CHECK(r.Ds.alloc((size_t)nb * nb));
+        if (!g->loopback) HIP_CHECK(r.bstage.alloc((size_t)nb * nb * (size_t)(TLrM > TLcM ? TLrM : TLcM)));
         // local point sets (host-side gather, uploaded once)
         std::vector<long> gR((size_t)r.LR), gC((size_t)r.LC);
         std::vector<double> XsR((size_t)r.LR * D, 0.0), XsC((size_t)r.LC * D, 0.0);
@@ -1195,12 +563,12 @@ int mi355gp_grid_set_data(mi355gp_grid* g, const double* X, int64_t N, int D, co
             gC[l] = gj;
             if (gj < N) { memcpy(&XsC[(size_t)l * D], X + gj * D, sizeof(double) * D); r.nvc = l + 1; }
         }
-        HIP_CHECK(hipMalloc(&r.gR, sizeof(long) * r.LR));
-        HIP_CHECK(hipMalloc(&r.gC, sizeof(long) * r.LC));
-        HIP_CHECK(hipMalloc(&r.XsR, sizeof(double) * r.LR * D));
-        HIP_CHECK(hipMalloc(&r.XsC, sizeof(double) * r.LC * D));
-        HIP_CHECK(hipMalloc(&r.XtR, sizeof(double) * r.LR * D));
-        HIP_CHECK(hipMalloc(&r.XtC, sizeof(double) * r.LC * D));
+        HIP_CHECK(r.gR.alloc((size_t)r.LR));
+        HIP_CHECK(r.gC.alloc((size_t)r.LC));
+        HIP_CHECK(r.XsR.alloc((size_t)r.LR * D));
+        HIP_CHECK(r.XsC.alloc((size_t)r.LC * D));
+        HIP_CHECK(r.XtR.alloc((size_t)r.LR * D));
+        HIP_CHECK(r.XtC.alloc((size_t)r.LC * D));
         HIP_CHECK(hipMemcpy(r.gR, gR.data(), sizeof(long) * r.LR, hipMemcpyHostToDevice));
         HIP_CHECK(hipMemcpy(r.gC, gC.data(), sizeof(long) * r.LC, hipMemcpyHostToDevice));
         HIP_CHECK(hipMemcpy(r.XsR, XsR.data(), sizeof(double) * r.LR * D, hipMemcpyHostToDevice));
@@ -1214,28 +582,27 @@ int mi355gp_grid_set_data(mi355gp_grid* g, const double* X, int64_t N, int D, co
                 dg.push_back((int)t);
             }
         r.ndiag = (int)dg.size();
-        HIP_CHECK(hipMalloc(&r.dl_r, sizeof(int) * (r.ndiag + 1)));
-        HIP_CHECK(hipMalloc(&r.dl_c, sizeof(int) * (r.ndiag + 1)));
-        HIP_CHECK(hipMalloc(&r.dg, sizeof(int) * (r.ndiag + 1)));
+        HIP_CHECK(r.dl_r.alloc((size_t)r.ndiag + 1));
+        HIP_CHECK(r.dl_c.alloc((size_t)r.ndiag + 1));
+        HIP_CHECK(r.dg.alloc((size_t)r.ndiag + 1));
         if (r.ndiag) {
             HIP_CHECK(hipMemcpy(r.dl_r, dlr.data(), sizeof(int) * r.ndiag, hipMemcpyHostToDevice));
             HIP_CHECK(hipMemcpy(r.dl_c, dlc.data(), sizeof(int) * r.ndiag, hipMemcpyHostToDevice));
             HIP_CHECK(hipMemcpy(r.dg, dg.data(), sizeof(int) * r.ndiag, hipMemcpyHostToDevice));
         }
         const long vmax = (r.LR > r.LC ? r.LR : r.LC);
-        HIP_CHECK(hipMalloc(&r.vloc, sizeof(double) * vmax));
-        HIP_CHECK(hipMalloc(&r.gvec, sizeof(double) * N * Dy));
-        HIP_CHECK(hipMalloc(&r.gvec2, sizeof(double) * N));
-        HIP_CHECK(hipMalloc(&r.alpha, sizeof(double) * N * Dy));
-        HIP_CHECK(hipMalloc(&r.ybuf, sizeof(double) * N * Dy));
-        HIP_CHECK(hipMalloc(&r.Rg, sizeof(double) * N * Dy));
+        HIP_CHECK(r.vloc.alloc((size_t)vmax));
+        HIP_CHECK(r.gvec2.alloc((size_t)N));
+        HIP_CHECK(r.alpha.alloc((size_t)N * Dy));
+        HIP_CHECK(r.ybuf.alloc((size_t)N * Dy));
+        HIP_CHECK(r.Rg.alloc((size_t)N * Dy));
         HIP_CHECK(hipMemcpy(r.Rg, R, sizeof(double) * N * Dy, hipMemcpyHostToDevice));
-        HIP_CHECK(hipMalloc(&r.scal, sizeof(double) * 8));
-        HIP_CHECK(hipMalloc(&r.gradPart, sizeof(double) * groups * 2048 * GP_STRIDE));
-        HIP_CHECK(hipMalloc(&r.gradOut, sizeof(double) * groups * GP_STRIDE));
-        HIP_CHECK(hipMalloc(&r.invls, sizeof(double) * D));
-        HIP_CHECK(hipMalloc(&r.noise, sizeof(double) * N));
-        HIP_CHECK(hipMalloc(&r.info_g, sizeof(int) * 4));
+        HIP_CHECK(r.scal.alloc(8));
+        HIP_CHECK(r.gradPart.alloc((size_t)groups * 2048 * GP_STRIDE));
+        HIP_CHECK(r.gradOut.alloc((size_t)groups * GP_STRIDE));
+        HIP_CHECK(r.invls.alloc((size_t)D));
+        HIP_CHECK(r.noise.alloc((size_t)N));
+        HIP_CHECK(r.info_g.alloc(4));
         if (factor_ws_alloc(&r.ws, nb) != 0) return -3;
         r.ws.lookahead = 0;      // the nb x nb diagonal tile is factored in order on the rank's stream
     }
@@ -1244,30 +611,29 @@ int mi355gp_grid_set_data(mi355gp_grid* g, const double* X, int64_t N, int D, co
 
 }  // extern "C"
 
-// one evaluation on all local ranks
-static int grid_run(mi355gp_grid* g, const PartSpec& pt, const double* noise, int64_t noise_len, double jit, double* out_scalars, double* alpha_out,
-                    double* dtheta_out, double* diag_out, double* stage_ms, int attempt = 0) {
-    const KernParams& kp = pt.kp;
-    const long nb = g->nb, T = g->T, n = g->n;
-    const int Pr = g->Pr, Pc = g->Pc, Dy = g->Dy, D = g->D, q = (int)(nb / NB);
-    const size_t tile = (size_t)nb * nb;
-    const GridPred nopred{0, 1, 0, 1, 0, 0, 0};
-    {   // the L-panel ring is sized for the group size in effect when the data was set: follow a later change of G
-        long want = 2 * (g->G < 1 ? 1 : g->G);
-        if (want > T) want = T;
-        for (GridRank& r : g->ranks)
-            if (r.ring_slots != want) {
-                HIP_CHECK(hipDeviceSynchronize());
-                if (int rc = alloc_panel_stores(g, r)) return rc;
-            }
-    }
+// ---- one evaluation on all local ranks, phase by phase (grid_run at the end puts them in order) ----------------------------
+// the stream of a rank's critical path: sc under look-ahead, else everything runs in order on st
+static hipStream_t crit_stream(const mi355gp_grid* g, const GridRank& r) { return g->lookahead ? r.sc : r.st; }
+
+// prepare: the L-panel ring is sized for the group size in effect when the data was set -- follow a later change of G; empty
+// the collective logs
+static int grid_prepare(mi355gp_grid* g) {
+    long want = 2 * (g->G < 1 ? 1 : g->G);
+    if (want > g->T) want = g->T;
     for (GridRank& r : g->ranks)
-        for (int c = 0; c < 3; ++c) {
-            r.coll_hash[c] = 14695981039346656037ull;
-            r.coll_count[c] = 0;
+        if (r.ring_slots != want) {
+            HIP_CHECK(hipDeviceSynchronize());
+            if (int rc = alloc_panel_stores(g, r)) return rc;
         }
-    HIP_CHECK(hipEventRecord(g->ev[0], g->st));
-    // ---- covariance tiles: K(X_rows, X_cols) + diagonal fix-up -------------------------------------------
+    grid_coll_reset(g);
+    return 0;
+}
+
+// build K: the covariance tiles K(X_rows, X_cols) of every rank + the diagonal fix-up
+static int grid_build_K(mi355gp_grid* g, const PartSpec& pt, const double* noise, int64_t noise_len, double jit) {
+    const KernParams& kp = pt.kp;
+    const long nb = g->nb;
+    const int D = g->D;
     for (GridRank& r : g->ranks) {
         hipStream_t st = r.st;
         HIP_CHECK(hipMemcpyAsync(r.invls, pt.inv_ls.data(), sizeof(double) * D, hipMemcpyHostToDevice, st));
@@ -1282,175 +648,214 @@ static int grid_run(mi355gp_grid* g, const PartSpec& pt, const double* noise, in
         if (r.nvr > 0 && r.nvc > 0) launch_kbuild_cross(st, kp, r.XtR, r.LR, r.nvr, r.XtC, r.LC, r.nvc, r.A, r.LC);
         if (r.ndiag > 0) {
             const long cnt = (long)r.ndiag * nb;
-            hipLaunchKernelGGL(k_grid_fix_diag, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, st, r.A, r.LC, nb, n,
-                               r.ndiag, r.dl_r, r.dl_c, r.dg, r.noise, (long)noise_len, jit);
+            hipLaunchKernelGGL(k_grid_fix_diag, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, st, r.A.p, r.LC, nb, g->n,
+                               r.ndiag, r.dl_r.p, r.dl_c.p, r.dg.p, r.noise.p, (long)noise_len, jit);
         }
     }
-    HIP_CHECK(hipEventRecord(g->ev[1], g->st));
-    // ---- the one-pass factorisation / inversion, two-level blocked -----------------------------------------------
-    // Steps are taken in GROUPS of G (MI355GP_GRID_G).  Every step k runs its critical path crit(k) -- diagonal tile k,
-    // D = L_kk^-1, the panel solves, row k of X and ALL panel broadcasts -- and then brings only the REST OF ITS GROUP up to
-    // date with K = nb updates (near(k): tile columns k+1 .. ge-1 of A, tile rows k+1 .. ge-1 of B; ge = first step of the
-    // next group).  Everything beyond the group receives the group's G panels in ONE pass over C with K = G * nb
-    // (k_grid_gemm_multi): first the next group's columns / rows (part1(g), on the critical path), then the bulk.  W = X^T X is
-    // not read by anything before the end: its updates are aggregated over GW steps (MI355GP_GRID_GW; 0 = one deep-K pass
-    // after the last step, the distributed lauum).  The three read-modify-write passes per step of the one-level form
-    // become one pass per G (A, B) and per GW (W) steps: the C traffic of the updates drops accordingly and the tile
-    // pipeline runs K = G * nb deep (k_grid_gemm at K = 512: 0.61 of the fp64 peak; lauum-deep: 0.87).
-    // Two streams per rank, one group of look-ahead:
-    //   sc (high priority): crit(k), near(k) for the steps of group g, then part1(g) [after bulk(g-1): both write the
-    //                       columns / rows of group g+1], then group g+1
-    //   st                : bulk(g) [after crit of the group's last step]
-    //   sw (low priority) : the W updates [after crit of the last step they read]; st joins it after the loop
-    // bulk(g) touches columns / rows >= the start of group g+2 only, the critical path of group g+1 stays inside group
-    // g+1's columns / rows: they run concurrently.  The X panels keep one buffer per step for the whole evaluation (the
-    // deferred W = X^T X reads them late); the L panels live in a RING of 2 G full-height slots (alloc_panel_stores): slot
-    // reuse is safe because sc waits for ev_p1[gi-1] -- i.e. for bulk(g-1) on st -- before part1(g), so every reader of group
-    // g's panels has been enqueued behind the event that group g+2's crit (the next writer of those slots) waits for.
-    // Every rank enqueues the same sequence of collectives on sc, so their order is consistent across the grid.
+    return 0;
+}
+
+// step k, the diagonal tile: (a) L_kk and D = L_kk^-1 on its owner, the factor back into A
+static int grid_step_diag(mi355gp_grid* g, long k) {
+    const long nb = g->nb, lkr = k / g->Pr, lkc = k / g->Pc;
+    const int opr = (int)(k % g->Pr), opc = (int)(k % g->Pc), q = (int)(nb / NB);
+    const size_t tile = (size_t)nb * nb;
+    for (GridRank& r : g->ranks) {
+        if (r.pr != opr || r.pc != opc) continue;
+        hipStream_t s = crit_stream(g, r);
+        double* At = r.A + lkr * nb * r.LC + lkc * nb;
+        HIP_CHECK(hipMemcpy2DAsync(r.Dt, sizeof(double) * nb, At, sizeof(double) * r.LC, sizeof(double) * nb, nb,
+                                   hipMemcpyDeviceToDevice, s));
+        potrf_device(s, r.Dt, nb, &r.ws);
+        hipLaunchKernelGGL(k_grid_tile_stats, dim3(1), dim3(64), 0, s, r.ws.logsum, q, r.ws.info, k * nb, r.scal.p,
+                           r.info_g.p);
+        HIP_CHECK(hipMemsetAsync(r.Dv, 0, sizeof(double) * tile, s));
+        trtri_device(s, r.Dt, r.Dv, r.Ds, nb, &r.ws);
+        HIP_CHECK(hipMemcpy2DAsync(At, sizeof(double) * r.LC, r.Dt, sizeof(double) * nb, sizeof(double) * nb, nb,
+                                   hipMemcpyDeviceToDevice, s));
+    }
+    return 0;
+}
+
+// step k, the L panels: (b) D to its readers, (c) the panel solve, (d) the row panel along the process rows, (e) the column
+// panel down the process columns.  nobc (diagnostics, dbg_crit >= 2): the broadcasts are skipped
+static int grid_step_L_panels(mi355gp_grid* g, long k) {
+    const long nb = g->nb, T = g->T, lkc = k / g->Pc;
+    const int Pr = g->Pr, Pc = g->Pc, opr = (int)(k % Pr), opc = (int)(k % Pc);
+    const size_t tile = (size_t)nb * nb;
+    const bool nobc = g->dbg_crit >= 2;
+    const GridPred nopred{0, 1, 0, 1, 0, 0, 0};
+    // (b) D to the panel owners (process column opc) and to the owners of row k of X (process row opr)
+    if (!nobc) {
+        if (int rc = grid_bcast(g, GROUP_COL, opc, opr, tile, [](GridRank& r, bool) -> double* { return r.Dv; })) return rc;
+        if (int rc = grid_bcast(g, GROUP_ROW, opr, opc, tile, [](GridRank& r, bool) -> double* { return r.Dv; })) return rc;
+    }
+    // (c) panel solve L_ik = A_ik D^T on process column opc
+    for (GridRank& r : g->ranks) {
+        if (r.pc != opc) continue;
+        hipStream_t s = crit_stream(g, r);
+        const int lr0 = cnt_le(k, r.pr, Pr);
+        const long rows = (long)(r.TLr - lr0) * nb;
+        if (rows <= 0) continue;
+        double* Acol = r.A + (long)lr0 * nb * r.LC + lkc * nb;
+        grid_gemm_t<true, true>(s, r.hRP[k] + (long)lr0 * tile, nb, 0, GOp{Acol, r.LC, 0}, GOp{r.Dv, nb, 0}, rows, nb,
+                                nb, nb, 0, nopred);
+        HIP_CHECK(hipMemcpy2DAsync(Acol, sizeof(double) * r.LC, r.hRP[k] + (long)lr0 * tile, sizeof(double) * nb,
+                                   sizeof(double) * nb, rows, hipMemcpyDeviceToDevice, s));
+    }
+    // (d) row panel along every process row
+    for (int pr = 0; pr < Pr && !nobc; ++pr) {
+        const int lr0 = cnt_le(k, pr, Pr), TLr = cnt_le(T - 1, pr, Pr);
+        const size_t cnt = (size_t)(TLr - lr0) * tile;
+        if (int rc = grid_bcast(g, GROUP_ROW, pr, opc, cnt,
+                                [&](GridRank& r, bool) { return r.hRP[k] + (long)lr0 * tile; }))
+            return rc;
+    }
+    // (e) column panel: L_jk for the local columns j > k comes from process row j % Pr -- one broadcast per (process column,
+    //     root) pair: at most Pr per column (grid_bcast_tile_runs)
+    if (!nobc) {
+        std::vector<TileRun> runs;
+        for (int pc = 0; pc < Pc; ++pc)
+            for (int root = 0; root < Pr; ++root) {
+                long first, step;
+                int cnt;
+                tile_progression(k + 1, T, pc, Pc, root, Pr, &first, &step, &cnt);
+                if (cnt > 0) runs.push_back(TileRun{GROUP_COL, pc, root, cnt, first / Pr, step / Pr, first / Pc, step / Pc});
+            }
+        if (int rc = grid_bcast_tile_runs(g, runs, tile, [&](GridRank& r) { return r.hRP[k]; }, [&](GridRank& r) { return r.hCP[k]; }))
+            return rc;
+    }
+    return 0;
+}
+
+// step k, row k of X: (g) X_kj = D * B_kj (j < k), X_kk = D on process row opr and the row block back into X, (h) the X row
+// panel down the process columns, (i) along the process rows
+static int grid_step_X_row(mi355gp_grid* g, long k) {
+    const long nb = g->nb, lkr = k / g->Pr;
+    const int Pr = g->Pr, Pc = g->Pc, opr = (int)(k % Pr), opc = (int)(k % Pc);
+    const size_t tile = (size_t)nb * nb;
+    const bool nobc = g->dbg_crit >= 2;
+    const GridPred nopred{0, 1, 0, 1, 0, 0, 0};
+    // (g) row k of X on process row opr
+    for (GridRank& r : g->ranks) {
+        if (r.pr != opr) continue;
+        hipStream_t s = crit_stream(g, r);
+        const int lcB = cnt_lt(k, r.pc, Pc);                      // local columns with J < k
+        const double* Brow = r.X + lkr * nb * r.LC;
+        grid_gemm_t<true, false>(s, r.hXR[k], nb, 1, GOp{r.Dv, nb, 0}, GOp{Brow, r.LC, 0}, nb, (long)lcB * nb, nb, nb,
+                                 0, nopred);
+        if (r.pc == opc) HIP_CHECK(hipMemcpyAsync(r.hXR[k] + (long)lcB * tile, r.Dv, sizeof(double) * tile,
+                                                  hipMemcpyDeviceToDevice, s));
+        const int lc0 = cnt_le(k, r.pc, Pc);
+        if (lc0 > 0)                                                // final X row block back into the local matrix
+            hipLaunchKernelGGL(k_tiles_to_rowblock, dim3(64, (unsigned)lc0), dim3(256), 0, s, r.X + lkr * nb * r.LC, (long)r.LC,
+                               (const double*)r.hXR[k], (int)nb);
+    }
+    // (h) X row panel down every process column
+    for (int pc = 0; pc < Pc && !nobc; ++pc) {
+        const size_t cnt = (size_t)cnt_le(k, pc, Pc) * tile;
+        if (int rc = grid_bcast(g, GROUP_COL, pc, opr, cnt, [&](GridRank& r, bool) { return r.hXR[k]; })) return rc;
+    }
+    // (i) X_ki for the local rows i <= k comes from process column i % Pc -- at most Pc broadcasts per process row
+    if (!nobc) {
+        std::vector<TileRun> runs;
+        for (int pr = 0; pr < Pr; ++pr)
+            for (int root = 0; root < Pc; ++root) {
+                long first, step;
+                int cnt;
+                tile_progression(0, k + 1, pr, Pr, root, Pc, &first, &step, &cnt);
+                if (cnt > 0) runs.push_back(TileRun{GROUP_ROW, pr, root, cnt, first / Pc, step / Pc, first / Pr, step / Pr});
+            }
+        if (int rc = grid_bcast_tile_runs(g, runs, tile, [&](GridRank& r) { return r.hXR[k]; }, [&](GridRank& r) { return r.hXRr[k]; }))
+            return rc;
+    }
+    return 0;
+}
+
+// crit(k), the critical path of step k: diagonal tile k, D = L_kk^-1, the panel solves, row k of X and ALL panel broadcasts
+static int grid_crit(mi355gp_grid* g, long k) {
+    if (int rc = grid_step_diag(g, k)) return rc;
+    if (g->dbg_crit >= 3) return 0;
+    if (int rc = grid_step_L_panels(g, k)) return rc;
+    return grid_step_X_row(g, k);
+}
+
+// updates of A and B by the panels [k0, k1) on local tile columns J in [ca, cb) (A, rows I >= ca) and tile rows I in
+// [ca, cb) (B, columns J < k1; panel k reaches the columns J <= k), on the critical-path stream or on st
+static void grid_update_AB(mi355gp_grid* g, bool on_crit, long k0, long k1, long ca, long cb) {
+    if (g->dbg_crit) return;
+    const int Pr = g->Pr, Pc = g->Pc;
+    for (GridRank& r : g->ranks) {
+        hipStream_t s = on_crit ? crit_stream(g, r) : r.st;
+        const GridPred lower{1, Pr, r.pr, Pc, r.pc, 0, 0}, all{0, Pr, r.pr, Pc, r.pc, 0, 0};
+        grid_gemm_multi<true, true, 2>(s, r.A, r.LC, r.dRP, r.dCP, (int)k0, (int)k1, cnt_lt(ca, r.pr, Pr), r.TLr,
+                                       cnt_lt(ca, r.pc, Pc), cnt_lt(cb, r.pc, Pc), g->nb, 0, lower);
+        grid_gemm_multi<true, false, 2>(s, r.X, r.LC, r.dRP, r.dXR, (int)k0, (int)k1, cnt_lt(ca, r.pr, Pr),
+                                        cnt_lt(cb, r.pr, Pr), 0, cnt_lt(k1, r.pc, Pc), g->nb, 1, all);
+    }
+}
+
+// W_ij += sum over the steps k in [k0, k1) of X_ki^T X_kj, k >= i >= j, on the low-priority stream: fills whatever the other
+// two leave idle
+static void grid_update_W(mi355gp_grid* g, long k0, long k1) {
+    const int Pr = g->Pr, Pc = g->Pc;
+    for (GridRank& r : g->ranks) {
+        const GridPred lower{1, Pr, r.pr, Pc, r.pc, 0, 0};
+        grid_gemm_multi<false, false, 1>(g->lookahead ? r.sw : r.st, r.W, r.LC, r.dXRr, r.dXR, (int)k0, (int)k1, 0,
+                                         cnt_lt(k1, r.pr, Pr), 0, cnt_lt(k1, r.pc, Pc), g->nb, 2, lower);
+    }
+}
+
+// ---- factor and invert: the one-pass factorisation / inversion, two-level blocked ------------------------------------------
+// Steps are taken in GROUPS of G (MI355GP_GRID_G).  Every step k runs its critical path crit(k) -- diagonal tile k,
+// D = L_kk^-1, the panel solves, row k of X and ALL panel broadcasts -- and then brings only the REST OF ITS GROUP up to
+// date with K = nb updates (near(k): tile columns k+1 .. ge-1 of A, tile rows k+1 .. ge-1 of B; ge = first step of the
+// next group).  Everything beyond the group receives the group's G panels in ONE pass over C with K = G * nb
+// (k_grid_gemm_multi): first the next group's columns / rows (part1(g), on the critical path), then the bulk.  W = X^T X is
+// not read by anything before the end: its updates are aggregated over GW steps (MI355GP_GRID_GW; 0 = one deep-K pass
+// after the last step, the distributed lauum).  The three read-modify-write passes per step of the one-level form
+// become one pass per G (A, B) and per GW (W) steps: the C traffic of the updates drops accordingly and the tile
+// pipeline runs K = G * nb deep (k_grid_gemm at K = 512: 0.61 of the fp64 peak; lauum-deep: 0.87).
+// Two streams per rank, one group of look-ahead:
+//   sc (high priority): crit(k), near(k) for the steps of group g, then part1(g) [after bulk(g-1): both write the
+//                       columns / rows of group g+1], then group g+1
+//   st                : bulk(g) [after crit of the group's last step]
+//   sw (low priority) : the W updates [after crit of the last step they read]; st joins it after the loop
+// bulk(g) touches columns / rows >= the start of group g+2 only, the critical path of group g+1 stays inside group
+// g+1's columns / rows: they run concurrently.  The X panels keep one buffer per step for the whole evaluation (the
+// deferred W = X^T X reads them late); the L panels live in a RING of 2 G full-height slots (alloc_panel_stores): slot
+// reuse is safe because sc waits for ev_p1[gi-1] -- i.e. for bulk(g-1) on st -- before part1(g), so every reader of group
+// g's panels has been enqueued behind the event that group g+2's crit (the next writer of those slots) waits for.
+// Every rank enqueues the same sequence of collectives on sc, so their order is consistent across the grid.
+static int grid_factor_invert(mi355gp_grid* g) {
     const bool la = g->lookahead != 0;
     hipStream_t scs = la ? g->sc : g->st;
-    const long G = g->G < 1 ? 1 : g->G, GW = g->GW;
+    const long T = g->T, G = g->G < 1 ? 1 : g->G, GW = g->GW;
     if (la) {
         HIP_CHECK(hipEventRecord(g->ev[5], g->st));          // the covariance tiles precede everything on sc / sw
         HIP_CHECK(hipStreamWaitEvent(g->sc, g->ev[5], 0));
         HIP_CHECK(hipStreamWaitEvent(g->sw, g->ev[5], 0));
     }
-    auto crit = [&](long k) -> int {
-        const int opr = (int)(k % Pr), opc = (int)(k % Pc);
-        const long lkr = k / Pr, lkc = k / Pc;
-        // (a) diagonal tile: L_kk and D = L_kk^-1 on its owner
-        for (GridRank& r : g->ranks) {
-            if (r.pr != opr || r.pc != opc) continue;
-            hipStream_t s = la ? r.sc : r.st;
-            double* At = r.A + lkr * nb * r.LC + lkc * nb;
-            HIP_CHECK(hipMemcpy2DAsync(r.Dt, sizeof(double) * nb, At, sizeof(double) * r.LC, sizeof(double) * nb, nb,
-                                       hipMemcpyDeviceToDevice, s));
-            potrf_device(s, r.Dt, nb, &r.ws);
-            hipLaunchKernelGGL(k_grid_tile_stats, dim3(1), dim3(64), 0, s, r.ws.logsum, q, r.ws.info, k * nb, r.scal,
-                               r.info_g);
-            HIP_CHECK(hipMemsetAsync(r.Dv, 0, sizeof(double) * tile, s));
-            trtri_device(s, r.Dt, r.Dv, r.Ds, nb, &r.ws);
-            HIP_CHECK(hipMemcpy2DAsync(At, sizeof(double) * r.LC, r.Dt, sizeof(double) * nb, sizeof(double) * nb, nb,
-                                       hipMemcpyDeviceToDevice, s));
-        }
-        if (g->dbg_crit >= 3) return 0;
-        const bool nobc = g->dbg_crit >= 2;
-        // (b) D to the panel owners (process column opc) and to the owners of row k of X (process row opr)
-        if (!nobc) {
-            if (int rc = grid_bcast(g, GROUP_COL, opc, opr, tile, [](GridRank& r, bool) { return r.Dv; })) return rc;
-            if (int rc = grid_bcast(g, GROUP_ROW, opr, opc, tile, [](GridRank& r, bool) { return r.Dv; })) return rc;
-        }
-        // (c) panel solve L_ik = A_ik D^T on process column opc
-        for (GridRank& r : g->ranks) {
-            if (r.pc != opc) continue;
-            hipStream_t s = la ? r.sc : r.st;
-            const int lr0 = cnt_le(k, r.pr, Pr);
-            const long rows = (long)(r.TLr - lr0) * nb;
-            if (rows <= 0) continue;
-            double* Acol = r.A + (long)lr0 * nb * r.LC + lkc * nb;
-            grid_gemm_t<true, true>(s, r.hRP[k] + (long)lr0 * tile, nb, 0, GOp{Acol, r.LC, 0}, GOp{r.Dv, nb, 0}, rows, nb,
-                                    nb, nb, 0, nopred);
-            HIP_CHECK(hipMemcpy2DAsync(Acol, sizeof(double) * r.LC, r.hRP[k] + (long)lr0 * tile, sizeof(double) * nb,
-                                       sizeof(double) * nb, rows, hipMemcpyDeviceToDevice, s));
-        }
-        // (d) row panel along every process row
-        for (int pr = 0; pr < Pr && !nobc; ++pr) {
-            const int lr0 = cnt_le(k, pr, Pr), TLr = cnt_le(T - 1, pr, Pr);
-            const size_t cnt = (size_t)(TLr - lr0) * tile;
-            if (int rc = grid_bcast(g, GROUP_ROW, pr, opc, cnt,
-                                    [&](GridRank& r, bool) { return r.hRP[k] + (long)lr0 * tile; }))
-                return rc;
-        }
-        // (e) column panel: L_jk for the local columns j > k comes from process row j % Pr -- one broadcast per (process column,
-        //     root) pair: at most Pr per column (grid_bcast_tile_runs)
-        if (!nobc) {
-            std::vector<TileRun> runs;
-            for (int pc = 0; pc < Pc; ++pc)
-                for (int root = 0; root < Pr; ++root) {
-                    long first, step;
-                    int cnt;
-                    tile_progression(k + 1, T, pc, Pc, root, Pr, &first, &step, &cnt);
-                    if (cnt > 0) runs.push_back(TileRun{GROUP_COL, pc, root, cnt, first / Pr, step / Pr, first / Pc, step / Pc});
-                }
-            if (int rc = grid_bcast_tile_runs(g, runs, tile, [&](GridRank& r) { return r.hRP[k]; }, [&](GridRank& r) { return r.hCP[k]; }))
-                return rc;
-        }
-        // (g) row k of X on process row opr: X_kj = D * B_kj (j < k), X_kk = D
-        for (GridRank& r : g->ranks) {
-            if (r.pr != opr) continue;
-            hipStream_t s = la ? r.sc : r.st;
-            const int lcB = cnt_lt(k, r.pc, Pc);                      // local columns with J < k
-            const double* Brow = r.X + lkr * nb * r.LC;
-            grid_gemm_t<true, false>(s, r.hXR[k], nb, 1, GOp{r.Dv, nb, 0}, GOp{Brow, r.LC, 0}, nb, (long)lcB * nb, nb, nb,
-                                     0, nopred);
-            if (r.pc == opc) HIP_CHECK(hipMemcpyAsync(r.hXR[k] + (long)lcB * tile, r.Dv, sizeof(double) * tile,
-                                                      hipMemcpyDeviceToDevice, s));
-            const int lc0 = cnt_le(k, r.pc, Pc);
-            if (lc0 > 0)                                                // final X row block back into the local matrix
-                hipLaunchKernelGGL(k_tiles_to_rowblock, dim3(64, (unsigned)lc0), dim3(256), 0, s, r.X + lkr * nb * r.LC, (long)r.LC,
-                                   (const double*)r.hXR[k], (int)nb);
-        }
-        // (h) X row panel down every process column
-        for (int pc = 0; pc < Pc && !nobc; ++pc) {
-            const size_t cnt = (size_t)cnt_le(k, pc, Pc) * tile;
-            if (int rc = grid_bcast(g, GROUP_COL, pc, opr, cnt, [&](GridRank& r, bool) { return r.hXR[k]; })) return rc;
-        }
-        // (i) X_ki for the local rows i <= k comes from process column i % Pc -- at most Pc broadcasts per process row
-        if (!nobc) {
-            std::vector<TileRun> runs;
-            for (int pr = 0; pr < Pr; ++pr)
-                for (int root = 0; root < Pc; ++root) {
-                    long first, step;
-                    int cnt;
-                    tile_progression(0, k + 1, pr, Pr, root, Pc, &first, &step, &cnt);
-                    if (cnt > 0) runs.push_back(TileRun{GROUP_ROW, pr, root, cnt, first / Pc, step / Pc, first / Pr, step / Pr});
-                }
-            if (int rc = grid_bcast_tile_runs(g, runs, tile, [&](GridRank& r) { return r.hXR[k]; }, [&](GridRank& r) { return r.hXRr[k]; }))
-                return rc;
-        }
-        return 0;
-    };
-    // updates of A and B by the panels [k0, k1) on local tile columns J in [ca, cb) (A, rows I >= ca) and tile rows I in
-    // [ca, cb) (B, columns J < k1; panel k reaches the columns J <= k)
-    auto update_AB = [&](hipStream_t (*pick)(GridRank&, bool), long k0, long k1, long ca, long cb) {
-        if (g->dbg_crit) return;
-        for (GridRank& r : g->ranks) {
-            hipStream_t s = pick(r, la);
-            const GridPred lower{1, Pr, r.pr, Pc, r.pc, 0, 0}, all{0, Pr, r.pr, Pc, r.pc, 0, 0};
-            grid_gemm_multi<true, true, 2>(s, r.A, r.LC, r.dRP, r.dCP, (int)k0, (int)k1, cnt_lt(ca, r.pr, Pr), r.TLr,
-                                           cnt_lt(ca, r.pc, Pc), cnt_lt(cb, r.pc, Pc), nb, 0, lower);
-            grid_gemm_multi<true, false, 2>(s, r.X, r.LC, r.dRP, r.dXR, (int)k0, (int)k1, cnt_lt(ca, r.pr, Pr),
-                                            cnt_lt(cb, r.pr, Pr), 0, cnt_lt(k1, r.pc, Pc), nb, 1, all);
-        }
-    };
-    auto on_sc = [](GridRank& r, bool la_) -> hipStream_t { return la_ ? r.sc : r.st; };
-    auto on_st = [](GridRank& r, bool) -> hipStream_t { return r.st; };
     long kw0 = 0;                                            // first step whose X panels W has not received yet
     const long ngroups = (T + G - 1) / G;
     for (long gi = 0; gi < ngroups; ++gi) {
         const long kb = gi * G, ge = (kb + G < T) ? kb + G : T, ge2 = (ge + G < T) ? ge + G : T;
         for (long k = kb; k < ge; ++k) {
-            if (int rc = crit(k)) return rc;
-            if (k + 1 < ge) update_AB(on_sc, k, k + 1, k + 1, ge);                 // near(k)
+            if (int rc = grid_crit(g, k)) return rc;
+            if (k + 1 < ge) grid_update_AB(g, true, k, k + 1, k + 1, ge);          // near(k)
         }
         if (la) HIP_CHECK(hipEventRecord(g->ev_cr[gi], scs));
         if (ge < T) {                                                              // part1(g): the next group's columns / rows
             if (la && gi > 0) HIP_CHECK(hipStreamWaitEvent(g->sc, g->ev_p1[gi - 1], 0));
-            update_AB(on_sc, kb, ge, ge, ge2);
+            grid_update_AB(g, true, kb, ge, ge, ge2);
         }
         if (la) HIP_CHECK(hipStreamWaitEvent(g->st, g->ev_cr[gi], 0));
-        if (ge2 < T) update_AB(on_st, kb, ge, ge2, T);                             // bulk(g)
+        if (ge2 < T) grid_update_AB(g, false, kb, ge, ge2, T);                     // bulk(g)
         if (la) HIP_CHECK(hipEventRecord(g->ev_p1[gi], g->st));
-        // W_ij += sum_k X_ki^T X_kj over the finished steps, k >= i >= j
         const bool flush = !g->dbg_crit && ((ge == T) || (GW > 0 && ge - kw0 >= GW));
-        if (flush) {                                          // on the low-priority stream: fills whatever the other two leave idle
+        if (flush) {                                                               // W over the finished steps
             if (la) HIP_CHECK(hipStreamWaitEvent(g->sw, g->ev_cr[gi], 0));
-            for (GridRank& r : g->ranks) {
-                const GridPred lower{1, Pr, r.pr, Pc, r.pc, 0, 0};
-                grid_gemm_multi<false, false, 1>(la ? r.sw : r.st, r.W, r.LC, r.dXRr, r.dXR, (int)kw0, (int)ge, 0,
-                                                 cnt_lt(ge, r.pr, Pr), 0, cnt_lt(ge, r.pc, Pc), nb, 2, lower);
-            }
+            grid_update_W(g, kw0, ge);
             kw0 = ge;
         }
     }
@@ -1458,88 +863,104 @@ static int grid_run(mi355gp_grid* g, const PartSpec& pt, const double* noise, in
         HIP_CHECK(hipEventRecord(g->ev_w, g->sw));
         HIP_CHECK(hipStreamWaitEvent(g->st, g->ev_w, 0));
     }
-    HIP_CHECK(hipEventRecord(g->ev[2], g->st));
-    // ---- alpha = X^T (X R), diag W, logdet ------------------------------------------------------------------
-    const unsigned nblkN = (unsigned)((n * Dy + 255) / 256);
+    return 0;
+}
+
+// vloc[j] = sum_i X_ij * (v ? v[g(i)][d] : X_ij)
+static void grid_col_reduce(mi355gp_grid* g, GridRank& r, const double* v, int d) {
+    const long nch = (r.LR + CR_ROWS - 1) / CR_ROWS;
+    hipLaunchKernelGGL(k_grid_col_reduce_part, dim3((unsigned)((r.LC + 63) / 64), (unsigned)nch), dim3(256), 0, r.st, r.X.p,
+                       r.LC, r.LR, r.LC, r.gR.p, v, v ? g->Dy : 1, d, g->n, r.cpart.p, g->nb, g->Pr, r.pr, g->Pc, r.pc);
+    hipLaunchKernelGGL(k_grid_col_combine, dim3((unsigned)((r.LC + 255) / 256)), dim3(256), 0, r.st, r.cpart.p, nch, r.LC,
+                       r.vloc.p);
+}
+
+// solve: y = X R, alpha = X^T y, diag W, and the sums over ranks (logdet and the failure counts travel in scal)
+static int grid_solve(mi355gp_grid* g) {
+    const long n = g->n;
+    const int Dy = g->Dy;
     for (GridRank& r : g->ranks) {                       // y = X R (partial over the local columns)
         HIP_CHECK(hipMemsetAsync(r.ybuf, 0, sizeof(double) * n * Dy, r.st));
         for (int d = 0; d < Dy; ++d) {
-            hipLaunchKernelGGL(k_grid_row_reduce, dim3((unsigned)((r.LR + 3) / 4)), dim3(256), 0, r.st, r.X, r.LC, r.LR,
-                               r.LC, r.gC, r.Rg, Dy, d, n, r.vloc);
-            hipLaunchKernelGGL(k_grid_scatter, dim3((unsigned)((r.LR + 255) / 256)), dim3(256), 0, r.st, r.vloc, r.LR,
-                               r.gR, n, Dy, d, r.ybuf);
+            hipLaunchKernelGGL(k_grid_row_reduce, dim3((unsigned)((r.LR + 3) / 4)), dim3(256), 0, r.st, r.X.p, r.LC, r.LR,
+                               r.LC, r.gC.p, r.Rg.p, Dy, d, n, r.vloc.p);
+            hipLaunchKernelGGL(k_grid_scatter, dim3((unsigned)((r.LR + 255) / 256)), dim3(256), 0, r.st, r.vloc.p, r.LR,
+                               r.gR.p, n, Dy, d, r.ybuf.p);
         }
     }
     // NB: a rank's partial y covers only its local columns, and ranks of one process row write the same global
     // rows: the scatter above must not overwrite -- every rank owns a private ybuf, and the all-reduce sums them.
-    if (int rc = grid_allreduce(g, (size_t)n * Dy, [](GridRank& r) { return r.ybuf; })) return rc;
-    auto col_reduce = [&](GridRank& r, const double* v, int d) {    // vloc[j] = sum_i X_ij * (v ? v[g(i)][d] : X_ij)
-        const long nch = (r.LR + CR_ROWS - 1) / CR_ROWS;
-        hipLaunchKernelGGL(k_grid_col_reduce_part, dim3((unsigned)((r.LC + 63) / 64), (unsigned)nch), dim3(256), 0, r.st, r.X,
-                           r.LC, r.LR, r.LC, r.gR, v, v ? Dy : 1, d, n, r.cpart, nb, Pr, r.pr, Pc, r.pc);
-        hipLaunchKernelGGL(k_grid_col_combine, dim3((unsigned)((r.LC + 255) / 256)), dim3(256), 0, r.st, r.cpart, nch, r.LC,
-                           r.vloc);
-    };
+    if (int rc = grid_allreduce(g, (size_t)n * Dy, [](GridRank& r) -> double* { return r.ybuf; })) return rc;
     for (GridRank& r : g->ranks) {                       // alpha = X^T y (partial over the local rows), diag W
         HIP_CHECK(hipMemsetAsync(r.alpha, 0, sizeof(double) * n * Dy, r.st));
         HIP_CHECK(hipMemsetAsync(r.gvec2, 0, sizeof(double) * n, r.st));
         for (int d = 0; d < Dy; ++d) {
-            col_reduce(r, r.ybuf, d);
-            hipLaunchKernelGGL(k_grid_scatter, dim3((unsigned)((r.LC + 255) / 256)), dim3(256), 0, r.st, r.vloc, r.LC,
-                               r.gC, n, Dy, d, r.alpha);
+            grid_col_reduce(g, r, r.ybuf, d);
+            hipLaunchKernelGGL(k_grid_scatter, dim3((unsigned)((r.LC + 255) / 256)), dim3(256), 0, r.st, r.vloc.p, r.LC,
+                               r.gC.p, n, Dy, d, r.alpha.p);
         }
-        col_reduce(r, nullptr, 0);
-        hipLaunchKernelGGL(k_grid_scatter, dim3((unsigned)((r.LC + 255) / 256)), dim3(256), 0, r.st, r.vloc, r.LC, r.gC,
-                           n, 1, 0, r.gvec2);
+        grid_col_reduce(g, r, nullptr, 0);
+        hipLaunchKernelGGL(k_grid_scatter, dim3((unsigned)((r.LC + 255) / 256)), dim3(256), 0, r.st, r.vloc.p, r.LC, r.gC.p,
+                           n, 1, 0, r.gvec2.p);
     }
-    if (int rc = grid_allreduce(g, (size_t)n * Dy, [](GridRank& r) { return r.alpha; })) return rc;
-    if (int rc = grid_allreduce(g, (size_t)n, [](GridRank& r) { return r.gvec2; })) return rc;
-    if (int rc = grid_allreduce(g, 8, [](GridRank& r) { return r.scal; })) return rc;
-    (void)nblkN;
-    HIP_CHECK(hipEventRecord(g->ev[3], g->st));
-    // ---- gradient reduction on the local tiles ----------------------------------------------------------------
-    const int groups = (D + 31) / 32;
-    std::vector<int> nblocks(g->ranks.size(), 0);
-    for (size_t ri = 0; ri < g->ranks.size(); ++ri) {
-        GridRank& r = g->ranks[ri];
+    if (int rc = grid_allreduce(g, (size_t)n * Dy, [](GridRank& r) -> double* { return r.alpha; })) return rc;
+    if (int rc = grid_allreduce(g, (size_t)n, [](GridRank& r) -> double* { return r.gvec2; })) return rc;
+    return grid_allreduce(g, 8, [](GridRank& r) -> double* { return r.scal; });
+}
+
+// gradient: the reduction over the local dL_dK tiles, summed over ranks
+static int grid_gradient(mi355gp_grid* g, const KernParams& kp) {
+    const int groups = (g->D + 31) / 32;
+    for (GridRank& r : g->ranks) {
         HIP_CHECK(hipMemsetAsync(r.gradOut, 0, sizeof(double) * groups * GP_STRIDE, r.st));
         if (r.nvr <= 0 || r.nvc <= 0) continue;
-        // local dL_dK tiles into A (the factor is no longer needed there?  no: keep L for fetch) -> use CP/RP? too small:
-        // W is consumed in place: G overwrites W after diag W has been taken (fetch of Kinv re-derives from X if needed).
-        hipLaunchKernelGGL(k_grid_dldk, dim3((unsigned)((r.nvc + 255) / 256), (unsigned)r.nvr), dim3(256), 0, r.st, r.W,
-                           r.W, r.LC, r.nvr, r.nvc, r.gR, r.gC, r.alpha, Dy, n);
+        // W is consumed in place: dL/dK overwrites it once diag W has been taken
+        hipLaunchKernelGGL(k_grid_dldk, dim3((unsigned)((r.nvc + 255) / 256), (unsigned)r.nvr), dim3(256), 0, r.st, r.W.p,
+                           r.W.p, r.LC, r.nvr, r.nvc, r.gR.p, r.gC.p, r.alpha.p, g->Dy, g->n);
         const int nbk = grad_generic_num_blocks(r.nvr, r.nvc);
-        nblocks[ri] = nbk;
         launch_grad_generic(r.st, kp, r.XtR, r.LR, r.nvr, r.XtC, r.LC, r.nvc, 0, r.W, r.LC, r.gradPart);
         for (int gi = 0; gi < (kp.ard ? groups : 1); ++gi)
             launch_reduce_partials(r.st, r.gradPart + (long)gi * nbk * GP_STRIDE, nbk, GP_STRIDE,
                                    r.gradOut + (long)gi * GP_STRIDE);
     }
-    if (int rc = grid_allreduce(g, (size_t)groups * GP_STRIDE, [](GridRank& r) { return r.gradOut; })) return rc;
-    HIP_CHECK(hipEventRecord(g->ev[4], g->st));
-    // ---- results (replicated on every rank) -----------------------------------------------------------------------
-    GridRank& r0 = g->ranks[0];
-    std::vector<double> alpha((size_t)n * Dy), dW((size_t)n), R((size_t)n * Dy), sums((size_t)groups * GP_STRIDE);
+    return grid_allreduce(g, (size_t)groups * GP_STRIDE, [](GridRank& r) -> double* { return r.gradOut; });
+}
+
+// what the host reads back from an evaluation (the results are replicated on every rank: rank 0's copy)
+struct GridHost {
+    std::vector<double> alpha, dW, R, sums;
     double scal[8];
     int info = 0;
-    HIP_CHECK(hipMemcpyAsync(alpha.data(), r0.alpha, sizeof(double) * n * Dy, hipMemcpyDeviceToHost, g->st));
-    HIP_CHECK(hipMemcpyAsync(dW.data(), r0.gvec2, sizeof(double) * n, hipMemcpyDeviceToHost, g->st));
-    HIP_CHECK(hipMemcpyAsync(R.data(), r0.Rg, sizeof(double) * n * Dy, hipMemcpyDeviceToHost, g->st));
-    HIP_CHECK(hipMemcpyAsync(sums.data(), r0.gradOut, sizeof(double) * groups * GP_STRIDE, hipMemcpyDeviceToHost, g->st));
-    HIP_CHECK(hipMemcpyAsync(scal, r0.scal, sizeof(double) * 8, hipMemcpyDeviceToHost, g->st));
+    bool redo = false;               // a persistent tile factorisation did not run: the evaluation has to be redone
+};
+
+// collect: copy to the host, agree on info across ranks, check the collective sequences, decide on a redo
+static int grid_collect(mi355gp_grid* g, GridHost& h) {
+    const long n = g->n;
+    const int Dy = g->Dy, groups = (g->D + 31) / 32;
+    GridRank& r0 = g->ranks[0];
+    h.alpha.resize((size_t)n * Dy);
+    h.dW.resize((size_t)n);
+    h.R.resize((size_t)n * Dy);
+    h.sums.resize((size_t)groups * GP_STRIDE);
+    HIP_CHECK(hipMemcpyAsync(h.alpha.data(), r0.alpha, sizeof(double) * n * Dy, hipMemcpyDeviceToHost, g->st));
+    HIP_CHECK(hipMemcpyAsync(h.dW.data(), r0.gvec2, sizeof(double) * n, hipMemcpyDeviceToHost, g->st));
+    HIP_CHECK(hipMemcpyAsync(h.R.data(), r0.Rg, sizeof(double) * n * Dy, hipMemcpyDeviceToHost, g->st));
+    HIP_CHECK(hipMemcpyAsync(h.sums.data(), r0.gradOut, sizeof(double) * groups * GP_STRIDE, hipMemcpyDeviceToHost, g->st));
+    HIP_CHECK(hipMemcpyAsync(h.scal, r0.scal, sizeof(double) * 8, hipMemcpyDeviceToHost, g->st));
     HIP_CHECK(hipStreamSynchronize(g->st));
     // Every rank must take the same branch of the caller's jitter ladder: "some tile failed" travels in the all-reduced
     // scal[1]; the failing column itself is only known to the ranks hosting that tile (others report N).
     for (GridRank& r : g->ranks) {
         int ir = 0;
         HIP_CHECK(hipMemcpy(&ir, r.info_g, sizeof(int), hipMemcpyDeviceToHost));
-        if (ir > 0 && (info == 0 || ir < info)) info = ir;
+        if (ir > 0 && (h.info == 0 || ir < h.info)) h.info = ir;
     }
-    if (scal[1] > 0.0 && info == 0) info = (int)n;
+    if (h.scal[1] > 0.0 && h.info == 0) h.info = (int)n;
     HIP_CHECK(hipGetLastError());
     if (g->check_seq)
         if (int rc = grid_check_sequences(g)) return rc;
-    if (scal[2] > 0.0) {
+    if (h.scal[2] > 0.0) {
         // A persistent factorisation of a diagonal tile was called off (co-residency gate) or aborted on some rank: the count
         // travels in the all-reduced scal[2], so EVERY rank takes this branch and the collectives of the redone evaluation
         // line up.  The tile factorisations stay on the launch-per-step schedule from here on.
@@ -1547,51 +968,88 @@ static int grid_run(mi355gp_grid* g, const PartSpec& pt, const double* noise, in
             r.ws.persist_aborts += 1;
             r.ws.persist = 0;
         }
-        if (attempt == 0)
-            return grid_run(g, pt, noise, noise_len, jit, out_scalars, alpha_out, dtheta_out, diag_out, stage_ms, 1);
-        mi355gp_set_error("mi355gp_grid_exact_inference: a tile factorisation aborted twice");
-        return -6;
+        h.redo = true;
     }
-    if (stage_ms) {
-        for (int i = 0; i < MI355GP_NUM_T; ++i) stage_ms[i] = 0.0;
-        float ms;
-        const int map[4] = {MI355GP_T_KBUILD, MI355GP_T_POTRF, MI355GP_T_SOLVE, MI355GP_T_GRAD};
-        for (int i = 0; i < 4; ++i) {
-            HIP_CHECK(hipEventElapsedTime(&ms, g->ev[i], g->ev[i + 1]));
-            stage_ms[map[i]] = ms;
-        }
-        HIP_CHECK(hipEventElapsedTime(&ms, g->ev[0], g->ev[4]));
-        stage_ms[MI355GP_T_TOTAL] = ms;
+    return 0;
+}
+
+// the caller's outputs of one evaluation
+struct GridOut {
+    double *scalars, *alpha, *dtheta, *diag, *stage_ms;
+};
+
+static int grid_stage_times(mi355gp_grid* g, double* stage_ms) {
+    for (int i = 0; i < MI355GP_NUM_T; ++i) stage_ms[i] = 0.0;
+    float ms;
+    const int map[4] = {MI355GP_T_KBUILD, MI355GP_T_POTRF, MI355GP_T_SOLVE, MI355GP_T_GRAD};
+    for (int i = 0; i < 4; ++i) {
+        HIP_CHECK(hipEventElapsedTime(&ms, g->ev[i], g->ev[i + 1]));
+        stage_ms[map[i]] = ms;
     }
+    HIP_CHECK(hipEventElapsedTime(&ms, g->ev[0], g->ev[4]));
+    stage_ms[MI355GP_T_TOTAL] = ms;
+    return 0;
+}
+
+// the scalars and vectors of the result from what grid_collect read back; returns the LAPACK-style info of a failed factorisation
+static int grid_assemble(mi355gp_grid* g, const PartSpec& pt, const GridHost& h, const GridOut& out) {
+    const long n = g->n;
+    const int Dy = g->Dy;
+    int info = h.info;
     // a failed factorisation poisons logdet/alpha with NaN on every rank: detect it everywhere, not only on the owner
     double datafit = 0.0, alpha2 = 0.0, trw = 0.0;
     for (long i = 0; i < n * Dy; ++i) {
-        datafit += alpha[i] * R[i];
-        alpha2 += alpha[i] * alpha[i];
+        datafit += h.alpha[i] * h.R[i];
+        alpha2 += h.alpha[i] * h.alpha[i];
     }
-    for (long i = 0; i < n; ++i) trw += dW[i];
-    const double logdet = 2.0 * scal[0];
+    for (long i = 0; i < n; ++i) trw += h.dW[i];
+    const double logdet = 2.0 * h.scal[0];
     if (info == 0 && !(std::isfinite(logdet) && std::isfinite(datafit))) info = (int)n;
     if (info > 0) {
         g->have_result = false;
         return info > n ? (int)n : info;
     }
     g->have_result = true;
-    for (int i = 0; i < MI355GP_NUM_OUT; ++i) out_scalars[i] = 0.0;
-    out_scalars[MI355GP_OUT_LML] = 0.5 * (-(double)n * Dy * LOG_2_PI - Dy * logdet - datafit);
-    out_scalars[MI355GP_OUT_LOGDET] = logdet;
-    out_scalars[MI355GP_OUT_DATAFIT] = datafit;
-    out_scalars[MI355GP_OUT_DNOISE] = 0.5 * (alpha2 - Dy * trw);
-    out_scalars[MI355GP_OUT_TRKINV] = trw;
-    if (alpha_out) memcpy(alpha_out, alpha.data(), sizeof(double) * n * Dy);
-    if (diag_out)
+    for (int i = 0; i < MI355GP_NUM_OUT; ++i) out.scalars[i] = 0.0;
+    out.scalars[MI355GP_OUT_LML] = 0.5 * (-(double)n * Dy * LOG_2_PI - Dy * logdet - datafit);
+    out.scalars[MI355GP_OUT_LOGDET] = logdet;
+    out.scalars[MI355GP_OUT_DATAFIT] = datafit;
+    out.scalars[MI355GP_OUT_DNOISE] = 0.5 * (alpha2 - Dy * trw);
+    out.scalars[MI355GP_OUT_TRKINV] = trw;
+    if (out.alpha) memcpy(out.alpha, h.alpha.data(), sizeof(double) * n * Dy);
+    if (out.diag)
         for (long i = 0; i < n; ++i) {
             double a2 = 0.0;
-            for (int d = 0; d < Dy; ++d) a2 += alpha[i * Dy + d] * alpha[i * Dy + d];
-            diag_out[i] = 0.5 * (a2 - Dy * dW[i]);
+            for (int d = 0; d < Dy; ++d) a2 += h.alpha[i * Dy + d] * h.alpha[i * Dy + d];
+            out.diag[i] = 0.5 * (a2 - Dy * h.dW[i]);
         }
-    if (dtheta_out) part_dtheta(pt, sums.data(), nullptr, dtheta_out);
+    if (out.dtheta) part_dtheta(pt, h.sums.data(), nullptr, out.dtheta);
     return 0;
+}
+
+// The driver.  ev[0..4] bracket the four timed stages on st; a pass that met a called-off persistent tile factorisation is
+// redone once on the launch-per-step schedule.
+static int grid_run(mi355gp_grid* g, const PartSpec& pt, const double* noise, int64_t noise_len, double jit, const GridOut& out) {
+    for (int attempt = 0; attempt < 2; ++attempt) {
+        if (int rc = grid_prepare(g)) return rc;
+        HIP_CHECK(hipEventRecord(g->ev[0], g->st));
+        if (int rc = grid_build_K(g, pt, noise, noise_len, jit)) return rc;
+        HIP_CHECK(hipEventRecord(g->ev[1], g->st));
+        if (int rc = grid_factor_invert(g)) return rc;
+        HIP_CHECK(hipEventRecord(g->ev[2], g->st));
+        if (int rc = grid_solve(g)) return rc;
+        HIP_CHECK(hipEventRecord(g->ev[3], g->st));
+        if (int rc = grid_gradient(g, pt.kp)) return rc;
+        HIP_CHECK(hipEventRecord(g->ev[4], g->st));
+        GridHost h;
+        if (int rc = grid_collect(g, h)) return rc;
+        if (h.redo) continue;
+        if (out.stage_ms)
+            if (int rc = grid_stage_times(g, out.stage_ms)) return rc;
+        return grid_assemble(g, pt, h, out);
+    }
+    mi355gp_set_error("mi355gp_grid_exact_inference: a tile factorisation aborted twice");
+    return -6;
 }
 
 extern "C" {
@@ -1621,8 +1079,8 @@ int mi355gp_grid_exact_inference(mi355gp_grid* g, int kind, int ard, const doubl
     PartSpec pt;
     if (int rc = parse_part(mi355gp_part{kind, ard, 0, nullptr, theta, 0}, g->D, KS_STATIONARY, "grid path", &pt)) return rc;
     HIP_CHECK(hipSetDevice(g->device));
-    return grid_run(g, pt, noise, noise_len, jitter + extra_jitter, out_scalars, alpha_out, dtheta_out,
-                    diag_dLdK_out, stage_ms);
+    return grid_run(g, pt, noise, noise_len, jitter + extra_jitter,
+                    GridOut{out_scalars, alpha_out, dtheta_out, diag_dLdK_out, stage_ms});
 }
 
 int mi355gp_grid_set_option(mi355gp_grid* g, int option, int value) {
@@ -1646,23 +1104,6 @@ int mi355gp_grid_get_option(mi355gp_grid* g, int option, int* value) {
     ARG_CHECK(g && value && option >= 0 && option < MI355GP_GRID_OPT_NUM, "mi355gp_grid_get_option: unknown option");
     *value = option == MI355GP_GRID_OPT_LOOKAHEAD ? g->lookahead : option == MI355GP_GRID_OPT_G ? g->G
              : option == MI355GP_GRID_OPT_CHECK_SEQ ? g->check_seq : g->GW;
-    return 0;
-}
-
-// Collective log of logical rank `rank` of this process (loopback: any rank of the grid; one rank per process: its own, rank is
-// ignored) for the LAST evaluation: out9 = [count world, row, column, then per communicator the hash as (high 32 bits, low 32 bits)].
-int mi355gp_grid_coll_log(mi355gp_grid* g, int rank, double* out9) {
-    ARG_CHECK(g && out9 && !g->single, "mi355gp_grid_coll_log: not available on the degenerate 1 x 1 grid");
-    const GridRank* r = &g->ranks[0];
-    if (g->loopback) {
-        ARG_CHECK(rank >= 0 && rank < (int)g->ranks.size(), "mi355gp_grid_coll_log: bad rank");
-        r = &g->ranks[(size_t)rank];
-    }
-    for (int c = 0; c < 3; ++c) {
-        out9[c] = (double)r->coll_count[c];
-        out9[3 + 2 * c] = (double)(r->coll_hash[c] >> 32);
-        out9[4 + 2 * c] = (double)(r->coll_hash[c] & 0xffffffffull);
-    }
     return 0;
 }
 

@@ -342,7 +342,7 @@ void launch_symv_lower(hipStream_t st, const double* K, long npad, long n, const
 void launch_laplace_dLdK(hipStream_t st, const double* Binv, long npad, long n, const double* sw, const double* a,
                          const double* u, double* G);
 
-// ---- grid.hip : RCCL (dlopen'ed) world communicator for row-sharded paths ---------------------------------------
+// ---- grid_comm.hip : RCCL (dlopen'ed) world communicator for row-sharded paths ----------------------------------
 int rccl_comm_create(int rank, int world, const void* id128, void** comm);
 int rccl_allreduce_sum(void* comm, double* buf, size_t count, hipStream_t st);
 void rccl_comm_destroy(void* comm);

@@ -102,6 +102,10 @@ def test_two_level_blocking_options_on_a_1x1_grid_with_the_generic_code():
         _generic_1x1(False)
 
 
+BLOCKING_OPTIONS = [(1, 1, 1), (1, 0, 0), (2, 0, 1), (2, 3, 1), (3, 2, 0), (4, 0, 1), (4, 4, 1), (5, 1, 1), (64, 0, 1),
+                    (64, 7, 0)]      # (G, GW, lookahead); tools/grid_bits.py walks the same list
+
+
 def _blocking_options_case(Pr, Pc, nb, N):
     kind, ARD, D = "matern52", True, 4
     X, Y = O.synthetic(N, D, seed=N + 3, Dy=2)
@@ -112,8 +116,7 @@ def _blocking_options_case(Pr, Pc, nb, N):
         assert g.get_option("G") == 1 and g.get_option("GW") == 4 and g.get_option("lookahead") == 1
         g.set_data(X, Y)
         th = L.theta_vec(var, ls, ARD, D)
-        for Gs, GW, la in [(1, 1, 1), (1, 0, 0), (2, 0, 1), (2, 3, 1), (3, 2, 0), (4, 0, 1), (4, 4, 1), (5, 1, 1), (64, 0, 1),
-                           (64, 7, 0)]:
+        for Gs, GW, la in BLOCKING_OPTIONS:
             g.set_option("G", Gs)
             g.set_option("GW", GW)
             g.set_option("lookahead", la)
@@ -129,6 +132,49 @@ def _blocking_options_case(Pr, Pc, nb, N):
             assert np.abs(Xg @ ref["L"] - np.eye(N)).max() <= 1e-9
         g.set_option("G", -1)
         assert g.get_option("G") == 1
+    finally:
+        g.close()
+
+
+def test_set_data_twice_on_one_context_matches_a_fresh_context():
+    """set_data on a context that already holds data replaces every rank by a fresh one that keeps its identity: smaller data
+    (fewer tiles, T = 3 does not divide over Pr = 2), then a changed G and larger data (the L-panel ring is sized anew).  After
+    each step the evaluation meets the oracle and equals, byte for byte, that of a fresh context given the same data and
+    options.  (The extra evaluation straight after set_option re-sizes the ring inside the evaluation.)"""
+    kind, ARD, nb = "matern52", True, 128
+    g = G.GridContext.loopback(2, 2, nb)
+
+    def evaluate(ctx, X, Y, th, noise):
+        info, res = ctx.exact_inference(kind, ARD, th, noise, want_diag=True)
+        assert info == 0
+        return res, ctx.fetch(G.FETCH_L)
+
+    def step(N, D, Dy, Gs, new_data=True):
+        X, Y = O.synthetic(N, D, seed=N + 2, Dy=Dy)
+        var, ls, noise = O.default_theta(D, ARD)
+        th = L.theta_vec(var, ls, ARD, D)
+        if new_data:
+            g.set_data(X, Y)
+        res, Lg = evaluate(g, X, Y, th, noise)
+        _check(res, O.parameters_changed(kind, X, Y, var, ls, ARD, noise))
+        f = G.GridContext.loopback(2, 2, nb)
+        try:
+            f.set_option("G", Gs)
+            f.set_data(X, Y)
+            fres, fL = evaluate(f, X, Y, th, noise)
+        finally:
+            f.close()
+        assert res["lml"] == fres["lml"]
+        for k in ("alpha", "dtheta", "diag_dL_dK"):
+            assert res[k].tobytes() == fres[k].tobytes(), (N, k)
+        assert Lg.tobytes() == fL.tobytes(), N
+
+    try:
+        step(700, 4, 1, 1)
+        step(300, 3, 2, 1)
+        g.set_option("G", 2)
+        step(300, 3, 2, 2, new_data=False)
+        step(900, 4, 1, 2)
     finally:
         g.close()
 
