@@ -182,6 +182,8 @@ def lib():
     L.mi355gp_svgp_forward.argtypes = [vp, ci, ctypes.POINTER(Part), _dp, i64, _dp, _dp, ci, cd, _dp, _dp, _dp, _c_dp]
     L.mi355gp_svgp_backward.argtypes = [vp, _dp, _dp, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp]
     L.mi355gp_svgp_predict.argtypes = [vp, ci, ctypes.POINTER(Part), _c_dp, i64, ci, _c_dp, _c_dp, _c_dp, _c_dp]
+    L.mi355gp_pep_inference.argtypes = [vp, ci, ctypes.POINTER(Part), _dp, i64, cd, cd, cd, _dp, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp]
+    L.mi355gp_pep_check_sigma.argtypes = [_dp, i64, i64, cd, cd]
     L.mi355gp_sparse_attach_comm.argtypes = [vp, ci, ci, ctypes.c_char_p]
     L.mi355gp_rbf_psi.argtypes = [ci, cd, _dp, ci, _dp, i64, _dp, _dp, i64, ci, _c_dp, _c_dp, _c_dp]
     L.mi355gp_rbf_psi_grad.argtypes = [ci, cd, _dp, ci, _dp, i64, _dp, _dp, i64, ci, _c_dp, _c_dp, _c_dp, _c_dp, _dp, _dp, _dp,
@@ -213,7 +215,7 @@ def lib():
                  "laplace_implicit", "laplace_predict", "ep_recompute", "ep_sweep", "rbf_psi", "rbf_psi_grad",
                  "sparse_set_input_variance", "vardtc_inference_uncertain", "svgp_forward", "svgp_backward",
                  "svgp_predict", "sparse_set_inputs", "sparse_predict_uncertain",
-                 "sparse_get_predict_ms"):
+                 "sparse_get_predict_ms", "pep_inference", "pep_check_sigma"):
         getattr(L, "mi355gp_" + name).restype = ci
     _lib = L
     return L
@@ -239,7 +241,8 @@ EXPORTED = ("mi355gp_last_error", "mi355gp_version", "mi355gp_device_count", "mi
             "mi355gp_laplace_implicit", "mi355gp_laplace_predict", "mi355gp_ep_recompute", "mi355gp_ep_sweep",
             "mi355gp_rbf_psi", "mi355gp_rbf_psi_grad", "mi355gp_sparse_set_input_variance",
             "mi355gp_vardtc_inference_uncertain", "mi355gp_svgp_forward", "mi355gp_svgp_backward", "mi355gp_svgp_predict",
-            "mi355gp_sparse_set_inputs", "mi355gp_sparse_predict_uncertain", "mi355gp_sparse_get_predict_ms")
+            "mi355gp_sparse_set_inputs", "mi355gp_sparse_predict_uncertain", "mi355gp_sparse_get_predict_ms",
+            "mi355gp_pep_inference", "mi355gp_pep_check_sigma")
 
 
 # mi355gp_set_option / mi355gp_get_option ids (include/mi355gp.h, MI355GP_OPT_*)
@@ -692,6 +695,28 @@ class SparseContext(object):
         out = np.empty((nrows, self.M))
         check(lib().mi355gp_sparse_fetch_dLdKnm(self._h, int(row0), int(nrows), out), "mi355gp_sparse_fetch_dLdKnm")
         return out
+
+    # ---- PEP / FITC (pep.hip) ---------------------------------------------------------------------------------------------
+    def pep(self, specs, Z, noise_variance, alpha, jitter, want_stage_ms=False):
+        """One `PEP.inference` (alpha = 1: `FITC.inference`) with one noise variance; `jitter` is the whole term on Kmm's
+        diagonal.  (info, dict(lml, dnoise (= dL_dthetaL), dL_dR (N), dtheta (concatenated), dZ, woodbury_vector[, stage_ms]))"""
+        arr, keep, ntheta = make_parts(specs)
+        Z = f64(Z)
+        self.M = Z.shape[0]
+        assert Z.shape[1] == self.D
+        out = np.zeros(NUM_OUT)
+        dtheta = np.zeros(ntheta)
+        dZ = np.zeros((self.M, self.D))
+        wv = np.zeros((self.M, 1))
+        dR = np.zeros(self.N)
+        ms = np.zeros(4) if want_stage_ms else None
+        rc = check(lib().mi355gp_pep_inference(self._h, len(specs), arr, Z, self.M, float(noise_variance), float(alpha),
+                                               float(jitter), out, _opt(dtheta), _opt(dZ), _opt(wv), _opt(dR), _opt(ms)),
+                   "mi355gp_pep_inference")
+        res = dict(lml=out[0], dnoise=out[1], sum_dL_dR=out[2], dL_dR=dR, dtheta=dtheta, dZ=dZ, woodbury_vector=wv)
+        if ms is not None:
+            res["stage_ms"] = dict(pass1=ms[0], mxm=ms[1], pass2=ms[2], total=ms[3])
+        return rc, res
 
     # ---- SVGP: forward -> the likelihood's quadrature on the host -> backward (svgp.hip) ------------------------------------
     def svgp_forward(self, specs, Z, q_mean, q_chol, extra_jitter=0.0, want_stage_ms=False):

@@ -205,6 +205,7 @@ bool sharded(const mi355gp_sparse* s) { return s->comm != nullptr || s->loop != 
 
 static void free_m(mi355gp_sparse* s) {
     svgp_release(s);
+    pep_release(s);
     s->parts.clear();
     double** ptrs[] = {&s->dZ, &s->zero1, &s->Lm, &s->Xm, &s->Tm, &s->psi2part, &s->psi2, &s->Amat,
                        &s->LB, &s->XB, &s->Bi, &s->P, &s->E, &s->T1, &s->Q2, &s->dLdKmm, &s->Winv, &s->psi1Y, &s->vecA,
@@ -681,7 +682,8 @@ int sparse_open(mi355gp_sparse* s, int nparts, const mi355gp_part* parts, int64_
     HIP_CHECK(hipSetDevice(s->device));
     if (M != s->m)
         if (int rc = alloc_m(s, M)) return rc;
-    s->have_result = s->winv_ok = s->svgp_result = false;
+    s->have_result = s->winv_ok = s->svgp_result = s->pep_result = false;
+    s->kmm_jitter = 1e-8;
     s->h_info[0] = s->h_info[1] = 0;
     return prepare_sparse_parts(s, nparts, parts);
 }
@@ -1425,8 +1427,11 @@ int mi355gp_sparse_fetch(mi355gp_sparse* s, int which, double* out) {
         launch_extract(st, s->Lm, mp, mp, 0, nullptr, 0, s->E, 0);
         src = s->E;
     } else if (which == 3) {
-        build_kmm(s, s->E, s->T1, 1e-8, /*lower_only=*/0);
+        build_kmm(s, s->E, s->T1, s->kmm_jitter, /*lower_only=*/0);
         src = s->E;
+    } else if ((which == 4 || which == 5) && s->pep_result) {
+        mi355gp_set_error("mi355gp_sparse_fetch: matrix id %d (psi2 / dL_dpsi2) does not exist for a PEP / FITC result", which);
+        return -1;
     } else if (which == 4) src = s->psi2;
     else if (which == 5) src = s->Q2;
     else {
@@ -1449,6 +1454,7 @@ int mi355gp_sparse_fetch_dLdKnm(mi355gp_sparse* s, int64_t row0, int64_t nrows, 
     ARG_CHECK(!s->uncertain_result, "mi355gp_sparse_fetch_dLdKnm: the last call had uncertain inputs (dL_dpsi1 / dL_dpsi2 take dL_dKnm's place)");
     HIP_CHECK(hipSetDevice(s->device));
     EngineShared gate(s->device);
+    if (s->pep_result) return pep_fetch_dLdKnm(s, row0, nrows, out);      // (pep.py:81-84: PEP's rows, formed by pep.hip)
     hipStream_t st = s->st;
     const long m = s->m, mp = s->mp, rc = nrows, rcp = round_up(rc, NB);
     if (int rc2 = sparse_cross_rows(s, row0, rc, 0, rcp, nullptr)) return rc2;

@@ -9,6 +9,7 @@
 
 struct LoopGroup;              // the loopback rendezvous of the row-sharded mode (sparse.hip)
 struct SvgpState;              // svgp.hip
+struct PepState;               // pep.hip
 
 struct SPart : DevicePart {
     DevBuf XtZ, XtC, HX, HZ, gradNM, gradMM;
@@ -60,6 +61,12 @@ struct mi355gp_sparse {
     // predict entry points describe VarDTC's result and refuse then, as fetch_dLdKnm does after an uncertain-input call)
     SvgpState* svgp = nullptr;
     bool svgp_result = false;
+    // PEP / FITC (pep.hip): its chunk buffers, and whether the context's latest result is a PEP one.  It lies where VarDTC's
+    // does (vvec, Winv, dLdKmm, Lm), so fetch and predict serve it unchanged; dL_dKnm's rows are formed by pep.hip, psi2 and
+    // dL_dpsi2 do not exist.  kmm_jitter: what the call that left the result added to Kmm's diagonal (mi355gp_sparse_fetch, Kmm).
+    PepState* pep = nullptr;
+    bool pep_result = false;
+    double kmm_jitter = 1e-8;
 };
 
 // ---- sparse.hip ----------------------------------------------------------------------------------------------------
@@ -109,3 +116,6 @@ int sparse_newpoints_var(mi355gp_sparse* s, NewPoints* q, const double* Winv, bo
 }
 // ---- svgp.hip ------------------------------------------------------------------------------------------------------
 void svgp_release(mi355gp_sparse* s);      // frees the SVGP state (M-dependent: called by free_m)
+// ---- pep.hip -------------------------------------------------------------------------------------------------------
+void pep_release(mi355gp_sparse* s);       // frees the PEP state (M-dependent: called by free_m)
+int pep_fetch_dLdKnm(mi355gp_sparse* s, long row0, long nrows, double* out);   // the PEP half of mi355gp_sparse_fetch_dLdKnm

@@ -459,8 +459,8 @@ int mi355gp_sparse_attach_comm(mi355gp_sparse* s, int rank, int world, const voi
 /* The same mode over the LOOPBACK transport: `world` contexts of ONE process (one host thread each) that name the same
  * group_key rendezvous for every exchange step and are summed in rank order -- world > 1 on a single GPU (tests). */
 int mi355gp_sparse_attach_loopback(mi355gp_sparse* s, int rank, int world, int group_key);
-/* M x M results of the last call: 0 dL_dKmm, 1 woodbury_inv (var_dtc.py:206-210), 2 Lm, 3 Kmm (+1e-8 I), 4 psi2,
- * 5 dL_dpsi2_beta (var_dtc.py:220) */
+/* M x M results of the last call: 0 dL_dKmm, 1 woodbury_inv (var_dtc.py:206-210), 2 Lm, 3 Kmm (+1e-8 I; after
+ * mi355gp_pep_inference: + that call's jitter), 4 psi2, 5 dL_dpsi2_beta (var_dtc.py:220; 4 and 5: VarDTC results only) */
 int mi355gp_sparse_fetch(mi355gp_sparse* s, int which, double* out);
 /* Launch timing of the two MFMA kernels of the last mi355gp_vardtc_inference_sum call (hipEvent pairs on the launching
  * stream, recorded on every call): out6 = [T = Kfu dL_dpsi2 GEMM: summed ms, algorithmic flops (2 rows M^2), launches,
@@ -474,7 +474,8 @@ int mi355gp_sparse_get_profile(mi355gp_sparse* s, double* out6);
  * q(u_d) = N(m_d, L_d L_d^T) for d < L latent functions, 1 <= L <= 16; M inducing points.  Accepted parts: those of
  * mi355gp_vardtc_inference_sum.  A row-sharded context and a context holding input variances are refused.  All reductions run
  * in a fixed order: two sessions on the same inputs give the same bytes.  After an SVGP call mi355gp_sparse_fetch,
- * mi355gp_sparse_fetch_dLdKnm and mi355gp_sparse_predict (they describe VarDTC's result) are refused until the next VarDTC call.
+ * mi355gp_sparse_fetch_dLdKnm and mi355gp_sparse_predict (they describe VarDTC's result) are refused until the next VarDTC or
+ * PEP call.
  *
  * mi355gp_svgp_forward replaces svgp.py:12-56: Kmm = K(Z) with NO 1e-8 term (svgp.py:37, unlike var_dtc.py:93), Lm, Kmm^-1,
  * S_d, S_d^-1, Kmm^-1 m, the KL term (:54-56), and over the context's row chunks A^T = K(X, Z) Kmm^-1, mu = A^T m,
@@ -498,6 +499,34 @@ int mi355gp_svgp_backward(mi355gp_sparse* s, const double* dF_dmu, const double*
  *   wv_out (M x L) / winv_out (L x M x M) may be NULL: the Woodbury quantities themselves; Mn == 0 fetches only them. */
 int mi355gp_svgp_predict(mi355gp_sparse* s, int nparts, const mi355gp_part* parts, const double* Xnew, int64_t Mn, int full_cov,
                          double* mu_out, double* var_out, double* wv_out, double* winv_out);
+
+/* ---- FITC and power EP (PEP) on the sparse context: the sparse methods for a Gaussian likelihood beside VarDTC -------------
+ * One PEP.inference (inference/latent_function_inference/pep.py:23-93; Bui, Yan and Turner, arXiv:1605.07066) and the
+ * certain-input branch of SparseGP._update_gradients (core/sparse_gp.py:108-119).  alpha = 1 is FITC.inference
+ * (fitc.py:21-88, Snelson and Ghahramani: the same arithmetic line for line); alpha -> 0 approaches VarDTC.
+ *   sigma*_n = noise + alpha (Kdiag_n - |Lm^-1 k_n|^2), beta* = 1 / sigma* (pep.py:44-46), A = I + Lm^-1 Kuf diag(beta*) Kfu Lm^-T
+ *   (:49), b, v, P (:53-59), the log marginal (:64-68), dL_dR (:70-72), dL_dKmm (:75-78), dL_dKnm (:81-84), dL_dKdiag = alpha dL_dR
+ *   and dL_dthetaL = sum dL_dR + (1 - alpha) / alpha N / (2 noise) (:86-88).
+ * Arguments as mi355gp_vardtc_inference_sum, with ONE noise variance and
+ *   alpha in (0, 1];  jitter: the WHOLE term added to Kmm's diagonal, the classes' const_jitter = 1e-6 (pep.py:17, fitc.py:17;
+ *   not VarDTC's 1e-8) plus the jitchol ladder's term;
+ *   out_scalars[MI355GP_NUM_OUT]: [0] log marginal, [1] dL_dthetaL, [2] sum dL_dR, [3] |b|^2, [4] sum log diag LA, [5] sum log beta*;
+ *   dtheta_out (concatenated over the parts), dZ_out (M x D), wv_out (M), dLdR_out (N: dL_dKdiag = alpha times it) and
+ *   stage_ms[4] (pass 1, M x M, pass 2, total; HIP events on the launching stream) may be NULL.
+ * Accepted parts: those of mi355gp_vardtc_inference_sum.  Refused with an error that names it: alpha outside (0, 1], more than
+ * one output column (the reference's v.reshape(-1, 1)), a row-sharded context, a context holding input variances, and a
+ * sigma*_n that is not positive -- rounding can do that when the noise is tiny and a point sits on an inducing input; the
+ * check runs on the host between the passes (mi355gp_pep_check_sigma) and names the row.  Returns LAPACK-style info > 0 when Kmm
+ * or A is not positive definite (the caller raises the jitter).  Every reduction has a fixed order: two calls give the same bytes.
+ * The result lies where VarDTC's does: mi355gp_sparse_predict and mi355gp_sparse_fetch (0 dL_dKmm, 1 woodbury_inv = Kmm^-1 - P,
+ * 2 Lm, 3 Kmm with THIS call's jitter; 4 and 5 do not exist and are refused) work on it unchanged, and
+ * mi355gp_sparse_fetch_dLdKnm serves PEP's rows (pep.py:81-84).  A later VarDTC or SVGP call replaces it, and the reverse. */
+int mi355gp_pep_inference(mi355gp_sparse* s, int nparts, const mi355gp_part* parts, const double* Z, int64_t M,
+                          double noise_variance, double alpha, double jitter, double* out_scalars, double* dtheta_out,
+                          double* dZ_out, double* wv_out, double* dLdR_out, double* stage_ms);
+/* The host's check of sigma*_n (pep.py:44) for rows [row0, row0 + n): 0, or -8 and an error naming the first row whose
+ * sigma* is not positive (NaN included).  Reads no device state; noise_variance and alpha only word the message. */
+int mi355gp_pep_check_sigma(const double* sigma, int64_t n, int64_t row0, double noise_variance, double alpha);
 
 /* ---- psi-statistics of the RBF kernel for Gaussian inputs q(x_n) = N(mu_n, diag S_n) (kern/src/psi_comp/rbf_psi_comp.py) ----
  * Stateless, like mi355gp_kern_K.  lengthscale: D entries if ard, else one.  Z: M x D, mu / S: N x D row-major; every S
