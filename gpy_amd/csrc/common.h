@@ -91,6 +91,9 @@ typedef DevArr<double> DevBuf;
 
 static inline int64_t round_up(int64_t n, int64_t m) { return (n + m - 1) / m * m; }
 
+// a helper shared between translation units that is no part of the library's dynamic symbol list
+#define MI355GP_LOCAL __attribute__((visibility("hidden")))
+
 // ---- environment switches ----------------------------------------------------------------------------------------------
 // The PRODUCT library (libmi355gp.so) reads nine variables, all through PRODUCT_ENV: the transport of the multi-process
 // mode (TRANSPORT, IPC_HOST, IPC_TIMEOUT_S), the collective-sequence self-check of the grid mode (GRID_CHECK_SEQ) and five

@@ -1,4 +1,4 @@
-// ctx.h -- the exact-GP context (mi355gp_ctx) and the helpers of api.hip that laplace.hip shares with it.
+// ctx.h -- the exact-GP context (mi355gp_ctx) and the helpers of api.hip that exact.hip, predict.hip and laplace.hip share.
 #pragma once
 #include <string>
 #include <vector>
@@ -62,6 +62,9 @@ struct mi355gp_ctx {
 };
 
 // api.hip
+MI355GP_LOCAL void apply_options(mi355gp_ctx* c);   // (re)applies the option overrides to the factorisation workspace
+MI355GP_LOCAL void drop_graph(mi355gp_ctx* c);      // forgets the captured factorisation region (the next graphable call runs plain, the one after captures)
+MI355GP_LOCAL void free_data(mi355gp_ctx* c);       // everything set_data allocated, the parts, the graph and a Laplace session
 int ctx_prepare_parts(mi355gp_ctx* c, int nparts, const mi355gp_part* parts);   // validates the part list, (re)builds the per-part device inputs
 void ctx_scale_parts(mi355gp_ctx* c);                                            // scaled training inputs of every part, on the context's stream
 Resident<mi355gp_ctx::Part> ctx_training_points(const mi355gp_ctx* c);

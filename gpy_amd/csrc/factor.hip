@@ -342,7 +342,7 @@ static void early_inverse(hipStream_t sq, double* A, long npad, int h, FactorWs*
 }
 
 // Leading tiles whose inverse (+ T21) goes on the side stream underneath the PERSISTENT launch: the largest power of two <= 2 nt / 3,
-// 0 = not this time.  (The hipGraph replay of the factorisation region is not used then -- api.hip asks here: measured at
+// 0 = not this time.  (The hipGraph replay of the factorisation region is not used then -- run_factor_region of exact.hip asks here: measured at
 // N = 4096, replay + early inverse 3.73 ms per evaluation, replay alone 3.35, plain launches + early inverse 3.05.)
 int persist_early_h(long npad, const FactorWs* ws) {
     const int ntl = (int)(npad / NB);
@@ -359,6 +359,30 @@ int persist_early_h(long npad, const FactorWs* ws) {
     if (two_thirds) while (6 * h <= 2 * ntl) h *= 2;
     else while (4 * h <= ntl) h *= 2;
     return h;
+}
+
+// Schedule of a small factorisation by measurement (FactorWs::persist_auto).  ms: potrf .. lauum of one evaluation that ran on plain
+// launches, device time; nt: its tiles.  Two warm samples of the persistent schedule (from the fourth evaluation on), then THREE
+// evaluations on launches (potrf_device counts sched_force_steps down) -- the first untimed (that workspace's first run on that
+// schedule pays one-time function attributes and cold caches), the next two timed; the minima are compared.  One sample each on
+// a shared GPU used to pin the wrong schedule.
+void calibrate_schedule(FactorWs& w, float ms, int nt) {
+    if (w.sched_state == 0 && w.persist_used && w.evals_done >= 3) {     // persistent launch + early inverse, warm
+        w.sched_ms_persist = (w.sched_np == 0 || ms < w.sched_ms_persist) ? ms : w.sched_ms_persist;
+        if (++w.sched_np >= 2) {
+            w.sched_state = 1;
+            w.sched_force_steps = 3;
+            w.sched_ns = 0;
+        }
+    } else if (w.sched_state == 1 && !w.persist_used) {
+        if (w.sched_ns++ > 0) w.sched_ms_steps = (w.sched_ns == 2 || ms < w.sched_ms_steps) ? ms : w.sched_ms_steps;
+        if (w.sched_ns >= 3) {
+            w.sched_state = 2;
+            w.sched_force_steps = 0;
+            w.persist_auto_off = (w.sched_ms_steps < 0.97f * w.sched_ms_persist) ? 1 : 0;
+            if (nt >= 21) persist_box_verdict(w.persist_auto_off);   // one vote for the process-wide verdict
+        }
+    }
 }
 
 // Two-level right-looking Cholesky with one panel of look-ahead (default).  Outer panels of NBO = 512 columns keep

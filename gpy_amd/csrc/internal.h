@@ -182,6 +182,23 @@ struct EngineShared {
 int factor_engine(int device, hipStream_t* main, hipStream_t* panel, hipStream_t* tri, hipStream_t* tri_half = nullptr);
 int factor_ws_alloc(FactorWs* ws, long npad);
 void factor_ws_free(FactorWs* ws);
+// A FactorWs and N events for the length of one standalone call: released on every return path
+template <int N>
+struct MI355GP_LOCAL WorkspaceGuard {
+    FactorWs ws;
+    hipEvent_t ev[N] = {};
+    ~WorkspaceGuard() {
+        factor_ws_free(&ws);
+        for (hipEvent_t e : ev)
+            if (e) (void)hipEventDestroy(e);
+    }
+    int create_events() {
+        for (hipEvent_t& e : ev) HIP_CHECK(hipEventCreate(&e));
+        return 0;
+    }
+};
+// one sample of the schedule calibration of a workspace whose owner times its evaluations (FactorWs::persist_auto)
+MI355GP_LOCAL void calibrate_schedule(FactorWs& w, float ms, int nt);
 // A (npad x npad, ld = npad, lower) -> L in place.  Asynchronous; on return all work is ordered before later work on `st`.
 void potrf_device(hipStream_t st, double* A, long npad, FactorWs* ws);
 // X = L^-1 (into X, using T as scratch), asynchronous.
@@ -233,6 +250,14 @@ void launch_scale_inputs(hipStream_t st, const double* X, long n, int D, const d
 void launch_kbuild_sym(hipStream_t st, KernParams kp, const double* Xt, long ldx, long n, long npad, double* A,
                        const double* noise, long noise_len, double jit, int lower_only, int add_diag,
                        int accumulate = 0, const double* mul = nullptr);
+// dense.hip: the synthetic SPD matrix of the bench / debug factorisation routines, resident in HBM -- the RBF covariance
+// (D = 4, 1 / lengthscale = 0.7) of N pseudo-random points (LCG, fixed seed) + (0.1 + 1e-8) I
+struct MI355GP_LOCAL SyntheticSpd {
+    long n = 0, np = 0;
+    DevBuf dX, dXt, dIl, dNoise;
+    int init(hipStream_t st, long N);               // points and noise uploaded, the input scaling enqueued on st
+    void build(hipStream_t st, double* A) const;    // enqueues the lower tiles of the matrix into A (np x np)
+};
 void launch_kbuild_cross(hipStream_t st, KernParams kp, const double* Xt1, long ld1, long n, const double* Xt2,
                          long ld2, long m, double* Kout, long ldk, int accumulate = 0, int diag_same = 0,
                          const double* mul = nullptr);

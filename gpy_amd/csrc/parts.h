@@ -437,6 +437,46 @@ static void gradx_mlp(const double* x, long rows, int D, const std::vector<doubl
         for (int q = 0; q < D; ++q) put(i, q, il[(size_t)q] * (h[q] - il[(size_t)q] * x[i * D + q] * r));
     }
 }
+// The device reductions of one part's dK/dX and their host finish.  W (ld ldw): the weights, rows = the nr points xr that are
+// summed over, columns = the n points xc the gradient is taken at (both scaled for the part, dimension-major; Linear does not
+// read xc); StdPeriodic alone reads W transposed unless s.wt.  x_host: the unscaled points of xc (n x D).  put(row, q, g)
+// receives every element.  Synchronises st.
+struct GradXScratch {
+    double* H;                         // H = W * (dK/dr)/r (may be W itself), ld ldh
+    long ldh;
+    double *part, *col, *hx;           // theta partials (unused here), column partials 64 x n x (D + 1), their sum n x (D + 1)
+    double* host;                      // n x (D + 1) on the host
+    int wt;                            // StdPeriodic: W is indexed [xr point][xc point] like the other kinds' weights
+};
+template <class Part, class Put>
+static int part_gradients_X(hipStream_t st, const Part& pt, const double* W, long ldw, const double* xr, long ldr, long nr,
+                            const double* xc, long ldc, long n, const double* x_host, int D, const GradXScratch& s, Put put) {
+    auto fetch = [&](long cnt) -> int {
+        HIP_CHECK(hipMemcpyAsync(s.host, s.hx, sizeof(double) * cnt, hipMemcpyDeviceToHost, st));
+        HIP_CHECK(hipStreamSynchronize(st));
+        return 0;
+    };
+    if (pt.linear()) {
+        // dK(x_i, x2_j)/dx_iq = variance_q x2_jq (linear.py:108-114): the column reduction W^T x2~ of the weights themselves
+        const int ns = launch_colreduce_multi(st, W, ldw, nr, n, xr, 1, ldr, D, 0, s.col);
+        launch_sum_splits(st, s.col, n * D, ns, 0, s.hx);
+        if (int rc = fetch(n * D)) return rc;
+        gradx_linear(pt.inv_ls, n, D, s.host, put);
+    } else if (pt.kp.kind == MI355GP_STDPERIODIC) {             // not a function of r: the row reduction instead of H
+        launch_periodic_gradx(st, pt.kp, xc, ldc, n, xr, ldr, nr, W, ldw, s.wt, s.hx);
+        if (int rc = fetch(n * D)) return rc;
+        gradx_periodic(pt.pw, n, D, s.host, put);
+    } else {
+        launch_grad_generic(st, pt.kp, xr, ldr, nr, xc, ldc, n, 0, W, ldw, s.part, s.H, s.ldh);
+        const int ns = launch_colreduce_multi(st, s.H, s.ldh, nr, n, xr, 1, ldr, D, 1, s.col);
+        launch_sum_splits(st, s.col, n * (D + 1), ns, 0, s.hx);
+        if (int rc = fetch(n * (D + 1))) return rc;
+        // MLP: H = c of the weights (k_grad_dot); dK/dx from H^T [x2~ | 1] (mlp.py:124-130)
+        if (pt.mlp()) gradx_mlp(x_host, n, D, pt.inv_ls, pt.kp.bias, s.host, put);
+        else gradx_stationary(x_host, n, D, pt.inv_ls, s.host, put);       // (il = 0 outside active_dims)
+    }
+    return 0;
+}
 // Kdiag of an MLP part at one point and its derivative factor (mlp.py:61-64,133-147): p = sum_q w_q x_q^2 + b over the active
 // columns; Kdiag = var (2/pi) asin(p / (p + 1)), dKdiag/dx_q = 2 cd w_q x_q with cd = var (2/pi) / (sqrt(1 - (p/(p+1))^2) (p+1)^2)
 static inline double mlp_point_p(const PartSpec& p, const double* x) {
