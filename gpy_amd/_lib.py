@@ -91,8 +91,104 @@ def build(force=False):
     return product
 
 
-_dp = ndpointer(dtype=np.float64, flags="C_CONTIGUOUS")
-_c_dp = ctypes.POINTER(ctypes.c_double)
+_ci, _i64, _cd, _vp, _str = ctypes.c_int, ctypes.c_int64, ctypes.c_double, ctypes.c_void_p, ctypes.c_char_p
+_dp = ndpointer(dtype=np.float64, flags="C_CONTIGUOUS")              # a double array that must be there
+_c_dp = ctypes.POINTER(ctypes.c_double)                               # a double array or scalar that may be NULL
+_ip, _hp, _parts = ctypes.POINTER(_ci), ctypes.POINTER(_vp), ctypes.POINTER(Part)
+_i32a, _i64a = (ndpointer(dtype=t, flags="C_CONTIGUOUS") for t in (np.int32, np.int64))
+_EXACT = [_vp, _ci, _ci, _dp, _dp, _i64, _cd, _cd, _dp] + [_c_dp] * 4   # (ctx, kind, ard, theta, array, length, 2 scalars, out, 4 optional)
+_KERN_X2 = [_dp, _i64, _c_dp, _i64, _ci, _dp]                           # (X, N, X2 or NULL, M, D, out)
+
+# The C-ABI, once: every function of include/mi355gp.h and include/mi355gp_debug.h, in their order, with its parameter types.
+# All return int except the two `const char*` ones (`lib()`); tests/test_abi.py holds each entry against the headers' prototypes.
+ABI = {
+    "mi355gp_last_error": [],
+    "mi355gp_version": [],
+    "mi355gp_device_count": [_ip],
+    "mi355gp_device_synchronize": [_ci],
+    "mi355gp_create": [_ci, _hp],
+    "mi355gp_destroy": [_vp],
+    "mi355gp_set_data": [_vp, _dp, _i64, _ci, _dp, _ci],
+    "mi355gp_set_targets": [_vp, _dp, _ci],
+    "mi355gp_kern_K": [_ci, _ci, _ci, _dp] + _KERN_X2,
+    "mi355gp_kern_Kdiag": [_ci, _dp, _i64, _dp],
+    "mi355gp_update_gradients_full": [_ci, _ci, _ci, _dp, _dp] + _KERN_X2,
+    "mi355gp_gradients_X": [_ci, _ci, _ci, _dp, _dp] + _KERN_X2,
+    "mi355gp_exact_inference": _EXACT,
+    "mi355gp_exact_inference_sum": [_vp, _ci, _parts, _dp, _i64, _cd, _cd, _dp] + [_c_dp] * 4,
+    "mi355gp_exact_studentt_sum": [_vp, _ci, _parts, _cd, _cd, _cd, _dp] + [_c_dp] * 3,
+    "mi355gp_inference_given_K": [_vp, _dp, _dp, _i64, _cd, _cd, _dp] + [_c_dp] * 3,
+    "mi355gp_fetch": [_vp, _ci, _dp, _ci],
+    "mi355gp_predict": [_vp, _ci, _ci, _dp, _dp, _i64, _c_dp, _c_dp, _ci],
+    "mi355gp_predict_sum": [_vp, _ci, _parts, _dp, _i64, _c_dp, _c_dp, _ci],
+    "mi355gp_predictive_gradients_sum": [_vp, _ci, _parts, _dp, _i64, _c_dp, _c_dp],
+    "mi355gp_laplace_begin": [_vp, _ci, _parts],
+    "mi355gp_laplace_newton": [_vp, _dp, _dp, _cd, _dp, _dp, _c_dp],
+    "mi355gp_laplace_finish": [_vp, _dp, _cd, _dp, _c_dp],
+    "mi355gp_laplace_gradients": [_vp, _dp, _dp, _dp],
+    "mi355gp_laplace_implicit": [_vp, _dp, _dp],
+    "mi355gp_laplace_predict": [_vp, _ci, _parts, _dp, _i64, _dp, _c_dp, _c_dp, _ci],
+    "mi355gp_ep_recompute": [_vp, _dp, _dp, _cd, _cd, _ci, _dp, _dp, _c_dp, _c_dp],
+    "mi355gp_ep_sweep": [_vp, _ci, _i64a, _dp, _cd, _cd] + [_dp] * 7 + [_c_dp],
+    "mi355gp_covariance_between_points": [_vp, _ci, _parts, _dp, _i64, _dp, _i64, _dp],
+    "mi355gp_potrf": [_ci, _dp, _i64, _c_dp],
+    "mi355gp_pdinv": [_ci, _dp, _i64] + [_c_dp] * 4,
+    "mi355gp_pdinv_full": [_ci, _dp, _i64] + [_c_dp] * 5,
+    "mi355gp_set_option": [_vp, _ci, _ci],
+    "mi355gp_get_option": [_vp, _ci, _ip],
+    "mi355gp_get_profile": [_vp, _dp, _dp, _i32a],
+    "mi355gp_grid_unique_id": [_str],
+    "mi355gp_grid_create": [_ci] * 6 + [_str, _hp],
+    "mi355gp_grid_destroy": [_vp],
+    "mi355gp_grid_set_data": [_vp, _dp, _i64, _ci, _dp, _ci],
+    "mi355gp_grid_exact_inference": _EXACT,
+    "mi355gp_grid_fetch": [_vp, _ci, _dp],
+    "mi355gp_grid_set_option": [_vp, _ci, _ci],
+    "mi355gp_grid_get_option": [_vp, _ci, _ip],
+    "mi355gp_grid_coll_log": [_vp, _ci, _dp],
+    "mi355gp_sparse_create": [_ci, _hp],
+    "mi355gp_sparse_destroy": [_vp],
+    "mi355gp_sparse_set_data": [_vp, _dp, _i64, _ci, _dp, _ci],
+    "mi355gp_vardtc_inference": _EXACT,
+    "mi355gp_vardtc_inference_sum": [_vp, _ci, _parts, _dp, _i64, _dp, _i64, _cd, _dp] + [_c_dp] * 6,
+    "mi355gp_sparse_set_input_variance": [_vp, _dp, _i64, _ci],
+    "mi355gp_sparse_set_inputs": [_vp, _dp, _c_dp, _i64, _ci],
+    "mi355gp_vardtc_inference_uncertain": [_vp, _ci, _parts, _dp, _i64, _dp, _i64, _cd, _dp] + [_c_dp] * 6,
+    "mi355gp_sparse_predict": [_vp, _ci, _parts, _dp, _i64, _c_dp, _c_dp, _ci],
+    "mi355gp_sparse_predict_uncertain": [_vp, _ci, _parts, _dp, _dp, _i64, _dp, _c_dp],
+    "mi355gp_sparse_get_predict_ms": [_vp, _c_dp],
+    "mi355gp_sparse_fetch_dLdKnm": [_vp, _i64, _i64, _dp],
+    "mi355gp_sparse_attach_comm": [_vp, _ci, _ci, _str],
+    "mi355gp_sparse_attach_loopback": [_vp, _ci, _ci, _ci],
+    "mi355gp_sparse_fetch": [_vp, _ci, _dp],
+    "mi355gp_sparse_get_profile": [_vp, _dp],
+    "mi355gp_svgp_forward": [_vp, _ci, _parts, _dp, _i64, _dp, _dp, _ci, _cd, _dp, _dp, _dp, _c_dp],
+    "mi355gp_svgp_backward": [_vp, _dp, _dp] + [_c_dp] * 5,
+    "mi355gp_svgp_predict": [_vp, _ci, _parts, _c_dp, _i64, _ci] + [_c_dp] * 4,
+    "mi355gp_pep_inference": [_vp, _ci, _parts, _dp, _i64, _cd, _cd, _cd, _dp] + [_c_dp] * 5,
+    "mi355gp_pep_check_sigma": [_dp, _i64, _i64, _cd, _cd],
+    "mi355gp_rbf_psi": [_ci, _cd, _dp, _ci, _dp, _i64, _dp, _dp, _i64, _ci] + [_c_dp] * 3,
+    "mi355gp_rbf_psi_grad": [_ci, _cd, _dp, _ci, _dp, _i64, _dp, _dp, _i64, _ci] + [_c_dp] * 4 + [_dp] * 5,
+    # ---- include/mi355gp_debug.h ----
+    "mi355gp_bench_factor": [_ci, _i64, _ci, _c_dp, _c_dp, _c_dp],
+    "mi355gp_dbg_ipc_selftest": [_str, _ci, _ci, _ci, _ci, _i64, _dp],
+    "mi355gp_dbg_comm_selftest": [_ci, _str, _ci, _ci, _ci, _ci, _i64, _ci, _dp],
+    "mi355gp_dbg_grid_multi": [_ci, _ci, _ci, _ci, _dp],
+    "mi355gp_dbg_update_nt": [_ci, _ci, _ip, _ci, _ci, _dp],
+    "mi355gp_dbg_update_rect": [_ci, _ci, _ci, _ip, _ci, _ci, _dp],
+    "mi355gp_dbg_mfma": [_ci, _dp, _dp, _dp],
+    "mi355gp_dbg_gemm": [_ci, _ci, _ci, _i64, _i64, _i64, _dp, _dp, _dp, _cd, _cd, _ci, _c_dp],
+    "mi355gp_dbg_peaks": [_ci, _dp],
+    "mi355gp_dbg_gemm_clock": [_c_dp, _c_dp],
+    "mi355gp_dbg_cu_map": [_ci, _ci, _ci, ctypes.POINTER(ctypes.c_uint)],
+    "mi355gp_dbg_pipe_share": [_ci, _dp],
+    "mi355gp_dbg_graph_factor": [_ci, _i64, _ci, _dp],
+    "mi355gp_dbg_persist": [_ci, _i64, _ci, _ci, _dp],
+    "mi355gp_dbg_lauum_plan": [_ci, _ip, _ci, _ip],
+    "mi355gp_dbg_persist_owners": [_ci, _ci, _ci, _ip, _ip],
+    "mi355gp_dbg_mask_probe": [_ci, _ci, _ci, _dp],
+}
+EXPORTED = tuple(ABI)
 
 
 def _opt(a):
@@ -102,147 +198,15 @@ def _opt(a):
 
 def lib():
     global _lib
-    if _lib is not None:
-        return _lib
-    if not os.path.exists(LIB_PATH):
-        build()
-    L = ctypes.CDLL(LIB_PATH)
-    i64, ci, cd, vp = ctypes.c_int64, ctypes.c_int, ctypes.c_double, ctypes.c_void_p
-    L.mi355gp_last_error.restype = ctypes.c_char_p
-    L.mi355gp_version.restype = ctypes.c_char_p
-    L.mi355gp_device_count.argtypes = [ctypes.POINTER(ci)]
-    L.mi355gp_device_synchronize.argtypes = [ci]
-    L.mi355gp_create.argtypes = [ci, ctypes.POINTER(vp)]
-    L.mi355gp_destroy.argtypes = [vp]
-    L.mi355gp_set_data.argtypes = [vp, _dp, i64, ci, _dp, ci]
-    L.mi355gp_set_targets.argtypes = [vp, _dp, ci]
-    L.mi355gp_kern_K.argtypes = [ci, ci, ci, _dp, _dp, i64, _c_dp, i64, ci, _dp]
-    L.mi355gp_kern_Kdiag.argtypes = [ci, _dp, i64, _dp]
-    L.mi355gp_update_gradients_full.argtypes = [ci, ci, ci, _dp, _dp, _dp, i64, _c_dp, i64, ci, _dp]
-    L.mi355gp_gradients_X.argtypes = [ci, ci, ci, _dp, _dp, _dp, i64, _c_dp, i64, ci, _dp]
-    L.mi355gp_exact_inference.argtypes = [vp, ci, ci, _dp, _dp, i64, cd, cd, _dp, _c_dp, _c_dp, _c_dp, _c_dp]
-    L.mi355gp_exact_inference_sum.argtypes = [vp, ci, ctypes.POINTER(Part), _dp, i64, cd, cd, _dp, _c_dp, _c_dp, _c_dp,
-                                              _c_dp]
-    L.mi355gp_exact_studentt_sum.argtypes = [vp, ci, ctypes.POINTER(Part), cd, cd, cd, _dp, _c_dp, _c_dp, _c_dp]
-    L.mi355gp_covariance_between_points.argtypes = [vp, ci, ctypes.POINTER(Part), _dp, i64, _dp, i64, _dp]
-    L.mi355gp_predictive_gradients_sum.argtypes = [vp, ci, ctypes.POINTER(Part), _dp, i64, _c_dp, _c_dp]
-    L.mi355gp_predict_sum.argtypes = [vp, ci, ctypes.POINTER(Part), _dp, i64, _c_dp, _c_dp, ci]
-    L.mi355gp_laplace_begin.argtypes = [vp, ci, ctypes.POINTER(Part)]
-    L.mi355gp_laplace_newton.argtypes = [vp, _dp, _dp, cd, _dp, _dp, _c_dp]
-    L.mi355gp_laplace_finish.argtypes = [vp, _dp, cd, _dp, _c_dp]
-    L.mi355gp_laplace_gradients.argtypes = [vp, _dp, _dp, _dp]
-    L.mi355gp_laplace_implicit.argtypes = [vp, _dp, _dp]
-    L.mi355gp_laplace_predict.argtypes = [vp, ci, ctypes.POINTER(Part), _dp, i64, _dp, _c_dp, _c_dp, ci]
-    L.mi355gp_ep_recompute.argtypes = [vp, _dp, _dp, cd, cd, ci, _dp, _dp, _c_dp, _c_dp]
-    L.mi355gp_ep_sweep.argtypes = [vp, ci, ndpointer(dtype=np.int64, flags="C_CONTIGUOUS"), _dp, cd, cd, _dp, _dp, _dp, _dp, _dp, _dp,
-                                   _dp, _c_dp]
-    L.mi355gp_inference_given_K.argtypes = [vp, _dp, _dp, i64, cd, cd, _dp, _c_dp, _c_dp, _c_dp]
-    L.mi355gp_fetch.argtypes = [vp, ci, _dp, ci]
-    L.mi355gp_predict.argtypes = [vp, ci, ci, _dp, _dp, i64, _c_dp, _c_dp, ci]
-    L.mi355gp_potrf.argtypes = [ci, _dp, i64, _c_dp]
-    L.mi355gp_pdinv.argtypes = [ci, _dp, i64, _c_dp, _c_dp, _c_dp, _c_dp]
-    L.mi355gp_pdinv_full.argtypes = [ci, _dp, i64, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp]
-    L.mi355gp_set_option.argtypes = [vp, ci, ci]
-    L.mi355gp_get_option.argtypes = [vp, ci, ctypes.POINTER(ci)]
-    L.mi355gp_sparse_get_profile.argtypes = [vp, _dp]
-    L.mi355gp_dbg_comm_selftest.argtypes = [ci, ctypes.c_char_p, ci, ci, ci, ci, i64, ci, _dp]
-    L.mi355gp_dbg_comm_selftest.restype = ci
-    L.mi355gp_bench_factor.argtypes = [ci, i64, ci, _c_dp, _c_dp, _c_dp]
-    L.mi355gp_bench_factor.restype = ci
-    L.mi355gp_get_profile.argtypes = [vp, _dp, _dp, ndpointer(dtype=np.int32, flags="C_CONTIGUOUS")]
-    L.mi355gp_grid_unique_id.argtypes = [ctypes.c_char_p]
-    L.mi355gp_grid_create.argtypes = [ci, ci, ci, ci, ci, ci, ctypes.c_char_p, ctypes.POINTER(vp)]
-    L.mi355gp_grid_destroy.argtypes = [vp]
-    L.mi355gp_grid_set_data.argtypes = [vp, _dp, i64, ci, _dp, ci]
-    L.mi355gp_grid_exact_inference.argtypes = [vp, ci, ci, _dp, _dp, i64, cd, cd, _dp, _c_dp, _c_dp, _c_dp, _c_dp]
-    L.mi355gp_grid_fetch.argtypes = [vp, ci, _dp]
-    L.mi355gp_grid_set_option.argtypes = [vp, ci, ci]
-    L.mi355gp_grid_coll_log.argtypes = [vp, ci, _dp]
-    L.mi355gp_grid_coll_log.restype = ci
-    L.mi355gp_dbg_grid_multi.argtypes = [ci, ci, ci, ci, _dp]
-    L.mi355gp_dbg_update_nt.argtypes = [ci, ci, ctypes.POINTER(ci), ci, ci, _dp]
-    L.mi355gp_dbg_update_rect.argtypes = [ci, ci, ci, ctypes.POINTER(ci), ci, ci, _dp]
-    L.mi355gp_grid_get_option.argtypes = [vp, ci, ctypes.POINTER(ci)]
-    L.mi355gp_sparse_create.argtypes = [ci, ctypes.POINTER(vp)]
-    L.mi355gp_sparse_destroy.argtypes = [vp]
-    L.mi355gp_sparse_set_data.argtypes = [vp, _dp, i64, ci, _dp, ci]
-    L.mi355gp_vardtc_inference.argtypes = [vp, ci, ci, _dp, _dp, i64, cd, cd, _dp, _c_dp, _c_dp, _c_dp, _c_dp]
-    L.mi355gp_sparse_fetch.argtypes = [vp, ci, _dp]
-    L.mi355gp_vardtc_inference_sum.argtypes = [vp, ci, ctypes.POINTER(Part), _dp, i64, _dp, i64, cd, _dp, _c_dp, _c_dp, _c_dp,
-                                               _c_dp, _c_dp, _c_dp]
-    L.mi355gp_sparse_set_input_variance.argtypes = [vp, _dp, i64, ci]
-    L.mi355gp_vardtc_inference_uncertain.argtypes = [vp, ci, ctypes.POINTER(Part), _dp, i64, _dp, i64, cd, _dp, _c_dp, _c_dp,
-                                                     _c_dp, _c_dp, _c_dp, _c_dp]
-    L.mi355gp_sparse_predict.argtypes = [vp, ci, ctypes.POINTER(Part), _dp, i64, _c_dp, _c_dp, ci]
-    L.mi355gp_sparse_set_inputs.argtypes = [vp, _dp, _c_dp, i64, ci]
-    L.mi355gp_sparse_predict_uncertain.argtypes = [vp, ci, ctypes.POINTER(Part), _dp, _dp, i64, _dp, _c_dp]
-    L.mi355gp_sparse_get_predict_ms.argtypes = [vp, _c_dp]
-    L.mi355gp_sparse_fetch_dLdKnm.argtypes = [vp, i64, i64, _dp]
-    L.mi355gp_sparse_attach_loopback.argtypes = [vp, ci, ci, ci]
-    L.mi355gp_svgp_forward.argtypes = [vp, ci, ctypes.POINTER(Part), _dp, i64, _dp, _dp, ci, cd, _dp, _dp, _dp, _c_dp]
-    L.mi355gp_svgp_backward.argtypes = [vp, _dp, _dp, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp]
-    L.mi355gp_svgp_predict.argtypes = [vp, ci, ctypes.POINTER(Part), _c_dp, i64, ci, _c_dp, _c_dp, _c_dp, _c_dp]
-    L.mi355gp_pep_inference.argtypes = [vp, ci, ctypes.POINTER(Part), _dp, i64, cd, cd, cd, _dp, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp]
-    L.mi355gp_pep_check_sigma.argtypes = [_dp, i64, i64, cd, cd]
-    L.mi355gp_sparse_attach_comm.argtypes = [vp, ci, ci, ctypes.c_char_p]
-    L.mi355gp_rbf_psi.argtypes = [ci, cd, _dp, ci, _dp, i64, _dp, _dp, i64, ci, _c_dp, _c_dp, _c_dp]
-    L.mi355gp_rbf_psi_grad.argtypes = [ci, cd, _dp, ci, _dp, i64, _dp, _dp, i64, ci, _c_dp, _c_dp, _c_dp, _c_dp, _dp, _dp, _dp,
-                                       _dp, _dp]
-    L.mi355gp_dbg_mfma.argtypes = [ci, _dp, _dp, _dp]
-    L.mi355gp_dbg_gemm.argtypes = [ci, ci, ci, i64, i64, i64, _dp, _dp, _dp, cd, cd, ci, _c_dp]
-    L.mi355gp_dbg_peaks.argtypes = [ci, _dp]
-    L.mi355gp_dbg_pipe_share.argtypes = [ci, _dp]
-    L.mi355gp_dbg_graph_factor.argtypes = [ci, i64, ci, _dp]
-    L.mi355gp_dbg_gemm_clock.argtypes = [_c_dp, _c_dp]
-    L.mi355gp_dbg_mask_probe.argtypes = [ci, ci, ci, _dp]
-    L.mi355gp_dbg_lauum_plan.argtypes = [ci, ctypes.POINTER(ci), ci, ctypes.POINTER(ci)]
-    L.mi355gp_dbg_lauum_plan.restype = ci
-    L.mi355gp_dbg_persist_owners.argtypes = [ci, ci, ci, ctypes.POINTER(ci), ctypes.POINTER(ci)]
-    L.mi355gp_dbg_persist_owners.restype = ci
-    L.mi355gp_dbg_persist.argtypes = [ci, i64, ci, ci, _dp]
-    L.mi355gp_dbg_ipc_selftest.argtypes = [ctypes.c_char_p, ci, ci, ci, ci, i64, _dp]
-    for name in ("device_count", "create", "destroy", "set_data", "set_targets", "kern_K", "kern_Kdiag",
-                 "update_gradients_full", "exact_inference", "inference_given_K", "fetch", "predict", "potrf",
-                 "pdinv", "dbg_mfma", "dbg_gemm", "dbg_peaks", "set_option", "get_profile", "grid_unique_id",
-                 "grid_create", "grid_destroy", "grid_set_data", "grid_exact_inference", "grid_fetch", "grid_set_option",
-                 "grid_get_option", "sparse_create",
-                 "sparse_destroy", "sparse_set_data", "vardtc_inference", "sparse_fetch", "gradients_X", "sparse_attach_comm", "exact_inference_sum",
-                 "predict_sum", "dbg_gemm_clock", "covariance_between_points", "exact_studentt_sum", "dbg_mask_probe",
-                 "vardtc_inference_sum", "sparse_predict", "sparse_fetch_dLdKnm", "sparse_attach_loopback",
-                 "predictive_gradients_sum", "dbg_pipe_share", "pdinv_full", "dbg_graph_factor", "get_option",
-                 "sparse_get_profile", "dbg_persist", "dbg_grid_multi", "dbg_update_nt", "dbg_update_rect",
-                 "dbg_ipc_selftest", "laplace_begin", "laplace_newton", "laplace_finish", "laplace_gradients",
-                 "laplace_implicit", "laplace_predict", "ep_recompute", "ep_sweep", "rbf_psi", "rbf_psi_grad",
-                 "sparse_set_input_variance", "vardtc_inference_uncertain", "svgp_forward", "svgp_backward",
-                 "svgp_predict", "sparse_set_inputs", "sparse_predict_uncertain",
-                 "sparse_get_predict_ms", "pep_inference", "pep_check_sigma"):
-        getattr(L, "mi355gp_" + name).restype = ci
-    _lib = L
-    return L
-
-
-EXPORTED = ("mi355gp_last_error", "mi355gp_version", "mi355gp_device_count", "mi355gp_device_synchronize", "mi355gp_create", "mi355gp_destroy",
-            "mi355gp_set_data", "mi355gp_set_targets", "mi355gp_kern_K", "mi355gp_kern_Kdiag",
-            "mi355gp_update_gradients_full", "mi355gp_exact_inference", "mi355gp_inference_given_K",
-            "mi355gp_fetch", "mi355gp_predict", "mi355gp_potrf", "mi355gp_pdinv", "mi355gp_bench_factor",
-            "mi355gp_set_option", "mi355gp_get_profile", "mi355gp_grid_unique_id", "mi355gp_grid_create",
-            "mi355gp_grid_destroy", "mi355gp_grid_set_data", "mi355gp_grid_exact_inference", "mi355gp_grid_fetch",
-            "mi355gp_grid_set_option", "mi355gp_grid_get_option",
-            "mi355gp_sparse_create", "mi355gp_sparse_destroy", "mi355gp_sparse_set_data", "mi355gp_vardtc_inference",
-            "mi355gp_sparse_fetch", "mi355gp_gradients_X", "mi355gp_sparse_attach_comm",
-            "mi355gp_exact_inference_sum", "mi355gp_predict_sum", "mi355gp_dbg_gemm_clock",
-            "mi355gp_covariance_between_points", "mi355gp_exact_studentt_sum", "mi355gp_vardtc_inference_sum",
-            "mi355gp_sparse_predict", "mi355gp_sparse_fetch_dLdKnm", "mi355gp_sparse_attach_loopback",
-            "mi355gp_predictive_gradients_sum", "mi355gp_dbg_pipe_share", "mi355gp_pdinv_full", "mi355gp_dbg_graph_factor",
-            "mi355gp_dbg_mfma", "mi355gp_dbg_gemm", "mi355gp_dbg_peaks", "mi355gp_dbg_mask_probe", "mi355gp_get_option",
-            "mi355gp_sparse_get_profile", "mi355gp_dbg_persist", "mi355gp_dbg_grid_multi", "mi355gp_dbg_update_nt", "mi355gp_dbg_update_rect",
-            "mi355gp_dbg_ipc_selftest", "mi355gp_grid_coll_log", "mi355gp_dbg_lauum_plan", "mi355gp_dbg_persist_owners",
-            "mi355gp_laplace_begin", "mi355gp_laplace_newton", "mi355gp_laplace_finish", "mi355gp_laplace_gradients",
-            "mi355gp_laplace_implicit", "mi355gp_laplace_predict", "mi355gp_ep_recompute", "mi355gp_ep_sweep",
-            "mi355gp_rbf_psi", "mi355gp_rbf_psi_grad", "mi355gp_sparse_set_input_variance",
-            "mi355gp_vardtc_inference_uncertain", "mi355gp_svgp_forward", "mi355gp_svgp_backward", "mi355gp_svgp_predict",
-            "mi355gp_sparse_set_inputs", "mi355gp_sparse_predict_uncertain", "mi355gp_sparse_get_predict_ms",
-            "mi355gp_pep_inference", "mi355gp_pep_check_sigma")
+    if _lib is None:
+        if not os.path.exists(LIB_PATH):
+            build()
+        L = ctypes.CDLL(LIB_PATH)
+        for name, argtypes in ABI.items():
+            getattr(L, name).argtypes = argtypes
+        L.mi355gp_last_error.restype = L.mi355gp_version.restype = _str
+        _lib = L
+    return _lib
 
 
 # mi355gp_set_option / mi355gp_get_option ids (include/mi355gp.h, MI355GP_OPT_*)
@@ -320,19 +284,20 @@ def _predict(entry, head, Xnew, D, Dy, full_cov, want_var, between=()):
     return mu, var
 
 
-class Context(object):
-    """One device context = one uploaded data set (X, R = Y - mean) with its N x N buffers in HBM."""
+class _Handle(object):
+    """Owner of one context handle of the C-ABI: made by the entry `_create` on construction, given to `_destroy` once, by
+    `close()` or when the object is collected."""
+    _create = _destroy = None
 
     def __init__(self, device=0):
         require_device(device)
         self._h = ctypes.c_void_p()
-        check(lib().mi355gp_create(device, ctypes.byref(self._h)), "mi355gp_create")
+        check(getattr(lib(), self._create)(device, ctypes.byref(self._h)), self._create)
         self.device = device
-        self.N = self.D = self.Dy = 0
 
     def close(self):
         if getattr(self, "_h", None) is not None and self._h.value:
-            lib().mi355gp_destroy(self._h)
+            getattr(lib(), self._destroy)(self._h)
             self._h = ctypes.c_void_p()
 
     def __del__(self):
@@ -340,6 +305,15 @@ class Context(object):
             self.close()
         except Exception:
             pass
+
+
+class Context(_Handle):
+    """One device context = one uploaded data set (X, R = Y - mean) with its N x N buffers in HBM."""
+    _create, _destroy = "mi355gp_create", "mi355gp_destroy"
+
+    def __init__(self, device=0):
+        super(Context, self).__init__(device)
+        self.N = self.D = self.Dy = 0
 
     def set_data(self, X, R):
         X, R = f64(X), f64(R)
@@ -536,27 +510,15 @@ class Context(object):
         return out
 
 
-class SparseContext(object):
+class SparseContext(_Handle):
     """One device context of the sparse (VarDTC) path = one uploaded (X, Y); Z and theta change per call."""
     FETCH_DLDKMM, FETCH_WOODBURY_INV, FETCH_LM, FETCH_KMM, FETCH_PSI2, FETCH_DLDPSI2_BETA = 0, 1, 2, 3, 4, 5
     sharded = False
+    _create, _destroy = "mi355gp_sparse_create", "mi355gp_sparse_destroy"
 
     def __init__(self, device=0):
-        require_device(device)
-        self._h = ctypes.c_void_p()
-        check(lib().mi355gp_sparse_create(device, ctypes.byref(self._h)), "mi355gp_sparse_create")
+        super(SparseContext, self).__init__(device)
         self.N = self.D = self.Dy = self.M = 0
-
-    def close(self):
-        if getattr(self, "_h", None) is not None and self._h.value:
-            lib().mi355gp_sparse_destroy(self._h)
-            self._h = ctypes.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def attach_comm(self, rank, world, id_bytes):
         """Row-sharded multi-GPU mode: this rank will upload only its slice of (X, Y) (see gpy_amd.grid.shard_rows)."""
@@ -576,22 +538,30 @@ class SparseContext(object):
         check(lib().mi355gp_sparse_get_profile(self._h, o), "mi355gp_sparse_get_profile")
         return {"gemm_T": (o[0], o[1], int(o[2])), "gram_psi2": (o[3], o[4], int(o[5]))}
 
-    def vardtc(self, kind, ARD, theta, Z, noise_var, extra_jitter=0.0, want_stage_ms=False):
-        """(info, dict(lml, dnoise, dtheta, dZ, woodbury_vector[, stage_ms]))"""
-        theta, Z = f64(theta), f64(Z)
+    def _fit(self, entry, head, ntheta, Z, scalars, extras, want_stage_ms, wv_cols=None):
+        """the shared part of the four fit entries, which all run (ctx, *head, Z, M, *scalars, out, dtheta, dZ, woodbury_vector,
+        *extras (optional outputs), ms): (info, out, dict(lml, dnoise, dtheta, dZ, woodbury_vector[, stage_ms]))"""
+        Z = f64(Z)
         self.M = Z.shape[0]
         assert Z.shape[1] == self.D
         out = np.zeros(NUM_OUT)
-        dtheta = np.zeros(theta.size)
+        dtheta = np.zeros(ntheta)
         dZ = np.zeros((self.M, self.D))
-        wv = np.zeros((self.M, self.Dy))
+        wv = np.zeros((self.M, self.Dy if wv_cols is None else wv_cols))
         ms = np.zeros(4) if want_stage_ms else None
-        rc = check(lib().mi355gp_vardtc_inference(self._h, KIND_IDS[kind], int(bool(ARD)), theta, Z, self.M,
-                                                  float(noise_var), float(extra_jitter), out, _opt(dtheta), _opt(dZ),
-                                                  _opt(wv), _opt(ms)), "mi355gp_vardtc_inference")
-        res = dict(lml=out[0], dnoise=out[1], trA=out[2], data_fit=out[3], dtheta=dtheta, dZ=dZ, woodbury_vector=wv)
+        args = tuple(head) + (Z, self.M) + tuple(scalars) + (out, _opt(dtheta), _opt(dZ), _opt(wv))
+        rc = check(getattr(lib(), entry)(self._h, *(args + tuple(_opt(e) for e in extras) + (_opt(ms),))), entry)
+        res = dict(lml=out[0], dnoise=out[1], dtheta=dtheta, dZ=dZ, woodbury_vector=wv)
         if ms is not None:
             res["stage_ms"] = dict(pass1=ms[0], mxm=ms[1], pass2=ms[2], total=ms[3])
+        return rc, out, res
+
+    def vardtc(self, kind, ARD, theta, Z, noise_var, extra_jitter=0.0, want_stage_ms=False):
+        """(info, dict(lml, dnoise, dtheta, dZ, woodbury_vector[, stage_ms]))"""
+        theta = f64(theta)
+        rc, out, res = self._fit("mi355gp_vardtc_inference", (KIND_IDS[kind], int(bool(ARD)), theta), theta.size, Z,
+                                 (float(noise_var), float(extra_jitter)), (), want_stage_ms)
+        res.update(trA=out[2], data_fit=out[3])
         return rc, res
 
     def fetch(self, which):
@@ -609,25 +579,14 @@ class SparseContext(object):
         (info, dict(lml, dnoise (scalar; per-point noise: the N-vector dL_dR, N x Dy for several output columns), dtheta
         (concatenated), dZ, woodbury_vector[, dL_dm, stage_ms]))"""
         arr, keep, ntheta = make_parts(specs)
-        Z = f64(Z)
-        self.M = Z.shape[0]
-        assert Z.shape[1] == self.D
         noise = f64(np.atleast_1d(noise)).ravel()
-        het = noise.size > 1
-        out = np.zeros(NUM_OUT)
-        dtheta = np.zeros(ntheta)
-        dZ = np.zeros((self.M, self.D))
-        wv = np.zeros((self.M, self.Dy))
-        rows = np.zeros((self.N, self.Dy)) if het else None       # dL_dR per point and output column (var_dtc.py:240-256)
+        rows = np.zeros((self.N, self.Dy)) if noise.size > 1 else None   # dL_dR per point and output column (var_dtc.py:240-256)
         dm = np.zeros((self.N, self.Dy)) if want_dL_dm else None
-        ms = np.zeros(4) if want_stage_ms else None
-        rc = check(lib().mi355gp_vardtc_inference_sum(self._h, len(specs), arr, Z, self.M, noise, noise.size,
-                                                      float(extra_jitter), out, _opt(dtheta), _opt(dZ), _opt(wv), _opt(rows),
-                                                      _opt(dm), _opt(ms)), "mi355gp_vardtc_inference_sum")
-        res = dict(lml=out[0], dnoise=(rows[:, 0] if self.Dy == 1 else rows) if het else out[1], trA=out[2],
-                   data_fit=out[3], dtheta=dtheta, dZ=dZ, woodbury_vector=wv, dL_dm=dm)
-        if ms is not None:
-            res["stage_ms"] = dict(pass1=ms[0], mxm=ms[1], pass2=ms[2], total=ms[3])
+        rc, out, res = self._fit("mi355gp_vardtc_inference_sum", (len(specs), arr), ntheta, Z,
+                                 (noise, noise.size, float(extra_jitter)), (rows, dm), want_stage_ms)
+        if rows is not None:
+            res["dnoise"] = rows[:, 0] if self.Dy == 1 else rows
+        res.update(trA=out[2], data_fit=out[3], dL_dm=dm)
         return rc, res
 
     def set_input_variance(self, S):
@@ -665,25 +624,12 @@ class SparseContext(object):
         """One evaluation with uncertain inputs (one RBF part alone or with White parts, ONE noise variance).
         (info, dict(lml, dnoise, dtheta (concatenated), dZ, woodbury_vector, dmu, dS[, stage_ms]))"""
         arr, keep, ntheta = make_parts(specs)
-        Z = f64(Z)
-        self.M = Z.shape[0]
-        assert Z.shape[1] == self.D
         noise = f64(np.atleast_1d(noise)).ravel()
-        out = np.zeros(NUM_OUT)
-        dtheta = np.zeros(ntheta)
-        dZ = np.zeros((self.M, self.D))
-        wv = np.zeros((self.M, self.Dy))
         dmu = np.zeros((self.N, self.D)) if want_dmu_dS else None
         dS = np.zeros((self.N, self.D)) if want_dmu_dS else None
-        ms = np.zeros(4) if want_stage_ms else None
-        rc = check(lib().mi355gp_vardtc_inference_uncertain(self._h, len(specs), arr, Z, self.M, noise, noise.size,
-                                                            float(extra_jitter), out, _opt(dtheta), _opt(dZ), _opt(wv),
-                                                            _opt(dmu), _opt(dS), _opt(ms)),
-                   "mi355gp_vardtc_inference_uncertain")
-        res = dict(lml=out[0], dnoise=out[1], trA=out[2], data_fit=out[3], dtheta=dtheta, dZ=dZ, woodbury_vector=wv,
-                   dmu=dmu, dS=dS)
-        if ms is not None:
-            res["stage_ms"] = dict(pass1=ms[0], mxm=ms[1], pass2=ms[2], total=ms[3])
+        rc, out, res = self._fit("mi355gp_vardtc_inference_uncertain", (len(specs), arr), ntheta, Z,
+                                 (noise, noise.size, float(extra_jitter)), (dmu, dS), want_stage_ms)
+        res.update(trA=out[2], data_fit=out[3], dmu=dmu, dS=dS)
         return rc, res
 
     def predict(self, specs, Xnew, full_cov=False, want_var=True):
@@ -701,21 +647,10 @@ class SparseContext(object):
         """One `PEP.inference` (alpha = 1: `FITC.inference`) with one noise variance; `jitter` is the whole term on Kmm's
         diagonal.  (info, dict(lml, dnoise (= dL_dthetaL), dL_dR (N), dtheta (concatenated), dZ, woodbury_vector[, stage_ms]))"""
         arr, keep, ntheta = make_parts(specs)
-        Z = f64(Z)
-        self.M = Z.shape[0]
-        assert Z.shape[1] == self.D
-        out = np.zeros(NUM_OUT)
-        dtheta = np.zeros(ntheta)
-        dZ = np.zeros((self.M, self.D))
-        wv = np.zeros((self.M, 1))
         dR = np.zeros(self.N)
-        ms = np.zeros(4) if want_stage_ms else None
-        rc = check(lib().mi355gp_pep_inference(self._h, len(specs), arr, Z, self.M, float(noise_variance), float(alpha),
-                                               float(jitter), out, _opt(dtheta), _opt(dZ), _opt(wv), _opt(dR), _opt(ms)),
-                   "mi355gp_pep_inference")
-        res = dict(lml=out[0], dnoise=out[1], sum_dL_dR=out[2], dL_dR=dR, dtheta=dtheta, dZ=dZ, woodbury_vector=wv)
-        if ms is not None:
-            res["stage_ms"] = dict(pass1=ms[0], mxm=ms[1], pass2=ms[2], total=ms[3])
+        rc, out, res = self._fit("mi355gp_pep_inference", (len(specs), arr), ntheta, Z,
+                                 (float(noise_variance), float(alpha), float(jitter)), (dR,), want_stage_ms, wv_cols=1)
+        res.update(sum_dL_dR=out[2], dL_dR=dR)
         return rc, res
 
     # ---- SVGP: forward -> the likelihood's quadrature on the host -> backward (svgp.hip) ------------------------------------
@@ -780,19 +715,29 @@ class SparseContext(object):
         return wv, (None if wi is None else np.ascontiguousarray(np.transpose(wi, (1, 2, 0))))
 
 
-def kern_K(kind, ARD, theta, X, X2=None, device=0):
-    require_device(device)
+def _point_sets(X, X2, dL_dK=None):
+    """the (X, N, X2 or NULL, M, D) run of the three kernel functions, X2 = None standing for X itself; with `dL_dK`, that
+    matrix checked against N x M comes first"""
     X = f64(X)
     N, D = X.shape
     if X2 is None:
         M, p2 = N, None
     else:
         X2 = f64(X2)
-        M, p2 = X2.shape[0], X2.ctypes.data_as(_c_dp)
+        M, p2 = X2.shape[0], X2.ctypes.data_as(_c_dp)        # (the pointer keeps the converted X2 alive)
         assert X2.shape[1] == D
-    out = np.empty((N, M))
-    check(lib().mi355gp_kern_K(device, KIND_IDS[kind], ard_id(kind, ARD), f64(theta), X, N, p2, M, D, out),
-          "mi355gp_kern_K")
+    if dL_dK is None:
+        return X, N, p2, M, D
+    G = f64(dL_dK)
+    assert G.shape == (N, M), "dL_dK must be N x M"
+    return G, X, N, p2, M, D
+
+
+def kern_K(kind, ARD, theta, X, X2=None, device=0):
+    require_device(device)
+    sets = _point_sets(X, X2)
+    out = np.empty((sets[1], sets[3]))
+    check(lib().mi355gp_kern_K(device, KIND_IDS[kind], ard_id(kind, ARD), f64(theta), *(sets + (out,))), "mi355gp_kern_K")
     return out
 
 
@@ -804,36 +749,19 @@ def kern_Kdiag(kind, theta, N):
 
 def update_gradients_full(kind, ARD, theta, dL_dK, X, X2=None, device=0):
     require_device(device)
-    X = f64(X)
-    N, D = X.shape
-    if X2 is None:
-        M, p2 = N, None
-    else:
-        X2 = f64(X2)
-        M, p2 = X2.shape[0], X2.ctypes.data_as(_c_dp)
-    G = f64(dL_dK)
-    assert G.shape == (N, M), "dL_dK must be N x M"
     theta = f64(theta)
     out = np.zeros(theta.size)
-    check(lib().mi355gp_update_gradients_full(device, KIND_IDS[kind], ard_id(kind, ARD), theta, G, X, N, p2, M, D, out),
-          "mi355gp_update_gradients_full")
+    check(lib().mi355gp_update_gradients_full(device, KIND_IDS[kind], ard_id(kind, ARD), theta,
+                                              *(_point_sets(X, X2, dL_dK) + (out,))), "mi355gp_update_gradients_full")
     return out
 
 
 def gradients_X(kind, ARD, theta, dL_dK, X, X2=None, device=0):
     """dL/dX (N x D) from dL_dK (N x M) (reference `Stationary.gradients_X`, stationary.py:245-252)."""
     require_device(device)
-    X = f64(X)
-    N, D = X.shape
-    if X2 is None:
-        M, p2 = N, None
-    else:
-        X2 = f64(X2)
-        M, p2 = X2.shape[0], X2.ctypes.data_as(_c_dp)
-    G = f64(dL_dK)
-    assert G.shape == (N, M), "dL_dK must be N x M"
-    out = np.zeros((N, D))
-    check(lib().mi355gp_gradients_X(device, KIND_IDS[kind], ard_id(kind, ARD), f64(theta), G, X, N, p2, M, D, out),
+    sets = _point_sets(X, X2, dL_dK)
+    out = np.zeros(sets[1].shape)
+    check(lib().mi355gp_gradients_X(device, KIND_IDS[kind], ard_id(kind, ARD), f64(theta), *(sets + (out,))),
           "mi355gp_gradients_X")
     return out
 

@@ -10,6 +10,7 @@ gradients, prediction).  Nothing N x N leaves the device unless a caller materia
 import numpy as np
 
 from . import _lib
+from .inference import LatentFunctionInference
 from .laplace import begin_session, entry_checks
 from .lazy import DeviceResult, kernel_signature
 from .likelihoods import Bernoulli
@@ -62,7 +63,9 @@ class posteriorParams(object):
         return {"mu": self.mu.tolist(), "Sigma_diag": self.Sigma_diag.tolist()}
 
 
-class EP(object):
+class EP(LatentFunctionInference):
+    _per_optimization = ("_ep_approximation",)
+
     def __init__(self, epsilon=1e-6, eta=1., delta=1., always_reset=False, max_iters=np.inf, ep_mode="alternated",
                  parallel_updates=False, device=0, maxtries=5):
         self.always_reset = always_reset
@@ -77,12 +80,6 @@ class EP(object):
     def reset(self):
         self.ga_approx_old = None
         self._ep_approximation = None
-
-    def on_optimization_start(self):
-        self._ep_approximation = None
-
-    def on_optimization_end(self):
-        pass
 
     def _stop_criteria(self, ga_approx):
         tau_diff = np.mean(np.square(ga_approx.tau - self.ga_approx_old.tau))
@@ -100,11 +97,6 @@ class EP(object):
             post, ga, cav, lz = self._ep_approximation
             d["_ep_approximation"] = {"post_params": post.to_dict(), "ga_approx": ga.to_dict(), "cav_params": cav.to_dict(),
                                       "log_Z_tilde": float(lz)}
-        return d
-
-    def __getstate__(self):
-        d = dict(self.__dict__)
-        d["_state"] = None
         return d
 
     def _with_ladder(self, attempt):

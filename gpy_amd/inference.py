@@ -19,6 +19,27 @@ from .linalg import jitter_ladder
 from .posterior import PosteriorExact, StudentTPosterior
 
 
+class LatentFunctionInference(object):
+    """What every inference class of the package shares with GPy's base (reference `latent_function_inference/__init__.py:38-49`):
+    the optimisation hooks, which do nothing but forget the members named in `_per_optimization` (EP's approximation,
+    reference `expectation_propagation.py:220-221`), and pickling without the members named in `_device_members` -- device
+    handles and the identities of what was uploaded never travel (cf. reference `rbf.py:313-318`)."""
+    _device_members = ("_state",)
+    _per_optimization = ()
+
+    def on_optimization_start(self):
+        for name in self._per_optimization:
+            setattr(self, name, None)
+
+    def on_optimization_end(self):
+        pass
+
+    def __getstate__(self):
+        d = dict(self.__dict__)
+        d.update(dict.fromkeys(self._device_members))
+        return d
+
+
 class _DeviceState(object):
     """One uploaded (X, R) pair and the HBM buffers behind it."""
 
@@ -88,7 +109,9 @@ class _DeviceState(object):
         return self.ctx.predict_sum(kern.part_specs(), kern._slice_X(Xnew), full_cov=full_cov)
 
 
-class ExactGaussianInference(object):
+class ExactGaussianInference(LatentFunctionInference):
+    _device_members = ("_state", "_last")        # (`_last` holds the device state of the last call)
+
     def __init__(self, device=0, maxtries=5):
         self.device = device
         self.maxtries = maxtries
@@ -98,21 +121,8 @@ class ExactGaussianInference(object):
         self.keep_diag = True      # N doubles per call: diag(Ky^-1) for LOO without fetching the N x N inverse
         self._last = None
 
-    # GPy's LatentFunctionInference hooks (reference latent_function_inference/__init__.py:38-49)
-    def on_optimization_start(self):
-        pass
-
-    def on_optimization_end(self):
-        pass
-
     def to_dict(self):
         return {"class": "GPy.inference.latent_function_inference.exact_gaussian_inference.ExactGaussianInference"}
-
-    def __getstate__(self):          # device handles never travel (cf. reference rbf.py:313-318)
-        d = dict(self.__dict__)
-        d["_state"] = None
-        d["_last"] = None            # holds the device state of the last call
-        return d
 
     def LOO(self, kern, X, Y, likelihood, posterior, Y_metadata=None, K=None):
         """Leave-one-out log predictive densities (reference `exact_gaussian_inference.py:76-88`):
@@ -198,7 +208,7 @@ class ExactGaussianInference(object):
         return post, log_marginal, {"dL_dK": dL_dK, "dL_dthetaL": dL_dthetaL, "dL_dm": alpha}
 
 
-class ExactStudentTInference(object):
+class ExactStudentTInference(LatentFunctionInference):
     """Student-t PROCESS inference (reference `exact_studentt_inference.py:13-52`): `inference(kern, X, Y, nu, mean_function=None,
     K=None)` -> (posterior, log_marginal, {'dL_dK', 'dL_dnu', 'dL_dm'}).  Same device pipeline as the Gaussian case
     (C-ABI `mi355gp_exact_studentt_sum`); the kernel gradients ride on the lazy dL_dK like in `ExactGaussianInference`."""
@@ -207,19 +217,8 @@ class ExactStudentTInference(object):
         self.device, self.maxtries = device, maxtries
         self._state = None
 
-    def on_optimization_start(self):
-        pass
-
-    def on_optimization_end(self):
-        pass
-
     def to_dict(self):
         return {"class": "GPy.inference.latent_function_inference.exact_studentt_inference.ExactStudentTInference"}
-
-    def __getstate__(self):
-        d = dict(self.__dict__)
-        d["_state"] = None
-        return d
 
     def inference(self, kern, X, Y, nu, mean_function=None, K=None):
         from scipy.special import digamma

@@ -11,7 +11,7 @@ import warnings
 import numpy as np
 
 from . import _lib
-from .inference import _DeviceState
+from .inference import LatentFunctionInference, _DeviceState
 from .lazy import DeviceResult, kernel_signature
 from .linalg import jitter_ladder
 from .posterior import PosteriorExact
@@ -68,7 +68,7 @@ class LaplacePosterior(PosteriorExact):
         raise NotImplementedError("covariance_between_points is not implemented for a non-Gaussian likelihood on this backend")
 
 
-class Laplace(object):
+class Laplace(LatentFunctionInference):
     def __init__(self, device=0, maxtries=5):
         self.device, self.maxtries = device, maxtries
         self._mode_finding_tolerance = 1e-4
@@ -79,19 +79,8 @@ class Laplace(object):
         self._state = None
         self.iterations = 0                  # Newton steps of the last call
 
-    def on_optimization_start(self):
-        pass
-
-    def on_optimization_end(self):
-        pass
-
     def to_dict(self):
         return {"class": "GPy.inference.latent_function_inference.laplace.Laplace"}
-
-    def __getstate__(self):
-        d = dict(self.__dict__)
-        d["_state"] = None
-        return d
 
     def _W(self, likelihood, f, Y, Y_metadata):
         W = -likelihood.d2logpdf_df2(f, Y, Y_metadata=Y_metadata)

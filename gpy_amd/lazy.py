@@ -64,47 +64,48 @@ class ArrayIdentity(object):
         return self.obj if self.obj is not None else self.copy
 
 
-class DeviceResult(object):
+class LazyArray(object):
+    """The array protocol of a host view of a result that lives on the device: `np.asarray`, indexing, `.T`, `len`, arithmetic,
+    `copy / sum / dot` and pickling all go through `fetch()`, which materialises once and keeps the host copy.
+    A subclass supplies `shape`, `_materialise()` (the host array) and, unless the view belongs to a sparse session (`_bind`),
+    `_current()`: is the result still the latest of its context?  `stale` is what a fetch after a later call raises."""
     __array_priority__ = 100.0
-
-    def __init__(self, ctx, which, n, token, fortran_order=False, kernel_sig=None, fused_dtheta=None):
-        self._ctx = ctx
-        self._which = which
-        self._n = n
-        self._token = token          # inference call counter: a stale proxy must not read newer buffers
-        self._fortran = fortran_order
-        self._host = None
-        self._kernel_sig = kernel_sig
-        self.fused_dtheta = fused_dtheta
-
-    shape = property(lambda self: (self._n, self._n))
     ndim = 2
     dtype = np.dtype(np.float64)
-    size = property(lambda self: self._n * self._n)
+    stale = "device-resident result overwritten by a later inference call"
+    _host = None
+
+    size = property(lambda self: self.shape[0] * self.shape[1])
+
+    def _bind(self, session):
+        """a view of the evaluation `session` (a `sparse.SparseSession`) has just run"""
+        self._ctx, self._owner, self._token = session._ctx, session, session._token
+
+    def _current(self):
+        return self._owner._token == self._token
+
+    def _require_current(self):
+        if self._ctx is None:
+            raise RuntimeError("this result was detached from its device context (unpickled) before being fetched")
+        if not self._current():
+            raise RuntimeError(self.stale)
+
+    def fetch(self):
+        if self._host is None:
+            self._require_current()
+            self._host = self._materialise()
+        return self._host
 
     def __getstate__(self):
         """Pickling materialises the host copy (while the device still holds it) and drops the device handle."""
         d = dict(self.__dict__)
-        if d["_host"] is None and d["_ctx"] is not None:
+        if d.get("_host") is None:
             try:
                 d["_host"] = self.fetch()
             except Exception:
                 d["_host"] = None
         d["_ctx"] = None
         return d
-
-    def matches_kernel(self, kern):
-        return self.fused_dtheta is not None and self._kernel_sig == kernel_signature(kern)
-
-    def fetch(self):
-        if self._host is None:
-            if self._ctx is None:
-                raise RuntimeError("this result was detached from its device context (unpickled) before being fetched")
-            if self._ctx.call_token != self._token:
-                raise RuntimeError("this device-resident result was overwritten by a later inference call; "
-                                   "materialise it (np.asarray) before re-running inference")
-            self._host = self._ctx.fetch(self._which, fortran_order=self._fortran)
-        return self._host
 
     def __array__(self, dtype=None, copy=None):
         a = self.fetch()
@@ -114,7 +115,7 @@ class DeviceResult(object):
         return self.fetch()[idx]
 
     def __len__(self):
-        return self._n
+        return self.shape[0]
 
     @property
     def T(self):
@@ -129,9 +130,13 @@ class DeviceResult(object):
     def dot(self, other):
         return self.fetch().dot(other)
 
+    def __neg__(self):
+        return -self.fetch()
+
     def __repr__(self):
-        return "DeviceResult(which=%d, shape=%r, %s)" % (self._which, self.shape,
-                                                         "materialised" if self._host is not None else "on device")
+        which = "which=%d, " % self._which if hasattr(self, "_which") else ""
+        return "%s(%sshape=%r, %s)" % (type(self).__name__, which, self.shape,
+                                       "materialised" if self._host is not None else "on device")
 
 
 def _binop(name):
@@ -141,11 +146,84 @@ def _binop(name):
 
 
 for _n in ("__add__", "__radd__", "__sub__", "__rsub__", "__mul__", "__rmul__", "__truediv__", "__rtruediv__",
-           "__matmul__", "__rmatmul__", "__neg__"):
-    if _n == "__neg__":
-        setattr(DeviceResult, _n, lambda self: -self.fetch())
-    else:
-        setattr(DeviceResult, _n, _binop(_n))
+           "__matmul__", "__rmatmul__"):
+    setattr(LazyArray, _n, _binop(_n))
+
+
+class DeviceResult(LazyArray):
+    """One of the N x N results of an exact-path context (`inference._DeviceState`), `which` = `_lib.FETCH_*`."""
+    stale = ("this device-resident result was overwritten by a later inference call; "
+             "materialise it (np.asarray) before re-running inference")
+
+    def __init__(self, ctx, which, n, token, fortran_order=False, kernel_sig=None, fused_dtheta=None):
+        self._ctx, self._which, self._token = ctx, which, token    # token: a stale proxy must not read newer buffers
+        self.shape = (n, n)
+        self._fortran = fortran_order
+        self._kernel_sig = kernel_sig
+        self.fused_dtheta = fused_dtheta
+
+    def matches_kernel(self, kern):
+        return self.fused_dtheta is not None and self._kernel_sig == kernel_signature(kern)
+
+    def _current(self):
+        return self._ctx.call_token == self._token
+
+    def _materialise(self):
+        return self._ctx.fetch(self._which, fortran_order=self._fortran)
+
+
+class LazyMM(LazyArray):
+    """Lazy M x M result (`SparseContext.FETCH_*`) of a sparse session's last evaluation, times `scale` if one is given
+    (dL_dpsi2 = beta * dL_dpsi2_beta, `var_dtc.py:220-233`)."""
+
+    def __init__(self, session, which, M, scale=None):
+        self._bind(session)
+        self._which, self.shape, self._scale = which, (M, M), scale
+
+    def _materialise(self):
+        a = self._ctx.fetch(self._which)
+        return a if self._scale is None else self._scale * a
+
+
+class LazyNM(LazyArray):
+    """dL_dKnm (N x M) of a sparse session's last evaluation.  It is never resident as a whole on the device (3.3 GB at
+    N = 200000, M = 2048): gpy_amd's own model driver uses the reductions the device made from it (`grad_dict['fused']`); a
+    FOREIGN consumer -- e.g. GPy's `SparseGP._update_gradients` handing it to `kern.update_gradients_full(dL_dKnm, X, Z)`
+    (reference `core/sparse_gp.py:108-119`) -- gets it materialised in row blocks (`blocks()`), or entirely (`np.asarray`)."""
+
+    def __init__(self, session, N, M, block=8192):
+        self._bind(session)
+        self.shape, self._block = (N, M), block
+
+    def blocks(self, rows=None):
+        """yields (row0, row1, dL_dKnm[row0:row1]) over the whole matrix"""
+        self._require_current()
+        step = rows or self._block
+        for r0 in range(0, self.shape[0], step):
+            r1 = min(self.shape[0], r0 + step)
+            yield r0, r1, self._ctx.fetch_dL_dKnm(r0, r1 - r0)
+
+    def _materialise(self):
+        out = np.empty(self.shape)
+        for r0, r1, B in self.blocks():
+            out[r0:r1] = B
+        return out
+
+
+class LazyPsi1(LazyArray):
+    """dL_dpsi1 = beta R v^T (N x M, reference `var_dtc.py:219`) of an uncertain-input call.  The device forms it on the fly
+    inside the gradient kernels and never holds it; a foreign consumer gets the rank-Dy product from the host, formed anew
+    for every use: the view holds host arrays only, is always current and keeps no N x M copy."""
+
+    def __init__(self, beta, R, wv):
+        self._beta, self._R, self._wv = beta, R, wv
+        self.shape = (R.shape[0], wv.shape[0])
+
+    def fetch(self):
+        return self._beta * np.dot(self._R, self._wv.T)
+
+    def __getstate__(self):
+        return self.__dict__
 
 
 def kernel_signature(kern):

@@ -18,45 +18,20 @@ variance.  Refused by name: a mean function (the reference asserts), per-point n
 import numpy as np
 
 from . import _lib
-from .lazy import ArrayIdentity, kernel_signature
-from .linalg import jitter_ladder
-from .sparse import SparsePosterior, _LazyMM, _LazyNM, sparse_path_kernel_check
+from .lazy import LazyNM
+from .sparse import SparseSession, noise_variances, sparse_path_kernel_check
 from .variational import NormalPosterior
 
 
-class PEP(object):
+class PEP(SparseSession):
     const_jitter = 1e-6                                       # (pep.py:17, fitc.py:17; VarDTC's is 1e-8)
 
     def __init__(self, alpha, device=0, maxtries=5):
-        self.alpha, self.device, self.maxtries = alpha, device, maxtries
-        self._ctx = None
-        self._X = self._Y = None
-        self._token = 0
-        self.last_stage_ms = None
-        self.collect_stage_ms = False
-
-    def on_optimization_start(self):
-        pass
-
-    def on_optimization_end(self):
-        pass
+        super(PEP, self).__init__(device=device, maxtries=maxtries)
+        self.alpha = alpha
 
     def to_dict(self):
         return {"class": "GPy.inference.latent_function_inference.pep.PEP", "alpha": self.alpha}
-
-    def __getstate__(self):
-        d = dict(self.__dict__)
-        d["_ctx"] = None
-        d["_X"] = d["_Y"] = None
-        return d
-
-    def _ensure(self, X, Y):
-        """`VarDTC._ensure`: one context, `set_data` only when X or Y changed"""
-        if self._ctx is None:
-            self._ctx = _lib.SparseContext(self.device)
-        if self._X is None or not (self._X.matches(X) and self._Y.matches(Y)):
-            self._ctx.set_data(X, Y)
-            self._X, self._Y = ArrayIdentity(X), ArrayIdentity(Y)
 
     def _refusals(self, kern, X, likelihood, Y, mean_function, Y_metadata):
         """everything that is out of scope, by name, before a context exists; returns the noise variance"""
@@ -68,15 +43,14 @@ class PEP(object):
         alpha = float(self.alpha)
         if not (0.0 < alpha <= 1.0):
             raise ValueError("%s: alpha = %r is outside (0, 1] (1 is FITC; VarDTC is the limit alpha -> 0)" % (name, self.alpha))
-        sigma_n = np.atleast_1d(np.asarray(likelihood.gaussian_variance(Y_metadata), dtype=np.float64)).ravel()
+        sigma_n = noise_variances(likelihood, Y_metadata)
         if sigma_n.size > 1:                                      # pep.py:30-32, fitc.py:28-30
             raise NotImplementedError("%s: no hetero (per-point) noise with this implementation" % name)
         if np.ndim(Y) != 2 or np.shape(Y)[1] != 1:
             raise NotImplementedError("%s: %s output columns; one is covered (the reference's v.reshape(-1, 1))"
                                       % (name, np.shape(Y)[1] if np.ndim(Y) == 2 else "no"))
         sparse_path_kernel_check(kern)
-        if self._ctx is not None and getattr(self._ctx, "sharded", False):
-            raise NotImplementedError("%s: a row-sharded sparse context is not supported" % name)
+        self._refuse_sharded("%s: a row-sharded sparse context is not supported" % name)
         return float(sigma_n[0])
 
     def inference(self, kern, X, Z, likelihood, Y, mean_function=None, Y_metadata=None):
@@ -86,22 +60,14 @@ class PEP(object):
         R = _lib.f64(Y)
         self._ensure(Xs, R)
         specs = kern.part_specs()
-        # jitchol's ladder (util/linalg.py:56-75) for Kmm / A, on top of const_jitter (pep.py:40-41,50)
-        (r,), _ = jitter_ladder(lambda extra: self._ctx.pep(specs, Zs, s2, alpha, self.const_jitter + extra,
-                                                            want_stage_ms=self.collect_stage_ms),
-                                kern.diag_variance(), self.maxtries)
-        self._token += 1
-        self.last_stage_ms = r.get("stage_ms")
+        # the ladder's jitter comes on top of const_jitter (pep.py:40-41,50)
+        r = self._run(kern, lambda extra: self._ctx.pep(specs, Zs, s2, alpha, self.const_jitter + extra,
+                                                        want_stage_ms=self.collect_stage_ms))
         M, N = Zs.shape[0], Xs.shape[0]
-        C = _lib.SparseContext
-        tok = (M, self._token, self)
-        post = SparsePosterior(woodbury_inv=_LazyMM(self._ctx, C.FETCH_WOODBURY_INV, *tok),               # Kmmi - P (pep.py:91)
-                               woodbury_vector=r["woodbury_vector"],
-                               K=_LazyMM(self._ctx, C.FETCH_KMM, *tok), K_chol=_LazyMM(self._ctx, C.FETCH_LM, *tok),
-                               device={"ctx": self._ctx, "token": self._token, "owner": self, "sig": kernel_signature(kern)})
-        grad_dict = {"dL_dKmm": _LazyMM(self._ctx, C.FETCH_DLDKMM, *tok),
+        post, dL_dKmm = self._posterior(kern, M, r["woodbury_vector"])                   # woodbury_inv = Kmmi - P (pep.py:91)
+        grad_dict = {"dL_dKmm": dL_dKmm,
                      "dL_dKdiag": alpha * r["dL_dR"],                                                   # pep.py:88
-                     "dL_dKnm": _LazyNM(self._ctx, N, M, self._token, self),
+                     "dL_dKnm": LazyNM(self, N, M),
                      # likelihood.exact_inference_gradients(dL_dR) + 0.5 (1 - alpha) / alpha N / sigma_n (pep.py:86-87)
                      "dL_dthetaL": r["dnoise"],
                      "fused": {"dtheta": r["dtheta"], "dZ": r["dZ"]}}

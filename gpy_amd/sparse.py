@@ -22,8 +22,9 @@ gradients, subtracts the KL term of the standard normal prior, uploads a step's 
 import numpy as np
 
 from . import _lib
+from .inference import LatentFunctionInference
 from .kern import RBF, Add, Prod, White, exact_only_leaves
-from .lazy import ArrayIdentity, freeze, kernel_signature
+from .lazy import ArrayIdentity, LazyMM, LazyNM, LazyPsi1, freeze, kernel_signature
 from .likelihoods import Gaussian
 from .linalg import LinAlgError, jitter_ladder
 from .models import PredictionCallers
@@ -31,122 +32,26 @@ from .param import Param, Parameterized
 from .variational import NormalPosterior, NormalPrior
 
 
-class _LazyMM(object):
-    """Lazy M x M result of the last VarDTC call (fetched on np.asarray)."""
-    __array_priority__ = 100.0
+class SessionPosterior(object):
+    """A posterior made by a `SparseSession`: `_device` = {"ctx", "token", "owner", "sig"} names the context, the session
+    (`owner`), its evaluation count when the posterior was made and the kernel's signature."""
+    _device = None
 
-    def __init__(self, ctx, which, M, token, owner):
-        self._ctx, self._which, self._M, self._token, self._owner = ctx, which, M, token, owner
-        self._host = None
-
-    shape = property(lambda self: (self._M, self._M))
-    ndim = 2
-    dtype = np.dtype(np.float64)
-
-    def fetch(self):
-        if self._host is None:
-            if self._owner._token != self._token:
-                raise RuntimeError("device-resident result overwritten by a later inference call")
-            self._host = self._ctx.fetch(self._which)
-        return self._host
-
-    def __array__(self, dtype=None, copy=None):
-        a = self.fetch()
-        return a if dtype is None else a.astype(dtype, copy=False)
-
-    def __getitem__(self, idx):
-        return self.fetch()[idx]
-
-    @property
-    def T(self):
-        return self.fetch().T
+    def _live(self, kern=None):
+        """True while the posterior is the context's latest result (and, given a kernel, `kern` is the one it was made with)"""
+        dev = self._device
+        return (dev is not None and dev["owner"]._token == dev["token"]
+                and (kern is None or kernel_signature(kern) == dev["sig"]))
 
 
-class _LazyNM(object):
-    """dL_dKnm (N x M) of the last VarDTC call.  It is never resident as a whole on the device (3.3 GB at N = 200000,
-    M = 2048): gpy_amd's own model driver uses the reductions the device made from it (`grad_dict['fused']`); a FOREIGN
-    consumer -- e.g. GPy's `SparseGP._update_gradients` handing it to `kern.update_gradients_full(dL_dKnm, X, Z)`
-    (reference `core/sparse_gp.py:108-119`) -- gets it materialised in row blocks (`blocks()`), or entirely (`np.asarray`)."""
-    __array_priority__ = 100.0
-    ndim = 2
-    dtype = np.dtype(np.float64)
-
-    def __init__(self, ctx, N, M, token, owner, block=8192):
-        self._ctx, self.shape, self._token, self._owner, self._block = ctx, (N, M), token, owner, block
-        self._host = None
-
-    def blocks(self, rows=None):
-        """yields (row0, row1, dL_dKnm[row0:row1]) over the whole matrix"""
-        if self._owner._token != self._token:
-            raise RuntimeError("device-resident result overwritten by a later inference call")
-        step = rows or self._block
-        for r0 in range(0, self.shape[0], step):
-            r1 = min(self.shape[0], r0 + step)
-            yield r0, r1, self._ctx.fetch_dL_dKnm(r0, r1 - r0)
-
-    def fetch(self):
-        if self._host is None:
-            out = np.empty(self.shape)
-            for r0, r1, B in self.blocks():
-                out[r0:r1] = B
-            self._host = out
-        return self._host
-
-    def __array__(self, dtype=None, copy=None):
-        a = self.fetch()
-        return a if dtype is None else a.astype(dtype, copy=False)
-
-    def __getitem__(self, idx):
-        return self.fetch()[idx]
-
-    @property
-    def T(self):
-        return self.fetch().T
-
-
-class _LazyPsi1(object):
-    """dL_dpsi1 = beta R v^T (N x M, reference `var_dtc.py:219`) of an uncertain-input call.  The device forms it on the fly
-    inside the gradient kernels and never holds it; a foreign consumer gets the rank-Dy product from the host."""
-    __array_priority__ = 100.0
-    ndim = 2
-    dtype = np.dtype(np.float64)
-
-    def __init__(self, beta, R, wv):
-        self._beta, self._R, self._wv = beta, R, wv
-        self.shape = (R.shape[0], wv.shape[0])
-
-    def fetch(self):
-        return self._beta * np.dot(self._R, self._wv.T)
-
-    def __array__(self, dtype=None, copy=None):
-        a = self.fetch()
-        return a if dtype is None else a.astype(dtype, copy=False)
-
-    def __getitem__(self, idx):
-        return self.fetch()[idx]
-
-
-class _LazyScaledMM(_LazyMM):
-    """an M x M device result times a scalar (dL_dpsi2 = beta * dL_dpsi2_beta, `var_dtc.py:220-233`)"""
-
-    def __init__(self, scale, *a):
-        super(_LazyScaledMM, self).__init__(*a)
-        self._scale = scale
-
-    def fetch(self):
-        if self._host is None:
-            self._host = self._scale * super(_LazyScaledMM, self).fetch()
-        return self._host
-
-
-class SparsePosterior(object):
+class SparsePosterior(SessionPosterior):
     """`Posterior(woodbury_inv, woodbury_vector, K=Kmm, K_chol=Lm)` of the reference (`var_dtc.py:213`,
     `posterior.py:21-77`); prediction follows `Posterior._raw_predict` (`posterior.py:198-262`) and runs on the device
     (C-ABI `mi355gp_sparse_predict`) while the posterior is the context's latest result."""
 
     def __init__(self, woodbury_inv, woodbury_vector, K, K_chol, device=None):
         self.woodbury_inv, self.woodbury_vector, self.K, self.K_chol = woodbury_inv, woodbury_vector, K, K_chol
-        self._device = device            # (ctx, token, owner, kernel signature, specs builder)
+        self._device = device
 
     def __getstate__(self):
         d = dict(self.__dict__)
@@ -156,8 +61,7 @@ class SparsePosterior(object):
         return d
 
     def _raw_predict(self, kern, Xnew, pred_var, full_cov=False):
-        dev = self._device
-        live = dev is not None and dev["owner"]._token == dev["token"] and kernel_signature(kern) == dev["sig"]
+        dev, live = self._device, self._live(kern)
         if isinstance(Xnew, NormalPosterior):
             return self._raw_predict_uncertain(kern, Xnew, pred_var, full_cov, dev if live else None)
         if live:
@@ -233,39 +137,84 @@ def sparse_path_kernel_check(kern):
                                   "Bias factors and sums (Add) of those and of White / Bias parts")
 
 
-class VarDTC(object):
-    const_jitter = 1e-8
+def noise_variances(likelihood, Y_metadata, precision=None):
+    """the Gaussian noise variances as a flat array: the likelihood's, or 1 / precision where one is given (var_dtc.py:78-80)"""
+    if precision is None:
+        return np.atleast_1d(np.asarray(likelihood.gaussian_variance(Y_metadata), dtype=np.float64)).ravel()
+    return 1.0 / np.atleast_1d(np.asarray(precision, dtype=np.float64)).ravel()
+
+
+class SparseSession(LatentFunctionInference):
+    """The host side that `VarDTC`, `PEP` / `FITC` and `SVGP` share: one sparse device context, made on first use; the identities
+    of the (X, Y) it holds, so that `set_data` runs only when they change; and `_token`, the count of evaluations, by which a
+    posterior or a lazy view knows whether it is still the context's latest result.  An `inference` method is its refusals,
+    `_ensure`, one `_run` over a context call and the results built by `_posterior` / `_device_dict`."""
+    _device_members = ("_ctx", "_X", "_Y")
 
     def __init__(self, device=0, maxtries=5):
         self.device, self.maxtries = device, maxtries
         self._ctx = None
-        self._X = self._Y = self._S = None
+        self._X = self._Y = None
         self._token = 0
         self.last_stage_ms = None
         self.collect_stage_ms = False
 
-    def on_optimization_start(self):
-        pass
+    def _refuse_sharded(self, message):
+        if self._ctx is not None and getattr(self._ctx, "sharded", False):
+            raise NotImplementedError(message)
 
-    def on_optimization_end(self):
-        pass
+    def _ensure(self, X, Y):
+        """one context, `set_data` only when X or Y changed (True then): frozen arrays (the model driver's X / Y) are
+        recognised by identity, anything else by a full comparison"""
+        if self._ctx is None:
+            self._ctx = _lib.SparseContext(self.device)
+        if self._X is not None and self._X.matches(X) and self._Y.matches(Y):
+            return False
+        self._ctx.set_data(X, Y)
+        self._X, self._Y = ArrayIdentity(X), ArrayIdentity(Y)
+        return True
+
+    def _run(self, kern, call):
+        """One evaluation: `call(extra_jitter)` -> (info, result) on the context under jitchol's ladder (util/linalg.py:56-75)
+        for Kmm.  Its result is then the context's latest: everything made from earlier ones is stale."""
+        (r,), _ = jitter_ladder(call, kern.diag_variance(), self.maxtries)
+        self._token += 1
+        self.last_stage_ms = r.get("stage_ms")
+        return r
+
+    def _device_dict(self, kern):
+        return {"ctx": self._ctx, "token": self._token, "owner": self, "sig": kernel_signature(kern)}
+
+    def _posterior(self, kern, M, woodbury_vector):
+        """(`SparsePosterior` of the evaluation just run, its lazy dL_dKmm)"""
+        C = _lib.SparseContext
+        post = SparsePosterior(woodbury_inv=LazyMM(self, C.FETCH_WOODBURY_INV, M), woodbury_vector=woodbury_vector,
+                               K=LazyMM(self, C.FETCH_KMM, M), K_chol=LazyMM(self, C.FETCH_LM, M), device=self._device_dict(kern))
+        return post, LazyMM(self, C.FETCH_DLDKMM, M)
+
+
+class VarDTC(SparseSession):
+    const_jitter = 1e-8
+    _device_members = SparseSession._device_members + ("_S",)
+    _S = None                                                        # identity of the uploaded input variances
 
     def to_dict(self):
         return {"class": "GPy.inference.latent_function_inference.var_dtc.VarDTC"}
 
-    def __getstate__(self):
-        d = dict(self.__dict__)
-        d["_ctx"] = None
-        d["_X"] = d["_Y"] = d["_S"] = None
-        return d
-
     def _ensure(self, X, Y):
-        if self._ctx is None:
-            self._ctx = _lib.SparseContext(self.device)
-        # frozen arrays (the model driver's X / Y) are recognised by identity, anything else by a full comparison
-        if self._X is None or not (self._X.matches(X) and self._Y.matches(Y)):
-            self._ctx.set_data(X, Y)
-            self._X, self._Y, self._S = ArrayIdentity(X), ArrayIdentity(Y), None      # (set_data discards input variances)
+        if super(VarDTC, self)._ensure(X, Y):
+            self._S = None                                             # (set_data discards input variances)
+
+    def _ensure_uncertain(self, mu, S, R):
+        if (self._ctx is not None and self._X is not None and self._Y.matches(R) and self._X.value().shape == mu.shape
+                and not self._X.matches(mu)):
+            self._ctx.set_inputs(mu, S)                                # the same Y, new inputs: Y is not uploaded again
+            self._X, self._S = ArrayIdentity(mu), ArrayIdentity(S)
+        else:
+            self._ensure(mu, R)
+            if self._S is None or not self._S.matches(S):
+                self._ctx.set_input_variance(S)
+                self._S = ArrayIdentity(S)
 
     def _inference_uncertain(self, kern, qX, Z, likelihood, Y, Y_metadata, mean_function, precision, Z_tilde):
         """X is a `NormalPosterior`: the psi-statistics form of the same evaluation (reference `var_dtc.py:66-215` with
@@ -282,62 +231,38 @@ class VarDTC(object):
             raise NotImplementedError("uncertain inputs: exactly one RBF part is covered, got %d (%s)"
                                       % (len(rbfs), ", ".join(repr(p.name) for p in rbfs)))
         Y = np.asarray(Y, dtype=np.float64)
-        if precision is None:
-            noise = np.atleast_1d(np.asarray(likelihood.gaussian_variance(Y_metadata), dtype=np.float64)).ravel()
-        else:
-            noise = 1.0 / np.atleast_1d(np.asarray(precision, dtype=np.float64)).ravel()
+        noise = noise_variances(likelihood, Y_metadata, precision)
         if noise.size > 1:                                             # var_dtc.py:243
             raise NotImplementedError("heteroscedastic (per-point) noise is not implemented with uncertain inputs")
         mu, S, Zs = kern._slice_X(qX.mean), kern._slice_X(qX.variance), kern._slice_X(Z)
         R = _lib.f64(Y)
-        if self._ctx is not None and getattr(self._ctx, "sharded", False):
-            raise NotImplementedError("uncertain inputs are not supported by a row-sharded sparse context")
-        if (self._ctx is not None and self._X is not None and self._Y.matches(R) and self._X.value().shape == mu.shape
-                and not self._X.matches(mu)):
-            self._ctx.set_inputs(mu, S)                                # the same Y, new inputs: Y is not uploaded again
-            self._X, self._S = ArrayIdentity(mu), ArrayIdentity(S)
-        else:
-            self._ensure(mu, R)
-            if self._S is None or not self._S.matches(S):
-                self._ctx.set_input_variance(S)
-                self._S = ArrayIdentity(S)
+        self._refuse_sharded("uncertain inputs are not supported by a row-sharded sparse context")
+        self._ensure_uncertain(mu, S, R)
         specs = kern.part_specs()
-        (r,), _ = jitter_ladder(lambda extra: self._ctx.vardtc_uncertain(specs, Zs, noise, extra_jitter=extra,
-                                                                         want_stage_ms=self.collect_stage_ms),
-                                kern.diag_variance(), self.maxtries)
-        self._token += 1
-        self.last_stage_ms = r.get("stage_ms")
+        r = self._run(kern, lambda extra: self._ctx.vardtc_uncertain(specs, Zs, noise, extra_jitter=extra,
+                                                                     want_stage_ms=self.collect_stage_ms))
         M, N = Zs.shape[0], mu.shape[0]
-        lml = r["lml"] + (0.0 if Z_tilde is None else Z_tilde)
-        C = _lib.SparseContext
-        tok = (self._ctx, M, self._token, self)
-        post = SparsePosterior(woodbury_inv=_LazyMM(self._ctx, C.FETCH_WOODBURY_INV, *tok[1:]),
-                               woodbury_vector=r["woodbury_vector"],
-                               K=_LazyMM(self._ctx, C.FETCH_KMM, *tok[1:]), K_chol=_LazyMM(self._ctx, C.FETCH_LM, *tok[1:]),
-                               device={"ctx": self._ctx, "token": self._token, "owner": self, "sig": kernel_signature(kern)})
+        post, dL_dKmm = self._posterior(kern, M, r["woodbury_vector"])
         beta = float(1.0 / np.fmax(noise, self.const_jitter)[0])
-        grad_dict = {"dL_dKmm": _LazyMM(self._ctx, C.FETCH_DLDKMM, *tok[1:]),
+        grad_dict = {"dL_dKmm": dL_dKmm,
                      "dL_dpsi0": -0.5 * Y.shape[1] * beta * np.ones(N),             # var_dtc.py:218
-                     "dL_dpsi1": _LazyPsi1(beta, R, r["woodbury_vector"]),
-                     "dL_dpsi2": _LazyScaledMM(beta, self._ctx, C.FETCH_DLDPSI2_BETA, *tok[1:]),
+                     "dL_dpsi1": LazyPsi1(beta, R, r["woodbury_vector"]),
+                     "dL_dpsi2": LazyMM(self, _lib.SparseContext.FETCH_DLDPSI2_BETA, M, scale=beta),
                      "dL_dthetaL": likelihood.exact_inference_gradients(r["dnoise"], Y_metadata),
                      "fused": {"dtheta": r["dtheta"], "dZ": r["dZ"], "dmu": r["dmu"], "dS": r["dS"]}}
-        return post, lml, grad_dict
+        return post, r["lml"] + (0.0 if Z_tilde is None else Z_tilde), grad_dict
 
     def inference(self, kern, X, Z, likelihood, Y, Y_metadata=None, mean_function=None, precision=None, Lm=None,
                   dL_dKmm=None, psi0=None, psi1=None, psi2=None, Z_tilde=None):
-        if isinstance(X, NormalPosterior):
-            if any(a is not None for a in (Lm, dL_dKmm, psi0, psi1, psi2)):
-                raise NotImplementedError("precomputed statistics are not accepted by the MI355X sparse path")
-            return self._inference_uncertain(kern, X, Z, likelihood, Y, Y_metadata, mean_function, precision, Z_tilde)
-        sparse_path_kernel_check(kern)
+        uncertain = isinstance(X, NormalPosterior)
+        if not uncertain:
+            sparse_path_kernel_check(kern)
         if any(a is not None for a in (Lm, dL_dKmm, psi0, psi1, psi2)):
             raise NotImplementedError("precomputed statistics are not accepted by the MI355X sparse path")
+        if uncertain:
+            return self._inference_uncertain(kern, X, Z, likelihood, Y, Y_metadata, mean_function, precision, Z_tilde)
         Y = np.asarray(Y, dtype=np.float64)
-        if precision is None:                                          # var_dtc.py:78-80
-            noise = np.atleast_1d(np.asarray(likelihood.gaussian_variance(Y_metadata), dtype=np.float64)).ravel()
-        else:
-            noise = 1.0 / np.atleast_1d(np.asarray(precision, dtype=np.float64)).ravel()
+        noise = noise_variances(likelihood, Y_metadata, precision)
         het = noise.size > 1
         if het and mean_function is not None:                          # var_dtc.py:85-86
             raise ValueError("Mean function not implemented with uncertain inputs or heteroscedasticity")
@@ -346,30 +271,20 @@ class VarDTC(object):
         R = _lib.f64(Y - m)
         self._ensure(Xs, R)
         specs = kern.part_specs()
-        # jitchol's ladder (util/linalg.py:56-75) for Kmm / B
-        (r,), _ = jitter_ladder(lambda extra: self._ctx.vardtc_sum(specs, Zs, noise, extra_jitter=extra,
-                                                                   want_dL_dm=mean_function is not None,
-                                                                   want_stage_ms=self.collect_stage_ms),
-                                kern.diag_variance(), self.maxtries)
-        self._token += 1
-        self.last_stage_ms = r.get("stage_ms")
+        r = self._run(kern, lambda extra: self._ctx.vardtc_sum(specs, Zs, noise, extra_jitter=extra,
+                                                               want_dL_dm=mean_function is not None,
+                                                               want_stage_ms=self.collect_stage_ms))
         M, N = Zs.shape[0], Xs.shape[0]
-        lml = r["lml"] + (0.0 if Z_tilde is None else Z_tilde)
-        C = _lib.SparseContext
-        post = SparsePosterior(woodbury_inv=_LazyMM(self._ctx, C.FETCH_WOODBURY_INV, M, self._token, self),
-                               woodbury_vector=r["woodbury_vector"],
-                               K=_LazyMM(self._ctx, C.FETCH_KMM, M, self._token, self),
-                               K_chol=_LazyMM(self._ctx, C.FETCH_LM, M, self._token, self),
-                               device={"ctx": self._ctx, "token": self._token, "owner": self, "sig": kernel_signature(kern)})
+        post, dL_dKmm = self._posterior(kern, M, r["woodbury_vector"])
         beta = 1.0 / np.fmax(noise, self.const_jitter)
         dL_dR = (r["dnoise"][:, None] if r["dnoise"].ndim == 1 else r["dnoise"]) if het else r["dnoise"]   # N x Dy (var_dtc.py:240-256)
-        grad_dict = {"dL_dKmm": _LazyMM(self._ctx, C.FETCH_DLDKMM, M, self._token, self),
+        grad_dict = {"dL_dKmm": dL_dKmm,
                      "dL_dKdiag": -0.5 * Y.shape[1] * (beta * np.ones(N)),            # var_dtc.py:218
-                     "dL_dKnm": _LazyNM(self._ctx, N, M, self._token, self),
+                     "dL_dKnm": LazyNM(self, N, M),
                      "dL_dthetaL": likelihood.exact_inference_gradients(dL_dR, Y_metadata),
                      "dL_dm": r["dL_dm"],
                      "fused": {"dtheta": r["dtheta"], "dZ": r["dZ"]}}
-        return post, lml, grad_dict
+        return post, r["lml"] + (0.0 if Z_tilde is None else Z_tilde), grad_dict
 
 
 class SparseGP(PredictionCallers, Parameterized):
@@ -458,27 +373,39 @@ class SparseGP(PredictionCallers, Parameterized):
                                                    Y_metadata=self.Y_metadata if Y_metadata is None else Y_metadata)
         return mu, var
 
+    # ---- the optimiser's view of the parameters: positive ones (kernel, noise) in log space, the others untransformed --------
+    def _positive(self):
+        return np.concatenate([np.full(p.size, bool(p.positive)) for p in self.flattened_parameters()])
+
+    @property
+    def optimizer_array(self):
+        pos, p = self._positive(), self.param_array
+        return np.where(pos, np.log(np.where(pos, p, 1.0)), p)
+
+    @optimizer_array.setter
+    def optimizer_array(self, x):
+        pos = self._positive()
+        self.param_array = np.where(pos, np.exp(np.where(pos, x, 0.0)), x)
+
+    def _grads(self, x):
+        """gradient of the objective (the negative bound) in the optimiser's parameters at x"""
+        self.optimizer_array = x
+        pos, g = self._positive(), self.objective_function_gradients()
+        return np.where(pos, g * self.param_array, g)
+
     def optimize(self, max_iters=100, messages=False, gtol=1e-6):
-        """L-BFGS-B; positive parameters (kernel, noise) in log space, Z untransformed."""
+        """L-BFGS-B on `optimizer_array`"""
         from scipy.optimize import minimize
-        pos = np.concatenate([np.full(p.size, bool(p.positive)) for p in self.flattened_parameters()])
-
-        def to_x(p):
-            return np.where(pos, np.log(np.where(pos, p, 1.0)), p)
-
-        def from_x(x):
-            return np.where(pos, np.exp(np.where(pos, x, 0.0)), x)
 
         def f(x):
             try:
-                self.param_array = from_x(x)
+                g = self._grads(x)
             except LinAlgError:
                 return 1e300, np.zeros_like(x)
-            g = self.objective_function_gradients()
-            return self.objective_function(), np.where(pos, g * self.param_array, g)
-        res = minimize(f, to_x(self.param_array), jac=True, method="L-BFGS-B",
+            return self.objective_function(), g
+        res = minimize(f, self.optimizer_array, jac=True, method="L-BFGS-B",
                        options={"maxiter": max_iters, "gtol": gtol, "disp": bool(messages)})
-        self.param_array = from_x(res.x)
+        self.optimizer_array = res.x
         return res
 
 

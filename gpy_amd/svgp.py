@@ -15,15 +15,14 @@ Not covered: a mean function, uncertain inputs, `KL_scale != 1`, natural gradien
 import numpy as np
 
 from . import _lib
-from .lazy import ArrayIdentity, freeze, kernel_signature
-from .linalg import jitter_ladder
+from .lazy import LazyArray, freeze
 from .param import Param
-from .sparse import SparseGP, sparse_path_kernel_check
+from .sparse import SessionPosterior, SparseGP, SparseSession, sparse_path_kernel_check
 from .util import choleskies
 from .variational import NormalPosterior
 
 
-class SVGPPosterior(object):
+class SVGPPosterior(SessionPosterior):
     """`Posterior(mean=q_u_mean, cov=S.T, K=Kmm, prior_mean=0)` of the reference (`svgp.py:121`, `posterior.py:79-107,176-209`):
     woodbury_vector = Kmm^-1 m and woodbury_inv[:, :, d] = Kmm^-1 - Kmm^-1 S_d Kmm^-1 stay on the device and prediction
     (`posterior.py:220-248`) runs there (C-ABI `mi355gp_svgp_predict`) while the posterior is the context's latest result."""
@@ -32,14 +31,10 @@ class SVGPPosterior(object):
         self.mean, self._chol, self._device = mean, chol, device
         self._wv = self._winv = None
 
-    def _live(self):
-        dev = self._device
-        return dev is not None and dev["owner"]._token == dev["token"]
-
     def _fetch(self, want_inv):
         if self._wv is None or (want_inv and self._winv is None):
             if not self._live():
-                raise RuntimeError("device-resident result overwritten by a later inference call")
+                raise RuntimeError(LazyArray.stale)
             self._wv, wi = self._device["ctx"].svgp_woodbury(want_inv=want_inv)
             if wi is not None:
                 self._winv = wi
@@ -67,9 +62,8 @@ class SVGPPosterior(object):
         return d
 
     def _raw_predict(self, kern, Xnew, pred_var, full_cov=False):
-        dev = self._device
-        if self._live() and kernel_signature(kern) == dev["sig"]:
-            return dev["ctx"].svgp_predict(kern.part_specs(), kern._slice_X(Xnew), full_cov=full_cov)
+        if self._live(kern):
+            return self._device["ctx"].svgp_predict(kern.part_specs(), kern._slice_X(Xnew), full_cov=full_cov)
         Kx = kern.K(pred_var, Xnew)                                   # (M, N*): foreign kernel / stale device state
         wv, Wi = self.woodbury_vector, self.woodbury_inv
         mu = np.dot(Kx.T, wv)
@@ -81,38 +75,11 @@ class SVGPPosterior(object):
         return mu, np.clip(var, 1e-15, np.inf)                        # posterior.py:248
 
 
-class SVGP(object):
+class SVGP(SparseSession):
     """The inference class (reference `svgp.py:8-121`)."""
-
-    def __init__(self, device=0, maxtries=5):
-        self.device, self.maxtries = device, maxtries
-        self._ctx = None
-        self._X = self._Y = None
-        self._token = 0
-        self.last_stage_ms = None
-        self.collect_stage_ms = False
-
-    def on_optimization_start(self):
-        pass
-
-    def on_optimization_end(self):
-        pass
 
     def to_dict(self):
         return {"class": "GPy.inference.latent_function_inference.svgp.SVGP"}
-
-    def __getstate__(self):
-        d = dict(self.__dict__)
-        d["_ctx"] = None
-        d["_X"] = d["_Y"] = None
-        return d
-
-    def _ensure(self, X, Y):
-        if self._ctx is None:
-            self._ctx = _lib.SparseContext(self.device)
-        if self._X is None or not (self._X.matches(X) and self._Y.matches(Y)):
-            self._ctx.set_data(X, Y)
-            self._X, self._Y = ArrayIdentity(X), ArrayIdentity(Y)
 
     def inference(self, q_u_mean, q_u_chol, kern, X, Z, likelihood, Y, mean_function=None, Y_metadata=None, KL_scale=1.0,
                   batch_scale=1.0):
@@ -127,8 +94,7 @@ class SVGP(object):
             raise NotImplementedError("the %s likelihood has no variational_expectations, which SVGP needs (svgp.py:77)"
                                       % type(likelihood).__name__)
         sparse_path_kernel_check(kern)
-        if self._ctx is not None and getattr(self._ctx, "sharded", False):
-            raise NotImplementedError("SVGP is not supported by a row-sharded sparse context")
+        self._refuse_sharded("SVGP is not supported by a row-sharded sparse context")
         q_u_mean = _lib.f64(np.asarray(q_u_mean))
         Y = np.asarray(Y, dtype=np.float64)
         num_inducing, num_outputs = q_u_mean.shape
@@ -140,11 +106,8 @@ class SVGP(object):
         assert Zs.shape[0] == num_inducing, "q_u_mean does not match Z"
         self._ensure(Xs, _lib.f64(Y))
         specs = kern.part_specs()
-        # jitchol's ladder (util/linalg.py:56-75) for Kmm (svgp.py:40)
-        (fw,), _ = jitter_ladder(lambda extra: self._ctx.svgp_forward(specs, Zs, q_u_mean, L, extra_jitter=extra,
-                                                                      want_stage_ms=self.collect_stage_ms),
-                                 kern.diag_variance(), self.maxtries)
-        self._token += 1
+        fw = self._run(kern, lambda extra: self._ctx.svgp_forward(specs, Zs, q_u_mean, L, extra_jitter=extra,
+                                                                  want_stage_ms=self.collect_stage_ms))   # Kmm (svgp.py:40)
         # quadrature for the likelihood (svgp.py:77), rescaled if working on a batch (:80-82)
         F, dF_dmu, dF_dv, dF_dthetaL = likelihood.variational_expectations(Y, fw["mu"], fw["v"], Y_metadata=Y_metadata)
         F, dF_dmu, dF_dv = F * batch_scale, dF_dmu * batch_scale, dF_dv * batch_scale
@@ -154,7 +117,7 @@ class SVGP(object):
         if self.collect_stage_ms:
             self.last_stage_ms = {"forward": fw.get("stage_ms"), "backward": bw.get("stage_ms")}
         log_marginal = F.sum() - fw["KL"]                                                       # svgp.py:111
-        post = SVGPPosterior(q_u_mean, L, {"ctx": self._ctx, "token": self._token, "owner": self, "sig": kernel_signature(kern)})
+        post = SVGPPosterior(q_u_mean, L, self._device_dict(kern))
         grad_dict = {"dL_dKdiag": dF_dv.sum(1), "dL_dm": bw["dL_dm"], "dL_dchol": choleskies.triang_to_flat(bw["dL_dchol"]),
                      "dL_dthetaL": dF_dthetaL, "fused": {"dtheta": bw["dtheta"], "dZ": bw["dZ"]},
                      "mu": fw["mu"], "v": fw["v"], "KL": fw["KL"]}
@@ -244,26 +207,6 @@ class SVGPModel(SparseGP):
         """the next minibatch (X, Y) of the complete data (reference `core/svgp.py:88-93`)"""
         i = next(self.slicer)
         return self.X_all[i], self.Y_all[i]
-
-    # ---- the optimiser's view of the parameters: positive ones (kernel, likelihood) in log space, as `optimize()` has it -----
-    def _positive(self):
-        return np.concatenate([np.full(p.size, bool(p.positive)) for p in self.flattened_parameters()])
-
-    @property
-    def optimizer_array(self):
-        pos, p = self._positive(), self.param_array
-        return np.where(pos, np.log(np.where(pos, p, 1.0)), p)
-
-    @optimizer_array.setter
-    def optimizer_array(self, x):
-        pos = self._positive()
-        self.param_array = np.where(pos, np.exp(np.where(pos, x, 0.0)), x)
-
-    def _grads(self, x):
-        """gradient of the objective (the negative bound) in the optimiser's parameters at x"""
-        self.optimizer_array = x
-        pos, g = self._positive(), self.objective_function_gradients()
-        return np.where(pos, g * self.param_array, g)
 
     def stochastic_grad(self, parameters):
         """the gradient at `parameters` (an `optimizer_array`) on the next minibatch (reference `core/svgp.py:95-97`)"""

@@ -27,8 +27,61 @@ def test_library_builds_and_exports_every_declared_symbol():
     declared = product + debug
     for sym in declared:
         assert hasattr(lib, sym), "libmi355gp.so does not export %s" % sym
-    assert set(_lib.EXPORTED) <= set(declared)
+    assert set(_lib.EXPORTED) == set(declared)
     assert b"gfx950" in lib.mi355gp_version()
+
+
+def _prototypes(header):
+    """[(name, return type, [parameter type, ...])] of a header, in its order; a parameter's type is its text without `const`
+    and without the parameter's name"""
+    text = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", header)).read(), flags=re.S)
+    out = []
+    for ret, name, params in re.findall(r"\b(int|const char\s*\*)\s*(mi355gp_\w+)\s*\(([^)]*)\)\s*;", text):
+        params = [" ".join(p.split()) for p in params.split(",")]
+        types = [] if params == ["void"] else [re.sub(r"\bconst\b|\s|\w+$", "", re.sub(r"\s*\*\s*", "* ", p)) for p in params]
+        out.append((name, ret.replace(" ", ""), types))
+    return out
+
+
+def _type_class(c_type, bound):
+    """does the ctypes parameter type `bound` of the binding's table pass what the header declares as `c_type`?"""
+    import ctypes
+    nd = lambda dtype: getattr(bound, "_dtype_", None) == np.dtype(dtype)          # a numpy.ctypeslib.ndpointer class
+    if re.fullmatch(r"mi355gp_\w+\*\*", c_type):                                   # any context T**
+        return bound is ctypes.POINTER(ctypes.c_void_p)
+    return {"int": bound is ctypes.c_int,
+            "int64_t": bound is ctypes.c_int64,
+            "double": bound is ctypes.c_double,
+            "double*": nd(np.float64) or bound is ctypes.POINTER(ctypes.c_double),
+            "int*": bound is ctypes.POINTER(ctypes.c_int) or nd(np.int32),
+            "int64_t*": nd(np.int64),
+            "unsigned*": bound is ctypes.POINTER(ctypes.c_uint),
+            "void*": bound in (ctypes.c_char_p, ctypes.c_void_p),
+            "mi355gp_part*": bound is ctypes.POINTER(_lib.Part)}.get(c_type, bound is ctypes.c_void_p)    # else: a context T*
+
+
+def test_the_binding_table_states_every_prototype_of_the_headers():
+    """`_lib.ABI` against the text of the two headers, without loading the library: the same functions in the same order,
+    and for each the same number of parameters, each of the ctypes class that passes the declared C type (an int bound where
+    the header says int64_t is silent stack garbage).  Only the two `const char*` functions return anything but int, and
+    `_lib.lib()` sets `restype` for exactly those."""
+    protos = _prototypes("mi355gp.h") + _prototypes("mi355gp_debug.h")
+    assert len(protos) == 84 and len(set(p[0] for p in protos)) == 84
+    assert sorted(p[0] for p in protos) == sorted(_declared_symbols() + _declared_symbols("mi355gp_debug.h"))
+    assert [p[0] for p in protos] == list(_lib.ABI) == list(_lib.EXPORTED)
+    assert [p[0] for p in protos if p[1] != "int"] == ["mi355gp_last_error", "mi355gp_version"]
+    known = {"int", "int64_t", "double", "double*", "int*", "int64_t*", "unsigned*", "void*", "mi355gp_part*"}
+    bad = []
+    for name, _, types in protos:
+        bound = _lib.ABI[name]
+        if len(bound) != len(types):
+            bad.append("%s: %d parameters declared, %d bound" % (name, len(types), len(bound)))
+            continue
+        for i, (c, b) in enumerate(zip(types, bound)):
+            assert c in known or re.fullmatch(r"mi355gp_\w+\*\*?", c), "%s parameter %d: unknown C type %r" % (name, i, c)
+            if not _type_class(c, b):
+                bad.append("%s parameter %d: %s declared, %r bound" % (name, i, c, b))
+    assert not bad, "\n".join(bad)
 
 
 PRODUCT_ENV = {"MI355GP_TRANSPORT", "MI355GP_IPC_HOST", "MI355GP_IPC_TIMEOUT_S", "MI355GP_GRID_CHECK_SEQ", "MI355GP_GRAPH",
