@@ -11,7 +11,7 @@ from ._lib import MI355GPError, build, device_count
 from .inference import ExactGaussianInference, ExactStudentTInference
 from .laplace import Laplace, LaplacePosterior
 from .ep import EP
-from .kern import (OU, RBF, Add, Prod, Bias, Coregionalize, ExpQuad, Exponential, Linear, Matern32, Matern52, MLP, Poly, RatQuad,
+from .kern import (OU, RBF, Add, Prod, Bias, Coregionalize, Cosine, ExpQuad, ExpQuadCosine, Sinc, Exponential, Linear, Matern32, Matern52, MLP, Poly, RatQuad,
                    Stationary, StdPeriodic, White)
 from .likelihoods import Bernoulli, Gaussian, HeteroscedasticGaussian, MixedNoise, Poisson, StudentT
 from .models import GP, GPClassification, GPCoregionalizedRegression, GPHeteroscedasticRegression, GPRegression
@@ -22,7 +22,7 @@ from .svgp import SVGPModel as SVGP
 from .svgp import SVGPPosterior
 from .variational import NormalPosterior, NormalPrior
 
-__all__ = ["RBF", "OU", "ExpQuad", "HeteroscedasticGaussian", "StudentTPosterior", "Matern52", "Matern32", "Exponential", "RatQuad", "StdPeriodic", "Coregionalize", "Linear", "MLP", "Poly", "MixedNoise", "Stationary", "White", "Bias", "Add", "Prod", "Gaussian", "ExactGaussianInference", "ExactStudentTInference",
+__all__ = ["RBF", "OU", "ExpQuad", "HeteroscedasticGaussian", "StudentTPosterior", "Matern52", "Matern32", "Exponential", "RatQuad", "Cosine", "Sinc", "ExpQuadCosine", "StdPeriodic", "Coregionalize", "Linear", "MLP", "Poly", "MixedNoise", "Stationary", "White", "Bias", "Add", "Prod", "Gaussian", "ExactGaussianInference", "ExactStudentTInference",
            "PosteriorExact", "GP", "GPRegression", "GPHeteroscedasticRegression", "GPCoregionalizedRegression", "Laplace", "LaplacePosterior", "EP", "PosteriorEP", "Bernoulli", "StudentT", "Poisson", "GPClassification", "VarDTC", "SparseGP", "SparseGPRegression", "SVGP", "SVGPPosterior", "NormalPosterior", "NormalPrior", "BayesianGPLVM", "FITC", "PEP", "MI355GPError", "build", "device_count"]
 
 # GPy's import paths, so that `import gpy_amd as GPy` reads like the reference on this path:

@@ -16,7 +16,7 @@ LIB_PATH = os.environ.get("MI355GP_LIB") or os.path.join(_HERE, "libmi355gp.so")
 CSRC = os.path.join(_HERE, "csrc")
 
 KIND_IDS = {"rbf": 0, "matern52": 1, "matern32": 2, "exponential": 3, "white": 4, "bias": 5, "ratquad": 6, "stdperiodic": 7,
-            "coregionalize": 8, "linear": 9, "mlp": 10, "poly": 11}
+            "coregionalize": 8, "linear": 9, "mlp": 10, "poly": 11, "cosine": 12, "sinc": 13, "expquadcosine": 14}
 
 
 def ard_id(kind, ARD):

@@ -77,7 +77,7 @@ int ctx_prepare_parts(mi355gp_ctx* c, int nparts, const mi355gp_part* parts) {
     }
     for (int i = 0; i < nparts; ++i) {
         mi355gp_ctx::Part& p = c->parts[(size_t)i];
-        if (int rc = parse_part(parts[i], c->D, KS_STATIONARY | KS_STATIC | KS_EXT | KS_COREG | KS_LINEAR | KS_DOT, "exact-GP path", &p)) return rc;
+        if (int rc = parse_part(parts[i], c->D, KS_STATIONARY | KS_STATIC | KS_EXT | KS_COREG | KS_LINEAR | KS_DOT | KS_OSC, "exact-GP path", &p)) return rc;
         if (p.coreg()) {
             const int col = p.kp.col;
             if (c->hIdxCol != col) {                     // the training indices of this column, validated once per upload

@@ -315,7 +315,7 @@ int mi355gp_exact_studentt_sum(mi355gp_ctx* c, int nparts, const mi355gp_part* p
 int mi355gp_exact_inference(mi355gp_ctx* c, int kind, int ard, const double* theta, const double* noise,
                             int64_t noise_len, double jitter, double extra_jitter, double* out_scalars,
                             double* alpha_out, double* dtheta_out, double* diag_dLdK_out, double* stage_ms) {
-    if (int rc = check_kind(kind, KS_STATIONARY | KS_EXT | KS_LINEAR | KS_DOT, "mi355gp_exact_inference")) return rc;
+    if (int rc = check_kind(kind, KS_STATIONARY | KS_EXT | KS_LINEAR | KS_DOT | KS_OSC, "mi355gp_exact_inference")) return rc;
     const mi355gp_part part{kind, ard, 0, nullptr, theta};
     return mi355gp_exact_inference_sum(c, 1, &part, noise, noise_len, jitter, extra_jitter, out_scalars, alpha_out,
                                        dtheta_out, diag_dLdK_out, stage_ms);

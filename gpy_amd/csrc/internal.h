@@ -235,7 +235,7 @@ struct KernParams {
     int D;
     double variance;
     // kinds 6 / 7 only (the kernels of the other kinds never read them)
-    double power = 0.0;               // RatQuad: alpha; Poly: order
+    double power = 0.0;               // RatQuad: alpha; Poly: order; ExpQuadCosine: the period T
     const double* pw = nullptr;       // StdPeriodic, device [2 D]: pi / T_q, then 1 / l_q (0 outside the active dimensions)
                                       // Coregionalize, device [P x P]: B (row-major; P = ard)
     int col = 0;                      // Coregionalize only: the input row of Xt that holds the (unscaled) output index

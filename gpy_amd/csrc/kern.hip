@@ -1371,6 +1371,79 @@ __device__ __forceinline__ void ratquad_all(double var, double a, double r2, dou
     dk_a = -k * lg;
 }
 
+// Cosine (kind 12, stationary.py:664-680), Sinc (kind 13, :717-743) and ExpQuadCosine (kind 14, :682-713): functions of the
+// scaled distance r = sqrt(s) alone, in the kernels of RatQuad (inputs scaled by 1 / l).  Each helper returns K and (dK/dr) / r
+// from ONE sincos evaluation; (dK/dr) / r is 0 at r = 0, the reference's _inv_dist convention (:225-232).  The arguments of
+// Sinc and ExpQuadCosine are multiples of pi: sincospi reduces 2 r and 2 r / T exactly instead of a product with a rounded pi.
+//   Cosine:        K = var cos r,                           dK/dr = -var sin r
+//   Sinc:          K = var sinc(2 r) = var sin(2 pi r) / (2 pi r),  dK/dr = var (cos(2 pi r) - sinc(2 r)) / r
+//   ExpQuadCosine: K = var E cos(2 pi r / T), E = exp(-2 pi^2 r^2),  dK/dr = -4 pi^2 r K - var (2 pi / T) E sin(2 pi r / T),
+//                  dK/dT = var (2 pi r / T^2) E sin(2 pi r / T)     (kp.power carries T)
+#define OSC_2PI2 (2.0 * M_PI * M_PI)
+#define OSC_4PI2 (4.0 * M_PI * M_PI)
+
+__device__ __forceinline__ void cosine_all(double var, double s, double& k, double& dk_or) {
+    const double r = sqrt(s);
+    double sn, cs;
+    sincos(r, &sn, &cs);
+    k = var * cs;
+    dk_or = (r > 0.0) ? -var * sn / r : 0.0;
+}
+
+// cos t - sin t / t = sum_{k >= 1} (-1)^k 2k / (2k + 1)! u^k in u = t^2 = 4 pi^2 s.  Below u = 1 the difference of the two
+// rounded values would cancel (the reference switches to its leading term -u / 3 below r = 1e-5, :733-743); ten terms leave a
+// truncation of 22 / 23! < 1e-21 there.
+__device__ __forceinline__ double sinc_diff_series(double u) {
+    double p = 20.0 / 51090942171709440000.0;                  // 20 / 21!
+    p = fma(p, u, -18.0 / 121645100408832000.0);               // 18 / 19!
+    p = fma(p, u, 16.0 / 355687428096000.0);                   // 16 / 17!
+    p = fma(p, u, -14.0 / 1307674368000.0);                    // 14 / 15!
+    p = fma(p, u, 12.0 / 6227020800.0);                        // 12 / 13!
+    p = fma(p, u, -10.0 / 39916800.0);                         // 10 / 11!
+    p = fma(p, u, 8.0 / 362880.0);                             // 8 / 9!
+    p = fma(p, u, -6.0 / 5040.0);                              // 6 / 7!
+    p = fma(p, u, 4.0 / 120.0);                                // 4 / 5!
+    p = fma(p, u, -2.0 / 6.0);                                 // 2 / 3!
+    return p;                                                  // (cos t - sin t / t) / u
+}
+
+__device__ __forceinline__ void sinc_all(double var, double s, double& k, double& dk_or) {
+    const double x = 2.0 * sqrt(s), u = OSC_4PI2 * s;
+    double sn, cs;
+    sincospi(x, &sn, &cs);
+    const double snc = (x > 0.0) ? sn / (M_PI * x) : 1.0;
+    k = var * snc;
+    // (dK/dr) / r = var (cos t - sinc) / r^2 = 4 pi^2 var (cos t - sinc) / u
+    if (u < 1.0) dk_or = (s > 0.0) ? OSC_4PI2 * var * sinc_diff_series(u) : 0.0;
+    else dk_or = var * (cs - snc) / s;
+}
+
+__device__ __forceinline__ void eqc_all(double var, double T, double s, double& k, double& dk_or, double& dk_T) {
+    const double r = sqrt(s), e = var * exp(-OSC_2PI2 * s);
+    double sn, cs;
+    sincospi(2.0 * r / T, &sn, &cs);
+    const double w = 2.0 * M_PI / T * e * sn;                  // var (2 pi / T) E sin(2 pi r / T)
+    k = e * cs;
+    dk_or = (r > 0.0) ? -OSC_4PI2 * k - w / r : 0.0;
+    dk_T = w * r / T;
+}
+
+// K, (dK/dr) / r and the derivative by the kind's scalar parameter (RatQuad: power, ExpQuadCosine: period; 0 otherwise)
+template <int KIND>
+__device__ __forceinline__ void ext_all(const KernParams& kp, double s, double& k, double& dk_or, double& dk_p) {
+    if (KIND == MI355GP_RATQUAD) {
+        ratquad_all(kp.variance, kp.power, s, k, dk_or, dk_p);
+    } else if (KIND == MI355GP_COSINE) {
+        cosine_all(kp.variance, s, k, dk_or);
+        dk_p = 0.0;
+    } else if (KIND == MI355GP_SINC) {
+        sinc_all(kp.variance, s, k, dk_or);
+        dk_p = 0.0;
+    } else {
+        eqc_all(kp.variance, kp.power, s, k, dk_or, dk_p);
+    }
+}
+
 // s[a][b] += sum_q (sin(pi / T_q (xi[q][ty*4+a] - xj[q][tx*4+b])) / l_q)^2 over the staged dimensions q0 .. q0 + qc
 __device__ __forceinline__ void accum_per(const double* si, const double* sj, const double* __restrict__ pw, int D, int q0, int qc,
                                           int ty, int tx, double (&s)[4][4]) {
@@ -1391,17 +1464,23 @@ __device__ __forceinline__ void accum_per(const double* si, const double* sj, co
 template <int KIND>
 __device__ __forceinline__ void accum_ext(const double* si, const double* sj, const KernParams& kp, int q0, int qc, int ty, int tx,
                                           double (&s)[4][4]) {
-    if (KIND == MI355GP_RATQUAD) accum_r2(si, sj, qc, ty, tx, s);
+    if (KIND != MI355GP_STDPERIODIC) accum_r2(si, sj, qc, ty, tx, s);
     else accum_per(si, sj, kp.pw, kp.D, q0, qc, ty, tx, s);
 }
 
 template <int KIND>
 __device__ __forceinline__ double ext_k(const KernParams& kp, double s) {
     if (KIND == MI355GP_RATQUAD) return kp.variance * exp(-kp.power * log1p(0.5 * s));
+    if (KIND == MI355GP_COSINE) return kp.variance * cos(sqrt(s));
+    if (KIND == MI355GP_SINC) {
+        const double x = 2.0 * sqrt(s);
+        return kp.variance * ((x > 0.0) ? sinpi(x) / (M_PI * x) : 1.0);
+    }
+    if (KIND == MI355GP_EXPQUADCOSINE) return kp.variance * exp(-OSC_2PI2 * s) * cospi(2.0 * sqrt(s) / kp.power);
     return kp.variance * exp(-0.5 * s);
 }
 
-// Covariance assembly for the two kinds: no White-like diagonal in either.
+// Covariance assembly for these kinds: no White-like diagonal in any.
 template <bool SYM, int KIND>
 __global__ __launch_bounds__(256) void k_kbuild_ext(KbuildArgs A) {
     __shared__ __attribute__((aligned(16))) double si[KDC * KT];
@@ -1428,8 +1507,9 @@ __global__ __launch_bounds__(256) void k_kbuild_ext(KbuildArgs A) {
     }
 }
 
-// Gradient pass of k_grad for the two kinds, one launch per group of 32 dimensions (q_off).  Record A [GP_STRIDE] per block:
-//   [0] sum g K, RatQuad [1] sum g dK/dr r (isotropic) or [2 + q] sum g (dK/dr / r) (x~_iq - x~_jq)^2 (ARD),
+// Gradient pass of k_grad for these kinds, one launch per group of 32 dimensions (q_off).  Record A [GP_STRIDE] per block:
+//   [0] sum g K, RatQuad [1] sum g dK/dr r (isotropic) or [2 + q] sum g (dK/dr / r) (x~_iq - x~_jq)^2 (ARD)
+//   (Cosine, Sinc and ExpQuadCosine as RatQuad; record B [0] of ExpQuadCosine: sum g dK/dperiod, none for the other two),
 //   StdPeriodic [2 + q] sum g K sin(D_q) cos(D_q) D_q (period);
 // record B at partB: RatQuad [0] sum g dK/dpower, StdPeriodic [2 + q] sum g K sin^2(D_q) (lengthscale).
 // StdPeriodic always reduces per dimension; the host applies 1 / (T_q l_q^2), 1 / l_q^3 and sums the isotropic cases.
@@ -1442,6 +1522,7 @@ __global__ __launch_bounds__(256) void k_grad_ext(KernParams kp, const double* _
                                                   double* __restrict__ Hout, long ldh, const double* __restrict__ aa_scale,
                                                   const double* __restrict__ Mul, long ldm) {
     constexpr bool PER = (KIND == MI355GP_STDPERIODIC);
+    constexpr bool SCALAR = (KIND == MI355GP_RATQUAD || KIND == MI355GP_EXPQUADCOSINE);   // a scalar parameter: record B [0]
     __shared__ __attribute__((aligned(16))) double si[KDC * KT];
     __shared__ __attribute__((aligned(16))) double sj[KDC * KTJ];
     const int t = threadIdx.x, tx = t & 15, ty = t >> 4;
@@ -1464,7 +1545,7 @@ __global__ __launch_bounds__(256) void k_grad_ext(KernParams kp, const double* _
         int last_q0 = -1;
         for (int q0 = 0; q0 < kp.D; last_q0 = q0, q0 += KDC)
             accum_ext<KIND>(si, sj, kp, q0, stage_chunk(kp.D, q0, Xt1, ld1, i0, Xt2, ld2, j0, si, sj, t), ty, tx, s);
-        double gw[4][4];   // RatQuad: g dK/dr / r;  StdPeriodic: g K
+        double gw[4][4];   // functions of r: g dK/dr / r;  StdPeriodic: g K
 #pragma unroll
         for (int a = 0; a < 4; ++a) {
             const long i = i0 + ty * 4 + a;
@@ -1478,15 +1559,15 @@ __global__ __launch_bounds__(256) void k_grad_ext(KernParams kp, const double* _
                     gw[a][b] = g * k;
                 } else {
                     double k, dk_or, dk_a;
-                    ratquad_all(kp.variance, kp.power, s[a][b], k, dk_or, dk_a);
+                    ext_all<KIND>(kp, s[a][b], k, dk_or, dk_a);
                     a_var = fma(g, k, a_var);
-                    a_pow = fma(g, dk_a, a_pow);
+                    if (SCALAR) a_pow = fma(g, dk_a, a_pow);
                     if (!kp.ard) a_iso = fma(g, dk_or * s[a][b], a_iso);
                     gw[a][b] = g * dk_or;
                 }
             }
         }
-        // RatQuad: H = dL_dK (dK/dr) / r as in k_grad (0 at r = 0); StdPeriodic has its own dK/dx pass (k_periodic_gradx)
+        // functions of r: H = dL_dK (dK/dr) / r as in k_grad (0 at r = 0); StdPeriodic has its own dK/dx pass (k_periodic_gradx)
         if (!PER && !FUSED && Hout) {
 #pragma unroll
             for (int a = 0; a < 4; ++a)
@@ -1535,8 +1616,10 @@ __global__ __launch_bounds__(256) void k_grad_ext(KernParams kp, const double* _
     const double sv = block_sum(t, a_var);
     if (t == 0) outA[0] = sv;
     if (!PER) {
-        const double sp = block_sum(t, a_pow);
-        if (t == 0) outB[0] = sp;
+        if (SCALAR) {
+            const double sp = block_sum(t, a_pow);
+            if (t == 0) outB[0] = sp;
+        }
         if (!kp.ard) {
             const double sl = block_sum(t, a_iso);
             if (t == 0) outA[1] = sl;
@@ -1570,6 +1653,15 @@ static void launch_grad_ext(hipStream_t st, bool fused, KernParams kp, const dou
         if (per) {
             if (fused) GRAD_EXT(true, MI355GP_STDPERIODIC);
             else GRAD_EXT(false, MI355GP_STDPERIODIC);
+        } else if (kp.kind == MI355GP_COSINE) {
+            if (fused) GRAD_EXT(true, MI355GP_COSINE);
+            else GRAD_EXT(false, MI355GP_COSINE);
+        } else if (kp.kind == MI355GP_SINC) {
+            if (fused) GRAD_EXT(true, MI355GP_SINC);
+            else GRAD_EXT(false, MI355GP_SINC);
+        } else if (kp.kind == MI355GP_EXPQUADCOSINE) {
+            if (fused) GRAD_EXT(true, MI355GP_EXPQUADCOSINE);
+            else GRAD_EXT(false, MI355GP_EXPQUADCOSINE);
         } else {
             if (fused) GRAD_EXT(true, MI355GP_RATQUAD);
             else GRAD_EXT(false, MI355GP_RATQUAD);
@@ -2215,6 +2307,9 @@ static void launch_kbuild(hipStream_t st, long nblocks, const KbuildArgs& A) {
     case MI355GP_LINEAR: hipLaunchKernelGGL((k_kbuild_lin<SYM>), g, b, 0, st, A); break;
     case MI355GP_MLP: hipLaunchKernelGGL((k_kbuild_dot<SYM, MI355GP_MLP>), g, b, 0, st, A); break;
     case MI355GP_POLY: hipLaunchKernelGGL((k_kbuild_dot<SYM, MI355GP_POLY>), g, b, 0, st, A); break;
+    case MI355GP_COSINE: hipLaunchKernelGGL((k_kbuild_ext<SYM, MI355GP_COSINE>), g, b, 0, st, A); break;
+    case MI355GP_SINC: hipLaunchKernelGGL((k_kbuild_ext<SYM, MI355GP_SINC>), g, b, 0, st, A); break;
+    case MI355GP_EXPQUADCOSINE: hipLaunchKernelGGL((k_kbuild_ext<SYM, MI355GP_EXPQUADCOSINE>), g, b, 0, st, A); break;
     default:
         hipLaunchKernelGGL((k_kbuild<SYM>), g, b, 0, st, A.kp, A.Xt1, A.ld1, A.n, A.Xt2, A.ld2, A.m, A.out, A.ldo, A.nrows_out, A.noise,
                            A.noise_len, A.jit, A.lower_only, A.add_diag, A.ntc, A.accumulate, A.diag_same, A.mul);

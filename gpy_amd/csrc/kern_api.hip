@@ -36,7 +36,7 @@ int mi355gp_kern_K(int device, int kind, int ard, const double* theta, const dou
     if (sym) M = N;
     ARG_CHECK(M > 0, "mi355gp_kern_K: M must be positive");
     StatelessPart pt;
-    if (int rc = pt.load(kind, ard, theta, D, KS_STATIONARY | KS_EXT | KS_COREG | KS_LINEAR | KS_DOT, "mi355gp_kern_K", X, N, X2, M)) return rc;
+    if (int rc = pt.load(kind, ard, theta, D, KS_STATIONARY | KS_EXT | KS_COREG | KS_LINEAR | KS_DOT | KS_OSC, "mi355gp_kern_K", X, N, X2, M)) return rc;
     PointSet x1, x2;
     if (int rc = pt.scaled(x1, X, N)) return rc;
     if (!sym)
@@ -62,8 +62,8 @@ int mi355gp_kern_Kdiag(int kind, const double* theta, int64_t N, double* out) {
                           kind == MI355GP_MLP ? "var (2/pi) asin(p / (p + 1)), mlp.py:61-64" : "var (scale |x|^2 + bias)^order, poly.py:33-34");
         return -1;
     }
-    ARG_CHECK(kind_in(kind, KS_STATIONARY | KS_EXT) && theta && out && N >= 0, "mi355gp_kern_Kdiag: bad arguments");
-    // stationary: K(x,x) = variance (stationary.py:170-173); StdPeriodic likewise (standard_periodic.py:105-109)
+    ARG_CHECK(kind_in(kind, KS_STATIONARY | KS_EXT | KS_OSC) && theta && out && N >= 0, "mi355gp_kern_Kdiag: bad arguments");
+    // stationary (Cosine, Sinc, ExpQuadCosine included): K(x,x) = variance (stationary.py:170-173); StdPeriodic likewise (standard_periodic.py:105-109)
     for (int64_t i = 0; i < N; ++i) out[i] = theta[0];
     return 0;
 }
@@ -79,7 +79,7 @@ int mi355gp_update_gradients_full(int device, int kind, int ard, const double* t
     if (sym) M = N;
     ARG_CHECK(kind != MI355GP_COREGIONALIZE || M > 0, "mi355gp_update_gradients_full: M must be positive");
     StatelessPart pt;
-    if (int rc = pt.load(kind, ard, theta, D, KS_STATIONARY | KS_EXT | KS_COREG | KS_LINEAR | KS_DOT, "mi355gp_update_gradients_full", X, N, X2, M))
+    if (int rc = pt.load(kind, ard, theta, D, KS_STATIONARY | KS_EXT | KS_COREG | KS_LINEAR | KS_DOT | KS_OSC, "mi355gp_update_gradients_full", X, N, X2, M))
         return rc;
     PointSet x1, x2;
     if (int rc = pt.scaled(x1, X, N)) return rc;
@@ -126,7 +126,7 @@ int mi355gp_gradients_X(int device, int kind, int ard, const double* theta, cons
         return -1;
     }
     StatelessPart pt;
-    if (int rc = pt.load(kind, ard, theta, D, KS_STATIONARY | KS_EXT | KS_LINEAR | 1u << MI355GP_MLP, "mi355gp_gradients_X", nullptr, 0, nullptr, 0)) return rc;
+    if (int rc = pt.load(kind, ard, theta, D, KS_STATIONARY | KS_EXT | KS_LINEAR | 1u << MI355GP_MLP | KS_OSC, "mi355gp_gradients_X", nullptr, 0, nullptr, 0)) return rc;
     const bool sym = (X2 == nullptr);
     if (sym) { M = N; X2 = X; }
     ARG_CHECK(M > 0, "mi355gp_gradients_X: M must be positive");

@@ -22,12 +22,15 @@ enum : KindSet {
     KS_COREG = 1u << MI355GP_COREGIONALIZE,
     KS_LINEAR = 1u << MI355GP_LINEAR,                               // exact path only; Kdiag depends on the point
     KS_DOT = 1u << MI355GP_MLP | 1u << MI355GP_POLY,                // likewise: functions of x.x', x.x and x'.x' (k_kbuild_dot)
+    // exact path only: the oscillating functions of r, in RatQuad's kernels (k_kbuild_ext / k_grad_ext)
+    KS_OSC = 1u << MI355GP_COSINE | 1u << MI355GP_SINC | 1u << MI355GP_EXPQUADCOSINE,
 };
 static inline bool kind_in(int kind, KindSet s) { return kind >= 0 && kind < 32 && ((s >> kind) & 1u); }
 static inline const char* kind_name(int kind) {
     static const char* const names[] = {"RBF", "Matern52", "Matern32", "Exponential", "White", "Bias", "RatQuad",
-                                        "StdPeriodic", "Coregionalize", "Linear", "MLP", "Poly"};
-    return kind_in(kind, KS_STATIONARY | KS_STATIC | KS_EXT | KS_COREG | KS_LINEAR | KS_DOT) ? names[kind] : "unknown";
+                                        "StdPeriodic", "Coregionalize", "Linear", "MLP", "Poly", "Cosine", "Sinc",
+                                        "ExpQuadCosine"};
+    return kind_in(kind, KS_STATIONARY | KS_STATIC | KS_EXT | KS_COREG | KS_LINEAR | KS_DOT | KS_OSC) ? names[kind] : "unknown";
 }
 
 #define PART_FAIL(...)                    \
@@ -73,7 +76,8 @@ struct PartSpec {
     int tix = 0;                    // index of its summand in the terms of group_terms
     bool stationary() const { return kind_in(kp.kind, KS_STATIONARY); }
     bool is_static() const { return kind_in(kp.kind, KS_STATIC); }
-    bool ext() const { return kind_in(kp.kind, KS_EXT); }
+    // a second reduction record (ExpQuadCosine: its [0] = the period sum, as RatQuad's power; Cosine and Sinc have none)
+    bool ext() const { return kind_in(kp.kind, KS_EXT | 1u << MI355GP_EXPQUADCOSINE); }
     bool coreg() const { return kp.kind == MI355GP_COREGIONALIZE; }
     bool linear() const { return kp.kind == MI355GP_LINEAR; }
     bool mlp() const { return kp.kind == MI355GP_MLP; }
@@ -191,7 +195,8 @@ static inline int parse_part(const mi355gp_part& in, int D, KindSet accepted, co
         p->kp.bias = th[2];
         p->kp.power = th[3];
         nt = 4;
-    } else if (!p->is_static()) {                      // stationary and RatQuad: [variance, lengthscale (1 or n_active)(, power)]
+    } else if (!p->is_static()) {                      // stationary, Cosine, Sinc: [variance, lengthscale (1 or n_active)];
+                                                       // RatQuad: (, power); ExpQuadCosine: (, period), carried in kp.power
         const int nl = ard ? na : 1;
         for (int a = 0; a < na; ++a) {
             const double l = th[1 + (ard ? a : 0)];
@@ -203,6 +208,10 @@ static inline int parse_part(const mi355gp_part& in, int D, KindSet accepted, co
         if (kind == MI355GP_RATQUAD) {
             p->kp.power = th[nt++];
             if (int rc = positive(p->kp.power, "power")) return rc;
+        } else if (kind == MI355GP_EXPQUADCOSINE) {    // (link order stationary.py:692-695)
+            p->kp.power = th[nt++];
+            if (int rc = positive(p->kp.power, "period")) return rc;
+            if (!std::isfinite(p->kp.power)) PART_FAIL("%s: period %g of an ExpQuadCosine (kind %d) part is not finite", where, p->kp.power, kind);
         }
     }
     p->theta.assign(th, th + nt);
@@ -210,7 +219,7 @@ static inline int parse_part(const mi355gp_part& in, int D, KindSet accepted, co
 }
 
 // Gradient of one part in theta order from its reduction records (rec: the kind's first record, groups * GP_STRIDE;
-// rec2: the second record of RatQuad / StdPeriodic; Coregionalize: rec = S, P x P).  Returns the number written.
+// rec2: the second record of RatQuad / StdPeriodic / ExpQuadCosine; Coregionalize: rec = S, P x P).  Returns the number written.
 // stationary.py:199,210-213 (x already divided by l inside the kernels), 790-798; standard_periodic.py:501-526
 static inline int part_dtheta(const PartSpec& p, const double* rec, const double* rec2, double* o) {
     const double* th = p.theta.data();
@@ -262,7 +271,7 @@ static inline int part_dtheta(const PartSpec& p, const double* rec, const double
     if (!p.kp.ard) o[k++] = -rec[1] / th[1];           // dl = -S / l
     else
         for (int a = 0; a < na; ++a) o[k++] = -rec_at(rec, p.dims[a]) / th[1 + a];
-    if (p.kp.kind == MI355GP_RATQUAD) o[k++] = rec2[0];
+    if (p.kp.kind == MI355GP_RATQUAD || p.kp.kind == MI355GP_EXPQUADCOSINE) o[k++] = rec2[0];   // power / period (:703-709)
     return k;
 }
 

@@ -6,8 +6,8 @@
 slicing (`kern.py:112-117`), `+` / `*`, serialisation, the cached device K-build and gradient passes, and the expression
 interface through which the inference classes describe any kernel, leaf or combination, to the C-ABI (`leaves`, `part_specs`,
 `_slice_X`, `jitter_diag`).  The leaves: the stationary kernels `RBF` / `ExpQuad` / `Matern52` / `Matern32` / `Exponential` /
-`OU` / `RatQuad` (`GPy/kern/src/stationary.py`, `rbf.py`), `StdPeriodic`, `Coregionalize`, `Linear`, `MLP`, `Poly` and the static
-`White` / `Bias`; the combinations: `Add` and `Prod`.  Same constructor arguments, parameter names, link order and `.gradient`
+`OU` / `RatQuad` / `Cosine` / `Sinc` / `ExpQuadCosine` (`GPy/kern/src/stationary.py`, `rbf.py`), `StdPeriodic`,
+`Coregionalize`, `Linear`, `MLP`, `Poly` and the static `White` / `Bias`; the combinations: `Add` and `Prod`.  Same constructor arguments, parameter names, link order and `.gradient`
 side effects as the reference.  All array math runs in hand-written HIP kernels (csrc/kern.hip); there is no NumPy fallback.
 """
 import numpy as np
@@ -404,6 +404,63 @@ class RatQuad(Stationary):
     def to_dict(self):
         d = super(RatQuad, self).to_dict()
         d["power"] = self.power.values.tolist()
+        return d
+
+
+class Cosine(Stationary):
+    """k(r) = variance cos r  (reference `stationary.py:664-680`).  Positive definite over one input dimension only:
+    give it one active column, alone or times a kernel on the others (`RBF * Cosine`: the locally periodic kernel)."""
+    kind = "cosine"
+    _gpy_class = "GPy.kern.Cosine"
+
+    def __init__(self, input_dim, variance=1., lengthscale=None, ARD=False, active_dims=None, name="Cosine", **kw):
+        super(Cosine, self).__init__(input_dim, variance, lengthscale, ARD, active_dims, name, **kw)
+
+
+class Sinc(Stationary):
+    """k(r) = variance sinc(2 r) = variance sin(2 pi r) / (2 pi r)  (reference `stationary.py:717-743`): the band-limited
+    prior.  One active column, as `Cosine`."""
+    kind = "sinc"
+    _gpy_class = "GPy.kern.Sinc"
+
+    def __init__(self, input_dim, variance=1., lengthscale=None, ARD=False, active_dims=None, name="Sinc", **kw):
+        super(Sinc, self).__init__(input_dim, variance, lengthscale, ARD, active_dims, name, **kw)
+
+
+class ExpQuadCosine(Stationary):
+    """k(r) = variance exp(-2 pi^2 r^2) cos(2 pi r / period), one component of the spectral-mixture kernel of Wilson and
+    Adams 2013 (reference `stationary.py:682-713`): the stationary machinery plus a third parameter, `period`, linked
+    after the lengthscale (`:692-695`) and reduced on the device in the same gradient pass (`:703-709`).  One active
+    column, as `Cosine`; a sum of these learns periodicities from data."""
+    kind = "expquadcosine"
+    _gpy_class = "GPy.kern.ExpQuadCosine"
+
+    def __init__(self, input_dim, variance=1., lengthscale=None, period=1., ARD=False, active_dims=None,
+                 name="ExpQuadCosine", **kw):
+        super(ExpQuadCosine, self).__init__(input_dim, variance, lengthscale, ARD, active_dims, name, **kw)
+        self.period = Param("period", period)
+        assert self.period.size == 1
+        self.link_parameter(self.period)
+
+    def _theta(self):
+        return np.concatenate([super(ExpQuadCosine, self)._theta(), [float(self.period.values[0])]])
+
+    def _install_gradients(self, g):
+        super(ExpQuadCosine, self)._install_gradients(g[:-1])
+        self.period.gradient = g[-1]
+
+    def update_gradients_diag(self, dL_dKdiag, X):
+        """(reference `stationary.py:711-713`)"""
+        super(ExpQuadCosine, self).update_gradients_diag(dL_dKdiag, X)
+        self.period.gradient = 0.
+
+    def reset_gradients(self):
+        super(ExpQuadCosine, self).reset_gradients()
+        self.period.gradient = 0.
+
+    def to_dict(self):
+        d = super(ExpQuadCosine, self).to_dict()
+        d["period"] = self.period.values.tolist()
         return d
 
 
@@ -805,7 +862,7 @@ class Poly(Kern):
 # kernels the exact-GP device path evaluates as one part (the fused inference call takes them alone or in Add / Prod)
 DEVICE_KERNELS = (Stationary, StdPeriodic, Linear, MLP, Poly)
 # kinds only the exact path has (the sparse and grid paths reject them)
-EXACT_ONLY_KINDS = ("ratquad", "stdperiodic", "coregionalize", "linear", "mlp", "poly")
+EXACT_ONLY_KINDS = ("ratquad", "stdperiodic", "coregionalize", "linear", "mlp", "poly", "cosine", "sinc", "expquadcosine")
 
 
 def has_coregionalize(kern):
@@ -1128,4 +1185,4 @@ class Prod(CombinationKernel):
 
 KERNEL_CLASSES = {"rbf": RBF, "expquad": ExpQuad, "matern52": Matern52, "matern32": Matern32, "exponential": Exponential,
                   "white": White, "bias": Bias, "ratquad": RatQuad, "stdperiodic": StdPeriodic, "coregionalize": Coregionalize,
-                  "linear": Linear, "mlp": MLP, "poly": Poly}
+                  "linear": Linear, "mlp": MLP, "poly": Poly, "cosine": Cosine, "sinc": Sinc, "expquadcosine": ExpQuadCosine}

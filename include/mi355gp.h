@@ -27,7 +27,7 @@ typedef struct mi355gp_ctx mi355gp_ctx;
 enum { MI355GP_RBF = 0, MI355GP_MATERN52 = 1, MI355GP_MATERN32 = 2, MI355GP_EXPONENTIAL = 3,
        MI355GP_WHITE = 4, MI355GP_BIAS = 5 /* static kernels, only as parts of a sum (kern/src/static.py:63-98,151-173) */,
        MI355GP_RATQUAD = 6, MI355GP_STDPERIODIC = 7, MI355GP_COREGIONALIZE = 8, MI355GP_LINEAR = 9,
-       MI355GP_MLP = 10, MI355GP_POLY = 11 };
+       MI355GP_MLP = 10, MI355GP_POLY = 11, MI355GP_COSINE = 12, MI355GP_SINC = 13, MI355GP_EXPQUADCOSINE = 14 };
 
 /* The exact-GP entry points (single kind and part lists; not the sparse or grid paths) also take
  *   MI355GP_RATQUAD      k = var (1 + r^2/2)^-power (kern/src/stationary.py:747-802, GPy.kern.RatQuad);
@@ -78,6 +78,20 @@ enum { MI355GP_RBF = 0, MI355GP_MATERN52 = 1, MI355GP_MATERN32 = 2, MI355GP_EXPO
  *                          mi355gp_gradients_X and mi355gp_predictive_gradients_sum reject the kind.
  * Both alone, as a summand or as a factor of a product term.  mi355gp_kern_Kdiag (no X argument) and the sparse and grid
  * paths reject both. */
+
+/* The exact-GP entry points (single kind and part lists, the Laplace / EP session included), mi355gp_predictive_gradients_sum
+ * and the stateless mi355gp_kern_K / mi355gp_kern_Kdiag / mi355gp_update_gradients_full / mi355gp_gradients_X also take the
+ * three oscillating stationary kinds, functions of the scaled distance r = sqrt(sum_q ((x_q - x'_q) / l_q)^2) alone:
+ *   MI355GP_COSINE         k = var cos r (kern/src/stationary.py:664-680, GPy.kern.Cosine)
+ *   MI355GP_SINC           k = var sinc(2 r) = var sin(2 pi r) / (2 pi r), 1 at r = 0 (:717-743, GPy.kern.Sinc)
+ *   MI355GP_EXPQUADCOSINE  k = var exp(-2 pi^2 r^2) cos(2 pi r / T), one component of the spectral-mixture kernel (:682-713,
+ *                          GPy.kern.ExpQuadCosine)
+ * theta = [variance, lengthscale (1, or n_active if ard)] for Cosine and Sinc, [variance, lengthscale..., period] for
+ * ExpQuadCosine (link order :692-695); every value must be positive.  Gradients come back in theta order (the period's from
+ * :703-709).  K(x, x) = variance; dK/dr / r is taken as 0 at r = 0 (the _inv_dist convention, :225-232), so coinciding points
+ * add nothing to the lengthscale and X gradients.  Alone, as a summand or as a factor of a product term.  The kinds are positive
+ * definite over ONE input dimension only (cos |x - x'| is not for D > 1): give them one active column.  The sparse, grid and
+ * psi-statistics paths reject all three. */
 
 /* One part of a sum-of-products kernel expression (GPy.kern.Add, kern/src/add.py:58-84; GPy.kern.Prod,
  * kern/src/prod.py:58-99).  theta = [variance, lengthscale (1, or n_active if ard)] (static kinds: [variance]);
