@@ -80,6 +80,7 @@ def build(force=False):
     srcs = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".hip", ".h")) or f == "Makefile"]
     srcs.append(os.path.join(_HERE, "..", "include", "mi355gp.h"))
     srcs.append(os.path.join(_HERE, "..", "include", "mi355gp_debug.h"))
+    srcs.append(os.path.join(_HERE, "..", "include", "mi355gp_debug_lauum.h"))
     product = os.path.join(_HERE, "libmi355gp.so")
     if not force and os.path.exists(product) and os.path.exists(DIAG_LIB_PATH):
         t = min(os.path.getmtime(product), os.path.getmtime(DIAG_LIB_PATH))
@@ -189,6 +190,12 @@ ABI = {
     "mi355gp_dbg_mask_probe": [_ci, _ci, _ci, _dp],
 }
 EXPORTED = tuple(ABI)
+# include/mi355gp_debug_lauum.h: the diagnostics of X^T X on the 128 x 256 tile, in its order (tests/test_lauum_wide_map.py holds the
+# table against that header's prototypes)
+DEBUG_LAUUM_ABI = {
+    "mi355gp_dbg_lauum_wide_map": [_ci, _ip, _ci, _ip],
+    "mi355gp_dbg_lauum": [_ci, _i64, _c_dp, _c_dp, _ci, _ci, _c_dp],
+}
 
 
 def _opt(a):
@@ -202,8 +209,9 @@ def lib():
         if not os.path.exists(LIB_PATH):
             build()
         L = ctypes.CDLL(LIB_PATH)
-        for name, argtypes in ABI.items():
-            getattr(L, name).argtypes = argtypes
+        for table in (ABI, DEBUG_LAUUM_ABI):
+            for name, argtypes in table.items():
+                getattr(L, name).argtypes = argtypes
         L.mi355gp_last_error.restype = L.mi355gp_version.restype = _str
         _lib = L
     return _lib
@@ -953,3 +961,30 @@ def lauum_plan(nt):
     buf = (ctypes.c_int * (6 * max(n, 1)))()
     check(lib().mi355gp_dbg_lauum_plan(nt, buf, n, out4), "mi355gp_dbg_lauum_plan")
     return np.frombuffer(buf, dtype=np.int32, count=6 * n).reshape(n, 6).copy(), out4[1], out4[2], out4[3]
+
+
+def lauum_wide_map(nt):
+    """Host only: the work list of X^T X on 128 x 256 tiles for nt x nt tiles (csrc/lauum_policy.h): (items as an int array of rows
+    (ti, tj, column blocks, K), whether the policy gives this nt the wide tile, the policy's threshold in tiles)."""
+    out4 = (ctypes.c_int * 4)()
+    lib().mi355gp_dbg_lauum_wide_map(nt, None, 0, out4)
+    n = out4[0]
+    buf = (ctypes.c_int * (4 * max(n, 1)))()
+    check(lib().mi355gp_dbg_lauum_wide_map(nt, buf, n, out4), "mi355gp_dbg_lauum_wide_map")
+    return np.frombuffer(buf, dtype=np.int32, count=4 * n).reshape(n, 4).copy(), bool(out4[1]), out4[2]
+
+
+def dbg_lauum(X, variant, reps=0, device=0):
+    """W = X^T X of a lower-triangular X (n x n, n % 128 == 0) as one whole-K launch on the 128 x 128 tile (variant 0) or the
+    128 x 256 tile (variant 1): (W, ms per launch over `reps` further launches).  X an int n: a synthetic matrix made on the
+    device, W is None."""
+    require_device(device)
+    ms = ctypes.c_double(0.0)
+    if isinstance(X, (int, np.integer)):
+        check(lib().mi355gp_dbg_lauum(device, int(X), None, None, int(variant), int(reps), ctypes.byref(ms)), "mi355gp_dbg_lauum")
+        return None, ms.value
+    X = f64(X)
+    W = np.zeros_like(X)
+    check(lib().mi355gp_dbg_lauum(device, X.shape[0], X.ctypes.data_as(_c_dp), W.ctypes.data_as(_c_dp), int(variant), int(reps),
+                                  ctypes.byref(ms)), "mi355gp_dbg_lauum")
+    return W, ms.value

@@ -1,10 +1,12 @@
-// debug.hip -- the mi355gp_dbg_* probes of include/mi355gp_debug.h: measurements and self-checks for tests and tools, nothing
+// debug.hip -- the mi355gp_dbg_* probes of include/mi355gp_debug.h and mi355gp_debug_lauum.h: measurements and self-checks for tests and tools, nothing
 // an evaluation calls.
 #include <vector>
 
 #include "../../include/mi355gp.h"
 #include "../../include/mi355gp_debug.h"
+#include "../../include/mi355gp_debug_lauum.h"
 #include "internal.h"
+#include "lauum_policy.h"
 
 int run_peaks(int device, double* out4);
 
@@ -270,6 +272,74 @@ int mi355gp_dbg_lauum_plan(int nt, int* items_out, int max_items, int* out4) {
         const int row[6] = {it.ti, it.tj, it.q, it.k0, it.klen, it.part};
         for (int j = 0; j < 6; ++j) items_out[6 * i + j] = row[j];
     }
+    return 0;
+}
+
+// Host only: the work list of a k_lauum_wide launch for nt x nt tiles (lauum_policy.h; tests/test_lauum_wide_map.py checks that it
+// covers every lower block once), and what the policy says for this nt.
+int mi355gp_dbg_lauum_wide_map(int nt, int* items_out, int max_items, int* out4) {
+    ARG_CHECK(nt >= 1 && nt <= 4096 && out4 && (items_out || max_items == 0), "mi355gp_dbg_lauum_wide_map: bad arguments");
+    const long n = lauum_wide_items(nt);
+    int nwide = 0;
+    for (long b = 0; b < n; ++b) {
+        int ti, tj, wide;
+        lauum_wide_item(b, ti, tj, wide);
+        nwide += wide;
+        if (b < max_items) {
+            const int row[4] = {ti, tj, wide ? 2 : 1, (nt - ti) * NB};
+            for (int j = 0; j < 4; ++j) items_out[4 * b + j] = row[j];
+        }
+    }
+    out4[0] = (int)n;
+    out4[1] = lauum_wide_applies(nt, 0) ? 1 : 0;
+    out4[2] = LAUUM_WIDE_MIN_NT;
+    out4[3] = nwide;
+    return n > max_items ? -1 : 0;
+}
+
+// lower-triangular test matrix of mi355gp_dbg_lauum when the caller passes none: entries in [-1, 1) from a hash of the index
+__global__ void k_dbg_fill_lower(double* __restrict__ X, long n) {
+    for (long idx = (long)blockIdx.x * blockDim.x + threadIdx.x; idx < n * n; idx += (long)gridDim.x * blockDim.x) {
+        const long i = idx / n, j = idx - i * n;
+        unsigned long long h = (unsigned long long)idx * 0x9E3779B97F4A7C15ull;
+        h ^= h >> 29;
+        h *= 0xBF58476D1CE4E5B9ull;
+        h ^= h >> 32;
+        X[idx] = j <= i ? (double)(h >> 11) * (2.0 / 9007199254740992.0) - 1.0 : 0.0;
+    }
+}
+
+// Diagnostics: W = X^T X alone, as ONE whole-K launch on the tile of the caller's choice (variant 0: 128 x 128, k_lauum; 1: 128 x 256,
+// k_lauum_wide), whatever the policy would pick for this size, and its time.
+int mi355gp_dbg_lauum(int device, int64_t n, const double* X_host, double* W_host, int variant, int reps, double* ms) {
+    ARG_CHECK(n >= NB && n % NB == 0 && n <= 65536 && (variant == 0 || variant == 1) && reps >= 0 && (reps == 0 || ms),
+              "mi355gp_dbg_lauum: n a multiple of 128, variant 0 or 1, reps >= 0");
+    HIP_CHECK(hipSetDevice(device));
+    const int nt = (int)(n / NB);
+    DevBuf X, W;
+    HIP_CHECK(X.alloc(n * n));
+    HIP_CHECK(W.alloc(n * n));
+    if (X_host) HIP_CHECK(hipMemcpy(X, X_host, sizeof(double) * n * n, hipMemcpyHostToDevice));
+    else hipLaunchKernelGGL(k_dbg_fill_lower, dim3(4096), dim3(256), 0, 0, (double*)X, (long)n);
+    HIP_CHECK(hipMemset(W, 0, sizeof(double) * n * n));
+    launch_lauum_variant(0, X, W, n, nt, variant);
+    HIP_CHECK(hipDeviceSynchronize());
+    if (W_host) HIP_CHECK(hipMemcpy(W_host, W, sizeof(double) * n * n, hipMemcpyDeviceToHost));
+    if (reps > 0) {
+        hipEvent_t e0, e1;
+        HIP_CHECK(hipEventCreate(&e0));
+        HIP_CHECK(hipEventCreate(&e1));
+        HIP_CHECK(hipEventRecord(e0, 0));
+        for (int r = 0; r < reps; ++r) launch_lauum_variant(0, X, W, n, nt, variant);
+        HIP_CHECK(hipEventRecord(e1, 0));
+        HIP_CHECK(hipEventSynchronize(e1));
+        float t;
+        HIP_CHECK(hipEventElapsedTime(&t, e0, e1));
+        *ms = t / reps;
+        (void)hipEventDestroy(e0);
+        (void)hipEventDestroy(e1);
+    }
+    HIP_CHECK(hipGetLastError());
     return 0;
 }
 

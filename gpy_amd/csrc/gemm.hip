@@ -2,6 +2,7 @@
 // inverse (trtri) and X^T X (lauum).  One 128x128 output tile per workgroup; see gemm_tile.h.
 #include "gemm_tile.h"
 #include "internal.h"
+#include "lauum_policy.h"
 
 // kernels here use 72 KiB of dynamic LDS: opt in once per kernel
 #define LDS_OPT_IN(kernel)                                                                              \
@@ -342,6 +343,30 @@ __global__ __launch_bounds__(256) void k_lauum64(const double* __restrict__ X, d
     gt64_store<0>(W + r0 * ld + c0, ld, acc);
 }
 
+// The same on 128 x 256 tiles (gemm_tile.h, "128 x 256 output tile"): one workgroup per CU, work item b = (tile row ti, column
+// blocks {tj, tj + 1}) from lauum_policy.h, longest K first.  The diagonal block of an even ti has no partner and runs the
+// 128 x 128 code of k_lauum as an item of the same launch.  Same fma chain per element: bit-identical to k_lauum.
+__global__ __launch_bounds__(256, 1) void k_lauum_wide(const double* __restrict__ X, double* __restrict__ W, long ld, int nt) {
+    extern __shared__ __attribute__((aligned(16))) double smem[];
+    int ti, tj, wide;
+    lauum_wide_item((long)blockIdx.x, ti, tj, wide);
+    const int K = (nt - ti) * NB;
+    const double* Ap = X + (long)ti * NB * ld + (long)ti * NB;
+    const double* Bp = X + (long)ti * NB * ld + (long)tj * NB;
+    double* Wp = W + (long)ti * NB * ld + (long)tj * NB;
+    if (wide) {
+        d4 acc[8][4];
+        gtw_zero(acc);
+        gemm_tile_128x256<false, false>(Ap, ld, Bp, ld, K, acc, smem);
+        gtw_store(Wp, ld, acc);
+    } else {
+        d4 acc[4][GTCfg<4>::NI];
+        gt_zero<4>(acc);
+        gemm_tile_128<false, false, 4>(Ap, ld, Bp, ld, K, acc, smem);
+        gt_store<0, 4>(Wp, ld, acc);
+    }
+}
+
 // The same on a work list with the long k ranges CUT (small matrices: nt <= LAUUM_SPLIT_MAX_NT).  W(k,l) sums over the tile rows i >= k, so the
 // tiles of the first block columns carry K ~ N while most carry a fraction of it: one quadrant of tile (0,0) at N = 4096 is 3.4e7
 // flops, 0.44 ms at the quarter of a CU it gets while four workgroups share the CU -- alone more than the whole product needs at
@@ -484,6 +509,22 @@ static void launch_lauum_t(hipStream_t st, long nblocks, const double* X, double
     hipLaunchKernelGGL((k_lauum<NW>), dim3((unsigned)nblocks), dim3(NW * 64), GT_LDS_BYTES, st, X, W, ld, nt);
 }
 
+static void launch_lauum_wide(hipStream_t st, const double* X, double* W, long ld, int nt) {
+    static bool done = false;
+    if (!done) {
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_lauum_wide), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                  GTW_LDS_BYTES);
+        done = true;
+    }
+    hipLaunchKernelGGL(k_lauum_wide, dim3((unsigned)lauum_wide_items(nt)), dim3(256), GTW_LDS_BYTES, st, X, W, ld, nt);
+}
+
+// one whole-K launch on the tile of the caller's choice (mi355gp_dbg_lauum): 0 = 128 x 128 (k_lauum), 1 = 128 x 256 (k_lauum_wide)
+void launch_lauum_variant(hipStream_t st, const double* X, double* W, long ld, int nt, int variant) {
+    if (variant) launch_lauum_wide(st, X, W, ld, nt);
+    else launch_lauum_t<4>(st, (long)nt * (nt + 1) / 2, X, W, ld, nt);
+}
+
 bool lauum_uses_64(int nt) {
     static const int lauum64_max = env_int("LAUUM64_MAX", GEMM_DEFAULT_LAUUM64_MAX);
     return (long)nt * (nt + 1) / 2 <= lauum64_max;
@@ -494,6 +535,11 @@ void launch_lauum(hipStream_t st, const double* X, double* W, long ld, int nt) {
     static const int lauum64_max = env_int("LAUUM64_MAX", GEMM_DEFAULT_LAUUM64_MAX);
     if (nblocks <= lauum64_max) {
         hipLaunchKernelGGL(k_lauum64, dim3((unsigned)(4 * nblocks)), dim3(256), GT64_LDS_BYTES, st, X, W, ld, nt);
+        return;
+    }
+    static const int wide_on = env_int("LAUUM_WIDE", 1);       // diagnostics build: 0 = every size on the 128 x 128 tile
+    if (lauum_wide_applies(nt, !wide_on)) {
+        launch_lauum_wide(st, X, W, ld, nt);
         return;
     }
     launch_lauum_t<4>(st, nblocks, X, W, ld, nt);

@@ -4,7 +4,7 @@
 // accumulators (128 accumulator VGPRs; 2 workgroups per CU = 2 waves per SIMD).  K is consumed in slabs of 16 (four MFMA
 // k-slices); slabs are double-buffered in LDS and move global -> LDS by LDS-DMA (the pipeline is described at
 // gemm_tile_128_v3 below; the register-staged and 8-wave pipelines of rounds 1-2 measured within +-4 % of it and are gone,
-// DESIGN.md 6e).
+// DESIGN.md 6e).  X^T X of a large matrix runs on a 128x256 tile with one workgroup per CU instead: gemm_tile_128x256 below.
 //
 // Operand storage (row-major buffers with leading dimension ld):
 //   k-contiguous  : element (i, k) at P[i*ld + k]
@@ -300,6 +300,130 @@ __device__ __forceinline__ void gemm_tile_128_v3_multi(const double* const* __re
         __builtin_amdgcn_s_waitcnt(0x0F70);
         __syncthreads();
     }
+}
+
+// =====================================================================================================================
+// 128 x 256 output tile for a workgroup that owns the WHOLE CU: 256 threads = 4 waves, ONE wave per SIMD
+// (__launch_bounds__(256, 1): the unified 512-register file holds the wave's 256 accumulator registers), three LDS stages.
+// Against the 128 x 128 tile, per MFMA: fragment reads x 0.75 (12 per 32 MFMAs instead of 8 per 16), operand bytes into LDS x 0.75,
+// barriers x 0.5; nothing but the wave's own instruction order hides a stall here, so the pipeline is explicit:
+//   waves    : wave w owns rows 0..127 x columns 64 w .. 64 w + 63 = 8 x 4 accumulators.  (2 x 2 waves of 64 x 128 read the same 12
+//              fragments per half-slab from the same banks; 4 x 1 keeps the wave's B columns one scalar offset and the store rows
+//              512 B contiguous per wave.)
+//   slabs    : 16 deep, physical k = 4 kq + s for slice s, slices in ascending order, slabs in ascending order: every output
+//              element sees the fma chain of gemm_tile_128_v3 -- bit-identical results.
+//   LDS image: (TN: both operands m/n-contiguous) one stage is [16 k-rows][GTW_S = 388 doubles], columns 0..127 the A row,
+//              128..383 the B row; a k-row arrives as three LDS-DMAs of 128 doubles (1 KiB, lane-linear), wave w fetches k-rows
+//              4 w .. 4 w + 3 (12 DMAs per wave and slab).  Bank argument, as for GT3_SMN: a fragment read is ds_read_b64, served in
+//              two 32-lane groups; lanes 0-15 (kq even) read 16 consecutive doubles from a 16-double-aligned column = one aligned
+//              half (32 banks) of the 64-bank row, lanes 16-31 (kq odd) the same columns four k-rows on: 4 * 388 * 8 B = 12,416 B
+//              = 128 mod 256, the other half.  Any stride = 4 mod 8 doubles does it; 388 is the first >= 384.  Row starts are
+//              16-byte aligned (3,104 B) for the DMA.  388 * 8 B is also no multiple ds_read2_b64 / ds_read2st64_b64 can encode,
+//              so the reads stay full-rate ds_read_b64.
+//   stages   : three of 16 * 388 * 8 = 49,664 B (148,992 B in all).  Slab kt+3 is requested in the MIDDLE of slab kt, into the
+//              stage slab kt has just finished with: two slabs of DMAs are in flight at any time.
+//   order    : the barrier sits between the two half-slabs, not at the slab's end, so that the fragments of half-slab h + 1 are
+//              always requested before the MFMAs of half-slab h, across slab boundaries too (2 x 48 fragment registers).  Every
+//              LDS read and every DMA goes into the shadow of one MFMA, and the order is pinned (sched_barrier): left to the
+//              compiler's blocks of 12 reads / 12 DMAs the matrix pipe idles while a block issues (X^T X, N = 16384: 23.0 ms
+//              against 20.4).  F0 = fragments (kt, 0) on entry;
+//                 64 MFMAs on F0, the 12 fragments of F1 = (kt, 1) one behind each of the first 12;
+//                 s_waitcnt lgkmcnt(0) vmcnt(12);  s_barrier;
+//                 64 MFMAs on F1, the 12 DMAs of slab kt + 3 one behind each of the first 12, F0 = (kt + 1, 0) behind the next 12
+//              LDS-DMA rules (own DMAs covered by a counted vmcnt, then a barrier, before anyone reads): vmcnt(12) leaves
+//              slab kt+2's DMAs outstanding and retires this wave's of slab kt+1; after the barrier every wave's have landed, and
+//              the read of (kt + 1, 0) comes after it.  lgkmcnt(0) before the same barrier retires this wave's last reads of
+//              stage kt (F1 was requested before the MFMAs), so after it the stage is free for slab kt+3.
+#define GTW_S 388
+#define GTW_STAGE (16 * GTW_S)
+#define GTW_LDS_BYTES (3 * GTW_STAGE * 8)   // 148,992 B
+
+template <bool AK, bool BK>
+__device__ __forceinline__ void gemm_tile_128x256(const double* __restrict__ A, long lda, const double* __restrict__ B,
+                                                  long ldb, int K, d4 (&acc)[8][4], double* smem) {
+    static_assert(!AK && !BK, "gemm_tile_128x256: only the TN form (both operands m/n-contiguous) is built");
+    const int t = threadIdx.x, lane = t & 63, w = __builtin_amdgcn_readfirstlane(t >> 6), kq = lane >> 4;
+    const int nk = K / 16;
+    auto rsrc = [](const double* p) {
+        return __builtin_amdgcn_make_buffer_rsrc(const_cast<double*>(p), 0, 0x7fffffff, 0x00020000);
+    };
+    const int voff = lane * 16;                              // the lane's 16 bytes of a 1 KiB piece; k-row and piece are scalar
+    const int lda8 = (int)lda * 8, ldb8 = (int)ldb * 8;
+    // DMA i = 0..11 of this wave for one slab: k-row 4 w + i / 3, piece i % 3 (A row, first and second half of the B row)
+    auto dma = [&](__amdgpu_buffer_rsrc_t ra, __amdgpu_buffer_rsrc_t rb, int stage, int i) {
+        const int kr = 4 * w + i / 3, pc = i % 3;
+        double* d = smem + stage * GTW_STAGE + kr * GTW_S + pc * 128;
+        if (pc == 0) __builtin_amdgcn_raw_ptr_buffer_load_lds(ra, d, 16, voff, kr * lda8, 0, 0);
+        else __builtin_amdgcn_raw_ptr_buffer_load_lds(rb, d, 16, voff, kr * ldb8 + (pc - 1) * 1024, 0, 0);
+    };
+    // the base advances with k, as in gemm_tile_128_v3.  Past the last slab the last one is fetched again, into a stage nobody
+    // reads any more: every slab of the loop then has the same twelve DMAs behind it and the vmcnt counts hold to the end.
+    auto slab_a = [&](int slab) { return rsrc(A + (long)(slab < nk ? slab : nk - 1) * 16 * lda); };
+    auto slab_b = [&](int slab) { return rsrc(B + (long)(slab < nk ? slab : nk - 1) * 16 * ldb); };
+    const int fbase = 4 * kq * GTW_S + (lane & 15);
+    // fragment u = 0..11 of slices 2e, 2e+1 at p = stage + fbase + 2 e GTW_S: A rows 16 u (u < 8), B columns 16 (u - 8)
+    auto frag = [&](const double* p, int u, d2 (&af)[8], d2 (&bf)[4]) {
+        if (u < 8) af[u] = (d2){p[u * 16], p[GTW_S + u * 16]};
+        else bf[u - 8] = (d2){p[128 + 64 * w + (u - 8) * 16], p[GTW_S + 128 + 64 * w + (u - 8) * 16]};
+    };
+    d2 a0[8], b0[4], a1[8], b1[4];
+#pragma unroll
+    for (int sl = 0; sl < 3; ++sl) {
+        const __amdgpu_buffer_rsrc_t ra = slab_a(sl), rb = slab_b(sl);
+#pragma unroll
+        for (int i = 0; i < 12; ++i) dma(ra, rb, sl, i);
+    }
+    __builtin_amdgcn_s_waitcnt(0x4F78);                      // vmcnt(24): slab 0 has landed
+    __builtin_amdgcn_s_barrier();
+#pragma unroll
+    for (int u = 0; u < 12; ++u) frag(smem + fbase, u, a0, b0);
+    int cur = 0;                                             // stage of slab kt
+    for (int kt = 0; kt < nk; ++kt) {
+        const int nxt = cur == 2 ? 0 : cur + 1;
+        // With one wave per SIMD nothing but this wave's own order fills the 64 cycles of an MFMA: every LDS read and every DMA
+        // is issued in the shadow of one, and the order is pinned.
+        const double* p1 = smem + cur * GTW_STAGE + fbase + 2 * GTW_S;
+#pragma unroll
+        for (int i = 0; i < 64; ++i) {                       // half-slab (kt, 0) on F0; F1 = fragments (kt, 1) on the way
+            const int s = i >> 5, mi = (i >> 2) & 7, ni = i & 3;
+            acc[mi][ni] = mfma_f64(a0[mi][s], b0[ni][s], acc[mi][ni]);
+            if (i < 12) frag(p1, i, a1, b1);
+            __builtin_amdgcn_sched_barrier(0);
+        }
+        __builtin_amdgcn_s_waitcnt(0x007C);                  // lgkmcnt(0) vmcnt(12): slab kt+2 stays in flight, kt+1 is in LDS
+        __builtin_amdgcn_s_barrier();
+        const __amdgpu_buffer_rsrc_t ra = slab_a(kt + 3), rb = slab_b(kt + 3);
+        const double* p0 = smem + nxt * GTW_STAGE + fbase;
+#pragma unroll
+        for (int i = 0; i < 64; ++i) {                       // half-slab (kt, 1) on F1; slab kt+3 requested; F0 = (kt + 1, 0)
+            const int s = i >> 5, mi = (i >> 2) & 7, ni = i & 3;
+            acc[mi][ni] = mfma_f64(a1[mi][s], b1[ni][s], acc[mi][ni]);
+            if (i < 12) dma(ra, rb, cur, i);
+            else if (i < 24) frag(p0, i - 12, a0, b0);       // after the last slab: stale words nobody uses
+            __builtin_amdgcn_sched_barrier(0);
+        }
+        cur = nxt;
+    }
+    __builtin_amdgcn_s_waitcnt(0x0F70);                      // vmcnt(0): the re-fetched slabs must not outlive the workgroup's LDS
+}
+
+__device__ __forceinline__ void gtw_zero(d4 (&acc)[8][4]) {
+#pragma unroll
+    for (int mi = 0; mi < 8; ++mi)
+#pragma unroll
+        for (int ni = 0; ni < 4; ++ni) acc[mi][ni] = (d4){0.0, 0.0, 0.0, 0.0};
+}
+
+// C (pointer to the tile's (0,0) element) = acc: element (mi, ni, r) of this lane is C[(mi*16 + 4r + lane>>4) * ldc + 64w + ni*16 + (lane & 15)]
+__device__ __forceinline__ void gtw_store(double* __restrict__ C, long ldc, const d4 (&acc)[8][4]) {
+    const int t = threadIdx.x, lane = t & 63, w = t >> 6;
+    double* base = C + (long)(lane >> 4) * ldc + 64 * w + (lane & 15);
+#pragma unroll
+    for (int mi = 0; mi < 8; ++mi)
+#pragma unroll
+        for (int ni = 0; ni < 4; ++ni)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) base[(long)(mi * 16 + 4 * r) * ldc + ni * 16] = acc[mi][ni][r];
 }
 
 // =====================================================================================================================

@@ -21,6 +21,7 @@ void launch_trtri_level(hipStream_t st, const double* L, double* X, double* T, l
                         int stages = 3);
 // W (lower tiles) = X^T X for lower-triangular X
 void launch_lauum(hipStream_t st, const double* X, double* W, long ld, int nt);
+void launch_lauum_variant(hipStream_t st, const double* X, double* W, long ld, int nt, int variant);   // 0: 128 x 128 tile, 1: 128 x 256
 // X^T X of a SMALL matrix with the long k ranges cut into chunks (gemm.hip, "k_lauum64_items"): one quadrant chunk per item
 struct LauumItem { int ti, tj, q, k0, klen, part; };       // part: index of the 64 x 64 partial it stores, -1: stores W itself
 struct LauumSum { int ti, tj, q, first, n; };              // W quadrant = sum of partials first .. first + n - 1
