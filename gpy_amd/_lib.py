@@ -81,6 +81,7 @@ def build(force=False):
     srcs.append(os.path.join(_HERE, "..", "include", "mi355gp.h"))
     srcs.append(os.path.join(_HERE, "..", "include", "mi355gp_debug.h"))
     srcs.append(os.path.join(_HERE, "..", "include", "mi355gp_debug_lauum.h"))
+    srcs.append(os.path.join(_HERE, "..", "include", "mi355gp_debug_tileops.h"))
     product = os.path.join(_HERE, "libmi355gp.so")
     if not force and os.path.exists(product) and os.path.exists(DIAG_LIB_PATH):
         t = min(os.path.getmtime(product), os.path.getmtime(DIAG_LIB_PATH))
@@ -196,6 +197,12 @@ DEBUG_LAUUM_ABI = {
     "mi355gp_dbg_lauum_wide_map": [_ci, _ip, _ci, _ip],
     "mi355gp_dbg_lauum": [_ci, _i64, _c_dp, _c_dp, _ci, _ci, _c_dp],
 }
+# include/mi355gp_debug_tileops.h: one launcher of the tile-GEMM family alone (tests/test_oracle_tileops.py holds the table against
+# that header's prototype)
+DEBUG_TILEOPS_ABI = {
+    "mi355gp_dbg_tileop": [_ci, _ci, ctypes.POINTER(_i64), _c_dp, _c_dp, _c_dp, _cd],
+}
+TILEOPS = {"trmm_lower": 0, "trmm_lower_T": 1, "trmm64": 2, "gram_splitk": 3, "update_nt": 4}    # MI355GP_TILEOP_*
 
 
 def _opt(a):
@@ -209,7 +216,7 @@ def lib():
         if not os.path.exists(LIB_PATH):
             build()
         L = ctypes.CDLL(LIB_PATH)
-        for table in (ABI, DEBUG_LAUUM_ABI):
+        for table in (ABI, DEBUG_LAUUM_ABI, DEBUG_TILEOPS_ABI):
             for name, argtypes in table.items():
                 getattr(L, name).argtypes = argtypes
         L.mi355gp_last_error.restype = L.mi355gp_version.restype = _str
@@ -974,17 +981,44 @@ def lauum_wide_map(nt):
     return np.frombuffer(buf, dtype=np.int32, count=4 * n).reshape(n, 4).copy(), bool(out4[1]), out4[2]
 
 
-def dbg_lauum(X, variant, reps=0, device=0):
+def dbg_lauum(X, variant, reps=0, device=0, W0=None):
     """W = X^T X of a lower-triangular X (n x n, n % 128 == 0) as one whole-K launch on the 128 x 128 tile (variant 0) or the
-    128 x 256 tile (variant 1): (W, ms per launch over `reps` further launches).  X an int n: a synthetic matrix made on the
-    device, W is None."""
+    128 x 256 tile (variant 1), or as `lauum_device` launches it with a default workspace (variant 2; W then starts as W0):
+    (W, ms per launch over `reps` further launches).  X an int n: a synthetic matrix made on the device, W is None."""
     require_device(device)
     ms = ctypes.c_double(0.0)
     if isinstance(X, (int, np.integer)):
         check(lib().mi355gp_dbg_lauum(device, int(X), None, None, int(variant), int(reps), ctypes.byref(ms)), "mi355gp_dbg_lauum")
         return None, ms.value
     X = f64(X)
-    W = np.zeros_like(X)
+    W = np.zeros_like(X) if W0 is None else f64(W0).copy()
+    assert W.shape == X.shape and (W0 is None or variant == 2)
     check(lib().mi355gp_dbg_lauum(device, X.shape[0], X.ctypes.data_as(_c_dp), W.ctypes.data_as(_c_dp), int(variant), int(reps),
                                   ctypes.byref(ms)), "mi355gp_dbg_lauum")
     return W, ms.value
+
+
+def dbg_tileop(op, dims, X, B, Out, alpha=1.0, device=0):
+    """One launcher of the tile-GEMM family alone (include/mi355gp_debug_tileops.h): op a key of TILEOPS, dims its integers, X / B
+    the operands (None where the op has none), Out what the output buffer holds before the launch.  Returns the buffer after it
+    (same shape as Out); the shapes are checked here against what the entry point will read and write."""
+    require_device(device)
+    d = [int(v) for v in dims]
+    if op in ("trmm_lower", "trmm_lower_T", "trmm64"):
+        n, m = 128 * d[0], 128 * d[1]
+        shapes = ((n, n), (m, n) if op == "trmm64" and d[2] >= 2 else (n, m))
+        shapes += (shapes[1],)
+    elif op == "gram_splitk":
+        shapes = ((d[0], d[1]), None, (d[2], d[1], d[1]))
+    else:
+        n = d[0] + 128 * max(d[3] + d[1], d[4] + d[2])
+        shapes = (None, None, (n, n))
+    arrs = []
+    for a, shp in zip((X, B, Out), shapes):
+        assert (a is None) == (shp is None) and (a is None or np.shape(a) == shp), (op, d, shp)
+        arrs.append(None if a is None else f64(a))
+    out = arrs[2].copy()
+    da = (ctypes.c_int64 * len(d))(*d)
+    check(lib().mi355gp_dbg_tileop(device, TILEOPS[op], da, _opt(arrs[0]), _opt(arrs[1]), out.ctypes.data_as(_c_dp), float(alpha)),
+          "mi355gp_dbg_tileop")
+    return out

@@ -1,10 +1,11 @@
-// debug.hip -- the mi355gp_dbg_* probes of include/mi355gp_debug.h and mi355gp_debug_lauum.h: measurements and self-checks for tests and tools, nothing
+// debug.hip -- the mi355gp_dbg_* probes of include/mi355gp_debug.h, mi355gp_debug_lauum.h and mi355gp_debug_tileops.h: measurements and self-checks for tests and tools, nothing
 // an evaluation calls.
 #include <vector>
 
 #include "../../include/mi355gp.h"
 #include "../../include/mi355gp_debug.h"
 #include "../../include/mi355gp_debug_lauum.h"
+#include "../../include/mi355gp_debug_tileops.h"
 #include "internal.h"
 #include "lauum_policy.h"
 
@@ -309,29 +310,43 @@ __global__ void k_dbg_fill_lower(double* __restrict__ X, long n) {
     }
 }
 
-// Diagnostics: W = X^T X alone, as ONE whole-K launch on the tile of the caller's choice (variant 0: 128 x 128, k_lauum; 1: 128 x 256,
-// k_lauum_wide), whatever the policy would pick for this size, and its time.
+// Diagnostics: W = X^T X alone.  Variant 0 / 1: ONE whole-K launch on the tile of the caller's choice (0: 128 x 128, k_lauum; 1: 128 x 256,
+// k_lauum_wide), whatever the policy would pick for this size, and its time.  Variant 2: what the policy picks -- lauum_device with a
+// default workspace (k_lauum64, the split work list, k_lauum, k_lauum_wide by size); W starts as the caller's W, so tiles the
+// launchers must not write come back as they went in.
 int mi355gp_dbg_lauum(int device, int64_t n, const double* X_host, double* W_host, int variant, int reps, double* ms) {
-    ARG_CHECK(n >= NB && n % NB == 0 && n <= 65536 && (variant == 0 || variant == 1) && reps >= 0 && (reps == 0 || ms),
-              "mi355gp_dbg_lauum: n a multiple of 128, variant 0 or 1, reps >= 0");
+    ARG_CHECK(n >= NB && n % NB == 0 && n <= 65536 && variant >= 0 && variant <= 2 && reps >= 0 && (reps == 0 || ms),
+              "mi355gp_dbg_lauum: n a multiple of 128, variant 0, 1 or 2, reps >= 0");
     HIP_CHECK(hipSetDevice(device));
     const int nt = (int)(n / NB);
     DevBuf X, W;
+    WorkspaceGuard<1> guard;
+    hipStream_t st = 0;
+    if (variant == 2) {
+        if (factor_engine(device, &st, nullptr, nullptr) != 0) return -2;
+        if (factor_ws_alloc(&guard.ws, n) != 0) return -3;
+    }
     HIP_CHECK(X.alloc(n * n));
     HIP_CHECK(W.alloc(n * n));
     if (X_host) HIP_CHECK(hipMemcpy(X, X_host, sizeof(double) * n * n, hipMemcpyHostToDevice));
     else hipLaunchKernelGGL(k_dbg_fill_lower, dim3(4096), dim3(256), 0, 0, (double*)X, (long)n);
-    HIP_CHECK(hipMemset(W, 0, sizeof(double) * n * n));
-    launch_lauum_variant(0, X, W, n, nt, variant);
+    if (variant == 2 && W_host) HIP_CHECK(hipMemcpy(W, W_host, sizeof(double) * n * n, hipMemcpyHostToDevice));
+    else HIP_CHECK(hipMemset(W, 0, sizeof(double) * n * n));
+    HIP_CHECK(hipDeviceSynchronize());
+    auto launch = [&]() {
+        if (variant == 2) lauum_device(st, X, W, n, &guard.ws);
+        else launch_lauum_variant(st, X, W, n, nt, variant);
+    };
+    launch();
     HIP_CHECK(hipDeviceSynchronize());
     if (W_host) HIP_CHECK(hipMemcpy(W_host, W, sizeof(double) * n * n, hipMemcpyDeviceToHost));
     if (reps > 0) {
         hipEvent_t e0, e1;
         HIP_CHECK(hipEventCreate(&e0));
         HIP_CHECK(hipEventCreate(&e1));
-        HIP_CHECK(hipEventRecord(e0, 0));
-        for (int r = 0; r < reps; ++r) launch_lauum_variant(0, X, W, n, nt, variant);
-        HIP_CHECK(hipEventRecord(e1, 0));
+        HIP_CHECK(hipEventRecord(e0, st));
+        for (int r = 0; r < reps; ++r) launch();
+        HIP_CHECK(hipEventRecord(e1, st));
         HIP_CHECK(hipEventSynchronize(e1));
         float t;
         HIP_CHECK(hipEventElapsedTime(&t, e0, e1));
@@ -339,6 +354,79 @@ int mi355gp_dbg_lauum(int device, int64_t n, const double* X_host, double* W_hos
         (void)hipEventDestroy(e0);
         (void)hipEventDestroy(e1);
     }
+    HIP_CHECK(hipGetLastError());
+    return 0;
+}
+
+// Diagnostics: ONE launcher of the tile-GEMM family alone on the caller's operands (include/mi355gp_debug_tileops.h), with the
+// leading dimensions the product passes.  Out goes to the device before the launch and comes back after it.
+int mi355gp_dbg_tileop(int device, int op, const int64_t* dims, const double* X_host, const double* B_host, double* Out_host,
+                       double alpha) {
+    ARG_CHECK(dims && Out_host && op >= MI355GP_TILEOP_TRMM_LOWER && op <= MI355GP_TILEOP_UPDATE_NT, "mi355gp_dbg_tileop: bad arguments");
+    const int64_t lim = 64;                                     // tiles per dimension: a test tool, not a benchmark
+    long nx = 0, nb = 0, no = 0;                               // doubles of X, B, Out
+    long n = 0, m = 0;
+    switch (op) {
+        case MI355GP_TILEOP_TRMM_LOWER:
+        case MI355GP_TILEOP_TRMM_LOWER_T:
+        case MI355GP_TILEOP_TRMM64:
+            ARG_CHECK(dims[0] >= 1 && dims[0] <= lim && dims[1] >= 1 && dims[1] <= lim &&
+                          (op != MI355GP_TILEOP_TRMM64 || (dims[2] >= 0 && dims[2] <= 3)) && X_host && B_host,
+                      "mi355gp_dbg_tileop: trmm needs 1 <= nt, ntc <= 64, mode 0..3, X and B");
+            n = dims[0] * NB;
+            m = dims[1] * NB;
+            nx = n * n;
+            nb = no = n * m;
+            break;
+        case MI355GP_TILEOP_GRAM_SPLITK:
+            ARG_CHECK(dims[0] >= 16 && dims[1] >= NB && dims[1] % NB == 0 && dims[1] <= lim * NB && dims[2] >= 1 && dims[2] <= 64 &&
+                          dims[0] % (16 * dims[2]) == 0 && dims[0] <= (1 << 20) && X_host,
+                      "mi355gp_dbg_tileop: gram_splitk needs rows % (16 S) == 0, mp % 128 == 0, the panel in X");
+            n = dims[0];
+            m = dims[1];
+            nx = n * m;
+            no = dims[2] * m * m;
+            break;
+        default:
+            ARG_CHECK(dims[0] >= 16 && dims[0] % NB == 0 && dims[0] <= lim * NB && dims[1] >= 1 && dims[2] >= 1 && dims[3] >= 0 &&
+                          dims[4] >= 0 && dims[3] + dims[1] <= lim && dims[4] + dims[2] <= lim,
+                      "mi355gp_dbg_tileop: update_nt needs K % 128 == 0 and a region of at most 64 tiles per dimension");
+            n = dims[0] + NB * (dims[3] + dims[1] > dims[4] + dims[2] ? dims[3] + dims[1] : dims[4] + dims[2]);
+            no = n * n;
+            break;
+    }
+    HIP_CHECK(hipSetDevice(device));
+    DevBuf X, B, Out;
+    if (nx) {
+        HIP_CHECK(X.alloc(nx));
+        HIP_CHECK(hipMemcpy(X, X_host, sizeof(double) * nx, hipMemcpyHostToDevice));
+    }
+    if (nb) {
+        HIP_CHECK(B.alloc(nb));
+        HIP_CHECK(hipMemcpy(B, B_host, sizeof(double) * nb, hipMemcpyHostToDevice));
+    }
+    HIP_CHECK(Out.alloc(no));
+    HIP_CHECK(hipMemcpy(Out, Out_host, sizeof(double) * no, hipMemcpyHostToDevice));
+    const int nt = (int)dims[0], nto = (int)dims[1];
+    switch (op) {
+        case MI355GP_TILEOP_TRMM_LOWER: launch_trmm_lower(0, X, n, B, m, Out, m, nt, nto); break;
+        case MI355GP_TILEOP_TRMM_LOWER_T: launch_trmm_lower_T(0, X, n, B, m, Out, m, nt, nto); break;
+        case MI355GP_TILEOP_TRMM64: {
+            const long ldb = dims[2] < 2 ? m : n;              // B and Out: n x m for X B / X^T B, m x n for B X^T / B X
+            launch_trmm64(0, (int)dims[2], X, n, B, ldb, Out, ldb, nt, nto, alpha);
+            break;
+        }
+        case MI355GP_TILEOP_GRAM_SPLITK: launch_gram_splitk(0, X, m, n, m, (int)dims[2], (int)dims[3], Out); break;
+        default: {
+            const long K = dims[0], r0 = K + dims[3] * NB, c0 = K + dims[4] * NB;
+            double* A = Out;
+            launch_update_nt(0, A + r0 * n + c0, n, A + r0 * n, n, A + c0 * n, n, (int)K, (int)dims[1], (int)dims[2], (int)(r0 / NB),
+                             (int)(c0 / NB));
+            break;
+        }
+    }
+    HIP_CHECK(hipDeviceSynchronize());
+    HIP_CHECK(hipMemcpy(Out_host, Out, sizeof(double) * no, hipMemcpyDeviceToHost));
     HIP_CHECK(hipGetLastError());
     return 0;
 }

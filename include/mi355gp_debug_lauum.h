@@ -16,7 +16,10 @@ int mi355gp_dbg_lauum_wide_map(int nt, int* items, int max_items, int* out4);
 /* Diagnostics: W = X^T X of a lower-triangular n x n matrix (row-major, n a multiple of 128; only tiles on and below the diagonal are
  * read) as ONE whole-K launch on the 128 x 128 tile (variant 0) or the 128 x 256 tile (variant 1), and the average milliseconds of
  * `reps` further launches (reps = 0: none).  X == NULL: a synthetic matrix made on the device; W == NULL: nothing is copied back.
- * W gets the blocks on and below the diagonal; the rest is zero. */
+ * W gets the blocks on and below the diagonal; the rest is zero.
+ * Variant 2: the product's own choice instead -- lauum_device with a default workspace (k_lauum64 up to 8 tiles per dimension, then
+ * the split work list, k_lauum, k_lauum_wide by size).  W is then copied to the device BEFORE the launch as well: blocks above the
+ * diagonal, which no X^T X kernel may write, come back as they went in (tests/test_gpu_tileops.py). */
 int mi355gp_dbg_lauum(int device, int64_t n, const double* X, double* W, int variant, int reps, double* ms);
 
 #ifdef __cplusplus
