@@ -18,12 +18,13 @@ from .models import GP, GPClassification, GPCoregionalizedRegression, GPHeterosc
 from .posterior import PosteriorEP, PosteriorExact, StudentTPosterior
 from .sparse import BayesianGPLVM, SparseGP, SparseGPRegression, VarDTC
 from .pep import FITC, PEP
+from .epdtc import EPDTC, SparseGPClassification
 from .svgp import SVGPModel as SVGP
 from .svgp import SVGPPosterior
 from .variational import NormalPosterior, NormalPrior
 
 __all__ = ["RBF", "OU", "ExpQuad", "HeteroscedasticGaussian", "StudentTPosterior", "Matern52", "Matern32", "Exponential", "RatQuad", "Cosine", "Sinc", "ExpQuadCosine", "StdPeriodic", "Coregionalize", "Linear", "MLP", "Poly", "MixedNoise", "Stationary", "White", "Bias", "Add", "Prod", "Gaussian", "ExactGaussianInference", "ExactStudentTInference",
-           "PosteriorExact", "GP", "GPRegression", "GPHeteroscedasticRegression", "GPCoregionalizedRegression", "Laplace", "LaplacePosterior", "EP", "PosteriorEP", "Bernoulli", "StudentT", "Poisson", "GPClassification", "VarDTC", "SparseGP", "SparseGPRegression", "SVGP", "SVGPPosterior", "NormalPosterior", "NormalPrior", "BayesianGPLVM", "FITC", "PEP", "MI355GPError", "build", "device_count"]
+           "PosteriorExact", "GP", "GPRegression", "GPHeteroscedasticRegression", "GPCoregionalizedRegression", "Laplace", "LaplacePosterior", "EP", "PosteriorEP", "Bernoulli", "StudentT", "Poisson", "GPClassification", "VarDTC", "SparseGP", "SparseGPRegression", "SVGP", "SVGPPosterior", "NormalPosterior", "NormalPrior", "BayesianGPLVM", "FITC", "PEP", "EPDTC", "SparseGPClassification", "MI355GPError", "build", "device_count"]
 
 # GPy's import paths, so that `import gpy_amd as GPy` reads like the reference on this path:
 #   GPy.kern.RBF, GPy.likelihoods.Gaussian, GPy.models.GPRegression / SparseGPRegression / GPHeteroscedasticRegression,
@@ -31,12 +32,14 @@ __all__ = ["RBF", "OU", "ExpQuad", "HeteroscedasticGaussian", "StudentTPosterior
 #   Identity / Log,
 #   GPy.core.GP / SparseGP / SVGP, GPy.inference.latent_function_inference.ExactGaussianInference / VarDTC / Laplace / EP / SVGP,
 #   GPy.inference.latent_function_inference.FITC / PEP (and .fitc.FITC, .pep.PEP),
+#   GPy.inference.latent_function_inference.EPDTC (and .expectation_propagation.EPDTC), GPy.models.SparseGPClassification,
 #   GPy.util.choleskies, GPy.models.BayesianGPLVM, GPy.util.initialization.initialize_latent
-from . import ep, inference, kern, laplace, likelihoods, link_functions, linalg, models, pep, sparse, svgp, util  # noqa: E402
+from . import ep, epdtc, inference, kern, laplace, likelihoods, link_functions, linalg, models, pep, sparse, svgp, util  # noqa: E402
 import types as _types  # noqa: E402
 
 models.SparseGPRegression = SparseGPRegression
 models.BayesianGPLVM = BayesianGPLVM
+models.SparseGPClassification = SparseGPClassification
 core = _types.SimpleNamespace(GP=GP, SparseGP=SparseGP, SVGP=SVGP, svgp=_types.SimpleNamespace(SVGP=SVGP), parameterization=_types.SimpleNamespace(
     variational=_types.SimpleNamespace(NormalPosterior=NormalPosterior, NormalPrior=NormalPrior)))
 likelihoods.mixed_noise = _types.SimpleNamespace(MixedNoise=MixedNoise)
@@ -44,7 +47,7 @@ inference.latent_function_inference = _types.SimpleNamespace(
     ExactGaussianInference=ExactGaussianInference, ExactStudentTInference=ExactStudentTInference, VarDTC=VarDTC,
     PosteriorExact=PosteriorExact, StudentTPosterior=StudentTPosterior, Laplace=Laplace,
     laplace=_types.SimpleNamespace(Laplace=Laplace), EP=EP, PosteriorEP=PosteriorEP,
-    expectation_propagation=_types.SimpleNamespace(EP=EP), posterior=_types.SimpleNamespace(PosteriorEP=PosteriorEP, PosteriorExact=PosteriorExact),
+    expectation_propagation=_types.SimpleNamespace(EP=EP, EPDTC=EPDTC), EPDTC=EPDTC, posterior=_types.SimpleNamespace(PosteriorEP=PosteriorEP, PosteriorExact=PosteriorExact),
     exact_gaussian_inference=_types.SimpleNamespace(ExactGaussianInference=ExactGaussianInference),
     var_dtc=_types.SimpleNamespace(VarDTC=VarDTC), SVGP=svgp.SVGP, svgp=_types.SimpleNamespace(SVGP=svgp.SVGP),
     FITC=FITC, PEP=PEP, fitc=_types.SimpleNamespace(FITC=FITC), pep=_types.SimpleNamespace(PEP=PEP))

@@ -82,6 +82,7 @@ def build(force=False):
     srcs.append(os.path.join(_HERE, "..", "include", "mi355gp_debug.h"))
     srcs.append(os.path.join(_HERE, "..", "include", "mi355gp_debug_lauum.h"))
     srcs.append(os.path.join(_HERE, "..", "include", "mi355gp_debug_tileops.h"))
+    srcs.append(os.path.join(_HERE, "..", "include", "mi355gp_epdtc.h"))
     product = os.path.join(_HERE, "libmi355gp.so")
     if not force and os.path.exists(product) and os.path.exists(DIAG_LIB_PATH):
         t = min(os.path.getmtime(product), os.path.getmtime(DIAG_LIB_PATH))
@@ -202,6 +203,14 @@ DEBUG_LAUUM_ABI = {
 DEBUG_TILEOPS_ABI = {
     "mi355gp_dbg_tileop": [_ci, _ci, ctypes.POINTER(_i64), _c_dp, _c_dp, _c_dp, _cd],
 }
+# include/mi355gp_epdtc.h: EPDTC on the sparse context, in its order (tests/test_oracle_epdtc.py holds the table against that
+# header's prototypes)
+EPDTC_ABI = {
+    "mi355gp_epdtc_begin": [_vp, _ci, _parts, _dp, _i64, _cd],
+    "mi355gp_epdtc_recompute": [_vp, _dp, _dp, _dp, _dp, _c_dp],
+    "mi355gp_epdtc_sweep": [_vp, _i64a, _dp, _cd, _cd, _ci] + [_dp] * 7 + [_c_dp],
+    "mi355gp_epdtc_inference": [_vp, _ci, _parts, _dp, _i64, _dp, _dp, _cd, _dp] + [_c_dp] * 5,
+}
 TILEOPS = {"trmm_lower": 0, "trmm_lower_T": 1, "trmm64": 2, "gram_splitk": 3, "update_nt": 4}    # MI355GP_TILEOP_*
 
 
@@ -216,7 +225,7 @@ def lib():
         if not os.path.exists(LIB_PATH):
             build()
         L = ctypes.CDLL(LIB_PATH)
-        for table in (ABI, DEBUG_LAUUM_ABI, DEBUG_TILEOPS_ABI):
+        for table in (ABI, DEBUG_LAUUM_ABI, DEBUG_TILEOPS_ABI, EPDTC_ABI):
             for name, argtypes in table.items():
                 getattr(L, name).argtypes = argtypes
         L.mi355gp_last_error.restype = L.mi355gp_version.restype = _str
@@ -656,6 +665,46 @@ class SparseContext(_Handle):
         out = np.empty((nrows, self.M))
         check(lib().mi355gp_sparse_fetch_dLdKnm(self._h, int(row0), int(nrows), out), "mi355gp_sparse_fetch_dLdKnm")
         return out
+
+    # ---- EPDTC (epdtc.hip, include/mi355gp_epdtc.h) -------------------------------------------------------------------------
+    def epdtc_begin(self, specs, Z, jitter=0.0):
+        """The part list, Z and Kmm + jitter I, factored: (info, {})."""
+        arr, keep, _ = make_parts(specs)
+        Z = f64(Z)
+        self.M = Z.shape[0]
+        assert Z.shape[1] == self.D
+        return check(lib().mi355gp_epdtc_begin(self._h, len(specs), arr, Z, self.M, float(jitter)), "mi355gp_epdtc_begin"), {}
+
+    def epdtc_recompute(self, tau, v, want_ms=False):
+        """`posteriorParamsDTC._recompute` for the site parameters (tau, v): (info, mu, Sigma_diag[, ms])."""
+        mu, sd, ms = np.empty(self.N), np.empty(self.N), np.zeros(1)
+        rc = check(lib().mi355gp_epdtc_recompute(self._h, f64(tau), f64(v), mu, sd, _opt(ms)), "mi355gp_epdtc_recompute")
+        return (rc, mu, sd, float(ms[0])) if want_ms else (rc, mu, sd)
+
+    def epdtc_sweep(self, order, ysign, tau, v, eta=1.0, delta=1.0, first=False, want_ms=False):
+        """One sequential pass over the sites in `order`, from the P and gamma of the last recompute: dict(tau, v, cav_tau,
+        cav_v, log_Z_hat, mu_hat, sigma2_hat[, ms])."""
+        order = np.ascontiguousarray(order, dtype=np.int64)
+        assert order.shape == (self.N,), "order must have N entries"
+        tau, v = f64(tau).copy(), f64(v).copy()
+        out = [np.empty(self.N) for _ in range(5)]
+        ms = np.zeros(1)
+        check(lib().mi355gp_epdtc_sweep(self._h, order, f64(ysign), float(eta), float(delta), int(bool(first)), tau, v, *out,
+                                        _opt(ms)), "mi355gp_epdtc_sweep")
+        r = dict(zip(("cav_tau", "cav_v", "log_Z_hat", "mu_hat", "sigma2_hat"), out), tau=tau, v=v)
+        if want_ms:
+            r["ms"] = float(ms[0])
+        return r
+
+    def epdtc_inference(self, specs, Z, tau, v, jitter=0.0, want_stage_ms=False):
+        """The VarDTC evaluation of the sites (targets v / tau, precisions tau, `jitter` the whole term on Kmm's diagonal):
+        (info, dict(lml (without log Z_tilde), dL_dR (N), dtheta (concatenated), dZ, woodbury_vector[, stage_ms]))"""
+        arr, keep, ntheta = make_parts(specs)
+        dR = np.zeros(self.N)
+        rc, out, res = self._fit("mi355gp_epdtc_inference", (len(specs), arr), ntheta, Z, (f64(tau), f64(v), float(jitter)), (dR,),
+                                 want_stage_ms)
+        res["dL_dR"] = dR
+        return rc, res
 
     # ---- PEP / FITC (pep.hip) ---------------------------------------------------------------------------------------------
     def pep(self, specs, Z, noise_variance, alpha, jitter, want_stage_ms=False):

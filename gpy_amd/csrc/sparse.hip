@@ -206,6 +206,7 @@ bool sharded(const mi355gp_sparse* s) { return s->comm != nullptr || s->loop != 
 static void free_m(mi355gp_sparse* s) {
     svgp_release(s);
     pep_release(s);
+    epdtc_release(s);
     s->parts.clear();
     double** ptrs[] = {&s->dZ, &s->zero1, &s->Lm, &s->Xm, &s->Tm, &s->psi2part, &s->psi2, &s->Amat,
                        &s->LB, &s->XB, &s->Bi, &s->P, &s->E, &s->T1, &s->Q2, &s->dLdKmm, &s->Winv, &s->psi1Y, &s->vecA,
@@ -939,19 +940,19 @@ static void vardtc_scalars(const mi355gp_sparse* s, const double* scal, double k
     }
 }
 
-// Kmm + (1e-8 + extra_jitter) I (var_dtc.py:93-94) = sum of the parts' K(Z) (White on the diagonal), Lm = chol (jitchol, :95),
-// Xm = Lm^-1, and pass 1 over the row chunks: psi2 = sum_n beta_n k_n k_n^T (heteroscedastic) or Kuf Kfu (then A carries
-// beta), psi1V = Kuf V; records ev[1].
+// Kmm + kmm_jitter I (VarDTC: 1e-8 + extra_jitter, var_dtc.py:93-94) = sum of the parts' K(Z) (White on the diagonal),
+// Lm = chol (jitchol, :95), Xm = Lm^-1, and pass 1 over the row chunks: psi2 = sum_n beta_n k_n k_n^T (heteroscedastic) or
+// Kuf Kfu (then A carries beta), psi1V = Kuf V; records ev[1].
 // Kmm's three steps need only Z: when the factorisation is the single persistent launch (a latency-bound chain on an otherwise
 // idle GPU), they go to a side stream and pass 1 is enqueued underneath; the launch is first in line, so its workgroups are
 // resident before pass 1 fills the remaining CUs.  info is read (and a called-off launch redone) after pass 1 is queued.
-static int vardtc_pass1(mi355gp_sparse* s, bool het, double extra_jitter) {
+static int vardtc_pass1(mi355gp_sparse* s, bool het, double kmm_jitter) {
     hipStream_t st = s->st;
     const long n = s->n, m = s->m, mp = s->mp, chunk = s->chunk;
     const int Dy = s->Dy;
     const bool overlap_kmm = s->kmm_overlap && s->st_kmm && potrf_persist_eligible(mp, &s->ws);
     hipStream_t sk = overlap_kmm ? s->st_kmm : st;
-    auto rebuild_kmm = [&]() { build_kmm(s, s->Lm, s->T1, 1e-8 + extra_jitter, /*lower_only=*/1, sk); };
+    auto rebuild_kmm = [&]() { build_kmm(s, s->Lm, s->T1, kmm_jitter, /*lower_only=*/1, sk); };
     if (overlap_kmm) {
         HIP_CHECK(hipEventRecord(s->ev_z, st));
         HIP_CHECK(hipStreamWaitEvent(sk, s->ev_z, 0));
@@ -1092,9 +1093,7 @@ int mi355gp_vardtc_inference_sum(mi355gp_sparse* s, int nparts, const mi355gp_pa
     ARG_CHECK(!het || dnoise_rows_out, "per-point noise: dnoise_rows_out (N x Dy) is required");
     EngineShared gate(s->device);
     if (int rc = sparse_open(s, nparts, parts, M)) return rc;
-    hipStream_t st = s->st;
-    const long n = s->n, m = s->m;
-    const int Dy = s->Dy;
+    const long n = s->n;
     // per-point precision beta_n = 1 / max(noise_n, 1e-8) (var_dtc.py:78-80)
     // (scalar noise: the three sums are closed forms -- unused by the homoscedastic formulas -- and the precision vector is filled on
     //  the device: the N-element host loop with its logarithms and the 1.6 MB upload cost ~1 ms per evaluation at N = 200000)
@@ -1114,6 +1113,22 @@ int mi355gp_vardtc_inference_sum(mi355gp_sparse* s, int nparts, const mi355gp_pa
         glob[1] = log(hbeta[0]) * (double)n;
         glob[2] = hbeta[0] * s->trYYT_local;
     }
+    return vardtc_evaluate(s, Z, hbeta, glob, 1e-8 + extra_jitter, out_scalars, dtheta_out, dZ_out, wv_out, dnoise_rows_out, dLdm_out,
+                           stage_ms);
+}
+
+}  // extern "C"
+
+// The evaluation itself, for a call that sparse_open has opened: hbeta = the precisions (one for every row, or n), glob =
+// {sum beta_n, sum log beta_n, sum beta_n |R_n|^2} of this shard, kmm_jitter = the whole term on Kmm's diagonal.  The targets
+// are the context's (dY, rowYY, trYYT).  EPDTC (epdtc.hip) evaluates its converged sites through it.
+int vardtc_evaluate(mi355gp_sparse* s, const double* Z, const std::vector<double>& hbeta, double (&glob)[3], double kmm_jitter,
+                    double* out_scalars, double* dtheta_out, double* dZ_out, double* wv_out, double* dnoise_rows_out,
+                    double* dLdm_out, double* stage_ms) {
+    hipStream_t st = s->st;
+    const long n = s->n, m = s->m;
+    const int Dy = s->Dy;
+    const bool het = hbeta.size() > 1;
     const double beta = het ? 0.0 : hbeta[0];
     s->beta_scalar = beta;
     s->mfma_prof.on = true;
@@ -1127,7 +1142,7 @@ int mi355gp_vardtc_inference_sum(mi355gp_sparse* s, int nparts, const mi355gp_pa
     }
     if (inject == 1 || inject == 2) s->ws.persist_test = inject, s->ws.persist_skip = 0;
     const bool want_rows = het || dLdm_out != nullptr;
-    if (int rc = vardtc_pass1(s, het, extra_jitter)) return rc;
+    if (int rc = vardtc_pass1(s, het, kmm_jitter)) return rc;
     if (int rc = sparse_mm_block(s, het, beta, inject)) return rc;
     if (int rc = vardtc_pass2(s, het, want_rows)) return rc;
     sparse_kmm_gradients(s);
@@ -1174,6 +1189,8 @@ int mi355gp_vardtc_inference_sum(mi355gp_sparse* s, int nparts, const mi355gp_pa
     s->uncertain_result = false;
     return 0;
 }
+
+extern "C" {
 
 int mi355gp_vardtc_inference(mi355gp_sparse* s, int kind, int ard, const double* theta, const double* Z, int64_t M,
                              double noise_var, double extra_jitter, double* out_scalars, double* dtheta_out,

@@ -10,6 +10,7 @@
 struct LoopGroup;              // the loopback rendezvous of the row-sharded mode (sparse.hip)
 struct SvgpState;              // svgp.hip
 struct PepState;               // pep.hip
+struct EpdtcState;             // epdtc.hip
 
 struct SPart : DevicePart {
     DevBuf XtZ, XtC, HX, HZ, gradNM, gradMM;
@@ -67,6 +68,8 @@ struct mi355gp_sparse {
     PepState* pep = nullptr;
     bool pep_result = false;
     double kmm_jitter = 1e-8;
+    // EPDTC (epdtc.hip): Kmm, P = LLT^-1 and gamma between its begin / recompute / sweep calls, the buffers of a site block
+    EpdtcState* epdtc = nullptr;
 };
 
 // ---- sparse.hip ----------------------------------------------------------------------------------------------------
@@ -114,8 +117,14 @@ int sparse_newpoints(mi355gp_sparse* s, const double* Xnew, int64_t Mn, bool wan
                      const char* where, NewPoints* q);
 int sparse_newpoints_var(mi355gp_sparse* s, NewPoints* q, const double* Winv, bool full_cov, bool keep_kss);
 }
+// the VarDTC evaluation of an opened call with the precisions and Kmm's jitter as given (mi355gp_vardtc_inference_sum, EPDTC)
+int vardtc_evaluate(mi355gp_sparse* s, const double* Z, const std::vector<double>& hbeta, double (&glob)[3], double kmm_jitter,
+                    double* out_scalars, double* dtheta_out, double* dZ_out, double* wv_out, double* dnoise_rows_out,
+                    double* dLdm_out, double* stage_ms);
 // ---- svgp.hip ------------------------------------------------------------------------------------------------------
 void svgp_release(mi355gp_sparse* s);      // frees the SVGP state (M-dependent: called by free_m)
 // ---- pep.hip -------------------------------------------------------------------------------------------------------
 void pep_release(mi355gp_sparse* s);       // frees the PEP state (M-dependent: called by free_m)
 int pep_fetch_dLdKnm(mi355gp_sparse* s, long row0, long nrows, double* out);   // the PEP half of mi355gp_sparse_fetch_dLdKnm
+// ---- epdtc.hip -----------------------------------------------------------------------------------------------------
+void epdtc_release(mi355gp_sparse* s);     // frees the EPDTC state (M-dependent: called by free_m)
