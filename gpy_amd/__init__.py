@@ -11,10 +11,12 @@ from ._lib import MI355GPError, build, device_count
 from .inference import ExactGaussianInference, ExactStudentTInference
 from .laplace import Laplace, LaplacePosterior
 from .ep import EP
+from .vargauss import VarGauss, VarGaussPosterior
 from .kern import (OU, RBF, Add, Prod, Bias, Coregionalize, Cosine, ExpQuad, ExpQuadCosine, Sinc, Exponential, Linear, Matern32, Matern52, MLP, Poly, RatQuad,
                    Stationary, StdPeriodic, White)
 from .likelihoods import Bernoulli, Gaussian, HeteroscedasticGaussian, MixedNoise, Poisson, StudentT
-from .models import GP, GPClassification, GPCoregionalizedRegression, GPHeteroscedasticRegression, GPRegression
+from .models import (GP, GPClassification, GPCoregionalizedRegression, GPHeteroscedasticRegression, GPRegression,
+                     GPVariationalGaussianApproximation)
 from .posterior import PosteriorEP, PosteriorExact, StudentTPosterior
 from .sparse import BayesianGPLVM, SparseGP, SparseGPRegression, VarDTC
 from .pep import FITC, PEP
@@ -24,7 +26,7 @@ from .svgp import SVGPPosterior
 from .variational import NormalPosterior, NormalPrior
 
 __all__ = ["RBF", "OU", "ExpQuad", "HeteroscedasticGaussian", "StudentTPosterior", "Matern52", "Matern32", "Exponential", "RatQuad", "Cosine", "Sinc", "ExpQuadCosine", "StdPeriodic", "Coregionalize", "Linear", "MLP", "Poly", "MixedNoise", "Stationary", "White", "Bias", "Add", "Prod", "Gaussian", "ExactGaussianInference", "ExactStudentTInference",
-           "PosteriorExact", "GP", "GPRegression", "GPHeteroscedasticRegression", "GPCoregionalizedRegression", "Laplace", "LaplacePosterior", "EP", "PosteriorEP", "Bernoulli", "StudentT", "Poisson", "GPClassification", "VarDTC", "SparseGP", "SparseGPRegression", "SVGP", "SVGPPosterior", "NormalPosterior", "NormalPrior", "BayesianGPLVM", "FITC", "PEP", "EPDTC", "SparseGPClassification", "MI355GPError", "build", "device_count"]
+           "PosteriorExact", "GP", "GPRegression", "GPHeteroscedasticRegression", "GPCoregionalizedRegression", "Laplace", "LaplacePosterior", "EP", "PosteriorEP", "Bernoulli", "StudentT", "Poisson", "GPClassification", "VarDTC", "SparseGP", "SparseGPRegression", "SVGP", "SVGPPosterior", "NormalPosterior", "NormalPrior", "BayesianGPLVM", "FITC", "PEP", "EPDTC", "SparseGPClassification", "VarGauss", "VarGaussPosterior", "GPVariationalGaussianApproximation", "MI355GPError", "build", "device_count"]
 
 # GPy's import paths, so that `import gpy_amd as GPy` reads like the reference on this path:
 #   GPy.kern.RBF, GPy.likelihoods.Gaussian, GPy.models.GPRegression / SparseGPRegression / GPHeteroscedasticRegression,
@@ -33,8 +35,9 @@ __all__ = ["RBF", "OU", "ExpQuad", "HeteroscedasticGaussian", "StudentTPosterior
 #   GPy.core.GP / SparseGP / SVGP, GPy.inference.latent_function_inference.ExactGaussianInference / VarDTC / Laplace / EP / SVGP,
 #   GPy.inference.latent_function_inference.FITC / PEP (and .fitc.FITC, .pep.PEP),
 #   GPy.inference.latent_function_inference.EPDTC (and .expectation_propagation.EPDTC), GPy.models.SparseGPClassification,
+#   GPy.inference.latent_function_inference.VarGauss (and .var_gauss.VarGauss), GPy.models.GPVariationalGaussianApproximation,
 #   GPy.util.choleskies, GPy.models.BayesianGPLVM, GPy.util.initialization.initialize_latent
-from . import ep, epdtc, inference, kern, laplace, likelihoods, link_functions, linalg, models, pep, sparse, svgp, util  # noqa: E402
+from . import ep, epdtc, inference, kern, laplace, likelihoods, link_functions, linalg, models, pep, sparse, svgp, util, vargauss  # noqa: E402
 import types as _types  # noqa: E402
 
 models.SparseGPRegression = SparseGPRegression
@@ -50,4 +53,5 @@ inference.latent_function_inference = _types.SimpleNamespace(
     expectation_propagation=_types.SimpleNamespace(EP=EP, EPDTC=EPDTC), EPDTC=EPDTC, posterior=_types.SimpleNamespace(PosteriorEP=PosteriorEP, PosteriorExact=PosteriorExact),
     exact_gaussian_inference=_types.SimpleNamespace(ExactGaussianInference=ExactGaussianInference),
     var_dtc=_types.SimpleNamespace(VarDTC=VarDTC), SVGP=svgp.SVGP, svgp=_types.SimpleNamespace(SVGP=svgp.SVGP),
-    FITC=FITC, PEP=PEP, fitc=_types.SimpleNamespace(FITC=FITC), pep=_types.SimpleNamespace(PEP=PEP))
+    FITC=FITC, PEP=PEP, fitc=_types.SimpleNamespace(FITC=FITC), pep=_types.SimpleNamespace(PEP=PEP),
+    VarGauss=VarGauss, var_gauss=_types.SimpleNamespace(VarGauss=VarGauss))

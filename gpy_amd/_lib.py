@@ -83,6 +83,7 @@ def build(force=False):
     srcs.append(os.path.join(_HERE, "..", "include", "mi355gp_debug_lauum.h"))
     srcs.append(os.path.join(_HERE, "..", "include", "mi355gp_debug_tileops.h"))
     srcs.append(os.path.join(_HERE, "..", "include", "mi355gp_epdtc.h"))
+    srcs.append(os.path.join(_HERE, "..", "include", "mi355gp_vargauss.h"))
     product = os.path.join(_HERE, "libmi355gp.so")
     if not force and os.path.exists(product) and os.path.exists(DIAG_LIB_PATH):
         t = min(os.path.getmtime(product), os.path.getmtime(DIAG_LIB_PATH))
@@ -211,6 +212,13 @@ EPDTC_ABI = {
     "mi355gp_epdtc_sweep": [_vp, _i64a, _dp, _cd, _cd, _ci] + [_dp] * 7 + [_c_dp],
     "mi355gp_epdtc_inference": [_vp, _ci, _parts, _dp, _i64, _dp, _dp, _cd, _dp] + [_c_dp] * 5,
 }
+# include/mi355gp_vargauss.h: the variational Gaussian approximation inside the Laplace session of an exact context, in its order
+# (tests/test_oracle_vargauss.py holds the table against that header's prototypes)
+VARGAUSS_ABI = {
+    "mi355gp_vargauss_forward": [_vp, _dp, _dp, _cd, _dp, _dp, _dp],
+    "mi355gp_vargauss_backward": [_vp, _dp, _dp, _dp, _dp, _dp],
+    "mi355gp_vargauss_backward_exact": [_vp, _dp, _dp, _dp, _dp, _dp],
+}
 TILEOPS = {"trmm_lower": 0, "trmm_lower_T": 1, "trmm64": 2, "gram_splitk": 3, "update_nt": 4}    # MI355GP_TILEOP_*
 
 
@@ -225,7 +233,7 @@ def lib():
         if not os.path.exists(LIB_PATH):
             build()
         L = ctypes.CDLL(LIB_PATH)
-        for table in (ABI, DEBUG_LAUUM_ABI, DEBUG_TILEOPS_ABI, EPDTC_ABI):
+        for table in (ABI, DEBUG_LAUUM_ABI, DEBUG_TILEOPS_ABI, EPDTC_ABI, VARGAUSS_ABI):
             for name, argtypes in table.items():
                 getattr(L, name).argtypes = argtypes
         L.mi355gp_last_error.restype = L.mi355gp_version.restype = _str
@@ -473,6 +481,28 @@ class Context(_Handle):
         assert wv.size == self.N
         return _predict("mi355gp_laplace_predict", (self._h, len(specs), arr), Xnew, self.D, 1, full_cov, want_var,
                         between=(wv,))
+
+    # ---- VarGauss inside a Laplace session (include/mi355gp_vargauss.h: begin, then forward / backward per evaluation) ----
+    def vargauss_forward(self, alpha, beta, extra_jitter=0.0):
+        """The N x N half of reference `var_gauss.py:34-41,54`: (info, m = K alpha, diag Sigma, log det A, tr A^-1, m^T alpha)
+        for A = I + diag(beta) K diag(beta); beta is signed."""
+        alpha, beta = f64(np.ravel(alpha)), f64(np.ravel(beta))
+        assert alpha.size == self.N and beta.size == self.N
+        m, var, scal = np.empty(self.N), np.empty(self.N), np.zeros(3)
+        rc = check(lib().mi355gp_vargauss_forward(self._h, alpha, beta, float(extra_jitter), m, var, scal),
+                   "mi355gp_vargauss_forward")
+        return rc, m, var, scal[0], scal[1], scal[2]
+
+    def vargauss_backward(self, dF_dm, dF_dv, exact=False):
+        """Reference `var_gauss.py:48-65`: (alpha.gradient, beta.gradient, dL/dtheta of every part) from the symmetrised
+        dL_dK, which stays on the device.  `exact`: the dF_dv term of dL_dK as the derivative of the bound, T diag(dF_dv) T^T,
+        instead of the reference's row-scaled (T o dF_dv) T^T (`mi355gp_vargauss_backward_exact`)."""
+        g, v = f64(np.ravel(dF_dm)), f64(np.ravel(dF_dv))
+        assert g.size == self.N and v.size == self.N
+        da, db, dtheta = np.empty(self.N), np.empty(self.N), np.zeros(self._lap_ntheta)
+        entry = "mi355gp_vargauss_backward_exact" if exact else "mi355gp_vargauss_backward"
+        check(getattr(lib(), entry)(self._h, g, v, da, db, dtheta), entry)
+        return da, db, dtheta
 
     # ---- EP inside a Laplace session (include/mi355gp.h: recompute, sweep; the final pass is newton / finish / gradients) ----
     def ep_recompute(self, tau, v, extra_jitter=0.0, add_diag=0.0, want_sigma=True, want_ms=False):

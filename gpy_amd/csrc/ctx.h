@@ -57,6 +57,7 @@ struct mi355gp_ctx {
     // Laplace session (laplace.hip): everything it needs beyond A / B / C is allocated by its first mi355gp_laplace_begin, so a
     // context that never runs one keeps its footprint; lap_stage: 0 none, 1 begun (K resident), 2 Newton step factored,
     // 3 finished (B^-1 in C), 4 gradients done (dL_dK in A).  Any exact / Student-t / given-K evaluation resets it to 0.
+    // mi355gp_vargauss_forward / _backward (vargauss.hip) leave it at 3 / 4 with the session's `vg` flag set.
     LaplaceSession* lap = nullptr;
     int lap_stage = 0;
 };

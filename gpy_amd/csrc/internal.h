@@ -367,6 +367,25 @@ void launch_symv_lower(hipStream_t st, const double* K, long npad, long n, const
 // G (both triangles) = 0.5 (a a^T - diag(sw) Binv diag(sw)) + 0.5 (a u^T + u a^T), Binv read from its lower tiles (laplace.py:260-272)
 void launch_laplace_dLdK(hipStream_t st, const double* Binv, long npad, long n, const double* sw, const double* a,
                          const double* u, double* G);
+// VarGauss (vargauss.hip) over the same resident K; every matrix npad x npad with ld = npad
+// M[i][j] * s[i] (inverse != 0: / s[i]) into Out (may alias M), rows x cols (ld shared): launch_rowscale_sqrt for a signed scale
+void launch_rowscale(hipStream_t st, const double* M, long ld, long rows, long cols, const double* s, int inverse, double* Out);
+// lower triangle (lower 64-tiles) -> both triangles, in place
+void launch_vg_mirror(hipStream_t st, double* A, long npad);
+size_t vg_part_doubles(long npad);
+// H (P1 = Ai Ai in its lower tiles) <- the Ai / P1 part of the symmetrised dL_dK, in place (lower tiles); the partial sums of the
+// two beta gradients into `part` (vg_part_doubles(npad)).  Ai: both triangles; g = dF_dm, v = dF_dv, var = diag Sigma
+void launch_vg_assemble(hipStream_t st, const double* Ai, const double* K, long npad, long n, const double* beta,
+                        const double* alpha, const double* g, const double* v, const double* var, int scaled, double* H, double* part);
+// dbeta = -2 beta S1 - S2 from the partials, added in a fixed order; dalpha = Kg - m
+void launch_vg_finish_vec(hipStream_t st, const double* part, long npad, long n, const double* beta, const double* Kg,
+                          const double* m, double* dalpha, double* dbeta);
+// G (both triangles, bitwise symmetric, in H's buffer) = H + 0.5 (v_i + v_j) beta_i beta_j P2_ij from the lower tiles of H and P2
+void launch_vg_dLdK(hipStream_t st, const double* P2, long npad, long n, const double* beta, const double* v, int exact, double* G);
+// exact form: scaled != 0 above leaves H / (beta_i beta_j); Out = diag(sqrt(max(sign v, 0)) / |beta|) M on the first `rows` rows, zero on
+// the rest up to allrows; exact != 0 multiplies the accumulated lower tiles back by beta_i beta_j (P2 not read)
+void launch_vg_rowscale_v(hipStream_t st, const double* M, long ld, long rows, long allrows, long cols, const double* v,
+                          const double* beta, double sign, double* Out);
 
 // ---- grid_comm.hip : RCCL (dlopen'ed) world communicator for row-sharded paths ----------------------------------
 int rccl_comm_create(int rank, int world, const void* id128, void** comm);

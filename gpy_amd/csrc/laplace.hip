@@ -14,7 +14,7 @@
 
 void laplace_session_free(LaplaceSession* s) {
     if (!s) return;
-    double** ptrs[] = {&s->K, &s->vec, &s->part, &s->coregPart};
+    double** ptrs[] = {&s->K, &s->vec, &s->part, &s->coregPart, &s->vgPart};
     for (auto p : ptrs)
         if (*p) (void)hipFree(*p);
     if (s->ws_ok) factor_ws_free(&s->ws);
@@ -87,10 +87,15 @@ int lap_check_vec(const double* v, long n, const char* where, const char* name) 
 // W (device, LV_W) -> sw, B into A, L_B in place, X = L_B^-1 into the context's B buffer; all enqueued, nothing read back
 void lap_enqueue_factor(mi355gp_ctx* c, double jit) {
     LaplaceSession* L = c->lap;
+    L->vg = L->vg_ai = L->vg_bwd = false;                    // sw is W^1/2 again: nothing of a VarGauss evaluation is left
+    hipLaunchKernelGGL(k_lap_sqrt, VGRID(c->n), 0, c->st, lvec(c, LV_W), c->n, lvec(c, LV_SW));
+    lap_enqueue_factor_sw(c, jit);
+}
+void lap_enqueue_factor_sw(mi355gp_ctx* c, double jit) {
+    LaplaceSession* L = c->lap;
     L->ep_sigma = false;                                     // A is overwritten: a resident EP Sigma is gone
     hipStream_t st = c->st;
     const long n = c->n, np = c->npad;
-    hipLaunchKernelGGL(k_lap_sqrt, VGRID(n), 0, st, lvec(c, LV_W), n, lvec(c, LV_SW));
     launch_laplace_B(st, L->K, np, n, lvec(c, LV_SW), jit, c->A);
     L->ws.scratchX = c->B;                                   // free until trtri overwrites them
     L->ws.scratchT = c->C;
@@ -125,6 +130,52 @@ int lap_factor_outcome(mi355gp_ctx* c, int info, int attempt, int* info_out) {
     return 0;
 }
 
+// every part reduces the dL_dK in the context's A against its own dK/dtheta (the unfused reductions of mi355gp_update_gradients_full)
+int lap_reduce_dtheta(mi355gp_ctx* c, double* dtheta_out) {
+    LaplaceSession* L = c->lap;
+    hipStream_t st = c->st;
+    const long n = c->n, np = c->npad;
+    const int groups = (c->D + 31) / 32;
+    const size_t nparts = c->parts.size();
+    HIP_CHECK(hipMemsetAsync(c->dGradOutAll, 0, sizeof(double) * nparts * groups * GP_STRIDE, st));
+    HIP_CHECK(hipMemsetAsync(c->dPack + c->offExt, 0, sizeof(double) * nparts * groups * GP_STRIDE, st));
+    const int nb = grad_generic_num_blocks(n, n);
+    bool coreg = false;
+    for (size_t p = 0; p < nparts; ++p) {
+        const mi355gp_ctx::Part& pt = c->parts[p];
+        // factor of a product: dL_dK times the covariances of the term's other factors (prod.py:86-99), materialised in Mbuf
+        const bool prod = emit_other_factors(c->terms, pt.tix, p, c->Mbuf, [&](int g, double* dst, const double* mul, int, bool) {
+            launch_kbuild_sym(st, c->parts[(size_t)g].kp, c->parts[(size_t)g].dXt, np, n, np, dst, nullptr, 0, 0.0, /*lower_only=*/0,
+                              /*add_diag=*/0, /*accumulate=*/0, mul);
+        });
+        if (prod) hipLaunchKernelGGL(k_lap_mm_mul, MGRID(n), 0, st, c->Mbuf, c->A, np, n);
+        const double* G = prod ? c->Mbuf : c->A;
+        if (pt.coreg()) {
+            coreg = true;
+            const int P = pt.kp.ard;
+            const int nbc = launch_grad_coreg(st, false, pt.kp, pt.dXt, np, n, pt.dXt, np, n, G, np, nullptr, 0, L->coregPart);
+            launch_reduce_partials(st, L->coregPart, nbc, P * P, c->dPack + c->offCoreg + p * COREG_REC);
+            continue;
+        }
+        launch_grad_generic(st, pt.kp, pt.dXt, np, n, pt.dXt, np, n, /*symmetric=*/1, G, np, c->dGradPart);
+        for (int r = 0; r < (pt.ext() ? 2 : 1); ++r)
+            for (int g = 0; g < (pt.kp.ard ? groups : 1); ++g)
+                launch_reduce_partials(st, c->dGradPart + ((long)r * groups + g) * nb * GP_STRIDE, nb, GP_STRIDE,
+                                       (r == 0 ? c->dGradOutAll : c->dPack + c->offExt) + ((long)p * groups + g) * GP_STRIDE);
+    }
+    const size_t ncopy = coreg ? c->packDoubles : c->offAlpha;
+    HIP_CHECK(hipMemcpyAsync(c->hPack, c->dPack, sizeof(double) * ncopy, hipMemcpyDeviceToHost, st));
+    HIP_CHECK(hipStreamSynchronize(st));
+    HIP_CHECK(hipGetLastError());
+    double* o = dtheta_out;
+    for (size_t p = 0; p < nparts; ++p) {
+        const double* rec = c->parts[p].coreg() ? c->hPack + c->offCoreg + p * COREG_REC
+                                                : c->hPack + c->offGrad + p * (size_t)groups * GP_STRIDE;
+        o += part_dtheta(c->parts[p], rec, c->hPack + c->offExt + p * (size_t)groups * GP_STRIDE, o);
+    }
+    return 0;
+}
+
 extern "C" {
 
 int mi355gp_laplace_begin(mi355gp_ctx* c, int nparts, const mi355gp_part* parts) {
@@ -153,6 +204,7 @@ int mi355gp_laplace_begin(mi355gp_ctx* c, int nparts, const mi355gp_part* parts)
     c->have_factor = false;                                   // A / B / C belong to the session from here on
     c->lap_stage = 0;
     L->ep_sigma = false;
+    L->vg = L->vg_ai = L->vg_bwd = false;
     ctx_scale_parts(c);
     // K = sum_t prod_f K_f, both triangles (the prediction-style products read it whole; the mat-vecs read its lower tiles)
     emit_expression(c->terms, L->K, c->Mbuf, false, [&](int p, double* dst, const double* mul, int acc, bool) {
@@ -250,12 +302,12 @@ int mi355gp_laplace_finish(mi355gp_ctx* c, const double* W, double extra_jitter,
 int mi355gp_laplace_gradients(mi355gp_ctx* c, const double* Ki_f, const double* dL_dfhat, double* dtheta_out) {
     ARG_CHECK(c && c->n > 0 && c->lap && c->lap_stage >= 3, "mi355gp_laplace_gradients: call mi355gp_laplace_finish first");
     ARG_CHECK(Ki_f && dL_dfhat && dtheta_out, "mi355gp_laplace_gradients: NULL argument");
+    ARG_CHECK(!c->lap->vg, "mi355gp_laplace_gradients: the session holds a VarGauss evaluation, call mi355gp_laplace_finish first");
     const long n = c->n, np = c->npad;
     if (int rc = lap_check_vec(Ki_f, n, "mi355gp_laplace_gradients", "Ki_f")) return rc;
     if (int rc = lap_check_vec(dL_dfhat, n, "mi355gp_laplace_gradients", "dL_dfhat")) return rc;
     HIP_CHECK(hipSetDevice(c->device));
     EngineShared gate(c->device);
-    LaplaceSession* L = c->lap;
     hipStream_t st = c->st;
     HIP_CHECK(hipMemcpyAsync(lvec(c, LV_A), Ki_f, sizeof(double) * n, hipMemcpyHostToDevice, st));
     HIP_CHECK(hipMemcpyAsync(lvec(c, LV_S), dL_dfhat, sizeof(double) * n, hipMemcpyHostToDevice, st));
@@ -264,51 +316,13 @@ int mi355gp_laplace_gradients(mi355gp_ctx* c, const double* Ki_f, const double* 
     // dL_dK, symmetrised, into A (what finish left there is spent); C keeps B^-1 for MI355GP_FETCH_KINV and prediction keeps X
     launch_laplace_dLdK(st, c->C, np, n, lvec(c, LV_SW), lvec(c, LV_A), lvec(c, LV_U), c->A);
     c->lap_stage = 4;
-    // every part reduces that dL_dK against its own dK/dtheta (the unfused reductions of mi355gp_update_gradients_full)
-    const int groups = (c->D + 31) / 32;
-    const size_t nparts = c->parts.size();
-    HIP_CHECK(hipMemsetAsync(c->dGradOutAll, 0, sizeof(double) * nparts * groups * GP_STRIDE, st));
-    HIP_CHECK(hipMemsetAsync(c->dPack + c->offExt, 0, sizeof(double) * nparts * groups * GP_STRIDE, st));
-    const int nb = grad_generic_num_blocks(n, n);
-    bool coreg = false;
-    for (size_t p = 0; p < nparts; ++p) {
-        const mi355gp_ctx::Part& pt = c->parts[p];
-        // factor of a product: dL_dK times the covariances of the term's other factors (prod.py:86-99), materialised in Mbuf
-        const bool prod = emit_other_factors(c->terms, pt.tix, p, c->Mbuf, [&](int g, double* dst, const double* mul, int, bool) {
-            launch_kbuild_sym(st, c->parts[(size_t)g].kp, c->parts[(size_t)g].dXt, np, n, np, dst, nullptr, 0, 0.0, /*lower_only=*/0,
-                              /*add_diag=*/0, /*accumulate=*/0, mul);
-        });
-        if (prod) hipLaunchKernelGGL(k_lap_mm_mul, MGRID(n), 0, st, c->Mbuf, c->A, np, n);
-        const double* G = prod ? c->Mbuf : c->A;
-        if (pt.coreg()) {
-            coreg = true;
-            const int P = pt.kp.ard;
-            const int nbc = launch_grad_coreg(st, false, pt.kp, pt.dXt, np, n, pt.dXt, np, n, G, np, nullptr, 0, L->coregPart);
-            launch_reduce_partials(st, L->coregPart, nbc, P * P, c->dPack + c->offCoreg + p * COREG_REC);
-            continue;
-        }
-        launch_grad_generic(st, pt.kp, pt.dXt, np, n, pt.dXt, np, n, /*symmetric=*/1, G, np, c->dGradPart);
-        for (int r = 0; r < (pt.ext() ? 2 : 1); ++r)
-            for (int g = 0; g < (pt.kp.ard ? groups : 1); ++g)
-                launch_reduce_partials(st, c->dGradPart + ((long)r * groups + g) * nb * GP_STRIDE, nb, GP_STRIDE,
-                                       (r == 0 ? c->dGradOutAll : c->dPack + c->offExt) + ((long)p * groups + g) * GP_STRIDE);
-    }
-    const size_t ncopy = coreg ? c->packDoubles : c->offAlpha;
-    HIP_CHECK(hipMemcpyAsync(c->hPack, c->dPack, sizeof(double) * ncopy, hipMemcpyDeviceToHost, st));
-    HIP_CHECK(hipStreamSynchronize(st));
-    HIP_CHECK(hipGetLastError());
-    double* o = dtheta_out;
-    for (size_t p = 0; p < nparts; ++p) {
-        const double* rec = c->parts[p].coreg() ? c->hPack + c->offCoreg + p * COREG_REC
-                                                : c->hPack + c->offGrad + p * (size_t)groups * GP_STRIDE;
-        o += part_dtheta(c->parts[p], rec, c->hPack + c->offExt + p * (size_t)groups * GP_STRIDE, o);
-    }
-    return 0;
+    return lap_reduce_dtheta(c, dtheta_out);
 }
 
 int mi355gp_laplace_implicit(mi355gp_ctx* c, const double* dL_dfhat, double* s_out) {
     ARG_CHECK(c && c->n > 0 && c->lap && c->lap_stage >= 3, "mi355gp_laplace_implicit: call mi355gp_laplace_finish first");
     ARG_CHECK(dL_dfhat && s_out, "mi355gp_laplace_implicit: NULL argument");
+    ARG_CHECK(!c->lap->vg, "mi355gp_laplace_implicit: the session holds a VarGauss evaluation, call mi355gp_laplace_finish first");
     const long n = c->n, np = c->npad;
     if (int rc = lap_check_vec(dL_dfhat, n, "mi355gp_laplace_implicit", "dL_dfhat")) return rc;
     HIP_CHECK(hipSetDevice(c->device));
@@ -367,7 +381,8 @@ int mi355gp_laplace_predict(mi355gp_ctx* c, int nparts, const mi355gp_part* part
     if (full_cov && var_out) emit_cross(st, c->parts, c->terms, xs, xs, dVar, mp, dScr2, true, /*diag_same=*/1);
     launch_col_reduce(st, dKx, mp, n, M, dWv, 1, 0.0, 0, dMu);
     if (var_out) {
-        launch_rowscale_sqrt(st, dKx, mp, n, mp, lvec(c, LV_W), dKx);
+        if (c->lap->vg) launch_rowscale(st, dKx, mp, n, mp, lvec(c, LV_SW), 0, dKx);     // VarGauss: sw is the signed beta
+        else launch_rowscale_sqrt(st, dKx, mp, n, mp, lvec(c, LV_W), dKx);
         launch_trmm_lower(st, c->B, np, dKx, mp, dTmp, mp, (int)(np / NB), (int)(mp / NB));
         if (!full_cov) {
             if (kd_points) launch_col_reduce_vec(st, dTmp, mp, n, M, dKd, dVar);
@@ -397,6 +412,10 @@ int laplace_fetch(mi355gp_ctx* c, int which, double* tmp) {
     if (which == MI355GP_FETCH_K) {
         hipLaunchKernelGGL(k_lap_extract_full, MGRID(n), 0, st, c->lap->K, np, n, tmp);
     } else if (which == MI355GP_FETCH_KINV && c->lap_stage >= 3) {
+        if (c->lap->vg && !c->lap->vg_ai) {                  // VarGauss's backward spent Ai: one lauum of the resident X brings it back
+            lauum_device(st, c->B, c->C, np, &c->lap->ws);
+            c->lap->vg_ai = true;
+        }
         hipLaunchKernelGGL(k_lap_extract_kwi, MGRID(n), 0, st, c->C, np, n, lvec(c, LV_SW), tmp);
     } else if (which == MI355GP_FETCH_DLDK && c->lap_stage >= 4) {
         hipLaunchKernelGGL(k_lap_extract_full, MGRID(n), 0, st, c->A, np, n, tmp);

@@ -345,6 +345,28 @@ class GPClassification(GP):
                 "likelihood": self.likelihood.to_dict(), "inference_method": self.inference_method.to_dict()}
 
 
+class GPVariationalGaussianApproximation(GP):
+    """The variational Gaussian approximation revisited (Opper and Archambeau 2009; reference `GPy/models/gp_var_gauss.py:12-30`):
+    N x 1 `alpha` (zeros) and N `beta` (ones, signed and unconstrained) are parameters of the model, linked after the kernel and
+    the likelihood, so the flat order is [kernel, likelihood, alpha, beta].  One output column; no mean function."""
+
+    def __init__(self, X, Y, kernel, likelihood, Y_metadata=None, device=0):
+        from .param import Param
+        from .vargauss import VarGauss
+        num_data = np.asarray(Y).shape[0]
+        self.alpha = Param("alpha", np.zeros((num_data, 1)), positive=False)      # only one latent function
+        self.beta = Param("beta", np.ones(num_data), positive=False)
+        inf = VarGauss(self.alpha, self.beta, device=device)
+        super(GPVariationalGaussianApproximation, self).__init__(X, Y, kernel, likelihood, name="VarGP", inference_method=inf,
+                                                                 Y_metadata=Y_metadata, device=device)
+        self.link_parameter(self.alpha)
+        self.link_parameter(self.beta)
+
+    def to_dict(self):
+        return {"class": "GPy.models.GPVariationalGaussianApproximation", "name": self.name, "kernel": self.kern.to_dict(),
+                "likelihood": self.likelihood.to_dict(), "inference_method": self.inference_method.to_dict()}
+
+
 class GPHeteroscedasticRegression(GP):
     """One Gaussian noise variance per data point (reference `GPy/models/gp_heteroscedastic_regression.py:10-40`): the
     length-N noise vector goes to the device with the inference call and the N noise gradients come back as diag(dL_dK)."""
