@@ -228,7 +228,7 @@ int persist_early_h(long npad, const FactorWs* ws);
 // row up to and including the diagonal block and its inverted diagonal tiles), the launch was called off / aborted, or 20 ms passed
 void launch_wait_persist_rows(hipStream_t st, const FactorWs* ws, int r0, int r1, int cols, int give_up = 0);
 
-// ---- kern.hip : covariance assembly, reductions, solves, fetch helpers ----------------------------
+// ---- kern.hip : covariance assembly and fused gradient reduction: the stationary kernels, every kind's dispatch ---
 #define GP_STRIDE 34           // doubles of one reduction record: [0] variance sum, [1] lengthscale sum, [2 + q % 32] per dimension
 struct KernParams {
     int kind;
@@ -262,13 +262,6 @@ struct MI355GP_LOCAL SyntheticSpd {
 void launch_kbuild_cross(hipStream_t st, KernParams kp, const double* Xt1, long ld1, long n, const double* Xt2,
                          long ld2, long m, double* Kout, long ldk, int accumulate = 0, int diag_same = 0,
                          const double* mul = nullptr);
-// K(X1, X2) into Kout AND the column partials of psi1^T V = sum_i K[i][j] V[i][d] in one pass (one plain stationary part);
-// returns the number of row splits in colpart ([split][mcols][Dy]; combine with launch_sum_splits), 0 = not applicable
-int launch_kbuild_cols(hipStream_t st, KernParams kp, const double* Xt1, long ld1, long n, const double* Xt2, long ld2, long m,
-                       long mcols, double* Kout, long ldk, const double* V, int Dy, double* colpart);
-// y = X r (lower-triangular X, n x n within npad), then a = X^T y   (Dy right-hand sides, row-major n x Dy)
-void launch_tri_matvec(hipStream_t st, const double* X, long ld, long n, const double* R, int Dy, double* tmp,
-                       double* alpha, double* partials);
 // fused gradient reduction over the lower tiles of W; results (per block partials) reduced by launch_finalize
 struct GradOut {
     double* partials;   // [nblocks][stride]
@@ -292,16 +285,14 @@ struct RankTerm {
     double beta, gscale;
     const double* rowscale = nullptr;
 };
-// sparse pass 2: theta partials + H^T [x~ | 1] column partials in one pass over the weights (k_grad_cols); 0 = not applicable
-int launch_grad_cols(hipStream_t st, KernParams kp, const double* Xt1, long ld1, long n, const double* Xt2, long ld2,
-                     long m, long mcols, const double* G, long ldg, RankTerm rk, double* partials, double* colpart,
-                     int* nblocks_out);
-void launch_studentt_scale(hipStream_t st, const double* scal, double nu, long n, double* out);
 // Hout (optional, may alias G): H = dL_dK * (dK/dr)/r, the weights of the gradients_X reductions
 void launch_grad_generic(hipStream_t st, KernParams kp, const double* Xt1, long ld1, long n, const double* Xt2,
                          long ld2, long m, int symmetric, const double* G, long ldg, double* partials,
                          double* Hout = nullptr, long ldh = 0,
                          RankTerm rk = RankTerm{nullptr, nullptr, 0, 0.0, 1.0, nullptr});
+int grad_generic_num_blocks(long n, long m);
+
+// ---- kern_families.hip : the kinds that are no function of plain r^2 (family launchers: kern_tile.h) --------------
 // StdPeriodic dK/dx (standard_periodic.py:574-580) as a row reduction over a group of 32 dimensions from q_off:
 //   out[i][q] = sum_j W(i, j) K(x1_i, x2_j) sin(2 Delta_ijq),  W(i, j) = W[i * ldw + j], or W[j * ldw + i] if wt
 // (out: n x D row-major; the caller applies -pi / (2 T_q l_q^2)).  Xt1 / Xt2: unscaled, dimension-major.
@@ -317,24 +308,31 @@ int launch_grad_coreg(hipStream_t st, bool fused, KernParams kp, const double* X
                       const double* aa_scale = nullptr, const double* Mul = nullptr, long ldm = 0);
 // out[j] = kd[j] - sum_i M[i][j]^2  (the per-point Kdiag form of launch_col_reduce mode 1)
 void launch_col_reduce_vec(hipStream_t st, const double* M, long ld, long rows, long cols, const double* kd, double* out);
+
+// ---- kern_sparse.hip : the streaming sparse path's covariance passes with the column reductions fused in ----------
+// K(X1, X2) into Kout AND the column partials of psi1^T V = sum_i K[i][j] V[i][d] in one pass (one plain stationary part);
+// returns the number of row splits in colpart ([split][mcols][Dy]; combine with launch_sum_splits), 0 = not applicable
+int launch_kbuild_cols(hipStream_t st, KernParams kp, const double* Xt1, long ld1, long n, const double* Xt2, long ld2, long m,
+                       long mcols, double* Kout, long ldk, const double* V, int Dy, double* colpart);
+// sparse pass 2: theta partials + H^T [x~ | 1] column partials in one pass over the weights (k_grad_cols); 0 = not applicable
+int launch_grad_cols(hipStream_t st, KernParams kp, const double* Xt1, long ld1, long n, const double* Xt2, long ld2,
+                     long m, long mcols, const double* G, long ldg, RankTerm rk, double* partials, double* colpart,
+                     int* nblocks_out);
 // part[split][cols][nv] = sum over a row range of M[i][j] * V(i, c); V(i, c) = V[i*sr + c*sc] plus an optional
 // all-ones column; returns the number of row splits (sum them with launch_sum_splits)
 int launch_colreduce_multi(hipStream_t st, const double* M, long ld, long rows, long cols, const double* V, long sr,
                            long sc, int nvt, int ones, double* part);
 void launch_sum_splits(hipStream_t st, const double* src, long cnt, int nsplit, int accumulate, double* dst);
+
+// ---- reduce.hip : reductions, triangular solves and fetch helpers that stage no input slabs -----------------------
+// y = X r (lower-triangular X, n x n within npad), then a = X^T y   (Dy right-hand sides, row-major n x Dy)
+void launch_tri_matvec(hipStream_t st, const double* X, long ld, long n, const double* R, int Dy, double* tmp,
+                       double* alpha, double* partials);
+void launch_studentt_scale(hipStream_t st, const double* scal, double nu, long n, double* out);
 int trmv_chunk_rows(long n);        // rows per partial-sum chunk of launch_trmv_lower_T / launch_tri_matvec (partials: ceil(n / rows) * n * Dy)
 void launch_trmv_lower(hipStream_t st, const double* X, long ld, long n, const double* R, int Dy, double* y);
 void launch_trmv_lower_T(hipStream_t st, const double* X, long ld, long n, const double* y, int Dy, double* out,
                          double* partials);
-int gemm_last_clock(double* mhz, double* cycles);
-// general tiled GEMM C = alpha*op(A) op(B) + beta*C; M, N % 128 == 0, K % 16 == 0 (see k_gemm_full)
-void launch_gemm(hipStream_t st, int a_mcontig, int b_ncontig, long M, long N, long K, const double* A, long lda,
-                 const double* B, long ldb, double* C, long ldc, double alpha, double beta);
-// split-K Gram matrix of a tall panel: part[s] (lower 128-tiles of an mp x mp matrix, ld = mp) (+)= P_s^T P_s, where P_s
-// are rows [s*rows/S, (s+1)*rows/S) of the (rows x mp) row-major panel P; rows % (16*S) == 0
-void launch_gram_splitk(hipStream_t st, const double* P, long ldp, long rows, long mp, int S, int accumulate,
-                        double* part);
-int grad_generic_num_blocks(long n, long m);
 // sums `nblocks` rows of `stride` doubles in a fixed order into out[stride]
 void launch_reduce_partials(hipStream_t st, const double* partials, int nblocks, int stride, double* out);
 // out4[0]=sum alpha*R ; [1]=sum alpha^2 ; [2]=trace W ; [3]=2*sum(logsum) ; [6]=info[0] ; diag_out (n) = 0.5*(|alpha_i|^2 - Dy*W_ii)
@@ -350,13 +348,25 @@ void launch_pad_from_dense(hipStream_t st, const double* src, long n, double* A,
 // column reductions over a (rows x ld) matrix: mode 0: out[j*Dy+d] = sum_i M[i][j]*v[i*Dy+d]; mode 1: out[j] = c0 - sum_i M[i][j]^2
 void launch_col_reduce(hipStream_t st, const double* M, long ld, long rows, long cols, const double* v, int Dy,
                        double c0, int mode, double* out);
-
 // out_s[i][d] = sum_j K[i][j] v[j][d]  and (t_out != NULL)  t_out[i] = sum_j K[i][j] T[i][j]   over j < m, one wave per row
 void launch_rowdots(hipStream_t st, const double* K, const double* T, long ld, long rows, long m, const double* v, int Dy,
                     double* out_s, double* t_out);
 // M[i][j] *= sqrt(w[i]) into Out (may alias M), rows x cols (ld shared)
 void launch_rowscale_sqrt(hipStream_t st, const double* M, long ld, long rows, long cols, const double* w, double* Out);
+// M[i][j] * s[i] (inverse != 0: / s[i]) into Out (may alias M), rows x cols (ld shared): launch_rowscale_sqrt for a signed scale
+void launch_rowscale(hipStream_t st, const double* M, long ld, long rows, long cols, const double* s, int inverse, double* Out);
 
+// ---- gemm.hip : general GEMM and split-K Gram matrix --------------------------------------------------------------
+int gemm_last_clock(double* mhz, double* cycles);
+// general tiled GEMM C = alpha*op(A) op(B) + beta*C; M, N % 128 == 0, K % 16 == 0 (see k_gemm_full)
+void launch_gemm(hipStream_t st, int a_mcontig, int b_ncontig, long M, long N, long K, const double* A, long lda,
+                 const double* B, long ldb, double* C, long ldc, double alpha, double beta);
+// split-K Gram matrix of a tall panel: part[s] (lower 128-tiles of an mp x mp matrix, ld = mp) (+)= P_s^T P_s, where P_s
+// are rows [s*rows/S, (s+1)*rows/S) of the (rows x mp) row-major panel P; rows % (16*S) == 0
+void launch_gram_splitk(hipStream_t st, const double* P, long ldp, long rows, long mp, int S, int accumulate,
+                        double* part);
+
+// ---- laplace.hip : the Laplace session's passes over the resident K -----------------------------------------------
 // Laplace approximation (laplace.hip) over the resident K = kern.K(X) (npad x npad, ld = npad, symmetric, lower 64-tiles read)
 // A (lower 64-tiles) = I + diag(sw) K diag(sw) + jit I on the first n rows; identity in the padding   (laplace.py:333-334)
 void launch_laplace_B(hipStream_t st, const double* K, long npad, long n, const double* sw, double jit, double* A);
@@ -367,9 +377,9 @@ void launch_symv_lower(hipStream_t st, const double* K, long npad, long n, const
 // G (both triangles) = 0.5 (a a^T - diag(sw) Binv diag(sw)) + 0.5 (a u^T + u a^T), Binv read from its lower tiles (laplace.py:260-272)
 void launch_laplace_dLdK(hipStream_t st, const double* Binv, long npad, long n, const double* sw, const double* a,
                          const double* u, double* G);
-// VarGauss (vargauss.hip) over the same resident K; every matrix npad x npad with ld = npad
-// M[i][j] * s[i] (inverse != 0: / s[i]) into Out (may alias M), rows x cols (ld shared): launch_rowscale_sqrt for a signed scale
-void launch_rowscale(hipStream_t st, const double* M, long ld, long rows, long cols, const double* s, int inverse, double* Out);
+
+// ---- vargauss.hip : the k_vg_* passes of one backward -------------------------------------------------------------
+// VarGauss over the same resident K; every matrix npad x npad with ld = npad
 // lower triangle (lower 64-tiles) -> both triangles, in place
 void launch_vg_mirror(hipStream_t st, double* A, long npad);
 size_t vg_part_doubles(long npad);

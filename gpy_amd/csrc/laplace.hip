@@ -21,6 +21,212 @@ void laplace_session_free(LaplaceSession* s) {
     delete s;
 }
 
+#define KT 64      // edge of the tiles of the resident K and of every N x N buffer of the session (the covariance tile, kern_tile.h)
+
+// ------------------------------------------------------------------------------------------------
+// Laplace approximation (GPy/inference/latent_function_inference/laplace.py): the three passes over the resident K = kern.K(X)
+// that one mode search and its gradients need.  They share nothing with the assembly kernels above but the tile size.
+//
+// B = I + diag(sw) K diag(sw) (laplace.py:333-334), sw = sqrt(W), lower 64-tiles into A (npad x npad); identity in the
+// padding; `jit` (the jitchol ladder term) on the diagonal.  One read and one 32-byte store per four elements.
+__global__ __launch_bounds__(256) void k_laplace_B(const double* __restrict__ K, long ld, long n, const double* __restrict__ sw,
+                                                   double jit, int nt, double* __restrict__ A) {
+    const int t = threadIdx.x, tx = t & 15, ty = t >> 4;
+    const long ti = blockIdx.x / nt, tj = blockIdx.x % nt;
+    if (tj > ti) return;
+    const long j0 = tj * KT + tx * 4;
+    double wj[4];
+#pragma unroll
+    for (int b = 0; b < 4; ++b) wj[b] = (j0 + b < n) ? sw[j0 + b] : 0.0;
+#pragma unroll
+    for (int a = 0; a < 4; ++a) {
+        const long i = ti * KT + ty * 4 + a;
+        const double wi = (i < n) ? sw[i] : 0.0;
+        const d4 k = *reinterpret_cast<const d4*>(K + i * ld + j0);
+        d4 o;
+#pragma unroll
+        for (int b = 0; b < 4; ++b) {
+            const long j = j0 + b;
+            double v = (i < n && j < n) ? wi * k[b] * wj[b] : 0.0;
+            if (i == j) v += (i < n) ? 1.0 + jit : 1.0;
+            o[b] = v;
+        }
+        *reinterpret_cast<d4*>(A + i * ld + j0) = o;
+    }
+}
+void launch_laplace_B(hipStream_t st, const double* K, long npad, long n, const double* sw, double jit, double* A) {
+    const int nt = (int)(npad / KT);
+    hipLaunchKernelGGL(k_laplace_B, dim3((unsigned)((long)nt * nt)), dim3(256), 0, st, K, npad, n, sw, jit, nt, A);
+}
+
+// y = K v for NV right-hand sides from the LOWER 64-tiles of the symmetric resident K: every tile is read once (4 N^2 bytes) and
+// serves both its rows (y_i += K_ij v_j, j <= i) and, transposed, its columns (y_j += K_ij v_i, i > j).  Block = (row chunk c
+// of 64 rows, segment s of SYMV_SEG tiles of that chunk's tile row): the row sums of the segment go to rowpart[s][i], the column
+// sums of every tile to colpart[c][j]; k_symv_finish adds them in a fixed order: bit reproducible.  The next tile's four
+// 32-byte loads per lane are issued before the current tile's arithmetic (eight loads in flight per lane).
+#define SYMV_SEG 8
+template <int NV>
+__global__ __launch_bounds__(256) void k_symv_lower(const double* __restrict__ K, long ld, long n, const double* __restrict__ v0,
+                                                    const double* __restrict__ v1, double* __restrict__ rowpart,
+                                                    double* __restrict__ colpart) {
+    __shared__ double red[NV][16][KT + 1];
+    const int t = threadIdx.x, tx = t & 15, ty = t >> 4;
+    const long c = blockIdx.x, s = blockIdx.y;
+    const long tj0 = s * SYMV_SEG;
+    if (tj0 > c) return;
+    const long tj1 = (tj0 + SYMV_SEG - 1 < c) ? tj0 + SYMV_SEG - 1 : c;      // inclusive
+    const long i0 = c * KT + ty * 4;
+    const double* vv[2] = {v0, v1};
+    double vi[NV][4], racc[NV][4];
+#pragma unroll
+    for (int r = 0; r < NV; ++r)
+#pragma unroll
+        for (int a = 0; a < 4; ++a) {
+            vi[r][a] = (i0 + a < n) ? vv[r][i0 + a] : 0.0;
+            racc[r][a] = 0.0;
+        }
+    d4 cur[4], nxt[4];
+#pragma unroll
+    for (int a = 0; a < 4; ++a) cur[a] = *reinterpret_cast<const d4*>(K + (i0 + a) * ld + tj0 * KT + tx * 4);
+    for (long tj = tj0; tj <= tj1; ++tj) {
+        if (tj < tj1) {
+#pragma unroll
+            for (int a = 0; a < 4; ++a) nxt[a] = *reinterpret_cast<const d4*>(K + (i0 + a) * ld + (tj + 1) * KT + tx * 4);
+        }
+        const long j0 = tj * KT + tx * 4;
+        const bool diag = (tj == c);
+        double vj[NV][4], cs[NV][4];
+#pragma unroll
+        for (int r = 0; r < NV; ++r)
+#pragma unroll
+            for (int b = 0; b < 4; ++b) {
+                vj[r][b] = (j0 + b < n) ? vv[r][j0 + b] : 0.0;
+                cs[r][b] = 0.0;
+            }
+#pragma unroll
+        for (int a = 0; a < 4; ++a)
+#pragma unroll
+            for (int b = 0; b < 4; ++b) {
+                const double k = cur[a][b];
+                const bool lower = !diag || (j0 + b <= i0 + a), strict = !diag || (j0 + b < i0 + a);
+#pragma unroll
+                for (int r = 0; r < NV; ++r) {
+                    if (lower) racc[r][a] = fma(k, vj[r][b], racc[r][a]);
+                    if (strict) cs[r][b] = fma(k, vi[r][a], cs[r][b]);
+                }
+            }
+        __syncthreads();
+#pragma unroll
+        for (int r = 0; r < NV; ++r)
+#pragma unroll
+            for (int b = 0; b < 4; ++b) red[r][ty][tx * 4 + b] = cs[r][b];
+        __syncthreads();
+        if (t < KT * NV) {
+            const int r = t / KT, col = t % KT;
+            double sum = 0.0;
+#pragma unroll
+            for (int g = 0; g < 16; ++g) sum += red[r][g][col];
+            colpart[((long)r * gridDim.x + c) * ld + tj * KT + col] = sum;
+        }
+#pragma unroll
+        for (int a = 0; a < 4; ++a) cur[a] = nxt[a];
+    }
+    // row sums of the segment: the 16 column groups of a row in a fixed order
+    __syncthreads();
+#pragma unroll
+    for (int r = 0; r < NV; ++r)
+#pragma unroll
+        for (int a = 0; a < 4; ++a) red[r][tx][ty * 4 + a] = racc[r][a];
+    __syncthreads();
+    if (t < KT * NV) {
+        const int r = t / KT, row = t % KT;
+        double sum = 0.0;
+#pragma unroll
+        for (int g = 0; g < 16; ++g) sum += red[r][g][row];
+        rowpart[((long)r * gridDim.y + s) * ld + c * KT + row] = sum;
+    }
+}
+// y_j = sum over the segments of j's chunk of rowpart + sum over the chunks c >= j / 64 of colpart, both in ascending order
+__global__ void k_symv_finish(const double* __restrict__ rowpart, const double* __restrict__ colpart, long ld, long n, int nchunks,
+                              int nsegmax, double* __restrict__ y0, double* __restrict__ y1) {
+    const long j = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= n) return;
+    const int r = blockIdx.y;
+    const long cj = j / KT;
+    double sum = 0.0;
+    for (long s = 0; s * SYMV_SEG <= cj; ++s) sum += rowpart[((long)r * nsegmax + s) * ld + j];
+    for (long c = cj; c < nchunks; ++c) sum += colpart[((long)r * nchunks + c) * ld + j];
+    (r == 0 ? y0 : y1)[j] = sum;
+}
+size_t symv_part_doubles(long npad) {
+    const long nchunks = npad / KT, nseg = (nchunks + SYMV_SEG - 1) / SYMV_SEG;
+    return (size_t)2 * (size_t)(nchunks + nseg) * (size_t)npad;
+}
+void launch_symv_lower(hipStream_t st, const double* K, long npad, long n, const double* v0, const double* v1, double* y0,
+                       double* y1, double* part) {
+    const int nchunks = (int)((n + KT - 1) / KT), nseg = (nchunks + SYMV_SEG - 1) / SYMV_SEG, nv = v1 ? 2 : 1;
+    double* rowpart = part;
+    double* colpart = part + (size_t)2 * nseg * npad;
+    if (nv == 2)
+        hipLaunchKernelGGL((k_symv_lower<2>), dim3((unsigned)nchunks, (unsigned)nseg), dim3(256), 0, st, K, npad, n, v0, v1, rowpart,
+                           colpart);
+    else
+        hipLaunchKernelGGL((k_symv_lower<1>), dim3((unsigned)nchunks, (unsigned)nseg), dim3(256), 0, st, K, npad, n, v0, v0, rowpart,
+                           colpart);
+    hipLaunchKernelGGL(k_symv_finish, dim3((unsigned)((n + 255) / 256), (unsigned)nv), dim3(256), 0, st, rowpart, colpart, npad, n,
+                       nchunks, nseg, y0, y1);
+}
+
+// The symmetrised dL_dK of the Laplace approximation (laplace.py:260-272) from Binv = B^-1 (lower tiles, lauum) into G, BOTH
+// triangles (launch_grad_generic reads every element):
+//   G_ij = 0.5 (a_i a_j - sw_i Binv_ij sw_j) + 0.5 (a_i u_j + u_i a_j),   a = Ki_f,  u = dL_dfhat - K_Wi_i K dL_dfhat
+// One block per lower 64-tile: the tile is read once, written row-wise, and its mirror is written row-wise from LDS.
+__global__ __launch_bounds__(256) void k_laplace_dLdK(const double* __restrict__ Binv, long ld, long n,
+                                                      const double* __restrict__ sw, const double* __restrict__ a,
+                                                      const double* __restrict__ u, int nt, double* __restrict__ G) {
+    __shared__ double tile[KT][KT + 1];
+    const int t = threadIdx.x, tx = t & 15, ty = t >> 4;
+    const long ti = blockIdx.x / nt, tj = blockIdx.x % nt;
+    if (tj > ti) return;
+    const long i0 = ti * KT, j0 = tj * KT;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        const long i = i0 + ty * 4 + r;
+        const d4 bi = *reinterpret_cast<const d4*>(Binv + i * ld + j0 + tx * 4);
+        const double ai = (i < n) ? a[i] : 0.0, ui = (i < n) ? u[i] : 0.0, wi = (i < n) ? sw[i] : 0.0;
+#pragma unroll
+        for (int b = 0; b < 4; ++b) {
+            const long j = j0 + tx * 4 + b;
+            double v = 0.0;
+            if (i < n && j < n) {
+                const double aj = a[j], uj = u[j];
+                v = 0.5 * (ai * aj - wi * bi[b] * sw[j]) + 0.5 * (ai * uj + ui * aj);
+            }
+            tile[ty * 4 + r][tx * 4 + b] = v;
+        }
+    }
+    __syncthreads();
+    const bool diag = (ti == tj);
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        const int li = ty * 4 + r;
+        d4 o, m;
+#pragma unroll
+        for (int b = 0; b < 4; ++b) {
+            const int lj = tx * 4 + b;
+            o[b] = (diag && lj > li) ? tile[lj][li] : tile[li][lj];      // diagonal tile: the lower triangle on both sides
+            m[b] = tile[lj][li];
+        }
+        *reinterpret_cast<d4*>(G + (i0 + li) * ld + j0 + tx * 4) = o;
+        if (!diag) *reinterpret_cast<d4*>(G + (j0 + li) * ld + i0 + tx * 4) = m;
+    }
+}
+void launch_laplace_dLdK(hipStream_t st, const double* Binv, long npad, long n, const double* sw, const double* a,
+                         const double* u, double* G) {
+    const int nt = (int)(npad / KT);
+    hipLaunchKernelGGL(k_laplace_dLdK, dim3((unsigned)((long)nt * nt)), dim3(256), 0, st, Binv, npad, n, sw, a, u, nt, G);
+}
+
 // elementwise helpers on N-vectors (grid: ceil(n / 256) blocks of 256)
 __global__ void k_lap_sqrt(const double* __restrict__ w, long n, double* __restrict__ sw) {
     const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;

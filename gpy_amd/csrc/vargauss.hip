@@ -19,6 +19,240 @@
 
 #define VG_VGRID(n) dim3((unsigned)(((n) + 255) / 256)), dim3(256)
 
+#define KT 64      // edge of the tiles of the resident K and of every N x N buffer of the session (the covariance tile, kern_tile.h)
+
+// ------------------------------------------------------------------------------------------------
+// Variational Gaussian approximation (GPy/inference/latent_function_inference/var_gauss.py): the passes of one backward over
+// Ai = (I + diag(beta) K diag(beta))^-1, P1 = Ai Ai, P2 = Ai diag(beta^-2) Ai and the resident K.  Written like k_laplace_dLdK:
+// one block per lower 64-tile, 32-byte loads, the mirror written from LDS.
+// A symmetric matrix held in its lower triangle (lower 64-tiles, and the lower triangle of the diagonal tiles) -> both
+// triangles, in place: what the full-tile Gram products of the backward read.  A block reads its own tile only and writes
+// the mirrored one (or, on the diagonal, its own upper triangle), so no block reads what another writes.
+__global__ __launch_bounds__(256) void k_vg_mirror(double* __restrict__ A, long ld, int nt) {
+    __shared__ double tile[KT][KT + 1];
+    const int t = threadIdx.x, tx = t & 15, ty = t >> 4;
+    const long ti = blockIdx.x / nt, tj = blockIdx.x % nt;
+    if (tj > ti) return;
+    const long i0 = ti * KT, j0 = tj * KT;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        const d4 x = *reinterpret_cast<const d4*>(A + (i0 + ty * 4 + r) * ld + j0 + tx * 4);
+#pragma unroll
+        for (int b = 0; b < 4; ++b) tile[ty * 4 + r][tx * 4 + b] = x[b];
+    }
+    __syncthreads();
+    const bool diag = (ti == tj);
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        const int li = ty * 4 + r;
+        d4 o;
+#pragma unroll
+        for (int b = 0; b < 4; ++b) {
+            const int lj = tx * 4 + b;
+            o[b] = (diag && lj <= li) ? tile[li][lj] : tile[lj][li];
+        }
+        if (diag) *reinterpret_cast<d4*>(A + (i0 + li) * ld + j0 + tx * 4) = o;
+        else *reinterpret_cast<d4*>(A + (j0 + li) * ld + i0 + tx * 4) = o;
+    }
+}
+void launch_vg_mirror(hipStream_t st, double* A, long npad) {
+    const int nt = (int)(npad / KT);
+    hipLaunchKernelGGL(k_vg_mirror, dim3((unsigned)((long)nt * nt)), dim3(256), 0, st, A, npad, nt);
+}
+
+// First pass, while Ai is intact.  H holds P1 (lower tiles read) and receives, in place, the part of the symmetrised dL_dK
+// that needs Ai and P1:
+//   H_ij = 0.5 (alpha_i g_j + g_i alpha_j) - 0.5 (alpha_i alpha_j + beta_i beta_j (Ai_ij - P1_ij)),   g = dF_dm
+// and every tile leaves the partial sums of the two beta gradients (var_gauss.py:51,57), f1 = Sigma_ij^2 weighted by
+// v = dF_dv and f2 = K_ij (Ai - P1)_ij weighted by beta, over its rows for its 64 columns (cp[q][ti][j]) and, transposed,
+// over its columns for its 64 rows (rp[q][tj][i]; the diagonal tile: lower / strictly lower, as k_symv_lower):
+//   Sigma_ij = -Ai_ij / (beta_i beta_j) off the diagonal, Sigma_ii = var_i (the forward's cancellation-free diag Sigma).
+// k_vg_finish_vec adds the partials in a fixed order: no atomics, two calls give the same bytes.
+__global__ __launch_bounds__(256) void k_vg_assemble(const double* __restrict__ Ai, const double* __restrict__ K, long ld, long n,
+                                                     const double* __restrict__ beta, const double* __restrict__ alpha,
+                                                     const double* __restrict__ g, const double* __restrict__ v,
+                                                     const double* __restrict__ var, int nt, int scaled, double* __restrict__ H,
+                                                     double* __restrict__ cp, double* __restrict__ rp) {
+    __shared__ double red[2][16][KT + 1];
+    const int t = threadIdx.x, tx = t & 15, ty = t >> 4;
+    const long ti = blockIdx.x / nt, tj = blockIdx.x % nt;
+    if (tj > ti) return;
+    const long i0 = ti * KT + ty * 4, j0 = tj * KT + tx * 4;
+    const bool diag = (ti == tj);
+    double bj[4], aj[4], gj[4], vj[4], cs1[4], cs2[4], rs1[4], rs2[4];
+#pragma unroll
+    for (int b = 0; b < 4; ++b) {
+        const bool in = j0 + b < n;
+        bj[b] = in ? beta[j0 + b] : 0.0;
+        aj[b] = in ? alpha[j0 + b] : 0.0;
+        gj[b] = in ? g[j0 + b] : 0.0;
+        vj[b] = in ? v[j0 + b] : 0.0;
+        cs1[b] = cs2[b] = 0.0;
+    }
+#pragma unroll
+    for (int a = 0; a < 4; ++a) {
+        const long i = i0 + a;
+        const bool in_i = i < n;
+        const double bi = in_i ? beta[i] : 0.0, ai = in_i ? alpha[i] : 0.0, gi = in_i ? g[i] : 0.0, vi = in_i ? v[i] : 0.0;
+        const double si = in_i ? var[i] : 0.0;
+        const d4 x = *reinterpret_cast<const d4*>(Ai + i * ld + j0);
+        const d4 p = *reinterpret_cast<const d4*>(H + i * ld + j0);
+        const d4 k = *reinterpret_cast<const d4*>(K + i * ld + j0);
+        d4 o;
+        double r1 = 0.0, r2 = 0.0;
+#pragma unroll
+        for (int b = 0; b < 4; ++b) {
+            const long j = j0 + b;
+            double h = 0.0;
+            if (in_i && j < n) {
+                const double d = x[b] - p[b], bb = bi * bj[b];
+                h = 0.5 * (ai * gj[b] + gi * aj[b]) - 0.5 * (ai * aj[b] + bb * d);
+                if (scaled) h /= bb;                                 // the exact form accumulates its Gram products onto H / (beta_i beta_j)
+                const double s = (i == j) ? si : x[b] / bb;
+                const double f1 = s * s, f2 = k[b] * d;
+                if (!diag || j <= i) {
+                    cs1[b] = fma(f1, vi, cs1[b]);
+                    cs2[b] = fma(f2, bi, cs2[b]);
+                }
+                if (!diag || j < i) {
+                    r1 = fma(f1, vj[b], r1);
+                    r2 = fma(f2, bj[b], r2);
+                }
+            }
+            o[b] = h;
+        }
+        *reinterpret_cast<d4*>(H + i * ld + j0) = o;
+        rs1[a] = r1;
+        rs2[a] = r2;
+    }
+    // column sums: the 16 row groups of a column in a fixed order
+#pragma unroll
+    for (int b = 0; b < 4; ++b) {
+        red[0][ty][tx * 4 + b] = cs1[b];
+        red[1][ty][tx * 4 + b] = cs2[b];
+    }
+    __syncthreads();
+    if (t < 2 * KT) {
+        const int q = t / KT, col = t % KT;
+        double sum = 0.0;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) sum += red[q][r][col];
+        cp[((long)q * nt + ti) * ld + tj * KT + col] = sum;
+    }
+    __syncthreads();
+    // row sums: the 16 column groups of a row in a fixed order
+#pragma unroll
+    for (int a = 0; a < 4; ++a) {
+        red[0][tx][ty * 4 + a] = rs1[a];
+        red[1][tx][ty * 4 + a] = rs2[a];
+    }
+    __syncthreads();
+    if (t < 2 * KT) {
+        const int q = t / KT, row = t % KT;
+        double sum = 0.0;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) sum += red[q][r][row];
+        rp[((long)q * nt + tj) * ld + ti * KT + row] = sum;
+    }
+}
+// beta.gradient_j = -2 beta_j S1_j - S2_j with S_j = the column partials of the tiles below j's chunk + the row partials of the
+// tiles left of it, both ascending (var_gauss.py:51,57,60);  alpha.gradient_j = (K dF_dm)_j - m_j (:48,59)
+__global__ void k_vg_finish_vec(const double* __restrict__ cp, const double* __restrict__ rp, long ld, long n, int nt,
+                                const double* __restrict__ beta, const double* __restrict__ Kg, const double* __restrict__ m,
+                                double* __restrict__ dalpha, double* __restrict__ dbeta) {
+    const long j = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= n) return;
+    const long cj = j / KT;
+    double s[2];
+    for (int q = 0; q < 2; ++q) {
+        double sum = 0.0;
+        for (long ti = cj; ti < nt; ++ti) sum += cp[((long)q * nt + ti) * ld + j];
+        for (long tj = 0; tj <= cj; ++tj) sum += rp[((long)q * nt + tj) * ld + j];
+        s[q] = sum;
+    }
+    dbeta[j] = -2.0 * beta[j] * s[0] - s[1];
+    dalpha[j] = Kg[j] - m[j];
+}
+// Second pass: G = H + 0.5 (v_i + v_j) beta_i beta_j P2_ij from the lower tiles of H and P2, into BOTH triangles of H's buffer
+// (launch_grad_generic reads every element); the upper triangle is the copy of the lower one, so G is bitwise symmetric
+// exact != 0: G's buffer holds G_ij / (beta_i beta_j) in its lower tiles (launch_vg_assemble with scaled, then the Gram products of
+// the exact form accumulated onto it) and is multiplied back; P2 is not read
+__global__ __launch_bounds__(256) void k_vg_dLdK(const double* __restrict__ P2, long ld, long n, const double* __restrict__ beta,
+                                                 const double* __restrict__ v, int nt, int exact, double* __restrict__ G) {
+    __shared__ double tile[KT][KT + 1];
+    const int t = threadIdx.x, tx = t & 15, ty = t >> 4;
+    const long ti = blockIdx.x / nt, tj = blockIdx.x % nt;
+    if (tj > ti) return;
+    const long i0 = ti * KT, j0 = tj * KT;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        const long i = i0 + ty * 4 + r;
+        const d4 h = *reinterpret_cast<const d4*>(G + i * ld + j0 + tx * 4);
+        d4 p = {0.0, 0.0, 0.0, 0.0};
+        if (!exact) p = *reinterpret_cast<const d4*>(P2 + i * ld + j0 + tx * 4);
+        const double bi = (i < n) ? beta[i] : 0.0, vi = (i < n) ? v[i] : 0.0;
+#pragma unroll
+        for (int b = 0; b < 4; ++b) {
+            const long j = j0 + tx * 4 + b;
+            double val = 0.0;
+            if (i < n && j < n) val = exact ? h[b] * (bi * beta[j]) : h[b] + 0.5 * (vi + v[j]) * (bi * beta[j]) * p[b];
+            tile[ty * 4 + r][tx * 4 + b] = val;
+        }
+    }
+    __syncthreads();
+    const bool diag = (ti == tj);
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        const int li = ty * 4 + r;
+        d4 o, m;
+#pragma unroll
+        for (int b = 0; b < 4; ++b) {
+            const int lj = tx * 4 + b;
+            o[b] = (diag && lj > li) ? tile[lj][li] : tile[li][lj];      // diagonal tile: the lower triangle on both sides
+            m[b] = tile[lj][li];
+        }
+        *reinterpret_cast<d4*>(G + (i0 + li) * ld + j0 + tx * 4) = o;
+        if (!diag) *reinterpret_cast<d4*>(G + (j0 + li) * ld + i0 + tx * 4) = m;
+    }
+}
+size_t vg_part_doubles(long npad) { return (size_t)4 * (size_t)(npad / KT) * (size_t)npad; }
+void launch_vg_assemble(hipStream_t st, const double* Ai, const double* K, long npad, long n, const double* beta,
+                        const double* alpha, const double* g, const double* v, const double* var, int scaled, double* H, double* part) {
+    const int nt = (int)(npad / KT);
+    double* cp = part;
+    double* rp = part + (size_t)2 * nt * npad;
+    hipLaunchKernelGGL(k_vg_assemble, dim3((unsigned)((long)nt * nt)), dim3(256), 0, st, Ai, K, npad, n, beta, alpha, g, v, var, nt,
+                       scaled, H, cp, rp);
+}
+void launch_vg_finish_vec(hipStream_t st, const double* part, long npad, long n, const double* beta, const double* Kg,
+                          const double* m, double* dalpha, double* dbeta) {
+    const int nt = (int)(npad / KT);
+    hipLaunchKernelGGL(k_vg_finish_vec, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, part, part + (size_t)2 * nt * npad,
+                       npad, n, nt, beta, Kg, m, dalpha, dbeta);
+}
+void launch_vg_dLdK(hipStream_t st, const double* P2, long npad, long n, const double* beta, const double* v, int exact, double* G) {
+    const int nt = (int)(npad / KT);
+    hipLaunchKernelGGL(k_vg_dLdK, dim3((unsigned)((long)nt * nt)), dim3(256), 0, st, P2, npad, n, beta, v, nt, exact, G);
+}
+// Out[i][j] = M[i][j] sqrt(max(sign v_i, 0)) / |beta_i| for i < rows, 0 for rows <= i < allrows (cols wide, ld shared): the factor R
+// of Ai diag(max(sign v, 0) / beta^2) Ai = R^T R, one per sign of dF_dv
+__global__ void k_vg_rowscale_v(const double* __restrict__ M, long ld, long rows, long cols, const double* __restrict__ v,
+                                const double* __restrict__ beta, double sign, double* __restrict__ Out) {
+    const long j = (long)blockIdx.y * blockDim.x + threadIdx.x, i = blockIdx.x;
+    if (j >= cols) return;
+    double s = 0.0;
+    if (i < rows) {
+        const double w = sign * v[i];
+        s = w > 0.0 ? sqrt(w) / fabs(beta[i]) : 0.0;
+    }
+    Out[i * ld + j] = s != 0.0 ? M[i * ld + j] * s : 0.0;
+}
+void launch_vg_rowscale_v(hipStream_t st, const double* M, long ld, long rows, long allrows, long cols, const double* v,
+                          const double* beta, double sign, double* Out) {
+    hipLaunchKernelGGL(k_vg_rowscale_v, dim3((unsigned)allrows, (unsigned)((cols + 255) / 256)), dim3(256), 0, st, M, ld, rows, cols, v,
+                       beta, sign, Out);
+}
+
 static int vg_check_beta(const double* beta, long n) {
     for (long i = 0; i < n; ++i)
         if (!std::isfinite(beta[i]) || beta[i] == 0.0) {

@@ -8,7 +8,7 @@ interface through which the inference classes describe any kernel, leaf or combi
 `_slice_X`, `jitter_diag`).  The leaves: the stationary kernels `RBF` / `ExpQuad` / `Matern52` / `Matern32` / `Exponential` /
 `OU` / `RatQuad` / `Cosine` / `Sinc` / `ExpQuadCosine` (`GPy/kern/src/stationary.py`, `rbf.py`), `StdPeriodic`,
 `Coregionalize`, `Linear`, `MLP`, `Poly` and the static `White` / `Bias`; the combinations: `Add` and `Prod`.  Same constructor arguments, parameter names, link order and `.gradient`
-side effects as the reference.  All array math runs in hand-written HIP kernels (csrc/kern.hip); there is no NumPy fallback.
+side effects as the reference.  All array math runs in hand-written HIP kernels (csrc/kern*.hip); there is no NumPy fallback.
 """
 import numpy as np
 

@@ -1,5 +1,5 @@
 """Long-double (x86 80-bit) restatement of the Laplace / EP device session on the exact context (C-ABI mi355gp_laplace_* and
-mi355gp_ep_*, csrc/laplace.hip, csrc/ep.hip and the session kernels at the end of csrc/kern.hip), one function per device call,
+mi355gp_ep_*, csrc/laplace.hip with its session kernels and csrc/ep.hip), one function per device call,
 and the shape sweep that tests/test_oracle_laplace_ld.py (CPU) and tests/test_gpu_laplace_shapes.py (GPU) share.  Written from
 the formulas of the reference as laplace.hip and ep.hip cite them:
 

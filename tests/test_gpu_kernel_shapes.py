@@ -53,7 +53,7 @@ stationary.py:225-232); the device returned entries of 1e-17 ... 5e-16 (RBF iso:
 0]]).  `mi355gp_gradients_X` forms x_iq sum_j H_ij - sum_j H_ij x_jq from the column reduction H^T [X2~ | 1] with
 H = dL_dK dK/dr / r, and for these kinds dK/dr / r stays finite at r = 0 (-K for RBF), so a coincident pair was not masked but
 left to cancel, which it does only to rounding (the Exponential kernel, masked at r = 0 of necessity, was exact).  `k_grad` and
-`k_grad_ext` (csrc/kern.hip) now store H_ij = 0 where r_ij = 0.
+`k_grad_ext` (csrc/kern_ext.hip) now store H_ij = 0 where r_ij = 0.
 """
 import os
 

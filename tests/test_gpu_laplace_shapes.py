@@ -1,6 +1,6 @@
 """GPU (-m gpu): the Laplace / EP session on the exact context -- mi355gp_laplace_begin / newton / finish / gradients / implicit /
-predict, mi355gp_ep_recompute / mi355gp_ep_sweep and the three fetches, i.e. csrc/laplace.hip, csrc/ep.hip and the session
-kernels at the end of csrc/kern.hip -- at every shape edge, judged against the long-double restatement tests/laplace_ld.py
+predict, mi355gp_ep_recompute / mi355gp_ep_sweep and the three fetches, i.e. csrc/laplace.hip with its session
+kernels and csrc/ep.hip -- at every shape edge, judged against the long-double restatement tests/laplace_ld.py
 (80-bit; tests/test_oracle_laplace_ld.py is its own proof).
 
 Judge (laplace_ld.judge): err(q) = max |got - q_ld| / max |q_ld| <= max(32 e64(q), 256 eps64 kappa), e64 = the distance of the

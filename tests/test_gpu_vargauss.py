@@ -1,6 +1,6 @@
 """GPU (-m gpu): VarGauss on the exact context -- mi355gp_vargauss_forward / mi355gp_vargauss_backward inside the session of
-mi355gp_laplace_begin, mi355gp_laplace_predict and the three fetches, i.e. csrc/vargauss.hip and the k_vg_* kernels at the end of
-csrc/kern.hip -- at every shape edge, judged against the long-double restatement tests/vargauss_ld.py (80-bit;
+mi355gp_laplace_begin, mi355gp_laplace_predict and the three fetches, i.e. csrc/vargauss.hip with its k_vg_*
+kernels -- at every shape edge, judged against the long-double restatement tests/vargauss_ld.py (80-bit;
 tests/test_oracle_vargauss.py holds it against the reference's own fixtures).
 
 Judge (vargauss_ld.judge, the rule of laplace_ld.judge): err(q) = max |got - q_ld| / max |q_ld| <= max(32 e64(q), 256 eps64 kappa),

@@ -422,3 +422,22 @@ def test_every_tile_of_a_persistent_launch_has_exactly_one_owner(tune):
             assert all(v == -2 for v in upper)
             if nw >= 136:
                 assert most <= 48, (nt, nw, most)
+
+
+def test_makefile_lists_every_source_and_header():
+    """A file left out of SRCS links into nothing and shows only as an undefined symbol where the library is loaded; a header
+    left out of HDRS is edited without a rebuild."""
+    import glob
+    import os
+    import re
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    csrc = os.path.join(root, "gpy_amd", "csrc")
+    text = open(os.path.join(csrc, "Makefile")).read()
+    var = {name: re.search(r"^%s\s*=\s*(.*)$" % name, text, re.M).group(1).split() for name in ("SRCS", "HDRS")}
+    on_disk = sorted(os.path.basename(p) for p in glob.glob(os.path.join(csrc, "*.hip")))
+    assert sorted(var["SRCS"]) == on_disk
+    assert len(set(var["SRCS"])) == len(var["SRCS"]) and len(set(var["HDRS"])) == len(var["HDRS"])
+    headers = [os.path.basename(p) for p in glob.glob(os.path.join(csrc, "*.h"))]
+    headers += ["../../include/" + os.path.basename(p) for p in glob.glob(os.path.join(root, "include", "*.h"))]
+    assert headers and set(headers) <= set(var["HDRS"]), sorted(set(headers) - set(var["HDRS"]))
+    assert all(os.path.isfile(os.path.join(csrc, h)) for h in var["HDRS"])

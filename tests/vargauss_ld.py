@@ -1,5 +1,5 @@
 """Long-double (x86 80-bit) restatement of one VarGauss evaluation on the exact context (C-ABI mi355gp_vargauss_forward /
-mi355gp_vargauss_backward, csrc/vargauss.hip and the k_vg_* kernels at the end of csrc/kern.hip) and the shape sweep that
+mi355gp_vargauss_backward, csrc/vargauss.hip with its k_vg_* kernels) and the shape sweep that
 tests/test_oracle_vargauss.py (CPU) and tests/test_gpu_vargauss.py (GPU) share.  Written from the formulas of the reference
 (GPy/inference/latent_function_inference/var_gauss.py:34-65), not from the device's identities:
 

@@ -1,4 +1,4 @@
-"""Compare two AMDGPU assembly files (`hipcc --save-temps`: *-gfx950.s) kernel by kernel.
+"""Compare two sets of AMDGPU assembly files (`hipcc --save-temps`: *-gfx950.s) kernel by kernel.
 
 Per kernel symbol: the four resource figures of its `.amdhsa_kernel` block (next_free_vgpr, next_free_sgpr,
 group_segment_fixed_size, private_segment_fixed_size) and the histogram of its opcodes.  Two kernels MATCH if the figures
@@ -7,7 +7,10 @@ are equal and the opcode multisets are equal once scalar-ALU and branch instruct
 the vector units, LDS and memory are asked to do.  Kernels whose name matches --free are reported but not held to it.
 Exit status 1 if a held kernel differs or exists on one side only.
 
-    python tools/isa_compare.py OLD.s NEW.s [--free REGEX] [--verbose]
+    python tools/isa_compare.py OLD.s[,OLD2.s,...] NEW.s[,NEW2.s,...] [--free REGEX] [--verbose]
+
+Either side may be several files, separated by commas: a kernel meets its counterpart by name, whichever file holds it (code
+that moved between translation units).  A kernel defined in two files of one side is an error.
 """
 import argparse
 import collections
@@ -54,6 +57,18 @@ def parse(path):
     return out
 
 
+def parse_all(paths):
+    """parse() over a comma-separated list of files, merged; a kernel name may come from one of them only"""
+    out = {}
+    for path in paths.split(","):
+        one = parse(path)
+        twice = sorted(set(one) & set(out))
+        if twice:
+            sys.exit(f"{path}: kernels already defined in an earlier file of the same side: {', '.join(twice)}")
+        out.update(one)
+    return out
+
+
 def held(ops):
     return collections.Counter({o: c for o, c in ops.items() if not o.startswith("s_") or o in KEPT_SCALAR})
 
@@ -68,12 +83,12 @@ def demangle(names):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("old")
-    ap.add_argument("new")
+    ap.add_argument("old", help="assembly file, or several separated by commas")
+    ap.add_argument("new", help="assembly file, or several separated by commas")
     ap.add_argument("--free", default=None, help="regex on the demangled name: kernels reported but not held to the condition")
     ap.add_argument("--verbose", action="store_true", help="print the full opcode histogram of every kernel")
     a = ap.parse_args()
-    A, B = parse(a.old), parse(a.new)
+    A, B = parse_all(a.old), parse_all(a.new)
     names = sorted(set(A) | set(B))
     nsame = nmatch = 0
     bad, free_diff = [], []

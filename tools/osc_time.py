@@ -1,7 +1,7 @@
 """Device time of one fused exact-GP evaluation with Cosine, Sinc and ExpQuadCosine next to RBF and RatQuad in the same run: the
 context's own `stage_ms` (HIP events on the launching stream) -- K build (MI355GP_T_KBUILD), gradient pass (MI355GP_T_GRAD) and
 the total -- at N = 8192 with D = 1 and D = 8 (isotropic; the oscillating kinds act on column 0 alone, where they are positive
-definite, and are summed with a White part at every D so that the factorisation never fails).  Medians of 7 after 2 warm-ups.
+definite, and are summed with a White part at every D so that the factorisation never fails).  Medians of 7 after 2 warm-ups (with the minimum and maximum of each, for A/B margins).
 A record, no gate: the new kernels are not tuned.
 
     python tools/osc_time.py [--reps 7] [--out profiles]      (needs the GPU; writes profiles/osc_time_n8192.json)
@@ -47,6 +47,8 @@ def run(reps, warmup=2):
                     ms.append(r["stage_ms"])
             res["kinds"]["%s_d%d" % (kind, D)] = dict(
                 kbuild_ms=float(np.median([m["kbuild"] for m in ms])), grad_ms=float(np.median([m["grad"] for m in ms])),
+                kbuild_ms_min_max=[float(min(m["kbuild"] for m in ms)), float(max(m["kbuild"] for m in ms))],
+                grad_ms_min_max=[float(min(m["grad"] for m in ms)), float(max(m["grad"] for m in ms))],
                 total_ms=float(np.median([m["total"] for m in ms])),
                 total_ms_min_max=[float(min(m["total"] for m in ms)), float(max(m["total"] for m in ms))], log_marginal=float(r["lml"]))
     ctx.close()
