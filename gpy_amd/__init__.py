@@ -12,6 +12,7 @@ from .inference import ExactGaussianInference, ExactStudentTInference
 from .laplace import Laplace, LaplacePosterior
 from .ep import EP
 from .vargauss import VarGauss, VarGaussPosterior
+from .kron import GaussianGridInference, GpGrid, GPRegressionGrid, GridPosterior
 from .kern import (OU, RBF, Add, Prod, Bias, Coregionalize, Cosine, ExpQuad, ExpQuadCosine, Sinc, Exponential, Linear, Matern32, Matern52, MLP, Poly, RatQuad,
                    Stationary, StdPeriodic, White)
 from .likelihoods import Bernoulli, Gaussian, HeteroscedasticGaussian, MixedNoise, Poisson, StudentT
@@ -26,7 +27,7 @@ from .svgp import SVGPPosterior
 from .variational import NormalPosterior, NormalPrior
 
 __all__ = ["RBF", "OU", "ExpQuad", "HeteroscedasticGaussian", "StudentTPosterior", "Matern52", "Matern32", "Exponential", "RatQuad", "Cosine", "Sinc", "ExpQuadCosine", "StdPeriodic", "Coregionalize", "Linear", "MLP", "Poly", "MixedNoise", "Stationary", "White", "Bias", "Add", "Prod", "Gaussian", "ExactGaussianInference", "ExactStudentTInference",
-           "PosteriorExact", "GP", "GPRegression", "GPHeteroscedasticRegression", "GPCoregionalizedRegression", "Laplace", "LaplacePosterior", "EP", "PosteriorEP", "Bernoulli", "StudentT", "Poisson", "GPClassification", "VarDTC", "SparseGP", "SparseGPRegression", "SVGP", "SVGPPosterior", "NormalPosterior", "NormalPrior", "BayesianGPLVM", "FITC", "PEP", "EPDTC", "SparseGPClassification", "VarGauss", "VarGaussPosterior", "GPVariationalGaussianApproximation", "MI355GPError", "build", "device_count"]
+           "PosteriorExact", "GP", "GPRegression", "GPHeteroscedasticRegression", "GPCoregionalizedRegression", "Laplace", "LaplacePosterior", "EP", "PosteriorEP", "Bernoulli", "StudentT", "Poisson", "GPClassification", "VarDTC", "SparseGP", "SparseGPRegression", "SVGP", "SVGPPosterior", "NormalPosterior", "NormalPrior", "BayesianGPLVM", "FITC", "PEP", "EPDTC", "SparseGPClassification", "VarGauss", "VarGaussPosterior", "GPVariationalGaussianApproximation", "GaussianGridInference", "GridPosterior", "GpGrid", "GPRegressionGrid", "MI355GPError", "build", "device_count"]
 
 # GPy's import paths, so that `import gpy_amd as GPy` reads like the reference on this path:
 #   GPy.kern.RBF, GPy.likelihoods.Gaussian, GPy.models.GPRegression / SparseGPRegression / GPHeteroscedasticRegression,
@@ -36,14 +37,17 @@ __all__ = ["RBF", "OU", "ExpQuad", "HeteroscedasticGaussian", "StudentTPosterior
 #   GPy.inference.latent_function_inference.FITC / PEP (and .fitc.FITC, .pep.PEP),
 #   GPy.inference.latent_function_inference.EPDTC (and .expectation_propagation.EPDTC), GPy.models.SparseGPClassification,
 #   GPy.inference.latent_function_inference.VarGauss (and .var_gauss.VarGauss), GPy.models.GPVariationalGaussianApproximation,
+#   GPy.models.GPRegressionGrid, GPy.core.GpGrid, GPy.inference.latent_function_inference.GaussianGridInference (and
+#   .gaussian_grid_inference.GaussianGridInference, .grid_posterior.GridPosterior), GPy.kern.GridRBF,
 #   GPy.util.choleskies, GPy.models.BayesianGPLVM, GPy.util.initialization.initialize_latent
-from . import ep, epdtc, inference, kern, laplace, likelihoods, link_functions, linalg, models, pep, sparse, svgp, util, vargauss  # noqa: E402
+from . import ep, epdtc, inference, kern, kron, laplace, likelihoods, link_functions, linalg, models, pep, sparse, svgp, util, vargauss  # noqa: E402
 import types as _types  # noqa: E402
 
 models.SparseGPRegression = SparseGPRegression
 models.BayesianGPLVM = BayesianGPLVM
 models.SparseGPClassification = SparseGPClassification
-core = _types.SimpleNamespace(GP=GP, SparseGP=SparseGP, SVGP=SVGP, svgp=_types.SimpleNamespace(SVGP=SVGP), parameterization=_types.SimpleNamespace(
+models.GPRegressionGrid = GPRegressionGrid
+core = _types.SimpleNamespace(GP=GP, GpGrid=GpGrid, gp_grid=_types.SimpleNamespace(GpGrid=GpGrid), SparseGP=SparseGP, SVGP=SVGP, svgp=_types.SimpleNamespace(SVGP=SVGP), parameterization=_types.SimpleNamespace(
     variational=_types.SimpleNamespace(NormalPosterior=NormalPosterior, NormalPrior=NormalPrior)))
 likelihoods.mixed_noise = _types.SimpleNamespace(MixedNoise=MixedNoise)
 inference.latent_function_inference = _types.SimpleNamespace(
@@ -54,4 +58,7 @@ inference.latent_function_inference = _types.SimpleNamespace(
     exact_gaussian_inference=_types.SimpleNamespace(ExactGaussianInference=ExactGaussianInference),
     var_dtc=_types.SimpleNamespace(VarDTC=VarDTC), SVGP=svgp.SVGP, svgp=_types.SimpleNamespace(SVGP=svgp.SVGP),
     FITC=FITC, PEP=PEP, fitc=_types.SimpleNamespace(FITC=FITC), pep=_types.SimpleNamespace(PEP=PEP),
-    VarGauss=VarGauss, var_gauss=_types.SimpleNamespace(VarGauss=VarGauss))
+    VarGauss=VarGauss, var_gauss=_types.SimpleNamespace(VarGauss=VarGauss),
+    GaussianGridInference=GaussianGridInference, GridPosterior=GridPosterior,
+    gaussian_grid_inference=_types.SimpleNamespace(GaussianGridInference=GaussianGridInference),
+    grid_posterior=_types.SimpleNamespace(GridPosterior=GridPosterior))

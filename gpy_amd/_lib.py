@@ -84,6 +84,7 @@ def build(force=False):
     srcs.append(os.path.join(_HERE, "..", "include", "mi355gp_debug_tileops.h"))
     srcs.append(os.path.join(_HERE, "..", "include", "mi355gp_epdtc.h"))
     srcs.append(os.path.join(_HERE, "..", "include", "mi355gp_vargauss.h"))
+    srcs.append(os.path.join(_HERE, "..", "include", "mi355gp_kron.h"))
     product = os.path.join(_HERE, "libmi355gp.so")
     if not force and os.path.exists(product) and os.path.exists(DIAG_LIB_PATH):
         t = min(os.path.getmtime(product), os.path.getmtime(DIAG_LIB_PATH))
@@ -219,6 +220,19 @@ VARGAUSS_ABI = {
     "mi355gp_vargauss_backward": [_vp, _dp, _dp, _dp, _dp, _dp],
     "mi355gp_vargauss_backward_exact": [_vp, _dp, _dp, _dp, _dp, _dp],
 }
+# include/mi355gp_kron.h: exact GP regression on a full Cartesian grid (Kronecker-structured covariance), in its order
+# (tests/test_oracle_kron.py holds the table against that header's prototypes)
+KRON_ABI = {
+    "mi355gp_kron_create": [_ci, _hp],
+    "mi355gp_kron_destroy": [_vp],
+    "mi355gp_kron_set_data": [_vp, _ci, _i64a, _dp],
+    "mi355gp_kron_solve": [_vp, _dp, _dp, _cd, _dp],
+    "mi355gp_kron_quadforms": [_vp, _ci, _dp, _dp, _dp],
+    "mi355gp_kron_predict": [_vp, _i64, _dp, _c_dp, _cd, _dp, _c_dp],
+    "mi355gp_kron_fetch": [_vp, _ci, _dp],
+    "mi355gp_kron_mode_probe": [_vp, _i64, _i64, _i64, _ci, _dp, _dp, _dp, _ci, _c_dp],
+    "mi355gp_kron_get_ms": [_vp, _c_dp],
+}
 TILEOPS = {"trmm_lower": 0, "trmm_lower_T": 1, "trmm64": 2, "gram_splitk": 3, "update_nt": 4}    # MI355GP_TILEOP_*
 
 
@@ -233,7 +247,7 @@ def lib():
         if not os.path.exists(LIB_PATH):
             build()
         L = ctypes.CDLL(LIB_PATH)
-        for table in (ABI, DEBUG_LAUUM_ABI, DEBUG_TILEOPS_ABI, EPDTC_ABI, VARGAUSS_ABI):
+        for table in (ABI, DEBUG_LAUUM_ABI, DEBUG_TILEOPS_ABI, EPDTC_ABI, VARGAUSS_ABI, KRON_ABI):
             for name, argtypes in table.items():
                 getattr(L, name).argtypes = argtypes
         L.mi355gp_last_error.restype = L.mi355gp_version.restype = _str
@@ -1101,3 +1115,83 @@ def dbg_tileop(op, dims, X, B, Out, alpha=1.0, device=0):
     check(lib().mi355gp_dbg_tileop(device, TILEOPS[op], da, _opt(arrs[0]), _opt(arrs[1]), out.ctypes.data_as(_c_dp), float(alpha)),
           "mi355gp_dbg_tileop")
     return out
+
+
+class KronContext(_Handle):
+    """One device context of the Kronecker grid path (include/mi355gp_kron.h) = one uploaded y on a grid G_1 x ... x G_D: y, alpha
+    and two work vectors of N = prod G_d doubles, nothing larger.  The flat index has the last dimension fastest."""
+    _create, _destroy = "mi355gp_kron_create", "mi355gp_kron_destroy"
+    FETCH_ALPHA = 0
+
+    def __init__(self, device=0):
+        super(KronContext, self).__init__(device)
+        self.G, self.N = (), 0
+
+    def set_data(self, G, y):
+        G = np.ascontiguousarray(G, dtype=np.int64).ravel()
+        y = f64(np.ravel(y))
+        assert G.size >= 1 and y.size == int(np.prod(G)), "y must have prod(G) entries"
+        check(lib().mi355gp_kron_set_data(self._h, G.size, G, y), "mi355gp_kron_set_data")
+        self.G, self.N = tuple(int(g) for g in G), y.size
+
+    def _mats(self, mats, what):
+        assert len(mats) == len(self.G) and all(np.shape(m) == (g, g) for m, g in zip(mats, self.G)), what + " must be D matrices G_d x G_d"
+        return f64(np.concatenate([np.ravel(f64(m)) for m in mats]))
+
+    def _vecs(self, vecs, what):
+        assert len(vecs) == len(self.G) and all(np.size(v) == g for v, g in zip(vecs, self.G)), what + " must be D vectors of G_d entries"
+        return f64(np.concatenate([np.ravel(f64(v)) for v in vecs]))
+
+    def solve(self, Qs, lams, noise):
+        """alpha stays resident: (y^T alpha, sum log(V + noise)); `noise` is the whole term on the diagonal"""
+        sc = np.zeros(2)
+        check(lib().mi355gp_kron_solve(self._h, self._mats(Qs, "Qs"), self._vecs(lams, "lams"), float(noise), sc), "mi355gp_kron_solve")
+        return float(sc[0]), float(sc[1])
+
+    def quadforms(self, factors, gammas):
+        """factors, gammas: one list of D matrices, resp. D vectors, per parameter: (q (nmat), s (nmat)) with
+        q_t = alpha^T ((x)A_d) alpha and s_t = sum_i ((x)gamma_d)_i / (V_i + noise)"""
+        assert len(factors) == len(gammas)
+        nmat = len(factors)
+        out = np.zeros(2 * max(nmat, 1))
+        F = f64(np.concatenate([self._mats(f, "factors") for f in factors])) if nmat else np.zeros(1)
+        g = f64(np.concatenate([self._vecs(v, "gammas") for v in gammas])) if nmat else np.zeros(1)
+        check(lib().mi355gp_kron_quadforms(self._h, nmat, F, g, out), "mi355gp_kron_quadforms")
+        return out[0:2 * nmat:2].copy(), out[1:2 * nmat:2].copy()
+
+    def predict(self, kx, bx, noise_pred, want_var=True):
+        """kx, bx: D blocks M x G_d (bx[d] = kx[d] Q_d): (mu (M), variance reduction (M) or None)"""
+        M = np.shape(kx[0])[0]
+        assert len(kx) == len(self.G) and all(np.shape(k) == (M, g) for k, g in zip(kx, self.G)), "kx must be D blocks M x G_d"
+        K = f64(np.concatenate([np.ravel(f64(k)) for k in kx]))
+        mu = np.empty(M)
+        B = var = None
+        if want_var:
+            assert len(bx) == len(self.G) and all(np.shape(b) == (M, g) for b, g in zip(bx, self.G)), "bx must be D blocks M x G_d"
+            B = f64(np.concatenate([np.ravel(f64(b)) for b in bx]))
+            var = np.empty(M)
+        check(lib().mi355gp_kron_predict(self._h, M, K, _opt(B), float(noise_pred), mu, _opt(var)), "mi355gp_kron_predict")
+        return mu, var
+
+    def fetch_alpha(self):
+        out = np.empty(self.N)
+        check(lib().mi355gp_kron_fetch(self._h, self.FETCH_ALPHA, out), "mi355gp_kron_fetch")
+        return out
+
+    def mode_probe(self, A, x, transA=False, reps=1):
+        """One mode product alone: x (P x G), A (R x G, or G x R with transA) -> (out (R x P), ms per launch)"""
+        A, x = f64(A), f64(x)
+        P, G = x.shape
+        R = A.shape[1] if transA else A.shape[0]
+        assert A.shape == ((G, R) if transA else (R, G))
+        out = np.empty((R, P))
+        ms = ctypes.c_double(0.0)
+        check(lib().mi355gp_kron_mode_probe(self._h, P, G, R, int(bool(transA)), A, x, out, int(reps), ctypes.byref(ms)),
+              "mi355gp_kron_mode_probe")
+        return out, ms.value
+
+    def last_ms(self):
+        """HIP-event time (ms) of the mode products and the scaling of the last solve + quadforms pair"""
+        ms = ctypes.c_double(0.0)
+        check(lib().mi355gp_kron_get_ms(self._h, ctypes.byref(ms)), "mi355gp_kron_get_ms")
+        return ms.value

@@ -260,6 +260,10 @@ class RBF(Stationary):
         if self.use_invLengthscale:
             self.lengthscale[:] = 1. / np.sqrt(self.inv_l.values + 1e-200)
 
+    def get_one_dimensional_kernel(self, dim):
+        """the per-dimension kernel of grid regression (reference `rbf.py:333-338`)"""
+        return GridRBF(input_dim=1, variance=self.variance.values.copy(), originalDimensions=dim)
+
     def _install_gradients(self, g):
         super(RBF, self)._install_gradients(g)
         if self.use_invLengthscale:
@@ -324,6 +328,48 @@ class RBF(Stationary):
         d = super(RBF, self).to_dict()
         d["inv_l"] = self.use_invLengthscale
         return d
+
+
+class GridRBF(object):
+    """One dimension's factor of an RBF on a Cartesian grid (reference `GPy/kern/src/grid_kerns.py:11-76`): an RBF on one
+    column with variance^(1 / originalDimensions), so that the Kronecker product over the D dimensions carries the variance once.
+    Host NumPy on G_d x G_d matrices: `GaussianGridInference` builds them per evaluation, the device never sees X.  Not a `Kern`:
+    it has no parameters of its own to optimise (`lengthscale` is set by the caller per dimension, as the reference does)."""
+
+    def __init__(self, input_dim=1, variance=1., lengthscale=None, ARD=False, active_dims=None, name="gridRBF",
+                 originalDimensions=1, useGPU=False):
+        assert int(input_dim) == 1 and not ARD, "GridRBF is the one-dimensional factor of a grid kernel"
+        self.input_dim, self.name, self.originalDimensions = 1, name, int(originalDimensions)
+        self.variance = float(np.ravel(np.asarray(variance, dtype=np.float64))[0])
+        self.lengthscale = 1.0 if lengthscale is None else float(np.ravel(np.asarray(lengthscale, dtype=np.float64))[0])
+
+    def _scaled_dist(self, X, X2=None):
+        X = np.asarray(X, dtype=np.float64).reshape(-1, 1)
+        X2 = X if X2 is None else np.asarray(X2, dtype=np.float64).reshape(-1, 1)
+        return np.abs(X - X2.T) / float(np.ravel(self.lengthscale)[0])
+
+    def K_of_r(self, r):
+        return (self.variance ** (float(1) / self.originalDimensions)) * np.exp(-0.5 * r ** 2)
+
+    def K(self, X, X2=None):
+        return self.K_of_r(self._scaled_dist(X, X2))
+
+    def dKdVar_of_r(self, r):
+        return np.exp(-0.5 * r ** 2)
+
+    def dKdLen_of_r(self, r, dimCheck, lengthscale):
+        """(reference `grid_kerns.py:64-73`): the factor of dimension d in d K / d lengthscale_t, with r^2 where d is t"""
+        k = (self.variance ** (float(1) / self.originalDimensions)) * np.exp(-0.5 * r ** 2)
+        lengthscale = float(np.ravel(lengthscale)[0])
+        if dimCheck:
+            return k * (r ** 2) / (lengthscale ** (float(1) / self.originalDimensions))
+        return k / (lengthscale ** (float(1) / self.originalDimensions))
+
+    def dKd_dVar(self, X, X2=None):
+        return self.dKdVar_of_r(self._scaled_dist(X, X2))
+
+    def dKd_dLen(self, X, dimension, lengthscale, X2=None):
+        return self.dKdLen_of_r(self._scaled_dist(X, X2), dimension, lengthscale)
 
 
 class ExpQuad(Stationary):
