@@ -83,6 +83,7 @@ def build(force=False):
     srcs.append(os.path.join(_HERE, "..", "include", "mi355gp_debug_lauum.h"))
     srcs.append(os.path.join(_HERE, "..", "include", "mi355gp_debug_tileops.h"))
     srcs.append(os.path.join(_HERE, "..", "include", "mi355gp_epdtc.h"))
+    srcs.append(os.path.join(_HERE, "..", "include", "mi355gp_sparse_diag.h"))
     srcs.append(os.path.join(_HERE, "..", "include", "mi355gp_vargauss.h"))
     srcs.append(os.path.join(_HERE, "..", "include", "mi355gp_kron.h"))
     product = os.path.join(_HERE, "libmi355gp.so")
@@ -213,6 +214,12 @@ EPDTC_ABI = {
     "mi355gp_epdtc_sweep": [_vp, _i64a, _dp, _cd, _cd, _ci] + [_dp] * 7 + [_c_dp],
     "mi355gp_epdtc_inference": [_vp, _ci, _parts, _dp, _i64, _dp, _dp, _cd, _dp] + [_c_dp] * 5,
 }
+# include/mi355gp_sparse_diag.h: the per-point diagonal of an expression on the sparse context (tests/test_sparse_lin_host.py holds
+# the table against that header's prototype)
+SPARSE_DIAG_ABI = {
+    "mi355gp_sparse_set_linear": [_vp, _ci],
+    "mi355gp_sparse_kdiag": [_vp, _ci, _parts] + [_c_dp] * 4,
+}
 # include/mi355gp_vargauss.h: the variational Gaussian approximation inside the Laplace session of an exact context, in its order
 # (tests/test_oracle_vargauss.py holds the table against that header's prototypes)
 VARGAUSS_ABI = {
@@ -247,7 +254,7 @@ def lib():
         if not os.path.exists(LIB_PATH):
             build()
         L = ctypes.CDLL(LIB_PATH)
-        for table in (ABI, DEBUG_LAUUM_ABI, DEBUG_TILEOPS_ABI, EPDTC_ABI, VARGAUSS_ABI, KRON_ABI):
+        for table in (ABI, DEBUG_LAUUM_ABI, DEBUG_TILEOPS_ABI, EPDTC_ABI, SPARSE_DIAG_ABI, VARGAUSS_ABI, KRON_ABI):
             for name, argtypes in table.items():
                 getattr(L, name).argtypes = argtypes
         L.mi355gp_last_error.restype = L.mi355gp_version.restype = _str
@@ -709,6 +716,25 @@ class SparseContext(_Handle):
         out = np.empty((nrows, self.M))
         check(lib().mi355gp_sparse_fetch_dLdKnm(self._h, int(row0), int(nrows), out), "mi355gp_sparse_fetch_dLdKnm")
         return out
+
+    def set_linear(self, on=True):
+        """Linear parts on this context's inference and prediction entry points (`mi355gp_sparse_set_linear`); off at first"""
+        check(lib().mi355gp_sparse_set_linear(self._h, int(bool(on))), "mi355gp_sparse_set_linear")
+
+    def kdiag(self, specs, w=None):
+        """Kdiag of the expression at the context's rows (`mi355gp_sparse_kdiag`): kd (N), and with weights w (N) also
+        (sum w kd, sum w^2 kd) and the gradient of sum w kd in the parts' parameters, concatenated in theta order --
+        what `update_gradients_diag(w, X)` installs.  Returns kd, or (kd, sums, ddiag)."""
+        arr, keep, ntheta = make_parts(specs)
+        kd = np.empty(self.N)
+        if w is None:
+            check(lib().mi355gp_sparse_kdiag(self._h, len(specs), arr, None, _opt(kd), None, None), "mi355gp_sparse_kdiag")
+            return kd
+        w = f64(np.asarray(w)).ravel()
+        assert w.size == self.N, "w must have one entry per row of X"
+        sums, ddiag = np.zeros(2), np.zeros(ntheta)
+        check(lib().mi355gp_sparse_kdiag(self._h, len(specs), arr, _opt(w), _opt(kd), _opt(sums), _opt(ddiag)), "mi355gp_sparse_kdiag")
+        return kd, sums, ddiag
 
     # ---- EPDTC (epdtc.hip, include/mi355gp_epdtc.h) -------------------------------------------------------------------------
     def epdtc_begin(self, specs, Z, jitter=0.0):

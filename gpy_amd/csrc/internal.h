@@ -318,11 +318,39 @@ int launch_kbuild_cols(hipStream_t st, KernParams kp, const double* Xt1, long ld
 int launch_grad_cols(hipStream_t st, KernParams kp, const double* Xt1, long ld1, long n, const double* Xt2, long ld2,
                      long m, long mcols, const double* G, long ldg, RankTerm rk, double* partials, double* colpart,
                      int* nblocks_out);
+// sparse pass 2 for a Linear part (kind 9, D <= 16): the column partials of HX[j][q] = sum_i g[i][j] x~[i][q] ([split][mcols][D],
+// no ones column) in one pass over the weights, formed on the fly as launch_grad_cols forms them; the theta record follows on
+// the host from HX and the scaled Z.  Returns the number of row splits, 0 = not applicable (D > 16)
+int launch_grad_cols_lin(hipStream_t st, const double* Xt1, long ld1, long n, int D, long m, long mcols, const double* G, long ldg,
+                         RankTerm rk, double* colpart);
+// out[i][j] = the weight the RankTerm describes (rows x m; 0 in the columns [m, ld)), for the passes that need it in memory
+void launch_form_rank_weights(hipStream_t st, const double* G, long ld, long rows, long m, RankTerm rk, double* out);
 // part[split][cols][nv] = sum over a row range of M[i][j] * V(i, c); V(i, c) = V[i*sr + c*sc] plus an optional
 // all-ones column; returns the number of row splits (sum them with launch_sum_splits)
 int launch_colreduce_multi(hipStream_t st, const double* M, long ld, long rows, long cols, const double* V, long sr,
                            long sc, int nvt, int ones, double* part);
 void launch_sum_splits(hipStream_t st, const double* src, long cnt, int nsplit, int accumulate, double* dst);
+
+// ---- kern_diag.hip : the per-point diagonal of an expression over rows of a row-major point set ---------------------
+// kd_n = sum over terms of the product of the factors' diagonals at x_n: the variance for a constant-diagonal kind,
+// sum_q coef[p][q] x_nq^2 for a part whose diagonal depends on the point (Linear: coef = variance_q, 0 off its dimensions).
+#define KDIAG_MAX_PARTS 16
+struct DiagDesc {
+    int nparts, nterms;
+    int tstart[KDIAG_MAX_PARTS + 1];   // term t: the parts tpart[tstart[t] .. tstart[t + 1])
+    int tpart[KDIAG_MAX_PARTS];
+    int tix[KDIAG_MAX_PARTS];          // the term of part p
+    int by_point[KDIAG_MAX_PARTS];     // 1: the diagonal of part p is sum_q coef[p][q] x_q^2
+    double var[KDIAG_MAX_PARTS];       // else: its variance
+};
+// doubles of one record of weighted sums: [0] sum w kd, [1] sum w^2 kd, [2 + p D + q] sum w (other factors of p) x_q^2 for a
+// by-point part p, [2 + p D] sum w (other factors of p) for a constant-diagonal one
+__host__ __device__ static inline int kdiag_slots(int nparts, int D) { return 2 + nparts * D; }
+static inline long kdiag_blocks(long n) { return (n + 255) / 256; }
+// kd_out (n, optional) and, with weights w (n), the record sums_out (kdiag_slots doubles) -- block partials (partials:
+// kdiag_blocks(n) records) combined in block order, no atomics: two calls give the same bytes.  coef: nparts x D.
+void launch_kdiag(hipStream_t st, const DiagDesc& ds, const double* X, long n, int D, const double* coef, const double* w,
+                  double* kd_out, double* partials, double* sums_out);
 
 // ---- reduce.hip : reductions, triangular solves and fetch helpers that stage no input slabs -----------------------
 // y = X r (lower-triangular X, n x n within npad), then a = X^T y   (Dy right-hand sides, row-major n x Dy)

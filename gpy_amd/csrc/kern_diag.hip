@@ -1,0 +1,88 @@
+// kern_diag.hip -- the per-point diagonal of a kernel expression (add.py:74-79, prod.py:67-71, linear.py:84-85,100-105) over the
+// rows of a resident row-major point set: kd_n = sum over terms of the product of the factors' diagonals at x_n, and for a
+// weight vector w the sums that update_gradients_diag and the sparse bounds need.  One thread per row; a block's sums are
+// reduced by a fixed tree, the blocks' records are added in block order by one more launch (no floating-point atomics).
+#include "../../include/mi355gp.h"
+#include "internal.h"
+
+// fixed-tree sum of one value per thread; the result is valid in thread 0
+__device__ __forceinline__ double kdiag_block_sum(double* red, int t, double v) {
+    __syncthreads();
+    red[t] = v;
+    __syncthreads();
+    for (int k = 128; k > 0; k >>= 1) {
+        if (t < k) red[t] += red[t + k];
+        __syncthreads();
+    }
+    return red[0];
+}
+
+__global__ __launch_bounds__(256) void k_kdiag_rows(DiagDesc ds, const double* __restrict__ X, long n, int D,
+                                                    const double* __restrict__ coef, const double* __restrict__ w,
+                                                    double* __restrict__ kd_out, double* __restrict__ partials) {
+    __shared__ double sd[KDIAG_MAX_PARTS][256];        // the parts' diagonals at this thread's row
+    __shared__ double red[256];
+    const int t = threadIdx.x;
+    const long i = (long)blockIdx.x * 256 + t;
+    const bool valid = i < n;
+    const double* x = X + (valid ? i : 0) * D;
+    for (int p = 0; p < ds.nparts; ++p) {
+        double d = ds.var[p];
+        if (ds.by_point[p]) {
+            d = 0.0;
+            for (int q = 0; q < D; ++q) d = fma(coef[p * D + q], x[q] * x[q], d);
+        }
+        sd[p][t] = d;
+    }
+    double kd = 0.0;
+    for (int tm = 0; tm < ds.nterms; ++tm) {
+        double v = 1.0;
+        for (int k = ds.tstart[tm]; k < ds.tstart[tm + 1]; ++k) v *= sd[ds.tpart[k]][t];
+        kd += v;
+    }
+    if (kd_out && valid) kd_out[i] = kd;
+    if (!w) return;                                      // (the same for every thread)
+    const double wv = valid ? w[i] : 0.0;
+    double* rec = partials + (long)blockIdx.x * kdiag_slots(ds.nparts, D);
+    double s = kdiag_block_sum(red, t, wv * kd);
+    if (t == 0) rec[0] = s;
+    s = kdiag_block_sum(red, t, wv * wv * kd);
+    if (t == 0) rec[1] = s;
+    for (int p = 0; p < ds.nparts; ++p) {
+        double o = wv;                                   // the weight times the other factors of p's term
+        const int tm = ds.tix[p];
+        for (int k = ds.tstart[tm]; k < ds.tstart[tm + 1]; ++k)
+            if (ds.tpart[k] != p) o *= sd[ds.tpart[k]][t];
+        double* out = rec + 2 + p * D;
+        if (!ds.by_point[p]) {
+            s = kdiag_block_sum(red, t, o);
+            if (t == 0) {
+                out[0] = s;
+                for (int q = 1; q < D; ++q) out[q] = 0.0;
+            }
+        } else {
+            for (int q = 0; q < D; ++q) {
+                s = kdiag_block_sum(red, t, o * (x[q] * x[q]));
+                if (t == 0) out[q] = s;
+            }
+        }
+    }
+}
+
+// out[s] = sum over the blocks, in block order, of partials[b][s]
+__global__ void k_kdiag_combine(const double* __restrict__ partials, long nblk, int S, double* __restrict__ out) {
+    const int s = blockIdx.x * blockDim.x + threadIdx.x;
+    if (s >= S) return;
+    double a = 0.0;
+    for (long b = 0; b < nblk; ++b) a += partials[b * S + s];
+    out[s] = a;
+}
+
+void launch_kdiag(hipStream_t st, const DiagDesc& ds, const double* X, long n, int D, const double* coef, const double* w,
+                  double* kd_out, double* partials, double* sums_out) {
+    const long nblk = kdiag_blocks(n);
+    hipLaunchKernelGGL(k_kdiag_rows, dim3((unsigned)nblk), dim3(256), 0, st, ds, X, n, D, coef, w, kd_out, partials);
+    if (!w) return;
+    const int S = kdiag_slots(ds.nparts, D);
+    hipLaunchKernelGGL(k_kdiag_combine, dim3((unsigned)((S + 255) / 256)), dim3(256), 0, st, partials, nblk, S, sums_out);
+}

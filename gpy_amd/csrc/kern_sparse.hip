@@ -1,6 +1,6 @@
 // kern_sparse.hip -- the streaming sparse path's covariance passes: K(X_chunk, Z) with the column reduction fused in
-// (k_kbuild_cols), the gradient pass with the column reductions fused in (k_grad_cols, k_grad_cols_mfma), and the column
-// reductions over a resident chunk with their fixed-order combine (k_colreduce_multi, k_sum_splits).
+// (k_kbuild_cols), the gradient pass with the column reductions fused in (k_grad_cols, k_grad_cols_mfma; k_grad_cols_lin for a
+// Linear part), and the column reductions over a resident chunk with their fixed-order combine (k_colreduce_multi, k_sum_splits).
 #include <cstdint>
 #include <cstdlib>
 
@@ -449,6 +449,128 @@ int launch_grad_cols(hipStream_t st, KernParams kp, const double* Xt1, long ld1,
 #endif
     *nblocks_out = nb;
     return nsplit;
+}
+
+// The pass for a Linear part (kind 9, linear.py:87-114; D <= 16).  K = sum_q x~_iq z~_jq with x~ = sqrt(variance_q) x, so the whole
+// row-side gradient is the skinny product  HX[j][q] = sum_i g[i][j] x~[i][q]  of the weights themselves: dL/dvariance_q =
+// sum_j z~_jq HX[j][q] / variance_q and dL/dZ_jq = sqrt(variance_q) HX[j][q], both finished on the host from HX and the scaled Z.
+// No covariance is evaluated, the Z slab is not staged and there is no ones column.  Block = (column tile, row split), the
+// weights formed on the fly and the 64 x 16 x 64 product per tile on v_mfma_f64_16x16x4 exactly as in k_grad_cols_mfma (the
+// weight formation is that kernel's, repeated here so that its code stays as measured).
+__global__ __launch_bounds__(256, 2) void k_grad_cols_lin(const double* __restrict__ Xt1, long ld1, long n, int D, long m,
+                                                          const double* __restrict__ G, long ldg, RankTerm rk, int ntc, int ntr,
+                                                          int tiles_per_split, double* __restrict__ colpart, long mcols) {
+    __shared__ __attribute__((aligned(16))) double sit[KT * 18];   // x~ slab row-major [i][c], stride 18: the B operand
+    __shared__ __attribute__((aligned(16))) double sh[KT * GC_HS];  // the tile of weights: the A operand
+    const int t = threadIdx.x, tx = t & 15, ty = t >> 4, lane = t & 63, w = t >> 6;
+    const int tj = blockIdx.x % ntc, split = blockIdx.x / ntc;
+    const long j0 = (long)tj * KT;
+    d4 hx = {0.0, 0.0, 0.0, 0.0};                        // HX[j = 16 w + (lane >> 4) + 4 r][c = lane & 15]
+    for (int idx = t; idx < KT * 18; idx += 256) sit[idx] = 0.0;      // columns c >= D stay zero
+    const bool vec4 = (j0 + tx * 4 + 3 < m) && (ldg % 4 == 0) && ((reinterpret_cast<unsigned long long>(G) & 31ull) == 0);
+    const bool rkfast = rk.Y != nullptr && rk.Dy <= GC_DY;
+    double vcol[4][GC_DY];
+#pragma unroll
+    for (int b = 0; b < 4; ++b)
+#pragma unroll
+        for (int d = 0; d < GC_DY; ++d)
+            vcol[b][d] = (rkfast && d < rk.Dy && j0 + tx * 4 + b < m) ? rk.V[(j0 + tx * 4 + b) * rk.Dy + d] : 0.0;
+    const int ti_end = ((split + 1) * tiles_per_split < ntr) ? (split + 1) * tiles_per_split : ntr;
+    for (int ti = split * tiles_per_split; ti < ti_end; ++ti) {
+        const long i0 = (long)ti * KT;
+        __syncthreads();                                 // the previous tile's MFMA reads of sh / sit are done
+        for (int idx = t; idx < D * KT; idx += 256) {
+            const int q = idx >> 6, ii = idx & 63;
+            sit[ii * 18 + q] = Xt1[(long)q * ld1 + i0 + ii];
+        }
+#pragma unroll
+        for (int a = 0; a < 4; ++a) {
+            const long i = i0 + ty * 4 + a;
+            d4 gv = {0.0, 0.0, 0.0, 0.0};
+            double yrow[GC_DY], rs = 1.0;
+            if (i < n) {
+                if (vec4) gv = *reinterpret_cast<const d4*>(G + i * ldg + j0 + tx * 4);
+                else
+#pragma unroll
+                    for (int b = 0; b < 4; ++b)
+                        if (j0 + tx * 4 + b < m) gv[b] = G[i * ldg + j0 + tx * 4 + b];
+                if (rk.Y && rkfast) {
+#pragma unroll
+                    for (int d = 0; d < GC_DY; ++d) yrow[d] = (d < rk.Dy) ? rk.Y[i * rk.Dy + d] : 0.0;
+                    if (rk.rowscale) rs = rk.rowscale[i];
+                }
+            }
+            d4 go = {0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+            for (int b = 0; b < 4; ++b) {
+                const long j = j0 + tx * 4 + b;
+                double g = 0.0;
+                if (i < n && j < m) {
+                    g = gv[b];
+                    if (rk.Y) {
+                        double yv = 0.0;
+                        if (rkfast) {
+#pragma unroll
+                            for (int d = 0; d < GC_DY; ++d)
+                                if (d < rk.Dy) yv = fma(yrow[d], vcol[b][d], yv);
+                        } else {
+                            for (int d = 0; d < rk.Dy; ++d) yv = fma(rk.Y[i * rk.Dy + d], rk.V[j * rk.Dy + d], yv);
+                        }
+                        g = fma(rk.gscale, g, rk.beta * yv);
+                        if (rk.rowscale) g *= rkfast ? rs : rk.rowscale[i];
+                    }
+                }
+                go[b] = g;
+            }
+            *reinterpret_cast<d4*>(sh + (ty * 4 + a) * GC_HS + tx * 4) = go;
+        }
+        __syncthreads();                                 // the tile of weights and the x~ slab are complete
+        // HX[16 w .., :] += g[:, 16 w ..]^T x~ : k = 4 s + (lane >> 4) over the 64 rows of the tile
+        const double* ha = sh + (lane >> 4) * GC_HS + 16 * w + (lane & 15);
+        const double* xb = sit + (lane >> 4) * 18 + (lane & 15);
+#pragma unroll
+        for (int s4 = 0; s4 < 16; ++s4) hx = mfma_f64(ha[4 * s4 * GC_HS], xb[4 * s4 * 18], hx);
+    }
+    double* cp = colpart + (long)split * mcols * D;      // every (j, c) is one accumulator register
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        const long j = j0 + 16 * w + (lane >> 4) + 4 * r;
+        const int c = lane & 15;
+        if (c < D && j < mcols) cp[j * D + c] = (j < m) ? hx[r] : 0.0;
+    }
+}
+
+int launch_grad_cols_lin(hipStream_t st, const double* Xt1, long ld1, long n, int D, long m, long mcols, const double* G, long ldg,
+                         RankTerm rk, double* colpart) {
+    if (D > 16) return 0;
+    const int ntr = (int)((n + KT - 1) / KT), ntc = (int)((mcols + KT - 1) / KT);
+    int nsplit = 2048 / ntc;                             // the splits of launch_grad_cols
+    if (nsplit > 64) nsplit = 64;
+    if (nsplit > ntr) nsplit = ntr;
+    if (nsplit < 1) nsplit = 1;
+    const int tps = (ntr + nsplit - 1) / nsplit;
+    nsplit = (ntr + tps - 1) / tps;
+    hipLaunchKernelGGL(k_grad_cols_lin, dim3((unsigned)(ntc * nsplit)), dim3(256), 0, st, Xt1, ld1, n, D, m, G, ldg, rk, ntc, ntr, tps,
+                       colpart, mcols);
+    return nsplit;
+}
+
+// out[i][j] = rowscale_i (gscale G[i][j] + beta sum_d Y[i][d] V[j][d]) for j < m, 0 for m <= j < ld: the weights of a RankTerm in
+// memory, in the arithmetic of the fused passes
+__global__ void k_form_rank_weights(const double* __restrict__ G, long ld, long rows, long m, RankTerm rk, double* __restrict__ out) {
+    const long j = (long)blockIdx.y * blockDim.x + threadIdx.x, i = blockIdx.x;
+    if (j >= ld || i >= rows) return;
+    double g = 0.0;
+    if (j < m) {
+        double yv = 0.0;
+        for (int d = 0; d < rk.Dy; ++d) yv = fma(rk.Y[i * rk.Dy + d], rk.V[j * rk.Dy + d], yv);
+        g = fma(rk.gscale, G[i * ld + j], rk.beta * yv);
+        if (rk.rowscale) g *= rk.rowscale[i];
+    }
+    out[i * ld + j] = g;
+}
+void launch_form_rank_weights(hipStream_t st, const double* G, long ld, long rows, long m, RankTerm rk, double* out) {
+    hipLaunchKernelGGL(k_form_rank_weights, dim3((unsigned)rows, (unsigned)((ld + 255) / 256)), dim3(256), 0, st, G, ld, rows, m, rk, out);
 }
 
 // out[j][c] = sum_i M[i][j] * V(i, c), c < nv <= 33.  V(i, c) = V[i*sr + c*sc] for c < nvt, 1 for c == nvt (the column

@@ -63,11 +63,12 @@ __global__ void k_pep_sym_splits(const double* __restrict__ part, long mp, int n
 
 // Pass 1, one wave per chunk row, W read once (pep.py:44-46,49):
 //   q = |w_n|^2, sigma* = s2 + alpha (Knn - q), beta* = 1 / sigma*;  Out[n][:] = sqrt(beta*) w_n;  V[n] = beta* y_n
+// Knn = knn for every row, or kd[n] where a per-point diagonal is given.
 // A sigma* that is not positive leaves beta* = 0 behind (the row drops out of every sum) and sigma* itself for the host's
 // check, which ends the call: nothing downstream sees a NaN.  Rows [rows, rows_pad) of Out are zeroed for the Gram.
 __global__ __launch_bounds__(256) void k_pep_rows1(const double* __restrict__ W, long ld, long rows, long rows_pad,
                                                    const double* __restrict__ y, double s2, double alpha, double knn,
-                                                   double* __restrict__ sigma, double* __restrict__ logb,
+                                                   const double* __restrict__ kd, double* __restrict__ sigma, double* __restrict__ logb,
                                                    double* __restrict__ beta, double* __restrict__ V,
                                                    double* __restrict__ Out) {
     const int lane = threadIdx.x & 63;
@@ -82,7 +83,7 @@ __global__ __launch_bounds__(256) void k_pep_rows1(const double* __restrict__ W,
     double q = 0.0;
     for (long j = lane; j < ld; j += 64) q = fma(w[j], w[j], q);
     for (int off = 32; off > 0; off >>= 1) q += __shfl_xor(q, off);
-    const double sg = s2 + alpha * (knn - q);
+    const double sg = s2 + alpha * ((kd ? kd[i] : knn) - q);
     const bool ok = sg > 0.0;
     const double b = ok ? 1.0 / sg : 0.0, sb = sqrt(b);
     for (long j = lane; j < ld; j += 64) o[j] = sb * w[j];
@@ -252,7 +253,10 @@ int mi355gp_pep_inference(mi355gp_sparse* s, int nparts, const mi355gp_part* par
     s->mfma_prof.on = false;
     s->beta_scalar = 0.0;
     if (int rc = sparse_start(s, Z, nullptr, 0)) return rc;
-    const double knn = expression_kdiag(s->parts, s->terms);                         // Knn = kern.Kdiag(X), a constant (pep.py:38)
+    // Knn = kern.Kdiag(X) (pep.py:38): a constant, or by point in s->dKd
+    const double knn = s->diag_pt ? 0.0 : expression_kdiag(s->parts, s->terms);
+    if (s->diag_pt)
+        if (int rc = sparse_kdiag_data(s, nullptr, nullptr)) return rc;
     double* sigma = pp->rowStat;
     double* logb = pp->rowStat + n;
     // ---- pass 1 ------------------------------------------------------------------------------------------------------------------
@@ -268,7 +272,7 @@ int mi355gp_pep_inference(mi355gp_sparse* s, int nparts, const mi355gp_part* par
         if (int rc2 = pep_chunk_W(s, r0, rc)) return rc2;
         // LiUT = Lm^-1 Kuf (pep.py:42), sigma_star, beta_star (:44-45), the rows scaled for A (:49-50)
         hipLaunchKernelGGL(k_pep_rows1, dim3((unsigned)((rz + 3) / 4)), dim3(256), 0, st, s->T, mp, rc, rz, s->dY + r0, noise_variance,
-                           alpha, knn, sigma + r0, logb + r0, s->dBeta + r0, s->dV + r0, pp->C1);
+                           alpha, knn, s->diag_pt ? s->dKd + r0 : nullptr, sigma + r0, logb + r0, s->dBeta + r0, s->dV + r0, pp->C1);
         launch_gram_splitk(st, pp->C1, mp, round_up(rc, 16L * s->splitk), mp, s->splitk, nch > 0, s->psi2part);
         // URiy = Kuf (beta* y) in the whitened basis (pep.py:53)
         const int ns = launch_colreduce_multi(st, s->T, mp, rc, mp, s->dV + r0, 1, 1, 1, 0, s->colPart);
@@ -322,6 +326,10 @@ int mi355gp_pep_inference(mi355gp_sparse* s, int nparts, const mi355gp_part* par
     }
     hipLaunchKernelGGL(k_pep_dLdKmm, grid2d(mp, mp), dim3(256), 0, st, s->Winv, s->vvec, pp->S, alpha, mp, m, s->dLdKmm);
     sparse_kmm_gradients(s);
+    // a per-point diagonal: update_gradients_diag's sums against w_n = dL_dR_n (times alpha on the host, pep.py:85)
+    std::vector<double> dsums;
+    if (s->diag_pt)
+        if (int rc = sparse_kdiag(s, s->dX, n, s->dRowR, nullptr, &dsums)) return rc;
     HIP_CHECK(hipEventRecord(s->ev[3], st));
     // ---- small results to the host -----------------------------------------------------------------------------------------------
     KernGrads kg;
@@ -352,6 +360,7 @@ int mi355gp_pep_inference(mi355gp_sparse* s, int nparts, const mi355gp_part* par
     if (dLdR_out)
         for (long i = 0; i < n; ++i) dLdR_out[i] = hdR[(size_t)i];
     // update_gradients_diag(dL_dKdiag = alpha dL_dR) (pep.py:85, sparse_gp.py:110)
+    if (s->diag_pt) sparse_diag_dtheta(s, dsums, alpha, &kg.ddiag);
     sparse_assemble_gradients(s, kg, alpha * sum_dR, dtheta_out, dZ_out);
     s->have_result = s->winv_ok = true;
     s->uncertain_result = false;

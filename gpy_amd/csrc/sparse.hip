@@ -18,6 +18,7 @@
 
 #include "../../include/mi355gp.h"
 #include "../../include/mi355gp_debug.h"
+#include "../../include/mi355gp_sparse_diag.h"
 #include "internal.h"
 #include "parts.h"
 #include "psi.h"
@@ -114,9 +115,11 @@ __global__ void k_form_dLdKnm(double* __restrict__ G, long ld, long rows, long r
     }
     G[i * ld + j] = g;
 }
-// out[j] = c0 - sum_i A[i][j] * B[i][j]   (64 columns per block, 4 row groups, fixed-order combine)
+// out[j] = c0 - sum_i A[i][j] * B[i][j], c0 = cv[j] where a vector is given   (64 columns per block, 4 row groups, fixed-order
+// combine)
 __global__ __launch_bounds__(256) void k_col_dot(const double* __restrict__ A, const double* __restrict__ B, long ld,
-                                                 long rows, long cols, double c0, double* __restrict__ out) {
+                                                 long rows, long cols, double c0, const double* __restrict__ cv,
+                                                 double* __restrict__ out) {
     __shared__ double red[4][64];
     const int tx = threadIdx.x & 63, g = threadIdx.x >> 6;
     const long j = (long)blockIdx.x * 64 + tx;
@@ -125,7 +128,7 @@ __global__ __launch_bounds__(256) void k_col_dot(const double* __restrict__ A, c
         for (long i = g; i < rows; i += 4) acc = fma(A[i * ld + j], B[i * ld + j], acc);
     red[g][tx] = acc;
     __syncthreads();
-    if (g == 0 && j < cols) out[j] = c0 - ((red[0][tx] + red[1][tx]) + (red[2][tx] + red[3][tx]));
+    if (g == 0 && j < cols) out[j] = (cv ? cv[j] : c0) - ((red[0][tx] + red[1][tx]) + (red[2][tx] + red[3][tx]));
 }
 __global__ void k_vec_axpy(double* __restrict__ dst, const double* __restrict__ src, long cnt, double a) {
     const long l = (long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -269,9 +272,98 @@ int alloc_m(mi355gp_sparse* s, long M) {
     return 0;
 }
 
+// Describes an expression to the kernels of kern_diag.hip: the terms, the constant diagonals, and per by-point part its D
+// coefficients (Linear: variance_q itself, not the square of the input scaling; MLP / Poly / Coregionalize are not sparse-path
+// kinds).  Part: PartSpec or anything derived from it, grouped by group_terms.
+template <class Part>
+static void describe_diag(const std::vector<Part>& parts, const Terms& terms, int D, DiagDesc* ds, std::vector<double>* coef) {
+    const int np_ = (int)parts.size();
+    ds->nparts = np_;
+    ds->nterms = (int)terms.size();
+    int k = 0;
+    for (size_t t = 0; t < terms.size(); ++t) {
+        ds->tstart[t] = k;
+        for (int f : terms[t]) ds->tpart[k++] = f;
+    }
+    ds->tstart[terms.size()] = k;
+    coef->assign((size_t)np_ * D, 0.0);
+    for (int i = 0; i < np_; ++i) {
+        const Part& p = parts[(size_t)i];
+        ds->tix[i] = p.tix;
+        ds->by_point[i] = p.diag_by_point() ? 1 : 0;
+        ds->var[i] = p.kp.variance;
+        if (p.linear())
+            for (size_t a = 0; a < p.dims.size(); ++a) (*coef)[(size_t)i * D + p.dims[a]] = p.theta[p.kp.ard ? a : 0];
+    }
+}
+// update_gradients_diag of every part in theta order from a record of weighted sums, times `scale`
+template <class Part>
+static void diag_dtheta(const std::vector<Part>& parts, int D, const std::vector<double>& sums, double scale, std::vector<double>* out) {
+    out->clear();
+    for (size_t i = 0; i < parts.size(); ++i) {
+        const Part& p = parts[i];
+        const double* r = sums.data() + 2 + i * (size_t)D;
+        const size_t o = out->size();
+        out->resize(o + p.theta.size(), 0.0);
+        double* g = out->data() + o;
+        if (!p.diag_by_point()) g[0] = scale * r[0];                         // the variance slot (stationary.py:175-184, static.py)
+        else if (p.kp.ard)                                                   // linear.py:100-105
+            for (size_t a = 0; a < p.dims.size(); ++a) g[a] = scale * r[p.dims[a]];
+        else
+            for (size_t a = 0; a < p.dims.size(); ++a) g[0] += scale * r[p.dims[a]];
+    }
+}
+
+// Decides whether Kdiag of the call's expression is a vector (a diag_by_point() part) and, if so, leaves its description in
+// s->diag and the coefficients on the device
+static int prepare_diag(mi355gp_sparse* s) {
+    s->diag_pt = false;
+    for (const SPart& p : s->parts) s->diag_pt = s->diag_pt || p.diag_by_point();
+    if (!s->diag_pt) return 0;
+    std::vector<double> coef;
+    describe_diag(s->parts, s->terms, s->D, &s->diag, &coef);
+    HIP_CHECK(s->diagCoef.need(coef.size()));
+    // (pageable memory: the copy has left `coef` when the call returns)
+    HIP_CHECK(hipMemcpyAsync(s->diagCoef, coef.data(), sizeof(double) * coef.size(), hipMemcpyHostToDevice, s->st));
+    return 0;
+}
+
+// the kernels of kern_diag.hip for a described expression (coef: device); the record of weighted sums on its way to host_sums
+static int run_kdiag(mi355gp_sparse* s, const DiagDesc& ds, const double* coef, const double* X, long rows, const double* w,
+                     double* kd_out, std::vector<double>* host_sums) {
+    const int S = kdiag_slots(ds.nparts, s->D);
+    if (w) {
+        HIP_CHECK(s->diagPart.need((size_t)kdiag_blocks(rows) * S));
+        HIP_CHECK(s->diagSums.need((size_t)S));
+    }
+    launch_kdiag(s->st, ds, X, rows, s->D, coef, w, kd_out, s->diagPart, s->diagSums);
+    if (w && host_sums) {
+        host_sums->assign((size_t)S, 0.0);
+        HIP_CHECK(hipMemcpyAsync(host_sums->data(), s->diagSums, sizeof(double) * S, hipMemcpyDeviceToHost, s->st));
+    }
+    return 0;
+}
+int sparse_kdiag(mi355gp_sparse* s, const double* X, long rows, const double* w, double* kd_out, std::vector<double>* host_sums) {
+    return run_kdiag(s, s->diag, s->diagCoef, X, rows, w, kd_out, host_sums);
+}
+int sparse_kdiag_data(mi355gp_sparse* s, const double* w, std::vector<double>* host_sums) {
+    HIP_CHECK(s->dKd.need((size_t)s->n));
+    return sparse_kdiag(s, s->dX, s->n, w, s->dKd, host_sums);
+}
+void sparse_diag_dtheta(const mi355gp_sparse* s, const std::vector<double>& sums, double scale, std::vector<double>* out) {
+    diag_dtheta(s->parts, s->D, sums, scale, out);
+}
+
 // (re)builds the part list of a call; the device buffers of a part are kept while the number of parts is unchanged
 int prepare_sparse_parts(mi355gp_sparse* s, int nparts, const mi355gp_part* parts) {
     ARG_CHECK(nparts >= 1 && nparts <= 16 && parts, "between 1 and 16 kernel parts");
+    // Linear is taken where the context was told so (mi355gp_sparse_set_linear; off in a new context: a caller that has not
+    // asked keeps the refusal by name)
+    const KindSet accepted = KS_STATIONARY | KS_STATIC | (s->take_linear ? KS_LINEAR : 0u);
+    for (int i = 0; i < nparts; ++i)                             // before any device work: the global sums of a per-point
+        if (kind_in(parts[i].kind, accepted) && parts[i].kind == MI355GP_LINEAR && sharded(s))   // diagonal would need another all-reduce
+            PART_FAIL("sparse path: a Linear (kind 9) part is not supported by a row-sharded context (its Kdiag depends on the "
+                      "point: the sums over rows would need a collective of their own)");
     const long mp = s->mp, D = s->D;
     const int groups = (int)((D + 31) / 32);
     if ((int)s->parts.size() != nparts) {
@@ -291,7 +383,7 @@ int prepare_sparse_parts(mi355gp_sparse* s, int nparts, const mi355gp_part* part
     }
     for (int i = 0; i < nparts; ++i) {
         SPart& p = s->parts[(size_t)i];
-        if (int rc = parse_part(parts[i], (int)D, KS_STATIONARY | KS_STATIC, "sparse path", &p)) return rc;
+        if (int rc = parse_part(parts[i], (int)D, accepted, "sparse path", &p)) return rc;
         if (int rc = p.upload(s->st)) return rc;
     }
     s->terms = group_terms(s->parts);
@@ -299,7 +391,7 @@ int prepare_sparse_parts(mi355gp_sparse* s, int nparts, const mi355gp_part* part
         if (t.size() > 1)
             for (int f : t)
                 ARG_CHECK(s->parts[(size_t)f].kp.kind != MI355GP_WHITE, "a White factor inside a product is not supported by the sparse path");
-    return 0;
+    return prepare_diag(s);
 }
 
 // product of the OTHER factors' variances of part p's summand (= dKdiag/dvariance_p; 1 for a plain summand)
@@ -672,6 +764,9 @@ void sparse_kmm_gradients(mi355gp_sparse* s) {
         if (p.stationary()) {
             const int ns = launch_colreduce_multi(st, s->T1, mp, m, mp, p.XtZ, 1, mp, D, 1, s->colPart);
             launch_sum_splits(st, s->colPart, mp * (D + 1), ns, 0, p.HZ);
+        } else if (p.linear()) {                         // HZ = G^T z~ of the weights themselves (linear.py:108-114)
+            const int ns = launch_colreduce_multi(st, prod ? s->T1 : s->dLdKmm, mp, m, mp, p.XtZ, 1, mp, D, 0, s->colPart);
+            launch_sum_splits(st, s->colPart, mp * D, ns, 0, p.HZ);
         }
     }
 }
@@ -769,6 +864,23 @@ void sparse_rows_gradients(mi355gp_sparse* s, long rc, const double* W, double* 
             const SPart& pf = s->parts[(size_t)f];
             launch_kbuild_cross(st, pf.kp, pf.XtC, chunk, rc, pf.XtZ, mp, m, dst, mp, 0, 0, mul);
         });
+        if (p.linear()) {
+            // HX = g^T x~ is all there is (k_grad_cols_lin); the theta record follows on the host (sparse_assemble_gradients).
+            // A factor of a product, D > 16: the weights in memory (launch_grad returns without a launch for a kind past the
+            // stationary ones when a rank term is given), then the column reduction of the stationary fallback
+            if (prod) form_times();
+            else if (s->fuse_cols) ns = launch_grad_cols_lin(st, p.XtC, chunk, rc, D, m, mp, W, mp, rk, s->colPart);
+            if (ns == 0) {
+                const double* g = prod ? scratch : W;
+                if (!prod && rk.Y) {
+                    launch_form_rank_weights(st, W, mp, rc, m, rk, scratch);
+                    g = scratch;
+                }
+                ns = launch_colreduce_multi(st, g, mp, rc, mp, p.XtC, 1, chunk, D, 0, s->colPart);
+            }
+            launch_sum_splits(st, s->colPart, mp * D, ns, 1, p.HX);
+            continue;
+        }
         if (prod) {
             form_times();
             nbk = grad_generic_num_blocks(rc, m);
@@ -807,7 +919,7 @@ int sparse_fetch_gradients(mi355gp_sparse* s, bool with_nm, KernGrads* h) {
         SPart& p = s->parts[i];
         if (with_nm) HIP_CHECK(hipMemcpyAsync(h->gnm.data() + i * gsz, p.gradNM, sizeof(double) * gsz, hipMemcpyDeviceToHost, s->st));
         HIP_CHECK(hipMemcpyAsync(h->gmm.data() + i * gsz, p.gradMM, sizeof(double) * gsz, hipMemcpyDeviceToHost, s->st));
-        if (!p.stationary()) continue;
+        if (!p.stationary() && !p.linear()) continue;
         if (with_nm) HIP_CHECK(hipMemcpyAsync(h->HX.data() + i * hsz, p.HX, sizeof(double) * hsz, hipMemcpyDeviceToHost, s->st));
         HIP_CHECK(hipMemcpyAsync(h->HZ.data() + i * hsz, p.HZ, sizeof(double) * hsz, hipMemcpyDeviceToHost, s->st));
         HIP_CHECK(hipMemcpyAsync(h->Zs.data() + i * zsz, p.XtZ, sizeof(double) * zsz, hipMemcpyDeviceToHost, s->st));
@@ -831,8 +943,21 @@ void sparse_assemble_gradients(const mi355gp_sparse* s, const KernGrads& h, doub
             const double* a = h.gnm.data() + i * gsz;
             const double* b = h.gmm.data() + i * gsz;
             for (size_t k = 0; k < gsz; ++k) ab[k] = h.with_nm ? a[k] + b[k] : b[k];
-            const int k = part_dtheta(s->parts[i], ab.data(), nullptr, o);
-            o[0] = kdiag_coef * sparse_other_variances(s, i) + o[0];
+            const SPart& p = s->parts[i];
+            if (p.linear() && h.with_nm) {               // the Knm record: sum_j z~_jq HX[j][q] per dimension (k_grad_cols_lin)
+                const double* hx = h.HX.data() + i * hsz;
+                const double* zs = h.Zs.data() + i * (size_t)D * mp;
+                for (int q = 0; q < D; ++q) {
+                    if (p.inv_ls[(size_t)q] == 0.0) continue;
+                    double sq = 0.0;
+                    for (long j = 0; j < m; ++j) sq = fma(zs[(size_t)q * mp + j], hx[j * D + q], sq);
+                    ab[p.kp.ard ? (size_t)(q / 32) * GP_STRIDE + 2 + (q % 32) : 0] += sq;
+                }
+            }
+            const int k = part_dtheta(p, ab.data(), nullptr, o);
+            if (h.ddiag.empty()) o[0] = kdiag_coef * sparse_other_variances(s, i) + o[0];
+            else
+                for (int c = 0; c < k; ++c) o[c] += h.ddiag[(size_t)(o - dtheta_out) + c];
             o += k;
         }
     }
@@ -840,10 +965,19 @@ void sparse_assemble_gradients(const mi355gp_sparse* s, const KernGrads& h, doub
         for (long j = 0; j < m * D; ++j) dZ_out[j] = 0.0;
         for (size_t i = 0; i < np_; ++i) {
             const SPart& p = s->parts[i];
-            if (!p.stationary()) continue;
+            if (!p.stationary() && !p.linear()) continue;
             const double* hx = h.HX.data() + i * hsz;
             const double* hz = h.HZ.data() + i * hsz;
             const double* zs = h.Zs.data() + i * (size_t)D * mp;
+            if (p.linear()) {                            // sqrt(variance_q) (HX + 2 HZ) (linear.py:108-114; dL_dKmm is symmetric);
+                for (long j = 0; j < m; ++j)             // an inactive dimension has il = 0 and stays exactly zero
+                    for (int q = 0; q < D; ++q) {
+                        const double il = p.inv_ls[(size_t)q];
+                        if (il == 0.0) continue;
+                        dZ_out[j * D + q] += ((h.with_nm ? hx[j * D + q] : 0.0) + 2.0 * hz[j * D + q]) * il;
+                    }
+                continue;
+            }
             for (long j = 0; j < m; ++j)
                 for (int q = 0; q < D; ++q) {
                     const double il = p.inv_ls[(size_t)q];
@@ -866,8 +1000,12 @@ int sparse_newpoints(mi355gp_sparse* s, const double* Xnew, int64_t Mn, bool wan
     const long m = s->m, mp = s->mp, mnp = round_up(Mn, NB);
     q->Mn = Mn;
     q->mnp = mnp;
-    q->kdiag = expression_kdiag(s->parts, s->terms);
+    q->kdiag = s->diag_pt ? 0.0 : expression_kdiag(s->parts, s->terms);
     if (int rc = q->xs.load(st, Xnew, Mn, s->D)) return rc;
+    if (s->diag_pt) {                                             // Kdiag(X*) by point, from the raw rows just uploaded
+        HIP_CHECK(q->kdv.alloc(Mn));
+        if (int rc = sparse_kdiag(s, q->xs.raw, Mn, nullptr, q->kdv, nullptr)) return rc;
+    }
     HIP_CHECK(q->Kx.alloc(mp * mnp));
     HIP_CHECK(q->Tmp.alloc(mp * mnp));
     HIP_CHECK(q->Mu.alloc(Mn * ncol));
@@ -899,7 +1037,7 @@ int sparse_newpoints_var(mi355gp_sparse* s, NewPoints* q, const double* Winv, bo
     launch_gemm(st, 0, 1, mp, mnp, mp, Winv, mp, q->Kx, mnp, q->Tmp, mnp, 1.0, 0.0);                   // Winv Kx
     if (!full_cov) {
         hipLaunchKernelGGL(k_col_dot, dim3((unsigned)((Mn + 63) / 64)), dim3(256), 0, st, (const double*)q->Kx, (const double*)q->Tmp,
-                           mnp, m, Mn, q->kdiag, q->var);
+                           mnp, m, Mn, q->kdiag, (const double*)q->kdv, q->var);
         return 0;
     }
     if (keep_kss) HIP_CHECK(hipMemcpyAsync(q->var, q->Kss, sizeof(double) * mnp * mnp, hipMemcpyDeviceToDevice, st));
@@ -912,18 +1050,20 @@ int sparse_newpoints_var(mi355gp_sparse* s, NewPoints* q, const double* Winv, bo
 // out_scalars: [0] log marginal likelihood, [1] dL/d(noise variance) (0 for per-point noise), [2] trace(A), [3] data_fit,
 // [4] sum(log diag LB), [5] beta.  scal: the four sums of sparse_mm_block; kdiag: psi0_n, the same for every row; sums: {sum
 // beta_n, sum log beta_n, sum beta_n |R_n|^2} over ALL shards (read for per-point noise, beta == 0, only)
+// psi0 (NULL: Kdiag is the one number kdiag): {sum beta_n kd_n, sum beta_n^2 kd_n} of a per-point diagonal, which take the place
+// of sum(beta) kdiag and N beta^2 kdiag
 static void vardtc_scalars(const mi355gp_sparse* s, const double* scal, double kdiag, double beta, const double* sums,
-                           double* out_scalars) {
+                           double* out_scalars, const double* psi0 = nullptr) {
     const int Dy = s->Dy;
     const double trA = scal[0], sumAP = scal[1], logLB = scal[2], data_fit = scal[3];
     const double ng = (double)s->n_global, nd = ng * Dy;
     double lik_1, lik_2;
     if (beta == 0.0) {
         lik_1 = -0.5 * nd * log(2.0 * M_PI) + 0.5 * Dy * sums[1] - 0.5 * sums[2];
-        lik_2 = -0.5 * Dy * (sums[0] * kdiag - trA);
+        lik_2 = -0.5 * Dy * ((psi0 ? psi0[0] : sums[0] * kdiag) - trA);
     } else {
         lik_1 = -0.5 * nd * (log(2.0 * M_PI) - log(beta)) - 0.5 * beta * s->trYYT;
-        lik_2 = -0.5 * Dy * (beta * ng * kdiag - trA);
+        lik_2 = -0.5 * Dy * ((psi0 ? psi0[0] : beta * ng * kdiag) - trA);
     }
     const double lik_3 = -(double)Dy * logLB;
     for (int i = 0; i < MI355GP_NUM_OUT; ++i) out_scalars[i] = 0.0;
@@ -934,7 +1074,7 @@ static void vardtc_scalars(const mi355gp_sparse* s, const double* scal, double k
     out_scalars[5] = beta;
     if (beta != 0.0) {
         double dL_dR = -0.5 * nd * beta + 0.5 * s->trYYT * beta * beta;
-        dL_dR += 0.5 * Dy * (ng * kdiag * beta * beta - trA * beta);
+        dL_dR += 0.5 * Dy * ((psi0 ? psi0[1] : ng * kdiag * beta * beta) - trA * beta);
         dL_dR += beta * (0.5 * sumAP - data_fit);
         out_scalars[1] = dL_dR;
     }
@@ -1064,12 +1204,15 @@ static int vardtc_pass2(mi355gp_sparse* s, bool het, bool want_rows) {
 // t_n = sum_j T_nj Kfu_nj, q_n = |Lm^-1 k_n|^2, r_n = |LB^-1 Lm^-1 k_n|^2 and the identity Dy q_n = 2 t_n + Dy r_n + sum_d s_nd^2:
 //   dL_dR_nd = -b/2 + (b R_nd)^2/2 + Dy b^2 psi0/2 - b^2 t_n - (Dy - 1) b^2 r_n/2 - b^2 sum_d' s_nd'^2/2
 //              - b^2 s_nd R_nd + b^2 s_nd^2/2                       (Dy = 1: the r_n and s^2 terms cancel; rowR is then empty)
-static void vardtc_dnoise_rows(long n, int Dy, double kdiag, const double* hbeta, const double* Rh, const std::vector<double>& rowS,
-                               const std::vector<double>& rowT, const std::vector<double>& rowR, double* out) {
+// kdv (NULL: psi0 is kdiag for every row): psi0_n of a per-point diagonal
+static void vardtc_dnoise_rows(long n, int Dy, double kdiag, const double* kdv, const double* hbeta, const double* Rh,
+                               const std::vector<double>& rowS, const std::vector<double>& rowT, const std::vector<double>& rowR,
+                               double* out) {
     for (long i = 0; i < n; ++i) {
         const double b = hbeta[i], b2 = b * b;
         double ss = 0.0;
         for (int d = 0; d < Dy; ++d) ss += rowS[(size_t)i * Dy + d] * rowS[(size_t)i * Dy + d];
+        if (kdv) kdiag = kdv[i];
         const double common = -0.5 * b + 0.5 * Dy * b2 * kdiag - b2 * rowT[(size_t)i] - 0.5 * b2 * ss -
                               (rowR.empty() ? 0.0 : 0.5 * (Dy - 1) * b2 * rowR[(size_t)i]);
         for (int d = 0; d < Dy; ++d) {
@@ -1135,6 +1278,11 @@ int vardtc_evaluate(mi355gp_sparse* s, const double* Z, const std::vector<double
     s->mfma_prof.mask = 0x3u;
     s->mfma_prof.reset();
     if (int rc = sparse_start(s, Z, hbeta.data(), (long)hbeta.size())) return rc;
+    // a per-point diagonal: psi0_n = Kdiag(x_n) and its sums against w_n = beta_n -- sum beta kd, sum beta^2 kd and the
+    // update_gradients_diag sums (dL_dKdiag_n = -Dy beta_n / 2, sparse_gp.py:110)
+    std::vector<double> dsums, kdh;
+    if (s->diag_pt)
+        if (int rc = sparse_kdiag_data(s, s->dBeta, &dsums)) return rc;
     int inject = 0;                                            // fault injection for the tests: 1 / 2 hit Kmm's launch, 11 / 12 B's
     {
         const char* et = DIAG_ENV("SPARSE_PERSIST_TEST");
@@ -1164,6 +1312,10 @@ int vardtc_evaluate(mi355gp_sparse* s, const double* Z, const std::vector<double
                 rowR.resize((size_t)n);
                 HIP_CHECK(hipMemcpyAsync(rowR.data(), s->dRowR, sizeof(double) * n, hipMemcpyDeviceToHost, st));
             }
+            if (s->diag_pt) {
+                kdh.resize((size_t)n);
+                HIP_CHECK(hipMemcpyAsync(kdh.data(), s->dKd, sizeof(double) * n, hipMemcpyDeviceToHost, st));
+            }
         }
     }
     if (int rc = sparse_finish(s, 3, stage_ms)) return rc;      // (info > 0: Kmm or B not positive definite, the caller adds jitter)
@@ -1173,17 +1325,19 @@ int vardtc_evaluate(mi355gp_sparse* s, const double* Z, const std::vector<double
         HIP_CHECK(hipStreamSynchronize(st));
         HIP_CHECK(hipMemcpy(glob, s->scal + 4, sizeof(glob), hipMemcpyDeviceToHost));
     }
-    const double kdiag = expression_kdiag(s->parts, s->terms);                        // psi0_n = Kdiag of the expression
-    vardtc_scalars(s, scal, kdiag, beta, glob, out_scalars);
+    // psi0_n = Kdiag of the expression: one number, or by point (then the two sums of the record stand in for it)
+    const double kdiag = s->diag_pt ? 0.0 : expression_kdiag(s->parts, s->terms);
+    vardtc_scalars(s, scal, kdiag, beta, glob, out_scalars, s->diag_pt ? dsums.data() : nullptr);
     if (want_rows) {
         Rh.resize((size_t)n * Dy);
         HIP_CHECK(hipMemcpy(Rh.data(), s->dY, sizeof(double) * n * Dy, hipMemcpyDeviceToHost));
     }
-    if (het) vardtc_dnoise_rows(n, Dy, kdiag, hbeta.data(), Rh.data(), rowS, rowT, rowR, dnoise_rows_out);
+    if (het) vardtc_dnoise_rows(n, Dy, kdiag, s->diag_pt ? kdh.data() : nullptr, hbeta.data(), Rh.data(), rowS, rowT, rowR, dnoise_rows_out);
     if (dLdm_out)                                                // dL_dm = V - Kfu v (var_dtc.py:148)
         for (long i = 0; i < n; ++i)
             for (int d = 0; d < Dy; ++d) dLdm_out[i * Dy + d] = hbeta[het ? (size_t)i : (size_t)0] * Rh[(size_t)i * Dy + d] - rowS[(size_t)i * Dy + d];
     // update_gradients_diag(dL_dKdiag = -0.5 Dy beta_n) (sparse_gp.py:110)
+    if (s->diag_pt) sparse_diag_dtheta(s, dsums, -0.5 * Dy, &kg.ddiag);
     sparse_assemble_gradients(s, kg, -0.5 * Dy * glob[0], dtheta_out, dZ_out);
     s->have_result = true;
     s->uncertain_result = false;
@@ -1597,6 +1751,55 @@ int mi355gp_sparse_predict_uncertain(mi355gp_sparse* s, int nparts, const mi355g
     float ms = 0.0f;
     HIP_CHECK(hipEventElapsedTime(&ms, s->ev[4], s->ev[5]));   // the chunks' uploads, kernels and copies back
     s->predict_ms = ms;
+    return 0;
+}
+
+// Whether the inference and prediction entry points of this context take Linear (kind 9) parts; a new context does not
+int mi355gp_sparse_set_linear(mi355gp_sparse* s, int on) {
+    ARG_CHECK(s, "mi355gp_sparse_set_linear: NULL context");
+    s->take_linear = on != 0;
+    return 0;
+}
+
+// Kdiag of an expression at the context's rows and its weighted sums (include/mi355gp_sparse_diag.h): the kernels of
+// kern_diag.hip on their own, for any expression of the sparse path's kinds with Linear (one without a by-point part is
+// described to them all the same).  The expression is parsed into a list of its own: the context's part list, its description
+// and coefficients, and with them the last result and what fetch / predict / an SVGP backward call derive from it, stay as
+// they are.  Only scratch is shared (dKd, the weights, the block records).
+int mi355gp_sparse_kdiag(mi355gp_sparse* s, int nparts, const mi355gp_part* parts, const double* w, double* kd_out,
+                         double* sums_out, double* ddiag_out) {
+    ARG_CHECK(s && s->n > 0, "mi355gp_sparse_kdiag: set_data first");
+    ARG_CHECK(nparts >= 1 && nparts <= KDIAG_MAX_PARTS && parts, "mi355gp_sparse_kdiag: between 1 and 16 kernel parts");
+    ARG_CHECK(!sharded(s), "mi355gp_sparse_kdiag: a row-sharded context is not supported (the sums would need a collective)");
+    std::vector<PartSpec> ps((size_t)nparts);
+    for (int i = 0; i < nparts; ++i)
+        if (int rc = parse_part(parts[i], s->D, KS_STATIONARY | KS_STATIC | KS_LINEAR, "mi355gp_sparse_kdiag", &ps[(size_t)i])) return rc;
+    const Terms terms = group_terms(ps);
+    DiagDesc ds;
+    std::vector<double> coef, sums;
+    describe_diag(ps, terms, s->D, &ds, &coef);
+    HIP_CHECK(hipSetDevice(s->device));
+    EngineShared gate(s->device);
+    hipStream_t st = s->st;
+    const long n = s->n;
+    DevBuf dcoef;
+    HIP_CHECK(dcoef.alloc(coef.size()));
+    HIP_CHECK(hipMemcpyAsync(dcoef, coef.data(), sizeof(double) * coef.size(), hipMemcpyHostToDevice, st));
+    if (w) {
+        HIP_CHECK(s->diagW.need((size_t)n));
+        HIP_CHECK(hipMemcpyAsync(s->diagW, w, sizeof(double) * n, hipMemcpyHostToDevice, st));
+    }
+    HIP_CHECK(s->dKd.need((size_t)n));
+    if (int rc = run_kdiag(s, ds, dcoef, s->dX, n, w ? (const double*)s->diagW : nullptr, s->dKd, &sums)) return rc;
+    if (kd_out) HIP_CHECK(hipMemcpyAsync(kd_out, s->dKd, sizeof(double) * n, hipMemcpyDeviceToHost, st));
+    HIP_CHECK(hipStreamSynchronize(st));
+    HIP_CHECK(hipGetLastError());
+    if (w && sums_out) sums_out[0] = sums[0], sums_out[1] = sums[1];
+    if (w && ddiag_out) {
+        std::vector<double> g;
+        diag_dtheta(ps, s->D, sums, 1.0, &g);
+        for (size_t k = 0; k < g.size(); ++k) ddiag_out[k] = g[k];
+    }
     return 0;
 }
 

@@ -13,7 +13,23 @@ struct PepState;               // pep.hip
 struct EpdtcState;             // epdtc.hip
 
 struct SPart : DevicePart {
-    DevBuf XtZ, XtC, HX, HZ, gradNM, gradMM;
+    DevBuf XtZ, XtC, HX, HZ, gradNM, gradMM;   // (HX / HZ of a Linear part: mp x D, no ones column)
+};
+
+// a device array that grows when more is asked of it and keeps its size otherwise
+struct GrowBuf {
+    DevBuf b;
+    size_t cap = 0;
+    hipError_t need(size_t count) {
+        if (count <= cap) return hipSuccess;
+        DevBuf nb;
+        const hipError_t e = nb.alloc(count);
+        if (e != hipSuccess) return e;
+        b = std::move(nb);
+        cap = count;
+        return hipSuccess;
+    }
+    operator double*() const { return b.p; }
 };
 
 struct mi355gp_sparse {
@@ -70,7 +86,23 @@ struct mi355gp_sparse {
     double kmm_jitter = 1e-8;
     // EPDTC (epdtc.hip): Kmm, P = LLT^-1 and gamma between its begin / recompute / sweep calls, the buffers of a site block
     EpdtcState* epdtc = nullptr;
+    // The per-point diagonal: diag_pt is decided by every prepare_sparse_parts -- the expression of THIS call has
+    // a diag_by_point() part (Linear), Kdiag is a vector and nothing of an earlier call's is read; otherwise it is the one
+    // number expression_kdiag() and no code below looks at these members.
+    bool diag_pt = false;
+    bool take_linear = false;     // mi355gp_sparse_set_linear: the entry points take Linear parts (off: refused by name, as before)
+    DiagDesc diag;
+    GrowBuf diagCoef, dKd, diagW, diagPart, diagSums;   // nparts x D coefficients; Kdiag(X) (n); a family's weights (n); records
 };
+
+// ---- the per-point diagonal (sparse.hip) ---------------------------------------------------------------------------
+// Kdiag of `rows` row-major points (device) into kd_out (device, optional) and, with weights w (device), the record of
+// weighted sums (kdiag_slots doubles) on its way into host_sums (valid after the stream is synchronised)
+int sparse_kdiag(mi355gp_sparse* s, const double* X, long rows, const double* w, double* kd_out, std::vector<double>* host_sums);
+// Kdiag(X) of the context's own rows into s->dKd (and the weighted sums, as above)
+int sparse_kdiag_data(mi355gp_sparse* s, const double* w, std::vector<double>* host_sums);
+// update_gradients_diag of every part in theta order from a record of weighted sums, times `scale` (KernGrads::ddiag)
+void sparse_diag_dtheta(const mi355gp_sparse* s, const std::vector<double>& sums, double scale, std::vector<double>* out);
 
 // ---- sparse.hip ----------------------------------------------------------------------------------------------------
 // doubles of one part's theta record (one GP_STRIDE record per 32 dimensions) and of its H^T [X~ | 1] sums
@@ -79,10 +111,14 @@ inline size_t hsum_doubles(const mi355gp_sparse* s) { return (size_t)s->mp * (s-
 struct KernGrads {             // the parts' records and sums on the host (sparse_fetch_gradients)
     bool with_nm = true;
     std::vector<double> gnm, gmm, HX, HZ, Zs;
+    // per-point diagonal: update_gradients_diag of every part in theta order (sparse_diag_dtheta); empty: Kdiag is one number
+    // and sparse_assemble_gradients adds kdiag_coef to the variances
+    std::vector<double> ddiag;
 };
 struct NewPoints {             // K(Z, X*) and what a prediction derives from it (sparse_newpoints)
     PointSet xs;
     DevBuf Kx, Tmp, Kss, scr, Mu, Var;
+    DevBuf kdv;                // Kdiag of the new points where it depends on the point (else NULL: kdiag)
     long Mn = 0, mnp = 0;
     double kdiag = 0.0;
     double* var = nullptr;     // where sparse_newpoints_var left its result

@@ -88,11 +88,11 @@ __global__ __launch_bounds__(256) void k_svgp_kl_rows(const double* __restrict__
 // The three row reductions of svgp.py:45-51 in one pass, one wave per chunk row, 16-byte loads (ld % 2 == 0, the padding
 // columns of At / U / Kfu and the padding rows of qm are zero):
 //   first latent (d == 0):  mu[i][:] = sum_j At[i][j] m[j][:],  q[i] = sum_j At[i][j] Kfu[i][j]  (kept for the other latents)
-//   every latent:           v[i][d] = sum_j U[i][j]^2 + kdiag - q[i],   U = A^T L_d
+//   every latent:           v[i][d] = sum_j U[i][j]^2 + kdiag - q[i],   U = A^T L_d   (kdiag: kd[i] where a vector is given)
 __global__ __launch_bounds__(256) void k_svgp_rowstats(const double* __restrict__ At, const double* __restrict__ Kfu,
                                                        const double* __restrict__ U, long ld, long rows,
                                                        const double* __restrict__ qm, int L, int d, double kdiag,
-                                                       double* __restrict__ mu, double* __restrict__ q, double* __restrict__ v) {
+                                                       const double* __restrict__ kd, double* __restrict__ mu, double* __restrict__ q, double* __restrict__ v) {
     const int lane = threadIdx.x & 63;
     const long i = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (i >= rows) return;
@@ -132,7 +132,7 @@ __global__ __launch_bounds__(256) void k_svgp_rowstats(const double* __restrict_
     } else if (lane == 0) {
         qq = q[i];
     }
-    if (lane == 0) v[i * L + d] = (ss + kdiag) - qq;
+    if (lane == 0) v[i * L + d] = (ss + (kd ? kd[i] : kdiag)) - qq;
 }
 // U[i][j] = w[i][d] * At[i][j] for i < rows, 0 for rows <= i < rows_pad   (Adv_d of svgp.py:85, N x M; the weights are signed)
 __global__ void k_svgp_weight_rows(const double* __restrict__ At, long ld, long rows, long rows_pad, const double* __restrict__ w,
@@ -294,7 +294,9 @@ int mi355gp_svgp_forward(mi355gp_sparse* s, int nparts, const mi355gp_part* part
     launch_reduce_partials(st, sv->rowPart, (int)m, 2 * L + 1, sv->red);
     HIP_CHECK(hipEventRecord(s->ev[1], st));
     // ---- row phase: mu = A^T m, v_d = diag(A^T S_d A) + Kdiag - diag(A^T Kmn) (svgp.py:45-51) ------------------------------
-    const double kdiag = expression_kdiag(s->parts, s->terms);
+    const double kdiag = s->diag_pt ? 0.0 : expression_kdiag(s->parts, s->terms);
+    if (s->diag_pt)                                            // Kdiag by point, in s->dKd
+        if (int rc = sparse_kdiag_data(s, nullptr, nullptr)) return rc;
     for (long r0 = 0; r0 < n; r0 += chunk) {
         const long rc = (n - r0 < chunk) ? (n - r0) : chunk;
         const long rcp = round_up(rc, NB);
@@ -302,7 +304,7 @@ int mi355gp_svgp_forward(mi355gp_sparse* s, int nparts, const mi355gp_part* part
         for (int d = 0; d < L; ++d) {
             launch_gemm(st, 0, 1, rcp, mp, mp, s->T, mp, sv->Ld + (size_t)d * mm, mp, sv->U, mp, 1.0, 0.0);
             hipLaunchKernelGGL(k_svgp_rowstats, dim3((unsigned)((rc + 3) / 4)), dim3(256), 0, st, s->T, s->Kfu, sv->U, mp, rc, sv->qm, L,
-                               d, kdiag, sv->dMu + r0 * L, sv->dQ + r0, sv->dVv + r0 * L);
+                               d, kdiag, s->diag_pt ? s->dKd + r0 : nullptr, sv->dMu + r0 * L, sv->dQ + r0, sv->dVv + r0 * L);
         }
     }
     HIP_CHECK(hipEventRecord(s->ev[2], st));
@@ -404,6 +406,16 @@ int mi355gp_svgp_backward(mi355gp_sparse* s, const double* dF_dmu, const double*
         launch_gemm(st, 0, 1, mp, mp, mp, s->P, mp, sv->Ld + (size_t)d * mm, mp, sv->Tq + (size_t)d * mm, mp, 2.0, 0.0);
     }
     sparse_kmm_gradients(s);
+    // a per-point diagonal: update_gradients_diag's sums against w_n = dL_dKdiag_n = sum_d dF_dv[n][d] (svgp.py:117)
+    std::vector<double> dsums, wrow;
+    if (s->diag_pt) {
+        wrow.assign((size_t)n, 0.0);
+        for (long i = 0; i < n; ++i)
+            for (int d = 0; d < L; ++d) wrow[(size_t)i] += dF_dv[i * L + d];
+        HIP_CHECK(s->diagW.need((size_t)n));
+        HIP_CHECK(hipMemcpyAsync(s->diagW, wrow.data(), sizeof(double) * n, hipMemcpyHostToDevice, st));
+        if (int rc = sparse_kdiag(s, s->dX, n, s->diagW, nullptr, &dsums)) return rc;
+    }
     HIP_CHECK(hipEventRecord(s->ev[2], st));
     // ---- small results to the host ------------------------------------------------------------------------------------------
     KernGrads kg;
@@ -425,6 +437,7 @@ int mi355gp_svgp_backward(mi355gp_sparse* s, const double* dF_dmu, const double*
     // dL_dKdiag = dF_dv.sum(1) (svgp.py:117): update_gradients_diag gives its sum to every part's variance
     double sum_dv = 0.0;
     for (long i = 0; i < n * L; ++i) sum_dv += dF_dv[i];
+    if (s->diag_pt) sparse_diag_dtheta(s, dsums, 1.0, &kg.ddiag);
     sparse_assemble_gradients(s, kg, sum_dv, dtheta_out, dZ_out);             // (core/svgp.py:58-65)
     return 0;
 }

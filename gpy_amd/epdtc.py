@@ -29,8 +29,8 @@ class EPDTC(SparseSession):
     _stop_criteria = _EP._stop_criteria
 
     def __init__(self, epsilon=1e-6, eta=1., delta=1., always_reset=False, max_iters=np.inf, ep_mode="alternated",
-                 parallel_updates=False, device=0, maxtries=5):
-        super(EPDTC, self).__init__(device=device, maxtries=maxtries)
+                 parallel_updates=False, device=0, maxtries=5, linear=False):
+        super(EPDTC, self).__init__(device=device, maxtries=maxtries, linear=linear)
         self.always_reset = always_reset
         self.epsilon, self.eta, self.delta, self.max_iters = epsilon, eta, delta, max_iters
         self.ep_mode = ep_mode
@@ -75,7 +75,7 @@ class EPDTC(SparseSession):
         if not isinstance(likelihood.gp_link, Probit):
             raise NotImplementedError("EPDTC on the MI355X path matches moments for the probit link only, not %s"
                                       % type(likelihood.gp_link).__name__)
-        sparse_path_kernel_check(kern)
+        sparse_path_kernel_check(kern, self.linear)
         if self.ep_mode not in ("nested", "alternated"):
             raise ValueError("ep_mode value not valid")
         self._refuse_sharded("a row-sharded sparse context is not supported by EPDTC")
@@ -85,7 +85,7 @@ class EPDTC(SparseSession):
         self._ensure(Xs, Y)
         specs = kern.part_specs()
         # Lm = jitchol(kern.K(Z)) (:448-450): the ladder runs on the device factorisation's info, its jitter stays on Kmm
-        _, self._jitter = jitter_ladder(lambda jit: self._ctx.epdtc_begin(specs, Zs, jit), kern.diag_variance(), self.maxtries)
+        _, self._jitter = jitter_ladder(lambda jit: self._ctx.epdtc_begin(specs, Zs, jit), lambda: kern.jitter_diag(Z), self.maxtries)
         if self.ep_mode == "nested":
             self._ep_approximation = None
         if self._ep_approximation is None:

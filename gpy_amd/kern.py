@@ -907,8 +907,11 @@ class Poly(Kern):
 
 # kernels the exact-GP device path evaluates as one part (the fused inference call takes them alone or in Add / Prod)
 DEVICE_KERNELS = (Stationary, StdPeriodic, Linear, MLP, Poly)
-# kinds only the exact path has (the sparse and grid paths reject them)
+# kinds the exact path alone evaluates in full: the grid path rejects every one of them, the sparse path all but Linear
 EXACT_ONLY_KINDS = ("ratquad", "stdperiodic", "coregionalize", "linear", "mlp", "poly", "cosine", "sinc", "expquadcosine")
+# ... of which the sparse path (certain inputs, one device) takes Linear where it is asked to (`linear=True` on the inference
+# class): its Kdiag travels by point
+SPARSE_REFUSED_KINDS = tuple(k for k in EXACT_ONLY_KINDS if k != "linear")
 
 
 def has_coregionalize(kern):
@@ -932,6 +935,11 @@ def _spec_dims(f):
 def exact_only_leaves(kern):
     """names of the kernels in `kern` (a foreign object has none) that only the exact-GP path evaluates"""
     return [type(k).__name__ for k in (kern.leaves() if isinstance(kern, Kern) else []) if k.kind in EXACT_ONLY_KINDS]
+
+
+def sparse_refused_leaves(kern):
+    """names of the kernels in `kern` that the sparse path does not evaluate (`SPARSE_REFUSED_KINDS`)"""
+    return [type(k).__name__ for k in (kern.leaves() if isinstance(kern, Kern) else []) if k.kind in SPARSE_REFUSED_KINDS]
 
 
 class Static(Kern):

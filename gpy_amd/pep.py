@@ -26,8 +26,8 @@ from .variational import NormalPosterior
 class PEP(SparseSession):
     const_jitter = 1e-6                                       # (pep.py:17, fitc.py:17; VarDTC's is 1e-8)
 
-    def __init__(self, alpha, device=0, maxtries=5):
-        super(PEP, self).__init__(device=device, maxtries=maxtries)
+    def __init__(self, alpha, device=0, maxtries=5, linear=False):
+        super(PEP, self).__init__(device=device, maxtries=maxtries, linear=linear)
         self.alpha = alpha
 
     def to_dict(self):
@@ -49,7 +49,7 @@ class PEP(SparseSession):
         if np.ndim(Y) != 2 or np.shape(Y)[1] != 1:
             raise NotImplementedError("%s: %s output columns; one is covered (the reference's v.reshape(-1, 1))"
                                       % (name, np.shape(Y)[1] if np.ndim(Y) == 2 else "no"))
-        sparse_path_kernel_check(kern)
+        sparse_path_kernel_check(kern, self.linear)
         self._refuse_sharded("%s: a row-sharded sparse context is not supported" % name)
         return float(sigma_n[0])
 
@@ -62,7 +62,7 @@ class PEP(SparseSession):
         specs = kern.part_specs()
         # the ladder's jitter comes on top of const_jitter (pep.py:40-41,50)
         r = self._run(kern, lambda extra: self._ctx.pep(specs, Zs, s2, alpha, self.const_jitter + extra,
-                                                        want_stage_ms=self.collect_stage_ms))
+                                                        want_stage_ms=self.collect_stage_ms), Z)
         M, N = Zs.shape[0], Xs.shape[0]
         post, dL_dKmm = self._posterior(kern, M, r["woodbury_vector"])                   # woodbury_inv = Kmmi - P (pep.py:91)
         grad_dict = {"dL_dKmm": dL_dKmm,
@@ -77,8 +77,8 @@ class PEP(SparseSession):
 class FITC(PEP):
     """`GPy.inference.latent_function_inference.FITC` (reference `fitc.py:10-88`): `PEP` with alpha = 1."""
 
-    def __init__(self, device=0, maxtries=5):
-        super(FITC, self).__init__(1.0, device=device, maxtries=maxtries)
+    def __init__(self, device=0, maxtries=5, linear=False):
+        super(FITC, self).__init__(1.0, device=device, maxtries=maxtries, linear=linear)
 
     def to_dict(self):
         return {"class": "GPy.inference.latent_function_inference.fitc.FITC"}

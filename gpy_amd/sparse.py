@@ -4,7 +4,8 @@
 and a homoscedastic Gaussian likelihood (BASELINE config 5).
 
 `VarDTC.inference(kern, X, Z, likelihood, Y, ...)` returns `(Posterior, log_marginal, grad_dict)` with the reference's
-keys, for gpy_amd's stationary kernels and sums (`Add`) of stationary / White / Bias parts, a scalar or per-point
+keys, for gpy_amd's stationary kernels, `Linear` where the class is made with `linear=True`, products of those and Bias, and sums
+(`Add`) of those and White / Bias parts, a scalar or per-point
 Gaussian noise variance and an optional mean function.  The N x M matrix `dL_dKnm` is never resident: the kernel and
 inducing-input gradients that `SparseGP._update_gradients` derives from it are reduced on the device in the second
 streaming pass and travel in `grad_dict['fused']`; `dL_dKmm` is a lazy device view and `dL_dKnm` a lazy object that a
@@ -23,7 +24,7 @@ import numpy as np
 
 from . import _lib
 from .inference import LatentFunctionInference
-from .kern import RBF, Add, Prod, White, exact_only_leaves
+from .kern import RBF, Add, Prod, White, diag_depends_on_point, exact_only_leaves, sparse_refused_leaves
 from .lazy import ArrayIdentity, LazyMM, LazyNM, LazyPsi1, freeze, kernel_signature
 from .likelihoods import Gaussian
 from .linalg import LinAlgError, jitter_ladder
@@ -119,22 +120,25 @@ def _host_predictive_gradients(kern, Xnew, pred_var, woodbury_vector, woodbury_i
     return mean_jac, var_jac + kern.gradients_X(a2, Xnew, pred_var)
 
 
-def sparse_path_kernel_check(kern):
-    """What the sparse device context evaluates (VarDTC and SVGP alike); anything else is refused by name."""
-    new_kinds = exact_only_leaves(kern)
+def sparse_path_kernel_check(kern, linear=False):
+    """What the sparse device context evaluates (VarDTC and SVGP alike); anything else is refused by name.  `linear`: the
+    inference class was made with `linear=True` and takes Linear leaves; without it they are refused like the other kinds
+    that only the exact path has, as they were before the sparse path could evaluate them."""
+    new_kinds = sparse_refused_leaves(kern) if linear else exact_only_leaves(kern)
     if new_kinds:
-        raise NotImplementedError("the MI355X sparse path does not evaluate %s kernels (the exact GPRegression path does)"
-                                  % ", ".join(sorted(set(new_kinds))))
-    # stationary kernels, products (Prod, reference `prod.py:58-99`) of stationary / Bias factors, and sums (Add) of those
-    # and of White / Bias parts
+        hint = "; Linear: make the inference class with linear=True" if "Linear" in new_kinds else ""
+        raise NotImplementedError("the MI355X sparse path does not evaluate %s kernels (the exact GPRegression path does%s)"
+                                  % (", ".join(sorted(set(new_kinds))), hint))
+    # stationary and Linear kernels, products (Prod, reference `prod.py:58-99`) of stationary / Linear / Bias factors, and sums
+    # (Add) of those and of White / Bias parts
     def _prod_ok(k):
         return isinstance(k, Prod) and not any(isinstance(f, (White, Add, Prod)) for f in k.parts)
     lone = getattr(kern, "is_leaf", False) and kern.fused_alone          # (not a lone White / Bias)
     ok = lone or _prod_ok(kern) or (
         isinstance(kern, Add) and all(_prod_ok(p) if isinstance(p, Prod) else not isinstance(p, Add) for p in kern.parts))
     if not ok:
-        raise NotImplementedError("the MI355X sparse path covers gpy_amd's stationary kernels, products of stationary / "
-                                  "Bias factors and sums (Add) of those and of White / Bias parts")
+        raise NotImplementedError("the MI355X sparse path covers gpy_amd's stationary kernels and Linear, products of "
+                                  "stationary / Linear / Bias factors and sums (Add) of those and of White / Bias parts")
 
 
 def noise_variances(likelihood, Y_metadata, precision=None):
@@ -151,8 +155,9 @@ class SparseSession(LatentFunctionInference):
     `_ensure`, one `_run` over a context call and the results built by `_posterior` / `_device_dict`."""
     _device_members = ("_ctx", "_X", "_Y")
 
-    def __init__(self, device=0, maxtries=5):
+    def __init__(self, device=0, maxtries=5, linear=False):
         self.device, self.maxtries = device, maxtries
+        self.linear = bool(linear)       # take Linear leaves (Kdiag by point on the device); off: refused by name, as before
         self._ctx = None
         self._X = self._Y = None
         self._token = 0
@@ -168,16 +173,20 @@ class SparseSession(LatentFunctionInference):
         recognised by identity, anything else by a full comparison"""
         if self._ctx is None:
             self._ctx = _lib.SparseContext(self.device)
+            if self.linear:
+                self._ctx.set_linear(True)
         if self._X is not None and self._X.matches(X) and self._Y.matches(Y):
             return False
         self._ctx.set_data(X, Y)
         self._X, self._Y = ArrayIdentity(X), ArrayIdentity(Y)
         return True
 
-    def _run(self, kern, call):
+    def _run(self, kern, call, Z):
         """One evaluation: `call(extra_jitter)` -> (info, result) on the context under jitchol's ladder (util/linalg.py:56-75)
-        for Kmm.  Its result is then the context's latest: everything made from earlier ones is stale."""
-        (r,), _ = jitter_ladder(call, kern.diag_variance(), self.maxtries)
+        for Kmm, whose first rung is mean(diag Kmm) * 1e-6 (:65): `kern.jitter_diag(Z)`, one number unless a Linear leaf makes
+        the diagonal depend on the inducing point.  Its result is then the context's latest: everything made from earlier
+        ones is stale."""
+        (r,), _ = jitter_ladder(call, lambda: kern.jitter_diag(Z), self.maxtries)
         self._token += 1
         self.last_stage_ms = r.get("stage_ms")
         return r
@@ -224,8 +233,9 @@ class VarDTC(SparseSession):
         parts = kern.parts if isinstance(kern, Add) else [kern]
         for p in parts:
             if not isinstance(p, (RBF, White)) or type(p) not in (RBF, White):
+                what = type(p).__name__ if p.is_leaf else "%s of %s" % (type(p).__name__, ", ".join(type(f).__name__ for f in p.leaves()))
                 raise NotImplementedError("uncertain inputs: the part %r (%s) has no psi-statistics on the MI355X sparse path; "
-                                          "one RBF kernel and White parts are covered" % (p.name, type(p).__name__))
+                                          "one RBF kernel and White parts are covered" % (p.name, what))
         rbfs = [p for p in parts if isinstance(p, RBF)]
         if len(rbfs) != 1:
             raise NotImplementedError("uncertain inputs: exactly one RBF part is covered, got %d (%s)"
@@ -240,7 +250,7 @@ class VarDTC(SparseSession):
         self._ensure_uncertain(mu, S, R)
         specs = kern.part_specs()
         r = self._run(kern, lambda extra: self._ctx.vardtc_uncertain(specs, Zs, noise, extra_jitter=extra,
-                                                                     want_stage_ms=self.collect_stage_ms))
+                                                                     want_stage_ms=self.collect_stage_ms), Z)
         M, N = Zs.shape[0], mu.shape[0]
         post, dL_dKmm = self._posterior(kern, M, r["woodbury_vector"])
         beta = float(1.0 / np.fmax(noise, self.const_jitter)[0])
@@ -256,7 +266,7 @@ class VarDTC(SparseSession):
                   dL_dKmm=None, psi0=None, psi1=None, psi2=None, Z_tilde=None):
         uncertain = isinstance(X, NormalPosterior)
         if not uncertain:
-            sparse_path_kernel_check(kern)
+            sparse_path_kernel_check(kern, self.linear)
         if any(a is not None for a in (Lm, dL_dKmm, psi0, psi1, psi2)):
             raise NotImplementedError("precomputed statistics are not accepted by the MI355X sparse path")
         if uncertain:
@@ -269,11 +279,14 @@ class VarDTC(SparseSession):
         m = 0 if mean_function is None else mean_function.f(X)
         Xs, Zs = kern._slice_X(X), kern._slice_X(Z)
         R = _lib.f64(Y - m)
+        if diag_depends_on_point(kern):
+            self._refuse_sharded("a Linear kernel is not supported by a row-sharded sparse context: its Kdiag depends on the "
+                                 "point, so the sums over rows would need another all-reduce")
         self._ensure(Xs, R)
         specs = kern.part_specs()
         r = self._run(kern, lambda extra: self._ctx.vardtc_sum(specs, Zs, noise, extra_jitter=extra,
                                                                want_dL_dm=mean_function is not None,
-                                                               want_stage_ms=self.collect_stage_ms))
+                                                               want_stage_ms=self.collect_stage_ms), Z)
         M, N = Zs.shape[0], Xs.shape[0]
         post, dL_dKmm = self._posterior(kern, M, r["woodbury_vector"])
         beta = 1.0 / np.fmax(noise, self.const_jitter)
@@ -410,10 +423,11 @@ class SparseGP(PredictionCallers, Parameterized):
 
 
 class SparseGPRegression(SparseGP):
-    """(reference `GPy/models/sparse_gp_regression.py:20-60`): Z defaults to a random subset of X."""
+    """(reference `GPy/models/sparse_gp_regression.py:20-60`): Z defaults to a random subset of X.  `linear=True`: the kernel
+    may hold Linear leaves (`VarDTC(linear=True)`)."""
 
     def __init__(self, X, Y, kernel=None, Z=None, num_inducing=10, noise_var=1., device=0, seed=None, mean_function=None,
-                 X_variance=None):
+                 X_variance=None, linear=False):
         X = np.asarray(X, dtype=np.float64)
         if kernel is None:
             kernel = RBF(X.shape[1], device=device)
@@ -421,6 +435,7 @@ class SparseGPRegression(SparseGP):
             i = np.random.default_rng(seed).permutation(X.shape[0])[:min(num_inducing, X.shape[0])]
             Z = X[i].copy()
         super(SparseGPRegression, self).__init__(X, Y, Z, kernel, Gaussian(variance=noise_var),
+                                                 inference_method=VarDTC(device=device, linear=True) if linear else None,
                                                  name="sparse_gp", device=device, mean_function=mean_function,
                                                  X_variance=X_variance)
 

@@ -93,7 +93,7 @@ class SVGP(SparseSession):
         if not hasattr(likelihood, "variational_expectations"):
             raise NotImplementedError("the %s likelihood has no variational_expectations, which SVGP needs (svgp.py:77)"
                                       % type(likelihood).__name__)
-        sparse_path_kernel_check(kern)
+        sparse_path_kernel_check(kern, self.linear)
         self._refuse_sharded("SVGP is not supported by a row-sharded sparse context")
         q_u_mean = _lib.f64(np.asarray(q_u_mean))
         Y = np.asarray(Y, dtype=np.float64)
@@ -107,7 +107,7 @@ class SVGP(SparseSession):
         self._ensure(Xs, _lib.f64(Y))
         specs = kern.part_specs()
         fw = self._run(kern, lambda extra: self._ctx.svgp_forward(specs, Zs, q_u_mean, L, extra_jitter=extra,
-                                                                  want_stage_ms=self.collect_stage_ms))   # Kmm (svgp.py:40)
+                                                                  want_stage_ms=self.collect_stage_ms), Z)   # Kmm (svgp.py:40)
         # quadrature for the likelihood (svgp.py:77), rescaled if working on a batch (:80-82)
         F, dF_dmu, dF_dv, dF_dthetaL = likelihood.variational_expectations(Y, fw["mu"], fw["v"], Y_metadata=Y_metadata)
         F, dF_dmu, dF_dv = F * batch_scale, dF_dmu * batch_scale, dF_dv * batch_scale
@@ -157,7 +157,7 @@ class SVGPModel(SparseGP):
     `optimize()` is the inherited full-batch L-BFGS-B; a stochastic optimiser is not part of the package."""
 
     def __init__(self, X, Y, Z, kernel, likelihood, batchsize=None, seed=None, device=0, name="SVGP", Y_metadata=None,
-                 num_latent_functions=None, mean_function=None):
+                 num_latent_functions=None, mean_function=None, linear=False):
         if mean_function is not None:
             raise NotImplementedError("SVGP on the MI355X path has no mean function")
         if isinstance(X, NormalPosterior):
@@ -175,7 +175,7 @@ class SVGPModel(SparseGP):
         else:
             self.slicer = _MiniSlices(self.X_all.shape[0], batchsize, seed)
             X_batch, Y_batch = self.new_batch()
-        super(SVGPModel, self).__init__(X_batch, Y_batch, Z, kernel, likelihood, inference_method=SVGP(device=device), name=name,
+        super(SVGPModel, self).__init__(X_batch, Y_batch, Z, kernel, likelihood, inference_method=SVGP(device=device, linear=linear), name=name,
                                         device=device, Y_metadata=Y_metadata)
         self.link_parameter(self.chol)
         self.link_parameter(self.m)
