@@ -84,6 +84,8 @@ def build(force=False):
     srcs.append(os.path.join(_HERE, "..", "include", "mi355gp_debug_tileops.h"))
     srcs.append(os.path.join(_HERE, "..", "include", "mi355gp_epdtc.h"))
     srcs.append(os.path.join(_HERE, "..", "include", "mi355gp_sparse_diag.h"))
+    srcs.append(os.path.join(_HERE, "..", "include", "mi355gp_psi_lin.h"))
+    srcs.append(os.path.join(_HERE, "..", "include", "mi355gp_debug_psi_lin.h"))
     srcs.append(os.path.join(_HERE, "..", "include", "mi355gp_vargauss.h"))
     srcs.append(os.path.join(_HERE, "..", "include", "mi355gp_kron.h"))
     product = os.path.join(_HERE, "libmi355gp.so")
@@ -220,6 +222,15 @@ SPARSE_DIAG_ABI = {
     "mi355gp_sparse_set_linear": [_vp, _ci],
     "mi355gp_sparse_kdiag": [_vp, _ci, _parts] + [_c_dp] * 4,
 }
+# include/mi355gp_psi_lin.h: Linear and Bias psi-statistics on the sparse context (tests/test_psi_lin_host.py holds the table
+# against that header's prototype)
+PSI_LIN_ABI = {
+    "mi355gp_sparse_set_psi_lin_bias": [_vp, _ci],
+}
+# include/mi355gp_debug_psi_lin.h: the row kernel of a Linear part on its own, a diagnostic (held by the same test)
+DEBUG_PSI_LIN_ABI = {
+    "mi355gp_dbg_psi_lin_rows": [_ci, _ci, _dp] + [_c_dp] * 3 + [_cd, _cd, _dp, _dp, _dp, _cd, _i64, _i64, _ci, _ci, _dp, _ci, _c_dp],
+}
 # include/mi355gp_vargauss.h: the variational Gaussian approximation inside the Laplace session of an exact context, in its order
 # (tests/test_oracle_vargauss.py holds the table against that header's prototypes)
 VARGAUSS_ABI = {
@@ -254,7 +265,7 @@ def lib():
         if not os.path.exists(LIB_PATH):
             build()
         L = ctypes.CDLL(LIB_PATH)
-        for table in (ABI, DEBUG_LAUUM_ABI, DEBUG_TILEOPS_ABI, EPDTC_ABI, SPARSE_DIAG_ABI, VARGAUSS_ABI, KRON_ABI):
+        for table in (ABI, DEBUG_LAUUM_ABI, DEBUG_TILEOPS_ABI, EPDTC_ABI, SPARSE_DIAG_ABI, PSI_LIN_ABI, DEBUG_PSI_LIN_ABI, VARGAUSS_ABI, KRON_ABI):
             for name, argtypes in table.items():
                 getattr(L, name).argtypes = argtypes
         L.mi355gp_last_error.restype = L.mi355gp_version.restype = _str
@@ -720,6 +731,11 @@ class SparseContext(_Handle):
     def set_linear(self, on=True):
         """Linear parts on this context's inference and prediction entry points (`mi355gp_sparse_set_linear`); off at first"""
         check(lib().mi355gp_sparse_set_linear(self._h, int(bool(on))), "mi355gp_sparse_set_linear")
+
+    def set_psi_lin_bias(self, on=True):
+        """One RBF or Linear part with Bias and White parts on this context's uncertain-input entry points
+        (`mi355gp_sparse_set_psi_lin_bias`); off at first.  On also switches Linear on."""
+        check(lib().mi355gp_sparse_set_psi_lin_bias(self._h, int(bool(on))), "mi355gp_sparse_set_psi_lin_bias")
 
     def kdiag(self, specs, w=None):
         """Kdiag of the expression at the context's rows (`mi355gp_sparse_kdiag`): kd (N), and with weights w (N) also
@@ -1221,3 +1237,28 @@ class KronContext(_Handle):
         ms = ctypes.c_double(0.0)
         check(lib().mi355gp_kron_get_ms(self._h, ctypes.byref(ms)), "mi355gp_kron_get_ms")
         return ms.value
+
+
+def psi_lin_rows_probe(W, X, Z, variances, c0=0.0, Y=None, V=None, rowscale=None, beta=0.0, gscale=1.0, fused=True, device=0,
+                       time_reps=0):
+    """The row-side kernel of a Linear part on its own (`mi355gp_dbg_psi_lin_rows`, include/mi355gp_debug_psi_lin.h):
+    out[i][q] = variances_q (sum_j g[i][j] Z[j][q] + c0 X[i][q]), g = W, or rowscale_i (gscale W + beta Y V^T) formed on the fly.
+    `fused`: the MFMA kernel (D <= 16); otherwise the weights in memory and the plain kernel.  time_reps > 0: returns
+    (out, the milliseconds of each of that many further launches, by HIP events)."""
+    W, X, Z = f64(W), f64(X), f64(Z)
+    rows, M = W.shape
+    D = X.shape[1]
+    assert X.shape == (rows, D) and Z.shape == (M, D), "W is rows x M, X rows x D, Z M x D"
+    var = f64(np.broadcast_to(np.asarray(variances, dtype=np.float64).ravel(), (D,)))
+    Dy = 0
+    if Y is not None:
+        Y, V = f64(Y), f64(V)
+        Dy = Y.shape[1]
+        assert Y.shape == (rows, Dy) and V.shape == (M, Dy), "Y is rows x Dy, V M x Dy"
+        rowscale = None if rowscale is None else f64(np.asarray(rowscale)).ravel()
+        assert rowscale is None or rowscale.size == rows
+    out, ms = np.empty((rows, D)), np.zeros(max(1, int(time_reps)))
+    check(lib().mi355gp_dbg_psi_lin_rows(int(device), int(bool(fused)), W, _opt(Y), _opt(V if Y is not None else None),
+                                           _opt(rowscale if Y is not None else None), float(beta), float(gscale), X, Z, var,
+                                           float(c0), rows, M, D, Dy, out, int(time_reps), _opt(ms)), "mi355gp_dbg_psi_lin_rows")
+    return (out, ms) if time_reps > 0 else out

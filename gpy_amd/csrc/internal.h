@@ -323,6 +323,14 @@ int launch_grad_cols(hipStream_t st, KernParams kp, const double* Xt1, long ld1,
 // the host from HX and the scaled Z.  Returns the number of row splits, 0 = not applicable (D > 16)
 int launch_grad_cols_lin(hipStream_t st, const double* Xt1, long ld1, long n, int D, long m, long mcols, const double* G, long ldg,
                          RankTerm rk, double* colpart);
+// the row side of a Linear part under uncertain inputs (k_grad_rows_lin, D <= 16): out[i][q] = il_q (sum_j g[i][j] z~[j][q] +
+// c0 x~[i][q]) (n x D row-major) in one pass over the weights, formed on the fly as above; Xt1 / Xt2: the scaled rows and
+// inducing inputs, dimension-major; il: the part's input scaling (D, device).  Returns 1, or 0 = not applicable (D > 16) ...
+int launch_grad_rows_lin(hipStream_t st, const double* Xt1, long ld1, long n, int D, const double* Xt2, long ld2, long m,
+                         const double* G, long ldg, RankTerm rk, const double* il, double c0, double* out);
+// ... then the weights g are formed in memory first (launch_form_rank_weights) and this plain kernel takes any D <= 64
+void launch_rows_lin_plain(hipStream_t st, const double* Xt1, long ld1, long n, int D, const double* Xt2, long ld2, long m,
+                           const double* g, long ldg, const double* il, double c0, double* out);
 // out[i][j] = the weight the RankTerm describes (rows x m; 0 in the columns [m, ld)), for the passes that need it in memory
 void launch_form_rank_weights(hipStream_t st, const double* G, long ld, long rows, long m, RankTerm rk, double* out);
 // part[split][cols][nv] = sum over a row range of M[i][j] * V(i, c); V(i, c) = V[i*sr + c*sc] plus an optional
@@ -351,6 +359,10 @@ static inline long kdiag_blocks(long n) { return (n + 255) / 256; }
 // kdiag_blocks(n) records) combined in block order, no atomics: two calls give the same bytes.  coef: nparts x D.
 void launch_kdiag(hipStream_t st, const DiagDesc& ds, const double* X, long n, int D, const double* coef, const double* w,
                   double* kd_out, double* partials, double* sums_out);
+
+// Gaussian rows N(mu_n, diag S_n): sums_out[q] = sum_n S_nq, sums_out[D + q] = sum_n mu_nq^2 (2 D doubles; partials:
+// kdiag_blocks(n) records of 2 D), combined in block order like the record above
+void launch_kdiag_var_sums(hipStream_t st, const double* mu, const double* S, long n, int D, double* partials, double* sums_out);
 
 // ---- reduce.hip : reductions, triangular solves and fetch helpers that stage no input slabs -----------------------
 // y = X r (lower-triangular X, n x n within npad), then a = X^T y   (Dy right-hand sides, row-major n x Dy)

@@ -78,6 +78,30 @@ __global__ void k_kdiag_combine(const double* __restrict__ partials, long nblk, 
     out[s] = a;
 }
 
+// Gaussian rows q(x_n) = N(mu_n, diag S_n): the column sums a Linear part's psi0 = sum_q variance_q (mu_q^2 + S_q) and its
+// psi2 need -- rec[q] = sum_n S_nq, rec[D + q] = sum_n mu_nq^2 -- one record of 2 D doubles per block, as above
+__global__ __launch_bounds__(256) void k_kdiag_var_rows(const double* __restrict__ mu, const double* __restrict__ S, long n, int D,
+                                                        double* __restrict__ partials) {
+    __shared__ double red[256];
+    const int t = threadIdx.x;
+    const long i = (long)blockIdx.x * 256 + t;
+    const bool valid = i < n;
+    double* rec = partials + (long)blockIdx.x * 2 * D;
+    for (int q = 0; q < D; ++q) {
+        const double sv = valid ? S[i * D + q] : 0.0, x = valid ? mu[i * D + q] : 0.0;
+        double s = kdiag_block_sum(red, t, sv);
+        if (t == 0) rec[q] = s;
+        s = kdiag_block_sum(red, t, x * x);
+        if (t == 0) rec[D + q] = s;
+    }
+}
+
+void launch_kdiag_var_sums(hipStream_t st, const double* mu, const double* S, long n, int D, double* partials, double* sums_out) {
+    const long nblk = kdiag_blocks(n);
+    hipLaunchKernelGGL(k_kdiag_var_rows, dim3((unsigned)nblk), dim3(256), 0, st, mu, S, n, D, partials);
+    hipLaunchKernelGGL(k_kdiag_combine, dim3((unsigned)((2 * D + 255) / 256)), dim3(256), 0, st, partials, nblk, 2 * D, sums_out);
+}
+
 void launch_kdiag(hipStream_t st, const DiagDesc& ds, const double* X, long n, int D, const double* coef, const double* w,
                   double* kd_out, double* partials, double* sums_out) {
     const long nblk = kdiag_blocks(n);

@@ -555,6 +555,125 @@ int launch_grad_cols_lin(hipStream_t st, const double* Xt1, long ld1, long n, in
     return nsplit;
 }
 
+// The row-side counterpart for a Linear part under uncertain inputs (D <= 16): the gradient with respect to the rows themselves,
+//   out[i][q] = il_q (sum_j g[i][j] z~[j][q] + c0 x~[i][q]),     il_q = sqrt(variance_q), z~ = il z, x~ = il x,
+// which is d/dmu_iq of sum g K(mu, Z) + (c0 / 2) sum_i Kdiag(mu_i): the tall-skinny product (rows x m) (m x D).  A workgroup owns
+// 64 rows and walks the column tiles in order; the weights are formed on the fly exactly as k_grad_cols_lin forms them (no
+// rows x m array is written), the z~ slab of the tile is staged in LDS (zero past m and past D) and every wave multiplies its
+// 16 rows on v_mfma_f64_16x16x4.  One accumulator per output, summed over j in a fixed order: no atomics, the same bytes on
+// every call.  The kernel reads the chunk's weights once and is bound by that read.
+__global__ __launch_bounds__(256, 2) void k_grad_rows_lin(const double* __restrict__ Xt1, long ld1, long n, int D,
+                                                          const double* __restrict__ Xt2, long ld2, long m,
+                                                          const double* __restrict__ G, long ldg, RankTerm rk,
+                                                          const double* __restrict__ il, double c0, double* __restrict__ out) {
+    __shared__ __attribute__((aligned(16))) double szt[KT * 18];   // z~ slab row-major [j][c], stride 18: the B operand
+    __shared__ __attribute__((aligned(16))) double sh[KT * GC_HS];  // the tile of weights [i][j]: the A operand
+    const int t = threadIdx.x, tx = t & 15, ty = t >> 4, lane = t & 63, w = t >> 6;
+    const long i0 = (long)blockIdx.x * KT;
+    const int ntc = (int)((m + KT - 1) / KT);
+    d4 acc = {0.0, 0.0, 0.0, 0.0};                       // out[i = i0 + 16 w + (lane >> 4) + 4 r][c = lane & 15]
+    for (int idx = t; idx < KT * 18; idx += 256) szt[idx] = 0.0;      // columns c >= D stay zero
+    const bool rkfast = rk.Y != nullptr && rk.Dy <= GC_DY;
+    double yrow[4][GC_DY], rs[4];                        // the block's rows do not change: their rank-term rows once
+#pragma unroll
+    for (int a = 0; a < 4; ++a) {
+        const long i = i0 + ty * 4 + a;
+        rs[a] = 1.0;
+#pragma unroll
+        for (int d = 0; d < GC_DY; ++d) yrow[a][d] = (rkfast && i < n && d < rk.Dy) ? rk.Y[i * rk.Dy + d] : 0.0;
+        if (rkfast && i < n && rk.rowscale) rs[a] = rk.rowscale[i];
+    }
+    for (int tj = 0; tj < ntc; ++tj) {
+        const long j0 = (long)tj * KT;
+        __syncthreads();                                 // the previous tile's MFMA reads of sh / szt are done
+        for (int idx = t; idx < D * KT; idx += 256) {
+            const int q = idx >> 6, jj = idx & 63;
+            szt[jj * 18 + q] = (j0 + jj < m) ? Xt2[(long)q * ld2 + j0 + jj] : 0.0;
+        }
+        const bool vec4 = (j0 + tx * 4 + 3 < m) && (ldg % 4 == 0) && ((reinterpret_cast<unsigned long long>(G) & 31ull) == 0);
+        double vcol[4][GC_DY];
+#pragma unroll
+        for (int b = 0; b < 4; ++b)
+#pragma unroll
+            for (int d = 0; d < GC_DY; ++d)
+                vcol[b][d] = (rkfast && d < rk.Dy && j0 + tx * 4 + b < m) ? rk.V[(j0 + tx * 4 + b) * rk.Dy + d] : 0.0;
+#pragma unroll
+        for (int a = 0; a < 4; ++a) {
+            const long i = i0 + ty * 4 + a;
+            d4 gv = {0.0, 0.0, 0.0, 0.0};
+            if (i < n) {
+                if (vec4) gv = *reinterpret_cast<const d4*>(G + i * ldg + j0 + tx * 4);
+                else
+#pragma unroll
+                    for (int b = 0; b < 4; ++b)
+                        if (j0 + tx * 4 + b < m) gv[b] = G[i * ldg + j0 + tx * 4 + b];
+            }
+            d4 go = {0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+            for (int b = 0; b < 4; ++b) {
+                const long j = j0 + tx * 4 + b;
+                double g = 0.0;
+                if (i < n && j < m) {
+                    g = gv[b];
+                    if (rk.Y) {
+                        double yv = 0.0;
+                        if (rkfast) {
+#pragma unroll
+                            for (int d = 0; d < GC_DY; ++d)
+                                if (d < rk.Dy) yv = fma(yrow[a][d], vcol[b][d], yv);
+                        } else {
+                            for (int d = 0; d < rk.Dy; ++d) yv = fma(rk.Y[i * rk.Dy + d], rk.V[j * rk.Dy + d], yv);
+                        }
+                        g = fma(rk.gscale, g, rk.beta * yv);
+                        if (rk.rowscale) g *= rkfast ? rs[a] : rk.rowscale[i];
+                    }
+                }
+                go[b] = g;
+            }
+            *reinterpret_cast<d4*>(sh + (ty * 4 + a) * GC_HS + tx * 4) = go;
+        }
+        __syncthreads();                                 // the tile of weights and the z~ slab are complete
+        // out[16 w .., :] += g[16 w .., :] z~ : k = 4 s + (lane >> 4) over the 64 columns of the tile
+        const double* ha = sh + (16 * w + (lane & 15)) * GC_HS + (lane >> 4);
+        const double* zb = szt + (lane >> 4) * 18 + (lane & 15);
+#pragma unroll
+        for (int s4 = 0; s4 < 16; ++s4) acc = mfma_f64(ha[4 * s4], zb[4 * s4 * 18], acc);
+    }
+    const int c = lane & 15;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        const long i = i0 + 16 * w + (lane >> 4) + 4 * r;
+        if (c < D && i < n) out[i * D + c] = il[c] * fma(c0, Xt1[(long)c * ld1 + i], acc[r]);
+    }
+}
+
+// the same from weights in memory (any D up to 64; the fallback of the fused kernel, as on the column side): one thread per
+// output, j in order
+__global__ __launch_bounds__(256) void k_rows_lin_plain(const double* __restrict__ Xt1, long ld1, long n, int D,
+                                                        const double* __restrict__ Xt2, long ld2, long m,
+                                                        const double* __restrict__ g, long ldg, const double* __restrict__ il,
+                                                        double c0, double* __restrict__ out) {
+    const int q = threadIdx.x & 63;
+    const long i = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (i >= n || q >= D) return;
+    double a = 0.0;
+    for (long j = 0; j < m; ++j) a = fma(g[i * ldg + j], Xt2[(long)q * ld2 + j], a);
+    out[i * D + q] = il[q] * fma(c0, Xt1[(long)q * ld1 + i], a);
+}
+
+int launch_grad_rows_lin(hipStream_t st, const double* Xt1, long ld1, long n, int D, const double* Xt2, long ld2, long m,
+                         const double* G, long ldg, RankTerm rk, const double* il, double c0, double* out) {
+    if (D > 16) return 0;
+    hipLaunchKernelGGL(k_grad_rows_lin, dim3((unsigned)((n + KT - 1) / KT)), dim3(256), 0, st, Xt1, ld1, n, D, Xt2, ld2, m, G, ldg, rk,
+                       il, c0, out);
+    return 1;
+}
+void launch_rows_lin_plain(hipStream_t st, const double* Xt1, long ld1, long n, int D, const double* Xt2, long ld2, long m,
+                           const double* g, long ldg, const double* il, double c0, double* out) {
+    hipLaunchKernelGGL(k_rows_lin_plain, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, st, Xt1, ld1, n, D, Xt2, ld2, m, g, ldg, il, c0,
+                       out);
+}
+
 // out[i][j] = rowscale_i (gscale G[i][j] + beta sum_d Y[i][d] V[j][d]) for j < m, 0 for m <= j < ld: the weights of a RankTerm in
 // memory, in the arithmetic of the fused passes
 __global__ void k_form_rank_weights(const double* __restrict__ G, long ld, long rows, long m, RankTerm rk, double* __restrict__ out) {

@@ -23,6 +23,12 @@ struct PsiRank {
     double beta;
 };
 
+// ... plus add[m] on every row (the Bias parts' share of dL_dpsi1: b t^T, t = 2 rowsum(dL_dpsi2)); a kernel instantiated for
+// PsiRank itself is the code it was before this form existed
+struct PsiRankAdd : PsiRank {
+    const double* add;         // m
+};
+
 int psi_qp(int D);             // dimensions padded to a power of two up to 32, then to 64
 int psi2_nsplit(long rows, long m);
 // per row: rd1 / rd2 (rows x Qp double2 = (mu, c1) / (mu, c2)) and lg1 / lg2 (rows); a: Qp entries 1 / l_q^2 (0: not seen)
@@ -38,7 +44,8 @@ int launch_psi2(hipStream_t st, const double* rd2, const double* lg2, const doub
 void launch_psi2_combine(hipStream_t st, const double* part, long ld, long m, int nsplit, int accumulate, double* out, long ldo);
 // Ppart: ceil(m / 16) x rows x (1 + 2 Qp); Zpart: ceil(rows / PSI_GROWS) x mpad x Qp.  G == NULL: the weights are rk's product
 void launch_psi1_grad(hipStream_t st, const double* rd1, const double* lg1, const double* Zp, const double* G, long ldg,
-                      PsiRank rk, long rows, long m, long mpad, int Qp, double var, double* Ppart, double* Zpart);
+                      PsiRank rk, long rows, long m, long mpad, int Qp, double var, double* Ppart, double* Zpart,
+                      const double* add = nullptr);     // add (m, optional, with G == NULL only): see PsiRankAdd
 void launch_psi2_grad(hipStream_t st, const double* rd2, const double* lg2, const double* w, const double* Zp, const double* ap,
                       const double* dL, long ldd, long rows, long m, long mpad, int Qp, double var2, double* Ppart,
                       double* Zpart);
@@ -54,5 +61,20 @@ int psi_contract_nsplit(long rows, long m, int Qp);
 int launch_psi2n_contract(hipStream_t st, const double* rd2, const double* lg2, const double* Zp, const double* ap,
                           const double* lam, int Dy, const double* W, long ldw, long rows, long m, int Qp, double var2,
                           double* part);
+// ---- psi_lin.hip: the M-sized helpers of a Linear part and of Bias parts under uncertain inputs -----------
+// psi2[i][j] += sum_q (il_q^4 sums[q]) Z[i][q] Z[j][q], i, j < m (Z: m x D row-major, il / sums: device)
+void launch_psi2_rank_add(hipStream_t st, const double* Z, const double* il, const double* sums, long m, int D, double* psi2, long ld);
+// out (m x D) = A Z for a symmetric A (leading m x m of ld)
+void launch_mm_times_z(hipStream_t st, const double* A, long ld, const double* Z, long m, int D, double* out);
+// out[j] = scale sum_{i < m} A[i][j]
+void launch_mm_colsums(hipStream_t st, const double* A, long ld, long m, double scale, double* out);
+// psi2[i][j] += b (c[i] + c[j]) + nb2;  psi1Y[j][d] += b vs[d]   (i, j < m)
+void launch_psi2_bias_add(hipStream_t st, double* psi2, long ld, long m, const double* c, double b, double nb2);
+void launch_psi1y_bias_add(hipStream_t st, double* psi1Y, long m, int Dy, const double* vs, double b);
+// var[n][d] = max(base[n] + sum_q S[n][q] g[d][q], 1e-15)   (S: rows x D, g: Dy x D)
+void launch_lin_predvar(hipStream_t st, const double* base, const double* S, const double* g, long rows, int D, int Dy, double* var);
+// mean[n][d] += bsl[d];  C (optional, rows x (Dy + 1)): C[n][d] += sum_j psi1[n][j] u[j][d] + cst[d]
+void launch_psi_bias_pred(hipStream_t st, const double* psi1, long ldp, const double* u, const double* cst, const double* bsl, long rows,
+                          long m, int Dy, double* C, double* mean);
 // var (rows x Dy) = max(psi0 + C[n][d] - C[n][Dy] - mean[n][d]^2, 1e-15); C: rows x (Dy + 1)
 void launch_psi_predvar(hipStream_t st, const double* C, const double* mean, double psi0, long rows, int Dy, double* var);

@@ -19,6 +19,7 @@
 //
 // Prediction at uncertain points (posterior.py:249-269) contracts psi2n per row against given M x M weights: k_psi2n_contract.
 #include <cmath>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/mi355gp.h"
@@ -330,10 +331,11 @@ __device__ __forceinline__ void psi_grad_emit_z(int t, int gz, int Qp, long mcol
 }
 
 // psi1: L = G[n][m] var exp(lg1 - 1/2 sum c1 d^2), d = mu - z_m
-template <int QG>
+// (RK = PsiRankAdd: the rank product plus add[m] per column; RK = PsiRank compiles to the code it always was)
+template <int QG, class RK>
 __global__ __launch_bounds__(256) void k_psi1_grad(const double2* __restrict__ rd, const double* __restrict__ lg1,
                                                    const double* __restrict__ Zp, const double* __restrict__ G, long ldg,
-                                                   PsiRank rk, long rows, long m, long mpad, int Qp, double var,
+                                                   RK rk, long rows, long m, long mpad, int Qp, double var,
                                                    double* __restrict__ Ppart, double* __restrict__ Zpart) {
     extern __shared__ __align__(16) double sm[];
     double* zm = sm;                                           // 16 x (Qp + 1)
@@ -372,6 +374,7 @@ __global__ __launch_bounds__(256) void k_psi1_grad(const double2* __restrict__ r
             else {
                 for (int d = 0; d < rk.Dy; ++d) gw = fma(rk.R[n * rk.Dy + d], rk.v[mcol * rk.Dy + d], gw);
                 gw *= rk.beta;
+                if constexpr (std::is_same<RK, PsiRankAdd>::value) gw += rk.add[mcol];
             }
         }
         const double L = ok ? gw * var * exp(fma(-0.5, e, lg1[n])) : 0.0;
@@ -592,11 +595,19 @@ static size_t psi_grad_lds(int Qp, int QG, bool second) {
     }
 // Ppart: ceil(m / 16) x rows x (1 + 2 Qp); Zpart: ceil(rows / PSI_GROWS) x mpad x Qp
 void launch_psi1_grad(hipStream_t st, const double* rd1, const double* lg1, const double* Zp, const double* G, long ldg,
-                      PsiRank rk, long rows, long m, long mpad, int Qp, double var, double* Ppart, double* Zpart) {
+                      PsiRank rk, long rows, long m, long mpad, int Qp, double var, double* Ppart, double* Zpart,
+                      const double* add) {
     const int QG = Qp < PSI_KDC ? Qp : PSI_KDC;
     const dim3 grid((unsigned)((m + 15) / 16), (unsigned)((rows + PSI_GROWS - 1) / PSI_GROWS), (unsigned)(Qp / QG));
     const size_t lds = psi_grad_lds(Qp, QG, false);
-#define PSI_CALL(N) hipLaunchKernelGGL((k_psi1_grad<N>), grid, dim3(256), lds, st, (const double2*)rd1, lg1, Zp, G, ldg, rk, rows, m, mpad, Qp, var, Ppart, Zpart)
+    if (add && !G) {
+        const PsiRankAdd rka{rk, add};
+#define PSI_CALL(N) hipLaunchKernelGGL((k_psi1_grad<N, PsiRankAdd>), grid, dim3(256), lds, st, (const double2*)rd1, lg1, Zp, G, ldg, rka, rows, m, mpad, Qp, var, Ppart, Zpart)
+        PSI_QG_SWITCH(QG, PSI_CALL)
+#undef PSI_CALL
+        return;
+    }
+#define PSI_CALL(N) hipLaunchKernelGGL((k_psi1_grad<N, PsiRank>), grid, dim3(256), lds, st, (const double2*)rd1, lg1, Zp, G, ldg, rk, rows, m, mpad, Qp, var, Ppart, Zpart)
     PSI_QG_SWITCH(QG, PSI_CALL)
 #undef PSI_CALL
 }

@@ -19,6 +19,7 @@
 #include "../../include/mi355gp.h"
 #include "../../include/mi355gp_debug.h"
 #include "../../include/mi355gp_sparse_diag.h"
+#include "../../include/mi355gp_psi_lin.h"
 #include "internal.h"
 #include "parts.h"
 #include "psi.h"
@@ -870,8 +871,9 @@ void sparse_rows_gradients(mi355gp_sparse* s, long rc, const double* W, double* 
             // stationary ones when a rank term is given), then the column reduction of the stationary fallback
             if (prod) form_times();
             else if (s->fuse_cols) ns = launch_grad_cols_lin(st, p.XtC, chunk, rc, D, m, mp, W, mp, rk, s->colPart);
+            const double* g = nullptr;                   // the weights in memory, where a pass needed them there
             if (ns == 0) {
-                const double* g = prod ? scratch : W;
+                g = prod ? scratch : W;
                 if (!prod && rk.Y) {
                     launch_form_rank_weights(st, W, mp, rc, m, rk, scratch);
                     g = scratch;
@@ -879,6 +881,14 @@ void sparse_rows_gradients(mi355gp_sparse* s, long rc, const double* W, double* 
                 ns = launch_colreduce_multi(st, g, mp, rc, mp, p.XtC, 1, chunk, D, 0, s->colPart);
             }
             launch_sum_splits(st, s->colPart, mp * D, ns, 1, p.HX);
+            if (s->lin_dmu) {
+                // uncertain inputs: the gradient in the rows' means while the chunk's weights are hot (k_grad_rows_lin: one
+                // more read of them, formed on the fly as above; where they are in memory already, the plain kernel)
+                double* o = s->lin_dmu + s->lin_row0 * D;
+                // (g == NULL means the fused column pass ran, which it does for D <= 16 only: the fused row kernel applies)
+                if (g) launch_rows_lin_plain(st, p.XtC, chunk, rc, D, p.XtZ, mp, m, g, mp, p.dIl, s->lin_c0, o);
+                else launch_grad_rows_lin(st, p.XtC, chunk, rc, D, p.XtZ, mp, m, W, mp, rk, p.dIl, s->lin_c0, o);
+            }
             continue;
         }
         if (prod) {
@@ -1176,6 +1186,7 @@ static int vardtc_pass2(mi355gp_sparse* s, bool het, bool want_rows) {
         // the weights are T, the scratch the Kfu buffer: not needed any more for this chunk (the gradient kernels recompute
         // the covariance from the inputs)
         const RankTerm rk{s->dY + r0 * Dy, s->vvec, Dy, 1.0, 2.0, s->dBeta + r0};
+        s->lin_row0 = r0;                                    // (read with lin_dmu only: a Linear part under uncertain inputs)
         sparse_rows_gradients(s, rc, s->T, s->Kfu, rk, [&]() {
             hipLaunchKernelGGL(k_form_dLdKnm_times, dim3((unsigned)rcp, (unsigned)((mp + 255) / 256)), dim3(256), 0, st, s->T, s->Kfu,
                                mp, rc, rcp, m, s->dY + r0 * Dy, s->vvec, Dy, s->dBeta + r0);
@@ -1372,6 +1383,11 @@ struct PsiWork {
     double var = 0.0;                       // the RBF part's variance
     std::vector<double> ha, hzp, sums;      // a_q; padded Z; [0] the variance record, [1 + q] the lengthscale sums of psi1 and psi2
     DevBuf dA, dZp, rd1, rd2, lg1, lg2, Ppart, P1s, P2s, Zpart, Zs1, Zs2, dMuO, dSO, rowrec, rec, zz;
+    // Bias parts (b > 0, mi355gp_sparse_set_psi_lin_bias): the column sums c of the RBF part's psi1 (mp), of V (Dy),
+    // t = 2 rowsum(dL_dpsi2) (m), b t (m) and the RBF part's own psi2 (mp x mp: s->psi2 then holds the expression's) -- the
+    // context's buffers (biasC ...), kept between calls
+    double b = 0.0;
+    double *csum = nullptr, *vsum = nullptr, *tvec = nullptr, *addv = nullptr, *psi2rbf = nullptr;
 };
 
 static int psi_work_setup(mi355gp_sparse* s, const SPart& rbf, const double* Z, PsiWork* w) {
@@ -1417,6 +1433,8 @@ static int psi_work_setup(mi355gp_sparse* s, const SPart& rbf, const double* Z, 
 
 // Kmm, Lm, Xm as for certain inputs, on the main stream; pass 1 over chunks of PSI_CHUNK rows: psi1 chunk (in the Kfu buffer,
 // ld mp) -> psi1^T V, psi2 += the chunk's sum (fixed order); records ev[1]
+// With Bias parts (w.b > 0): psi1 = psi1_rbf + b, so psi1^T V gains b colsum(V) and psi2 gains b (c 1^T + 1 c^T) + N b^2 with
+// c = colsum(psi1_rbf), summed per chunk in chunk order; the Kfu buffer keeps the RBF part's psi1 alone
 static int uncertain_pass1(mi355gp_sparse* s, PsiWork& w, double extra_jitter) {
     hipStream_t st = s->st;
     const long n = s->n, m = s->m, mp = s->mp;
@@ -1434,8 +1452,19 @@ static int uncertain_pass1(mi355gp_sparse* s, PsiWork& w, double extra_jitter) {
         launch_psi1(st, w.rd1, w.lg1, w.dZp, rc, m, w.mpad, w.Qp, w.var, s->Kfu, mp);
         const int nsc = launch_colreduce_multi(st, s->Kfu, mp, rc, mp, s->dV + r0 * Dy, Dy, 1, Dy, 0, s->colPart);
         launch_sum_splits(st, s->colPart, mp * Dy, nsc, 1, s->psi1Y);                 // psi1^T V += psi1_chunk^T V_chunk
+        if (w.b > 0.0) {                                                              // c += the chunk's column sums of psi1
+            const int nso = launch_colreduce_multi(st, s->Kfu, mp, rc, mp, nullptr, 0, 0, 0, 1, s->colPart);
+            launch_sum_splits(st, s->colPart, mp, nso, nch > 0, w.csum);
+        }
         const int ns = launch_psi2(st, w.rd2, w.lg2, nullptr, w.dZp, w.dA, rc, m, w.Qp, w.var * w.var, w.ld2, s->psi2part);
         launch_psi2_combine(st, s->psi2part, w.ld2, m, ns, nch > 0, s->psi2, mp);
+    }
+    if (w.b > 0.0) {
+        HIP_CHECK(hipMemcpyAsync(w.psi2rbf, s->psi2, sizeof(double) * mp * mp, hipMemcpyDeviceToDevice, st));
+        launch_psi2_bias_add(st, s->psi2, mp, m, w.csum, w.b, (double)n * w.b * w.b);
+        const int nsv = launch_colreduce_multi(st, s->dV, Dy, n, Dy, nullptr, 0, 0, 0, 1, s->colPart);   // colsum(V), Dy numbers
+        launch_sum_splits(st, s->colPart, Dy, nsv, 0, w.vsum);
+        launch_psi1y_bias_add(st, s->psi1Y, m, Dy, w.vsum, w.b);
     }
     HIP_CHECK(hipEventRecord(s->ev[1], st));
     return 0;
@@ -1449,7 +1478,12 @@ static int uncertain_pass2(mi355gp_sparse* s, PsiWork& w, double beta) {
     const long n = s->n, m = s->m, mp = s->mp;
     const int D = s->D, Dy = s->Dy, Qp = w.Qp;
     hipLaunchKernelGGL(k_sym_scaled, grid2d(mp, mp), dim3(256), 0, st, s->Q2, mp, m, beta, s->E);
-    launch_psi2_zz(st, s->E, s->psi2, mp, w.dZp, m, Qp, w.zz);
+    launch_psi2_zz(st, s->E, w.b > 0.0 ? (const double*)w.psi2rbf : (const double*)s->psi2, mp, w.dZp, m, Qp, w.zz);
+    if (w.b > 0.0) {                                           // Bias parts: dL_dpsi1 of the RBF part gains b t^T, t = 2 rowsum(E)
+        launch_mm_colsums(st, s->E, mp, m, 2.0, w.tvec);
+        launch_mm_colsums(st, s->E, mp, m, 2.0 * w.b, w.addv);
+    }
+    const double* add = w.b > 0.0 ? w.addv : nullptr;
     std::vector<double> csum((size_t)(1 + Qp));
     int nch = 0;
     for (long r0 = 0; r0 < n; r0 += PSI_CHUNK, ++nch) {
@@ -1457,7 +1491,7 @@ static int uncertain_pass2(mi355gp_sparse* s, PsiWork& w, double beta) {
         const int nb = (int)((rc + PSI_GROWS - 1) / PSI_GROWS);
         launch_psi_rows(st, s->dX + r0 * D, s->dSvar + r0 * D, w.dA, rc, D, Qp, w.rd1, w.rd2, w.lg1, w.lg2);
         launch_psi1_grad(st, w.rd1, w.lg1, w.dZp, nullptr, 0, PsiRank{s->dY + r0 * Dy, s->vvec, Dy, beta}, rc, m, w.mpad, Qp, w.var,
-                         w.Ppart, w.Zpart);
+                         w.Ppart, w.Zpart, add);
         launch_sum_splits(st, w.Ppart, rc * w.RL, (int)w.mt, 0, w.P1s);
         launch_sum_splits(st, w.Zpart, w.mpad * Qp, nb, nch > 0, w.Zs1);
         launch_psi2_grad(st, w.rd2, w.lg2, nullptr, w.dZp, w.dA, s->E, mp, rc, m, w.mpad, Qp, w.var * w.var, w.Ppart, w.Zpart);
@@ -1472,15 +1506,39 @@ static int uncertain_pass2(mi355gp_sparse* s, PsiWork& w, double beta) {
     return 0;
 }
 
+// The expressions the uncertain-input entry points take, checked before any device work.  By default one RBF part and White
+// parts; on a context that was asked to (mi355gp_sparse_set_psi_lin_bias) ONE input-dependent part, RBF or Linear, with Bias
+// and White parts.  irbf_out: the index of that part.
 static int uncertain_check_parts(const mi355gp_sparse* s, int nparts, const mi355gp_part* parts, int64_t M, int* irbf_out,
                                  const char* where = "mi355gp_vardtc_inference_uncertain") {
     int irbf = -1;
+    if (s->take_psi_lin) {
+        for (int i = 0; i < nparts; ++i) {
+            if (parts[i].term != 0) PART_FAIL("%s: part %d is a factor of a product; products have no psi statistics here", where, i);
+            if (parts[i].kind == MI355GP_WHITE || parts[i].kind == MI355GP_BIAS) continue;
+            if (parts[i].kind != MI355GP_RBF && parts[i].kind != MI355GP_LINEAR)
+                PART_FAIL("%s: part %d is a %s (kind %d) part; uncertain inputs take one RBF or Linear part with Bias and White parts "
+                          "only", where, i, kind_name(parts[i].kind), parts[i].kind);
+            if (irbf >= 0)
+                PART_FAIL("%s: parts %d (%s) and %d (%s) are both input-dependent; uncertain inputs take ONE RBF or Linear part (psi2 "
+                          "of two has cross terms that need E[k1 k2^T]), with Bias and White parts", where, irbf,
+                          kind_name(parts[irbf].kind), i, kind_name(parts[i].kind));
+            irbf = i;
+        }
+        if (irbf < 0) PART_FAIL("%s: no RBF or Linear part; uncertain inputs take one RBF or Linear part with Bias and White parts", where);
+        if (s->D > PSI_QMAX) PART_FAIL("%s: the psi-statistics kernels take at most 64 input dimensions", where);
+        if (M > PSI_MMAX) PART_FAIL("%s: the psi-statistics kernels take at most 65535 inducing points", where);
+        *irbf_out = irbf;
+        return 0;
+    }
     for (int i = 0; i < nparts; ++i) {
         if (parts[i].term != 0) PART_FAIL("%s: part %d is a factor of a product; products have no psi statistics here", where, i);
         if (parts[i].kind == MI355GP_WHITE) continue;
         if (parts[i].kind != MI355GP_RBF)
-            PART_FAIL("%s: part %d is a %s (kind %d) part; uncertain inputs take one RBF part and White parts only", where, i,
-                      kind_name(parts[i].kind), parts[i].kind);
+            PART_FAIL("%s: part %d is a %s (kind %d) part; uncertain inputs take one RBF part and White parts only%s", where, i,
+                      kind_name(parts[i].kind), parts[i].kind,
+                      (parts[i].kind == MI355GP_BIAS || parts[i].kind == MI355GP_LINEAR)
+                          ? " (Bias and Linear: ask the context with mi355gp_sparse_set_psi_lin_bias)" : "");
         if (irbf >= 0) PART_FAIL("%s: parts %d and %d are both RBF; uncertain inputs take ONE RBF part (and White parts)", where, irbf, i);
         irbf = i;
     }
@@ -1488,6 +1546,105 @@ static int uncertain_check_parts(const mi355gp_sparse* s, int nparts, const mi35
     if (s->D > PSI_QMAX) PART_FAIL("%s: the psi-statistics kernels take at most 64 input dimensions", where);
     if (M > PSI_MMAX) PART_FAIL("%s: the psi-statistics kernels take at most 65535 inducing points", where);
     *irbf_out = irbf;
+    return 0;
+}
+
+// b = the sum of the Bias parts' variances of the call's expression (0: none)
+static double bias_sum(const mi355gp_sparse* s) {
+    double b = 0.0;
+    for (const SPart& p : s->parts)
+        if (p.kp.kind == MI355GP_BIAS) b += p.kp.variance;
+    return b;
+}
+
+struct LinDmuScope {           // sparse_rows_gradients writes row gradients only inside the call that asked for them
+    mi355gp_sparse* s;
+    ~LinDmuScope() { s->lin_dmu = nullptr; }
+};
+
+// The uncertain-input evaluation of an opened call whose input-dependent part is Linear (part ilin), with Bias (b) and White
+// parts.  The statistics are the certain-input ones at X = mu plus terms of size M or D:
+//   psi1 = K(mu, Z) of the expression,  psi2 = sum_n k_n k_n^T + Zv diag(s) Zv^T,  psi0_n = sum_q v_q (mu_nq^2 + S_nq) + b + w
+// (Zv = Z diag(v), s_q = sum_n S_nq), so the two passes are vardtc_pass1 / vardtc_pass2 over the resident means; on top of them
+// the rank-D term of psi2, the row gradient k_grad_rows_lin inside pass 2, and with E = beta sym(Q2), ze = diag(Z^T E Z):
+//   dS_nq = v_q^2 ze_q + dpsi0 v_q,  dZ += v^2 s (2 E Z),  dv_q += 2 v_q s_q ze_q + dpsi0 (sum_n mu_nq^2 + s_q)
+static int vardtc_uncertain_linear(mi355gp_sparse* s, int ilin, const double* Z, double beta, double extra_jitter,
+                                   double* out_scalars, double* dtheta_out, double* dZ_out, double* wv_out, double* dmu_out,
+                                   double* dS_out, double* stage_ms) {
+    hipStream_t st = s->st;
+    const long n = s->n, m = s->m, mp = s->mp;
+    const int D = s->D, Dy = s->Dy;
+    const double dpsi0 = -0.5 * Dy * beta;
+    s->mfma_prof.on = true;
+    s->mfma_prof.mask = 0x3u;
+    s->mfma_prof.reset();
+    const SPart& lin = s->parts[(size_t)ilin];
+    HIP_CHECK(s->linDmu.need((size_t)n * D));
+    HIP_CHECK(s->linEZ.need((size_t)m * D));
+    double *dMuO = s->linDmu, *dEZ = s->linEZ;
+    HIP_CHECK(s->diagPart.need((size_t)kdiag_blocks(n) * 2 * D));
+    HIP_CHECK(s->diagSums.need((size_t)2 * D));
+    if (int rc = sparse_start(s, Z, &beta, 1)) return rc;
+    launch_kdiag_var_sums(st, s->dX, s->dSvar, n, D, s->diagPart, s->diagSums);       // s_q and sum_n mu_nq^2
+    if (int rc = vardtc_pass1(s, false, 1e-8 + extra_jitter)) return rc;
+    launch_psi2_rank_add(st, s->dZ, lin.dIl, s->diagSums, m, D, s->psi2, mp);
+    if (int rc = sparse_mm_block(s, false, beta, 0)) return rc;
+    hipLaunchKernelGGL(k_sym_scaled, grid2d(mp, mp), dim3(256), 0, st, s->Q2, mp, m, beta, s->E);
+    launch_mm_times_z(st, s->E, mp, s->dZ, m, D, dEZ);
+    {
+        LinDmuScope scope{s};
+        s->lin_dmu = dMuO;
+        s->lin_c0 = 2.0 * dpsi0;
+        if (int rc = vardtc_pass2(s, false, false)) return rc;
+    }
+    sparse_kmm_gradients(s);
+    HIP_CHECK(hipEventRecord(s->ev[3], st));
+    // ---- small results to the host -----------------------------------------------------------------------------------------
+    KernGrads kg;
+    std::vector<double> ez((size_t)m * D), cs((size_t)2 * D), hz((size_t)m * D);
+    double scal[8];
+    if (int rc = sparse_fetch_gradients(s, true, &kg)) return rc;
+    HIP_CHECK(hipMemcpyAsync(ez.data(), dEZ, sizeof(double) * m * D, hipMemcpyDeviceToHost, st));
+    HIP_CHECK(hipMemcpyAsync(cs.data(), s->diagSums, sizeof(double) * 2 * D, hipMemcpyDeviceToHost, st));
+    HIP_CHECK(hipMemcpyAsync(hz.data(), s->dZ, sizeof(double) * m * D, hipMemcpyDeviceToHost, st));
+    HIP_CHECK(hipMemcpyAsync(scal, s->scal, sizeof(double) * 4, hipMemcpyDeviceToHost, st));
+    if (wv_out) HIP_CHECK(hipMemcpyAsync(wv_out, s->vvec, sizeof(double) * m * Dy, hipMemcpyDeviceToHost, st));
+    if (dmu_out) HIP_CHECK(hipMemcpyAsync(dmu_out, dMuO, sizeof(double) * n * D, hipMemcpyDeviceToHost, st));
+    if (int rc = sparse_finish(s, 3, stage_ms)) return rc;
+    std::vector<double> v((size_t)D), ze((size_t)D, 0.0);
+    double psi0sum = 0.0;
+    for (int q = 0; q < D; ++q) {
+        v[(size_t)q] = lin.inv_ls[(size_t)q] * lin.inv_ls[(size_t)q];
+        for (long j = 0; j < m; ++j) ze[(size_t)q] = fma(hz[(size_t)(j * D + q)], ez[(size_t)(j * D + q)], ze[(size_t)q]);
+        psi0sum = fma(v[(size_t)q], cs[(size_t)(D + q)] + cs[(size_t)q], psi0sum);
+    }
+    for (const SPart& p : s->parts)
+        if (!p.linear()) psi0sum += (double)n * p.kp.variance;           // Bias and White: their variance at every row
+    const double psi0[2] = {beta * psi0sum, beta * beta * psi0sum};
+    vardtc_scalars(s, scal, 0.0, beta, nullptr, out_scalars, psi0);
+    // update_gradients_expectations through psi0 (every part) and the rank-D term of psi2 (the Linear part), in theta order
+    for (const SPart& p : s->parts) {
+        const size_t o = kg.ddiag.size();
+        kg.ddiag.resize(o + p.theta.size(), 0.0);
+        double* g = kg.ddiag.data() + o;
+        if (!p.linear()) {
+            g[0] = dpsi0 * (double)n;
+            continue;
+        }
+        for (size_t a = 0; a < p.dims.size(); ++a) {
+            const size_t q = (size_t)p.dims[a];
+            g[p.kp.ard ? a : 0] += 2.0 * v[q] * cs[q] * ze[q] + dpsi0 * (cs[(size_t)D + q] + cs[q]);
+        }
+    }
+    sparse_assemble_gradients(s, kg, 0.0, dtheta_out, dZ_out);
+    if (dZ_out)
+        for (long j = 0; j < m; ++j)
+            for (int q = 0; q < D; ++q) dZ_out[j * D + q] += v[(size_t)q] * v[(size_t)q] * cs[(size_t)q] * 2.0 * ez[(size_t)(j * D + q)];
+    if (dS_out)
+        for (long i = 0; i < n; ++i)
+            for (int q = 0; q < D; ++q) dS_out[i * D + q] = fma(v[(size_t)q] * v[(size_t)q], ze[(size_t)q], dpsi0 * v[(size_t)q]);
+    s->have_result = true;
+    s->uncertain_result = true;
     return 0;
 }
 
@@ -1517,10 +1674,22 @@ int mi355gp_vardtc_inference_uncertain(mi355gp_sparse* s, int nparts, const mi35
     const int D = s->D, Dy = s->Dy;
     const double beta = 1.0 / fmax(noise[0], 1e-8);
     s->beta_scalar = beta;
+    if (s->parts[(size_t)irbf].linear())
+        return vardtc_uncertain_linear(s, irbf, Z, beta, extra_jitter, out_scalars, dtheta_out, dZ_out, wv_out, dmu_out, dS_out,
+                                       stage_ms);
     s->mfma_prof.on = false;
     const SPart& rbf = s->parts[(size_t)irbf];
     PsiWork w;
     if (int rc = psi_work_setup(s, rbf, Z, &w)) return rc;
+    w.b = bias_sum(s);
+    if (w.b > 0.0) {                                             // (a part's variance is positive: parse_part refuses any other)
+        HIP_CHECK(s->biasC.need((size_t)s->mp));
+        HIP_CHECK(s->biasV.need((size_t)s->Dy));
+        HIP_CHECK(s->biasT.need((size_t)s->m));
+        HIP_CHECK(s->biasAdd.need((size_t)s->m));
+        HIP_CHECK(s->biasPsi2.need((size_t)s->mp * s->mp));
+        w.csum = s->biasC, w.vsum = s->biasV, w.tvec = s->biasT, w.addv = s->biasAdd, w.psi2rbf = s->biasPsi2;
+    }
     if (int rc = sparse_start(s, Z, &beta, 1)) return rc;
     if (int rc = uncertain_pass1(s, w, extra_jitter)) return rc;
     if (int rc = sparse_mm_block(s, false, beta, 0)) return rc;
@@ -1531,8 +1700,16 @@ int mi355gp_vardtc_inference_uncertain(mi355gp_sparse* s, int nparts, const mi35
     const int Qp = w.Qp;
     KernGrads kg;
     std::vector<double> zs1((size_t)w.mpad * Qp), zs2((size_t)w.mpad * Qp), zzh((size_t)m * 2 * Qp);
+    std::vector<double> hc, ht, hvs, hwv;                          // Bias parts: c, t, colsum(V), the Woodbury vector
     double scal[8];
     if (int rc = sparse_fetch_gradients(s, false, &kg)) return rc;
+    if (w.b > 0.0) {
+        hc.resize((size_t)m), ht.resize((size_t)m), hvs.resize((size_t)Dy), hwv.resize((size_t)m * Dy);
+        HIP_CHECK(hipMemcpyAsync(hc.data(), w.csum, sizeof(double) * m, hipMemcpyDeviceToHost, st));
+        HIP_CHECK(hipMemcpyAsync(ht.data(), w.tvec, sizeof(double) * m, hipMemcpyDeviceToHost, st));
+        HIP_CHECK(hipMemcpyAsync(hvs.data(), w.vsum, sizeof(double) * Dy, hipMemcpyDeviceToHost, st));
+        HIP_CHECK(hipMemcpyAsync(hwv.data(), s->vvec, sizeof(double) * m * Dy, hipMemcpyDeviceToHost, st));
+    }
     HIP_CHECK(hipMemcpyAsync(zs1.data(), w.Zs1, sizeof(double) * zs1.size(), hipMemcpyDeviceToHost, st));
     HIP_CHECK(hipMemcpyAsync(zs2.data(), w.Zs2, sizeof(double) * zs2.size(), hipMemcpyDeviceToHost, st));
     HIP_CHECK(hipMemcpyAsync(zzh.data(), w.zz, sizeof(double) * zzh.size(), hipMemcpyDeviceToHost, st));
@@ -1553,6 +1730,23 @@ int mi355gp_vardtc_inference_uncertain(mi355gp_sparse* s, int nparts, const mi35
         const double lq = w.sums[(size_t)(1 + q)] + 0.5 * w.ha[(size_t)q] * zq;
         ab[(size_t)(q / 32) * GP_STRIDE + 2 + (q % 32)] -= lq;
         ab[1] -= lq;
+    }
+    if (w.b > 0.0) {
+        // every Bias part, on top of Kmm's record and of N dL_dpsi0 below: sum dL_dpsi1 + t . c + 2 N b sum(E)   (static.py:165-
+        // 172 with add.py's cross terms; sum dL_dpsi1 = colsum(V) . colsum(v)); the record is divided by the variance later
+        double s1 = 0.0, tc = 0.0, ts = 0.0;
+        for (int d = 0; d < Dy; ++d) {
+            double cv = 0.0;
+            for (long j = 0; j < m; ++j) cv += hwv[(size_t)(j * Dy + d)];
+            s1 = fma(hvs[(size_t)d], cv, s1);
+        }
+        for (long j = 0; j < m; ++j) {
+            tc = fma(ht[(size_t)j], hc[(size_t)j], tc);
+            ts += ht[(size_t)j];
+        }
+        const double extra = s1 + tc + (double)s->n * w.b * ts;        // (sum(E) = sum(t) / 2)
+        for (size_t i = 0; i < s->parts.size(); ++i)
+            if (s->parts[i].kp.kind == MI355GP_BIAS) kg.gmm[i * rec_doubles(s)] += extra * s->parts[i].kp.variance;
     }
     // dL_dpsi0 = -Dy beta / 2 per row, dpsi0 / dvariance = 1
     sparse_assemble_gradients(s, kg, -0.5 * Dy * beta * (double)n, dtheta_out, dZ_out);
@@ -1672,6 +1866,57 @@ int mi355gp_sparse_predict(mi355gp_sparse* s, int nparts, const mi355gp_part* pa
     return 0;
 }
 
+// Prediction at uncertain points for a Linear part (ilin) with Bias and White parts.  psi1* is the expression's K(mu*, Z) and the
+// psi1 psi1^T half of psi2n contracts to (k lam_d)^2 - k W k^T, so with Zv = Z diag(v)
+//   var[n][d] = Kdiag(mu*_n) - k_n W k_n^T + sum_q S*_nq [ v_q + (Zv^T lam_d)_q^2 - diag(Zv^T W Zv)_q ],  clipped at 1e-15:
+// the certain-input prediction at the means plus a D-vector dot per row (k_lin_predvar); no psi2n is formed.
+static int predict_uncertain_linear(mi355gp_sparse* s, int ilin, const double* mu_new, const double* S_new, int64_t Mn,
+                                    double* mean_out, double* var_out) {
+    hipStream_t st = s->st;
+    const long m = s->m, mp = s->mp;
+    const int D = s->D, Dy = s->Dy;
+    const SPart& lin = s->parts[(size_t)ilin];
+    HIP_CHECK(hipEventRecord(s->ev[4], st));
+    NewPoints q;
+    if (int rc = sparse_newpoints(s, mu_new, Mn, false, s->vvec, Dy, "mi355gp_sparse_predict_uncertain", &q)) return rc;
+    HIP_CHECK(hipMemcpyAsync(mean_out, q.Mu, sizeof(double) * Mn * Dy, hipMemcpyDeviceToHost, st));
+    DevBuf dWZ, dS, dG, dVar;
+    if (var_out) {
+        if (int rc = sparse_newpoints_var(s, &q, s->Winv, false, false)) return rc;
+        std::vector<double> wz((size_t)m * D), hz((size_t)m * D), lam((size_t)m * Dy), g((size_t)Dy * D);
+        HIP_CHECK(dWZ.alloc(m * D));
+        launch_mm_times_z(st, s->Winv, mp, s->dZ, m, D, dWZ);
+        HIP_CHECK(hipMemcpyAsync(wz.data(), dWZ, sizeof(double) * m * D, hipMemcpyDeviceToHost, st));
+        HIP_CHECK(hipMemcpyAsync(hz.data(), s->dZ, sizeof(double) * m * D, hipMemcpyDeviceToHost, st));
+        HIP_CHECK(hipMemcpyAsync(lam.data(), s->vvec, sizeof(double) * m * Dy, hipMemcpyDeviceToHost, st));
+        HIP_CHECK(hipStreamSynchronize(st));
+        for (int c = 0; c < D; ++c) {
+            const double v = lin.inv_ls[(size_t)c] * lin.inv_ls[(size_t)c];
+            double zwz = 0.0;
+            for (long j = 0; j < m; ++j) zwz = fma(hz[(size_t)(j * D + c)], wz[(size_t)(j * D + c)], zwz);
+            for (int d = 0; d < Dy; ++d) {
+                double zl = 0.0;
+                for (long j = 0; j < m; ++j) zl = fma(hz[(size_t)(j * D + c)], lam[(size_t)(j * Dy + d)], zl);
+                g[(size_t)(d * D + c)] = v + v * v * (zl * zl - zwz);
+            }
+        }
+        HIP_CHECK(dS.alloc(Mn * D));
+        HIP_CHECK(dG.alloc(Dy * D));
+        HIP_CHECK(dVar.alloc(Mn * Dy));
+        HIP_CHECK(hipMemcpyAsync(dS, S_new, sizeof(double) * Mn * D, hipMemcpyHostToDevice, st));
+        HIP_CHECK(hipMemcpyAsync(dG, g.data(), sizeof(double) * Dy * D, hipMemcpyHostToDevice, st));
+        launch_lin_predvar(st, q.var, dS, dG, Mn, D, Dy, dVar);
+        HIP_CHECK(hipMemcpyAsync(var_out, dVar, sizeof(double) * Mn * Dy, hipMemcpyDeviceToHost, st));
+    }
+    HIP_CHECK(hipEventRecord(s->ev[5], st));
+    HIP_CHECK(hipStreamSynchronize(st));
+    HIP_CHECK(hipGetLastError());
+    float ms = 0.0f;
+    HIP_CHECK(hipEventElapsedTime(&ms, s->ev[4], s->ev[5]));
+    s->predict_ms = ms;
+    return 0;
+}
+
 // Prediction at UNCERTAIN new points q(x*) = N(mu_new, diag S_new) (Posterior._raw_predict with a VariationalPosterior,
 // posterior.py:249-269, full_cov = False) for the kernel of the last VarDTC call, one RBF part alone or with White parts
 // (White adds to psi0* only: its psi1 / psi2 are zero, static.py):
@@ -1698,9 +1943,38 @@ int mi355gp_sparse_predict_uncertain(mi355gp_sparse* s, int nparts, const mi355g
     hipStream_t st = s->st;
     scale_for_parts(s, s->dZ, s->m, s->mp, true);
     if (int rc = ensure_winv(s)) return rc;
+    if (s->parts[(size_t)irbf].linear()) return predict_uncertain_linear(s, irbf, mu_new, S_new, Mn, mean_out, var_out);
     const long m = s->m, mp = s->mp, mpad = round_up(m, PSI_KT), chunk = Mn < PSI_CHUNK ? Mn : PSI_CHUNK;
     const int Qp = psi_qp(D);
     const SPart& rbf = s->parts[(size_t)irbf];
+    // Bias parts (b > 0): psi1 = psi1_rbf + b and psi2n = psi2n_rbf + b (psi1_n 1^T + 1 psi1_n^T) + b^2, so with A_d = lam_d lam_d^T - W
+    //   mean += b sum(lam_d),   C[n][d] += 2 b psi1_n . (A_d 1) + b^2 1^T A_d 1,   A_d 1 = lam_d sum(lam_d) - W 1
+    // -- u = 2 b (A_d 1) (m x Dy) and the two Dy-vectors are formed once on the host from lam and the row sums of W
+    const double bsum = bias_sum(s);
+    DevBuf dW1, dU, dCst, dBsl;
+    if (bsum > 0.0) {
+        std::vector<double> lam((size_t)m * Dy), w1((size_t)m), u((size_t)m * Dy), cst((size_t)Dy), bsl((size_t)Dy);
+        HIP_CHECK(dW1.alloc(m));
+        launch_mm_colsums(st, s->Winv, mp, m, 1.0, dW1);
+        HIP_CHECK(hipMemcpyAsync(w1.data(), dW1, sizeof(double) * m, hipMemcpyDeviceToHost, st));
+        HIP_CHECK(hipMemcpyAsync(lam.data(), s->vvec, sizeof(double) * m * Dy, hipMemcpyDeviceToHost, st));
+        HIP_CHECK(hipStreamSynchronize(st));
+        double sw = 0.0;
+        for (long j = 0; j < m; ++j) sw += w1[(size_t)j];
+        for (int d = 0; d < Dy; ++d) {
+            double sl = 0.0;
+            for (long j = 0; j < m; ++j) sl += lam[(size_t)(j * Dy + d)];
+            for (long j = 0; j < m; ++j) u[(size_t)(j * Dy + d)] = 2.0 * bsum * (lam[(size_t)(j * Dy + d)] * sl - w1[(size_t)j]);
+            cst[(size_t)d] = bsum * bsum * (sl * sl - sw);
+            bsl[(size_t)d] = bsum * sl;
+        }
+        HIP_CHECK(dU.alloc(m * Dy));
+        HIP_CHECK(dCst.alloc(Dy));
+        HIP_CHECK(dBsl.alloc(Dy));
+        HIP_CHECK(hipMemcpy(dU, u.data(), sizeof(double) * m * Dy, hipMemcpyHostToDevice));
+        HIP_CHECK(hipMemcpy(dCst, cst.data(), sizeof(double) * Dy, hipMemcpyHostToDevice));
+        HIP_CHECK(hipMemcpy(dBsl, bsl.data(), sizeof(double) * Dy, hipMemcpyHostToDevice));
+    }
     const double var = rbf.kp.variance, psi0 = expression_kdiag(s->parts, s->terms);
     std::vector<double> ha((size_t)Qp, 0.0), hz((size_t)m * D), hzp((size_t)mpad * Qp, 0.0);
     HIP_CHECK(hipMemcpyAsync(hz.data(), s->dZ, sizeof(double) * m * D, hipMemcpyDeviceToHost, st));
@@ -1736,10 +2010,15 @@ int mi355gp_sparse_predict_uncertain(mi355gp_sparse* s, int nparts, const mi355g
         launch_psi_rows(st, dMu, dS, dA, rc, D, Qp, rd1, rd2, lg1, lg2);
         launch_psi1(st, rd1, lg1, dZp, rc, m, mpad, Qp, var, psi1, m);
         launch_rowdots(st, psi1, psi1, m, rc, m, s->vvec, Dy, mean, nullptr);
-        HIP_CHECK(hipMemcpyAsync(mean_out + r0 * Dy, mean, sizeof(double) * rc * Dy, hipMemcpyDeviceToHost, st));
+        if (bsum > 0.0 && !var_out) launch_psi_bias_pred(st, psi1, m, dU, dCst, dBsl, rc, m, Dy, nullptr, mean);
+        if (!(bsum > 0.0 && var_out)) HIP_CHECK(hipMemcpyAsync(mean_out + r0 * Dy, mean, sizeof(double) * rc * Dy, hipMemcpyDeviceToHost, st));
         if (var_out) {
             const int ns = launch_psi2n_contract(st, rd2, lg2, dZp, dA, s->vvec, Dy, s->Winv, mp, rc, m, Qp, var * var, part);
             launch_sum_splits(st, part, rc * NC, ns, 0, C);
+            if (bsum > 0.0) {
+                launch_psi_bias_pred(st, psi1, m, dU, dCst, dBsl, rc, m, Dy, C, mean);
+                HIP_CHECK(hipMemcpyAsync(mean_out + r0 * Dy, mean, sizeof(double) * rc * Dy, hipMemcpyDeviceToHost, st));
+            }
             launch_psi_predvar(st, C, mean, psi0, rc, Dy, vout);
             HIP_CHECK(hipMemcpyAsync(var_out + r0 * Dy, vout, sizeof(double) * rc * Dy, hipMemcpyDeviceToHost, st));
         }
@@ -1758,6 +2037,15 @@ int mi355gp_sparse_predict_uncertain(mi355gp_sparse* s, int nparts, const mi355g
 int mi355gp_sparse_set_linear(mi355gp_sparse* s, int on) {
     ARG_CHECK(s, "mi355gp_sparse_set_linear: NULL context");
     s->take_linear = on != 0;
+    return 0;
+}
+
+// Whether the uncertain-input entry points of this context take one RBF or Linear part with Bias and White parts
+// (include/mi355gp_psi_lin.h); on also switches Linear on (prediction at certain points needs it), off leaves that as it is
+int mi355gp_sparse_set_psi_lin_bias(mi355gp_sparse* s, int on) {
+    ARG_CHECK(s, "mi355gp_sparse_set_psi_lin_bias: NULL context");
+    s->take_psi_lin = on != 0;
+    if (on) s->take_linear = true;
     return 0;
 }
 

@@ -91,6 +91,18 @@ struct mi355gp_sparse {
     // number expression_kdiag() and no code below looks at these members.
     bool diag_pt = false;
     bool take_linear = false;     // mi355gp_sparse_set_linear: the entry points take Linear parts (off: refused by name, as before)
+    // mi355gp_sparse_set_psi_lin_bias: the uncertain-input entry points take one RBF or Linear part with Bias and White parts
+    // (off: Bias and Linear are refused there by name, as before).  lin_dmu (device, n x D; NULL outside such a call): where
+    // sparse_rows_gradients leaves a Linear part's gradient in the rows of the chunk that starts at lin_row0, with
+    // lin_c0 = 2 dL_dpsi0 on the rows' own diagonal term (k_grad_rows_lin)
+    bool take_psi_lin = false;
+    double* lin_dmu = nullptr;
+    long lin_row0 = 0;
+    double lin_c0 = 0.0;
+    // ... and what those calls keep between evaluations, so that an optimiser step allocates nothing: the Linear part's row
+    // gradient (n x D) and E Z (m x D); for Bias parts next to an RBF part the psi1 column sums c (mp), colsum(V) (Dy),
+    // t = 2 rowsum(dL_dpsi2) and b t (m each) and the RBF part's own psi2 (mp x mp)
+    GrowBuf linDmu, linEZ, biasC, biasV, biasT, biasAdd, biasPsi2;
     DiagDesc diag;
     GrowBuf diagCoef, dKd, diagW, diagPart, diagSums;   // nparts x D coefficients; Kdiag(X) (n); a family's weights (n); records
 };

@@ -751,6 +751,67 @@ class Linear(Kern):
         """(reference `linear.py:151-152`)"""
         return np.ones(self.input_dim) * self._theta()
 
+    # ---- psi-statistics for Gaussian inputs qX = NormalPosterior (reference `linear.py:158-181`, `psi_comp/linear_psi_comp.py`):
+    # plain NumPy on the host, the yardstick and the fallback of the device path (`psi_lin_bias=True` on the inference classes).
+    # With v_q the variances, s_q = sum_n S_nq:  psi0_n = sum_q v_q (mu_nq^2 + S_nq),  psi1 = (mu v) Z^T,
+    # psi2_n = psi1_n psi1_n^T + Z diag(v^2 S_n) Z^T
+    def _psi_operands(self, Z, qX):
+        v = self._theta() * np.ones(self.input_dim)
+        return v, self._slice_X(Z), self._slice_X(qX.mean), self._slice_X(qX.variance)
+
+    def psi0(self, Z, qX):
+        v, _, mu, S = self._psi_operands(Z, qX)
+        return np.sum(v * (np.square(mu) + S), 1)
+
+    def psi1(self, Z, qX):
+        v, Zs, mu, _ = self._psi_operands(Z, qX)
+        return np.dot(mu * v, Zs.T)
+
+    def psi2(self, Z, qX):
+        v, Zs, mu, S = self._psi_operands(Z, qX)
+        p1 = np.dot(mu * v, Zs.T)
+        return np.dot(p1.T, p1) + np.dot(Zs * (v * v * S.sum(0)), Zs.T)
+
+    def psi2n(self, Z, qX):
+        v, Zs, mu, S = self._psi_operands(Z, qX)
+        p1 = np.dot(mu * v, Zs.T)
+        return p1[:, :, None] * p1[:, None, :] + np.einsum("mq,nq,oq->nmo", Zs, v * v * S, Zs)
+
+    def _psi_grad(self, dL_dpsi0, dL_dpsi1, dL_dpsi2, Z, qX):
+        """(dvariances per dimension, dZ, dmu, dS), the last three over the active columns"""
+        if np.ndim(dL_dpsi2) != 2:
+            raise NotImplementedError("Linear psi gradients take dL_dpsi2 as M x M (the summed psi2), not per data point")
+        v, Zs, mu, S = self._psi_operands(Z, qX)
+        d0, d1 = np.asarray(dL_dpsi0, dtype=float).ravel(), np.asarray(dL_dpsi1, dtype=float)
+        E2 = np.asarray(dL_dpsi2, dtype=float)
+        E2 = E2 + E2.T
+        T = d1 + np.dot(np.dot(mu * v, Zs.T), E2)              # dL / d psi1, the psi1 psi1^T half of psi2 included
+        TZ, EZ, s = np.dot(T, Zs), np.dot(E2, Zs), S.sum(0)
+        ze = 0.5 * np.sum(Zs * EZ, 0)                          # diag(Z^T dL_dpsi2 Z)
+        dv = np.dot(d0, np.square(mu) + S) + np.sum(mu * TZ, 0) + 2. * v * s * ze
+        dZ = np.dot(T.T, mu * v) + v * v * s * EZ
+        dmu = TZ * v + 2. * d0[:, None] * v * mu
+        dS = v * v * ze + d0[:, None] * v
+        return dv, dZ, dmu, dS
+
+    def _scatter(self, g, like):
+        if g.shape == np.shape(like):
+            return g
+        full = np.zeros(np.shape(like))
+        full[:, self.active_dims] = g
+        return full
+
+    def update_gradients_expectations(self, dL_dpsi0, dL_dpsi1, dL_dpsi2, Z, qX):
+        dv = self._psi_grad(dL_dpsi0, dL_dpsi1, dL_dpsi2, Z, qX)[0]
+        self.variances.gradient = dv.copy() if self.ARD else np.atleast_1d(dv.sum())
+
+    def gradients_Z_expectations(self, dL_dpsi0, dL_dpsi1, dL_dpsi2, Z, qX):
+        return self._scatter(self._psi_grad(dL_dpsi0, dL_dpsi1, dL_dpsi2, Z, qX)[1], Z)
+
+    def gradients_qX_expectations(self, dL_dpsi0, dL_dpsi1, dL_dpsi2, Z, qX):
+        g = self._psi_grad(dL_dpsi0, dL_dpsi1, dL_dpsi2, Z, qX)
+        return self._scatter(g[2], qX.mean), self._scatter(g[3], qX.mean)
+
     def to_dict(self):
         """(reference `linear.py:54-59`)"""
         d = super(Linear, self).to_dict()
@@ -1021,6 +1082,31 @@ class Bias(Static):
     def update_gradients_full(self, dL_dK, X, X2=None):
         self.variance.gradient = np.sum(np.asarray(dL_dK))
 
+    # psi-statistics (reference `static.py:133-189`): psi0 = psi1 = variance, psi2_n = variance^2
+    def psi0(self, Z, qX):
+        return np.full(qX.mean.shape[0], float(self.variance.values[0]))
+
+    def psi1(self, Z, qX):
+        return np.full((qX.mean.shape[0], np.asarray(Z).shape[0]), float(self.variance.values[0]))
+
+    def psi2(self, Z, qX):
+        return np.full((np.asarray(Z).shape[0],) * 2, float(self.variance.values[0]) ** 2 * qX.mean.shape[0])
+
+    def psi2n(self, Z, qX):
+        return np.full((qX.mean.shape[0],) + (np.asarray(Z).shape[0],) * 2, float(self.variance.values[0]) ** 2)
+
+    def update_gradients_expectations(self, dL_dpsi0, dL_dpsi1, dL_dpsi2, Z, qX):
+        if np.ndim(dL_dpsi2) != 2:
+            raise NotImplementedError("Bias psi gradients take dL_dpsi2 as M x M (the summed psi2), not per data point")
+        self.variance.gradient = (np.sum(dL_dpsi0) + np.sum(dL_dpsi1)
+                                  + 2. * float(self.variance.values[0]) * np.sum(dL_dpsi2) * qX.mean.shape[0])
+
+    def gradients_Z_expectations(self, dL_dpsi0, dL_dpsi1, dL_dpsi2, Z, qX):
+        return np.zeros(np.asarray(Z).shape)
+
+    def gradients_qX_expectations(self, dL_dpsi0, dL_dpsi1, dL_dpsi2, Z, qX):
+        return np.zeros(qX.mean.shape), np.zeros(qX.mean.shape)
+
 
 class CombinationKernel(Kern):
     """Common part of `Add` and `Prod` (reference `GPy/kern/src/kern.py:363-451`): owns the parts, spans their input
@@ -1121,39 +1207,97 @@ class Add(CombinationKernel):
     def gradients_X_diag(self, dL_dKdiag, X):                                    # add.py:102-105
         return sum(p.gradients_X_diag(dL_dKdiag, X) for p in self.parts)
 
-    # ---- psi-statistics (reference `add.py:107-246`): one RBF part and White parts only.  White's psi1 is zero, so the cross
-    # terms of psi2 vanish and every part sees the same dL_dpsi0/1/2.
-    def _psi_parts(self):
+    # ---- psi-statistics (reference `add.py:107-266`).  By default one RBF part and White parts only: White's psi1 is zero, so
+    # the cross terms of psi2 vanish and every part sees the same dL_dpsi0/1/2.  `psi_lin_bias=True`: one input-dependent part,
+    # RBF or Linear, with any number of Bias and White parts; Bias (b = the sum of their variances) crosses with the psi1 of
+    # the input-dependent part:  psi2_n += b (psi1_n 1^T + 1 psi1_n^T) + b^2, and every part sees dL_dpsi1 plus the OTHER
+    # parts' psi1 times (dL_dpsi2 + dL_dpsi2^T).  Two input-dependent parts stay refused (their cross term needs E[k1 k2^T]).
+    def _psi_parts(self, psi_lin_bias=False):
+        how = "; Linear and Bias parts: pass psi_lin_bias=True"
+        if psi_lin_bias:
+            for p in self.parts:
+                if type(p) not in (RBF, Linear, Bias, White):
+                    what = type(p).__name__ if p.is_leaf else "%s of %s" % (type(p).__name__, ", ".join(type(f).__name__ for f in p.leaves()))
+                    raise NotImplementedError("psi-statistics of a sum cover one RBF or Linear part with Bias and White parts; "
+                                              "part %r is a %s" % (p.name, what))
+            dep = [p for p in self.parts if isinstance(p, (RBF, Linear))]
+            if len(dep) != 1:
+                raise NotImplementedError("psi-statistics of a sum cover ONE input-dependent part (RBF or Linear; psi2 of two has "
+                                          "cross terms that need E[k1 k2^T]), got %d (%s)"
+                                          % (len(dep), ", ".join("%r: %s" % (p.name, type(p).__name__) for p in dep)))
+            return self.parts
         for p in self.parts:
             if not isinstance(p, (RBF, White)):
-                raise NotImplementedError("psi-statistics of a sum cover one RBF part and White parts; part %r is a %s"
-                                          % (p.name, type(p).__name__))
+                raise NotImplementedError("psi-statistics of a sum cover one RBF part and White parts; part %r is a %s%s"
+                                          % (p.name, type(p).__name__, how))
         if sum(isinstance(p, RBF) for p in self.parts) > 1:
             raise NotImplementedError("psi-statistics of a sum cover ONE RBF part (psi2 of two has cross terms); part %r is "
                                       "a second RBF" % [p.name for p in self.parts if isinstance(p, RBF)][1])
         return self.parts
 
-    def psi0(self, Z, qX):
-        return sum(p.psi0(Z, qX) for p in self._psi_parts())
+    def _bias_sum(self):
+        return float(sum(float(p.variance.values[0]) for p in self.parts if isinstance(p, Bias)))
 
-    def psi1(self, Z, qX):
-        return sum(p.psi1(Z, qX) for p in self._psi_parts())
+    def _dep_part(self):
+        return [p for p in self.parts if isinstance(p, (RBF, Linear))][0]
 
-    def psi2(self, Z, qX):
-        return sum(p.psi2(Z, qX) for p in self._psi_parts())
+    def psi0(self, Z, qX, psi_lin_bias=False):
+        return sum(p.psi0(Z, qX) for p in self._psi_parts(psi_lin_bias))
 
-    def psi2n(self, Z, qX):
-        return sum(p.psi2n(Z, qX) for p in self._psi_parts())
+    def psi1(self, Z, qX, psi_lin_bias=False):
+        return sum(p.psi1(Z, qX) for p in self._psi_parts(psi_lin_bias))
 
-    def update_gradients_expectations(self, dL_dpsi0, dL_dpsi1, dL_dpsi2, Z, qX):
-        for p in self._psi_parts():
-            p.update_gradients_expectations(dL_dpsi0, dL_dpsi1, dL_dpsi2, Z, qX)
+    def psi2(self, Z, qX, psi_lin_bias=False):
+        out = sum(p.psi2(Z, qX) for p in self._psi_parts(psi_lin_bias))
+        b = self._bias_sum() if psi_lin_bias else 0.0
+        if b != 0.0:                                      # the pairs of Bias parts, and Bias against the input-dependent part
+            c = self._dep_part().psi1(Z, qX).sum(0)
+            n = qX.mean.shape[0]
+            out = out + b * (c[:, None] + c[None, :]) + n * (b * b - sum(float(p.variance.values[0]) ** 2 for p in self.parts
+                                                                         if isinstance(p, Bias)))
+        return out
 
-    def gradients_Z_expectations(self, dL_dpsi0, dL_dpsi1, dL_dpsi2, Z, qX):
-        return sum(p.gradients_Z_expectations(dL_dpsi0, dL_dpsi1, dL_dpsi2, Z, qX) for p in self._psi_parts())
+    def psi2n(self, Z, qX, psi_lin_bias=False):
+        out = sum(p.psi2n(Z, qX) for p in self._psi_parts(psi_lin_bias))
+        b = self._bias_sum() if psi_lin_bias else 0.0
+        if b != 0.0:
+            p1 = self._dep_part().psi1(Z, qX)
+            out = out + b * (p1[:, :, None] + p1[:, None, :]) + (b * b - sum(float(p.variance.values[0]) ** 2 for p in self.parts
+                                                                            if isinstance(p, Bias)))
+        return out
 
-    def gradients_qX_expectations(self, dL_dpsi0, dL_dpsi1, dL_dpsi2, Z, qX):
-        gs = [p.gradients_qX_expectations(dL_dpsi0, dL_dpsi1, dL_dpsi2, Z, qX) for p in self._psi_parts()]
+    def _psi1_eff(self, parts, dL_dpsi1, dL_dpsi2, Z, qX):
+        """per part: dL_dpsi1 + (the other parts' psi1) (dL_dpsi2 + dL_dpsi2^T) (reference `add.py:147-266`)"""
+        if not any(isinstance(p, Bias) for p in parts):
+            return [dL_dpsi1] * len(parts)
+        if np.ndim(dL_dpsi2) != 2:
+            raise NotImplementedError("psi gradients of a sum take dL_dpsi2 as M x M (the summed psi2), not per data point")
+        E2 = np.asarray(dL_dpsi2, dtype=float)
+        E2 = E2 + E2.T
+        p1 = [None if isinstance(p, White) else p.psi1(Z, qX) for p in parts]
+        out = []
+        for i, p in enumerate(parts):
+            if isinstance(p, White):
+                out.append(dL_dpsi1)
+                continue
+            others = [p1[j] for j in range(len(parts)) if j != i and p1[j] is not None]
+            out.append(np.asarray(dL_dpsi1) + np.dot(sum(others), E2) if others else dL_dpsi1)
+        return out
+
+    def update_gradients_expectations(self, dL_dpsi0, dL_dpsi1, dL_dpsi2, Z, qX, psi_lin_bias=False):
+        parts = self._psi_parts(psi_lin_bias)
+        for p, d1 in zip(parts, self._psi1_eff(parts, dL_dpsi1, dL_dpsi2, Z, qX)):
+            p.update_gradients_expectations(dL_dpsi0, d1, dL_dpsi2, Z, qX)
+
+    def gradients_Z_expectations(self, dL_dpsi0, dL_dpsi1, dL_dpsi2, Z, qX, psi_lin_bias=False):
+        parts = self._psi_parts(psi_lin_bias)
+        return sum(p.gradients_Z_expectations(dL_dpsi0, d1, dL_dpsi2, Z, qX)
+                   for p, d1 in zip(parts, self._psi1_eff(parts, dL_dpsi1, dL_dpsi2, Z, qX)))
+
+    def gradients_qX_expectations(self, dL_dpsi0, dL_dpsi1, dL_dpsi2, Z, qX, psi_lin_bias=False):
+        parts = self._psi_parts(psi_lin_bias)
+        gs = [p.gradients_qX_expectations(dL_dpsi0, d1, dL_dpsi2, Z, qX)
+              for p, d1 in zip(parts, self._psi1_eff(parts, dL_dpsi1, dL_dpsi2, Z, qX))]
         return sum(g[0] for g in gs), sum(g[1] for g in gs)
 
 

@@ -15,6 +15,8 @@ Uncertain inputs: an X that is a `NormalPosterior` (or `SparseGPRegression(X, Y,
 RBF psi-statistics on the device (`mi355gp_vardtc_inference_uncertain`) for one RBF kernel alone or summed with White parts
 and one noise variance; `grad_dict` then has the reference's keys `dL_dpsi0 / dL_dpsi1 / dL_dpsi2` in place of
 `dL_dKdiag / dL_dKnm`, and `fused` also carries the gradients with respect to the inputs' means and variances.
+`VarDTC(psi_lin_bias=True)` (and the models' keyword of the same name) takes one RBF or Linear part with Bias and White parts
+there (`mi355gp_sparse_set_psi_lin_bias`, include/mi355gp_psi_lin.h); made without it the classes refuse those as before.
 
 `BayesianGPLVM` (reference `models/bayesian_gplvm.py`) is the `SparseGP` whose inputs are parameters: it consumes those
 gradients, subtracts the KL term of the standard normal prior, uploads a step's new means and variances without Y
@@ -24,7 +26,7 @@ import numpy as np
 
 from . import _lib
 from .inference import LatentFunctionInference
-from .kern import RBF, Add, Prod, White, diag_depends_on_point, exact_only_leaves, sparse_refused_leaves
+from .kern import RBF, Add, Bias, Linear, Prod, White, diag_depends_on_point, exact_only_leaves, sparse_refused_leaves
 from .lazy import ArrayIdentity, LazyMM, LazyNM, LazyPsi1, freeze, kernel_signature
 from .likelihoods import Gaussian
 from .linalg import LinAlgError, jitter_ladder
@@ -49,6 +51,8 @@ class SparsePosterior(SessionPosterior):
     """`Posterior(woodbury_inv, woodbury_vector, K=Kmm, K_chol=Lm)` of the reference (`var_dtc.py:213`,
     `posterior.py:21-77`); prediction follows `Posterior._raw_predict` (`posterior.py:198-262`) and runs on the device
     (C-ABI `mi355gp_sparse_predict`) while the posterior is the context's latest result."""
+
+    psi_lin_bias = False        # made by an inference class with psi_lin_bias=True: the host fallback asks `Add` for the same
 
     def __init__(self, woodbury_inv, woodbury_vector, K, K_chol, device=None):
         self.woodbury_inv, self.woodbury_vector, self.K, self.K_chol = woodbury_inv, woodbury_vector, K, K_chol
@@ -89,9 +93,10 @@ class SparsePosterior(SessionPosterior):
         M, n = la.shape[0], Xnew.shape[0]
         step = max(1, (1 << 22) // (M * M))                          # at most 32 MB of psi2n at a time
         mu, var = np.empty((n, la.shape[1])), np.empty((n, la.shape[1]))
+        kw = {"psi_lin_bias": True} if self.psi_lin_bias and isinstance(kern, Add) else {}
         for r0 in range(0, n, step):
             q = Xnew[r0:r0 + step]
-            psi0, psi1, psi2n = kern.psi0(pred_var, q), kern.psi1(pred_var, q), kern.psi2n(pred_var, q)
+            psi0, psi1, psi2n = kern.psi0(pred_var, q, **kw), kern.psi1(pred_var, q, **kw), kern.psi2n(pred_var, q, **kw)
             mb = np.dot(psi1, la)
             vb = np.einsum("nmo,md,od->nd", psi2n, la, la) - mb * mb + psi0[:, None] - np.einsum("nmo,mo->n", psi2n, Wi)[:, None]
             mu[r0:r0 + step], var[r0:r0 + step] = mb, np.clip(vb, 1e-15, np.inf)
@@ -155,9 +160,11 @@ class SparseSession(LatentFunctionInference):
     `_ensure`, one `_run` over a context call and the results built by `_posterior` / `_device_dict`."""
     _device_members = ("_ctx", "_X", "_Y")
 
-    def __init__(self, device=0, maxtries=5, linear=False):
+    def __init__(self, device=0, maxtries=5, linear=False, psi_lin_bias=False):
         self.device, self.maxtries = device, maxtries
-        self.linear = bool(linear)       # take Linear leaves (Kdiag by point on the device); off: refused by name, as before
+        # psi_lin_bias: uncertain inputs take one RBF or Linear part with Bias and White parts (`VarDTC`); implies `linear`
+        self.psi_lin_bias = bool(psi_lin_bias)
+        self.linear = bool(linear) or self.psi_lin_bias   # take Linear leaves (Kdiag by point on the device); off: refused by name, as before
         self._ctx = None
         self._X = self._Y = None
         self._token = 0
@@ -173,7 +180,9 @@ class SparseSession(LatentFunctionInference):
         recognised by identity, anything else by a full comparison"""
         if self._ctx is None:
             self._ctx = _lib.SparseContext(self.device)
-            if self.linear:
+            if self.psi_lin_bias:
+                self._ctx.set_psi_lin_bias(True)                       # (switches Linear on as well)
+            elif self.linear:
                 self._ctx.set_linear(True)
         if self._X is not None and self._X.matches(X) and self._Y.matches(Y):
             return False
@@ -199,6 +208,7 @@ class SparseSession(LatentFunctionInference):
         C = _lib.SparseContext
         post = SparsePosterior(woodbury_inv=LazyMM(self, C.FETCH_WOODBURY_INV, M), woodbury_vector=woodbury_vector,
                                K=LazyMM(self, C.FETCH_KMM, M), K_chol=LazyMM(self, C.FETCH_LM, M), device=self._device_dict(kern))
+        post.psi_lin_bias = self.psi_lin_bias
         return post, LazyMM(self, C.FETCH_DLDKMM, M)
 
 
@@ -231,12 +241,21 @@ class VarDTC(SparseSession):
         if mean_function is not None:                                  # var_dtc.py:85-86
             raise ValueError("Mean function not implemented with uncertain inputs or heteroscedasticity")
         parts = kern.parts if isinstance(kern, Add) else [kern]
+        covered = (RBF, Linear, Bias, White) if self.psi_lin_bias else (RBF, White)
         for p in parts:
-            if not isinstance(p, (RBF, White)) or type(p) not in (RBF, White):
+            if type(p) not in covered:
                 what = type(p).__name__ if p.is_leaf else "%s of %s" % (type(p).__name__, ", ".join(type(f).__name__ for f in p.leaves()))
+                if self.psi_lin_bias:
+                    raise NotImplementedError("uncertain inputs: the part %r (%s) has no psi-statistics on the MI355X sparse path; "
+                                              "one RBF or Linear kernel with Bias and White parts is covered" % (p.name, what))
                 raise NotImplementedError("uncertain inputs: the part %r (%s) has no psi-statistics on the MI355X sparse path; "
-                                          "one RBF kernel and White parts are covered" % (p.name, what))
-        rbfs = [p for p in parts if isinstance(p, RBF)]
+                                          "one RBF kernel and White parts are covered (one RBF or Linear kernel with Bias and "
+                                          "White parts: make the inference class with psi_lin_bias=True)" % (p.name, what))
+        rbfs = [p for p in parts if isinstance(p, (RBF, Linear))]
+        if len(rbfs) != 1 and self.psi_lin_bias:
+            raise NotImplementedError("uncertain inputs: exactly one input-dependent part (RBF or Linear) is covered, got %d (%s); "
+                                      "psi2 of two has cross terms that need E[k1 k2^T]"
+                                      % (len(rbfs), ", ".join("%r: %s" % (p.name, type(p).__name__) for p in rbfs)))
         if len(rbfs) != 1:
             raise NotImplementedError("uncertain inputs: exactly one RBF part is covered, got %d (%s)"
                                       % (len(rbfs), ", ".join(repr(p.name) for p in rbfs)))
@@ -424,10 +443,11 @@ class SparseGP(PredictionCallers, Parameterized):
 
 class SparseGPRegression(SparseGP):
     """(reference `GPy/models/sparse_gp_regression.py:20-60`): Z defaults to a random subset of X.  `linear=True`: the kernel
-    may hold Linear leaves (`VarDTC(linear=True)`)."""
+    may hold Linear leaves (`VarDTC(linear=True)`).  `psi_lin_bias=True`: with `X_variance`, one RBF or Linear part with Bias
+    and White parts (`VarDTC(psi_lin_bias=True)`; implies `linear`)."""
 
     def __init__(self, X, Y, kernel=None, Z=None, num_inducing=10, noise_var=1., device=0, seed=None, mean_function=None,
-                 X_variance=None, linear=False):
+                 X_variance=None, linear=False, psi_lin_bias=False):
         X = np.asarray(X, dtype=np.float64)
         if kernel is None:
             kernel = RBF(X.shape[1], device=device)
@@ -435,7 +455,8 @@ class SparseGPRegression(SparseGP):
             i = np.random.default_rng(seed).permutation(X.shape[0])[:min(num_inducing, X.shape[0])]
             Z = X[i].copy()
         super(SparseGPRegression, self).__init__(X, Y, Z, kernel, Gaussian(variance=noise_var),
-                                                 inference_method=VarDTC(device=device, linear=True) if linear else None,
+                                                 inference_method=(VarDTC(device=device, psi_lin_bias=True) if psi_lin_bias else
+                                                                   VarDTC(device=device, linear=True) if linear else None),
                                                  name="sparse_gp", device=device, mean_function=mean_function,
                                                  X_variance=X_variance)
 
@@ -446,11 +467,13 @@ class BayesianGPLVM(SparseGP):
     bound.  The flat parameter order is [X.mean, X.variance, Z, kernel, noise] (X is linked at index 0).  The bound, its
     gradients in every parameter -- the means and variances of q(X) included -- and prediction at certain or uncertain
     latent points run on the device through the uncertain-input path of `VarDTC`: the kernel is one `RBF` alone or summed
-    with `White` parts (the reference's default, `RBF(input_dim, ARD=True)`, is covered)."""
+    with `White` parts (the reference's default, `RBF(input_dim, ARD=True)`, is covered).  `psi_lin_bias=True`
+    (`VarDTC(psi_lin_bias=True)`): one `RBF` or `Linear` part with `Bias` and `White` parts -- `Linear(Q, ARD=True) + Bias + White`
+    is Bayesian PCA; the flat parameter order is then [X.mean, X.variance, Z, variances, bias, white, noise]."""
 
     def __init__(self, Y, input_dim, X=None, X_variance=None, init="PCA", num_inducing=10, Z=None, kernel=None,
                  inference_method=None, likelihood=None, name="bayesian gplvm", device=0, mpi_comm=None, normalizer=None,
-                 missing_data=False, stochastic=False, batchsize=1, Y_metadata=None):
+                 missing_data=False, stochastic=False, batchsize=1, Y_metadata=None, psi_lin_bias=False):
         for arg, value, default in (("mpi_comm", mpi_comm, None), ("normalizer", normalizer, None),
                                     ("missing_data", missing_data, False), ("stochastic", stochastic, False),
                                     ("batchsize", batchsize, 1)):
@@ -480,6 +503,12 @@ class BayesianGPLVM(SparseGP):
         if likelihood is None:
             likelihood = Gaussian()
         self.variational_prior = NormalPrior()
+        if psi_lin_bias:
+            if inference_method is None:
+                inference_method = VarDTC(device=device, psi_lin_bias=True)
+            elif not getattr(inference_method, "psi_lin_bias", False):
+                raise ValueError("BayesianGPLVM: psi_lin_bias=True, but the given inference_method was made without it; make it "
+                                 "with VarDTC(psi_lin_bias=True) or leave inference_method out")
         super(BayesianGPLVM, self).__init__(NormalPosterior(X, X_variance), Y, Z, kernel, likelihood,
                                             inference_method=inference_method, name=name, device=device, Y_metadata=Y_metadata)
         self.link_parameter(self.X, index=0)
