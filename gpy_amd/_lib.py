@@ -84,6 +84,8 @@ def build(force=False):
     srcs.append(os.path.join(_HERE, "..", "include", "mi355gp_debug_tileops.h"))
     srcs.append(os.path.join(_HERE, "..", "include", "mi355gp_epdtc.h"))
     srcs.append(os.path.join(_HERE, "..", "include", "mi355gp_sparse_diag.h"))
+    srcs.append(os.path.join(_HERE, "..", "include", "mi355gp_sparse_coreg.h"))
+    srcs.append(os.path.join(_HERE, "..", "include", "mi355gp_debug_sparse_coreg.h"))
     srcs.append(os.path.join(_HERE, "..", "include", "mi355gp_psi_lin.h"))
     srcs.append(os.path.join(_HERE, "..", "include", "mi355gp_debug_psi_lin.h"))
     srcs.append(os.path.join(_HERE, "..", "include", "mi355gp_vargauss.h"))
@@ -222,6 +224,16 @@ SPARSE_DIAG_ABI = {
     "mi355gp_sparse_set_linear": [_vp, _ci],
     "mi355gp_sparse_kdiag": [_vp, _ci, _parts] + [_c_dp] * 4,
 }
+# include/mi355gp_sparse_coreg.h: Coregionalize parts on the sparse context (tests/test_sparse_coreg_host.py holds the table
+# against that header's prototype)
+SPARSE_COREG_ABI = {
+    "mi355gp_sparse_set_coregionalize": [_vp, _ci],
+}
+# include/mi355gp_debug_sparse_coreg.h: the A/B switch of the sparse context's fused gradient passes, a diagnostic (held by the
+# same test)
+DEBUG_SPARSE_COREG_ABI = {
+    "mi355gp_dbg_sparse_set_fuse_cols": [_vp, _ci],
+}
 # include/mi355gp_psi_lin.h: Linear and Bias psi-statistics on the sparse context (tests/test_psi_lin_host.py holds the table
 # against that header's prototype)
 PSI_LIN_ABI = {
@@ -265,7 +277,8 @@ def lib():
         if not os.path.exists(LIB_PATH):
             build()
         L = ctypes.CDLL(LIB_PATH)
-        for table in (ABI, DEBUG_LAUUM_ABI, DEBUG_TILEOPS_ABI, EPDTC_ABI, SPARSE_DIAG_ABI, PSI_LIN_ABI, DEBUG_PSI_LIN_ABI, VARGAUSS_ABI, KRON_ABI):
+        for table in (ABI, DEBUG_LAUUM_ABI, DEBUG_TILEOPS_ABI, EPDTC_ABI, SPARSE_DIAG_ABI, SPARSE_COREG_ABI, DEBUG_SPARSE_COREG_ABI, PSI_LIN_ABI, DEBUG_PSI_LIN_ABI,
+                      VARGAUSS_ABI, KRON_ABI):
             for name, argtypes in table.items():
                 getattr(L, name).argtypes = argtypes
         L.mi355gp_last_error.restype = L.mi355gp_version.restype = _str
@@ -731,6 +744,16 @@ class SparseContext(_Handle):
     def set_linear(self, on=True):
         """Linear parts on this context's inference and prediction entry points (`mi355gp_sparse_set_linear`); off at first"""
         check(lib().mi355gp_sparse_set_linear(self._h, int(bool(on))), "mi355gp_sparse_set_linear")
+
+    def set_coregionalize(self, on=True):
+        """Coregionalize parts on this context's `vardtc_sum`, `predict` and `kdiag` (`mi355gp_sparse_set_coregionalize`); off at
+        first.  Switch it on before `set_data`: the rows' output indices are checked against a host copy that set_data keeps."""
+        check(lib().mi355gp_sparse_set_coregionalize(self._h, int(bool(on))), "mi355gp_sparse_set_coregionalize")
+
+    def set_fuse_cols(self, on=True):
+        """A/B switch of the second pass (`mi355gp_dbg_sparse_set_fuse_cols`, a diagnostic): off, the unfused routes -- for a
+        stationary x Coregionalize term the product route in place of k_grad_cols_icm"""
+        check(lib().mi355gp_dbg_sparse_set_fuse_cols(self._h, int(bool(on))), "mi355gp_dbg_sparse_set_fuse_cols")
 
     def set_psi_lin_bias(self, on=True):
         """One RBF or Linear part with Bias and White parts on this context's uncertain-input entry points

@@ -318,6 +318,15 @@ int launch_kbuild_cols(hipStream_t st, KernParams kp, const double* Xt1, long ld
 int launch_grad_cols(hipStream_t st, KernParams kp, const double* Xt1, long ld1, long n, const double* Xt2, long ld2,
                      long m, long mcols, const double* G, long ldg, RankTerm rk, double* partials, double* colpart,
                      int* nblocks_out);
+// sparse pass 2 for a term that is one stationary factor (kp) times one Coregionalize factor (kc; D <= 16, P <= 16): what
+// launch_grad_cols leaves for the stationary factor, with dL_dKnm times B[a_i][b_j] as its weights, and per block the
+// Coregionalize factor's buckets S[a][b] = sum g K_stationary at spart + block * P * P (combine: launch_reduce_partials with stride
+// P * P), in one pass over the weights (k_grad_cols_icm).  Ct1 / Ct2: the Coregionalize part's own scaled copies of the rows and
+// the inducing inputs (dimension-major; only the index row kc.col is read).  Returns the number of row splits, 0 = not applicable
+bool grad_cols_icm_applies(int D, int P, long mcols);      // (the pass's own conditions; launch_grad_cols_icm returns 0 without them)
+int launch_grad_cols_icm(hipStream_t st, KernParams kp, KernParams kc, const double* Xt1, long ld1, long n, const double* Xt2, long ld2,
+                         long m, long mcols, const double* Ct1, long ldc1, const double* Ct2, long ldc2, const double* G, long ldg,
+                         RankTerm rk, double* partials, double* colpart, double* spart, int* nblocks_out);
 // sparse pass 2 for a Linear part (kind 9, D <= 16): the column partials of HX[j][q] = sum_i g[i][j] x~[i][q] ([split][mcols][D],
 // no ones column) in one pass over the weights, formed on the fly as launch_grad_cols forms them; the theta record follows on
 // the host from HX and the scaled Z.  Returns the number of row splits, 0 = not applicable (D > 16)
@@ -343,17 +352,31 @@ void launch_sum_splits(hipStream_t st, const double* src, long cnt, int nsplit, 
 // kd_n = sum over terms of the product of the factors' diagonals at x_n: the variance for a constant-diagonal kind,
 // sum_q coef[p][q] x_nq^2 for a part whose diagonal depends on the point (Linear: coef = variance_q, 0 off its dimensions).
 #define KDIAG_MAX_PARTS 16
+// Coregionalize (kind 8): at most COREG_PMAX outputs, and the one guard every kernel that reads an output index goes through --
+// the output a value of the index column names, or -1 where it is no integer in [0, P) (nothing of B is read then)
+#define COREG_PMAX 16
+__host__ __device__ static inline int coreg_idx(double x, int P) {
+    const int a = (int)x;
+    return ((double)a == x && a >= 0 && a < P) ? a : -1;
+}
 struct DiagDesc {
     int nparts, nterms;
     int tstart[KDIAG_MAX_PARTS + 1];   // term t: the parts tpart[tstart[t] .. tstart[t + 1])
     int tpart[KDIAG_MAX_PARTS];
     int tix[KDIAG_MAX_PARTS];          // the term of part p
-    int by_point[KDIAG_MAX_PARTS];     // 1: the diagonal of part p is sum_q coef[p][q] x_q^2
+    int by_point[KDIAG_MAX_PARTS];     // 1: the diagonal of part p is sum_q coef[p][q] x_q^2; 2: Coregionalize, diag(B)[idx]
     double var[KDIAG_MAX_PARTS];       // else: its variance
+    // Coregionalize parts (by_point == 2; coregionalize.py:106-107,145-151): the input column of the output index and the number
+    // of outputs P <= KDIAG_MAX_OUT; diag(B) lies behind the nparts x D coefficients, at coef[nparts D + p KDIAG_MAX_OUT + a]
+    int ccol[KDIAG_MAX_PARTS], cP[KDIAG_MAX_PARTS];
+    int width;                         // doubles per part in the record of weighted sums: D, or the largest P if that is more
 };
-// doubles of one record of weighted sums: [0] sum w kd, [1] sum w^2 kd, [2 + p D + q] sum w (other factors of p) x_q^2 for a
-// by-point part p, [2 + p D] sum w (other factors of p) for a constant-diagonal one
-__host__ __device__ static inline int kdiag_slots(int nparts, int D) { return 2 + nparts * D; }
+#define KDIAG_MAX_OUT COREG_PMAX
+// doubles of one record of weighted sums: [0] sum w kd, [1] sum w^2 kd, [2 + p width + q] sum w (other factors of p) x_q^2 for a
+// by-point part p, [2 + p width] sum w (other factors of p) for a constant-diagonal one, [2 + p width + a] the same sum over the
+// rows of output a alone for a Coregionalize part.  width = D unless a Coregionalize part has more outputs than that.
+__host__ __device__ static inline int kdiag_slots(int nparts, int width) { return 2 + nparts * width; }
+static inline size_t kdiag_coefs(int nparts, int D) { return (size_t)nparts * D + (size_t)nparts * KDIAG_MAX_OUT; }
 static inline long kdiag_blocks(long n) { return (n + 255) / 256; }
 // kd_out (n, optional) and, with weights w (n), the record sums_out (kdiag_slots doubles) -- block partials (partials:
 // kdiag_blocks(n) records) combined in block order, no atomics: two calls give the same bytes.  coef: nparts x D.

@@ -1,4 +1,5 @@
-// kern_diag.hip -- the per-point diagonal of a kernel expression (add.py:74-79, prod.py:67-71, linear.py:84-85,100-105) over the
+// kern_diag.hip -- the per-point diagonal of a kernel expression (add.py:74-79, prod.py:67-71, linear.py:84-85,100-105,
+// coregionalize.py:106-107,145-151) over the
 // rows of a resident row-major point set: kd_n = sum over terms of the product of the factors' diagonals at x_n, and for a
 // weight vector w the sums that update_gradients_diag and the sparse bounds need.  One thread per row; a block's sums are
 // reduced by a fixed tree, the blocks' records are added in block order by one more launch (no floating-point atomics).
@@ -28,9 +29,12 @@ __global__ __launch_bounds__(256) void k_kdiag_rows(DiagDesc ds, const double* _
     const double* x = X + (valid ? i : 0) * D;
     for (int p = 0; p < ds.nparts; ++p) {
         double d = ds.var[p];
-        if (ds.by_point[p]) {
+        if (ds.by_point[p] == 1) {
             d = 0.0;
             for (int q = 0; q < D; ++q) d = fma(coef[p * D + q], x[q] * x[q], d);
+        } else if (ds.by_point[p] == 2) {                // diag(B) at the row's output; an index outside [0, P) reads nothing: NaN
+            const int a = coreg_idx(x[ds.ccol[p]], ds.cP[p]);
+            d = a >= 0 ? coef[ds.nparts * D + p * KDIAG_MAX_OUT + a] : __builtin_nan("");
         }
         sd[p][t] = d;
     }
@@ -43,7 +47,8 @@ __global__ __launch_bounds__(256) void k_kdiag_rows(DiagDesc ds, const double* _
     if (kd_out && valid) kd_out[i] = kd;
     if (!w) return;                                      // (the same for every thread)
     const double wv = valid ? w[i] : 0.0;
-    double* rec = partials + (long)blockIdx.x * kdiag_slots(ds.nparts, D);
+    const int W = ds.width;
+    double* rec = partials + (long)blockIdx.x * kdiag_slots(ds.nparts, W);
     double s = kdiag_block_sum(red, t, wv * kd);
     if (t == 0) rec[0] = s;
     s = kdiag_block_sum(red, t, wv * wv * kd);
@@ -53,18 +58,32 @@ __global__ __launch_bounds__(256) void k_kdiag_rows(DiagDesc ds, const double* _
         const int tm = ds.tix[p];
         for (int k = ds.tstart[tm]; k < ds.tstart[tm + 1]; ++k)
             if (ds.tpart[k] != p) o *= sd[ds.tpart[k]][t];
-        double* out = rec + 2 + p * D;
+        double* out = rec + 2 + p * W;
         if (!ds.by_point[p]) {
             s = kdiag_block_sum(red, t, o);
             if (t == 0) {
                 out[0] = s;
-                for (int q = 1; q < D; ++q) out[q] = 0.0;
+                for (int q = 1; q < W; ++q) out[q] = 0.0;
             }
-        } else {
+        } else if (ds.by_point[p] == 1) {
             for (int q = 0; q < D; ++q) {
                 s = kdiag_block_sum(red, t, o * (x[q] * x[q]));
                 if (t == 0) out[q] = s;
             }
+            if (t == 0)
+                for (int q = D; q < W; ++q) out[q] = 0.0;
+        } else {
+            // the per-output buckets (coregionalize.py:145-151): the rows of output a alone; a row whose index is no output
+            // poisons bucket 0, as the bucketed gradient pass does
+            const int P = ds.cP[p], a = coreg_idx(x[ds.ccol[p]], P);
+            for (int q = 0; q < P; ++q) {
+                double v = (a == q) ? o : 0.0;
+                if (q == 0 && a < 0 && valid) v = __builtin_nan("");
+                s = kdiag_block_sum(red, t, v);
+                if (t == 0) out[q] = s;
+            }
+            if (t == 0)
+                for (int q = P; q < W; ++q) out[q] = 0.0;
         }
     }
 }
@@ -107,6 +126,6 @@ void launch_kdiag(hipStream_t st, const DiagDesc& ds, const double* X, long n, i
     const long nblk = kdiag_blocks(n);
     hipLaunchKernelGGL(k_kdiag_rows, dim3((unsigned)nblk), dim3(256), 0, st, ds, X, n, D, coef, w, kd_out, partials);
     if (!w) return;
-    const int S = kdiag_slots(ds.nparts, D);
+    const int S = kdiag_slots(ds.nparts, ds.width);
     hipLaunchKernelGGL(k_kdiag_combine, dim3((unsigned)((S + 255) / 256)), dim3(256), 0, st, partials, nblk, S, sums_out);
 }

@@ -12,12 +12,7 @@
 // Coregionalize (kind 8, coregionalize.py:82-157): k(x, x') = B[idx][idx'], idx = the value of input row kp.col of Xt (staged
 // unscaled), B = kp.pw (P x P row-major, P = kp.ard <= 16).  The host validates every index before a launch; an index that is
 // not an integer in [0, P) still never reads outside B here: it yields NaN (K-build) or poisons the block's record (gradient).
-#define COREG_PMAX 16
-
-__device__ __forceinline__ int coreg_idx(double x, int P) {
-    const int a = (int)x;
-    return ((double)a == x && a >= 0 && a < P) ? a : -1;
-}
+// (COREG_PMAX and the index guard coreg_idx: internal.h)
 
 // Covariance assembly: the skeleton's tile decode and row epilogue around a lookup -- nothing to accumulate.  B lives in LDS
 // once per block, the tile's row / column indices as integers.  The diagonal is what B gives.

@@ -451,6 +451,271 @@ int launch_grad_cols(hipStream_t st, KernParams kp, const double* Xt1, long ld1,
     return nsplit;
 }
 
+// ------------------------------------------------------------------------------------------------
+// The pass for a term that is exactly one stationary factor times one Coregionalize factor (what util.multioutput.ICM builds;
+// D <= 16, P <= 16): k_grad_cols_mfma with the lookup B[a_i][b_j] folded in.  The product route (sparse_rows_gradients) builds
+// the other factor's covariance, multiplies dL_dKnm up in memory, runs the gradient kernel with H written and the column
+// reduction, per factor: about eight passes over a chunk x M array.  Here the chunk's rows of W are read once, dL_dKnm is
+// formed on the fly from the RankTerm (rowscale included: MixedNoise gives per-point precisions) and nothing of chunk x M is
+// written.  From ONE evaluation of c = cov_all(r^2) per element:
+//   the stationary factor's theta record from  g B[a][b] c            (a_var, a_iso / a_q as in k_grad_cols_mfma),
+//   HX = H^T [x~ | 1] with H = g B[a][b] c.dk_or                      (v_mfma_f64_16x16x4, the ones column on the VALU),
+//   the Coregionalize factor's buckets  S[a][b] += g c.k              (the weights of update_gradients_full: dL_dK times the
+//                                                                      OTHER factor's covariance, prod.py:86-99).
+// B lives in LDS; the tile's row and column output indices are read from the Coregionalize part's own scaled copies (Ct1 / Ct2:
+// they hold the index column alone) into LDS as integers, with the masks of the outputs present.  Per tile and present pair
+// (a, b), in a fixed order, every thread sums its matching elements and a fixed wave / block tree adds them into the block's LDS
+// record, as k_grad_coreg does: rows sorted by output give ONE pair, one block reduction, in nearly every tile; a tile with
+// many pairs is right all the same.  The block's S goes to spart + block * P * P (combine: launch_reduce_partials, block order).
+// An index that is no output never reads outside B: its elements count as NaN and the block's record is poisoned.
+// LDS: k_grad_cols_mfma's 68.6 KB (si 8, sj 9, sit 9, sh 40, red 2) + B 2 KB + S 2 KB + two index arrays 0.5 KB = 73 KB: two
+// workgroups per CU (160 KB) as that kernel has; __launch_bounds__(256, 2) holds the registers to the same budget.
+template <bool ARD>
+__global__ __launch_bounds__(256, 2) void k_grad_cols_icm(KernParams kp, KernParams kc, const double* __restrict__ Xt1, long ld1, long n,
+                                                          const double* __restrict__ Xt2, long ld2, long m,
+                                                          const double* __restrict__ Ct1, long ldc1,
+                                                          const double* __restrict__ Ct2, long ldc2,
+                                                          const double* __restrict__ G, long ldg, RankTerm rk, int ntc, int ntr,
+                                                          int tiles_per_split, double* __restrict__ partials,
+                                                          double* __restrict__ colpart, long mcols, int nv,
+                                                          double* __restrict__ spart) {
+    constexpr int DM = 16;                               // D <= 16
+    __shared__ __attribute__((aligned(16))) double si[DM * KT];
+    __shared__ __attribute__((aligned(16))) double sj[DM * KTJ];
+    __shared__ __attribute__((aligned(16))) double sit[KT * 18];   // x~ slab row-major [i][c], stride 18: the B operand
+    __shared__ __attribute__((aligned(16))) double sh[KT * GC_HS];
+    __shared__ double sB[COREG_PMAX * COREG_PMAX], sacc[COREG_PMAX * COREG_PMAX];
+    __shared__ int sa[KT], sb[KT];
+    __shared__ unsigned smask[2];
+    __shared__ double redS[4];
+    double* red = block_red();
+    const int t = threadIdx.x, tx = t & 15, ty = t >> 4, lane = t & 63, w = t >> 6;
+    const int tj = blockIdx.x % ntc, split = blockIdx.x / ntc;
+    const long j0 = (long)tj * KT;
+    const int D = kp.D, P = kc.ard;
+    double a_var = 0.0, a_iso = 0.0;
+    double a_q[DM];
+    double csum[4] = {0.0, 0.0, 0.0, 0.0};
+    d4 hx = {0.0, 0.0, 0.0, 0.0};                        // HX[j = 16 w + (lane >> 4) + 4 r][c = lane & 15]
+    bool poisoned = false;                               // (thread 0) an index outside [0, P) was met
+#pragma unroll
+    for (int q = 0; q < DM; ++q) a_q[q] = 0.0;
+    for (int idx = t; idx < KT * 18; idx += 256) sit[idx] = 0.0;      // columns c >= D stay zero
+    for (int k = t; k < P * P; k += 256) {
+        sB[k] = kc.pw[k];
+        sacc[k] = 0.0;
+    }
+    if (w == 1) {                                        // the column tile's outputs: the same for every row tile of this block
+        const long j = j0 + lane;
+        int v = -2;                                      // -2: padding (no element), -1: an invalid index
+        if (j < m) v = coreg_idx(Ct2[(long)kc.col * ldc2 + j], P);
+        unsigned bit = (v >= 0) ? (1u << v) : (v == -1 ? (1u << COREG_PMAX) : 0u);
+        for (int off = 32; off > 0; off >>= 1) bit |= (unsigned)__shfl_xor((int)bit, off);
+        sb[lane] = v;
+        if (lane == 0) smask[1] = bit;
+    }
+    const bool vec4 = (j0 + tx * 4 + 3 < m) && (ldg % 4 == 0) && ((reinterpret_cast<unsigned long long>(G) & 31ull) == 0);
+    const bool rkfast = rk.Y != nullptr && rk.Dy <= GC_DY;
+    double vcol[4][GC_DY];
+#pragma unroll
+    for (int b = 0; b < 4; ++b)
+#pragma unroll
+        for (int d = 0; d < GC_DY; ++d)
+            vcol[b][d] = (rkfast && d < rk.Dy && j0 + tx * 4 + b < m) ? rk.V[(j0 + tx * 4 + b) * rk.Dy + d] : 0.0;
+    const int ti_end = ((split + 1) * tiles_per_split < ntr) ? (split + 1) * tiles_per_split : ntr;
+    for (int ti = split * tiles_per_split; ti < ti_end; ++ti) {
+        const long i0 = (long)ti * KT;
+        double r2[4][4];
+#pragma unroll
+        for (int a = 0; a < 4; ++a)
+#pragma unroll
+            for (int b = 0; b < 4; ++b) r2[a][b] = 0.0;
+        __syncthreads();                                 // the previous tile's reads of sh / sit / sa / smask are done
+        for (int idx = t; idx < D * KT; idx += 256) {
+            const int q = idx >> 6, ii = idx & 63;
+            const double v = Xt1[(long)q * ld1 + i0 + ii];
+            si[q * KT + ii] = v;
+            sit[ii * 18 + q] = v;
+        }
+        stage_xj(Xt2, ld2, j0, 0, D, sj, t);
+        if (w == 0) {                                    // the row tile's outputs
+            const long i = i0 + lane;
+            int v = -2;
+            if (i < n) v = coreg_idx(Ct1[(long)kc.col * ldc1 + i], P);
+            unsigned bit = (v >= 0) ? (1u << v) : (v == -1 ? (1u << COREG_PMAX) : 0u);
+            for (int off = 32; off > 0; off >>= 1) bit |= (unsigned)__shfl_xor((int)bit, off);
+            sa[lane] = v;
+            if (lane == 0) smask[0] = bit;
+        }
+        __syncthreads();
+        accum_r2(si, sj, D, ty, tx, r2);
+        const unsigned rm = smask[0], cm = smask[1];
+        if (t == 0 && ((rm | cm) >> COREG_PMAX)) poisoned = true;
+        int ra[4], cb[4];
+#pragma unroll
+        for (int a = 0; a < 4; ++a) ra[a] = sa[ty * 4 + a];
+#pragma unroll
+        for (int b = 0; b < 4; ++b) cb[b] = sb[tx * 4 + b];
+        double gT[4][4], sw[4][4];
+#pragma unroll
+        for (int a = 0; a < 4; ++a) {
+            const long i = i0 + ty * 4 + a;
+            d4 gv = {0.0, 0.0, 0.0, 0.0};
+            double yrow[GC_DY], rs = 1.0;
+            if (i < n) {
+                if (vec4) gv = *reinterpret_cast<const d4*>(G + i * ldg + j0 + tx * 4);
+                else
+#pragma unroll
+                    for (int b = 0; b < 4; ++b)
+                        if (j0 + tx * 4 + b < m) gv[b] = G[i * ldg + j0 + tx * 4 + b];
+                if (rk.Y && rkfast) {
+#pragma unroll
+                    for (int d = 0; d < GC_DY; ++d) yrow[d] = (d < rk.Dy) ? rk.Y[i * rk.Dy + d] : 0.0;
+                    if (rk.rowscale) rs = rk.rowscale[i];
+                }
+            }
+#pragma unroll
+            for (int b = 0; b < 4; ++b) {
+                const long j = j0 + tx * 4 + b;
+                double g = 0.0, bij = 0.0;
+                if (i < n && j < m) {
+                    g = gv[b];
+                    if (rk.Y) {
+                        double yv = 0.0;
+                        if (rkfast) {
+#pragma unroll
+                            for (int d = 0; d < GC_DY; ++d)
+                                if (d < rk.Dy) yv = fma(yrow[d], vcol[b][d], yv);
+                        } else {
+                            for (int d = 0; d < rk.Dy; ++d) yv = fma(rk.Y[i * rk.Dy + d], rk.V[j * rk.Dy + d], yv);
+                        }
+                        g = fma(rk.gscale, g, rk.beta * yv);
+                        if (rk.rowscale) g *= rkfast ? rs : rk.rowscale[i];
+                    }
+                    bij = (ra[a] >= 0 && cb[b] >= 0) ? sB[ra[a] * P + cb[b]] : __builtin_nan("");
+                }
+                const CovVal c = cov_all(kp.kind, kp.variance, r2[a][b], false);
+                const double gb = g * bij;               // the weight the stationary factor sees (prod.py:86-99)
+                sw[a][b] = g * c.k;                      // ... and the one the Coregionalize factor sees
+                a_var = fma(gb, c.k, a_var);
+                if (!ARD) a_iso = fma(gb, c.dk_r, a_iso);
+                gT[a][b] = gb * c.dk_or;
+                csum[b] += gT[a][b];
+            }
+            *reinterpret_cast<d4*>(sh + (ty * 4 + a) * GC_HS + tx * 4) = (d4){gT[a][0], gT[a][1], gT[a][2], gT[a][3]};
+        }
+        if (ARD) {
+#pragma unroll
+            for (int q = 0; q < DM; ++q) {
+                if (q < D) {
+                    const d4 xi = *reinterpret_cast<const d4*>(si + q * KT + ty * 4);
+                    const d4 xj = ld_xj(sj, q, tx);
+                    double sacc_q = 0.0;
+#pragma unroll
+                    for (int a = 0; a < 4; ++a)
+#pragma unroll
+                        for (int b = 0; b < 4; ++b) {
+                            const double d = xi[a] - xj[b];
+                            sacc_q = fma(gT[a][b], d * d, sacc_q);
+                        }
+                    a_q[q] += sacc_q;
+                }
+            }
+        }
+        __syncthreads();                                 // the H tile is complete
+        const double* ha = sh + (lane >> 4) * GC_HS + 16 * w + (lane & 15);
+        const double* xb = sit + (lane >> 4) * 18 + (lane & 15);
+#pragma unroll
+        for (int s4 = 0; s4 < 16; ++s4) hx = mfma_f64(ha[4 * s4 * GC_HS], xb[4 * s4 * 18], hx);
+        // the buckets: every present pair in a fixed order (the masks are the block's: the loop is uniform)
+        for (unsigned rmm = rm & ((1u << COREG_PMAX) - 1); rmm; rmm &= rmm - 1) {
+            const int pa = __ffs(rmm) - 1;
+            for (unsigned cmm = cm & ((1u << COREG_PMAX) - 1); cmm; cmm &= cmm - 1) {
+                const int pb = __ffs(cmm) - 1;
+                double v = 0.0;
+#pragma unroll
+                for (int a = 0; a < 4; ++a)
+#pragma unroll
+                    for (int b = 0; b < 4; ++b)
+                        if (ra[a] == pa && cb[b] == pb) v += sw[a][b];
+                for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off);
+                if (lane == 0) redS[w] = v;
+                __syncthreads();
+                if (t == 0) sacc[pa * P + pb] += (redS[0] + redS[1]) + (redS[2] + redS[3]);
+                __syncthreads();
+            }
+        }
+    }
+    // theta partials of this block
+    double* out = partials + (long)blockIdx.x * GP_STRIDE;
+    const double sv = block_sum(t, a_var);
+    if (t == 0) out[0] = sv;
+    if (!ARD) {
+        const double sl = block_sum(t, a_iso);
+        if (t == 0) out[1] = sl;
+    } else {
+#pragma unroll
+        for (int q = 0; q < DM; ++q) {
+            if (q < D) {
+                const double sq = block_sum(t, a_q[q]);
+                if (t == 0) out[2 + q] = sq;
+            }
+        }
+    }
+    double* cp = colpart + (long)split * mcols * nv;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        const long j = j0 + 16 * w + (lane >> 4) + 4 * r;
+        const int c = lane & 15;
+        if (c < D && j < mcols) cp[j * nv + c] = (j < m) ? hx[r] : 0.0;
+    }
+#pragma unroll
+    for (int b = 0; b < 4; ++b) {
+        __syncthreads();
+        red[ty * 16 + tx] = csum[b];
+        __syncthreads();
+        if (ty == 0) {
+            double sacc_c = 0.0;
+            for (int r = 0; r < 16; ++r) sacc_c += red[r * 16 + tx];
+            const long j = j0 + tx * 4 + b;
+            if (j < mcols) cp[j * nv + D] = (j < m) ? sacc_c : 0.0;
+        }
+    }
+    __syncthreads();
+    if (t == 0 && poisoned) sacc[0] = __builtin_nan("");
+    __syncthreads();
+    double* so = spart + (long)blockIdx.x * P * P;
+    for (int k = t; k < P * P; k += 256) so[k] = sacc[k];
+}
+
+// Whether the pass applies (the one list of its conditions: the caller asks before it decides on a route) ...
+// ... and the launch: returns the number of row splits (0, with nothing launched, where it does not apply); *nblocks_out <= 2048
+// blocks have written a GP_STRIDE record to partials and a P x P record to spart, colpart holds nsplit * mcols * (D + 1) doubles
+bool grad_cols_icm_applies(int D, int P, long mcols) {
+    return D <= 16 && P >= 1 && P <= COREG_PMAX && (mcols + KT - 1) / KT <= 2048;      // (spart and partials hold 2048 block records)
+}
+int launch_grad_cols_icm(hipStream_t st, KernParams kp, KernParams kc, const double* Xt1, long ld1, long n, const double* Xt2, long ld2,
+                         long m, long mcols, const double* Ct1, long ldc1, const double* Ct2, long ldc2, const double* G, long ldg,
+                         RankTerm rk, double* partials, double* colpart, double* spart, int* nblocks_out) {
+    if (!grad_cols_icm_applies(kp.D, kc.ard, mcols)) return 0;
+    const int ntr = (int)((n + KT - 1) / KT), ntc = (int)((mcols + KT - 1) / KT);
+    int nsplit = 2048 / ntc;
+    if (nsplit > 64) nsplit = 64;
+    if (nsplit > ntr) nsplit = ntr;
+    if (nsplit < 1) nsplit = 1;
+    const int tps = (ntr + nsplit - 1) / nsplit;
+    nsplit = (ntr + tps - 1) / tps;
+    const int nb = ntc * nsplit;
+    if (kp.ard)
+        hipLaunchKernelGGL((k_grad_cols_icm<true>), dim3(nb), dim3(256), 0, st, kp, kc, Xt1, ld1, n, Xt2, ld2, m, Ct1, ldc1, Ct2, ldc2, G,
+                           ldg, rk, ntc, ntr, tps, partials, colpart, mcols, kp.D + 1, spart);
+    else
+        hipLaunchKernelGGL((k_grad_cols_icm<false>), dim3(nb), dim3(256), 0, st, kp, kc, Xt1, ld1, n, Xt2, ld2, m, Ct1, ldc1, Ct2, ldc2, G,
+                           ldg, rk, ntc, ntr, tps, partials, colpart, mcols, kp.D + 1, spart);
+    *nblocks_out = nb;
+    return nsplit;
+}
+
 // The pass for a Linear part (kind 9, linear.py:87-114; D <= 16).  K = sum_q x~_iq z~_jq with x~ = sqrt(variance_q) x, so the whole
 // row-side gradient is the skinny product  HX[j][q] = sum_i g[i][j] x~[i][q]  of the weights themselves: dL/dvariance_q =
 // sum_j z~_jq HX[j][q] / variance_q and dL/dZ_jq = sqrt(variance_q) HX[j][q], both finished on the host from HX and the scaled Z.

@@ -19,6 +19,8 @@
 #include "../../include/mi355gp.h"
 #include "../../include/mi355gp_debug.h"
 #include "../../include/mi355gp_sparse_diag.h"
+#include "../../include/mi355gp_sparse_coreg.h"
+#include "../../include/mi355gp_debug_sparse_coreg.h"
 #include "../../include/mi355gp_psi_lin.h"
 #include "internal.h"
 #include "parts.h"
@@ -274,8 +276,8 @@ int alloc_m(mi355gp_sparse* s, long M) {
 }
 
 // Describes an expression to the kernels of kern_diag.hip: the terms, the constant diagonals, and per by-point part its D
-// coefficients (Linear: variance_q itself, not the square of the input scaling; MLP / Poly / Coregionalize are not sparse-path
-// kinds).  Part: PartSpec or anything derived from it, grouped by group_terms.
+// coefficients (Linear: variance_q itself, not the square of the input scaling), per Coregionalize part its index column, P and
+// diag(B) behind those (MLP / Poly are not sparse-path kinds).  Part: PartSpec or anything derived from it, grouped by group_terms.
 template <class Part>
 static void describe_diag(const std::vector<Part>& parts, const Terms& terms, int D, DiagDesc* ds, std::vector<double>* coef) {
     const int np_ = (int)parts.size();
@@ -287,27 +289,41 @@ static void describe_diag(const std::vector<Part>& parts, const Terms& terms, in
         for (int f : terms[t]) ds->tpart[k++] = f;
     }
     ds->tstart[terms.size()] = k;
-    coef->assign((size_t)np_ * D, 0.0);
+    coef->assign(kdiag_coefs(np_, D), 0.0);
+    ds->width = D;
     for (int i = 0; i < np_; ++i) {
         const Part& p = parts[(size_t)i];
         ds->tix[i] = p.tix;
-        ds->by_point[i] = p.diag_by_point() ? 1 : 0;
+        ds->by_point[i] = p.coreg() ? 2 : p.diag_by_point() ? 1 : 0;
         ds->var[i] = p.kp.variance;
+        ds->ccol[i] = ds->cP[i] = 0;
         if (p.linear())
             for (size_t a = 0; a < p.dims.size(); ++a) (*coef)[(size_t)i * D + p.dims[a]] = p.theta[p.kp.ard ? a : 0];
+        if (p.coreg()) {                                                     // diag(B) behind the nparts x D coefficients
+            const int P = p.ard_in;
+            ds->ccol[i] = p.kp.col;
+            ds->cP[i] = P;
+            if (P > ds->width) ds->width = P;
+            for (int a = 0; a < P; ++a) (*coef)[(size_t)np_ * D + (size_t)i * KDIAG_MAX_OUT + a] = p.theta[(size_t)a * P + a];
+        }
     }
 }
 // update_gradients_diag of every part in theta order from a record of weighted sums, times `scale`
 template <class Part>
 static void diag_dtheta(const std::vector<Part>& parts, int D, const std::vector<double>& sums, double scale, std::vector<double>* out) {
     out->clear();
+    int width = D;                                                           // (DiagDesc::width, as describe_diag sets it)
+    for (const Part& p : parts)
+        if (p.coreg() && p.ard_in > width) width = p.ard_in;
     for (size_t i = 0; i < parts.size(); ++i) {
         const Part& p = parts[i];
-        const double* r = sums.data() + 2 + i * (size_t)D;
+        const double* r = sums.data() + 2 + i * (size_t)width;
         const size_t o = out->size();
         out->resize(o + p.theta.size(), 0.0);
         double* g = out->data() + o;
         if (!p.diag_by_point()) g[0] = scale * r[0];                         // the variance slot (stationary.py:175-184, static.py)
+        else if (p.coreg())                                                  // the per-output sums land on dB[a][a] (coregionalize.py:145-151)
+            for (int a = 0; a < p.ard_in; ++a) g[(size_t)a * p.ard_in + a] = scale * r[a];
         else if (p.kp.ard)                                                   // linear.py:100-105
             for (size_t a = 0; a < p.dims.size(); ++a) g[a] = scale * r[p.dims[a]];
         else
@@ -332,7 +348,7 @@ static int prepare_diag(mi355gp_sparse* s) {
 // the kernels of kern_diag.hip for a described expression (coef: device); the record of weighted sums on its way to host_sums
 static int run_kdiag(mi355gp_sparse* s, const DiagDesc& ds, const double* coef, const double* X, long rows, const double* w,
                      double* kd_out, std::vector<double>* host_sums) {
-    const int S = kdiag_slots(ds.nparts, s->D);
+    const int S = kdiag_slots(ds.nparts, ds.width);
     if (w) {
         HIP_CHECK(s->diagPart.need((size_t)kdiag_blocks(rows) * S));
         HIP_CHECK(s->diagSums.need((size_t)S));
@@ -355,16 +371,47 @@ void sparse_diag_dtheta(const mi355gp_sparse* s, const std::vector<double>& sums
     diag_dtheta(s->parts, s->D, sums, scale, out);
 }
 
+// The index column of the context's rows against a Coregionalize part, on the host copy that set_data keeps while
+// mi355gp_sparse_set_coregionalize is on; once per (column, P) and data set
+static int coreg_check_data(mi355gp_sparse* s, const PartSpec& p) {
+    const std::pair<int, int> key(p.kp.col, p.ard_in);
+    for (const auto& k : s->coreg_ok)
+        if (k == key) return 0;
+    if (s->hX.size() != (size_t)s->n * (size_t)s->D)
+        PART_FAIL("sparse path: Coregionalize (kind 8): mi355gp_sparse_set_coregionalize must be on before mi355gp_sparse_set_data "
+                  "(the rows' output indices are checked on the host copy that set_data keeps while it is on)");
+    if (int rc = coreg_check_index(s->hX.data() + p.kp.col, s->n, s->D, p.ard_in, "training")) return rc;
+    s->coreg_ok.push_back(key);
+    return 0;
+}
+// the same check of m row-major points (Z, new points) against every Coregionalize part of the call: every time
+static int coreg_check_points(const mi355gp_sparse* s, const double* X, long m, const char* what) {
+    for (const SPart& p : s->parts)
+        if (p.coreg())
+            if (int rc = coreg_check_index(X + p.kp.col, m, s->D, p.ard_in, what)) return rc;
+    return 0;
+}
+
 // (re)builds the part list of a call; the device buffers of a part are kept while the number of parts is unchanged
-int prepare_sparse_parts(mi355gp_sparse* s, int nparts, const mi355gp_part* parts) {
+int prepare_sparse_parts(mi355gp_sparse* s, int nparts, const mi355gp_part* parts, bool coreg) {
     ARG_CHECK(nparts >= 1 && nparts <= 16 && parts, "between 1 and 16 kernel parts");
     // Linear is taken where the context was told so (mi355gp_sparse_set_linear; off in a new context: a caller that has not
-    // asked keeps the refusal by name)
-    const KindSet accepted = KS_STATIONARY | KS_STATIC | (s->take_linear ? KS_LINEAR : 0u);
+    // asked keeps the refusal by name); Coregionalize likewise (mi355gp_sparse_set_coregionalize), by the entry points that say so
+    const KindSet accepted = KS_STATIONARY | KS_STATIC | (s->take_linear ? KS_LINEAR : 0u) | (s->take_coreg && coreg ? KS_COREG : 0u);
     for (int i = 0; i < nparts; ++i)                             // before any device work: the global sums of a per-point
         if (kind_in(parts[i].kind, accepted) && parts[i].kind == MI355GP_LINEAR && sharded(s))   // diagonal would need another all-reduce
             PART_FAIL("sparse path: a Linear (kind 9) part is not supported by a row-sharded context (its Kdiag depends on the "
                       "point: the sums over rows would need a collective of their own)");
+    for (int i = 0; i < nparts; ++i) {
+        if (parts[i].kind != MI355GP_COREGIONALIZE || !s->take_coreg) continue;
+        if (!coreg)
+            PART_FAIL("sparse path: a Coregionalize (kind 8) part is taken by mi355gp_vardtc_inference_sum and mi355gp_sparse_predict "
+                      "alone; this entry point does not evaluate the kind (PEP / FITC, SVGP and EPDTC have no per-point noise model that "
+                      "fits the outputs' own noise variances; uncertain inputs have no psi-statistics for it)");
+        if (sharded(s))
+            PART_FAIL("sparse path: a Coregionalize (kind 8) part is not supported by a row-sharded context (its Kdiag depends on "
+                      "the point: the sums over rows would need a collective of their own)");
+    }
     const long mp = s->mp, D = s->D;
     const int groups = (int)((D + 31) / 32);
     if ((int)s->parts.size() != nparts) {
@@ -385,6 +432,13 @@ int prepare_sparse_parts(mi355gp_sparse* s, int nparts, const mi355gp_part* part
     for (int i = 0; i < nparts; ++i) {
         SPart& p = s->parts[(size_t)i];
         if (int rc = parse_part(parts[i], (int)D, accepted, "sparse path", &p)) return rc;
+        if (p.coreg()) {
+            if (int rc = coreg_check_data(s, p)) return rc;             // before any launch reads an index of X
+            if (!p.cgNM) HIP_CHECK(p.cgNM.alloc(COREG_REC));
+            if (!p.cgMM) HIP_CHECK(p.cgMM.alloc(COREG_REC));
+            HIP_CHECK(s->cgPart.need((size_t)2048 * COREG_REC));
+            HIP_CHECK(s->cgChunk.need(COREG_REC));
+        }
         if (int rc = p.upload(s->st)) return rc;
     }
     s->terms = group_terms(s->parts);
@@ -544,6 +598,9 @@ int mi355gp_sparse_set_data(mi355gp_sparse* s, const double* X, int64_t N, int D
     HIP_CHECK(hipMalloc(&s->dRowR, sizeof(double) * N));
     HIP_CHECK(hipMemcpy(s->dX, X, sizeof(double) * N * D, hipMemcpyHostToDevice));
     HIP_CHECK(hipMemcpy(s->dY, Y, sizeof(double) * N * Dy, hipMemcpyHostToDevice));
+    s->coreg_ok.clear();                                        // (Coregionalize: the rows' indices are checked against this copy)
+    if (s->take_coreg) s->hX.assign(X, X + N * D);
+    else std::vector<double>().swap(s->hX);
     double t = 0.0;
     s->rowYY.assign((size_t)N, 0.0);
     for (int64_t i = 0; i < N; ++i) {
@@ -608,6 +665,9 @@ int mi355gp_sparse_set_inputs(mi355gp_sparse* s, const double* X, const double* 
     if (S && !s->dSvar) HIP_CHECK(hipMalloc(&s->dSvar, sizeof(double) * N * D));
     HIP_CHECK(hipMemcpy(s->dX, X, sizeof(double) * N * D, hipMemcpyHostToDevice));
     if (S) HIP_CHECK(hipMemcpy(s->dSvar, S, sizeof(double) * N * D, hipMemcpyHostToDevice));
+    s->coreg_ok.clear();                                        // (as set_data: no stale rows for a later index check)
+    if (s->take_coreg) s->hX.assign(X, X + N * D);
+    else std::vector<double>().swap(s->hX);
     s->have_result = s->winv_ok = s->svgp_result = false;
     return 0;
 }
@@ -758,6 +818,14 @@ void sparse_kmm_gradients(mi355gp_sparse* s) {
             launch_kbuild_cross(st, pf.kp, pf.XtZ, mp, m, pf.XtZ, mp, m, dst, mp, 0, /*diag_same=*/1, mul);
         });
         if (prod) hipLaunchKernelGGL(k_mm_mul, grid2d(mp, mp), dim3(256), 0, st, s->T1, s->dLdKmm, mp);
+        if (p.coreg()) {
+            // the bucketed pass over the whole M x M matrix (dL_dKmm is symmetric; every element once): S[a][b] = the sum over
+            // rows of output a and columns of output b, blocks combined in block order; gradients_X is zero (coregionalize.py:153)
+            const int P2 = p.ard_in * p.ard_in;
+            const int nb = launch_grad_coreg(st, false, p.kp, p.XtZ, mp, m, p.XtZ, mp, m, prod ? s->T1 : s->dLdKmm, mp, nullptr, 0, s->cgPart);
+            launch_reduce_partials(st, s->cgPart, nb, P2, p.cgMM);
+            continue;
+        }
         launch_grad_generic(st, p.kp, p.XtZ, mp, m, p.XtZ, mp, m, 1, prod ? s->T1 : s->dLdKmm, mp, s->gradPart,
                             p.stationary() ? s->T1 : nullptr, mp);
         for (int g = 0; g < (p.kp.ard ? groups : 1); ++g)
@@ -775,14 +843,14 @@ void sparse_kmm_gradients(mi355gp_sparse* s) {
 // ---- the phases an inference family is built from ---------------------------------------------------------
 // Opens a call (the caller holds the EngineShared gate): the buffers for M inducing points and the part list; the previous
 // result is forgotten
-int sparse_open(mi355gp_sparse* s, int nparts, const mi355gp_part* parts, int64_t M) {
+int sparse_open(mi355gp_sparse* s, int nparts, const mi355gp_part* parts, int64_t M, bool coreg) {
     HIP_CHECK(hipSetDevice(s->device));
     if (M != s->m)
         if (int rc = alloc_m(s, M)) return rc;
     s->have_result = s->winv_ok = s->svgp_result = s->pep_result = false;
     s->kmm_jitter = 1e-8;
     s->h_info[0] = s->h_info[1] = 0;
-    return prepare_sparse_parts(s, nparts, parts);
+    return prepare_sparse_parts(s, nparts, parts, coreg);
 }
 
 // Starts the stream work of a call: the precision vector (nbeta = 1: beta[0] for every row, filled on the device; nbeta = n:
@@ -841,8 +909,21 @@ int sparse_rows_gradients_reset(mi355gp_sparse* s) {
     for (SPart& p : s->parts) {
         HIP_CHECK(hipMemsetAsync(p.gradNM, 0, sizeof(double) * rec_doubles(s), s->st));
         HIP_CHECK(hipMemsetAsync(p.HX, 0, sizeof(double) * hsum_doubles(s), s->st));
+        if (p.coreg()) HIP_CHECK(hipMemsetAsync(p.cgNM, 0, sizeof(double) * COREG_REC, s->st));
     }
     return 0;
+}
+
+// The other factor of part pi where its term is exactly one stationary factor times one Coregionalize factor and the pass fused
+// over the two (k_grad_cols_icm) applies (grad_cols_icm_applies, the launcher's own list of conditions) and fuse_cols is on.
+// -1 otherwise
+static int icm_partner(const mi355gp_sparse* s, size_t pi) {
+    const std::vector<int>& t = s->terms[(size_t)s->parts[pi].tix];
+    if (!s->fuse_cols || t.size() != 2) return -1;
+    const SPart &a = s->parts[(size_t)t[0]], &b = s->parts[(size_t)t[1]];
+    if (!((a.stationary() && b.coreg()) || (a.coreg() && b.stationary()))) return -1;
+    if (!grad_cols_icm_applies(s->D, (a.coreg() ? a : b).ard_in, s->mp)) return -1;      // (what the launcher itself asks)
+    return (size_t)t[0] == pi ? t[1] : t[0];
 }
 
 // The row-gradient step of one chunk of rc rows (scaled into the parts' XtC): from W, the chunk's rows of dL_dKnm without the
@@ -861,10 +942,47 @@ void sparse_rows_gradients(mi355gp_sparse* s, long rc, const double* W, double* 
         SPart& p = s->parts[pi];
         if (p.kp.kind == MI355GP_WHITE) continue;        // White: K(X, Z) = 0, no contribution (static.py:89-93)
         int nbk = 0, ns = 0;
+        // a term that is exactly stationary x Coregionalize (ICM; one such term per summand of an LCM), D <= 16: both factors'
+        // gradients from ONE pass over the weights (k_grad_cols_icm), made when the stationary factor comes up; fuse_cols off
+        // (or a pass that does not apply) leaves both to the product route below
+        const int partner = icm_partner(s, pi);
+        if (partner >= 0) {
+            if (p.coreg()) continue;                     // (done with its stationary partner)
+            // (icm_partner has asked grad_cols_icm_applies, the launcher's own conditions: the launch is made, ns >= 1)
+            SPart& c = s->parts[(size_t)partner];
+            ns = launch_grad_cols_icm(st, p.kp, c.kp, p.XtC, chunk, rc, p.XtZ, mp, m, mp, c.XtC, chunk, c.XtZ, mp, W, mp, rk, s->gradPart,
+                                      s->colPart, s->cgPart, &nbk);
+            for (int g = 0; g < (p.kp.ard ? groups : 1); ++g)
+                launch_reduce_partials(st, s->gradPart + (long)g * nbk * GP_STRIDE, nbk, GP_STRIDE, s->gradChunk + (long)g * GP_STRIDE);
+            hipLaunchKernelGGL(k_vec_axpy, dim3((unsigned)((gsz + 255) / 256)), dim3(256), 0, st, p.gradNM, s->gradChunk, gsz, 1.0);
+            launch_sum_splits(st, s->colPart, mp * (D + 1), ns, 1, p.HX);
+            const int P2 = c.ard_in * c.ard_in;
+            launch_reduce_partials(st, s->cgPart, nbk, P2, s->cgChunk);
+            hipLaunchKernelGGL(k_vec_axpy, dim3(1), dim3(256), 0, st, (double*)c.cgNM, (const double*)s->cgChunk, (long)P2, 1.0);
+            continue;
+        }
         const bool prod = emit_other_factors(s->terms, p.tix, pi, scratch, [&](int f, double* dst, const double* mul, int, bool) {
             const SPart& pf = s->parts[(size_t)f];
             launch_kbuild_cross(st, pf.kp, pf.XtC, chunk, rc, pf.XtZ, mp, m, dst, mp, 0, 0, mul);
         });
+        if (p.coreg()) {
+            // the bucketed pass (k_grad_coreg) over the weights in memory -- dL_dKnm times the other factors' covariance, or
+            // dL_dKnm itself formed from the rank term -- every element once; the chunk's S is the blocks' records summed in
+            // block order, and the chunks are added in chunk order.  No H: gradients_X is zero (coregionalize.py:153-154)
+            const double* g = W;
+            if (prod) {
+                form_times();
+                g = scratch;
+            } else if (rk.Y) {
+                launch_form_rank_weights(st, W, mp, rc, m, rk, scratch);
+                g = scratch;
+            }
+            const int P2 = p.ard_in * p.ard_in;
+            const int nb = launch_grad_coreg(st, false, p.kp, p.XtC, chunk, rc, p.XtZ, mp, m, g, mp, nullptr, 0, s->cgPart);
+            launch_reduce_partials(st, s->cgPart, nb, P2, s->cgChunk);
+            hipLaunchKernelGGL(k_vec_axpy, dim3(1), dim3(256), 0, st, (double*)p.cgNM, (const double*)s->cgChunk, (long)P2, 1.0);
+            continue;
+        }
         if (p.linear()) {
             // HX = g^T x~ is all there is (k_grad_cols_lin); the theta record follows on the host (sparse_assemble_gradients).
             // A factor of a product, D > 16: the weights in memory (launch_grad returns without a launch for a kind past the
@@ -925,8 +1043,21 @@ int sparse_fetch_gradients(mi355gp_sparse* s, bool with_nm, KernGrads* h) {
     h->HX.assign(np_ * hsz, 0.0);
     h->HZ.assign(np_ * hsz, 0.0);
     h->Zs.assign(np_ * zsz, 0.0);
+    h->cnm.clear();
+    h->cmm.clear();
+    for (const SPart& p : s->parts)
+        if (p.coreg() && h->cmm.empty()) {
+            h->cnm.assign(np_ * COREG_REC, 0.0);
+            h->cmm.assign(np_ * COREG_REC, 0.0);
+        }
     for (size_t i = 0; i < np_; ++i) {
         SPart& p = s->parts[i];
+        if (p.coreg()) {                                  // S of the two sides; no record of the stationary shape, no H sums
+            const size_t P2 = (size_t)p.ard_in * p.ard_in;
+            if (with_nm) HIP_CHECK(hipMemcpyAsync(h->cnm.data() + i * COREG_REC, p.cgNM, sizeof(double) * P2, hipMemcpyDeviceToHost, s->st));
+            HIP_CHECK(hipMemcpyAsync(h->cmm.data() + i * COREG_REC, p.cgMM, sizeof(double) * P2, hipMemcpyDeviceToHost, s->st));
+            continue;
+        }
         if (with_nm) HIP_CHECK(hipMemcpyAsync(h->gnm.data() + i * gsz, p.gradNM, sizeof(double) * gsz, hipMemcpyDeviceToHost, s->st));
         HIP_CHECK(hipMemcpyAsync(h->gmm.data() + i * gsz, p.gradMM, sizeof(double) * gsz, hipMemcpyDeviceToHost, s->st));
         if (!p.stationary() && !p.linear()) continue;
@@ -954,6 +1085,17 @@ void sparse_assemble_gradients(const mi355gp_sparse* s, const KernGrads& h, doub
             const double* b = h.gmm.data() + i * gsz;
             for (size_t k = 0; k < gsz; ++k) ab[k] = h.with_nm ? a[k] + b[k] : b[k];
             const SPart& p = s->parts[i];
+            if (p.coreg()) {                             // S = S_nm + S_mm in B's order, the per-output diagonal sums on dB[a][a]
+                const int P2 = p.ard_in * p.ard_in;
+                const double* cn = h.cnm.data() + i * COREG_REC;
+                const double* cm = h.cmm.data() + i * COREG_REC;
+                for (int c = 0; c < P2; ++c) {
+                    o[c] = h.with_nm ? cn[c] + cm[c] : cm[c];
+                    if (!h.ddiag.empty()) o[c] += h.ddiag[(size_t)(o - dtheta_out) + c];
+                }
+                o += P2;
+                continue;
+            }
             if (p.linear() && h.with_nm) {               // the Knm record: sum_j z~_jq HX[j][q] per dimension (k_grad_cols_lin)
                 const double* hx = h.HX.data() + i * hsz;
                 const double* zs = h.Zs.data() + i * (size_t)D * mp;
@@ -1246,7 +1388,8 @@ int mi355gp_vardtc_inference_sum(mi355gp_sparse* s, int nparts, const mi355gp_pa
     const bool het = noise_len > 1;
     ARG_CHECK(!het || dnoise_rows_out, "per-point noise: dnoise_rows_out (N x Dy) is required");
     EngineShared gate(s->device);
-    if (int rc = sparse_open(s, nparts, parts, M)) return rc;
+    if (int rc = sparse_open(s, nparts, parts, M, /*coreg=*/true)) return rc;
+    if (int rc = coreg_check_points(s, Z, M, "inducing")) return rc;       // (X's: prepare_sparse_parts; no kernel has run yet)
     const long n = s->n;
     // per-point precision beta_n = 1 / max(noise_n, 1e-8) (var_dtc.py:78-80)
     // (scalar noise: the three sums are closed forms -- unused by the homoscedastic formulas -- and the precision vector is filled on
@@ -1843,7 +1986,8 @@ int mi355gp_sparse_predict(mi355gp_sparse* s, int nparts, const mi355gp_part* pa
     ARG_CHECK(Xnew && Mn > 0 && mu_out, "mi355gp_sparse_predict: bad arguments");
     HIP_CHECK(hipSetDevice(s->device));
     EngineShared gate(s->device);
-    if (int rc = prepare_sparse_parts(s, nparts, parts)) return rc;
+    if (int rc = prepare_sparse_parts(s, nparts, parts, /*coreg=*/true)) return rc;
+    if (int rc = coreg_check_points(s, Xnew, Mn, "new-point")) return rc;
     hipStream_t st = s->st;
     scale_for_parts(s, s->dZ, s->m, s->mp, true);
     if (int rc = ensure_winv(s)) return rc;
@@ -2040,6 +2184,21 @@ int mi355gp_sparse_set_linear(mi355gp_sparse* s, int on) {
     return 0;
 }
 
+// Whether mi355gp_vardtc_inference_sum, mi355gp_sparse_predict and mi355gp_sparse_kdiag of this context take Coregionalize
+// (kind 8) parts (include/mi355gp_sparse_coreg.h); a new context does not.  On: the next set_data keeps the rows on the host
+int mi355gp_sparse_set_coregionalize(mi355gp_sparse* s, int on) {
+    ARG_CHECK(s, "mi355gp_sparse_set_coregionalize: NULL context");
+    s->take_coreg = on != 0;
+    return 0;
+}
+
+// The A/B switch of the second pass (include/mi355gp_debug_sparse_coreg.h): off, every part takes the unfused route
+int mi355gp_dbg_sparse_set_fuse_cols(mi355gp_sparse* s, int on) {
+    ARG_CHECK(s, "mi355gp_dbg_sparse_set_fuse_cols: NULL context");
+    s->fuse_cols = on != 0;
+    return 0;
+}
+
 // Whether the uncertain-input entry points of this context take one RBF or Linear part with Bias and White parts
 // (include/mi355gp_psi_lin.h); on also switches Linear on (prediction at certain points needs it), off leaves that as it is
 int mi355gp_sparse_set_psi_lin_bias(mi355gp_sparse* s, int on) {
@@ -2060,8 +2219,13 @@ int mi355gp_sparse_kdiag(mi355gp_sparse* s, int nparts, const mi355gp_part* part
     ARG_CHECK(nparts >= 1 && nparts <= KDIAG_MAX_PARTS && parts, "mi355gp_sparse_kdiag: between 1 and 16 kernel parts");
     ARG_CHECK(!sharded(s), "mi355gp_sparse_kdiag: a row-sharded context is not supported (the sums would need a collective)");
     std::vector<PartSpec> ps((size_t)nparts);
-    for (int i = 0; i < nparts; ++i)
-        if (int rc = parse_part(parts[i], s->D, KS_STATIONARY | KS_STATIC | KS_LINEAR, "mi355gp_sparse_kdiag", &ps[(size_t)i])) return rc;
+    for (int i = 0; i < nparts; ++i) {
+        if (int rc = parse_part(parts[i], s->D, KS_STATIONARY | KS_STATIC | KS_LINEAR | (s->take_coreg ? KS_COREG : 0u),
+                                "mi355gp_sparse_kdiag", &ps[(size_t)i]))
+            return rc;
+        if (ps[(size_t)i].coreg())
+            if (int rc = coreg_check_data(s, ps[(size_t)i])) return rc;
+    }
     const Terms terms = group_terms(ps);
     DiagDesc ds;
     std::vector<double> coef, sums;

@@ -14,6 +14,9 @@ struct EpdtcState;             // epdtc.hip
 
 struct SPart : DevicePart {
     DevBuf XtZ, XtC, HX, HZ, gradNM, gradMM;   // (HX / HZ of a Linear part: mp x D, no ones column)
+    // a Coregionalize part: S (P x P in COREG_REC doubles) of update_gradients_full(dL_dKnm, X, Z), summed over the chunks in
+    // chunk order, and of update_gradients_full(dL_dKmm, Z); S[a][b] = the weights over rows of output a and columns of output b
+    DevBuf cgNM, cgMM;
 };
 
 // a device array that grows when more is asked of it and keeps its size otherwise
@@ -105,6 +108,15 @@ struct mi355gp_sparse {
     GrowBuf linDmu, linEZ, biasC, biasV, biasT, biasAdd, biasPsi2;
     DiagDesc diag;
     GrowBuf diagCoef, dKd, diagW, diagPart, diagSums;   // nparts x D coefficients; Kdiag(X) (n); a family's weights (n); records
+    // mi355gp_sparse_set_coregionalize (include/mi355gp_sparse_coreg.h): mi355gp_vardtc_inference_sum and mi355gp_sparse_predict
+    // take Coregionalize (kind 8) parts (off: refused by name, as before).  hX: set_data's X on the host, kept while the switch
+    // is on, so that a call can check the index column its Coregionalize part names (coreg_check_index) before any launch;
+    // coreg_ok: the (column, P) pairs already checked against it.  cgPart / cgChunk: the block records of the bucketed pass
+    // (2048 x P x P) and their sum for one chunk.
+    bool take_coreg = false;
+    std::vector<double> hX;
+    std::vector<std::pair<int, int>> coreg_ok;
+    GrowBuf cgPart, cgChunk;
 };
 
 // ---- the per-point diagonal (sparse.hip) ---------------------------------------------------------------------------
@@ -126,6 +138,8 @@ struct KernGrads {             // the parts' records and sums on the host (spars
     // per-point diagonal: update_gradients_diag of every part in theta order (sparse_diag_dtheta); empty: Kdiag is one number
     // and sparse_assemble_gradients adds kdiag_coef to the variances
     std::vector<double> ddiag;
+    // the S records of the Coregionalize parts (COREG_REC doubles per part; empty: the expression has none)
+    std::vector<double> cnm, cmm;
 };
 struct NewPoints {             // K(Z, X*) and what a prediction derives from it (sparse_newpoints)
     PointSet xs;
@@ -137,7 +151,9 @@ struct NewPoints {             // K(Z, X*) and what a prediction derives from it
 };
 bool sharded(const mi355gp_sparse* s);
 int alloc_m(mi355gp_sparse* s, long M);
-int prepare_sparse_parts(mi355gp_sparse* s, int nparts, const mi355gp_part* parts);
+// coreg: the entry point evaluates Coregionalize parts (VarDTC with certain inputs and its prediction); the others refuse them
+// by name even on a context that was asked
+int prepare_sparse_parts(mi355gp_sparse* s, int nparts, const mi355gp_part* parts, bool coreg = false);
 double sparse_other_variances(const mi355gp_sparse* s, size_t p);
 bool skip_white(const mi355gp_sparse* s, const std::vector<int>& t);
 void scale_for_parts(mi355gp_sparse* s, const double* src, long rows, long ldt, bool inducing);
@@ -152,7 +168,7 @@ int potrf_checked(hipStream_t st, double* A, double* X, double* T, double* W, lo
                   const std::function<void()>& rebuild);
 void sparse_kmm_gradients(mi355gp_sparse* s);
 // the phases an inference family is built from, in the order of a call (each is described where it is defined)
-int sparse_open(mi355gp_sparse* s, int nparts, const mi355gp_part* parts, int64_t M);
+int sparse_open(mi355gp_sparse* s, int nparts, const mi355gp_part* parts, int64_t M, bool coreg = false);
 int sparse_start(mi355gp_sparse* s, const double* Z, const double* beta, long nbeta);
 int sparse_cross_rows(mi355gp_sparse* s, long r0, long rc, long z0, long z1, const double* V);
 int sparse_rows_gradients_reset(mi355gp_sparse* s);

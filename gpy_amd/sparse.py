@@ -18,6 +18,12 @@ and one noise variance; `grad_dict` then has the reference's keys `dL_dpsi0 / dL
 `VarDTC(psi_lin_bias=True)` (and the models' keyword of the same name) takes one RBF or Linear part with Bias and White parts
 there (`mi355gp_sparse_set_psi_lin_bias`, include/mi355gp_psi_lin.h); made without it the classes refuse those as before.
 
+Multi-output kernels: `VarDTC(coregionalize=True)` takes Coregionalize factors with certain inputs -- the `ICM` / `LCM` kernels of
+`util.multioutput` with a `MixedNoise` likelihood -- and `SparseGPCoregionalizedRegression` (reference
+`models/sparse_gp_coregionalized_regression.py`) is the `SparseGP` built on it, with inducing inputs that carry a fixed output
+index (`mi355gp_sparse_set_coregionalize`, include/mi355gp_sparse_coreg.h); made without the keyword the classes refuse the kind
+as before.
+
 `BayesianGPLVM` (reference `models/bayesian_gplvm.py`) is the `SparseGP` whose inputs are parameters: it consumes those
 gradients, subtracts the KL term of the standard normal prior, uploads a step's new means and variances without Y
 (`mi355gp_sparse_set_inputs`) and predicts at uncertain new points on the device (`mi355gp_sparse_predict_uncertain`).
@@ -26,7 +32,7 @@ import numpy as np
 
 from . import _lib
 from .inference import LatentFunctionInference
-from .kern import RBF, Add, Bias, Linear, Prod, White, diag_depends_on_point, exact_only_leaves, sparse_refused_leaves
+from .kern import RBF, Add, Bias, Coregionalize, Linear, Prod, White, diag_depends_on_point, exact_only_leaves, has_coregionalize
 from .lazy import ArrayIdentity, LazyMM, LazyNM, LazyPsi1, freeze, kernel_signature
 from .likelihoods import Gaussian
 from .linalg import LinAlgError, jitter_ladder
@@ -125,17 +131,26 @@ def _host_predictive_gradients(kern, Xnew, pred_var, woodbury_vector, woodbury_i
     return mean_jac, var_jac + kern.gradients_X(a2, Xnew, pred_var)
 
 
-def sparse_path_kernel_check(kern, linear=False):
+def sparse_path_kernel_check(kern, linear=False, coregionalize=False):
     """What the sparse device context evaluates (VarDTC and SVGP alike); anything else is refused by name.  `linear`: the
     inference class was made with `linear=True` and takes Linear leaves; without it they are refused like the other kinds
-    that only the exact path has, as they were before the sparse path could evaluate them."""
-    new_kinds = sparse_refused_leaves(kern) if linear else exact_only_leaves(kern)
-    if new_kinds:
-        hint = "; Linear: make the inference class with linear=True" if "Linear" in new_kinds else ""
+    that only the exact path has, as they were before the sparse path could evaluate them.  `coregionalize`: likewise for
+    Coregionalize leaves (`VarDTC(coregionalize=True)`, the one class that takes them), as factors of a product -- what `ICM` /
+    `LCM` build -- with at most 16 outputs."""
+    refused = [k for k in exact_only_leaves(kern)
+               if not (linear and k == "Linear") and not (coregionalize and k == "Coregionalize")]
+    if refused:
+        hint = "; Linear: make the inference class with linear=True" if "Linear" in refused else ""
+        if "Coregionalize" in refused:
+            hint += "; Coregionalize: VarDTC(coregionalize=True) or SparseGPCoregionalizedRegression"
         raise NotImplementedError("the MI355X sparse path does not evaluate %s kernels (the exact GPRegression path does%s)"
-                                  % (", ".join(sorted(set(new_kinds))), hint))
-    # stationary and Linear kernels, products (Prod, reference `prod.py:58-99`) of stationary / Linear / Bias factors, and sums
-    # (Add) of those and of White / Bias parts
+                                  % (", ".join(sorted(set(refused))), hint))
+    for k in (kern.leaves() if coregionalize else []):
+        if isinstance(k, Coregionalize) and k.output_dim > 16:
+            raise NotImplementedError("the MI355X sparse path evaluates Coregionalize kernels with at most 16 outputs, %r has %d"
+                                      % (k.name, k.output_dim))
+    # stationary and Linear kernels, products (Prod, reference `prod.py:58-99`) of stationary / Linear / Bias / Coregionalize
+    # factors, and sums (Add) of those and of White / Bias parts
     def _prod_ok(k):
         return isinstance(k, Prod) and not any(isinstance(f, (White, Add, Prod)) for f in k.parts)
     lone = getattr(kern, "is_leaf", False) and kern.fused_alone          # (not a lone White / Bias)
@@ -159,6 +174,8 @@ class SparseSession(LatentFunctionInference):
     posterior or a lazy view knows whether it is still the context's latest result.  An `inference` method is its refusals,
     `_ensure`, one `_run` over a context call and the results built by `_posterior` / `_device_dict`."""
     _device_members = ("_ctx", "_X", "_Y")
+
+    coregionalize = False       # `VarDTC(coregionalize=True)` alone takes Coregionalize leaves; the other families have no keyword
 
     def __init__(self, device=0, maxtries=5, linear=False, psi_lin_bias=False):
         self.device, self.maxtries = device, maxtries
@@ -184,6 +201,8 @@ class SparseSession(LatentFunctionInference):
                 self._ctx.set_psi_lin_bias(True)                       # (switches Linear on as well)
             elif self.linear:
                 self._ctx.set_linear(True)
+            if self.coregionalize:
+                self._ctx.set_coregionalize(True)                      # (before set_data: it keeps the rows for the index check)
         if self._X is not None and self._X.matches(X) and self._Y.matches(Y):
             return False
         self._ctx.set_data(X, Y)
@@ -216,6 +235,12 @@ class VarDTC(SparseSession):
     const_jitter = 1e-8
     _device_members = SparseSession._device_members + ("_S",)
     _S = None                                                        # identity of the uploaded input variances
+
+    def __init__(self, device=0, maxtries=5, linear=False, psi_lin_bias=False, coregionalize=False):
+        """`coregionalize=True`: the kernel may hold Coregionalize factors (`util.multioutput.ICM` / `LCM`) with certain inputs;
+        the context is told so (`mi355gp_sparse_set_coregionalize`).  Made without it the class refuses them by name, as before."""
+        super(VarDTC, self).__init__(device=device, maxtries=maxtries, linear=linear, psi_lin_bias=psi_lin_bias)
+        self.coregionalize = bool(coregionalize)
 
     def to_dict(self):
         return {"class": "GPy.inference.latent_function_inference.var_dtc.VarDTC"}
@@ -285,7 +310,7 @@ class VarDTC(SparseSession):
                   dL_dKmm=None, psi0=None, psi1=None, psi2=None, Z_tilde=None):
         uncertain = isinstance(X, NormalPosterior)
         if not uncertain:
-            sparse_path_kernel_check(kern, self.linear)
+            sparse_path_kernel_check(kern, self.linear, self.coregionalize)
         if any(a is not None for a in (Lm, dL_dKmm, psi0, psi1, psi2)):
             raise NotImplementedError("precomputed statistics are not accepted by the MI355X sparse path")
         if uncertain:
@@ -298,6 +323,9 @@ class VarDTC(SparseSession):
         m = 0 if mean_function is None else mean_function.f(X)
         Xs, Zs = kern._slice_X(X), kern._slice_X(Z)
         R = _lib.f64(Y - m)
+        if has_coregionalize(kern):
+            self._refuse_sharded("a Coregionalize kernel is not supported by a row-sharded sparse context: its Kdiag depends on the "
+                                 "point, so the sums over rows would need another all-reduce")
         if diag_depends_on_point(kern):
             self._refuse_sharded("a Linear kernel is not supported by a row-sharded sparse context: its Kdiag depends on the "
                                  "point, so the sums over rows would need another all-reduce")
@@ -459,6 +487,56 @@ class SparseGPRegression(SparseGP):
                                                                    VarDTC(device=device, linear=True) if linear else None),
                                                  name="sparse_gp", device=device, mean_function=mean_function,
                                                  X_variance=X_variance)
+
+
+class SparseGPCoregionalizedRegression(SparseGP):
+    """Sparse multi-output GP regression with coregionalization (reference
+    `GPy/models/sparse_gp_coregionalized_regression.py:11-99`): a `SparseGP` with `VarDTC(coregionalize=True)`, the per-output
+    inputs stacked with an output-index column (`util.multioutput.build_XY`), an `ICM` of `RBF(D - 1)` unless a kernel is given,
+    `MixedNoise` (one Gaussian noise per output) and inducing inputs that carry an output index: `Z_list[i]` belongs to
+    output i, by default `num_inducing` (one number, or one per output) random rows of `X_list[i]`.  The flat parameter order
+    is [Z, kernel, noise]; the index column of Z is fixed (the reference's `self['.*inducing'][:, -1].fix()`): its gradient is
+    exactly zero and no assignment to the parameter vector moves it.  `predict(Xnew, Y_metadata={'output_index': ...})` takes
+    Xnew with the index column appended."""
+
+    def __init__(self, X_list, Y_list, Z_list=None, kernel=None, likelihoods_list=None, num_inducing=10, X_variance=None,
+                 name="SGPCR", W_rank=1, kernel_name="coreg", device=0, seed=None):
+        from .util import multioutput
+        if X_variance is not None:
+            raise NotImplementedError("SparseGPCoregionalizedRegression: X_variance (uncertain inputs) is not implemented on the "
+                                      "MI355X path: a Coregionalize part has no psi-statistics")
+        X, Y, self.output_index = multioutput.build_XY(X_list, Y_list)
+        Ny = len(Y_list)
+        if kernel is None:
+            kernel = multioutput.ICM(input_dim=X.shape[1] - 1, num_outputs=Ny, kernel=RBF(X.shape[1] - 1, device=device),
+                                     W_rank=W_rank, name=kernel_name)
+        likelihood = multioutput.build_likelihood(Y_list, self.output_index, likelihoods_list)
+        if Z_list is not None and len(Z_list):
+            assert len(Z_list) == Ny, "Number of outputs do not match length of inducing inputs list."
+            Z_list = [np.asarray(Zi, dtype=np.float64) for Zi in Z_list]
+        else:                                        # (a list of the call's own: the reference appends into its shared default)
+            ni = np.asarray([num_inducing] * Ny if isinstance(num_inducing, (int, np.integer)) else num_inducing)
+            assert ni.size == Ny, "Number of outputs do not match length of inducing inputs list."
+            rng = np.random.default_rng(seed)
+            Z_list = [np.asarray(Xi, dtype=np.float64)[rng.permutation(np.shape(Xi)[0])[:n]].copy() for n, Xi in zip(ni, X_list)]
+        Z, _, Iz = multioutput.build_XY(Z_list)
+        self._Z_index = np.asarray(Iz, dtype=np.float64).ravel()       # before SparseGP.__init__: the first evaluation reads Z
+        super(SparseGPCoregionalizedRegression, self).__init__(X, Y, Z, kernel, likelihood,
+                                                               inference_method=VarDTC(device=device, coregionalize=True),
+                                                               name=name, device=device,
+                                                               Y_metadata={"output_index": self.output_index})
+
+    @property
+    def param_array(self):
+        return SparseGP.param_array.fget(self)
+
+    @param_array.setter
+    def param_array(self, x):
+        """as `Parameterized.param_array`, with the index column of Z held at the outputs the inducing inputs belong to"""
+        x = np.array(x, dtype=np.float64).ravel()
+        D = self.input_dim
+        x[D - 1:self.Z.size:D] = self._Z_index
+        SparseGP.param_array.fset(self, x)
 
 
 class BayesianGPLVM(SparseGP):
