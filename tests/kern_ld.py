@@ -443,14 +443,14 @@ def lgamma(x, dt=LD):
 
 def exact(specs, X, Y, noise, nu=None, jitter=1e-8, dt=LD, max_n=129):
     """ExactGaussianInference (exact_gaussian_inference.py) or, with nu, the Student-t process (exact_studentt_inference.py:20-52):
-    dict(lml, logdet, alpha, L, Ki, dL_dK, dtheta, dtheta_cond, dnoise, lv)"""
+    dict(lml, logdet, alpha, L, Linv, Ki, dL_dK, dtheta, dtheta_cond, dnoise)"""
     lv = leaves(specs, X, None, dt)
     Kx = K(specs, X, None, dt, lv)
     Y = _a(Y, dt)
     N, Dy = Y.shape
     pi = _c(dt)["pi"]
     Ky = np.array(Kx)
-    Ky[np.arange(N), np.arange(N)] += (dt(0) if nu is not None else dt(noise)) + dt(jitter)
+    Ky[np.arange(N), np.arange(N)] += (dt(0) if nu is not None else _a(noise, dt)) + dt(jitter)      # noise: one variance or N
     L = cholesky(Ky, max_n)
     Li = solve_lower(L, np.eye(N, dtype=dt))
     Ki = matmul(Li.T, Li)
@@ -469,7 +469,7 @@ def exact(specs, X, Y, noise, nu=None, jitter=1e-8, dt=LD, max_n=129):
         dL_dK = ((nu + N) / (nu + beta - 2) * aaT - Ki) / 2
         dnoise = None
     val, cond = dtheta(specs, dL_dK, X, None, dt, lv)
-    return dict(lml=lml, logdet=logdet, alpha=alpha, L=L, Ki=Ki, dL_dK=dL_dK, dtheta=val, dtheta_cond=cond, dnoise=dnoise)
+    return dict(lml=lml, logdet=logdet, alpha=alpha, L=L, Linv=Li, Ki=Ki, dL_dK=dL_dK, dtheta=val, dtheta_cond=cond, dnoise=dnoise)
 
 
 def predict(specs, X, ex, Xs, dt=LD):
