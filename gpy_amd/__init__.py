@@ -19,15 +19,15 @@ from .likelihoods import Bernoulli, Gaussian, HeteroscedasticGaussian, MixedNois
 from .models import (GP, GPClassification, GPCoregionalizedRegression, GPHeteroscedasticRegression, GPRegression,
                      GPVariationalGaussianApproximation)
 from .posterior import PosteriorEP, PosteriorExact, StudentTPosterior
-from .sparse import BayesianGPLVM, SparseGP, SparseGPCoregionalizedRegression, SparseGPRegression, VarDTC
+from .sparse import SSGPLVM, BayesianGPLVM, SparseGP, SparseGPCoregionalizedRegression, SparseGPRegression, VarDTC
 from .pep import FITC, PEP
 from .epdtc import EPDTC, SparseGPClassification
 from .svgp import SVGPModel as SVGP
 from .svgp import SVGPPosterior
-from .variational import NormalPosterior, NormalPrior
+from .variational import NormalPosterior, NormalPrior, SpikeAndSlabPosterior, SpikeAndSlabPrior
 
 __all__ = ["RBF", "OU", "ExpQuad", "HeteroscedasticGaussian", "StudentTPosterior", "Matern52", "Matern32", "Exponential", "RatQuad", "Cosine", "Sinc", "ExpQuadCosine", "StdPeriodic", "Coregionalize", "Linear", "MLP", "Poly", "MixedNoise", "Stationary", "White", "Bias", "Add", "Prod", "Gaussian", "ExactGaussianInference", "ExactStudentTInference",
-           "PosteriorExact", "GP", "GPRegression", "GPHeteroscedasticRegression", "GPCoregionalizedRegression", "Laplace", "LaplacePosterior", "EP", "PosteriorEP", "Bernoulli", "StudentT", "Poisson", "GPClassification", "VarDTC", "SparseGP", "SparseGPRegression", "SparseGPCoregionalizedRegression", "SVGP", "SVGPPosterior", "NormalPosterior", "NormalPrior", "BayesianGPLVM", "FITC", "PEP", "EPDTC", "SparseGPClassification", "VarGauss", "VarGaussPosterior", "GPVariationalGaussianApproximation", "GaussianGridInference", "GridPosterior", "GpGrid", "GPRegressionGrid", "MI355GPError", "build", "device_count"]
+           "PosteriorExact", "GP", "GPRegression", "GPHeteroscedasticRegression", "GPCoregionalizedRegression", "Laplace", "LaplacePosterior", "EP", "PosteriorEP", "Bernoulli", "StudentT", "Poisson", "GPClassification", "VarDTC", "SparseGP", "SparseGPRegression", "SparseGPCoregionalizedRegression", "SVGP", "SVGPPosterior", "NormalPosterior", "NormalPrior", "SpikeAndSlabPosterior", "SpikeAndSlabPrior", "BayesianGPLVM", "SSGPLVM", "FITC", "PEP", "EPDTC", "SparseGPClassification", "VarGauss", "VarGaussPosterior", "GPVariationalGaussianApproximation", "GaussianGridInference", "GridPosterior", "GpGrid", "GPRegressionGrid", "MI355GPError", "build", "device_count"]
 
 # GPy's import paths, so that `import gpy_amd as GPy` reads like the reference on this path:
 #   GPy.kern.RBF, GPy.likelihoods.Gaussian, GPy.models.GPRegression / SparseGPRegression / GPHeteroscedasticRegression,
@@ -40,17 +40,20 @@ __all__ = ["RBF", "OU", "ExpQuad", "HeteroscedasticGaussian", "StudentTPosterior
 #   GPy.models.GPRegressionGrid, GPy.core.GpGrid, GPy.inference.latent_function_inference.GaussianGridInference (and
 #   .gaussian_grid_inference.GaussianGridInference, .grid_posterior.GridPosterior), GPy.kern.GridRBF,
 #   GPy.util.choleskies, GPy.models.BayesianGPLVM, GPy.util.initialization.initialize_latent,
-#   GPy.models.SparseGPCoregionalizedRegression
+#   GPy.models.SparseGPCoregionalizedRegression, GPy.models.ss_gplvm.SSGPLVM,
+#   GPy.core.parameterization.variational.SpikeAndSlabPosterior / SpikeAndSlabPrior
 from . import ep, epdtc, inference, kern, kron, laplace, likelihoods, link_functions, linalg, models, pep, sparse, svgp, util, vargauss  # noqa: E402
 import types as _types  # noqa: E402
 
 models.SparseGPRegression = SparseGPRegression
 models.SparseGPCoregionalizedRegression = SparseGPCoregionalizedRegression
 models.BayesianGPLVM = BayesianGPLVM
+models.ss_gplvm = _types.SimpleNamespace(SSGPLVM=SSGPLVM)         # (GPy.models.SSGPLVM itself keeps refusing: models.__getattr__)
 models.SparseGPClassification = SparseGPClassification
 models.GPRegressionGrid = GPRegressionGrid
 core = _types.SimpleNamespace(GP=GP, GpGrid=GpGrid, gp_grid=_types.SimpleNamespace(GpGrid=GpGrid), SparseGP=SparseGP, SVGP=SVGP, svgp=_types.SimpleNamespace(SVGP=SVGP), parameterization=_types.SimpleNamespace(
-    variational=_types.SimpleNamespace(NormalPosterior=NormalPosterior, NormalPrior=NormalPrior)))
+    variational=_types.SimpleNamespace(NormalPosterior=NormalPosterior, NormalPrior=NormalPrior,
+                                       SpikeAndSlabPosterior=SpikeAndSlabPosterior, SpikeAndSlabPrior=SpikeAndSlabPrior)))
 likelihoods.mixed_noise = _types.SimpleNamespace(MixedNoise=MixedNoise)
 inference.latent_function_inference = _types.SimpleNamespace(
     ExactGaussianInference=ExactGaussianInference, ExactStudentTInference=ExactStudentTInference, VarDTC=VarDTC,

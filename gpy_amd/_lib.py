@@ -88,6 +88,7 @@ def build(force=False):
     srcs.append(os.path.join(_HERE, "..", "include", "mi355gp_debug_sparse_coreg.h"))
     srcs.append(os.path.join(_HERE, "..", "include", "mi355gp_psi_lin.h"))
     srcs.append(os.path.join(_HERE, "..", "include", "mi355gp_debug_psi_lin.h"))
+    srcs.append(os.path.join(_HERE, "..", "include", "mi355gp_psi_ss.h"))
     srcs.append(os.path.join(_HERE, "..", "include", "mi355gp_vargauss.h"))
     srcs.append(os.path.join(_HERE, "..", "include", "mi355gp_kron.h"))
     product = os.path.join(_HERE, "libmi355gp.so")
@@ -243,6 +244,15 @@ PSI_LIN_ABI = {
 DEBUG_PSI_LIN_ABI = {
     "mi355gp_dbg_psi_lin_rows": [_ci, _ci, _dp] + [_c_dp] * 3 + [_cd, _cd, _dp, _dp, _dp, _cd, _i64, _i64, _ci, _ci, _dp, _ci, _c_dp],
 }
+# include/mi355gp_psi_ss.h: the RBF psi-statistics for spike-and-slab inputs, in its order (tests/test_oracle_psi_ss.py holds the
+# table against that header's prototypes)
+PSI_SS_ABI = {
+    "mi355gp_ssrbf_psi": [_ci, _cd, _dp, _ci, _dp, _i64, _dp, _dp, _dp, _i64, _ci] + [_c_dp] * 3,
+    "mi355gp_ssrbf_psi_grad": [_ci, _cd, _dp, _ci, _dp, _i64, _dp, _dp, _dp, _i64, _ci] + [_c_dp] * 4 + [_dp] * 6,
+    "mi355gp_sparse_set_binary_prob": [_vp, _c_dp, _i64, _ci],
+    "mi355gp_sparse_set_inputs_ss": [_vp, _dp, _dp, _dp, _i64, _ci],
+    "mi355gp_vardtc_inference_ss": [_vp, _ci, _parts, _dp, _i64, _dp, _i64, _cd, _dp] + [_c_dp] * 7,
+}
 # include/mi355gp_vargauss.h: the variational Gaussian approximation inside the Laplace session of an exact context, in its order
 # (tests/test_oracle_vargauss.py holds the table against that header's prototypes)
 VARGAUSS_ABI = {
@@ -278,7 +288,7 @@ def lib():
             build()
         L = ctypes.CDLL(LIB_PATH)
         for table in (ABI, DEBUG_LAUUM_ABI, DEBUG_TILEOPS_ABI, EPDTC_ABI, SPARSE_DIAG_ABI, SPARSE_COREG_ABI, DEBUG_SPARSE_COREG_ABI, PSI_LIN_ABI, DEBUG_PSI_LIN_ABI,
-                      VARGAUSS_ABI, KRON_ABI):
+                      PSI_SS_ABI, VARGAUSS_ABI, KRON_ABI):
             for name, argtypes in table.items():
                 getattr(L, name).argtypes = argtypes
         L.mi355gp_last_error.restype = L.mi355gp_version.restype = _str
@@ -731,6 +741,34 @@ class SparseContext(_Handle):
         res.update(trA=out[2], data_fit=out[3], dmu=dmu, dS=dS)
         return rc, res
 
+    def set_binary_prob(self, gamma):
+        """Slab probabilities (N x D, strictly inside (0, 1)) next to the means and variances: spike-and-slab inputs
+        (`mi355gp_sparse_set_binary_prob`).  None takes the context back to Gaussian inputs."""
+        if gamma is None:
+            check(lib().mi355gp_sparse_set_binary_prob(self._h, None, 0, 0), "mi355gp_sparse_set_binary_prob")
+            return
+        gamma = f64(gamma)
+        assert gamma.ndim == 2, "gamma must be N x D"
+        check(lib().mi355gp_sparse_set_binary_prob(self._h, _opt(gamma), gamma.shape[0], gamma.shape[1]),
+              "mi355gp_sparse_set_binary_prob")
+
+    def set_inputs_ss(self, X, S, gamma):
+        """Replaces means, variances and slab probabilities (`mi355gp_sparse_set_inputs_ss`); Y stays resident on the device."""
+        X, S, gamma = f64(X), f64(S), f64(gamma)
+        assert X.ndim == 2 and S.shape == X.shape and gamma.shape == X.shape, "X, S and gamma must be N x D"
+        check(lib().mi355gp_sparse_set_inputs_ss(self._h, X, S, gamma, X.shape[0], X.shape[1]), "mi355gp_sparse_set_inputs_ss")
+
+    def vardtc_ss(self, specs, Z, noise, extra_jitter=0.0, want_dq=True, want_stage_ms=False):
+        """One evaluation with spike-and-slab inputs (one RBF part alone or with White parts, ONE noise variance).
+        (info, dict(lml, dnoise, dtheta (concatenated), dZ, woodbury_vector, dmu, dS, dgamma[, stage_ms]))"""
+        arr, keep, ntheta = make_parts(specs)
+        noise = f64(np.atleast_1d(noise)).ravel()
+        dmu, dS, dg = (np.zeros((self.N, self.D)) if want_dq else None for _ in range(3))
+        rc, out, res = self._fit("mi355gp_vardtc_inference_ss", (len(specs), arr), ntheta, Z,
+                                 (noise, noise.size, float(extra_jitter)), (dmu, dS, dg), want_stage_ms)
+        res.update(trA=out[2], data_fit=out[3], dmu=dmu, dS=dS, dgamma=dg)
+        return rc, res
+
     def predict(self, specs, Xnew, full_cov=False, want_var=True):
         """(mu (M* x Dy), var (M* x 1) or cov) of the sparse posterior of the last call, on the device."""
         arr, keep, _ = make_parts(specs)
@@ -978,6 +1016,45 @@ def rbf_psi_grad(variance, lengthscale, ARD, Z, mu, S, dL_dpsi0=None, dL_dpsi1=N
     check(lib().mi355gp_rbf_psi_grad(device, *(args + (_opt(d0), _opt(d1), _opt(d2), dvar, dl, dZ, dmu, dS))),
           "mi355gp_rbf_psi_grad")
     return dvar[0], dl, dZ, dmu, dS
+
+
+def _ss_args(variance, lengthscale, ARD, Z, mu, S, gamma, weights):
+    args, w = _psi_args(variance, lengthscale, ARD, Z, mu, S, weights)
+    gamma = f64(gamma)
+    assert gamma.shape == args[5].shape, "gamma is N x D, as mu and S"
+    return args[:7] + (gamma,) + args[7:], w
+
+
+def ssrbf_psi(variance, lengthscale, ARD, Z, mu, S, gamma, weights=None, want_psi1=True, want_psi2=True, device=0):
+    """(psi1 (N x M) or None, psi2 = sum_n w_n psi2n (M x M) or None) of an RBF kernel for spike-and-slab inputs
+    gamma N(mu, diag S) + (1 - gamma) delta_0 (reference `ssrbf_psi_comp.py:209-288`), on the device."""
+    require_device(device)
+    args, keep = _ss_args(variance, lengthscale, ARD, Z, mu, S, gamma, weights)
+    M, N = args[4], args[8]
+    p1 = np.empty((N, M)) if want_psi1 else None
+    p2 = np.empty((M, M)) if want_psi2 else None
+    check(lib().mi355gp_ssrbf_psi(device, *(args + (_opt(p1), _opt(p2)))), "mi355gp_ssrbf_psi")
+    return p1, p2
+
+
+def ssrbf_psi_grad(variance, lengthscale, ARD, Z, mu, S, gamma, dL_dpsi0=None, dL_dpsi1=None, dL_dpsi2=None, weights=None,
+                   device=0):
+    """(dvariance, dlengthscale, dZ, dmu, dS, dgamma) from dL_dpsi0 (N), dL_dpsi1 (N x M), dL_dpsi2 (M x M, symmetrised inside)
+    (reference `ssrbf_psi_comp.py:290-398`), on the device."""
+    require_device(device)
+    args, keep = _ss_args(variance, lengthscale, ARD, Z, mu, S, gamma, weights)
+    M, N, D = args[4], args[8], args[9]
+    d0 = None if dL_dpsi0 is None else f64(np.ravel(dL_dpsi0))
+    d1 = None if dL_dpsi1 is None else f64(dL_dpsi1)
+    d2 = None if dL_dpsi2 is None else f64(dL_dpsi2)
+    assert d0 is None or d0.size == N
+    assert d1 is None or d1.shape == (N, M), "dL_dpsi1 must be N x M"
+    assert d2 is None or d2.shape == (M, M), "dL_dpsi2 must be M x M"
+    dvar, dl = np.zeros(1), np.zeros(D if ARD else 1)
+    dZ, dmu, dS, dg = np.zeros((M, D)), np.zeros((N, D)), np.zeros((N, D)), np.zeros((N, D))
+    check(lib().mi355gp_ssrbf_psi_grad(device, *(args + (_opt(d0), _opt(d1), _opt(d2), dvar, dl, dZ, dmu, dS, dg))),
+          "mi355gp_ssrbf_psi_grad")
+    return dvar[0], dl, dZ, dmu, dS, dg
 
 
 def potrf(A, device=0):

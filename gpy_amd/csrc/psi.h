@@ -1,5 +1,5 @@
 // psi.h -- launchers of the psi-statistics kernels (psi.hip) shared by the stateless entry points and the uncertain-input
-// fit of the sparse context (sparse.hip).  Host code only; see psi.hip for the formulas and the buffer layouts.
+// fit of the sparse context (sparse.hip).  Host code but for psi_tile; see psi.hip for the formulas and the buffer layouts.
 #pragma once
 #include "internal.h"
 
@@ -14,6 +14,15 @@
 #define PSI_CONTRACT_RB(QP) ((QP) > 32 ? 16 : ((QP) > 16 ? 32 : 64))     // rows a workgroup of the contraction stages (16 KB)
 #define PSI_CONTRACT_SPLIT_MAX 64    // most splits of the contraction's lower-tile list
 #define PSI_MMAX 65535         // most inducing points: the M x M helper kernels put M in gridDim.y
+
+// lower 16 x 16 tile number -> (ti, tj), ti >= tj (device; shared by the psi2 kernels of psi.hip and psi_ss.hip)
+__device__ __forceinline__ void psi_tile(long tl, int* ti, int* tj) {
+    long i = (long)((sqrt(8.0 * (double)tl + 1.0) - 1.0) * 0.5);
+    while (i * (i + 1) / 2 > tl) --i;
+    while ((i + 1) * (i + 2) / 2 <= tl) ++i;
+    *ti = (int)i;
+    *tj = (int)(tl - i * (i + 1) / 2);
+}
 
 // dL_dpsi1[n][m] = beta sum_d R[n][d] v[m][d] formed on the fly (the fit's rank-Dy product, var_dtc.py:219)
 struct PsiRank {

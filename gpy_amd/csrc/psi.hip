@@ -1,6 +1,7 @@
 // psi.hip -- psi-statistics of the RBF kernel for Gaussian inputs q(x_n) = N(mu_n, diag S_n), and their gradients.
 // Restates (does not port) GPy/kern/src/psi_comp/rbf_psi_comp.py:22-50 (psi1, psi2) and :70-133 (the chain rule from
-// dL_dpsi0/1/2 to variance, lengthscale, Z, mu, S), the one piece of device code of the reference (rbf_psi_gpucomp.py).
+// dL_dpsi0/1/2 to variance, lengthscale, Z, mu, S), one of the two pieces of device code of the reference (rbf_psi_gpucomp.py;
+// the other, ssrbf_psi_gpucomp.py for spike-and-slab inputs, has its counterpart in psi_ss.hip).
 // With a_q = 1 / l_q^2 (0 on a dimension the kernel does not see), c1 = a / (S a + 1), c2 = a / (2 S a + 1):
 //   psi1[n,m]  = var   exp(-1/2 sum_q log(S a + 1)  - 1/2 sum_q c1 (mu - z_m)^2)
 //   psi2n[m,o] = var^2 exp(-1/2 sum_q log(2 S a + 1) - sum_q a (z_m - z_o)^2 / 4 - sum_q c2 (mu - (z_m + z_o)/2)^2)
@@ -96,15 +97,6 @@ __global__ __launch_bounds__(256) void k_psi1(const double2* __restrict__ rd, co
         const long n = n0 + g * 16 + k;
         if (n < rows) out[n * ldo + m0 + mc] = var * exp(fma(-0.5, e[k], lg1[n]));
     }
-}
-
-// lower 16 x 16 tile number -> (ti, tj), ti >= tj
-__device__ __forceinline__ void psi_tile(long tl, int* ti, int* tj) {
-    long i = (long)((sqrt(8.0 * (double)tl + 1.0) - 1.0) * 0.5);
-    while (i * (i + 1) / 2 > tl) --i;
-    while ((i + 1) * (i + 2) / 2 <= tl) ++i;
-    *ti = (int)i;
-    *tj = (int)(tl - i * (i + 1) / 2);
 }
 
 // psi2 partial sums: part[split][mi][oj] (ld x ld, lower 16-tiles) = var^2 sum over the split's rows of w_n psi2n[mi][oj] / var^2.

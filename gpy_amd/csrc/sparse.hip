@@ -22,9 +22,11 @@
 #include "../../include/mi355gp_sparse_coreg.h"
 #include "../../include/mi355gp_debug_sparse_coreg.h"
 #include "../../include/mi355gp_psi_lin.h"
+#include "../../include/mi355gp_psi_ss.h"
 #include "internal.h"
 #include "parts.h"
 #include "psi.h"
+#include "psi_ss.h"
 #include "sparse_ctx.h"
 
 #define SPLITK_MAX 16
@@ -557,7 +559,7 @@ int mi355gp_sparse_destroy(mi355gp_sparse* s) {
     (void)hipSetDevice(s->device);
     (void)hipStreamSynchronize(s->st);
     free_m(s);
-    double** ptrs[] = {&s->dX, &s->dY, &s->dV, &s->dBeta, &s->dRowS, &s->dRowT, &s->dRowR, &s->dSvar};
+    double** ptrs[] = {&s->dX, &s->dY, &s->dV, &s->dBeta, &s->dRowS, &s->dRowT, &s->dRowR, &s->dSvar, &s->dGam};
     for (auto p : ptrs)
         if (*p) (void)hipFree(*p);
     if (s->comm) rccl_comm_destroy(s->comm);
@@ -581,7 +583,7 @@ int mi355gp_sparse_set_data(mi355gp_sparse* s, const double* X, int64_t N, int D
     EngineShared gate(s->device);
     HIP_CHECK(hipStreamSynchronize(s->st));
     free_m(s);
-    double** ptrs[] = {&s->dX, &s->dY, &s->dV, &s->dBeta, &s->dRowS, &s->dRowT, &s->dRowR, &s->dSvar};
+    double** ptrs[] = {&s->dX, &s->dY, &s->dV, &s->dBeta, &s->dRowS, &s->dRowT, &s->dRowR, &s->dSvar, &s->dGam};
     for (auto p : ptrs) {
         if (*p) (void)hipFree(*p);
         *p = nullptr;
@@ -669,6 +671,54 @@ int mi355gp_sparse_set_inputs(mi355gp_sparse* s, const double* X, const double* 
     if (s->take_coreg) s->hX.assign(X, X + N * D);
     else std::vector<double>().swap(s->hX);
     s->have_result = s->winv_ok = s->svgp_result = false;
+    return 0;
+}
+
+// Slab probabilities gamma (N x D) next to the resident means (set_data's X) and variances: q(x_nq) is then the spike-and-slab
+// gamma_nq N(mu_nq, S_nq) + (1 - gamma_nq) delta_0 of mi355gp_vardtc_inference_ss.  gamma == NULL takes the context back to
+// Gaussian inputs.  Every entry must be finite and strictly inside (0, 1); set_data discards them.
+static int check_binary_prob(const char* where, const double* gamma, int64_t N, int D) {
+    for (int64_t i = 0; i < N * D; ++i)
+        if (!(gamma[i] > 0.0 && gamma[i] < 1.0))
+            PART_FAIL("%s: slab probability gamma[%lld][%lld] = %g: every entry must be finite and strictly inside (0, 1)", where,
+                      (long long)(i / D), (long long)(i % D), gamma[i]);
+    return 0;
+}
+int mi355gp_sparse_set_binary_prob(mi355gp_sparse* s, const double* gamma, int64_t N, int D) {
+    ARG_CHECK(s && s->n > 0, "mi355gp_sparse_set_binary_prob: set_data first");
+    ARG_CHECK(!sharded(s), "mi355gp_sparse_set_binary_prob: spike-and-slab inputs are not supported by a row-sharded context");
+    HIP_CHECK(hipSetDevice(s->device));
+    if (!gamma) {
+        EngineShared gate(s->device);
+        HIP_CHECK(hipStreamSynchronize(s->st));
+        if (s->dGam) (void)hipFree(s->dGam);
+        s->dGam = nullptr;
+        s->have_result = s->winv_ok = s->svgp_result = false;
+        return 0;
+    }
+    ARG_CHECK(N == s->n && D == s->D, "mi355gp_sparse_set_binary_prob: gamma must be N x D, the shape of X");
+    ARG_CHECK(s->dSvar, "mi355gp_sparse_set_binary_prob: no input variances; call mi355gp_sparse_set_input_variance first");
+    if (int rc = check_binary_prob("mi355gp_sparse_set_binary_prob", gamma, N, D)) return rc;
+    EngineShared gate(s->device);
+    HIP_CHECK(hipStreamSynchronize(s->st));
+    if (!s->dGam) HIP_CHECK(hipMalloc(&s->dGam, sizeof(double) * N * D));
+    HIP_CHECK(hipMemcpy(s->dGam, gamma, sizeof(double) * N * D, hipMemcpyHostToDevice));
+    s->have_result = s->winv_ok = s->svgp_result = false;
+    return 0;
+}
+
+// The three-array form of mi355gp_sparse_set_inputs, the upload of one SSGPLVM step: means, variances and slab probabilities
+// (all N x D, all required); Y stays resident.
+int mi355gp_sparse_set_inputs_ss(mi355gp_sparse* s, const double* X, const double* S, const double* gamma, int64_t N, int D) {
+    ARG_CHECK(s && s->n > 0, "mi355gp_sparse_set_inputs_ss: set_data first");
+    ARG_CHECK(X && S && gamma && N == s->n && D == s->D,
+              "mi355gp_sparse_set_inputs_ss: X, S and gamma must be N x D, the shape of set_data's X");
+    ARG_CHECK(!sharded(s), "mi355gp_sparse_set_inputs_ss: replacing the inputs of a row-sharded context is not supported");
+    if (int rc = check_binary_prob("mi355gp_sparse_set_inputs_ss", gamma, N, D)) return rc;
+    if (int rc = mi355gp_sparse_set_inputs(s, X, S, N, D)) return rc;
+    EngineShared gate(s->device);
+    if (!s->dGam) HIP_CHECK(hipMalloc(&s->dGam, sizeof(double) * N * D));
+    HIP_CHECK(hipMemcpy(s->dGam, gamma, sizeof(double) * N * D, hipMemcpyHostToDevice));
     return 0;
 }
 
@@ -1521,11 +1571,12 @@ __global__ void k_sym_scaled(const double* __restrict__ A, long mp, long m, doub
 // The psi kernels' operands and partial sums for one call: a_q = 1 / l_q^2 (0 on a dimension the RBF part does not see), Z zero
 // padded to mpad x Qp, the per-chunk row records and the sums the two passes leave behind
 struct PsiWork {
-    int Qp = 0, RL = 0;
+    bool ss = false;                        // spike-and-slab inputs (s->dGam): the kernels and layouts of psi_ss.hip
+    int Qp = 0, RL = 0, ZL = 0;             // doubles of one row record and of one inducing point's Z sums
     long mpad = 0, ld2 = 0, mt = 0, chunk = 0;
     double var = 0.0;                       // the RBF part's variance
     std::vector<double> ha, hzp, sums;      // a_q; padded Z; [0] the variance record, [1 + q] the lengthscale sums of psi1 and psi2
-    DevBuf dA, dZp, rd1, rd2, lg1, lg2, Ppart, P1s, P2s, Zpart, Zs1, Zs2, dMuO, dSO, rowrec, rec, zz;
+    DevBuf dA, dZp, dEp, rd1, rd2, lg1, lg2, Ppart, P1s, P2s, Zpart, Zs1, Zs2, dMuO, dSO, dGO, rowrec, rec, zz;
     // Bias parts (b > 0, mi355gp_sparse_set_psi_lin_bias): the column sums c of the RBF part's psi1 (mp), of V (Dy),
     // t = 2 rowsum(dL_dpsi2) (m), b t (m) and the RBF part's own psi2 (mp x mp: s->psi2 then holds the expression's) -- the
     // context's buffers (biasC ...), kept between calls
@@ -1537,7 +1588,8 @@ static int psi_work_setup(mi355gp_sparse* s, const SPart& rbf, const double* Z, 
     const long n = s->n, m = s->m;
     const int D = s->D, Qp = psi_qp(D);
     w->Qp = Qp;
-    w->RL = 1 + 2 * Qp;
+    w->RL = w->ss ? PSS_RL(Qp) : 1 + 2 * Qp;
+    w->ZL = w->ss ? PSS_NZ * Qp : Qp;
     w->var = rbf.kp.variance;
     w->mpad = round_up(m, PSI_KT);
     w->ld2 = round_up(m, PSI_T2);
@@ -1553,24 +1605,31 @@ static int psi_work_setup(mi355gp_sparse* s, const SPart& rbf, const double* Z, 
         for (int q = 0; q < D; ++q) hzp[(size_t)i * Qp + q] = Z[i * D + q];
     HIP_CHECK(w->dA.alloc(Qp));
     HIP_CHECK(w->dZp.alloc(hzp.size()));
-    HIP_CHECK(w->rd1.alloc(2 * chunk * Qp));
-    HIP_CHECK(w->rd2.alloc(2 * chunk * Qp));
-    HIP_CHECK(w->lg1.alloc(chunk));
-    HIP_CHECK(w->lg2.alloc(chunk));
+    HIP_CHECK(w->rd1.alloc((w->ss ? 4 : 2) * chunk * Qp));
+    HIP_CHECK(w->rd2.alloc((w->ss ? 4 : 2) * chunk * Qp));
+    if (!w->ss) {                                                 // (the spike-and-slab records carry their prefactors)
+        HIP_CHECK(w->lg1.alloc(chunk));
+        HIP_CHECK(w->lg2.alloc(chunk));
+    }
     HIP_CHECK(w->Ppart.alloc((size_t)w->mt * chunk * w->RL));
     HIP_CHECK(w->P1s.alloc((size_t)chunk * w->RL));
     HIP_CHECK(w->P2s.alloc((size_t)chunk * w->RL));
-    HIP_CHECK(w->Zpart.alloc((size_t)nzb * mpad * Qp));
-    HIP_CHECK(w->Zs1.alloc((size_t)mpad * Qp));
-    HIP_CHECK(w->Zs2.alloc((size_t)mpad * Qp));
+    HIP_CHECK(w->Zpart.alloc((size_t)nzb * mpad * w->ZL));
+    HIP_CHECK(w->Zs1.alloc((size_t)mpad * w->ZL));
+    HIP_CHECK(w->Zs2.alloc((size_t)mpad * w->ZL));
     HIP_CHECK(w->dMuO.alloc(n * D));
     HIP_CHECK(w->dSO.alloc(n * D));
     HIP_CHECK(w->rowrec.alloc((size_t)chunk * (1 + Qp)));
     HIP_CHECK(w->rec.alloc(1 + Qp));
-    HIP_CHECK(w->zz.alloc((size_t)m * 2 * Qp));
+    if (!w->ss) HIP_CHECK(w->zz.alloc((size_t)m * 2 * Qp));      // (spike-and-slab: the z_m - z_o sums come from the gradient kernel)
     HIP_CHECK(hipMemcpyAsync(w->dA, w->ha.data(), sizeof(double) * Qp, hipMemcpyHostToDevice, s->st));
     HIP_CHECK(hipMemcpyAsync(w->dZp, hzp.data(), sizeof(double) * hzp.size(), hipMemcpyHostToDevice, s->st));
-    HIP_CHECK(hipMemsetAsync(w->Zpart, 0, sizeof(double) * nzb * mpad * Qp, s->st));   // the kernels write rows < round_up(m, 16) only
+    HIP_CHECK(hipMemsetAsync(w->Zpart, 0, sizeof(double) * nzb * mpad * w->ZL, s->st));   // the kernels write rows < round_up(m, 16) only
+    if (w->ss) {
+        HIP_CHECK(w->dEp.alloc(hzp.size()));
+        HIP_CHECK(w->dGO.alloc(n * D));
+        launch_pss_e(s->st, w->dZp, w->dA, mpad, Qp, w->dEp);
+    }
     return 0;
 }
 
@@ -1590,16 +1649,19 @@ static int uncertain_pass1(mi355gp_sparse* s, PsiWork& w, double extra_jitter) {
     int nch = 0;
     for (long r0 = 0; r0 < n; r0 += PSI_CHUNK, ++nch) {
         const long rc = (n - r0 < PSI_CHUNK) ? (n - r0) : PSI_CHUNK;
-        launch_psi_rows(st, s->dX + r0 * D, s->dSvar + r0 * D, w.dA, rc, D, w.Qp, w.rd1, w.rd2, w.lg1, w.lg2);
+        if (w.ss) launch_pss_rows(st, s->dX + r0 * D, s->dSvar + r0 * D, s->dGam + r0 * D, w.dA, rc, D, w.Qp, w.rd1, w.rd2);
+        else launch_psi_rows(st, s->dX + r0 * D, s->dSvar + r0 * D, w.dA, rc, D, w.Qp, w.rd1, w.rd2, w.lg1, w.lg2);
         HIP_CHECK(hipMemsetAsync(s->Kfu, 0, sizeof(double) * rc * mp, st));          // psi1 writes columns < m only
-        launch_psi1(st, w.rd1, w.lg1, w.dZp, rc, m, w.mpad, w.Qp, w.var, s->Kfu, mp);
+        if (w.ss) launch_pss_psi1(st, w.rd1, w.dZp, w.dEp, rc, m, w.mpad, w.Qp, w.var, s->Kfu, mp);
+        else launch_psi1(st, w.rd1, w.lg1, w.dZp, rc, m, w.mpad, w.Qp, w.var, s->Kfu, mp);
         const int nsc = launch_colreduce_multi(st, s->Kfu, mp, rc, mp, s->dV + r0 * Dy, Dy, 1, Dy, 0, s->colPart);
         launch_sum_splits(st, s->colPart, mp * Dy, nsc, 1, s->psi1Y);                 // psi1^T V += psi1_chunk^T V_chunk
         if (w.b > 0.0) {                                                              // c += the chunk's column sums of psi1
             const int nso = launch_colreduce_multi(st, s->Kfu, mp, rc, mp, nullptr, 0, 0, 0, 1, s->colPart);
             launch_sum_splits(st, s->colPart, mp, nso, nch > 0, w.csum);
         }
-        const int ns = launch_psi2(st, w.rd2, w.lg2, nullptr, w.dZp, w.dA, rc, m, w.Qp, w.var * w.var, w.ld2, s->psi2part);
+        const int ns = w.ss ? launch_pss_psi2(st, w.rd2, nullptr, w.dZp, w.dEp, w.dA, rc, m, w.Qp, w.var * w.var, w.ld2, s->psi2part)
+                            : launch_psi2(st, w.rd2, w.lg2, nullptr, w.dZp, w.dA, rc, m, w.Qp, w.var * w.var, w.ld2, s->psi2part);
         launch_psi2_combine(st, s->psi2part, w.ld2, m, ns, nch > 0, s->psi2, mp);
     }
     if (w.b > 0.0) {
@@ -1621,7 +1683,7 @@ static int uncertain_pass2(mi355gp_sparse* s, PsiWork& w, double beta) {
     const long n = s->n, m = s->m, mp = s->mp;
     const int D = s->D, Dy = s->Dy, Qp = w.Qp;
     hipLaunchKernelGGL(k_sym_scaled, grid2d(mp, mp), dim3(256), 0, st, s->Q2, mp, m, beta, s->E);
-    launch_psi2_zz(st, s->E, w.b > 0.0 ? (const double*)w.psi2rbf : (const double*)s->psi2, mp, w.dZp, m, Qp, w.zz);
+    if (!w.ss) launch_psi2_zz(st, s->E, w.b > 0.0 ? (const double*)w.psi2rbf : (const double*)s->psi2, mp, w.dZp, m, Qp, w.zz);
     if (w.b > 0.0) {                                           // Bias parts: dL_dpsi1 of the RBF part gains b t^T, t = 2 rowsum(E)
         launch_mm_colsums(st, s->E, mp, m, 2.0, w.tvec);
         launch_mm_colsums(st, s->E, mp, m, 2.0 * w.b, w.addv);
@@ -1632,15 +1694,24 @@ static int uncertain_pass2(mi355gp_sparse* s, PsiWork& w, double beta) {
     for (long r0 = 0; r0 < n; r0 += PSI_CHUNK, ++nch) {
         const long rc = (n - r0 < PSI_CHUNK) ? (n - r0) : PSI_CHUNK;
         const int nb = (int)((rc + PSI_GROWS - 1) / PSI_GROWS);
-        launch_psi_rows(st, s->dX + r0 * D, s->dSvar + r0 * D, w.dA, rc, D, Qp, w.rd1, w.rd2, w.lg1, w.lg2);
-        launch_psi1_grad(st, w.rd1, w.lg1, w.dZp, nullptr, 0, PsiRank{s->dY + r0 * Dy, s->vvec, Dy, beta}, rc, m, w.mpad, Qp, w.var,
-                         w.Ppart, w.Zpart, add);
+        const PsiRank rk{s->dY + r0 * Dy, s->vvec, Dy, beta};
+        if (w.ss) {
+            launch_pss_rows(st, s->dX + r0 * D, s->dSvar + r0 * D, s->dGam + r0 * D, w.dA, rc, D, Qp, w.rd1, w.rd2);
+            launch_pss_psi1_grad(st, w.rd1, w.dZp, w.dEp, nullptr, 0, rk, rc, m, w.mpad, Qp, w.var, w.Ppart, w.Zpart);
+        } else {
+            launch_psi_rows(st, s->dX + r0 * D, s->dSvar + r0 * D, w.dA, rc, D, Qp, w.rd1, w.rd2, w.lg1, w.lg2);
+            launch_psi1_grad(st, w.rd1, w.lg1, w.dZp, nullptr, 0, rk, rc, m, w.mpad, Qp, w.var, w.Ppart, w.Zpart, add);
+        }
         launch_sum_splits(st, w.Ppart, rc * w.RL, (int)w.mt, 0, w.P1s);
-        launch_sum_splits(st, w.Zpart, w.mpad * Qp, nb, nch > 0, w.Zs1);
-        launch_psi2_grad(st, w.rd2, w.lg2, nullptr, w.dZp, w.dA, s->E, mp, rc, m, w.mpad, Qp, w.var * w.var, w.Ppart, w.Zpart);
+        launch_sum_splits(st, w.Zpart, w.mpad * w.ZL, nb, nch > 0, w.Zs1);
+        if (w.ss) launch_pss_psi2_grad(st, w.rd2, nullptr, w.dZp, w.dEp, w.dA, s->E, mp, rc, m, w.mpad, Qp, w.var * w.var, w.Ppart, w.Zpart);
+        else launch_psi2_grad(st, w.rd2, w.lg2, nullptr, w.dZp, w.dA, s->E, mp, rc, m, w.mpad, Qp, w.var * w.var, w.Ppart, w.Zpart);
         launch_sum_splits(st, w.Ppart, rc * w.RL, (int)w.mt, 0, w.P2s);
-        launch_sum_splits(st, w.Zpart, w.mpad * Qp, nb, nch > 0, w.Zs2);
-        launch_psi_rowfinish(st, w.P1s, w.P2s, s->dSvar + r0 * D, w.dA, rc, D, Qp, w.dMuO + r0 * D, w.dSO + r0 * D, w.rowrec);
+        launch_sum_splits(st, w.Zpart, w.mpad * w.ZL, nb, nch > 0, w.Zs2);
+        if (w.ss)
+            launch_pss_rowfinish(st, w.P1s, w.P2s, s->dSvar + r0 * D, s->dGam + r0 * D, w.dA, rc, D, Qp, w.dMuO + r0 * D, w.dSO + r0 * D,
+                                 w.dGO + r0 * D, w.rowrec);
+        else launch_psi_rowfinish(st, w.P1s, w.P2s, s->dSvar + r0 * D, w.dA, rc, D, Qp, w.dMuO + r0 * D, w.dSO + r0 * D, w.rowrec);
         launch_reduce_partials(st, w.rowrec, (int)rc, 1 + Qp, w.rec);
         HIP_CHECK(hipMemcpyAsync(csum.data(), w.rec, sizeof(double) * (1 + Qp), hipMemcpyDeviceToHost, st));
         HIP_CHECK(hipStreamSynchronize(st));
@@ -1653,9 +1724,9 @@ static int uncertain_pass2(mi355gp_sparse* s, PsiWork& w, double beta) {
 // parts; on a context that was asked to (mi355gp_sparse_set_psi_lin_bias) ONE input-dependent part, RBF or Linear, with Bias
 // and White parts.  irbf_out: the index of that part.
 static int uncertain_check_parts(const mi355gp_sparse* s, int nparts, const mi355gp_part* parts, int64_t M, int* irbf_out,
-                                 const char* where = "mi355gp_vardtc_inference_uncertain") {
+                                 const char* where = "mi355gp_vardtc_inference_uncertain", bool ss = false) {
     int irbf = -1;
-    if (s->take_psi_lin) {
+    if (s->take_psi_lin && !ss) {                                  // (spike-and-slab inputs: one RBF part and White parts on every context)
         for (int i = 0; i < nparts; ++i) {
             if (parts[i].term != 0) PART_FAIL("%s: part %d is a factor of a product; products have no psi statistics here", where, i);
             if (parts[i].kind == MI355GP_WHITE || parts[i].kind == MI355GP_BIAS) continue;
@@ -1680,7 +1751,7 @@ static int uncertain_check_parts(const mi355gp_sparse* s, int nparts, const mi35
         if (parts[i].kind != MI355GP_RBF)
             PART_FAIL("%s: part %d is a %s (kind %d) part; uncertain inputs take one RBF part and White parts only%s", where, i,
                       kind_name(parts[i].kind), parts[i].kind,
-                      (parts[i].kind == MI355GP_BIAS || parts[i].kind == MI355GP_LINEAR)
+                      (!ss && (parts[i].kind == MI355GP_BIAS || parts[i].kind == MI355GP_LINEAR))
                           ? " (Bias and Linear: ask the context with mi355gp_sparse_set_psi_lin_bias)" : "");
         if (irbf >= 0) PART_FAIL("%s: parts %d and %d are both RBF; uncertain inputs take ONE RBF part (and White parts)", where, irbf, i);
         irbf = i;
@@ -1791,40 +1862,21 @@ static int vardtc_uncertain_linear(mi355gp_sparse* s, int ilin, const double* Z,
     return 0;
 }
 
-// One SparseGP.parameters_changed for UNCERTAIN inputs q(x_n) = N(X_n, diag S_n) (set_data + set_input_variance), a scalar
-// noise variance and one RBF part alone or with White parts (var_dtc.py:93-120,133-163,217-233,258-276 with psi statistics
-// in place of Kdiag / Knm / Knm^T Knm; rbf_psi_comp.py; static.py: White adds its variance to psi0 and to Kmm's diagonal):
-// the phases of the certain-input call with the psi kernels in the two passes and dL_dpsi0 = -Dy beta / 2.
-// out_scalars, dtheta_out (concatenated over the parts), dZ_out, wv_out, stage_ms as mi355gp_vardtc_inference_sum;
-// dmu_out / dS_out (optional, N x D): the gradients with respect to the means and variances of the inputs.
-int mi355gp_vardtc_inference_uncertain(mi355gp_sparse* s, int nparts, const mi355gp_part* parts, const double* Z, int64_t M,
-                                       const double* noise, int64_t noise_len, double extra_jitter, double* out_scalars,
-                                       double* dtheta_out, double* dZ_out, double* wv_out, double* dmu_out, double* dS_out,
-                                       double* stage_ms) {
-    ARG_CHECK(s && s->n > 0, "mi355gp_vardtc_inference_uncertain: set_data first");
-    ARG_CHECK(parts && Z && M > 0 && out_scalars && noise && nparts >= 1, "mi355gp_vardtc_inference_uncertain: bad arguments");
-    ARG_CHECK(!sharded(s), "mi355gp_vardtc_inference_uncertain: a row-sharded context is not supported with uncertain inputs");
-    ARG_CHECK(s->dSvar, "mi355gp_vardtc_inference_uncertain: no input variances; call mi355gp_sparse_set_input_variance after set_data");
-    if (noise_len != 1)
-        PART_FAIL("mi355gp_vardtc_inference_uncertain: per-point noise (%lld variances) is not supported with uncertain inputs "
-                  "(var_dtc.py:243); pass one noise variance", (long long)noise_len);
-    int irbf = -1;
-    if (int rc = uncertain_check_parts(s, nparts, parts, M, &irbf)) return rc;
-    EngineShared gate(s->device);
-    if (int rc = sparse_open(s, nparts, parts, M)) return rc;
+// The uncertain-input evaluation of an opened call whose input-dependent part is the RBF part irbf: sparse_start, pass 1, the
+// M x M block, pass 2, the results.  ss: the inputs are spike-and-slab (s->dGam; no Bias parts then) and dgamma_out (optional,
+// N x D) takes the gradient with respect to the slab probabilities.
+static int vardtc_uncertain_rbf(mi355gp_sparse* s, int irbf, bool ss, const double* Z, double beta, double extra_jitter,
+                                double* out_scalars, double* dtheta_out, double* dZ_out, double* wv_out, double* dmu_out,
+                                double* dS_out, double* dgamma_out, double* stage_ms) {
     hipStream_t st = s->st;
     const long n = s->n, m = s->m;
     const int D = s->D, Dy = s->Dy;
-    const double beta = 1.0 / fmax(noise[0], 1e-8);
-    s->beta_scalar = beta;
-    if (s->parts[(size_t)irbf].linear())
-        return vardtc_uncertain_linear(s, irbf, Z, beta, extra_jitter, out_scalars, dtheta_out, dZ_out, wv_out, dmu_out, dS_out,
-                                       stage_ms);
     s->mfma_prof.on = false;
     const SPart& rbf = s->parts[(size_t)irbf];
     PsiWork w;
+    w.ss = ss;
     if (int rc = psi_work_setup(s, rbf, Z, &w)) return rc;
-    w.b = bias_sum(s);
+    w.b = ss ? 0.0 : bias_sum(s);
     if (w.b > 0.0) {                                             // (a part's variance is positive: parse_part refuses any other)
         HIP_CHECK(s->biasC.need((size_t)s->mp));
         HIP_CHECK(s->biasV.need((size_t)s->Dy));
@@ -1842,7 +1894,7 @@ int mi355gp_vardtc_inference_uncertain(mi355gp_sparse* s, int nparts, const mi35
     // ---- small results to the host -----------------------------------------------------------------------------------------
     const int Qp = w.Qp;
     KernGrads kg;
-    std::vector<double> zs1((size_t)w.mpad * Qp), zs2((size_t)w.mpad * Qp), zzh((size_t)m * 2 * Qp);
+    std::vector<double> zs1((size_t)w.mpad * w.ZL), zs2((size_t)w.mpad * w.ZL), zzh((size_t)m * 2 * Qp);
     std::vector<double> hc, ht, hvs, hwv;                          // Bias parts: c, t, colsum(V), the Woodbury vector
     double scal[8];
     if (int rc = sparse_fetch_gradients(s, false, &kg)) return rc;
@@ -1855,11 +1907,12 @@ int mi355gp_vardtc_inference_uncertain(mi355gp_sparse* s, int nparts, const mi35
     }
     HIP_CHECK(hipMemcpyAsync(zs1.data(), w.Zs1, sizeof(double) * zs1.size(), hipMemcpyDeviceToHost, st));
     HIP_CHECK(hipMemcpyAsync(zs2.data(), w.Zs2, sizeof(double) * zs2.size(), hipMemcpyDeviceToHost, st));
-    HIP_CHECK(hipMemcpyAsync(zzh.data(), w.zz, sizeof(double) * zzh.size(), hipMemcpyDeviceToHost, st));
+    if (!ss) HIP_CHECK(hipMemcpyAsync(zzh.data(), w.zz, sizeof(double) * zzh.size(), hipMemcpyDeviceToHost, st));
     HIP_CHECK(hipMemcpyAsync(scal, s->scal, sizeof(double) * 4, hipMemcpyDeviceToHost, st));
     if (wv_out) HIP_CHECK(hipMemcpyAsync(wv_out, s->vvec, sizeof(double) * m * Dy, hipMemcpyDeviceToHost, st));
     if (dmu_out) HIP_CHECK(hipMemcpyAsync(dmu_out, w.dMuO, sizeof(double) * n * D, hipMemcpyDeviceToHost, st));
     if (dS_out) HIP_CHECK(hipMemcpyAsync(dS_out, w.dSO, sizeof(double) * n * D, hipMemcpyDeviceToHost, st));
+    if (ss && dgamma_out) HIP_CHECK(hipMemcpyAsync(dgamma_out, w.dGO, sizeof(double) * n * D, hipMemcpyDeviceToHost, st));
     if (int rc = sparse_finish(s, 3, stage_ms)) return rc;
     // psi0_n = variance_rbf + sum variance_white, every row: psi0.sum() = N psi0
     vardtc_scalars(s, scal, expression_kdiag(s->parts, s->terms), beta, nullptr, out_scalars);
@@ -1867,10 +1920,16 @@ int mi355gp_vardtc_inference_uncertain(mi355gp_sparse* s, int nparts, const mi35
     // dvariance = rec[0] / variance, dl = -rec / l); the z_m - z_o terms of psi2 add a_q sum LS dz^2 / 2 to dimension q
     double* ab = kg.gmm.data() + (size_t)irbf * rec_doubles(s);
     ab[0] += w.sums[0];
+    std::vector<double> dZss;                                      // spike-and-slab: the psi1 / psi2 shares of dZ (psi_ss.hip)
+    if (ss) {
+        dZss.assign((size_t)m * D, 0.0);
+        pss_finish_z(zs1.data(), zs2.data(), w.ha.data(), w.hzp.data(), m, D, Qp, dZss.data(), w.sums.data() + 1);
+    }
     for (int q = 0; q < D; ++q) {
         double zq = 0.0;
-        for (long j = 0; j < m; ++j) zq += zzh[(size_t)j * 2 * Qp + Qp + q];
-        const double lq = w.sums[(size_t)(1 + q)] + 0.5 * w.ha[(size_t)q] * zq;
+        if (!ss)
+            for (long j = 0; j < m; ++j) zq += zzh[(size_t)j * 2 * Qp + Qp + q];
+        const double lq = ss ? w.sums[(size_t)(1 + q)] : w.sums[(size_t)(1 + q)] + 0.5 * w.ha[(size_t)q] * zq;
         ab[(size_t)(q / 32) * GP_STRIDE + 2 + (q % 32)] -= lq;
         ab[1] -= lq;
     }
@@ -1893,13 +1952,75 @@ int mi355gp_vardtc_inference_uncertain(mi355gp_sparse* s, int nparts, const mi35
     }
     // dL_dpsi0 = -Dy beta / 2 per row, dpsi0 / dvariance = 1
     sparse_assemble_gradients(s, kg, -0.5 * Dy * beta * (double)n, dtheta_out, dZ_out);
-    if (dZ_out)         // + gradients_Z_expectations (the psi1 and psi2 parts; sparse_gp.py:100-107)
+    if (dZ_out && ss)
+        for (long j = 0; j < m * D; ++j) dZ_out[j] += dZss[(size_t)j];
+    if (dZ_out && !ss)  // + gradients_Z_expectations (the psi1 and psi2 parts; sparse_gp.py:100-107)
         for (long j = 0; j < m; ++j)
             for (int q = 0; q < D; ++q)
                 dZ_out[j * D + q] += zs1[(size_t)j * Qp + q] + 2.0 * zs2[(size_t)j * Qp + q] - w.ha[(size_t)q] * zzh[(size_t)j * 2 * Qp + q];
     s->have_result = true;
     s->uncertain_result = true;
     return 0;
+}
+
+// One SparseGP.parameters_changed for UNCERTAIN inputs q(x_n) = N(X_n, diag S_n) (set_data + set_input_variance), a scalar
+// noise variance and one RBF part alone or with White parts (var_dtc.py:93-120,133-163,217-233,258-276 with psi statistics
+// in place of Kdiag / Knm / Knm^T Knm; rbf_psi_comp.py; static.py: White adds its variance to psi0 and to Kmm's diagonal):
+// the phases of the certain-input call with the psi kernels in the two passes and dL_dpsi0 = -Dy beta / 2.
+// out_scalars, dtheta_out (concatenated over the parts), dZ_out, wv_out, stage_ms as mi355gp_vardtc_inference_sum;
+// dmu_out / dS_out (optional, N x D): the gradients with respect to the means and variances of the inputs.
+int mi355gp_vardtc_inference_uncertain(mi355gp_sparse* s, int nparts, const mi355gp_part* parts, const double* Z, int64_t M,
+                                       const double* noise, int64_t noise_len, double extra_jitter, double* out_scalars,
+                                       double* dtheta_out, double* dZ_out, double* wv_out, double* dmu_out, double* dS_out,
+                                       double* stage_ms) {
+    ARG_CHECK(s && s->n > 0, "mi355gp_vardtc_inference_uncertain: set_data first");
+    ARG_CHECK(parts && Z && M > 0 && out_scalars && noise && nparts >= 1, "mi355gp_vardtc_inference_uncertain: bad arguments");
+    ARG_CHECK(!sharded(s), "mi355gp_vardtc_inference_uncertain: a row-sharded context is not supported with uncertain inputs");
+    ARG_CHECK(s->dSvar, "mi355gp_vardtc_inference_uncertain: no input variances; call mi355gp_sparse_set_input_variance after set_data");
+    ARG_CHECK(!s->dGam, "mi355gp_vardtc_inference_uncertain: the context holds slab probabilities (mi355gp_sparse_set_binary_prob), which "
+                        "this entry would drop; call mi355gp_vardtc_inference_ss, or clear them with a NULL gamma");
+    if (noise_len != 1)
+        PART_FAIL("mi355gp_vardtc_inference_uncertain: per-point noise (%lld variances) is not supported with uncertain inputs "
+                  "(var_dtc.py:243); pass one noise variance", (long long)noise_len);
+    int irbf = -1;
+    if (int rc = uncertain_check_parts(s, nparts, parts, M, &irbf)) return rc;
+    EngineShared gate(s->device);
+    if (int rc = sparse_open(s, nparts, parts, M)) return rc;
+    const double beta = 1.0 / fmax(noise[0], 1e-8);
+    s->beta_scalar = beta;
+    if (s->parts[(size_t)irbf].linear())
+        return vardtc_uncertain_linear(s, irbf, Z, beta, extra_jitter, out_scalars, dtheta_out, dZ_out, wv_out, dmu_out, dS_out,
+                                       stage_ms);
+    return vardtc_uncertain_rbf(s, irbf, false, Z, beta, extra_jitter, out_scalars, dtheta_out, dZ_out, wv_out, dmu_out, dS_out, nullptr,
+                                stage_ms);
+}
+
+// VarDTC with spike-and-slab inputs q(x_nq) = gamma_nq N(mu_nq, S_nq) + (1 - gamma_nq) delta_0 (set_data's X as the means,
+// mi355gp_sparse_set_input_variance, mi355gp_sparse_set_binary_prob; GPy/models/ss_gplvm.py with ssrbf_psi_comp.py): the phases of
+// mi355gp_vardtc_inference_uncertain with the kernels of psi_ss.hip in the psi slots.  One RBF part alone or summed with White
+// parts, one noise variance.  dgamma_out (optional, N x D): the gradient with respect to gamma.  The result lies where VarDTC's
+// does: mi355gp_sparse_predict, mi355gp_sparse_fetch and mi355gp_sparse_predict_uncertain (Gaussian new points) serve it.
+int mi355gp_vardtc_inference_ss(mi355gp_sparse* s, int nparts, const mi355gp_part* parts, const double* Z, int64_t M,
+                                const double* noise, int64_t noise_len, double extra_jitter, double* out_scalars, double* dtheta_out,
+                                double* dZ_out, double* wv_out, double* dmu_out, double* dS_out, double* dgamma_out,
+                                double* stage_ms) {
+    const char* where = "mi355gp_vardtc_inference_ss";
+    ARG_CHECK(s && s->n > 0, "mi355gp_vardtc_inference_ss: set_data first");
+    ARG_CHECK(parts && Z && M > 0 && out_scalars && noise && nparts >= 1, "mi355gp_vardtc_inference_ss: bad arguments");
+    ARG_CHECK(!sharded(s), "mi355gp_vardtc_inference_ss: a row-sharded context is not supported with spike-and-slab inputs");
+    ARG_CHECK(s->dSvar && s->dGam, "mi355gp_vardtc_inference_ss: no slab probabilities; call mi355gp_sparse_set_input_variance and "
+                                   "mi355gp_sparse_set_binary_prob (or mi355gp_sparse_set_inputs_ss) after set_data");
+    if (noise_len != 1)
+        PART_FAIL("%s: per-point noise (%lld variances) is not supported with spike-and-slab inputs; pass one noise variance", where,
+                  (long long)noise_len);
+    int irbf = -1;
+    if (int rc = uncertain_check_parts(s, nparts, parts, M, &irbf, where, true)) return rc;
+    EngineShared gate(s->device);
+    if (int rc = sparse_open(s, nparts, parts, M)) return rc;
+    const double beta = 1.0 / fmax(noise[0], 1e-8);
+    s->beta_scalar = beta;
+    return vardtc_uncertain_rbf(s, irbf, true, Z, beta, extra_jitter, out_scalars, dtheta_out, dZ_out, wv_out, dmu_out, dS_out, dgamma_out,
+                                stage_ms);
 }
 
 // ---- results of the last VarDTC call ------------------------------------------------------------------------------------

@@ -55,6 +55,7 @@ struct mi355gp_sparse {
     int world = 1, rank = 0;
     long n_global = 0;
     double* dSvar = nullptr;      // N x D input variances (mi355gp_sparse_set_input_variance): X is then the mean of q(x_n)
+    double* dGam = nullptr;       // N x D slab probabilities (mi355gp_sparse_set_binary_prob): q(x_n) is then spike-and-slab
     bool uncertain_result = false; // the last result came from mi355gp_vardtc_inference_uncertain (no dL_dKnm then)
     double *dX = nullptr, *dY = nullptr, *dV = nullptr, *dBeta = nullptr, *dRowS = nullptr, *dRowT = nullptr, *dRowR = nullptr,
            *Kfu = nullptr,

@@ -17,6 +17,7 @@ from .likelihoods import Bernoulli
 from .linalg import jitter_ladder
 from .link_functions import Probit
 from .posterior import PosteriorEP
+from .variational import refuse_spike_and_slab
 
 log_2_pi = np.log(2 * np.pi)
 
@@ -105,6 +106,7 @@ class EP(LatentFunctionInference):
 
     # ---- the public entry point (reference `expectation_propagation.py:246-277`) -----------------------------------------
     def inference(self, kern, X, likelihood, Y, mean_function=None, Y_metadata=None, precision=None, K=None):
+        refuse_spike_and_slab(X, "EP")
         if mean_function is not None:
             raise NotImplementedError("EP on the MI355X path takes a zero prior mean: a mean function is not implemented")
         if precision is not None:

@@ -19,7 +19,7 @@ from .likelihoods import Bernoulli
 from .link_functions import Probit
 from .linalg import LinAlgError, jitter_ladder
 from .sparse import SparseGP, SparseSession, sparse_path_kernel_check
-from .variational import NormalPosterior
+from .variational import NormalPosterior, refuse_spike_and_slab
 
 log_2_pi = np.log(2 * np.pi)
 
@@ -59,6 +59,7 @@ class EPDTC(SparseSession):
                   psi1=None, psi2=None):
         if mean_function is not None:
             raise NotImplementedError("EPDTC on the MI355X path takes a zero prior mean: a mean function is not implemented")
+        refuse_spike_and_slab(X, "EPDTC")
         if isinstance(X, NormalPosterior):
             raise NotImplementedError("EPDTC on the MI355X path takes certain inputs: a NormalPosterior X "
                                       "(SparseGPClassificationUncertainInput) is not implemented")
@@ -191,6 +192,7 @@ class SparseGPClassification(SparseGP):
                                       "implemented")
         if normalizer:
             raise NotImplementedError("SparseGPClassification: a normalizer is not implemented on the MI355X path")
+        refuse_spike_and_slab(X, "SparseGPClassification")
         if isinstance(X, NormalPosterior):
             raise NotImplementedError("SparseGPClassification takes certain inputs: a NormalPosterior X "
                                       "(SparseGPClassificationUncertainInput) is not implemented on the MI355X path")

@@ -17,6 +17,7 @@ from .lazy import ArrayIdentity, DeviceResult, kernel_signature
 from .likelihoods import Gaussian
 from .linalg import jitter_ladder
 from .posterior import PosteriorExact, StudentTPosterior
+from .variational import refuse_spike_and_slab
 
 
 class LatentFunctionInference(object):
@@ -144,6 +145,7 @@ class ExactGaussianInference(LatentFunctionInference):
 
     def inference(self, kern, X, likelihood, Y, mean_function=None, Y_metadata=None, K=None, variance=None,
                   Z_tilde=None):
+        refuse_spike_and_slab(X, "ExactGaussianInference")
         X = np.asarray(X)
         Y = np.asarray(Y, dtype=np.float64)
         if variance is None:
@@ -224,6 +226,7 @@ class ExactStudentTInference(LatentFunctionInference):
         from scipy.special import digamma
         if K is not None or not getattr(kern, "fused_alone", False):
             raise NotImplementedError("the MI355X Student-t path evaluates gpy_amd kernels on the device")
+        refuse_spike_and_slab(X, "ExactStudentTInference")
         X = np.asarray(X)
         Y = np.asarray(Y, dtype=np.float64)
         m = 0 if mean_function is None else mean_function.f(X)

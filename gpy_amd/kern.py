@@ -15,6 +15,7 @@ import numpy as np
 from . import _lib
 from .lazy import ArrayIdentity, DeviceResult
 from .param import Param, Parameterized
+from .variational import SpikeAndSlabPosterior
 
 
 class _KCache(object):
@@ -274,19 +275,29 @@ class RBF(Stationary):
         if self.use_invLengthscale:
             self.inv_l.gradient = self.lengthscale.gradient * (self.lengthscale.values ** 3 / -2.)
 
-    # ---- psi-statistics for Gaussian inputs qX = NormalPosterior (reference `rbf.py:344-367`, `psi_comp/rbf_psi_comp.py`) ----
+    # ---- psi-statistics for Gaussian inputs qX = NormalPosterior (reference `rbf.py:344-367`, `psi_comp/rbf_psi_comp.py`) and,
+    # chosen by the type of qX, for a SpikeAndSlabPosterior (`psi_comp/ssrbf_psi_comp.py`; C-ABI mi355gp_ssrbf_psi / _grad) ----
     def _psi_operands(self, Z, qX):
         return self._slice_X(Z), self._slice_X(qX.mean), self._slice_X(qX.variance)
+
+    def _ss_operands(self, Z, qX):
+        return self._psi_operands(Z, qX) + (self._slice_X(qX.binary_prob),)
 
     def psi0(self, Z, qX):
         return np.full(qX.mean.shape[0], float(self.variance.values[0]))
 
     def psi1(self, Z, qX):
+        if isinstance(qX, SpikeAndSlabPosterior):
+            return _lib.ssrbf_psi(self.variance.values, self.lengthscale.values, self.ARD, *self._ss_operands(Z, qX),
+                                  want_psi2=False, device=self.device)[0]
         Zs, mu, S = self._psi_operands(Z, qX)
         return _lib.rbf_psi(self.variance.values, self.lengthscale.values, self.ARD, Zs, mu, S, want_psi2=False,
                             device=self.device)[0]
 
     def psi2(self, Z, qX):
+        if isinstance(qX, SpikeAndSlabPosterior):
+            return _lib.ssrbf_psi(self.variance.values, self.lengthscale.values, self.ARD, *self._ss_operands(Z, qX),
+                                  want_psi1=False, device=self.device)[1]
         Zs, mu, S = self._psi_operands(Z, qX)
         return _lib.rbf_psi(self.variance.values, self.lengthscale.values, self.ARD, Zs, mu, S, want_psi1=False,
                             device=self.device)[1]
@@ -295,6 +306,9 @@ class RBF(Stationary):
         """N x M x M ON THE HOST for a foreign consumer that wants the summands; the inference path never forms it.
         The cost is O(N) C-ABI calls: every row validates, uploads Z and allocates its buffers again (the device kernel has no
         per-row output mode yet)."""
+        if isinstance(qX, SpikeAndSlabPosterior):
+            raise NotImplementedError("RBF.psi2n: the per-point psi2 of a SpikeAndSlabPosterior is not implemented (the reference's "
+                                      "ssrbf_psi_comp has no return_psi2_n either)")
         Zs, mu, S = self._psi_operands(Z, qX)
         return np.stack([_lib.rbf_psi(self.variance.values, self.lengthscale.values, self.ARD, Zs, mu[n:n + 1], S[n:n + 1],
                                       want_psi1=False, device=self.device)[1] for n in range(mu.shape[0])])
@@ -302,6 +316,9 @@ class RBF(Stationary):
     def _psi_grad(self, dL_dpsi0, dL_dpsi1, dL_dpsi2, Z, qX):
         if dL_dpsi2 is not None and np.ndim(dL_dpsi2) != 2:
             raise NotImplementedError("RBF psi gradients take dL_dpsi2 as M x M (the summed psi2), not per data point")
+        if isinstance(qX, SpikeAndSlabPosterior):
+            return _lib.ssrbf_psi_grad(self.variance.values, self.lengthscale.values, self.ARD, *self._ss_operands(Z, qX),
+                                       dL_dpsi0=dL_dpsi0, dL_dpsi1=dL_dpsi1, dL_dpsi2=dL_dpsi2, device=self.device)
         Zs, mu, S = self._psi_operands(Z, qX)
         return _lib.rbf_psi_grad(self.variance.values, self.lengthscale.values, self.ARD, Zs, mu, S, dL_dpsi0, dL_dpsi1,
                                  dL_dpsi2, device=self.device)
@@ -322,7 +339,7 @@ class RBF(Stationary):
 
     def gradients_qX_expectations(self, dL_dpsi0, dL_dpsi1, dL_dpsi2, Z, qX):
         g = self._psi_grad(dL_dpsi0, dL_dpsi1, dL_dpsi2, Z, qX)
-        return self._scatter(g[3], qX.mean), self._scatter(g[4], qX.mean)
+        return tuple(self._scatter(x, qX.mean) for x in g[3:])        # (dmean, dvariance[, dbinary_prob])
 
     def to_dict(self):
         d = super(RBF, self).to_dict()
@@ -1067,7 +1084,7 @@ class White(Static):
         return np.zeros(np.asarray(Z).shape)
 
     def gradients_qX_expectations(self, dL_dpsi0, dL_dpsi1, dL_dpsi2, Z, qX):
-        return np.zeros(qX.mean.shape), np.zeros(qX.mean.shape)
+        return tuple(np.zeros(qX.mean.shape) for _ in range(3 if isinstance(qX, SpikeAndSlabPosterior) else 2))
 
 
 class Bias(Static):
@@ -1212,8 +1229,10 @@ class Add(CombinationKernel):
     # RBF or Linear, with any number of Bias and White parts; Bias (b = the sum of their variances) crosses with the psi1 of
     # the input-dependent part:  psi2_n += b (psi1_n 1^T + 1 psi1_n^T) + b^2, and every part sees dL_dpsi1 plus the OTHER
     # parts' psi1 times (dL_dpsi2 + dL_dpsi2^T).  Two input-dependent parts stay refused (their cross term needs E[k1 k2^T]).
-    def _psi_parts(self, psi_lin_bias=False):
+    def _psi_parts(self, psi_lin_bias=False, qX=None):
         how = "; Linear and Bias parts: pass psi_lin_bias=True"
+        if isinstance(qX, SpikeAndSlabPosterior):                     # one RBF part and White parts, whatever the keyword says
+            psi_lin_bias, how = False, " (spike-and-slab inputs: the Linear statistics, sslinear_psi_comp, are not implemented)"
         if psi_lin_bias:
             for p in self.parts:
                 if type(p) not in (RBF, Linear, Bias, White):
@@ -1242,13 +1261,13 @@ class Add(CombinationKernel):
         return [p for p in self.parts if isinstance(p, (RBF, Linear))][0]
 
     def psi0(self, Z, qX, psi_lin_bias=False):
-        return sum(p.psi0(Z, qX) for p in self._psi_parts(psi_lin_bias))
+        return sum(p.psi0(Z, qX) for p in self._psi_parts(psi_lin_bias, qX))
 
     def psi1(self, Z, qX, psi_lin_bias=False):
-        return sum(p.psi1(Z, qX) for p in self._psi_parts(psi_lin_bias))
+        return sum(p.psi1(Z, qX) for p in self._psi_parts(psi_lin_bias, qX))
 
     def psi2(self, Z, qX, psi_lin_bias=False):
-        out = sum(p.psi2(Z, qX) for p in self._psi_parts(psi_lin_bias))
+        out = sum(p.psi2(Z, qX) for p in self._psi_parts(psi_lin_bias, qX))
         b = self._bias_sum() if psi_lin_bias else 0.0
         if b != 0.0:                                      # the pairs of Bias parts, and Bias against the input-dependent part
             c = self._dep_part().psi1(Z, qX).sum(0)
@@ -1258,7 +1277,7 @@ class Add(CombinationKernel):
         return out
 
     def psi2n(self, Z, qX, psi_lin_bias=False):
-        out = sum(p.psi2n(Z, qX) for p in self._psi_parts(psi_lin_bias))
+        out = sum(p.psi2n(Z, qX) for p in self._psi_parts(psi_lin_bias, qX))
         b = self._bias_sum() if psi_lin_bias else 0.0
         if b != 0.0:
             p1 = self._dep_part().psi1(Z, qX)
@@ -1285,20 +1304,20 @@ class Add(CombinationKernel):
         return out
 
     def update_gradients_expectations(self, dL_dpsi0, dL_dpsi1, dL_dpsi2, Z, qX, psi_lin_bias=False):
-        parts = self._psi_parts(psi_lin_bias)
+        parts = self._psi_parts(psi_lin_bias, qX)
         for p, d1 in zip(parts, self._psi1_eff(parts, dL_dpsi1, dL_dpsi2, Z, qX)):
             p.update_gradients_expectations(dL_dpsi0, d1, dL_dpsi2, Z, qX)
 
     def gradients_Z_expectations(self, dL_dpsi0, dL_dpsi1, dL_dpsi2, Z, qX, psi_lin_bias=False):
-        parts = self._psi_parts(psi_lin_bias)
+        parts = self._psi_parts(psi_lin_bias, qX)
         return sum(p.gradients_Z_expectations(dL_dpsi0, d1, dL_dpsi2, Z, qX)
                    for p, d1 in zip(parts, self._psi1_eff(parts, dL_dpsi1, dL_dpsi2, Z, qX)))
 
     def gradients_qX_expectations(self, dL_dpsi0, dL_dpsi1, dL_dpsi2, Z, qX, psi_lin_bias=False):
-        parts = self._psi_parts(psi_lin_bias)
+        parts = self._psi_parts(psi_lin_bias, qX)
         gs = [p.gradients_qX_expectations(dL_dpsi0, d1, dL_dpsi2, Z, qX)
               for p, d1 in zip(parts, self._psi1_eff(parts, dL_dpsi1, dL_dpsi2, Z, qX))]
-        return sum(g[0] for g in gs), sum(g[1] for g in gs)
+        return tuple(sum(g[i] for g in gs) for i in range(len(gs[0])))
 
 
 class Prod(CombinationKernel):

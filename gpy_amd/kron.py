@@ -33,6 +33,7 @@ from .kern import RBF
 from .lazy import ArrayIdentity
 from .likelihoods import Gaussian
 from .models import GP
+from .variational import refuse_spike_and_slab
 
 log_2_pi = np.log(2 * np.pi)
 
@@ -176,6 +177,7 @@ class GaussianGridInference(LatentFunctionInference):
         return x.reshape(-1, 1)
 
     def inference(self, kern, X, likelihood, Y, Y_metadata=None):
+        refuse_spike_and_slab(X, "GaussianGridInference")
         X = np.asarray(X)
         if X.ndim != 2:
             raise ValueError("grid regression: X must be N x D, got shape %r" % (X.shape,))

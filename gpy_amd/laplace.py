@@ -15,6 +15,7 @@ from .inference import LatentFunctionInference, _DeviceState
 from .lazy import DeviceResult, kernel_signature
 from .linalg import jitter_ladder
 from .posterior import PosteriorExact
+from .variational import refuse_spike_and_slab
 
 
 class _LaplaceState(_DeviceState):
@@ -92,6 +93,7 @@ class Laplace(LatentFunctionInference):
 
     def inference(self, kern, X, likelihood, Y, mean_function=None, Y_metadata=None):
         assert mean_function is None, "inference with a mean function not implemented"
+        refuse_spike_and_slab(X, "Laplace")
         Y = entry_checks("Laplace", "Laplace inference", kern, Y)
         st, kd = begin_session(self, kern, X, Y)
         ctx, n = st.ctx, Y.shape[0]

@@ -407,5 +407,7 @@ class GPCoregionalizedRegression(GP):
 def __getattr__(name):
     """the latent variable models of the reference that this backend does not have are refused by name"""
     if name in ("SSGPLVM", "MRD", "GPLVM", "SparseGPLVM"):
-        raise NotImplementedError("GPy.models.%s is not implemented on the MI355X path; BayesianGPLVM is" % name)
+        raise NotImplementedError("GPy.models.%s is not implemented on the MI355X path; BayesianGPLVM is%s"
+                                  % (name, " (the spike-and-slab model with one RBF and White parts lives at "
+                                           "GPy.models.ss_gplvm.SSGPLVM / gpy_amd.SSGPLVM)" if name == "SSGPLVM" else ""))
     raise AttributeError("module %r has no attribute %r" % (__name__, name))

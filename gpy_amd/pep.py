@@ -20,7 +20,7 @@ import numpy as np
 from . import _lib
 from .lazy import LazyNM
 from .sparse import SparseSession, noise_variances, sparse_path_kernel_check
-from .variational import NormalPosterior
+from .variational import NormalPosterior, refuse_spike_and_slab
 
 
 class PEP(SparseSession):
@@ -38,6 +38,7 @@ class PEP(SparseSession):
         name = type(self).__name__
         if mean_function is not None:                             # pep.py:24, fitc.py:22
             raise NotImplementedError("%s: inference with a mean function is not implemented (the reference asserts the same)" % name)
+        refuse_spike_and_slab(X, name)
         if isinstance(X, NormalPosterior):
             raise NotImplementedError("%s: uncertain inputs (a NormalPosterior X) are not implemented; VarDTC covers them" % name)
         alpha = float(self.alpha)

@@ -38,7 +38,7 @@ from .likelihoods import Gaussian
 from .linalg import LinAlgError, jitter_ladder
 from .models import PredictionCallers
 from .param import Param, Parameterized
-from .variational import NormalPosterior, NormalPrior
+from .variational import NormalPosterior, NormalPrior, SpikeAndSlabPosterior, SpikeAndSlabPrior, refuse_spike_and_slab
 
 
 class SessionPosterior(object):
@@ -73,6 +73,9 @@ class SparsePosterior(SessionPosterior):
 
     def _raw_predict(self, kern, Xnew, pred_var, full_cov=False):
         dev, live = self._device, self._live(kern)
+        if isinstance(Xnew, SpikeAndSlabPosterior):
+            raise NotImplementedError("prediction at spike-and-slab new points (a SpikeAndSlabPosterior Xnew) is not implemented; "
+                                      "pass their means, or a NormalPosterior")
         if isinstance(Xnew, NormalPosterior):
             return self._raw_predict_uncertain(kern, Xnew, pred_var, full_cov, dev if live else None)
         if live:
@@ -233,8 +236,9 @@ class SparseSession(LatentFunctionInference):
 
 class VarDTC(SparseSession):
     const_jitter = 1e-8
-    _device_members = SparseSession._device_members + ("_S",)
+    _device_members = SparseSession._device_members + ("_S", "_G")
     _S = None                                                        # identity of the uploaded input variances
+    _G = None                                                        # ... and of the slab probabilities (None: Gaussian inputs)
 
     def __init__(self, device=0, maxtries=5, linear=False, psi_lin_bias=False, coregionalize=False):
         """`coregionalize=True`: the kernel may hold Coregionalize factors (`util.multioutput.ICM` / `LCM`) with certain inputs;
@@ -247,7 +251,7 @@ class VarDTC(SparseSession):
 
     def _ensure(self, X, Y):
         if super(VarDTC, self)._ensure(X, Y):
-            self._S = None                                             # (set_data discards input variances)
+            self._S = self._G = None                                   # (set_data discards input variances and slab probabilities)
 
     def _ensure_uncertain(self, mu, S, R):
         if (self._ctx is not None and self._X is not None and self._Y.matches(R) and self._X.value().shape == mu.shape
@@ -259,17 +263,40 @@ class VarDTC(SparseSession):
             if self._S is None or not self._S.matches(S):
                 self._ctx.set_input_variance(S)
                 self._S = ArrayIdentity(S)
+        if self._G is not None:                                        # the context last held spike-and-slab inputs
+            self._ctx.set_binary_prob(None)
+            self._G = None
+
+    def _ensure_ss(self, mu, S, G, R):
+        if (self._ctx is not None and self._X is not None and self._Y.matches(R) and self._X.value().shape == mu.shape
+                and not (self._X.matches(mu) and self._S is not None and self._S.matches(S)
+                         and self._G is not None and self._G.matches(G))):
+            self._ctx.set_inputs_ss(mu, S, G)                          # the same Y, new inputs: Y is not uploaded again
+            self._X, self._S, self._G = ArrayIdentity(mu), ArrayIdentity(S), ArrayIdentity(G)
+            return
+        self._ensure(mu, R)
+        if self._S is None or not self._S.matches(S):
+            self._ctx.set_input_variance(S)
+            self._S = ArrayIdentity(S)
+        if self._G is None or not self._G.matches(G):
+            self._ctx.set_binary_prob(G)
+            self._G = ArrayIdentity(G)
 
     def _inference_uncertain(self, kern, qX, Z, likelihood, Y, Y_metadata, mean_function, precision, Z_tilde):
         """X is a `NormalPosterior`: the psi-statistics form of the same evaluation (reference `var_dtc.py:66-215` with
         `uncertain_inputs`), for one RBF kernel alone or summed with White parts and ONE noise variance."""
         if mean_function is not None:                                  # var_dtc.py:85-86
             raise ValueError("Mean function not implemented with uncertain inputs or heteroscedasticity")
+        ss = isinstance(qX, SpikeAndSlabPosterior)                     # -> mi355gp_vardtc_inference_ss: one RBF and White parts
         parts = kern.parts if isinstance(kern, Add) else [kern]
-        covered = (RBF, Linear, Bias, White) if self.psi_lin_bias else (RBF, White)
+        covered = (RBF, Linear, Bias, White) if self.psi_lin_bias and not ss else (RBF, White)
         for p in parts:
             if type(p) not in covered:
                 what = type(p).__name__ if p.is_leaf else "%s of %s" % (type(p).__name__, ", ".join(type(f).__name__ for f in p.leaves()))
+                if ss:
+                    raise NotImplementedError("spike-and-slab inputs: the part %r (%s) has no psi-statistics on the MI355X sparse "
+                                              "path; one RBF kernel and White parts are covered (the reference's Linear "
+                                              "statistics, sslinear_psi_comp, are not implemented)" % (p.name, what))
                 if self.psi_lin_bias:
                     raise NotImplementedError("uncertain inputs: the part %r (%s) has no psi-statistics on the MI355X sparse path; "
                                               "one RBF or Linear kernel with Bias and White parts is covered" % (p.name, what))
@@ -277,7 +304,7 @@ class VarDTC(SparseSession):
                                           "one RBF kernel and White parts are covered (one RBF or Linear kernel with Bias and "
                                           "White parts: make the inference class with psi_lin_bias=True)" % (p.name, what))
         rbfs = [p for p in parts if isinstance(p, (RBF, Linear))]
-        if len(rbfs) != 1 and self.psi_lin_bias:
+        if len(rbfs) != 1 and self.psi_lin_bias and not ss:
             raise NotImplementedError("uncertain inputs: exactly one input-dependent part (RBF or Linear) is covered, got %d (%s); "
                                       "psi2 of two has cross terms that need E[k1 k2^T]"
                                       % (len(rbfs), ", ".join("%r: %s" % (p.name, type(p).__name__) for p in rbfs)))
@@ -291,10 +318,14 @@ class VarDTC(SparseSession):
         mu, S, Zs = kern._slice_X(qX.mean), kern._slice_X(qX.variance), kern._slice_X(Z)
         R = _lib.f64(Y)
         self._refuse_sharded("uncertain inputs are not supported by a row-sharded sparse context")
-        self._ensure_uncertain(mu, S, R)
         specs = kern.part_specs()
-        r = self._run(kern, lambda extra: self._ctx.vardtc_uncertain(specs, Zs, noise, extra_jitter=extra,
-                                                                     want_stage_ms=self.collect_stage_ms), Z)
+        if ss:
+            self._ensure_ss(mu, S, kern._slice_X(qX.binary_prob), R)
+            call = self._ctx.vardtc_ss
+        else:
+            self._ensure_uncertain(mu, S, R)
+            call = self._ctx.vardtc_uncertain
+        r = self._run(kern, lambda extra: call(specs, Zs, noise, extra_jitter=extra, want_stage_ms=self.collect_stage_ms), Z)
         M, N = Zs.shape[0], mu.shape[0]
         post, dL_dKmm = self._posterior(kern, M, r["woodbury_vector"])
         beta = float(1.0 / np.fmax(noise, self.const_jitter)[0])
@@ -304,11 +335,13 @@ class VarDTC(SparseSession):
                      "dL_dpsi2": LazyMM(self, _lib.SparseContext.FETCH_DLDPSI2_BETA, M, scale=beta),
                      "dL_dthetaL": likelihood.exact_inference_gradients(r["dnoise"], Y_metadata),
                      "fused": {"dtheta": r["dtheta"], "dZ": r["dZ"], "dmu": r["dmu"], "dS": r["dS"]}}
+        if ss:
+            grad_dict["fused"]["dgamma"] = r["dgamma"]
         return post, r["lml"] + (0.0 if Z_tilde is None else Z_tilde), grad_dict
 
     def inference(self, kern, X, Z, likelihood, Y, Y_metadata=None, mean_function=None, precision=None, Lm=None,
                   dL_dKmm=None, psi0=None, psi1=None, psi2=None, Z_tilde=None):
-        uncertain = isinstance(X, NormalPosterior)
+        uncertain = isinstance(X, (NormalPosterior, SpikeAndSlabPosterior))
         if not uncertain:
             sparse_path_kernel_check(kern, self.linear, self.coregionalize)
         if any(a is not None for a in (Lm, dL_dKmm, psi0, psi1, psi2)):
@@ -352,12 +385,16 @@ class SparseGP(PredictionCallers, Parameterized):
     Flat parameter order follows GPy's links: [Z, kern.variance, kern.lengthscale..., noise variance]
     (`sparse_gp.py:59`: Z is linked at index 0)."""
 
+    _takes_spike_and_slab = False                # SSGPLVM alone holds a SpikeAndSlabPosterior; every other model refuses it by name
+
     def __init__(self, X, Y, Z, kernel, likelihood, inference_method=None, name="sparse gp", device=0, mean_function=None,
                  Y_metadata=None, X_variance=None):
         super(SparseGP, self).__init__(name)
         self.mean_function, self.Y_metadata = mean_function, Y_metadata
         self.Y = freeze(Y)                           # private read-only copies (cf. `ObsAr`, reference `core/gp.py:44-60`)
-        if isinstance(X, NormalPosterior):           # (reference `core/sparse_gp.py:45-51`)
+        if not self._takes_spike_and_slab:
+            refuse_spike_and_slab(X, type(self).__name__)
+        if isinstance(X, (NormalPosterior, SpikeAndSlabPosterior)):   # (reference `core/sparse_gp.py:45-51`)
             self.X = X.copy()
         elif X_variance is not None:                 # data, not a parameter: the flat parameter order is unchanged
             self.X = NormalPosterior(X, X_variance)
@@ -380,7 +417,7 @@ class SparseGP(PredictionCallers, Parameterized):
 
     def has_uncertain_inputs(self):
         """(reference `core/sparse_gp.py:68-69`)"""
-        return isinstance(self.X, NormalPosterior)
+        return isinstance(self.X, (NormalPosterior, SpikeAndSlabPosterior))
 
     def parameters_changed(self):
         # certain and uncertain inputs alike: the kernel and inducing-input gradients of `_update_gradients` (reference
@@ -416,7 +453,7 @@ class SparseGP(PredictionCallers, Parameterized):
 
     def _raw_predict(self, Xnew, full_cov=False, kern=None):
         """(reference `core/sparse_gp.py:121-160` -> `posterior.py:198-262`; same signature as `GP._raw_predict`)"""
-        if isinstance(Xnew, NormalPosterior):
+        if isinstance(Xnew, (NormalPosterior, SpikeAndSlabPosterior)):
             raise NotImplementedError("prediction at uncertain new points is not implemented; pass their means")
         mu, var = self.posterior._raw_predict(self.kern if kern is None else kern, np.asarray(Xnew), self.Z.values,
                                               full_cov=full_cov)
@@ -476,6 +513,7 @@ class SparseGPRegression(SparseGP):
 
     def __init__(self, X, Y, kernel=None, Z=None, num_inducing=10, noise_var=1., device=0, seed=None, mean_function=None,
                  X_variance=None, linear=False, psi_lin_bias=False):
+        refuse_spike_and_slab(X, "SparseGPRegression")
         X = np.asarray(X, dtype=np.float64)
         if kernel is None:
             kernel = RBF(X.shape[1], device=device)
@@ -624,3 +662,125 @@ class BayesianGPLVM(SparseGP):
 
     def infer_newX(self, Y_new, optimize=True):
         raise NotImplementedError("BayesianGPLVM.infer_newX is not implemented on the MI355X path")
+
+
+class SSGPLVM(SparseGP):
+    """Spike-and-slab GP latent variable model (reference `GPy/models/ss_gplvm.py:177-270`): a `SparseGP` whose inputs are the
+    parameters of q(x_nq) = gamma_nq N(mean_nq, variance_nq) + (1 - gamma_nq) delta_0, with the spike-and-slab prior's KL term
+    subtracted from the bound; gamma switches a latent dimension off per point where ARD does so per model.  The flat
+    parameter order is [X.mean, X.variance, X.binary_prob, Z, kernel, noise].  The bound and its gradients in every parameter
+    run on the device through `VarDTC` (`mi355gp_vardtc_inference_ss`): the kernel is one `RBF` alone or summed with `White`
+    parts.  Defaults as the reference's: gamma = 0.5 + 0.1 randn clipped to [1e-9, 1 - 1e-9], `RBF(input_dim,
+    lengthscale=fracs, ARD=True)` -- `fracs`, where `BayesianGPLVM` takes `1 / fracs`: the reference differs between the two
+    (`ss_gplvm.py:221`, `bayesian_gplvm.py:46`) and is followed -- `Gaussian()`, Z a permutation of X's rows, pi = 0.5.  The
+    optimiser sees gamma through the reference's `Logistic(1e-10, 1 - 1e-10)` transform (`variational.py:181`)."""
+    GAMMA_LOWER, GAMMA_UPPER = 1e-10, 1.0 - 1e-10
+    _takes_spike_and_slab = True
+
+    def __init__(self, Y, input_dim, X=None, X_variance=None, Gamma=None, init="PCA", num_inducing=10, Z=None, kernel=None,
+                 inference_method=None, likelihood=None, name="Spike_and_Slab GPLVM", group_spike=False, IBP=False, SLVM=False,
+                 alpha=2., beta=2., connM=None, tau=None, mpi_comm=None, pi=None, learnPi=False, normalizer=False, sharedX=False,
+                 variational_prior=None, device=0, Y_metadata=None):
+        for arg, value in (("group_spike", group_spike), ("IBP", IBP), ("SLVM", SLVM), ("learnPi", learnPi), ("sharedX", sharedX),
+                           ("mpi_comm", mpi_comm), ("normalizer", normalizer), ("variational_prior", variational_prior)):
+            if value is not None and value is not False:
+                raise NotImplementedError("SSGPLVM: %s = %r is not implemented on the MI355X path (the IBP / SLVM / group-spike "
+                                          "posteriors, learning pi, shared X, MPI and normalizers are out of scope)" % (arg, value))
+        if inference_method is not None and not isinstance(inference_method, VarDTC):
+            raise NotImplementedError("SSGPLVM: the inference method %s is not implemented on the MI355X path (the reference's "
+                                      "default, VarDTC_minibatch, included); VarDTC is" % type(inference_method).__name__)
+        Y = np.asarray(Y, dtype=np.float64)
+        if X is None:
+            from .util.initialization import initialize_latent
+            X, fracs = initialize_latent(init, input_dim, Y)
+        else:
+            X = np.asarray(X, dtype=np.float64)
+            fracs = np.ones(input_dim)
+        if X.shape != (Y.shape[0], input_dim):
+            raise ValueError("SSGPLVM: X must be %d x %d (one latent point per row of Y), got %r" % (Y.shape[0], input_dim, X.shape))
+        self.init = init
+        if X_variance is None:
+            X_variance = np.random.uniform(0, 0.1, X.shape)
+        if Gamma is None:
+            Gamma = np.clip(0.5 + 0.1 * np.random.randn(X.shape[0], input_dim), 1e-9, 1.0 - 1e-9)
+        if Z is None:
+            Z = np.random.permutation(X.copy())[:num_inducing]
+        Z = np.asarray(Z, dtype=np.float64)
+        if Z.ndim != 2 or Z.shape[1] != X.shape[1]:
+            raise ValueError("SSGPLVM: Z must have %d columns, got shape %r" % (X.shape[1], Z.shape))
+        if kernel is None:
+            kernel = RBF(input_dim, lengthscale=fracs, ARD=True, device=device)
+        if any(isinstance(k, Linear) for k in kernel.leaves()):
+            raise NotImplementedError("SSGPLVM: a Linear kernel needs the spike-and-slab Linear statistics (sslinear_psi_comp), "
+                                      "which are not implemented on the MI355X path; one RBF kernel and White parts are")
+        if likelihood is None:
+            likelihood = Gaussian()
+        self.variational_prior = SpikeAndSlabPrior(pi=0.5 if pi is None else pi)
+        super(SSGPLVM, self).__init__(SpikeAndSlabPosterior(X, X_variance, Gamma), Y, Z, kernel, likelihood,
+                                      inference_method=inference_method, name=name, device=device, Y_metadata=Y_metadata)
+        self.link_parameter(self.X, index=0)
+
+    def set_X_gradients(self, X, X_grad):
+        """(reference `ss_gplvm.py:245-247`)"""
+        X.mean.gradient, X.variance.gradient, X.binary_prob.gradient = X_grad
+
+    def get_X_gradients(self, X):
+        """(reference `ss_gplvm.py:249-251`)"""
+        return X.mean.gradient, X.variance.gradient, X.binary_prob.gradient
+
+    def _scatter_X(self, g):
+        if g.shape == self.X.shape:
+            return g
+        full = np.zeros(self.X.shape)
+        full[:, self.kern.active_dims] = g
+        return full
+
+    def parameters_changed(self):
+        super(SSGPLVM, self).parameters_changed()
+        self._log_marginal_likelihood = self._log_marginal_likelihood - self.variational_prior.KL_divergence(self.X)
+        # gradients_qX_expectations of the reference (ss_gplvm.py:266): the device reduced them inside the fit
+        fused = self.grad_dict["fused"]
+        self.set_X_gradients(self.X, tuple(self._scatter_X(fused[k]) for k in ("dmu", "dS", "dgamma")))
+        self.variational_prior.update_gradients_KL(self.X)
+
+    # ---- the optimiser's view: as SparseGP's, with gamma through Logistic(1e-10, 1 - 1e-10) (paramz transformations.Logistic) ----
+    def _logistic(self):
+        return np.concatenate([np.full(p.size, p is self.X.binary_prob) for p in self.flattened_parameters()])
+
+    @property
+    def optimizer_array(self):
+        x, lg, p = SparseGP.optimizer_array.fget(self), self._logistic(), self.param_array
+        lo, hi = self.GAMMA_LOWER, self.GAMMA_UPPER
+        g = np.clip(np.where(lg, p, 0.5), lo + 1e-10 * (hi - lo), hi - 1e-10 * (hi - lo))
+        return np.where(lg, np.log((g - lo) / (hi - g)), x)
+
+    @optimizer_array.setter
+    def optimizer_array(self, x):
+        x = np.asarray(x, dtype=np.float64)
+        pos, lg = self._positive(), self._logistic()
+        lo, hi = self.GAMMA_LOWER, self.GAMMA_UPPER
+        g = lo + (hi - lo) / (1.0 + np.exp(-np.where(lg, x, 0.0)))
+        self.param_array = np.where(lg, g, np.where(pos, np.exp(np.where(pos, x, 0.0)), x))
+
+    def _grads(self, x):
+        g, lg, p = super(SSGPLVM, self)._grads(x), self._logistic(), self.param_array
+        lo, hi = self.GAMMA_LOWER, self.GAMMA_UPPER
+        return np.where(lg, g * (p - lo) * (hi - p) / (hi - lo), g)
+
+    def input_sensitivity(self):
+        """(reference `ss_gplvm.py:272-276`)"""
+        return self.kern.input_sensitivity() if getattr(self.kern, "ARD", False) else self.variational_prior.pi
+
+    def _raw_predict(self, Xnew, full_cov=False, kern=None):
+        """as `SparseGP._raw_predict`; a `NormalPosterior` Xnew is predicted at as a distribution (the Woodbury pair does not care
+        how it was made); a `SpikeAndSlabPosterior` Xnew is refused"""
+        if not isinstance(Xnew, (NormalPosterior, SpikeAndSlabPosterior)):
+            return super(SSGPLVM, self)._raw_predict(Xnew, full_cov=full_cov, kern=kern)
+        return self.posterior._raw_predict(self.kern if kern is None else kern, Xnew, self.Z.values, full_cov=full_cov)
+
+    def sample_W(self, nSamples, raw_samples=False):
+        raise NotImplementedError("SSGPLVM.sample_W needs a Linear kernel, whose spike-and-slab statistics (sslinear_psi_comp) are "
+                                  "not implemented on the MI355X path")
+
+    def infer_newX(self, Y_new, optimize=True):
+        raise NotImplementedError("SSGPLVM.infer_newX is not implemented on the MI355X path")

@@ -19,7 +19,7 @@ from .lazy import LazyArray, freeze
 from .param import Param
 from .sparse import SessionPosterior, SparseGP, SparseSession, sparse_path_kernel_check
 from .util import choleskies
-from .variational import NormalPosterior
+from .variational import NormalPosterior, refuse_spike_and_slab
 
 
 class SVGPPosterior(SessionPosterior):
@@ -85,6 +85,7 @@ class SVGP(SparseSession):
                   batch_scale=1.0):
         if mean_function is not None:
             raise NotImplementedError("SVGP on the MI355X path has no mean function (svgp.py:29-31,62-74,103-107 are not built)")
+        refuse_spike_and_slab(X, "SVGP")
         if isinstance(X, NormalPosterior):
             raise NotImplementedError("SVGP on the MI355X path takes certain inputs; uncertain inputs are covered by VarDTC")
         if KL_scale != 1.0:
@@ -160,6 +161,7 @@ class SVGPModel(SparseGP):
                  num_latent_functions=None, mean_function=None, linear=False):
         if mean_function is not None:
             raise NotImplementedError("SVGP on the MI355X path has no mean function")
+        refuse_spike_and_slab(X, "SVGP")
         if isinstance(X, NormalPosterior):
             raise NotImplementedError("SVGP on the MI355X path takes certain inputs")
         self.batchsize = batchsize

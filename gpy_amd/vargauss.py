@@ -28,6 +28,7 @@ from .laplace import begin_session, entry_checks
 from .lazy import DeviceResult, LazyArray, kernel_signature
 from .linalg import jitter_ladder
 from .posterior import PosteriorExact
+from .variational import refuse_spike_and_slab
 
 
 class _LazySigma(LazyArray):
@@ -79,6 +80,7 @@ class VarGauss(LatentFunctionInference):
         return {"class": "GPy.inference.latent_function_inference.var_gauss.VarGauss"}
 
     def inference(self, kern, X, likelihood, Y, mean_function=None, Y_metadata=None, Z=None):
+        refuse_spike_and_slab(X, "VarGauss")
         if mean_function is not None:
             raise NotImplementedError("VarGauss inference with a mean function is not implemented on the MI355X path")
         Y = entry_checks("VarGauss", "VarGauss inference", kern, Y)

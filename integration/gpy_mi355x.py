@@ -316,3 +316,50 @@ def make_sparse_classes(L, gpy=None):
             return post, out[0] + (0.0 if Z_tilde is None else Z_tilde), grad_dict
 
     return types.SimpleNamespace(VarDTC=VarDTC, LazyNM=LazyNM)
+
+
+def bind_psi_ss(L):
+    """argument types of the stateless spike-and-slab psi-statistics of include/mi355gp_psi_ss.h on an already bound library"""
+    from numpy.ctypeslib import ndpointer
+    dp = ndpointer(np.float64, flags="C_CONTIGUOUS")
+    ci, i64, cd = ctypes.c_int, ctypes.c_int64, ctypes.c_double
+    head = [ci, cd, dp, ci, dp, i64, dp, dp, dp, i64, ci]             # device, variance, lengthscale, ard, Z, M, mu, S, gamma, N, D
+    L.mi355gp_ssrbf_psi.argtypes = head + [_p] * 3
+    L.mi355gp_ssrbf_psi_grad.argtypes = head + [_p] * 4 + [dp] * 6
+    return L
+
+
+def make_psicomp_ssrbf(L, device=0):
+    """The object a GPy maintainer assigns to `kernel.psicomp` where `GPy/models/ss_gplvm.py:222-223` assigns
+    `PSICOMP_SSRBF_GPU()`: the two methods of `GPy/kern/src/psi_comp/ssrbf_psi_gpucomp.py:377,411`, same arguments and return
+    values, on `mi355gp_ssrbf_psi` / `mi355gp_ssrbf_psi_grad`.  dL_dpsi2 is symmetrised inside the library."""
+    bind_psi_ss(L)
+
+    def check(rc, what):
+        if rc < 0:
+            raise RuntimeError("%s failed (rc=%d): %s" % (what, rc, L.mi355gp_last_error().decode()))
+
+    def operands(kern, Z, q):
+        ls = _f64(np.asarray(kern.lengthscale, dtype=float).ravel())
+        Z, mu, S, g = _f64(np.asarray(Z)), _f64(np.asarray(q.mean)), _f64(np.asarray(q.variance)), _f64(np.asarray(q.binary_prob))
+        N, D = mu.shape
+        return (device, float(np.asarray(kern.variance).ravel()[0]), ls, int(ls.size != 1), Z, Z.shape[0], mu, S, g, N, D, None), N, Z.shape[0], D
+
+    class PSICOMP_SSRBF_MI355X(object):
+        def psicomputations(self, kern, Z, variational_posterior, return_psi2_n=False):
+            if return_psi2_n:
+                raise NotImplementedError("psi2 per data point is not implemented for spike-and-slab inputs")
+            args, N, M, D = operands(kern, Z, variational_posterior)
+            psi1, psi2 = np.empty((N, M)), np.empty((M, M))
+            check(L.mi355gp_ssrbf_psi(*(args + (_ptr(psi1), _ptr(psi2)))), "mi355gp_ssrbf_psi")
+            return np.full(N, args[1]), psi1, psi2
+
+        def psiDerivativecomputations(self, kern, dL_dpsi0, dL_dpsi1, dL_dpsi2, Z, variational_posterior):
+            args, N, M, D = operands(kern, Z, variational_posterior)
+            d0, d1, d2 = _f64(np.ravel(dL_dpsi0)), _f64(np.asarray(dL_dpsi1)), _f64(np.asarray(dL_dpsi2))
+            dvar, dl = np.zeros(1), np.zeros(D if args[3] else 1)
+            dZ, dmu, dS, dg = np.zeros((M, D)), np.zeros((N, D)), np.zeros((N, D)), np.zeros((N, D))
+            check(L.mi355gp_ssrbf_psi_grad(*(args + (_ptr(d0), _ptr(d1), _ptr(d2), dvar, dl, dZ, dmu, dS, dg))), "mi355gp_ssrbf_psi_grad")
+            return dvar[0], dl, dZ, dmu, dS, dg
+
+    return PSICOMP_SSRBF_MI355X()
