@@ -19,7 +19,7 @@ from .likelihoods import Bernoulli, Gaussian, HeteroscedasticGaussian, MixedNois
 from .models import (GP, GPClassification, GPCoregionalizedRegression, GPHeteroscedasticRegression, GPRegression,
                      GPVariationalGaussianApproximation)
 from .posterior import PosteriorEP, PosteriorExact, StudentTPosterior
-from .sparse import SSGPLVM, BayesianGPLVM, SparseGP, SparseGPCoregionalizedRegression, SparseGPRegression, VarDTC
+from .sparse import SSGPLVM, BayesianGPLVM, BayesianGPLVMMiniBatch, SparseGP, SparseGPCoregionalizedRegression, SparseGPRegression, VarDTC
 from .pep import FITC, PEP
 from .epdtc import EPDTC, SparseGPClassification
 from .svgp import SVGPModel as SVGP
@@ -27,7 +27,7 @@ from .svgp import SVGPPosterior
 from .variational import NormalPosterior, NormalPrior, SpikeAndSlabPosterior, SpikeAndSlabPrior
 
 __all__ = ["RBF", "OU", "ExpQuad", "HeteroscedasticGaussian", "StudentTPosterior", "Matern52", "Matern32", "Exponential", "RatQuad", "Cosine", "Sinc", "ExpQuadCosine", "StdPeriodic", "Coregionalize", "Linear", "MLP", "Poly", "MixedNoise", "Stationary", "White", "Bias", "Add", "Prod", "Gaussian", "ExactGaussianInference", "ExactStudentTInference",
-           "PosteriorExact", "GP", "GPRegression", "GPHeteroscedasticRegression", "GPCoregionalizedRegression", "Laplace", "LaplacePosterior", "EP", "PosteriorEP", "Bernoulli", "StudentT", "Poisson", "GPClassification", "VarDTC", "SparseGP", "SparseGPRegression", "SparseGPCoregionalizedRegression", "SVGP", "SVGPPosterior", "NormalPosterior", "NormalPrior", "SpikeAndSlabPosterior", "SpikeAndSlabPrior", "BayesianGPLVM", "SSGPLVM", "FITC", "PEP", "EPDTC", "SparseGPClassification", "VarGauss", "VarGaussPosterior", "GPVariationalGaussianApproximation", "GaussianGridInference", "GridPosterior", "GpGrid", "GPRegressionGrid", "MI355GPError", "build", "device_count"]
+           "PosteriorExact", "GP", "GPRegression", "GPHeteroscedasticRegression", "GPCoregionalizedRegression", "Laplace", "LaplacePosterior", "EP", "PosteriorEP", "Bernoulli", "StudentT", "Poisson", "GPClassification", "VarDTC", "SparseGP", "SparseGPRegression", "SparseGPCoregionalizedRegression", "SVGP", "SVGPPosterior", "NormalPosterior", "NormalPrior", "SpikeAndSlabPosterior", "SpikeAndSlabPrior", "BayesianGPLVM", "BayesianGPLVMMiniBatch", "SSGPLVM", "FITC", "PEP", "EPDTC", "SparseGPClassification", "VarGauss", "VarGaussPosterior", "GPVariationalGaussianApproximation", "GaussianGridInference", "GridPosterior", "GpGrid", "GPRegressionGrid", "MI355GPError", "build", "device_count"]
 
 # GPy's import paths, so that `import gpy_amd as GPy` reads like the reference on this path:
 #   GPy.kern.RBF, GPy.likelihoods.Gaussian, GPy.models.GPRegression / SparseGPRegression / GPHeteroscedasticRegression,
@@ -39,7 +39,7 @@ __all__ = ["RBF", "OU", "ExpQuad", "HeteroscedasticGaussian", "StudentTPosterior
 #   GPy.inference.latent_function_inference.VarGauss (and .var_gauss.VarGauss), GPy.models.GPVariationalGaussianApproximation,
 #   GPy.models.GPRegressionGrid, GPy.core.GpGrid, GPy.inference.latent_function_inference.GaussianGridInference (and
 #   .gaussian_grid_inference.GaussianGridInference, .grid_posterior.GridPosterior), GPy.kern.GridRBF,
-#   GPy.util.choleskies, GPy.models.BayesianGPLVM, GPy.util.initialization.initialize_latent,
+#   GPy.util.choleskies, GPy.models.BayesianGPLVM, GPy.models.BayesianGPLVMMiniBatch (and .bayesian_gplvm_minibatch), GPy.util.initialization.initialize_latent,
 #   GPy.models.SparseGPCoregionalizedRegression, GPy.models.ss_gplvm.SSGPLVM,
 #   GPy.core.parameterization.variational.SpikeAndSlabPosterior / SpikeAndSlabPrior
 from . import ep, epdtc, inference, kern, kron, laplace, likelihoods, link_functions, linalg, models, pep, sparse, svgp, util, vargauss  # noqa: E402
@@ -48,6 +48,8 @@ import types as _types  # noqa: E402
 models.SparseGPRegression = SparseGPRegression
 models.SparseGPCoregionalizedRegression = SparseGPCoregionalizedRegression
 models.BayesianGPLVM = BayesianGPLVM
+models.BayesianGPLVMMiniBatch = BayesianGPLVMMiniBatch
+models.bayesian_gplvm_minibatch = _types.SimpleNamespace(BayesianGPLVMMiniBatch=BayesianGPLVMMiniBatch)
 models.ss_gplvm = _types.SimpleNamespace(SSGPLVM=SSGPLVM)         # (GPy.models.SSGPLVM itself keeps refusing: models.__getattr__)
 models.SparseGPClassification = SparseGPClassification
 models.GPRegressionGrid = GPRegressionGrid

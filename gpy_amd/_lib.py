@@ -89,6 +89,8 @@ def build(force=False):
     srcs.append(os.path.join(_HERE, "..", "include", "mi355gp_psi_lin.h"))
     srcs.append(os.path.join(_HERE, "..", "include", "mi355gp_debug_psi_lin.h"))
     srcs.append(os.path.join(_HERE, "..", "include", "mi355gp_psi_ss.h"))
+    srcs.append(os.path.join(_HERE, "..", "include", "mi355gp_sparse_missing.h"))
+    srcs.append(os.path.join(_HERE, "..", "include", "mi355gp_debug_sparse_missing.h"))
     srcs.append(os.path.join(_HERE, "..", "include", "mi355gp_vargauss.h"))
     srcs.append(os.path.join(_HERE, "..", "include", "mi355gp_kron.h"))
     product = os.path.join(_HERE, "libmi355gp.so")
@@ -273,6 +275,23 @@ KRON_ABI = {
     "mi355gp_kron_mode_probe": [_vp, _i64, _i64, _i64, _ci, _dp, _dp, _dp, _ci, _c_dp],
     "mi355gp_kron_get_ms": [_vp, _c_dp],
 }
+# include/mi355gp_sparse_missing.h: psi2 and its chain rule for several row masks at once (missing data), in its order
+# (tests/test_oracle_missing.py holds the table against that header's prototypes)
+MISSING_ABI = {
+    "mi355gp_psi_groups_batch": [],
+    "mi355gp_rbf_psi2_groups": [_ci, _cd, _dp, _ci, _dp, _i64, _dp, _dp, _i64, _ci, _dp, _ci, _dp],
+    "mi355gp_rbf_psi_grad_groups": [_ci, _cd, _dp, _ci, _dp, _i64, _dp, _dp, _i64, _ci, _dp, _ci, _dp] + [_dp] * 5,
+    "mi355gp_sparse_set_output_groups": [_vp, _ci, _ip, _c_dp],
+    "mi355gp_vardtc_inference_missing": [_vp, _ci, _parts, _dp, _i64, _dp, _i64, _cd, _dp] + [_c_dp] * 6,
+    "mi355gp_sparse_select_output_group": [_vp, _ci],
+    "mi355gp_sparse_fetch_group_scalars": [_vp, _dp],
+}
+# include/mi355gp_debug_sparse_missing.h: the stateless pair with the replaced route and the kernels' stream time, diagnostics
+# (held by the same test)
+DEBUG_MISSING_ABI = {
+    "mi355gp_dbg_rbf_psi2_groups": [_ci, _cd, _dp, _ci, _dp, _i64, _dp, _dp, _i64, _ci, _dp, _ci, _ci, _dp, _c_dp],
+    "mi355gp_dbg_rbf_psi_grad_groups": [_ci, _cd, _dp, _ci, _dp, _i64, _dp, _dp, _i64, _ci, _dp, _ci, _dp, _ci] + [_dp] * 5 + [_c_dp],
+}
 TILEOPS = {"trmm_lower": 0, "trmm_lower_T": 1, "trmm64": 2, "gram_splitk": 3, "update_nt": 4}    # MI355GP_TILEOP_*
 
 
@@ -288,7 +307,7 @@ def lib():
             build()
         L = ctypes.CDLL(LIB_PATH)
         for table in (ABI, DEBUG_LAUUM_ABI, DEBUG_TILEOPS_ABI, EPDTC_ABI, SPARSE_DIAG_ABI, SPARSE_COREG_ABI, DEBUG_SPARSE_COREG_ABI, PSI_LIN_ABI, DEBUG_PSI_LIN_ABI,
-                      PSI_SS_ABI, VARGAUSS_ABI, KRON_ABI):
+                      PSI_SS_ABI, VARGAUSS_ABI, KRON_ABI, MISSING_ABI, DEBUG_MISSING_ABI):
             for name, argtypes in table.items():
                 getattr(L, name).argtypes = argtypes
         L.mi355gp_last_error.restype = L.mi355gp_version.restype = _str
@@ -741,6 +760,52 @@ class SparseContext(_Handle):
         res.update(trA=out[2], data_fit=out[3], dmu=dmu, dS=dS)
         return rc, res
 
+    def set_output_groups(self, group_of_output, W):
+        """The row masks of Y's columns for a fit with missing data (`mi355gp_sparse_set_output_groups`; `output_groups(Y)` makes
+        them): group_of_output (Dy ints) and W (N x G, 0 / 1).  The Y of `set_data` holds 0 where unobserved.  None clears them."""
+        if group_of_output is None:
+            check(lib().mi355gp_sparse_set_output_groups(self._h, 0, None, None), "mi355gp_sparse_set_output_groups")
+            self.G = 0
+            return
+        gof, W = np.ascontiguousarray(group_of_output, dtype=np.int32), f64(W)
+        assert gof.shape == (self.Dy,) and W.ndim == 2 and W.shape[0] == self.N, "group_of_output has Dy entries, W is N x G"
+        check(lib().mi355gp_sparse_set_output_groups(self._h, W.shape[1], gof.ctypes.data_as(_ip), _opt(W)), "mi355gp_sparse_set_output_groups")
+        self.G, self.group_of_output = W.shape[1], gof.copy()
+
+    def vardtc_missing(self, specs, Z, noise, extra_jitter=0.0, want_dmu_dS=True, want_stage_ms=False):
+        """One evaluation with uncertain inputs and missing entries of Y (`set_output_groups` first; one RBF part alone or with
+        White parts, ONE noise variance).  (info, dict(lml, dnoise, dtheta (concatenated), dZ, woodbury_vector, dmu, dS,
+        group_scalars (G x 8: lml, dnoise, trA, data_fit, ... per group)[, stage_ms]))"""
+        arr, keep, ntheta = make_parts(specs)
+        noise = f64(np.atleast_1d(noise)).ravel()
+        dmu = np.zeros((self.N, self.D)) if want_dmu_dS else None
+        dS = np.zeros((self.N, self.D)) if want_dmu_dS else None
+        rc, out, res = self._fit("mi355gp_vardtc_inference_missing", (len(specs), arr), ntheta, Z,
+                                 (noise, noise.size, float(extra_jitter)), (dmu, dS), want_stage_ms)
+        gs = np.zeros((self.G, NUM_OUT))
+        check(lib().mi355gp_sparse_fetch_group_scalars(self._h, gs), "mi355gp_sparse_fetch_group_scalars")
+        res.update(trA=out[2], data_fit=out[3], dmu=dmu, dS=dS, group_scalars=gs)
+        return rc, res
+
+    def select_output_group(self, g):
+        """group g's woodbury_inv and psi2 become the context's current ones: `predict`, `predict_uncertain` and `fetch` then
+        serve the outputs of that group (`mi355gp_sparse_select_output_group`)"""
+        check(lib().mi355gp_sparse_select_output_group(self._h, int(g)), "mi355gp_sparse_select_output_group")
+
+    def predict_missing(self, specs, Xnew, S_new=None):
+        """(mean, variance), both M* x Dy, of the posterior of the last `vardtc_missing` call at certain points or at
+        N(Xnew, diag S_new): the mean from all Woodbury columns, output d's variance from its group's woodbury_inv
+        (`posterior.py:243-246`, `:268`) -- one device contraction per group"""
+        mean, var = None, None
+        for g in range(self.G):
+            self.select_output_group(g)
+            m, v = self.predict(specs, Xnew) if S_new is None else self.predict_uncertain(specs, Xnew, S_new)
+            if var is None:
+                mean, var = m, np.empty_like(m)
+            d = np.nonzero(self.group_of_output == g)[0]
+            var[:, d] = v if v.shape[1] == 1 else v[:, d]
+        return mean, var
+
     def set_binary_prob(self, gamma):
         """Slab probabilities (N x D, strictly inside (0, 1)) next to the means and variances: spike-and-slab inputs
         (`mi355gp_sparse_set_binary_prob`).  None takes the context back to Gaussian inputs."""
@@ -1016,6 +1081,65 @@ def rbf_psi_grad(variance, lengthscale, ARD, Z, mu, S, dL_dpsi0=None, dL_dpsi1=N
     check(lib().mi355gp_rbf_psi_grad(device, *(args + (_opt(d0), _opt(d1), _opt(d2), dvar, dl, dZ, dmu, dS))),
           "mi355gp_rbf_psi_grad")
     return dvar[0], dl, dZ, dmu, dS
+
+
+def output_groups(Y):
+    """(group_of_output (Dy ints), W (N x G, 0 / 1), Y with 0 for NaN) of an output matrix with NaN where unobserved: columns with
+    the same observed rows share a group, groups in order of their first column (`stochastics.py:57-79`)"""
+    Y = np.asarray(Y, dtype=np.float64)
+    obs = ~np.isnan(Y)
+    first, gof = {}, np.empty(Y.shape[1], dtype=np.int32)
+    for d in range(Y.shape[1]):
+        gof[d] = first.setdefault(obs[:, d].tobytes(), len(first))
+    W = np.stack([obs[:, int(np.argmax(gof == g))] for g in range(len(first))], axis=1).astype(np.float64)
+    return gof, W, np.where(obs, Y, 0.0)
+
+
+def psi_groups_batch():
+    """groups one launch of a group-batched psi2 kernel carries (PSI_GB of csrc/psi_missing.h)"""
+    return int(lib().mi355gp_psi_groups_batch())
+
+
+def _group_args(variance, lengthscale, ARD, Z, mu, S, W):
+    args, _ = _psi_args(variance, lengthscale, ARD, Z, mu, S, None)
+    W = f64(W)
+    assert W.ndim == 2 and W.shape[0] == args[7] and W.shape[1] >= 1, "W is N x G, one 0/1 column per group"
+    return args[:9] + (W, W.shape[1])
+
+
+def rbf_psi2_groups(variance, lengthscale, ARD, Z, mu, S, W, loop=False, device=0, want_ms=False):
+    """psi2_g = sum_n W[n, g] psi2n for every group g (G x M x M) of an RBF kernel for inputs N(mu, diag S): the psi2 side of a
+    fit with missing data (reference `sparse_gp_minibatch.py:228-286`), every exponential evaluated once for a batch of groups.
+    `loop=True` (a diagnostic): the single-mask kernel once per group instead, the route the batched kernel replaces; `want_ms`:
+    also the stream time of the psi2 kernels."""
+    require_device(device)
+    args = _group_args(variance, lengthscale, ARD, Z, mu, S, W)
+    M, G = args[4], args[10]
+    out, ms = np.empty((G, M, M)), ctypes.c_double(0.0)
+    if loop or want_ms:                                              # the diagnostic entry (include/mi355gp_debug_sparse_missing.h)
+        check(lib().mi355gp_dbg_rbf_psi2_groups(device, *(args + (int(bool(loop)), out, ctypes.byref(ms)))), "mi355gp_dbg_rbf_psi2_groups")
+    else:
+        check(lib().mi355gp_rbf_psi2_groups(device, *(args + (out,))), "mi355gp_rbf_psi2_groups")
+    return (out, ms.value) if want_ms else out
+
+
+def rbf_psi_grad_groups(variance, lengthscale, ARD, Z, mu, S, W, dL_dpsi2, loop=False, device=0, want_ms=False):
+    """(dvariance, dlengthscale, dZ, dmu, dS) of sum_g sum(dL_dpsi2[g] * psi2_g), psi2_g = sum_n W[n, g] psi2n: the chain rule of
+    `rbf_psi_comp.py:70-133` with the per-row dL_dpsi2[n] = sum_g W[n, g] dL_dpsi2[g] (each G x M x M matrix symmetrised inside)."""
+    require_device(device)
+    args = _group_args(variance, lengthscale, ARD, Z, mu, S, W)
+    M, N, D, G = args[4], args[7], args[8], args[10]
+    d2 = f64(dL_dpsi2)
+    assert d2.shape == (G, M, M), "dL_dpsi2 must be G x M x M"
+    dvar, dl, ms = np.zeros(1), np.zeros(D if ARD else 1), ctypes.c_double(0.0)
+    dZ, dmu, dS = np.zeros((M, D)), np.zeros((N, D)), np.zeros((N, D))
+    if loop or want_ms:                                              # the diagnostic entry
+        check(lib().mi355gp_dbg_rbf_psi_grad_groups(device, *(args + (d2, int(bool(loop)), dvar, dl, dZ, dmu, dS, ctypes.byref(ms)))),
+              "mi355gp_dbg_rbf_psi_grad_groups")
+    else:
+        check(lib().mi355gp_rbf_psi_grad_groups(device, *(args + (d2, dvar, dl, dZ, dmu, dS))), "mi355gp_rbf_psi_grad_groups")
+    r = (dvar[0], dl, dZ, dmu, dS)
+    return r + (ms.value,) if want_ms else r
 
 
 def _ss_args(variance, lengthscale, ARD, Z, mu, S, gamma, weights):

@@ -1,5 +1,5 @@
 // psi.h -- launchers of the psi-statistics kernels (psi.hip) shared by the stateless entry points and the uncertain-input
-// fit of the sparse context (sparse.hip).  Host code but for psi_tile; see psi.hip for the formulas and the buffer layouts.
+// fit of the sparse context (sparse.hip).  Host code but for psi_tile and the two reductions that end a gradient workgroup; see psi.hip for the formulas and the buffer layouts.
 #pragma once
 #include "internal.h"
 
@@ -22,6 +22,54 @@ __device__ __forceinline__ void psi_tile(long tl, int* ti, int* tj) {
     while ((i + 1) * (i + 2) / 2 <= tl) ++i;
     *ti = (int)i;
     *tj = (int)(tl - i * (i + 1) / 2);
+}
+
+// ---- the two reductions that end a workgroup of a gradient kernel (device; psi.hip and psi_missing.hip) -------------------
+// Ppart[mtile][row][1 + 2 Qp]: P0, P1[q], P2[q] summed over the tile's 16 inducing points (lane shuffles, fixed tree)
+template <int QG>
+__device__ __forceinline__ void psi_grad_emit(int t, int gz, int Qp, long n, bool nvalid, double a0, double* g1, double* g2,
+                                              double* __restrict__ prow) {
+    // sum over the 16 lanes that share a row; lane ml == 0 stores
+#pragma unroll
+    for (int s = 1; s < 16; s <<= 1) {
+        a0 += __shfl_xor(a0, s);
+#pragma unroll
+        for (int q = 0; q < QG; ++q) {
+            g1[q] += __shfl_xor(g1[q], s);
+            g2[q] += __shfl_xor(g2[q], s);
+        }
+    }
+    if ((t & 15) == 0 && nvalid) {
+        if (gz == 0) prow[0] = a0;
+#pragma unroll
+        for (int q = 0; q < QG; ++q) {
+            prow[1 + gz * PSI_KDC + q] = g1[q];
+            prow[1 + Qp + gz * PSI_KDC + q] = g2[q];
+        }
+    }
+}
+
+// sum zacc over the 16 rows of the workgroup (4 per wave by shuffles, 4 waves through LDS in wave order) and store
+template <int QG>
+__device__ __forceinline__ void psi_grad_emit_z(int t, int gz, int Qp, long mcol, long mpad, double* zacc, double* zred,
+                                                double* __restrict__ zblock) {
+#pragma unroll
+    for (int q = 0; q < QG; ++q) {
+        zacc[q] += __shfl_xor(zacc[q], 16);
+        zacc[q] += __shfl_xor(zacc[q], 32);
+    }
+    const int lane = t & 63, wv = t >> 6;
+    if (lane < 16)
+#pragma unroll
+        for (int q = 0; q < QG; ++q) zred[(wv * 16 + lane) * QG + q] = zacc[q];
+    __syncthreads();
+    if (t < 16 && mcol < mpad)
+#pragma unroll
+        for (int q = 0; q < QG; ++q) {
+            const double s = (zred[(0 * 16 + t) * QG + q] + zred[(1 * 16 + t) * QG + q]) +
+                             (zred[(2 * 16 + t) * QG + q] + zred[(3 * 16 + t) * QG + q]);
+            zblock[mcol * Qp + gz * PSI_KDC + q] = s;
+        }
 }
 
 // dL_dpsi1[n][m] = beta sum_d R[n][d] v[m][d] formed on the fly (the fit's rank-Dy product, var_dtc.py:219)

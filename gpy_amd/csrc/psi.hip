@@ -276,51 +276,7 @@ __global__ void k_psi_predvar(const double* __restrict__ C, const double* __rest
 //   Zpart[rowblock][m][Qp]:      sum over the block's rows (and all o) of c L d
 // LDS (dynamic): zm 16 x (Qp + 1) | rows 16 x Qp double2 | (psi2 only) zo PSI_OC x Qp, dLs PSI_OC x 16 | zred 4 x 16 x QG
 
-template <int QG>
-__device__ __forceinline__ void psi_grad_emit(int t, int gz, int Qp, long n, bool nvalid, double a0, double* g1, double* g2,
-                                              double* __restrict__ prow) {
-    // sum over the 16 lanes that share a row; lane ml == 0 stores
-#pragma unroll
-    for (int s = 1; s < 16; s <<= 1) {
-        a0 += __shfl_xor(a0, s);
-#pragma unroll
-        for (int q = 0; q < QG; ++q) {
-            g1[q] += __shfl_xor(g1[q], s);
-            g2[q] += __shfl_xor(g2[q], s);
-        }
-    }
-    if ((t & 15) == 0 && nvalid) {
-        if (gz == 0) prow[0] = a0;
-#pragma unroll
-        for (int q = 0; q < QG; ++q) {
-            prow[1 + gz * PSI_KDC + q] = g1[q];
-            prow[1 + Qp + gz * PSI_KDC + q] = g2[q];
-        }
-    }
-}
-
-// sum zacc over the 16 rows of the workgroup (4 per wave by shuffles, 4 waves through LDS in wave order) and store
-template <int QG>
-__device__ __forceinline__ void psi_grad_emit_z(int t, int gz, int Qp, long mcol, long mpad, double* zacc, double* zred,
-                                                double* __restrict__ zblock) {
-#pragma unroll
-    for (int q = 0; q < QG; ++q) {
-        zacc[q] += __shfl_xor(zacc[q], 16);
-        zacc[q] += __shfl_xor(zacc[q], 32);
-    }
-    const int lane = t & 63, wv = t >> 6;
-    if (lane < 16)
-#pragma unroll
-        for (int q = 0; q < QG; ++q) zred[(wv * 16 + lane) * QG + q] = zacc[q];
-    __syncthreads();
-    if (t < 16 && mcol < mpad)
-#pragma unroll
-        for (int q = 0; q < QG; ++q) {
-            const double s = (zred[(0 * 16 + t) * QG + q] + zred[(1 * 16 + t) * QG + q]) +
-                             (zred[(2 * 16 + t) * QG + q] + zred[(3 * 16 + t) * QG + q]);
-            zblock[mcol * Qp + gz * PSI_KDC + q] = s;
-        }
-}
+// (psi_grad_emit / psi_grad_emit_z, the two reductions that end a gradient workgroup, are in psi.h: psi_missing.hip shares them)
 
 // psi1: L = G[n][m] var exp(lg1 - 1/2 sum c1 d^2), d = mu - z_m
 // (RK = PsiRankAdd: the rank product plus add[m] per column; RK = PsiRank compiles to the code it always was)

@@ -12,6 +12,7 @@
 // Larger N streams through bounded chunk buffers (<= 262144 rows: 2 x 4.3 GB at M = 2048); up to that size the Kfu
 // chunk of pass 1 is still resident in pass 2 and is not rebuilt.
 #include <functional>
+#include <memory>
 #include <cmath>
 #include <cstring>
 #include <vector>
@@ -23,10 +24,12 @@
 #include "../../include/mi355gp_debug_sparse_coreg.h"
 #include "../../include/mi355gp_psi_lin.h"
 #include "../../include/mi355gp_psi_ss.h"
+#include "../../include/mi355gp_sparse_missing.h"
 #include "internal.h"
 #include "parts.h"
 #include "psi.h"
 #include "psi_ss.h"
+#include "psi_missing.h"
 #include "sparse_ctx.h"
 
 #define SPLITK_MAX 16
@@ -559,6 +562,7 @@ int mi355gp_sparse_destroy(mi355gp_sparse* s) {
     (void)hipSetDevice(s->device);
     (void)hipStreamSynchronize(s->st);
     free_m(s);
+    missing_release(s);
     double** ptrs[] = {&s->dX, &s->dY, &s->dV, &s->dBeta, &s->dRowS, &s->dRowT, &s->dRowR, &s->dSvar, &s->dGam};
     for (auto p : ptrs)
         if (*p) (void)hipFree(*p);
@@ -583,6 +587,7 @@ int mi355gp_sparse_set_data(mi355gp_sparse* s, const double* X, int64_t N, int D
     EngineShared gate(s->device);
     HIP_CHECK(hipStreamSynchronize(s->st));
     free_m(s);
+    missing_release(s);                                         // (the output groups of mi355gp_sparse_set_output_groups)
     double** ptrs[] = {&s->dX, &s->dY, &s->dV, &s->dBeta, &s->dRowS, &s->dRowT, &s->dRowR, &s->dSvar, &s->dGam};
     for (auto p : ptrs) {
         if (*p) (void)hipFree(*p);
@@ -1637,7 +1642,7 @@ static int psi_work_setup(mi355gp_sparse* s, const SPart& rbf, const double* Z, 
 // ld mp) -> psi1^T V, psi2 += the chunk's sum (fixed order); records ev[1]
 // With Bias parts (w.b > 0): psi1 = psi1_rbf + b, so psi1^T V gains b colsum(V) and psi2 gains b (c 1^T + 1 c^T) + N b^2 with
 // c = colsum(psi1_rbf), summed per chunk in chunk order; the Kfu buffer keeps the RBF part's psi1 alone
-static int uncertain_pass1(mi355gp_sparse* s, PsiWork& w, double extra_jitter) {
+static int uncertain_pass1(mi355gp_sparse* s, PsiWork& w, double extra_jitter, bool want_psi2 = true) {
     hipStream_t st = s->st;
     const long n = s->n, m = s->m, mp = s->mp;
     const int D = s->D, Dy = s->Dy;
@@ -1660,6 +1665,7 @@ static int uncertain_pass1(mi355gp_sparse* s, PsiWork& w, double extra_jitter) {
             const int nso = launch_colreduce_multi(st, s->Kfu, mp, rc, mp, nullptr, 0, 0, 0, 1, s->colPart);
             launch_sum_splits(st, s->colPart, mp, nso, nch > 0, w.csum);
         }
+        if (!want_psi2) continue;                                                     // (missing data: psi2 per group, by the caller)
         const int ns = w.ss ? launch_pss_psi2(st, w.rd2, nullptr, w.dZp, w.dEp, w.dA, rc, m, w.Qp, w.var * w.var, w.ld2, s->psi2part)
                             : launch_psi2(st, w.rd2, w.lg2, nullptr, w.dZp, w.dA, rc, m, w.Qp, w.var * w.var, w.ld2, s->psi2part);
         launch_psi2_combine(st, s->psi2part, w.ld2, m, ns, nch > 0, s->psi2, mp);
@@ -1979,6 +1985,8 @@ int mi355gp_vardtc_inference_uncertain(mi355gp_sparse* s, int nparts, const mi35
     ARG_CHECK(s->dSvar, "mi355gp_vardtc_inference_uncertain: no input variances; call mi355gp_sparse_set_input_variance after set_data");
     ARG_CHECK(!s->dGam, "mi355gp_vardtc_inference_uncertain: the context holds slab probabilities (mi355gp_sparse_set_binary_prob), which "
                         "this entry would drop; call mi355gp_vardtc_inference_ss, or clear them with a NULL gamma");
+    ARG_CHECK(!s->missing, "mi355gp_vardtc_inference_uncertain: the context holds output groups (mi355gp_sparse_set_output_groups), whose "
+                           "mask this entry would ignore; call mi355gp_vardtc_inference_missing, or clear them with G = 0");
     if (noise_len != 1)
         PART_FAIL("mi355gp_vardtc_inference_uncertain: per-point noise (%lld variances) is not supported with uncertain inputs "
                   "(var_dtc.py:243); pass one noise variance", (long long)noise_len);
@@ -2010,6 +2018,8 @@ int mi355gp_vardtc_inference_ss(mi355gp_sparse* s, int nparts, const mi355gp_par
     ARG_CHECK(!sharded(s), "mi355gp_vardtc_inference_ss: a row-sharded context is not supported with spike-and-slab inputs");
     ARG_CHECK(s->dSvar && s->dGam, "mi355gp_vardtc_inference_ss: no slab probabilities; call mi355gp_sparse_set_input_variance and "
                                    "mi355gp_sparse_set_binary_prob (or mi355gp_sparse_set_inputs_ss) after set_data");
+    ARG_CHECK(!s->missing, "mi355gp_vardtc_inference_ss: the context holds output groups (mi355gp_sparse_set_output_groups), whose mask "
+                           "this entry would ignore; clear them with G = 0");
     if (noise_len != 1)
         PART_FAIL("%s: per-point noise (%lld variances) is not supported with spike-and-slab inputs; pass one noise variance", where,
                   (long long)noise_len);
@@ -2021,6 +2031,343 @@ int mi355gp_vardtc_inference_ss(mi355gp_sparse* s, int nparts, const mi355gp_par
     s->beta_scalar = beta;
     return vardtc_uncertain_rbf(s, irbf, true, Z, beta, extra_jitter, out_scalars, dtheta_out, dZ_out, wv_out, dmu_out, dS_out, dgamma_out,
                                 stage_ms);
+}
+
+// ---- VarDTC with uncertain inputs and MISSING entries of Y (include/mi355gp_sparse_missing.h) ----------------------------------
+// The reference's loop (GPy/models/sparse_gp_minibatch.py:228-286): output columns with the same observed rows form a group g
+// (row weights w_g, c_g columns, N_g rows); every group is a VarDTC problem of its own on the shared Kmm,
+//   psi2_g = sum_n w_ng psi2n,  psi1^T V restricted to the group's columns (V = beta Y with Y = 0 where unobserved),
+// and the gradients add up: dL_dKmm = sum_g, dL_dpsi1 = beta Y v^T over ALL Woodbury columns (the zeros of Y make it the right
+// chain rule for every pattern at once), dL_dpsi2[n] = sum_g w_ng E_g with E_g = beta sym(Q2_g), dL_dpsi0[n] = -beta/2 times the
+// number of outputs observed at n.  psi2_g and the psi2 row pass go through the group-batched kernels of psi_missing.hip, the
+// M x M phase (sparse_mm_block) runs once per group in group order on the context's own buffers.
+struct MissingState {
+    int G = 0;
+    long n = 0, mp = 0;
+    std::vector<int> gof;                    // Dy: group of output d
+    std::vector<std::vector<int>> cols;      // per group: its output columns, ascending
+    std::vector<long> Ng;                    // per group: observed rows
+    std::vector<double> yy, gscal;           // per group: sum y^2 over its observed entries; MI355GP_NUM_OUT scalars of the last call
+    double obs_total = 0.0;                  // sum_g c_g N_g: observed entries of Y
+    std::vector<long> coff;                  // per group: where its columns start in dCols
+    DevBuf dWt, dCols;                       // the weights, group-major (G x n); the groups' column lists, concatenated (Dy ints)
+    // per M (grown on demand, kept between evaluations so that an optimiser step allocates nothing): G x {psi2_g, E_g, Winv_g},
+    // the wide Woodbury vector, a thin psi1^T V, the dL_dKmm and z_m - z_o sums, the partial buffer of one group batch
+    GrowBuf psi2g, Eg, Winvg, vvAll, psi1Yg, dKacc, zzAcc, part;
+    bool have = false;                       // the per-group results describe the context's latest evaluation
+};
+
+void missing_release(mi355gp_sparse* s) {
+    delete s->missing;
+    s->missing = nullptr;
+}
+
+// out = scale (A + A^T) / 2 over the leading m x m, 0 in the padding (k_sym_scaled)
+static void missing_sym(hipStream_t st, const double* A, long mp, long m, double scale, double* out) {
+    hipLaunchKernelGGL(k_sym_scaled, grid2d(mp, mp), dim3(256), 0, st, A, mp, m, scale, out);
+}
+// dst[j][cols[k]] = src[j][k] (scatter: src mp x c, dst mp x Dy) or src2[j][k] = dst[j][cols[k]] (gather), j < rows
+__global__ void k_missing_cols(double* __restrict__ wide, int Dy, double* __restrict__ thin, int c, const int* __restrict__ cols,
+                               long rows, int gather) {
+    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= rows * c) return;
+    const long j = i / c;
+    const int k = (int)(i - j * c);
+    if (gather) thin[i] = wide[j * Dy + cols[k]];
+    else wide[j * Dy + cols[k]] = thin[i];
+}
+
+// restores what the per-group M x M phase borrows from the context, whatever way the call ends
+struct MissingBorrow {
+    mi355gp_sparse* s;
+    int Dy;
+    long n_global;
+    double trYYT;
+    double *psi2, *psi1Y;
+    explicit MissingBorrow(mi355gp_sparse* s_) : s(s_), Dy(s_->Dy), n_global(s_->n_global), trYYT(s_->trYYT), psi2(s_->psi2), psi1Y(s_->psi1Y) {}
+    ~MissingBorrow() { s->Dy = Dy, s->n_global = n_global, s->trYYT = trYYT, s->psi2 = psi2, s->psi1Y = psi1Y; }
+};
+
+int mi355gp_sparse_set_output_groups(mi355gp_sparse* s, int G, const int* group_of_output, const double* W) {
+    const char* where = "mi355gp_sparse_set_output_groups";
+    ARG_CHECK(s && s->n > 0, "mi355gp_sparse_set_output_groups: set_data first");
+    HIP_CHECK(hipSetDevice(s->device));
+    if (G == 0) {
+        EngineShared gate(s->device);
+        HIP_CHECK(hipStreamSynchronize(s->st));
+        missing_release(s);
+        s->have_result = s->winv_ok = false;
+        return 0;
+    }
+    ARG_CHECK(G > 0 && group_of_output && W, "mi355gp_sparse_set_output_groups: bad arguments");
+    ARG_CHECK(!sharded(s), "mi355gp_sparse_set_output_groups: a row-sharded context is not supported with missing data");
+    ARG_CHECK(s->dSvar, "mi355gp_sparse_set_output_groups: no input variances (missing data is handled on the uncertain-input path); call "
+                        "mi355gp_sparse_set_input_variance after set_data");
+    ARG_CHECK(!s->dGam, "mi355gp_sparse_set_output_groups: the context holds slab probabilities; spike-and-slab inputs are not supported with missing data");
+    ARG_CHECK(!s->take_psi_lin && !s->take_linear && !s->take_coreg,
+              "mi355gp_sparse_set_output_groups: a context asked for psi_lin_bias, linear or coregionalize is not supported with missing data");
+    const long n = s->n;
+    const int Dy = s->Dy;
+    if (G > Dy) PART_FAIL("%s: %d groups for %d outputs", where, G, Dy);
+    MissingState* ms = new MissingState;
+    std::unique_ptr<MissingState> hold(ms);
+    ms->G = G, ms->n = n;
+    ms->gof.assign(group_of_output, group_of_output + Dy);
+    ms->cols.resize((size_t)G);
+    for (int d = 0; d < Dy; ++d) {
+        if (ms->gof[(size_t)d] < 0 || ms->gof[(size_t)d] >= G) PART_FAIL("%s: output %d is in group %d of %d", where, d, ms->gof[(size_t)d], G);
+        ms->cols[(size_t)ms->gof[(size_t)d]].push_back(d);
+    }
+    for (int g = 0; g < G; ++g)
+        if (ms->cols[(size_t)g].empty()) PART_FAIL("%s: group %d has no output", where, g);
+    std::vector<double> wt((size_t)G * n), hy((size_t)n * Dy);
+    ms->Ng.assign((size_t)G, 0);
+    ms->yy.assign((size_t)G, 0.0);
+    for (long i = 0; i < n; ++i)
+        for (int g = 0; g < G; ++g) {
+            const double w = W[i * G + g];
+            if (w != 0.0 && w != 1.0) PART_FAIL("%s: W[%ld][%d] = %g; the row weights are 0 or 1", where, i, g, w);
+            wt[(size_t)g * n + i] = w;
+            ms->Ng[(size_t)g] += (w == 1.0);
+        }
+    for (int g = 0; g < G; ++g)
+        if (ms->Ng[(size_t)g] == 0) PART_FAIL("%s: group %d (first output %d) has no observed row", where, g, ms->cols[(size_t)g][0]);
+    EngineShared gate(s->device);
+    HIP_CHECK(hipStreamSynchronize(s->st));
+    HIP_CHECK(hipMemcpy(hy.data(), s->dY, sizeof(double) * n * Dy, hipMemcpyDeviceToHost));
+    for (long i = 0; i < n; ++i)
+        for (int d = 0; d < Dy; ++d) {
+            const double y = hy[(size_t)(i * Dy + d)];
+            const int g = ms->gof[(size_t)d];
+            if (!std::isfinite(y)) PART_FAIL("%s: Y[%ld][%d] is not finite; store 0 where an entry is unobserved", where, i, d);
+            if (wt[(size_t)g * n + i] == 0.0 && y != 0.0)
+                PART_FAIL("%s: Y[%ld][%d] = %g is unobserved by its group %d; store 0 there", where, i, d, y, g);
+            ms->yy[(size_t)g] += y * y;
+        }
+    ms->obs_total = 0.0;
+    for (int g = 0; g < G; ++g) ms->obs_total += (double)ms->Ng[(size_t)g] * (double)ms->cols[(size_t)g].size();
+    HIP_CHECK(ms->dWt.alloc(wt.size()));
+    HIP_CHECK(hipMemcpy(ms->dWt, wt.data(), sizeof(double) * wt.size(), hipMemcpyHostToDevice));
+    std::vector<int> call;
+    for (int g = 0; g < G; ++g) {
+        ms->coff.push_back((long)call.size());
+        call.insert(call.end(), ms->cols[(size_t)g].begin(), ms->cols[(size_t)g].end());
+    }
+    HIP_CHECK(ms->dCols.alloc((size_t)(Dy + 1) / 2 + 1));                 // Dy ints
+    HIP_CHECK(hipMemcpy(ms->dCols, call.data(), sizeof(int) * call.size(), hipMemcpyHostToDevice));
+    missing_release(s);
+    s->missing = hold.release();
+    s->have_result = s->winv_ok = false;
+    return 0;
+}
+
+// the M x M buffers of the groups for the context's current mp: G x {psi2_g, E_g, Winv_g}, the wide Woodbury vector, a thin
+// psi1^T V, the dL_dKmm sum
+static int missing_alloc_m(mi355gp_sparse* s) {
+    MissingState* ms = s->missing;
+    const size_t mm = (size_t)s->mp * s->mp;
+    const long chunk = s->n < PSI_CHUNK ? s->n : PSI_CHUNK, ld2 = round_up(s->m, PSI_T2);
+    HIP_CHECK(ms->psi2g.need(mm * ms->G));
+    HIP_CHECK(ms->Eg.need(mm * ms->G));
+    HIP_CHECK(ms->Winvg.need(mm * ms->G));
+    HIP_CHECK(ms->vvAll.need((size_t)s->mp * s->Dy));
+    HIP_CHECK(ms->psi1Yg.need((size_t)s->mp * s->Dy));
+    HIP_CHECK(ms->dKacc.need(mm));
+    HIP_CHECK(ms->zzAcc.need((size_t)s->m * 2 * psi_qp(s->D)));
+    HIP_CHECK(ms->part.need((size_t)PSI_GB * psi2_nsplit(chunk, s->m) * ld2 * ld2));
+    ms->mp = s->mp;
+    return 0;
+}
+
+int mi355gp_vardtc_inference_missing(mi355gp_sparse* s, int nparts, const mi355gp_part* parts, const double* Z, int64_t M,
+                                     const double* noise, int64_t noise_len, double extra_jitter, double* out_scalars,
+                                     double* dtheta_out, double* dZ_out, double* wv_out, double* dmu_out, double* dS_out,
+                                     double* stage_ms) {
+    const char* where = "mi355gp_vardtc_inference_missing";
+    ARG_CHECK(s && s->n > 0, "mi355gp_vardtc_inference_missing: set_data first");
+    ARG_CHECK(parts && Z && M > 0 && out_scalars && noise && nparts >= 1, "mi355gp_vardtc_inference_missing: bad arguments");
+    ARG_CHECK(!sharded(s), "mi355gp_vardtc_inference_missing: a row-sharded context is not supported with missing data");
+    ARG_CHECK(s->missing, "mi355gp_vardtc_inference_missing: no output groups; call mi355gp_sparse_set_output_groups after set_data and "
+                          "mi355gp_sparse_set_input_variance");
+    ARG_CHECK(s->dSvar && !s->dGam, "mi355gp_vardtc_inference_missing: Gaussian input variances are required (and no slab probabilities)");
+    ARG_CHECK(!s->take_psi_lin && !s->take_linear && !s->take_coreg,
+              "mi355gp_vardtc_inference_missing: a context asked for psi_lin_bias, linear or coregionalize is not supported with missing data");
+    if (noise_len != 1)
+        PART_FAIL("%s: per-point noise (%lld variances) is not supported with missing data; pass one noise variance", where, (long long)noise_len);
+    int irbf = -1;
+    if (int rc = uncertain_check_parts(s, nparts, parts, M, &irbf, where, true)) return rc;
+    EngineShared gate(s->device);
+    if (int rc = sparse_open(s, nparts, parts, M)) return rc;
+    MissingState* ms = s->missing;
+    ms->have = false;
+    if (int rc = missing_alloc_m(s)) return rc;
+    const double beta = 1.0 / fmax(noise[0], 1e-8);
+    s->beta_scalar = beta;
+    hipStream_t st = s->st;
+    const long n = s->n, m = s->m, mp = s->mp;
+    const size_t mm = (size_t)mp * mp;
+    const int D = s->D, Dy = s->Dy, G = ms->G;
+    s->mfma_prof.on = false;
+    const SPart& rbf = s->parts[(size_t)irbf];
+    PsiWork w;
+    if (int rc = psi_work_setup(s, rbf, Z, &w)) return rc;
+    const int Qp = w.Qp;
+    double* part = ms->part;
+    if (int rc = sparse_start(s, Z, &beta, 1)) return rc;
+    // ---- pass 1: Kmm, Lm, Lm^-1 and psi1^T V as for complete data; psi2_g for every group through the batched kernel ----------
+    if (int rc = uncertain_pass1(s, w, extra_jitter, /*want_psi2=*/false)) return rc;
+    HIP_CHECK(hipMemsetAsync(ms->psi2g, 0, sizeof(double) * mm * G, st));
+    int nch = 0;
+    for (long r0 = 0; r0 < n; r0 += PSI_CHUNK, ++nch) {
+        const long rc = (n - r0 < PSI_CHUNK) ? (n - r0) : PSI_CHUNK;
+        launch_psi_rows(st, s->dX + r0 * D, s->dSvar + r0 * D, w.dA, rc, D, Qp, w.rd1, w.rd2, w.lg1, w.lg2);
+        for (int g0 = 0; g0 < G; g0 += PSI_GB) {
+            const int gb = (G - g0 < PSI_GB) ? (G - g0) : PSI_GB;
+            const int ns = launch_psi2_multi(st, w.rd2, w.lg2, ms->dWt + (long)g0 * n + r0, n, gb, w.dZp, w.dA, rc, m, Qp, w.var * w.var,
+                                             w.ld2, part);
+            for (int g = 0; g < gb; ++g)
+                launch_psi2_combine(st, part + (size_t)g * ns * w.ld2 * w.ld2, w.ld2, m, ns, nch > 0, ms->psi2g + (size_t)(g0 + g) * mm, mp);
+        }
+    }
+    HIP_CHECK(hipEventRecord(s->ev[1], st));
+    // ---- the M x M phase, once per group in group order ---------------------------------------------------------------------
+    std::vector<double> scal((size_t)G * 4);
+    int info_b = 0;                                                       // the first group's B that is not positive definite
+    {
+        MissingBorrow borrow(s);
+        for (int g = 0; g < G; ++g) {
+            const std::vector<int>& cg = ms->cols[(size_t)g];
+            const int c = (int)cg.size();
+            const int* dcols = (const int*)ms->dCols.p + ms->coff[(size_t)g];
+            hipLaunchKernelGGL(k_missing_cols, dim3((unsigned)((mp * c + 255) / 256)), dim3(256), 0, st, borrow.psi1Y, Dy, (double*)ms->psi1Yg, c,
+                               dcols, mp, 1);
+            s->Dy = c;
+            s->psi1Y = ms->psi1Yg;
+            s->psi2 = ms->psi2g + (size_t)g * mm;
+            if (int rc = sparse_mm_block(s, false, beta, 0)) return rc;
+            hipLaunchKernelGGL(k_missing_cols, dim3((unsigned)((mp * c + 255) / 256)), dim3(256), 0, st, (double*)ms->vvAll, Dy, s->vvec, c,
+                               dcols, mp, 0);
+            missing_sym(st, s->Q2, mp, m, beta, ms->Eg + (size_t)g * mm);
+            launch_mm_axpby(st, s->dLdKmm, 1.0, g ? (const double*)ms->dKacc : nullptr, 1.0, 0.0, mp, ms->dKacc);
+            // woodbury_inv_g = Lm^-T (I - B_g^-1) Lm^-1 (ensure_winv's steps, into the group's own matrix)
+            launch_mm_sym(st, s->Bi, mp, s->E);
+            launch_mm_axpby(st, s->E, -1.0, nullptr, 0.0, 1.0, mp, s->E);
+            launch_gemm(st, 1, 1, mp, mp, mp, s->Xm, mp, s->E, mp, s->T1, mp, 1.0, 0.0);
+            launch_gemm(st, 0, 1, mp, mp, mp, s->T1, mp, s->Xm, mp, ms->Winvg + (size_t)g * mm, mp, 1.0, 0.0);
+            HIP_CHECK(hipMemcpyAsync(scal.data() + (size_t)g * 4, s->scal, sizeof(double) * 4, hipMemcpyDeviceToHost, st));
+            HIP_CHECK(hipStreamSynchronize(st));                          // (h_info[1] is written again by the next group's factorisation)
+            if (!info_b && s->h_info[1] > 0) info_b = s->h_info[1];
+        }
+    }
+    s->h_info[1] = info_b;
+    HIP_CHECK(hipMemcpyAsync(s->vvec, ms->vvAll, sizeof(double) * mp * Dy, hipMemcpyDeviceToDevice, st));
+    HIP_CHECK(hipMemcpyAsync(s->dLdKmm, ms->dKacc, sizeof(double) * mm, hipMemcpyDeviceToDevice, st));
+    HIP_CHECK(hipEventRecord(s->ev[2], st));
+    // ---- pass 2: psi1 with dL_dpsi1 = beta Y v^T over all Woodbury columns; psi2 with the per-row sum_g w_ng E_g ---------------
+    for (int g = 0; g < G; ++g) {
+        launch_psi2_zz(st, ms->Eg + (size_t)g * mm, ms->psi2g + (size_t)g * mm, mp, w.dZp, m, Qp, w.zz);
+        launch_sum_splits(st, w.zz, m * 2 * Qp, 1, g > 0, ms->zzAcc);
+    }
+    std::vector<double> csum((size_t)(1 + Qp));
+    nch = 0;
+    for (long r0 = 0; r0 < n; r0 += PSI_CHUNK, ++nch) {
+        const long rc = (n - r0 < PSI_CHUNK) ? (n - r0) : PSI_CHUNK;
+        const int nb = (int)((rc + PSI_GROWS - 1) / PSI_GROWS);
+        const PsiRank rk{s->dY + r0 * Dy, s->vvec, Dy, beta};
+        launch_psi_rows(st, s->dX + r0 * D, s->dSvar + r0 * D, w.dA, rc, D, Qp, w.rd1, w.rd2, w.lg1, w.lg2);
+        launch_psi1_grad(st, w.rd1, w.lg1, w.dZp, nullptr, 0, rk, rc, m, w.mpad, Qp, w.var, w.Ppart, w.Zpart, nullptr);
+        launch_sum_splits(st, w.Ppart, rc * w.RL, (int)w.mt, 0, w.P1s);
+        launch_sum_splits(st, w.Zpart, w.mpad * w.ZL, nb, nch > 0, w.Zs1);
+        for (int g0 = 0; g0 < G; g0 += PSI_GB) {
+            const int gb = (G - g0 < PSI_GB) ? (G - g0) : PSI_GB;
+            launch_psi2_grad_multi(st, w.rd2, w.lg2, ms->dWt + (long)g0 * n + r0, n, gb, w.dZp, w.dA, ms->Eg + (size_t)g0 * mm, (long)mm, mp,
+                                   rc, m, w.mpad, Qp, w.var * w.var, w.Ppart, w.Zpart);
+            launch_sum_splits(st, w.Ppart, rc * w.RL, (int)w.mt, g0 > 0, w.P2s);
+            launch_sum_splits(st, w.Zpart, w.mpad * w.ZL, nb, nch > 0 || g0 > 0, w.Zs2);
+        }
+        launch_psi_rowfinish(st, w.P1s, w.P2s, s->dSvar + r0 * D, w.dA, rc, D, Qp, w.dMuO + r0 * D, w.dSO + r0 * D, w.rowrec);
+        launch_reduce_partials(st, w.rowrec, (int)rc, 1 + Qp, w.rec);
+        HIP_CHECK(hipMemcpyAsync(csum.data(), w.rec, sizeof(double) * (1 + Qp), hipMemcpyDeviceToHost, st));
+        HIP_CHECK(hipStreamSynchronize(st));
+        for (int k = 0; k <= Qp; ++k) w.sums[(size_t)k] += csum[(size_t)k];           // chunks in row order
+    }
+    sparse_kmm_gradients(s);
+    HIP_CHECK(hipEventRecord(s->ev[3], st));
+    // ---- small results to the host -----------------------------------------------------------------------------------------
+    KernGrads kg;
+    std::vector<double> zs1((size_t)w.mpad * w.ZL), zs2((size_t)w.mpad * w.ZL), zzh((size_t)m * 2 * Qp);
+    if (int rc = sparse_fetch_gradients(s, false, &kg)) return rc;
+    HIP_CHECK(hipMemcpyAsync(zs1.data(), w.Zs1, sizeof(double) * zs1.size(), hipMemcpyDeviceToHost, st));
+    HIP_CHECK(hipMemcpyAsync(zs2.data(), w.Zs2, sizeof(double) * zs2.size(), hipMemcpyDeviceToHost, st));
+    HIP_CHECK(hipMemcpyAsync(zzh.data(), ms->zzAcc, sizeof(double) * zzh.size(), hipMemcpyDeviceToHost, st));
+    if (wv_out) HIP_CHECK(hipMemcpyAsync(wv_out, s->vvec, sizeof(double) * m * Dy, hipMemcpyDeviceToHost, st));
+    if (dmu_out) HIP_CHECK(hipMemcpyAsync(dmu_out, w.dMuO, sizeof(double) * n * D, hipMemcpyDeviceToHost, st));
+    if (dS_out) HIP_CHECK(hipMemcpyAsync(dS_out, w.dSO, sizeof(double) * n * D, hipMemcpyDeviceToHost, st));
+    if (int rc = sparse_finish(s, 3, stage_ms)) return rc;
+    // the scalars: the existing formulas per group with (N_g, c_g, sum y^2 over the group's observed entries), added in group order
+    ms->gscal.assign((size_t)G * MI355GP_NUM_OUT, 0.0);
+    for (int i = 0; i < MI355GP_NUM_OUT; ++i) out_scalars[i] = 0.0;
+    {
+        MissingBorrow borrow(s);
+        const double kd = expression_kdiag(s->parts, s->terms);
+        for (int g = 0; g < G; ++g) {
+            double* og = ms->gscal.data() + (size_t)g * MI355GP_NUM_OUT;
+            s->Dy = (int)ms->cols[(size_t)g].size();
+            s->n_global = ms->Ng[(size_t)g];
+            s->trYYT = ms->yy[(size_t)g];
+            vardtc_scalars(s, scal.data() + (size_t)g * 4, kd, beta, nullptr, og);
+            for (int i = 0; i < 5; ++i) out_scalars[i] += og[i];
+        }
+    }
+    out_scalars[5] = beta;
+    double* ab = kg.gmm.data() + (size_t)irbf * rec_doubles(s);
+    ab[0] += w.sums[0];
+    for (int q = 0; q < D; ++q) {
+        double zq = 0.0;
+        for (long j = 0; j < m; ++j) zq += zzh[(size_t)j * 2 * Qp + Qp + q];
+        const double lq = w.sums[(size_t)(1 + q)] + 0.5 * w.ha[(size_t)q] * zq;
+        ab[(size_t)(q / 32) * GP_STRIDE + 2 + (q % 32)] -= lq;
+        ab[1] -= lq;
+    }
+    // sum_n dL_dpsi0_n = -beta/2 times the observed entries of Y, dpsi0 / dvariance = 1
+    sparse_assemble_gradients(s, kg, -0.5 * beta * ms->obs_total, dtheta_out, dZ_out);
+    if (dZ_out)
+        for (long j = 0; j < m; ++j)
+            for (int q = 0; q < D; ++q)
+                dZ_out[j * D + q] += zs1[(size_t)j * Qp + q] + 2.0 * zs2[(size_t)j * Qp + q] - w.ha[(size_t)q] * zzh[(size_t)j * 2 * Qp + q];
+    // the context's current result: the last group's B^-1 is still in place; point woodbury_inv at group 0 (select to change)
+    HIP_CHECK(hipMemcpyAsync(s->Winv, ms->Winvg, sizeof(double) * mm, hipMemcpyDeviceToDevice, st));
+    HIP_CHECK(hipMemcpyAsync(s->psi2, ms->psi2g, sizeof(double) * mm, hipMemcpyDeviceToDevice, st));
+    HIP_CHECK(hipStreamSynchronize(st));
+    s->winv_ok = true;
+    s->have_result = true;
+    s->uncertain_result = true;
+    ms->have = true;
+    return 0;
+}
+
+// Makes group g's woodbury_inv (and psi2) the context's current ones: mi355gp_sparse_predict, mi355gp_sparse_predict_uncertain and
+// mi355gp_sparse_fetch then serve the outputs of that group (posterior.py:243-246, :268); the mean uses all Woodbury columns
+int mi355gp_sparse_select_output_group(mi355gp_sparse* s, int g) {
+    ARG_CHECK(s && s->missing && s->missing->have && s->have_result && s->missing->mp == s->mp,
+              "mi355gp_sparse_select_output_group: run mi355gp_vardtc_inference_missing first");
+    MissingState* ms = s->missing;
+    if (g < 0 || g >= ms->G) PART_FAIL("mi355gp_sparse_select_output_group: group %d of %d", g, ms->G);
+    HIP_CHECK(hipSetDevice(s->device));
+    EngineShared gate(s->device);
+    const size_t mm = (size_t)s->mp * s->mp;
+    HIP_CHECK(hipMemcpyAsync(s->Winv, ms->Winvg + (size_t)g * mm, sizeof(double) * mm, hipMemcpyDeviceToDevice, s->st));
+    HIP_CHECK(hipMemcpyAsync(s->psi2, ms->psi2g + (size_t)g * mm, sizeof(double) * mm, hipMemcpyDeviceToDevice, s->st));
+    HIP_CHECK(hipStreamSynchronize(s->st));
+    s->winv_ok = true;
+    return 0;
+}
+
+// The per-group copies of out_scalars of the last mi355gp_vardtc_inference_missing call: G x 8, rows in group order
+int mi355gp_sparse_fetch_group_scalars(mi355gp_sparse* s, double* out) {
+    ARG_CHECK(s && out && s->missing && s->missing->have, "mi355gp_sparse_fetch_group_scalars: run mi355gp_vardtc_inference_missing first");
+    memcpy(out, s->missing->gscal.data(), sizeof(double) * s->missing->gscal.size());
+    return 0;
 }
 
 // ---- results of the last VarDTC call ------------------------------------------------------------------------------------

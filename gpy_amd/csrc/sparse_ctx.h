@@ -11,6 +11,7 @@ struct LoopGroup;              // the loopback rendezvous of the row-sharded mod
 struct SvgpState;              // svgp.hip
 struct PepState;               // pep.hip
 struct EpdtcState;             // epdtc.hip
+struct MissingState;           // sparse.hip: the output groups of a fit with missing data
 
 struct SPart : DevicePart {
     DevBuf XtZ, XtC, HX, HZ, gradNM, gradMM;   // (HX / HZ of a Linear part: mp x D, no ones column)
@@ -55,6 +56,7 @@ struct mi355gp_sparse {
     int world = 1, rank = 0;
     long n_global = 0;
     double* dSvar = nullptr;      // N x D input variances (mi355gp_sparse_set_input_variance): X is then the mean of q(x_n)
+    MissingState* missing = nullptr;   // mi355gp_sparse_set_output_groups: the row masks of Y's columns (forgotten by set_data)
     double* dGam = nullptr;       // N x D slab probabilities (mi355gp_sparse_set_binary_prob): q(x_n) is then spike-and-slab
     bool uncertain_result = false; // the last result came from mi355gp_vardtc_inference_uncertain (no dL_dKnm then)
     double *dX = nullptr, *dY = nullptr, *dV = nullptr, *dBeta = nullptr, *dRowS = nullptr, *dRowT = nullptr, *dRowR = nullptr,
@@ -168,6 +170,7 @@ extern "C" {       // (defined among the entry points of sparse.hip)
 int potrf_checked(hipStream_t st, double* A, double* X, double* T, double* W, long mp, FactorWs* ws, int* info_host,
                   const std::function<void()>& rebuild);
 void sparse_kmm_gradients(mi355gp_sparse* s);
+void missing_release(mi355gp_sparse* s);   // frees the output groups of mi355gp_sparse_set_output_groups
 // the phases an inference family is built from, in the order of a call (each is described where it is defined)
 int sparse_open(mi355gp_sparse* s, int nparts, const mi355gp_part* parts, int64_t M, bool coreg = false);
 int sparse_start(mi355gp_sparse* s, const double* Z, const double* beta, long nbeta);

@@ -406,6 +406,9 @@ class GPCoregionalizedRegression(GP):
 
 def __getattr__(name):
     """the latent variable models of the reference that this backend does not have are refused by name"""
+    if name == "SparseGPMiniBatch":
+        raise NotImplementedError("GPy.models.SparseGPMiniBatch (missing data with certain inputs) is not implemented on the MI355X "
+                                  "path; BayesianGPLVMMiniBatch (missing data with a NormalPosterior X) is")
     if name in ("SSGPLVM", "MRD", "GPLVM", "SparseGPLVM"):
         raise NotImplementedError("GPy.models.%s is not implemented on the MI355X path; BayesianGPLVM is%s"
                                   % (name, " (the spike-and-slab model with one RBF and White parts lives at "

@@ -121,6 +121,76 @@ class SparsePosterior(SessionPosterior):
         return kern.K(X1, X2) - np.dot(kern.K(X1, X), np.dot(np.asarray(self.woodbury_inv), kern.K(X, X2)))
 
 
+class MissingDataPosterior(SessionPosterior):
+    """The posterior of a fit with missing data (reference `sparse_gp_minibatch.py:274-283`): `woodbury_vector` (M x Dy) and a
+    3-D `woodbury_inv` (M x M x Dy, `woodbury_inv[:, :, d]` = the matrix of output d's group), expanded from the G matrices on
+    the device when it is first read.  Prediction (`posterior.py:233-246`, `:268`) runs on the device, one contraction per
+    group, while the posterior is the context's latest result; afterwards on the host from the expanded array, if it was read
+    in time."""
+
+    def __init__(self, woodbury_vector, group_of_output, K, K_chol, device=None):
+        self.woodbury_vector, self.group_of_output, self.K, self.K_chol = woodbury_vector, np.asarray(group_of_output), K, K_chol
+        self._device, self._wi = device, None
+
+    @property
+    def woodbury_inv(self):
+        if self._wi is None:
+            if not self._live():
+                raise RuntimeError("MissingDataPosterior.woodbury_inv: the device context has moved on to a later evaluation; "
+                                   "read woodbury_inv (or predict) before the next one")
+            ctx, gof = self._device["ctx"], self.group_of_output
+            M = self.woodbury_vector.shape[0]
+            wi = np.empty((M, M, gof.size))
+            for g in range(int(gof.max()) + 1):
+                ctx.select_output_group(g)
+                wi[:, :, gof == g] = ctx.fetch(ctx.FETCH_WOODBURY_INV)[:, :, None]
+            self._wi = wi
+        return self._wi
+
+    def __getstate__(self):
+        """as `SparsePosterior`: no device handle travels; the lazy members are materialised (woodbury_inv while it still can be)"""
+        d = dict(self.__dict__)
+        if d["_wi"] is None and self._live():
+            d["_wi"] = self.woodbury_inv
+        d["_device"] = None
+        for k in ("K", "K_chol"):
+            d[k] = np.asarray(d[k])
+        return d
+
+    def _raw_predict(self, kern, Xnew, pred_var, full_cov=False):
+        if isinstance(Xnew, SpikeAndSlabPosterior):
+            raise NotImplementedError("prediction at spike-and-slab new points (a SpikeAndSlabPosterior Xnew) is not implemented; "
+                                      "pass their means, or a NormalPosterior")
+        uncertain = isinstance(Xnew, NormalPosterior)
+        if uncertain and full_cov:
+            raise NotImplementedError("Full covariance at uncertain new points is not implemented (the reference has none either)")
+        if self._live(kern) and not full_cov:
+            ctx = self._device["ctx"]
+            if uncertain:
+                return ctx.predict_missing(kern.part_specs(), kern._slice_X(Xnew.mean), kern._slice_X(Xnew.variance))
+            return ctx.predict_missing(kern.part_specs(), kern._slice_X(Xnew))
+        Wi, la = self.woodbury_inv, np.asarray(self.woodbury_vector)
+        if uncertain:                                                  # posterior.py:250-269 with the 3-D woodbury_inv, in row
+            M, n = la.shape[0], Xnew.shape[0]                          # blocks that keep the N* x M x M array bounded
+            step = max(1, (1 << 22) // (M * M))                        # at most 32 MB of psi2n at a time
+            mu, var = np.empty((n, la.shape[1])), np.empty((n, la.shape[1]))
+            for r0 in range(0, n, step):
+                q = Xnew[r0:r0 + step]
+                psi0, psi1, psi2n = kern.psi0(pred_var, q), kern.psi1(pred_var, q), kern.psi2n(pred_var, q)
+                mb = np.dot(psi1, la)
+                vb = np.einsum("nmo,md,od->nd", psi2n, la, la) - mb * mb + psi0[:, None] - np.einsum("nmo,mod->nd", psi2n, Wi)
+                mu[r0:r0 + step], var[r0:r0 + step] = mb, np.clip(vb, 1e-15, np.inf)
+            return mu, var
+        Kx = kern.K(pred_var, Xnew)
+        mu = np.dot(Kx.T, la)
+        if full_cov:                                                   # posterior.py:233-237
+            Kxx = kern.K(Xnew)
+            return mu, np.stack([Kxx - Kx.T.dot(Wi[:, :, i]).dot(Kx) for i in range(Wi.shape[2])], axis=2)
+        Kd = kern.Kdiag(Xnew)
+        var = np.stack([Kd - np.sum(np.dot(Wi[:, :, i].T, Kx) * Kx, 0) for i in range(Wi.shape[2])], axis=1)
+        return mu, np.clip(var, 1e-15, np.inf)
+
+
 def _host_predictive_gradients(kern, Xnew, pred_var, woodbury_vector, woodbury_inv):
     """`GP.predictive_gradients` (reference `core/gp.py:440-474`, woodbury_inv.ndim == 2) composed from `kern.gradients_X`
     (device reductions) and the M x M / N x N Woodbury inverse."""
@@ -236,9 +306,11 @@ class SparseSession(LatentFunctionInference):
 
 class VarDTC(SparseSession):
     const_jitter = 1e-8
-    _device_members = SparseSession._device_members + ("_S", "_G")
+    _device_members = SparseSession._device_members + ("_S", "_G", "_groups_of", "_groups_mask")
     _S = None                                                        # identity of the uploaded input variances
     _G = None                                                        # ... and of the slab probabilities (None: Gaussian inputs)
+    _groups_of = None                                                # the uploaded Y (its identity) the context's output groups belong to
+    _groups_mask = None                                              # ... and the (group_of_output, W) that were uploaded with it
 
     def __init__(self, device=0, maxtries=5, linear=False, psi_lin_bias=False, coregionalize=False):
         """`coregionalize=True`: the kernel may hold Coregionalize factors (`util.multioutput.ICM` / `LCM`) with certain inputs;
@@ -339,8 +411,73 @@ class VarDTC(SparseSession):
             grad_dict["fused"]["dgamma"] = r["dgamma"]
         return post, r["lml"] + (0.0 if Z_tilde is None else Z_tilde), grad_dict
 
+    def _inference_missing(self, kern, qX, Z, likelihood, Y, Y_metadata, mean_function, precision, Lm, dL_dKmm, psi0, psi1, psi2,
+                           Z_tilde):
+        """NaNs in Y define groups of output columns with the same observed rows (order: first output index, reference
+        `stochastics.py:57-79`); one device call evaluates the reference's loop over them (`sparse_gp_minibatch.py:228-286`):
+        `mi355gp_sparse_set_output_groups` + `mi355gp_vardtc_inference_missing`.  X is a `NormalPosterior`, the kernel one RBF
+        alone or summed with White parts, the noise one variance.  Everything else is refused by name before a context is
+        touched."""
+        if any(a is not None for a in (Lm, dL_dKmm, psi0, psi1, psi2)):
+            raise NotImplementedError("precomputed statistics are not accepted by the MI355X sparse path")
+        if isinstance(qX, SpikeAndSlabPosterior):
+            raise NotImplementedError("missing_data: spike-and-slab inputs are not implemented with missing data on the MI355X path")
+        if not isinstance(qX, NormalPosterior):
+            raise NotImplementedError("missing_data: certain inputs (the reference's SparseGPMiniBatch) are not implemented on the "
+                                      "MI355X path; missing data is handled for a NormalPosterior X (BayesianGPLVMMiniBatch)")
+        if self.psi_lin_bias or self.linear or self.coregionalize:
+            raise NotImplementedError("missing_data: an inference class made with psi_lin_bias, linear or coregionalize is not "
+                                      "implemented with missing data; make it as VarDTC()")
+        if mean_function is not None:
+            raise ValueError("Mean function not implemented with uncertain inputs or heteroscedasticity")
+        parts = kern.parts if isinstance(kern, Add) else [kern]
+        for p in parts:
+            if type(p) not in (RBF, White):
+                raise NotImplementedError("missing_data: the part %r (%s) is not implemented with missing data on the MI355X path; "
+                                          "one RBF kernel and White parts are" % (p.name, type(p).__name__))
+        if sum(isinstance(p, RBF) for p in parts) != 1:
+            raise NotImplementedError("missing_data: exactly one RBF part is covered, got %d" % sum(isinstance(p, RBF) for p in parts))
+        noise = noise_variances(likelihood, Y_metadata, precision)
+        if noise.size > 1:
+            raise NotImplementedError("heteroscedastic (per-point) noise is not implemented with missing data")
+        self._refuse_sharded("missing data is not supported by a row-sharded sparse context")
+        gof, W, Y0 = _lib.output_groups(Y)
+        empty = [int(np.argmax(gof == g)) for g in range(W.shape[1]) if not W[:, g].any()]
+        if empty:
+            raise ValueError("missing_data: output column %d has no observed entry" % empty[0])
+        mu, S, Zs = kern._slice_X(qX.mean), kern._slice_X(qX.variance), kern._slice_X(Z)
+        self._ensure_uncertain(mu, S, Y0)
+        # set_data forgets the groups, set_inputs keeps them; and the zero-filled Y alone does not tell a NaN from an observed 0.0:
+        # the mask is compared as well
+        if (self._groups_of is not self._Y or not np.array_equal(self._groups_mask[0], gof)
+                or not np.array_equal(self._groups_mask[1], W)):
+            self._ctx.set_output_groups(gof, W)
+            self._groups_of, self._groups_mask = self._Y, (gof, W)
+        specs = kern.part_specs()
+        r = self._run(kern, lambda extra: self._ctx.vardtc_missing(specs, Zs, noise, extra_jitter=extra,
+                                                                   want_stage_ms=self.collect_stage_ms), Z)
+        M = Zs.shape[0]
+        C = _lib.SparseContext
+        post = MissingDataPosterior(r["woodbury_vector"], gof, K=LazyMM(self, C.FETCH_KMM, M), K_chol=LazyMM(self, C.FETCH_LM, M),
+                                    device=self._device_dict(kern))
+        beta = float(1.0 / np.fmax(noise, self.const_jitter)[0])
+        counts = np.bincount(gof, minlength=W.shape[1]).astype(np.float64)           # outputs per group
+        grad_dict = {"dL_dKmm": LazyMM(self, C.FETCH_DLDKMM, M),
+                     "dL_dpsi0": -0.5 * beta * W.dot(counts),                         # -beta/2 times the outputs observed at n
+                     "dL_dpsi1": LazyPsi1(beta, Y0, r["woodbury_vector"]),
+                     "dL_dthetaL": likelihood.exact_inference_gradients(r["dnoise"], Y_metadata),
+                     "fused": {"dtheta": r["dtheta"], "dZ": r["dZ"], "dmu": r["dmu"], "dS": r["dS"],
+                               "group_scalars": r["group_scalars"], "group_of_output": gof, "W": W}}
+        return post, r["lml"] + (0.0 if Z_tilde is None else Z_tilde), grad_dict
+
     def inference(self, kern, X, Z, likelihood, Y, Y_metadata=None, mean_function=None, precision=None, Lm=None,
-                  dL_dKmm=None, psi0=None, psi1=None, psi2=None, Z_tilde=None):
+                  dL_dKmm=None, psi0=None, psi1=None, psi2=None, Z_tilde=None, missing_data=False):
+        if missing_data:
+            return self._inference_missing(kern, X, Z, likelihood, Y, Y_metadata, mean_function, precision, Lm, dL_dKmm, psi0, psi1,
+                                           psi2, Z_tilde)
+        if self._groups_of is not None:                                # the context last held a fit with missing data
+            self._ctx.set_output_groups(None, None)
+            self._groups_of = self._groups_mask = None
         uncertain = isinstance(X, (NormalPosterior, SpikeAndSlabPosterior))
         if not uncertain:
             sparse_path_kernel_check(kern, self.linear, self.coregionalize)
@@ -595,7 +732,8 @@ class BayesianGPLVM(SparseGP):
                                     ("batchsize", batchsize, 1)):
             if value is not default and value != default:
                 raise NotImplementedError("BayesianGPLVM: %s = %r is not implemented on the MI355X path (the minibatch / MPI "
-                                          "variant, missing data and normalizers are out of scope)" % (arg, value))
+                                          "variant, missing data and normalizers are out of scope%s)"
+                                          % (arg, value, "; BayesianGPLVMMiniBatch takes missing_data=True" if arg == "missing_data" else ""))
         Y = np.asarray(Y, dtype=np.float64)
         if X is None:
             from .util.initialization import initialize_latent
@@ -662,6 +800,64 @@ class BayesianGPLVM(SparseGP):
 
     def infer_newX(self, Y_new, optimize=True):
         raise NotImplementedError("BayesianGPLVM.infer_newX is not implemented on the MI355X path")
+
+
+class BayesianGPLVMMiniBatch(BayesianGPLVM):
+    """Bayesian GPLVM with missing data (reference `GPy/models/bayesian_gplvm_minibatch.py` on `sparse_gp_minibatch.py`): with
+    `missing_data=True` NaNs in Y mark unobserved entries, output columns with the same observed rows are evaluated as one group
+    and the bound is the sum of the groups' bounds minus the KL term (`kl_factr` = 1).  The whole loop is one device call
+    (`VarDTC.inference(..., missing_data=True)`); the flat parameter order is [X.mean, X.variance, Z, kernel, noise].  With
+    `missing_data=False` it is `BayesianGPLVM`'s evaluation.  The kernel is one `RBF` alone or summed with `White` parts.
+    `predict(Xnew)` at certain or `NormalPosterior` points returns N* x Dy means and per-output variances.  Refused by name:
+    `stochastic=True`, `batchsize != 1`, a normalizer, `X_variance=False` (the sparse GPLVM), non-Gaussian likelihoods, `infer_newX`.
+    With NaNs in Y the PCA initialisation has nothing to decompose: pass X."""
+    kl_factr = 1.0
+
+    def __init__(self, Y, input_dim, X=None, X_variance=None, init="PCA", num_inducing=10, Z=None, kernel=None,
+                 inference_method=None, likelihood=None, name="bayesian gplvm", normalizer=None, missing_data=False,
+                 stochastic=False, batchsize=1, device=0):
+        who = "BayesianGPLVMMiniBatch"
+        if stochastic:
+            raise NotImplementedError("%s: stochastic=True (minibatches over outputs) is not implemented on the MI355X path" % who)
+        if batchsize != 1:
+            raise NotImplementedError("%s: batchsize = %r is not implemented on the MI355X path (it belongs to stochastic=True)" % (who, batchsize))
+        if normalizer is not None and normalizer is not False:
+            raise NotImplementedError("%s: normalizer = %r is not implemented on the MI355X path" % (who, normalizer))
+        if X_variance is False:
+            raise NotImplementedError("%s: X_variance=False (the sparse GPLVM with certain latent points) is not implemented on the "
+                                      "MI355X path" % who)
+        if likelihood is not None and not isinstance(likelihood, Gaussian):
+            raise NotImplementedError("%s: the likelihood %s is not implemented on the MI355X path; Gaussian is" % (who, type(likelihood).__name__))
+        if inference_method is not None and (not isinstance(inference_method, VarDTC) or inference_method.psi_lin_bias):
+            raise NotImplementedError("%s: the inference method must be a plain VarDTC() (psi_lin_bias and the reference's "
+                                      "VarDTC_minibatch are not implemented with this class)" % who)
+        Y = np.asarray(Y, dtype=np.float64)
+        self.missing_data = bool(missing_data)
+        if np.isnan(Y).any():
+            if not self.missing_data:
+                raise ValueError("%s: Y holds NaNs; pass missing_data=True" % who)
+            if X is None:
+                raise ValueError("%s: Y holds NaNs, which the PCA initialisation of the latent points cannot decompose; pass X" % who)
+        super(BayesianGPLVMMiniBatch, self).__init__(Y, input_dim, X=X, X_variance=X_variance, init=init, num_inducing=num_inducing,
+                                                     Z=Z, kernel=kernel, inference_method=inference_method, likelihood=likelihood,
+                                                     name=name, device=device)
+
+    def parameters_changed(self):
+        if not self.missing_data:
+            return super(BayesianGPLVMMiniBatch, self).parameters_changed()
+        self.posterior, self._log_marginal_likelihood, self.grad_dict = self.inference_method.inference(
+            self.kern, self.X, self.Z.values, self.likelihood, self.Y_normalized, Y_metadata=self.Y_metadata, missing_data=True)
+        self.likelihood.update_gradients(self.grad_dict["dL_dthetaL"])
+        fused = self.grad_dict["fused"]
+        self.kern._install_fused(fused["dtheta"])
+        self.Z.gradient = fused["dZ"] if fused["dZ"].shape == self.Z.shape else self._scatter_dZ(fused["dZ"])
+        self._log_marginal_likelihood = self._log_marginal_likelihood - self.kl_factr * self.variational_prior.KL_divergence(self.X)
+        self.set_X_gradients(self.X, (self._scatter_X(fused["dmu"]), self._scatter_X(fused["dS"])))
+        self.variational_prior.update_gradients_KL(self.X)
+        self._Xgrad = self.X.gradient.copy()
+
+    def infer_newX(self, Y_new, optimize=True):
+        raise NotImplementedError("BayesianGPLVMMiniBatch.infer_newX is not implemented on the MI355X path")
 
 
 class SSGPLVM(SparseGP):

@@ -363,3 +363,139 @@ def make_psicomp_ssrbf(L, device=0):
             return dvar[0], dl, dZ, dmu, dS, dg
 
     return PSICOMP_SSRBF_MI355X()
+
+
+def bind_missing(L):
+    """argument types of the missing-data entries of include/mi355gp_sparse_missing.h (and of the sparse-context calls they stand
+    on) on an already bound library"""
+    from numpy.ctypeslib import ndpointer
+    dp = ndpointer(np.float64, flags="C_CONTIGUOUS")
+    ci, i64, cd, vp = ctypes.c_int, ctypes.c_int64, ctypes.c_double, ctypes.c_void_p
+    L.mi355gp_sparse_create.argtypes = [ci, ctypes.POINTER(vp)]
+    L.mi355gp_sparse_set_data.argtypes = [vp, dp, i64, ci, dp, ci]
+    L.mi355gp_sparse_set_input_variance.argtypes = [vp, dp, i64, ci]
+    L.mi355gp_sparse_set_inputs.argtypes = [vp, dp, _p, i64, ci]
+    L.mi355gp_sparse_fetch.argtypes = [vp, ci, dp]
+    L.mi355gp_sparse_set_output_groups.argtypes = [vp, ci, ctypes.POINTER(ci), _p]
+    L.mi355gp_vardtc_inference_missing.argtypes = [vp, ci, ctypes.c_void_p, dp, i64, dp, i64, cd, dp] + [_p] * 6
+    L.mi355gp_sparse_select_output_group.argtypes = [vp, ci]
+    L.mi355gp_sparse_fetch_group_scalars.argtypes = [vp, dp]
+    return L
+
+
+class _Part(ctypes.Structure):           # mi355gp_part of include/mi355gp.h
+    _fields_ = [("kind", ctypes.c_int), ("ard", ctypes.c_int), ("n_active", ctypes.c_int), ("active_dims", ctypes.POINTER(ctypes.c_int)),
+                ("theta", ctypes.POINTER(ctypes.c_double)), ("term", ctypes.c_int)]
+
+
+MI355GP_RBF, MI355GP_WHITE = 0, 4
+
+
+def make_missing_data_loop(L, gpy=None, device=0, bind=True):
+    """The object a GPy maintainer binds where `GPy/models/sparse_gp_minibatch.py:228` defines `_outer_loop_for_missing_data`
+    (and `:164` `_outer_values_update`), for a `BayesianGPLVMMiniBatch(missing_data=True)` whose kernel is one RBF alone or
+    summed with White parts:
+
+        loop = make_missing_data_loop(L)
+        SparseGPMiniBatch._outer_loop_for_missing_data = lambda self: loop.outer_loop(self)
+        BayesianGPLVMMiniBatch._outer_values_update = lambda self, full_values: loop.outer_values_update(self, full_values)
+
+    `outer_loop` does what the reference's loop does -- groups of `self.stochastics.d`, `_log_marginal_likelihood`, `posterior`
+    with the M x M x Dy `woodbury_inv`, `full_values` -- in ONE device call (`mi355gp_vardtc_inference_missing`).  The per-row
+    `dL_dpsi2` (N x M x M) is never formed: `full_values` carries `dL_dKmm`, `dL_dpsi0`, `dL_dpsi1`, `dL_dthetaL` and `fused`
+    (`dtheta`, `dZ`, `dmu`, `dS`: the gradients `_outer_values_update` would assemble through the kernel's `*_expectations`),
+    which `outer_values_update` installs; the KL term stays with `BayesianGPLVMMiniBatch.parameters_changed`.
+    `gpy`: namespace with Posterior (default: imported from an installed GPy).  `bind=False`: L already has its argument types."""
+    if gpy is None:
+        from GPy.inference.latent_function_inference.posterior import Posterior
+        gpy = types.SimpleNamespace(Posterior=Posterior)
+    if bind:
+        bind_missing(L)
+
+    def check(rc, what):
+        if rc < 0:
+            raise RuntimeError("%s failed (rc=%d): %s" % (what, rc, L.mi355gp_last_error().decode()))
+        return rc
+
+    def parts_of(kern):
+        leaves = list(getattr(kern, "parts", None) or [kern])
+        names = [type(p).__name__ for p in leaves]
+        if names.count("RBF") != 1 or any(n not in ("RBF", "White") for n in names):
+            raise NotImplementedError("mi355gp missing data: one RBF kernel alone or summed with White parts, got %s" % ", ".join(names))
+        thetas = [_f64(np.r_[np.asarray(p.variance, float).ravel()[:1], np.asarray(p.lengthscale, float).ravel()]) if n == "RBF"
+                  else _f64(np.asarray(p.variance, float).ravel()[:1]) for p, n in zip(leaves, names)]
+        arr = (_Part * len(leaves))()
+        for i, (p, n, th) in enumerate(zip(leaves, names, thetas)):
+            arr[i] = _Part(MI355GP_RBF if n == "RBF" else MI355GP_WHITE, int(n == "RBF" and bool(p.ARD)), 0, None,
+                           th.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), 0)
+        return leaves, names, thetas, arr
+
+    class MissingDataLoop(object):
+        def __init__(self):
+            self._ctx, self._Y, self._mask = None, None, None
+
+        def _upload(self, mu, S, Y):
+            """Y (0 where unobserved) and the masks when either changed, else only the 2 N Q doubles of q(X)"""
+            obs = ~np.isnan(Y)
+            Y0 = _f64(np.where(obs, Y, 0.0))
+            if self._ctx is None:
+                self._ctx = ctypes.c_void_p()
+                check(L.mi355gp_sparse_create(device, ctypes.byref(self._ctx)), "mi355gp_sparse_create")
+            N, Q = mu.shape
+            if self._Y is not None and self._Y.shape == Y0.shape and np.array_equal(self._Y, Y0) and np.array_equal(self._mask, obs):
+                check(L.mi355gp_sparse_set_inputs(self._ctx, mu, _ptr(S), N, Q), "mi355gp_sparse_set_inputs")
+                return
+            first, gof = {}, np.empty(Y.shape[1], dtype=np.int32)          # stochastics.py:57-79: groups by first column
+            for d in range(Y.shape[1]):
+                gof[d] = first.setdefault(obs[:, d].tobytes(), len(first))
+            W = _f64(np.stack([obs[:, int(np.argmax(gof == g))] for g in range(len(first))], axis=1))
+            check(L.mi355gp_sparse_set_data(self._ctx, mu, N, Q, Y0, Y0.shape[1]), "mi355gp_sparse_set_data")
+            check(L.mi355gp_sparse_set_input_variance(self._ctx, S, N, Q), "mi355gp_sparse_set_input_variance")
+            check(L.mi355gp_sparse_set_output_groups(self._ctx, W.shape[1], gof.ctypes.data_as(ctypes.POINTER(ctypes.c_int)), _ptr(W)),
+                  "mi355gp_sparse_set_output_groups")
+            self._Y, self._mask, self.group_of_output, self.W = Y0, obs, gof, W
+
+        def outer_loop(self, model):
+            kern, X = model.kern, model.X
+            leaves, names, thetas, arr = parts_of(kern)
+            mu, S, Z = _f64(np.asarray(X.mean)), _f64(np.asarray(X.variance)), _f64(np.asarray(model.Z))
+            Y = np.asarray(model.Y_normalized, dtype=np.float64)
+            noise = _f64(np.asarray(model.likelihood.gaussian_variance(model.Y_metadata), float).ravel())
+            self._upload(mu, S, Y)
+            (N, Q), M, Dy, G = mu.shape, Z.shape[0], Y.shape[1], self.W.shape[1]
+            out, dtheta = np.zeros(8), np.zeros(sum(t.size for t in thetas))
+            dZ, wv, dmu, dS = np.zeros((M, Q)), np.zeros((M, Dy)), np.zeros((N, Q)), np.zeros((N, Q))
+            rc = check(L.mi355gp_vardtc_inference_missing(self._ctx, len(leaves), ctypes.cast(arr, ctypes.c_void_p), Z, M, noise,
+                                                          noise.size, 0.0, out, _ptr(dtheta), _ptr(dZ), _ptr(wv), _ptr(dmu), _ptr(dS),
+                                                          None), "mi355gp_vardtc_inference_missing")
+            if rc != 0:
+                raise np.linalg.LinAlgError("not positive definite (Kmm or a group's B); the jitter ladder is not bound here")
+            fetch = lambda which: (lambda o: (check(L.mi355gp_sparse_fetch(self._ctx, which, o), "mi355gp_sparse_fetch"), o)[1])(np.empty((M, M)))
+            woodbury_inv = np.empty((M, M, Dy))
+            for g in range(G):
+                check(L.mi355gp_sparse_select_output_group(self._ctx, g), "mi355gp_sparse_select_output_group")
+                woodbury_inv[:, :, self.group_of_output == g] = fetch(SP_WOODBURY_INV)[:, :, None]
+            beta = out[5]
+            counts = np.bincount(self.group_of_output, minlength=G).astype(np.float64)
+            model._log_marginal_likelihood = out[0]
+            model.posterior = gpy.Posterior(woodbury_inv=woodbury_inv, woodbury_vector=wv, K=fetch(SP_KMM), mean=None, cov=None,
+                                            K_chol=fetch(SP_LM))
+            model.full_values = {"dL_dKmm": fetch(SP_DLDKMM), "dL_dpsi0": -0.5 * beta * self.W.dot(counts),
+                                 "dL_dpsi1": beta * self._Y.dot(wv.T), "dL_dthetaL": out[1],
+                                 "fused": {"dtheta": dtheta, "dZ": dZ, "dmu": dmu, "dS": dS, "parts": (leaves, names, thetas)}}
+            model._outer_values_update(model.full_values)
+
+        def outer_values_update(self, model, full_values):
+            f = full_values["fused"]
+            leaves, names, thetas = f["parts"]
+            o = 0
+            for p, n, th in zip(leaves, names, thetas):
+                p.variance.gradient = f["dtheta"][o:o + 1]
+                if n == "RBF":
+                    p.lengthscale.gradient = f["dtheta"][o + 1:o + th.size]
+                o += th.size
+            model.Z.gradient = f["dZ"]
+            model.X.mean.gradient, model.X.variance.gradient = f["dmu"], f["dS"]
+            model.likelihood.update_gradients(full_values["dL_dthetaL"])
+
+    return MissingDataLoop()
