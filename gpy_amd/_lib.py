@@ -93,6 +93,7 @@ def build(force=False):
     srcs.append(os.path.join(_HERE, "..", "include", "mi355gp_debug_sparse_missing.h"))
     srcs.append(os.path.join(_HERE, "..", "include", "mi355gp_vargauss.h"))
     srcs.append(os.path.join(_HERE, "..", "include", "mi355gp_kron.h"))
+    srcs.append(os.path.join(_HERE, "..", "include", "mi355gp_eigh.h"))
     product = os.path.join(_HERE, "libmi355gp.so")
     if not force and os.path.exists(product) and os.path.exists(DIAG_LIB_PATH):
         t = min(os.path.getmtime(product), os.path.getmtime(DIAG_LIB_PATH))
@@ -292,6 +293,12 @@ DEBUG_MISSING_ABI = {
     "mi355gp_dbg_rbf_psi2_groups": [_ci, _cd, _dp, _ci, _dp, _i64, _dp, _dp, _i64, _ci, _dp, _ci, _ci, _dp, _c_dp],
     "mi355gp_dbg_rbf_psi_grad_groups": [_ci, _cd, _dp, _ci, _dp, _i64, _dp, _dp, _i64, _ci, _dp, _ci, _dp, _ci] + [_dp] * 5 + [_c_dp],
 }
+# include/mi355gp_eigh.h: the symmetric positive semi-definite eigensolver (tests/test_eigh_host.py holds the table against that
+# header's prototype)
+EIGH_ABI = {
+    "mi355gp_eigh": [_ci, _dp, _i64, _dp, _dp, _ip, _c_dp],
+}
+EIGH_B, EIGH_MAX_SWEEPS, EIGH_MAX_N = 32, 30, 16384      # MI355GP_EIGH_*
 TILEOPS = {"trmm_lower": 0, "trmm_lower_T": 1, "trmm64": 2, "gram_splitk": 3, "update_nt": 4}    # MI355GP_TILEOP_*
 
 
@@ -307,7 +314,7 @@ def lib():
             build()
         L = ctypes.CDLL(LIB_PATH)
         for table in (ABI, DEBUG_LAUUM_ABI, DEBUG_TILEOPS_ABI, EPDTC_ABI, SPARSE_DIAG_ABI, SPARSE_COREG_ABI, DEBUG_SPARSE_COREG_ABI, PSI_LIN_ABI, DEBUG_PSI_LIN_ABI,
-                      PSI_SS_ABI, VARGAUSS_ABI, KRON_ABI, MISSING_ABI, DEBUG_MISSING_ABI):
+                      PSI_SS_ABI, VARGAUSS_ABI, KRON_ABI, MISSING_ABI, DEBUG_MISSING_ABI, EIGH_ABI):
             for name, argtypes in table.items():
                 getattr(L, name).argtypes = argtypes
         L.mi355gp_last_error.restype = L.mi355gp_version.restype = _str
@@ -1188,6 +1195,18 @@ def potrf(A, device=0):
     ms = ctypes.c_double(0.0)
     info = check(lib().mi355gp_potrf(device, L, L.shape[0], ctypes.byref(ms)), "mi355gp_potrf")
     return L, info, ms.value
+
+
+def eigh(A, device=0):
+    """Eigendecomposition of a symmetric positive semi-definite A on the device (include/mi355gp_eigh.h) ->
+    (w ascending, V with the eigenvectors in columns, info: 1 when the sweep cap was reached, sweeps, ms)."""
+    require_device(device)
+    A = f64(A)
+    n = A.shape[0]
+    w, V = np.empty(n), np.empty((n, n))
+    sweeps, ms = ctypes.c_int(0), ctypes.c_double(0.0)
+    info = check(lib().mi355gp_eigh(device, A, n, w, V, ctypes.byref(sweeps), ctypes.byref(ms)), "mi355gp_eigh")
+    return w, V, info, sweeps.value, ms.value
 
 
 def pdinv(A, device=0):

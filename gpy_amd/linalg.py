@@ -4,6 +4,11 @@ method of the reference: Laplace, EP, VarDTC) goes through:
     jitchol(A, maxtries=5)  -> L                      (reference `util/linalg.py:56-75`)
     pdinv(A)                -> (Ai, L, Li, logdet)    (reference `util/linalg.py:193-214`)
 
+and the eigendecomposition the Kronecker models of the reference are built around (`numpy.linalg.eigh` / `eig` of a covariance
+matrix in `models/gp_kronecker_gaussian_regression.py` and `gaussian_grid_inference.py`):
+
+    eigh(A)                 -> (w, V)                 symmetric POSITIVE SEMI-DEFINITE A only (`mi355gp_eigh`: blocked one-sided Jacobi)
+
 The matrix travels to the device once, the factorisation (`mi355gp_potrf`) / factorisation + inverse (`mi355gp_pdinv_full`:
 blocked Cholesky, triangular inverse, X^T X) run on the device, the results come back as NumPy arrays in the reference's
 layout (C-order `Ai`, lower-triangular `L` with a zero upper triangle, `Li = L^-1`).  Errors are the reference's:
@@ -73,3 +78,24 @@ def pdinv(A, *args, **kw):
         Ai, L, Li, logdet, info = _lib.pdinv_full(M, device=device)
         return (Ai, L, Li, logdet), info
     return _ladder(A, kw.pop("maxtries", 5), attempt)
+
+
+def eigh(A, device=0, return_info=False):
+    """(w, V) of a symmetric positive semi-definite matrix -- a covariance matrix, rank-deficient ones included: the eigenvalues
+    ascending, the eigenvectors in the columns of V, as `numpy.linalg.eigh` returns them, computed on the device
+    (include/mi355gp_eigh.h).  An indefinite matrix is outside the contract and is not detected.  Refused by name: a matrix that
+    is not square, not symmetric, not finite or larger than `_lib.EIGH_MAX_N`; `LinAlgError` when the sweep cap was reached.
+    `return_info`: also a dict with the sweeps that ran, the cap and the device time in ms."""
+    A = np.asarray(A, dtype=np.float64)
+    if A.ndim != 2 or A.shape[0] != A.shape[1] or A.shape[0] < 1:
+        raise ValueError("eigh: A must be a square matrix, got shape %r" % (A.shape,))
+    if A.shape[0] > _lib.EIGH_MAX_N:
+        raise ValueError("eigh: n = %d is above the device eigensolver's limit of %d" % (A.shape[0], _lib.EIGH_MAX_N))
+    if not np.isfinite(A).all():
+        raise ValueError("eigh: A has entries that are not finite")
+    if np.abs(A - A.T).max() > 8 * np.finfo(np.float64).eps * np.abs(A).max():
+        raise ValueError("eigh: A is not symmetric (beyond rounding; the triangle with column <= row is what is read)")
+    w, V, info, sweeps, ms = _lib.eigh(A, device=device)
+    if info != 0:
+        raise LinAlgError("eigh: no convergence in %d sweeps (is A positive semi-definite?)" % sweeps)
+    return (w, V, {"sweeps": sweeps, "max_sweeps": _lib.EIGH_MAX_SWEEPS, "ms": ms}) if return_info else (w, V)
