@@ -13,6 +13,7 @@ from .laplace import Laplace, LaplacePosterior
 from .ep import EP
 from .vargauss import VarGauss, VarGaussPosterior
 from .kron import GaussianGridInference, GpGrid, GPRegressionGrid, GridPosterior
+from .kgpr import GPKroneckerGaussianRegression
 from .kern import (OU, RBF, Add, Prod, Bias, Coregionalize, Cosine, ExpQuad, ExpQuadCosine, Sinc, Exponential, Linear, Matern32, Matern52, MLP, Poly, RatQuad,
                    Stationary, StdPeriodic, White)
 from .likelihoods import Bernoulli, Gaussian, HeteroscedasticGaussian, MixedNoise, Poisson, StudentT
@@ -27,7 +28,7 @@ from .svgp import SVGPPosterior
 from .variational import NormalPosterior, NormalPrior, SpikeAndSlabPosterior, SpikeAndSlabPrior
 
 __all__ = ["RBF", "OU", "ExpQuad", "HeteroscedasticGaussian", "StudentTPosterior", "Matern52", "Matern32", "Exponential", "RatQuad", "Cosine", "Sinc", "ExpQuadCosine", "StdPeriodic", "Coregionalize", "Linear", "MLP", "Poly", "MixedNoise", "Stationary", "White", "Bias", "Add", "Prod", "Gaussian", "ExactGaussianInference", "ExactStudentTInference",
-           "PosteriorExact", "GP", "GPRegression", "GPHeteroscedasticRegression", "GPCoregionalizedRegression", "Laplace", "LaplacePosterior", "EP", "PosteriorEP", "Bernoulli", "StudentT", "Poisson", "GPClassification", "VarDTC", "SparseGP", "SparseGPRegression", "SparseGPCoregionalizedRegression", "SVGP", "SVGPPosterior", "NormalPosterior", "NormalPrior", "SpikeAndSlabPosterior", "SpikeAndSlabPrior", "BayesianGPLVM", "BayesianGPLVMMiniBatch", "SSGPLVM", "FITC", "PEP", "EPDTC", "SparseGPClassification", "VarGauss", "VarGaussPosterior", "GPVariationalGaussianApproximation", "GaussianGridInference", "GridPosterior", "GpGrid", "GPRegressionGrid", "MI355GPError", "build", "device_count"]
+           "PosteriorExact", "GP", "GPRegression", "GPHeteroscedasticRegression", "GPCoregionalizedRegression", "Laplace", "LaplacePosterior", "EP", "PosteriorEP", "Bernoulli", "StudentT", "Poisson", "GPClassification", "VarDTC", "SparseGP", "SparseGPRegression", "SparseGPCoregionalizedRegression", "SVGP", "SVGPPosterior", "NormalPosterior", "NormalPrior", "SpikeAndSlabPosterior", "SpikeAndSlabPrior", "BayesianGPLVM", "BayesianGPLVMMiniBatch", "SSGPLVM", "FITC", "PEP", "EPDTC", "SparseGPClassification", "VarGauss", "VarGaussPosterior", "GPVariationalGaussianApproximation", "GaussianGridInference", "GridPosterior", "GpGrid", "GPRegressionGrid", "GPKroneckerGaussianRegression", "MI355GPError", "build", "device_count"]
 
 # GPy's import paths, so that `import gpy_amd as GPy` reads like the reference on this path:
 #   GPy.kern.RBF, GPy.likelihoods.Gaussian, GPy.models.GPRegression / SparseGPRegression / GPHeteroscedasticRegression,
@@ -37,12 +38,12 @@ __all__ = ["RBF", "OU", "ExpQuad", "HeteroscedasticGaussian", "StudentTPosterior
 #   GPy.inference.latent_function_inference.FITC / PEP (and .fitc.FITC, .pep.PEP),
 #   GPy.inference.latent_function_inference.EPDTC (and .expectation_propagation.EPDTC), GPy.models.SparseGPClassification,
 #   GPy.inference.latent_function_inference.VarGauss (and .var_gauss.VarGauss), GPy.models.GPVariationalGaussianApproximation,
-#   GPy.models.GPRegressionGrid, GPy.core.GpGrid, GPy.inference.latent_function_inference.GaussianGridInference (and
+#   GPy.models.GPKroneckerGaussianRegression, GPy.models.GPRegressionGrid, GPy.core.GpGrid, GPy.inference.latent_function_inference.GaussianGridInference (and
 #   .gaussian_grid_inference.GaussianGridInference, .grid_posterior.GridPosterior), GPy.kern.GridRBF,
 #   GPy.util.choleskies, GPy.models.BayesianGPLVM, GPy.models.BayesianGPLVMMiniBatch (and .bayesian_gplvm_minibatch), GPy.util.initialization.initialize_latent,
 #   GPy.models.SparseGPCoregionalizedRegression, GPy.models.ss_gplvm.SSGPLVM,
 #   GPy.core.parameterization.variational.SpikeAndSlabPosterior / SpikeAndSlabPrior
-from . import ep, epdtc, inference, kern, kron, laplace, likelihoods, link_functions, linalg, models, pep, sparse, svgp, util, vargauss  # noqa: E402
+from . import ep, epdtc, inference, kern, kgpr, kron, laplace, likelihoods, link_functions, linalg, models, pep, sparse, svgp, util, vargauss  # noqa: E402
 import types as _types  # noqa: E402
 
 models.SparseGPRegression = SparseGPRegression
@@ -53,6 +54,7 @@ models.bayesian_gplvm_minibatch = _types.SimpleNamespace(BayesianGPLVMMiniBatch=
 models.ss_gplvm = _types.SimpleNamespace(SSGPLVM=SSGPLVM)         # (GPy.models.SSGPLVM itself keeps refusing: models.__getattr__)
 models.SparseGPClassification = SparseGPClassification
 models.GPRegressionGrid = GPRegressionGrid
+models.GPKroneckerGaussianRegression = GPKroneckerGaussianRegression
 core = _types.SimpleNamespace(GP=GP, GpGrid=GpGrid, gp_grid=_types.SimpleNamespace(GpGrid=GpGrid), SparseGP=SparseGP, SVGP=SVGP, svgp=_types.SimpleNamespace(SVGP=SVGP), parameterization=_types.SimpleNamespace(
     variational=_types.SimpleNamespace(NormalPosterior=NormalPosterior, NormalPrior=NormalPrior,
                                        SpikeAndSlabPosterior=SpikeAndSlabPosterior, SpikeAndSlabPrior=SpikeAndSlabPrior)))

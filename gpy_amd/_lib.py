@@ -94,6 +94,7 @@ def build(force=False):
     srcs.append(os.path.join(_HERE, "..", "include", "mi355gp_vargauss.h"))
     srcs.append(os.path.join(_HERE, "..", "include", "mi355gp_kron.h"))
     srcs.append(os.path.join(_HERE, "..", "include", "mi355gp_eigh.h"))
+    srcs.append(os.path.join(_HERE, "..", "include", "mi355gp_kgpr.h"))
     product = os.path.join(_HERE, "libmi355gp.so")
     if not force and os.path.exists(product) and os.path.exists(DIAG_LIB_PATH):
         t = min(os.path.getmtime(product), os.path.getmtime(DIAG_LIB_PATH))
@@ -299,6 +300,19 @@ EIGH_ABI = {
     "mi355gp_eigh": [_ci, _dp, _i64, _dp, _dp, _ip, _c_dp],
 }
 EIGH_B, EIGH_MAX_SWEEPS, EIGH_MAX_N = 32, 30, 16384      # MI355GP_EIGH_*
+# include/mi355gp_kgpr.h: Kronecker GP regression with two arbitrary kernels on the device eigensolver, in its order
+# (tests/test_kgpr_host.py holds the table against that header's prototypes)
+KGPR_ABI = {
+    "mi355gp_kgpr_create": [_ci, _hp],
+    "mi355gp_kgpr_destroy": [_vp],
+    "mi355gp_kgpr_set_data": [_vp, _dp, _i64, _i64],
+    "mi355gp_kgpr_inference": [_vp, _dp, _dp, _cd, _dp, _dp, _dp, _ip],
+    "mi355gp_kgpr_predict": [_vp, _dp, _i64, _dp, _i64, _dp, _dp, _dp, _dp],
+    "mi355gp_kgpr_fetch": [_vp, _ci, _dp],
+    "mi355gp_kgpr_get_ms": [_vp, _dp],
+    "mi355gp_kgpr_wsyrk": [_ci, _i64, _dp, _i64, _dp, _dp, _i64, _dp, _dp, _ci, _c_dp],
+}
+KGPR_NUM_MS = 9                                          # MI355GP_KGPR_NUM_MS
 TILEOPS = {"trmm_lower": 0, "trmm_lower_T": 1, "trmm64": 2, "gram_splitk": 3, "update_nt": 4}    # MI355GP_TILEOP_*
 
 
@@ -314,7 +328,7 @@ def lib():
             build()
         L = ctypes.CDLL(LIB_PATH)
         for table in (ABI, DEBUG_LAUUM_ABI, DEBUG_TILEOPS_ABI, EPDTC_ABI, SPARSE_DIAG_ABI, SPARSE_COREG_ABI, DEBUG_SPARSE_COREG_ABI, PSI_LIN_ABI, DEBUG_PSI_LIN_ABI,
-                      PSI_SS_ABI, VARGAUSS_ABI, KRON_ABI, MISSING_ABI, DEBUG_MISSING_ABI, EIGH_ABI):
+                      PSI_SS_ABI, VARGAUSS_ABI, KRON_ABI, MISSING_ABI, DEBUG_MISSING_ABI, EIGH_ABI, KGPR_ABI):
             for name, argtypes in table.items():
                 getattr(L, name).argtypes = argtypes
         L.mi355gp_last_error.restype = L.mi355gp_version.restype = _str
@@ -1480,6 +1494,71 @@ class KronContext(_Handle):
         ms = ctypes.c_double(0.0)
         check(lib().mi355gp_kron_get_ms(self._h, ctypes.byref(ms)), "mi355gp_kron_get_ms")
         return ms.value
+
+
+class KgprContext(_Handle):
+    """One device context of Kronecker GP regression with two arbitrary kernels (include/mi355gp_kgpr.h) = one uploaded Y (N1 x N2)
+    and, after an evaluation, U1, S1, U2, S2, Ytilde and Wi resident on the device."""
+    _create, _destroy = "mi355gp_kgpr_create", "mi355gp_kgpr_destroy"
+    FETCH_U1, FETCH_S1, FETCH_U2, FETCH_S2, FETCH_YTILDE, FETCH_WI = range(6)
+    MS_NAMES = ("eigh", "rotations", "spectral", "wsyrk", "transfers", "total", "wsyrk_K1", "wsyrk_K2", "predict")
+
+    def __init__(self, device=0):
+        super(KgprContext, self).__init__(device)
+        self.N1 = self.N2 = 0
+        self.call_token = 0
+
+    def set_data(self, Y):
+        Y = f64(Y)
+        assert Y.ndim == 2
+        check(lib().mi355gp_kgpr_set_data(self._h, Y, Y.shape[0], Y.shape[1]), "mi355gp_kgpr_set_data")
+        self.N1, self.N2 = Y.shape
+
+    def inference(self, K1, K2, noise):
+        """(lml, dL_dsigma2, dL_dK1, dL_dK2, (sweeps of K1, sweeps of K2)); U1, S1, U2, S2, Ytilde, Wi stay resident"""
+        K1, K2 = f64(K1), f64(K2)
+        assert K1.shape == (self.N1, self.N1) and K2.shape == (self.N2, self.N2), "K1 must be N1 x N1 and K2 N2 x N2"
+        sc, g1, g2 = np.zeros(2), np.empty((self.N1, self.N1)), np.empty((self.N2, self.N2))
+        sweeps = (ctypes.c_int * 2)(0, 0)
+        self.call_token += 1
+        check(lib().mi355gp_kgpr_inference(self._h, K1, K2, float(noise), sc, g1, g2, sweeps), "mi355gp_kgpr_inference")
+        return float(sc[0]), float(sc[1]), g1, g2, (sweeps[0], sweeps[1])
+
+    def predict(self, k1xf, k2xf, k1xx, k2xx):
+        """all M1 M2 combinations, flat index i + M1 j: (mu, var)"""
+        k1xf, k2xf, k1xx, k2xx = f64(k1xf), f64(k2xf), f64(np.ravel(k1xx)), f64(np.ravel(k2xx))
+        M1, M2 = k1xf.shape[0], k2xf.shape[0]
+        assert k1xf.shape == (M1, self.N1) and k2xf.shape == (M2, self.N2) and k1xx.size == M1 and k2xx.size == M2
+        mu, var = np.empty(M1 * M2), np.empty(M1 * M2)
+        check(lib().mi355gp_kgpr_predict(self._h, k1xf, M1, k2xf, M2, k1xx, k2xx, mu, var), "mi355gp_kgpr_predict")
+        return mu, var
+
+    def fetch(self, which):
+        shape = {self.FETCH_U1: (self.N1, self.N1), self.FETCH_S1: (self.N1,), self.FETCH_U2: (self.N2, self.N2),
+                 self.FETCH_S2: (self.N2,)}.get(which, (self.N1, self.N2))
+        out = np.empty(shape)
+        check(lib().mi355gp_kgpr_fetch(self._h, int(which), out), "mi355gp_kgpr_fetch")
+        return out
+
+    def last_ms(self):
+        """HIP-event times (ms) of the last inference and the last predict, by `MS_NAMES`"""
+        ms = np.zeros(KGPR_NUM_MS)
+        check(lib().mi355gp_kgpr_get_ms(self._h, ms), "mi355gp_kgpr_get_ms")
+        return dict(zip(self.MS_NAMES, ms.tolist()))
+
+
+def kgpr_wsyrk(Pa, da, Pb, db, reps=1, device=0):
+    """The weighted symmetric rank-k kernel alone (`mi355gp_kgpr_wsyrk`): (C = 1/2 Pa diag(da) Pa^T + 1/2 Pb diag(db) Pb^T, ms per
+    launch) for Pa (n x ka), Pb (n x kb) and signed weights da (ka), db (kb)."""
+    require_device(device)
+    Pa, Pb, da, db = f64(Pa), f64(Pb), f64(np.ravel(da)), f64(np.ravel(db))
+    n, ka = Pa.shape
+    kb = Pb.shape[1]
+    assert Pb.shape[0] == n and da.size == ka and db.size == kb
+    C = np.empty((n, n))
+    ms = ctypes.c_double(0.0)
+    check(lib().mi355gp_kgpr_wsyrk(device, n, Pa, ka, da, Pb, kb, db, C, int(reps), ctypes.byref(ms)), "mi355gp_kgpr_wsyrk")
+    return C, ms.value
 
 
 def psi_lin_rows_probe(W, X, Z, variances, c0=0.0, Y=None, V=None, rowscale=None, beta=0.0, gscale=1.0, fused=True, device=0,

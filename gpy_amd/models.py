@@ -52,13 +52,8 @@ def _gaussian_only(likelihood, what):
         raise NotImplementedError("%s is not implemented for the %s likelihood on this backend" % (what, type(likelihood).__name__))
 
 
-class PredictionCallers(object):
-    """The prediction-side callers of the hot path in the reference's `GP` class (`core/gp.py:367-474,601-652,700-790`), shared
-    by the exact and the sparse model driver: everything here is a thin wrapper around `_raw_predict` / the posterior, exactly as
-    in the reference (`SparseGP` inherits them from `GP`; `_predictive_variable` is X for the exact model and Z for the sparse
-    one, `core/gp.py:201-203`, `core/sparse_gp.py:72-74`)."""
-    normalizer = None
-    output_dim = 1
+class GradientCheck(object):
+    """`checkgrad` for any model with `param_array`, `objective_function` and `objective_function_gradients`"""
 
     def checkgrad(self, verbose=False, step=1e-6, tolerance=1e-3):
         """The gradient check the reference's tests lean on (`paramz.Model.checkgrad`, used e.g. at
@@ -80,6 +75,15 @@ class PredictionCallers(object):
         if abs(ana) < 1e-14 and abs(num) < 1e-14:
             return True
         return bool(abs(1.0 - num / ana) < tolerance) if ana != 0 else False
+
+
+class PredictionCallers(GradientCheck):
+    """The prediction-side callers of the hot path in the reference's `GP` class (`core/gp.py:367-474,601-652,700-790`), shared
+    by the exact and the sparse model driver: everything here is a thin wrapper around `_raw_predict` / the posterior, exactly as
+    in the reference (`SparseGP` inherits them from `GP`; `_predictive_variable` is X for the exact model and Z for the sparse
+    one, `core/gp.py:201-203`, `core/sparse_gp.py:72-74`)."""
+    normalizer = None
+    output_dim = 1
 
     def input_sensitivity(self, summarize=True):
         """(reference `core/gp.py:654-658`)"""
@@ -153,103 +157,15 @@ class PredictionCallers(object):
         return cov
 
 
-class GP(PredictionCallers, Parameterized):
-    def __init__(self, X, Y, kernel, likelihood, mean_function=None, inference_method=None, name="gp",
-                 Y_metadata=None, device=0, normalizer=False):
-        super(GP, self).__init__(name)
-        # private read-only copies, as GPy wraps X / Y in `ObsAr` (reference `core/gp.py:44-60`): a frozen array is what
-        # lets the per-iteration "same data?" check of the inference method be O(1) without ever missing an edit.  New
-        # data go through set_XY / set_X / set_Y; `m.X[i] = ...` raises instead of silently leaving the device stale.
-        X, Y = freeze(X), freeze(Y)
-        assert X.ndim == 2 and Y.ndim == 2
-        self.X, self.Y = X, Y
-        # (reference `core/gp.py:49-60`): normalizer=True -> Standardize
-        self.normalizer = Standardize() if normalizer is True else (None if normalizer is False else normalizer)
-        if self.normalizer is not None:
-            self.normalizer.scale_by(Y)
-            self.Y_normalized = freeze(self.normalizer.normalize(Y))
-        else:
-            self.Y_normalized = Y
-        self.num_data, self.input_dim = X.shape
-        self.output_dim = Y.shape[1]
-        self.Y_metadata = Y_metadata
-        self.kern = kernel
-        self.likelihood = likelihood
-        self.mean_function = mean_function
-        self.inference_method = inference_method or ExactGaussianInference(device=device)
-        self.link_parameter(self.kern)
-        self.link_parameter(self.likelihood)
-        self.posterior = None
-        self._log_marginal_likelihood = None
-        self.grad_dict = None
-        self.parameters_changed()
-
-    def parameters_changed(self):
-        """The hot loop body (reference `core/gp.py:278-282`)."""
-        self.posterior, self._log_marginal_likelihood, self.grad_dict = self.inference_method.inference(
-            self.kern, self.X, self.likelihood, self.Y_normalized, self.mean_function, self.Y_metadata)
-        self.likelihood.update_gradients(self.grad_dict["dL_dthetaL"])
-        self.kern.update_gradients_full(self.grad_dict["dL_dK"], self.X)
-        if self.mean_function is not None:
-            self.mean_function.update_gradients(self.grad_dict["dL_dm"], self.X)
-
-    def log_likelihood(self):
-        return self._log_marginal_likelihood
+class ObjectiveOptimizer(object):
+    """The objective (the negative log marginal likelihood) and its L-BFGS-B driver, for any `Parameterized` with
+    `_log_marginal_likelihood`: what `GP` and `GPKroneckerGaussianRegression` (kgpr.py) share."""
 
     def objective_function(self):
         return -float(self._log_marginal_likelihood)
 
     def objective_function_gradients(self):
         return -self.gradient
-
-    def set_XY(self, X=None, Y=None):
-        """(reference `core/gp.py:188-246`)"""
-        if X is not None:
-            self.X = freeze(X)                      # a copy: later in-place edits of the caller's buffer do not alias it
-            self.num_data = self.X.shape[0]
-        if Y is not None:
-            self.Y = freeze(Y)
-            if self.normalizer is not None:
-                self.normalizer.scale_by(self.Y)
-                self.Y_normalized = freeze(self.normalizer.normalize(self.Y))
-            else:
-                self.Y_normalized = self.Y
-        self.parameters_changed()
-
-    def _raw_predict(self, Xnew, full_cov=False, kern=None):
-        """(reference `core/gp.py:290-306`)"""
-        mu, var = self.posterior._raw_predict(kern=self.kern if kern is None else kern, Xnew=np.asarray(Xnew),
-                                              pred_var=self.X, full_cov=full_cov)
-        if self.mean_function is not None:
-            mu = mu + self.mean_function.f(Xnew)
-        return mu, var
-
-    def predict(self, Xnew, full_cov=False, Y_metadata=None, kern=None, likelihood=None, include_likelihood=True):
-        """(reference `core/gp.py:308-365`, same argument order)"""
-        mu, var = self._raw_predict(Xnew, full_cov=full_cov, kern=kern)
-        if include_likelihood:
-            likelihood = self.likelihood if likelihood is None else likelihood
-            mu, var = likelihood.predictive_values(mu, var, full_cov=full_cov,
-                                                   Y_metadata=self.Y_metadata if Y_metadata is None else Y_metadata)
-        if self.normalizer is not None:              # (reference `core/gp.py:353-363`)
-            mu = self.normalizer.inverse_mean(mu)
-            if full_cov and mu.shape[1] > 1:
-                var = self.normalizer.inverse_covariance(var)
-            else:
-                var = self.normalizer.inverse_variance(var)
-        return mu, var
-
-    @property
-    def _predictive_variable(self):
-        return self.X
-
-    def set_X(self, X):
-        """(reference `core/gp.py:251-258`)"""
-        self.set_XY(X=X)
-
-    def set_Y(self, Y):
-        """(reference `core/gp.py:260-267`)"""
-        self.set_XY(Y=Y)
 
     def optimize(self, max_iters=1000, messages=False, gtol=1e-6):
         """L-BFGS-B on the negative log marginal likelihood in log-parameter space; parameters declared `positive=False`
@@ -302,6 +218,99 @@ class GP(PredictionCallers, Parameterized):
         self.param_array = params(res.x)
         self._optimization_hook("on_optimization_end")
         return res
+
+
+class GP(PredictionCallers, ObjectiveOptimizer, Parameterized):
+    def __init__(self, X, Y, kernel, likelihood, mean_function=None, inference_method=None, name="gp",
+                 Y_metadata=None, device=0, normalizer=False):
+        super(GP, self).__init__(name)
+        # private read-only copies, as GPy wraps X / Y in `ObsAr` (reference `core/gp.py:44-60`): a frozen array is what
+        # lets the per-iteration "same data?" check of the inference method be O(1) without ever missing an edit.  New
+        # data go through set_XY / set_X / set_Y; `m.X[i] = ...` raises instead of silently leaving the device stale.
+        X, Y = freeze(X), freeze(Y)
+        assert X.ndim == 2 and Y.ndim == 2
+        self.X, self.Y = X, Y
+        # (reference `core/gp.py:49-60`): normalizer=True -> Standardize
+        self.normalizer = Standardize() if normalizer is True else (None if normalizer is False else normalizer)
+        if self.normalizer is not None:
+            self.normalizer.scale_by(Y)
+            self.Y_normalized = freeze(self.normalizer.normalize(Y))
+        else:
+            self.Y_normalized = Y
+        self.num_data, self.input_dim = X.shape
+        self.output_dim = Y.shape[1]
+        self.Y_metadata = Y_metadata
+        self.kern = kernel
+        self.likelihood = likelihood
+        self.mean_function = mean_function
+        self.inference_method = inference_method or ExactGaussianInference(device=device)
+        self.link_parameter(self.kern)
+        self.link_parameter(self.likelihood)
+        self.posterior = None
+        self._log_marginal_likelihood = None
+        self.grad_dict = None
+        self.parameters_changed()
+
+    def parameters_changed(self):
+        """The hot loop body (reference `core/gp.py:278-282`)."""
+        self.posterior, self._log_marginal_likelihood, self.grad_dict = self.inference_method.inference(
+            self.kern, self.X, self.likelihood, self.Y_normalized, self.mean_function, self.Y_metadata)
+        self.likelihood.update_gradients(self.grad_dict["dL_dthetaL"])
+        self.kern.update_gradients_full(self.grad_dict["dL_dK"], self.X)
+        if self.mean_function is not None:
+            self.mean_function.update_gradients(self.grad_dict["dL_dm"], self.X)
+
+    def log_likelihood(self):
+        return self._log_marginal_likelihood
+
+    def set_XY(self, X=None, Y=None):
+        """(reference `core/gp.py:188-246`)"""
+        if X is not None:
+            self.X = freeze(X)                      # a copy: later in-place edits of the caller's buffer do not alias it
+            self.num_data = self.X.shape[0]
+        if Y is not None:
+            self.Y = freeze(Y)
+            if self.normalizer is not None:
+                self.normalizer.scale_by(self.Y)
+                self.Y_normalized = freeze(self.normalizer.normalize(self.Y))
+            else:
+                self.Y_normalized = self.Y
+        self.parameters_changed()
+
+    def _raw_predict(self, Xnew, full_cov=False, kern=None):
+        """(reference `core/gp.py:290-306`)"""
+        mu, var = self.posterior._raw_predict(kern=self.kern if kern is None else kern, Xnew=np.asarray(Xnew),
+                                              pred_var=self.X, full_cov=full_cov)
+        if self.mean_function is not None:
+            mu = mu + self.mean_function.f(Xnew)
+        return mu, var
+
+    def predict(self, Xnew, full_cov=False, Y_metadata=None, kern=None, likelihood=None, include_likelihood=True):
+        """(reference `core/gp.py:308-365`, same argument order)"""
+        mu, var = self._raw_predict(Xnew, full_cov=full_cov, kern=kern)
+        if include_likelihood:
+            likelihood = self.likelihood if likelihood is None else likelihood
+            mu, var = likelihood.predictive_values(mu, var, full_cov=full_cov,
+                                                   Y_metadata=self.Y_metadata if Y_metadata is None else Y_metadata)
+        if self.normalizer is not None:              # (reference `core/gp.py:353-363`)
+            mu = self.normalizer.inverse_mean(mu)
+            if full_cov and mu.shape[1] > 1:
+                var = self.normalizer.inverse_covariance(var)
+            else:
+                var = self.normalizer.inverse_variance(var)
+        return mu, var
+
+    @property
+    def _predictive_variable(self):
+        return self.X
+
+    def set_X(self, X):
+        """(reference `core/gp.py:251-258`)"""
+        self.set_XY(X=X)
+
+    def set_Y(self, Y):
+        """(reference `core/gp.py:260-267`)"""
+        self.set_XY(Y=Y)
 
 
 class GPRegression(GP):
