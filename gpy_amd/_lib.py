@@ -723,13 +723,16 @@ class SparseContext(_Handle):
         check(lib().mi355gp_sparse_attach_loopback(self._h, rank, world, int(group_key)), "mi355gp_sparse_attach_loopback")
         self.sharded = True
 
-    def vardtc_sum(self, specs, Z, noise, extra_jitter=0.0, want_dL_dm=False, want_stage_ms=False):
+    def vardtc_sum(self, specs, Z, noise, extra_jitter=0.0, want_dL_dm=False, want_stage_ms=False, per_point=False):
         """Sum-of-parts kernel (specs as for `Context.exact_inference_sum`), scalar or per-point noise variances.
         (info, dict(lml, dnoise (scalar; per-point noise: the N-vector dL_dR, N x Dy for several output columns), dtheta
-        (concatenated), dZ, woodbury_vector[, dL_dm, stage_ms]))"""
+        (concatenated), dZ, woodbury_vector[, dL_dm, stage_ms])).  More than one variance is per-point noise.  per_point: what
+        a rank of a row-sharded context that holds ONE row says to have its one variance read as per-point noise, as the
+        other ranks read theirs (every rank must take the same reading; an unsharded context takes one row as scalar noise)."""
         arr, keep, ntheta = make_parts(specs)
         noise = f64(np.atleast_1d(noise)).ravel()
-        rows = np.zeros((self.N, self.Dy)) if noise.size > 1 else None   # dL_dR per point and output column (var_dtc.py:240-256)
+        het = noise.size > 1 or (bool(per_point) and self.sharded and self.N == 1)
+        rows = np.zeros((self.N, self.Dy)) if het else None              # dL_dR per point and output column (var_dtc.py:240-256)
         dm = np.zeros((self.N, self.Dy)) if want_dL_dm else None
         rc, out, res = self._fit("mi355gp_vardtc_inference_sum", (len(specs), arr), ntheta, Z,
                                  (noise, noise.size, float(extra_jitter)), (rows, dm), want_stage_ms)

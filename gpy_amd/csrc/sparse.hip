@@ -1440,7 +1440,10 @@ int mi355gp_vardtc_inference_sum(mi355gp_sparse* s, int nparts, const mi355gp_pa
     ARG_CHECK(s && s->n > 0, "mi355gp_vardtc_inference: set_data first");
     ARG_CHECK(parts && Z && M > 0 && out_scalars && noise, "mi355gp_vardtc_inference: bad arguments");
     ARG_CHECK(noise_len == 1 || noise_len == s->n, "noise must have 1 or N entries");
-    const bool het = noise_len > 1;
+    // One row and one variance: scalar and per-point noise are then the same model, and an unsharded context reads it as scalar.
+    // The ranks of a row-sharded context must all take the SAME reading (psi2 carries the precisions in one and not in the
+    // other), and a rank cannot see from its one row what the others hold: it states per-point noise by passing dnoise_rows_out.
+    const bool het = noise_len > 1 || (sharded(s) && s->n == 1 && dnoise_rows_out != nullptr);
     ARG_CHECK(!het || dnoise_rows_out, "per-point noise: dnoise_rows_out (N x Dy) is required");
     EngineShared gate(s->device);
     if (int rc = sparse_open(s, nparts, parts, M, /*coreg=*/true)) return rc;
@@ -1466,21 +1469,22 @@ int mi355gp_vardtc_inference_sum(mi355gp_sparse* s, int nparts, const mi355gp_pa
         glob[2] = hbeta[0] * s->trYYT_local;
     }
     return vardtc_evaluate(s, Z, hbeta, glob, 1e-8 + extra_jitter, out_scalars, dtheta_out, dZ_out, wv_out, dnoise_rows_out, dLdm_out,
-                           stage_ms);
+                           stage_ms, het ? 1 : 0);
 }
 
 }  // extern "C"
 
 // The evaluation itself, for a call that sparse_open has opened: hbeta = the precisions (one for every row, or n), glob =
 // {sum beta_n, sum log beta_n, sum beta_n |R_n|^2} of this shard, kmm_jitter = the whole term on Kmm's diagonal.  The targets
-// are the context's (dY, rowYY, trYYT).  EPDTC (epdtc.hip) evaluates its converged sites through it.
+// are the context's (dY, rowYY, trYYT).  EPDTC (epdtc.hip) evaluates its converged sites through it.  per_point: 1 / 0 = the
+// noise model as the caller states it (a context of ONE row holds one precision either way), -1 = by the number of precisions.
 int vardtc_evaluate(mi355gp_sparse* s, const double* Z, const std::vector<double>& hbeta, double (&glob)[3], double kmm_jitter,
                     double* out_scalars, double* dtheta_out, double* dZ_out, double* wv_out, double* dnoise_rows_out,
-                    double* dLdm_out, double* stage_ms) {
+                    double* dLdm_out, double* stage_ms, int per_point) {
     hipStream_t st = s->st;
     const long n = s->n, m = s->m;
     const int Dy = s->Dy;
-    const bool het = hbeta.size() > 1;
+    const bool het = per_point < 0 ? hbeta.size() > 1 : per_point != 0;
     const double beta = het ? 0.0 : hbeta[0];
     s->beta_scalar = beta;
     s->mfma_prof.on = true;
@@ -1529,10 +1533,18 @@ int vardtc_evaluate(mi355gp_sparse* s, const double* Z, const std::vector<double
     }
     if (int rc = sparse_finish(s, 3, stage_ms)) return rc;      // (info > 0: Kmm or B not positive definite, the caller adds jitter)
     if (sharded(s)) {                                           // sums over ALL shards of the per-point quantities
-        HIP_CHECK(hipMemcpy(s->scal + 4, glob, sizeof(glob), hipMemcpyHostToDevice));
-        if (int rc = sparse_allreduce(s, s->scal + 4, 3)) return rc;
+        // and, in the buffer's fourth entry, of the ranks that read the noise as per point: every rank sees the same count, so a
+        // mixed group (psi2 summed over both readings) is refused on all of them alike, after the call's last collective
+        double h[4] = {glob[0], glob[1], glob[2], het ? 1.0 : 0.0};
+        HIP_CHECK(hipMemcpy(s->scal + 4, h, sizeof(h), hipMemcpyHostToDevice));
+        if (int rc = sparse_allreduce(s, s->scal + 4, 4)) return rc;
         HIP_CHECK(hipStreamSynchronize(st));
-        HIP_CHECK(hipMemcpy(glob, s->scal + 4, sizeof(glob), hipMemcpyDeviceToHost));
+        HIP_CHECK(hipMemcpy(h, s->scal + 4, sizeof(h), hipMemcpyDeviceToHost));
+        for (int i = 0; i < 3; ++i) glob[i] = h[i];
+        if (h[3] != 0.0 && h[3] != (double)s->world)
+            PART_FAIL("mi355gp_vardtc_inference_sum: %d of the %d ranks of this row-sharded context passed per-point noise and the others one "
+                      "variance; every rank must pass the same kind (a rank that holds ONE row states per-point noise by passing "
+                      "dnoise_rows_out)", (int)(h[3] + 0.5), s->world);
     }
     // psi0_n = Kdiag of the expression: one number, or by point (then the two sums of the record stand in for it)
     const double kdiag = s->diag_pt ? 0.0 : expression_kdiag(s->parts, s->terms);

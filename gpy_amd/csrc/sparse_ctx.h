@@ -188,7 +188,7 @@ int sparse_newpoints_var(mi355gp_sparse* s, NewPoints* q, const double* Winv, bo
 // the VarDTC evaluation of an opened call with the precisions and Kmm's jitter as given (mi355gp_vardtc_inference_sum, EPDTC)
 int vardtc_evaluate(mi355gp_sparse* s, const double* Z, const std::vector<double>& hbeta, double (&glob)[3], double kmm_jitter,
                     double* out_scalars, double* dtheta_out, double* dZ_out, double* wv_out, double* dnoise_rows_out,
-                    double* dLdm_out, double* stage_ms);
+                    double* dLdm_out, double* stage_ms, int per_point = -1);
 // ---- svgp.hip ------------------------------------------------------------------------------------------------------
 void svgp_release(mi355gp_sparse* s);      // frees the SVGP state (M-dependent: called by free_m)
 // ---- pep.hip -------------------------------------------------------------------------------------------------------

@@ -416,7 +416,10 @@ int mi355gp_vardtc_inference(mi355gp_sparse* s, int kind, int ard, const double*
  * kern/src/add.py:58-88, static.py:63-98,151-173; product terms are not accepted here), scalar OR per-point noise
  * variances (heteroscedastic precision: var_dtc.py:78-86,126-129,224-226,240-256,267-269; any Dy) and targets
  * R = Y - mean_function.f(X) uploaded by mi355gp_sparse_set_data (var_dtc.py:73-76,88-89).
- *   noise: noise_len == 1 or N (the rows of this context) noise VARIANCES
+ *   noise: noise_len == 1 or N (the rows of this context) noise VARIANCES.  N == 1: one variance for one row is the same model
+ *          either way and is read as scalar noise -- but on a row-sharded context every rank must take the same reading, so
+ *          there a rank that holds ONE row is read as per-point exactly when dnoise_rows_out is given; ranks that disagree
+ *          are refused, all alike, at the end of the call
  *   out_scalars: as above; [1] (dL/d noise variance) only for noise_len == 1
  *   dtheta_out: concatenation over the parts, each [variance, lengthscale(s)] ([variance] for White / Bias)
  *   dnoise_rows_out (N x Dy, required for noise_len == N): dL_dR per point and output column = what
