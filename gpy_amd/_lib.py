@@ -89,6 +89,7 @@ def build(force=False):
     srcs.append(os.path.join(_HERE, "..", "include", "mi355gp_psi_lin.h"))
     srcs.append(os.path.join(_HERE, "..", "include", "mi355gp_debug_psi_lin.h"))
     srcs.append(os.path.join(_HERE, "..", "include", "mi355gp_psi_ss.h"))
+    srcs.append(os.path.join(_HERE, "..", "include", "mi355gp_psi_gh.h"))
     srcs.append(os.path.join(_HERE, "..", "include", "mi355gp_sparse_missing.h"))
     srcs.append(os.path.join(_HERE, "..", "include", "mi355gp_debug_sparse_missing.h"))
     srcs.append(os.path.join(_HERE, "..", "include", "mi355gp_vargauss.h"))
@@ -257,6 +258,13 @@ PSI_SS_ABI = {
     "mi355gp_sparse_set_inputs_ss": [_vp, _dp, _dp, _dp, _i64, _ci],
     "mi355gp_vardtc_inference_ss": [_vp, _ci, _parts, _dp, _i64, _dp, _i64, _cd, _dp] + [_c_dp] * 7,
 }
+# include/mi355gp_psi_gh.h: psi-statistics by Gauss-Hermite quadrature (Matern52, Matern32, Exponential, ExpQuad), in its order
+PSI_GH_ABI = {
+    "mi355gp_gh_psi": [_ci, _ci, _ci, _dp, _dp, _i64, _dp, _dp, _i64, _ci, _dp, _dp, _ci] + [_c_dp] * 3,
+    "mi355gp_gh_psi_grad": [_ci, _ci, _ci, _dp, _dp, _i64, _dp, _dp, _i64, _ci, _dp, _dp, _ci] + [_c_dp] * 4 + [_ci, _cd] + [_c_dp] * 5,
+    "mi355gp_vardtc_inference_gh": [_vp, _ci, _parts, _dp, _i64, _dp, _i64, _cd, _dp, _dp, _ci, _dp] + [_c_dp] * 6,
+}
+GH_KINDS = ("rbf", "matern52", "matern32", "exponential")     # the kinds the quadrature takes
 # include/mi355gp_vargauss.h: the variational Gaussian approximation inside the Laplace session of an exact context, in its order
 # (tests/test_oracle_vargauss.py holds the table against that header's prototypes)
 VARGAUSS_ABI = {
@@ -328,7 +336,7 @@ def lib():
             build()
         L = ctypes.CDLL(LIB_PATH)
         for table in (ABI, DEBUG_LAUUM_ABI, DEBUG_TILEOPS_ABI, EPDTC_ABI, SPARSE_DIAG_ABI, SPARSE_COREG_ABI, DEBUG_SPARSE_COREG_ABI, PSI_LIN_ABI, DEBUG_PSI_LIN_ABI,
-                      PSI_SS_ABI, VARGAUSS_ABI, KRON_ABI, MISSING_ABI, DEBUG_MISSING_ABI, EIGH_ABI, KGPR_ABI):
+                      PSI_SS_ABI, PSI_GH_ABI, VARGAUSS_ABI, KRON_ABI, MISSING_ABI, DEBUG_MISSING_ABI, EIGH_ABI, KGPR_ABI):
             for name, argtypes in table.items():
                 getattr(L, name).argtypes = argtypes
         L.mi355gp_last_error.restype = L.mi355gp_version.restype = _str
@@ -858,6 +866,20 @@ class SparseContext(_Handle):
         res.update(trA=out[2], data_fit=out[3], dmu=dmu, dS=dS, dgamma=dg)
         return rc, res
 
+    def vardtc_gh(self, specs, Z, noise, degree=11, extra_jitter=0.0, want_dmu_dS=True, want_stage_ms=False):
+        """One evaluation with uncertain inputs and Gauss-Hermite psi-statistics of `degree` nodes (one Matern52, Matern32,
+        Exponential or ExpQuad part alone or with White parts, ONE noise variance; `mi355gp_vardtc_inference_gh`).
+        (info, dict(lml, dnoise, dtheta (concatenated), dZ, woodbury_vector, dmu, dS[, stage_ms]))"""
+        arr, keep, ntheta = make_parts(specs)
+        noise = f64(np.atleast_1d(noise)).ravel()
+        t, w = gh_rule(degree)
+        dmu = np.zeros((self.N, self.D)) if want_dmu_dS else None
+        dS = np.zeros((self.N, self.D)) if want_dmu_dS else None
+        rc, out, res = self._fit("mi355gp_vardtc_inference_gh", (len(specs), arr), ntheta, Z,
+                                 (noise, noise.size, float(extra_jitter), t, w, t.size), (dmu, dS), want_stage_ms)
+        res.update(trA=out[2], data_fit=out[3], dmu=dmu, dS=dS)
+        return rc, res
+
     def predict(self, specs, Xnew, full_cov=False, want_var=True):
         """(mu (M* x Dy), var (M* x 1) or cov) of the sparse posterior of the last call, on the device."""
         arr, keep, _ = make_parts(specs)
@@ -1203,6 +1225,52 @@ def ssrbf_psi_grad(variance, lengthscale, ARD, Z, mu, S, gamma, dL_dpsi0=None, d
     check(lib().mi355gp_ssrbf_psi_grad(device, *(args + (_opt(d0), _opt(d1), _opt(d2), dvar, dl, dZ, dmu, dS, dg))),
           "mi355gp_ssrbf_psi_grad")
     return dvar[0], dl, dZ, dmu, dS, dg
+
+
+def gh_rule(degree=11):
+    """(nodes t_i = sqrt(2) x_i, weights w_i = omega_i / sqrt(pi)) of `hermgauss(degree)` (reference `gaussherm.py:24-27`): the
+    expectation of f under N(m, s) is sum_i w_i f(m + t_i sqrt(s))."""
+    x, w = np.polynomial.hermite.hermgauss(int(degree))
+    return f64(x * np.sqrt(2.0)), f64(w / np.sqrt(np.pi))
+
+
+def _gh_args(kind, ARD, theta, Z, mu, S, degree):
+    Z, mu, S, theta = f64(Z), f64(mu), f64(S), f64(theta)
+    assert kind in GH_KINDS, "the quadrature takes %s kernels" % ", ".join(GH_KINDS)
+    assert mu.ndim == 2 and S.shape == mu.shape and Z.ndim == 2 and Z.shape[1] == mu.shape[1], "Z: M x D; mu, S: N x D"
+    t, w = gh_rule(degree) if np.isscalar(degree) else (f64(degree[0]), f64(degree[1]))
+    return (KIND_IDS[kind], int(bool(ARD)), theta, Z, Z.shape[0], mu, S, mu.shape[0], mu.shape[1], t, w, t.size)
+
+
+def gh_psi(kind, ARD, theta, Z, mu, S, degree=11, want_psi0=True, want_psi1=True, want_psi2=True, device=0):
+    """(psi0 (N), psi1 (N x M), psi2 (M x M)) of a stationary kernel under q(x_n) = N(mu_n, diag S_n) by Gauss-Hermite quadrature
+    with the same node in every dimension (reference `gaussherm.py:36-58`), on the device.  theta = [variance, lengthscale...];
+    `degree`: the number of nodes, or a (nodes, weights) pair."""
+    args = _gh_args(kind, ARD, theta, Z, mu, S, degree)
+    N, M = args[7], args[4]
+    p0 = np.empty(N) if want_psi0 else None
+    p1 = np.empty((N, M)) if want_psi1 else None
+    p2 = np.empty((M, M)) if want_psi2 else None
+    check(lib().mi355gp_gh_psi(device, *(args + (_opt(p0), _opt(p1), _opt(p2)))), "mi355gp_gh_psi")
+    return p0, p1, p2
+
+
+def gh_psi_grad(kind, ARD, theta, Z, mu, S, dL_dpsi0=None, dL_dpsi1=None, dL_dpsi2=None, degree=11, rank=None, device=0):
+    """(dtheta, dZ, dmu, dS) of sum dL_dpsi0 psi0 + sum dL_dpsi1 * psi1 + sum dL_dpsi2 * psi2 (reference `gaussherm.py:60-101`), on
+    the device.  `rank` = (beta, R (N x Dy), v (M x Dy)) gives dL_dpsi1 = beta R v^T without forming it."""
+    args = _gh_args(kind, ARD, theta, Z, mu, S, degree)
+    N, M, D = args[7], args[4], args[8]
+    d0 = None if dL_dpsi0 is None else f64(np.broadcast_to(np.asarray(dL_dpsi0, dtype=np.float64).ravel(), (N,)))
+    d1 = None if dL_dpsi1 is None else f64(dL_dpsi1)
+    d2 = None if dL_dpsi2 is None else f64(dL_dpsi2)
+    assert d1 is None or d1.shape == (N, M), "dL_dpsi1 must be N x M"
+    assert d2 is None or d2.shape == (M, M), "dL_dpsi2 must be M x M (per data point: not implemented)"
+    beta, R, v = (0.0, None, None) if rank is None else (float(rank[0]), f64(rank[1]), f64(rank[2]))
+    assert rank is None or (R.shape[0] == N and v.shape == (M, R.shape[1])), "rank = (beta, R (N x Dy), v (M x Dy))"
+    dth, dZ, dmu, dS = np.zeros(args[2].size), np.zeros((M, D)), np.zeros((N, D)), np.zeros((N, D))
+    check(lib().mi355gp_gh_psi_grad(device, *(args + (_opt(d0), _opt(d1), _opt(R), _opt(v), 0 if R is None else R.shape[1], beta,
+                                                      _opt(d2), _opt(dth), _opt(dZ), _opt(dmu), _opt(dS)))), "mi355gp_gh_psi_grad")
+    return dth, dZ, dmu, dS
 
 
 def potrf(A, device=0):

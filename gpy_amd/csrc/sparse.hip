@@ -24,11 +24,13 @@
 #include "../../include/mi355gp_debug_sparse_coreg.h"
 #include "../../include/mi355gp_psi_lin.h"
 #include "../../include/mi355gp_psi_ss.h"
+#include "../../include/mi355gp_psi_gh.h"
 #include "../../include/mi355gp_sparse_missing.h"
 #include "internal.h"
 #include "parts.h"
 #include "psi.h"
 #include "psi_ss.h"
+#include "psi_gh.h"
 #include "psi_missing.h"
 #include "sparse_ctx.h"
 
@@ -2043,6 +2045,132 @@ int mi355gp_vardtc_inference_ss(mi355gp_sparse* s, int nparts, const mi355gp_par
     s->beta_scalar = beta;
     return vardtc_uncertain_rbf(s, irbf, true, Z, beta, extra_jitter, out_scalars, dtheta_out, dZ_out, wv_out, dmu_out, dS_out, dgamma_out,
                                 stage_ms);
+}
+
+// VarDTC with uncertain inputs whose psi-statistics come from Gauss-Hermite quadrature (include/mi355gp_psi_gh.h; psi_gh.hip):
+// the phases of mi355gp_vardtc_inference_uncertain with k_gh_stats in pass 1 and k_gh_grad in pass 2.  One stationary part (ExpQuad,
+// Matern52, Matern32, Exponential) alone or summed with White parts, one noise variance.  psi0_n = (sum of the variances) sum_i w_i;
+// dL_dpsi1 = beta R v^T in rank form, dL_dpsi2 = beta sym(Q2), so D2 = 2 beta sym(Q2).
+int mi355gp_vardtc_inference_gh(mi355gp_sparse* s, int nparts, const mi355gp_part* parts, const double* Z, int64_t M,
+                                const double* noise, int64_t noise_len, double extra_jitter, const double* nodes,
+                                const double* weights, int H, double* out_scalars, double* dtheta_out, double* dZ_out,
+                                double* wv_out, double* dmu_out, double* dS_out, double* stage_ms) {
+    const char* where = "mi355gp_vardtc_inference_gh";
+    ARG_CHECK(s && s->n > 0, "mi355gp_vardtc_inference_gh: set_data first");
+    ARG_CHECK(parts && Z && M > 0 && out_scalars && noise && nparts >= 1 && nodes && weights, "mi355gp_vardtc_inference_gh: bad arguments");
+    ARG_CHECK(!sharded(s), "mi355gp_vardtc_inference_gh: a row-sharded context is not supported with uncertain inputs");
+    ARG_CHECK(s->dSvar, "mi355gp_vardtc_inference_gh: no input variances; call mi355gp_sparse_set_input_variance after set_data");
+    ARG_CHECK(!s->dGam, "mi355gp_vardtc_inference_gh: the context holds slab probabilities (mi355gp_sparse_set_binary_prob); spike-and-slab "
+                        "inputs have no quadrature statistics; clear them with a NULL gamma");
+    ARG_CHECK(!s->missing, "mi355gp_vardtc_inference_gh: the context holds output groups (mi355gp_sparse_set_output_groups); missing data "
+                           "is not implemented with quadrature statistics; clear them with G = 0");
+    if (noise_len != 1)
+        PART_FAIL("%s: per-point noise (%lld variances) is not supported with uncertain inputs; pass one noise variance", where,
+                  (long long)noise_len);
+    GhQuad q;
+    if (int rc = gh_quad(where, nodes, weights, H, &q)) return rc;
+    const double wsum = q.wsum;
+    int ist = -1;
+    for (int i = 0; i < nparts; ++i) {
+        if (parts[i].term != 0) PART_FAIL("%s: part %d is a factor of a product; products have no psi statistics here", where, i);
+        if (parts[i].kind == MI355GP_WHITE) continue;
+        if (!kind_in(parts[i].kind, KS_STATIONARY))
+            PART_FAIL("%s: part %d is a %s (kind %d) part; the quadrature takes one ExpQuad, Matern52, Matern32 or Exponential part and "
+                      "White parts only (the cross terms of a sum with Bias, Linear or a second kernel are not implemented)", where, i,
+                      kind_name(parts[i].kind), parts[i].kind);
+        if (ist >= 0)
+            PART_FAIL("%s: parts %d (%s) and %d (%s) are both input-dependent; the quadrature takes ONE such part (psi2 of two has cross "
+                      "terms)", where, ist, kind_name(parts[ist].kind), i, kind_name(parts[i].kind));
+        ist = i;
+    }
+    if (ist < 0) PART_FAIL("%s: no stationary part; the quadrature takes one ExpQuad, Matern52, Matern32 or Exponential part", where);
+    if (s->D > PSI_QMAX) PART_FAIL("%s: the psi-statistics kernels take at most 64 input dimensions", where);
+    if (M > PSI_MMAX) PART_FAIL("%s: the psi-statistics kernels take at most 65535 inducing points", where);
+    EngineShared gate(s->device);
+    if (int rc = sparse_open(s, nparts, parts, M)) return rc;
+    const double beta = 1.0 / fmax(noise[0], 1e-8);
+    s->beta_scalar = beta;
+    s->mfma_prof.on = false;
+    hipStream_t st = s->st;
+    const long n = s->n, m = s->m, mp = s->mp, mp64 = round_up(m, GH_MT);
+    const int D = s->D, Dy = s->Dy;
+    const SPart& sp = s->parts[(size_t)ist];
+    const long chunk = n < PSI_CHUNK ? n : PSI_CHUNK, nbmax = (chunk + GH_RB - 1) / GH_RB;
+    DevBuf dZt, dTw, scratch, dMuO, dSO, Zpart, Zs, recpart, rec;
+    HIP_CHECK(dZt.alloc((size_t)mp64 * D));
+    HIP_CHECK(dTw.alloc(2 * H));
+    HIP_CHECK(hipMemcpyAsync(dTw, q.tw, sizeof(double) * 2 * H, hipMemcpyHostToDevice, s->st));
+    HIP_CHECK(scratch.alloc(gh_grad_scratch(chunk, mp64, D)));
+    HIP_CHECK(dMuO.alloc(n * D));
+    HIP_CHECK(dSO.alloc(n * D));
+    HIP_CHECK(Zpart.alloc((size_t)nbmax * D * mp64));
+    HIP_CHECK(Zs.alloc((size_t)D * mp64));
+    HIP_CHECK(recpart.alloc((size_t)nbmax * (1 + D)));
+    HIP_CHECK(rec.alloc(1 + D));
+    HIP_CHECK(hipMemsetAsync(Zpart, 0, sizeof(double) * nbmax * D * mp64, st));       // the kernel writes columns < m only
+    if (int rc = sparse_start(s, Z, &beta, 1)) return rc;
+    const GhKern gk{sp.kp.kind, D, sp.kp.variance, sp.dIl, dZt, m, mp64, dTw, H};
+    launch_gh_zt(st, s->dZ, sp.dIl, m, mp64, D, dZt);
+    // pass 1 (uncertain_pass1 with the quadrature in the psi slots)
+    auto rebuild_kmm = [&]() { build_kmm(s, s->Lm, s->T1, 1e-8 + extra_jitter, /*lower_only=*/1, st); };
+    rebuild_kmm();
+    if (int rc = potrf_checked(st, s->Lm, s->Xm, s->Tm, nullptr, mp, &s->ws, &s->h_info[0], rebuild_kmm)) return rc;
+    HIP_CHECK(hipMemsetAsync(s->psi1Y, 0, sizeof(double) * mp * Dy, st));
+    HIP_CHECK(hipMemsetAsync(s->psi2, 0, sizeof(double) * mp * mp, st));
+    int nch = 0;
+    for (long r0 = 0; r0 < n; r0 += PSI_CHUNK, ++nch) {
+        const long rc = (n - r0 < PSI_CHUNK) ? (n - r0) : PSI_CHUNK;
+        HIP_CHECK(hipMemsetAsync(s->Kfu, 0, sizeof(double) * rc * mp, st));          // psi1 writes columns < m only
+        const int ns = launch_gh_stats(st, gk, s->dX + r0 * D, s->dSvar + r0 * D, rc, s->Kfu, mp, s->psi2part);
+        const int nsc = launch_colreduce_multi(st, s->Kfu, mp, rc, mp, s->dV + r0 * Dy, Dy, 1, Dy, 0, s->colPart);
+        launch_sum_splits(st, s->colPart, mp * Dy, nsc, 1, s->psi1Y);                 // psi1^T V += psi1_chunk^T V_chunk
+        launch_psi2_combine(st, s->psi2part, mp64, m, ns, nch > 0, s->psi2, mp);
+    }
+    HIP_CHECK(hipEventRecord(s->ev[1], st));
+    if (int rc = sparse_mm_block(s, false, beta, 0)) return rc;
+    // pass 2: dL_dpsi2 = beta sym(Q2), so E = D2 = 2 beta sym(Q2) (zero outside m x m); dL_dpsi1 = beta R v^T
+    hipLaunchKernelGGL(k_sym_scaled, grid2d(mp, mp), dim3(256), 0, st, s->Q2, mp, m, 2.0 * beta, s->E);
+    nch = 0;
+    for (long r0 = 0; r0 < n; r0 += PSI_CHUNK, ++nch) {
+        const long rc = (n - r0 < PSI_CHUNK) ? (n - r0) : PSI_CHUNK;
+        const PsiRank rk{s->dY + r0 * Dy, s->vvec, Dy, beta};
+        const int nb = launch_gh_grad(st, gk, s->dX + r0 * D, s->dSvar + r0 * D, rc, nullptr, rk, s->E, mp, scratch,
+                                      dMuO + r0 * D, dSO + r0 * D, Zpart, recpart);
+        launch_sum_splits(st, Zpart, D * mp64, nb, nch > 0, Zs);
+        launch_sum_splits(st, recpart, 1 + D, nb, nch > 0, rec);
+    }
+    sparse_kmm_gradients(s);
+    HIP_CHECK(hipEventRecord(s->ev[3], st));
+    // ---- small results to the host -----------------------------------------------------------------------------------------
+    KernGrads kg;
+    std::vector<double> zs((size_t)D * mp64), hrec((size_t)(1 + D));
+    double scal[8];
+    if (int rc = sparse_fetch_gradients(s, false, &kg)) return rc;
+    HIP_CHECK(hipMemcpyAsync(zs.data(), Zs, sizeof(double) * zs.size(), hipMemcpyDeviceToHost, st));
+    HIP_CHECK(hipMemcpyAsync(hrec.data(), rec, sizeof(double) * hrec.size(), hipMemcpyDeviceToHost, st));
+    HIP_CHECK(hipMemcpyAsync(scal, s->scal, sizeof(double) * 4, hipMemcpyDeviceToHost, st));
+    if (wv_out) HIP_CHECK(hipMemcpyAsync(wv_out, s->vvec, sizeof(double) * m * Dy, hipMemcpyDeviceToHost, st));
+    if (dmu_out) HIP_CHECK(hipMemcpyAsync(dmu_out, dMuO, sizeof(double) * n * D, hipMemcpyDeviceToHost, st));
+    if (dS_out) HIP_CHECK(hipMemcpyAsync(dS_out, dSO, sizeof(double) * n * D, hipMemcpyDeviceToHost, st));
+    if (int rc = sparse_finish(s, 3, stage_ms)) return rc;
+    const double psi0sum = (double)n * wsum * expression_kdiag(s->parts, s->terms);
+    const double psi0[2] = {beta * psi0sum, beta * beta * psi0sum};
+    vardtc_scalars(s, scal, 0.0, beta, nullptr, out_scalars, psi0);
+    // on top of the Kmm record of the stationary part: sum G K and the lengthscale sums L_q (part_dtheta: dl = -rec / l)
+    double* ab = kg.gmm.data() + (size_t)ist * rec_doubles(s);
+    ab[0] += hrec[0];
+    for (int qd = 0; qd < D; ++qd) {
+        ab[(size_t)(qd / 32) * GP_STRIDE + 2 + (qd % 32)] += hrec[(size_t)(1 + qd)];
+        ab[1] += hrec[(size_t)(1 + qd)];
+    }
+    // dL_dpsi0 = -Dy beta / 2 per row, dpsi0 / dvariance = sum_i w_i for every part
+    sparse_assemble_gradients(s, kg, -0.5 * Dy * beta * (double)n * wsum, dtheta_out, dZ_out);
+    if (dZ_out)
+        for (long j = 0; j < m; ++j)
+            for (int qd = 0; qd < D; ++qd) dZ_out[j * D + qd] -= sp.inv_ls[(size_t)qd] * zs[(size_t)qd * mp64 + j];
+    s->have_result = true;
+    s->uncertain_result = true;
+    return 0;
 }
 
 // ---- VarDTC with uncertain inputs and MISSING entries of Y (include/mi355gp_sparse_missing.h) ----------------------------------

@@ -389,7 +389,53 @@ class GridRBF(object):
         return self.dKdLen_of_r(self._scaled_dist(X, X2), dimension, lengthscale)
 
 
-class ExpQuad(Stationary):
+class GaussHermitePsi(object):
+    """psi-statistics by Gauss-Hermite quadrature for the stationary kernels without a closed form (reference `kern.py:60-61`:
+    every kernel's default `PSICOMP_GH`; `psi_comp/gaussherm.py`; C-ABI mi355gp_gh_psi / _grad, csrc/psi_gh.hip).  `degree` nodes,
+    11 as in the reference, and the SAME node in every input dimension -- the reference's rule, which for input_dim > 1 is not a
+    tensor-product quadrature.  qX is a `NormalPosterior`.  `RBF` keeps its closed form."""
+
+    def _gh(self, Z, qX):
+        if isinstance(qX, SpikeAndSlabPosterior):
+            raise NotImplementedError("%s: a SpikeAndSlabPosterior has no Gauss-Hermite psi-statistics (one RBF kernel has the "
+                                      "closed form)" % type(self).__name__)
+        return self.kind, self.ARD, self._theta(), self._slice_X(Z), self._slice_X(qX.mean), self._slice_X(qX.variance)
+
+    def psi0(self, Z, qX, degree=11):
+        return _lib.gh_psi(*self._gh(Z, qX), degree=degree, want_psi1=False, want_psi2=False, device=self.device)[0]
+
+    def psi1(self, Z, qX, degree=11):
+        return _lib.gh_psi(*self._gh(Z, qX), degree=degree, want_psi0=False, want_psi2=False, device=self.device)[1]
+
+    def psi2(self, Z, qX, degree=11):
+        return _lib.gh_psi(*self._gh(Z, qX), degree=degree, want_psi0=False, want_psi1=False, device=self.device)[2]
+
+    def _gh_grad(self, dL_dpsi0, dL_dpsi1, dL_dpsi2, Z, qX, degree):
+        if dL_dpsi2 is not None and np.ndim(dL_dpsi2) != 2:
+            raise NotImplementedError("%s psi gradients take dL_dpsi2 as M x M (the summed psi2), not per data point"
+                                      % type(self).__name__)
+        return _lib.gh_psi_grad(*self._gh(Z, qX), dL_dpsi0=dL_dpsi0, dL_dpsi1=dL_dpsi1, dL_dpsi2=dL_dpsi2, degree=degree,
+                                device=self.device)
+
+    def _gh_scatter(self, g, like):
+        if g.shape == np.shape(like):
+            return g
+        full = np.zeros(np.shape(like))
+        full[:, self.active_dims] = g
+        return full
+
+    def update_gradients_expectations(self, dL_dpsi0, dL_dpsi1, dL_dpsi2, Z, qX, degree=11):
+        self._install_gradients(self._gh_grad(dL_dpsi0, dL_dpsi1, dL_dpsi2, Z, qX, degree)[0])
+
+    def gradients_Z_expectations(self, dL_dpsi0, dL_dpsi1, dL_dpsi2, Z, qX, degree=11):
+        return self._gh_scatter(self._gh_grad(dL_dpsi0, dL_dpsi1, dL_dpsi2, Z, qX, degree)[1], Z)
+
+    def gradients_qX_expectations(self, dL_dpsi0, dL_dpsi1, dL_dpsi2, Z, qX, degree=11):
+        g = self._gh_grad(dL_dpsi0, dL_dpsi1, dL_dpsi2, Z, qX, degree)
+        return tuple(self._gh_scatter(x, qX.mean) for x in g[2:])     # (dmean, dvariance)
+
+
+class ExpQuad(GaussHermitePsi, Stationary):
     """The exponentiated quadratic k(r) = variance * exp(-r^2/2) (reference `stationary.py:623-662`): the same
     function as `RBF` without the psi-statistics / `inv_l` extras; serialises as "GPy.kern.ExpQuad"."""
     kind = "rbf"
@@ -399,7 +445,7 @@ class ExpQuad(Stationary):
         super(ExpQuad, self).__init__(input_dim, variance, lengthscale, ARD, active_dims, name, **kw)
 
 
-class Matern52(Stationary):
+class Matern52(GaussHermitePsi, Stationary):
     """k(r) = variance (1 + sqrt5 r + 5/3 r^2) exp(-sqrt5 r)  (reference `stationary.py:585-589`)."""
     kind = "matern52"
     _gpy_class = "GPy.kern.Matern52"
@@ -408,7 +454,7 @@ class Matern52(Stationary):
         super(Matern52, self).__init__(input_dim, variance, lengthscale, ARD, active_dims, name, **kw)
 
 
-class Matern32(Stationary):
+class Matern32(GaussHermitePsi, Stationary):
     """k(r) = variance (1 + sqrt3 r) exp(-sqrt3 r)  (reference `stationary.py:488-492`)."""
     kind = "matern32"
     _gpy_class = "GPy.kern.Matern32"
@@ -417,7 +463,7 @@ class Matern32(Stationary):
         super(Matern32, self).__init__(input_dim, variance, lengthscale, ARD, active_dims, name, **kw)
 
 
-class Exponential(Stationary):
+class Exponential(GaussHermitePsi, Stationary):
     """k(r) = variance exp(-r)  (reference `stationary.py:382-386`)."""
     kind = "exponential"
     _gpy_class = "GPy.kern.Exponential"

@@ -17,6 +17,10 @@ and one noise variance; `grad_dict` then has the reference's keys `dL_dpsi0 / dL
 `dL_dKdiag / dL_dKnm`, and `fused` also carries the gradients with respect to the inputs' means and variances.
 `VarDTC(psi_lin_bias=True)` (and the models' keyword of the same name) takes one RBF or Linear part with Bias and White parts
 there (`mi355gp_sparse_set_psi_lin_bias`, include/mi355gp_psi_lin.h); made without it the classes refuse those as before.
+`VarDTC(psi_gh=True)` (or `psi_gh=<degree>`) takes one Matern52, Matern32, Exponential / OU or ExpQuad part alone or with White
+parts there, on Gauss-Hermite psi-statistics with the same node in every dimension (`mi355gp_vardtc_inference_gh`,
+include/mi355gp_psi_gh.h, csrc/psi_gh.hip); Bias, Linear or RBF beside such a part, spike-and-slab inputs, missing data and
+prediction at uncertain new points are refused by name, and made without the keyword the classes refuse those kernels as before.
 
 Multi-output kernels: `VarDTC(coregionalize=True)` takes Coregionalize factors with certain inputs -- the `ICM` / `LCM` kernels of
 `util.multioutput` with a `MixedNoise` likelihood -- and `SparseGPCoregionalizedRegression` (reference
@@ -32,7 +36,7 @@ import numpy as np
 
 from . import _lib
 from .inference import LatentFunctionInference
-from .kern import RBF, Add, Bias, Coregionalize, Linear, Prod, White, diag_depends_on_point, exact_only_leaves, has_coregionalize
+from .kern import RBF, Add, Bias, GaussHermitePsi, Coregionalize, Linear, Prod, White, diag_depends_on_point, exact_only_leaves, has_coregionalize
 from .lazy import ArrayIdentity, LazyMM, LazyNM, LazyPsi1, freeze, kernel_signature
 from .likelihoods import Gaussian
 from .linalg import LinAlgError, jitter_ladder
@@ -59,6 +63,7 @@ class SparsePosterior(SessionPosterior):
     (C-ABI `mi355gp_sparse_predict`) while the posterior is the context's latest result."""
 
     psi_lin_bias = False        # made by an inference class with psi_lin_bias=True: the host fallback asks `Add` for the same
+    psi_gh = 0                  # made by `VarDTC(psi_gh=...)` from quadrature statistics: no prediction at uncertain new points
 
     def __init__(self, woodbury_inv, woodbury_vector, K, K_chol, device=None):
         self.woodbury_inv, self.woodbury_vector, self.K, self.K_chol = woodbury_inv, woodbury_vector, K, K_chol
@@ -76,6 +81,9 @@ class SparsePosterior(SessionPosterior):
         if isinstance(Xnew, SpikeAndSlabPosterior):
             raise NotImplementedError("prediction at spike-and-slab new points (a SpikeAndSlabPosterior Xnew) is not implemented; "
                                       "pass their means, or a NormalPosterior")
+        if isinstance(Xnew, NormalPosterior) and self.psi_gh:
+            raise NotImplementedError("prediction at uncertain new points (a NormalPosterior Xnew) is not implemented for a fit on "
+                                      "Gauss-Hermite psi-statistics (psi_gh): it needs a per-row psi2n contraction; pass their means")
         if isinstance(Xnew, NormalPosterior):
             return self._raw_predict_uncertain(kern, Xnew, pred_var, full_cov, dev if live else None)
         if live:
@@ -312,11 +320,18 @@ class VarDTC(SparseSession):
     _groups_of = None                                                # the uploaded Y (its identity) the context's output groups belong to
     _groups_mask = None                                              # ... and the (group_of_output, W) that were uploaded with it
 
-    def __init__(self, device=0, maxtries=5, linear=False, psi_lin_bias=False, coregionalize=False):
+    def __init__(self, device=0, maxtries=5, linear=False, psi_lin_bias=False, coregionalize=False, psi_gh=False):
         """`coregionalize=True`: the kernel may hold Coregionalize factors (`util.multioutput.ICM` / `LCM`) with certain inputs;
-        the context is told so (`mi355gp_sparse_set_coregionalize`).  Made without it the class refuses them by name, as before."""
+        the context is told so (`mi355gp_sparse_set_coregionalize`).  Made without it the class refuses them by name, as before.
+        `psi_gh=True` (11 nodes, the reference's default) or `psi_gh=<degree>`: with uncertain inputs, one Matern52, Matern32,
+        Exponential / OU or ExpQuad part alone or with White parts is fitted on Gauss-Hermite psi-statistics
+        (`mi355gp_vardtc_inference_gh`; the same node in every dimension, reference `psi_comp/gaussherm.py`).  Made without it the
+        class refuses those kernels under uncertain inputs, as before."""
         super(VarDTC, self).__init__(device=device, maxtries=maxtries, linear=linear, psi_lin_bias=psi_lin_bias)
         self.coregionalize = bool(coregionalize)
+        self.psi_gh = 11 if psi_gh is True else int(psi_gh)
+        if not 0 <= self.psi_gh <= 32:
+            raise ValueError("psi_gh: the number of Gauss-Hermite nodes must be between 1 and 32, got %r" % (psi_gh,))
 
     def to_dict(self):
         return {"class": "GPy.inference.latent_function_inference.var_dtc.VarDTC"}
@@ -361,8 +376,24 @@ class VarDTC(SparseSession):
             raise ValueError("Mean function not implemented with uncertain inputs or heteroscedasticity")
         ss = isinstance(qX, SpikeAndSlabPosterior)                     # -> mi355gp_vardtc_inference_ss: one RBF and White parts
         parts = kern.parts if isinstance(kern, Add) else [kern]
+        gh = self.psi_gh and [p for p in parts if isinstance(p, GaussHermitePsi)]
+        if gh:                                                         # -> mi355gp_vardtc_inference_gh: one such part and White parts
+            if ss:
+                raise NotImplementedError("spike-and-slab inputs (a SpikeAndSlabPosterior) have no Gauss-Hermite psi-statistics; "
+                                          "part %r (%s) needs a NormalPosterior" % (gh[0].name, type(gh[0]).__name__))
+            for p in parts:
+                if not isinstance(p, (GaussHermitePsi, White)):
+                    what = type(p).__name__ if p.is_leaf else "%s of %s" % (type(p).__name__, ", ".join(type(f).__name__ for f in p.leaves()))
+                    raise NotImplementedError("uncertain inputs (psi_gh): the part %r (%s) beside the quadrature part %r (%s) is not "
+                                              "covered: the reference's cross terms are not implemented; one Matern52, Matern32, "
+                                              "Exponential or ExpQuad part and White parts are"
+                                              % (p.name, what, gh[0].name, type(gh[0]).__name__))
+            if len(gh) != 1:
+                raise NotImplementedError("uncertain inputs (psi_gh): exactly one input-dependent part is covered, got %d (%s); "
+                                          "psi2 of two has cross terms"
+                                          % (len(gh), ", ".join("%r: %s" % (p.name, type(p).__name__) for p in gh)))
         covered = (RBF, Linear, Bias, White) if self.psi_lin_bias and not ss else (RBF, White)
-        for p in parts:
+        for p in ([] if gh else parts):
             if type(p) not in covered:
                 what = type(p).__name__ if p.is_leaf else "%s of %s" % (type(p).__name__, ", ".join(type(f).__name__ for f in p.leaves()))
                 if ss:
@@ -375,7 +406,7 @@ class VarDTC(SparseSession):
                 raise NotImplementedError("uncertain inputs: the part %r (%s) has no psi-statistics on the MI355X sparse path; "
                                           "one RBF kernel and White parts are covered (one RBF or Linear kernel with Bias and "
                                           "White parts: make the inference class with psi_lin_bias=True)" % (p.name, what))
-        rbfs = [p for p in parts if isinstance(p, (RBF, Linear))]
+        rbfs = gh or [p for p in parts if isinstance(p, (RBF, Linear))]
         if len(rbfs) != 1 and self.psi_lin_bias and not ss:
             raise NotImplementedError("uncertain inputs: exactly one input-dependent part (RBF or Linear) is covered, got %d (%s); "
                                       "psi2 of two has cross terms that need E[k1 k2^T]"
@@ -391,7 +422,10 @@ class VarDTC(SparseSession):
         R = _lib.f64(Y)
         self._refuse_sharded("uncertain inputs are not supported by a row-sharded sparse context")
         specs = kern.part_specs()
-        if ss:
+        if gh:
+            self._ensure_uncertain(mu, S, R)
+            call = lambda *a, **kw: self._ctx.vardtc_gh(*a, degree=self.psi_gh, **kw)
+        elif ss:
             self._ensure_ss(mu, S, kern._slice_X(qX.binary_prob), R)
             call = self._ctx.vardtc_ss
         else:
@@ -400,6 +434,7 @@ class VarDTC(SparseSession):
         r = self._run(kern, lambda extra: call(specs, Zs, noise, extra_jitter=extra, want_stage_ms=self.collect_stage_ms), Z)
         M, N = Zs.shape[0], mu.shape[0]
         post, dL_dKmm = self._posterior(kern, M, r["woodbury_vector"])
+        post.psi_gh = self.psi_gh if gh else 0
         beta = float(1.0 / np.fmax(noise, self.const_jitter)[0])
         grad_dict = {"dL_dKmm": dL_dKmm,
                      "dL_dpsi0": -0.5 * Y.shape[1] * beta * np.ones(N),             # var_dtc.py:218
@@ -425,9 +460,9 @@ class VarDTC(SparseSession):
         if not isinstance(qX, NormalPosterior):
             raise NotImplementedError("missing_data: certain inputs (the reference's SparseGPMiniBatch) are not implemented on the "
                                       "MI355X path; missing data is handled for a NormalPosterior X (BayesianGPLVMMiniBatch)")
-        if self.psi_lin_bias or self.linear or self.coregionalize:
-            raise NotImplementedError("missing_data: an inference class made with psi_lin_bias, linear or coregionalize is not "
-                                      "implemented with missing data; make it as VarDTC()")
+        if self.psi_lin_bias or self.linear or self.coregionalize or self.psi_gh:
+            raise NotImplementedError("missing_data: an inference class made with psi_lin_bias, linear, coregionalize or psi_gh "
+                                      "(Gauss-Hermite psi-statistics) is not implemented with missing data; make it as VarDTC()")
         if mean_function is not None:
             raise ValueError("Mean function not implemented with uncertain inputs or heteroscedasticity")
         parts = kern.parts if isinstance(kern, Add) else [kern]
@@ -646,10 +681,11 @@ class SparseGP(PredictionCallers, Parameterized):
 class SparseGPRegression(SparseGP):
     """(reference `GPy/models/sparse_gp_regression.py:20-60`): Z defaults to a random subset of X.  `linear=True`: the kernel
     may hold Linear leaves (`VarDTC(linear=True)`).  `psi_lin_bias=True`: with `X_variance`, one RBF or Linear part with Bias
-    and White parts (`VarDTC(psi_lin_bias=True)`; implies `linear`)."""
+    and White parts (`VarDTC(psi_lin_bias=True)`; implies `linear`).  `psi_gh=True` or `psi_gh=<degree>`: with `X_variance`, one
+    Matern52, Matern32, Exponential / OU or ExpQuad part with White parts, on Gauss-Hermite psi-statistics (`VarDTC(psi_gh=...)`)."""
 
     def __init__(self, X, Y, kernel=None, Z=None, num_inducing=10, noise_var=1., device=0, seed=None, mean_function=None,
-                 X_variance=None, linear=False, psi_lin_bias=False):
+                 X_variance=None, linear=False, psi_lin_bias=False, psi_gh=False):
         refuse_spike_and_slab(X, "SparseGPRegression")
         X = np.asarray(X, dtype=np.float64)
         if kernel is None:
@@ -658,8 +694,9 @@ class SparseGPRegression(SparseGP):
             i = np.random.default_rng(seed).permutation(X.shape[0])[:min(num_inducing, X.shape[0])]
             Z = X[i].copy()
         super(SparseGPRegression, self).__init__(X, Y, Z, kernel, Gaussian(variance=noise_var),
-                                                 inference_method=(VarDTC(device=device, psi_lin_bias=True) if psi_lin_bias else
-                                                                   VarDTC(device=device, linear=True) if linear else None),
+                                                 inference_method=(VarDTC(device=device, linear=linear, psi_lin_bias=psi_lin_bias,
+                                                                          psi_gh=psi_gh)
+                                                                   if linear or psi_lin_bias or psi_gh else None),
                                                  name="sparse_gp", device=device, mean_function=mean_function,
                                                  X_variance=X_variance)
 
