@@ -21,6 +21,7 @@ from .models import (GP, GPClassification, GPCoregionalizedRegression, GPHeteros
                      GPVariationalGaussianApproximation)
 from .posterior import PosteriorEP, PosteriorExact, StudentTPosterior
 from .sparse import SSGPLVM, BayesianGPLVM, BayesianGPLVMMiniBatch, SparseGP, SparseGPCoregionalizedRegression, SparseGPRegression, VarDTC
+from .gplvm import GPLVM
 from .pep import FITC, PEP
 from .epdtc import EPDTC, SparseGPClassification
 from .svgp import SVGPModel as SVGP
@@ -28,7 +29,7 @@ from .svgp import SVGPPosterior
 from .variational import NormalPosterior, NormalPrior, SpikeAndSlabPosterior, SpikeAndSlabPrior
 
 __all__ = ["RBF", "OU", "ExpQuad", "HeteroscedasticGaussian", "StudentTPosterior", "Matern52", "Matern32", "Exponential", "RatQuad", "Cosine", "Sinc", "ExpQuadCosine", "StdPeriodic", "Coregionalize", "Linear", "MLP", "Poly", "MixedNoise", "Stationary", "White", "Bias", "Add", "Prod", "Gaussian", "ExactGaussianInference", "ExactStudentTInference",
-           "PosteriorExact", "GP", "GPRegression", "GPHeteroscedasticRegression", "GPCoregionalizedRegression", "Laplace", "LaplacePosterior", "EP", "PosteriorEP", "Bernoulli", "StudentT", "Poisson", "GPClassification", "VarDTC", "SparseGP", "SparseGPRegression", "SparseGPCoregionalizedRegression", "SVGP", "SVGPPosterior", "NormalPosterior", "NormalPrior", "SpikeAndSlabPosterior", "SpikeAndSlabPrior", "BayesianGPLVM", "BayesianGPLVMMiniBatch", "SSGPLVM", "FITC", "PEP", "EPDTC", "SparseGPClassification", "VarGauss", "VarGaussPosterior", "GPVariationalGaussianApproximation", "GaussianGridInference", "GridPosterior", "GpGrid", "GPRegressionGrid", "GPKroneckerGaussianRegression", "MI355GPError", "build", "device_count"]
+           "PosteriorExact", "GP", "GPRegression", "GPHeteroscedasticRegression", "GPCoregionalizedRegression", "Laplace", "LaplacePosterior", "EP", "PosteriorEP", "Bernoulli", "StudentT", "Poisson", "GPClassification", "VarDTC", "SparseGP", "SparseGPRegression", "SparseGPCoregionalizedRegression", "SVGP", "SVGPPosterior", "NormalPosterior", "NormalPrior", "SpikeAndSlabPosterior", "SpikeAndSlabPrior", "BayesianGPLVM", "BayesianGPLVMMiniBatch", "SSGPLVM", "GPLVM", "FITC", "PEP", "EPDTC", "SparseGPClassification", "VarGauss", "VarGaussPosterior", "GPVariationalGaussianApproximation", "GaussianGridInference", "GridPosterior", "GpGrid", "GPRegressionGrid", "GPKroneckerGaussianRegression", "MI355GPError", "build", "device_count"]
 
 # GPy's import paths, so that `import gpy_amd as GPy` reads like the reference on this path:
 #   GPy.kern.RBF, GPy.likelihoods.Gaussian, GPy.models.GPRegression / SparseGPRegression / GPHeteroscedasticRegression,
@@ -41,7 +42,7 @@ __all__ = ["RBF", "OU", "ExpQuad", "HeteroscedasticGaussian", "StudentTPosterior
 #   GPy.models.GPKroneckerGaussianRegression, GPy.models.GPRegressionGrid, GPy.core.GpGrid, GPy.inference.latent_function_inference.GaussianGridInference (and
 #   .gaussian_grid_inference.GaussianGridInference, .grid_posterior.GridPosterior), GPy.kern.GridRBF,
 #   GPy.util.choleskies, GPy.models.BayesianGPLVM, GPy.models.BayesianGPLVMMiniBatch (and .bayesian_gplvm_minibatch), GPy.util.initialization.initialize_latent,
-#   GPy.models.SparseGPCoregionalizedRegression, GPy.models.ss_gplvm.SSGPLVM,
+#   GPy.models.SparseGPCoregionalizedRegression, GPy.models.ss_gplvm.SSGPLVM, GPy.models.gplvm.GPLVM,
 #   GPy.core.parameterization.variational.SpikeAndSlabPosterior / SpikeAndSlabPrior
 from . import ep, epdtc, inference, kern, kgpr, kron, laplace, likelihoods, link_functions, linalg, models, pep, sparse, svgp, util, vargauss  # noqa: E402
 import types as _types  # noqa: E402
@@ -52,6 +53,7 @@ models.BayesianGPLVM = BayesianGPLVM
 models.BayesianGPLVMMiniBatch = BayesianGPLVMMiniBatch
 models.bayesian_gplvm_minibatch = _types.SimpleNamespace(BayesianGPLVMMiniBatch=BayesianGPLVMMiniBatch)
 models.ss_gplvm = _types.SimpleNamespace(SSGPLVM=SSGPLVM)         # (GPy.models.SSGPLVM itself keeps refusing: models.__getattr__)
+models.gplvm = _types.SimpleNamespace(GPLVM=GPLVM)                # (likewise: GPy.models.GPLVM keeps refusing, the module path has it)
 models.SparseGPClassification = SparseGPClassification
 models.GPRegressionGrid = GPRegressionGrid
 models.GPKroneckerGaussianRegression = GPKroneckerGaussianRegression

@@ -96,6 +96,8 @@ def build(force=False):
     srcs.append(os.path.join(_HERE, "..", "include", "mi355gp_kron.h"))
     srcs.append(os.path.join(_HERE, "..", "include", "mi355gp_eigh.h"))
     srcs.append(os.path.join(_HERE, "..", "include", "mi355gp_kgpr.h"))
+    srcs.append(os.path.join(_HERE, "..", "include", "mi355gp_latent.h"))
+    srcs.append(os.path.join(_HERE, "..", "include", "mi355gp_debug_latent.h"))
     product = os.path.join(_HERE, "libmi355gp.so")
     if not force and os.path.exists(product) and os.path.exists(DIAG_LIB_PATH):
         t = min(os.path.getmtime(product), os.path.getmtime(DIAG_LIB_PATH))
@@ -320,6 +322,15 @@ KGPR_ABI = {
     "mi355gp_kgpr_get_ms": [_vp, _dp],
     "mi355gp_kgpr_wsyrk": [_ci, _i64, _dp, _i64, _dp, _dp, _i64, _dp, _dp, _ci, _c_dp],
 }
+# include/mi355gp_latent.h: the exact-GP evaluation with the inputs as parameters (GPLVM), in its order, and
+# include/mi355gp_debug_latent.h: its gradient kernel alone (tests/test_latent_host.py holds both against the headers' prototypes)
+LATENT_ABI = {
+    "mi355gp_latent_set_X": [_vp, _dp],
+    "mi355gp_latent_inference_sum": [_vp, _ci, _parts, _dp, _i64, _cd, _cd, _dp, _c_dp, _c_dp, _dp, _c_dp],
+}
+DEBUG_LATENT_ABI = {
+    "mi355gp_dbg_latent_grad": [_ci, _ci, _ci, _dp, _dp, _i64, _ci, _dp, _dp, _ci, _dp, _dp],
+}
 KGPR_NUM_MS = 9                                          # MI355GP_KGPR_NUM_MS
 TILEOPS = {"trmm_lower": 0, "trmm_lower_T": 1, "trmm64": 2, "gram_splitk": 3, "update_nt": 4}    # MI355GP_TILEOP_*
 
@@ -336,7 +347,8 @@ def lib():
             build()
         L = ctypes.CDLL(LIB_PATH)
         for table in (ABI, DEBUG_LAUUM_ABI, DEBUG_TILEOPS_ABI, EPDTC_ABI, SPARSE_DIAG_ABI, SPARSE_COREG_ABI, DEBUG_SPARSE_COREG_ABI, PSI_LIN_ABI, DEBUG_PSI_LIN_ABI,
-                      PSI_SS_ABI, PSI_GH_ABI, VARGAUSS_ABI, KRON_ABI, MISSING_ABI, DEBUG_MISSING_ABI, EIGH_ABI, KGPR_ABI):
+                      PSI_SS_ABI, PSI_GH_ABI, VARGAUSS_ABI, KRON_ABI, MISSING_ABI, DEBUG_MISSING_ABI, EIGH_ABI, KGPR_ABI,
+                      LATENT_ABI, DEBUG_LATENT_ABI):
             for name, argtypes in table.items():
                 getattr(L, name).argtypes = argtypes
         L.mi355gp_last_error.restype = L.mi355gp_version.restype = _str
@@ -486,6 +498,23 @@ class Context(_Handle):
         arr, keep, ntheta = make_parts(specs)
         return self._exact("mi355gp_exact_inference_sum", (len(specs), arr), ntheta, noise, jitter, extra_jitter, want_alpha,
                            want_diag, want_stage_ms)
+
+    def latent_set_X(self, X):
+        """Re-upload the inputs alone (`mi355gp_latent_set_X`): R, Dy and every buffer stay."""
+        X = f64(X)
+        assert X.shape == (self.N, self.D)
+        check(lib().mi355gp_latent_set_X(self._h, X), "mi355gp_latent_set_X")
+
+    def latent_inference_sum(self, specs, noise, jitter=1e-8, extra_jitter=0.0, want_stage_ms=False):
+        """`exact_inference_sum` with the latent-input pass as its gradient phase: the result also holds dX (N x D) = dL/dX."""
+        arr, keep, ntheta = make_parts(specs)
+        noise = f64(np.atleast_1d(noise))
+        out, alpha, dtheta = np.zeros(NUM_OUT), np.empty((self.N, self.Dy)), np.zeros(ntheta)
+        dX = np.empty((self.N, self.D))
+        ms = np.zeros(NUM_T) if want_stage_ms else None
+        rc = check(lib().mi355gp_latent_inference_sum(self._h, len(specs), arr, noise, noise.size, jitter, extra_jitter, out,
+                                                      _opt(alpha), _opt(dtheta), dX, _opt(ms)), "mi355gp_latent_inference_sum")
+        return rc, _exact_result(out, ms, alpha=alpha, dtheta=dtheta, diag_dL_dK=None, dX=dX)
 
     def predict_sum(self, specs, Xnew, full_cov=False, want_var=True):
         arr, keep, _ = make_parts(specs)
@@ -1655,3 +1684,16 @@ def psi_lin_rows_probe(W, X, Z, variances, c0=0.0, Y=None, V=None, rowscale=None
                                            _opt(rowscale if Y is not None else None), float(beta), float(gscale), X, Z, var,
                                            float(c0), rows, M, D, Dy, out, int(time_reps), _opt(ms)), "mi355gp_dbg_psi_lin_rows")
     return (out, ms) if time_reps > 0 else out
+
+
+def dbg_latent_grad(kind, ARD, theta, X, W, alpha, device=0):
+    """The latent-input gradient kernel alone (`mi355gp_dbg_latent_grad`, include/mi355gp_debug_latent.h) with any symmetric W in the
+    place of Ky^-1: (dX (N x D), rec (68): the part's two reduction records)."""
+    require_device(device)
+    theta, X, W, alpha = f64(theta), f64(X), f64(W), f64(alpha)
+    N, D = X.shape
+    assert W.shape == (N, N) and alpha.ndim == 2 and alpha.shape[0] == N
+    dX, rec = np.empty((N, D)), np.empty(68)
+    check(lib().mi355gp_dbg_latent_grad(int(device), KIND_IDS[kind], ard_id(kind, ARD), theta, X, N, D, W, alpha, alpha.shape[1],
+                                        dX, rec), "mi355gp_dbg_latent_grad")
+    return dX, rec

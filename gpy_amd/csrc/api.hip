@@ -49,13 +49,16 @@ void free_data(mi355gp_ctx* c) {
     drop_graph(c);                                            // every node holds pointers into the buffers freed below
     c->parts.clear();
     double** ptrs[] = {&c->dX, &c->dR, &c->dNoise, &c->A, &c->B, &c->C, &c->Mbuf,
-                       &c->dTmp, &c->dTrmvPart, &c->dGradPart, &c->dGradOut, &c->dPack, &c->dCoregPart};
+                       &c->dTmp, &c->dTrmvPart, &c->dGradPart, &c->dGradOut, &c->dPack, &c->dCoregPart,
+                       &c->dLatPart, &c->dLatT, &c->dLatX};
     for (auto p : ptrs) {
         if (*p) (void)hipFree(*p);
         *p = nullptr;
     }
     if (c->hPack) (void)hipHostFree(c->hPack);
     c->hPack = nullptr;
+    if (c->hLatX) (void)hipHostFree(c->hLatX);
+    c->hLatX = nullptr;
     c->dAlpha = c->dScal = c->dDiag = c->dGradOutAll = nullptr;      // views into dPack
     c->hIdx.clear();
     c->hIdxCol = -1;

@@ -60,6 +60,9 @@ struct mi355gp_ctx {
     // mi355gp_vargauss_forward / _backward (vargauss.hip) leave it at 3 / 4 with the session's `vg` flag set.
     LaplaceSession* lap = nullptr;
     int lap_stage = 0;
+    // The latent-input gradient pass (latent.hip), allocated by the first mi355gp_latent_inference_sum of a data set: the strips'
+    // partials, the workgroups' theta sums, dL/dX on the device and its pinned host copy
+    double *dLatPart = nullptr, *dLatT = nullptr, *dLatX = nullptr, *hLatX = nullptr;
 };
 
 // api.hip
@@ -72,5 +75,7 @@ Resident<mi355gp_ctx::Part> ctx_training_points(const mi355gp_ctx* c);
 int ctx_coreg_check_points(const mi355gp_ctx* c, const double* Xn, int64_t M, const char* what);
 bool ctx_has_point_diag(const mi355gp_ctx* c);
 std::vector<double> ctx_kdiag_points(const mi355gp_ctx* c, const double* Xn, int64_t M);
+// latent.hip: what the latent entry takes (kinds, no product terms, D <= 32), judged on the host before any device work
+int latent_check_parts(int nparts, const mi355gp_part* parts, int D, const char* where);
 // laplace.hip: mi355gp_fetch of a context whose last evaluation was a Laplace session (tmp: n x n device, row-major)
 int laplace_fetch(mi355gp_ctx* c, int which, double* tmp);

@@ -5,6 +5,7 @@
 #include <cstring>
 #include <functional>
 
+#include "../../include/mi355gp_latent.h"
 #include "ctx.h"
 
 #define LOG_2_PI 1.8378770664093454836
@@ -15,6 +16,7 @@ struct Evaluation {
     double nu;                          // > 0: Student-t process with nu degrees of freedom
     double *out_scalars, *alpha_out, *dtheta_out, *diag_out, *stage_ms;
     std::function<int()> rebuild;       // re-enqueues the construction of Ky in c->A (only after a DIRTY abort of the persistent factorisation)
+    double* dX_out = nullptr;           // set: the gradient phase is the latent-input pass (latent.hip), dL/dX (n x D) comes back
     size_t nparts(const mi355gp_ctx* c) const { return with_kernel_grads ? c->parts.size() : 0; }
 };
 
@@ -106,8 +108,17 @@ static int enqueue_part_gradients(mi355gp_ctx* c, const Evaluation& ev) {
         HIP_CHECK(hipMemsetAsync(c->dGradOutAll, 0, sizeof(double) * nparts * groups * GP_STRIDE, st));
         HIP_CHECK(hipMemsetAsync(c->dPack + c->offExt, 0, sizeof(double) * nparts * groups * GP_STRIDE, st));
         const int nb = grad_num_blocks(n);
+        bool first_dX = true;
         for (size_t p = 0; p < nparts; ++p) {
             const mi355gp_ctx::Part& pt = c->parts[p];
+            if (ev.dX_out && !pt.is_static()) {                         // dL/dX and the part's records from one pass (latent.hip)
+                if (int rc = launch_latent_grad(st, pt.kp, pt.dXt, np, n, c->C, np, c->dAlpha, c->Dy, pt.dIl, c->dLatPart, c->dLatT,
+                                                c->dLatX, first_dX ? 0 : 1, c->dGradOutAll + (long)p * groups * GP_STRIDE,
+                                                c->dPack + c->offExt + (long)p * groups * GP_STRIDE))
+                    return rc;
+                first_dX = false;
+                continue;
+            }
             // factor of a product: dL_dK is weighted by the covariances of the term's other factors (prod.py:86-99),
             // rebuilt into Mbuf (lower tiles) by one K-build pass per other factor
             const bool prod = emit_other_factors(c->terms, pt.tix, p, c->Mbuf, [&](int g, double* dst, const double* mul, int, bool) {
@@ -140,9 +151,11 @@ static int fetch_results(mi355gp_ctx* c, const Evaluation& ev, int* info) {
     for (size_t p = 0; p < ev.nparts(c); ++p) coreg = coreg || c->parts[p].coreg();
     const size_t ncopy = coreg ? c->packDoubles : (ev.diag_out ? c->offCoreg : (ev.alpha_out ? c->offDiag : c->offAlpha));
     HIP_CHECK(hipMemcpyAsync(c->hPack, c->dPack, sizeof(double) * ncopy, hipMemcpyDeviceToHost, c->st));
+    if (ev.dX_out) HIP_CHECK(hipMemcpyAsync(c->hLatX, c->dLatX, sizeof(double) * c->n * c->D, hipMemcpyDeviceToHost, c->st));
     HIP_CHECK(hipStreamSynchronize(c->st));
     HIP_CHECK(hipGetLastError());
     *info = (int)c->hPack[6];
+    if (ev.dX_out) memcpy(ev.dX_out, c->hLatX, sizeof(double) * c->n * c->D);
     if (ev.alpha_out) memcpy(ev.alpha_out, c->hPack + c->offAlpha, sizeof(double) * c->n * c->Dy);
     if (ev.diag_out) memcpy(ev.diag_out, c->hPack + c->offDiag, sizeof(double) * c->n);
     return 0;
@@ -269,10 +282,17 @@ static int upload_noise(mi355gp_ctx* c, const double* noise, int64_t noise_len) 
 // The body of the Gaussian (nu = 0) and Student-t process (nu > 2) entry points: Ky = sum_t prod_f K_f + (noise + jitter) I
 // (add.py:58-72, prod.py:58-65), then the evaluation.
 static int exact_sum(mi355gp_ctx* c, int nparts, const mi355gp_part* parts, const double* noise, int64_t noise_len, double jitter,
-                     double nu, double* out_scalars, double* alpha_out, double* dtheta_out, double* diag_out, double* stage_ms) {
+                     double nu, double* out_scalars, double* alpha_out, double* dtheta_out, double* diag_out, double* stage_ms,
+                     double* dX_out = nullptr) {
     HIP_CHECK(hipSetDevice(c->device));
     EngineShared gate(c->device);
     if (int rc = ctx_prepare_parts(c, nparts, parts)) return rc;
+    if (dX_out && !c->dLatX) {                                   // the latent-input pass's buffers, once per data set
+        HIP_CHECK(hipMalloc(&c->dLatPart, sizeof(double) * latent_part_doubles(c->n, c->D)));
+        HIP_CHECK(hipMalloc(&c->dLatT, sizeof(double) * latent_tpart_doubles(c->n)));
+        HIP_CHECK(hipHostMalloc(&c->hLatX, sizeof(double) * c->n * c->D, hipHostMallocDefault));
+        HIP_CHECK(hipMalloc(&c->dLatX, sizeof(double) * c->n * c->D));
+    }
     if (int rc = upload_noise(c, noise, noise_len)) return rc;
     hipStream_t st = c->st;
     c->have_kernel = true;
@@ -286,7 +306,7 @@ static int exact_sum(mi355gp_ctx* c, int nparts, const mi355gp_part* parts, cons
         return 0;
     };
     build();
-    return evaluate(c, &gate, Evaluation{true, nu, out_scalars, alpha_out, dtheta_out, diag_out, stage_ms, build});
+    return evaluate(c, &gate, Evaluation{true, nu, out_scalars, alpha_out, dtheta_out, diag_out, stage_ms, build, dX_out});
 }
 
 extern "C" {
@@ -298,6 +318,24 @@ int mi355gp_exact_inference_sum(mi355gp_ctx* c, int nparts, const mi355gp_part* 
     ARG_CHECK(out_scalars != nullptr, "out_scalars is NULL");
     return exact_sum(c, nparts, parts, noise, noise_len, jitter + extra_jitter, 0.0, out_scalars, alpha_out, dtheta_out,
                      diag_dLdK_out, stage_ms);
+}
+
+// The evaluation of a model whose inputs are parameters (GPLVM): the gradient phase is the latent-input pass of latent.hip
+int mi355gp_latent_inference_sum(mi355gp_ctx* c, int nparts, const mi355gp_part* parts, const double* noise, int64_t noise_len,
+                                 double jitter, double extra_jitter, double* out_scalars, double* alpha_out, double* dtheta_out,
+                                 double* dX_out, double* stage_ms) {
+    ARG_CHECK(c && c->n > 0, "mi355gp_latent_inference_sum: set_data first");
+    ARG_CHECK(out_scalars != nullptr && dX_out != nullptr, "mi355gp_latent_inference_sum: out_scalars or dX_out is NULL");
+    if (int rc = latent_check_parts(nparts, parts, c->D, "mi355gp_latent_inference_sum")) return rc;
+    if (c->lap_stage != 0) {
+        mi355gp_set_error("mi355gp_latent_inference_sum: a Laplace session is open on this context; it has no latent-input gradient pass");
+        return -1;
+    }
+    bool any = false;
+    for (int p = 0; p < nparts; ++p) any = any || !kind_in(parts[p].kind, KS_STATIC);
+    ARG_CHECK(any, "mi355gp_latent_inference_sum: no part depends on the inputs");
+    return exact_sum(c, nparts, parts, noise, noise_len, jitter + extra_jitter, 0.0, out_scalars, alpha_out, dtheta_out, nullptr,
+                     stage_ms, dX_out);
 }
 
 // Student-t PROCESS inference (ExactStudentTInference.inference, exact_studentt_inference.py:20-52): the same pdinv +

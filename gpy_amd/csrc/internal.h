@@ -292,6 +292,15 @@ void launch_grad_generic(hipStream_t st, KernParams kp, const double* Xt1, long 
                          RankTerm rk = RankTerm{nullptr, nullptr, 0, 0.0, 1.0, nullptr});
 int grad_generic_num_blocks(long n, long m);
 
+// ---- latent.hip : dL/dX and the theta record of one stationary part from ONE pass over W = Ky^-1 and alpha -------------
+// part: latent_part_doubles(n, D), tpart: latent_tpart_doubles(n) doubles of scratch; il: the part's input scaling (D, device);
+// dX (n x D) (+)= the part's dL/dX; rec / rec2: the records launch_grad_fused + launch_reduce_partials leave (one group: D <= 32)
+size_t latent_part_doubles(long n, int D);
+size_t latent_tpart_doubles(long n);
+int launch_latent_grad(hipStream_t st, KernParams kp, const double* Xt, long ldx, long n, const double* W, long ldw,
+                       const double* alpha, int Dy, const double* il, double* part, double* tpart, double* dX, int accumulate,
+                       double* rec, double* rec2);
+
 // ---- kern_families.hip : the kinds that are no function of plain r^2 (family launchers: kern_tile.h) --------------
 // StdPeriodic dK/dx (standard_periodic.py:574-580) as a row reduction over a group of 32 dimensions from q_off:
 //   out[i][q] = sum_j W(i, j) K(x1_i, x2_j) sin(2 Delta_ijq),  W(i, j) = W[i * ldw + j], or W[j * ldw + i] if wt

@@ -18,13 +18,7 @@
 //                (inputs staged UNSCALED: Delta is formed from the difference of the raw coordinates, so calendar-year
 //                inputs keep their precision; pi / T_q and 1 / l_q are applied per dimension in the pair loop)
 
-__device__ __forceinline__ void ratquad_all(double var, double a, double r2, double& k, double& dk_or, double& dk_a) {
-    const double h = 0.5 * r2;
-    const double lg = log1p(h);
-    k = var * exp(-a * lg);
-    dk_or = -a * k / (1.0 + h);
-    dk_a = -k * lg;
-}
+// (ratquad_all: kern_tile.h, shared with latent.hip)
 
 // Cosine (kind 12, stationary.py:664-680), Sinc (kind 13, :717-743) and ExpQuadCosine (kind 14, :682-713): functions of the
 // scaled distance r = sqrt(s) alone, in the kernels of RatQuad (inputs scaled by 1 / l).  Each helper returns K and (dK/dr) / r

@@ -73,6 +73,15 @@ __device__ __forceinline__ CovVal cov_all(int kind, double var, double r2, bool 
     return c;
 }
 
+// RatQuad (kind 6, stationary.py:747-802): K, (dK/dr) / r and dK/dpower at the scaled squared distance r2
+__device__ __forceinline__ void ratquad_all(double var, double a, double r2, double& k, double& dk_or, double& dk_a) {
+    const double h = 0.5 * r2;
+    const double lg = log1p(h);
+    k = var * exp(-a * lg);
+    dk_or = -a * k / (1.0 + h);
+    dk_a = -k * lg;
+}
+
 // Stage rows [i0, i0+64) of dims [q0, q0+qc) of a dimension-major input into LDS s[q][64].
 __device__ __forceinline__ void stage_x(const double* __restrict__ Xt, long ldx, long i0, int q0, int qc,
                                         double* s, int t) {

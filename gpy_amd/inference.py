@@ -53,12 +53,16 @@ class _DeviceState(object):
     def __getstate__(self):              # the HBM buffers and the ctypes handle never travel
         return {"_idX": None, "_idR": None, "call_token": self.call_token, "kern": None, "ctx": None}
 
-    def ensure_data(self, X, R):
+    def ensure_data(self, X, R, latent=False):
         """Upload X / R unless the device already holds exactly these data.  An array the caller froze (the model drivers
         keep private read-only copies of X and Y, like GPy's `ObsAr`, reference `core/gp.py:44-60`) is recognised by
         identity in O(1); anything writable is compared element by element with a private copy (O(N D), negligible next
         to the N^3 step) -- an in-place edit of a caller-owned buffer is never missed."""
         same_x = self._idX is not None and self._idX.matches(X)
+        if latent and not same_x and self._idX is not None and self._idX.value().shape == X.shape and self._idR.matches(R):
+            self.ctx.latent_set_X(X)             # the inputs are parameters: they alone travel, nothing is reallocated
+            self._idX = ArrayIdentity(X)
+            return
         if not same_x or self._idR is None or self._idR.value().shape != R.shape:
             self.ctx.set_data(X, R)
             self._idX, self._idR = ArrayIdentity(X), ArrayIdentity(R)
@@ -113,9 +117,13 @@ class _DeviceState(object):
 class ExactGaussianInference(LatentFunctionInference):
     _device_members = ("_state", "_last")        # (`_last` holds the device state of the last call)
 
-    def __init__(self, device=0, maxtries=5):
+    LATENT_KINDS = ("rbf", "matern52", "matern32", "exponential", "ratquad", "white", "bias")
+    LATENT_MAX_D = 32
+
+    def __init__(self, device=0, maxtries=5, latent=False):
         self.device = device
         self.maxtries = maxtries
+        self.latent = latent           # the inputs are parameters (GPLVM): the evaluation's gradient phase also gives dL/dX
         self._state = None
         self.last_stage_ms = None
         self.collect_stage_ms = False
@@ -138,6 +146,24 @@ class ExactGaussianInference(LatentFunctionInference):
         neg = 0.5 * np.log(2 * np.pi) - 0.5 * np.log(c_diag) + 0.5 * (g ** 2) / c_diag
         return -neg
 
+    def _refuse_latent(self, kern, X, likelihood, noise, mean_function, K):
+        """what `mi355gp_latent_inference_sum` does not take, refused by name before any device work"""
+        if K is not None or not getattr(kern, "fused_alone", False):
+            raise NotImplementedError("latent inputs need a kernel that is evaluated on the device with a part that depends on X")
+        if mean_function is not None:
+            raise NotImplementedError("latent inputs with a mean function: R = Y - m(X) would depend on X")
+        if not (isinstance(likelihood, Gaussian) and noise.size == 1):
+            raise NotImplementedError("latent inputs take the Gaussian likelihood with one noise variance")
+        specs = kern.part_specs()
+        if any(s[4] != 0 for s in specs):
+            raise NotImplementedError("latent inputs: product terms (Prod) have no latent-input gradient pass")
+        for s in specs:
+            if s[0] not in self.LATENT_KINDS:
+                raise NotImplementedError("latent inputs: a %s part has no latent-input gradient pass" % s[0])
+        if kern._slice_X(X).shape[1] > self.LATENT_MAX_D:
+            raise NotImplementedError("latent inputs: at most %d latent dimensions, got %d"
+                                      % (self.LATENT_MAX_D, kern._slice_X(X).shape[1]))
+
     def _run_with_ladder(self, attempt, diagA):
         """`attempt(extra_jitter)` -> (info, result) under jitchol's ladder"""
         (res,), _ = jitter_ladder(attempt, diagA, self.maxtries, check_diag=True)
@@ -154,13 +180,15 @@ class ExactGaussianInference(LatentFunctionInference):
         # (reference :42-50) R = Y - m; without a mean function R IS Y (same object every iteration: O(1) data check)
         R = _lib.f64(Y) if mean_function is None else _lib.f64(Y - mean_function.f(X))
         n = X.shape[0]
+        if self.latent:
+            self._refuse_latent(kern, X, likelihood, noise, mean_function, K)
         # a lone White / Bias / Coregionalize, a foreign kernel or a given K: K comes from the host (`inference_given_K`)
         fused = K is None and getattr(kern, "fused_alone", False)
         Xdev = kern._slice_X(X) if fused else _lib.f64(X)
         if self._state is None:
             self._state = _DeviceState(self.device)
         st = self._state
-        st.ensure_data(Xdev, R)
+        st.ensure_data(Xdev, R, latent=self.latent)
         st.call_token += 1
         want_ms = self.collect_stage_ms
         # Gaussian.exact_inference_gradients == sum(diag(dL_dK)) == trace(dL_dK), which the device already reduces:
@@ -173,6 +201,8 @@ class ExactGaussianInference(LatentFunctionInference):
             diagA = kern.jitter_diag(X) + noise + 1e-8
 
             def attempt(extra):
+                if self.latent:
+                    return st.ctx.latent_inference_sum(specs, noise, jitter=1e-8, extra_jitter=extra, want_stage_ms=want_ms)
                 return st.ctx.exact_inference_sum(specs, noise, jitter=1e-8, extra_jitter=extra, want_alpha=True,
                                                   want_diag=want_diag, want_stage_ms=want_ms)
             res = self._run_with_ladder(attempt, diagA)
@@ -207,7 +237,11 @@ class ExactGaussianInference(LatentFunctionInference):
             woodbury_chol=DeviceResult(st, _lib.FETCH_L, n, st.call_token, fortran_order=True),
             woodbury_vector=alpha, K=K_view,
             woodbury_inv=DeviceResult(st, _lib.FETCH_KINV, n, st.call_token), state=st)
-        return post, log_marginal, {"dL_dK": dL_dK, "dL_dthetaL": dL_dthetaL, "dL_dm": alpha}
+        grad_dict = {"dL_dK": dL_dK, "dL_dthetaL": dL_dthetaL, "dL_dm": alpha}
+        if self.latent:                            # dL/dX in the columns of X that the kernel sees
+            grad_dict["dL_dX"] = np.zeros(X.shape)
+            grad_dict["dL_dX"][:, kern.active_dims if Xdev.shape[1] != X.shape[1] else slice(None)] = res["dX"]
+        return post, log_marginal, grad_dict
 
 
 class ExactStudentTInference(LatentFunctionInference):
